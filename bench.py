@@ -17,12 +17,16 @@ Contract (driver):  python bench.py --gpus N --steps K --warmup W
   * weak scaling (default): 32 restarts per GPU (BASELINE.json configs[2] at N=1, configs[3] at N=8),
     dataset replicated, restarts block-partitioned, no data-path collective;
     strong scaling (--restarts-total R): one fixed job of R restarts split over the ranks.
-After the timed steps (never part of `value`):
+A plain run stops there: set-up, warm-up, the K timed steps, --dump-outputs DIR if given (the restarts' weights and scores
+after the last timed step, what fr_ca_state hands a caller, as DIR/<name>.npy), and the result line.
+With --full, after the timed steps (never part of `value`):
+  * the timed region repeated on fresh jobs (`value_runs`) and instrumented steps (per-kernel times);
   * a few lock-step steps (one launch per step, nothing else on the device): the ISOLATED launch the roofline
     object is computed from;
   * one whole job trained to convergence INCLUDING its single all-gather and the model selection (`e2e`:
     time-to-model, per-rank ticks / busy time / idle share -- the load imbalance restart sharding has;
     --steal-block B lets the ranks pull blocks of B restarts from a shared counter instead);
+  * the power / clock leg, the in-process fan-out and peer-copy legs, the hardties side line;
   * the CPU baseline (oracle/, rank 0, N=1 only).
 Rank 0 prints ONE JSON line.
 """
@@ -293,7 +297,7 @@ def load_tree_pmc(shape):
     """rocprofv3 --pmc figures of the tree-scoring kernel (profiles/hbm_traffic.json[shape]["trees"], captured by
     tools/pmc_trees.sh on `bench.py --measure trees`): static, tied to the SHA-1 of the kernel sources, `stale` when the
     sources built here differ."""
-    meta = {"source": "profiles/hbm_traffic.json[{}][trees] (rocprofv3 --pmc passes over `python bench.py --measure trees`, "
+    meta = {"source": "profiles/hbm_traffic.json[{}][trees] (rocprofv3 --pmc passes over `python bench.py --full --measure trees`, "
                       "tools/pmc_trees.sh); static, not measured in this run".format(shape),
             "current_sha1": source_sha1(TREE_PMC_SOURCES)}
     try:
@@ -335,11 +339,15 @@ def bench_trees(args, comm, fr, native, dataset, X, y, qid, n, d):
     stats = native.profile_stats()
     kname = "tree_rank_kernel" if "tree_rank_kernel" in stats else "tree_ensemble_kernel"
     k = stats[kname]
-    from oracle import pyoracle as o  # the checker, outside the timed region
+    if args.dump_outputs:  # (the pass is deterministic: this one returns what the last timed pass computed)
+        dump_outputs(args.dump_outputs, {"scores": native.predict_scores_dense(model, dataset, n)})
+    ok = None
+    if args.full:
+        from oracle import pyoracle as o  # the checker, outside the timed region
 
-    m = min(20000, n)
-    got = native.predict_scores_dense(model, dataset, n)[:m]
-    ok = bool(np.array_equal(o.Dataset(X[:m], y[:m], qid[:m]).score_ensemble(trees, [1.0] * len(trees)), got))
+        m = min(20000, n)
+        got = native.predict_scores_dense(model, dataset, n)[:m]
+        ok = bool(np.array_equal(o.Dataset(X[:m], y[:m], qid[:m]).score_ensemble(trees, [1.0] * len(trees)), got))
     b_rf = n * (4 * d + 8)  # read X once, write one f64 score per document
     sec = k["avg_ms"] * 1e-3
     tj, pmc_meta = load_tree_pmc(args.shape)
@@ -375,7 +383,7 @@ def load_pmc(shape, usable):
     They are NOT measured in this run: the object says where they come from, which sources they were captured on,
     and `stale` when those sources differ from the ones built here (or when the capture carries no hashes)."""
     tpath = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-    meta = {"source": "profiles/hbm_traffic.json (rocprofv3 --pmc passes over `python bench.py --steps 20 --warmup 3`, "
+    meta = {"source": "profiles/hbm_traffic.json (rocprofv3 --pmc passes over `python bench.py --full --steps 20 --warmup 3`, "
                       "tools/pmc_bench.sh); static, not measured in this run", "current_sha1": source_sha1()}
     if not usable:
         meta.update({"stale": None, "note": "PMC figures exist only for the headline workload (mslr data, ndcg@10): none applied"})
@@ -610,7 +618,31 @@ def parse_args():
                     help="auto: the ranks torch.distributed.run started when WORLD_SIZE is set, otherwise N host threads of this "
                          "process (one per device, no PyTorch); torch: re-execute under torch.distributed.run when no launcher "
                          "started this process; threads: always threads")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other leg (repeats, instrumented and isolated steps, power, e2e, "
+                         "in-process fan-out, peer copy, side line, CPU baseline, oracle checks) and report roofline / limiter / pmc")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float64)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float64 (the inputs are seeded, so two builds compare output for output)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
+def restart_arrays(restarts, suffix=""):
+    """The restarts' state as fr_ca_state returns it, ordered by restart id: weights [R, D] and scores [R]."""
+    rs = sorted(restarts, key=lambda r: r["restart_id"])
+    return {"restart_weights" + suffix: np.array([r["weights"] for r in rs], dtype=np.float64).reshape(len(rs), -1),
+            "restart_scores" + suffix: np.array([r["score"] for r in rs], dtype=np.float64)}
 
 
 def main():
@@ -830,6 +862,70 @@ def rank_main(args, comm, fr, native, X, y, qid, gen_s, dev_ordinal, thread_devi
     if solo:
         native.profile_enable(False)
     s1 = snapshot()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, restart_arrays(run.state()["restarts"], "" if world == 1 else "_rank%d" % rank))
+
+    def headline_line(elapsed_max, useful_all, raw_all, best_so_far):
+        """The fields of the result line that the timed region alone gives (a plain run prints just these)."""
+        vp = float(s1["verify_pairs"] - s0["verify_pairs"])
+        vr = float(s1["verify_redone"] - s0["verify_redone"])
+        headline = (args.data == "mslr" and args.measure == "ndcg@10")
+        return {
+            "metric": "coordinate-ascent NDCG@10 evals/sec on MSLR-WEB30K shape" if (headline and args.shape == "30k")
+            else "coordinate-ascent {} evals/sec on MSLR-WEB{} shape, data={} (side measurement)".format(args.measure, args.shape.upper(), args.data),
+            "value": useful_all / elapsed_max,
+            "unit": "evals/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed_max * 1e3 / args.steps,
+            "higher_is_better": True,
+            "scaling": "strong" if strong else "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic" if args.data == "mslr" else "synthetic ({})".format(args.data),
+            "config": {
+                "workload": "synthetic MSLR-WEB{} shape: {} docs x {} features x {} queries, coordinate ascent "
+                            "{}, {} x 25 steps/coord (configs[{}])".format(
+                                args.shape.upper(), n, d, q, args.measure.upper() if args.measure.startswith("ndcg") else args.measure,
+                                "{} restarts in total".format(R) if strong else "{} restarts/GPU".format(args.restarts_per_gpu),
+                                1 if args.shape == "10k" else (3 if R == 256 and world == 8 else 2)),
+                "restarts_total": R,
+                "parallelism": "restart-sharded x{} (dataset replicated)".format(world),
+                "launcher": {"none": "single process", "threads": "one host thread per device in one process (no PyTorch)"}.get(
+                    comm.backend, "torch.distributed.run, backend {}".format(comm.backend)),
+                "collective_note": getattr(comm, "note", None),
+                "evals_per_step_per_gpu": (s1["raw_evals"] - s0["raw_evals"]) / max(1, args.steps),
+                "jobs_finished_inside_timed_region": jobs["finished"],
+            },
+            "raw_evals_per_s": raw_all / elapsed_max,
+            "useful_fraction": useful_all / max(1.0, raw_all),
+            "verify": {
+                "pairs": vp, "redone": vr, "redo_fraction": (vr / vp) if vp else None,
+                "ticks": s1["ticks"] - s0["ticks"],
+                "line_searches": s1["line_searches"] - s0["line_searches"],
+                # line searches evaluated by the exact kernels alone (after one with > 25 % redone pairs)
+                "exact_line_search_share": (s1["exact_ticks"] - s0["exact_ticks"]) / max(1, s1["line_searches"] - s0["line_searches"]),
+                # single restarts' line searches routed to the exact kernel (their last verified one left > 25 % undecided)
+                "exact_group_share": (s1["exact_groups"] - s0["exact_groups"]) / max(1, s1["groups"] - s0["groups"]),
+                # 16-candidate slices the exact kernel recomputed per listed (query, group) pair (4 = all of a 51-candidate group)
+                "redo_slices_per_pair": ((s1["verify_redo_entries"] - s0["verify_redo_entries"]) / vr) if vr else None,
+                # documents that made a wave of the verify kernel run its insertion chain, per (document, group) visit (device counter)
+                "chain_runs_per_visit": ((s1["chain_runs"] - s0["chain_runs"]) / (s1["chain_visits"] - s0["chain_visits"])) if s1["chain_visits"] > s0["chain_visits"] else None,
+            },
+            "setup": {"generate_s": gen_s, "upload_and_init_s": upload_s, "best_score_so_far": best_so_far,
+                      "preheat_ticks": PREHEAT_TICKS, "preheat_s": preheat_s},
+        }
+
+    if not args.full:
+        elapsed_max = comm.allreduce([elapsed], "max")[0]
+        useful_all, raw_all = comm.allreduce([float(s1["useful_evals"] - s0["useful_evals"]), float(s1["raw_evals"] - s0["raw_evals"])], "sum")
+        best_so_far = max(r["score"] for r in run.state()["restarts"]) if my_restarts else float("nan")
+        run.close()
+        if rank == 0:
+            print(json.dumps(headline_line(elapsed_max, useful_all, raw_all, best_so_far)))
+            sys.stdout.flush()
+        return
     # The driver fixes --steps, so the timed region above is ~50 ms of device time.  The same region -- warm-up, then exactly
     # K pipelined steps between barriers -- is repeated on fresh jobs (new master seeds): `value_runs` in the line shows
     # the spread `value` sits in.  Not part of `value`.
@@ -1145,67 +1241,28 @@ def rank_main(args, comm, fr, native, X, y, qid, gen_s, dev_ordinal, thread_devi
                 "frac": (adds_per_launch / iso_s / 1e12 / FP64_VALU_PEAK_TADDS) if iso_s > 0 else 0.0,
                 "measured_ceiling": 35.4,  # pure v_add_f64 stream on this chip, tools/ubench/dpadd.hip
             }
-        vp = float(s1["verify_pairs"] - s0["verify_pairs"])
-        vr = float(s1["verify_redone"] - s0["verify_redone"])
         runs_eps = [u / e for u, e in zip(vr_useful, vr_elapsed)]
         srt = sorted(runs_eps)
-        out = {
-            "metric": "coordinate-ascent NDCG@10 evals/sec on MSLR-WEB30K shape" if (headline and args.shape == "30k")
-            else "coordinate-ascent {} evals/sec on MSLR-WEB{} shape, data={} (side measurement)".format(args.measure, args.shape.upper(), args.data),
-            "value": useful_all / elapsed_max,
-            "unit": "evals/s",
+        out = headline_line(elapsed_max, useful_all, raw_all, best_so_far)
+        out["config"].update({
+            "launches_per_step": ls["launches"] / max(1, prof_steps),
+            "groups_per_launch": groups_per_launch,
+        })
+        out["verify"].update({
+            "exact_kernel_ms_per_step": exact["total_ms"] / max(1, prof_steps),
+            # restarts (all jobs of this process so far) whose R-rank tables were found worth keeping / not worth it by that counter
+            "rank_slots_on_off": [s1b["rank_slots_on"], s1b["rank_slots_off"]],
+        })
+        out.update({
             # the timed region again on fresh jobs (entry 0 IS `value`): K steps are ~50 ms, so one region alone is noise-prone
             "value_runs": runs_eps,
             "value_runs_job_seeds": [r["job_seed"] for r in value_runs],
             "value_runs_min_median_max": [srt[0], srt[len(srt) // 2] if len(srt) % 2 else 0.5 * (srt[len(srt) // 2 - 1] + srt[len(srt) // 2]), srt[-1]],
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed_max * 1e3 / args.steps,
-            "higher_is_better": True,
-            "scaling": "strong" if strong else "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic" if args.data == "mslr" else "synthetic ({})".format(args.data),
-            "config": {
-                "workload": "synthetic MSLR-WEB{} shape: {} docs x {} features x {} queries, coordinate ascent "
-                            "{}, {} x 25 steps/coord (configs[{}])".format(
-                                args.shape.upper(), n, d, q, args.measure.upper() if args.measure.startswith("ndcg") else args.measure,
-                                "{} restarts in total".format(R) if strong else "{} restarts/GPU".format(args.restarts_per_gpu),
-                                1 if args.shape == "10k" else (3 if R == 256 and world == 8 else 2)),
-                "restarts_total": R,
-                "parallelism": "restart-sharded x{} (dataset replicated)".format(world),
-                "launcher": {"none": "single process", "threads": "one host thread per device in one process (no PyTorch)"}.get(
-                    comm.backend, "torch.distributed.run, backend {}".format(comm.backend)),
-                "collective_note": getattr(comm, "note", None),
-                "evals_per_step_per_gpu": evals_per_step,
-                "launches_per_step": ls["launches"] / max(1, prof_steps),
-                "groups_per_launch": groups_per_launch,
-                "jobs_finished_inside_timed_region": jobs["finished"],
-            },
-            "raw_evals_per_s": raw_all / elapsed_max,
-            "useful_fraction": useful_all / max(1.0, raw_all),
             "e2e_evals_per_s": e2e_top,
             "roofline": roofline,
             "limiter": limiter,
             "pmc": pmc_meta,
             "power": power,
-            "verify": {
-                "pairs": vp, "redone": vr, "redo_fraction": (vr / vp) if vp else None,
-                "ticks": s1["ticks"] - s0["ticks"],
-                "line_searches": s1["line_searches"] - s0["line_searches"],
-                # line searches evaluated by the exact kernels alone (after one with > 25 % redone pairs)
-                "exact_line_search_share": (s1["exact_ticks"] - s0["exact_ticks"]) / max(1, s1["line_searches"] - s0["line_searches"]),
-                # single restarts' line searches routed to the exact kernel (their last verified one left > 25 % undecided)
-                "exact_group_share": (s1["exact_groups"] - s0["exact_groups"]) / max(1, s1["groups"] - s0["groups"]),
-                # 16-candidate slices the exact kernel recomputed per listed (query, group) pair (4 = all of a 51-candidate group)
-                "redo_slices_per_pair": ((s1["verify_redo_entries"] - s0["verify_redo_entries"]) / vr) if vr else None,
-                "exact_kernel_ms_per_step": exact["total_ms"] / max(1, prof_steps),
-                # documents that made a wave of the verify kernel run its insertion chain, per (document, group) visit (device counter)
-                "chain_runs_per_visit": ((s1["chain_runs"] - s0["chain_runs"]) / (s1["chain_visits"] - s0["chain_visits"])) if s1["chain_visits"] > s0["chain_visits"] else None,
-                # restarts (all jobs of this process so far) whose R-rank tables were found worth keeping / not worth it by that counter
-                "rank_slots_on_off": [s1b["rank_slots_on"], s1b["rank_slots_off"]],
-            },
             "per_launch_overlapped": {"avg_launch_ms": ls["avg_ms"], "launches": ls["launches"],
                                       "note": "HIP-event durations of pipelined launches (three sets in flight, so they overlap), from {} "
                                               "instrumented steps {}".format(prof_steps, "= the timed region" if profile_timed else "after the timed region")},
@@ -1215,9 +1272,7 @@ def rank_main(args, comm, fr, native, X, y, qid, gen_s, dev_ordinal, thread_devi
             "e2e": e2e,
             "inprocess": inproc,
             "peer_copy": peer,
-            "setup": {"generate_s": gen_s, "upload_and_init_s": upload_s, "best_score_so_far": best_so_far,
-                      "preheat_ticks": PREHEAT_TICKS, "preheat_s": preheat_s},
-        }
+        })
         if world == 1 and headline and not args.no_side:
             p.seed = 42
             # (the headline's dataset goes first -- free_dataset, as a caller done with it would: its tiles, order tables and

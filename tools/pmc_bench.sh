@@ -11,7 +11,7 @@ ROUND=${2:-r02}
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 mkdir -p "$OUT"
-CMD=(python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-e2e)
+CMD=(python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-e2e)
 rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INST_CYCLES_VALU SQ_WAVE_CYCLES --kernel-trace --output-format csv -d "$OUT/sq" -o p -- "${CMD[@]}" > "$OUT/sq.log" 2>&1
 rocprofv3 --pmc SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_CVT SQ_INSTS_SALU --kernel-trace --output-format csv -d "$OUT/mix" -o p -- "${CMD[@]}" > "$OUT/mix.log" 2>&1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/fetch" -o p -- "${CMD[@]}" > "$OUT/fetch.log" 2>&1
@@ -82,7 +82,7 @@ for name in ("timed", "isolated"):
         mix["f64_class_per_group"] = sum(mix.get(k) or 0.0 for k in ("valu_add_f64_per_group", "valu_mul_f64_per_group",
                                                                     "valu_fma_f64_per_group", "valu_trans_f64_per_group"))
         keys["bench_%s_valu_mix" % name] = mix
-keys["captured"] = {"round": rnd, "sha1": bench.source_sha1(), "command": "python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-e2e"}
+keys["captured"] = {"round": rnd, "sha1": bench.source_sha1(), "command": "python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-e2e"}
 summary = {"raw": res, "hbm_traffic_keys": keys}
 json.dump(summary, open(os.path.join(out, "summary.json"), "w"), indent=1)
 print(json.dumps(summary, indent=1))

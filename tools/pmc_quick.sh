@@ -6,7 +6,7 @@ OUT=${1:-gpurun_out/pmc_quick}; shift
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 mkdir -p "$OUT"
-CMD=(python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-e2e --no-side --repeats 0 --no-power)
+CMD=(python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-e2e --no-side --repeats 0 --no-power)
 i=0
 for C in "$@"; do
   rocprofv3 --pmc $C --kernel-trace --output-format csv -d "$OUT/p$i" -o p -- "${CMD[@]}" > "$OUT/p$i.log" 2>&1

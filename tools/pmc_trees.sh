@@ -1,5 +1,5 @@
 #!/bin/bash
-# PMC passes over `python bench.py --measure trees` (BASELINE.json configs[4]; rocprofv3 --pmc with --kernel-trace only, one
+# PMC passes over `python bench.py --full --measure trees` (BASELINE.json configs[4]; rocprofv3 --pmc with --kernel-trace only, one
 # counter set per pass): HBM bytes, VALU / LDS instructions, VALU-active and LDS-address-unit cycles of the tree-scoring
 # kernel per pass.  Writes $OUT/summary.json and merges it into profiles/hbm_traffic.json[30k]["trees"] together with the
 # SHA-1 of the sources it was captured on (bench.py marks the figures `stale` when they differ).
@@ -10,7 +10,7 @@ ROUND=${2:-r04}
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 mkdir -p "$OUT"
-CMD=(python bench.py --measure trees --steps 5 --warmup 1)
+CMD=(python bench.py --full --measure trees --steps 5 --warmup 1)
 rocprofv3 --pmc SQ_BUSY_CYCLES SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU --kernel-trace --output-format csv -d "$OUT/sq1" -o p -- "${CMD[@]}" > "$OUT/sq1.log" 2>&1
 rocprofv3 --pmc SQ_BUSY_CYCLES SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS --kernel-trace --output-format csv -d "$OUT/sq2" -o p -- "${CMD[@]}" > "$OUT/sq2.log" 2>&1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/fetch" -o p -- "${CMD[@]}" > "$OUT/fetch.log" 2>&1
@@ -60,7 +60,7 @@ keys = {
     "valu_active_frac_of_busy_cycles": avg("sq1", "SQ_ACTIVE_INST_VALU") * 4.0 / (1024.0 * busy1 / 32.0) if busy1 and avg("sq1", "SQ_ACTIVE_INST_VALU") else None,
     "lds_idx_active_frac_of_busy_cycles": avg("sq2", "SQ_LDS_IDX_ACTIVE") / (256.0 * busy2 / 32.0) if busy2 and avg("sq2", "SQ_LDS_IDX_ACTIVE") else None,
     "lds_bank_conflict_frac_of_lds_active": avg("sq2", "SQ_LDS_BANK_CONFLICT") / avg("sq2", "SQ_LDS_IDX_ACTIVE") if avg("sq2", "SQ_LDS_IDX_ACTIVE") else None,
-    "captured": {"round": rnd, "sha1": bench.source_sha1(bench.TREE_PMC_SOURCES), "command": "python bench.py --measure trees --steps 5 --warmup 1"},
+    "captured": {"round": rnd, "sha1": bench.source_sha1(bench.TREE_PMC_SOURCES), "command": "python bench.py --full --measure trees --steps 5 --warmup 1"},
 }
 json.dump(keys, open(os.path.join(out, "summary.json"), "w"), indent=1)
 path = os.path.join("profiles", "hbm_traffic.json")

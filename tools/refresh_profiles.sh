@@ -9,10 +9,10 @@ cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/profiles_new
 mkdir -p "$OUT"
 # 1. the bench line (HIP-event roofline inside)
-python bench.py --steps 20 --warmup 3 > "$OUT/${TAG}_bench.json" 2> "$OUT/bench.err"
+python bench.py --full --steps 20 --warmup 3 > "$OUT/${TAG}_bench.json" 2> "$OUT/bench.err"
 # 2. rocprofv3 kernel trace + stats of the same command
 # (without the pre-heating throwaway job and the hardties side line, so that the launches below sort into the legs by their order alone)
-FR_BENCH_NO_PREHEAT=1 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -o p -- python bench.py --steps 20 --warmup 3 --no-side > "$OUT/kt.log" 2>&1
+FR_BENCH_NO_PREHEAT=1 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -o p -- python bench.py --full --steps 20 --warmup 3 --no-side > "$OUT/kt.log" 2>&1
 cp "$OUT"/kt/*kernel_stats.csv "$OUT/${TAG}_kernel_stats.csv" 2>/dev/null || cp "$OUT"/kt/*/*kernel_stats.csv "$OUT/${TAG}_kernel_stats.csv"
 # the dominant kernel's launches by kind (the trainer keeps three launches in flight, bench.py appends isolated ones)
 python - "$OUT" > "$OUT/${TAG}_verify_launches.txt" <<'PY'
@@ -28,7 +28,7 @@ first_iso, last_iso = rows.index(iso[0]), rows.index(iso[-1])
 rest = rows[:first_iso]                 # warm-up, timed, then the instrumented pipelined steps (bench.py's legs in order)
 e2e = rows[last_iso + 1:]               # the train-to-convergence leg
 warm, timed, instr = rest[:9], rest[9:69], rest[69:]
-print("rocprofv3 --kernel-trace of `FR_BENCH_NO_PREHEAT=1 python bench.py --steps 20 --warmup 3 --no-side`: linesearch_verify_kernel launches by kind")
+print("rocprofv3 --kernel-trace of `FR_BENCH_NO_PREHEAT=1 python bench.py --full --steps 20 --warmup 3 --no-side`: linesearch_verify_kernel launches by kind")
 for name, sel in (("warm-up (3 ticks x 3 sets)", warm), ("timed (20 ticks x 3 sets, overlapping)", timed), ("repeats of the timed region, instrumented pipelined steps", instr),
                   ("isolated lock-step (32 groups)", iso), ("train-to-convergence leg (408 ticks x 3 sets, fewer groups as restarts converge)", e2e)):
     if sel:
@@ -51,20 +51,20 @@ rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt_full" -o p -- p
 cp "$OUT"/kt_full/*kernel_stats.csv "$OUT/${TAG}_fullrank_kernel_stats.csv" 2>/dev/null || cp "$OUT"/kt_full/*/*kernel_stats.csv "$OUT/${TAG}_fullrank_kernel_stats.csv"
 # side measurements on tie-heavy and on hard data: bench line + a whole run each
 for kind in ties tiesmix hard hardties; do
-  python bench.py --steps 20 --warmup 3 --data $kind --no-cpu-baseline 2> "$OUT/bench_$kind.err" | tail -1 > "$OUT/${TAG}_bench_$kind.json"
+  python bench.py --full --steps 20 --warmup 3 --data $kind --no-cpu-baseline 2> "$OUT/bench_$kind.err" | tail -1 > "$OUT/${TAG}_bench_$kind.json"
 done
 # the N>1 path on one GPU (gloo, both ranks on device 0): strong scaling of a 32-restart job, static and work stealing
 for steal in 0 4; do
   FR_BENCH_DEVICE=0 FR_BENCH_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 \
-    bench.py --gpus 2 --steps 10 --warmup 2 --shape 10k --restarts-total 32 --steal-block $steal 2> "$OUT/bench_2rank_$steal.err" | tail -1 > "$OUT/${TAG}_bench_2rank_1gpu_steal$steal.json"
+    bench.py --full --gpus 2 --steps 10 --warmup 2 --shape 10k --restarts-total 32 --steal-block $steal 2> "$OUT/bench_2rank_$steal.err" | tail -1 > "$OUT/${TAG}_bench_2rank_1gpu_steal$steal.json"
 done
 # random-forest training and sampled views
 python tools/rfbench.py --shape 30k --trees 100 --cpu-trees 1 --check 2>&1 | tail -1 > "$OUT/${TAG}_rfbench_30k.json"
 python tools/rfbench.py --shape 10k --trees 30 --split-candidates 32 --cpu-trees 1 --check 2>&1 | tail -1 > "$OUT/${TAG}_rfbench_10k_k32.json"
 python tools/viewbench.py 2>&1 | tail -1 > "$OUT/${TAG}_views_30k.json"
 # round 3: config 5 as a bench line, the in-process fan-out (two contexts on the one GPU of this box), NDCG with a depth beyond 20
-python bench.py --measure trees --steps 20 --warmup 3 2> "$OUT/bench_trees.err" | tail -1 > "$OUT/${TAG}_bench_trees.json"
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --inprocess-devices 0,0 2> "$OUT/bench_inproc.err" | tail -1 > "$OUT/${TAG}_bench_inprocess_2ctx_1gpu.json"
+python bench.py --full --measure trees --steps 20 --warmup 3 2> "$OUT/bench_trees.err" | tail -1 > "$OUT/${TAG}_bench_trees.json"
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --inprocess-devices 0,0 2> "$OUT/bench_inproc.err" | tail -1 > "$OUT/${TAG}_bench_inprocess_2ctx_1gpu.json"
 { for m in ndcg@50 ndcg@100; do python tools/train_e2e.py --measure $m --shape 30k --restarts 32 --max-ticks 136 2>&1 | tail -1; done; } > "$OUT/${TAG}_train_ndcg_cut_30k.json"
 FR_UPLOAD_TIMING=1 python tools/train_e2e.py --shape 30k --restarts 32 --max-ticks 3 2>&1 | grep "upload" > "$OUT/${TAG}_upload_stages.txt"
 python tools/train_e2e.py 2>&1 | tail -1 > "$OUT/${TAG}_train_e2e_10k.json"

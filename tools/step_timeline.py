@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """What fills a pipelined step?  From a `rocprofv3 --kernel-trace --output-format csv` trace of
-`python bench.py --steps N --no-e2e --repeats 0`: over the middle of the timed region (pipelined verify launches: the ones with
+`python bench.py --full --steps N --no-e2e --repeats 0`: over the middle of the timed region (pipelined verify launches: the ones with
 the smaller grids), the share of the time any kernel / a verify kernel is running, each kernel's summed duration, and the
 step time the window implies.  usage: python tools/step_timeline.py <..._kernel_trace.csv>"""
 import collections
