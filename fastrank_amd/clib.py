@@ -79,6 +79,7 @@ def _load():
         "fr_ca_free": (None, [vp]),
         "fr_last_train_stats": (vp, []),
         "fr_predict_scores_dense": (vp, [vp, vp, vp, sz]),
+        "fr_debug_lambda_gradients": (vp, [vp, vp, vp, C.c_char_p, C.c_double, vp, vp, sz]),
         "fr_evaluate_dense": (vp, [vp, vp, vp, C.c_char_p, vp, sz, C.POINTER(vp)]),
         "fr_rank_order": (vp, [vp, vp, vp, sz, vp, sz]),
         "fr_dataset_num_queries": (sz, [vp]),

@@ -11,6 +11,7 @@
 #include "../../include/fastrank.h"
 #include "host.hpp"
 #include "loader.hpp"
+#include "lambdamart.hpp"
 #include "rf_train.hpp"
 
 using fr::FrError;
@@ -187,11 +188,14 @@ Value stats_to_json(const fr::TrainStats& s) {
     return o;
 }
 
+enum class Learner { CoordinateAscent, RandomForest, LambdaMART };
+
 struct ParsedRequest {
     std::string measure;
-    bool is_ca = false;
+    Learner learner = Learner::CoordinateAscent;
     fr::CAParams ca;
     fr::RFParams rf;
+    fr::LambdaMARTParams lm;
     bool has_qrel = false;
     fr::QRel qrel;
 };
@@ -206,14 +210,18 @@ ParsedRequest parse_train_request(const std::string& text) {
     rq.measure = m.s;
     const auto& var = fr::json_variant(fr::json_field(v, "params"), "FastRankModelParams");
     if (var.first == "CoordinateAscent") {
-        rq.is_ca = true;
+        rq.learner = Learner::CoordinateAscent;
         rq.ca = fr::CAParams::from_json(var.second);
     } else if (var.first == "RandomForest") {
-        rq.is_ca = false;
+        rq.learner = Learner::RandomForest;
         rq.rf = fr::RFParams::from_json(var.second);
+    } else if (var.first == "LambdaMART") {
+        rq.learner = Learner::LambdaMART;
+        rq.lm = fr::LambdaMARTParams::from_json(var.second);
+        fr::lambdamart_check_measure(rq.measure);
     } else {
         fr::fail_raw("Error(\"unknown variant `" + var.first +
-                     "`, expected `CoordinateAscent` or `RandomForest`\", line: 1, column: 1)");
+                     "`, expected one of `CoordinateAscent`, `RandomForest`, `LambdaMART`\", line: 1, column: 1)");
     }
     const Value* j = v.find("judgments");
     if (j && !j->is_null()) {
@@ -276,10 +284,12 @@ std::string rust_display_f64(double v) {
 }
 
 std::vector<fr::TrainStats> g_last_per_device;  // one entry per device of the last multi-device train_model call
+Value g_last_lambdamart;                         // the last LambdaMART training's own numbers (null after any other training)
 static void set_last_stats(const fr::TrainStats& st, std::vector<fr::TrainStats> per_device = {}) {
     std::lock_guard<std::mutex> lk(g_stats_mu);
     g_last_stats = st;
     g_last_per_device = std::move(per_device);
+    g_last_lambdamart = Value::null();
 }
 
 // Per-trainer bound on the restarts kept live at once (FR_RESTART_SLOTS, default 64): a request with more restarts than
@@ -591,6 +601,24 @@ fr::Model train_rf(const std::shared_ptr<fr::DatasetView>& view, const ParsedReq
     return m;
 }
 
+// LambdaMART trains on the view's primary device only: its trees depend on each other, and a request that names several
+// devices gets the single-device model
+fr::Model train_lambdamart(const std::shared_ptr<fr::DatasetView>& view, const ParsedRequest& rq) {
+    auto t0 = std::chrono::steady_clock::now();
+    fr::Evaluator ev = fr::make_evaluator(*view, rq.measure, rq.has_qrel ? &rq.qrel : nullptr);
+    fr::LambdaMARTTrainer trainer(view, std::move(ev), rq.lm);
+    fr::Model m = trainer.learn();
+    fr::TrainStats st;
+    st.devices = 1;
+    st.path = "lambdamart";
+    st.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    st.restarts = trainer.stats().trees;
+    set_last_stats(st);
+    std::lock_guard<std::mutex> lk(g_stats_mu);
+    g_last_lambdamart = trainer.stats().to_json();
+    return m;
+}
+
 Value restarts_to_json(const std::vector<fr::RestartResult>& hist) {
     Value arr = Value::array();
     for (const auto& h : hist) {
@@ -780,12 +808,14 @@ const void* query_json(const void* json_cmd_str) {
     return json_call([&]() {
         std::string cmd = accept_str("query_json_str", json_cmd_str);
         // src/ffi.rs:215-236
-        if (cmd == "coordinate_ascent_defaults" || cmd == "random_forest_defaults") {
+        if (cmd == "coordinate_ascent_defaults" || cmd == "random_forest_defaults" || cmd == "lambdamart_defaults") {
             Value o = Value::object();
             o.set("measure", Value::string("ndcg"));
             Value params = Value::object();
             if (cmd == "coordinate_ascent_defaults")
                 params.set("CoordinateAscent", fr::CAParams::defaults().to_json());
+            else if (cmd == "lambdamart_defaults")
+                params.set("LambdaMART", fr::LambdaMARTParams().to_json());
             else
                 params.set("RandomForest", random_forest_defaults_json());
             o.set("params", std::move(params));
@@ -820,7 +850,11 @@ const CResult* train_model(void* train_request_json, void* dataset) {
         std::lock_guard<std::mutex> lk(api_mu_of(ds));
         auto* out = new CModel();
         try {
-            out->actual = rq.is_ca ? train_ca_devices(ds.view, rq) : train_rf(ds.view, rq);
+            switch (rq.learner) {
+                case Learner::CoordinateAscent: out->actual = train_ca_devices(ds.view, rq); break;
+                case Learner::RandomForest: out->actual = train_rf(ds.view, rq); break;
+                case Learner::LambdaMART: out->actual = train_lambdamart(ds.view, rq); break;
+            }
         } catch (...) {
             delete out;
             throw;
@@ -1161,7 +1195,7 @@ const void* fr_train_model_shard(const void* train_request_json, const CDataset*
     return json_call([&]() {
         const CDataset& ds = require_dataset(dataset);
         ParsedRequest rq = parse_train_request(accept_str("train_request_json", train_request_json));
-        if (!rq.is_ca) fr::fail_str("fr_train_model_shard: only CoordinateAscent shards by restart");
+        if (rq.learner != Learner::CoordinateAscent) fr::fail_str("fr_train_model_shard: only CoordinateAscent shards by restart");
         std::lock_guard<std::mutex> lk(api_mu_of(ds));
         std::vector<fr::RestartResult> hist;
         train_ca(ds.view, rq, restart_begin, restart_end, &hist);
@@ -1188,7 +1222,7 @@ void* fr_ca_begin(const void* train_request_json, const CDataset* dataset, uint3
     const void* st = status_call([&]() {
         const CDataset& ds = require_dataset(dataset);
         ParsedRequest rq = parse_train_request(accept_str("train_request_json", train_request_json));
-        if (!rq.is_ca) fr::fail_str("fr_ca_begin: only CoordinateAscent");
+        if (rq.learner != Learner::CoordinateAscent) fr::fail_str("fr_ca_begin: only CoordinateAscent");
         std::lock_guard<std::mutex> lk(api_mu_of(ds));
         fr::Evaluator ev = fr::make_evaluator(*ds.view, rq.measure, rq.has_qrel ? &rq.qrel : nullptr);
         if (ds.view->host_csr().nq == 0) fr::fail_str("assertion failed: !data.queries().is_empty()");
@@ -1212,7 +1246,7 @@ void* fr_ca_begin_query_shard(const void* train_request_json, const CDataset* da
     const void* st = status_call([&]() {
         const CDataset& ds = require_dataset(dataset);
         ParsedRequest rq = parse_train_request(accept_str("train_request_json", train_request_json));
-        if (!rq.is_ca) fr::fail_str("fr_ca_begin_query_shard: only CoordinateAscent");
+        if (rq.learner != Learner::CoordinateAscent) fr::fail_str("fr_ca_begin_query_shard: only CoordinateAscent");
         if (!allreduce) fr::fail_str("fr_ca_begin_query_shard: allreduce callback is null!");
         std::lock_guard<std::mutex> lk(api_mu_of(ds));
         fr::Evaluator ev = fr::make_evaluator(*ds.view, rq.measure, rq.has_qrel ? &rq.qrel : nullptr);
@@ -1289,6 +1323,7 @@ const void* fr_last_train_stats(void) {
             for (const fr::TrainStats& st : g_last_per_device) a.push(stats_to_json(st));
             o.set("per_device", std::move(a));
         }
+        if (!g_last_lambdamart.is_null()) o.set("lambdamart", g_last_lambdamart);
         return frjson::dump(o);
     });
 }
@@ -1304,6 +1339,26 @@ const void* fr_predict_scores_dense(const CModel* model, const CDataset* dataset
         fr::score_model(view, m.actual);
         std::string err;
         if (!dev.download_scores(0, out, out_len, &err)) fr::fail_str(err);
+    });
+}
+
+const void* fr_debug_lambda_gradients(const CModel* model, const CDataset* dataset, const CQRel* qrel, const void* measure,
+                                      double sigma, double* lambda_out, double* weight_out, size_t out_len) {
+    return status_call([&]() {
+        const CModel& m = require_model(model);
+        const CDataset& ds = require_dataset(dataset);
+        std::string name = accept_str("measure", measure);
+        fr::lambdamart_check_measure(name);
+        if (out_len && (!lambda_out || !weight_out)) fr::fail_str("NULL pointer: gradient outputs");
+        std::lock_guard<std::mutex> lk(api_mu_of(ds));
+        fr::DatasetView& view = *ds.view;
+        if (view.instances.empty()) return;
+        fr::Evaluator ev = fr::make_evaluator(view, name, qrel ? &qrel->actual : nullptr);
+        frdev::DeviceDataset& dev = view.device();
+        fr::score_model(view, m.actual);
+        std::string err;
+        if (!dev.lambda_gradients(ev.norms.data(), ev.depth, sigma, &err)) fr::fail_str(err);
+        if (!dev.lambda_download(lambda_out, weight_out, out_len, &err)) fr::fail_str(err);
     });
 }
 

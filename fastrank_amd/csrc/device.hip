@@ -24,6 +24,7 @@
 //                             and verifying the gaps (the exact kernels of kernels_fullrank.inc redo what fails)
 //   kernels_rf.inc          random-forest TRAINING: level-synchronous split search over a batch of trees (rocPRIM radix sort +
 //                           sequential-association importance kernels)
+//   kernels_lambda.inc      lambda_grad_kernel: LambdaMART's LambdaRank gradients, one workgroup per query
 //   device_dataset.inc      DeviceDataset: HBM layout (runs, tiles, tables) and every launcher
 #include "device.hpp"
 
@@ -65,6 +66,7 @@ namespace frdev {
 #include "kernels_fullrank.inc"
 #include "kernels_rr.inc"
 #include "kernels_rf.inc"
+#include "kernels_lambda.inc"
 #include "device_dataset.inc"
 #include "rccl_exchange.inc"
 

@@ -283,8 +283,11 @@ class DeviceDataset {
     // File-loaded datasets: bit f of bits_by_instance[id * words + f / 32] = instance id HOLDS feature f (the reference's
     // FeatureStats skips absent values, src/normalizers.rs:24-29, while the sort reads them as 0.0).  nullptr: all held.
     bool rf_set_presence(const uint32_t* bits_by_instance, size_t words, size_t n_instances, std::string* err);
+    // lambda_targets: the instances' split targets are the f32 LambdaMART gradients of the last lambda_gradients() call
+    // instead of their gains (the tree then fits the gradients: labels_int does not apply)
     bool rf_begin(const std::vector<uint32_t>& root_off, const std::vector<uint32_t>& root_ids, uint32_t nf,
-                  const std::vector<uint32_t>& feats, std::string* err, const uint32_t* positions = nullptr);
+                  const std::vector<uint32_t>& feats, std::string* err, const uint32_t* positions = nullptr,
+                  bool lambda_targets = false);
     // host only, callable from another thread while the device works: positions[g] = where instance root_ids[g] sits in the
     // tiled layout (what rf_begin otherwise works out itself); hand the result to rf_begin
     bool rf_positions(const std::vector<uint32_t>& root_ids, uint32_t* positions /*[root_ids.size()]*/, std::string* err);
@@ -302,6 +305,15 @@ class DeviceDataset {
     // device bytes per (sampled instance x sampled feature) of a batch: two key and two payload arrays (8 + 8 + 4 + 4), the sorted
     // gains and values of this level and the one before (4 x 4), the side byte of the stable partition
     size_t rf_bytes_per_item() const { return 41; }
+
+    // --- LambdaMART gradients (kernels_lambda.inc) ------------------------------------------------
+    // One gradient pass on score slot 0: per document the LambdaRank gradient lambda and weight w (f64) and float(lambda),
+    // the split target rf_begin(.., lambda_targets = true) reads.  norms[nq]: the NDCG evaluator's; depth < 0 = None.
+    bool lambda_gradients(const double* norms, int64_t depth, double sigma, std::string* err);
+    // the last pass's lambda / w by padded position ([np] each)
+    bool lambda_download_positions(std::vector<double>* lambda, std::vector<double>* weight, std::string* err);
+    // ... scattered to original instance ids (ids outside this dataset or >= out_len are left untouched)
+    bool lambda_download(double* lambda_by_instance, double* weight_by_instance, size_t out_len, std::string* err);
 
     int take_flags();  // returns and clears the accumulated kernel error bits
 

@@ -257,8 +257,19 @@ struct DeviceDataset::Impl {
         DevBuf<unsigned char> side, side_r;
         std::vector<uint32_t> prev_act_n;  // host copy of the previous level's node sizes
         uint32_t splits_for_A = 0;         // rf.splits holds the decisions of a level of this many nodes (0: none)
+        const float* targets = nullptr;    // what the batch's trees fit, by padded position: the gains, or LambdaMART's lm.target
     } rf;
     void rf_args(RFArgs& a);
+    // LambdaMART gradient pass (kernels_lambda.inc)
+    struct LmState {
+        bool built = false;
+        DevBuf<uint32_t> off, pos, qorder;  // [nq+1] / [n] positions of every query's documents in stored order / queries longest first
+        DevBuf<double> lam, wt;             // [np] by padded position
+        DevBuf<float> target;               // [np] float(lam): the trees' split targets
+        DevBuf<unsigned char> slab;         // staging for queries too long for LDS
+        uint32_t n_lds = 0, max_len = 0;    // queries (qorder[n_lds..] are staged in the slab) / the longest one
+    } lm;
+    bool lm_build(std::string* err);
     DevBuf<uint64_t> forest;
     DevBuf<uint32_t> tree_fdesc;  // tree_ensemble_rank_kernel: per-feature descriptors, Eytzinger threshold tables
     DevBuf<float> tree_tables;
@@ -3533,7 +3544,7 @@ bool DeviceDataset::linesearch_fullrank(int measure, int64_t depth, const double
 // ----------------------------------------------------------------------------------------------
 void DeviceDataset::Impl::rf_args(RFArgs& a) {
     a.xb = xb.p;
-    a.gain = gain.p;
+    a.gain = rf.targets != nullptr ? rf.targets : gain.p;
     a.dq = (uint32_t)dq;
     a.roff = rf.roff.p;
     a.pos = rf.pos.p;
@@ -3561,7 +3572,7 @@ void DeviceDataset::Impl::rf_args(RFArgs& a) {
     a.pw = rf.pw;
     const char* int_env = frdev::path_env("FR_RF_INT_SUMS");
     const bool int_off = int_env != nullptr && int_env[0] == '0';
-    a.labels_int = (labels_small_int && !int_off) ? 1u : 0u;
+    a.labels_int = (labels_small_int && !int_off && a.gain == gain.p) ? 1u : 0u;
 }
 
 // which features every instance holds, by instance id ([n_instances][words]; nullptr / 0 words: all of them): random-forest
@@ -3610,7 +3621,7 @@ bool DeviceDataset::rf_positions(const std::vector<uint32_t>& root_ids, uint32_t
 }
 
 bool DeviceDataset::rf_begin(const std::vector<uint32_t>& root_off, const std::vector<uint32_t>& root_ids, uint32_t nf,
-                             const std::vector<uint32_t>& feats, std::string* err, const uint32_t* positions) {
+                             const std::vector<uint32_t>& feats, std::string* err, const uint32_t* positions, bool lambda_targets) {
     std::vector<uint32_t> pos_own;
     if (positions == nullptr) {
         pos_own.resize(root_ids.size());
@@ -3647,7 +3658,12 @@ bool DeviceDataset::rf_begin(const std::vector<uint32_t>& root_off, const std::v
     FR_HIP(hipMemcpyAsync(rf.pos.p, positions, total * 4, hipMemcpyHostToDevice, m.stream));
     FR_HIP(hipMemcpyAsync(rf.feats.p, feats.data(), T * nf * 4, hipMemcpyHostToDevice, m.stream));
     // (the instances' first node keys -- their tree's root, key t -- are written on the device: no second 4-byte-per-instance upload)
-    if (total != 0) rf_gainr_kernel<<<grid1d(total, 256), 256, 0, m.stream>>>(m.gain.p, rf.pos.p, rf.roff.p, (uint32_t)T, rf.gain_r.p, rf.node_of.p, (uint32_t)total);
+    if (lambda_targets && !m.lm.built) {
+        if (err) *err = "rf_begin: no LambdaMART gradients computed";
+        return false;
+    }
+    rf.targets = lambda_targets ? m.lm.target.p : m.gain.p;
+    if (total != 0) rf_gainr_kernel<<<grid1d(total, 256), 256, 0, m.stream>>>(rf.targets, rf.pos.p, rf.roff.p, (uint32_t)T, rf.gain_r.p, rf.node_of.p, (uint32_t)total);
     FR_HIP(hipGetLastError());
     FR_HIP(hipStreamSynchronize(m.stream));
     rf.A = 0;
@@ -3856,4 +3872,101 @@ void DeviceDataset::rf_end() {
     auto& rf = m.rf;
     rf.keys_a.release(), rf.keys_b.release(), rf.vals_a.release(), rf.vals_b.release(), rf.sg.release(), rf.sv.release(), rf.sg_o.release(), rf.sv_o.release(), rf.temp.release(), rf.side.release(), rf.tile_cnt.release();
     rf.cands.release();
+}
+
+// ----------------------------------------------------------------------------------------------
+// LambdaMART gradient pass (kernels_lambda.inc)
+// ----------------------------------------------------------------------------------------------
+// per query the positions of its documents in stored order (instance ids ascending), and the launch order (longest first)
+bool DeviceDataset::Impl::lm_build(std::string* err) {
+    if (lm.built) return true;
+    std::vector<uint32_t> off(nq + 1, 0), pos, order(nq);
+    pos.reserve(n);
+    uint32_t maxl = 0;
+    for (size_t q = 0; q < nq; q++) {
+        const size_t b = pos.size();
+        for (uint32_t k = 0; k < qlen_h[q]; k++) pos.push_back(qstart_h[q] + k);
+        std::sort(pos.begin() + b, pos.end(), [&](uint32_t x, uint32_t y) { return perm_host[x] < perm_host[y]; });
+        off[q + 1] = (uint32_t)pos.size();
+        maxl = std::max(maxl, qlen_h[q]);
+        order[q] = (uint32_t)q;
+    }
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return qlen_h[a] > qlen_h[b]; });
+    // queries beyond the LDS budget (4096 documents, 144 KiB) are staged in a per-block global slab; they come first in
+    // the longest-first order
+    uint32_t n_long = 0;
+    while (n_long < nq && (size_t)qlen_h[order[n_long]] * LM_STAGE_BYTES > LM_LDS_MAX) n_long++;
+    if (!upload(lm.off, off, err) || !upload(lm.pos, pos, err) || !upload(lm.qorder, order, err)) return false;
+    if (!lm.lam.ensure(np, err) || !lm.wt.ensure(np, err) || !lm.target.ensure(np, err)) return false;
+    FR_HIP(hipMemsetAsync(lm.lam.p, 0, np * sizeof(double), stream));
+    FR_HIP(hipMemsetAsync(lm.wt.p, 0, np * sizeof(double), stream));
+    FR_HIP(hipMemsetAsync(lm.target.p, 0, np * sizeof(float), stream));
+    lm.n_lds = (uint32_t)nq - n_long;
+    lm.max_len = maxl;
+    if (n_long && !lm.slab.ensure((size_t)LM_SLAB_BLOCKS * maxl * LM_STAGE_BYTES, err)) return false;
+    lm.built = true;
+    return true;
+}
+
+bool DeviceDataset::lambda_gradients(const double* norms, int64_t depth, double sigma, std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    if (m.scores_slots < 1 || m.scores.p == nullptr) {
+        if (err) *err = "lambda_gradients: no scores resident";
+        return false;
+    }
+    if (!m.lm_build(err)) return false;
+    if (!m.norms.ensure(m.nq, err) || !m.upload_norms(norms, err)) return false;
+    auto& lm = m.lm;
+    const uint32_t n_long = (uint32_t)m.nq - lm.n_lds;
+    ProfScope ps("lambda_grad_kernel", m.stream);
+    for (uint32_t q0 = 0; q0 < n_long; q0 += LM_SLAB_BLOCKS) {  // (longest first: these open the pass)
+        const uint32_t cnt = std::min<uint32_t>(LM_SLAB_BLOCKS, n_long - q0);
+        lambda_grad_kernel<<<cnt, 256, 0, m.stream>>>(m.scores.p, lm.off.p, lm.pos.p, lm.qorder.p, q0, m.gain.p, m.gexp.p, m.disc.p,
+                                                     m.perm.p, m.norms.p, depth, sigma, lm.lam.p, lm.wt.p, lm.target.p, lm.slab.p,
+                                                     lm.max_len);
+    }
+    if (lm.n_lds != 0) {
+        const size_t longest = n_long < m.nq ? std::min<size_t>(lm.max_len, LM_LDS_MAX / LM_STAGE_BYTES) : 0;
+        const size_t bytes = std::max<size_t>(longest * LM_STAGE_BYTES, 64);
+        FR_HIP(hipFuncSetAttribute((const void*)lambda_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        lambda_grad_kernel<<<lm.n_lds, 256, bytes, m.stream>>>(m.scores.p, lm.off.p, lm.pos.p, lm.qorder.p, n_long, m.gain.p, m.gexp.p,
+                                                              m.disc.p, m.perm.p, m.norms.p, depth, sigma, lm.lam.p, lm.wt.p,
+                                                              lm.target.p, nullptr, 0u);
+    }
+    FR_HIP(hipGetLastError());
+    return true;
+}
+
+bool DeviceDataset::lambda_download_positions(std::vector<double>* lambda, std::vector<double>* weight, std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    if (!m.lm.built) {
+        if (err) *err = "lambda_download: no gradients computed";
+        return false;
+    }
+    lambda->resize(m.np);
+    weight->resize(m.np);
+    FR_HIP(hipMemcpyAsync(lambda->data(), m.lm.lam.p, m.np * sizeof(double), hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipMemcpyAsync(weight->data(), m.lm.wt.p, m.np * sizeof(double), hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipStreamSynchronize(m.stream));
+    return true;
+}
+
+bool DeviceDataset::lambda_download(double* lambda_by_instance, double* weight_by_instance, size_t out_len, std::string* err) {
+    std::vector<double> lam, wt;
+    if (!lambda_download_positions(&lam, &wt, err)) return false;
+    Impl& m = *impl_;
+    std::vector<char> in_query(m.np, 0);
+    for (size_t q = 0; q < m.nq; q++)
+        for (uint32_t k = 0; k < m.qlen_h[q]; k++) in_query[m.qstart_h[q] + k] = 1;
+    for (size_t p = 0; p < m.np; p++) {
+        const uint32_t id = m.perm_host[p];
+        if (!in_query[p] || id == IDX_INVALID || id >= out_len) continue;
+        lambda_by_instance[id] = lam[p];
+        weight_by_instance[id] = wt[p];
+    }
+    return true;
 }

@@ -1,0 +1,238 @@
+// LambdaMART on the MI355X path: gradient-boosted regression trees fitted to LambdaRank gradients.
+//
+// Scores start at 0.0.  Per tree:
+//   gradient  lambda_grad_kernel (kernels_lambda.inc) on the running scores in device score slot 0: lambda_p, w_p (f64)
+//   grow      the random-forest grower (rf_train.hpp, kernels_rf.inc), SquaredError over ALL of the view's instances and
+//             features, fitted to float(lambda_p)
+//   leaves    Newton step sum_L lambda / sum_L w over the instances the tree's SCORING rule (x <= split -> lhs) sends to
+//             the leaf, both sums sequential f64 in the instance list's order; 0.0 for an empty leaf or sum_L w == 0.
+//             The routing is the tree-scoring kernel run on a copy of the tree whose leaves hold their own index.
+//   update    s_p = s_p + learning_rate * tree(x_p) (unfused: ensemble_accumulate), the WeightedEnsemble recurrence, so
+//             the running scores are what predicting with the model so far gives, bit for bit.
+// The instance list is the RF trainer's: queries in the view's order, instance ids ascending inside a query.
+#pragma once
+#include <chrono>
+#include <cmath>
+
+#include "host.hpp"
+#include "rf_train.hpp"
+
+namespace fr {
+
+struct LambdaMARTParams {
+    uint32_t num_trees = 100;
+    double learning_rate = 0.1;
+    uint32_t max_depth = 6;
+    uint32_t min_leaf_support = 10;
+    uint32_t split_candidates = 64;
+    double sigma = 1.0;
+    bool quiet = false;
+
+    [[noreturn]] static void invalid(const std::string& what) {
+        fail_raw("Error(\"invalid value: " + what + "\", line: 0, column: 0)");
+    }
+    static LambdaMARTParams from_json(const Value& v) {
+        if (!v.is_object()) fail_raw("Error(\"invalid type: expected struct LambdaMARTParams\", line: 0, column: 0)");
+        LambdaMARTParams p;
+        p.num_trees = json_u32(json_field(v, "num_trees"), "num_trees");
+        p.learning_rate = json_f64(json_field(v, "learning_rate"), "learning_rate");
+        p.max_depth = json_u32(json_field(v, "max_depth"), "max_depth");
+        p.min_leaf_support = json_u32(json_field(v, "min_leaf_support"), "min_leaf_support");
+        p.split_candidates = json_u32(json_field(v, "split_candidates"), "split_candidates");
+        p.sigma = json_f64(json_field(v, "sigma"), "sigma");
+        p.quiet = json_bool(json_field(v, "quiet"), "quiet");
+        if (p.num_trees < 1) invalid("num_trees must be at least 1");
+        if (!(std::isfinite(p.learning_rate) && p.learning_rate > 0.0)) invalid("learning_rate must be finite and greater than 0");
+        if (p.max_depth < 1) invalid("max_depth must be at least 1");
+        if (!(std::isfinite(p.sigma) && p.sigma > 0.0)) invalid("sigma must be finite and greater than 0");
+        return p;
+    }
+    Value to_json() const {
+        Value o = Value::object();
+        o.set("num_trees", Value::uint(num_trees));
+        o.set("learning_rate", Value::number(learning_rate));
+        o.set("max_depth", Value::uint(max_depth));
+        o.set("min_leaf_support", Value::uint(min_leaf_support));
+        o.set("split_candidates", Value::uint(split_candidates));
+        o.set("sigma", Value::number(sigma));
+        o.set("quiet", Value::boolean(quiet));
+        return o;
+    }
+};
+
+// the measures LambdaMART has gradients for: ndcg and ndcg@k (checked before any device work)
+inline void lambdamart_check_measure(const std::string& measure) {
+    std::string base = measure.substr(0, measure.find('@'));
+    for (auto& ch : base) ch = (char)std::tolower((unsigned char)ch);
+    if (base != "ndcg")
+        fail_str("LambdaMART: unsupported training measure \"" + measure + "\" (supported: ndcg, ndcg@k)");
+}
+
+struct LambdaMARTStats {
+    uint32_t trees = 0;
+    double seconds = 0.0;
+    double t_gradient = 0.0, t_grow = 0.0, t_leaves = 0.0, t_update = 0.0;  // wall seconds per stage (device work waited for)
+    std::vector<double> train_measure;                                        // evaluator mean of the running scores after each tree
+
+    Value to_json() const {
+        Value o = Value::object();
+        o.set("trees", Value::uint(trees));
+        o.set("seconds", Value::number(seconds));
+        o.set("gradient_ms", Value::number(t_gradient * 1e3));
+        o.set("grow_ms", Value::number(t_grow * 1e3));
+        o.set("leaves_ms", Value::number(t_leaves * 1e3));
+        o.set("update_ms", Value::number(t_update * 1e3));
+        Value a = Value::array();
+        for (double x : train_measure) a.push(Value::number(x));
+        o.set("train_measure", std::move(a));
+        return o;
+    }
+};
+
+class LambdaMARTTrainer {
+  public:
+    LambdaMARTTrainer(std::shared_ptr<DatasetView> view, Evaluator ev, LambdaMARTParams p)
+        : view_(std::move(view)), ev_(std::move(ev)), p_(p) {}
+
+    Model learn() {
+        auto t0 = std::chrono::steady_clock::now();
+        auto tnow = [] { return std::chrono::steady_clock::now(); };
+        auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
+            return std::chrono::duration<double>(b - a).count();
+        };
+        if (ev_.measure != frdev::M_NDCG) fail_str("LambdaMART: only ndcg and ndcg@k have gradients");
+        frdev::DeviceDataset& dev = view_->device();
+        const frdev::HostCSR& csr = view_->host_csr();
+        const DataCore& core = *view_->core;
+        std::string err;
+        std::vector<uint32_t> feats = view_->features;
+        std::sort(feats.begin(), feats.end());
+        if (feats.empty()) fail_str("assertion failed: !features.is_empty()");
+        if (csr.nq == 0) fail_str("assertion failed: !data.queries().is_empty()");
+        // the instance list: queries in the view's order, ids ascending inside each (RFTrainer's order)
+        std::vector<uint32_t> root_ids;
+        root_ids.reserve(csr.n);
+        for (size_t qi = 0; qi < csr.nq; qi++) {
+            const size_t b = root_ids.size();
+            root_ids.insert(root_ids.end(), csr.perm.begin() + csr.qoff[qi], csr.perm.begin() + csr.qoff[qi + 1]);
+            std::sort(root_ids.begin() + b, root_ids.end());
+        }
+        if ((uint64_t)root_ids.size() * feats.size() >= (1ull << 31))
+            fail_str("LambdaMART: instances x features exceeds the device sort's index range");
+        const std::vector<uint32_t> root_off = {0u, (uint32_t)root_ids.size()};
+        std::vector<uint32_t> positions(root_ids.size());
+        if (!dev.rf_positions(root_ids, positions.data(), &err)) fail_str(err);
+        if (!dev.rf_set_presence(core.present_bits.empty() ? nullptr : core.present_bits.data(), core.present_words, core.n, &err))
+            fail_str(err);
+        uint32_t max_id = 0;
+        for (uint32_t id : root_ids) max_id = std::max(max_id, id);
+
+        RFParams rp;
+        rp.quiet = true;
+        rp.num_trees = 1;
+        rp.weight_trees = false;
+        rp.split_method = 0;
+        rp.min_leaf_support = p_.min_leaf_support;
+        rp.split_candidates = p_.split_candidates;
+        rp.max_depth = p_.max_depth;
+        RFTrainer grower(view_, ev_, rp);
+        RFStats rst;
+        struct EndGuard {
+            frdev::DeviceDataset& d;
+            ~EndGuard() { d.rf_end(); }
+        } end_guard{dev};
+
+        Model out;
+        out.kind = Model::Ensemble;
+        // running scores: acc = 0, slot 0 = acc
+        if (!dev.ensemble_begin(&err) || !dev.ensemble_finish(&err)) fail_str(err);
+        if (!p_.quiet) printf("-----------------------\n|%7s|%15s|\n-----------------------\n", "Tree", ev_.name.c_str());
+        std::vector<double> lam, wt, leaf_of(max_id + 1, 0.0);
+        for (uint32_t t = 0; t < p_.num_trees; t++) {
+            auto ta = tnow();
+            if (!dev.lambda_gradients(ev_.norms.data(), ev_.depth, p_.sigma, &err)) fail_str(err);
+            if (!frdev::device_synchronize(&err)) fail_str(err);
+            auto tb = tnow();
+            std::shared_ptr<TreeNode> root = grower.grow_lambda_tree(dev, root_off, root_ids, feats, positions.data(), rst);
+            auto tc = tnow();
+            // leaves: route every instance through a copy of the tree whose leaves hold their index
+            std::vector<TreeNode*> leaves;
+            std::shared_ptr<TreeNode> routing = number_leaves(*root, leaves);
+            {
+                Model rm;
+                rm.kind = Model::DecisionTree;
+                rm.tree = routing;
+                score_model(*view_, rm, &dev);
+            }
+            if (!dev.download_scores(0, leaf_of.data(), leaf_of.size(), &err)) fail_str(err);
+            if (!dev.lambda_download_positions(&lam, &wt, &err)) fail_str(err);
+            std::vector<double> sl(leaves.size(), 0.0), sw(leaves.size(), 0.0);
+            for (size_t g = 0; g < root_ids.size(); g++) {
+                const double lv = leaf_of[root_ids[g]];
+                if (!(lv >= 0.0 && lv < (double)leaves.size())) fail_str("LambdaMART: an instance was routed to no leaf");
+                const size_t L = (size_t)lv;
+                sl[L] = sl[L] + lam[positions[g]];
+                sw[L] = sw[L] + wt[positions[g]];
+            }
+            for (size_t L = 0; L < leaves.size(); L++) leaves[L]->value = sw[L] != 0.0 ? sl[L] / sw[L] : 0.0;
+            auto td = tnow();
+            // update: slot 0 = tree(x); acc = acc + learning_rate * slot 0; slot 0 = acc
+            Model tm;
+            tm.kind = Model::DecisionTree;
+            tm.tree = root;
+            score_model(*view_, tm, &dev);
+            if (!dev.ensemble_accumulate(p_.learning_rate, &err) || !dev.ensemble_finish(&err)) fail_str(err);
+            double mean = 0.0;
+            if (!dev.metric_from_scores(ev_.measure, ev_.depth, ev_.norms.data(), 1, false, &err)) fail_str(err);
+            if (!dev.reduce_means(1, &mean, &err)) fail_str(err);
+            check_flags(dev);
+            auto te = tnow();
+            stats_.t_gradient += secs(ta, tb);
+            stats_.t_grow += secs(tb, tc);
+            stats_.t_leaves += secs(tc, td);
+            stats_.t_update += secs(td, te);
+            stats_.train_measure.push_back(mean);
+            out.members.push_back(std::move(tm));
+            out.ens_weights.push_back(p_.learning_rate);
+            if (!p_.quiet) {
+                printf("|%7u|%15.6f|\n", t + 1, mean);
+                fflush(stdout);
+            }
+        }
+        if (!p_.quiet) printf("-----------------------\n");
+        stats_.trees = p_.num_trees;
+        stats_.seconds = secs(t0, tnow());
+        return out;
+    }
+
+    const LambdaMARTStats& stats() const { return stats_; }
+
+  private:
+    // a copy of `n` whose leaves hold 0, 1, 2, ... in depth-first order; leaves[i] = the original leaf numbered i
+    static std::shared_ptr<TreeNode> number_leaves(TreeNode& n, std::vector<TreeNode*>& leaves) {
+        auto c = std::make_shared<TreeNode>();
+        copy_numbered(n, *c, leaves);
+        return c;
+    }
+    static void copy_numbered(TreeNode& n, TreeNode& c, std::vector<TreeNode*>& leaves) {
+        c.leaf = n.leaf;
+        c.fid = n.fid;
+        if (n.leaf) {
+            c.value = (double)leaves.size();
+            leaves.push_back(&n);
+            return;
+        }
+        c.value = n.value;
+        c.lhs.reset(new TreeNode());
+        c.rhs.reset(new TreeNode());
+        copy_numbered(*n.lhs, *c.lhs, leaves);
+        copy_numbered(*n.rhs, *c.rhs, leaves);
+    }
+
+    std::shared_ptr<DatasetView> view_;
+    Evaluator ev_;
+    LambdaMARTParams p_;
+    LambdaMARTStats stats_;
+};
+
+}  // namespace fr

@@ -295,6 +295,24 @@ class RFTrainer {
 
     const RFStats& stats() const { return stats_; }
 
+    // One tree over root_ids (one root: root_off = {0, n}) and the features feats, fitted to the LambdaMART gradients of the
+    // device's last lambda_gradients() pass instead of the gains (lambdamart.hpp).  Leaf values are the grower's means.
+    std::shared_ptr<TreeNode> grow_lambda_tree(frdev::DeviceDataset& dev, const std::vector<uint32_t>& root_off,
+                                               const std::vector<uint32_t>& root_ids, const std::vector<uint32_t>& feats,
+                                               const uint32_t* positions, RFStats& stats) {
+        Model out;
+        out.kind = Model::Ensemble;
+        out.members.resize(1);
+        out.ens_weights.assign(1, 1.0);
+        lambda_targets_ = true;
+        struct Reset {
+            bool& b;
+            ~Reset() { b = false; }
+        } reset{lambda_targets_};
+        grow_batch(dev, 0, 1, root_off, root_ids, (uint32_t)feats.size(), feats, positions, out, stats);
+        return out.members[0].tree;
+    }
+
   private:
     struct Open {          // a node whose split is being searched this level
         uint32_t tree;     // index inside the batch
@@ -315,7 +333,7 @@ class RFTrainer {
         auto tnow = [] { return std::chrono::steady_clock::now(); };
         auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
         auto tb0 = tnow();
-        if (!dev.rf_begin(root_off, root_ids, nf, feats, &err, positions)) fail_str(err);
+        if (!dev.rf_begin(root_off, root_ids, nf, feats, &err, positions, lambda_targets_)) fail_str(err);
         stats_.t_begin += secs(tb0, tnow());
         std::vector<std::shared_ptr<TreeNode>> roots(T);
         std::vector<Open> open;
@@ -479,6 +497,7 @@ class RFTrainer {
     size_t n_features_ = 0, n_queries_ = 0;
     std::vector<std::vector<uint32_t>> qids_sorted_;
     std::vector<uint64_t> seeds_;
+    bool lambda_targets_ = false;  // grow_lambda_tree: the split targets are the device's LambdaMART gradients
 };
 
 }  // namespace fr

@@ -63,6 +63,24 @@ def evaluate_dense(model: CModel, dataset: CDataset, evaluator: str, qrel: Optio
     return json.loads(_take_str(qids_ptr.value)), out
 
 
+def lambda_gradients(model: CModel, dataset: CDataset, measure: str = "ndcg", sigma: float = 1.0,
+                     qrel: Optional[CQRel] = None, n_total: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """LambdaMART's gradient pass on the scores of `model`: (lambda, weight) indexed by instance id (NaN where the id is
+    not part of a sampled dataset)."""
+    n = int(n_total if n_total is not None else _load().fr_dataset_num_instances(dataset.pointer))
+    if n_total is None and dataset.is_sampled():
+        n = 1 + max(max(ids) for ids in dataset.instances_by_query().values())
+    lam = np.full(n, np.nan, dtype=np.float64)
+    wt = np.full(n, np.nan, dtype=np.float64)
+    _status(
+        _load().fr_debug_lambda_gradients(
+            model.pointer, dataset.pointer, None if qrel is None else qrel.pointer, measure.encode("utf-8"), float(sigma),
+            lam.ctypes.data, wt.ctypes.data, n,
+        )
+    )
+    return lam, wt
+
+
 def rank_order(model: CModel, dataset: CDataset) -> Tuple[np.ndarray, np.ndarray]:
     """(instance ids grouped by query, best first; offsets[nq+1]) under the reference's
     (score desc, gain asc, id asc) order."""

@@ -1,7 +1,8 @@
 """Training requests for the C ABI's `train_model` (JSON wire form: src/json_api.rs:13-34).
 
 The public names and fields are those of the reference's Python package so that user code keeps
-working (`TrainRequest`, `CoordinateAscentParams`, `RandomForestParams`; fastrank/training.py), but
+working (`TrainRequest`, `CoordinateAscentParams`, `RandomForestParams`; fastrank/training.py; plus
+`LambdaMARTParams`), but
 the implementation is table-driven: every parameter class registers its serde variant name in
 `_VARIANTS`, and `TrainRequest` (de)serialises through that registry.
 """
@@ -77,6 +78,22 @@ class RandomForestParams(_LearnerParams):
 
 
 @dataclasses.dataclass
+class LambdaMARTParams(_LearnerParams):
+    """Gradient-boosted regression trees fitted to LambdaRank gradients, trained on the device (csrc/lambdamart.hpp,
+    kernels_lambda.inc).  The wire form requires all seven keys.  Measures: ndcg and ndcg@k."""
+
+    VARIANT: ClassVar[str] = "LambdaMART"
+
+    num_trees: int = 100
+    learning_rate: float = 0.1
+    max_depth: int = 6
+    min_leaf_support: int = 10
+    split_candidates: int = 64
+    sigma: float = 1.0
+    quiet: bool = False
+
+
+@dataclasses.dataclass
 class TrainRequest:
     """What to optimise (`measure`: "ndcg", "ndcg@10", "map", "mrr", ...), how (`params`) and,
     optionally, the judgments that define ideal gains / relevant counts."""
@@ -121,3 +138,7 @@ class TrainRequest:
     @staticmethod
     def random_forest() -> "TrainRequest":
         return TrainRequest._defaults("random_forest_defaults")
+
+    @staticmethod
+    def lambdamart() -> "TrainRequest":
+        return TrainRequest._defaults("lambdamart_defaults")

@@ -170,6 +170,13 @@ const void *fr_predict_scores_dense(const CModel *model, const CDataset *dataset
 const void *fr_evaluate_dense(const CModel *model, const CDataset *dataset, const CQRel *qrel,
                               const void *evaluator_name, double *out_values, size_t out_len,
                               const void **out_qids_json);
+/* LambdaMART test hook: one gradient pass on the scores of `model` for `measure` (ndcg or ndcg@k;
+ * qrel-judged norms when qrel is given) with sigmoid scale sigma.  lambda_out / weight_out[i] = the
+ * LambdaRank gradient / weight of instance i (instances outside the view are left untouched).
+ * Returns NULL on success or an error-envelope string. */
+const void *fr_debug_lambda_gradients(const CModel *model, const CDataset *dataset, const CQRel *qrel,
+                                      const void *measure, double sigma, double *lambda_out,
+                                      double *weight_out, size_t out_len);
 /* Full per-query rank order under the reference's total order (src/evaluators.rs:34-49):
  * out_instance_ids[n] grouped by query (device query order), best first; out_offsets[nq+1]. */
 const void *fr_rank_order(const CModel *model, const CDataset *dataset, uint32_t *out_instance_ids,

@@ -1,0 +1,226 @@
+"""LambdaMART on the device against the numpy restatement (tests/lambdamart_model.py)."""
+import json
+import os
+
+import numpy as np
+import pytest
+
+import fastrank_amd as fr
+from fastrank_amd import native
+from oracle import pyoracle as o
+from tests import lambdamart_model as lm
+from tests.conftest import GOLDEN, synth_dataset
+
+pytestmark = pytest.mark.gpu
+
+
+def _request(measure="ndcg", **kw):
+    req = fr.TrainRequest.lambdamart()
+    req.measure = measure
+    req.params.quiet = True
+    for k, v in kw.items():
+        setattr(req.params, k, v)
+    return req
+
+
+@pytest.fixture(scope="module")
+def trec():
+    d = np.load(os.path.join(GOLDEN, "trec_news_2018.npz"))
+    X, y, qid = d["train_X"], d["train_y"], d["train_qid"]
+    return X, y, qid, fr.CDataset.from_numpy(X, y, qid), o.Dataset(X, y, qid)
+
+
+@pytest.fixture(scope="module")
+def qrel_dict():
+    with open(os.path.join(GOLDEN, "newsir18_entity_qrel.json")) as fh:
+        return json.load(fh)
+
+
+def _tied_set():
+    """Queries of 1, 2 and up to 1 300 documents; one query without a positive label, one whose labels are all equal."""
+    X, y, qid = synth_dataset(21, 6000, 8, 40, max_len=1300)
+    qid = qid.copy()
+    qid[-1300:] = 2000  # one query of 1 300 documents
+    # query 1 -> one document, query 2 -> two documents (moved to fresh qids 1001 / 1002)
+    first = np.flatnonzero(qid == 1)
+    qid[first[0]] = 1001
+    second = np.flatnonzero(qid == 2)
+    qid[second[:2]] = 1002
+    y = y.copy()
+    y[qid == 3] = 0.0  # no positive label
+    y[qid == 4] = 2.0  # all labels equal
+    return X, y, qid
+
+
+def _check_gradients(g, c, X, y, model, measure, norms, qrel=None, sigma=1.0):
+    scores = native.predict_scores_dense(model, g)
+    lam, wt = native.lambda_gradients(model, g, measure, sigma, qrel)
+    queries = lm.query_lists(c)
+    elam, ewt = lm.gradients(scores, y, queries, norms, lm.depth_of(measure), sigma)
+    assert np.all(np.isfinite(lam)) and np.all(np.isfinite(wt))
+    for got, exp in ((lam, elam), (wt, ewt)):
+        zero = exp == 0.0
+        assert np.array_equal(got[zero], exp[zero])
+        np.testing.assert_allclose(got, exp, rtol=1e-12, atol=0.0)
+    for ids in queries:
+        assert abs(lam[ids].sum()) <= 1e-9 * max(1.0, np.abs(lam[ids]).sum())
+    return lam, wt
+
+
+@pytest.mark.parametrize("measure", ["ndcg", "ndcg@1", "ndcg@10", "ndcg@5000"])
+def test_gradient_kernel_matches_restatement(measure):
+    X, y, qid = _tied_set()
+    g, c = fr.CDataset.from_numpy(X, y, qid), o.Dataset(X, y, qid)
+    # a linear model on the integer columns: many tied scores
+    w = [0.0] * X.shape[1]
+    w[1], w[5] = 1.0, 2.0
+    model = fr.CModel.from_dict({"Linear": {"weights": w}})
+    lam, wt = _check_gradients(g, c, X, y, model, measure, c.default_norms(measure), sigma=1.5)
+    assert np.all(lam[qid == 3] == 0.0) and np.all(wt[qid == 3] == 0.0)
+    assert np.all(lam[qid == 4] == 0.0) and np.all(wt[qid == 4] == 0.0)
+    assert np.all(lam[qid == 1001] == 0.0)
+    assert np.any(lam[qid == 1002] != 0.0) or len(set(y[qid == 1002])) == 1
+
+
+def test_gradient_kernel_with_qrel_norms(trec, qrel_dict):
+    X, y, qid, g, c = trec
+    qrel = fr.CQRel.from_dict(qrel_dict)
+    model = fr.CModel.from_dict({"Linear": {"weights": [0.0, 0.3, -0.2, 0.5, 0.1, 0.9]}})
+    for measure in ("ndcg", "ndcg@5"):
+        _check_gradients(g, c, X, y, model, measure, c.qrel_norms(measure, qrel_dict), qrel=qrel)
+
+
+def _stagewise(g, c, X, y, measure, T, params):
+    req = _request(measure, num_trees=T, **params)
+    model = g.train_model(req)
+    d = model.to_dict()
+    trees = [m["DecisionTree"] for m in d["Ensemble"]["models"]]
+    assert d["Ensemble"]["weights"] == [req.params.learning_rate] * T
+    queries = lm.query_lists(c)
+    order_ids = np.concatenate(queries)
+    for t in range(T):
+        prefix = fr.CModel.from_dict({"Ensemble": {"weights": [req.params.learning_rate] * t,
+                                                   "models": [{"DecisionTree": x} for x in trees[:t]]}})
+        lam, wt = native.lambda_gradients(prefix, g, measure, req.params.sigma)
+        exp = lm.fit_tree(X, lam, wt, order_ids, range(X.shape[1]), req.params.max_depth, req.params.min_leaf_support,
+                          req.params.split_candidates)
+        assert trees[t] == exp, "tree %d differs from the restatement's fit" % t
+    return model, req
+
+
+def test_stagewise_identity_trec(trec):
+    X, y, qid, g, c = trec
+    _stagewise(g, c, X, y, "ndcg@10", 20, dict(max_depth=5, min_leaf_support=5, split_candidates=16, learning_rate=0.1))
+
+
+def test_stagewise_identity_synthetic():
+    X, y, qid = synth_dataset(7, 5000, 10, 50)
+    g, c = fr.CDataset.from_numpy(X, y, qid), o.Dataset(X, y, qid)
+    _stagewise(g, c, X, y, "ndcg", 20, dict(max_depth=4, min_leaf_support=10, split_candidates=12, sigma=1.0))
+
+
+def _train_stats(g, req):
+    model = g.train_model(req)
+    st = native.last_train_stats()
+    assert st["path"] == "lambdamart"
+    return model, st["lambdamart"]
+
+
+@pytest.mark.parametrize("measure", ["ndcg", "ndcg@10"])
+def test_running_scores_equal_prediction(trec, measure):
+    X, y, qid, g, c = trec
+    model, st = _train_stats(g, _request(measure, num_trees=12, max_depth=4, min_leaf_support=5, split_candidates=16))
+    assert st["trees"] == 12 and len(st["train_measure"]) == 12
+    for key in ("seconds", "gradient_ms", "grow_ms", "leaves_ms", "update_ms"):
+        assert st[key] >= 0.0
+    _, per_q = native.evaluate_dense(model, g, measure)
+    assert st["train_measure"][-1] == o.mean(per_q)
+    d = model.to_dict()["Ensemble"]
+    exp = c.score_ensemble([m["DecisionTree"] for m in d["models"]], d["weights"])
+    assert np.array_equal(native.predict_scores_dense(model, g), exp)
+
+
+def test_learning_happens():
+    X, y, qid = synth_dataset(3, 5000, 16, 60)
+    g, c = fr.CDataset.from_numpy(X, y, qid), o.Dataset(X, y, qid)
+    model, st = _train_stats(g, _request("ndcg@10", num_trees=50, split_candidates=32))
+    assert st["train_measure"][-1] > st["train_measure"][0]
+    zero = fr.CModel.from_dict({"Linear": {"weights": [0.0] * X.shape[1]}})
+    _, base = native.evaluate_dense(zero, g, "ndcg@10")
+    _, mine = native.evaluate_dense(model, g, "ndcg@10")
+    assert np.nanmean(mine) > np.nanmean(base) + 0.05
+
+
+def test_full_restatement_small(trec):
+    """The whole loop on the CPU gives the device's model (the exp of the two sides may differ in the last bit, so the
+    CPU's own gradients can in principle pick another split: a tiny dataset and few trees)."""
+    X, y, qid, g, c = trec
+    req = _request("ndcg@5", num_trees=3, max_depth=3, min_leaf_support=5, split_candidates=8)
+    model = g.train_model(req)
+    exp, s = lm.train(X, y, c, "ndcg@5", num_trees=3, learning_rate=0.1, max_depth=3, min_leaf_support=5,
+                      split_candidates=8)
+    got = model.to_dict()
+    assert [m["DecisionTree"] for m in got["Ensemble"]["models"]] == [m["DecisionTree"] for m in exp["Ensemble"]["models"]] or \
+        np.allclose(native.predict_scores_dense(model, g), s, rtol=1e-9, atol=1e-12)
+
+
+def test_query_subsample_trains_like_its_own_rows(trec):
+    X, y, qid, g, c = trec
+    names = sorted(g.queries())
+    sub_q = names[::2]
+    sub = g.subsample_queries(sub_q)
+    rows = np.isin(np.array([str(int(q)) for q in qid]), sub_q)
+    own = fr.CDataset.from_numpy(np.ascontiguousarray(X[rows]), np.ascontiguousarray(y[rows]), np.ascontiguousarray(qid[rows]))
+    req = _request("ndcg@10", num_trees=8, max_depth=4, min_leaf_support=4, split_candidates=16)
+    assert sub.train_model(req).to_dict() == own.train_model(req).to_dict()
+
+
+def _fids(node, out):
+    if "FeatureSplit" in node:
+        out.add(node["FeatureSplit"]["fid"])
+        _fids(node["FeatureSplit"]["lhs"], out)
+        _fids(node["FeatureSplit"]["rhs"], out)
+    return out
+
+
+def test_feature_subsample_uses_only_its_features(trec):
+    X, y, qid, g, c = trec
+    names = sorted(g.feature_names())
+    keep = names[1::2]
+    sub = g.subsample_feature_names(keep)
+    allowed = set(sub.feature_ids())
+    model = sub.train_model(_request("ndcg", num_trees=10, max_depth=4, min_leaf_support=4, split_candidates=16))
+    used = set()
+    for m in model.to_dict()["Ensemble"]["models"]:
+        _fids(m["DecisionTree"], used)
+    assert used and used <= allowed
+
+
+def test_ranksvm_dataset_trains():
+    rd = fr.CDataset.open_ranksvm(os.path.join(GOLDEN, "data", "trec_news_2018.train"))
+    model = rd.train_model(_request("ndcg@5", num_trees=5, max_depth=3, min_leaf_support=5, split_candidates=8))
+    assert len(model.to_dict()["Ensemble"]["models"]) == 5
+    vals = rd.evaluate(model, "ndcg@5")
+    assert all(np.isfinite(v) for v in vals.values())
+
+
+def test_deterministic_and_single_device(trec, monkeypatch):
+    X, y, qid, g, c = trec
+    req = _request("ndcg", num_trees=6, max_depth=4, min_leaf_support=5, split_candidates=16)
+    a = json.dumps(g.train_model(req).to_dict())
+    b = json.dumps(g.train_model(req).to_dict())
+    assert a == b
+    monkeypatch.setenv("FR_DEVICES", "0,0")
+    g2 = fr.CDataset.from_numpy(X, y, qid)
+    assert json.dumps(g2.train_model(req).to_dict()) == a
+    assert native.last_train_stats()["devices"] == 1
+
+
+def test_quiet_false_prints_one_line_per_tree(trec, capfd):
+    X, y, qid, g, c = trec
+    req = _request("ndcg", num_trees=3, max_depth=3, min_leaf_support=5, split_candidates=8)
+    req.params.quiet = False
+    g.train_model(req)
+    out = capfd.readouterr().out
+    rows = [l for l in out.splitlines() if l.startswith("|") and l.strip("|").split("|")[0].strip().isdigit()]
+    assert len(rows) == 3

@@ -1,0 +1,100 @@
+"""lmbench.py -- LambdaMART training time on an MSLR-WEB30K-shaped matrix (bench.py's generator), one JSON line.
+
+    python tools/lmbench.py --shape 30k --trees 100            # the device: seconds per tree and the per-stage split
+    python tools/lmbench.py --shape 30k --cpu-baseline 0.01    # the numpy restatement (tests/lambdamart_model.py) timed on
+                                                               # a query sample, scaled to the full shape (labelled as such)
+Every other parameter is the LambdaMART default (TrainRequest.lambdamart()).
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from bench import SHAPES, gen_mslr_shaped  # noqa: E402
+
+
+def device_run(args, X, y, qid):
+    import fastrank_amd as fr
+    from fastrank_amd import native
+
+    t0 = time.perf_counter()
+    ds = fr.CDataset.from_numpy(X, y, qid)
+    req = fr.TrainRequest.lambdamart()
+    req.measure = args.measure
+    req.params.num_trees = args.trees
+    req.params.quiet = True
+    # upload and first touch of the device (not part of training)
+    native.device_info(ds)
+    t_ds = time.perf_counter() - t0
+    native.profile_enable(True)
+    native.profile_reset()
+    t1 = time.perf_counter()
+    model = ds.train_model(req)
+    wall = time.perf_counter() - t1
+    st = native.last_train_stats()["lambdamart"]
+    prof = native.profile_stats()
+    native.profile_enable(False)
+    T = st["trees"]
+    return {
+        "metric": "LambdaMART seconds per tree (device) on MSLR-WEB30K shape" if args.shape == "30k" else "LambdaMART seconds per tree (device)",
+        "shape": args.shape, "n": int(X.shape[0]), "d": int(X.shape[1]), "queries": int(len(np.unique(qid))),
+        "measure": args.measure, "trees": T, "params": req.params.to_dict(),
+        "dataset_seconds": t_ds, "train_seconds": wall, "seconds_per_tree": wall / T,
+        "per_tree_ms": {k: st[k + "_ms"] / T for k in ("gradient", "grow", "leaves", "update")},
+        "train_measure_first": st["train_measure"][0], "train_measure_last": st["train_measure"][-1],
+        "kernel_profile": {k: v for k, v in prof.items() if "lambda" in k or "rf_" in k or "tree" in k},
+        "model_nodes": len(json.dumps(model.to_dict())),
+    }
+
+
+def cpu_run(args, X, y, qid):
+    from oracle import pyoracle as o
+    from tests import lambdamart_model as lm
+
+    rng = np.random.default_rng(1)
+    uq = np.unique(qid)
+    keep = rng.choice(uq, size=max(1, int(round(len(uq) * args.cpu_baseline))), replace=False)
+    rows = np.isin(qid, keep)
+    Xs, ys, qs = np.ascontiguousarray(X[rows]), np.ascontiguousarray(y[rows]), np.ascontiguousarray(qid[rows])
+    c = o.Dataset(Xs, ys, qs)
+    queries = lm.query_lists(c)
+    order_ids = np.concatenate(queries)
+    norms = c.default_norms(args.measure)
+    s = np.zeros(len(ys))
+    t0 = time.perf_counter()
+    lam, wt = lm.gradients(s, ys, queries, norms, lm.depth_of(args.measure), 1.0)
+    t1 = time.perf_counter()
+    lm.fit_tree(Xs, lam, wt, order_ids, range(Xs.shape[1]), 6, 10, 64)
+    t2 = time.perf_counter()
+    scale = X.shape[0] / Xs.shape[0]
+    return {
+        "metric": "LambdaMART seconds per tree, CPU restatement (numpy, one thread), SCALED from a %g query sample" % args.cpu_baseline,
+        "shape": args.shape, "sample_rows": int(Xs.shape[0]), "sample_queries": int(len(keep)),
+        "sample_gradient_seconds": t1 - t0, "sample_fit_seconds": t2 - t1,
+        "scaled_seconds_per_tree": (t2 - t0) * scale, "scale": scale,
+        "note": "linear scaling by rows; not a measurement of the full shape",
+    }
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shape", default="30k", choices=sorted(SHAPES))
+    ap.add_argument("--trees", type=int, default=100)
+    ap.add_argument("--measure", default="ndcg")
+    ap.add_argument("--cpu-baseline", type=float, default=0.0, help="query fraction for the CPU restatement (0: device run)")
+    args = ap.parse_args()
+    n, d, q, seed = SHAPES[args.shape]
+    X, y, qid = gen_mslr_shaped(seed, n, d, q)
+    out = cpu_run(args, X, y, qid) if args.cpu_baseline > 0 else device_run(args, X, y, qid)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
