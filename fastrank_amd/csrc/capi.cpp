@@ -1458,9 +1458,7 @@ const void* fr_evaluate_candidates(const CDataset* dataset, const CQRel* qrel, c
         for (size_t g = 0; g < n_groups; g++)
             if (n_cand[g] == 0 || n_cand[g] > 64 || features[g] >= d)
                 fr::fail_str("fr_evaluate_candidates: malformed group");
-        const bool topk = dev.linesearch_supported(ev.measure, ev.depth);
-        const bool full = !topk && dev.fullrank_supported(ev.measure, ev.depth) && !frdev::path_env("FR_FORCE_GENERIC");
-        if (topk || full) {
+        if (dev.linesearch_path(ev.measure, ev.depth) != frdev::DeviceDataset::LS_NONE) {
             std::vector<frdev::LineGroup> groups(n_groups);
             for (size_t g = 0; g < n_groups; g++) {
                 groups[g].feature = features[g];
@@ -1468,11 +1466,7 @@ const void* fr_evaluate_candidates(const CDataset* dataset, const CQRel* qrel, c
                 groups[g].candidates.assign(candidates + g * 64, candidates + g * 64 + n_cand[g]);
             }
             std::vector<double> means;
-            if (topk) {
-                if (!dev.linesearch_ndcg(ev.depth, ev.norms.data(), groups, &means, &err)) fr::fail_str(err);
-            } else {
-                if (!dev.linesearch_fullrank(ev.measure, ev.depth, ev.norms.data(), groups, &means, &err)) fr::fail_str(err);
-            }
+            if (!dev.linesearch(ev.measure, ev.depth, ev.norms.data(), groups, &means, nullptr, &err)) fr::fail_str(err);
             fr::check_flags(dev);
             std::copy(means.begin(), means.end(), out_means);
             if (out_per_query) {

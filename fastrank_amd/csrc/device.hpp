@@ -219,29 +219,27 @@ class DeviceDataset {
     // SUM over this dataset's queries, in the fixed two-level shape, instead of the mean
     void set_sums_only(bool on);
 
-    // --- fused line search (NDCG@k, k <= 20) --------------------------------------------------
-    // false for non-NDCG@k measures, k > 20, and datasets with non-finite features
-    bool linesearch_supported(int measure, int64_t depth) const;
-    // evaluates every candidate of every group; means[g*64 + c]
-    bool linesearch_ndcg(int64_t depth, const double* norms, const std::vector<LineGroup>& groups,
-                         std::vector<double>* means, std::string* err);
-    // The same in parts, for callers that keep several independent sets of groups in flight (ctx 0 ..
-    // LINESEARCH_CONTEXTS-1: each has its own stream and buffers, so the host's work between two line searches of
-    // one set overlaps the kernels of the others).  submit queues everything and returns; collect waits and
-    // returns means[g*64 + c].
+    // --- line search: every candidate of every group, means[g*64 + c] --------------------------------------
+    // Bound-and-verify: candidates are decided from approximate scores with a proven error bound, what is left
+    // is recomputed by the exact kernels.  LS_TOPK: NDCG@k, k <= 20 (kernels_verify.inc).  LS_FULLRANK: NDCG of any depth
+    // and AP (kernels_fullverify.inc), reciprocal rank (kernels_rr.inc).  LS_NONE: the general sort evaluator's (non-finite
+    // features, too many gain classes or documents per query; FR_FORCE_GENERIC for the full-ranking measures).
+    enum LsPath : int { LS_NONE = 0, LS_TOPK = 1, LS_FULLRANK = 2 };
+    LsPath linesearch_path(int measure, int64_t depth) const;
+    // Contexts 0 .. LINESEARCH_CONTEXTS-1 have their own streams and buffers: callers keep several sets of groups in flight
+    // and the host's work between two line searches of one set overlaps the kernels of the others.  submit always leaves the
+    // context pending (where bound-and-verify does not apply it runs the exact kernels at once); collect waits for it.
+    // counts: the (query, group) pairs this line search gave to the verify kernels, and how many of them were redone.
     static constexpr int LINESEARCH_CONTEXTS = 4;
-    bool linesearch_ndcg_submit(int ctx, int64_t depth, const double* norms, const std::vector<LineGroup>& groups, std::string* err);
-    bool linesearch_ndcg_collect(int ctx, std::vector<double>* means, std::string* err);
-    // Reciprocal rank on resident sums, same contexts: *queued = false means "not applicable right now" (nothing is
-    // pending; pending resident updates were applied) and the caller evaluates the groups with linesearch_fullrank.
-    bool linesearch_rr_submit(int ctx, const std::vector<LineGroup>& groups, bool* queued, std::string* err);
-    bool linesearch_rr_collect(int ctx, std::vector<double>* means, std::string* err);
-    // The same protocol for every full-ranking measure: reciprocal rank as above; NDCG of any depth and AP by sorting
-    // approximate keys in registers and verifying the gaps between neighbours of different gain class
-    // (kernels_fullverify.inc; works from resident sums or, for stateless callers, from the feature tiles).
-    bool linesearch_fullrank_submit(int ctx, int measure, int64_t depth, const double* norms,
-                                    const std::vector<LineGroup>& groups, bool* queued, std::string* err);
-    bool linesearch_fullrank_collect(int ctx, std::vector<double>* means, std::string* err);
+    struct LsCounts {
+        unsigned long long pairs = 0, redone = 0;
+    };
+    bool linesearch_submit(int ctx, int measure, int64_t depth, const double* norms, const std::vector<LineGroup>& groups,
+                           std::string* err);
+    bool linesearch_collect(int ctx, std::vector<double>* means, LsCounts* counts, std::string* err);
+    // lock step: submit, then collect (LS_TOPK on context 0, LS_FULLRANK on a context of its own on the main stream)
+    bool linesearch(int measure, int64_t depth, const double* norms, const std::vector<LineGroup>& groups,
+                    std::vector<double>* means, LsCounts* counts, std::string* err);
     // resident per-document sums for LineGroup::resident_slot: `slots` double-buffered arrays of np doubles
     // Returns an owner ticket (0 on failure).  A later reserve by someone else takes the buffers over: groups
     // and stores that carry the old ticket are then treated as non-resident / refused.
@@ -250,8 +248,6 @@ class DeviceDataset {
     // empty *err when the ticket is stale
     bool resident_store_from_scores(uint64_t owner, size_t slot, size_t b, std::string* err);
     const std::vector<double>& column_absmax() const;  // per-column max |x|
-    // running totals: (run, group) pairs given to the bound-and-verify kernel / recomputed exactly
-    void verify_counters(unsigned long long* pairs, unsigned long long* redone) const;
     // line searches evaluated by the exact kernels alone (NDCG@k: every group of the line search was routed there; the other
     // measures: a recent line search had > 25 % of its pairs redone)
     unsigned long long exact_fallbacks() const;
@@ -265,12 +261,6 @@ class DeviceDataset {
                         unsigned long long* ranked_off = nullptr) const;
     // FR_VERIFY_AUDIT=1: values re-derived by the exact kernel after a bound-and-verify line search / how many differed
     void audit_counters(unsigned long long* values, unsigned long long* mismatches) const;
-    // --- full-ranking line search (AP, RR, NDCG of any depth): scores kernel + rank-counting kernel ----
-    bool fullrank_supported(int measure, int64_t depth) const;
-    bool linesearch_fullrank(int measure, int64_t depth, const double* norms, const std::vector<LineGroup>& groups,
-                             std::vector<double>* means, std::string* err);
-    // column stride of the last linesearch result (for download_per_query-style inspection)
-    size_t last_ldm() const;
     bool download_last_matrix(std::vector<double>* out, size_t* ldm, std::string* err);
 
     // --- random-forest training (src/random_forest.rs:211-408; kernels_rf.inc) ---------------------------------

@@ -82,8 +82,10 @@ struct DeviceDataset::Impl {
     };
     // A line-search context: its own stream and every buffer one tick writes, so that two ticks (of disjoint sets
     // of restarts) can be in flight at once and the host's work between the ticks of one set hides behind the
-    // kernels of the others.  ls[0 .. LS_CONTEXTS-1]: NDCG@k submit / collect; ls[LS_CONTEXTS]: the reciprocal-rank
-    // path (main stream).
+    // kernels of the others.  ls[0 .. LS_CONTEXTS-1]: submit / collect (ls[0] also the lock-step top-k path);
+    // ls[LS_CONTEXTS]: the lock-step full-ranking path (main stream).
+    // The three verify kernels a line search can take: top-k NDCG, reciprocal rank, full-ranking NDCG / AP
+    enum LsKind { LSK_TOPK, LSK_RR, LSK_FV };
     struct LsCtx {
         hipStream_t stream = nullptr;
         PinnedBuf tick_h, tick_res;
@@ -95,50 +97,53 @@ struct DeviceDataset::Impl {
         template <typename T> T* td(size_t off) { return reinterpret_cast<T*>(tick_d.p + off); }
         // a submitted, not yet collected line search
         bool pending = false, approx = false;
+        bool ready = false;  // evaluated by the exact kernels at submit: exact_means holds the result
+        LsKind kind = LSK_TOPK;
         TickStage ts;
-        LSArgs a;
+        LSArgs a;     // top-k: the kernels' arguments; every kind: the resident parameters (resident_update_kernel)
         RRArgs ra;
         FSArgs fsa;   // full-ranking bound-and-verify: the exact kernels' arguments for the redo list
         RMArgs rma;
-        bool fv = false;  // the pending line search is fv_launch's (else rr_launch's)
         DevBuf<double> fv_rows;  // score rows of this context's redo slots (contexts run concurrently: no sharing)
         size_t ldm = 0, maxc = 0, lds = 0;
         int64_t depth = 0;
         int xs_used = 1;         // list length variant of the pending verify launch
         bool xs_pinned = false;  // ... chosen by FR_VERIFY_XS
-        unsigned redo_grid = 512, redo_grid_used = 512;  // NDCG@k: pairs the exact kernel's fixed first launch takes (adapts to the redo counts seen)
+        bool audit = false;      // FR_VERIFY_AUDIT
+        unsigned redo_grid = 512, redo_grid_used = 512;  // pairs the exact kernels' fixed first launch takes (NDCG@k: adapts to the redo counts seen)
         // NDCG@k per-group routing: the pending line search staged its groups as [verify groups | exact groups];
         // gorder[k] = the caller's index of staged group k (empty: the caller's order), gslot[k] = its resident slot
         size_t nverify = 0;
         std::vector<uint32_t> gorder, gredo_h;
         std::vector<int> gslot;
         std::vector<LineGroup> pgroups;
+        std::vector<double> exact_means;
+        LsCounts counts;  // this line search's verify pairs / redone pairs
     };
     LsCtx ls[LS_CONTEXTS + 1];
     hipEvent_t res_ready = nullptr;  // recorded on the main stream after a resident-sum store; the contexts wait on it
     bool res_ready_set = false;
     const double* last_M = nullptr;  // device matrix of the last per-query result (download_per_query / reduce_means)
+    bool ls_submit(LsCtx& c, int path, int measure, int64_t depth, const double* norms, const std::vector<LineGroup>& groups,
+                   std::string* err);
+    bool ls_collect(LsCtx& c, std::vector<double>* means, std::string* err);
+    bool topk_policy(LsCtx& c, uint32_t nredo, uint32_t nslices, std::string* err);
+    bool ls_exact(LsCtx& c, int measure, int64_t depth, const double* norms, const std::vector<LineGroup>& groups, std::string* err);
+    bool ls_means(LsCtx& c, std::string* err);
     bool tick_begin(LsCtx& c, const std::vector<LineGroup>& groups, std::string* err);
     bool tick_upload(LsCtx& c, bool with_eps2, std::string* err);
-    double* tick_host_out(LsCtx& c, size_t ldm, std::string* err);
     bool tick_finish(LsCtx& c, size_t ldm, std::vector<double>* means, uint32_t* nredo, std::string* err, uint32_t* npairs = nullptr,
                      std::vector<uint32_t>* by_group = nullptr);
-    bool stage_resident(const std::vector<LineGroup>& groups, LSArgs& a, LsCtx& c, bool* resident_out, bool* any_update_out);
+    bool stage_resident(LsCtx& c, const std::vector<LineGroup>& groups, bool* any_update_out);
     // key_relative (the NDCG@k verify kernel): eps2_host holds only the ABSOLUTE part of a pair's bound, eps_gamma the factor on
     // |key_a| + |key_b| the kernel adds (verify_far)
     bool compute_eps2(const std::vector<LineGroup>& groups, bool resident, uint32_t cls_bits, bool bare_admission = false, bool key_relative = false);
     double eps_gamma = 0.0;
+    bool update_resident(LsCtx& c, size_t g_base, size_t ng, std::string* err);
     void flip_resident(const std::vector<LineGroup>& groups);
-    // reciprocal rank by bound-and-verify (resident sums only); *done = false: not applicable, use the exact kernels
-    bool linesearch_rr_verify(const std::vector<LineGroup>& groups, std::vector<double>* means, bool* done, std::string* err);
-    bool rr_launch(LsCtx& c, const std::vector<LineGroup>& groups, bool* queued, std::string* err);
-    bool rr_finish(LsCtx& c, std::vector<double>* means, std::string* err);
-    // NDCG (any depth) / AP by sorting approximate keys and verifying the gaps (kernels_fullverify.inc)
-    bool fv_usable(int measure) const;
-    bool fv_launch(LsCtx& c, int measure, int64_t depth, const double* norms, const std::vector<LineGroup>& groups,
-                   bool* queued, std::string* err);
-    bool fv_finish(LsCtx& c, std::vector<double>* means, std::string* err);
-    bool fv_redo_launch(LsCtx& c, const uint32_t* list, const uint32_t* count_dev, unsigned nblocks, std::string* err);
+    bool redo_launch(LsCtx& c, uint32_t off, const uint32_t* count_dev, uint32_t n, std::string* err);
+    FSArgs scores_args(const uint32_t* gfeat, const double* gw, const double* gcand, double* rows, int* flags, size_t gc) const;
+    RMArgs rank_args(const double* rows, const uint32_t* gncand, double* M, int* flags, size_t gc, size_t ldm, int measure, int64_t depth) const;
     int device = 0;
     hipStream_t stream = nullptr;
     size_t n = 0, d = 0, nq = 0, np = 0, dq = 0, maxlen = 0, nruns = 0;
@@ -337,7 +342,6 @@ size_t DeviceDataset::n() const { return impl_->n; }
 size_t DeviceDataset::d() const { return impl_->d; }
 size_t DeviceDataset::nq() const { return impl_->nq; }
 size_t DeviceDataset::max_query_len() const { return impl_->maxlen; }
-size_t DeviceDataset::last_ldm() const { return impl_->last_ldm; }
 size_t DeviceDataset::hbm_bytes() const {
     // bytes of dataset arrays this object OWNS (aliases of a parent's buffers are the parent's)
     const Impl& m = *impl_;
@@ -1290,7 +1294,7 @@ static bool launch_means(const double* M, size_t ldm, size_t ncols, size_t nq, b
                          const int* tail_flags = nullptr, double* host_copy = nullptr, const uint32_t* tail_groups = nullptr) {
     // (a tick's means, redo counter and error bits reach the host only through final_mean_kernel's copy into the
     // context's page-locked block: a tick -- the callers that pass tail_count -- without that block must fail here, not
-    // read stale or null memory in tick_finish; tick_host_out has set *err)
+    // read stale or null memory in tick_finish; ls_means has set *err)
     if (tail_count != nullptr && host_copy == nullptr) return false;
     const size_t nseg = (nq + MEAN_SEG - 1) / MEAN_SEG;
     if (!partial.ensure(std::max<size_t>(1, nseg) * ldm, err) || !means.ensure(ldm + mean_tail_words(ldm), err)) return false;
@@ -2041,11 +2045,17 @@ bool DeviceDataset::reduce_means(size_t ncols, double* out, std::string* err) {
     FR_HIP(hipStreamSynchronize(m.stream));
     return true;
 }
-
-bool DeviceDataset::linesearch_supported(int measure, int64_t depth) const {
+DeviceDataset::LsPath DeviceDataset::linesearch_path(int measure, int64_t depth) const {
+    const Impl& m = *impl_;
     // zero-weight masking is exact only for finite features (inf * 0 = NaN)
-    return measure == M_NDCG && depth >= 0 && depth <= 20 && !impl_->nonfinite && impl_->dq * 4 <= 2048;
+    if (m.nonfinite || m.dq * 4 > 2048) return LS_NONE;
+    if (measure == M_NDCG && depth >= 0 && depth <= 20) return LS_TOPK;
+    if (frdev::path_env("FR_FORCE_GENERIC") != nullptr) return LS_NONE;
+    if (m.maxlen > 2048) return LS_NONE;                                          // per-lane rank table must fit LDS (64 B per rank)
+    if (measure == M_NDCG && m.termtab.cap < m.ncls * m.tablen) return LS_NONE;  // too many gain classes
+    return (measure == M_NDCG || measure == M_AP || measure == M_RR) ? LS_FULLRANK : LS_NONE;
 }
+
 
 // ---- resident base sums and error bounds shared by the bound-and-verify paths -------------------------
 
@@ -2103,12 +2113,15 @@ bool DeviceDataset::Impl::tick_upload(LsCtx& c, bool with_eps2, std::string* err
     FR_HIP(hipMemcpyAsync(c.tick_d.p, c.tick_h.p, c.ts.total, hipMemcpyHostToDevice, c.stream));
     return true;
 }
-
-// where final_mean_kernel writes a tick's results for the host: the context's page-locked result block (the means, then
-// the redo counter, the kernel error bits and the per-group redo counts) -- no copy of their own brings them back
-double* DeviceDataset::Impl::tick_host_out(LsCtx& c, size_t ldm, std::string* err) {
-    if (!c.tick_res.ensure((ldm + mean_tail_words(ldm)) * sizeof(double), err)) return nullptr;
-    return reinterpret_cast<double*>(c.tick_res.p);
+// column means of the context's result matrix.  final_mean_kernel writes them for the host into the context's page-locked
+// result block (the means, then the redo counter, the kernel error bits and, top-k, the per-group redo counts) -- no copy of
+// their own brings them back
+bool DeviceDataset::Impl::ls_means(LsCtx& c, std::string* err) {
+    Impl& m = *this;
+    const size_t ldm = c.ldm;
+    if (!c.tick_res.ensure((ldm + mean_tail_words(ldm)) * sizeof(double), err)) return false;
+    return launch_means(c.M.p, ldm, ldm, m.nq, m.sums_only, c.partial, c.means, c.stream, err, c.td<unsigned long long>(c.ts.o_count),
+                        c.flags.p, reinterpret_cast<double*>(c.tick_res.p), c.kind == LSK_TOPK ? c.td<uint32_t>(c.ts.o_gredo) : nullptr);
 }
 
 // waits for the context's stream and hands the results over: *nredo = entries of the redo list, *npairs = the high word of
@@ -2137,14 +2150,12 @@ bool DeviceDataset::Impl::tick_finish(LsCtx& c, size_t ldm, std::vector<double>*
     }
     return true;
 }
-
-// Resident sums are used when every group carries the current owner's ticket.  Writes the per-group
-// parameters (slot * 2 + current half; 1/norm, base_f, pending update) into the tick block and points `a` at
-// their device copies.
-bool DeviceDataset::Impl::stage_resident(const std::vector<LineGroup>& groups, LSArgs& a, LsCtx& c,
-                                         bool* resident_out, bool* any_update_out) {
+// Resident sums are used when every group carries the current owner's ticket.  Writes the per-group parameters (slot * 2 +
+// current half; 1/norm, base_f, pending update) into the tick block and points c.a at their device copies.
+bool DeviceDataset::Impl::stage_resident(LsCtx& c, const std::vector<LineGroup>& groups, bool* any_update_out) {
     Impl& m = *this;
     const TickStage& ts = c.ts;
+    LSArgs& a = c.a;
     const size_t G = groups.size();
     bool resident = G > 0, any_update = false;
     for (const LineGroup& lg : groups) {
@@ -2177,9 +2188,8 @@ bool DeviceDataset::Impl::stage_resident(const std::vector<LineGroup>& groups, L
         a.rs_par = c.td<double>(ts.o_par);
         a.rs_updf = c.td<uint32_t>(ts.o_updf);
     }
-    *resident_out = resident;
     *any_update_out = any_update;
-    return true;
+    return resident;
 }
 
 // m.eps2_host[g*64 + c] = 2 * eps_c, where eps_c bounds |approximate key - reference score| for every document
@@ -2236,6 +2246,21 @@ bool DeviceDataset::Impl::compute_eps2(const std::vector<LineGroup>& groups, boo
     return ok;
 }
 
+// the pending updates of staged groups [g_base, g_base + ng) where no verify kernel applies them
+bool DeviceDataset::Impl::update_resident(LsCtx& c, size_t g_base, size_t ng, std::string* err) {
+    Impl& m = *this;
+    LSArgs x = c.a;
+    x.g_base = (uint32_t)g_base;
+    x.posmap = m.posmap();
+    {
+        ProfScope ps("resident_update_kernel", c.stream);
+        resident_update_kernel<<<dim3((unsigned)((m.pos_threads() + 255) / 256), (unsigned)ng), 256, 0, c.stream>>>(x);
+    }
+    FR_HIP(hipGetLastError());
+    return true;
+}
+
+
 // after a launch that applied the pending updates: the updated sums are in the other half of their slot
 void DeviceDataset::Impl::flip_resident(const std::vector<LineGroup>& groups) {
     Impl& m = *this;
@@ -2280,12 +2305,6 @@ static unsigned redo_grid_env() {
     const char* e = frdev::path_env("FR_REDO_GRID");
     return e ? (unsigned)std::min<long>(std::max<long>(std::atol(e), 64), 1 << 20) : 0u;
 }
-#define REDO_GRID (redo_grid_env() ? redo_grid_env() : 8192u)
-
-bool DeviceDataset::linesearch_ndcg(int64_t depth, const double* norms, const std::vector<LineGroup>& groups,
-                                    std::vector<double>* means, std::string* err) {
-    return linesearch_ndcg_submit(0, depth, norms, groups, err) && linesearch_ndcg_collect(0, means, err);
-}
 
 // Chain runs per (document, group) visit (running mean of a restart) below which its R ranks stop being refreshed, and above
 // which they are again.  Measured (profiles/r06_rank_policy.txt; ranks kept / never made, and what keeping them is worth):
@@ -2315,466 +2334,6 @@ static void launch_verify(const LSArgs& a, bool resident, bool dupk, int xs, uns
         const dim3 grid((unsigned)(nruns8 * ((G + 1) / 2)));
         linesearch_verify_kernel<K, 2, false><<<grid, dim3(WAVE), 2 * dp * sizeof(double) + tab_lds, st>>>(a);
     }
-}
-
-bool DeviceDataset::linesearch_ndcg_submit(int ctx, int64_t depth, const double* norms, const std::vector<LineGroup>& groups_in,
-                                           std::string* err) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    if (ctx < 0 || ctx >= LS_CONTEXTS) {
-        if (err) *err = "linesearch_ndcg: no such context";
-        return false;
-    }
-    Impl::LsCtx& c = m.ls[ctx];
-    if (c.pending) {
-        if (err) *err = "linesearch_ndcg: context busy (collect the submitted line search first)";
-        return false;
-    }
-    if (!linesearch_supported(M_NDCG, depth)) {
-        if (err) *err = "linesearch_ndcg: unsupported depth, feature count or non-finite features";
-        return false;
-    }
-    const size_t G = groups_in.size();
-    c.ldm = G * 64;
-    c.depth = depth;
-    c.approx = false;
-    c.nverify = 0;
-    c.gorder.clear();
-    if (G == 0) {
-        c.pending = true;
-        return true;
-    }
-    const size_t dp = m.dq * 4;
-    size_t maxc = 0;
-    for (size_t g = 0; g < G; g++) {
-        const LineGroup& lg = groups_in[g];
-        if (lg.feature >= m.d || lg.weights.size() != m.d || lg.candidates.empty() || lg.candidates.size() > 64) {
-            if (err) *err = "linesearch_ndcg: malformed line group";
-            return false;
-        }
-        maxc = std::max(maxc, lg.candidates.size());
-    }
-    c.maxc = maxc;
-    const size_t ldm = c.ldm;
-    if (m.nq * G >= (size_t(1) << 28)) {  // (a redo entry is (q * G + g) * 16 + slice mask in 32 bits; M itself would be > 130 GB)
-        if (err) *err = "linesearch_ndcg: too many (query, group) pairs for one launch";
-        return false;
-    }
-    if (!c.M.ensure(m.nq * ldm, err) || !m.norms.ensure(m.nq, err) || !c.redo.ensure(m.nq * G, err)) return false;
-    {
-        // (a trainer's norms never change: its resident-sum ticket + the array's address stand for the contents, so the two
-        // 250 KB comparisons a tick used to make happen once.  Evaluator::norms must stay as it is for a trainer's lifetime.)
-        const uint64_t tok = groups_in[0].resident_owner;
-        if (!(tok != 0 && tok == m.norms_token && norms == m.norms_token_ptr)) {
-            const bool fresh = !(m.norms_cache.size() == m.nq && std::memcmp(m.norms_cache.data(), norms, m.nq * sizeof(double)) == 0);
-            if (!m.upload_norms(norms, err)) return false;
-            if (fresh) FR_HIP(hipStreamSynchronize(m.stream));  // uploaded on the main stream, read on the context's
-            m.norms_token = tok;
-            m.norms_token_ptr = norms;
-        }
-    }
-    // FR_LS_EXACT=1: the exact kernel only.  Otherwise bound-and-verify first (kernels_verify.inc): every (query, group)
-    // pair is evaluated from cheap approximate scores with a proven error bound, and what it could not decide is recomputed
-    // by the exact kernel.  Per-group routing: a restart whose last verified line search left more than a quarter of its
-    // pairs undecided (its weights make many scores tie exactly) sends its next few line searches straight to the exact
-    // kernel -- the other groups of the tick stay on the verify kernel.
-    const bool exact_only = std::getenv("FR_LS_EXACT") != nullptr;
-    const bool can_verify = !exact_only && m.colmax.size() == m.d && m.ncls <= 256;
-    size_t nV = can_verify ? G : 0;
-    const std::vector<LineGroup>* gp = &groups_in;
-    if (can_verify && m.res_owner != 0) {
-        std::vector<char> ex(G, 0);
-        size_t nE = 0;
-        for (size_t g = 0; g < G; g++) {
-            const LineGroup& lg = groups_in[g];
-            if (lg.resident_owner == m.res_owner && lg.resident_slot >= 0 && (size_t)lg.resident_slot < m.slot_exact_left.size() &&
-                m.slot_exact_left[lg.resident_slot] > 0) {
-                ex[g] = 1;
-                nE++;
-            }
-        }
-        if (nE > 0) {
-            // (once per distinct slot and tick: a restart with more than 64 candidates has several groups on one slot)
-            std::vector<char> seen(m.slot_exact_left.size(), 0);
-            for (size_t g = 0; g < G; g++) {
-                if (!ex[g]) continue;
-                const size_t slot = (size_t)groups_in[g].resident_slot;
-                if (seen[slot]) continue;
-                seen[slot] = 1;
-                if (m.slot_exact_left[slot] > 0) m.slot_exact_left[slot]--;
-            }
-            m.exact_groups += nE;
-            nV = G - nE;
-            if (nV > 0) {  // verify groups first, exact groups behind them; collect() puts the columns back
-                c.gorder.resize(G);
-                size_t iv = 0, ie = nV;
-                for (size_t g = 0; g < G; g++) c.gorder[ex[g] ? ie++ : iv++] = (uint32_t)g;
-                c.pgroups.clear();
-                for (size_t k = 0; k < G; k++) c.pgroups.push_back(groups_in[c.gorder[k]]);
-                gp = &c.pgroups;
-            }
-        }
-    }
-    const std::vector<LineGroup>& groups = *gp;
-    if (nV == 0) m.exact_fallbacks++;
-    if (!m.tick_begin(c, groups, err)) return false;
-    const Impl::TickStage& ts = c.ts;
-    LSArgs& a = c.a;
-    a = LSArgs{};
-    a.xb = (const float4*)m.xb.p;
-    a.gcls = m.gcls.p;
-    a.dcgtab = m.dcgtab.p;
-    a.qstart = m.qstart.p;
-    a.qlen = m.qlen.p;
-    a.run_q0 = m.run_q0.p;
-    a.run_q1 = m.run_q1.p;
-    a.run_pos = m.run_pos.p;
-    a.run_lo = m.run_lo.p;
-    a.run_docs = m.run_docs.p;
-    a.run_order = m.run_order.p;
-    a.wt_start = m.wt_start.p;
-    a.run_wt0 = m.run_wt0.p;
-    a.norms = m.norms.p;
-    a.disc = m.disc.p;
-    a.gfeat = c.td<uint32_t>(ts.o_gfeat);
-    a.gw = c.td<double>(ts.o_gw);
-    a.gcand = c.td<double>(ts.o_gcand);
-    a.gncand = c.td<uint32_t>(ts.o_gncand);
-    a.M = c.M.p;
-    a.flags = c.flags.p;
-    a.dbg_counters = m.dbgc.p;
-    a.dq = (uint32_t)m.dq;
-    a.d = (uint32_t)m.d;
-    a.nruns = (uint32_t)m.nruns;
-    a.G = (uint32_t)G;
-    a.ldm = (uint32_t)ldm;
-    a.depth = (int)depth;
-    a.ncls = (uint32_t)m.ncls;
-    static const int ls_debug = [] {  // FR_LS_DEBUG (timing ablations of the kernels: 1 = no phase K, 2 = no threshold filter, 16 = count rows)
-        const char* dbg = frdev::pricing_env("FR_LS_DEBUG");
-        return dbg ? atoi(dbg) : 0;
-    }();
-    LS_DEBUG_SET(a, ls_debug);
-    if (LS_DEBUG(a) & 16) FR_HIP(hipMemsetAsync(m.dbgc.p, 0, 4 * sizeof(unsigned long long), c.stream));
-    const size_t nruns8 = ((m.nruns + 7) / 8) * 8;
-    if (nruns8 * G > 0x7fffffffull) {
-        if (err) *err = "linesearch_ndcg: grid too large";
-        return false;
-    }
-    const size_t lds = 2 * dp * sizeof(double);
-    c.lds = lds;
-    bool approx = nV > 0 && (LS_DEBUG(a) & ~3) == 0;  // (debug 1/2: timing ablations)
-    const uint32_t cls_bits = m.key_bits;  // class bits + duplicate-group bits ride in the keys' low mantissa
-    a.cls_mask = (1u << cls_bits) - 1u;
-    a.cls_only_mask = (1u << m.key_cls_bits) - 1u;
-    a.gkey = m.gkey.p;
-    bool resident = false, any_update = false;
-    if (!m.stage_resident(groups, a, c, &resident, &any_update)) return false;
-    const bool dupk = resident && m.key_bits > m.key_cls_bits;  // duplicate groups with mixed gains exist: the DUP variants
-    if (approx) approx = m.compute_eps2(groups, resident, cls_bits, /*bare_admission=*/true, /*key_relative=*/true);
-    a.gamma = m.eps_gamma;
-    const size_t tab_lds = (m.ncls + 1) * (size_t)(LS_KT + 1) * sizeof(double);  // the verify kernel's rank-major copy of the DCG term table (+ a row of zeros)
-    // (sums from the tiles keep two groups' weights in LDS next to the table: a wide matrix with many gain classes does not fit)
-    if (approx && !resident && 2 * dp * sizeof(double) + tab_lds + 2 * (WAVE + 4) * sizeof(uint4) > 64 * 1024) approx = false;
-    if (!approx && nV > 0) {
-        // the verify launch turned out unusable (compute_eps2 refused the weights, the tables do not fit LDS): the exact kernel
-        // takes ALL staged groups -- the else-branch below with a.G = G, g_base = 0; if some were routed, collect() puts the
-        // columns back in the caller's order through gorder as it always does
-        m.exact_fallbacks++;
-        nV = 0;
-    }
-    // visiting order of the resident verify kernel (kernels_verify.inc): per group the |w_c - base_f| below which a
-    // candidate ranks like the current model -- where the spread its change of w_f adds, |delta| sigma_x(f), stays under the
-    // spread of the current scores, sqrt(sum_j (w_j sigma_j)^2) -- and the mode bits of columns with crowded extremes;
-    // the R ranks of a restart are redone after its first 1, 2, 4, 8 line searches and then every 16 (FR_RANK_PERIOD in a
-    // pricing build; a stale order only costs admissions: 16 against 8 is +1.4 % in the first 25 ticks of a job and level
-    // afterwards, profiles/r06_rank_policy.txt)
-    a.xslot = nullptr;
-    size_t nrank = 0;
-    if (approx && resident && m.xslot.p != nullptr && m.rslot.p != nullptr && m.colstd.size() == m.d) {
-        static const double kappa = [] {
-            const char* e = frdev::pricing_env("FR_ORDER_KAPPA");
-            return e ? std::atof(e) : 1.0;
-        }();
-        static const unsigned period = [] {
-            const char* e = frdev::pricing_env("FR_RANK_PERIOD");
-            return e ? (unsigned)std::max(1, std::atoi(e)) : 16u;
-        }();
-        double* gthr = c.th<double>(ts.o_gthr);
-        uint32_t* gmode = c.th<uint32_t>(ts.o_gmode);
-        int32_t* rank = c.th<int32_t>(ts.o_rank);
-        for (size_t g = 0; g < nV; g++) {
-            const LineGroup& lg = groups[g];
-            double var = 0.0;
-            for (size_t j = 0; j < m.d; j++) {
-                const double t = lg.weights[j] * m.colstd[j];
-                var += t * t;
-            }
-            const double sx = m.colstd[lg.feature];
-            gthr[g] = sx > 0.0 ? kappa * std::sqrt(var) / sx : std::numeric_limits<double>::infinity();
-            gmode[g] = m.colmode[lg.feature];
-            const size_t slot = (size_t)lg.resident_slot;
-            if (slot < m.slot_rank_age.size() && m.slot_rank_mode[slot] == 1) {
-                if (lg.has_update && m.slot_rank_upd[slot] < 0xFFFF) m.slot_rank_upd[slot]++;
-                // (ranks age only while the sums change: a restart that accepts nothing keeps its order)
-                // (a restart's first accepted steps move its model the most: ranks made from the initial sums are stale one line
-                // search later -- 0.32-0.34 chain runs per visit through ticks 1-7 of a job against 0.16-0.19 behind the first refresh,
-                // tools/chain_by_tick.py -- so the first refreshes come after 1, 2 and 4 line searches, then every `period`)
-                if (m.slot_rank_age[slot] == 0xFFFF || (m.slot_rank_age[slot] >= std::min<unsigned>(period, m.slot_rank_gap[slot]) && m.slot_rank_upd[slot] > 0)) {
-                    bool listed = false;  // (a restart with more than 64 candidates has several groups)
-                    for (size_t k = 0; k < nrank; k++) listed = listed || (rank[k] >> 1) == (int32_t)slot;
-                    if (!listed) {
-                        rank[G + nrank] = (int32_t)g;  // (rslot_kernel applies this group's pending update to the sums it ranks)
-                        rank[nrank++] = (int32_t)(slot * 2 + m.res_half[slot]);
-                    }
-                    m.slot_rank_upd[slot] = 0;  // (the ranks are made from the sums WITH this tick's pending update applied)
-                } else if (m.slot_rank_age[slot] < 0xFFFE) {
-                    m.slot_rank_age[slot]++;
-                }
-            }
-        }
-        for (size_t k = 0; k < nrank; k++) {
-            const size_t slot = (size_t)(rank[k] >> 1);
-            if (m.slot_rank_age[slot] != 0xFFFF && m.slot_rank_gap[slot] < 0x4000) m.slot_rank_gap[slot] *= 2;  // 1, 2, 4, ... line searches to the next refresh
-            m.slot_rank_age[slot] = 1;
-        }
-        a.xslot = m.xslot.p;
-        a.rslot = m.rslot.p;
-        a.gthr = c.td<double>(ts.o_gthr);
-        a.gmode = c.td<uint32_t>(ts.o_gmode);
-    }
-    if (!m.tick_upload(c, approx, err)) return false;
-    if (nrank > 0) {
-        ProfScope ps("rslot_kernel", c.stream);
-        const uint32_t* wl = m.nwlist ? m.wlist.p : nullptr;  // (a view ranks the walk tiles that hold its documents)
-        const unsigned nw = (unsigned)(m.nwlist ? m.nwlist : m.nwt);
-        rslot_kernel<<<dim3((nw + 3) / 4), 256, 0, c.stream>>>(m.res.p, c.td<int32_t>(ts.o_rank), c.td<int32_t>(ts.o_rank) + G, (uint32_t)nrank, a.rs_par,
-                                                              a.rs_updf, m.xcol.p, m.segtab.p, m.wt_start.p, wl, nw, (uint32_t)m.np, m.rslot.p);
-        FR_HIP(hipGetLastError());
-        if (std::getenv("FR_VERIFY_AUDIT")) {
-            // the permutation invariant of the tables this launch reads (kernels_order.inc): the R ranks just rewritten and
-            // the x_f ranks of the tick's features; an offending document counts as an audit mismatch
-            if (!m.audit_cnt.ensure(1, err)) return false;
-            FR_HIP(hipMemsetAsync(m.audit_cnt.p, 0, sizeof(unsigned long long), c.stream));
-            const int32_t* rk = c.th<int32_t>(ts.o_rank);
-            for (size_t k = 0; k < nrank; k++)
-                order_audit_kernel<<<dim3((nw + 3) / 4), 256, 0, c.stream>>>(m.rslot.p + (size_t)(rk[k] >> 1) * m.np, m.segtab.p, m.wt_start.p, wl, nw, m.audit_cnt.p);
-            for (size_t g = 0; g < nV; g++)
-                order_audit_kernel<<<dim3((nw + 3) / 4), 256, 0, c.stream>>>(m.xslot.p + (size_t)groups[g].feature * m.np, m.segtab.p, m.wt_start.p, wl, nw, m.audit_cnt.p);
-            unsigned long long bad = 0;
-            FR_HIP(hipMemcpyAsync(&bad, m.audit_cnt.p, sizeof(bad), hipMemcpyDeviceToHost, c.stream));
-            FR_HIP(hipStreamSynchronize(c.stream));
-            m.audit_mismatches += bad;
-        }
-    }
-    a.redo_count = c.td<unsigned long long>(ts.o_count);
-    a.redo_list = c.redo.p;
-    a.chain_count = c.td<uint32_t>(ts.o_gredo) + G;
-    if (approx) {
-        // keys kept per list: K + 1, or K + 2 / K + 3 once many pairs failed verification (tied clusters at the cut);
-        // FR_VERIFY_XS=1|2|3 pins it (tests)
-        const char* xs_e = frdev::path_env("FR_VERIFY_XS");
-        const int xs = std::min(xs_e ? std::atoi(xs_e) : m.verify_xs, depth <= 5 ? 3 : VERIFY_XS_MAX);
-        c.xs_used = xs;
-        c.xs_pinned = xs_e != nullptr;
-        a.eps2 = c.td<double>(ts.o_eps2);
-        a.G = (uint32_t)nV;  // (the verify launch and its redo list cover the first nV staged groups)
-        {
-            ProfScope ps("linesearch_verify_kernel", c.stream);
-            if (depth <= 5) launch_verify<5>(a, resident, dupk, xs, (unsigned)nruns8, nV, dp, tab_lds, c.stream);
-            else if (depth <= 10) launch_verify<10>(a, resident, dupk, xs, (unsigned)nruns8, nV, dp, tab_lds, c.stream);
-            else launch_verify<20>(a, resident, dupk, xs, (unsigned)nruns8, nV, dp, tab_lds, c.stream);
-        }
-        FR_HIP(hipGetLastError());
-        // the exact kernel on the redo list: a fixed-size grid whose blocks compare themselves with the count on the
-        // device, so the host does not wait here (a longer list is finished when the results are collected).  The grid
-        // follows the redo counts this context has seen (512 .. 8192 pairs): a short list wants a short grid -- every
-        // block, empty or not, needs a wave slot, and those are contested while another set's verify grid is dispatching --
-        // a long one (tie-heavy data) must not cost a second round trip
-        a.work_list = c.redo.p;
-        a.work_count = c.td<uint32_t>(ts.o_count);
-        a.slice_count = c.td<uint32_t>(ts.o_count) + 1;
-        {
-            ProfScope ps("linesearch_ndcg_kernel", c.stream);
-            c.redo_grid_used = redo_grid_env() ? redo_grid_env() : c.redo_grid;
-            dispatch_exact(a, depth, c.redo_grid_used, maxc, lds, c.stream);
-        }
-        if (nV < G) {  // the routed groups: the exact kernel over all their (run, group) pairs
-            LSArgs x = a;
-            x.work_list = nullptr;
-            x.work_count = nullptr;
-            x.g_base = (uint32_t)nV;
-            x.G = (uint32_t)(G - nV);
-            if (any_update) {  // (the verify kernel applies the pending resident updates of its own groups only)
-                ProfScope ps("resident_update_kernel", c.stream);
-                x.posmap = m.posmap();
-                resident_update_kernel<<<dim3((unsigned)((m.pos_threads() + 255) / 256), (unsigned)(G - nV)), 256, 0, c.stream>>>(x);
-            }
-            ProfScope ps("linesearch_ndcg_kernel", c.stream);
-            dispatch_exact(x, depth, (unsigned)(nruns8 * (G - nV)), maxc, lds, c.stream);
-        }
-    } else {
-        if (resident && any_update) {  // the verify kernel would have applied these
-            ProfScope ps("resident_update_kernel", c.stream);
-            a.posmap = m.posmap();
-            resident_update_kernel<<<dim3((unsigned)((m.pos_threads() + 255) / 256), (unsigned)G), 256, 0, c.stream>>>(a);
-        }
-        ProfScope ps("linesearch_ndcg_kernel", c.stream);
-        dispatch_exact(a, depth, (unsigned)(nruns8 * G), maxc, lds, c.stream);
-    }
-    FR_HIP(hipGetLastError());
-    if (!launch_means(c.M.p, ldm, ldm, m.nq, m.sums_only, c.partial, c.means, c.stream, err, c.td<unsigned long long>(ts.o_count), c.flags.p,
-                      m.tick_host_out(c, ldm, err), c.td<uint32_t>(ts.o_gredo)))
-        return false;
-    if (resident) m.flip_resident(groups);
-    c.gslot.assign(G, -1);
-    if (resident)
-        for (size_t k = 0; k < G; k++) c.gslot[k] = groups[k].resident_slot;
-    c.approx = approx;
-    c.nverify = approx ? nV : 0;
-    c.pending = true;
-    return true;
-}
-
-bool DeviceDataset::linesearch_ndcg_collect(int ctx, std::vector<double>* means, std::string* err) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    if (ctx < 0 || ctx >= LS_CONTEXTS || !m.ls[ctx].pending) {
-        if (err) *err = "linesearch_ndcg: nothing was submitted on this context";
-        return false;
-    }
-    Impl::LsCtx& c = m.ls[ctx];
-    c.pending = false;
-    const size_t ldm = c.ldm, G = ldm / 64;
-    means->assign(ldm, 0.0);
-    if (G == 0) return true;
-    uint32_t nredo = 0, nslices = 0;  // pairs listed; slices of them the first launch recomputed
-    std::vector<uint32_t>& by_group = c.gredo_h;
-    if (!m.tick_finish(c, ldm, means, &nredo, err, &nslices, &by_group)) return false;
-    LSArgs& a = c.a;  // (a.G = the groups of the verify launch)
-    if (c.approx) {
-        const size_t nV = c.nverify;
-        m.approx_pairs += m.nq * nV;
-        m.approx_redo += nredo;
-        const unsigned grid_used = c.redo_grid_used;
-        if (nredo > grid_used / 2) c.redo_grid = std::min(8192u, std::max(c.redo_grid, 512u) * 4u);
-        else if (nredo < grid_used / 16 && c.redo_grid > 512u) c.redo_grid /= 2u;
-        if (nredo > grid_used) {  // the rest of a long redo list, then the column results again
-            a.work_list = c.redo.p + grid_used;
-            a.work_count = nullptr;
-            {
-                ProfScope ps("linesearch_ndcg_kernel", c.stream);
-                dispatch_exact(a, c.depth, nredo - grid_used, c.maxc, c.lds, c.stream);
-            }
-            FR_HIP(hipGetLastError());
-            if (!launch_means(c.M.p, ldm, ldm, m.nq, m.sums_only, c.partial, c.means, c.stream, err, c.td<unsigned long long>(c.ts.o_count), c.flags.p,
-                              m.tick_host_out(c, ldm, err), c.td<uint32_t>(c.ts.o_gredo)))
-                return false;
-            uint32_t again = 0;
-            if (!m.tick_finish(c, ldm, means, &again, err, &nslices)) return false;
-        }
-        m.approx_redo_entries += nslices;
-        for (size_t k = 0; k < nV; k++) m.chain_runs += by_group[G + k];
-        m.chain_visits += (unsigned long long)m.n * nV;
-        {
-            // the restarts' running means of chain runs per visit, and the switch (see slot_rank_mode)
-            static const double t_off = [] {
-                const char* e = frdev::pricing_env("FR_RANK_OFF_BELOW");
-                return e ? std::atof(e) : RANK_OFF_BELOW;
-            }();
-            static const double t_on = [] {
-                const char* e = frdev::pricing_env("FR_RANK_ON_ABOVE");
-                return e ? std::atof(e) : RANK_ON_ABOVE;
-            }();
-            std::vector<double> runs(m.slot_rank_mode.size(), 0.0), visits(m.slot_rank_mode.size(), 0.0);
-            for (size_t k = 0; k < nV; k++) {
-                const int slot = c.gslot[k];
-                if (slot < 0 || (size_t)slot >= m.slot_rank_mode.size()) continue;
-                runs[slot] += (double)by_group[G + k];
-                visits[slot] += (double)m.n;
-            }
-            for (size_t slot = 0; slot < runs.size(); slot++) {
-                if (visits[slot] == 0.0) continue;
-                const double r = runs[slot] / visits[slot];
-                uint16_t& n = m.slot_rate_n[slot];
-                if (n < 16) n++;
-                m.slot_rate[slot] += (float)((r - (double)m.slot_rate[slot]) / (double)n);  // (plain mean up to 16, exponential from there)
-                if (n < 16) continue;
-                if (m.slot_rank_mode[slot] == 1 && (double)m.slot_rate[slot] < t_off) {
-                    m.slot_rank_mode[slot] = 2;
-                    m.rank_slots_off++;
-                } else if (m.slot_rank_mode[slot] == 2 && (double)m.slot_rate[slot] > t_on) {
-                    m.slot_rank_mode[slot] = 1;
-                    m.rank_slots_on++;
-                }
-            }
-        }
-        if (std::getenv("FR_VERIFY_AUDIT")) {
-            // audit: every value this line search published (verified, or recomputed from the redo list) against the
-            // exact kernel run over ALL (run, group) pairs -- bit for bit.  The exact kernel rewrites M with what must
-            // be the same numbers; the means were already formed from the published ones.
-            const size_t nel = m.nq * ldm;
-            if (!m.audit.ensure(nel, err) || !m.audit_cnt.ensure(1, err)) return false;
-            FR_HIP(hipMemcpyAsync(m.audit.p, c.M.p, nel * sizeof(double), hipMemcpyDeviceToDevice, c.stream));
-            LSArgs x = a;
-            x.work_list = nullptr;
-            x.work_count = nullptr;
-            x.g_base = 0;
-            x.G = (uint32_t)G;
-            dispatch_exact(x, c.depth, (unsigned)(((m.nruns + 7) / 8) * 8 * G), c.maxc, c.lds, c.stream);
-            FR_HIP(hipMemsetAsync(m.audit_cnt.p, 0, sizeof(unsigned long long), c.stream));
-            audit_compare_kernel<<<dim3(1024), dim3(256), 0, c.stream>>>(m.audit.p, c.M.p, nel, m.audit_cnt.p);
-            unsigned long long bad = 0;
-            FR_HIP(hipMemcpyAsync(&bad, m.audit_cnt.p, sizeof(bad), hipMemcpyDeviceToHost, c.stream));
-            FR_HIP(hipStreamSynchronize(c.stream));
-            m.audit_values += nel;
-            m.audit_mismatches += bad;
-        }
-        // tie-heavy data (more than 0.4 % of the pairs redone -- a redone pair costs ~12 verified ones, a longer list ~4 % of
-        // the kernel): first keep more keys per list (up to K + 4), so that tied clusters of one
-        // gain class may straddle the cut (raised only; a new trainer starts one below the last one's; launches already in flight used
-        // the old length).  With the longest lists (or a pinned length), a restart whose line search still left more than
-        // a quarter of its pairs undecided -- its weights make scores tie exactly -- sends its next 4 / 8 / 16 line
-        // searches to the exact kernel (doubled while the verify kernel keeps failing on it, halved when it succeeds).
-        size_t total = 0;
-        for (size_t k = 0; k < nV; k++) total += by_group[k];
-        if (total * 250 > m.nq * nV && c.xs_used < (c.depth <= 5 ? 3 : VERIFY_XS_MAX) && !c.xs_pinned) {
-            if (m.verify_xs <= c.xs_used) m.verify_xs = c.xs_used + 1;
-        } else if (LS_DEBUG(a) == 0) {
-            // (per distinct slot: 1 = seen, 2 = one of its groups left more than a quarter of its pairs undecided)
-            std::vector<char> verdict(m.slot_backoff.size(), 0);
-            for (size_t k = 0; k < nV; k++) {
-                const int slot = c.gslot[k];
-                if (slot < 0 || (size_t)slot >= m.slot_backoff.size()) continue;
-                verdict[slot] |= (char)(((size_t)by_group[k] * 4 > m.nq) ? 3 : 1);
-            }
-            for (size_t slot = 0; slot < verdict.size(); slot++) {
-                if (verdict[slot] & 2) {
-                    m.slot_backoff[slot] = (uint8_t)std::min<unsigned>(16u, std::max<unsigned>(4u, m.slot_backoff[slot] * 2u));
-                    m.slot_exact_left[slot] = m.slot_backoff[slot];
-                } else if (verdict[slot]) {
-                    m.slot_backoff[slot] = (uint8_t)(m.slot_backoff[slot] / 2u);
-                }
-            }
-        }
-    }
-    if (!c.gorder.empty()) {  // routed groups were staged behind the others: columns back in the caller's order
-        std::vector<double> tmp(*means);
-        for (size_t k = 0; k < G; k++) std::memcpy(means->data() + (size_t)c.gorder[k] * 64, tmp.data() + k * 64, 64 * sizeof(double));
-    }
-    m.last_ldm = ldm;
-    m.last_cols = ldm;
-    m.last_M = c.M.p;  // (per-query inspection is for stateless callers, whose groups are never routed)
-    if (LS_DEBUG(a) & 16) {
-        unsigned long long cnt[4];
-        FR_HIP(hipMemcpyAsync(cnt, m.dbgc.p, sizeof(cnt), hipMemcpyDeviceToHost, c.stream));
-        FR_HIP(hipStreamSynchronize(c.stream));
-        fprintf(stderr, "[FR_LS_DEBUG] docs=%llu rows=%llu (%.3f of docs) batches=%llu insertion_rows=%llu\n", cnt[3], cnt[0],
-                (double)cnt[0] / (double)cnt[3], cnt[1], cnt[2]);
-    }
-    return true;
 }
 
 uint64_t DeviceDataset::resident_reserve(size_t slots, std::string* err) {
@@ -2841,12 +2400,6 @@ bool DeviceDataset::resident_store_from_scores(uint64_t owner, size_t slot, size
 
 const std::vector<double>& DeviceDataset::column_absmax() const { return impl_->colmax; }
 
-void DeviceDataset::verify_counters(unsigned long long* pairs, unsigned long long* redone) const {
-    std::lock_guard<std::mutex> lk(impl_->mu);
-    *pairs = impl_->approx_pairs;
-    *redone = impl_->approx_redo;
-}
-
 void DeviceDataset::audit_counters(unsigned long long* values, unsigned long long* mismatches) const {
     std::lock_guard<std::mutex> lk(impl_->mu);
     *values = impl_->audit_values;
@@ -2873,196 +2426,60 @@ void DeviceDataset::routing_counters(unsigned long long* exact_groups, unsigned 
     *redo_entries = impl_->approx_redo_entries;
 }
 
-bool DeviceDataset::fullrank_supported(int measure, int64_t depth) const {
-    const Impl& m = *impl_;
-    (void)depth;
-    if (m.nonfinite || m.dq * 4 > 2048) return false;
-    if (m.maxlen > 2048) return false;                       // per-lane rank table must fit LDS (64 B per rank)
-    if (measure == M_NDCG && m.termtab.cap < m.ncls * m.tablen) return false;  // too many gain classes
-    return measure == M_NDCG || measure == M_AP || measure == M_RR;
+static void launch_scores(const FSArgs& a, size_t maxc, unsigned nblocks, size_t lds, hipStream_t st) {
+    if (maxc <= 16) linesearch_scores_kernel<16, 16><<<dim3(nblocks), dim3(WAVE), lds, st>>>(a);
+    else if (maxc <= 51) linesearch_scores_kernel<51, 16><<<dim3(nblocks), dim3(WAVE), lds, st>>>(a);
+    else linesearch_scores_kernel<64, 16><<<dim3(nblocks), dim3(WAVE), lds, st>>>(a);
 }
 
-template <int CT>
-static void launch_scores(const FSArgs& a, unsigned nblocks, size_t lds, hipStream_t st) {
-    linesearch_scores_kernel<CT, 16><<<dim3(nblocks), dim3(WAVE), lds, st>>>(a);
+// arguments of the exact full-ranking kernels (kernels_fullrank.inc): the chunked evaluation's, and the redo list's of the
+// full-ranking verify kernel (work-list mode)
+FSArgs DeviceDataset::Impl::scores_args(const uint32_t* gf, const double* w, const double* cand, double* rows, int* fl, size_t gc) const {
+    FSArgs a{};
+    a.xb = (const float4*)xb.p;
+    a.run_pos = run_pos.p;
+    a.run_docs = run_docs.p;
+    a.run_order = run_order.p;
+    a.gfeat = gf;
+    a.gw = w;
+    a.gcand = cand;
+    a.rows = rows;
+    a.flags = fl;
+    a.dq = (uint32_t)dq;
+    a.d = (uint32_t)d;
+    a.nruns = (uint32_t)nruns;
+    a.GC = (uint32_t)gc;
+    a.np = (uint32_t)np;
+    return a;
 }
 
-// Reciprocal rank by bound-and-verify on context c (its stream, tick block, result matrix): queues everything up to
-// the copies back.  *queued = false: not applicable (no resident sums / bound unusable / exact-only ticks) -- pending
-// resident updates have been applied and the caller uses the exact kernels.
-bool DeviceDataset::Impl::rr_launch(LsCtx& c, const std::vector<LineGroup>& groups, bool* queued, std::string* err) {
-    Impl& m = *this;
-    *queued = false;
-    const size_t G = groups.size();
-    if (G == 0 || std::getenv("FR_LS_EXACT") != nullptr || m.colmax.size() != m.d) return true;
-    if (!m.tick_begin(c, groups, err)) return false;
-    const Impl::TickStage& ts = c.ts;
-    LSArgs la{};  // carrier for the resident parameters
-    bool resident = false, any_update = false;
-    if (!m.stage_resident(groups, la, c, &resident, &any_update)) return false;
-    if (!resident) return true;
-    bool approx = m.compute_eps2(groups, true, 0);
-    if (approx && m.approx_skip > 0) {
-        m.approx_skip--;
-        m.exact_fallbacks++;
-        approx = false;
-    }
-    if (!m.tick_upload(c, approx, err)) return false;
-    if (!approx) {  // the exact kernels run instead: keep the resident sums current
-        if (any_update) {
-            la.xb = (const float4*)m.xb.p;
-            la.dq = (uint32_t)m.dq;
-            la.posmap = m.posmap();
-            resident_update_kernel<<<dim3((unsigned)((m.pos_threads() + 255) / 256), (unsigned)G), 256, 0, c.stream>>>(la);
-            FR_HIP(hipGetLastError());
-            m.flip_resident(groups);
-        }
-        FR_HIP(hipStreamSynchronize(c.stream));  // the tick block is reused by the next call; the exact kernels use the main stream
-        return true;
-    }
-    const size_t ldm = G * 64;
-    c.ldm = ldm;
-    if (!c.M.ensure(m.nq * ldm, err) || !c.means.ensure(ldm + mean_tail_words(ldm), err) || !c.redo.ensure(m.nq * G, err)) return false;
-    RRArgs& ra = c.ra;
-    ra = RRArgs{};
-    ra.xb = (const float4*)m.xb.p;
-    ra.qstart = m.qstart.p;
-    ra.qlen = m.qlen.p;
-    ra.qnpos = m.qnpos.p;
-    ra.gfeat = c.td<uint32_t>(ts.o_gfeat);
-    ra.gw = c.td<double>(ts.o_gw);
-    ra.gcand = c.td<double>(ts.o_gcand);
-    ra.gncand = c.td<uint32_t>(ts.o_gncand);
-    ra.eps2 = c.td<double>(ts.o_eps2);
-    ra.redo_count = c.td<uint32_t>(ts.o_count);
-    ra.redo_list = c.redo.p;
-    ra.work_list = nullptr;
-    ra.work_count = nullptr;
-    ra.res_cur = m.res.p;
-    ra.rs_slot = la.rs_slot;
-    ra.rs_par = la.rs_par;
-    ra.rs_updf = la.rs_updf;
-    ra.xcol = la.xcol;
-    ra.M = c.M.p;
-    ra.flags = c.flags.p;
-    ra.G = (uint32_t)G;
-    ra.ldm = (uint32_t)ldm;
-    ra.dq = (uint32_t)m.dq;
-    ra.d = (uint32_t)m.d;
-    ra.np = (uint32_t)m.np;
-    {
-        ProfScope ps("rr_verify_kernel", c.stream);
-        FR_HIP(hipFuncSetAttribute((const void*)rr_verify_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-        for (size_t ci = m.size_classes.size(); ci-- > 0;) {
-            const auto& sc = m.size_classes[ci];
-            ra.qlist = m.qlist.p + sc.offset;
-            rr_verify_kernel<<<dim3((unsigned)sc.count, (unsigned)G), WAVE, (size_t)sc.npad * sizeof(uint4), c.stream>>>(ra);
-        }
-    }
-    FR_HIP(hipGetLastError());
-    m.flip_resident(groups);
-    // exact recomputation of the redo list: fixed-size grid against the device-side count (see linesearch_ndcg_submit)
-    ra.work_list = c.redo.p;
-    ra.work_count = c.td<uint32_t>(ts.o_count);
-    {
-        ProfScope ps("rr_exact_kernel", c.stream);
-        rr_exact_kernel<<<dim3(REDO_GRID), WAVE, m.d * sizeof(double), c.stream>>>(ra);
-    }
-    FR_HIP(hipGetLastError());
-    if (!launch_means(c.M.p, ldm, ldm, m.nq, m.sums_only, c.partial, c.means, c.stream, err, c.td<uint32_t>(c.ts.o_count), c.flags.p, m.tick_host_out(c, ldm, err))) return false;
-    *queued = true;
-    return true;
-}
-
-// waits for what rr_launch queued on c and returns the column results (the rest of a long redo list first)
-bool DeviceDataset::Impl::rr_finish(LsCtx& c, std::vector<double>* means, std::string* err) {
-    Impl& m = *this;
-    const size_t ldm = c.ldm, G = ldm / 64;
-    means->assign(ldm, 0.0);
-    uint32_t nredo = 0;
-    if (!m.tick_finish(c, ldm, means, &nredo, err)) return false;
-    m.approx_pairs += m.nq * G;
-    m.approx_redo += nredo;
-    if (nredo > REDO_GRID) {
-        RRArgs& ra = c.ra;
-        ra.work_list = c.redo.p + REDO_GRID;
-        ra.work_count = nullptr;
-        {
-            ProfScope ps("rr_exact_kernel", c.stream);
-            rr_exact_kernel<<<dim3(nredo - REDO_GRID), WAVE, m.d * sizeof(double), c.stream>>>(ra);
-        }
-        FR_HIP(hipGetLastError());
-        if (!launch_means(c.M.p, ldm, ldm, m.nq, m.sums_only, c.partial, c.means, c.stream, err, c.td<uint32_t>(c.ts.o_count), c.flags.p, m.tick_host_out(c, ldm, err))) return false;
-        uint32_t again = 0;
-        if (!m.tick_finish(c, ldm, means, &again, err)) return false;
-    }
-    if ((size_t)nredo * 4 > m.nq * G) m.approx_skip = 16;
-    m.last_ldm = ldm;
-    m.last_cols = ldm;
-    m.last_M = c.M.p;
-    return true;
-}
-
-// lock-step form (linesearch_fullrank): its own context on the main stream
-bool DeviceDataset::Impl::linesearch_rr_verify(const std::vector<LineGroup>& groups, std::vector<double>* means, bool* done,
-                                               std::string* err) {
-    Impl& m = *this;
-    Impl::LsCtx& c = m.ls[LS_CONTEXTS];
-    c.stream = m.stream;
-    *done = false;
-    bool queued = false;
-    if (!m.rr_launch(c, groups, &queued, err)) return false;
-    if (!queued) return true;
-    if (!m.rr_finish(c, means, err)) return false;
-    *done = true;
-    return true;
-}
-
-bool DeviceDataset::linesearch_rr_submit(int ctx, const std::vector<LineGroup>& groups, bool* queued, std::string* err) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    *queued = false;
-    if (ctx < 0 || ctx >= LS_CONTEXTS || m.ls[ctx].pending) {
-        if (err) *err = "linesearch_rr: no such context, or a submitted line search was not collected";
-        return false;
-    }
-    if (!fullrank_supported(M_RR, -1) || m.maxlen > 8192) return true;
-    for (const auto& lg : groups)
-        if (lg.feature >= m.d || lg.weights.size() != m.d || lg.candidates.empty() || lg.candidates.size() > 64) {
-            if (err) *err = "linesearch_rr: malformed line group";
-            return false;
-        }
-    if (!m.rr_launch(m.ls[ctx], groups, queued, err)) return false;
-    m.ls[ctx].pending = *queued;
-    return true;
-}
-
-bool DeviceDataset::linesearch_rr_collect(int ctx, std::vector<double>* means, std::string* err) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    if (ctx < 0 || ctx >= LS_CONTEXTS || !m.ls[ctx].pending) {
-        if (err) *err = "linesearch_rr: nothing was submitted on this context";
-        return false;
-    }
-    m.ls[ctx].pending = false;
-    return m.rr_finish(m.ls[ctx], means, err);
+RMArgs DeviceDataset::Impl::rank_args(const double* rows, const uint32_t* gnc, double* out, int* fl, size_t gc, size_t ldm, int measure,
+                                      int64_t depth) const {
+    RMArgs a{};
+    a.rows = rows;
+    a.qstart = qstart.p;
+    a.qlen = qlen.p;
+    a.qnpos = qnpos.p;
+    a.qnneg = qnneg.p;
+    a.gcls = gcls.p;
+    a.termtab = termtab.p;
+    a.norms = norms.p;
+    a.gncand = gnc;
+    a.M = out;
+    a.flags = fl;
+    a.GC = (uint32_t)gc;
+    a.np = (uint32_t)np;
+    a.ldm = (uint32_t)ldm;
+    a.tablen = (uint32_t)tablen;
+    a.measure = measure;
+    a.depth = depth < 0 ? -1 : (depth > 0x7fffffff ? 0x7fffffff : (int)depth);
+    return a;
 }
 
 // ---- NDCG of any depth / AP by bound-and-verify (kernels_fullverify.inc) -------------------------------------
 
 // (query, group) pairs of the redo list the exact kernels take per launch: each block owns one slot of score rows
 static constexpr unsigned FV_REDO_GRID = 1024;
-
-bool DeviceDataset::Impl::fv_usable(int measure) const {
-    const Impl& m = *this;
-    if (std::getenv("FR_LS_EXACT") != nullptr || frdev::path_env("FR_FV_OFF") != nullptr) return false;
-    if (m.nonfinite || m.dq * 4 > 2048 || m.maxlen > 2048 || m.colmax.size() != m.d || m.ncls > 256) return false;
-    if (measure == M_NDCG) return m.termtab.cap >= m.ncls * m.tablen && m.termtab.cap > 0;
-    if (measure == M_AP) return m.ncls <= 31;  // (relevance of a class: one bit of a 32-bit mask, the padding class included)
-    return false;
-}
 
 // One size class: workgroups of FV_BLOCK_WAVES waves, each walking a slice of the class's queries for one line group
 // in batches of qb queries (kernels_fullverify.inc).  qb is chosen so that qb * ncand candidates fill whole sorting
@@ -3147,297 +2564,536 @@ static bool fv_launch_class(FVArgs a, int ci, unsigned nqueries, unsigned G, uns
 #ifndef FV_REDO_WAVES
 #define FV_REDO_WAVES 4  // waves per redone (query, group); 8 measured the same (tools/ab/rf_md.sh)
 #endif
-// the exact kernels (kernels_fullrank.inc, work-list mode) on `nblocks` entries of a redo list
-bool DeviceDataset::Impl::fv_redo_launch(LsCtx& c, const uint32_t* list, const uint32_t* count_dev, unsigned nblocks,
-                                         std::string* err) {
+// The exact kernels on n entries of the context's redo list from entry `off` on.  count_dev: the device-side count of the
+// list, which the blocks of the fixed-size first launch compare themselves with (the host does not wait for it); nullptr
+// for the rest of a long list.
+bool DeviceDataset::Impl::redo_launch(LsCtx& c, uint32_t off, const uint32_t* count_dev, uint32_t n, std::string* err) {
     Impl& m = *this;
-    if (nblocks == 0) return true;
-    FSArgs fs = c.fsa;
-    fs.work_list = list;
-    fs.work_count = count_dev;
-    RMArgs rm = c.rma;
-    rm.work_list = list;
-    rm.work_count = count_dev;
-    {
-        ProfScope ps("linesearch_scores_kernel", c.stream);
-        const size_t lds = 2 * m.dq * 4 * sizeof(double);
-        if (c.maxc <= 16) linesearch_scores_kernel<16, 16><<<dim3(nblocks), dim3(WAVE), lds, c.stream>>>(fs);
-        else if (c.maxc <= 51) linesearch_scores_kernel<51, 16><<<dim3(nblocks), dim3(WAVE), lds, c.stream>>>(fs);
-        else linesearch_scores_kernel<64, 16><<<dim3(nblocks), dim3(WAVE), lds, c.stream>>>(fs);
-    }
-    FR_HIP(hipGetLastError());
-    {
-        ProfScope ps("rank_metric_kernel", c.stream);
-        FR_HIP(hipFuncSetAttribute((const void*)rank_metric_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-        const size_t npad_max = m.size_classes.empty() ? 64 : m.size_classes.back().npad;
-        rank_metric_kernel<<<dim3(nblocks), WAVE * FV_REDO_WAVES, npad_max * 64, c.stream>>>(rm);
+    switch (c.kind) {
+        case LSK_TOPK: {
+            c.a.work_list = c.redo.p + off;
+            c.a.work_count = count_dev;
+            ProfScope ps("linesearch_ndcg_kernel", c.stream);
+            dispatch_exact(c.a, c.depth, n, c.maxc, c.lds, c.stream);
+            break;
+        }
+        case LSK_RR: {
+            c.ra.work_list = c.redo.p + off;
+            c.ra.work_count = count_dev;
+            ProfScope ps("rr_exact_kernel", c.stream);
+            rr_exact_kernel<<<dim3(n), WAVE, m.d * sizeof(double), c.stream>>>(c.ra);
+            break;
+        }
+        case LSK_FV:  // the scores kernel, then the rank-counting kernel; a block owns one slot of score rows: FV_REDO_GRID at a time
+            for (uint32_t k = 0; k < n; k += FV_REDO_GRID) {
+                const uint32_t nb = std::min(FV_REDO_GRID, n - k);
+                FSArgs fs = c.fsa;
+                fs.work_list = c.redo.p + off + k;
+                fs.work_count = count_dev;
+                RMArgs rm = c.rma;
+                rm.work_list = fs.work_list;
+                rm.work_count = count_dev;
+                {
+                    ProfScope ps("linesearch_scores_kernel", c.stream);
+                    launch_scores(fs, c.maxc, nb, 2 * m.dq * 4 * sizeof(double), c.stream);
+                }
+                FR_HIP(hipGetLastError());
+                ProfScope ps("rank_metric_kernel", c.stream);
+                FR_HIP(hipFuncSetAttribute((const void*)rank_metric_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+                const size_t npad_max = m.size_classes.empty() ? 64 : m.size_classes.back().npad;
+                rank_metric_kernel<<<dim3(nb), WAVE * FV_REDO_WAVES, npad_max * 64, c.stream>>>(rm);
+            }
+            break;
     }
     FR_HIP(hipGetLastError());
     return true;
 }
 
-// Queues one line search of NDCG / AP on context c (its stream, tick block, result matrix) up to the copies back.
-// *queued = false: not applicable right now (the bound is unusable, or exact-only ticks after many redos) -- pending
-// resident updates have been applied and the caller uses the exact kernels.
-bool DeviceDataset::Impl::fv_launch(LsCtx& c, int measure, int64_t depth, const double* norms,
-                                    const std::vector<LineGroup>& groups, bool* queued, std::string* err) {
+// ---- the line-search driver ----------------------------------------------------------------------------------------
+// submit: validate, stage the groups and their resident parameters in the tick block, bound the error, then queue the verify
+// kernel and a fixed-size first launch of the exact kernels on its redo list -- or, where bound-and-verify does not apply,
+// the exact kernels alone.  collect: wait, finish a long redo list, count, and set the policies that steer the next line
+// searches.  The three verify kernels differ only in the switches on c.kind.
+
+static constexpr unsigned RR_REDO_GRID = 8192;  // reciprocal rank: redo-list pairs the exact kernel's first launch takes
+
+bool DeviceDataset::Impl::ls_submit(LsCtx& c, int path, int measure, int64_t depth, const double* norms,
+                                    const std::vector<LineGroup>& groups_in, std::string* err) {
     Impl& m = *this;
-    *queued = false;
-    const size_t G = groups.size();
-    if (G == 0 || !m.fv_usable(measure)) return true;
-    size_t maxc = 0;
-    for (const auto& lg : groups) maxc = std::max(maxc, lg.candidates.size());
-    const size_t slot_rows = ((m.maxlen + 63) / 64 + 1) * 64;
-    if (!m.norms.ensure(m.nq, err) || !c.fv_rows.ensure((size_t)FV_REDO_GRID * slot_rows * 64, err)) return false;
-    {
-        const bool fresh = !(m.norms_cache.size() == m.nq && std::memcmp(m.norms_cache.data(), norms, m.nq * sizeof(double)) == 0);
-        if (!m.upload_norms(norms, err)) return false;
-        if (fresh) FR_HIP(hipStreamSynchronize(m.stream));  // uploaded on the main stream, read on the context's
+    if (path == LS_NONE) {
+        if (err) *err = "linesearch: unsupported measure, depth or dataset (the general sort evaluator takes it)";
+        return false;
     }
+    const size_t G = groups_in.size();
+    size_t maxc = 0;
+    for (const LineGroup& lg : groups_in) {
+        if (lg.feature >= m.d || lg.weights.size() != m.d || lg.candidates.empty() || lg.candidates.size() > 64) {
+            if (err) *err = "linesearch: malformed line group";
+            return false;
+        }
+        maxc = std::max(maxc, lg.candidates.size());
+    }
+    if (&c == &m.ls[LS_CONTEXTS]) c.stream = m.stream;
+    c.kind = path == LS_TOPK ? LSK_TOPK : (measure == M_RR ? LSK_RR : LSK_FV);
+    c.ldm = G * 64;
+    c.maxc = maxc;
+    c.depth = depth;
+    c.approx = c.ready = false;
+    c.nverify = 0;
+    c.gorder.clear();
+    c.counts = LsCounts{};
+    if (G == 0) {
+        c.pending = true;
+        return true;
+    }
+    const size_t ldm = c.ldm, dp = m.dq * 4, nruns8 = ((m.nruns + 7) / 8) * 8;
+    if (c.kind == LSK_TOPK) {
+        if (m.nq * G >= (size_t(1) << 28)) {  // (a redo entry is (q * G + g) * 16 + slice mask in 32 bits; M itself would be > 130 GB)
+            if (err) *err = "linesearch: too many (query, group) pairs for one launch";
+            return false;
+        }
+        if (!c.M.ensure(m.nq * ldm, err) || !c.redo.ensure(m.nq * G, err)) return false;
+    }
+    // FR_LS_EXACT=1: the exact kernels only
+    const bool exact_only = std::getenv("FR_LS_EXACT") != nullptr;
+    c.audit = std::getenv("FR_VERIFY_AUDIT") != nullptr;
+    const unsigned redo_pin = redo_grid_env();
+    bool can_verify = !exact_only && m.colmax.size() == m.d;
+    switch (c.kind) {
+        case LSK_TOPK: can_verify = can_verify && m.ncls <= 256; break;
+        case LSK_RR: break;
+        case LSK_FV:  // (AP: the relevance of a class is one bit of a 32-bit mask, the padding class included)
+            can_verify = can_verify && frdev::path_env("FR_FV_OFF") == nullptr && m.ncls <= 256 &&
+                         (measure == M_NDCG ? m.termtab.cap > 0 : m.ncls <= 31);
+            break;
+    }
+    if (!can_verify && c.kind != LSK_TOPK) return m.ls_exact(c, measure, depth, norms, groups_in, err);
+    if (c.kind != LSK_RR) {
+        // (a trainer's norms never change: its resident-sum ticket + the array's address stand for the contents, so the two
+        // 250 KB comparisons a tick used to make happen once.  Evaluator::norms must stay as it is for a trainer's lifetime.)
+        if (!m.norms.ensure(m.nq, err)) return false;
+        const uint64_t tok = groups_in[0].resident_owner;
+        if (!(tok != 0 && tok == m.norms_token && norms == m.norms_token_ptr)) {
+            const bool fresh = !(m.norms_cache.size() == m.nq && std::memcmp(m.norms_cache.data(), norms, m.nq * sizeof(double)) == 0);
+            if (!m.upload_norms(norms, err)) return false;
+            if (fresh) FR_HIP(hipStreamSynchronize(m.stream));  // uploaded on the main stream, read on the context's
+            m.norms_token = tok;
+            m.norms_token_ptr = norms;
+        }
+    }
+    // Top-k, per-group routing: a restart whose last verified line search left more than a quarter of its pairs undecided
+    // (its weights make many scores tie exactly) sends its next few line searches straight to the exact kernel -- the other
+    // groups of the tick stay on the verify kernel.
+    size_t nV = can_verify ? G : 0;  // groups the verify kernel takes (staged first)
+    const std::vector<LineGroup>* gp = &groups_in;
+    if (c.kind == LSK_TOPK && can_verify && m.res_owner != 0) {
+        std::vector<char> ex(G, 0);
+        size_t nE = 0;
+        for (size_t g = 0; g < G; g++) {
+            const LineGroup& lg = groups_in[g];
+            if (lg.resident_owner == m.res_owner && lg.resident_slot >= 0 && (size_t)lg.resident_slot < m.slot_exact_left.size() &&
+                m.slot_exact_left[lg.resident_slot] > 0) {
+                ex[g] = 1;
+                nE++;
+            }
+        }
+        if (nE > 0) {
+            // (once per distinct slot and tick: a restart with more than 64 candidates has several groups on one slot)
+            std::vector<char> seen(m.slot_exact_left.size(), 0);
+            for (size_t g = 0; g < G; g++) {
+                if (!ex[g]) continue;
+                const size_t slot = (size_t)groups_in[g].resident_slot;
+                if (seen[slot]) continue;
+                seen[slot] = 1;
+                if (m.slot_exact_left[slot] > 0) m.slot_exact_left[slot]--;
+            }
+            m.exact_groups += nE;
+            nV = G - nE;
+            if (nV > 0) {  // verify groups first, exact groups behind them; collect() puts the columns back
+                c.gorder.resize(G);
+                size_t iv = 0, ie = nV;
+                for (size_t g = 0; g < G; g++) c.gorder[ex[g] ? ie++ : iv++] = (uint32_t)g;
+                c.pgroups.clear();
+                for (size_t k = 0; k < G; k++) c.pgroups.push_back(groups_in[c.gorder[k]]);
+                gp = &c.pgroups;
+            }
+        }
+    }
+    const std::vector<LineGroup>& groups = *gp;
+    if (c.kind == LSK_TOPK && nV == 0) m.exact_fallbacks++;
     if (!m.tick_begin(c, groups, err)) return false;
-    const Impl::TickStage& ts = c.ts;
-    LSArgs la{};  // carrier for the resident parameters
-    bool resident = false, any_update = false;
-    if (!m.stage_resident(groups, la, c, &resident, &any_update)) return false;
-    uint32_t cls_bits = 0;
-    while ((size_t(1) << cls_bits) < m.ncls + 1) cls_bits++;  // (+1: the padding class)
-    // duplicate groups with mixed gain classes (found at upload): the DUP instantiations carry the group id in the keys behind
-    // the class and decide pairs of one group by the reference's tie-break (kernels_fullverify.inc)
-    const uint32_t dup_bits = (m.key_bits > m.key_cls_bits && cls_bits + (m.key_bits - m.key_cls_bits) <= 20) ? m.key_bits - m.key_cls_bits : 0u;
-    bool approx = m.compute_eps2(groups, resident, cls_bits + dup_bits);
-    if (approx && m.approx_skip > 0) {
+    const TickStage& ts = c.ts;
+    LSArgs& a = c.a;
+    a = LSArgs{};
+    bool any_update = false;
+    const bool resident = m.stage_resident(c, groups, &any_update);
+    // the error bound of the approximate scores (false: unusable, the exact kernels take the line search)
+    bool approx = false;
+    uint32_t cls_bits = 0, dup_bits = 0;  // full ranking: low key bits of the gain class / duplicate group
+    size_t nrank = 0;                     // top-k: resident slots whose R ranks this tick refreshes
+    switch (c.kind) {
+        case LSK_TOPK: {
+            a.xb = (const float4*)m.xb.p;
+            a.gcls = m.gcls.p;
+            a.dcgtab = m.dcgtab.p;
+            a.qstart = m.qstart.p;
+            a.qlen = m.qlen.p;
+            a.run_q0 = m.run_q0.p;
+            a.run_q1 = m.run_q1.p;
+            a.run_pos = m.run_pos.p;
+            a.run_lo = m.run_lo.p;
+            a.run_docs = m.run_docs.p;
+            a.run_order = m.run_order.p;
+            a.wt_start = m.wt_start.p;
+            a.run_wt0 = m.run_wt0.p;
+            a.norms = m.norms.p;
+            a.disc = m.disc.p;
+            a.gfeat = c.td<uint32_t>(ts.o_gfeat);
+            a.gw = c.td<double>(ts.o_gw);
+            a.gcand = c.td<double>(ts.o_gcand);
+            a.gncand = c.td<uint32_t>(ts.o_gncand);
+            a.M = c.M.p;
+            a.flags = c.flags.p;
+            a.dbg_counters = m.dbgc.p;
+            a.dq = (uint32_t)m.dq;
+            a.d = (uint32_t)m.d;
+            a.nruns = (uint32_t)m.nruns;
+            a.G = (uint32_t)G;
+            a.ldm = (uint32_t)ldm;
+            a.depth = (int)depth;
+            a.ncls = (uint32_t)m.ncls;
+            a.redo_count = c.td<unsigned long long>(ts.o_count);
+            a.redo_list = c.redo.p;
+            a.chain_count = c.td<uint32_t>(ts.o_gredo) + G;
+            static const int ls_debug = [] {  // FR_LS_DEBUG (timing ablations of the kernels: 1 = no phase K, 2 = no threshold filter, 16 = count rows)
+                const char* dbg = frdev::pricing_env("FR_LS_DEBUG");
+                return dbg ? atoi(dbg) : 0;
+            }();
+            LS_DEBUG_SET(a, ls_debug);
+            if (LS_DEBUG(a) & 16) FR_HIP(hipMemsetAsync(m.dbgc.p, 0, 4 * sizeof(unsigned long long), c.stream));
+            if (nruns8 * G > 0x7fffffffull) {
+                if (err) *err = "linesearch: grid too large";
+                return false;
+            }
+            c.lds = 2 * dp * sizeof(double);
+            approx = nV > 0 && (LS_DEBUG(a) & ~3) == 0;  // (debug 1/2: timing ablations)
+            a.cls_mask = (1u << m.key_bits) - 1u;  // class bits + duplicate-group bits ride in the keys' low mantissa
+            a.cls_only_mask = (1u << m.key_cls_bits) - 1u;
+            a.gkey = m.gkey.p;
+            if (approx) approx = m.compute_eps2(groups, resident, m.key_bits, /*bare_admission=*/true, /*key_relative=*/true);
+            a.gamma = m.eps_gamma;
+            // (sums from the tiles keep two groups' weights in LDS next to the verify kernel's rank-major copy of the DCG term
+            // table: a wide matrix with many gain classes does not fit)
+            const size_t tab_lds = (m.ncls + 1) * (size_t)(LS_KT + 1) * sizeof(double);
+            if (approx && !resident && 2 * dp * sizeof(double) + tab_lds + 2 * (WAVE + 4) * sizeof(uint4) > 64 * 1024) approx = false;
+            if (!approx && nV > 0) {
+                // the verify launch turned out unusable (compute_eps2 refused the weights, the tables do not fit LDS): the exact
+                // kernel takes ALL staged groups; if some were routed, collect() puts the columns back through gorder
+                m.exact_fallbacks++;
+                nV = 0;
+            }
+            // visiting order of the resident verify kernel (kernels_verify.inc): per group the |w_c - base_f| below which a
+            // candidate ranks like the current model -- where the spread its change of w_f adds, |delta| sigma_x(f), stays under
+            // the spread of the current scores, sqrt(sum_j (w_j sigma_j)^2) -- and the mode bits of columns with crowded extremes;
+            // the R ranks of a restart are redone after its first 1, 2, 4, 8 line searches and then every 16 (FR_RANK_PERIOD in a
+            // pricing build; a stale order only costs admissions: 16 against 8 is +1.4 % in the first 25 ticks of a job and level
+            // afterwards, profiles/r06_rank_policy.txt)
+            a.xslot = nullptr;
+            if (approx && resident && m.xslot.p != nullptr && m.rslot.p != nullptr && m.colstd.size() == m.d) {
+                static const double kappa = [] {
+                    const char* e = frdev::pricing_env("FR_ORDER_KAPPA");
+                    return e ? std::atof(e) : 1.0;
+                }();
+                static const unsigned period = [] {
+                    const char* e = frdev::pricing_env("FR_RANK_PERIOD");
+                    return e ? (unsigned)std::max(1, std::atoi(e)) : 16u;
+                }();
+                double* gthr = c.th<double>(ts.o_gthr);
+                uint32_t* gmode = c.th<uint32_t>(ts.o_gmode);
+                int32_t* rank = c.th<int32_t>(ts.o_rank);
+                for (size_t g = 0; g < nV; g++) {
+                    const LineGroup& lg = groups[g];
+                    double var = 0.0;
+                    for (size_t j = 0; j < m.d; j++) {
+                        const double t = lg.weights[j] * m.colstd[j];
+                        var += t * t;
+                    }
+                    const double sx = m.colstd[lg.feature];
+                    gthr[g] = sx > 0.0 ? kappa * std::sqrt(var) / sx : std::numeric_limits<double>::infinity();
+                    gmode[g] = m.colmode[lg.feature];
+                    const size_t slot = (size_t)lg.resident_slot;
+                    if (slot < m.slot_rank_age.size() && m.slot_rank_mode[slot] == 1) {
+                        if (lg.has_update && m.slot_rank_upd[slot] < 0xFFFF) m.slot_rank_upd[slot]++;
+                        // (ranks age only while the sums change: a restart that accepts nothing keeps its order)
+                        // (a restart's first accepted steps move its model the most: ranks made from the initial sums are stale one line
+                        // search later -- 0.32-0.34 chain runs per visit through ticks 1-7 of a job against 0.16-0.19 behind the first refresh,
+                        // tools/chain_by_tick.py -- so the first refreshes come after 1, 2 and 4 line searches, then every `period`)
+                        if (m.slot_rank_age[slot] == 0xFFFF || (m.slot_rank_age[slot] >= std::min<unsigned>(period, m.slot_rank_gap[slot]) && m.slot_rank_upd[slot] > 0)) {
+                            bool listed = false;  // (a restart with more than 64 candidates has several groups)
+                            for (size_t k = 0; k < nrank; k++) listed = listed || (rank[k] >> 1) == (int32_t)slot;
+                            if (!listed) {
+                                rank[G + nrank] = (int32_t)g;  // (rslot_kernel applies this group's pending update to the sums it ranks)
+                                rank[nrank++] = (int32_t)(slot * 2 + m.res_half[slot]);
+                            }
+                            m.slot_rank_upd[slot] = 0;  // (the ranks are made from the sums WITH this tick's pending update applied)
+                        } else if (m.slot_rank_age[slot] < 0xFFFE) {
+                            m.slot_rank_age[slot]++;
+                        }
+                    }
+                }
+                for (size_t k = 0; k < nrank; k++) {
+                    const size_t slot = (size_t)(rank[k] >> 1);
+                    if (m.slot_rank_age[slot] != 0xFFFF && m.slot_rank_gap[slot] < 0x4000) m.slot_rank_gap[slot] *= 2;  // 1, 2, 4, ... line searches to the next refresh
+                    m.slot_rank_age[slot] = 1;
+                }
+                a.xslot = m.xslot.p;
+                a.rslot = m.rslot.p;
+                a.gthr = c.td<double>(ts.o_gthr);
+                a.gmode = c.td<uint32_t>(ts.o_gmode);
+            }
+            break;
+        }
+        case LSK_RR:
+            if (!resident) return m.ls_exact(c, measure, depth, norms, groups, err);
+            approx = m.compute_eps2(groups, true, 0);
+            break;
+        case LSK_FV:
+            while ((size_t(1) << cls_bits) < m.ncls + 1) cls_bits++;  // (+1: the padding class)
+            // duplicate groups with mixed gain classes (found at upload): the DUP instantiations carry the group id in the keys
+            // behind the class and decide pairs of one group by the reference's tie-break (kernels_fullverify.inc)
+            dup_bits = (m.key_bits > m.key_cls_bits && cls_bits + (m.key_bits - m.key_cls_bits) <= 20) ? m.key_bits - m.key_cls_bits : 0u;
+            approx = m.compute_eps2(groups, resident, cls_bits + dup_bits);
+            break;
+    }
+    if (c.kind != LSK_TOPK && approx && m.approx_skip > 0) {  // a recent line search redid many pairs
         m.approx_skip--;
         m.exact_fallbacks++;
         approx = false;
     }
     if (!m.tick_upload(c, approx, err)) return false;
-    if (!approx) {  // the exact kernels run instead: keep the resident sums current
+    if (c.kind != LSK_TOPK && !approx) {  // the exact kernels take the line search: keep the resident sums current first
         if (resident && any_update) {
-            la.xb = (const float4*)m.xb.p;
-            la.dq = (uint32_t)m.dq;
-            la.posmap = m.posmap();
-            resident_update_kernel<<<dim3((unsigned)((m.pos_threads() + 255) / 256), (unsigned)G), 256, 0, c.stream>>>(la);
-            FR_HIP(hipGetLastError());
+            if (!m.update_resident(c, 0, G, err)) return false;
             m.flip_resident(groups);
         }
         FR_HIP(hipStreamSynchronize(c.stream));  // the tick block is reused by the next call; the exact kernels use the main stream
-        return true;
+        return m.ls_exact(c, measure, depth, norms, groups, err);
     }
-    const size_t ldm = G * 64;
-    c.ldm = ldm;
-    c.maxc = maxc;
-    if (!c.M.ensure(m.nq * ldm, err) || !c.means.ensure(ldm + mean_tail_words(ldm), err) || !c.redo.ensure(m.nq * G, err)) return false;
-    FVArgs fa{};
-    fa.xb = (const float4*)m.xb.p;
-    fa.qstart = m.qstart.p;
-    fa.qlen = m.qlen.p;
-    fa.qnpos = m.qnpos.p;
-    fa.gcls = m.gcls.p;
-    fa.gfeat = c.td<uint32_t>(ts.o_gfeat);
-    fa.gw = c.td<double>(ts.o_gw);
-    fa.gcand = c.td<double>(ts.o_gcand);
-    fa.gncand = c.td<uint32_t>(ts.o_gncand);
-    fa.eps2 = c.td<double>(ts.o_eps2);
-    fa.termtab = m.termtab.p;
-    fa.norms = m.norms.p;
-    fa.redo_count = c.td<uint32_t>(ts.o_count);
-    fa.redo_list = c.redo.p;
-    fa.res_cur = m.res.p;
-    fa.rs_slot = resident ? la.rs_slot : nullptr;
-    fa.rs_par = la.rs_par;
-    fa.rs_updf = la.rs_updf;
-    fa.M = c.M.p;
-    fa.flags = c.flags.p;
-    fa.relmask = m.relmask;
-    fa.G = (uint32_t)G;
-    fa.ldm = (uint32_t)ldm;
-    fa.dq = (uint32_t)m.dq;
-    fa.d = (uint32_t)m.d;
-    fa.np = (uint32_t)m.np;
-    fa.tablen = (uint32_t)m.tablen;
-    fa.cls_mask = (1u << (cls_bits + dup_bits)) - 1u;
-    fa.cls_only_mask = (1u << cls_bits) - 1u;
-    fa.cls_bits = cls_bits;
-    fa.key_cls_bits = m.key_cls_bits;
-    fa.dup = dup_bits ? 1u : 0u;
-    fa.gkey = m.gkey.p;
-    fa.padcls = (uint32_t)m.ncls;
-    fa.measure = measure;
-    fa.depth = depth < 0 ? -1 : (depth > 0x7fffffff ? 0x7fffffff : (int)depth);
-    {
-        // longest queries first (fewest blocks, longest running).  FR_FV_PROFILE=1 times every size class on its own.
-        static const bool per_class = frdev::pricing_env("FR_FV_PROFILE") != nullptr;
-        hipStream_t vs = c.stream;
-        {
-        ProfScope ps_all(per_class ? "fullrank_verify_all" : "fullrank_verify_kernel", vs);
-        for (size_t ci = m.fv_classes.size(); ci-- > 0;) {
-            const auto& sc = m.fv_classes[ci];
-            static std::vector<std::string> names = [] {
-                std::vector<std::string> v;
-                for (int i = 0; i < FV_NCLASSES; i++) v.push_back("fullrank_verify_kernel<" + std::to_string(FV_CLASSES[i].nl) + "x" + std::to_string(FV_CLASSES[i].pl) + ">");
-                return v;
-            }();
-            std::unique_ptr<ProfScope> ps(per_class ? new ProfScope(names[sc.npad].c_str(), vs) : nullptr);
-            fa.qlist = m.fv_qlist.p + sc.offset;
-            if (!fv_launch_class(fa, (int)sc.npad, (unsigned)sc.count, (unsigned)G, (unsigned)maxc, vs)) {
-                if (err) *err = "fullrank_verify_kernel: no instantiation for this size class";
-                return false;
+    if (c.kind != LSK_TOPK && (!c.M.ensure(m.nq * ldm, err) || !c.redo.ensure(m.nq * G, err))) return false;
+    if (!approx) {  // top-k: the exact kernel on every (run, group) pair, the resident updates first (the verify kernel applies them)
+        if (resident && any_update && !m.update_resident(c, 0, G, err)) return false;
+        ProfScope ps("linesearch_ndcg_kernel", c.stream);
+        dispatch_exact(a, depth, (unsigned)(nruns8 * G), maxc, c.lds, c.stream);
+    } else {
+        // the verify kernel, then the exact kernels on its redo list: a fixed-size grid whose blocks compare themselves with the
+        // count on the device, so the host does not wait here (a longer list is finished when the results are collected)
+        switch (c.kind) {
+            case LSK_TOPK: {
+                if (nrank > 0) {
+                    ProfScope ps("rslot_kernel", c.stream);
+                    const uint32_t* wl = m.nwlist ? m.wlist.p : nullptr;  // (a view ranks the walk tiles that hold its documents)
+                    const unsigned nw = (unsigned)(m.nwlist ? m.nwlist : m.nwt);
+                    rslot_kernel<<<dim3((nw + 3) / 4), 256, 0, c.stream>>>(m.res.p, c.td<int32_t>(ts.o_rank), c.td<int32_t>(ts.o_rank) + G, (uint32_t)nrank,
+                                                                          a.rs_par, a.rs_updf, m.xcol.p, m.segtab.p, m.wt_start.p, wl, nw, (uint32_t)m.np, m.rslot.p);
+                    FR_HIP(hipGetLastError());
+                    if (c.audit) {
+                        // the permutation invariant of the tables this launch reads (kernels_order.inc): the R ranks just rewritten and
+                        // the x_f ranks of the tick's features; an offending document counts as an audit mismatch
+                        if (!m.audit_cnt.ensure(1, err)) return false;
+                        FR_HIP(hipMemsetAsync(m.audit_cnt.p, 0, sizeof(unsigned long long), c.stream));
+                        const int32_t* rk = c.th<int32_t>(ts.o_rank);
+                        for (size_t k = 0; k < nrank; k++)
+                            order_audit_kernel<<<dim3((nw + 3) / 4), 256, 0, c.stream>>>(m.rslot.p + (size_t)(rk[k] >> 1) * m.np, m.segtab.p, m.wt_start.p, wl, nw, m.audit_cnt.p);
+                        for (size_t g = 0; g < nV; g++)
+                            order_audit_kernel<<<dim3((nw + 3) / 4), 256, 0, c.stream>>>(m.xslot.p + (size_t)groups[g].feature * m.np, m.segtab.p, m.wt_start.p, wl, nw, m.audit_cnt.p);
+                        unsigned long long bad = 0;
+                        FR_HIP(hipMemcpyAsync(&bad, m.audit_cnt.p, sizeof(bad), hipMemcpyDeviceToHost, c.stream));
+                        FR_HIP(hipStreamSynchronize(c.stream));
+                        m.audit_mismatches += bad;
+                    }
+                }
+                // keys kept per list: K + 1, or K + 2 / K + 3 once many pairs failed verification (tied clusters at the cut);
+                // FR_VERIFY_XS=1|2|3 pins it (tests)
+                const char* xs_e = frdev::path_env("FR_VERIFY_XS");
+                const int xs = std::min(xs_e ? std::atoi(xs_e) : m.verify_xs, depth <= 5 ? 3 : VERIFY_XS_MAX);
+                c.xs_used = xs;
+                c.xs_pinned = xs_e != nullptr;
+                a.eps2 = c.td<double>(ts.o_eps2);
+                a.G = (uint32_t)nV;  // (the verify launch and its redo list cover the first nV staged groups)
+                const bool dupk = resident && m.key_bits > m.key_cls_bits;  // duplicate groups with mixed gains exist: the DUP variants
+                const size_t tab_lds = (m.ncls + 1) * (size_t)(LS_KT + 1) * sizeof(double);
+                {
+                    ProfScope ps("linesearch_verify_kernel", c.stream);
+                    if (depth <= 5) launch_verify<5>(a, resident, dupk, xs, (unsigned)nruns8, nV, dp, tab_lds, c.stream);
+                    else if (depth <= 10) launch_verify<10>(a, resident, dupk, xs, (unsigned)nruns8, nV, dp, tab_lds, c.stream);
+                    else launch_verify<20>(a, resident, dupk, xs, (unsigned)nruns8, nV, dp, tab_lds, c.stream);
+                }
+                FR_HIP(hipGetLastError());
+                // (the grid follows the redo counts this context has seen, 512 .. 8192 pairs: a short list wants a short grid --
+                // every block, empty or not, needs a wave slot, and those are contested while another set's verify grid is
+                // dispatching -- a long one (tie-heavy data) must not cost a second round trip)
+                a.slice_count = c.td<uint32_t>(ts.o_count) + 1;
+                c.redo_grid_used = redo_pin ? redo_pin : c.redo_grid;
+                if (!m.redo_launch(c, 0, c.td<uint32_t>(ts.o_count), c.redo_grid_used, err)) return false;
+                if (nV < G) {  // the routed groups: the exact kernel over all their (run, group) pairs
+                    if (any_update && !m.update_resident(c, nV, G - nV, err)) return false;  // (the verify kernel applies the pending updates of its own groups only)
+                    LSArgs x = a;
+                    x.work_list = nullptr;
+                    x.work_count = nullptr;
+                    x.g_base = (uint32_t)nV;
+                    x.G = (uint32_t)(G - nV);
+                    ProfScope ps("linesearch_ndcg_kernel", c.stream);
+                    dispatch_exact(x, depth, (unsigned)(nruns8 * (G - nV)), maxc, c.lds, c.stream);
+                }
+                break;
             }
-        }
+            case LSK_RR: {
+                RRArgs& ra = c.ra;
+                ra = RRArgs{};
+                ra.xb = (const float4*)m.xb.p;
+                ra.qstart = m.qstart.p;
+                ra.qlen = m.qlen.p;
+                ra.qnpos = m.qnpos.p;
+                ra.gfeat = c.td<uint32_t>(ts.o_gfeat);
+                ra.gw = c.td<double>(ts.o_gw);
+                ra.gcand = c.td<double>(ts.o_gcand);
+                ra.gncand = c.td<uint32_t>(ts.o_gncand);
+                ra.eps2 = c.td<double>(ts.o_eps2);
+                ra.redo_count = c.td<uint32_t>(ts.o_count);
+                ra.redo_list = c.redo.p;
+                ra.res_cur = m.res.p;
+                ra.rs_slot = a.rs_slot;
+                ra.rs_par = a.rs_par;
+                ra.rs_updf = a.rs_updf;
+                ra.xcol = a.xcol;
+                ra.M = c.M.p;
+                ra.flags = c.flags.p;
+                ra.G = (uint32_t)G;
+                ra.ldm = (uint32_t)ldm;
+                ra.dq = (uint32_t)m.dq;
+                ra.d = (uint32_t)m.d;
+                ra.np = (uint32_t)m.np;
+                {
+                    ProfScope ps("rr_verify_kernel", c.stream);
+                    FR_HIP(hipFuncSetAttribute((const void*)rr_verify_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+                    for (size_t ci = m.size_classes.size(); ci-- > 0;) {
+                        const auto& sc = m.size_classes[ci];
+                        ra.qlist = m.qlist.p + sc.offset;
+                        rr_verify_kernel<<<dim3((unsigned)sc.count, (unsigned)G), WAVE, (size_t)sc.npad * sizeof(uint4), c.stream>>>(ra);
+                    }
+                }
+                FR_HIP(hipGetLastError());
+                c.redo_grid_used = redo_pin ? redo_pin : RR_REDO_GRID;
+                if (!m.redo_launch(c, 0, c.td<uint32_t>(ts.o_count), c.redo_grid_used, err)) return false;
+                break;
+            }
+            case LSK_FV: {
+                const size_t slot_rows = ((m.maxlen + 63) / 64 + 1) * 64;
+                if (!c.fv_rows.ensure((size_t)FV_REDO_GRID * slot_rows * 64, err)) return false;
+                FVArgs fa{};
+                fa.xb = (const float4*)m.xb.p;
+                fa.qstart = m.qstart.p;
+                fa.qlen = m.qlen.p;
+                fa.qnpos = m.qnpos.p;
+                fa.gcls = m.gcls.p;
+                fa.gfeat = c.td<uint32_t>(ts.o_gfeat);
+                fa.gw = c.td<double>(ts.o_gw);
+                fa.gcand = c.td<double>(ts.o_gcand);
+                fa.gncand = c.td<uint32_t>(ts.o_gncand);
+                fa.eps2 = c.td<double>(ts.o_eps2);
+                fa.termtab = m.termtab.p;
+                fa.norms = m.norms.p;
+                fa.redo_count = c.td<uint32_t>(ts.o_count);
+                fa.redo_list = c.redo.p;
+                fa.res_cur = m.res.p;
+                fa.rs_slot = a.rs_slot;
+                fa.rs_par = a.rs_par;
+                fa.rs_updf = a.rs_updf;
+                fa.M = c.M.p;
+                fa.flags = c.flags.p;
+                fa.relmask = m.relmask;
+                fa.G = (uint32_t)G;
+                fa.ldm = (uint32_t)ldm;
+                fa.dq = (uint32_t)m.dq;
+                fa.d = (uint32_t)m.d;
+                fa.np = (uint32_t)m.np;
+                fa.tablen = (uint32_t)m.tablen;
+                fa.cls_mask = (1u << (cls_bits + dup_bits)) - 1u;
+                fa.cls_only_mask = (1u << cls_bits) - 1u;
+                fa.cls_bits = cls_bits;
+                fa.key_cls_bits = m.key_cls_bits;
+                fa.dup = dup_bits ? 1u : 0u;
+                fa.gkey = m.gkey.p;
+                fa.padcls = (uint32_t)m.ncls;
+                fa.measure = measure;
+                fa.depth = depth < 0 ? -1 : (depth > 0x7fffffff ? 0x7fffffff : (int)depth);
+                {
+                    // longest queries first (fewest blocks, longest running).  FR_FV_PROFILE=1 times every size class on its own.
+                    static const bool per_class = frdev::pricing_env("FR_FV_PROFILE") != nullptr;
+                    ProfScope ps_all(per_class ? "fullrank_verify_all" : "fullrank_verify_kernel", c.stream);
+                    for (size_t ci = m.fv_classes.size(); ci-- > 0;) {
+                        const auto& sc = m.fv_classes[ci];
+                        static std::vector<std::string> names = [] {
+                            std::vector<std::string> v;
+                            for (int i = 0; i < FV_NCLASSES; i++) v.push_back("fullrank_verify_kernel<" + std::to_string(FV_CLASSES[i].nl) + "x" + std::to_string(FV_CLASSES[i].pl) + ">");
+                            return v;
+                        }();
+                        std::unique_ptr<ProfScope> ps(per_class ? new ProfScope(names[sc.npad].c_str(), c.stream) : nullptr);
+                        fa.qlist = m.fv_qlist.p + sc.offset;
+                        if (!fv_launch_class(fa, (int)sc.npad, (unsigned)sc.count, (unsigned)G, (unsigned)maxc, c.stream)) {
+                            if (err) *err = "fullrank_verify_kernel: no instantiation for this size class";
+                            return false;
+                        }
+                    }
+                }
+                FR_HIP(hipGetLastError());
+                FSArgs& fs = c.fsa;
+                fs = m.scores_args(fa.gfeat, fa.gw, fa.gcand, c.fv_rows.p, c.flags.p, G);
+                fs.qstart = m.qstart.p;
+                fs.qlen = m.qlen.p;
+                fs.G = (uint32_t)G;
+                fs.slot_rows = (uint32_t)slot_rows;
+                RMArgs& rm = c.rma;
+                rm = m.rank_args(c.fv_rows.p, fa.gncand, c.M.p, c.flags.p, G, ldm, measure, depth);
+                rm.G = (uint32_t)G;
+                rm.slot_rows = (uint32_t)slot_rows;
+                c.redo_grid_used = FV_REDO_GRID;
+                if (!m.redo_launch(c, 0, c.td<uint32_t>(ts.o_count), FV_REDO_GRID, err)) return false;
+                break;
+            }
         }
     }
     FR_HIP(hipGetLastError());
+    if (!m.ls_means(c, err)) return false;
     if (resident) m.flip_resident(groups);
-    // exact recomputation of the redo list: fixed-size grids against the device-side count, so the host does not
-    // wait here (a longer list is finished when the results are collected)
-    FSArgs& fs = c.fsa;
-    fs = FSArgs{};
-    fs.xb = (const float4*)m.xb.p;
-    fs.gfeat = c.td<uint32_t>(ts.o_gfeat);
-    fs.gw = c.td<double>(ts.o_gw);
-    fs.gcand = c.td<double>(ts.o_gcand);
-    fs.rows = c.fv_rows.p;
-    fs.flags = c.flags.p;
-    fs.dq = (uint32_t)m.dq;
-    fs.d = (uint32_t)m.d;
-    fs.nruns = 0;
-    fs.GC = (uint32_t)G;
-    fs.np = (uint32_t)m.np;
-    fs.qstart = m.qstart.p;
-    fs.qlen = m.qlen.p;
-    fs.G = (uint32_t)G;
-    fs.slot_rows = (uint32_t)slot_rows;
-    RMArgs& rm = c.rma;
-    rm = RMArgs{};
-    rm.rows = c.fv_rows.p;
-    rm.qstart = m.qstart.p;
-    rm.qlen = m.qlen.p;
-    rm.qnpos = m.qnpos.p;
-    rm.qnneg = m.qnneg.p;
-    rm.gcls = m.gcls.p;
-    rm.termtab = m.termtab.p;
-    rm.norms = m.norms.p;
-    rm.gncand = c.td<uint32_t>(ts.o_gncand);
-    rm.qlist = nullptr;
-    rm.M = c.M.p;
-    rm.flags = c.flags.p;
-    rm.GC = (uint32_t)G;
-    rm.np = (uint32_t)m.np;
-    rm.ldm = (uint32_t)ldm;
-    rm.col0 = 0;
-    rm.tablen = (uint32_t)m.tablen;
-    rm.measure = measure;
-    rm.depth = fa.depth;
-    rm.G = (uint32_t)G;
-    rm.slot_rows = (uint32_t)slot_rows;
-    if (!m.fv_redo_launch(c, c.redo.p, c.td<uint32_t>(ts.o_count), FV_REDO_GRID, err)) return false;
-    if (!launch_means(c.M.p, ldm, ldm, m.nq, m.sums_only, c.partial, c.means, c.stream, err, c.td<uint32_t>(c.ts.o_count), c.flags.p, m.tick_host_out(c, ldm, err))) return false;
-    c.fv = true;
-    *queued = true;
+    c.gslot.assign(G, -1);  // (top-k: the restarts the policies at collect steer)
+    if (resident)
+        for (size_t k = 0; k < G; k++) c.gslot[k] = groups[k].resident_slot;
+    c.approx = approx;
+    c.nverify = approx ? nV : 0;
+    c.pending = true;
     return true;
 }
 
-// waits for what fv_launch queued on c and returns the column results (the rest of a long redo list first)
-bool DeviceDataset::Impl::fv_finish(LsCtx& c, std::vector<double>* means, std::string* err) {
+// The exact kernels alone: the scores kernel and the rank-counting kernel on the main stream, in chunks of groups whose score
+// rows take at most half of the free HBM.  A context of its own hands the groups, their resident updates applied, to the
+// lock-step form on the main stream's context, which tries bound-and-verify once more before it comes here (the skip
+// counter has moved on: the last tick of a back-off verifies again).
+bool DeviceDataset::Impl::ls_exact(LsCtx& c, int measure, int64_t depth, const double* norms, const std::vector<LineGroup>& groups,
+                                   std::string* err) {
     Impl& m = *this;
-    const size_t ldm = c.ldm, G = ldm / 64;
-    means->assign(ldm, 0.0);
-    uint32_t nredo = 0;
-    if (!m.tick_finish(c, ldm, means, &nredo, err)) return false;
-    m.approx_pairs += m.nq * G;
-    m.approx_redo += nredo;
-    if (nredo > FV_REDO_GRID) {
-        for (uint32_t off = FV_REDO_GRID; off < nredo; off += FV_REDO_GRID)
-            if (!m.fv_redo_launch(c, c.redo.p + off, nullptr, std::min<uint32_t>(FV_REDO_GRID, nredo - off), err)) return false;
-        if (!launch_means(c.M.p, ldm, ldm, m.nq, m.sums_only, c.partial, c.means, c.stream, err, c.td<uint32_t>(c.ts.o_count), c.flags.p, m.tick_host_out(c, ldm, err))) return false;
-        uint32_t again = 0;
-        if (!m.tick_finish(c, ldm, means, &again, err)) return false;
+    if (&c != &m.ls[LS_CONTEXTS]) {
+        c.pgroups.assign(groups.begin(), groups.end());
+        for (LineGroup& lg : c.pgroups) lg.has_update = false;
+        LsCtx& l = m.ls[LS_CONTEXTS];
+        if (!m.ls_submit(l, LS_FULLRANK, measure, depth, norms, c.pgroups, err) || !m.ls_collect(l, &c.exact_means, err)) return false;
+        c.counts = l.counts;
+        c.ready = c.pending = true;
+        return true;
     }
-    if ((size_t)nredo * 4 > m.nq * G) m.approx_skip = 16;
-    m.last_ldm = ldm;
-    m.last_cols = ldm;
-    m.last_M = c.M.p;
-    return true;
-}
-
-bool DeviceDataset::linesearch_fullrank_submit(int ctx, int measure, int64_t depth, const double* norms,
-                                               const std::vector<LineGroup>& groups, bool* queued, std::string* err) {
-    if (measure == M_RR) return linesearch_rr_submit(ctx, groups, queued, err);
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    *queued = false;
-    if (ctx < 0 || ctx >= LS_CONTEXTS || m.ls[ctx].pending) {
-        if (err) *err = "linesearch_fullrank: no such context, or a submitted line search was not collected";
-        return false;
-    }
-    for (const auto& lg : groups)
-        if (lg.feature >= m.d || lg.weights.size() != m.d || lg.candidates.empty() || lg.candidates.size() > 64) {
-            if (err) *err = "linesearch_fullrank: malformed line group";
-            return false;
-        }
-    m.ls[ctx].fv = false;
-    if (!m.fv_launch(m.ls[ctx], measure, depth, norms, groups, queued, err)) return false;
-    m.ls[ctx].pending = *queued;
-    return true;
-}
-
-bool DeviceDataset::linesearch_fullrank_collect(int ctx, std::vector<double>* means, std::string* err) {
-    Impl& m = *impl_;
-    {
-        std::lock_guard<std::mutex> lk(m.mu);
-        if (ctx >= 0 && ctx < LS_CONTEXTS && m.ls[ctx].pending && m.ls[ctx].fv) {
-            if (!m.bind(err)) return false;
-            m.ls[ctx].pending = false;
-            m.ls[ctx].fv = false;
-            return m.fv_finish(m.ls[ctx], means, err);
-        }
-    }
-    return linesearch_rr_collect(ctx, means, err);
-}
-
-// Full-ranking line search: every candidate of every group, any measure.  means[g*64 + c].
-bool DeviceDataset::linesearch_fullrank(int measure, int64_t depth, const double* norms,
-                                        const std::vector<LineGroup>& groups, std::vector<double>* means,
-                                        std::string* err) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    if (!fullrank_supported(measure, depth)) {
-        if (err) *err = "linesearch_fullrank: unsupported dataset or measure";
-        return false;
-    }
-    const size_t G = groups.size();
-    means->assign(G * 64, 0.0);
-    if (G == 0) return true;
-    const size_t dp = m.dq * 4;
-    const size_t ldm = G * 64;
-    size_t maxc = 0;
-    for (const auto& lg : groups) {
-        if (lg.feature >= m.d || lg.weights.size() != m.d || lg.candidates.empty() || lg.candidates.size() > 64) {
-            if (err) *err = "linesearch_fullrank: malformed line group";
-            return false;
-        }
-        maxc = std::max(maxc, lg.candidates.size());
-    }
-    if (measure == M_RR && m.maxlen <= 8192) {
-        bool done = false;
-        if (!m.linesearch_rr_verify(groups, means, &done, err)) return false;
-        if (done) return true;
-    }
-    if (measure != M_RR && m.fv_usable(measure)) {  // bound-and-verify in lock step: its own context on the main stream
-        Impl::LsCtx& c = m.ls[LS_CONTEXTS];
-        c.stream = m.stream;
-        bool queued = false;
-        if (!m.fv_launch(c, measure, depth, norms, groups, &queued, err)) return false;
-        if (queued) {
-            c.fv = false;
-            return m.fv_finish(c, means, err);
-        }
-        // (not queued: fv_launch has applied the pending resident updates; the exact kernels below do not use the sums)
-    }
-    // chunk the groups so that the score rows take at most half of the free HBM (62 GB for 32 groups at
-    // the 30K shape: one chunk on a 288 GB part)
+    const size_t G = groups.size(), dp = m.dq * 4, ldm = G * 64, maxc = c.maxc;
+    std::vector<double>& means = c.exact_means;
+    means.assign(ldm, 0.0);
     const size_t row_bytes = 64 * sizeof(double);
     size_t budget = m.rows.bytes();
     if (G * m.np * row_bytes > budget) {  // the buffer has to grow: see what is there (it is released first)
@@ -3451,7 +3107,6 @@ bool DeviceDataset::linesearch_fullrank(int measure, int64_t depth, const double
         !m.gcand.ensure(GC * 64, err) || !m.means.ensure(ldm, err))
         return false;
     if (!m.upload_norms(norms, err)) return false;
-    int dd = depth < 0 ? -1 : (depth > 0x7fffffff ? 0x7fffffff : (int)depth);
     for (size_t g0 = 0; g0 < G; g0 += GC) {
         const size_t gc = std::min(GC, G - g0);
         std::vector<uint32_t> gfeat(gc), gncand(gc);
@@ -3468,49 +3123,14 @@ bool DeviceDataset::linesearch_fullrank(int measure, int64_t depth, const double
         FR_HIP(hipMemcpyAsync(m.gw.p, gw.data(), gc * dp * sizeof(double), hipMemcpyHostToDevice, m.stream));
         FR_HIP(hipMemcpyAsync(m.gcand.p, gcand.data(), gc * 64 * sizeof(double), hipMemcpyHostToDevice, m.stream));
         FR_HIP(hipStreamSynchronize(m.stream));  // the staging vectors are locals
-        FSArgs fa;
-        fa.xb = (const float4*)m.xb.p;
-        fa.run_pos = m.run_pos.p;
-        fa.run_docs = m.run_docs.p;
-        fa.run_order = m.run_order.p;
-        fa.gfeat = m.gfeat.p;
-        fa.gw = m.gw.p;
-        fa.gcand = m.gcand.p;
-        fa.rows = m.rows.p;
-        fa.flags = m.flags.p;
-        fa.dq = (uint32_t)m.dq;
-        fa.d = (uint32_t)m.d;
-        fa.nruns = (uint32_t)m.nruns;
-        fa.GC = (uint32_t)gc;
-        fa.np = (uint32_t)m.np;
-        const size_t nblocks = ((m.nruns + 7) / 8) * 8 * gc;
         {
             ProfScope ps("linesearch_scores_kernel", m.stream);
-            const size_t lds = 2 * dp * sizeof(double);
-            if (maxc <= 16) launch_scores<16>(fa, (unsigned)nblocks, lds, m.stream);
-            else if (maxc <= 51) launch_scores<51>(fa, (unsigned)nblocks, lds, m.stream);
-            else launch_scores<64>(fa, (unsigned)nblocks, lds, m.stream);
+            const FSArgs fa = m.scores_args(m.gfeat.p, m.gw.p, m.gcand.p, m.rows.p, m.flags.p, gc);
+            launch_scores(fa, maxc, (unsigned)(((m.nruns + 7) / 8) * 8 * gc), 2 * dp * sizeof(double), m.stream);
         }
         FR_HIP(hipGetLastError());
-        RMArgs ra;
-        ra.rows = m.rows.p;
-        ra.qstart = m.qstart.p;
-        ra.qlen = m.qlen.p;
-        ra.qnpos = m.qnpos.p;
-        ra.qnneg = m.qnneg.p;
-        ra.gcls = m.gcls.p;
-        ra.termtab = m.termtab.p;
-        ra.norms = m.norms.p;
-        ra.gncand = m.gncand.p;
-        ra.M = m.M.p;
-        ra.flags = m.flags.p;
-        ra.GC = (uint32_t)gc;
-        ra.np = (uint32_t)m.np;
-        ra.ldm = (uint32_t)ldm;
+        RMArgs ra = m.rank_args(m.rows.p, m.gncand.p, m.M.p, m.flags.p, gc, ldm, measure, depth);
         ra.col0 = (uint32_t)(g0 * 64);
-        ra.tablen = (uint32_t)m.tablen;
-        ra.measure = measure;
-        ra.depth = dd;
         {
             ProfScope ps("rank_metric_kernel", m.stream);
             FR_HIP(hipFuncSetAttribute((const void*)rank_metric_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -3529,12 +3149,203 @@ bool DeviceDataset::linesearch_fullrank(int measure, int64_t depth, const double
         FR_HIP(hipGetLastError());
     }
     if (!launch_means(m.M.p, ldm, ldm, m.nq, m.sums_only, m.partial, m.means, m.stream, err)) return false;
-    FR_HIP(hipMemcpyAsync(means->data(), m.means.p, ldm * sizeof(double), hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipMemcpyAsync(means.data(), m.means.p, ldm * sizeof(double), hipMemcpyDeviceToHost, m.stream));
     m.last_ldm = ldm;
     m.last_cols = ldm;
     m.last_M = m.M.p;
-    return m.pull_flags(err);
+    if (!m.pull_flags(err)) return false;
+    c.ready = c.pending = true;
+    return true;
 }
+
+bool DeviceDataset::Impl::ls_collect(LsCtx& c, std::vector<double>* means, std::string* err) {
+    Impl& m = *this;
+    c.pending = false;
+    if (c.ready) {
+        *means = c.exact_means;
+        return true;
+    }
+    const size_t ldm = c.ldm, G = ldm / 64;
+    means->assign(ldm, 0.0);
+    if (G == 0) return true;
+    uint32_t nredo = 0, nslices = 0;  // pairs listed; top-k: slices of them the exact kernel recomputed
+    std::vector<uint32_t>& by_group = c.gredo_h;
+    if (!m.tick_finish(c, ldm, means, &nredo, err, &nslices, c.kind == LSK_TOPK ? &by_group : nullptr)) return false;
+    LSArgs& a = c.a;  // (top-k: a.G = the groups of the verify launch)
+    if (c.approx) {
+        const size_t nV = c.nverify;
+        m.approx_pairs += m.nq * nV;
+        m.approx_redo += nredo;
+        c.counts.pairs += m.nq * nV;
+        c.counts.redone += nredo;
+        const unsigned grid = c.redo_grid_used;
+        uint32_t again = 0;
+        if (nredo > grid &&  // the rest of a long redo list, then the column results again
+            (!m.redo_launch(c, grid, nullptr, nredo - grid, err) || !m.ls_means(c, err) || !m.tick_finish(c, ldm, means, &again, err, &nslices)))
+            return false;
+        switch (c.kind) {
+            case LSK_TOPK:
+                if (!m.topk_policy(c, nredo, nslices, err)) return false;
+                break;
+            default:  // many pairs redone: the exact kernels take the next 16 line searches
+                if ((size_t)nredo * 4 > m.nq * G) m.approx_skip = 16;
+                break;
+        }
+    }
+    if (!c.gorder.empty()) {  // routed groups were staged behind the others: columns back in the caller's order
+        std::vector<double> tmp(*means);
+        for (size_t k = 0; k < G; k++) std::memcpy(means->data() + (size_t)c.gorder[k] * 64, tmp.data() + k * 64, 64 * sizeof(double));
+    }
+    m.last_ldm = ldm;
+    m.last_cols = ldm;
+    m.last_M = c.M.p;  // (per-query inspection is for stateless callers, whose groups are never routed)
+    if (LS_DEBUG(a) & 16) {
+        unsigned long long cnt[4];
+        FR_HIP(hipMemcpyAsync(cnt, m.dbgc.p, sizeof(cnt), hipMemcpyDeviceToHost, c.stream));
+        FR_HIP(hipStreamSynchronize(c.stream));
+        fprintf(stderr, "[FR_LS_DEBUG] docs=%llu rows=%llu (%.3f of docs) batches=%llu insertion_rows=%llu\n", cnt[3], cnt[0],
+                (double)cnt[0] / (double)cnt[3], cnt[1], cnt[2]);
+    }
+    return true;
+}
+
+// Top-k, after a verified line search: the redo grid, the restarts' R-rank modes, the audit, and the list length / back-off.
+bool DeviceDataset::Impl::topk_policy(LsCtx& c, uint32_t nredo, uint32_t nslices, std::string* err) {
+    Impl& m = *this;
+    const size_t ldm = c.ldm, G = ldm / 64, nV = c.nverify;
+    const std::vector<uint32_t>& by_group = c.gredo_h;
+    LSArgs& a = c.a;
+    const unsigned grid_used = c.redo_grid_used;
+    if (nredo > grid_used / 2) c.redo_grid = std::min(8192u, std::max(c.redo_grid, 512u) * 4u);
+    else if (nredo < grid_used / 16 && c.redo_grid > 512u) c.redo_grid /= 2u;
+    m.approx_redo_entries += nslices;
+    for (size_t k = 0; k < nV; k++) m.chain_runs += by_group[G + k];
+    m.chain_visits += (unsigned long long)m.n * nV;
+    {
+        // the restarts' running means of chain runs per visit, and the switch (see slot_rank_mode)
+        static const double t_off = [] {
+            const char* e = frdev::pricing_env("FR_RANK_OFF_BELOW");
+            return e ? std::atof(e) : RANK_OFF_BELOW;
+        }();
+        static const double t_on = [] {
+            const char* e = frdev::pricing_env("FR_RANK_ON_ABOVE");
+            return e ? std::atof(e) : RANK_ON_ABOVE;
+        }();
+        std::vector<double> runs(m.slot_rank_mode.size(), 0.0), visits(m.slot_rank_mode.size(), 0.0);
+        for (size_t k = 0; k < nV; k++) {
+            const int slot = c.gslot[k];
+            if (slot < 0 || (size_t)slot >= m.slot_rank_mode.size()) continue;
+            runs[slot] += (double)by_group[G + k];
+            visits[slot] += (double)m.n;
+        }
+        for (size_t slot = 0; slot < runs.size(); slot++) {
+            if (visits[slot] == 0.0) continue;
+            const double r = runs[slot] / visits[slot];
+            uint16_t& n = m.slot_rate_n[slot];
+            if (n < 16) n++;
+            m.slot_rate[slot] += (float)((r - (double)m.slot_rate[slot]) / (double)n);  // (plain mean up to 16, exponential from there)
+            if (n < 16) continue;
+            if (m.slot_rank_mode[slot] == 1 && (double)m.slot_rate[slot] < t_off) {
+                m.slot_rank_mode[slot] = 2;
+                m.rank_slots_off++;
+            } else if (m.slot_rank_mode[slot] == 2 && (double)m.slot_rate[slot] > t_on) {
+                m.slot_rank_mode[slot] = 1;
+                m.rank_slots_on++;
+            }
+        }
+    }
+    if (c.audit) {
+        // audit: every value this line search published (verified, or recomputed from the redo list) against the
+        // exact kernel run over ALL (run, group) pairs -- bit for bit.  The exact kernel rewrites M with what must
+        // be the same numbers; the means were already formed from the published ones.
+        const size_t nel = m.nq * ldm;
+        if (!m.audit.ensure(nel, err) || !m.audit_cnt.ensure(1, err)) return false;
+        FR_HIP(hipMemcpyAsync(m.audit.p, c.M.p, nel * sizeof(double), hipMemcpyDeviceToDevice, c.stream));
+        LSArgs x = a;
+        x.work_list = nullptr;
+        x.work_count = nullptr;
+        x.g_base = 0;
+        x.G = (uint32_t)G;
+        dispatch_exact(x, c.depth, (unsigned)(((m.nruns + 7) / 8) * 8 * G), c.maxc, c.lds, c.stream);
+        FR_HIP(hipMemsetAsync(m.audit_cnt.p, 0, sizeof(unsigned long long), c.stream));
+        audit_compare_kernel<<<dim3(1024), dim3(256), 0, c.stream>>>(m.audit.p, c.M.p, nel, m.audit_cnt.p);
+        unsigned long long bad = 0;
+        FR_HIP(hipMemcpyAsync(&bad, m.audit_cnt.p, sizeof(bad), hipMemcpyDeviceToHost, c.stream));
+        FR_HIP(hipStreamSynchronize(c.stream));
+        m.audit_values += nel;
+        m.audit_mismatches += bad;
+    }
+    // tie-heavy data (more than 0.4 % of the pairs redone -- a redone pair costs ~12 verified ones, a longer list ~4 % of
+    // the kernel): first keep more keys per list (up to K + 4), so that tied clusters of one
+    // gain class may straddle the cut (raised only; a new trainer starts one below the last one's; launches already in flight used
+    // the old length).  With the longest lists (or a pinned length), a restart whose line search still left more than
+    // a quarter of its pairs undecided -- its weights make scores tie exactly -- sends its next 4 / 8 / 16 line
+    // searches to the exact kernel (doubled while the verify kernel keeps failing on it, halved when it succeeds).
+    size_t total = 0;
+    for (size_t k = 0; k < nV; k++) total += by_group[k];
+    if (total * 250 > m.nq * nV && c.xs_used < (c.depth <= 5 ? 3 : VERIFY_XS_MAX) && !c.xs_pinned) {
+        if (m.verify_xs <= c.xs_used) m.verify_xs = c.xs_used + 1;
+    } else if (LS_DEBUG(a) == 0) {
+        // (per distinct slot: 1 = seen, 2 = one of its groups left more than a quarter of its pairs undecided)
+        std::vector<char> verdict(m.slot_backoff.size(), 0);
+        for (size_t k = 0; k < nV; k++) {
+            const int slot = c.gslot[k];
+            if (slot < 0 || (size_t)slot >= m.slot_backoff.size()) continue;
+            verdict[slot] |= (char)(((size_t)by_group[k] * 4 > m.nq) ? 3 : 1);
+        }
+        for (size_t slot = 0; slot < verdict.size(); slot++) {
+            if (verdict[slot] & 2) {
+                m.slot_backoff[slot] = (uint8_t)std::min<unsigned>(16u, std::max<unsigned>(4u, m.slot_backoff[slot] * 2u));
+                m.slot_exact_left[slot] = m.slot_backoff[slot];
+            } else if (verdict[slot]) {
+                m.slot_backoff[slot] = (uint8_t)(m.slot_backoff[slot] / 2u);
+            }
+        }
+    }
+    return true;
+}
+
+bool DeviceDataset::linesearch_submit(int ctx, int measure, int64_t depth, const double* norms, const std::vector<LineGroup>& groups,
+                                      std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    if (ctx < 0 || ctx >= LS_CONTEXTS || m.ls[ctx].pending) {
+        if (err) *err = "linesearch_submit: no such context, or a submitted line search was not collected";
+        return false;
+    }
+    return m.ls_submit(m.ls[ctx], linesearch_path(measure, depth), measure, depth, norms, groups, err);
+}
+
+bool DeviceDataset::linesearch_collect(int ctx, std::vector<double>* means, LsCounts* counts, std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    if (ctx < 0 || ctx >= LS_CONTEXTS || !m.ls[ctx].pending) {
+        if (err) *err = "linesearch_collect: nothing was submitted on this context";
+        return false;
+    }
+    if (!m.ls_collect(m.ls[ctx], means, err)) return false;
+    if (counts) *counts = m.ls[ctx].counts;
+    return true;
+}
+
+bool DeviceDataset::linesearch(int measure, int64_t depth, const double* norms, const std::vector<LineGroup>& groups,
+                               std::vector<double>* means, LsCounts* counts, std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    const LsPath path = linesearch_path(measure, depth);
+    Impl::LsCtx& c = m.ls[path == LS_TOPK ? 0 : LS_CONTEXTS];
+    if (c.pending) {
+        if (err) *err = "linesearch: context 0 busy (collect the submitted line search first)";
+        return false;
+    }
+    if (!m.ls_submit(c, path, measure, depth, norms, groups, err) || !m.ls_collect(c, means, err)) return false;
+    if (counts) *counts = c.counts;
+    return true;
+}
+
 
 
 

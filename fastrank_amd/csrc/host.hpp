@@ -1006,22 +1006,18 @@ class CATrainer {
             while (rs_.size() < (size_t)std::max<uint32_t>(capacity, 1) && queue_->pop(&id)) rs_.emplace_back(id, child_[id]);
         }
         refill_min_ = std::max<size_t>(1, rs_.size() / 8);
-        bool can_fused = dev.linesearch_supported(ev_.measure, ev_.depth);
-        bool can_fullrank = dev.fullrank_supported(ev_.measure, ev_.depth) && !frdev::path_env("FR_FORCE_GENERIC");
+        path_ = dev.linesearch_path(ev_.measure, ev_.depth);
         if (shard_.allreduce) {
             // Query shards: what a shard's device form supports depends on that shard's data (a non-finite
             // feature, a query beyond the rank-table size, the number of gain classes), and the vector each
             // tick hands to the exchange is laid out per path (groups*64 sums on the fused paths, one sum per
             // candidate on the generic one).  Every rank must therefore take the same path: the one all of
             // them support.  Counts are small integers, so the rank-ordered sum is exact.
-            double caps[3] = {can_fused ? 1.0 : 0.0, can_fullrank ? 1.0 : 0.0, 1.0};
+            double caps[3] = {path_ == LS_TOPK ? 1.0 : 0.0, path_ == LS_FULLRANK ? 1.0 : 0.0, 1.0};
             shard_.allreduce(caps, 3);
-            can_fused = caps[0] == caps[2];
-            can_fullrank = caps[1] == caps[2];
+            path_ = caps[0] == caps[2] ? LS_TOPK : (caps[1] == caps[2] ? LS_FULLRANK : LS_NONE);
         }
-        fused_ = can_fused;
-        fullrank_ = !fused_ && can_fullrank;
-        stats_.path = fused_ ? "fused_linesearch" : (fullrank_ ? "fused_fullrank" : "generic_sort");
+        stats_.path = path_ == LS_TOPK ? "fused_linesearch" : (path_ == LS_FULLRANK ? "fused_fullrank" : "generic_sort");
         stats_.restarts = (uint32_t)rs_.size();
         if (rs_.empty()) return;
         const size_t R = rs_.size();
@@ -1032,7 +1028,7 @@ class CATrainer {
         // R ~ sum_j x_j * best_w_j for every document, so a tick reads 24 bytes per document and restart instead
         // of the whole feature row.  FR_LS_RESIDENT=0 turns it off (every tick then forms the sums from the tiles).
         const char* res_env = frdev::path_env("FR_LS_RESIDENT");
-        if ((fused_ || fullrank_) && !(res_env && res_env[0] == '0')) {
+        if (path_ != LS_NONE && !(res_env && res_env[0] == '0')) {
             std::string _err;
             res_owner_ = dev.resident_reserve(R, &_err);
             if (res_owner_ != 0) {
@@ -1060,38 +1056,26 @@ class CATrainer {
         if (!build_groups(-1, groups_, &gen_B)) return false;
         stats_.line_searches++;
         dev.set_sums_only((bool)shard_.allreduce);  // the dataset object may be shared with other callers
-        if (fused_) {
+        if (path_ != LS_NONE) {
             std::string _err;
-            unsigned long long p0 = 0, r0 = 0, p1 = 0, r1 = 0;
-            dev.verify_counters(&p0, &r0);
-            if (!dev.linesearch_ndcg(ev_.depth, ev_.norms.data(), groups_, &means_, &_err)) fail_str(_err);
-            dev.verify_counters(&p1, &r1);
-            stats_.verify_pairs += p1 - p0;
-            stats_.verify_redone += r1 - r0;
-            check_flags(dev);
-        } else if (fullrank_) {
-            std::string _err;
-            unsigned long long p0 = 0, r0 = 0, p1 = 0, r1 = 0;
-            dev.verify_counters(&p0, &r0);
-            if (!dev.linesearch_fullrank(ev_.measure, ev_.depth, ev_.norms.data(), groups_, &means_, &_err))
-                fail_str(_err);
-            dev.verify_counters(&p1, &r1);
-            stats_.verify_pairs += p1 - p0;
-            stats_.verify_redone += r1 - r0;
+            frdev::DeviceDataset::LsCounts cnt;
+            if (!dev.linesearch(ev_.measure, ev_.depth, ev_.norms.data(), groups_, &means_, &cnt, &_err)) fail_str(_err);
+            stats_.verify_pairs += cnt.pairs;
+            stats_.verify_redone += cnt.redone;
             check_flags(dev);
         } else {
             evaluate_means_generic(dev, ev_, gen_w_, gen_B, means_);
         }
         global_means(means_);
         stats_.ticks++;
-        stats_.groups += (fused_ || fullrank_) ? groups_.size() : gen_B;
+        stats_.groups += path_ != LS_NONE ? groups_.size() : gen_B;
         apply_results(-1, means_);
         return true;
     }
 
     // Up to max_ticks lock-step ticks; *ticks_done = how many happened.  Returns false when every restart had
-    // already converged before the last of them.  On the fused NDCG@k path the restarts are stepped as a few
-    // sets with one line search of each in flight (DeviceDataset::linesearch_ndcg_submit): while the host
+    // already converged before the last of them.  On the bound-and-verify paths the restarts are stepped as a few
+    // sets with one line search of each in flight (DeviceDataset::linesearch_submit): while the host
     // replays the accept logic of one set and stages its next tick, the device works on the others.  A
     // restart's trajectory does not depend on what it is batched with, so the results are the same as tick()'s;
     // every submitted line search is collected and applied before this returns.
@@ -1103,8 +1087,8 @@ class CATrainer {
             long want = pe ? atol(pe) : 3;
             want = std::min<long>(want, frdev::DeviceDataset::LINESEARCH_CONTEXTS);
             want = std::min<long>(want, (long)rs_.size());
-            const bool fr_resident = fullrank_ && resident_;  // (MRR, NDCG of any depth, MAP: bound-and-verify on resident sums)
-            parts_ = ((fused_ || fr_resident) && !shard_.allreduce && want >= 2) ? (int)want : 1;
+            const bool fr_resident = path_ == LS_FULLRANK && resident_;  // (MRR, NDCG of any depth, MAP: bound-and-verify on resident sums)
+            parts_ = ((path_ == LS_TOPK || fr_resident) && !shard_.allreduce && want >= 2) ? (int)want : 1;
         }
         if (parts_ < 2) {
             while (n < max_ticks && (alive = tick())) n++;
@@ -1122,7 +1106,6 @@ class CATrainer {
             const uint64_t budget = max_ticks - n;
             uint64_t steps[MAXP] = {};
             bool inflight[MAXP] = {};
-            bool ready[MAXP] = {};  // reciprocal rank: the set was evaluated in lock step (means_h_ already holds the result)
             bool stop = false;
             auto submit = [&](int h) {
                 size_t unused = 0;
@@ -1134,43 +1117,15 @@ class CATrainer {
                 stats_.line_searches++;
                 dev.set_sums_only(false);
                 std::string _err;
-                ready[h] = false;
-                if (fused_) {
-                    if (!dev.linesearch_ndcg_submit(h, ev_.depth, ev_.norms.data(), groups_h_[h], &_err)) fail_str(_err);
-                } else {
-                    bool queued = false;
-                    if (!dev.linesearch_fullrank_submit(h, ev_.measure, ev_.depth, ev_.norms.data(), groups_h_[h], &queued, &_err))
-                        fail_str(_err);
-                    if (!queued) {  // not applicable this tick (the device applied the pending resident updates): exact kernels
-                        for (frdev::LineGroup& lg : groups_h_[h]) lg.has_update = false;
-                        unsigned long long p0 = 0, r0 = 0, p1 = 0, r1 = 0;
-                        dev.verify_counters(&p0, &r0);
-                        if (!dev.linesearch_fullrank(ev_.measure, ev_.depth, ev_.norms.data(), groups_h_[h], &means_h_[h], &_err))
-                            fail_str(_err);
-                        dev.verify_counters(&p1, &r1);
-                        stats_.verify_pairs += p1 - p0;
-                        stats_.verify_redone += r1 - r0;
-                        ready[h] = true;
-                    }
-                }
+                if (!dev.linesearch_submit(h, ev_.measure, ev_.depth, ev_.norms.data(), groups_h_[h], &_err)) fail_str(_err);
                 inflight[h] = true;
-            };
-            auto collect = [&](int h) {
-                std::string _err;
-                if (ready[h]) return;
-                if (fused_) {
-                    if (!dev.linesearch_ndcg_collect(h, &means_h_[h], &_err)) fail_str(_err);
-                } else {
-                    if (!dev.linesearch_fullrank_collect(h, &means_h_[h], &_err)) fail_str(_err);
-                }
             };
             auto drain = [&]() {  // an error is on its way out: leave no submitted line search behind
                 for (int h = 0; h < parts_; h++)
-                    if (inflight[h] && !ready[h]) {
+                    if (inflight[h]) {
                         std::string _e;
                         std::vector<double> tmp;
-                        if (fused_) (void)dev.linesearch_ndcg_collect(h, &tmp, &_e);
-                        else (void)dev.linesearch_fullrank_collect(h, &tmp, &_e);
+                        (void)dev.linesearch_collect(h, &tmp, nullptr, &_e);
                         inflight[h] = false;
                     }
             };
@@ -1181,16 +1136,15 @@ class CATrainer {
                     for (int h = 0; h < parts_; h++) {
                         if (!inflight[h]) continue;
                         any = true;
-                        unsigned long long p0 = 0, r0 = 0, p1 = 0, r1 = 0;
-                        dev.verify_counters(&p0, &r0);
                         inflight[h] = false;
+                        frdev::DeviceDataset::LsCounts cnt;
                         {
                             HostTimer ht_(host_us_[1]);
-                            collect(h);
+                            std::string _err;
+                            if (!dev.linesearch_collect(h, &means_h_[h], &cnt, &_err)) fail_str(_err);
                         }
-                        dev.verify_counters(&p1, &r1);
-                        stats_.verify_pairs += p1 - p0;
-                        stats_.verify_redone += r1 - r0;
+                        stats_.verify_pairs += cnt.pairs;
+                        stats_.verify_redone += cnt.redone;
                         check_flags(dev);
                         stats_.groups += groups_h_[h].size();
                         {
@@ -1292,7 +1246,7 @@ class CATrainer {
             }
             double orig = r.base[f];
             line_candidates(orig, p_, r.cands, r.block_len);
-            if (fused_ || fullrank_) {
+            if (path_ != LS_NONE) {
                 r.first_group = groups.size();
                 for (size_t c0 = 0; c0 < r.cands.size(); c0 += 64) {
                     frdev::LineGroup lg;
@@ -1341,7 +1295,7 @@ class CATrainer {
             long accepted = -1;  // index of the last accepted candidate of this line search
             for (int s = 0; s < 3; s++) {
                 for (uint32_t it = 0; it < r.block_len[s]; it++, c++) {
-                    double sc = (fused_ || fullrank_) ? means[(r.first_group + c / 64) * 64 + (c % 64)]
+                    double sc = path_ != LS_NONE ? means[(r.first_group + c / 64) * 64 + (c % 64)]
                                                       : means[r.first_group + c];
                     stats_.useful_evals++;
                     if (sc == sc && sc > r.best_score) {  // core.rs:57-66: NaN rejected, strict >
@@ -1496,8 +1450,9 @@ class CATrainer {
     QueryShard shard_;
     size_t d_ = 0;
     uint32_t model_dim_ = 0;
-    bool fused_ = false;
-    bool fullrank_ = false;
+    static constexpr frdev::DeviceDataset::LsPath LS_NONE = frdev::DeviceDataset::LS_NONE, LS_TOPK = frdev::DeviceDataset::LS_TOPK,
+                                                  LS_FULLRANK = frdev::DeviceDataset::LS_FULLRANK;
+    frdev::DeviceDataset::LsPath path_ = LS_NONE;  // bound-and-verify path of the line searches (LS_NONE: the general sort evaluator)
     int slot_ = 0, device_ = -1;
     bool resident_ = false;
     uint64_t res_owner_ = 0;
