@@ -107,9 +107,11 @@ struct DeviceDataset::Impl {
         DevBuf<double> fv_rows;  // score rows of this context's redo slots (contexts run concurrently: no sharing)
         size_t ldm = 0, maxc = 0, lds = 0;
         int64_t depth = 0;
+        int measure = 0;
         int xs_used = 1;         // list length variant of the pending verify launch
         bool xs_pinned = false;  // ... chosen by FR_VERIFY_XS
         bool audit = false;      // FR_VERIFY_AUDIT
+        std::vector<LineGroup> agroups;  // ... full ranking / reciprocal rank: the groups of the pending line search, for fr_audit
         unsigned redo_grid = 512, redo_grid_used = 512;  // pairs the exact kernels' fixed first launch takes (NDCG@k: adapts to the redo counts seen)
         // NDCG@k per-group routing: the pending line search staged its groups as [verify groups | exact groups];
         // gorder[k] = the caller's index of staged group k (empty: the caller's order), gslot[k] = its resident slot
@@ -129,6 +131,8 @@ struct DeviceDataset::Impl {
     bool ls_collect(LsCtx& c, std::vector<double>* means, std::string* err);
     bool topk_policy(LsCtx& c, uint32_t nredo, uint32_t nslices, std::string* err);
     bool ls_exact(LsCtx& c, int measure, int64_t depth, const double* norms, const std::vector<LineGroup>& groups, std::string* err);
+    bool exact_kernels(const std::vector<LineGroup>& groups, int measure, int64_t depth, size_t maxc, double* M, int* flags, std::string* err);
+    bool fr_audit(LsCtx& c, std::string* err);
     bool ls_means(LsCtx& c, std::string* err);
     bool tick_begin(LsCtx& c, const std::vector<LineGroup>& groups, std::string* err);
     bool tick_upload(LsCtx& c, bool with_eps2, std::string* err);
@@ -166,6 +170,7 @@ struct DeviceDataset::Impl {
     unsigned long long audit_values = 0, audit_mismatches = 0;  // FR_VERIFY_AUDIT=1: published values re-derived by the exact kernel
     DevBuf<double> audit;
     DevBuf<unsigned long long> audit_cnt;
+    DevBuf<int> audit_flags;  // (the exact kernels' flags of an audit: the published ones are not touched)
     unsigned long long exact_fallbacks = 0;                // line searches evaluated by the exact kernels alone (every group routed there, or approx_skip)
     std::vector<uint32_t> perm_host;   // [np] original instance id or IDX_INVALID (padding, or not part of this view)
     std::vector<uint32_t> qstart_h, qlen_h, qnpos_h, qnneg_h;  // host copies (views of this dataset are cut from them)
@@ -2638,6 +2643,7 @@ bool DeviceDataset::Impl::ls_submit(LsCtx& c, int path, int measure, int64_t dep
     c.ldm = G * 64;
     c.maxc = maxc;
     c.depth = depth;
+    c.measure = measure;
     c.approx = c.ready = false;
     c.nverify = 0;
     c.gorder.clear();
@@ -3069,14 +3075,15 @@ bool DeviceDataset::Impl::ls_submit(LsCtx& c, int path, int measure, int64_t dep
     c.gslot.assign(G, -1);  // (top-k: the restarts the policies at collect steer)
     if (resident)
         for (size_t k = 0; k < G; k++) c.gslot[k] = groups[k].resident_slot;
+    c.agroups.clear();
+    if (c.audit && approx && c.kind != LSK_TOPK) c.agroups.assign(groups.begin(), groups.end());  // (fr_audit scores their weights from the tiles)
     c.approx = approx;
     c.nverify = approx ? nV : 0;
     c.pending = true;
     return true;
 }
 
-// The exact kernels alone: the scores kernel and the rank-counting kernel on the main stream, in chunks of groups whose score
-// rows take at most half of the free HBM.  A context of its own hands the groups, their resident updates applied, to the
+// The exact kernels alone (exact_kernels), then the means.  A context of its own hands the groups, their resident updates applied, to the
 // lock-step form on the main stream's context, which tries bound-and-verify once more before it comes here (the skip
 // counter has moved on: the last tick of a back-off verifies again).
 bool DeviceDataset::Impl::ls_exact(LsCtx& c, int measure, int64_t depth, const double* norms, const std::vector<LineGroup>& groups,
@@ -3091,9 +3098,28 @@ bool DeviceDataset::Impl::ls_exact(LsCtx& c, int measure, int64_t depth, const d
         c.ready = c.pending = true;
         return true;
     }
-    const size_t G = groups.size(), dp = m.dq * 4, ldm = G * 64, maxc = c.maxc;
+    const size_t G = groups.size(), ldm = G * 64;
     std::vector<double>& means = c.exact_means;
     means.assign(ldm, 0.0);
+    if (!m.M.ensure(m.nq * ldm, err) || !m.norms.ensure(m.nq, err) || !m.means.ensure(ldm, err)) return false;
+    if (!m.upload_norms(norms, err)) return false;
+    if (!m.exact_kernels(groups, measure, depth, c.maxc, m.M.p, m.flags.p, err)) return false;
+    if (!launch_means(m.M.p, ldm, ldm, m.nq, m.sums_only, m.partial, m.means, m.stream, err)) return false;
+    FR_HIP(hipMemcpyAsync(means.data(), m.means.p, ldm * sizeof(double), hipMemcpyDeviceToHost, m.stream));
+    m.last_ldm = ldm;
+    m.last_cols = ldm;
+    m.last_M = m.M.p;
+    if (!m.pull_flags(err)) return false;
+    c.ready = c.pending = true;
+    return true;
+}
+
+// The exact kernels of ls_exact into M (nq x groups * 64, the main stream's norms): the scores kernel and the rank-counting
+// kernel on the main stream, in chunks of groups whose score rows take at most half of the free HBM.
+bool DeviceDataset::Impl::exact_kernels(const std::vector<LineGroup>& groups, int measure, int64_t depth, size_t maxc, double* M,
+                                        int* flags, std::string* err) {
+    Impl& m = *this;
+    const size_t G = groups.size(), dp = m.dq * 4, ldm = G * 64;
     const size_t row_bytes = 64 * sizeof(double);
     size_t budget = m.rows.bytes();
     if (G * m.np * row_bytes > budget) {  // the buffer has to grow: see what is there (it is released first)
@@ -3102,11 +3128,9 @@ bool DeviceDataset::Impl::ls_exact(LsCtx& c, int measure, int64_t depth, const d
         budget = std::max<size_t>(size_t(1) << 30, (free_b + m.rows.bytes()) / 2);
     }
     size_t GC = std::max<size_t>(1, std::min<size_t>(G, budget / (m.np * row_bytes)));
-    if (!m.M.ensure(m.nq * ldm, err) || !m.norms.ensure(m.nq, err) || !m.rows.ensure(m.np * GC * 64, err) ||
-        !m.gfeat.ensure(GC, err) || !m.gncand.ensure(GC, err) || !m.gw.ensure(GC * dp, err) ||
-        !m.gcand.ensure(GC * 64, err) || !m.means.ensure(ldm, err))
+    if (!m.rows.ensure(m.np * GC * 64, err) || !m.gfeat.ensure(GC, err) || !m.gncand.ensure(GC, err) || !m.gw.ensure(GC * dp, err) ||
+        !m.gcand.ensure(GC * 64, err))
         return false;
-    if (!m.upload_norms(norms, err)) return false;
     for (size_t g0 = 0; g0 < G; g0 += GC) {
         const size_t gc = std::min(GC, G - g0);
         std::vector<uint32_t> gfeat(gc), gncand(gc);
@@ -3125,11 +3149,11 @@ bool DeviceDataset::Impl::ls_exact(LsCtx& c, int measure, int64_t depth, const d
         FR_HIP(hipStreamSynchronize(m.stream));  // the staging vectors are locals
         {
             ProfScope ps("linesearch_scores_kernel", m.stream);
-            const FSArgs fa = m.scores_args(m.gfeat.p, m.gw.p, m.gcand.p, m.rows.p, m.flags.p, gc);
+            const FSArgs fa = m.scores_args(m.gfeat.p, m.gw.p, m.gcand.p, m.rows.p, flags, gc);
             launch_scores(fa, maxc, (unsigned)(((m.nruns + 7) / 8) * 8 * gc), 2 * dp * sizeof(double), m.stream);
         }
         FR_HIP(hipGetLastError());
-        RMArgs ra = m.rank_args(m.rows.p, m.gncand.p, m.M.p, m.flags.p, gc, ldm, measure, depth);
+        RMArgs ra = m.rank_args(m.rows.p, m.gncand.p, M, flags, gc, ldm, measure, depth);
         ra.col0 = (uint32_t)(g0 * 64);
         {
             ProfScope ps("rank_metric_kernel", m.stream);
@@ -3148,13 +3172,6 @@ bool DeviceDataset::Impl::ls_exact(LsCtx& c, int measure, int64_t depth, const d
         }
         FR_HIP(hipGetLastError());
     }
-    if (!launch_means(m.M.p, ldm, ldm, m.nq, m.sums_only, m.partial, m.means, m.stream, err)) return false;
-    FR_HIP(hipMemcpyAsync(means.data(), m.means.p, ldm * sizeof(double), hipMemcpyDeviceToHost, m.stream));
-    m.last_ldm = ldm;
-    m.last_cols = ldm;
-    m.last_M = m.M.p;
-    if (!m.pull_flags(err)) return false;
-    c.ready = c.pending = true;
     return true;
 }
 
@@ -3189,6 +3206,7 @@ bool DeviceDataset::Impl::ls_collect(LsCtx& c, std::vector<double>* means, std::
                 break;
             default:  // many pairs redone: the exact kernels take the next 16 line searches
                 if ((size_t)nredo * 4 > m.nq * G) m.approx_skip = 16;
+                if (c.audit && !m.fr_audit(c, err)) return false;
                 break;
         }
     }
@@ -3206,6 +3224,39 @@ bool DeviceDataset::Impl::ls_collect(LsCtx& c, std::vector<double>* means, std::
         fprintf(stderr, "[FR_LS_DEBUG] docs=%llu rows=%llu (%.3f of docs) batches=%llu insertion_rows=%llu\n", cnt[3], cnt[0],
                 (double)cnt[0] / (double)cnt[3], cnt[1], cnt[2]);
     }
+    return true;
+}
+
+// Full ranking / reciprocal rank under FR_VERIFY_AUDIT, after a verified line search and its long-redo pass: every value it
+// published (verified, or recomputed from the redo list by the work-list kernels) against ls_exact's kernels run over ALL
+// (query, group) pairs of the same groups, bit for bit.  Those write into a matrix of their own, so the published one, the
+// means and every counter but audit_* stay as they are.  It starts as all-ones words (a NaN no metric value has): a cell the
+// exact kernels leave unwritten differs.  The columns beyond each group's candidates (defined by neither side) are copied
+// from the published matrix and not counted.  The exact kernels read the norms on the device: those of this line search
+// (ls_submit uploaded them for the full-ranking kind, whose trainer's norms never change; reciprocal rank reads none).
+bool DeviceDataset::Impl::fr_audit(LsCtx& c, std::string* err) {
+    Impl& m = *this;
+    const size_t nel = m.nq * c.ldm;
+    if (!m.audit.ensure(nel, err) || !m.audit_cnt.ensure(1, err) || !m.audit_flags.ensure(1, err)) return false;
+    FR_HIP(hipMemsetAsync(m.audit.p, 0xFF, nel * sizeof(double), m.stream));
+    size_t ncells = 0;
+    for (size_t g = 0; g < c.agroups.size(); g++) {
+        const size_t nc = c.agroups[g].candidates.size();
+        ncells += m.nq * nc;
+        if (nc < 64)  // (c.M is final: collected)
+            FR_HIP(hipMemcpy2DAsync(m.audit.p + g * 64 + nc, c.ldm * sizeof(double), c.M.p + g * 64 + nc, c.ldm * sizeof(double),
+                                    (64 - nc) * sizeof(double), m.nq, hipMemcpyDeviceToDevice, m.stream));
+    }
+    FR_HIP(hipMemsetAsync(m.audit_flags.p, 0, sizeof(int), m.stream));
+    if (!m.exact_kernels(c.agroups, c.measure, c.depth, c.maxc, m.audit.p, m.audit_flags.p, err)) return false;
+    FR_HIP(hipMemsetAsync(m.audit_cnt.p, 0, sizeof(unsigned long long), m.stream));
+    audit_compare_kernel<<<dim3(1024), dim3(256), 0, m.stream>>>(m.audit.p, c.M.p, nel, m.audit_cnt.p);
+    FR_HIP(hipGetLastError());
+    unsigned long long bad = 0;
+    FR_HIP(hipMemcpyAsync(&bad, m.audit_cnt.p, sizeof(bad), hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipStreamSynchronize(m.stream));
+    m.audit_values += ncells;
+    m.audit_mismatches += bad;
     return true;
 }
 

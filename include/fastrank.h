@@ -158,8 +158,9 @@ const CResult *fr_select_model(const void *restarts_json, int output_ensemble);
  * bound-and-verify kernels and how many of them were recomputed by the exact kernels -- NDCG@k recomputes only the
  * 16-candidate slices of a pair that hold an undecided candidate: verify_redo_entries counts those; exact_ticks of
  * line_searches batched line searches went to the exact kernels alone, exact_groups of groups single restarts' line
- * searches were routed there while the rest of their tick stayed on the verify kernel; audit_*: with FR_VERIFY_AUDIT=1 every published NDCG@k
- * value is recomputed by the exact kernel and compared bit for bit -- values compared / values that differed). */
+ * searches were routed there while the rest of their tick stayed on the verify kernel; audit_*: with FR_VERIFY_AUDIT=1 every value a
+ * bound-and-verify line search publishes (NDCG@k, full ranking, reciprocal rank) is recomputed by the exact kernels and
+ * compared bit for bit -- values compared / values that differed). */
 const void *fr_last_train_stats(void);
 
 /* Dense results without JSON.  out[i] = score of instance i (instances outside the dataset

@@ -24,6 +24,27 @@ def _shape(name):
     return _CACHE[name]
 
 
+def _kind30(kind):
+    """(X, y, qid, device dataset) of the 30K shape; kind "tiesmix": duplicate rows with labels of their own and integer
+    columns (bench.gen_mslr_shaped), cached like _shape's."""
+    if kind == "mslr":
+        return _shape("30k")[1:]
+    key = "30k/" + kind
+    if key not in _CACHE:
+        n, d, q, seed = bench.SHAPES["30k"]
+        X, y, qid = bench.gen_mslr_shaped(seed, n, d, q, kind)
+        _CACHE[key] = (X, y, qid, fr.CDataset.from_numpy(X, y, qid))
+    return _CACHE[key]
+
+
+def _oracle30(kind):
+    key = "30k/" + kind + "/oracle"
+    if key not in _CACHE:
+        X, y, qid, _ = _kind30(kind)
+        _CACHE[key] = o.Dataset(X, y, qid)
+    return _CACHE[key]
+
+
 @pytest.fixture(scope="module", params=["10k", "30k"])
 def big(request):
     return _shape(request.param)
@@ -158,12 +179,7 @@ def test_resident_training_equals_the_oracle_at_the_30k_shape(kind):
     must be what the CPU restatement of evaluate_mean (src/evaluators.rs:173-224, src/dense_dataset.rs:67-76) gives
     for that restart's best weights, bit for bit (oracle in the HIP path's 256-query summation shape).  tiesmix =
     duplicate rows and integer columns, i.e. the variant with duplicate groups."""
-    n, d, q, seed = bench.SHAPES["30k"]
-    if kind == "mslr":
-        _, X, y, qid, g = _shape("30k")
-    else:
-        X, y, qid = bench.gen_mslr_shaped(seed, n, d, q, kind)
-        g = fr.CDataset.from_numpy(X, y, qid)
+    X, y, qid, g = _kind30(kind)
     req = fr.TrainRequest.coordinate_ascent()
     req.measure = "ndcg@10"
     req.params.seed, req.params.quiet, req.params.num_restarts = 5, True, 4
@@ -173,7 +189,7 @@ def test_resident_training_equals_the_oracle_at_the_30k_shape(kind):
     run.close()
     if not os.environ.get("FR_LS_EXACT"):
         assert st["stats"]["verify_pairs"] > 0 and st["stats"]["exact_groups"] * 2 < st["stats"]["groups"], st["stats"]
-    c = o.Dataset(X, y, qid)
+    c = _oracle30(kind)
     o.set_mean_segment(o.DEVICE_MEAN_SEGMENT)
     try:
         for r in st["restarts"]:
@@ -189,12 +205,7 @@ def test_every_resident_verify_variant_runs_at_the_30k_shape(kind, monkeypatch):
     under load -- while every small-size parity test of it passed.  So every resident variant (depth 5 / 10 / 20 x list
     length K+1..K+4, without and with duplicate groups = tiesmix) takes a few ticks of real training on the whole matrix
     here, and every value it publishes is recomputed by the exact kernel (FR_VERIFY_AUDIT: bit for bit, 0 mismatches)."""
-    n, d, q, seed = bench.SHAPES["30k"]
-    if kind == "mslr":
-        g = _shape("30k")[4]
-    else:
-        X, y, qid = bench.gen_mslr_shaped(seed, n, d, q, kind)
-        g = fr.CDataset.from_numpy(X, y, qid)
+    g = _kind30(kind)[3]
     monkeypatch.setenv("FR_VERIFY_AUDIT", "1")
     for measure in ("ndcg@5", "ndcg@10", "ndcg@20"):
         for xs in ("1", "2", "3", "4"):
@@ -209,6 +220,124 @@ def test_every_resident_verify_variant_runs_at_the_30k_shape(kind, monkeypatch):
             if not os.environ.get("FR_LS_EXACT"):
                 assert st["verify_pairs"] > 0 and st["audit_values"] > 0, (kind, measure, xs, st)
             assert st["audit_mismatches"] == 0, (kind, measure, xs, st)
+
+
+# the measures the full-ranking verify kernel (NDCG without a depth, AP, NDCG beyond depth 20) and the reciprocal-rank
+# verify kernel train
+_FULLRANK_MEASURES = ("ndcg", "map", "mrr", "ndcg@30")
+
+
+def _fullrank_verify_on(measure):
+    """The full-ranking / reciprocal-rank verify kernel runs (not under FR_LS_EXACT, RR not without resident sums,
+    the full-ranking one not under FR_FV_OFF): the suite is also run under those switches."""
+    if os.environ.get("FR_LS_EXACT"):
+        return False
+    if measure == "mrr":
+        return os.environ.get("FR_LS_RESIDENT", "1")[:1] != "0"
+    return not os.environ.get("FR_FV_OFF")
+
+
+@pytest.mark.parametrize("kind", ["mslr", "tiesmix"])
+@pytest.mark.parametrize("measure", _FULLRANK_MEASURES)
+def test_fullrank_and_rr_training_equal_the_oracle_at_the_30k_shape(measure, kind):
+    """fullrank_verify_kernel / rr_verify_kernel on resident sums against the ORACLE on the whole 3.8 M x 136 matrix:
+    after 25 ticks every restart's best_score is what the CPU restatement of evaluate_mean gives for that restart's best
+    weights, bit for bit (oracle in the HIP path's 256-query summation shape), as for NDCG@10 above."""
+    X, y, qid, g = _kind30(kind)
+    req = fr.TrainRequest.coordinate_ascent()
+    req.measure = measure
+    req.params.seed, req.params.quiet, req.params.num_restarts = 5, True, 4
+    run = native.CoordinateAscentRun(g, req)
+    run.step(25)
+    st = run.state()
+    run.close()
+    assert st["stats"]["path"] == "fused_fullrank"
+    if _fullrank_verify_on(measure):
+        assert st["stats"]["verify_pairs"] > 0, st["stats"]
+    c = _oracle30(kind)
+    o.set_mean_segment(o.DEVICE_MEAN_SEGMENT)
+    try:
+        for r in st["restarts"]:
+            assert c.evaluate_mean(measure, np.asarray(r["weights"])) == r["score"], (measure, kind, r["restart_id"])
+    finally:
+        o.set_mean_segment(0)
+
+
+def _audited_stats(g, measure, restarts=6, steps=3):
+    req = fr.TrainRequest.coordinate_ascent()
+    req.measure = measure
+    req.params.seed, req.params.quiet, req.params.num_restarts = 11, True, restarts
+    run = native.CoordinateAscentRun(g, req)
+    run.step(steps)
+    st = run.state()["stats"]
+    run.close()
+    return st
+
+
+@pytest.mark.parametrize("kind", ["mslr", "tiesmix"])
+def test_every_fullrank_and_rr_verify_variant_runs_at_the_30k_shape(kind, monkeypatch):
+    """The full-ranking and reciprocal-rank verify kernels at the size where they run (a verify variant once faulted at the
+    30K shape only): a few ticks of real training for each of their measures, every value they publish recomputed by the
+    exact kernels (FR_VERIFY_AUDIT: bit for bit, 0 mismatches).  On tiesmix the DUP instantiations take the mixed-label
+    duplicates: NDCG on two fresh uploads of the matrix, with the duplicate-group rule and without it (FR_NO_DUP_GROUPS=1,
+    read when the device dataset is built, i.e. at its first use), both audited; with the rule at least 20 times fewer
+    pairs are redone (measured over these 3 ticks: 7 560 with the rule, 165 086 without it, where the many redone pairs
+    also send 12 line searches to the exact kernels)."""
+    g = _kind30(kind)[3]
+    monkeypatch.setenv("FR_VERIFY_AUDIT", "1")
+    for measure in _FULLRANK_MEASURES:
+        st = _audited_stats(g, measure)
+        if _fullrank_verify_on(measure):
+            assert st["verify_pairs"] > 0 and st["audit_values"] > 0, (kind, measure, st)
+        assert st["audit_mismatches"] == 0, (kind, measure, st)
+    if kind != "tiesmix":
+        return
+    X, y, qid, _ = _kind30(kind)
+    redone = {}
+    for rule in (True, False):
+        if not rule:
+            monkeypatch.setenv("FR_NO_DUP_GROUPS", "1")
+        fresh = fr.CDataset.from_numpy(X, y, qid)
+        st = _audited_stats(fresh, "ndcg")
+        del fresh
+        if _fullrank_verify_on("ndcg"):
+            assert st["verify_pairs"] > 0 and st["audit_values"] > 0, (rule, st)
+        assert st["audit_mismatches"] == 0, (rule, st)
+        redone[rule] = st["verify_redone"]
+    monkeypatch.delenv("FR_NO_DUP_GROUPS")
+    if _fullrank_verify_on("ndcg"):
+        assert redone[True] * 20 < redone[False], ("pairs redone with / without duplicate groups", redone[True], redone[False])
+
+
+@pytest.mark.parametrize("measure", _FULLRANK_MEASURES)
+def test_stateless_fullrank_and_rr_per_query_values_at_the_30k_shape(measure):
+    """Stateless line searches (sums from the tiles) on tiesmix, every query: group 0 has random weights, group 1 all its
+    weight on the integer column 1 (exact ties across gain classes; its candidate 0.0 on column 5 scores with column 1
+    alone).  For the base weights (put in front of the candidates), the zeroed coordinate, both ends of the line (the last
+    negative and the last positive step) and one step in between, the per-query column equals the oracle's
+    metric_from_scores for all 31 000 queries, bit for bit."""
+    X, y, qid, g = _kind30("tiesmix")
+    c = _oracle30("tiesmix")
+    d = X.shape[1]
+    rng = np.random.default_rng(109)
+    w = rng.uniform(-1, 1, d)
+    w /= np.abs(w).sum()
+    tied = np.zeros(d)
+    tied[1] = 1.0
+    feats, bases = [17, 5], np.asarray([w, tied])
+    cands = [np.concatenate(([b[f]], o.ca_candidates(b[f], 0.05, 2.0, 25))) for f, b in zip(feats, bases)]
+    _, pq = native.evaluate_candidates(g, measure, feats, bases, cands, per_query=True)
+    assert pq.shape == (31_000, 2 * 64)
+    norms = c.default_norms(measure)
+    for gi in range(2):
+        last = len(cands[gi]) - 1
+        for ci in (0, 1, 13, 26, last):
+            ww = bases[gi].copy()
+            ww[feats[gi]] = cands[gi][ci]
+            exp, err = c.metric_from_scores(measure, c.score_linear(ww), norms)
+            assert err == 0
+            got = pq[:, gi * 64 + ci]
+            assert np.array_equal(got, exp), (measure, gi, ci, np.flatnonzero(got != exp)[:10])
 
 
 # ------------------------------------------------- BASELINE.json configs[4]: 500 trees x 30K shape

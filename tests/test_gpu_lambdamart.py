@@ -113,6 +113,85 @@ def test_stagewise_identity_trec(trec):
     _stagewise(g, c, X, y, "ndcg@10", 20, dict(max_depth=5, min_leaf_support=5, split_candidates=16, learning_rate=0.1))
 
 
+_LABEL_P = [0.515, 0.324, 0.134, 0.019, 0.008]
+
+
+def _long_query_set():
+    """Queries beyond the LDS budget of lambda_grad_kernel (LM_LDS_MAX: 4 096 documents) take a per-block global slab.
+    Here 4 095 and 4 096 documents (LDS, the second at its limit), 4 097, 4 099 and 6 001 (slab), 5 000 without a positive
+    label (slab, the zero branch), and 1, 2 and 300.  Slab launch order (longest first): 6 001, 5 000, 4 099, 4 097.  A slab
+    block holds 36 * max_len bytes and max_len = 6 001 is odd, so the f64 arrays of block 3 (the 4 097-document query)
+    start 4 bytes off 8-byte alignment."""
+    rng = np.random.default_rng(43)
+    lens = [300, 4097, 1, 6001, 4095, 5000, 2, 4099, 4096]
+    qid = np.repeat(np.arange(1, len(lens) + 1, dtype=np.int64), lens)
+    n = len(qid)
+    y = rng.choice(5, size=n, p=_LABEL_P).astype(np.float64)
+    y[qid == 6] = 0.0
+    X = np.empty((n, 6), dtype=np.float32)
+    X[:, 0] = rng.random(n) + 0.3 * y
+    X[:, 1] = np.floor(rng.exponential(2.0, n))  # integer columns: tied scores
+    X[:, 2] = rng.lognormal(0.0, 2.0, n)
+    X[:, 3] = np.where(rng.random(n) < 0.7, 0.0, rng.random(n))
+    X[:, 4] = rng.integers(0, 5, n)
+    X[:, 5] = rng.normal(0.0, 1.0, n)
+    return X, y, qid
+
+
+@pytest.mark.parametrize("measure", ["ndcg", "ndcg@10", "ndcg@5000"])
+def test_gradient_kernel_on_queries_longer_than_lds(measure):
+    X, y, qid = _long_query_set()
+    g, c = fr.CDataset.from_numpy(X, y, qid), o.Dataset(X, y, qid)
+    model = fr.CModel.from_dict({"Linear": {"weights": [0.25, 1.0, 0.0, 0.0, 0.5, 0.0]}})
+    lam, wt = _check_gradients(g, c, X, y, model, measure, c.default_norms(measure), sigma=1.5)
+    assert np.all(lam[qid == 6] == 0.0) and np.all(wt[qid == 6] == 0.0)
+    assert np.all(lam[qid == 3] == 0.0) and np.all(wt[qid == 3] == 0.0)
+    for q in (1, 2, 4, 5, 8, 9):
+        assert np.any(lam[qid == q] != 0.0), q
+
+
+def test_stagewise_identity_on_queries_longer_than_lds():
+    X, y, qid = _long_query_set()
+    g, c = fr.CDataset.from_numpy(X, y, qid), o.Dataset(X, y, qid)
+    _stagewise(g, c, X, y, "ndcg@10", 3, dict(max_depth=3, min_leaf_support=20, split_candidates=8, learning_rate=0.1))
+
+
+def test_gradient_kernel_on_more_slab_queries_than_one_launch_takes():
+    """1 030 queries of 4 097 - 4 099 documents: all in the slab, launched LM_SLAB_BLOCKS = 1 024 at a time, so a second
+    launch starts at q_first = 1 024 (max_len 4 099: every odd block misaligned).  Launch order is longest first and
+    stable; the queries at launch order 0, 1 023 (the first launch's last block), 1 024 (the second launch's first) and
+    1 029 (the last) are restated, every query's gradients are finite and sum to ~0."""
+    rng = np.random.default_rng(47)
+    nq = 1030
+    lens = rng.integers(4097, 4100, nq)
+    lens[517] = 4099
+    qid = np.repeat(np.arange(1, nq + 1, dtype=np.int64), lens)
+    n = len(qid)
+    y = rng.choice(5, size=n, p=_LABEL_P).astype(np.float64)
+    X = np.stack([rng.random(n) + 0.3 * y, np.floor(rng.exponential(2.0, n))], axis=1).astype(np.float32)
+    g, c = fr.CDataset.from_numpy(X, y, qid), o.Dataset(X, y, qid)
+    model = fr.CModel.from_dict({"Linear": {"weights": [1.0, 0.5]}})
+    measure = "ndcg@10"
+    lam, wt = native.lambda_gradients(model, g, measure, 1.0)
+    assert np.all(np.isfinite(lam)) and np.all(np.isfinite(wt))
+    queries = lm.query_lists(c)
+    qlen = [len(ids) for ids in queries]
+    order = sorted(range(nq), key=lambda q: -qlen[q])  # (stable, as the launch order)
+    pick = [order[0], order[1023], order[1024], order[-1]]
+    norms = c.default_norms(measure)
+    scores = native.predict_scores_dense(model, g)
+    elam, ewt = lm.gradients(scores, y, [queries[q] for q in pick], norms[pick], lm.depth_of(measure), 1.0)
+    for q in pick:
+        ids = queries[q]
+        for got, exp in ((lam[ids], elam[ids]), (wt[ids], ewt[ids])):
+            zero = exp == 0.0
+            assert np.array_equal(got[zero], exp[zero]), q
+            np.testing.assert_allclose(got, exp, rtol=1e-12, atol=0.0)
+        assert np.any(lam[ids] != 0.0), q
+    for ids in queries:
+        assert abs(lam[ids].sum()) <= 1e-9 * max(1.0, np.abs(lam[ids]).sum())
+
+
 def test_stagewise_identity_synthetic():
     X, y, qid = synth_dataset(7, 5000, 10, 50)
     g, c = fr.CDataset.from_numpy(X, y, qid), o.Dataset(X, y, qid)

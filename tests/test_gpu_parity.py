@@ -1445,14 +1445,9 @@ def test_fullrank_training_by_sort_and_verify(small, measure, ties):
     assert st["useful_evals"] == int(exp_e.sum())
 
 
-@pytest.mark.parametrize("measure", ["ndcg", "map", "ndcg@25", "ndcg@150"])
-def test_fullrank_verify_decides_mixed_label_duplicates(measure, monkeypatch):
-    """Round 6: bit-identical rows with DIFFERENT labels inside a query (their exact scores tie under every weight vector, the
-    reference orders them by gain ascending, src/evaluators.rs:34-49).  The sort-and-verify kernel's DUP instantiations carry
-    the duplicate-group id in the keys and accept a cluster whose pairs all belong to one group; without the rule
-    (FR_NO_DUP_GROUPS=1 when the dataset is made) every such pair goes to the exact kernels.  Same trajectory either way, the
-    oracle's; far fewer pairs redone with the rule.  Queries of 30-400 documents: single- and multi-lane size classes; the
-    depths 25 and 150 cut the lists in their first lane and in later ones (only clusters that reach into the cut matter)."""
+def _mixed_label_duplicates_set():
+    """24 queries of 30-400 documents; a fifth of every query's documents are copies of others of the query, with labels
+    of their own."""
     rng = np.random.default_rng(41)
     lens = rng.integers(30, 400, 24)
     qid = np.repeat(np.arange(1, len(lens) + 1, dtype=np.int64), lens)
@@ -1465,6 +1460,18 @@ def test_fullrank_verify_decides_mixed_label_duplicates(measure, monkeypatch):
         src, dst = start + rng.integers(0, L, k), start + rng.integers(0, L, k)
         X[dst] = X[src]
         start += int(L)
+    return X, y, qid
+
+
+@pytest.mark.parametrize("measure", ["ndcg", "map", "ndcg@25", "ndcg@150"])
+def test_fullrank_verify_decides_mixed_label_duplicates(measure, monkeypatch):
+    """Round 6: bit-identical rows with DIFFERENT labels inside a query (their exact scores tie under every weight vector, the
+    reference orders them by gain ascending, src/evaluators.rs:34-49).  The sort-and-verify kernel's DUP instantiations carry
+    the duplicate-group id in the keys and accept a cluster whose pairs all belong to one group; without the rule
+    (FR_NO_DUP_GROUPS=1 when the dataset is made) every such pair goes to the exact kernels.  Same trajectory either way, the
+    oracle's; far fewer pairs redone with the rule.  Queries of 30-400 documents: single- and multi-lane size classes; the
+    depths 25 and 150 cut the lists in their first lane and in later ones (only clusters that reach into the cut matter)."""
+    X, y, qid = _mixed_label_duplicates_set()
     c = o.Dataset(X, y, qid)
     req = fr.TrainRequest.coordinate_ascent()
     req.measure = measure
@@ -1488,11 +1495,10 @@ def test_fullrank_verify_decides_mixed_label_duplicates(measure, monkeypatch):
         assert redone[True][1] > 0 and redone[True][0] * 4 < redone[False][0], redone
 
 
-@pytest.mark.parametrize("measure", ["ndcg", "map", "ndcg@100"])
-def test_fullrank_verify_every_size_class(measure):
-    """Queries of 1 .. 2048 documents cover every instantiation of the sort kernel (16/32/64 keys in one lane; 2, 4,
-    8, 16, 32 lanes per candidate with cross-lane merge rounds), with negative gains, a query without relevant
-    documents, and near-duplicate columns: per-query values against the oracle, stateless (sums from the tiles)."""
+def _every_size_class_set():
+    """Queries of 1 .. 2048 documents, an integer column (3), a sparse column (7), a query without relevant documents (5)
+    and one with negative gains (12); the generator is left where the groups of test_fullrank_verify_every_size_class
+    start."""
     lens = np.array([1, 2, 7, 15, 16, 17, 31, 33, 63, 64, 65, 100, 128, 129, 200, 256, 300, 511, 513, 1000, 1025, 2048, 40])
     rng = np.random.default_rng(71)
     qid = np.repeat(np.arange(1, len(lens) + 1, dtype=np.int64), lens)
@@ -1503,6 +1509,16 @@ def test_fullrank_verify_every_size_class(measure):
     y = rng.choice([0.0, 0.0, 1.0, 2.0, 3.0, 4.0], n)
     y[qid == 5] = 0.0
     y[(qid == 12) & (y == 0)] = -1.0
+    return X, y, qid, rng
+
+
+@pytest.mark.parametrize("measure", ["ndcg", "map", "ndcg@100"])
+def test_fullrank_verify_every_size_class(measure):
+    """Queries of 1 .. 2048 documents cover every instantiation of the sort kernel (16/32/64 keys in one lane; 2, 4,
+    8, 16, 32 lanes per candidate with cross-lane merge rounds), with negative gains, a query without relevant
+    documents, and near-duplicate columns: per-query values against the oracle, stateless (sums from the tiles)."""
+    X, y, qid, rng = _every_size_class_set()
+    d = X.shape[1]
     g, c = fr.CDataset.from_numpy(X, y, qid), o.Dataset(X, y, qid)
     feats, bases, cands = _ca_groups(rng, d, 4, iters=25)
     feats[0], feats[1] = 3, 7
@@ -1520,6 +1536,65 @@ def test_fullrank_verify_every_size_class(measure):
             exp, err = c.metric_from_scores(measure, c.score_linear(w), norms)
             assert err == 0
             assert np.array_equal(pq[:, gi * 64 + ci], exp), (measure, gi, ci, np.nonzero(pq[:, gi * 64 + ci] != exp)[0])
+
+
+_AUDIT_SETS = {"every_size_class": lambda: _every_size_class_set()[:3], "mixed_label_duplicates": _mixed_label_duplicates_set}
+
+
+def _audited_request(measure):
+    req = fr.TrainRequest.coordinate_ascent()
+    req.measure = measure
+    p = req.params
+    p.seed, p.quiet, p.num_restarts, p.num_max_iterations = 29, True, 3, 4
+    return req
+
+
+def _fullrank_or_rr_verify_on(measure):
+    """The full-ranking or reciprocal-rank verify kernel runs (RR verifies on resident sums only; FR_FV_OFF turns the
+    full-ranking one off)."""
+    if measure == "mrr":
+        return _verify_path_on(resident_needed=True)
+    return _verify_path_on() and not os.environ.get("FR_FV_OFF")
+
+
+@pytest.mark.parametrize("data", sorted(_AUDIT_SETS))
+@pytest.mark.parametrize("measure", ["ndcg", "map", "mrr", "ndcg@100"])
+def test_fullrank_and_rr_verify_audited_against_the_exact_kernels(data, measure, monkeypatch):
+    """FR_VERIFY_AUDIT=1: every value fullrank_verify_kernel / rr_verify_kernel (and the work-list kernels behind them)
+    publish in a line search is recomputed by the exact kernels over all (query, group) pairs, bit for bit.  On every size
+    class (1 .. 2048 documents, ties, negative gains, a query without relevant documents) and on mixed-label duplicates
+    (the DUP instantiations); the trajectory is the oracle's."""
+    X, y, qid = _AUDIT_SETS[data]()
+    monkeypatch.setenv("FR_VERIFY_AUDIT", "1")
+    g, c = fr.CDataset.from_numpy(X, y, qid), o.Dataset(X, y, qid)
+    req = _audited_request(measure)
+    shard, st = _train_stats(g, req)
+    assert st["path"] == "fused_fullrank"
+    if _fullrank_or_rr_verify_on(measure):
+        assert st["verify_pairs"] > 0 and st["audit_values"] > 0, st
+    assert st["audit_mismatches"] == 0, st
+    exp_s, exp_w, exp_e, err = c.ca_learn(measure, req.params.to_dict(), threads=2)
+    assert err == 0
+    for r in shard["restarts"]:
+        assert r["score"] == exp_s[r["restart_id"]] and r["weights"] == exp_w[r["restart_id"]].tolist(), (data, measure)
+    assert st["useful_evals"] == int(exp_e.sum())
+
+
+@pytest.mark.parametrize("measure", ["ndcg", "mrr"])
+def test_verify_audit_changes_nothing_but_its_counters(measure, monkeypatch):
+    """The audit only reads what a line search published: the restarts and every statistic but audit_* (and the wall
+    time) are the same with and without FR_VERIFY_AUDIT."""
+    X, y, qid = _mixed_label_duplicates_set()
+    req = _audited_request(measure)
+    plain, st_plain = _train_stats(fr.CDataset.from_numpy(X, y, qid), req)
+    monkeypatch.setenv("FR_VERIFY_AUDIT", "1")
+    audited, st_audit = _train_stats(fr.CDataset.from_numpy(X, y, qid), req)
+    assert audited["restarts"] == plain["restarts"]
+    skip = ("seconds", "audit_values", "audit_mismatches")
+    assert {k: v for k, v in st_audit.items() if k not in skip} == {k: v for k, v in st_plain.items() if k not in skip}
+    assert st_plain["audit_values"] == 0 and st_audit["audit_mismatches"] == 0
+    if _fullrank_or_rr_verify_on(measure):
+        assert st_audit["audit_values"] > 0
 
 
 @pytest.mark.parametrize("measure", ["ndcg@3", "ndcg@20", "ndcg@1"])
