@@ -1362,6 +1362,69 @@ const void* fr_debug_lambda_gradients(const CModel* model, const CDataset* datas
     });
 }
 
+// the histogram grower's inputs for a view: its instance list and their positions, its features ascending
+static void hist_debug_lists(fr::DatasetView& view, std::vector<uint32_t>* ids, std::vector<uint32_t>* positions, std::vector<uint32_t>* feats) {
+    *ids = fr::lambdamart_instance_list(view.host_csr());
+    *feats = view.features;
+    std::sort(feats->begin(), feats->end());
+    positions->resize(ids->size());
+    std::string err;
+    if (!view.device().rf_positions(*ids, positions->data(), &err)) fr::fail_str(err);
+}
+
+const void* fr_debug_hist_bins(const CDataset* dataset, uint32_t split_candidates, size_t n, size_t f, uint32_t* ids_out,
+                               uint32_t* feats_out, float* edges_out, uint32_t* nedges_out, uint8_t* bins_out) {
+    return status_call([&]() {
+        const CDataset& ds = require_dataset(dataset);
+        if (!ids_out || !feats_out || !edges_out || !nedges_out || !bins_out) fr::fail_str("NULL pointer: bin outputs");
+        std::lock_guard<std::mutex> lk(api_mu_of(ds));
+        fr::DatasetView& view = *ds.view;
+        std::vector<uint32_t> ids, positions, feats, nedges;
+        hist_debug_lists(view, &ids, &positions, &feats);
+        if (ids.size() != n || feats.size() != f) fr::fail_str("fr_debug_hist_bins: the view has " + std::to_string(ids.size()) + " instances and " + std::to_string(feats.size()) + " features");
+        frdev::DeviceDataset& dev = view.device();
+        std::string err;
+        std::vector<float> edges;
+        if (!dev.hist_bins(positions.data(), n, feats, split_candidates, nullptr, &err)) fr::fail_str(err);
+        if (!dev.hist_edges(&edges, &nedges, &err)) fr::fail_str(err);
+        if (!dev.hist_download_bins(bins_out, n * f, &err)) fr::fail_str(err);
+        std::copy(ids.begin(), ids.end(), ids_out);
+        std::copy(feats.begin(), feats.end(), feats_out);
+        std::copy(edges.begin(), edges.end(), edges_out);
+        std::copy(nedges.begin(), nedges.end(), nedges_out);
+    });
+}
+
+const CResult* fr_debug_hist_tree(const CDataset* dataset, uint32_t split_candidates, uint32_t max_depth, uint32_t min_leaf_support,
+                                  const double* lambda, const double* weight, size_t len) {
+    return c_call<CModel>([&]() {
+        const CDataset& ds = require_dataset(dataset);
+        if (!lambda || !weight) fr::fail_str("NULL pointer: gradient inputs");
+        if (max_depth < 1) fr::fail_str("max_depth must be at least 1");
+        std::lock_guard<std::mutex> lk(api_mu_of(ds));
+        fr::DatasetView& view = *ds.view;
+        std::vector<uint32_t> ids, positions, feats;
+        hist_debug_lists(view, &ids, &positions, &feats);
+        std::vector<double> lam(ids.size()), wt(ids.size());
+        for (size_t i = 0; i < ids.size(); i++) {
+            if (ids[i] >= len) fr::fail_str("fr_debug_hist_tree: the gradient arrays are shorter than the largest instance id");
+            lam[i] = lambda[ids[i]];
+            wt[i] = weight[ids[i]];
+        }
+        fr::HistGrower grower(view.device(), feats, split_candidates, max_depth, min_leaf_support);
+        grower.prepare(positions);
+        auto* out = new CModel();
+        try {
+            out->actual.kind = fr::Model::DecisionTree;
+            out->actual.tree = grower.grow(lam.data(), wt.data());
+        } catch (...) {
+            delete out;
+            throw;
+        }
+        return out;
+    });
+}
+
 const void* fr_evaluate_dense(const CModel* model, const CDataset* dataset, const CQRel* qrel,
                               const void* evaluator_name, double* out_values, size_t out_len,
                               const void** out_qids_json) {

@@ -25,6 +25,7 @@
 //   kernels_rf.inc          random-forest TRAINING: level-synchronous split search over a batch of trees (rocPRIM radix sort +
 //                           sequential-association importance kernels)
 //   kernels_lambda.inc      lambda_grad_kernel: LambdaMART's LambdaRank gradients, one workgroup per query
+//   kernels_hist.inc        LambdaMART's histogram grower: one-byte bins, int64 fixed-point gradients, per-node histograms
 //   device_dataset.inc      DeviceDataset: HBM layout (runs, tiles, tables) and every launcher
 #include "device.hpp"
 
@@ -38,6 +39,7 @@
 #include <unistd.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
 #include <chrono>
@@ -67,6 +69,7 @@ namespace frdev {
 #include "kernels_rr.inc"
 #include "kernels_rf.inc"
 #include "kernels_lambda.inc"
+#include "kernels_hist.inc"
 #include "device_dataset.inc"
 #include "rccl_exchange.inc"
 

@@ -305,6 +305,32 @@ class DeviceDataset {
     // ... scattered to original instance ids (ids outside this dataset or >= out_len are left untouched)
     bool lambda_download(double* lambda_by_instance, double* weight_by_instance, size_t out_len, std::string* err);
 
+    // --- LambdaMART histogram grower (kernels_hist.inc) ----------------------
+    // The host (lambdamart_hist.hpp) keeps the tree and decides; the device keeps the bin matrix, the fixed-point gradients,
+    // an index list partitioned by node, and one level's histograms [slot][feature][bin] of (count u32, sum Q i64).
+    struct HistNode { uint32_t slot, begin, end; };             // a node's histogram slot and its stretch of the index list
+    struct HistSplit { uint32_t begin, end, fslot, edge, nl; }; // bins 0..edge of feature slot fslot go left: nl of them
+    struct HistSub { uint32_t parent, small, large; };          // next level's slot `large` = this level's `parent` - next level's `small`
+    struct HistBest { double imp; long long ql, qtot; uint32_t edge, nl, valid, pad; };
+    // bins of the instance list (positions[n], rf_positions' output) for the features `feats` and k = split_candidates
+    // (2..256); kept until any of the three changes.  *built = false when the kept ones were reused.
+    bool hist_bins(const uint32_t* positions, size_t n, const std::vector<uint32_t>& feats, uint32_t k, bool* built, std::string* err);
+    // edges[slot * 256 + j], j < nedges[slot]
+    bool hist_edges(std::vector<float>* edges, std::vector<uint32_t>* nedges, std::string* err);
+    bool hist_download_bins(uint8_t* out /*[features][n]*/, size_t len, std::string* err);
+    // Q / W of the tree to grow, from the last gradient pass (lam_list == nullptr) or from host arrays in instance-list
+    // order.  *all_zero: every lambda is 0 (nothing was quantised); s_l / s_w: the exponents S of the definition
+    bool hist_quantise(const double* lam_list, const double* wt_list, int* s_l, int* s_w, bool* all_zero, std::string* err);
+    bool hist_root(std::string* err);  // index list = 0..n-1; the level holds the root's histogram in slot 0
+    // best[a * features + slot]: node a's last-maximum candidate of that feature (valid = 0: none)
+    bool hist_search(const std::vector<HistNode>& nodes, uint32_t min_leaf, std::vector<HistBest>* best, std::string* err);
+    // stable partition of the splitting nodes' stretches, then the next level (next_slots histograms; 0: none): `builds` are
+    // built from their stretches, `subs` by subtraction from the level just searched
+    bool hist_split(const std::vector<HistSplit>& splits, const std::vector<HistNode>& builds, const std::vector<HistSub>& subs,
+                    uint32_t next_slots, std::string* err);
+    bool hist_leaf_sums(const std::vector<HistNode>& leaves, std::vector<long long>* qw /*[leaf][2]*/, std::string* err);
+    void hist_end();  // frees the level histograms (the bins stay)
+
     int take_flags();  // returns and clears the accumulated kernel error bits
 
   private:

@@ -280,6 +280,33 @@ struct DeviceDataset::Impl {
         uint32_t n_lds = 0, max_len = 0;    // queries (qorder[n_lds..] are staged in the slab) / the longest one
     } lm;
     bool lm_build(std::string* err);
+    // LambdaMART histogram grower (kernels_hist.inc).  The bin matrix is kept for as long as the instance list, the features
+    // and k stay the same (across trees and across trainings); everything else is scratch of the tree being grown.
+    struct HistState {
+        uint32_t k = 0, n = 0, F = 0;
+        std::vector<uint32_t> feats, pos_host;
+        std::vector<float> edges_host;      // [F][HIST_MAX_BINS]
+        std::vector<uint32_t> nedges_host;  // [F]
+        DevBuf<uint32_t> pos, nedges;
+        DevBuf<float> edges;
+        DevBuf<uint8_t> xbin;  // [F][n]
+        DevBuf<double> lam_in, wt_in;
+        DevBuf<long long> Q, W;
+        DevBuf<unsigned long long> absmax, leaf;
+        DevBuf<uint32_t> idx, idx_o, flag, scan;
+        DevBuf<unsigned char> temp;
+        DevBuf<uint32_t> cnt, cnt_o;  // level histograms [slot][F][k]: this level's, and the next one's while it is built
+        DevBuf<unsigned long long> sum, sum_o;
+        DevBuf<HistItemDev> items, items_b, nodes;  // (items: partition and leaf sums; items_b: histogram builds)
+        DevBuf<HistSplitDev> splits;
+        DevBuf<HistSubDev> subs;
+        DevBuf<HistBestDev> best;
+        // host staging of the tables above: overwritten only after the stream was waited for
+        std::vector<HistItemDev> items_h, items_bh, nodes_h;
+        std::vector<HistSplitDev> splits_h;
+        std::vector<HistSubDev> subs_h;
+    } hist;
+    bool hist_items(const std::vector<HistItemDev>& stretches, std::vector<HistItemDev>& host, DevBuf<HistItemDev>& dev, std::string* err);
     DevBuf<uint64_t> forest;
     DevBuf<uint32_t> tree_fdesc;  // tree_ensemble_rank_kernel: per-feature descriptors, Eytzinger threshold tables
     DevBuf<float> tree_tables;
@@ -3831,4 +3858,325 @@ bool DeviceDataset::lambda_download(double* lambda_by_instance, double* weight_b
         weight_by_instance[id] = wt[p];
     }
     return true;
+}
+
+// ----------------------------------------------------------------------------------------------
+// LambdaMART histogram grower (kernels_hist.inc)
+// ----------------------------------------------------------------------------------------------
+static bool hist_fail(std::string* err, const std::string& what) {
+    if (err) *err = "LambdaMART histogram grower: " + what;
+    return false;
+}
+
+bool DeviceDataset::hist_bins(const uint32_t* positions, size_t n, const std::vector<uint32_t>& feats, uint32_t k, bool* built,
+                              std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    if (built) *built = false;
+    if (k < 2 || k > HIST_MAX_BINS) return hist_fail(err, "split_candidates must be between 2 and 256");
+    if (n == 0 || feats.empty()) return hist_fail(err, "no instances or no features");
+    if (n >= (1ull << 31)) return hist_fail(err, "more instances than the index list can hold");
+    for (uint32_t f : feats)
+        if (f >= m.d) return hist_fail(err, "feature id outside the dataset");
+    if (h.k == k && h.n == n && h.feats == feats && std::equal(h.pos_host.begin(), h.pos_host.end(), positions)) return true;
+    h.k = 0;  // (nothing valid until the end of this function)
+    const size_t F = feats.size();
+    for (size_t i = 0; i < n; i++)
+        if (positions[i] >= m.np) return hist_fail(err, "instance position outside the dataset");
+    {
+        const size_t need = F * n + 3 * n * sizeof(float) + ((size_t)64 << 20), have = device_free_bytes() + h.xbin.bytes();
+        if (have != h.xbin.bytes() && have < need)
+            return hist_fail(err, "the bin matrix needs " + std::to_string(need >> 20) + " MB of device memory, " +
+                                      std::to_string(have >> 20) + " MB are free");
+    }
+    h.pos_host.assign(positions, positions + n);
+    if (!h.pos.ensure(n, err) || !h.xbin.ensure(F * n, err) || !h.edges.ensure(F * HIST_MAX_BINS, err) || !h.nedges.ensure(F, err)) return false;
+    DevBuf<float> col, sorted, firsts;
+    DevBuf<uint32_t> count;
+    DevBuf<int> nan_flag;
+    if (!col.ensure(n, err) || !sorted.ensure(n, err) || !firsts.ensure(F * (HIST_MAX_BINS + 1), err) || !count.ensure(F, err) || !nan_flag.ensure(1, err))
+        return false;
+    FR_HIP(hipMemcpyAsync(h.pos.p, h.pos_host.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, m.stream));
+    FR_HIP(hipMemsetAsync(count.p, 0, F * sizeof(uint32_t), m.stream));
+    FR_HIP(hipMemsetAsync(nan_flag.p, 0, sizeof(int), m.stream));
+    FR_HIP(hipMemsetAsync(h.edges.p, 0, F * HIST_MAX_BINS * sizeof(float), m.stream));
+    size_t temp_bytes = 0;
+    FR_HIP(rocprim::radix_sort_keys(nullptr, temp_bytes, col.p, sorted.p, n, 0u, 32u, m.stream));
+    if (!h.temp.ensure(std::max<size_t>(temp_bytes, 16), err)) return false;
+    const uint32_t n32 = (uint32_t)n;
+    {
+        ProfScope ps("hist_binning", m.stream);
+        for (size_t s = 0; s < F; s++) {
+            hist_column_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(m.xb.p, (uint32_t)m.dq, h.pos.p, n32, feats[s], col.p, nan_flag.p);
+            size_t tb = h.temp.bytes();
+            FR_HIP(rocprim::radix_sort_keys((void*)h.temp.p, tb, col.p, sorted.p, n, 0u, 32u, m.stream));
+            hist_distinct_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(sorted.p, n32, count.p + s, firsts.p + s * (HIST_MAX_BINS + 1));
+            hist_edges_kernel<<<1, 256, 0, m.stream>>>(sorted.p, n32, k, count.p + s, firsts.p + s * (HIST_MAX_BINS + 1),
+                                                       h.edges.p + s * HIST_MAX_BINS, h.nedges.p + s);
+            hist_bin_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(col.p, n32, h.edges.p + s * HIST_MAX_BINS, h.nedges.p + s, h.xbin.p + s * n);
+        }
+    }
+    FR_HIP(hipGetLastError());
+    h.edges_host.assign(F * HIST_MAX_BINS, 0.0f);
+    h.nedges_host.assign(F, 0);
+    int bad = 0;
+    FR_HIP(hipMemcpyAsync(h.edges_host.data(), h.edges.p, F * HIST_MAX_BINS * sizeof(float), hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipMemcpyAsync(h.nedges_host.data(), h.nedges.p, F * sizeof(uint32_t), hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipMemcpyAsync(&bad, nan_flag.p, sizeof(int), hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipStreamSynchronize(m.stream));
+    if (bad) return hist_fail(err, "a feature value is NaN; NaN has no bin (use the exact grower, or clean the data)");
+    for (size_t s = 0; s < F; s++)
+        if (h.nedges_host[s] >= k) return hist_fail(err, "internal error: more edges than bins");
+    h.feats = feats;
+    h.n = n32, h.F = (uint32_t)F, h.k = k;
+    if (built) *built = true;
+    return true;
+}
+
+bool DeviceDataset::hist_edges(std::vector<float>* edges, std::vector<uint32_t>* nedges, std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (m.hist.k == 0) return hist_fail(err, "no bins built");
+    *edges = m.hist.edges_host;
+    *nedges = m.hist.nedges_host;
+    return true;
+}
+
+bool DeviceDataset::hist_download_bins(uint8_t* out, size_t len, std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    if (h.k == 0) return hist_fail(err, "no bins built");
+    if (len != (size_t)h.F * h.n) return hist_fail(err, "bin matrix output has the wrong length");
+    FR_HIP(hipMemcpyAsync(out, h.xbin.p, len, hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipStreamSynchronize(m.stream));
+    return true;
+}
+
+bool DeviceDataset::hist_quantise(const double* lam_list, const double* wt_list, int* s_l, int* s_w, bool* all_zero, std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    if (h.k == 0) return hist_fail(err, "no bins built");
+    const uint32_t n = h.n;
+    const double *lam = nullptr, *wt = nullptr;
+    const uint32_t* pos = nullptr;
+    if (lam_list != nullptr) {
+        if (!h.lam_in.ensure(n, err) || !h.wt_in.ensure(n, err)) return false;
+        FR_HIP(hipMemcpyAsync(h.lam_in.p, lam_list, n * sizeof(double), hipMemcpyHostToDevice, m.stream));
+        FR_HIP(hipMemcpyAsync(h.wt_in.p, wt_list, n * sizeof(double), hipMemcpyHostToDevice, m.stream));
+        lam = h.lam_in.p, wt = h.wt_in.p;
+    } else {
+        if (!m.lm.built) return hist_fail(err, "no gradients computed");
+        lam = m.lm.lam.p, wt = m.lm.wt.p, pos = h.pos.p;
+    }
+    if (!h.absmax.ensure(2, err) || !h.Q.ensure(n, err) || !h.W.ensure(n, err)) return false;
+    FR_HIP(hipMemsetAsync(h.absmax.p, 0, 2 * sizeof(unsigned long long), m.stream));
+    {
+        ProfScope ps("hist_absmax_kernel", m.stream);
+        hist_absmax_kernel<<<std::min<unsigned>(grid1d(n, 256).x, 1024u), 256, 0, m.stream>>>(lam, wt, pos, n, h.absmax.p);
+    }
+    unsigned long long bits[2] = {0, 0};
+    FR_HIP(hipMemcpyAsync(bits, h.absmax.p, sizeof(bits), hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipStreamSynchronize(m.stream));
+    double mx[2];
+    std::memcpy(mx, bits, sizeof(mx));
+    if (!std::isfinite(mx[0]) || !std::isfinite(mx[1])) return hist_fail(err, "a gradient is not finite");
+    *all_zero = mx[0] == 0.0;
+    *s_l = *s_w = 0;
+    if (*all_zero) return true;
+    uint32_t c = 0;  // ceil(log2(n + 1)) = the bit length of n
+    for (uint32_t x = n; x != 0; x >>= 1) c++;
+    int e = 0;
+    (void)std::frexp(mx[0], &e);
+    *s_l = 61 - e - (int)c;
+    if (mx[1] != 0.0) {
+        (void)std::frexp(mx[1], &e);
+        *s_w = 61 - e - (int)c;
+    }
+    ProfScope ps("hist_quant_kernel", m.stream);
+    hist_quant_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(lam, wt, pos, n, *s_l, *s_w, mx[1] == 0.0 ? 1 : 0, h.Q.p, h.W.p);
+    FR_HIP(hipGetLastError());
+    return true;
+}
+
+// the stretches cut into pieces of at most HIST_CHUNK entries (slot carried along): one workgroup each
+bool DeviceDataset::Impl::hist_items(const std::vector<HistItemDev>& stretches, std::vector<HistItemDev>& host, DevBuf<HistItemDev>& dev,
+                                     std::string* err) {
+    host.clear();
+    for (const HistItemDev& s : stretches)
+        for (uint32_t b = s.begin; b < s.end; b += HIST_CHUNK) host.push_back({s.slot, b, std::min(s.end, b + HIST_CHUNK)});
+    if (host.empty()) return true;
+    if (!dev.ensure(host.size(), err)) return false;
+    FR_HIP(hipMemcpyAsync(dev.p, host.data(), host.size() * sizeof(HistItemDev), hipMemcpyHostToDevice, stream));
+    return true;
+}
+
+static bool hist_level_alloc(DevBuf<uint32_t>& cnt, DevBuf<unsigned long long>& sum, size_t cells, std::string* err) {
+    std::string e2;
+    if (!cnt.ensure(cells, &e2) || !sum.ensure(cells, &e2)) {
+        (void)hipGetLastError();
+        return hist_fail(err, "no device memory for a level's histograms (" + std::to_string((cells * 12) >> 20) +
+                                  " MB: open nodes x features x bins x 12 bytes); lower max_depth or split_candidates");
+    }
+    return true;
+}
+
+bool DeviceDataset::hist_root(std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    if (h.k == 0) return hist_fail(err, "no bins built");
+    const uint32_t n = h.n;
+    const size_t fk = (size_t)h.F * h.k;
+    if (!h.idx.ensure(n, err) || !h.idx_o.ensure(n, err) || !h.flag.ensure(n, err) || !h.scan.ensure(n, err)) return false;
+    if (!hist_level_alloc(h.cnt, h.sum, fk, err)) return false;
+    FR_HIP(hipMemsetAsync(h.flag.p, 0, n * sizeof(uint32_t), m.stream));
+    FR_HIP(hipMemsetAsync(h.cnt.p, 0, fk * sizeof(uint32_t), m.stream));
+    FR_HIP(hipMemsetAsync(h.sum.p, 0, fk * sizeof(unsigned long long), m.stream));
+    hist_iota_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(h.idx.p, n);
+    if (!m.hist_items({{0u, 0u, n}}, h.items_bh, h.items_b, err)) return false;
+    ProfScope ps("hist_build_kernel", m.stream);
+    hist_build_kernel<<<dim3((unsigned)h.items_bh.size(), (h.F + HIST_FB - 1) / HIST_FB), 256, (size_t)HIST_FB * h.k * 12, m.stream>>>(
+        h.items_b.p, h.xbin.p, n, h.idx.p, h.Q.p, h.F, h.k, h.cnt.p, h.sum.p);
+    FR_HIP(hipGetLastError());
+    return true;
+}
+
+bool DeviceDataset::hist_search(const std::vector<HistNode>& nodes, uint32_t min_leaf, std::vector<HistBest>* best, std::string* err) {
+    static_assert(sizeof(HistBest) == sizeof(HistBestDev) && sizeof(HistNode) == sizeof(HistItemDev), "host and device records differ");
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    const size_t A = nodes.size();
+    best->assign(A * h.F, HistBest{});
+    if (A == 0) return true;
+    const size_t fk = (size_t)h.F * h.k;
+    h.nodes_h.resize(A);
+    for (size_t a = 0; a < A; a++) {
+        if ((size_t)(nodes[a].slot + 1) * fk > h.cnt.cap || nodes[a].end > h.n || nodes[a].begin > nodes[a].end)
+            return hist_fail(err, "internal error: a node outside the level's histograms");
+        h.nodes_h[a] = {nodes[a].slot, nodes[a].begin, nodes[a].end};
+    }
+    if (!h.nodes.ensure(A, err) || !h.best.ensure(A * h.F, err)) return false;
+    FR_HIP(hipMemcpyAsync(h.nodes.p, h.nodes_h.data(), A * sizeof(HistItemDev), hipMemcpyHostToDevice, m.stream));
+    {
+        ProfScope ps("hist_scan_kernel", m.stream);
+        hist_scan_kernel<<<(unsigned)(A * h.F), 64, 0, m.stream>>>(h.nodes.p, h.F, h.k, h.nedges.p, h.cnt.p, h.sum.p, min_leaf, h.best.p);
+    }
+    FR_HIP(hipGetLastError());
+    FR_HIP(hipMemcpyAsync(best->data(), h.best.p, A * h.F * sizeof(HistBestDev), hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipStreamSynchronize(m.stream));
+    return true;
+}
+
+bool DeviceDataset::hist_split(const std::vector<HistSplit>& splits, const std::vector<HistNode>& builds, const std::vector<HistSub>& subs,
+                               uint32_t next_slots, std::string* err) {
+    static_assert(sizeof(HistSplit) == sizeof(HistSplitDev) && sizeof(HistSub) == sizeof(HistSubDev), "host and device records differ");
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    const uint32_t n = h.n;
+    const size_t fk = (size_t)h.F * h.k;
+    if (!splits.empty()) {
+        std::vector<HistItemDev> stretches(splits.size());
+        h.splits_h.resize(splits.size());
+        for (size_t i = 0; i < splits.size(); i++) {
+            const HistSplit& s = splits[i];
+            if (s.begin >= s.end || s.end > n || s.nl > s.end - s.begin || s.fslot >= h.F || s.edge >= h.k)
+                return hist_fail(err, "internal error: a split outside the index list");
+            h.splits_h[i] = {s.begin, s.end, s.fslot, s.edge, s.nl};
+            stretches[i] = {(uint32_t)i, s.begin, s.end};
+        }
+        if (!h.splits.ensure(splits.size(), err) || !m.hist_items(stretches, h.items_h, h.items, err)) return false;
+        FR_HIP(hipMemcpyAsync(h.splits.p, h.splits_h.data(), splits.size() * sizeof(HistSplitDev), hipMemcpyHostToDevice, m.stream));
+        const unsigned g = (unsigned)h.items_h.size();
+        ProfScope ps("hist_partition", m.stream);
+        hist_flag_kernel<<<g, 256, 0, m.stream>>>(h.items.p, h.splits.p, h.xbin.p, n, h.idx.p, h.flag.p);
+        size_t tb = 0;
+        FR_HIP(rocprim::exclusive_scan(nullptr, tb, h.flag.p, h.scan.p, 0u, (size_t)n, rocprim::plus<uint32_t>(), m.stream));
+        if (tb > h.temp.bytes()) {
+            FR_HIP(hipStreamSynchronize(m.stream));  // (the sort's scratch is not in use: binning has been waited for)
+            if (!h.temp.ensure(tb, err)) return false;
+        }
+        FR_HIP(rocprim::exclusive_scan((void*)h.temp.p, tb, h.flag.p, h.scan.p, 0u, (size_t)n, rocprim::plus<uint32_t>(), m.stream));
+        hist_scatter_kernel<<<g, 256, 0, m.stream>>>(h.items.p, h.splits.p, h.flag.p, h.scan.p, h.idx.p, h.idx_o.p);
+        hist_copy_kernel<<<g, 256, 0, m.stream>>>(h.items.p, h.idx_o.p, h.idx.p);
+        FR_HIP(hipGetLastError());
+    }
+    if (next_slots == 0) return true;
+    // the next level's histograms: the smaller child of every pair from its stretch, the larger by subtraction
+    if (!hist_level_alloc(h.cnt_o, h.sum_o, (size_t)next_slots * fk, err)) return false;
+    FR_HIP(hipMemsetAsync(h.cnt_o.p, 0, (size_t)next_slots * fk * sizeof(uint32_t), m.stream));
+    FR_HIP(hipMemsetAsync(h.sum_o.p, 0, (size_t)next_slots * fk * sizeof(unsigned long long), m.stream));
+    std::vector<HistItemDev> stretches(builds.size());
+    for (size_t i = 0; i < builds.size(); i++) {
+        if (builds[i].slot >= next_slots || builds[i].end > n || builds[i].begin > builds[i].end)
+            return hist_fail(err, "internal error: a child outside the next level");
+        stretches[i] = {builds[i].slot, builds[i].begin, builds[i].end};
+    }
+    if (!m.hist_items(stretches, h.items_bh, h.items_b, err)) return false;
+    if (!h.items_bh.empty()) {
+        ProfScope ps("hist_build_kernel", m.stream);
+        hist_build_kernel<<<dim3((unsigned)h.items_bh.size(), (h.F + HIST_FB - 1) / HIST_FB), 256, (size_t)HIST_FB * h.k * 12, m.stream>>>(
+            h.items_b.p, h.xbin.p, n, h.idx.p, h.Q.p, h.F, h.k, h.cnt_o.p, h.sum_o.p);
+    }
+    if (!subs.empty()) {
+        h.subs_h.resize(subs.size());
+        for (size_t i = 0; i < subs.size(); i++) {
+            if ((size_t)(subs[i].parent + 1) * fk > h.cnt.cap || subs[i].small >= next_slots || subs[i].large >= next_slots)
+                return hist_fail(err, "internal error: a subtraction outside the histograms");
+            h.subs_h[i] = {subs[i].parent, subs[i].small, subs[i].large};
+        }
+        if (!h.subs.ensure(subs.size(), err)) return false;
+        FR_HIP(hipMemcpyAsync(h.subs.p, h.subs_h.data(), subs.size() * sizeof(HistSubDev), hipMemcpyHostToDevice, m.stream));
+        ProfScope ps("hist_sub_kernel", m.stream);
+        hist_sub_kernel<<<dim3((unsigned)subs.size(), (unsigned)((fk + 255) / 256)), 256, 0, m.stream>>>(h.subs.p, (uint32_t)fk, h.cnt.p, h.sum.p,
+                                                                                                       h.cnt_o.p, h.sum_o.p);
+    }
+    FR_HIP(hipGetLastError());
+    std::swap(h.cnt.p, h.cnt_o.p), std::swap(h.cnt.cap, h.cnt_o.cap);
+    std::swap(h.sum.p, h.sum_o.p), std::swap(h.sum.cap, h.sum_o.cap);
+    return true;
+}
+
+bool DeviceDataset::hist_leaf_sums(const std::vector<HistNode>& leaves, std::vector<long long>* qw, std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    const size_t L = leaves.size();
+    qw->assign(L * 2, 0);
+    if (L == 0) return true;
+    std::vector<HistItemDev> stretches(L);
+    for (size_t i = 0; i < L; i++) {
+        if (leaves[i].end > h.n || leaves[i].begin > leaves[i].end) return hist_fail(err, "internal error: a leaf outside the index list");
+        stretches[i] = {(uint32_t)i, leaves[i].begin, leaves[i].end};
+    }
+    FR_HIP(hipStreamSynchronize(m.stream));  // (hist.items is about to be rewritten)
+    if (!h.leaf.ensure(L * 2, err) || !m.hist_items(stretches, h.items_h, h.items, err)) return false;
+    FR_HIP(hipMemsetAsync(h.leaf.p, 0, L * 2 * sizeof(unsigned long long), m.stream));
+    if (!h.items_h.empty()) {
+        ProfScope ps("hist_leafsum_kernel", m.stream);
+        hist_leafsum_kernel<<<(unsigned)h.items_h.size(), 256, 0, m.stream>>>(h.items.p, h.idx.p, h.Q.p, h.W.p, h.leaf.p);
+    }
+    FR_HIP(hipGetLastError());
+    FR_HIP(hipMemcpyAsync(qw->data(), h.leaf.p, L * 2 * sizeof(long long), hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipStreamSynchronize(m.stream));
+    return true;
+}
+
+void DeviceDataset::hist_end() {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    auto& h = m.hist;
+    (void)hipStreamSynchronize(m.stream);
+    h.cnt.release(), h.cnt_o.release(), h.sum.release(), h.sum_o.release(), h.best.release(), h.lam_in.release(), h.wt_in.release();
 }

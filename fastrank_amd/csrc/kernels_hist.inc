@@ -1,0 +1,338 @@
+// Part of device.hip (single translation unit; see that file's header).  LambdaMART's histogram grower (DESIGN.md section 11,
+// "Histogram grower"): features binned once into one byte each, gradients as int64 fixed point, per-node histograms of
+// (count, sum Q) per (feature, bin).  Integer sums do not depend on their order, so the histograms may be built with
+// atomics -- in LDS inside a workgroup, then one 64-bit add per touched bin to global memory -- and a sibling's histogram is
+// exactly parent minus child.
+//
+//   hist_column_kernel    a feature's f32 column over the instance list (-0.0 read as 0.0; NaN raises a flag)
+//   (rocPRIM)             radix sort of that column
+//   hist_distinct_kernel  number of distinct values, and the first HIST_MAX_BINS + 1 of them (in no particular order)
+//   hist_edges_kernel     the feature's at most k - 1 edges: every distinct value but the largest when there are at most k,
+//                         else sorted[(j n + k - 1) / k - 1], j = 1..k-1, duplicates and the maximum dropped
+//   hist_bin_kernel       bin(x) = number of edges strictly below x, so bins 0..j hold exactly x <= edge_j
+//   hist_absmax_kernel    max |lambda|, max |w| over the instance list (bit patterns of non-negative doubles order like them)
+//   hist_quant_kernel     Q = (int64) rint(ldexp(lambda, S)), W likewise
+//   hist_build_kernel     one workgroup per (stretch of a node's index list, block of HIST_FB features)
+//   hist_sub_kernel       sibling = parent - child
+//   hist_scan_kernel      one wave per (node, feature): prefix sums over the bins, every edge a candidate, the last maximum wins
+//   hist_flag_kernel / (rocPRIM exclusive scan) / hist_scatter_kernel / hist_copy_kernel
+//                         stable partition of every splitting node's stretch of the index list
+//   hist_leafsum_kernel   sum Q, sum W of every leaf's stretch
+
+constexpr uint32_t HIST_MAX_BINS = 256;  // bins are one byte
+constexpr uint32_t HIST_FB = 8;          // features per workgroup of hist_build_kernel: 8 x 256 bins x 12 B = 24 KiB of LDS, six workgroups per CU
+constexpr uint32_t HIST_CHUNK = 8192;    // index-list entries per workgroup
+
+struct HistItemDev {
+    uint32_t slot, begin, end;
+};
+struct HistSplitDev {
+    uint32_t begin, end, fslot, edge, nl;
+};
+struct HistSubDev {
+    uint32_t parent, small, large;
+};
+struct HistBestDev {
+    double imp;
+    long long ql, qtot;
+    uint32_t edge, nl, valid, pad;
+};
+
+__global__ __launch_bounds__(256) void hist_column_kernel(const float* __restrict__ xb, uint32_t dq, const uint32_t* __restrict__ pos,
+                                                          uint32_t n, uint32_t f, float* __restrict__ out, int* __restrict__ nan_flag) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float v = xb[xb_index(pos[i], f, dq)] + 0.0f;
+    if (v != v) atomicOr(nan_flag, 1);
+    out[i] = v;
+}
+
+__global__ __launch_bounds__(256) void hist_distinct_kernel(const float* __restrict__ sorted, uint32_t n, uint32_t* __restrict__ count,
+                                                            float* __restrict__ firsts /*[HIST_MAX_BINS + 1]*/) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (i == 0 || sorted[i] != sorted[i - 1]) {
+        const uint32_t s = atomicAdd(count, 1u);
+        if (s <= HIST_MAX_BINS) firsts[s] = sorted[i];
+    }
+}
+
+__global__ __launch_bounds__(256) void hist_edges_kernel(const float* __restrict__ sorted, uint32_t n, uint32_t k,
+                                                         const uint32_t* __restrict__ count, const float* __restrict__ firsts,
+                                                         float* __restrict__ edges /*[HIST_MAX_BINS]*/, uint32_t* __restrict__ nedges) {
+    __shared__ float vals[HIST_MAX_BINS + 1];
+    __shared__ uint32_t keep[HIST_MAX_BINS + 1];
+    const uint32_t t = threadIdx.x;
+    const uint32_t nd = *count;
+    if (nd <= k) {  // few distinct values: each its own bin (rank by counting: firsts[] arrives in no order)
+        for (uint32_t u = t; u < nd; u += blockDim.x) vals[u] = firsts[u];
+        __syncthreads();
+        for (uint32_t u = t; u < nd; u += blockDim.x) {
+            uint32_t r = 0;
+            for (uint32_t w = 0; w < nd; w++) r += vals[w] < vals[u] ? 1u : 0u;
+            if (r + 1 < nd) edges[r] = vals[u];
+        }
+        if (t == 0) *nedges = nd ? nd - 1 : 0;
+        return;
+    }
+    const float vmax = sorted[n - 1];
+    for (uint32_t j = t; j <= HIST_MAX_BINS; j += blockDim.x) {
+        keep[j] = 0;
+        if (j >= 1 && j < k) {
+            const float v = sorted[((uint64_t)j * n + k - 1) / k - 1];
+            vals[j] = v;
+            const bool dup = j > 1 && v == sorted[((uint64_t)(j - 1) * n + k - 1) / k - 1];
+            keep[j] = (!dup && v != vmax) ? 1u : 0u;
+        }
+    }
+    __syncthreads();
+    for (uint32_t j = t; j < k; j += blockDim.x) {
+        if (j < 1 || !keep[j]) continue;
+        uint32_t r = 0;
+        for (uint32_t w = 1; w < j; w++) r += keep[w];
+        edges[r] = vals[j];
+    }
+    if (t == 0) {
+        uint32_t r = 0;
+        for (uint32_t w = 1; w < k; w++) r += keep[w];
+        *nedges = r;
+    }
+}
+
+__global__ __launch_bounds__(256) void hist_bin_kernel(const float* __restrict__ col, uint32_t n, const float* __restrict__ edges,
+                                                       const uint32_t* __restrict__ nedges, uint8_t* __restrict__ out) {
+    __shared__ float e[HIST_MAX_BINS];
+    const uint32_t ne = min(*nedges, HIST_MAX_BINS - 1);
+    for (uint32_t u = threadIdx.x; u < ne; u += blockDim.x) e[u] = edges[u];
+    __syncthreads();
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float x = col[i];
+    uint32_t lo = 0, hi = ne;  // first edge that is not below x
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (e[mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    out[i] = (uint8_t)lo;
+}
+
+// pos == nullptr: lam / wt are already in instance-list order
+__global__ __launch_bounds__(256) void hist_absmax_kernel(const double* __restrict__ lam, const double* __restrict__ wt,
+                                                          const uint32_t* __restrict__ pos, uint32_t n,
+                                                          unsigned long long* __restrict__ out /*[2]*/) {
+    unsigned long long ml = 0, mw = 0;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const uint32_t p = pos ? pos[i] : i;
+        ml = max(ml, (unsigned long long)__double_as_longlong(fabs(lam[p])));
+        mw = max(mw, (unsigned long long)__double_as_longlong(fabs(wt[p])));
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        ml = max(ml, (unsigned long long)__shfl_xor((long long)ml, o));
+        mw = max(mw, (unsigned long long)__shfl_xor((long long)mw, o));
+    }
+    if ((threadIdx.x & 63u) == 0) {
+        atomicMax(&out[0], ml);
+        atomicMax(&out[1], mw);
+    }
+}
+
+__global__ __launch_bounds__(256) void hist_quant_kernel(const double* __restrict__ lam, const double* __restrict__ wt,
+                                                         const uint32_t* __restrict__ pos, uint32_t n, int s_l, int s_w, int w_zero,
+                                                         long long* __restrict__ Q, long long* __restrict__ W) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t p = pos ? pos[i] : i;
+    Q[i] = (long long)rint(ldexp(lam[p], s_l));
+    W[i] = w_zero ? 0ll : (long long)rint(ldexp(wt[p], s_w));
+}
+
+__global__ __launch_bounds__(256) void hist_iota_kernel(uint32_t* __restrict__ idx, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) idx[i] = i;
+}
+
+// grid (items, feature blocks).  cnt / sum: [slot][F][k]
+__global__ __launch_bounds__(256) void hist_build_kernel(const HistItemDev* __restrict__ items, const uint8_t* __restrict__ xbin,
+                                                         uint32_t n, const uint32_t* __restrict__ idx, const long long* __restrict__ Q,
+                                                         uint32_t F, uint32_t k, uint32_t* __restrict__ cnt,
+                                                         unsigned long long* __restrict__ sum) {
+    extern __shared__ unsigned long long hist_lds[];
+    const HistItemDev it = items[blockIdx.x];
+    const uint32_t f0 = blockIdx.y * HIST_FB, nf = min(HIST_FB, F - f0);
+    unsigned long long* lq = hist_lds;
+    uint32_t* lc = (uint32_t*)(hist_lds + (size_t)HIST_FB * k);
+    for (uint32_t t = threadIdx.x; t < HIST_FB * k; t += blockDim.x) {
+        lq[t] = 0ull;
+        lc[t] = 0u;
+    }
+    __syncthreads();
+    const uint8_t* xb0 = xbin + (size_t)f0 * n;
+    for (uint32_t i = it.begin + threadIdx.x; i < it.end; i += blockDim.x) {
+        const uint32_t r = idx[i];
+        const unsigned long long q = (unsigned long long)Q[r];
+        if (nf == HIST_FB) {
+            uint32_t b[HIST_FB];
+#pragma unroll
+            for (uint32_t u = 0; u < HIST_FB; u++) b[u] = xb0[(size_t)u * n + r];
+#pragma unroll
+            for (uint32_t u = 0; u < HIST_FB; u++) {
+                atomicAdd(&lq[u * k + b[u]], q);
+                atomicAdd(&lc[u * k + b[u]], 1u);
+            }
+        } else {
+            for (uint32_t u = 0; u < nf; u++) {
+                const uint32_t b = xb0[(size_t)u * n + r];
+                atomicAdd(&lq[u * k + b], q);
+                atomicAdd(&lc[u * k + b], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    const size_t base = ((size_t)it.slot * F + f0) * k;
+    for (uint32_t t = threadIdx.x; t < nf * k; t += blockDim.x) {
+        const uint32_t c = lc[t];
+        if (c == 0) continue;
+        atomicAdd(&cnt[base + t], c);
+        atomicAdd(&sum[base + t], lq[t]);
+    }
+}
+
+// grid (pairs, ceil(F k / 256)): the larger child's histogram = the parent's (previous level) - the smaller child's
+__global__ __launch_bounds__(256) void hist_sub_kernel(const HistSubDev* __restrict__ pairs, uint32_t fk, const uint32_t* __restrict__ pcnt,
+                                                       const unsigned long long* __restrict__ psum, uint32_t* __restrict__ cnt,
+                                                       unsigned long long* __restrict__ sum) {
+    const HistSubDev pr = pairs[blockIdx.x];
+    const uint32_t t = blockIdx.y * blockDim.x + threadIdx.x;
+    if (t >= fk) return;
+    const size_t p = (size_t)pr.parent * fk + t, s = (size_t)pr.small * fk + t, l = (size_t)pr.large * fk + t;
+    cnt[l] = pcnt[p] - cnt[s];
+    sum[l] = psum[p] - sum[s];
+}
+
+// one wave per (node, feature); nodes[a] = {slot, begin, end} of the a-th open node; best[a * F + f]
+__global__ __launch_bounds__(64) void hist_scan_kernel(const HistItemDev* __restrict__ nodes, uint32_t F, uint32_t k,
+                                                       const uint32_t* __restrict__ nedges, const uint32_t* __restrict__ cnt,
+                                                       const unsigned long long* __restrict__ sum, uint32_t min_leaf,
+                                                       HistBestDev* __restrict__ best) {
+    const uint32_t a = blockIdx.x / F, f = blockIdx.x % F, lane = threadIdx.x;
+    const HistItemDev nd = nodes[a];
+    const uint32_t n = nd.end - nd.begin;
+    const uint32_t ne = min(nedges[f], k - 1);
+    const size_t base = ((size_t)nd.slot * F + f) * k;
+    const uint32_t B = (k + 63) / 64;  // bins per lane (<= 4)
+    uint32_t c[4];
+    long long s[4];
+    uint32_t tc = 0;
+    long long ts = 0;
+    for (uint32_t u = 0; u < 4; u++) {
+        const uint32_t b = lane * B + u;
+        const bool in = u < B && b < k;
+        c[u] = in ? cnt[base + b] : 0u;
+        s[u] = in ? (long long)sum[base + b] : 0ll;
+        tc += c[u];
+        ts += s[u];
+    }
+    uint32_t ic = tc;
+    long long is = ts;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t oc = __shfl_up(ic, o);
+        const long long os = __shfl_up(is, o);
+        if ((int)lane >= o) {
+            ic += oc;
+            is += os;
+        }
+    }
+    const long long qtot = __shfl(is, 63);
+    uint32_t rc = ic - tc;  // counts / sums of the bins before this lane's
+    long long rs = is - ts;
+    double bimp = 0.0;
+    uint32_t bj = 0, bnl = 0, have = 0;
+    long long bql = 0;
+    for (uint32_t u = 0; u < B; u++) {
+        const uint32_t j = lane * B + u;
+        rc += c[u];
+        rs += s[u];
+        if (j >= ne) break;
+        const uint32_t nl = rc, nr = n - rc;
+        if (nl == 0 || nr == 0 || nl < min_leaf || nr < min_leaf) continue;
+        const double sl = (double)rs, sr = (double)(qtot - rs);
+        const double imp = (sl * sl) / (double)nl + (sr * sr) / (double)nr;
+        if (!have || imp >= bimp) {
+            have = 1;
+            bimp = imp;
+            bj = j;
+            bnl = nl;
+            bql = rs;
+        }
+    }
+    // the last maximum over the lanes: larger importance, then the later edge
+    double wimp = bimp;
+    uint32_t wj = bj, whave = have;
+    for (int o = 32; o > 0; o >>= 1) {
+        const double oimp = __shfl_xor(wimp, o);
+        const uint32_t oj = __shfl_xor(wj, o), ohave = __shfl_xor(whave, o);
+        if (ohave && (!whave || oimp > wimp || (oimp == wimp && oj > wj))) {
+            whave = 1;
+            wimp = oimp;
+            wj = oj;
+        }
+    }
+    HistBestDev* out = best + (size_t)a * F + f;
+    if (!whave) {
+        if (lane == 0) *out = HistBestDev{0.0, 0ll, qtot, 0u, 0u, 0u, 0u};
+    } else if (have && bj == wj) {
+        *out = HistBestDev{bimp, bql, qtot, bj, bnl, 1u, 0u};
+    }
+}
+
+// grid: chunks of the splitting nodes' stretches.  items[i].slot = index into splits
+__global__ __launch_bounds__(256) void hist_flag_kernel(const HistItemDev* __restrict__ items, const HistSplitDev* __restrict__ splits,
+                                                        const uint8_t* __restrict__ xbin, uint32_t n, const uint32_t* __restrict__ idx,
+                                                        uint32_t* __restrict__ flag) {
+    const HistItemDev it = items[blockIdx.x];
+    const HistSplitDev sp = splits[it.slot];
+    const uint8_t* col = xbin + (size_t)sp.fslot * n;
+    for (uint32_t i = it.begin + threadIdx.x; i < it.end; i += blockDim.x) flag[i] = col[idx[i]] <= sp.edge ? 1u : 0u;
+}
+
+// scan = exclusive prefix sums of flag over the whole list; inside a node only differences are used
+__global__ __launch_bounds__(256) void hist_scatter_kernel(const HistItemDev* __restrict__ items, const HistSplitDev* __restrict__ splits,
+                                                           const uint32_t* __restrict__ flag, const uint32_t* __restrict__ scan,
+                                                           const uint32_t* __restrict__ idx, uint32_t* __restrict__ out) {
+    const HistItemDev it = items[blockIdx.x];
+    const HistSplitDev sp = splits[it.slot];
+    const uint32_t s0 = scan[sp.begin];
+    for (uint32_t i = it.begin + threadIdx.x; i < it.end; i += blockDim.x) {
+        const uint32_t lb = scan[i] - s0;  // left-goers before i in the node
+        const uint32_t d = flag[i] ? sp.begin + lb : sp.begin + sp.nl + (i - sp.begin - lb);
+        if (d < sp.end) out[d] = idx[i];
+    }
+}
+
+__global__ __launch_bounds__(256) void hist_copy_kernel(const HistItemDev* __restrict__ items, const uint32_t* __restrict__ src,
+                                                        uint32_t* __restrict__ dst) {
+    const HistItemDev it = items[blockIdx.x];
+    for (uint32_t i = it.begin + threadIdx.x; i < it.end; i += blockDim.x) dst[i] = src[i];
+}
+
+// items[i].slot = leaf number; out[leaf * 2] += sum Q, out[leaf * 2 + 1] += sum W
+__global__ __launch_bounds__(256) void hist_leafsum_kernel(const HistItemDev* __restrict__ items, const uint32_t* __restrict__ idx,
+                                                           const long long* __restrict__ Q, const long long* __restrict__ W,
+                                                           unsigned long long* __restrict__ out) {
+    const HistItemDev it = items[blockIdx.x];
+    long long q = 0, w = 0;
+    for (uint32_t i = it.begin + threadIdx.x; i < it.end; i += blockDim.x) {
+        const uint32_t r = idx[i];
+        q += Q[r];
+        w += W[r];
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        q += __shfl_xor(q, o);
+        w += __shfl_xor(w, o);
+    }
+    if ((threadIdx.x & 63u) == 0) {
+        atomicAdd(&out[(size_t)it.slot * 2], (unsigned long long)q);
+        atomicAdd(&out[(size_t)it.slot * 2 + 1], (unsigned long long)w);
+    }
+}

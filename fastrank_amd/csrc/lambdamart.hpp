@@ -7,6 +7,8 @@
 //   leaves    Newton step sum_L lambda / sum_L w over the instances the tree's SCORING rule (x <= split -> lhs) sends to
 //             the leaf, both sums sequential f64 in the instance list's order; 0.0 for an empty leaf or sum_L w == 0.
 //             The routing is the tree-scoring kernel run on a copy of the tree whose leaves hold their own index.
+// grower = "histogram" (lambdamart_hist.hpp, kernels_hist.inc) replaces grow and leaves: features binned once into one byte,
+// gradients as int64 fixed point, per-node histograms; leaf values from the leaves' own integer sums.
 //   update    s_p = s_p + learning_rate * tree(x_p) (unfused: ensemble_accumulate), the WeightedEnsemble recurrence, so
 //             the running scores are what predicting with the model so far gives, bit for bit.
 // The instance list is the RF trainer's: queries in the view's order, instance ids ascending inside a query.
@@ -15,6 +17,7 @@
 #include <cmath>
 
 #include "host.hpp"
+#include "lambdamart_hist.hpp"
 #include "rf_train.hpp"
 
 namespace fr {
@@ -27,6 +30,7 @@ struct LambdaMARTParams {
     uint32_t split_candidates = 64;
     double sigma = 1.0;
     bool quiet = false;
+    bool histogram = false;  // wire key "grower": "exact" (the default, not written) or "histogram"
 
     [[noreturn]] static void invalid(const std::string& what) {
         fail_raw("Error(\"invalid value: " + what + "\", line: 0, column: 0)");
@@ -41,10 +45,17 @@ struct LambdaMARTParams {
         p.split_candidates = json_u32(json_field(v, "split_candidates"), "split_candidates");
         p.sigma = json_f64(json_field(v, "sigma"), "sigma");
         p.quiet = json_bool(json_field(v, "quiet"), "quiet");
+        if (const Value* g = v.find("grower")) {  // optional (serde: default + skip_serializing_if)
+            if (!g->is_string()) fail_raw("Error(\"invalid type: expected a string for grower\", line: 0, column: 0)");
+            if (g->s != "exact" && g->s != "histogram") invalid("grower must be `exact` or `histogram`, not `" + g->s + "`");
+            p.histogram = g->s == "histogram";
+        }
         if (p.num_trees < 1) invalid("num_trees must be at least 1");
         if (!(std::isfinite(p.learning_rate) && p.learning_rate > 0.0)) invalid("learning_rate must be finite and greater than 0");
         if (p.max_depth < 1) invalid("max_depth must be at least 1");
         if (!(std::isfinite(p.sigma) && p.sigma > 0.0)) invalid("sigma must be finite and greater than 0");
+        if (p.histogram && (p.split_candidates < 2 || p.split_candidates > 256))
+            invalid("split_candidates must be between 2 and 256 for the histogram grower (bins are one byte)");
         return p;
     }
     Value to_json() const {
@@ -56,6 +67,7 @@ struct LambdaMARTParams {
         o.set("split_candidates", Value::uint(split_candidates));
         o.set("sigma", Value::number(sigma));
         o.set("quiet", Value::boolean(quiet));
+        if (histogram) o.set("grower", Value::string("histogram"));
         return o;
     }
 };
@@ -68,11 +80,26 @@ inline void lambdamart_check_measure(const std::string& measure) {
         fail_str("LambdaMART: unsupported training measure \"" + measure + "\" (supported: ndcg, ndcg@k)");
 }
 
+// the instance list: queries in the view's order, ids ascending inside each (RFTrainer's order)
+inline std::vector<uint32_t> lambdamart_instance_list(const frdev::HostCSR& csr) {
+    std::vector<uint32_t> ids;
+    ids.reserve(csr.n);
+    for (size_t qi = 0; qi < csr.nq; qi++) {
+        const size_t b = ids.size();
+        ids.insert(ids.end(), csr.perm.begin() + csr.qoff[qi], csr.perm.begin() + csr.qoff[qi + 1]);
+        std::sort(ids.begin() + b, ids.end());
+    }
+    return ids;
+}
+
 struct LambdaMARTStats {
     uint32_t trees = 0;
     double seconds = 0.0;
     double t_gradient = 0.0, t_grow = 0.0, t_leaves = 0.0, t_update = 0.0;  // wall seconds per stage (device work waited for)
     std::vector<double> train_measure;                                        // evaluator mean of the running scores after each tree
+    bool histogram = false;
+    uint32_t bins = 0;     // histogram grower: k
+    double t_bins = 0.0;   // one-off binning (0 when the view's kept bins were reused, and for the exact grower)
 
     Value to_json() const {
         Value o = Value::object();
@@ -82,6 +109,9 @@ struct LambdaMARTStats {
         o.set("grow_ms", Value::number(t_grow * 1e3));
         o.set("leaves_ms", Value::number(t_leaves * 1e3));
         o.set("update_ms", Value::number(t_update * 1e3));
+        o.set("grower", Value::string(histogram ? "histogram" : "exact"));
+        o.set("bins_ms", Value::number(t_bins * 1e3));
+        if (histogram) o.set("bins", Value::uint(bins));
         Value a = Value::array();
         for (double x : train_measure) a.push(Value::number(x));
         o.set("train_measure", std::move(a));
@@ -110,23 +140,25 @@ class LambdaMARTTrainer {
         if (feats.empty()) fail_str("assertion failed: !features.is_empty()");
         if (csr.nq == 0) fail_str("assertion failed: !data.queries().is_empty()");
         // the instance list: queries in the view's order, ids ascending inside each (RFTrainer's order)
-        std::vector<uint32_t> root_ids;
-        root_ids.reserve(csr.n);
-        for (size_t qi = 0; qi < csr.nq; qi++) {
-            const size_t b = root_ids.size();
-            root_ids.insert(root_ids.end(), csr.perm.begin() + csr.qoff[qi], csr.perm.begin() + csr.qoff[qi + 1]);
-            std::sort(root_ids.begin() + b, root_ids.end());
-        }
-        if ((uint64_t)root_ids.size() * feats.size() >= (1ull << 31))
+        const std::vector<uint32_t> root_ids = lambdamart_instance_list(csr);
+        if (!p_.histogram && (uint64_t)root_ids.size() * feats.size() >= (1ull << 31))
             fail_str("LambdaMART: instances x features exceeds the device sort's index range");
         const std::vector<uint32_t> root_off = {0u, (uint32_t)root_ids.size()};
         std::vector<uint32_t> positions(root_ids.size());
         if (!dev.rf_positions(root_ids, positions.data(), &err)) fail_str(err);
-        if (!dev.rf_set_presence(core.present_bits.empty() ? nullptr : core.present_bits.data(), core.present_words, core.n, &err))
+        if (!p_.histogram && !dev.rf_set_presence(core.present_bits.empty() ? nullptr : core.present_bits.data(), core.present_words, core.n, &err))
             fail_str(err);
         uint32_t max_id = 0;
         for (uint32_t id : root_ids) max_id = std::max(max_id, id);
 
+        stats_.histogram = p_.histogram;
+        std::unique_ptr<HistGrower> hist;
+        if (p_.histogram) {
+            hist.reset(new HistGrower(dev, feats, p_.split_candidates, p_.max_depth, p_.min_leaf_support));
+            auto tb0 = tnow();
+            if (hist->prepare(positions)) stats_.t_bins = secs(tb0, tnow());
+            stats_.bins = p_.split_candidates;
+        }
         RFParams rp;
         rp.quiet = true;
         rp.num_trees = 1;
@@ -153,28 +185,30 @@ class LambdaMARTTrainer {
             if (!dev.lambda_gradients(ev_.norms.data(), ev_.depth, p_.sigma, &err)) fail_str(err);
             if (!frdev::device_synchronize(&err)) fail_str(err);
             auto tb = tnow();
-            std::shared_ptr<TreeNode> root = grower.grow_lambda_tree(dev, root_off, root_ids, feats, positions.data(), rst);
-            auto tc = tnow();
-            // leaves: route every instance through a copy of the tree whose leaves hold their index
+            double leaf_secs = 0.0;
+            std::shared_ptr<TreeNode> root = hist ? hist->grow(nullptr, nullptr, &leaf_secs)
+                                                  : grower.grow_lambda_tree(dev, root_off, root_ids, feats, positions.data(), rst);
+            auto tc = tnow() - std::chrono::duration_cast<std::chrono::steady_clock::duration>(std::chrono::duration<double>(leaf_secs));
+            // leaves (exact grower): route every instance through a copy of the tree whose leaves hold their index
             std::vector<TreeNode*> leaves;
-            std::shared_ptr<TreeNode> routing = number_leaves(*root, leaves);
-            {
+            std::shared_ptr<TreeNode> routing = hist ? nullptr : number_leaves(*root, leaves);
+            if (!hist) {
                 Model rm;
                 rm.kind = Model::DecisionTree;
                 rm.tree = routing;
                 score_model(*view_, rm, &dev);
+                if (!dev.download_scores(0, leaf_of.data(), leaf_of.size(), &err)) fail_str(err);
+                if (!dev.lambda_download_positions(&lam, &wt, &err)) fail_str(err);
+                std::vector<double> sl(leaves.size(), 0.0), sw(leaves.size(), 0.0);
+                for (size_t g = 0; g < root_ids.size(); g++) {
+                    const double lv = leaf_of[root_ids[g]];
+                    if (!(lv >= 0.0 && lv < (double)leaves.size())) fail_str("LambdaMART: an instance was routed to no leaf");
+                    const size_t L = (size_t)lv;
+                    sl[L] = sl[L] + lam[positions[g]];
+                    sw[L] = sw[L] + wt[positions[g]];
+                }
+                for (size_t L = 0; L < leaves.size(); L++) leaves[L]->value = sw[L] != 0.0 ? sl[L] / sw[L] : 0.0;
             }
-            if (!dev.download_scores(0, leaf_of.data(), leaf_of.size(), &err)) fail_str(err);
-            if (!dev.lambda_download_positions(&lam, &wt, &err)) fail_str(err);
-            std::vector<double> sl(leaves.size(), 0.0), sw(leaves.size(), 0.0);
-            for (size_t g = 0; g < root_ids.size(); g++) {
-                const double lv = leaf_of[root_ids[g]];
-                if (!(lv >= 0.0 && lv < (double)leaves.size())) fail_str("LambdaMART: an instance was routed to no leaf");
-                const size_t L = (size_t)lv;
-                sl[L] = sl[L] + lam[positions[g]];
-                sw[L] = sw[L] + wt[positions[g]];
-            }
-            for (size_t L = 0; L < leaves.size(); L++) leaves[L]->value = sw[L] != 0.0 ? sl[L] / sw[L] : 0.0;
             auto td = tnow();
             // update: slot 0 = tree(x); acc = acc + learning_rate * slot 0; slot 0 = acc
             Model tm;

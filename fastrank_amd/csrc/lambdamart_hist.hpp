@@ -1,0 +1,134 @@
+// LambdaMART's histogram grower, host side ("Histogram grower"; device side: kernels_hist.inc).
+//
+// The tree is grown level by level.  The device holds the u8 bin matrix (built once per instance list, feature list and k),
+// the tree's int64 fixed-point gradients Q / W, an index list partitioned by node and the level's histograms; the host
+// holds the tree and applies the selection rule: per node the largest importance over the features' last-maximum
+// candidates, the later feature among equals.  A level's histograms are built for the smaller child of every split and
+// derived for the larger one (parent - child: integer sums, so exact).  Leaf values come from the leaves' own integer sums:
+// the partition a split trains on (bins 0..j) is the one the scoring rule applies (x <= edge_j), so no routing pass.
+#pragma once
+#include <cmath>
+
+#include "host.hpp"
+
+namespace fr {
+
+class HistGrower {
+  public:
+    HistGrower(frdev::DeviceDataset& dev, std::vector<uint32_t> feats, uint32_t k, uint32_t max_depth, uint32_t min_leaf)
+        : dev_(dev), feats_(std::move(feats)), k_(k), max_depth_(max_depth), min_leaf_(min_leaf) {}
+    ~HistGrower() { dev_.hist_end(); }
+
+    // bins for the instance list at `positions`; true when they were built now (false: the view's kept ones were reused)
+    bool prepare(const std::vector<uint32_t>& positions) {
+        std::string err;
+        bool built = false;
+        if (!dev_.hist_bins(positions.data(), positions.size(), feats_, k_, &built, &err)) fail_str(err);
+        if (!dev_.hist_edges(&edges_, &nedges_, &err)) fail_str(err);
+        n_ = (uint32_t)positions.size();
+        return built;
+    }
+
+    // One tree for the gradients of the last gradient pass (lam_list == nullptr) or for lam_list / wt_list[n] in
+    // instance-list order.  *leaf_seconds: the share of the leaf sums.
+    std::shared_ptr<TreeNode> grow(const double* lam_list, const double* wt_list, double* leaf_seconds = nullptr) {
+        using Dev = frdev::DeviceDataset;
+        std::string err;
+        int s_l = 0, s_w = 0;
+        bool all_zero = false;
+        if (!dev_.hist_quantise(lam_list, wt_list, &s_l, &s_w, &all_zero, &err)) fail_str(err);
+        auto root = std::make_shared<TreeNode>();
+        if (all_zero) return root;  // one leaf of value 0.0
+        struct Open {
+            TreeNode* node;
+            uint32_t slot, begin, end, depth;
+        };
+        std::vector<Open> open, next;
+        std::vector<TreeNode*> leaf_nodes;
+        std::vector<Dev::HistNode> leaves;
+        auto close = [&](TreeNode* t, uint32_t b, uint32_t e) {
+            leaf_nodes.push_back(t);
+            leaves.push_back({(uint32_t)leaves.size(), b, e});
+        };
+        if (enterable(n_, 1)) {
+            if (!dev_.hist_root(&err)) fail_str(err);
+            open.push_back({root.get(), 0u, 0u, n_, 1u});
+        } else {
+            close(root.get(), 0u, n_);
+        }
+        const size_t F = feats_.size();
+        std::vector<Dev::HistNode> nodes, builds;
+        std::vector<Dev::HistBest> best;
+        std::vector<Dev::HistSplit> splits;
+        std::vector<Dev::HistSub> subs;
+        bool rooted = !open.empty();
+        while (!open.empty()) {
+            nodes.clear(), builds.clear(), splits.clear(), subs.clear(), next.clear();
+            for (const Open& o : open) nodes.push_back({o.slot, o.begin, o.end});
+            if (!dev_.hist_search(nodes, min_leaf_, &best, &err)) fail_str(err);
+            uint32_t next_slots = 0;
+            for (size_t a = 0; a < open.size(); a++) {
+                const Open& o = open[a];
+                const Dev::HistBest* w = nullptr;
+                size_t wf = 0;
+                for (size_t fi = 0; fi < F; fi++) {  // the last maximum: a later feature wins among equals
+                    const Dev::HistBest& b = best[a * F + fi];
+                    if (b.valid && (w == nullptr || b.imp >= w->imp)) w = &b, wf = fi;
+                }
+                if (w == nullptr) {
+                    close(o.node, o.begin, o.end);
+                    continue;
+                }
+                const uint32_t n = o.end - o.begin, nl = w->nl, nr = n - nl;
+                if (w->edge >= nedges_[wf] || nl == 0 || nl >= n) fail_str("LambdaMART histogram grower: internal error: an impossible split");
+                o.node->leaf = false;
+                o.node->fid = feats_[wf];
+                o.node->value = (double)edges_[wf * 256 + w->edge];
+                o.node->lhs.reset(new TreeNode());
+                o.node->rhs.reset(new TreeNode());
+                splits.push_back({o.begin, o.end, (uint32_t)wf, w->edge, nl});
+                const uint32_t mid = o.begin + nl;
+                const bool el = enterable(nl, o.depth + 1), er = enterable(nr, o.depth + 1);
+                if (!el) close(o.node->lhs.get(), o.begin, mid);
+                if (!er) close(o.node->rhs.get(), mid, o.end);
+                if (!el && !er) continue;
+                const bool left_small = nl <= nr;
+                const uint32_t small_slot = next_slots++;
+                builds.push_back(left_small ? Dev::HistNode{small_slot, o.begin, mid} : Dev::HistNode{small_slot, mid, o.end});
+                uint32_t large_slot = 0;
+                if (left_small ? er : el) {
+                    large_slot = next_slots++;
+                    subs.push_back({o.slot, small_slot, large_slot});
+                }
+                if (el) next.push_back({o.node->lhs.get(), left_small ? small_slot : large_slot, o.begin, mid, o.depth + 1});
+                if (er) next.push_back({o.node->rhs.get(), left_small ? large_slot : small_slot, mid, o.end, o.depth + 1});
+            }
+            if (!dev_.hist_split(splits, builds, subs, next_slots, &err)) fail_str(err);
+            open.swap(next);
+        }
+        auto t0 = std::chrono::steady_clock::now();
+        if (!rooted) {  // (the index list of a tree that never searched: the identity)
+            if (!dev_.hist_root(&err)) fail_str(err);
+        }
+        std::vector<long long> qw;
+        if (!dev_.hist_leaf_sums(leaves, &qw, &err)) fail_str(err);
+        for (size_t i = 0; i < leaf_nodes.size(); i++) {
+            const long long q = qw[i * 2], w = qw[i * 2 + 1];
+            leaf_nodes[i]->value = w != 0 ? std::ldexp((double)q, -s_l) / std::ldexp((double)w, -s_w) : 0.0;
+        }
+        if (leaf_seconds) *leaf_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return root;
+    }
+
+  private:
+    // rf_train.hpp's rule: may a node be searched at all?
+    bool enterable(uint32_t n, uint32_t depth) const { return n >= 2 && depth < max_depth_ && n >= min_leaf_; }
+
+    frdev::DeviceDataset& dev_;
+    std::vector<uint32_t> feats_;
+    uint32_t k_, max_depth_, min_leaf_, n_ = 0;
+    std::vector<float> edges_;
+    std::vector<uint32_t> nedges_;
+};
+
+}  // namespace fr

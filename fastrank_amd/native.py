@@ -81,6 +81,42 @@ def lambda_gradients(model: CModel, dataset: CDataset, measure: str = "ndcg", si
     return lam, wt
 
 
+def hist_bins(dataset: CDataset, split_candidates: int):
+    """The histogram grower's bins of a dataset view: (instance list ids[n], feature ids[f] ascending, edges: a list of f
+    float32 arrays, bins uint8[f, n] over the instance list)."""
+    n = sum(len(ids) for ids in dataset.instances_by_query().values())
+    f = len(dataset.feature_ids())
+    ids = np.zeros(n, dtype=np.uint32)
+    feats = np.zeros(f, dtype=np.uint32)
+    edges = np.zeros((f, 256), dtype=np.float32)
+    nedges = np.zeros(f, dtype=np.uint32)
+    bins = np.zeros((f, n), dtype=np.uint8)
+    _status(
+        _load().fr_debug_hist_bins(
+            dataset.pointer, int(split_candidates), n, f, ids.ctypes.data, feats.ctypes.data, edges.ctypes.data,
+            nedges.ctypes.data, bins.ctypes.data,
+        )
+    )
+    return ids, feats, [edges[s, : nedges[s]].copy() for s in range(f)], bins
+
+
+def hist_tree(dataset: CDataset, lam: np.ndarray, wt: np.ndarray, split_candidates: int, max_depth: int,
+              min_leaf_support: int) -> CModel:
+    """One tree of LambdaMART's histogram grower for the gradients lam / wt (indexed by instance id)."""
+    lam = np.ascontiguousarray(lam, dtype=np.float64)
+    wt = np.ascontiguousarray(wt, dtype=np.float64)
+    if lam.shape != wt.shape or lam.ndim != 1:
+        raise ValueError("lam and wt must be 1-d arrays of the same length")
+    return CModel(
+        _unwrap(
+            _load().fr_debug_hist_tree(
+                dataset.pointer, int(split_candidates), int(max_depth), int(min_leaf_support), lam.ctypes.data,
+                wt.ctypes.data, lam.shape[0],
+            )
+        )
+    )
+
+
 def rank_order(model: CModel, dataset: CDataset) -> Tuple[np.ndarray, np.ndarray]:
     """(instance ids grouped by query, best first; offsets[nq+1]) under the reference's
     (score desc, gain asc, id asc) order."""

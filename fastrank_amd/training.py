@@ -80,7 +80,9 @@ class RandomForestParams(_LearnerParams):
 @dataclasses.dataclass
 class LambdaMARTParams(_LearnerParams):
     """Gradient-boosted regression trees fitted to LambdaRank gradients, trained on the device (csrc/lambdamart.hpp,
-    kernels_lambda.inc).  The wire form requires all seven keys.  Measures: ndcg and ndcg@k."""
+    kernels_lambda.inc).  The wire form requires the first seven keys.  Measures: ndcg and ndcg@k.
+    `grower`: "exact" (the default; not written to the wire form) or "histogram" (features binned once into at most
+    `split_candidates` <= 256 bins, per-node histograms: csrc/lambdamart_hist.hpp, kernels_hist.inc)."""
 
     VARIANT: ClassVar[str] = "LambdaMART"
 
@@ -91,6 +93,13 @@ class LambdaMARTParams(_LearnerParams):
     split_candidates: int = 64
     sigma: float = 1.0
     quiet: bool = False
+    grower: str = "exact"
+
+    def to_dict(self) -> Dict[str, Any]:
+        wire = dataclasses.asdict(self)
+        if wire["grower"] == "exact":  # serde: skip_serializing_if
+            del wire["grower"]
+        return wire
 
 
 @dataclasses.dataclass

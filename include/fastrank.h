@@ -178,6 +178,17 @@ const void *fr_evaluate_dense(const CModel *model, const CDataset *dataset, cons
 const void *fr_debug_lambda_gradients(const CModel *model, const CDataset *dataset, const CQRel *qrel,
                                       const void *measure, double sigma, double *lambda_out,
                                       double *weight_out, size_t out_len);
+/* LambdaMART histogram grower, test hooks.  The view's instance list (queries in the view's
+ * order, ids ascending inside each; n entries) and features (ascending; f entries) are written to ids_out / feats_out.
+ * edges_out[s * 256 + j], j < nedges_out[s]: the edges of feature slot s for k = split_candidates (2..256);
+ * bins_out[s * n + i]: the bin of instance-list entry i.  Returns NULL on success or an error-envelope string. */
+const void *fr_debug_hist_bins(const CDataset *dataset, uint32_t split_candidates, size_t n, size_t f,
+                               uint32_t *ids_out, uint32_t *feats_out, float *edges_out,
+                               uint32_t *nedges_out, uint8_t *bins_out);
+/* One histogram tree (a DecisionTree model) grown from lambda / weight indexed by instance id (len entries). */
+const CResult *fr_debug_hist_tree(const CDataset *dataset, uint32_t split_candidates, uint32_t max_depth,
+                                  uint32_t min_leaf_support, const double *lambda, const double *weight,
+                                  size_t len);
 /* Full per-query rank order under the reference's total order (src/evaluators.rs:34-49):
  * out_instance_ids[n] grouped by query (device query order), best first; out_offsets[nq+1]. */
 const void *fr_rank_order(const CModel *model, const CDataset *dataset, uint32_t *out_instance_ids,

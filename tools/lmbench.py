@@ -1,6 +1,7 @@
 """lmbench.py -- LambdaMART training time on an MSLR-WEB30K-shaped matrix (bench.py's generator), one JSON line.
 
     python tools/lmbench.py --shape 30k --trees 100            # the device: seconds per tree and the per-stage split
+    python tools/lmbench.py --shape 30k --trees 100 --grower histogram   # the histogram grower
     python tools/lmbench.py --shape 30k --cpu-baseline 0.01    # the numpy restatement (tests/lambdamart_model.py) timed on
                                                                # a query sample, scaled to the full shape (labelled as such)
 Every other parameter is the LambdaMART default (TrainRequest.lambdamart()).
@@ -30,6 +31,7 @@ def device_run(args, X, y, qid):
     req.measure = args.measure
     req.params.num_trees = args.trees
     req.params.quiet = True
+    req.params.grower = args.grower
     # upload and first touch of the device (not part of training)
     native.device_info(ds)
     t_ds = time.perf_counter() - t0
@@ -47,9 +49,10 @@ def device_run(args, X, y, qid):
         "shape": args.shape, "n": int(X.shape[0]), "d": int(X.shape[1]), "queries": int(len(np.unique(qid))),
         "measure": args.measure, "trees": T, "params": req.params.to_dict(),
         "dataset_seconds": t_ds, "train_seconds": wall, "seconds_per_tree": wall / T,
+        "grower": st["grower"], "bins_ms": st["bins_ms"],
         "per_tree_ms": {k: st[k + "_ms"] / T for k in ("gradient", "grow", "leaves", "update")},
         "train_measure_first": st["train_measure"][0], "train_measure_last": st["train_measure"][-1],
-        "kernel_profile": {k: v for k, v in prof.items() if "lambda" in k or "rf_" in k or "tree" in k},
+        "kernel_profile": {k: v for k, v in prof.items() if "lambda" in k or "rf_" in k or "tree" in k or "hist_" in k},
         "model_nodes": len(json.dumps(model.to_dict())),
     }
 
@@ -88,6 +91,7 @@ def main():
     ap.add_argument("--shape", default="30k", choices=sorted(SHAPES))
     ap.add_argument("--trees", type=int, default=100)
     ap.add_argument("--measure", default="ndcg")
+    ap.add_argument("--grower", default="exact", choices=["exact", "histogram"])
     ap.add_argument("--cpu-baseline", type=float, default=0.0, help="query fraction for the CPU restatement (0: device run)")
     args = ap.parse_args()
     n, d, q, seed = SHAPES[args.shape]
