@@ -72,9 +72,11 @@ def _sq_error(t):
     return seq_sum((mean - t) ** 2)
 
 
-def _grow(X, target, rows, ridx, feats, depth, max_depth, min_leaf, k):
+def _grow(X, target, rows, ridx, feats, depth, max_depth, min_leaf, k, present=None):
     """rows: instance ids of the node, ridx: their index in the instance list.  Returns a nested dict whose leaves are
-    {"LeafNode": rows} (values filled in later)."""
+    {"LeafNode": rows} (values filled in later).  present[i, f] (file-loaded datasets): False where instance i does not
+    hold feature f; such a value reads 0.0, but a feature's range is taken over the held values only, and a feature fewer
+    than two of the node's instances hold yields no candidate (the RF grower's FeatureStats rule)."""
     n = len(rows)
     leaf = {"LeafNode": None}
     if n == 0 or depth >= max_depth or n < min_leaf or n <= 1:
@@ -85,7 +87,10 @@ def _grow(X, target, rows, ridx, feats, depth, max_depth, min_leaf, k):
     have, best = False, None
     for f in feats:
         v = X[rows, f].astype(np.float64)
-        fmin, fmax = float(v.min()), float(v.max())
+        held = v if present is None else v[present[rows, f]]
+        if held.size <= 1:
+            continue
+        fmin, fmax = float(held.min()), float(held.max())
         order = np.lexsort((ridx, v))
         vs = v[order]
         ts = target[rows[order]].astype(np.float64)
@@ -111,8 +116,8 @@ def _grow(X, target, rows, ridx, feats, depth, max_depth, min_leaf, k):
     _, split, pos, f, order = best
     r, x = rows[order], ridx[order]
     return {"FeatureSplit": {"fid": int(f), "split": float(split),
-                             "lhs": _grow(X, target, r[:pos], x[:pos], feats, depth + 1, max_depth, min_leaf, k),
-                             "rhs": _grow(X, target, r[pos:], x[pos:], feats, depth + 1, max_depth, min_leaf, k)}}
+                             "lhs": _grow(X, target, r[:pos], x[:pos], feats, depth + 1, max_depth, min_leaf, k, present),
+                             "rhs": _grow(X, target, r[pos:], x[pos:], feats, depth + 1, max_depth, min_leaf, k, present)}}
 
 
 def route(tree, X, ids):
@@ -133,15 +138,16 @@ def _leaves(tree):
     return _leaves(tree["FeatureSplit"]["lhs"]) + _leaves(tree["FeatureSplit"]["rhs"])
 
 
-def fit_tree(X, lam, wt, order_ids, feats, max_depth, min_leaf, k):
-    """One boosting round's tree for gradients lam / wt (by instance id); order_ids: the instance list."""
+def fit_tree(X, lam, wt, order_ids, feats, max_depth, min_leaf, k, present=None):
+    """One boosting round's tree for gradients lam / wt (by instance id); order_ids: the instance list; present: see
+    `_grow` (None: every value is held)."""
     order_ids = np.asarray(order_ids, dtype=np.int64)
     target = np.asarray(lam, dtype=np.float64).astype(np.float32)
     feats = sorted(int(f) for f in feats)
     if k < 2:
         tree = {"LeafNode": None}
     else:
-        tree = _grow(X, target, order_ids, np.arange(len(order_ids)), feats, 1, max_depth, min_leaf, k)
+        tree = _grow(X, target, order_ids, np.arange(len(order_ids)), feats, 1, max_depth, min_leaf, k, present)
     reached = route(tree, X, order_ids)
     for leaf in _leaves(tree):
         sel = np.array([r is leaf for r in reached], dtype=bool)

@@ -9,7 +9,8 @@ import fastrank_amd as fr
 from fastrank_amd import native
 from oracle import pyoracle as o
 from tests import lambdamart_model as lm
-from tests.conftest import GOLDEN, synth_dataset
+from tests import lambdamart_bound as hx
+from tests.conftest import GOLDEN, ranksvm_presence, synth_dataset
 
 pytestmark = pytest.mark.gpu
 
@@ -303,3 +304,159 @@ def test_quiet_false_prints_one_line_per_tree(trec, capfd):
     out = capfd.readouterr().out
     rows = [l for l in out.splitlines() if l.startswith("|") and l.strip("|").split("|")[0].strip().isdigit()]
     assert len(rows) == 3
+
+
+# --- the kernel against exact arithmetic (tests/lambdamart_exact.py; the bound: tests/test_lambdamart_exact_host.py) -------
+
+def _designed_dataset():
+    queries = hx.designed_queries() + hx.random_queries(3, 12)
+    X, y, qid = hx.as_dataset(queries)
+    return X, y, qid, fr.CDataset.from_numpy(X, y, qid), o.Dataset(X, y, qid)
+
+
+@pytest.mark.parametrize("sigma", hx.SIGMAS)
+def test_gradient_kernel_within_bound_of_exact_on_designed_queries(sigma):
+    """Equal scores, saturated gaps both ways, labels 0.5 / -1 / 30, one positive label, random queries of 2..400
+    documents, as one dataset of short queries; depths none / 1 / 10 / beyond the query.  Every document's lambda and w lie
+    within the derived bound of the exact value (the same constants as on the CPU side, the 2 ulp assumed for exp among
+    them).  One designed input does not carry over: the scores must come from `predict_scores_dense`, and a linear
+    model's sum turns -0.0 into +0.0, so the "signed zeros" query reaches the kernel as all +0.0 (one more all-equal
+    query); the -0.0 / +0.0 mix is held on the CPU side only."""
+    X, y, qid, g, c = _designed_dataset()
+    model = fr.CModel.from_dict({"Linear": {"weights": hx.WEIGHTS}})
+    scores = native.predict_scores_dense(model, g)
+    worst = 0.0
+    for measure in hx.MEASURES:
+        norms = c.default_norms(measure)
+        lam, wt = native.lambda_gradients(model, g, measure, sigma)
+        worst = max(worst, hx.check_dataset(c, scores, y, lam, wt, measure, sigma, norms))
+    print("kernel, designed queries, sigma %s: worst error / bound = %.4f" % (sigma, worst))
+
+
+_CONTINUOUS = [0.25, 1.0, 0.0, 0.0, 0.5, 0.0]  # the model of the rtol tests above: column 0 is continuous, ties are rare
+_INTEGER = [0.0, 1.0, 0.0, 0.0, 0.5, 0.0]      # the integer columns only: a few dozen scores, tie groups of hundreds
+
+
+@pytest.mark.parametrize("weights,measure,sigma", [(_CONTINUOUS, "ndcg", 0.3), (_CONTINUOUS, "ndcg@10", 1.0), (_CONTINUOUS, "ndcg@5000", 1.5),
+                                                   (_INTEGER, "ndcg@10", 1.5), (_INTEGER, "ndcg", 1.0)],
+                         ids=["continuous-ndcg-0.3", "continuous-ndcg@10-1.0", "continuous-ndcg@5000-1.5", "tied-ndcg@10-1.5", "tied-ndcg-1.0"])
+def test_gradient_kernel_within_bound_of_exact_on_long_queries(weights, measure, sigma):
+    """The LDS path at its limit (4 096 documents) and the slab path (4 097: the misaligned block; 6 001), with 300 and 2:
+    about 50 chosen documents of each -- the first and last stored, both sides of the cut, the best and worst ranked,
+    members of tie groups, a spread of the rest.  Under the continuous model two documents hardly ever share a score, so
+    the integer model is there for the rank count's gain / id branch: with it the chosen documents of every query of 300
+    documents and more must hold a tie group with different labels (and, under any model, both sides of the cut), or the
+    test fails rather than pass without them."""
+    X, y, qid = _long_query_set()
+    g, c = fr.CDataset.from_numpy(X, y, qid), o.Dataset(X, y, qid)
+    model = fr.CModel.from_dict({"Linear": {"weights": weights}})
+    scores = native.predict_scores_dense(model, g)
+    lam, wt = native.lambda_gradients(model, g, measure, sigma)
+    only = {k for k, ids in enumerate(lm.query_lists(c)) if len(ids) in (2, 300, 4096, 4097, 6001)}
+    assert len(only) == 5
+    worst = hx.check_dataset(c, scores, y, lam, wt, measure, sigma, c.default_norms(measure), limit=50, only=only,
+                             demand_ties_from=300 if weights is _INTEGER else None)
+    print("kernel, long queries, %s model, %s, sigma %s: worst error / bound = %.4f" % (
+        "integer" if weights is _INTEGER else "continuous", measure, sigma, worst))
+
+
+def _leaf_values(node, out):
+    if "LeafNode" in node:
+        out.append(node["LeafNode"])
+    else:
+        _leaf_values(node["FeatureSplit"]["lhs"], out)
+        _leaf_values(node["FeatureSplit"]["rhs"], out)
+    return out
+
+
+@pytest.mark.parametrize("grower", ["exact", "histogram"])
+def test_training_through_saturation_stays_finite(grower):
+    """Five trees with a learning rate that drives sigma (s_h - s_l) beyond +-745 after the first: every gradient, leaf value
+    and running score is finite, and train_measure is the oracle evaluator's mean of the prediction (a Newton step of
+    1e15 from a saturated leaf would at least show)."""
+    X, y, qid, g, c = _designed_dataset()
+    measure, T = "ndcg@10", 5
+    req = _request(measure, num_trees=T, max_depth=4, min_leaf_support=1, split_candidates=16, sigma=1.5, learning_rate=2000.0)
+    req.params.grower = grower
+    model = g.train_model(req)
+    st = native.last_train_stats()["lambdamart"]
+    trees = [m["DecisionTree"] for m in model.to_dict()["Ensemble"]["models"]]
+    norms = c.default_norms(measure)
+    queries = lm.query_lists(c)
+    saturated = False
+    for t in range(T + 1):
+        prefix = fr.CModel.from_dict({"Ensemble": {"weights": [2000.0] * t, "models": [{"DecisionTree": x} for x in trees[:t]]}})
+        s = native.predict_scores_dense(prefix, g)
+        assert np.all(np.isfinite(s)), t
+        saturated = saturated or any(1.5 * (s[ids].max() - s[ids].min()) > 745.0 for ids in queries)
+        if t > 0:
+            assert np.all(np.isfinite(_leaf_values(trees[t - 1], []))), t
+            per_q, err = c.metric_from_scores(measure, s, norms)
+            assert err == 0 and st["train_measure"][t - 1] == o.mean(per_q), t
+        lam, wt = native.lambda_gradients(prefix, g, measure, 1.5)
+        assert np.all(np.isfinite(lam)) and np.all(np.isfinite(wt)), t
+    assert saturated, "the case must reach saturation, or it tests nothing"
+
+
+def test_randomised_lambdamart_soak():
+    """tools/fuzz_lambdamart.py: random small datasets (1..40 features, constant / signed-zero / denormal / huge columns,
+    scattered queries, odd label sets, sampled views, file-loaded sparse rows) and random parameters, both growers; every
+    stage of every case must equal the restatement's."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "tools", "fuzz_lambdamart.py"), "--iters", "30", "--seed", "5"],
+                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
+    last = out.stdout.strip().splitlines()[-1]
+    assert out.returncode == 0, out.stdout[-2000:]
+    res = json.loads(last)
+    assert res["mismatches"] == 0 and res["both_error"] * 10 <= res["iters"]
+
+
+def _sparse_file(path):
+    """A small ranksvm file whose feature values all lie in 4 .. 6 and a third of whose rows list only three of their
+    nine features: an absent value reads 0.0, far outside the range of the held ones, so a grower that took a feature's range
+    over all the values it reads would place other thresholds.  Returns (X with the unlisted column 0, y, qid)."""
+    rng = np.random.default_rng(31)
+    n, d = 160, 9
+    qid = np.repeat(np.arange(1, 9, dtype=np.int64), 20)
+    y = rng.choice(5, n).astype(np.float64)
+    X = np.zeros((n, d + 1), dtype=np.float32)
+    X[:, 1:] = 4.0 + rng.integers(0, 17, (n, d)) / 8.0
+    X[:, 2] += (0.125 * y).astype(np.float32)
+    with open(path, "w") as fh:
+        for i in range(n):
+            if rng.random() < 0.35:  # three of nine, the last among them: under half of 1 .. 9, so the row holds only these
+                drop = np.ones(d, dtype=bool)
+                drop[rng.choice(d - 1, 2, replace=False)] = False
+                drop[d - 1] = False
+                X[i, 1:][drop] = 0.0
+            fh.write("%d qid:%d %s # doc%d\n" % (int(y[i]), int(qid[i]), " ".join("%d:%r" % (j, float(X[i, j])) for j in range(1, d + 1) if X[i, j] != 0.0), i))
+    return X, y, qid
+
+
+def test_stagewise_identity_file_loaded_with_absent_values(tmp_path):
+    """The exact grower on a file-loaded dataset: a feature's range is taken over the values the node's instances HOLD
+    (the RF grower's FeatureStats rule, restated in lm.fit_tree's `present`; the mask comes from conftest's reading of the
+    file, not from the loader).  Every tree equals the restatement's with the mask, and the mask matters here."""
+    path = str(tmp_path / "sparse.train")
+    X, y, qid = _sparse_file(path)
+    rd = fr.CDataset.open_ranksvm(path)
+    c = o.Dataset(X, y, qid)
+    present = ranksvm_presence(path, X.shape[1])
+    assert not present[:, 1:].all() and present[:, 1:].any(axis=0).all()
+    feats = sorted(rd.feature_ids())
+    assert feats == list(range(10))  # (0 too: a row that lists most of 1 .. max is held densely from index 0, which reads 0.0)
+    T, lr = 6, 0.1
+    req = _request("ndcg@10", num_trees=T, max_depth=4, min_leaf_support=3, split_candidates=16, learning_rate=lr)
+    trees = [m["DecisionTree"] for m in rd.train_model(req).to_dict()["Ensemble"]["models"]]
+    order_ids = np.concatenate(lm.query_lists(c))
+    mask_matters = False
+    for t in range(T):
+        prefix = fr.CModel.from_dict({"Ensemble": {"weights": [lr] * t, "models": [{"DecisionTree": x} for x in trees[:t]]}})
+        lam, wt = native.lambda_gradients(prefix, rd, "ndcg@10", 1.0)
+        assert trees[t] == lm.fit_tree(X, lam, wt, order_ids, feats, 4, 3, 16, present), "tree %d" % t
+        mask_matters = mask_matters or trees[t] != lm.fit_tree(X, lam, wt, order_ids, feats, 4, 3, 16, None)
+    assert mask_matters
+    exp = c.score_ensemble(trees, [lr] * T)
+    assert np.array_equal(native.predict_scores_dense(fr.CModel.from_dict({"Ensemble": {"weights": [lr] * T, "models": [{"DecisionTree": x} for x in trees]}}), rd), exp)

@@ -1704,3 +1704,16 @@ def test_sampled_views_share_the_parents_matrix_and_match_the_oracle(monkeypatch
             assert np.array_equal(np.asarray(got[k]), np.asarray(ref[k]), equal_nan=True)
         else:
             assert got[k] == ref[k], k
+
+
+def test_randomised_forest_scoring_soak():
+    """tools/fuzz_trees.py: random matrices (NaN, +-inf, -0.0, denormals) and random forests (depths 0..11, up to 400 trees, thresholds
+    on and between data values, absent features, odd weights); the device scores must equal the oracle's bit for bit."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "tools", "fuzz_trees.py"), "--iters", "8", "--seed", "13"],
+                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
+    last = out.stdout.strip().splitlines()[-1]
+    assert out.returncode == 0, out.stdout[-2000:]
+    assert json.loads(last)["mismatches"] == 0

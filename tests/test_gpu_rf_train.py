@@ -212,3 +212,16 @@ def test_file_loaded_dataset_feature_stats_skip_absent_values(method):
     dense_exp, _ = _oracle(c, req)
     assert fr.CDataset.from_numpy(X, y, qid).train_model(req).to_dict() == dense_exp
     assert dense_exp != exp
+
+
+def test_randomised_rf_training_soak():
+    """tools/fuzz_rf.py: random small datasets and random RandomForestParams (all four split methods, sampled views, cut batches,
+    several contexts); the device trainer must return the oracle's forest bit for bit."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "tools", "fuzz_rf.py"), "--iters", "60", "--seed", "11"],
+                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
+    last = out.stdout.strip().splitlines()[-1]
+    assert out.returncode == 0, out.stdout[-2000:]
+    assert json.loads(last)["mismatches"] == 0

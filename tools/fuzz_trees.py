@@ -9,6 +9,7 @@ inf - inf = NaN must be NaN on both sides).
 Usage: python tools/fuzz_trees.py --iters 300 [--seed 0]"""
 import argparse
 import collections
+import json
 import os
 import sys
 import time
@@ -129,6 +130,7 @@ def main():
                 bad += 1
                 print("MISMATCH iter", it, "n,d", X.shape, "trees", len(trees), "max |diff|", np.nanmax(np.abs(got - exp)), flush=True)
     print("fuzz_trees: %d datasets x 3 forests, %d mismatches, kernels %s, %.0f s" % (args.iters, bad, dict(kernels), time.time() - t0))
+    print(json.dumps({"iters": args.iters, "forests": 3 * args.iters, "mismatches": bad, "kernels": dict(kernels), "seconds": round(time.time() - t0, 1)}))
     sys.exit(1 if bad else 0)
 
 
