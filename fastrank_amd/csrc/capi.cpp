@@ -1362,6 +1362,66 @@ const void* fr_debug_lambda_gradients(const CModel* model, const CDataset* datas
     });
 }
 
+// per query of the view (its order) whether `queries` names it
+static std::vector<unsigned char> debug_query_flags(const uint32_t* queries, size_t n_queries, size_t nq) {
+    if (n_queries == 0) fr::fail_str("a query sample must name at least one query");
+    std::vector<unsigned char> flags(nq, 0);
+    for (size_t i = 0; i < n_queries; i++) {
+        if (queries[i] >= nq) fr::fail_str("a query sample names query " + std::to_string(queries[i]) + " of " + std::to_string(nq));
+        flags[queries[i]] = 1;
+    }
+    return flags;
+}
+
+// The sample LambdaMART's trainer uses for tree `tree` of the request parameters `params_json` ({"num_trees": ..}, the
+// LambdaMART variant's payload) on this view: {"features": [ids ascending], "queries": [indices in the view's order]}.
+// No device is touched.
+const void* fr_debug_lambdamart_sample(const CDataset* dataset, const void* params_json, uint32_t tree) {
+    return json_call([&]() {
+        const CDataset& ds = require_dataset(dataset);
+        const fr::LambdaMARTParams p = fr::LambdaMARTParams::from_json(parse_json_or_fail(accept_str("params_json", params_json)));
+        std::lock_guard<std::mutex> lk(api_mu_of(ds));
+        fr::DatasetView& view = *ds.view;
+        std::vector<uint32_t> feats = view.features;
+        std::sort(feats.begin(), feats.end());
+        const size_t nq = view.host_csr().nq;
+        fr::Rand64 master(p.seed);
+        fr::LambdaSample smp;
+        for (uint32_t t = 0; t <= tree; t++) smp = fr::lambdamart_next_sample(master, feats.size(), nq, p);
+        Value o = Value::object(), f = Value::array(), q = Value::array();
+        for (uint32_t s : smp.features) f.push(Value::uint(feats[s]));
+        for (uint32_t x : smp.queries) q.push(Value::uint(x));
+        o.set("features", std::move(f));
+        o.set("queries", std::move(q));
+        return frjson::dump(o);
+    });
+}
+
+// fr_debug_lambda_gradients for a query sample: queries[n_queries] = indices of the view's queries (its order).  Only their
+// instances are written.
+const void* fr_debug_lambda_gradients_sampled(const CModel* model, const CDataset* dataset, const CQRel* qrel, const void* measure,
+                                              double sigma, const uint32_t* queries, size_t n_queries, double* lambda_out,
+                                              double* weight_out, size_t out_len) {
+    return status_call([&]() {
+        const CModel& m = require_model(model);
+        const CDataset& ds = require_dataset(dataset);
+        std::string name = accept_str("measure", measure);
+        fr::lambdamart_check_measure(name);
+        if (out_len && (!lambda_out || !weight_out)) fr::fail_str("NULL pointer: gradient outputs");
+        if (!queries) fr::fail_str("NULL pointer: query sample");
+        std::lock_guard<std::mutex> lk(api_mu_of(ds));
+        fr::DatasetView& view = *ds.view;
+        if (view.instances.empty()) return;
+        const std::vector<unsigned char> flags = debug_query_flags(queries, n_queries, view.host_csr().nq);
+        fr::Evaluator ev = fr::make_evaluator(view, name, qrel ? &qrel->actual : nullptr);
+        frdev::DeviceDataset& dev = view.device();
+        fr::score_model(view, m.actual);
+        std::string err;
+        if (!dev.lambda_gradients(ev.norms.data(), ev.depth, sigma, &err, flags.data())) fr::fail_str(err);
+        if (!dev.lambda_download(lambda_out, weight_out, out_len, &err, flags.data())) fr::fail_str(err);
+    });
+}
+
 // the histogram grower's inputs for a view: its instance list and their positions, its features ascending
 static void hist_debug_lists(fr::DatasetView& view, std::vector<uint32_t>* ids, std::vector<uint32_t>* positions, std::vector<uint32_t>* feats) {
     *ids = fr::lambdamart_instance_list(view.host_csr());
@@ -1413,6 +1473,75 @@ const CResult* fr_debug_hist_tree(const CDataset* dataset, uint32_t split_candid
         }
         fr::HistGrower grower(view.device(), feats, split_candidates, max_depth, min_leaf_support);
         grower.prepare(positions);
+        auto* out = new CModel();
+        try {
+            out->actual.kind = fr::Model::DecisionTree;
+            out->actual.tree = grower.grow(lam.data(), wt.data());
+        } catch (...) {
+            delete out;
+            throw;
+        }
+        return out;
+    });
+}
+
+// fr_debug_hist_tree on a sample: queries[n_queries] = indices of the view's queries (NULL: all), features[n_features] =
+// feature ids of the view (NULL: all).  Gradients of instances outside the query sample are not read.
+const CResult* fr_debug_hist_tree_sampled(const CDataset* dataset, uint32_t split_candidates, uint32_t max_depth, uint32_t min_leaf_support,
+                                          const double* lambda, const double* weight, size_t len, const uint32_t* queries,
+                                          size_t n_queries, const uint32_t* features, size_t n_features) {
+    return c_call<CModel>([&]() {
+        const CDataset& ds = require_dataset(dataset);
+        if (!lambda || !weight) fr::fail_str("NULL pointer: gradient inputs");
+        if (max_depth < 1) fr::fail_str("max_depth must be at least 1");
+        std::lock_guard<std::mutex> lk(api_mu_of(ds));
+        fr::DatasetView& view = *ds.view;
+        const frdev::HostCSR& csr = view.host_csr();
+        std::vector<uint32_t> ids, positions, feats, sel;
+        hist_debug_lists(view, &ids, &positions, &feats);
+        std::vector<unsigned char> flags;
+        size_t n_t = ids.size();
+        if (queries) {
+            flags = debug_query_flags(queries, n_queries, csr.nq);
+            n_t = 0;
+            for (size_t q = 0; q < csr.nq; q++)
+                if (flags[q]) n_t += csr.qoff[q + 1] - csr.qoff[q];
+        }
+        if (features) {
+            std::vector<uint32_t> want(features, features + n_features);
+            std::sort(want.begin(), want.end());
+            for (size_t i = 0; i < want.size(); i++) {
+                const auto it = std::lower_bound(feats.begin(), feats.end(), want[i]);
+                if (it == feats.end() || *it != want[i] || (i > 0 && want[i] == want[i - 1]))
+                    fr::fail_str("fr_debug_hist_tree_sampled: feature " + std::to_string(want[i]) + " is not in the view, or is named twice");
+                sel.push_back((uint32_t)(it - feats.begin()));
+            }
+        }
+        // the caller's values go to the device as they are, also outside the query sample: the grower must not read those
+        std::vector<double> lam(ids.size(), 0.0), wt(ids.size(), 0.0);
+        size_t g = 0;
+        for (size_t q = 0; q < csr.nq; q++) {
+            for (size_t j = csr.qoff[q]; j < csr.qoff[q + 1]; j++, g++) {
+                if (ids[g] >= len) {
+                    if (queries && !flags[q]) continue;
+                    fr::fail_str("fr_debug_hist_tree_sampled: the gradient arrays are shorter than the largest sampled instance id");
+                }
+                lam[g] = lambda[ids[g]];
+                wt[g] = weight[ids[g]];
+            }
+        }
+        fr::HistGrower grower(view.device(), feats, split_candidates, max_depth, min_leaf_support);
+        grower.prepare(positions);
+        struct Unsample {  // (the bins stay with the view: leave them without a sample, also when growing fails)
+            fr::HistGrower& g;
+            ~Unsample() {
+                try {
+                    g.set_sample(nullptr, 0, nullptr);
+                } catch (...) {
+                }
+            }
+        } unsample{grower};
+        grower.set_sample(queries ? flags.data() : nullptr, (uint32_t)n_t, features ? &sel : nullptr);
         auto* out = new CModel();
         try {
             out->actual.kind = fr::Model::DecisionTree;

@@ -299,11 +299,15 @@ class DeviceDataset {
     // --- LambdaMART gradients (kernels_lambda.inc) ------------------------------------------------
     // One gradient pass on score slot 0: per document the LambdaRank gradient lambda and weight w (f64) and float(lambda),
     // the split target rf_begin(.., lambda_targets = true) reads.  norms[nq]: the NDCG evaluator's; depth < 0 = None.
-    bool lambda_gradients(const double* norms, int64_t depth, double sigma, std::string* err);
+    // query_flags[nq] (optional): only queries with a non-zero flag are visited (still longest first); they get the bits
+    // the full pass gives them, the values of the others are left as they were and must not be read.
+    bool lambda_gradients(const double* norms, int64_t depth, double sigma, std::string* err, const unsigned char* query_flags = nullptr);
     // the last pass's lambda / w by padded position ([np] each)
     bool lambda_download_positions(std::vector<double>* lambda, std::vector<double>* weight, std::string* err);
     // ... scattered to original instance ids (ids outside this dataset or >= out_len are left untouched)
-    bool lambda_download(double* lambda_by_instance, double* weight_by_instance, size_t out_len, std::string* err);
+    // (with query_flags: the instances of unflagged queries as well)
+    bool lambda_download(double* lambda_by_instance, double* weight_by_instance, size_t out_len, std::string* err,
+                         const unsigned char* query_flags = nullptr);
 
     // --- LambdaMART histogram grower (kernels_hist.inc) ----------------------
     // The host (lambdamart_hist.hpp) keeps the tree and decides; the device keeps the bin matrix, the fixed-point gradients,
@@ -318,10 +322,16 @@ class DeviceDataset {
     // edges[slot * 256 + j], j < nedges[slot]
     bool hist_edges(std::vector<float>* edges, std::vector<uint32_t>* nedges, std::string* err);
     bool hist_download_bins(uint8_t* out /*[features][n]*/, size_t len, std::string* err);
+    // The sample of the trees grown from now on, until hist_bins is called again.  query_flags[nq] (nullptr: every query):
+    // the root's index list becomes the ascending list of the instance-list indices whose query is flagged, made on the
+    // device; n_t must be their number.  fsel[f_t] (nullptr: every feature): ascending slots of the bin matrix; a level's
+    // histograms are then [slot][f_t][bin] and HistBest is indexed by these f_t features.  HistSplit::fslot stays a slot of
+    // the bin matrix.  Bins and edges are never rebuilt.
+    bool hist_sample(const unsigned char* query_flags, uint32_t n_t, const uint32_t* fsel, size_t f_t, std::string* err);
     // Q / W of the tree to grow, from the last gradient pass (lam_list == nullptr) or from host arrays in instance-list
     // order.  *all_zero: every lambda is 0 (nothing was quantised); s_l / s_w: the exponents S of the definition
     bool hist_quantise(const double* lam_list, const double* wt_list, int* s_l, int* s_w, bool* all_zero, std::string* err);
-    bool hist_root(std::string* err);  // index list = 0..n-1; the level holds the root's histogram in slot 0
+    bool hist_root(std::string* err);  // index list = 0..n-1 (the sample's root list); the level holds the root's histogram in slot 0
     // best[a * features + slot]: node a's last-maximum candidate of that feature (valid = 0: none)
     bool hist_search(const std::vector<HistNode>& nodes, uint32_t min_leaf, std::vector<HistBest>* best, std::string* err);
     // stable partition of the splitting nodes' stretches, then the next level (next_slots histograms; 0: none): `builds` are

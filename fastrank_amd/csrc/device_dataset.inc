@@ -278,12 +278,20 @@ struct DeviceDataset::Impl {
         DevBuf<float> target;               // [np] float(lam): the trees' split targets
         DevBuf<unsigned char> slab;         // staging for queries too long for LDS
         uint32_t n_lds = 0, max_len = 0;    // queries (qorder[n_lds..] are staged in the slab) / the longest one
+        std::vector<uint32_t> order_h, qsel_h;  // host copy of qorder / a sampled pass's queries, in qorder's order
+        DevBuf<uint32_t> qsel;                  // [nq] qsel_h on the device
     } lm;
     bool lm_build(std::string* err);
     // LambdaMART histogram grower (kernels_hist.inc).  The bin matrix is kept for as long as the instance list, the features
     // and k stay the same (across trees and across trainings); everything else is scratch of the tree being grown.
     struct HistState {
         uint32_t k = 0, n = 0, F = 0;
+        // the sample of the tree being grown (hist_sample): nt of the n instance-list entries (root: their ascending list,
+        // read when q_sampled) and Ft of the F feature slots (fsel, read when f_sampled).  Without a sample nt = n, Ft = F.
+        uint32_t nt = 0, Ft = 0;
+        bool q_sampled = false, f_sampled = false, qof_built = false, qof_ok = false;
+        DevBuf<uint32_t> qof, root, fsel, total;  // qof[n]: the query of every instance-list entry (hist_qof: once per bin matrix)
+        DevBuf<uint8_t> qflag;                     // [nq]
         std::vector<uint32_t> feats, pos_host;
         std::vector<float> edges_host;      // [F][HIST_MAX_BINS]
         std::vector<uint32_t> nedges_host;  // [F]
@@ -307,6 +315,8 @@ struct DeviceDataset::Impl {
         std::vector<HistSubDev> subs_h;
     } hist;
     bool hist_items(const std::vector<HistItemDev>& stretches, std::vector<HistItemDev>& host, DevBuf<HistItemDev>& dev, std::string* err);
+    bool hist_qof(std::string* err);
+    void hist_build(uint32_t* cnt, unsigned long long* sum);  // hist_build_kernel over hist.items_b into a level's histograms
     DevBuf<uint64_t> forest;
     DevBuf<uint32_t> tree_fdesc;  // tree_ensemble_rank_kernel: per-feature descriptors, Eytzinger threshold tables
     DevBuf<float> tree_tables;
@@ -3792,12 +3802,13 @@ bool DeviceDataset::Impl::lm_build(std::string* err) {
     FR_HIP(hipMemsetAsync(lm.target.p, 0, np * sizeof(float), stream));
     lm.n_lds = (uint32_t)nq - n_long;
     lm.max_len = maxl;
+    lm.order_h = order;
     if (n_long && !lm.slab.ensure((size_t)LM_SLAB_BLOCKS * maxl * LM_STAGE_BYTES, err)) return false;
     lm.built = true;
     return true;
 }
 
-bool DeviceDataset::lambda_gradients(const double* norms, int64_t depth, double sigma, std::string* err) {
+bool DeviceDataset::lambda_gradients(const double* norms, int64_t depth, double sigma, std::string* err, const unsigned char* query_flags) {
     Impl& m = *impl_;
     std::lock_guard<std::mutex> lk(m.mu);
     if (!m.bind(err)) return false;
@@ -3808,19 +3819,36 @@ bool DeviceDataset::lambda_gradients(const double* norms, int64_t depth, double 
     if (!m.lm_build(err)) return false;
     if (!m.norms.ensure(m.nq, err) || !m.upload_norms(norms, err)) return false;
     auto& lm = m.lm;
-    const uint32_t n_long = (uint32_t)m.nq - lm.n_lds;
+    uint32_t n_long = (uint32_t)m.nq - lm.n_lds, n_lds = lm.n_lds;
+    const uint32_t* qorder = lm.qorder.p;
+    size_t longest = n_long < m.nq ? std::min<size_t>(lm.max_len, LM_LDS_MAX / LM_STAGE_BYTES) : 0;
+    if (query_flags != nullptr) {  // a tree's query sample: qorder filtered, its order kept (slab queries still open the pass)
+        lm.qsel_h.clear();
+        uint32_t sel_long = 0;
+        for (size_t i = 0; i < m.nq; i++) {
+            const uint32_t q = lm.order_h[i];
+            if (!query_flags[q]) continue;
+            if (i < n_long) sel_long++;
+            lm.qsel_h.push_back(q);
+        }
+        if (lm.qsel_h.empty()) return true;
+        if (!lm.qsel.ensure(m.nq, err)) return false;
+        FR_HIP(hipMemcpyAsync(lm.qsel.p, lm.qsel_h.data(), lm.qsel_h.size() * sizeof(uint32_t), hipMemcpyHostToDevice, m.stream));
+        n_long = sel_long, n_lds = (uint32_t)lm.qsel_h.size() - sel_long;
+        qorder = lm.qsel.p;
+        longest = n_lds ? m.qlen_h[lm.qsel_h[n_long]] : 0;  // (the longest sampled query that is staged in LDS)
+    }
     ProfScope ps("lambda_grad_kernel", m.stream);
     for (uint32_t q0 = 0; q0 < n_long; q0 += LM_SLAB_BLOCKS) {  // (longest first: these open the pass)
         const uint32_t cnt = std::min<uint32_t>(LM_SLAB_BLOCKS, n_long - q0);
-        lambda_grad_kernel<<<cnt, 256, 0, m.stream>>>(m.scores.p, lm.off.p, lm.pos.p, lm.qorder.p, q0, m.gain.p, m.gexp.p, m.disc.p,
+        lambda_grad_kernel<<<cnt, 256, 0, m.stream>>>(m.scores.p, lm.off.p, lm.pos.p, qorder, q0, m.gain.p, m.gexp.p, m.disc.p,
                                                      m.perm.p, m.norms.p, depth, sigma, lm.lam.p, lm.wt.p, lm.target.p, lm.slab.p,
                                                      lm.max_len);
     }
-    if (lm.n_lds != 0) {
-        const size_t longest = n_long < m.nq ? std::min<size_t>(lm.max_len, LM_LDS_MAX / LM_STAGE_BYTES) : 0;
+    if (n_lds != 0) {
         const size_t bytes = std::max<size_t>(longest * LM_STAGE_BYTES, 64);
         FR_HIP(hipFuncSetAttribute((const void*)lambda_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-        lambda_grad_kernel<<<lm.n_lds, 256, bytes, m.stream>>>(m.scores.p, lm.off.p, lm.pos.p, lm.qorder.p, n_long, m.gain.p, m.gexp.p,
+        lambda_grad_kernel<<<n_lds, 256, bytes, m.stream>>>(m.scores.p, lm.off.p, lm.pos.p, qorder, n_long, m.gain.p, m.gexp.p,
                                                               m.disc.p, m.perm.p, m.norms.p, depth, sigma, lm.lam.p, lm.wt.p,
                                                               lm.target.p, nullptr, 0u);
     }
@@ -3844,13 +3872,16 @@ bool DeviceDataset::lambda_download_positions(std::vector<double>* lambda, std::
     return true;
 }
 
-bool DeviceDataset::lambda_download(double* lambda_by_instance, double* weight_by_instance, size_t out_len, std::string* err) {
+bool DeviceDataset::lambda_download(double* lambda_by_instance, double* weight_by_instance, size_t out_len, std::string* err,
+                                    const unsigned char* query_flags) {
     std::vector<double> lam, wt;
     if (!lambda_download_positions(&lam, &wt, err)) return false;
     Impl& m = *impl_;
     std::vector<char> in_query(m.np, 0);
-    for (size_t q = 0; q < m.nq; q++)
+    for (size_t q = 0; q < m.nq; q++) {
+        if (query_flags != nullptr && !query_flags[q]) continue;
         for (uint32_t k = 0; k < m.qlen_h[q]; k++) in_query[m.qstart_h[q] + k] = 1;
+    }
     for (size_t p = 0; p < m.np; p++) {
         const uint32_t id = m.perm_host[p];
         if (!in_query[p] || id == IDX_INVALID || id >= out_len) continue;
@@ -3880,7 +3911,10 @@ bool DeviceDataset::hist_bins(const uint32_t* positions, size_t n, const std::ve
     if (n >= (1ull << 31)) return hist_fail(err, "more instances than the index list can hold");
     for (uint32_t f : feats)
         if (f >= m.d) return hist_fail(err, "feature id outside the dataset");
-    if (h.k == k && h.n == n && h.feats == feats && std::equal(h.pos_host.begin(), h.pos_host.end(), positions)) return true;
+    if (h.k == k && h.n == n && h.feats == feats && std::equal(h.pos_host.begin(), h.pos_host.end(), positions)) {
+        h.nt = h.n, h.Ft = h.F, h.q_sampled = h.f_sampled = false;  // (no sample until hist_sample says so)
+        return true;
+    }
     h.k = 0;  // (nothing valid until the end of this function)
     const size_t F = feats.size();
     for (size_t i = 0; i < n; i++)
@@ -3929,8 +3963,10 @@ bool DeviceDataset::hist_bins(const uint32_t* positions, size_t n, const std::ve
     if (bad) return hist_fail(err, "a feature value is NaN; NaN has no bin (use the exact grower, or clean the data)");
     for (size_t s = 0; s < F; s++)
         if (h.nedges_host[s] >= k) return hist_fail(err, "internal error: more edges than bins");
+    h.qof_built = false;  // (made for these bins by the first query sample: hist_qof)
     h.feats = feats;
     h.n = n32, h.F = (uint32_t)F, h.k = k;
+    h.nt = n32, h.Ft = (uint32_t)F, h.q_sampled = h.f_sampled = false;
     if (built) *built = true;
     return true;
 }
@@ -3956,15 +3992,76 @@ bool DeviceDataset::hist_download_bins(uint8_t* out, size_t len, std::string* er
     return true;
 }
 
-bool DeviceDataset::hist_quantise(const double* lam_list, const double* wt_list, int* s_l, int* s_w, bool* all_zero, std::string* err) {
+// the query of every instance-list entry, for the trees' query samples: made once per bin matrix, by the first tree that
+// samples queries (4 ms of host work at the 30K shape that a request without samples does not pay)
+bool DeviceDataset::Impl::hist_qof(std::string* err) {
+    auto& h = hist;
+    if (h.qof_built) return true;
+    std::vector<uint32_t> q_of_pos(np, IDX_INVALID), qof(h.n);
+    for (size_t q = 0; q < nq; q++)
+        for (uint32_t j = 0; j < qlen_h[q]; j++) q_of_pos[qstart_h[q] + j] = (uint32_t)q;
+    h.qof_ok = true;
+    for (size_t i = 0; i < h.n; i++) {
+        qof[i] = q_of_pos[h.pos_host[i]];
+        if (qof[i] == IDX_INVALID) h.qof_ok = false, qof[i] = 0;
+    }
+    if (!upload(h.qof, qof, err)) return false;
+    h.qof_built = true;
+    return true;
+}
+
+bool DeviceDataset::hist_sample(const unsigned char* query_flags, uint32_t n_t, const uint32_t* fsel, size_t f_t, std::string* err) {
     Impl& m = *impl_;
     std::lock_guard<std::mutex> lk(m.mu);
     if (!m.bind(err)) return false;
     auto& h = m.hist;
     if (h.k == 0) return hist_fail(err, "no bins built");
     const uint32_t n = h.n;
+    h.nt = n, h.Ft = h.F, h.q_sampled = h.f_sampled = false;
+    if (fsel != nullptr) {
+        if (f_t == 0 || f_t > h.F) return hist_fail(err, "a feature sample must hold between 1 and all of the features");
+        for (size_t i = 0; i < f_t; i++)
+            if (fsel[i] >= h.F || (i > 0 && fsel[i] <= fsel[i - 1])) return hist_fail(err, "a feature sample must be ascending slots of the bin matrix");
+        if (!h.fsel.ensure(h.F, err)) return false;
+        FR_HIP(hipMemcpyAsync(h.fsel.p, fsel, f_t * sizeof(uint32_t), hipMemcpyHostToDevice, m.stream));
+    }
+    uint32_t total = n_t;
+    if (query_flags != nullptr) {
+        if (!m.hist_qof(err)) return false;
+        if (!h.qof_ok) return hist_fail(err, "an instance of the list belongs to no query of the dataset: no query sample");
+        if (n_t == 0 || n_t > n) return hist_fail(err, "a query sample must hold between 1 and all of the instances");
+        if (!h.qflag.ensure(m.nq, err) || !h.root.ensure(n, err) || !h.flag.ensure(n, err) || !h.scan.ensure(n, err) || !h.total.ensure(1, err))
+            return false;
+        FR_HIP(hipMemcpyAsync(h.qflag.p, query_flags, m.nq, hipMemcpyHostToDevice, m.stream));
+        ProfScope ps("hist_rootlist", m.stream);
+        hist_qflag_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(h.qof.p, h.qflag.p, n, h.flag.p);
+        size_t tb = 0;
+        FR_HIP(rocprim::exclusive_scan(nullptr, tb, h.flag.p, h.scan.p, 0u, (size_t)n, rocprim::plus<uint32_t>(), m.stream));
+        if (tb > h.temp.bytes()) {
+            FR_HIP(hipStreamSynchronize(m.stream));  // (no earlier user of the scratch is in flight)
+            if (!h.temp.ensure(tb, err)) return false;
+        }
+        FR_HIP(rocprim::exclusive_scan((void*)h.temp.p, tb, h.flag.p, h.scan.p, 0u, (size_t)n, rocprim::plus<uint32_t>(), m.stream));
+        hist_rootlist_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(h.flag.p, h.scan.p, n, n_t, h.root.p, h.total.p);
+        FR_HIP(hipGetLastError());
+        FR_HIP(hipMemcpyAsync(&total, h.total.p, sizeof(uint32_t), hipMemcpyDeviceToHost, m.stream));
+    }
+    FR_HIP(hipStreamSynchronize(m.stream));  // (query_flags / fsel are the caller's pageable memory)
+    if (total != n_t) return hist_fail(err, "internal error: the query sample holds " + std::to_string(total) + " instances, not " + std::to_string(n_t));
+    if (query_flags != nullptr) h.nt = n_t, h.q_sampled = true;
+    if (fsel != nullptr) h.Ft = (uint32_t)f_t, h.f_sampled = true;
+    return true;
+}
+
+bool DeviceDataset::hist_quantise(const double* lam_list, const double* wt_list, int* s_l, int* s_w, bool* all_zero, std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    if (h.k == 0) return hist_fail(err, "no bins built");
+    const uint32_t n = h.n, nt = h.nt;  // (host arrays and Q / W: the full list; the maxima, c and the quantisation: the tree's)
     const double *lam = nullptr, *wt = nullptr;
-    const uint32_t* pos = nullptr;
+    const uint32_t *pos = nullptr, *root = h.q_sampled ? h.root.p : nullptr;
     if (lam_list != nullptr) {
         if (!h.lam_in.ensure(n, err) || !h.wt_in.ensure(n, err)) return false;
         FR_HIP(hipMemcpyAsync(h.lam_in.p, lam_list, n * sizeof(double), hipMemcpyHostToDevice, m.stream));
@@ -3978,7 +4075,7 @@ bool DeviceDataset::hist_quantise(const double* lam_list, const double* wt_list,
     FR_HIP(hipMemsetAsync(h.absmax.p, 0, 2 * sizeof(unsigned long long), m.stream));
     {
         ProfScope ps("hist_absmax_kernel", m.stream);
-        hist_absmax_kernel<<<std::min<unsigned>(grid1d(n, 256).x, 1024u), 256, 0, m.stream>>>(lam, wt, pos, n, h.absmax.p);
+        hist_absmax_kernel<<<std::min<unsigned>(grid1d(nt, 256).x, 1024u), 256, 0, m.stream>>>(lam, wt, pos, root, nt, h.absmax.p);
     }
     unsigned long long bits[2] = {0, 0};
     FR_HIP(hipMemcpyAsync(bits, h.absmax.p, sizeof(bits), hipMemcpyDeviceToHost, m.stream));
@@ -3990,7 +4087,7 @@ bool DeviceDataset::hist_quantise(const double* lam_list, const double* wt_list,
     *s_l = *s_w = 0;
     if (*all_zero) return true;
     uint32_t c = 0;  // ceil(log2(n + 1)) = the bit length of n
-    for (uint32_t x = n; x != 0; x >>= 1) c++;
+    for (uint32_t x = nt; x != 0; x >>= 1) c++;
     int e = 0;
     (void)std::frexp(mx[0], &e);
     *s_l = 61 - e - (int)c;
@@ -3999,7 +4096,7 @@ bool DeviceDataset::hist_quantise(const double* lam_list, const double* wt_list,
         *s_w = 61 - e - (int)c;
     }
     ProfScope ps("hist_quant_kernel", m.stream);
-    hist_quant_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(lam, wt, pos, n, *s_l, *s_w, mx[1] == 0.0 ? 1 : 0, h.Q.p, h.W.p);
+    hist_quant_kernel<<<grid1d(nt, 256), 256, 0, m.stream>>>(lam, wt, pos, root, nt, *s_l, *s_w, mx[1] == 0.0 ? 1 : 0, h.Q.p, h.W.p);
     FR_HIP(hipGetLastError());
     return true;
 }
@@ -4014,6 +4111,17 @@ bool DeviceDataset::Impl::hist_items(const std::vector<HistItemDev>& stretches, 
     if (!dev.ensure(host.size(), err)) return false;
     FR_HIP(hipMemcpyAsync(dev.p, host.data(), host.size() * sizeof(HistItemDev), hipMemcpyHostToDevice, stream));
     return true;
+}
+
+void DeviceDataset::Impl::hist_build(uint32_t* cnt, unsigned long long* sum) {
+    auto& h = hist;
+    ProfScope ps("hist_build_kernel", stream);
+    const dim3 grid((unsigned)h.items_bh.size(), (h.Ft + HIST_FB - 1) / HIST_FB);
+    const size_t lds = (size_t)HIST_FB * h.k * 12;
+    if (h.f_sampled)
+        hist_build_kernel<true><<<grid, 256, lds, stream>>>(h.items_b.p, h.xbin.p, h.n, h.idx.p, h.Q.p, h.fsel.p, h.Ft, h.k, cnt, sum);
+    else
+        hist_build_kernel<false><<<grid, 256, lds, stream>>>(h.items_b.p, h.xbin.p, h.n, h.idx.p, h.Q.p, nullptr, h.Ft, h.k, cnt, sum);
 }
 
 static bool hist_level_alloc(DevBuf<uint32_t>& cnt, DevBuf<unsigned long long>& sum, size_t cells, std::string* err) {
@@ -4032,18 +4140,20 @@ bool DeviceDataset::hist_root(std::string* err) {
     if (!m.bind(err)) return false;
     auto& h = m.hist;
     if (h.k == 0) return hist_fail(err, "no bins built");
-    const uint32_t n = h.n;
-    const size_t fk = (size_t)h.F * h.k;
-    if (!h.idx.ensure(n, err) || !h.idx_o.ensure(n, err) || !h.flag.ensure(n, err) || !h.scan.ensure(n, err)) return false;
+    const uint32_t n = h.nt;  // the tree's instances: the index list's length (the bin matrix's rows hold h.n)
+    const size_t fk = (size_t)h.Ft * h.k;
+    if (!h.idx.ensure(h.n, err) || !h.idx_o.ensure(h.n, err) || !h.flag.ensure(h.n, err) || !h.scan.ensure(h.n, err)) return false;
     if (!hist_level_alloc(h.cnt, h.sum, fk, err)) return false;
     FR_HIP(hipMemsetAsync(h.flag.p, 0, n * sizeof(uint32_t), m.stream));
     FR_HIP(hipMemsetAsync(h.cnt.p, 0, fk * sizeof(uint32_t), m.stream));
     FR_HIP(hipMemsetAsync(h.sum.p, 0, fk * sizeof(unsigned long long), m.stream));
-    hist_iota_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(h.idx.p, n);
+    if (h.q_sampled) {
+        FR_HIP(hipMemcpyAsync(h.idx.p, h.root.p, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, m.stream));
+    } else {
+        hist_iota_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(h.idx.p, n);
+    }
     if (!m.hist_items({{0u, 0u, n}}, h.items_bh, h.items_b, err)) return false;
-    ProfScope ps("hist_build_kernel", m.stream);
-    hist_build_kernel<<<dim3((unsigned)h.items_bh.size(), (h.F + HIST_FB - 1) / HIST_FB), 256, (size_t)HIST_FB * h.k * 12, m.stream>>>(
-        h.items_b.p, h.xbin.p, n, h.idx.p, h.Q.p, h.F, h.k, h.cnt.p, h.sum.p);
+    m.hist_build(h.cnt.p, h.sum.p);
     FR_HIP(hipGetLastError());
     return true;
 }
@@ -4055,23 +4165,24 @@ bool DeviceDataset::hist_search(const std::vector<HistNode>& nodes, uint32_t min
     if (!m.bind(err)) return false;
     auto& h = m.hist;
     const size_t A = nodes.size();
-    best->assign(A * h.F, HistBest{});
+    best->assign(A * h.Ft, HistBest{});
     if (A == 0) return true;
-    const size_t fk = (size_t)h.F * h.k;
+    const size_t fk = (size_t)h.Ft * h.k;
     h.nodes_h.resize(A);
     for (size_t a = 0; a < A; a++) {
-        if ((size_t)(nodes[a].slot + 1) * fk > h.cnt.cap || nodes[a].end > h.n || nodes[a].begin > nodes[a].end)
+        if ((size_t)(nodes[a].slot + 1) * fk > h.cnt.cap || nodes[a].end > h.nt || nodes[a].begin > nodes[a].end)
             return hist_fail(err, "internal error: a node outside the level's histograms");
         h.nodes_h[a] = {nodes[a].slot, nodes[a].begin, nodes[a].end};
     }
-    if (!h.nodes.ensure(A, err) || !h.best.ensure(A * h.F, err)) return false;
+    if (!h.nodes.ensure(A, err) || !h.best.ensure(A * h.Ft, err)) return false;
     FR_HIP(hipMemcpyAsync(h.nodes.p, h.nodes_h.data(), A * sizeof(HistItemDev), hipMemcpyHostToDevice, m.stream));
     {
         ProfScope ps("hist_scan_kernel", m.stream);
-        hist_scan_kernel<<<(unsigned)(A * h.F), 64, 0, m.stream>>>(h.nodes.p, h.F, h.k, h.nedges.p, h.cnt.p, h.sum.p, min_leaf, h.best.p);
+        hist_scan_kernel<<<(unsigned)(A * h.Ft), 64, 0, m.stream>>>(h.nodes.p, h.Ft, h.k, h.nedges.p, h.f_sampled ? h.fsel.p : nullptr, h.cnt.p,
+                                                                    h.sum.p, min_leaf, h.best.p);
     }
     FR_HIP(hipGetLastError());
-    FR_HIP(hipMemcpyAsync(best->data(), h.best.p, A * h.F * sizeof(HistBestDev), hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipMemcpyAsync(best->data(), h.best.p, A * h.Ft * sizeof(HistBestDev), hipMemcpyDeviceToHost, m.stream));
     FR_HIP(hipStreamSynchronize(m.stream));
     return true;
 }
@@ -4083,8 +4194,8 @@ bool DeviceDataset::hist_split(const std::vector<HistSplit>& splits, const std::
     std::lock_guard<std::mutex> lk(m.mu);
     if (!m.bind(err)) return false;
     auto& h = m.hist;
-    const uint32_t n = h.n;
-    const size_t fk = (size_t)h.F * h.k;
+    const uint32_t n = h.nt;  // the index list's length; the bin matrix's rows hold h.n entries
+    const size_t fk = (size_t)h.Ft * h.k;
     if (!splits.empty()) {
         std::vector<HistItemDev> stretches(splits.size());
         h.splits_h.resize(splits.size());
@@ -4099,7 +4210,7 @@ bool DeviceDataset::hist_split(const std::vector<HistSplit>& splits, const std::
         FR_HIP(hipMemcpyAsync(h.splits.p, h.splits_h.data(), splits.size() * sizeof(HistSplitDev), hipMemcpyHostToDevice, m.stream));
         const unsigned g = (unsigned)h.items_h.size();
         ProfScope ps("hist_partition", m.stream);
-        hist_flag_kernel<<<g, 256, 0, m.stream>>>(h.items.p, h.splits.p, h.xbin.p, n, h.idx.p, h.flag.p);
+        hist_flag_kernel<<<g, 256, 0, m.stream>>>(h.items.p, h.splits.p, h.xbin.p, h.n, h.idx.p, h.flag.p);
         size_t tb = 0;
         FR_HIP(rocprim::exclusive_scan(nullptr, tb, h.flag.p, h.scan.p, 0u, (size_t)n, rocprim::plus<uint32_t>(), m.stream));
         if (tb > h.temp.bytes()) {
@@ -4123,11 +4234,7 @@ bool DeviceDataset::hist_split(const std::vector<HistSplit>& splits, const std::
         stretches[i] = {builds[i].slot, builds[i].begin, builds[i].end};
     }
     if (!m.hist_items(stretches, h.items_bh, h.items_b, err)) return false;
-    if (!h.items_bh.empty()) {
-        ProfScope ps("hist_build_kernel", m.stream);
-        hist_build_kernel<<<dim3((unsigned)h.items_bh.size(), (h.F + HIST_FB - 1) / HIST_FB), 256, (size_t)HIST_FB * h.k * 12, m.stream>>>(
-            h.items_b.p, h.xbin.p, n, h.idx.p, h.Q.p, h.F, h.k, h.cnt_o.p, h.sum_o.p);
-    }
+    if (!h.items_bh.empty()) m.hist_build(h.cnt_o.p, h.sum_o.p);
     if (!subs.empty()) {
         h.subs_h.resize(subs.size());
         for (size_t i = 0; i < subs.size(); i++) {
@@ -4157,7 +4264,7 @@ bool DeviceDataset::hist_leaf_sums(const std::vector<HistNode>& leaves, std::vec
     if (L == 0) return true;
     std::vector<HistItemDev> stretches(L);
     for (size_t i = 0; i < L; i++) {
-        if (leaves[i].end > h.n || leaves[i].begin > leaves[i].end) return hist_fail(err, "internal error: a leaf outside the index list");
+        if (leaves[i].end > h.nt || leaves[i].begin > leaves[i].end) return hist_fail(err, "internal error: a leaf outside the index list");
         stretches[i] = {(uint32_t)i, leaves[i].begin, leaves[i].end};
     }
     FR_HIP(hipStreamSynchronize(m.stream));  // (hist.items is about to be rewritten)

@@ -91,6 +91,15 @@ inline void shuffle(std::vector<T>& v, Rand64& rand) {
     }
 }
 
+// sampling.rs:49-50: how many of `len` items a sampling rate keeps: max(1, (len as f64 * rate) as usize), at most len.
+// Rust's cast saturates (NaN / negative -> 0); a C++ cast of such a value is undefined behaviour.  Shared by the
+// random-forest trainer and LambdaMART's per-tree samples.
+inline size_t sample_count(size_t len, double rate) {
+    const double x = (double)len * rate;
+    const size_t c = (x != x || x <= 0.0) ? 0 : (x >= (double)len ? len : (size_t)x);
+    return std::min(len, std::max<size_t>(1, c));
+}
+
 // ---------------------------------------------------------------------------------------------
 // Models (src/model.rs:10-112) and their serde wire form
 // ---------------------------------------------------------------------------------------------

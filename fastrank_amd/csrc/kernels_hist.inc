@@ -10,7 +10,9 @@
 //   hist_edges_kernel     the feature's at most k - 1 edges: every distinct value but the largest when there are at most k,
 //                         else sorted[(j n + k - 1) / k - 1], j = 1..k-1, duplicates and the maximum dropped
 //   hist_bin_kernel       bin(x) = number of edges strictly below x, so bins 0..j hold exactly x <= edge_j
-//   hist_absmax_kernel    max |lambda|, max |w| over the instance list (bit patterns of non-negative doubles order like them)
+//   hist_qflag_kernel / (rocPRIM exclusive scan) / hist_rootlist_kernel
+//                         a tree's query sample: the ascending list of the instance-list indices whose query is flagged
+//   hist_absmax_kernel    max |lambda|, max |w| over the tree's instance list (bit patterns of non-negative doubles order like them)
 //   hist_quant_kernel     Q = (int64) rint(ldexp(lambda, S)), W likewise
 //   hist_build_kernel     one workgroup per (stretch of a node's index list, block of HIST_FB features)
 //   hist_sub_kernel       sibling = parent - child
@@ -18,6 +20,7 @@
 //   hist_flag_kernel / (rocPRIM exclusive scan) / hist_scatter_kernel / hist_copy_kernel
 //                         stable partition of every splitting node's stretch of the index list
 //   hist_leafsum_kernel   sum Q, sum W of every leaf's stretch
+// A tree's feature sample is a table fsel[F_t] of rows of the bin matrix: histograms are [slot][F_t][k] then (nullptr: all rows).
 
 constexpr uint32_t HIST_MAX_BINS = 256;  // bins are one byte
 constexpr uint32_t HIST_FB = 8;          // features per workgroup of hist_build_kernel: 8 x 256 bins x 12 B = 24 KiB of LDS, six workgroups per CU
@@ -117,13 +120,30 @@ __global__ __launch_bounds__(256) void hist_bin_kernel(const float* __restrict__
     out[i] = (uint8_t)lo;
 }
 
-// pos == nullptr: lam / wt are already in instance-list order
+// flag[i] = 1 when the query of instance-list entry i is in the tree's sample (qof[i] < nq by construction)
+__global__ __launch_bounds__(256) void hist_qflag_kernel(const uint32_t* __restrict__ qof, const uint8_t* __restrict__ qflag, uint32_t n,
+                                                         uint32_t* __restrict__ flag) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) flag[i] = qflag[qof[i]] ? 1u : 0u;
+}
+
+// scan = exclusive prefix sums of flag: root[scan[i]] = i for every flagged i (nt: the length the host expects)
+__global__ __launch_bounds__(256) void hist_rootlist_kernel(const uint32_t* __restrict__ flag, const uint32_t* __restrict__ scan, uint32_t n,
+                                                            uint32_t nt, uint32_t* __restrict__ root, uint32_t* __restrict__ total) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (flag[i] && scan[i] < nt) root[scan[i]] = i;
+    if (i == n - 1) *total = scan[i] + flag[i];
+}
+
+// root == nullptr: the tree's instance list is the whole one; pos == nullptr: lam / wt are already in instance-list order
 __global__ __launch_bounds__(256) void hist_absmax_kernel(const double* __restrict__ lam, const double* __restrict__ wt,
-                                                          const uint32_t* __restrict__ pos, uint32_t n,
+                                                          const uint32_t* __restrict__ pos, const uint32_t* __restrict__ root, uint32_t n,
                                                           unsigned long long* __restrict__ out /*[2]*/) {
     unsigned long long ml = 0, mw = 0;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const uint32_t p = pos ? pos[i] : i;
+        const uint32_t r = root ? root[i] : i;
+        const uint32_t p = pos ? pos[r] : r;
         ml = max(ml, (unsigned long long)__double_as_longlong(fabs(lam[p])));
         mw = max(mw, (unsigned long long)__double_as_longlong(fabs(wt[p])));
     }
@@ -138,13 +158,15 @@ __global__ __launch_bounds__(256) void hist_absmax_kernel(const double* __restri
 }
 
 __global__ __launch_bounds__(256) void hist_quant_kernel(const double* __restrict__ lam, const double* __restrict__ wt,
-                                                         const uint32_t* __restrict__ pos, uint32_t n, int s_l, int s_w, int w_zero,
-                                                         long long* __restrict__ Q, long long* __restrict__ W) {
+                                                         const uint32_t* __restrict__ pos, const uint32_t* __restrict__ root, uint32_t n,
+                                                         int s_l, int s_w, int w_zero, long long* __restrict__ Q,
+                                                         long long* __restrict__ W) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const uint32_t p = pos ? pos[i] : i;
-    Q[i] = (long long)rint(ldexp(lam[p], s_l));
-    W[i] = w_zero ? 0ll : (long long)rint(ldexp(wt[p], s_w));
+    const uint32_t r = root ? root[i] : i;  // Q / W stay indexed by the full list's index: the build kernel reads Q[idx[i]]
+    const uint32_t p = pos ? pos[r] : r;
+    Q[r] = (long long)rint(ldexp(lam[p], s_l));
+    W[r] = w_zero ? 0ll : (long long)rint(ldexp(wt[p], s_w));
 }
 
 __global__ __launch_bounds__(256) void hist_iota_kernel(uint32_t* __restrict__ idx, uint32_t n) {
@@ -152,11 +174,13 @@ __global__ __launch_bounds__(256) void hist_iota_kernel(uint32_t* __restrict__ i
     if (i < n) idx[i] = i;
 }
 
-// grid (items, feature blocks).  cnt / sum: [slot][F][k]
+// grid (items, feature blocks).  cnt / sum: [slot][F][k]; n: the bin matrix's row length.  SEL: feature u of the F is row
+// fsel[u] of the bin matrix (a tree's feature sample), else row u
+template <bool SEL>
 __global__ __launch_bounds__(256) void hist_build_kernel(const HistItemDev* __restrict__ items, const uint8_t* __restrict__ xbin,
                                                          uint32_t n, const uint32_t* __restrict__ idx, const long long* __restrict__ Q,
-                                                         uint32_t F, uint32_t k, uint32_t* __restrict__ cnt,
-                                                         unsigned long long* __restrict__ sum) {
+                                                         const uint32_t* __restrict__ fsel, uint32_t F, uint32_t k,
+                                                         uint32_t* __restrict__ cnt, unsigned long long* __restrict__ sum) {
     extern __shared__ unsigned long long hist_lds[];
     const HistItemDev it = items[blockIdx.x];
     const uint32_t f0 = blockIdx.y * HIST_FB, nf = min(HIST_FB, F - f0);
@@ -168,13 +192,16 @@ __global__ __launch_bounds__(256) void hist_build_kernel(const HistItemDev* __re
     }
     __syncthreads();
     const uint8_t* xb0 = xbin + (size_t)f0 * n;
+    const uint8_t* row[HIST_FB];  // (uniform: the block's rows of the bin matrix)
+#pragma unroll
+    for (uint32_t u = 0; u < HIST_FB; u++) row[u] = SEL ? xbin + (size_t)fsel[f0 + min(u, nf - 1)] * n : xb0 + (size_t)u * n;
     for (uint32_t i = it.begin + threadIdx.x; i < it.end; i += blockDim.x) {
         const uint32_t r = idx[i];
         const unsigned long long q = (unsigned long long)Q[r];
         if (nf == HIST_FB) {
             uint32_t b[HIST_FB];
 #pragma unroll
-            for (uint32_t u = 0; u < HIST_FB; u++) b[u] = xb0[(size_t)u * n + r];
+            for (uint32_t u = 0; u < HIST_FB; u++) b[u] = SEL ? row[u][r] : xb0[(size_t)u * n + r];
 #pragma unroll
             for (uint32_t u = 0; u < HIST_FB; u++) {
                 atomicAdd(&lq[u * k + b[u]], q);
@@ -182,7 +209,7 @@ __global__ __launch_bounds__(256) void hist_build_kernel(const HistItemDev* __re
             }
         } else {
             for (uint32_t u = 0; u < nf; u++) {
-                const uint32_t b = xb0[(size_t)u * n + r];
+                const uint32_t b = SEL ? xbin[(size_t)fsel[f0 + u] * n + r] : xb0[(size_t)u * n + r];
                 atomicAdd(&lq[u * k + b], q);
                 atomicAdd(&lc[u * k + b], 1u);
             }
@@ -210,15 +237,16 @@ __global__ __launch_bounds__(256) void hist_sub_kernel(const HistSubDev* __restr
     sum[l] = psum[p] - sum[s];
 }
 
-// one wave per (node, feature); nodes[a] = {slot, begin, end} of the a-th open node; best[a * F + f]
+// one wave per (node, feature); nodes[a] = {slot, begin, end} of the a-th open node; best[a * F + f]; fsel: as above
 __global__ __launch_bounds__(64) void hist_scan_kernel(const HistItemDev* __restrict__ nodes, uint32_t F, uint32_t k,
-                                                       const uint32_t* __restrict__ nedges, const uint32_t* __restrict__ cnt,
+                                                       const uint32_t* __restrict__ nedges, const uint32_t* __restrict__ fsel,
+                                                       const uint32_t* __restrict__ cnt,
                                                        const unsigned long long* __restrict__ sum, uint32_t min_leaf,
                                                        HistBestDev* __restrict__ best) {
     const uint32_t a = blockIdx.x / F, f = blockIdx.x % F, lane = threadIdx.x;
     const HistItemDev nd = nodes[a];
     const uint32_t n = nd.end - nd.begin;
-    const uint32_t ne = min(nedges[f], k - 1);
+    const uint32_t ne = min(nedges[fsel ? fsel[f] : f], k - 1);
     const size_t base = ((size_t)nd.slot * F + f) * k;
     const uint32_t B = (k + 63) / 64;  // bins per lane (<= 4)
     uint32_t c[4];

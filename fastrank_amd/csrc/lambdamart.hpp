@@ -12,6 +12,9 @@
 //   update    s_p = s_p + learning_rate * tree(x_p) (unfused: ensemble_accumulate), the WeightedEnsemble recurrence, so
 //             the running scores are what predicting with the model so far gives, bit for bit.
 // The instance list is the RF trainer's: queries in the view's order, instance ids ascending inside a query.
+// query_sampling_rate / feature_sampling_rate < 1 ("Sampling"): gradient, grow and leaves of a tree
+// cover a fresh sample of the queries (a subsequence of the instance list) and of the features, drawn from `seed`; update
+// and training measure still cover every document.
 #pragma once
 #include <chrono>
 #include <cmath>
@@ -31,7 +34,12 @@ struct LambdaMARTParams {
     double sigma = 1.0;
     bool quiet = false;
     bool histogram = false;  // wire key "grower": "exact" (the default, not written) or "histogram"
+    // per-tree samples (optional keys, not written at their defaults): the share of the view's queries a tree is fitted to,
+    // the share of the view's features it may split on, the master seed of the samples
+    double query_sampling_rate = 1.0, feature_sampling_rate = 1.0;
+    uint64_t seed = 0;
 
+    bool sampling() const { return query_sampling_rate < 1.0 || feature_sampling_rate < 1.0; }
     [[noreturn]] static void invalid(const std::string& what) {
         fail_raw("Error(\"invalid value: " + what + "\", line: 0, column: 0)");
     }
@@ -50,10 +58,17 @@ struct LambdaMARTParams {
             if (g->s != "exact" && g->s != "histogram") invalid("grower must be `exact` or `histogram`, not `" + g->s + "`");
             p.histogram = g->s == "histogram";
         }
+        if (const Value* r = v.find("query_sampling_rate")) p.query_sampling_rate = json_f64(*r, "query_sampling_rate");
+        if (const Value* r = v.find("feature_sampling_rate")) p.feature_sampling_rate = json_f64(*r, "feature_sampling_rate");
+        if (const Value* r = v.find("seed")) p.seed = json_u64(*r, "seed");
         if (p.num_trees < 1) invalid("num_trees must be at least 1");
         if (!(std::isfinite(p.learning_rate) && p.learning_rate > 0.0)) invalid("learning_rate must be finite and greater than 0");
         if (p.max_depth < 1) invalid("max_depth must be at least 1");
         if (!(std::isfinite(p.sigma) && p.sigma > 0.0)) invalid("sigma must be finite and greater than 0");
+        if (!(p.query_sampling_rate > 0.0 && p.query_sampling_rate <= 1.0))
+            invalid("query_sampling_rate must be greater than 0 and at most 1");
+        if (!(p.feature_sampling_rate > 0.0 && p.feature_sampling_rate <= 1.0))
+            invalid("feature_sampling_rate must be greater than 0 and at most 1");
         if (p.histogram && (p.split_candidates < 2 || p.split_candidates > 256))
             invalid("split_candidates must be between 2 and 256 for the histogram grower (bins are one byte)");
         return p;
@@ -68,6 +83,9 @@ struct LambdaMARTParams {
         o.set("sigma", Value::number(sigma));
         o.set("quiet", Value::boolean(quiet));
         if (histogram) o.set("grower", Value::string("histogram"));
+        if (query_sampling_rate != 1.0) o.set("query_sampling_rate", Value::number(query_sampling_rate));
+        if (feature_sampling_rate != 1.0) o.set("feature_sampling_rate", Value::number(feature_sampling_rate));
+        if (seed != 0) o.set("seed", Value::uint(seed));
         return o;
     }
 };
@@ -92,6 +110,28 @@ inline std::vector<uint32_t> lambdamart_instance_list(const frdev::HostCSR& csr)
     return ids;
 }
 
+// A tree's sample ("Sampling"): indices into the view's ascending feature list and into the view's
+// queries, both ascending.  The master generator Rand64(seed) gives every tree two seeds in order, fseed_t then qseed_t;
+// a list is shuffle(0..len-1) under its own Rand64, the first sample_count(len, rate) entries, sorted.  A rate of 1.0 skips
+// the shuffle (the full list) but not the seed.
+struct LambdaSample {
+    std::vector<uint32_t> features, queries;
+};
+inline std::vector<uint32_t> lambdamart_sample_list(uint64_t seed, size_t len, double rate) {
+    std::vector<uint32_t> v(len);
+    for (size_t i = 0; i < len; i++) v[i] = (uint32_t)i;
+    if (rate >= 1.0) return v;
+    Rand64 local(seed);
+    shuffle(v, local);
+    v.resize(sample_count(len, rate));
+    std::sort(v.begin(), v.end());
+    return v;
+}
+inline LambdaSample lambdamart_next_sample(Rand64& master, size_t n_features, size_t n_queries, const LambdaMARTParams& p) {
+    const uint64_t fseed = master.rand_u64(), qseed = master.rand_u64();
+    return {lambdamart_sample_list(fseed, n_features, p.feature_sampling_rate), lambdamart_sample_list(qseed, n_queries, p.query_sampling_rate)};
+}
+
 struct LambdaMARTStats {
     uint32_t trees = 0;
     double seconds = 0.0;
@@ -100,6 +140,10 @@ struct LambdaMARTStats {
     bool histogram = false;
     uint32_t bins = 0;     // histogram grower: k
     double t_bins = 0.0;   // one-off binning (0 when the view's kept bins were reused, and for the exact grower)
+    // per-tree samples (reported only when a rate is below 1): the request's keys and the trees' mean sample sizes
+    bool sampling = false;
+    double query_sampling_rate = 1.0, feature_sampling_rate = 1.0;
+    uint64_t seed = 0, sum_queries = 0, sum_instances = 0, sum_features = 0;
 
     Value to_json() const {
         Value o = Value::object();
@@ -112,6 +156,15 @@ struct LambdaMARTStats {
         o.set("grower", Value::string(histogram ? "histogram" : "exact"));
         o.set("bins_ms", Value::number(t_bins * 1e3));
         if (histogram) o.set("bins", Value::uint(bins));
+        if (sampling) {
+            const double T = trees ? (double)trees : 1.0;
+            o.set("query_sampling_rate", Value::number(query_sampling_rate));
+            o.set("feature_sampling_rate", Value::number(feature_sampling_rate));
+            o.set("seed", Value::uint(seed));
+            o.set("sample_queries", Value::number((double)sum_queries / T));
+            o.set("sample_instances", Value::number((double)sum_instances / T));
+            o.set("sample_features", Value::number((double)sum_features / T));
+        }
         Value a = Value::array();
         for (double x : train_measure) a.push(Value::number(x));
         o.set("train_measure", std::move(a));
@@ -180,14 +233,54 @@ class LambdaMARTTrainer {
         if (!dev.ensemble_begin(&err) || !dev.ensemble_finish(&err)) fail_str(err);
         if (!p_.quiet) printf("-----------------------\n|%7s|%15s|\n-----------------------\n", "Tree", ev_.name.c_str());
         std::vector<double> lam, wt, leaf_of(max_id + 1, 0.0);
+        // per-tree samples: with both rates at 1.0 nothing below differs from a request without the keys
+        const bool sampling = p_.sampling(), sample_q = p_.query_sampling_rate < 1.0, sample_f = p_.feature_sampling_rate < 1.0;
+        stats_.sampling = sampling;
+        stats_.query_sampling_rate = p_.query_sampling_rate, stats_.feature_sampling_rate = p_.feature_sampling_rate, stats_.seed = p_.seed;
+        Rand64 master(p_.seed);
+        std::vector<unsigned char> qflags;
+        std::vector<uint32_t> t_ids, t_pos, t_feats, t_off;
+        uint32_t t_n = 0;  // the tree's number of instances
         for (uint32_t t = 0; t < p_.num_trees; t++) {
+            auto ts = tnow();  // (drawing the sample and handing it to the grower count as grow time)
+            LambdaSample smp;
+            // the tree's instance list (a subsequence of the full one), feature list and positions
+            const std::vector<uint32_t>*ids_t = &root_ids, *feats_t = &feats, *off_t = &root_off;
+            const uint32_t* pos_t = positions.data();
+            if (sampling) {
+                smp = lambdamart_next_sample(master, feats.size(), csr.nq, p_);
+                size_t n_t = root_ids.size();
+                if (sample_q) {
+                    qflags.assign(csr.nq, 0);
+                    n_t = 0;
+                    for (uint32_t q : smp.queries) qflags[q] = 1, n_t += csr.qoff[q + 1] - csr.qoff[q];
+                }
+                if (sample_f) {
+                    t_feats.clear();
+                    for (uint32_t s : smp.features) t_feats.push_back(feats[s]);
+                    feats_t = &t_feats;
+                }
+                if (sample_q && !hist) {  // (the histogram grower makes its root list on the device from the flags)
+                    t_ids.clear(), t_pos.clear();
+                    for (uint32_t q : smp.queries) {
+                        const size_t b = csr.qoff[q] - csr.qoff[0], e = csr.qoff[q + 1] - csr.qoff[0];
+                        t_ids.insert(t_ids.end(), root_ids.begin() + b, root_ids.begin() + e);
+                        t_pos.insert(t_pos.end(), positions.begin() + b, positions.begin() + e);
+                    }
+                    t_off = {0u, (uint32_t)t_ids.size()};
+                    ids_t = &t_ids, off_t = &t_off, pos_t = t_pos.data();
+                }
+                t_n = (uint32_t)n_t;
+                stats_.sum_queries += smp.queries.size(), stats_.sum_instances += n_t, stats_.sum_features += smp.features.size();
+            }
             auto ta = tnow();
-            if (!dev.lambda_gradients(ev_.norms.data(), ev_.depth, p_.sigma, &err)) fail_str(err);
+            if (!dev.lambda_gradients(ev_.norms.data(), ev_.depth, p_.sigma, &err, sample_q ? qflags.data() : nullptr)) fail_str(err);
             if (!frdev::device_synchronize(&err)) fail_str(err);
             auto tb = tnow();
+            if (sampling && hist) hist->set_sample(sample_q ? qflags.data() : nullptr, t_n, sample_f ? &smp.features : nullptr);
             double leaf_secs = 0.0;
             std::shared_ptr<TreeNode> root = hist ? hist->grow(nullptr, nullptr, &leaf_secs)
-                                                  : grower.grow_lambda_tree(dev, root_off, root_ids, feats, positions.data(), rst);
+                                                  : grower.grow_lambda_tree(dev, *off_t, *ids_t, *feats_t, pos_t, rst);
             auto tc = tnow() - std::chrono::duration_cast<std::chrono::steady_clock::duration>(std::chrono::duration<double>(leaf_secs));
             // leaves (exact grower): route every instance through a copy of the tree whose leaves hold their index
             std::vector<TreeNode*> leaves;
@@ -200,12 +293,12 @@ class LambdaMARTTrainer {
                 if (!dev.download_scores(0, leaf_of.data(), leaf_of.size(), &err)) fail_str(err);
                 if (!dev.lambda_download_positions(&lam, &wt, &err)) fail_str(err);
                 std::vector<double> sl(leaves.size(), 0.0), sw(leaves.size(), 0.0);
-                for (size_t g = 0; g < root_ids.size(); g++) {
-                    const double lv = leaf_of[root_ids[g]];
+                for (size_t g = 0; g < ids_t->size(); g++) {  // (the tree's instance list, in its order)
+                    const double lv = leaf_of[(*ids_t)[g]];
                     if (!(lv >= 0.0 && lv < (double)leaves.size())) fail_str("LambdaMART: an instance was routed to no leaf");
                     const size_t L = (size_t)lv;
-                    sl[L] = sl[L] + lam[positions[g]];
-                    sw[L] = sw[L] + wt[positions[g]];
+                    sl[L] = sl[L] + lam[pos_t[g]];
+                    sw[L] = sw[L] + wt[pos_t[g]];
                 }
                 for (size_t L = 0; L < leaves.size(); L++) leaves[L]->value = sw[L] != 0.0 ? sl[L] / sw[L] : 0.0;
             }
@@ -222,7 +315,7 @@ class LambdaMARTTrainer {
             check_flags(dev);
             auto te = tnow();
             stats_.t_gradient += secs(ta, tb);
-            stats_.t_grow += secs(tb, tc);
+            stats_.t_grow += secs(ts, ta) + secs(tb, tc);
             stats_.t_leaves += secs(tc, td);
             stats_.t_update += secs(td, te);
             stats_.train_measure.push_back(mean);

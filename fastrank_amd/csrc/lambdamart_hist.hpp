@@ -25,8 +25,23 @@ class HistGrower {
         bool built = false;
         if (!dev_.hist_bins(positions.data(), positions.size(), feats_, k_, &built, &err)) fail_str(err);
         if (!dev_.hist_edges(&edges_, &nedges_, &err)) fail_str(err);
-        n_ = (uint32_t)positions.size();
+        n_ = n_full_ = (uint32_t)positions.size();
+        sel_.clear();
         return built;
+    }
+
+    // The sample of the trees grown from now on ("Sampling").  query_flags[q] != 0: query q of the
+    // view is in the sample, n_t of the instance list's entries in all (nullptr: every query); features: ascending indices
+    // into the feature list (nullptr: every feature).  Bins and edges stay those of the full lists.
+    void set_sample(const unsigned char* query_flags, uint32_t n_t, const std::vector<uint32_t>* features) {
+        std::string err;
+        if (features) sel_ = *features;
+        else sel_.clear();
+        for (uint32_t s : sel_)
+            if (s >= feats_.size()) fail_str("LambdaMART histogram grower: a sampled feature outside the feature list");
+        if (features && sel_.empty()) fail_str("LambdaMART histogram grower: an empty feature sample");
+        if (!dev_.hist_sample(query_flags, query_flags ? n_t : n_full_, features ? sel_.data() : nullptr, sel_.size(), &err)) fail_str(err);
+        n_ = query_flags ? n_t : n_full_;
     }
 
     // One tree for the gradients of the last gradient pass (lam_list == nullptr) or for lam_list / wt_list[n] in
@@ -56,7 +71,8 @@ class HistGrower {
         } else {
             close(root.get(), 0u, n_);
         }
-        const size_t F = feats_.size();
+        const size_t F = sel_.empty() ? feats_.size() : sel_.size();  // the tree's features; slot fi of them is slot full(fi) of the bins
+        auto full = [&](size_t fi) { return sel_.empty() ? fi : (size_t)sel_[fi]; };
         std::vector<Dev::HistNode> nodes, builds;
         std::vector<Dev::HistBest> best;
         std::vector<Dev::HistSplit> splits;
@@ -80,13 +96,14 @@ class HistGrower {
                     continue;
                 }
                 const uint32_t n = o.end - o.begin, nl = w->nl, nr = n - nl;
-                if (w->edge >= nedges_[wf] || nl == 0 || nl >= n) fail_str("LambdaMART histogram grower: internal error: an impossible split");
+                const size_t ws = full(wf);
+                if (w->edge >= nedges_[ws] || nl == 0 || nl >= n) fail_str("LambdaMART histogram grower: internal error: an impossible split");
                 o.node->leaf = false;
-                o.node->fid = feats_[wf];
-                o.node->value = (double)edges_[wf * 256 + w->edge];
+                o.node->fid = feats_[ws];
+                o.node->value = (double)edges_[ws * 256 + w->edge];
                 o.node->lhs.reset(new TreeNode());
                 o.node->rhs.reset(new TreeNode());
-                splits.push_back({o.begin, o.end, (uint32_t)wf, w->edge, nl});
+                splits.push_back({o.begin, o.end, (uint32_t)ws, w->edge, nl});  // (the bin matrix's row)
                 const uint32_t mid = o.begin + nl;
                 const bool el = enterable(nl, o.depth + 1), er = enterable(nr, o.depth + 1);
                 if (!el) close(o.node->lhs.get(), o.begin, mid);
@@ -107,7 +124,7 @@ class HistGrower {
             open.swap(next);
         }
         auto t0 = std::chrono::steady_clock::now();
-        if (!rooted) {  // (the index list of a tree that never searched: the identity)
+        if (!rooted) {  // (the index list of a tree that never searched: the root's)
             if (!dev_.hist_root(&err)) fail_str(err);
         }
         std::vector<long long> qw;
@@ -126,7 +143,8 @@ class HistGrower {
 
     frdev::DeviceDataset& dev_;
     std::vector<uint32_t> feats_;
-    uint32_t k_, max_depth_, min_leaf_, n_ = 0;
+    uint32_t k_, max_depth_, min_leaf_, n_ = 0, n_full_ = 0;  // n_: the tree's instances (n_full_ of them without a query sample)
+    std::vector<uint32_t> sel_;                                // the tree's features as slots of the bins (empty: all)
     std::vector<float> edges_;
     std::vector<uint32_t> nedges_;
 };

@@ -123,13 +123,7 @@ class RFTrainer {
         std::sort(queries_.begin(), queries_.end(), [&](uint32_t a, uint32_t b) {
             return core.qnames[view_->csr_query[a]] < core.qnames[view_->csr_query[b]];
         });
-        // sampling.rs:49-50: max(1, (len as f64 * rate) as usize), then take(n) from a list of len items.  Rust's cast
-        // saturates (NaN / negative -> 0); a C++ cast of such a value is undefined behaviour
-        auto sample_count = [](size_t len, double rate) {
-            const double x = (double)len * rate;
-            const size_t c = (x != x || x <= 0.0) ? 0 : (x >= (double)len ? len : (size_t)x);
-            return std::min(len, std::max<size_t>(1, c));
-        };
+        // sampling.rs:49-50 (host.hpp: sample_count), then take(n) from a list of len items
         n_features_ = sample_count(features_.size(), p_.feature_sampling_rate);
         n_queries_ = sample_count(queries_.size(), p_.instance_sampling_rate);
         if (features_.empty()) fail_str("assertion failed: !features.is_empty()");

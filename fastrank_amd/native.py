@@ -63,15 +63,33 @@ def evaluate_dense(model: CModel, dataset: CDataset, evaluator: str, qrel: Optio
     return json.loads(_take_str(qids_ptr.value)), out
 
 
+def lambdamart_sample(dataset: CDataset, params, tree: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The sample LambdaMART's trainer uses for tree `tree` of `params` (LambdaMARTParams or its wire dict) on `dataset`:
+    (feature ids ascending, indices of the view's queries ascending).  Needs no device."""
+    wire = params if isinstance(params, dict) else params.to_dict()
+    rep = _json_reply(_load().fr_debug_lambdamart_sample(dataset.pointer, json.dumps(wire).encode("utf-8"), int(tree)))
+    return np.asarray(rep["features"], dtype=np.uint32), np.asarray(rep["queries"], dtype=np.uint32)
+
+
 def lambda_gradients(model: CModel, dataset: CDataset, measure: str = "ndcg", sigma: float = 1.0,
-                     qrel: Optional[CQRel] = None, n_total: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+                     qrel: Optional[CQRel] = None, n_total: Optional[int] = None, queries=None) -> Tuple[np.ndarray, np.ndarray]:
     """LambdaMART's gradient pass on the scores of `model`: (lambda, weight) indexed by instance id (NaN where the id is
-    not part of a sampled dataset)."""
+    not part of a sampled dataset).  `queries`: indices of the view's queries (its order) the pass visits, as for a tree's
+    query sample; the instances of the others come back NaN."""
     n = int(n_total if n_total is not None else _load().fr_dataset_num_instances(dataset.pointer))
     if n_total is None and dataset.is_sampled():
         n = 1 + max(max(ids) for ids in dataset.instances_by_query().values())
     lam = np.full(n, np.nan, dtype=np.float64)
     wt = np.full(n, np.nan, dtype=np.float64)
+    if queries is not None:
+        qs = np.ascontiguousarray(queries, dtype=np.uint32)
+        _status(
+            _load().fr_debug_lambda_gradients_sampled(
+                model.pointer, dataset.pointer, None if qrel is None else qrel.pointer, measure.encode("utf-8"), float(sigma),
+                qs.ctypes.data, len(qs), lam.ctypes.data, wt.ctypes.data, n,
+            )
+        )
+        return lam, wt
     _status(
         _load().fr_debug_lambda_gradients(
             model.pointer, dataset.pointer, None if qrel is None else qrel.pointer, measure.encode("utf-8"), float(sigma),
@@ -101,12 +119,25 @@ def hist_bins(dataset: CDataset, split_candidates: int):
 
 
 def hist_tree(dataset: CDataset, lam: np.ndarray, wt: np.ndarray, split_candidates: int, max_depth: int,
-              min_leaf_support: int) -> CModel:
-    """One tree of LambdaMART's histogram grower for the gradients lam / wt (indexed by instance id)."""
+              min_leaf_support: int, queries=None, features=None) -> CModel:
+    """One tree of LambdaMART's histogram grower for the gradients lam / wt (indexed by instance id).  `queries` (indices of
+    the view's queries) / `features` (feature ids): the tree's sample; gradients outside the query sample are not read."""
     lam = np.ascontiguousarray(lam, dtype=np.float64)
     wt = np.ascontiguousarray(wt, dtype=np.float64)
     if lam.shape != wt.shape or lam.ndim != 1:
         raise ValueError("lam and wt must be 1-d arrays of the same length")
+    if queries is not None or features is not None:
+        qs = None if queries is None else np.ascontiguousarray(queries, dtype=np.uint32)
+        fs = None if features is None else np.ascontiguousarray(features, dtype=np.uint32)
+        return CModel(
+            _unwrap(
+                _load().fr_debug_hist_tree_sampled(
+                    dataset.pointer, int(split_candidates), int(max_depth), int(min_leaf_support), lam.ctypes.data,
+                    wt.ctypes.data, lam.shape[0], None if qs is None else qs.ctypes.data, 0 if qs is None else len(qs),
+                    None if fs is None else fs.ctypes.data, 0 if fs is None else len(fs),
+                )
+            )
+        )
     return CModel(
         _unwrap(
             _load().fr_debug_hist_tree(

@@ -82,7 +82,11 @@ class LambdaMARTParams(_LearnerParams):
     """Gradient-boosted regression trees fitted to LambdaRank gradients, trained on the device (csrc/lambdamart.hpp,
     kernels_lambda.inc).  The wire form requires the first seven keys.  Measures: ndcg and ndcg@k.
     `grower`: "exact" (the default; not written to the wire form) or "histogram" (features binned once into at most
-    `split_candidates` <= 256 bins, per-node histograms: csrc/lambdamart_hist.hpp, kernels_hist.inc)."""
+    `split_candidates` <= 256 bins, per-node histograms: csrc/lambdamart_hist.hpp, kernels_hist.inc).
+    `query_sampling_rate`, `feature_sampling_rate` (0 < r <= 1, default 1.0) and `seed` (u64, default 0): every tree is
+    fitted to a fresh sample of that share of the view's queries (whole queries, never single documents) and may split on a
+    fresh sample of that share of its features; the samples are a function of `seed` alone.  Like `grower` the three keys are
+    written to the wire form only when they differ from their defaults; with both rates at 1.0 `seed` has no effect."""
 
     VARIANT: ClassVar[str] = "LambdaMART"
 
@@ -94,11 +98,17 @@ class LambdaMARTParams(_LearnerParams):
     sigma: float = 1.0
     quiet: bool = False
     grower: str = "exact"
+    query_sampling_rate: float = 1.0
+    feature_sampling_rate: float = 1.0
+    seed: int = 0
+
+    _WIRE_DEFAULTS: ClassVar[Dict[str, Any]] = {"grower": "exact", "query_sampling_rate": 1.0, "feature_sampling_rate": 1.0, "seed": 0}
 
     def to_dict(self) -> Dict[str, Any]:
         wire = dataclasses.asdict(self)
-        if wire["grower"] == "exact":  # serde: skip_serializing_if
-            del wire["grower"]
+        for key, default in self._WIRE_DEFAULTS.items():  # serde: skip_serializing_if
+            if wire[key] == default:
+                del wire[key]
         return wire
 
 

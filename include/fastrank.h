@@ -189,6 +189,21 @@ const void *fr_debug_hist_bins(const CDataset *dataset, uint32_t split_candidate
 const CResult *fr_debug_hist_tree(const CDataset *dataset, uint32_t split_candidates, uint32_t max_depth,
                                   uint32_t min_leaf_support, const double *lambda, const double *weight,
                                   size_t len);
+/* LambdaMART per-tree samples, test hooks ("Sampling").  fr_debug_lambdamart_sample: JSON
+ * {"features": [feature ids ascending], "queries": [indices of the view's queries, ascending]} the trainer uses for
+ * tree `tree` of the LambdaMART parameters params_json on this view; no device is touched.  The _sampled forms of
+ * the two hooks above take queries[n_queries] = indices of the view's queries (fr_debug_hist_tree_sampled: NULL = all)
+ * and features[n_features] = feature ids of the view (NULL = all); only instances of the named queries are written
+ * (gradients) or read (tree). */
+const void *fr_debug_lambdamart_sample(const CDataset *dataset, const void *params_json, uint32_t tree);
+const void *fr_debug_lambda_gradients_sampled(const CModel *model, const CDataset *dataset, const CQRel *qrel,
+                                              const void *measure, double sigma, const uint32_t *queries,
+                                              size_t n_queries, double *lambda_out, double *weight_out,
+                                              size_t out_len);
+const CResult *fr_debug_hist_tree_sampled(const CDataset *dataset, uint32_t split_candidates, uint32_t max_depth,
+                                          uint32_t min_leaf_support, const double *lambda, const double *weight,
+                                          size_t len, const uint32_t *queries, size_t n_queries,
+                                          const uint32_t *features, size_t n_features);
 /* Full per-query rank order under the reference's total order (src/evaluators.rs:34-49):
  * out_instance_ids[n] grouped by query (device query order), best first; out_offsets[nq+1]. */
 const void *fr_rank_order(const CModel *model, const CDataset *dataset, uint32_t *out_instance_ids,

@@ -2,6 +2,8 @@
 
     python tools/lmbench.py --shape 30k --trees 100            # the device: seconds per tree and the per-stage split
     python tools/lmbench.py --shape 30k --trees 100 --grower histogram   # the histogram grower
+    python tools/lmbench.py --shape 30k --trees 100 --grower histogram --query-sampling-rate 0.5 --feature-sampling-rate 0.5 --seed 1
+                                                               # per-tree samples of the queries and the features
     python tools/lmbench.py --shape 30k --cpu-baseline 0.01    # the numpy restatement (tests/lambdamart_model.py) timed on
                                                                # a query sample, scaled to the full shape (labelled as such)
 Every other parameter is the LambdaMART default (TrainRequest.lambdamart()).
@@ -32,6 +34,9 @@ def device_run(args, X, y, qid):
     req.params.num_trees = args.trees
     req.params.quiet = True
     req.params.grower = args.grower
+    req.params.query_sampling_rate = args.query_sampling_rate
+    req.params.feature_sampling_rate = args.feature_sampling_rate
+    req.params.seed = args.seed
     # upload and first touch of the device (not part of training)
     native.device_info(ds)
     t_ds = time.perf_counter() - t0
@@ -44,7 +49,8 @@ def device_run(args, X, y, qid):
     prof = native.profile_stats()
     native.profile_enable(False)
     T = st["trees"]
-    return {
+    sample = {k: st[k] for k in ("sample_queries", "sample_instances", "sample_features") if k in st}
+    out = {
         "metric": "LambdaMART seconds per tree (device) on MSLR-WEB30K shape" if args.shape == "30k" else "LambdaMART seconds per tree (device)",
         "shape": args.shape, "n": int(X.shape[0]), "d": int(X.shape[1]), "queries": int(len(np.unique(qid))),
         "measure": args.measure, "trees": T, "params": req.params.to_dict(),
@@ -55,6 +61,9 @@ def device_run(args, X, y, qid):
         "kernel_profile": {k: v for k, v in prof.items() if "lambda" in k or "rf_" in k or "tree" in k or "hist_" in k},
         "model_nodes": len(json.dumps(model.to_dict())),
     }
+    if sample:  # (only when a rate is below 1, like the stats object)
+        out["sample"] = sample
+    return out
 
 
 def cpu_run(args, X, y, qid):
@@ -92,6 +101,9 @@ def main():
     ap.add_argument("--trees", type=int, default=100)
     ap.add_argument("--measure", default="ndcg")
     ap.add_argument("--grower", default="exact", choices=["exact", "histogram"])
+    ap.add_argument("--query-sampling-rate", type=float, default=1.0, help="share of the queries every tree is fitted to")
+    ap.add_argument("--feature-sampling-rate", type=float, default=1.0, help="share of the features every tree may split on")
+    ap.add_argument("--seed", type=int, default=0, help="master seed of the per-tree samples")
     ap.add_argument("--cpu-baseline", type=float, default=0.0, help="query fraction for the CPU restatement (0: device run)")
     args = ap.parse_args()
     n, d, q, seed = SHAPES[args.shape]
