@@ -1374,7 +1374,8 @@ static std::vector<unsigned char> debug_query_flags(const uint32_t* queries, siz
 }
 
 // The sample LambdaMART's trainer uses for tree `tree` of the request parameters `params_json` ({"num_trees": ..}, the
-// LambdaMART variant's payload) on this view: {"features": [ids ascending], "queries": [indices in the view's order]}.
+// LambdaMART variant's payload) on this view: {"features": [ids ascending], "queries": [indices in the view's order]}; with
+// validation_queries these are the sampled TRAINING queries.
 // No device is touched.
 const void* fr_debug_lambdamart_sample(const CDataset* dataset, const void* params_json, uint32_t tree) {
     return json_call([&]() {
@@ -1385,9 +1386,10 @@ const void* fr_debug_lambdamart_sample(const CDataset* dataset, const void* para
         std::vector<uint32_t> feats = view.features;
         std::sort(feats.begin(), feats.end());
         const size_t nq = view.host_csr().nq;
+        const fr::LambdaSplit split = fr::lambdamart_split(view, p);  // (held-out queries: the sample is drawn from the others)
         fr::Rand64 master(p.seed);
         fr::LambdaSample smp;
-        for (uint32_t t = 0; t <= tree; t++) smp = fr::lambdamart_next_sample(master, feats.size(), nq, p);
+        for (uint32_t t = 0; t <= tree; t++) smp = fr::lambdamart_next_sample(master, feats.size(), nq, p, split.held.empty() ? nullptr : &split.train);
         Value o = Value::object(), f = Value::array(), q = Value::array();
         for (uint32_t s : smp.features) f.push(Value::uint(feats[s]));
         for (uint32_t x : smp.queries) q.push(Value::uint(x));

@@ -218,6 +218,13 @@ class DeviceDataset {
     // query-sharded training: every reduction over queries (reduce_means, the line searches) returns the
     // SUM over this dataset's queries, in the fixed two-level shape, instead of the mean
     void set_sums_only(bool on);
+    // Means of column 0 of the last result over two subsets of the queries (LambdaMART's training and held-out queries):
+    // subset_means_set uploads the two index lists (queries of this dataset, each ascending, both non-empty) once;
+    // reduce_subset_means then gives {mean over a, mean over b}, each in the fixed two-level shape over the subset's
+    // compacted list, with one copy back.  subset_means_end forgets the lists.
+    bool subset_means_set(const std::vector<uint32_t>& a, const std::vector<uint32_t>& b, std::string* err);
+    bool reduce_subset_means(double out_means[2], std::string* err);
+    void subset_means_end();
 
     // --- line search: every candidate of every group, means[g*64 + c] --------------------------------------
     // Bound-and-verify: candidates are decided from approximate scores with a proven error bound, what is left
@@ -301,7 +308,10 @@ class DeviceDataset {
     // the split target rf_begin(.., lambda_targets = true) reads.  norms[nq]: the NDCG evaluator's; depth < 0 = None.
     // query_flags[nq] (optional): only queries with a non-zero flag are visited (still longest first); they get the bits
     // the full pass gives them, the values of the others are left as they were and must not be read.
-    bool lambda_gradients(const double* norms, int64_t depth, double sigma, std::string* err, const unsigned char* query_flags = nullptr);
+    // flags_unchanged: query_flags are those of the previous call (a fixed training split): the filtered query list already
+    // on the device is used again, nothing is uploaded.
+    bool lambda_gradients(const double* norms, int64_t depth, double sigma, std::string* err, const unsigned char* query_flags = nullptr,
+                          bool flags_unchanged = false);
     // the last pass's lambda / w by padded position ([np] each)
     bool lambda_download_positions(std::vector<double>* lambda, std::vector<double>* weight, std::string* err);
     // ... scattered to original instance ids (ids outside this dataset or >= out_len are left untouched)
@@ -327,7 +337,10 @@ class DeviceDataset {
     // device; n_t must be their number.  fsel[f_t] (nullptr: every feature): ascending slots of the bin matrix; a level's
     // histograms are then [slot][f_t][bin] and HistBest is indexed by these f_t features.  HistSplit::fslot stays a slot of
     // the bin matrix.  Bins and edges are never rebuilt.
-    bool hist_sample(const unsigned char* query_flags, uint32_t n_t, const uint32_t* fsel, size_t f_t, std::string* err);
+    // keep_queries (with query_flags == nullptr): the query sample of the previous call stays (a fixed training split under
+    // per-tree feature samples); only the feature sample changes.
+    bool hist_sample(const unsigned char* query_flags, uint32_t n_t, const uint32_t* fsel, size_t f_t, std::string* err,
+                     bool keep_queries = false);
     // Q / W of the tree to grow, from the last gradient pass (lam_list == nullptr) or from host arrays in instance-list
     // order.  *all_zero: every lambda is 0 (nothing was quantised); s_l / s_w: the exponents S of the definition
     bool hist_quantise(const double* lam_list, const double* wt_list, int* s_l, int* s_w, bool* all_zero, std::string* err);

@@ -126,6 +126,10 @@ struct DeviceDataset::Impl {
     hipEvent_t res_ready = nullptr;  // recorded on the main stream after a resident-sum store; the contexts wait on it
     bool res_ready_set = false;
     const double* last_M = nullptr;  // device matrix of the last per-query result (download_per_query / reduce_means)
+    // reduce_subset_means: the two subsets' queries (a then b), their sizes, the segment sums and the two means
+    DevBuf<uint32_t> sub_idx;
+    DevBuf<double> sub_partial, sub_means;
+    uint32_t sub_na = 0, sub_nb = 0;
     bool ls_submit(LsCtx& c, int path, int measure, int64_t depth, const double* norms, const std::vector<LineGroup>& groups,
                    std::string* err);
     bool ls_collect(LsCtx& c, std::vector<double>* means, std::string* err);
@@ -279,6 +283,8 @@ struct DeviceDataset::Impl {
         DevBuf<unsigned char> slab;         // staging for queries too long for LDS
         uint32_t n_lds = 0, max_len = 0;    // queries (qorder[n_lds..] are staged in the slab) / the longest one
         std::vector<uint32_t> order_h, qsel_h;  // host copy of qorder / a sampled pass's queries, in qorder's order
+        uint32_t sel_long = 0;                  // ... of which the slab path takes this many
+        bool qsel_valid = false;                // qsel holds qsel_h (lambda_gradients' flags_unchanged)
         DevBuf<uint32_t> qsel;                  // [nq] qsel_h on the device
     } lm;
     bool lm_build(std::string* err);
@@ -2087,6 +2093,56 @@ bool DeviceDataset::reduce_means(size_t ncols, double* out, std::string* err) {
     FR_HIP(hipStreamSynchronize(m.stream));
     return true;
 }
+
+bool DeviceDataset::subset_means_set(const std::vector<uint32_t>& a, const std::vector<uint32_t>& b, std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    m.sub_na = m.sub_nb = 0;
+    auto bad = [&](const char* what) {
+        if (err) *err = std::string("subset_means_set: ") + what;
+        return false;
+    };
+    if (a.empty() || b.empty()) return bad("an empty subset");
+    for (const std::vector<uint32_t>* v : {&a, &b})
+        for (size_t i = 0; i < v->size(); i++)
+            if ((*v)[i] >= m.nq || (i > 0 && (*v)[i] <= (*v)[i - 1])) return bad("a subset must be ascending queries of the dataset");
+    std::vector<uint32_t> idx(a);
+    idx.insert(idx.end(), b.begin(), b.end());
+    const size_t nseg = (a.size() + MEAN_SEG - 1) / MEAN_SEG + (b.size() + MEAN_SEG - 1) / MEAN_SEG;
+    if (!m.sub_partial.ensure(nseg, err) || !m.sub_means.ensure(2, err)) return false;
+    FR_HIP(hipStreamSynchronize(m.stream));  // (no earlier reader of the list is in flight)
+    if (!upload(m.sub_idx, idx, err)) return false;
+    m.sub_na = (uint32_t)a.size(), m.sub_nb = (uint32_t)b.size();
+    return true;
+}
+
+bool DeviceDataset::reduce_subset_means(double out[2], std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    if (m.sub_na == 0 || m.sub_nb == 0 || m.last_M == nullptr || m.last_ldm == 0 || m.sums_only) {
+        if (err) *err = "reduce_subset_means: no subsets set, or no per-query result";
+        return false;
+    }
+    const uint32_t nseg_a = (m.sub_na + MEAN_SEG - 1) / MEAN_SEG, nseg_b = (m.sub_nb + MEAN_SEG - 1) / MEAN_SEG;
+    {
+        ProfScope ps("subset_mean_kernels", m.stream);
+        subset_segment_sum_kernel<<<nseg_a + nseg_b, MEAN_SEG, 0, m.stream>>>(m.last_M, (uint32_t)m.last_ldm, m.sub_idx.p, m.sub_na, m.sub_nb,
+                                                                            nseg_a, m.sub_partial.p);
+        subset_final_mean_kernel<<<1, 128, 0, m.stream>>>(m.sub_partial.p, nseg_a, nseg_b, m.sub_na, m.sub_nb, m.sub_means.p);
+    }
+    FR_HIP(hipGetLastError());
+    FR_HIP(hipMemcpyAsync(out, m.sub_means.p, 2 * sizeof(double), hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipStreamSynchronize(m.stream));
+    return true;
+}
+
+void DeviceDataset::subset_means_end() {
+    std::lock_guard<std::mutex> lk(impl_->mu);
+    impl_->sub_na = impl_->sub_nb = 0;
+}
+
 DeviceDataset::LsPath DeviceDataset::linesearch_path(int measure, int64_t depth) const {
     const Impl& m = *impl_;
     // zero-weight masking is exact only for finite features (inf * 0 = NaN)
@@ -3808,7 +3864,8 @@ bool DeviceDataset::Impl::lm_build(std::string* err) {
     return true;
 }
 
-bool DeviceDataset::lambda_gradients(const double* norms, int64_t depth, double sigma, std::string* err, const unsigned char* query_flags) {
+bool DeviceDataset::lambda_gradients(const double* norms, int64_t depth, double sigma, std::string* err, const unsigned char* query_flags,
+                                     bool flags_unchanged) {
     Impl& m = *impl_;
     std::lock_guard<std::mutex> lk(m.mu);
     if (!m.bind(err)) return false;
@@ -3823,17 +3880,22 @@ bool DeviceDataset::lambda_gradients(const double* norms, int64_t depth, double 
     const uint32_t* qorder = lm.qorder.p;
     size_t longest = n_long < m.nq ? std::min<size_t>(lm.max_len, LM_LDS_MAX / LM_STAGE_BYTES) : 0;
     if (query_flags != nullptr) {  // a tree's query sample: qorder filtered, its order kept (slab queries still open the pass)
-        lm.qsel_h.clear();
-        uint32_t sel_long = 0;
-        for (size_t i = 0; i < m.nq; i++) {
-            const uint32_t q = lm.order_h[i];
-            if (!query_flags[q]) continue;
-            if (i < n_long) sel_long++;
-            lm.qsel_h.push_back(q);
+        if (!(flags_unchanged && lm.qsel_valid)) {
+            lm.qsel_valid = false;
+            lm.qsel_h.clear();
+            lm.sel_long = 0;
+            for (size_t i = 0; i < m.nq; i++) {
+                const uint32_t q = lm.order_h[i];
+                if (!query_flags[q]) continue;
+                if (i < n_long) lm.sel_long++;
+                lm.qsel_h.push_back(q);
+            }
+            if (lm.qsel_h.empty()) return true;
+            if (!lm.qsel.ensure(m.nq, err)) return false;
+            FR_HIP(hipMemcpyAsync(lm.qsel.p, lm.qsel_h.data(), lm.qsel_h.size() * sizeof(uint32_t), hipMemcpyHostToDevice, m.stream));
+            lm.qsel_valid = true;
         }
-        if (lm.qsel_h.empty()) return true;
-        if (!lm.qsel.ensure(m.nq, err)) return false;
-        FR_HIP(hipMemcpyAsync(lm.qsel.p, lm.qsel_h.data(), lm.qsel_h.size() * sizeof(uint32_t), hipMemcpyHostToDevice, m.stream));
+        const uint32_t sel_long = lm.sel_long;
         n_long = sel_long, n_lds = (uint32_t)lm.qsel_h.size() - sel_long;
         qorder = lm.qsel.p;
         longest = n_lds ? m.qlen_h[lm.qsel_h[n_long]] : 0;  // (the longest sampled query that is staged in LDS)
@@ -4010,14 +4072,20 @@ bool DeviceDataset::Impl::hist_qof(std::string* err) {
     return true;
 }
 
-bool DeviceDataset::hist_sample(const unsigned char* query_flags, uint32_t n_t, const uint32_t* fsel, size_t f_t, std::string* err) {
+bool DeviceDataset::hist_sample(const unsigned char* query_flags, uint32_t n_t, const uint32_t* fsel, size_t f_t, std::string* err,
+                                bool keep_queries) {
     Impl& m = *impl_;
     std::lock_guard<std::mutex> lk(m.mu);
     if (!m.bind(err)) return false;
     auto& h = m.hist;
     if (h.k == 0) return hist_fail(err, "no bins built");
     const uint32_t n = h.n;
-    h.nt = n, h.Ft = h.F, h.q_sampled = h.f_sampled = false;
+    if (keep_queries && query_flags == nullptr && h.q_sampled) {  // (the root list and its length stay)
+        n_t = h.nt;
+        h.Ft = h.F, h.f_sampled = false;
+    } else {
+        h.nt = n, h.Ft = h.F, h.q_sampled = h.f_sampled = false;
+    }
     if (fsel != nullptr) {
         if (f_t == 0 || f_t > h.F) return hist_fail(err, "a feature sample must hold between 1 and all of the features");
         for (size_t i = 0; i < f_t; i++)

@@ -214,3 +214,47 @@ __global__ void final_mean_kernel(const double* __restrict__ partial, uint32_t l
     if (host_copy != nullptr) host_copy[c] = mean;
 }
 
+// The same mean over two SUBSETS of the queries at once: LambdaMART's training and held-out queries (DESIGN.md section 11,
+// "Validation and early stopping").  idx = the first subset's queries (n_a, ascending), then the second's (n_b); a
+// subset's mean has the shape above over its COMPACTED list of per-query values (column 0 of M):
+//   partial[s] = sequential sum of segment s = MEAN_SEG consecutive entries of the compacted list
+//   mean       = (sequential sum of the subset's partials) / the subset's size
+// One workgroup per segment (nseg_a of the first subset, then the second's): the gather goes through LDS, one value per
+// thread, and one thread adds the values in order.
+__global__ __launch_bounds__(MEAN_SEG) void subset_segment_sum_kernel(const double* __restrict__ M, uint32_t ldm,
+                                                                      const uint32_t* __restrict__ idx, uint32_t n_a, uint32_t n_b,
+                                                                      uint32_t nseg_a, double* __restrict__ partial) {
+    __shared__ double v[MEAN_SEG];
+    const uint32_t s = blockIdx.x, tid = threadIdx.x;
+    const bool second = s >= nseg_a;
+    const uint32_t base = second ? n_a : 0u, n = second ? n_b : n_a;
+    const uint32_t i0 = (second ? s - nseg_a : s) * MEAN_SEG;
+    const uint32_t cnt = i0 < n ? (n - i0 < MEAN_SEG ? n - i0 : MEAN_SEG) : 0u;
+    if (tid < cnt) v[tid] = M[(size_t)idx[base + i0 + tid] * ldm];
+    __syncthreads();
+    if (tid != 0) return;
+    double sum = 0.0;
+    for (uint32_t i = 0; i < cnt; i++) sum += v[i];
+    partial[s] = sum;
+}
+
+// means[0] / means[1]: the first / second subset's mean.  One workgroup of two waves: a wave per subset, its partials
+// staged in LDS a stretch at a time, its first lane adding them in segment order.
+__global__ __launch_bounds__(128) void subset_final_mean_kernel(const double* __restrict__ partial, uint32_t nseg_a, uint32_t nseg_b,
+                                                                uint32_t n_a, uint32_t n_b, double* __restrict__ means) {
+    __shared__ double v[2][64];
+    const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const double* p = partial + (w ? nseg_a : 0u);
+    const uint32_t nseg = w ? nseg_b : nseg_a, div = w ? n_b : n_a;
+    const uint32_t rounds = ((nseg_a > nseg_b ? nseg_a : nseg_b) + 63) / 64;  // (both waves reach every barrier)
+    double sum = 0.0;
+    for (uint32_t r = 0; r < rounds; r++) {
+        const uint32_t s0 = r * 64;
+        if (s0 + lane < nseg) v[w][lane] = p[s0 + lane];
+        __syncthreads();
+        if (lane == 0)
+            for (uint32_t i = 0; i < 64 && s0 + i < nseg; i++) sum += v[w][i];
+        __syncthreads();
+    }
+    if (lane == 0) means[w] = div ? sum / (double)div : 0.0;
+}

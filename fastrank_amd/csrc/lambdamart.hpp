@@ -15,9 +15,15 @@
 // query_sampling_rate / feature_sampling_rate < 1 ("Sampling"): gradient, grow and leaves of a tree
 // cover a fresh sample of the queries (a subsequence of the instance list) and of the features, drawn from `seed`; update
 // and training measure still cover every document.
+// validation_queries ("Validation and early stopping"): the named queries are held out of gradient,
+// grow and leaves of every tree (the samples are then drawn from the others); update covers them as well, and the measure
+// is reported over the training and the held-out queries separately.  early_stopping_rounds = r > 0 ends training r trees
+// after the held-out measure's first maximum and returns the trees up to it.
 #pragma once
 #include <chrono>
 #include <cmath>
+#include <set>
+#include <unordered_map>
 
 #include "host.hpp"
 #include "lambdamart_hist.hpp"
@@ -38,6 +44,9 @@ struct LambdaMARTParams {
     // the share of the view's features it may split on, the master seed of the samples
     double query_sampling_rate = 1.0, feature_sampling_rate = 1.0;
     uint64_t seed = 0;
+    // held-out queries (ids as the dataset spells them) and the stopping rule (optional keys, not written at their defaults)
+    std::vector<std::string> validation_queries;
+    uint32_t early_stopping_rounds = 0;
 
     bool sampling() const { return query_sampling_rate < 1.0 || feature_sampling_rate < 1.0; }
     [[noreturn]] static void invalid(const std::string& what) {
@@ -61,6 +70,16 @@ struct LambdaMARTParams {
         if (const Value* r = v.find("query_sampling_rate")) p.query_sampling_rate = json_f64(*r, "query_sampling_rate");
         if (const Value* r = v.find("feature_sampling_rate")) p.feature_sampling_rate = json_f64(*r, "feature_sampling_rate");
         if (const Value* r = v.find("seed")) p.seed = json_u64(*r, "seed");
+        if (const Value* a = v.find("validation_queries")) {
+            if (!a->is_array()) fail_raw("Error(\"invalid type: expected an array of strings for validation_queries\", line: 0, column: 0)");
+            std::set<std::string> seen;
+            for (const Value& e : a->arr) {
+                if (!e.is_string()) fail_raw("Error(\"invalid type: expected a string for every entry of validation_queries\", line: 0, column: 0)");
+                if (!seen.insert(e.s).second) invalid("validation_queries names query `" + e.s + "` more than once");
+                p.validation_queries.push_back(e.s);
+            }
+        }
+        if (const Value* r = v.find("early_stopping_rounds")) p.early_stopping_rounds = json_u32(*r, "early_stopping_rounds");
         if (p.num_trees < 1) invalid("num_trees must be at least 1");
         if (!(std::isfinite(p.learning_rate) && p.learning_rate > 0.0)) invalid("learning_rate must be finite and greater than 0");
         if (p.max_depth < 1) invalid("max_depth must be at least 1");
@@ -71,6 +90,8 @@ struct LambdaMARTParams {
             invalid("feature_sampling_rate must be greater than 0 and at most 1");
         if (p.histogram && (p.split_candidates < 2 || p.split_candidates > 256))
             invalid("split_candidates must be between 2 and 256 for the histogram grower (bins are one byte)");
+        if (p.early_stopping_rounds > 0 && p.validation_queries.empty())
+            invalid("early_stopping_rounds needs at least one validation query (validation_queries is empty)");
         return p;
     }
     Value to_json() const {
@@ -86,6 +107,12 @@ struct LambdaMARTParams {
         if (query_sampling_rate != 1.0) o.set("query_sampling_rate", Value::number(query_sampling_rate));
         if (feature_sampling_rate != 1.0) o.set("feature_sampling_rate", Value::number(feature_sampling_rate));
         if (seed != 0) o.set("seed", Value::uint(seed));
+        if (!validation_queries.empty()) {
+            Value a = Value::array();
+            for (const std::string& q : validation_queries) a.push(Value::string(q));
+            o.set("validation_queries", std::move(a));
+        }
+        if (early_stopping_rounds != 0) o.set("early_stopping_rounds", Value::uint(early_stopping_rounds));
         return o;
     }
 };
@@ -110,10 +137,34 @@ inline std::vector<uint32_t> lambdamart_instance_list(const frdev::HostCSR& csr)
     return ids;
 }
 
+// The split of the view's queries Q (its order) into held-out H and training T = Q \ H, both as ascending indices into Q.
+// Host only: a request is checked by this before any device work.
+struct LambdaSplit {
+    std::vector<uint32_t> train, held;
+};
+inline LambdaSplit lambdamart_split(DatasetView& view, const LambdaMARTParams& p) {
+    const size_t nq = view.host_csr().nq;
+    LambdaSplit sp;
+    std::vector<unsigned char> out(nq, 0);
+    if (!p.validation_queries.empty()) {
+        std::unordered_map<std::string, uint32_t> index;
+        for (size_t q = 0; q < nq; q++) index.emplace(view.core->qnames[view.csr_query[q]], (uint32_t)q);
+        for (const std::string& id : p.validation_queries) {
+            auto it = index.find(id);
+            if (it == index.end()) LambdaMARTParams::invalid("validation_queries names `" + id + "`, which is not a query of the dataset");
+            out[it->second] = 1;  // (repeated ids were refused when the request was parsed)
+        }
+        if (p.validation_queries.size() >= nq) LambdaMARTParams::invalid("validation_queries holds out every query: no training query left");
+    }
+    for (size_t q = 0; q < nq; q++) (out[q] ? sp.held : sp.train).push_back((uint32_t)q);
+    return sp;
+}
+
 // A tree's sample ("Sampling"): indices into the view's ascending feature list and into the view's
 // queries, both ascending.  The master generator Rand64(seed) gives every tree two seeds in order, fseed_t then qseed_t;
 // a list is shuffle(0..len-1) under its own Rand64, the first sample_count(len, rate) entries, sorted.  A rate of 1.0 skips
-// the shuffle (the full list) but not the seed.
+// the shuffle (the full list) but not the seed.  With held-out queries the query list is drawn over 0..|T|-1 and mapped
+// through T (`train`): the result is still ascending indices of the view's queries.
 struct LambdaSample {
     std::vector<uint32_t> features, queries;
 };
@@ -127,9 +178,14 @@ inline std::vector<uint32_t> lambdamart_sample_list(uint64_t seed, size_t len, d
     std::sort(v.begin(), v.end());
     return v;
 }
-inline LambdaSample lambdamart_next_sample(Rand64& master, size_t n_features, size_t n_queries, const LambdaMARTParams& p) {
+inline LambdaSample lambdamart_next_sample(Rand64& master, size_t n_features, size_t n_queries, const LambdaMARTParams& p,
+                                           const std::vector<uint32_t>* train = nullptr) {
     const uint64_t fseed = master.rand_u64(), qseed = master.rand_u64();
-    return {lambdamart_sample_list(fseed, n_features, p.feature_sampling_rate), lambdamart_sample_list(qseed, n_queries, p.query_sampling_rate)};
+    LambdaSample smp{lambdamart_sample_list(fseed, n_features, p.feature_sampling_rate),
+                     lambdamart_sample_list(qseed, train ? train->size() : n_queries, p.query_sampling_rate)};
+    if (train)
+        for (uint32_t& q : smp.queries) q = (*train)[q];
+    return smp;
 }
 
 struct LambdaMARTStats {
@@ -144,6 +200,10 @@ struct LambdaMARTStats {
     bool sampling = false;
     double query_sampling_rate = 1.0, feature_sampling_rate = 1.0;
     uint64_t seed = 0, sum_queries = 0, sum_instances = 0, sum_features = 0;
+    // held-out queries (reported only when there are any): with them train_measure is the mean over the training queries
+    bool validation = false, stopped_early = false;
+    uint32_t validation_queries = 0, training_queries = 0, best_iteration = 0, early_stopping_rounds = 0;
+    std::vector<double> valid_measure;  // evaluator mean of the running scores over the held-out queries after each tree
 
     Value to_json() const {
         Value o = Value::object();
@@ -168,6 +228,17 @@ struct LambdaMARTStats {
         Value a = Value::array();
         for (double x : train_measure) a.push(Value::number(x));
         o.set("train_measure", std::move(a));
+        if (validation) {
+            o.set("validation_queries", Value::uint(validation_queries));
+            o.set("training_queries", Value::uint(training_queries));
+            Value b = Value::array();
+            for (double x : valid_measure) b.push(Value::number(x));
+            o.set("valid_measure", std::move(b));
+            o.set("best_iteration", Value::uint(best_iteration));
+            o.set("best_valid_measure", Value::number(best_iteration ? valid_measure[best_iteration - 1] : 0.0));
+            o.set("stopped_early", Value::boolean(stopped_early));
+            o.set("early_stopping_rounds", Value::uint(early_stopping_rounds));
+        }
         return o;
     }
 };
@@ -184,6 +255,8 @@ class LambdaMARTTrainer {
             return std::chrono::duration<double>(b - a).count();
         };
         if (ev_.measure != frdev::M_NDCG) fail_str("LambdaMART: only ndcg and ndcg@k have gradients");
+        const LambdaSplit split = lambdamart_split(*view_, p_);  // (host only: a bad list fails before any device work)
+        const bool hold = !split.held.empty();
         frdev::DeviceDataset& dev = view_->device();
         const frdev::HostCSR& csr = view_->host_csr();
         const DataCore& core = *view_->core;
@@ -224,23 +297,56 @@ class LambdaMARTTrainer {
         RFStats rst;
         struct EndGuard {
             frdev::DeviceDataset& d;
-            ~EndGuard() { d.rf_end(); }
+            ~EndGuard() { d.rf_end(), d.subset_means_end(); }
         } end_guard{dev};
 
         Model out;
         out.kind = Model::Ensemble;
         // running scores: acc = 0, slot 0 = acc
         if (!dev.ensemble_begin(&err) || !dev.ensemble_finish(&err)) fail_str(err);
-        if (!p_.quiet) printf("-----------------------\n|%7s|%15s|\n-----------------------\n", "Tree", ev_.name.c_str());
+        const char* rule = hold ? "---------------------------------------\n" : "-----------------------\n";
+        if (!p_.quiet) {
+            if (hold) printf("%s|%7s|%15s|%15s|\n%s", rule, "Tree", ev_.name.c_str(), "validation", rule);
+            else printf("%s|%7s|%15s|\n%s", rule, "Tree", ev_.name.c_str(), rule);
+        }
         std::vector<double> lam, wt, leaf_of(max_id + 1, 0.0);
         // per-tree samples: with both rates at 1.0 nothing below differs from a request without the keys
+        // held-out queries: every tree's query list is a subset of T -- T itself, set once, without a query rate
         const bool sampling = p_.sampling(), sample_q = p_.query_sampling_rate < 1.0, sample_f = p_.feature_sampling_rate < 1.0;
+        const bool subset_q = sample_q || hold, fixed_q = hold && !sample_q;
         stats_.sampling = sampling;
         stats_.query_sampling_rate = p_.query_sampling_rate, stats_.feature_sampling_rate = p_.feature_sampling_rate, stats_.seed = p_.seed;
         Rand64 master(p_.seed);
         std::vector<unsigned char> qflags;
         std::vector<uint32_t> t_ids, t_pos, t_feats, t_off;
         uint32_t t_n = 0;  // the tree's number of instances
+        // the tree's query list -> flags, number of instances and (exact grower) instance list and positions
+        auto take_queries = [&](const std::vector<uint32_t>& qs) {
+            qflags.assign(csr.nq, 0);
+            size_t n_t = 0;
+            for (uint32_t q : qs) qflags[q] = 1, n_t += csr.qoff[q + 1] - csr.qoff[q];
+            t_n = (uint32_t)n_t;
+            if (hist) return;  // (the histogram grower makes its root list on the device from the flags)
+            t_ids.clear(), t_pos.clear();
+            for (uint32_t q : qs) {
+                const size_t b = csr.qoff[q] - csr.qoff[0], e = csr.qoff[q + 1] - csr.qoff[0];
+                t_ids.insert(t_ids.end(), root_ids.begin() + b, root_ids.begin() + e);
+                t_pos.insert(t_pos.end(), positions.begin() + b, positions.begin() + e);
+            }
+            t_off = {0u, (uint32_t)t_ids.size()};
+        };
+        if (hold) {
+            stats_.validation = true;
+            stats_.validation_queries = (uint32_t)split.held.size(), stats_.training_queries = (uint32_t)split.train.size();
+            stats_.early_stopping_rounds = p_.early_stopping_rounds;
+            if (!dev.subset_means_set(split.train, split.held, &err)) fail_str(err);
+            if (fixed_q) {
+                take_queries(split.train);
+                if (hist) hist->set_sample(qflags.data(), t_n, nullptr);
+            }
+        }
+        uint32_t trained = 0, best_it = 0;
+        double best_valid = 0.0;
         for (uint32_t t = 0; t < p_.num_trees; t++) {
             auto ts = tnow();  // (drawing the sample and handing it to the grower count as grow time)
             LambdaSample smp;
@@ -248,36 +354,24 @@ class LambdaMARTTrainer {
             const std::vector<uint32_t>*ids_t = &root_ids, *feats_t = &feats, *off_t = &root_off;
             const uint32_t* pos_t = positions.data();
             if (sampling) {
-                smp = lambdamart_next_sample(master, feats.size(), csr.nq, p_);
-                size_t n_t = root_ids.size();
-                if (sample_q) {
-                    qflags.assign(csr.nq, 0);
-                    n_t = 0;
-                    for (uint32_t q : smp.queries) qflags[q] = 1, n_t += csr.qoff[q + 1] - csr.qoff[q];
-                }
+                smp = lambdamart_next_sample(master, feats.size(), csr.nq, p_, hold ? &split.train : nullptr);
+                if (sample_q) take_queries(smp.queries);
                 if (sample_f) {
                     t_feats.clear();
                     for (uint32_t s : smp.features) t_feats.push_back(feats[s]);
                     feats_t = &t_feats;
                 }
-                if (sample_q && !hist) {  // (the histogram grower makes its root list on the device from the flags)
-                    t_ids.clear(), t_pos.clear();
-                    for (uint32_t q : smp.queries) {
-                        const size_t b = csr.qoff[q] - csr.qoff[0], e = csr.qoff[q + 1] - csr.qoff[0];
-                        t_ids.insert(t_ids.end(), root_ids.begin() + b, root_ids.begin() + e);
-                        t_pos.insert(t_pos.end(), positions.begin() + b, positions.begin() + e);
-                    }
-                    t_off = {0u, (uint32_t)t_ids.size()};
-                    ids_t = &t_ids, off_t = &t_off, pos_t = t_pos.data();
-                }
-                t_n = (uint32_t)n_t;
-                stats_.sum_queries += smp.queries.size(), stats_.sum_instances += n_t, stats_.sum_features += smp.features.size();
+                stats_.sum_queries += smp.queries.size(), stats_.sum_instances += subset_q ? t_n : root_ids.size(), stats_.sum_features += smp.features.size();
             }
+            if (subset_q && !hist) ids_t = &t_ids, off_t = &t_off, pos_t = t_pos.data();
             auto ta = tnow();
-            if (!dev.lambda_gradients(ev_.norms.data(), ev_.depth, p_.sigma, &err, sample_q ? qflags.data() : nullptr)) fail_str(err);
+            if (!dev.lambda_gradients(ev_.norms.data(), ev_.depth, p_.sigma, &err, subset_q ? qflags.data() : nullptr, fixed_q && t > 0)) fail_str(err);
             if (!frdev::device_synchronize(&err)) fail_str(err);
             auto tb = tnow();
-            if (sampling && hist) hist->set_sample(sample_q ? qflags.data() : nullptr, t_n, sample_f ? &smp.features : nullptr);
+            if (sampling && hist) {
+                if (fixed_q) hist->set_sample(nullptr, t_n, sample_f ? &smp.features : nullptr, true);  // (T's root list stays)
+                else hist->set_sample(sample_q ? qflags.data() : nullptr, t_n, sample_f ? &smp.features : nullptr);
+            }
             double leaf_secs = 0.0;
             std::shared_ptr<TreeNode> root = hist ? hist->grow(nullptr, nullptr, &leaf_secs)
                                                   : grower.grow_lambda_tree(dev, *off_t, *ids_t, *feats_t, pos_t, rst);
@@ -309,9 +403,14 @@ class LambdaMARTTrainer {
             tm.tree = root;
             score_model(*view_, tm, &dev);
             if (!dev.ensemble_accumulate(p_.learning_rate, &err) || !dev.ensemble_finish(&err)) fail_str(err);
-            double mean = 0.0;
+            double mean = 0.0, two[2] = {0.0, 0.0};
             if (!dev.metric_from_scores(ev_.measure, ev_.depth, ev_.norms.data(), 1, false, &err)) fail_str(err);
-            if (!dev.reduce_means(1, &mean, &err)) fail_str(err);
+            if (hold) {  // the means over T and H, from the one per-query pass
+                if (!dev.reduce_subset_means(two, &err)) fail_str(err);
+                mean = two[0];
+            } else if (!dev.reduce_means(1, &mean, &err)) {
+                fail_str(err);
+            }
             check_flags(dev);
             auto te = tnow();
             stats_.t_gradient += secs(ta, tb);
@@ -322,12 +421,27 @@ class LambdaMARTTrainer {
             out.members.push_back(std::move(tm));
             out.ens_weights.push_back(p_.learning_rate);
             if (!p_.quiet) {
-                printf("|%7u|%15.6f|\n", t + 1, mean);
+                if (hold) printf("|%7u|%15.6f|%15.6f|\n", t + 1, mean, two[1]);
+                else printf("|%7u|%15.6f|\n", t + 1, mean);
                 fflush(stdout);
             }
+            trained = t + 1;
+            if (hold) {
+                stats_.valid_measure.push_back(two[1]);
+                if (best_it == 0 || two[1] > best_valid) best_it = trained, best_valid = two[1];  // the FIRST maximum
+                if (p_.early_stopping_rounds > 0 && trained - best_it >= p_.early_stopping_rounds) {
+                    stats_.stopped_early = trained < p_.num_trees;
+                    break;
+                }
+            }
         }
-        if (!p_.quiet) printf("-----------------------\n");
-        stats_.trees = p_.num_trees;
+        if (!p_.quiet) printf("%s", rule);
+        stats_.trees = trained;
+        stats_.best_iteration = best_it;
+        if (hold && p_.early_stopping_rounds > 0) {  // the ensemble up to the best tree (trees depend on their predecessors only)
+            out.members.resize(best_it);
+            out.ens_weights.resize(best_it);
+        }
         stats_.seconds = secs(t0, tnow());
         return out;
     }

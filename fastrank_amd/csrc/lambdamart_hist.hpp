@@ -33,13 +33,20 @@ class HistGrower {
     // The sample of the trees grown from now on ("Sampling").  query_flags[q] != 0: query q of the
     // view is in the sample, n_t of the instance list's entries in all (nullptr: every query); features: ascending indices
     // into the feature list (nullptr: every feature).  Bins and edges stay those of the full lists.
-    void set_sample(const unsigned char* query_flags, uint32_t n_t, const std::vector<uint32_t>* features) {
+    // keep_queries (query_flags == nullptr): the query sample set before stays, e.g. a fixed training split under per-tree
+    // feature samples.
+    void set_sample(const unsigned char* query_flags, uint32_t n_t, const std::vector<uint32_t>* features, bool keep_queries = false) {
         std::string err;
+        if (keep_queries && !query_flags) {
+            if (features) sel_ = *features;
+            else sel_.clear();
+            check_features(features);
+            if (!dev_.hist_sample(nullptr, n_, features ? sel_.data() : nullptr, sel_.size(), &err, true)) fail_str(err);
+            return;
+        }
         if (features) sel_ = *features;
         else sel_.clear();
-        for (uint32_t s : sel_)
-            if (s >= feats_.size()) fail_str("LambdaMART histogram grower: a sampled feature outside the feature list");
-        if (features && sel_.empty()) fail_str("LambdaMART histogram grower: an empty feature sample");
+        check_features(features);
         if (!dev_.hist_sample(query_flags, query_flags ? n_t : n_full_, features ? sel_.data() : nullptr, sel_.size(), &err)) fail_str(err);
         n_ = query_flags ? n_t : n_full_;
     }
@@ -138,6 +145,11 @@ class HistGrower {
     }
 
   private:
+    void check_features(const std::vector<uint32_t>* features) const {
+        for (uint32_t s : sel_)
+            if (s >= feats_.size()) fail_str("LambdaMART histogram grower: a sampled feature outside the feature list");
+        if (features && sel_.empty()) fail_str("LambdaMART histogram grower: an empty feature sample");
+    }
     // rf_train.hpp's rule: may a node be searched at all?
     bool enterable(uint32_t n, uint32_t depth) const { return n >= 2 && depth < max_depth_ && n >= min_leaf_; }
 

@@ -8,7 +8,9 @@ the implementation is table-driven: every parameter class registers its serde va
 """
 import dataclasses
 import random
-from typing import Any, ClassVar, Dict, Optional, Type
+from typing import Any, ClassVar, Dict, List, Optional, Sequence, Type
+
+import numpy as np
 
 from .clib import CQRel, query_json
 
@@ -86,7 +88,13 @@ class LambdaMARTParams(_LearnerParams):
     `query_sampling_rate`, `feature_sampling_rate` (0 < r <= 1, default 1.0) and `seed` (u64, default 0): every tree is
     fitted to a fresh sample of that share of the view's queries (whole queries, never single documents) and may split on a
     fresh sample of that share of its features; the samples are a function of `seed` alone.  Like `grower` the three keys are
-    written to the wire form only when they differ from their defaults; with both rates at 1.0 `seed` has no effect."""
+    written to the wire form only when they differ from their defaults; with both rates at 1.0 `seed` has no effect.
+    `validation_queries` (query ids as `CDataset.queries()` spells them, default none): these queries are held out of every
+    tree's gradients, splits and leaf values (per-tree query samples are then drawn from the others); the training stats
+    report the measure over the training and the held-out queries after every tree (`train_measure`, `valid_measure`,
+    `best_iteration`).  `early_stopping_rounds` = r > 0 (needs a held-out query): training ends r trees after the first
+    maximum of `valid_measure`, and the model is the trees up to that maximum.  Both keys are written only when set;
+    `hold_out_queries` makes a split."""
 
     VARIANT: ClassVar[str] = "LambdaMART"
 
@@ -101,8 +109,11 @@ class LambdaMARTParams(_LearnerParams):
     query_sampling_rate: float = 1.0
     feature_sampling_rate: float = 1.0
     seed: int = 0
+    validation_queries: List[str] = dataclasses.field(default_factory=list)
+    early_stopping_rounds: int = 0
 
-    _WIRE_DEFAULTS: ClassVar[Dict[str, Any]] = {"grower": "exact", "query_sampling_rate": 1.0, "feature_sampling_rate": 1.0, "seed": 0}
+    _WIRE_DEFAULTS: ClassVar[Dict[str, Any]] = {"grower": "exact", "query_sampling_rate": 1.0, "feature_sampling_rate": 1.0, "seed": 0,
+                                                "validation_queries": [], "early_stopping_rounds": 0}
 
     def to_dict(self) -> Dict[str, Any]:
         wire = dataclasses.asdict(self)
@@ -110,6 +121,22 @@ class LambdaMARTParams(_LearnerParams):
             if wire[key] == default:
                 del wire[key]
         return wire
+
+
+def hold_out_queries(queries: Sequence[str], rate: float, seed: int = 0) -> List[str]:
+    """A validation split for `LambdaMARTParams.validation_queries`: about `rate` of `queries` (e.g. `dataset.queries()`),
+    at least one and at most all but one, chosen by numpy's `default_rng(seed)`; the result keeps the order of `queries`.
+    The same arguments give the same split; a set, which has no order of its own (`dataset.queries()` is one), is sorted
+    first."""
+    queries = sorted(queries) if isinstance(queries, (set, frozenset)) else list(queries)
+    if len(queries) < 2:
+        raise ValueError("hold_out_queries needs at least two queries (one to train on, one to hold out)")
+    if not 0.0 < float(rate) < 1.0:
+        raise ValueError("hold_out_queries: rate must be greater than 0 and less than 1")
+    count = min(len(queries) - 1, max(1, int(len(queries) * float(rate))))
+    held = np.zeros(len(queries), dtype=bool)
+    held[np.random.default_rng(int(seed)).permutation(len(queries))[:count]] = True
+    return [q for q, h in zip(queries, held) if h]
 
 
 @dataclasses.dataclass

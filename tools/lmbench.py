@@ -4,6 +4,8 @@
     python tools/lmbench.py --shape 30k --trees 100 --grower histogram   # the histogram grower
     python tools/lmbench.py --shape 30k --trees 100 --grower histogram --query-sampling-rate 0.5 --feature-sampling-rate 0.5 --seed 1
                                                                # per-tree samples of the queries and the features
+    python tools/lmbench.py --shape 30k --trees 100 --grower histogram --validation-rate 0.1 --early-stopping-rounds 10
+                                                               # a held-out tenth of the queries, stop 10 trees after its best
     python tools/lmbench.py --shape 30k --cpu-baseline 0.01    # the numpy restatement (tests/lambdamart_model.py) timed on
                                                                # a query sample, scaled to the full shape (labelled as such)
 Every other parameter is the LambdaMART default (TrainRequest.lambdamart()).
@@ -37,6 +39,11 @@ def device_run(args, X, y, qid):
     req.params.query_sampling_rate = args.query_sampling_rate
     req.params.feature_sampling_rate = args.feature_sampling_rate
     req.params.seed = args.seed
+    if args.validation_rate > 0:
+        from fastrank_amd.training import hold_out_queries
+
+        req.params.validation_queries = hold_out_queries(ds.queries(), args.validation_rate, args.seed)
+    req.params.early_stopping_rounds = args.early_stopping_rounds
     # upload and first touch of the device (not part of training)
     native.device_info(ds)
     t_ds = time.perf_counter() - t0
@@ -53,7 +60,7 @@ def device_run(args, X, y, qid):
     out = {
         "metric": "LambdaMART seconds per tree (device) on MSLR-WEB30K shape" if args.shape == "30k" else "LambdaMART seconds per tree (device)",
         "shape": args.shape, "n": int(X.shape[0]), "d": int(X.shape[1]), "queries": int(len(np.unique(qid))),
-        "measure": args.measure, "trees": T, "params": req.params.to_dict(),
+        "measure": args.measure, "trees": T, "params": {k: v for k, v in req.params.to_dict().items() if k != "validation_queries"},
         "dataset_seconds": t_ds, "train_seconds": wall, "seconds_per_tree": wall / T,
         "grower": st["grower"], "bins_ms": st["bins_ms"],
         "per_tree_ms": {k: st[k + "_ms"] / T for k in ("gradient", "grow", "leaves", "update")},
@@ -63,6 +70,10 @@ def device_run(args, X, y, qid):
     }
     if sample:  # (only when a rate is below 1, like the stats object)
         out["sample"] = sample
+    if "valid_measure" in st:  # (only with held-out queries, like the stats object)
+        out["validation"] = {k: st[k] for k in ("validation_queries", "training_queries", "best_iteration", "best_valid_measure",
+                                                "stopped_early", "early_stopping_rounds", "valid_measure", "train_measure")}
+        out["model_trees"] = len(model.to_dict()["Ensemble"]["models"])
     return out
 
 
@@ -104,6 +115,8 @@ def main():
     ap.add_argument("--query-sampling-rate", type=float, default=1.0, help="share of the queries every tree is fitted to")
     ap.add_argument("--feature-sampling-rate", type=float, default=1.0, help="share of the features every tree may split on")
     ap.add_argument("--seed", type=int, default=0, help="master seed of the per-tree samples")
+    ap.add_argument("--validation-rate", type=float, default=0.0, help="share of the queries held out (hold_out_queries under --seed; 0: none)")
+    ap.add_argument("--early-stopping-rounds", type=int, default=0, help="stop this many trees after the held-out measure's best (0: never)")
     ap.add_argument("--cpu-baseline", type=float, default=0.0, help="query fraction for the CPU restatement (0: device run)")
     args = ap.parse_args()
     n, d, q, seed = SHAPES[args.shape]
