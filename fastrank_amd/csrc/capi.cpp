@@ -1167,6 +1167,42 @@ const void* fr_debug_walk_tiles(const uint32_t* run_pos, const uint32_t* run_q0,
     });
 }
 
+// Read-back of the device form of a dataset (include/fastrank.h; DeviceDataset::debug_form_*): read only, no product path
+// calls it.  slot 0 = the view's first device form (built if needed), slot k > 0 = the copy train_model keeps in context k
+// of its device list (an error when there is none: the hook makes no copies).
+const void* fr_debug_device_form(const CDataset* dataset, int slot, const void* table, void* out, size_t out_bytes) {
+    return json_call([&]() {
+        const CDataset& ds = require_dataset(dataset);
+        std::lock_guard<std::mutex> lk(api_mu_of(ds));
+        std::shared_ptr<frdev::DeviceDataset> devp;
+        if (slot <= 0) {
+            devp = ds.view->device_ptr();
+        } else {
+            std::lock_guard<std::mutex> vlk(ds.view->mu);
+            if ((size_t)slot <= ds.view->replicas.size()) devp = ds.view->replicas[(size_t)slot - 1];
+            if (!devp) fr::fail_str("fr_debug_device_form: the dataset has no device copy in slot " + std::to_string(slot));
+        }
+        Value o = Value::object();
+        if (!table) {
+            for (const auto& kv : devp->debug_form_scalars()) o.set(kv.first.c_str(), Value::uint(kv.second));
+            return frjson::dump(o);
+        }
+        const std::string name = accept_str("table", table);
+        std::vector<unsigned char> bytes;
+        bool present = false;
+        std::string err;
+        if (!devp->debug_form_table(name, &bytes, &present, &err)) fr::fail_str(err);
+        o.set("present", Value::boolean(present));
+        o.set("bytes", Value::uint(bytes.size()));
+        if (present) {
+            if (!out || out_bytes != bytes.size())
+                fr::fail_str("fr_debug_device_form: table " + name + " holds " + std::to_string(bytes.size()) + " bytes, the buffer " + std::to_string(out_bytes));
+            std::memcpy(out, bytes.data(), bytes.size());
+        }
+        return frjson::dump(o);
+    });
+}
+
 // The same call sequence on ONE device (a one-rank communicator): librccl.so opens, its symbols bind, ncclCommInitAll /
 // grouped ncclAllGather / ncclCommDestroy run and the data comes back.  What a one-GPU box can check of the exchange.
 const void* fr_debug_rccl_selftest(int device) {

@@ -15,6 +15,7 @@
 #include <cstdint>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace frdev {
@@ -355,6 +356,13 @@ class DeviceDataset {
     void hist_end();  // frees the level histograms (the bins stay)
 
     int take_flags();  // returns and clears the accumulated kernel error bits
+
+    // --- read-back of the device form, for the tests that hold every table to its definition ------
+    // Read only, used by no product path: sizes, switches and buffer addresses (to compare, never to follow) by name, and
+    // a copy of one named static table as bytes once the dataset's stream has drained.  *present = false: the dataset has
+    // no such table (an optional copy that was not made); an unknown name is an error.
+    std::vector<std::pair<std::string, uint64_t>> debug_form_scalars() const;
+    bool debug_form_table(const std::string& name, std::vector<unsigned char>* out, bool* present, std::string* err);
 
   private:
     DeviceDataset();

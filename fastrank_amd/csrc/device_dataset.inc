@@ -197,6 +197,7 @@ struct DeviceDataset::Impl {
     size_t nwt = 0, nwlist = 0;
     std::vector<double> colstd;        // per-column standard deviation over the dataset's documents
     std::vector<uint8_t> colmode;      // bit 0 / 1: more than a tenth of the documents sit at the column's maximum / minimum
+    std::vector<ColStats> colstats_h;  // the records colstd / colmode were made from (read by debug_form_table alone)
     // ... and per trainer
     DevBuf<uint8_t> rslot;             // [slots][np] the same by the resident sum R descending
     std::vector<uint16_t> slot_rank_age;  // line searches since a slot's ranks were made (0xFFFF: never)
@@ -219,6 +220,7 @@ struct DeviceDataset::Impl {
     bool build_columns(std::string* err);
     DevBuf<uint16_t> gkey;             // [np] gain class | duplicate group << key_cls_bits (<= 16 bits wherever the verify kernel runs): the low mantissa bits of its keys
     uint32_t key_bits = 0, key_cls_bits = 0;
+    uint64_t dup_groups = 0;           // duplicate groups found at upload, over all queries (whether or not gkey carries their ids)
     DevBuf<float> xb, gain;
     DevBuf<double> gexp, disc;
     DevBuf<uint32_t> qstart, qlen, qtight, perm, rank, run_q0, run_q1, run_pos, run_docs, run_order, gcls, qlist;
@@ -877,6 +879,7 @@ std::shared_ptr<DeviceDataset> DeviceDataset::create(const HostCSR& csr, std::st
         unsigned hw = std::thread::hardware_concurrency();
         const size_t nthreads = std::max<size_t>(1, std::min<size_t>(hw ? hw : 1, m.np > 200000 ? 16 : 1));
         std::vector<uint32_t> tmax(nthreads, 0);
+        std::vector<uint64_t> tsum(nthreads, 0);
         std::vector<char> tmixed(nthreads, 0);  // some group holds documents of different gain classes
         const size_t row_bytes = csr.d * sizeof(float);
         auto work = [&](size_t tid) {
@@ -913,6 +916,7 @@ std::shared_ptr<DeviceDataset> DeviceDataset::create(const HostCSR& csr, std::st
                     i = e;
                 }
                 tmax[tid] = std::max(tmax[tid], next_id - 1);
+                tsum[tid] += next_id - 1;
             }
         };
         std::vector<std::thread> pool;
@@ -921,6 +925,7 @@ std::shared_ptr<DeviceDataset> DeviceDataset::create(const HostCSR& csr, std::st
         for (auto& th : pool) th.join();
         uint32_t maxg = 0;
         for (uint32_t v : tmax) maxg = std::max(maxg, v);
+        for (uint64_t v : tsum) m.dup_groups += v;
         uint32_t dup_bits = 0;
         while ((1u << dup_bits) <= maxg) dup_bits++;  // ids 0..maxg
         bool mixed = false;
@@ -1029,6 +1034,7 @@ bool DeviceDataset::Impl::build_order_tables(std::string* err) {
         m.colstd[j] = var > 0.0 ? std::sqrt(var) : 0.0;
         m.colmode[j] = (uint8_t)(((double)init[j].at_max > 0.1 * nd ? 1 : 0) | ((double)init[j].at_min > 0.1 * nd ? 2 : 0));
     }
+    m.colstats_h = std::move(init);
     return true;
 }
 
@@ -1055,6 +1061,83 @@ bool DeviceDataset::Impl::build_columns(std::string* err) {
 }
 
 bool DeviceDataset::shares_parent_matrix() const { return (bool)impl_->parent; }
+
+// ---- read-back of the device form (device.hpp: for the tests that hold every table to its definition) ------------------
+std::vector<std::pair<std::string, uint64_t>> DeviceDataset::debug_form_scalars() const {
+    const Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(impl_->mu);
+    auto addr = [](const auto& b) { return (uint64_t) reinterpret_cast<uintptr_t>(b.p); };
+    return {{"np", m.np}, {"dq", m.dq}, {"d", m.d}, {"n", m.n}, {"nq", m.nq}, {"nonfinite", m.nonfinite ? 1u : 0u},
+            {"nruns", m.nruns}, {"nwt", m.nwt}, {"nvtiles", m.nvtiles}, {"nwlist", m.nwlist}, {"maxlen", m.maxlen},
+            {"ncls", m.ncls}, {"key_bits", m.key_bits}, {"key_cls_bits", m.key_cls_bits}, {"dup_groups", m.dup_groups},
+            {"no_document", IDX_INVALID}, {"walk_tile", WT}, {"dcg_ranks", (uint64_t)LS_KT}, {"colstats_bytes", sizeof(ColStats)},
+            {"shares_parent_matrix", m.parent ? 1u : 0u}, {"device", (uint64_t)m.device},
+            // (addresses, to be compared and never followed: a view's tables ARE its parent's)
+            {"xb_addr", addr(m.xb)}, {"xcol_addr", addr(m.xcol)}, {"xslot_addr", addr(m.xslot)}, {"segtab_addr", addr(m.segtab)},
+            {"gkey_addr", addr(m.gkey)}, {"perm_addr", addr(m.perm)}};
+}
+
+bool DeviceDataset::debug_form_table(const std::string& name, std::vector<unsigned char>* out, bool* present, std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    // what create() queued last (xcol_kernel) may still be running; a view's tables were written on its parent's stream
+    if (m.parent) FR_HIP(hipStreamSynchronize(m.parent->impl_->stream));
+    FR_HIP(hipStreamSynchronize(m.stream));
+    out->clear();
+    *present = true;
+    auto dev = [&](const auto& b, size_t count) {  // `count` elements of a device table (absent: an optional copy that was not made)
+        using T = std::remove_pointer_t<decltype(b.p)>;
+        if (b.p == nullptr || count == 0 || count > b.cap) {
+            *present = false;
+            return true;
+        }
+        out->resize(count * sizeof(T));
+        FR_HIP(hipMemcpy(out->data(), b.p, out->size(), hipMemcpyDeviceToHost));
+        return true;
+    };
+    auto host = [&](const auto& v) {
+        using T = typename std::remove_reference_t<decltype(v)>::value_type;
+        if (v.empty()) {
+            *present = false;
+            return true;
+        }
+        out->resize(v.size() * sizeof(T));
+        std::memcpy(out->data(), v.data(), out->size());
+        return true;
+    };
+    if (name == "xb") return dev(m.xb, m.np / 64 * m.dq * 256);
+    if (name == "xcol") return dev(m.xcol, m.d * m.np);
+    if (name == "xslot") return dev(m.xslot, m.d * m.np);
+    if (name == "perm") return dev(m.perm, m.np);
+    if (name == "perm_host") return host(m.perm_host);
+    if (name == "gain") return dev(m.gain, m.np);
+    if (name == "gexp") return dev(m.gexp, m.np);
+    if (name == "gcls") return dev(m.gcls, m.np);
+    if (name == "gkey") return dev(m.gkey, m.np);
+    if (name == "segtab") return dev(m.segtab, m.np);
+    if (name == "wofs") return dev(m.wofs, m.np);
+    if (name == "wt_start") return dev(m.wt_start, m.nwt + 1);
+    if (name == "qstart") return dev(m.qstart, m.nq);
+    if (name == "qlen") return dev(m.qlen, m.nq);
+    if (name == "qtight") return dev(m.qtight, m.nq + 1);
+    if (name == "run_q0") return dev(m.run_q0, m.nruns);
+    if (name == "run_q1") return dev(m.run_q1, m.nruns);
+    if (name == "run_pos") return dev(m.run_pos, m.nruns);
+    if (name == "run_docs") return dev(m.run_docs, m.nruns);
+    if (name == "run_lo") return dev(m.run_lo, m.nruns);
+    if (name == "run_order") return dev(m.run_order, m.nruns);
+    if (name == "run_wt0") return dev(m.run_wt0, m.nruns);
+    if (name == "vtiles") return dev(m.vtiles, m.nvtiles);
+    if (name == "wlist") return dev(m.wlist, m.nwlist);
+    if (name == "dcgtab") return dev(m.dcgtab, m.ncls * LS_KT);
+    if (name == "colmax") return host(m.colmax);
+    if (name == "colstd") return host(m.colstd);
+    if (name == "colmode") return host(m.colmode);
+    if (name == "colstats") return host(m.colstats_h);
+    if (err) *err = "debug_form_table: no table named " + name;
+    return false;
+}
 
 // A second copy of a dataset that owns its matrix, on another device (or a second context on the same one): everything
 // create() built -- the feature tiles, the per-position and per-query tables -- is copied device to device
@@ -1107,6 +1190,7 @@ std::shared_ptr<DeviceDataset> DeviceDataset::replicate(const std::shared_ptr<De
     m.perm_host = sm.perm_host;
     m.qstart_h = sm.qstart_h, m.qlen_h = sm.qlen_h, m.qnpos_h = sm.qnpos_h, m.qnneg_h = sm.qnneg_h;
     m.key_bits = sm.key_bits, m.key_cls_bits = sm.key_cls_bits;
+    m.dup_groups = sm.dup_groups;
     m.size_classes = sm.size_classes;
     m.fv_classes = sm.fv_classes;
     m.relmask = sm.relmask;
@@ -1161,6 +1245,7 @@ std::shared_ptr<DeviceDataset> DeviceDataset::replicate(const std::shared_ptr<De
     copy_optional(m.xslot, sm.xslot, "replicate xslot", "a device replica has no HBM for the visiting-order tables: its NDCG@k verify kernel walks in storage order");
     m.colstd = sm.colstd;
     m.colmode = sm.colmode;
+    m.colstats_h = sm.colstats_h;
     copy(m.qlist, sm.qlist, "replicate qlist");
     copy(m.fv_qlist, sm.fv_qlist, "replicate fv_qlist");
     copy(m.qnpos, sm.qnpos, "replicate qnpos");
@@ -1314,6 +1399,8 @@ std::shared_ptr<DeviceDataset> DeviceDataset::create_view(const std::shared_ptr<
     m.xcol.alias(pm.xcol);
     m.colstd = pm.colstd;
     m.colmode = pm.colmode;
+    m.colstats_h = pm.colstats_h;
+    m.dup_groups = pm.dup_groups;
     m.key_bits = pm.key_bits;
     m.key_cls_bits = pm.key_cls_bits;
     m.verify_xs = pm.verify_xs;

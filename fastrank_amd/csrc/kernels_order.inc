@@ -315,11 +315,15 @@ __global__ __launch_bounds__(256) void colstats_kernel(const float4* __restrict_
         if (pass == 0) {
             atomicAdd(&st[f].sum, s[k]);
             atomicAdd(&st[f].sumsq, s2[k]);
-            // (float min / max through their ordered integer images: non-negative and negative floats need different directions)
-            if (mn[k] >= 0.0f) atomicMin(reinterpret_cast<int*>(&st[f].mn), __float_as_int(mn[k]));
-            else atomicMax(reinterpret_cast<unsigned int*>(&st[f].mn), __float_as_uint(mn[k]));
-            if (mx[k] >= 0.0f) atomicMax(reinterpret_cast<int*>(&st[f].mx), __float_as_int(mx[k]));
-            else atomicMin(reinterpret_cast<unsigned int*>(&st[f].mx), __float_as_uint(mx[k]));
+            // (float min / max through their ordered integer images: non-negative and negative floats need different directions.
+            // A zero goes in as +0.0, by value: -0.0 >= 0.0f holds, but its image is INT_MIN -- as a minimum it would beat
+            // every negative float already stored, or not, by the order the atomics land in; as a maximum it would lose to
+            // every negative one)
+            const float lo = mn[k] + 0.0f, hi = mx[k] + 0.0f;
+            if (lo >= 0.0f) atomicMin(reinterpret_cast<int*>(&st[f].mn), __float_as_int(lo));
+            else atomicMax(reinterpret_cast<unsigned int*>(&st[f].mn), __float_as_uint(lo));
+            if (hi >= 0.0f) atomicMax(reinterpret_cast<int*>(&st[f].mx), __float_as_int(hi));
+            else atomicMin(reinterpret_cast<unsigned int*>(&st[f].mx), __float_as_uint(hi));
         } else {
             if (cmin[k]) atomicAdd(&st[f].at_min, cmin[k]);
             if (cmax[k]) atomicAdd(&st[f].at_max, cmax[k]);

@@ -382,6 +382,52 @@ def walk_tiles(run_pos, run_q0, run_q1, qstart, qlen, np_positions: int) -> Dict
                                                    arrs[3].ctypes.data, arrs[4].ctypes.data, len(arrs[3]), int(np_positions)))
 
 
+# ColStats of csrc/kernels_order.inc, as the device leaves them
+COLSTATS_DTYPE = np.dtype([("sum", "<f8"), ("sumsq", "<f8"), ("mn", "<f4"), ("mx", "<f4"), ("at_min", "<u8"), ("at_max", "<u8")])
+
+
+def device_form(dataset: CDataset, slot: int = 0) -> Dict:
+    """The device form of a dataset read back as numpy arrays and scalars (fr_debug_device_form:
+    read only, builds the form if needed).  Optional tables the dataset does not hold are None.  `slot` > 0: the copy
+    train_model keeps for that entry of its device list.  For a query-sampled view qstart / qlen / the run tables /
+    vtiles / wlist are the view's own and everything per position is the parent's, in the parent's position space."""
+    L = _load()
+    f = {k: int(v) for k, v in _json_reply(L.fr_debug_device_form(dataset.pointer, int(slot), None, None, 0)).items()}
+    f["nonfinite"] = bool(f["nonfinite"])
+    f["shares_parent_matrix"] = bool(f["shares_parent_matrix"])
+    npos, dq, d, nq, nruns = f["np"], f["dq"], f["d"], f["nq"], f["nruns"]
+
+    def table(name, dtype, count, shape=None):
+        arr = np.zeros(count, dtype=dtype)
+        rep = _json_reply(L.fr_debug_device_form(dataset.pointer, int(slot), name.encode("utf-8"), arr.ctypes.data, arr.nbytes))
+        if not rep["present"]:
+            return None
+        return arr if shape is None else arr.reshape(shape)
+
+    if f["colstats_bytes"] != COLSTATS_DTYPE.itemsize:
+        raise RuntimeError("device_form: the library's ColStats record is not the one this module describes")
+    f["xb"] = table("xb", np.float32, npos // 64 * dq * 256)
+    f["xcol"] = table("xcol", np.float32, d * npos, (d, npos))
+    f["xslot"] = table("xslot", np.uint8, d * npos, (d, npos))
+    for name, dtype in (("perm", np.uint32), ("perm_host", np.uint32), ("gain", np.float32), ("gexp", np.float64), ("gcls", np.uint32),
+                        ("gkey", np.uint16), ("segtab", np.uint16), ("wofs", np.uint8)):
+        f[name] = table(name, dtype, npos)
+    f["wt_start"] = table("wt_start", np.uint32, f["nwt"] + 1)
+    f["qstart"] = table("qstart", np.uint32, nq)
+    f["qlen"] = table("qlen", np.uint32, nq)
+    f["qtight"] = table("qtight", np.uint32, nq + 1)
+    for name in ("run_q0", "run_q1", "run_pos", "run_docs", "run_lo", "run_order", "run_wt0"):
+        f[name] = table(name, np.uint32, nruns)
+    f["vtiles"] = table("vtiles", np.uint32, f["nvtiles"])
+    f["wlist"] = table("wlist", np.uint32, f["nwlist"])
+    f["dcgtab"] = table("dcgtab", np.float64, f["ncls"] * f["dcg_ranks"], (f["ncls"], f["dcg_ranks"]))
+    f["colmax"] = table("colmax", np.float64, d)
+    f["colstd"] = table("colstd", np.float64, d)
+    f["colmode"] = table("colmode", np.uint8, d)
+    f["colstats"] = table("colstats", COLSTATS_DTYPE, d)
+    return f
+
+
 def rccl_selftest(device: int = 0) -> Dict:
     """A one-rank RCCL communicator on `device` through the library's exchange code (dlopen, ncclCommInitAll, grouped
     ncclAllGather, compare, destroy): the report of fr_rccl_allgather."""

@@ -289,6 +289,16 @@ const void *fr_rccl_allgather(const int *devices, size_t n, const double *blocks
  * computed on the host alone: JSON {"walk_tile":128,"wt_start":[...],"run_wt0":[...],"seg":[...],"wofs":[...]}. */
 const void *fr_debug_walk_tiles(const uint32_t *run_pos, const uint32_t *run_q0, const uint32_t *run_q1, size_t nruns,
                                 const uint32_t *qstart, const uint32_t *qlen, size_t nq, size_t np);
+/* Read-back of the device form of a dataset, for the tests that hold every table to its definition.
+ * Read only: it takes the dataset's lock, waits for the dataset's stream and copies; no product path calls it.
+ * slot 0 = the dataset's first device form (built if needed); slot k > 0 = the copy train_model keeps for entry k of its
+ * device list (an error when there is none).  table == NULL: JSON of sizes, switches and buffer addresses by name ("np",
+ * "dq", "d", "n", "nq", "nonfinite", "nruns", "nwt", "ncls", "key_bits", "key_cls_bits", "dup_groups", "no_document", ...).
+ * Otherwise the named static table ("xb", "xcol", "xslot", "perm", "qstart", "qlen", "run_*", "wt_start", "segtab", "gain",
+ * "gexp", "gcls", "gkey", "dcgtab", "colmax", "colstd", "colmode", "colstats", ...) is copied to `out` as raw bytes:
+ * JSON {"present": bool, "bytes": n}; present = false when the dataset has no such table (xcol, xslot and the column
+ * statistics are optional), an error when out_bytes is not n or the name is unknown. */
+const void *fr_debug_device_form(const CDataset *dataset, int slot, const void *table, void *out, size_t out_bytes);
 /* The same call sequence with a one-rank communicator on `device` (what a one-GPU box can run of it): same JSON. */
 const void *fr_debug_rccl_selftest(int device);
 /* Frees the device-to-device copies train_model made of this dataset on other devices / in other contexts (they are kept
