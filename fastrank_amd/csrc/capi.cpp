@@ -1523,11 +1523,12 @@ const CResult* fr_debug_hist_tree(const CDataset* dataset, uint32_t split_candid
     });
 }
 
-// fr_debug_hist_tree on a sample: queries[n_queries] = indices of the view's queries (NULL: all), features[n_features] =
-// feature ids of the view (NULL: all).  Gradients of instances outside the query sample are not read.
-const CResult* fr_debug_hist_tree_sampled(const CDataset* dataset, uint32_t split_candidates, uint32_t max_depth, uint32_t min_leaf_support,
-                                          const double* lambda, const double* weight, size_t len, const uint32_t* queries,
-                                          size_t n_queries, const uint32_t* features, size_t n_features) {
+// The body of the two sampled hooks below.  who: the exported function's name, for its error messages; newton: the split
+// criterion the grower is made with (HistNewton(): the variance criterion).
+static const CResult* hist_tree_debug(const std::string& who, const CDataset* dataset, uint32_t split_candidates, uint32_t max_depth,
+                                      uint32_t min_leaf_support, const double* lambda, const double* weight, size_t len,
+                                      const uint32_t* queries, size_t n_queries, const uint32_t* features, size_t n_features,
+                                      const fr::HistNewton& newton) {
     return c_call<CModel>([&]() {
         const CDataset& ds = require_dataset(dataset);
         if (!lambda || !weight) fr::fail_str("NULL pointer: gradient inputs");
@@ -1551,7 +1552,7 @@ const CResult* fr_debug_hist_tree_sampled(const CDataset* dataset, uint32_t spli
             for (size_t i = 0; i < want.size(); i++) {
                 const auto it = std::lower_bound(feats.begin(), feats.end(), want[i]);
                 if (it == feats.end() || *it != want[i] || (i > 0 && want[i] == want[i - 1]))
-                    fr::fail_str("fr_debug_hist_tree_sampled: feature " + std::to_string(want[i]) + " is not in the view, or is named twice");
+                    fr::fail_str(who + ": feature " + std::to_string(want[i]) + " is not in the view, or is named twice");
                 sel.push_back((uint32_t)(it - feats.begin()));
             }
         }
@@ -1562,13 +1563,13 @@ const CResult* fr_debug_hist_tree_sampled(const CDataset* dataset, uint32_t spli
             for (size_t j = csr.qoff[q]; j < csr.qoff[q + 1]; j++, g++) {
                 if (ids[g] >= len) {
                     if (queries && !flags[q]) continue;
-                    fr::fail_str("fr_debug_hist_tree_sampled: the gradient arrays are shorter than the largest sampled instance id");
+                    fr::fail_str(who + ": the gradient arrays are shorter than the largest sampled instance id");
                 }
                 lam[g] = lambda[ids[g]];
                 wt[g] = weight[ids[g]];
             }
         }
-        fr::HistGrower grower(view.device(), feats, split_candidates, max_depth, min_leaf_support);
+        fr::HistGrower grower(view.device(), feats, split_candidates, max_depth, min_leaf_support, newton);
         grower.prepare(positions);
         struct Unsample {  // (the bins stay with the view: leave them without a sample, also when growing fails)
             fr::HistGrower& g;
@@ -1590,6 +1591,28 @@ const CResult* fr_debug_hist_tree_sampled(const CDataset* dataset, uint32_t spli
         }
         return out;
     });
+}
+
+// fr_debug_hist_tree on a sample: queries[n_queries] = indices of the view's queries (NULL: all), features[n_features] =
+// feature ids of the view (NULL: all).  Gradients of instances outside the query sample are not read.
+const CResult* fr_debug_hist_tree_sampled(const CDataset* dataset, uint32_t split_candidates, uint32_t max_depth, uint32_t min_leaf_support,
+                                          const double* lambda, const double* weight, size_t len, const uint32_t* queries,
+                                          size_t n_queries, const uint32_t* features, size_t n_features) {
+    return hist_tree_debug("fr_debug_hist_tree_sampled", dataset, split_candidates, max_depth, min_leaf_support, lambda, weight, len, queries,
+                           n_queries, features, n_features, fr::HistNewton());
+}
+
+// fr_debug_hist_tree_sampled under the Newton split gain ("Newton split gain")
+const CResult* fr_debug_hist_tree_newton(const CDataset* dataset, uint32_t split_candidates, uint32_t max_depth, uint32_t min_leaf_support,
+                                         const double* lambda, const double* weight, size_t len, const uint32_t* queries,
+                                         size_t n_queries, const uint32_t* features, size_t n_features, double lambda_l2,
+                                         double min_sum_hessian, double min_split_gain) {
+    const double numbers[3] = {lambda_l2, min_sum_hessian, min_split_gain};
+    for (double x : numbers)
+        if (!(std::isfinite(x) && x >= 0.0))
+            return c_call<CModel>([&]() -> CModel* { fr::fail_str("fr_debug_hist_tree_newton: lambda_l2, min_sum_hessian and min_split_gain must be finite and at least 0"); });
+    return hist_tree_debug("fr_debug_hist_tree_newton", dataset, split_candidates, max_depth, min_leaf_support, lambda, weight, len, queries,
+                           n_queries, features, n_features, fr::HistNewton{true, lambda_l2, min_sum_hessian, min_split_gain});
 }
 
 const void* fr_evaluate_dense(const CModel* model, const CDataset* dataset, const CQRel* qrel,

@@ -327,6 +327,8 @@ class DeviceDataset {
     struct HistSplit { uint32_t begin, end, fslot, edge, nl; }; // bins 0..edge of feature slot fslot go left: nl of them
     struct HistSub { uint32_t parent, small, large; };          // next level's slot `large` = this level's `parent` - next level's `small`
     struct HistBest { double imp; long long ql, qtot; uint32_t edge, nl, valid, pad; };
+    // split_gain = "newton" ("Newton split gain"): the histograms also hold sum W, the record also the candidate's and the node's
+    struct HistBestNewton { double imp; long long ql, qtot, wl, wtot; uint32_t edge, nl, valid, pad; };
     // bins of the instance list (positions[n], rf_positions' output) for the features `feats` and k = split_candidates
     // (2..256); kept until any of the three changes.  *built = false when the kept ones were reused.
     bool hist_bins(const uint32_t* positions, size_t n, const std::vector<uint32_t>& feats, uint32_t k, bool* built, std::string* err);
@@ -345,13 +347,18 @@ class DeviceDataset {
     // Q / W of the tree to grow, from the last gradient pass (lam_list == nullptr) or from host arrays in instance-list
     // order.  *all_zero: every lambda is 0 (nothing was quantised); s_l / s_w: the exponents S of the definition
     bool hist_quantise(const double* lam_list, const double* wt_list, int* s_l, int* s_w, bool* all_zero, std::string* err);
-    bool hist_root(std::string* err);  // index list = 0..n-1 (the sample's root list); the level holds the root's histogram in slot 0
+    // index list = 0..n-1 (the sample's root list); the level holds the root's histogram in slot 0.  newton: with sum W
+    bool hist_root(std::string* err, bool newton = false);
     // best[a * features + slot]: node a's last-maximum candidate of that feature (valid = 0: none)
     bool hist_search(const std::vector<HistNode>& nodes, uint32_t min_leaf, std::vector<HistBest>* best, std::string* err);
+    // the same under the Newton gain (a level made with newton = true): imp = term(L) + term(R), term = G G / (H + lambda_l2)
+    // with G = ldexp(Q, -s_l), H = ldexp(W, -s_w); a candidate also needs H >= min_sum_hessian and H + lambda_l2 > 0 on both sides
+    bool hist_search_newton(const std::vector<HistNode>& nodes, uint32_t min_leaf, int s_l, int s_w, double lambda_l2,
+                            double min_sum_hessian, std::vector<HistBestNewton>* best, std::string* err);
     // stable partition of the splitting nodes' stretches, then the next level (next_slots histograms; 0: none): `builds` are
     // built from their stretches, `subs` by subtraction from the level just searched
     bool hist_split(const std::vector<HistSplit>& splits, const std::vector<HistNode>& builds, const std::vector<HistSub>& subs,
-                    uint32_t next_slots, std::string* err);
+                    uint32_t next_slots, std::string* err, bool newton = false);
     bool hist_leaf_sums(const std::vector<HistNode>& leaves, std::vector<long long>* qw /*[leaf][2]*/, std::string* err);
     void hist_end();  // frees the level histograms (the bins stay)
 

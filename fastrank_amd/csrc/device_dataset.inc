@@ -313,10 +313,12 @@ struct DeviceDataset::Impl {
         DevBuf<unsigned char> temp;
         DevBuf<uint32_t> cnt, cnt_o;  // level histograms [slot][F][k]: this level's, and the next one's while it is built
         DevBuf<unsigned long long> sum, sum_o;
+        DevBuf<unsigned long long> wsum, wsum_o;  // sum W per (feature, bin): the Newton gain's levels only
         DevBuf<HistItemDev> items, items_b, nodes;  // (items: partition and leaf sums; items_b: histogram builds)
         DevBuf<HistSplitDev> splits;
         DevBuf<HistSubDev> subs;
         DevBuf<HistBestDev> best;
+        DevBuf<HistBestNewtonDev> best_n;
         // host staging of the tables above: overwritten only after the stream was waited for
         std::vector<HistItemDev> items_h, items_bh, nodes_h;
         std::vector<HistSplitDev> splits_h;
@@ -325,6 +327,7 @@ struct DeviceDataset::Impl {
     bool hist_items(const std::vector<HistItemDev>& stretches, std::vector<HistItemDev>& host, DevBuf<HistItemDev>& dev, std::string* err);
     bool hist_qof(std::string* err);
     void hist_build(uint32_t* cnt, unsigned long long* sum);  // hist_build_kernel over hist.items_b into a level's histograms
+    void hist_build_newton(uint32_t* cnt, unsigned long long* sum, unsigned long long* wsum);
     DevBuf<uint64_t> forest;
     DevBuf<uint32_t> tree_fdesc;  // tree_ensemble_rank_kernel: per-feature descriptors, Eytzinger threshold tables
     DevBuf<float> tree_tables;
@@ -4279,6 +4282,17 @@ void DeviceDataset::Impl::hist_build(uint32_t* cnt, unsigned long long* sum) {
         hist_build_kernel<false><<<grid, 256, lds, stream>>>(h.items_b.p, h.xbin.p, h.n, h.idx.p, h.Q.p, nullptr, h.Ft, h.k, cnt, sum);
 }
 
+void DeviceDataset::Impl::hist_build_newton(uint32_t* cnt, unsigned long long* sum, unsigned long long* wsum) {
+    auto& h = hist;
+    ProfScope ps("hist_build_newton_kernel", stream);
+    const dim3 grid((unsigned)h.items_bh.size(), (h.Ft + HIST_FB_NEWTON - 1) / HIST_FB_NEWTON);
+    const size_t lds = (size_t)HIST_FB_NEWTON * h.k * 20;
+    if (h.f_sampled)
+        hist_build_newton_kernel<true><<<grid, 256, lds, stream>>>(h.items_b.p, h.xbin.p, h.n, h.idx.p, h.Q.p, h.W.p, h.fsel.p, h.Ft, h.k, cnt, sum, wsum);
+    else
+        hist_build_newton_kernel<false><<<grid, 256, lds, stream>>>(h.items_b.p, h.xbin.p, h.n, h.idx.p, h.Q.p, h.W.p, nullptr, h.Ft, h.k, cnt, sum, wsum);
+}
+
 static bool hist_level_alloc(DevBuf<uint32_t>& cnt, DevBuf<unsigned long long>& sum, size_t cells, std::string* err) {
     std::string e2;
     if (!cnt.ensure(cells, &e2) || !sum.ensure(cells, &e2)) {
@@ -4289,7 +4303,18 @@ static bool hist_level_alloc(DevBuf<uint32_t>& cnt, DevBuf<unsigned long long>& 
     return true;
 }
 
-bool DeviceDataset::hist_root(std::string* err) {
+// the Newton gain's third array of a level: the same plain error when it does not fit
+static bool hist_level_alloc_w(DevBuf<unsigned long long>& wsum, size_t cells, std::string* err) {
+    std::string e2;
+    if (!wsum.ensure(cells, &e2)) {
+        (void)hipGetLastError();
+        return hist_fail(err, "no device memory for a level's histograms (" + std::to_string((cells * 20) >> 20) +
+                                  " MB: open nodes x features x bins x 20 bytes under the Newton gain); lower max_depth or split_candidates");
+    }
+    return true;
+}
+
+bool DeviceDataset::hist_root(std::string* err, bool newton) {
     Impl& m = *impl_;
     std::lock_guard<std::mutex> lk(m.mu);
     if (!m.bind(err)) return false;
@@ -4299,16 +4324,19 @@ bool DeviceDataset::hist_root(std::string* err) {
     const size_t fk = (size_t)h.Ft * h.k;
     if (!h.idx.ensure(h.n, err) || !h.idx_o.ensure(h.n, err) || !h.flag.ensure(h.n, err) || !h.scan.ensure(h.n, err)) return false;
     if (!hist_level_alloc(h.cnt, h.sum, fk, err)) return false;
+    if (newton && !hist_level_alloc_w(h.wsum, fk, err)) return false;
     FR_HIP(hipMemsetAsync(h.flag.p, 0, n * sizeof(uint32_t), m.stream));
     FR_HIP(hipMemsetAsync(h.cnt.p, 0, fk * sizeof(uint32_t), m.stream));
     FR_HIP(hipMemsetAsync(h.sum.p, 0, fk * sizeof(unsigned long long), m.stream));
+    if (newton) FR_HIP(hipMemsetAsync(h.wsum.p, 0, fk * sizeof(unsigned long long), m.stream));
     if (h.q_sampled) {
         FR_HIP(hipMemcpyAsync(h.idx.p, h.root.p, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, m.stream));
     } else {
         hist_iota_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(h.idx.p, n);
     }
     if (!m.hist_items({{0u, 0u, n}}, h.items_bh, h.items_b, err)) return false;
-    m.hist_build(h.cnt.p, h.sum.p);
+    if (newton) m.hist_build_newton(h.cnt.p, h.sum.p, h.wsum.p);
+    else m.hist_build(h.cnt.p, h.sum.p);
     FR_HIP(hipGetLastError());
     return true;
 }
@@ -4342,8 +4370,40 @@ bool DeviceDataset::hist_search(const std::vector<HistNode>& nodes, uint32_t min
     return true;
 }
 
+bool DeviceDataset::hist_search_newton(const std::vector<HistNode>& nodes, uint32_t min_leaf, int s_l, int s_w, double lambda_l2,
+                                       double min_sum_hessian, std::vector<HistBestNewton>* best, std::string* err) {
+    static_assert(sizeof(HistBestNewton) == sizeof(HistBestNewtonDev), "host and device records differ");
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    const size_t A = nodes.size();
+    best->assign(A * h.Ft, HistBestNewton{});
+    if (A == 0) return true;
+    const size_t fk = (size_t)h.Ft * h.k;
+    h.nodes_h.resize(A);
+    for (size_t a = 0; a < A; a++) {
+        if ((size_t)(nodes[a].slot + 1) * fk > h.cnt.cap || (size_t)(nodes[a].slot + 1) * fk > h.wsum.cap || nodes[a].end > h.nt ||
+            nodes[a].begin > nodes[a].end)
+            return hist_fail(err, "internal error: a node outside the level's histograms");
+        h.nodes_h[a] = {nodes[a].slot, nodes[a].begin, nodes[a].end};
+    }
+    if (!h.nodes.ensure(A, err) || !h.best_n.ensure(A * h.Ft, err)) return false;
+    FR_HIP(hipMemcpyAsync(h.nodes.p, h.nodes_h.data(), A * sizeof(HistItemDev), hipMemcpyHostToDevice, m.stream));
+    {
+        ProfScope ps("hist_scan_newton_kernel", m.stream);
+        hist_scan_newton_kernel<<<(unsigned)(A * h.Ft), 64, 0, m.stream>>>(h.nodes.p, h.Ft, h.k, h.nedges.p, h.f_sampled ? h.fsel.p : nullptr,
+                                                                           h.cnt.p, h.sum.p, h.wsum.p, min_leaf, s_l, s_w, lambda_l2,
+                                                                           min_sum_hessian, h.best_n.p);
+    }
+    FR_HIP(hipGetLastError());
+    FR_HIP(hipMemcpyAsync(best->data(), h.best_n.p, A * h.Ft * sizeof(HistBestNewtonDev), hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipStreamSynchronize(m.stream));
+    return true;
+}
+
 bool DeviceDataset::hist_split(const std::vector<HistSplit>& splits, const std::vector<HistNode>& builds, const std::vector<HistSub>& subs,
-                               uint32_t next_slots, std::string* err) {
+                               uint32_t next_slots, std::string* err, bool newton) {
     static_assert(sizeof(HistSplit) == sizeof(HistSplitDev) && sizeof(HistSub) == sizeof(HistSubDev), "host and device records differ");
     Impl& m = *impl_;
     std::lock_guard<std::mutex> lk(m.mu);
@@ -4382,6 +4442,10 @@ bool DeviceDataset::hist_split(const std::vector<HistSplit>& splits, const std::
     if (!hist_level_alloc(h.cnt_o, h.sum_o, (size_t)next_slots * fk, err)) return false;
     FR_HIP(hipMemsetAsync(h.cnt_o.p, 0, (size_t)next_slots * fk * sizeof(uint32_t), m.stream));
     FR_HIP(hipMemsetAsync(h.sum_o.p, 0, (size_t)next_slots * fk * sizeof(unsigned long long), m.stream));
+    if (newton) {
+        if (!hist_level_alloc_w(h.wsum_o, (size_t)next_slots * fk, err)) return false;
+        FR_HIP(hipMemsetAsync(h.wsum_o.p, 0, (size_t)next_slots * fk * sizeof(unsigned long long), m.stream));
+    }
     std::vector<HistItemDev> stretches(builds.size());
     for (size_t i = 0; i < builds.size(); i++) {
         if (builds[i].slot >= next_slots || builds[i].end > n || builds[i].begin > builds[i].end)
@@ -4389,23 +4453,33 @@ bool DeviceDataset::hist_split(const std::vector<HistSplit>& splits, const std::
         stretches[i] = {builds[i].slot, builds[i].begin, builds[i].end};
     }
     if (!m.hist_items(stretches, h.items_bh, h.items_b, err)) return false;
-    if (!h.items_bh.empty()) m.hist_build(h.cnt_o.p, h.sum_o.p);
+    if (!h.items_bh.empty()) {
+        if (newton) m.hist_build_newton(h.cnt_o.p, h.sum_o.p, h.wsum_o.p);
+        else m.hist_build(h.cnt_o.p, h.sum_o.p);
+    }
     if (!subs.empty()) {
         h.subs_h.resize(subs.size());
         for (size_t i = 0; i < subs.size(); i++) {
-            if ((size_t)(subs[i].parent + 1) * fk > h.cnt.cap || subs[i].small >= next_slots || subs[i].large >= next_slots)
+            if ((size_t)(subs[i].parent + 1) * fk > h.cnt.cap || (newton && (size_t)(subs[i].parent + 1) * fk > h.wsum.cap) || subs[i].small >= next_slots || subs[i].large >= next_slots)
                 return hist_fail(err, "internal error: a subtraction outside the histograms");
             h.subs_h[i] = {subs[i].parent, subs[i].small, subs[i].large};
         }
         if (!h.subs.ensure(subs.size(), err)) return false;
         FR_HIP(hipMemcpyAsync(h.subs.p, h.subs_h.data(), subs.size() * sizeof(HistSubDev), hipMemcpyHostToDevice, m.stream));
-        ProfScope ps("hist_sub_kernel", m.stream);
-        hist_sub_kernel<<<dim3((unsigned)subs.size(), (unsigned)((fk + 255) / 256)), 256, 0, m.stream>>>(h.subs.p, (uint32_t)fk, h.cnt.p, h.sum.p,
-                                                                                                       h.cnt_o.p, h.sum_o.p);
+        if (newton) {
+            ProfScope ps("hist_sub_newton_kernel", m.stream);
+            hist_sub_newton_kernel<<<dim3((unsigned)subs.size(), (unsigned)((fk + 255) / 256)), 256, 0, m.stream>>>(
+                h.subs.p, (uint32_t)fk, h.cnt.p, h.sum.p, h.wsum.p, h.cnt_o.p, h.sum_o.p, h.wsum_o.p);
+        } else {
+            ProfScope ps("hist_sub_kernel", m.stream);
+            hist_sub_kernel<<<dim3((unsigned)subs.size(), (unsigned)((fk + 255) / 256)), 256, 0, m.stream>>>(h.subs.p, (uint32_t)fk, h.cnt.p, h.sum.p,
+                                                                                                           h.cnt_o.p, h.sum_o.p);
+        }
     }
     FR_HIP(hipGetLastError());
     std::swap(h.cnt.p, h.cnt_o.p), std::swap(h.cnt.cap, h.cnt_o.cap);
     std::swap(h.sum.p, h.sum_o.p), std::swap(h.sum.cap, h.sum_o.cap);
+    if (newton) std::swap(h.wsum.p, h.wsum_o.p), std::swap(h.wsum.cap, h.wsum_o.cap);
     return true;
 }
 
@@ -4440,5 +4514,5 @@ void DeviceDataset::hist_end() {
     std::lock_guard<std::mutex> lk(m.mu);
     auto& h = m.hist;
     (void)hipStreamSynchronize(m.stream);
-    h.cnt.release(), h.cnt_o.release(), h.sum.release(), h.sum_o.release(), h.best.release(), h.lam_in.release(), h.wt_in.release();
+    h.cnt.release(), h.cnt_o.release(), h.sum.release(), h.sum_o.release(), h.wsum.release(), h.wsum_o.release(), h.best.release(), h.best_n.release(), h.lam_in.release(), h.wt_in.release();
 }

@@ -364,3 +364,187 @@ __global__ __launch_bounds__(256) void hist_leafsum_kernel(const HistItemDev* __
         atomicAdd(&out[(size_t)it.slot * 2 + 1], (unsigned long long)w);
     }
 }
+
+// --- Newton split gain (DESIGN.md section 11, "Newton split gain") -------------------------------------------------------
+// The histograms carry a third quantity, sum W per (feature, bin): [slot][F][k] of (count u32, sum Q i64, sum W i64), 20 B
+// per bin.  The kernels above keep their code; these stand next to them and run only for split_gain = "newton".
+//
+//   hist_build_newton_kernel  hist_build_kernel with a third LDS atomic per (entry, feature) and a third global one per touched bin
+//   hist_sub_newton_kernel    sibling = parent - child, three arrays
+//   hist_scan_newton_kernel   three prefix sums; G = ldexp(Q, -S), H = ldexp(W, -S_w), term = (G G) / (H + lambda_l2);
+//                             a candidate also needs H >= min_sum_hessian and H + lambda_l2 > 0 on both sides
+
+#ifndef HIST_NEWTON_FB
+#define HIST_NEWTON_FB 8
+#endif
+// features per workgroup of hist_build_newton_kernel: 8 x 256 bins x 20 B = 40 KiB of LDS at k = 256 (four workgroups per CU
+// of 160 KiB, against six of hist_build_kernel), 10 KiB at the default k = 64.  Four features per workgroup (-DHIST_NEWTON_FB=4)
+// halve the footprint but read idx, Q and W twice as often: at the 30K shape grow_ms per tree was 5.06-5.17 ms against
+// 4.68-4.81 ms (6-10 % more), 100 trees 1.183-1.193 s against 1.144-1.197 s (DESIGN.md section 11, "Newton split gain")
+constexpr uint32_t HIST_FB_NEWTON = HIST_NEWTON_FB;
+
+struct HistBestNewtonDev {
+    double imp;
+    long long ql, qtot, wl, wtot;
+    uint32_t edge, nl, valid, pad;
+};
+
+// grid (items, feature blocks of HIST_FB_NEWTON).  cnt / sum / wsum: [slot][F][k]
+template <bool SEL>
+__global__ __launch_bounds__(256) void hist_build_newton_kernel(const HistItemDev* __restrict__ items, const uint8_t* __restrict__ xbin,
+                                                                uint32_t n, const uint32_t* __restrict__ idx, const long long* __restrict__ Q,
+                                                                const long long* __restrict__ W, const uint32_t* __restrict__ fsel, uint32_t F,
+                                                                uint32_t k, uint32_t* __restrict__ cnt, unsigned long long* __restrict__ sum,
+                                                                unsigned long long* __restrict__ wsum) {
+    constexpr uint32_t FB = HIST_FB_NEWTON;
+    extern __shared__ unsigned long long hist_lds[];
+    const HistItemDev it = items[blockIdx.x];
+    const uint32_t f0 = blockIdx.y * FB, nf = min(FB, F - f0);
+    unsigned long long* lq = hist_lds;
+    unsigned long long* lw = hist_lds + (size_t)FB * k;
+    uint32_t* lc = (uint32_t*)(hist_lds + (size_t)2 * FB * k);
+    for (uint32_t t = threadIdx.x; t < FB * k; t += blockDim.x) {
+        lq[t] = 0ull;
+        lw[t] = 0ull;
+        lc[t] = 0u;
+    }
+    __syncthreads();
+    const uint8_t* xb0 = xbin + (size_t)f0 * n;
+    const uint8_t* row[FB];  // (uniform: the block's rows of the bin matrix)
+#pragma unroll
+    for (uint32_t u = 0; u < FB; u++) row[u] = SEL ? xbin + (size_t)fsel[f0 + min(u, nf - 1)] * n : xb0 + (size_t)u * n;
+    for (uint32_t i = it.begin + threadIdx.x; i < it.end; i += blockDim.x) {
+        const uint32_t r = idx[i];
+        const unsigned long long q = (unsigned long long)Q[r], w = (unsigned long long)W[r];
+        if (nf == FB) {
+            uint32_t b[FB];
+#pragma unroll
+            for (uint32_t u = 0; u < FB; u++) b[u] = SEL ? row[u][r] : xb0[(size_t)u * n + r];
+#pragma unroll
+            for (uint32_t u = 0; u < FB; u++) {
+                atomicAdd(&lq[u * k + b[u]], q);
+                atomicAdd(&lw[u * k + b[u]], w);
+                atomicAdd(&lc[u * k + b[u]], 1u);
+            }
+        } else {
+            for (uint32_t u = 0; u < nf; u++) {
+                const uint32_t b = SEL ? xbin[(size_t)fsel[f0 + u] * n + r] : xb0[(size_t)u * n + r];
+                atomicAdd(&lq[u * k + b], q);
+                atomicAdd(&lw[u * k + b], w);
+                atomicAdd(&lc[u * k + b], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    const size_t base = ((size_t)it.slot * F + f0) * k;
+    for (uint32_t t = threadIdx.x; t < nf * k; t += blockDim.x) {
+        const uint32_t c = lc[t];
+        if (c == 0) continue;
+        atomicAdd(&cnt[base + t], c);
+        atomicAdd(&sum[base + t], lq[t]);
+        atomicAdd(&wsum[base + t], lw[t]);
+    }
+}
+
+// grid (pairs, ceil(F k / 256))
+__global__ __launch_bounds__(256) void hist_sub_newton_kernel(const HistSubDev* __restrict__ pairs, uint32_t fk, const uint32_t* __restrict__ pcnt,
+                                                              const unsigned long long* __restrict__ psum,
+                                                              const unsigned long long* __restrict__ pwsum, uint32_t* __restrict__ cnt,
+                                                              unsigned long long* __restrict__ sum, unsigned long long* __restrict__ wsum) {
+    const HistSubDev pr = pairs[blockIdx.x];
+    const uint32_t t = blockIdx.y * blockDim.x + threadIdx.x;
+    if (t >= fk) return;
+    const size_t p = (size_t)pr.parent * fk + t, s = (size_t)pr.small * fk + t, l = (size_t)pr.large * fk + t;
+    cnt[l] = pcnt[p] - cnt[s];
+    sum[l] = psum[p] - sum[s];
+    wsum[l] = pwsum[p] - wsum[s];
+}
+
+// (G G) / (H + lambda_l2) of the integer pair (q, w); every operation rounded on its own
+__device__ __forceinline__ double hist_newton_term(long long q, double h, int s_l, double l2) {
+    const double g = ldexp((double)q, -s_l);
+    return (g * g) / (h + l2);
+}
+
+// one wave per (node, feature), as hist_scan_kernel
+__global__ __launch_bounds__(64) void hist_scan_newton_kernel(const HistItemDev* __restrict__ nodes, uint32_t F, uint32_t k,
+                                                              const uint32_t* __restrict__ nedges, const uint32_t* __restrict__ fsel,
+                                                              const uint32_t* __restrict__ cnt, const unsigned long long* __restrict__ sum,
+                                                              const unsigned long long* __restrict__ wsum, uint32_t min_leaf, int s_l, int s_w,
+                                                              double l2, double min_hess, HistBestNewtonDev* __restrict__ best) {
+    const uint32_t a = blockIdx.x / F, f = blockIdx.x % F, lane = threadIdx.x;
+    const HistItemDev nd = nodes[a];
+    const uint32_t n = nd.end - nd.begin;
+    const uint32_t ne = min(nedges[fsel ? fsel[f] : f], k - 1);
+    const size_t base = ((size_t)nd.slot * F + f) * k;
+    const uint32_t B = (k + 63) / 64;  // bins per lane (<= 4)
+    uint32_t c[4];
+    long long s[4], w[4];
+    uint32_t tc = 0;
+    long long ts = 0, tw = 0;
+    for (uint32_t u = 0; u < 4; u++) {
+        const uint32_t b = lane * B + u;
+        const bool in = u < B && b < k;
+        c[u] = in ? cnt[base + b] : 0u;
+        s[u] = in ? (long long)sum[base + b] : 0ll;
+        w[u] = in ? (long long)wsum[base + b] : 0ll;
+        tc += c[u];
+        ts += s[u];
+        tw += w[u];
+    }
+    uint32_t ic = tc;
+    long long is = ts, iw = tw;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t oc = __shfl_up(ic, o);
+        const long long os = __shfl_up(is, o), ow = __shfl_up(iw, o);
+        if ((int)lane >= o) {
+            ic += oc;
+            is += os;
+            iw += ow;
+        }
+    }
+    const long long qtot = __shfl(is, 63), wtot = __shfl(iw, 63);
+    uint32_t rc = ic - tc;  // counts / sums of the bins before this lane's
+    long long rs = is - ts, rw = iw - tw;
+    double bimp = 0.0;
+    uint32_t bj = 0, bnl = 0, have = 0;
+    long long bql = 0, bwl = 0;
+    for (uint32_t u = 0; u < B; u++) {
+        const uint32_t j = lane * B + u;
+        rc += c[u];
+        rs += s[u];
+        rw += w[u];
+        if (j >= ne) break;
+        const uint32_t nl = rc, nr = n - rc;
+        if (nl == 0 || nr == 0 || nl < min_leaf || nr < min_leaf) continue;
+        const double hl = ldexp((double)rw, -s_w), hr = ldexp((double)(wtot - rw), -s_w);
+        if (!(hl >= min_hess && hr >= min_hess && hl + l2 > 0.0 && hr + l2 > 0.0)) continue;
+        const double imp = hist_newton_term(rs, hl, s_l, l2) + hist_newton_term(qtot - rs, hr, s_l, l2);
+        if (!have || imp >= bimp) {
+            have = 1;
+            bimp = imp;
+            bj = j;
+            bnl = nl;
+            bql = rs;
+            bwl = rw;
+        }
+    }
+    // the last maximum over the lanes: larger importance, then the later edge
+    double wimp = bimp;
+    uint32_t wj = bj, whave = have;
+    for (int o = 32; o > 0; o >>= 1) {
+        const double oimp = __shfl_xor(wimp, o);
+        const uint32_t oj = __shfl_xor(wj, o), ohave = __shfl_xor(whave, o);
+        if (ohave && (!whave || oimp > wimp || (oimp == wimp && oj > wj))) {
+            whave = 1;
+            wimp = oimp;
+            wj = oj;
+        }
+    }
+    HistBestNewtonDev* out = best + (size_t)a * F + f;
+    if (!whave) {
+        if (lane == 0) *out = HistBestNewtonDev{0.0, 0ll, qtot, 0ll, wtot, 0u, 0u, 0u, 0u};
+    } else if (have && bj == wj) {
+        *out = HistBestNewtonDev{bimp, bql, qtot, bwl, wtot, bj, bnl, 1u, 0u};
+    }
+}

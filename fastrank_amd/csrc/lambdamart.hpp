@@ -19,6 +19,8 @@
 // grow and leaves of every tree (the samples are then drawn from the others); update covers them as well, and the measure
 // is reported over the training and the held-out queries separately.  early_stopping_rounds = r > 0 ends training r trees
 // after the held-out measure's first maximum and returns the trees up to it.
+// split_gain = "newton" (histogram grower only; DESIGN.md section 11, "Newton split gain"): splits are placed by the
+// second-order gain G^2 / (H + lambda_l2) with the floors min_sum_hessian and min_split_gain, leaves are G / (H + lambda_l2).
 #pragma once
 #include <chrono>
 #include <cmath>
@@ -47,6 +49,10 @@ struct LambdaMARTParams {
     // held-out queries (ids as the dataset spells them) and the stopping rule (optional keys, not written at their defaults)
     std::vector<std::string> validation_queries;
     uint32_t early_stopping_rounds = 0;
+    // the split criterion (optional keys, not written at their defaults): wire key "split_gain": "variance" or "newton";
+    // the three numbers are read only under "newton"
+    bool newton = false;
+    double lambda_l2 = 0.0, min_sum_hessian = 0.0, min_split_gain = 0.0;
 
     bool sampling() const { return query_sampling_rate < 1.0 || feature_sampling_rate < 1.0; }
     [[noreturn]] static void invalid(const std::string& what) {
@@ -80,6 +86,14 @@ struct LambdaMARTParams {
             }
         }
         if (const Value* r = v.find("early_stopping_rounds")) p.early_stopping_rounds = json_u32(*r, "early_stopping_rounds");
+        if (const Value* g = v.find("split_gain")) {
+            if (!g->is_string()) fail_raw("Error(\"invalid type: expected a string for split_gain\", line: 0, column: 0)");
+            if (g->s != "variance" && g->s != "newton") invalid("split_gain must be `variance` or `newton`, not `" + g->s + "`");
+            p.newton = g->s == "newton";
+        }
+        if (const Value* r = v.find("lambda_l2")) p.lambda_l2 = json_f64(*r, "lambda_l2");
+        if (const Value* r = v.find("min_sum_hessian")) p.min_sum_hessian = json_f64(*r, "min_sum_hessian");
+        if (const Value* r = v.find("min_split_gain")) p.min_split_gain = json_f64(*r, "min_split_gain");
         if (p.num_trees < 1) invalid("num_trees must be at least 1");
         if (!(std::isfinite(p.learning_rate) && p.learning_rate > 0.0)) invalid("learning_rate must be finite and greater than 0");
         if (p.max_depth < 1) invalid("max_depth must be at least 1");
@@ -92,6 +106,12 @@ struct LambdaMARTParams {
             invalid("split_candidates must be between 2 and 256 for the histogram grower (bins are one byte)");
         if (p.early_stopping_rounds > 0 && p.validation_queries.empty())
             invalid("early_stopping_rounds needs at least one validation query (validation_queries is empty)");
+        if (p.newton && !p.histogram) invalid("split_gain `newton` needs grower: \"histogram\" (the exact grower keeps the random-forest criterion)");
+        const std::pair<const char*, double> numbers[] = {{"lambda_l2", p.lambda_l2}, {"min_sum_hessian", p.min_sum_hessian}, {"min_split_gain", p.min_split_gain}};
+        for (const auto& kv : numbers) {
+            if (!(std::isfinite(kv.second) && kv.second >= 0.0)) invalid(std::string(kv.first) + " must be finite and at least 0");
+            if (kv.second != 0.0 && !p.newton) invalid(std::string(kv.first) + " needs split_gain: \"newton\"");
+        }
         return p;
     }
     Value to_json() const {
@@ -113,6 +133,10 @@ struct LambdaMARTParams {
             o.set("validation_queries", std::move(a));
         }
         if (early_stopping_rounds != 0) o.set("early_stopping_rounds", Value::uint(early_stopping_rounds));
+        if (newton) o.set("split_gain", Value::string("newton"));
+        if (lambda_l2 != 0.0) o.set("lambda_l2", Value::number(lambda_l2));
+        if (min_sum_hessian != 0.0) o.set("min_sum_hessian", Value::number(min_sum_hessian));
+        if (min_split_gain != 0.0) o.set("min_split_gain", Value::number(min_split_gain));
         return o;
     }
 };
@@ -204,6 +228,9 @@ struct LambdaMARTStats {
     bool validation = false, stopped_early = false;
     uint32_t validation_queries = 0, training_queries = 0, best_iteration = 0, early_stopping_rounds = 0;
     std::vector<double> valid_measure;  // evaluator mean of the running scores over the held-out queries after each tree
+    // the Newton gain (reported only under split_gain = "newton"): the request's keys
+    bool newton = false;
+    double lambda_l2 = 0.0, min_sum_hessian = 0.0, min_split_gain = 0.0;
 
     Value to_json() const {
         Value o = Value::object();
@@ -238,6 +265,12 @@ struct LambdaMARTStats {
             o.set("best_valid_measure", Value::number(best_iteration ? valid_measure[best_iteration - 1] : 0.0));
             o.set("stopped_early", Value::boolean(stopped_early));
             o.set("early_stopping_rounds", Value::uint(early_stopping_rounds));
+        }
+        if (newton) {
+            o.set("split_gain", Value::string("newton"));
+            o.set("lambda_l2", Value::number(lambda_l2));
+            o.set("min_sum_hessian", Value::number(min_sum_hessian));
+            o.set("min_split_gain", Value::number(min_split_gain));
         }
         return o;
     }
@@ -280,7 +313,10 @@ class LambdaMARTTrainer {
         stats_.histogram = p_.histogram;
         std::unique_ptr<HistGrower> hist;
         if (p_.histogram) {
-            hist.reset(new HistGrower(dev, feats, p_.split_candidates, p_.max_depth, p_.min_leaf_support));
+            hist.reset(new HistGrower(dev, feats, p_.split_candidates, p_.max_depth, p_.min_leaf_support,
+                                      HistNewton{p_.newton, p_.lambda_l2, p_.min_sum_hessian, p_.min_split_gain}));
+            stats_.newton = p_.newton;
+            stats_.lambda_l2 = p_.lambda_l2, stats_.min_sum_hessian = p_.min_sum_hessian, stats_.min_split_gain = p_.min_split_gain;
             auto tb0 = tnow();
             if (hist->prepare(positions)) stats_.t_bins = secs(tb0, tnow());
             stats_.bins = p_.split_candidates;

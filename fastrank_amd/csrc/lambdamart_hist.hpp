@@ -6,6 +6,9 @@
 // candidates, the later feature among equals.  A level's histograms are built for the smaller child of every split and
 // derived for the larger one (parent - child: integer sums, so exact).  Leaf values come from the leaves' own integer sums:
 // the partition a split trains on (bins 0..j) is the one the scoring rule applies (x <= edge_j), so no routing pass.
+// split_gain = "newton" ("Newton split gain"): the histograms also carry sum W, a candidate's
+// importance is term(L) + term(R) with term = G G / (H + lambda_l2), a node splits only when that exceeds its own term by
+// more than min_split_gain, and leaves are G / (H + lambda_l2).
 #pragma once
 #include <cmath>
 
@@ -13,10 +16,17 @@
 
 namespace fr {
 
+// the Newton gain's numbers (on = false: the variance criterion, and none of them is read)
+struct HistNewton {
+    bool on = false;
+    double lambda_l2 = 0.0, min_sum_hessian = 0.0, min_split_gain = 0.0;
+};
+
 class HistGrower {
   public:
-    HistGrower(frdev::DeviceDataset& dev, std::vector<uint32_t> feats, uint32_t k, uint32_t max_depth, uint32_t min_leaf)
-        : dev_(dev), feats_(std::move(feats)), k_(k), max_depth_(max_depth), min_leaf_(min_leaf) {}
+    HistGrower(frdev::DeviceDataset& dev, std::vector<uint32_t> feats, uint32_t k, uint32_t max_depth, uint32_t min_leaf,
+               HistNewton newton = HistNewton())
+        : dev_(dev), feats_(std::move(feats)), k_(k), max_depth_(max_depth), min_leaf_(min_leaf), newton_(newton) {}
     ~HistGrower() { dev_.hist_end(); }
 
     // bins for the instance list at `positions`; true when they were built now (false: the view's kept ones were reused)
@@ -73,7 +83,7 @@ class HistGrower {
             leaves.push_back({(uint32_t)leaves.size(), b, e});
         };
         if (enterable(n_, 1)) {
-            if (!dev_.hist_root(&err)) fail_str(err);
+            if (!dev_.hist_root(&err, newton_.on)) fail_str(err);
             open.push_back({root.get(), 0u, 0u, n_, 1u});
         } else {
             close(root.get(), 0u, n_);
@@ -82,13 +92,28 @@ class HistGrower {
         auto full = [&](size_t fi) { return sel_.empty() ? fi : (size_t)sel_[fi]; };
         std::vector<Dev::HistNode> nodes, builds;
         std::vector<Dev::HistBest> best;
+        std::vector<Dev::HistBestNewton> best_n;
+        // (G G) / (H + lambda_l2) of an integer pair, every operation rounded on its own
+        auto term = [&](long long q, long long w) {
+            const double g = std::ldexp((double)q, -s_l);
+            return (g * g) / (std::ldexp((double)w, -s_w) + newton_.lambda_l2);
+        };
         std::vector<Dev::HistSplit> splits;
         std::vector<Dev::HistSub> subs;
         bool rooted = !open.empty();
         while (!open.empty()) {
             nodes.clear(), builds.clear(), splits.clear(), subs.clear(), next.clear();
             for (const Open& o : open) nodes.push_back({o.slot, o.begin, o.end});
-            if (!dev_.hist_search(nodes, min_leaf_, &best, &err)) fail_str(err);
+            if (newton_.on) {  // the selection below reads the fields the two records share
+                if (!dev_.hist_search_newton(nodes, min_leaf_, s_l, s_w, newton_.lambda_l2, newton_.min_sum_hessian, &best_n, &err)) fail_str(err);
+                best.resize(best_n.size());
+                for (size_t i = 0; i < best_n.size(); i++) {
+                    const Dev::HistBestNewton& b = best_n[i];
+                    best[i] = {b.imp, b.ql, b.qtot, b.edge, b.nl, b.valid, 0u};
+                }
+            } else if (!dev_.hist_search(nodes, min_leaf_, &best, &err)) {
+                fail_str(err);
+            }
             uint32_t next_slots = 0;
             for (size_t a = 0; a < open.size(); a++) {
                 const Open& o = open[a];
@@ -97,6 +122,10 @@ class HistGrower {
                 for (size_t fi = 0; fi < F; fi++) {  // the last maximum: a later feature wins among equals
                     const Dev::HistBest& b = best[a * F + fi];
                     if (b.valid && (w == nullptr || b.imp >= w->imp)) w = &b, wf = fi;
+                }
+                if (w != nullptr && newton_.on) {  // the node's totals (Qnode, Wnode) arrive with every record of the node
+                    const Dev::HistBestNewton& b = best_n[a * F + wf];
+                    if (!(w->imp - term(b.qtot, b.wtot) > newton_.min_split_gain)) w = nullptr;
                 }
                 if (w == nullptr) {
                     close(o.node, o.begin, o.end);
@@ -127,7 +156,7 @@ class HistGrower {
                 if (el) next.push_back({o.node->lhs.get(), left_small ? small_slot : large_slot, o.begin, mid, o.depth + 1});
                 if (er) next.push_back({o.node->rhs.get(), left_small ? large_slot : small_slot, mid, o.end, o.depth + 1});
             }
-            if (!dev_.hist_split(splits, builds, subs, next_slots, &err)) fail_str(err);
+            if (!dev_.hist_split(splits, builds, subs, next_slots, &err, newton_.on)) fail_str(err);
             open.swap(next);
         }
         auto t0 = std::chrono::steady_clock::now();
@@ -138,7 +167,12 @@ class HistGrower {
         if (!dev_.hist_leaf_sums(leaves, &qw, &err)) fail_str(err);
         for (size_t i = 0; i < leaf_nodes.size(); i++) {
             const long long q = qw[i * 2], w = qw[i * 2 + 1];
-            leaf_nodes[i]->value = w != 0 ? std::ldexp((double)q, -s_l) / std::ldexp((double)w, -s_w) : 0.0;
+            if (newton_.on) {
+                const double den = std::ldexp((double)w, -s_w) + newton_.lambda_l2;
+                leaf_nodes[i]->value = den != 0.0 ? std::ldexp((double)q, -s_l) / den : 0.0;
+            } else {
+                leaf_nodes[i]->value = w != 0 ? std::ldexp((double)q, -s_l) / std::ldexp((double)w, -s_w) : 0.0;
+            }
         }
         if (leaf_seconds) *leaf_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         return root;
@@ -156,6 +190,7 @@ class HistGrower {
     frdev::DeviceDataset& dev_;
     std::vector<uint32_t> feats_;
     uint32_t k_, max_depth_, min_leaf_, n_ = 0, n_full_ = 0;  // n_: the tree's instances (n_full_ of them without a query sample)
+    HistNewton newton_;
     std::vector<uint32_t> sel_;                                // the tree's features as slots of the bins (empty: all)
     std::vector<float> edges_;
     std::vector<uint32_t> nedges_;

@@ -94,7 +94,12 @@ class LambdaMARTParams(_LearnerParams):
     report the measure over the training and the held-out queries after every tree (`train_measure`, `valid_measure`,
     `best_iteration`).  `early_stopping_rounds` = r > 0 (needs a held-out query): training ends r trees after the first
     maximum of `valid_measure`, and the model is the trees up to that maximum.  Both keys are written only when set;
-    `hold_out_queries` makes a split."""
+    `hold_out_queries` makes a split.
+    `split_gain`: "variance" (the default: splits maximise sL^2/nL + sR^2/nR over the gradients) or "newton" (histogram
+    grower only: splits maximise G^2/(H + lambda_l2) over gradient sums G and hessian sums H, leaves are G/(H + lambda_l2)).
+    `lambda_l2`, `min_sum_hessian`, `min_split_gain` (finite, >= 0, default 0.0; only with "newton"): the L2 term, the least
+    hessian mass of a child, and the gain a split must exceed.  The four keys are written only when they differ from their
+    defaults ("Newton split gain")."""
 
     VARIANT: ClassVar[str] = "LambdaMART"
 
@@ -111,9 +116,14 @@ class LambdaMARTParams(_LearnerParams):
     seed: int = 0
     validation_queries: List[str] = dataclasses.field(default_factory=list)
     early_stopping_rounds: int = 0
+    split_gain: str = "variance"
+    lambda_l2: float = 0.0
+    min_sum_hessian: float = 0.0
+    min_split_gain: float = 0.0
 
     _WIRE_DEFAULTS: ClassVar[Dict[str, Any]] = {"grower": "exact", "query_sampling_rate": 1.0, "feature_sampling_rate": 1.0, "seed": 0,
-                                                "validation_queries": [], "early_stopping_rounds": 0}
+                                                "validation_queries": [], "early_stopping_rounds": 0, "split_gain": "variance",
+                                                "lambda_l2": 0.0, "min_sum_hessian": 0.0, "min_split_gain": 0.0}
 
     def to_dict(self) -> Dict[str, Any]:
         wire = dataclasses.asdict(self)

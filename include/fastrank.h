@@ -204,6 +204,14 @@ const CResult *fr_debug_hist_tree_sampled(const CDataset *dataset, uint32_t spli
                                           uint32_t min_leaf_support, const double *lambda, const double *weight,
                                           size_t len, const uint32_t *queries, size_t n_queries,
                                           const uint32_t *features, size_t n_features);
+/* fr_debug_hist_tree_sampled under the Newton split gain ("Newton split gain"): splits by
+ * G^2 / (H + lambda_l2) with the floors min_sum_hessian and min_split_gain, leaves G / (H + lambda_l2); the three
+ * numbers finite and >= 0. */
+const CResult *fr_debug_hist_tree_newton(const CDataset *dataset, uint32_t split_candidates, uint32_t max_depth,
+                                         uint32_t min_leaf_support, const double *lambda, const double *weight,
+                                         size_t len, const uint32_t *queries, size_t n_queries,
+                                         const uint32_t *features, size_t n_features, double lambda_l2,
+                                         double min_sum_hessian, double min_split_gain);
 /* Full per-query rank order under the reference's total order (src/evaluators.rs:34-49):
  * out_instance_ids[n] grouped by query (device query order), best first; out_offsets[nq+1]. */
 const void *fr_rank_order(const CModel *model, const CDataset *dataset, uint32_t *out_instance_ids,

@@ -8,6 +8,8 @@
                                                                # a held-out tenth of the queries, stop 10 trees after its best
     python tools/lmbench.py --shape 30k --cpu-baseline 0.01    # the numpy restatement (tests/lambdamart_model.py) timed on
                                                                # a query sample, scaled to the full shape (labelled as such)
+    python tools/lmbench.py --shape 30k --trees 100 --grower histogram --split-gain newton --lambda-l2 1
+                                                               # the second-order split gain with an L2 term
 Every other parameter is the LambdaMART default (TrainRequest.lambdamart()).
 """
 import argparse
@@ -44,6 +46,8 @@ def device_run(args, X, y, qid):
 
         req.params.validation_queries = hold_out_queries(ds.queries(), args.validation_rate, args.seed)
     req.params.early_stopping_rounds = args.early_stopping_rounds
+    req.params.split_gain = args.split_gain
+    req.params.lambda_l2, req.params.min_sum_hessian, req.params.min_split_gain = args.lambda_l2, args.min_sum_hessian, args.min_split_gain
     # upload and first touch of the device (not part of training)
     native.device_info(ds)
     t_ds = time.perf_counter() - t0
@@ -117,6 +121,10 @@ def main():
     ap.add_argument("--seed", type=int, default=0, help="master seed of the per-tree samples")
     ap.add_argument("--validation-rate", type=float, default=0.0, help="share of the queries held out (hold_out_queries under --seed; 0: none)")
     ap.add_argument("--early-stopping-rounds", type=int, default=0, help="stop this many trees after the held-out measure's best (0: never)")
+    ap.add_argument("--split-gain", default="variance", choices=["variance", "newton"], help="the split criterion (newton: histogram grower only)")
+    ap.add_argument("--lambda-l2", type=float, default=0.0, help="L2 term of the Newton gain and leaves")
+    ap.add_argument("--min-sum-hessian", type=float, default=0.0, help="least hessian mass of a child under the Newton gain")
+    ap.add_argument("--min-split-gain", type=float, default=0.0, help="gain a split must exceed under the Newton gain")
     ap.add_argument("--cpu-baseline", type=float, default=0.0, help="query fraction for the CPU restatement (0: device run)")
     args = ap.parse_args()
     n, d, q, seed = SHAPES[args.shape]
