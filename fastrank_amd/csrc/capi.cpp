@@ -1523,12 +1523,12 @@ const CResult* fr_debug_hist_tree(const CDataset* dataset, uint32_t split_candid
     });
 }
 
-// The body of the two sampled hooks below.  who: the exported function's name, for its error messages; newton: the split
-// criterion the grower is made with (HistNewton(): the variance criterion).
+// The body of the sampled hooks below.  who: the exported function's name, for its error messages; newton: the split
+// criterion the grower is made with (HistNewton(): the variance criterion); max_leaves: 0 = level-wise growth.
 static const CResult* hist_tree_debug(const std::string& who, const CDataset* dataset, uint32_t split_candidates, uint32_t max_depth,
                                       uint32_t min_leaf_support, const double* lambda, const double* weight, size_t len,
                                       const uint32_t* queries, size_t n_queries, const uint32_t* features, size_t n_features,
-                                      const fr::HistNewton& newton) {
+                                      const fr::HistNewton& newton, uint32_t max_leaves = 0) {
     return c_call<CModel>([&]() {
         const CDataset& ds = require_dataset(dataset);
         if (!lambda || !weight) fr::fail_str("NULL pointer: gradient inputs");
@@ -1569,7 +1569,7 @@ static const CResult* hist_tree_debug(const std::string& who, const CDataset* da
                 wt[g] = weight[ids[g]];
             }
         }
-        fr::HistGrower grower(view.device(), feats, split_candidates, max_depth, min_leaf_support, newton);
+        fr::HistGrower grower(view.device(), feats, split_candidates, max_depth, min_leaf_support, newton, max_leaves);
         grower.prepare(positions);
         struct Unsample {  // (the bins stay with the view: leave them without a sample, also when growing fails)
             fr::HistGrower& g;
@@ -1613,6 +1613,23 @@ const CResult* fr_debug_hist_tree_newton(const CDataset* dataset, uint32_t split
             return c_call<CModel>([&]() -> CModel* { fr::fail_str("fr_debug_hist_tree_newton: lambda_l2, min_sum_hessian and min_split_gain must be finite and at least 0"); });
     return hist_tree_debug("fr_debug_hist_tree_newton", dataset, split_candidates, max_depth, min_leaf_support, lambda, weight, len, queries,
                            n_queries, features, n_features, fr::HistNewton{true, lambda_l2, min_sum_hessian, min_split_gain});
+}
+
+// One tree grown leaf-wise ("Leaf-wise growth"): fr_debug_hist_tree_sampled / _newton (newton != 0: the
+// three numbers are read) under a leaf budget max_leaves >= 2.
+const CResult* fr_debug_hist_tree_leafwise(const CDataset* dataset, uint32_t split_candidates, uint32_t max_depth, uint32_t min_leaf_support,
+                                           const double* lambda, const double* weight, size_t len, const uint32_t* queries,
+                                           size_t n_queries, const uint32_t* features, size_t n_features, int newton, double lambda_l2,
+                                           double min_sum_hessian, double min_split_gain, uint32_t max_leaves) {
+    if (max_leaves < 2)
+        return c_call<CModel>([&]() -> CModel* { fr::fail_str("fr_debug_hist_tree_leafwise: max_leaves must be at least 2"); });
+    const double numbers[3] = {lambda_l2, min_sum_hessian, min_split_gain};
+    for (double x : numbers)
+        if (!(std::isfinite(x) && x >= 0.0) || (!newton && x != 0.0))
+            return c_call<CModel>([&]() -> CModel* { fr::fail_str("fr_debug_hist_tree_leafwise: lambda_l2, min_sum_hessian and min_split_gain must be finite and at least 0, and 0 without the Newton gain"); });
+    return hist_tree_debug("fr_debug_hist_tree_leafwise", dataset, split_candidates, max_depth, min_leaf_support, lambda, weight, len, queries,
+                           n_queries, features, n_features,
+                           newton ? fr::HistNewton{true, lambda_l2, min_sum_hessian, min_split_gain} : fr::HistNewton(), max_leaves);
 }
 
 const void* fr_evaluate_dense(const CModel* model, const CDataset* dataset, const CQRel* qrel,

@@ -360,7 +360,19 @@ class DeviceDataset {
     bool hist_split(const std::vector<HistSplit>& splits, const std::vector<HistNode>& builds, const std::vector<HistSub>& subs,
                     uint32_t next_slots, std::string* err, bool newton = false);
     bool hist_leaf_sums(const std::vector<HistNode>& leaves, std::vector<long long>* qw /*[leaf][2]*/, std::string* err);
-    void hist_end();  // frees the level histograms (the bins stay)
+    void hist_end();  // frees the level histograms and the leaf-wise pool (the bins stay)
+    // Leaf-wise growth ("Leaf-wise growth"): a pool of `slots` histograms replaces the level arrays, one leaf is split per
+    // step and one record per searched node comes back (hist_pick_kernel reduces the features on the device).
+    struct HistPick { double imp; long long ql, qtot, wl, wtot; uint32_t edge, nl, valid, fi; };  // fi: index among the tree's features
+    struct HistLeafSearch { uint32_t min_leaf; bool newton; int s_l, s_w; double lambda_l2, min_sum_hessian; };
+    // index list = the sample's root list; the root's histogram into slot 0 of a fresh pool; *root: the root's record
+    bool hist_leaf_begin(uint32_t slots, const HistLeafSearch& how, HistPick* root, std::string* err);
+    // One split step: the stable partition of split's stretch alone; then, when small_slot != HIST_NO_SLOT, the smaller child's
+    // histogram is built into small_slot; a searched larger child is derived in place in parent_slot (parent - smaller) and a
+    // searched child is scanned.  pick[0]: the lhs's record, pick[1]: the rhs's (written for the searched ones only).
+    static constexpr uint32_t HIST_NO_SLOT = 0xffffffffu;
+    struct HistLeafStep { HistSplit split; uint32_t parent_slot, small_slot; bool search_lhs, search_rhs; };
+    bool hist_leaf_step(const HistLeafStep& step, const HistLeafSearch& how, HistPick pick[2], std::string* err);
 
     int take_flags();  // returns and clears the accumulated kernel error bits
 

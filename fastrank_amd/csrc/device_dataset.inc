@@ -314,6 +314,12 @@ struct DeviceDataset::Impl {
         DevBuf<uint32_t> cnt, cnt_o;  // level histograms [slot][F][k]: this level's, and the next one's while it is built
         DevBuf<unsigned long long> sum, sum_o;
         DevBuf<unsigned long long> wsum, wsum_o;  // sum W per (feature, bin): the Newton gain's levels only
+        // leaf-wise growth: the pool [slot][Ft][k] of pool_slots histograms (pwsum: under the Newton gain), the per-feature
+        // records of the (at most two) children a step scans and their two picks
+        DevBuf<uint32_t> pcnt;
+        DevBuf<unsigned long long> psum, pwsum;
+        uint32_t pool_slots = 0;
+        DevBuf<HistPickDev> rec, pick;
         DevBuf<HistItemDev> items, items_b, nodes;  // (items: partition and leaf sums; items_b: histogram builds)
         DevBuf<HistSplitDev> splits;
         DevBuf<HistSubDev> subs;
@@ -328,6 +334,8 @@ struct DeviceDataset::Impl {
     bool hist_qof(std::string* err);
     void hist_build(uint32_t* cnt, unsigned long long* sum);  // hist_build_kernel over hist.items_b into a level's histograms
     void hist_build_newton(uint32_t* cnt, unsigned long long* sum, unsigned long long* wsum);
+    bool hist_leaf_scan(const HistLeafKids& kids, uint32_t count, const DeviceDataset::HistLeafSearch& how, DeviceDataset::HistPick* out,
+                        std::string* err);
     DevBuf<uint64_t> forest;
     DevBuf<uint32_t> tree_fdesc;  // tree_ensemble_rank_kernel: per-feature descriptors, Eytzinger threshold tables
     DevBuf<float> tree_tables;
@@ -4515,4 +4523,135 @@ void DeviceDataset::hist_end() {
     auto& h = m.hist;
     (void)hipStreamSynchronize(m.stream);
     h.cnt.release(), h.cnt_o.release(), h.sum.release(), h.sum_o.release(), h.wsum.release(), h.wsum_o.release(), h.best.release(), h.best_n.release(), h.lam_in.release(), h.wt_in.release();
+    h.pcnt.release(), h.psum.release(), h.pwsum.release(), h.rec.release(), h.pick.release();
+    h.pool_slots = 0;
+}
+
+// --- leaf-wise growth (kernels_hist.inc, "Leaf-wise growth") ---
+
+// scan (after deriving where asked) and pick of `count` children, their records to out[0..count); waits for the stream
+bool DeviceDataset::Impl::hist_leaf_scan(const HistLeafKids& kids, uint32_t count, const DeviceDataset::HistLeafSearch& how,
+                                         DeviceDataset::HistPick* out, std::string* err) {
+    static_assert(sizeof(DeviceDataset::HistPick) == sizeof(HistPickDev), "host and device records differ");
+    auto& h = hist;
+    if (!h.rec.ensure((size_t)2 * h.Ft, err) || !h.pick.ensure(2, err)) return false;
+    const uint32_t* fsel = h.f_sampled ? h.fsel.p : nullptr;
+    {
+        ProfScope ps(how.newton ? "hist_leaf_scan_kernel<newton>" : "hist_leaf_scan_kernel", stream);
+        const dim3 grid(h.Ft, count);
+        if (how.newton)
+            hist_leaf_scan_kernel<true><<<grid, 64, 0, stream>>>(kids, h.Ft, h.k, h.nedges.p, fsel, h.pcnt.p, h.psum.p, h.pwsum.p, how.min_leaf,
+                                                                 how.s_l, how.s_w, how.lambda_l2, how.min_sum_hessian, h.rec.p);
+        else
+            hist_leaf_scan_kernel<false><<<grid, 64, 0, stream>>>(kids, h.Ft, h.k, h.nedges.p, fsel, h.pcnt.p, h.psum.p, nullptr, how.min_leaf, 0, 0,
+                                                                  0.0, 0.0, h.rec.p);
+    }
+    {
+        ProfScope ps("hist_pick_kernel", stream);
+        hist_pick_kernel<<<count, 64, 0, stream>>>(h.rec.p, h.Ft, h.pick.p);
+    }
+    FR_HIP(hipGetLastError());
+    FR_HIP(hipMemcpyAsync(out, h.pick.p, count * sizeof(HistPickDev), hipMemcpyDeviceToHost, stream));
+    FR_HIP(hipStreamSynchronize(stream));
+    return true;
+}
+
+bool DeviceDataset::hist_leaf_begin(uint32_t slots, const HistLeafSearch& how, HistPick* root, std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    if (h.k == 0) return hist_fail(err, "no bins built");
+    if (slots == 0) return hist_fail(err, "internal error: an empty histogram pool");
+    const uint32_t n = h.nt;
+    const size_t fk = (size_t)h.Ft * h.k, cells = (size_t)slots * fk;
+    if (!h.idx.ensure(h.n, err) || !h.idx_o.ensure(h.n, err) || !h.flag.ensure(h.n, err) || !h.scan.ensure(h.n, err)) return false;
+    {
+        std::string e2;
+        if (!h.pcnt.ensure(cells, &e2) || !h.psum.ensure(cells, &e2) || (how.newton && !h.pwsum.ensure(cells, &e2))) {
+            (void)hipGetLastError();
+            h.pool_slots = 0;
+            return hist_fail(err, "no device memory for the leaf-wise histogram pool (" + std::to_string((cells * (how.newton ? 20 : 12)) >> 20) +
+                                      " MB: max_leaves x features x bins x " + (how.newton ? "20" : "12") + " bytes); lower max_leaves or split_candidates");
+        }
+    }
+    h.pool_slots = slots;
+    FR_HIP(hipMemsetAsync(h.pcnt.p, 0, fk * sizeof(uint32_t), m.stream));
+    FR_HIP(hipMemsetAsync(h.psum.p, 0, fk * sizeof(unsigned long long), m.stream));
+    if (how.newton) FR_HIP(hipMemsetAsync(h.pwsum.p, 0, fk * sizeof(unsigned long long), m.stream));
+    if (h.q_sampled) {
+        FR_HIP(hipMemcpyAsync(h.idx.p, h.root.p, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, m.stream));
+    } else {
+        hist_iota_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(h.idx.p, n);
+    }
+    if (!m.hist_items({{0u, 0u, n}}, h.items_bh, h.items_b, err)) return false;
+    if (how.newton) m.hist_build_newton(h.pcnt.p, h.psum.p, h.pwsum.p);
+    else m.hist_build(h.pcnt.p, h.psum.p);
+    FR_HIP(hipGetLastError());
+    HistLeafKids kids{};
+    kids.slot[0] = 0, kids.n[0] = n;
+    return m.hist_leaf_scan(kids, 1, how, root, err);
+}
+
+bool DeviceDataset::hist_leaf_step(const HistLeafStep& step, const HistLeafSearch& how, HistPick pick[2], std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    const HistSplit& s = step.split;
+    const size_t fk = (size_t)h.Ft * h.k;
+    const bool build = step.small_slot != HIST_NO_SLOT;
+    if (s.begin >= s.end || s.end > h.nt || s.nl == 0 || s.nl >= s.end - s.begin || s.fslot >= h.F || s.edge >= h.k)
+        return hist_fail(err, "internal error: a split outside the index list");
+    if (h.pool_slots == 0 || step.parent_slot >= h.pool_slots || (build && (step.small_slot >= h.pool_slots || step.small_slot == step.parent_slot)) ||
+        ((step.search_lhs || step.search_rhs) && !build))
+        return hist_fail(err, "internal error: a step outside the histogram pool");
+    const uint32_t n = s.end - s.begin, nr = n - s.nl;
+    {
+        ProfScope ps("hist_leaf_partition", m.stream);
+        const dim3 g = grid1d(n, 256);
+        hist_leaf_flag_kernel<<<g, 256, 0, m.stream>>>(s.begin, s.end, h.xbin.p + (size_t)s.fslot * h.n, s.edge, h.idx.p, h.flag.p);
+        size_t tb = 0;
+        FR_HIP(rocprim::exclusive_scan(nullptr, tb, h.flag.p + s.begin, h.scan.p + s.begin, 0u, (size_t)n, rocprim::plus<uint32_t>(), m.stream));
+        if (tb > h.temp.bytes()) {
+            FR_HIP(hipStreamSynchronize(m.stream));
+            if (!h.temp.ensure(tb, err)) return false;
+        }
+        FR_HIP(rocprim::exclusive_scan((void*)h.temp.p, tb, h.flag.p + s.begin, h.scan.p + s.begin, 0u, (size_t)n, rocprim::plus<uint32_t>(), m.stream));
+        hist_leaf_scatter_kernel<<<g, 256, 0, m.stream>>>(s.begin, s.end, s.nl, h.flag.p, h.scan.p, h.idx.p, h.idx_o.p);
+        FR_HIP(hipMemcpyAsync(h.idx.p + s.begin, h.idx_o.p + s.begin, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, m.stream));
+        FR_HIP(hipGetLastError());
+    }
+    if (!build) return true;
+    // the smaller child from its stretch (the lhs when the two are equal)
+    const bool left_small = s.nl <= nr;
+    const size_t off = (size_t)step.small_slot * fk;
+    FR_HIP(hipMemsetAsync(h.pcnt.p + off, 0, fk * sizeof(uint32_t), m.stream));
+    FR_HIP(hipMemsetAsync(h.psum.p + off, 0, fk * sizeof(unsigned long long), m.stream));
+    if (how.newton) FR_HIP(hipMemsetAsync(h.pwsum.p + off, 0, fk * sizeof(unsigned long long), m.stream));
+    const uint32_t mid = s.begin + s.nl;
+    if (!m.hist_items({left_small ? HistItemDev{step.small_slot, s.begin, mid} : HistItemDev{step.small_slot, mid, s.end}}, h.items_bh, h.items_b, err))
+        return false;
+    if (how.newton) m.hist_build_newton(h.pcnt.p, h.psum.p, h.pwsum.p);
+    else m.hist_build(h.pcnt.p, h.psum.p);
+    FR_HIP(hipGetLastError());
+    // the children to scan, the lhs first; the larger one is derived in place in its parent's slot
+    HistLeafKids kids{};
+    uint32_t count = 0;
+    int where[2] = {-1, -1};
+    for (int side = 0; side < 2; side++) {
+        if (!(side == 0 ? step.search_lhs : step.search_rhs)) continue;
+        const bool small = (side == 0) == left_small;
+        kids.slot[count] = small ? step.small_slot : step.parent_slot;
+        kids.n[count] = side == 0 ? s.nl : nr;
+        kids.derive[count] = small ? 0u : 1u;
+        kids.other[count] = step.small_slot;
+        where[side] = (int)count++;
+    }
+    if (count == 0) return true;
+    HistPick got[2];
+    if (!m.hist_leaf_scan(kids, count, how, got, err)) return false;
+    for (int side = 0; side < 2; side++)
+        if (where[side] >= 0) pick[side] = got[where[side]];
+    return true;
 }

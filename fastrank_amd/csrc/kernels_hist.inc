@@ -548,3 +548,164 @@ __global__ __launch_bounds__(64) void hist_scan_newton_kernel(const HistItemDev*
         *out = HistBestNewtonDev{bimp, bql, qtot, bwl, wtot, bj, bnl, 1u, 0u};
     }
 }
+
+// --- Leaf-wise growth (DESIGN.md section 11, "Leaf-wise growth") ---------------------------------------------------------
+// max_leaves >= 2: one leaf is split at a time, the open leaf with the largest gain.  The histograms live in a pool of slots
+// [slot][F][k] (the same three arrays; wsum only under the Newton gain); the larger child takes over its parent's slot, the
+// subtraction happens in place.  One split step works on one stretch, so the stretch and the slots are kernel arguments and
+// no table is uploaded but the build kernel's items.  The kernels above keep their code; these run only for max_leaves >= 2.
+//
+//   hist_leaf_flag_kernel / (rocPRIM exclusive scan of the stretch) / hist_leaf_scatter_kernel
+//                           stable partition of the one stretch [begin, end)
+//   hist_leaf_scan_kernel   one wave per (child, feature): a child marked `derive` is first made in place, parent - sibling,
+//                           then scanned; the arithmetic of a candidate is hist_scan_kernel's / hist_scan_newton_kernel's
+//   hist_pick_kernel        one wave per child: its F per-feature records reduced to the node's single one, the last maximum
+//                           over the tree's feature order, and the winning feature's index among the F
+
+struct HistPickDev {
+    double imp;
+    long long ql, qtot, wl, wtot;  // (wl, wtot: 0 under the variance criterion)
+    uint32_t edge, nl, valid, fi;  // fi: the winning feature's index among the tree's F
+};
+// the (at most two) children a step scans: derive != 0: slot (the parent's) becomes parent - slot `other` first
+struct HistLeafKids {
+    uint32_t slot[2], n[2], derive[2], other[2];
+};
+
+__global__ __launch_bounds__(256) void hist_leaf_flag_kernel(uint32_t begin, uint32_t end, const uint8_t* __restrict__ col, uint32_t edge,
+                                                             const uint32_t* __restrict__ idx, uint32_t* __restrict__ flag) {
+    const uint32_t i = begin + blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < end) flag[i] = col[idx[i]] <= edge ? 1u : 0u;
+}
+
+// scan[begin..end) = exclusive prefix sums of flag[begin..end) (0 at begin)
+__global__ __launch_bounds__(256) void hist_leaf_scatter_kernel(uint32_t begin, uint32_t end, uint32_t nl, const uint32_t* __restrict__ flag,
+                                                                const uint32_t* __restrict__ scan, const uint32_t* __restrict__ idx,
+                                                                uint32_t* __restrict__ out) {
+    const uint32_t i = begin + blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= end) return;
+    const uint32_t lb = scan[i];  // left-goers before i in the node
+    const uint32_t d = flag[i] ? begin + lb : begin + nl + (i - begin - lb);
+    if (d < end) out[d] = idx[i];
+}
+
+// grid (F, children).  rec[child * F + f]
+template <bool NEWTON>
+__global__ __launch_bounds__(64) void hist_leaf_scan_kernel(HistLeafKids kids, uint32_t F, uint32_t k, const uint32_t* __restrict__ nedges,
+                                                            const uint32_t* __restrict__ fsel, uint32_t* cnt, unsigned long long* sum,
+                                                            unsigned long long* wsum, uint32_t min_leaf, int s_l, int s_w, double l2,
+                                                            double min_hess, HistPickDev* __restrict__ rec) {
+    const uint32_t f = blockIdx.x, a = blockIdx.y, lane = threadIdx.x;
+    const uint32_t n = kids.n[a];
+    const uint32_t ne = min(nedges[fsel ? fsel[f] : f], k - 1);
+    const size_t base = ((size_t)kids.slot[a] * F + f) * k, obase = ((size_t)kids.other[a] * F + f) * k;
+    const bool derive = kids.derive[a] != 0;
+    const uint32_t B = (k + 63) / 64;  // bins per lane (<= 4)
+    uint32_t c[4];
+    long long s[4], w[4];
+    uint32_t tc = 0;
+    long long ts = 0, tw = 0;
+    for (uint32_t u = 0; u < 4; u++) {
+        const uint32_t b = lane * B + u;
+        const bool in = u < B && b < k;
+        c[u] = in ? cnt[base + b] : 0u;
+        s[u] = in ? (long long)sum[base + b] : 0ll;
+        w[u] = NEWTON && in ? (long long)wsum[base + b] : 0ll;
+        if (derive && in) {  // (this wave alone reads and writes the bins of (slot, f))
+            c[u] -= cnt[obase + b];
+            s[u] -= (long long)sum[obase + b];
+            cnt[base + b] = c[u];
+            sum[base + b] = (unsigned long long)s[u];
+            if (NEWTON) {
+                w[u] -= (long long)wsum[obase + b];
+                wsum[base + b] = (unsigned long long)w[u];
+            }
+        }
+        tc += c[u];
+        ts += s[u];
+        tw += w[u];
+    }
+    uint32_t ic = tc;
+    long long is = ts, iw = tw;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t oc = __shfl_up(ic, o);
+        const long long os = __shfl_up(is, o), ow = __shfl_up(iw, o);
+        if ((int)lane >= o) {
+            ic += oc;
+            is += os;
+            iw += ow;
+        }
+    }
+    const long long qtot = __shfl(is, 63), wtot = __shfl(iw, 63);
+    uint32_t rc = ic - tc;  // counts / sums of the bins before this lane's
+    long long rs = is - ts, rw = iw - tw;
+    double bimp = 0.0;
+    uint32_t bj = 0, bnl = 0, have = 0;
+    long long bql = 0, bwl = 0;
+    for (uint32_t u = 0; u < B; u++) {
+        const uint32_t j = lane * B + u;
+        rc += c[u];
+        rs += s[u];
+        rw += w[u];
+        if (j >= ne) break;
+        const uint32_t nl = rc, nr = n - rc;
+        if (nl == 0 || nr == 0 || nl < min_leaf || nr < min_leaf) continue;
+        double imp;
+        if (NEWTON) {
+            const double hl = ldexp((double)rw, -s_w), hr = ldexp((double)(wtot - rw), -s_w);
+            if (!(hl >= min_hess && hr >= min_hess && hl + l2 > 0.0 && hr + l2 > 0.0)) continue;
+            imp = hist_newton_term(rs, hl, s_l, l2) + hist_newton_term(qtot - rs, hr, s_l, l2);
+        } else {
+            const double sl = (double)rs, sr = (double)(qtot - rs);
+            imp = (sl * sl) / (double)nl + (sr * sr) / (double)nr;
+        }
+        if (!have || imp >= bimp) {
+            have = 1;
+            bimp = imp;
+            bj = j;
+            bnl = nl;
+            bql = rs;
+            bwl = rw;
+        }
+    }
+    // the last maximum over the lanes: larger importance, then the later edge
+    double wimp = bimp;
+    uint32_t wj = bj, whave = have;
+    for (int o = 32; o > 0; o >>= 1) {
+        const double oimp = __shfl_xor(wimp, o);
+        const uint32_t oj = __shfl_xor(wj, o), ohave = __shfl_xor(whave, o);
+        if (ohave && (!whave || oimp > wimp || (oimp == wimp && oj > wj))) {
+            whave = 1;
+            wimp = oimp;
+            wj = oj;
+        }
+    }
+    HistPickDev* out = rec + (size_t)a * F + f;
+    if (!whave) {
+        if (lane == 0) *out = HistPickDev{0.0, 0ll, qtot, 0ll, wtot, 0u, 0u, 0u, f};
+    } else if (have && bj == wj) {
+        *out = HistPickDev{bimp, bql, qtot, bwl, wtot, bj, bnl, 1u, f};
+    }
+}
+
+// grid (children).  pick[a] = the last maximum of rec[a * F .. a * F + F): larger importance, then the later feature; a node
+// without a valid record keeps valid = 0 and its totals
+__global__ __launch_bounds__(64) void hist_pick_kernel(const HistPickDev* __restrict__ rec, uint32_t F, HistPickDev* __restrict__ pick) {
+    const uint32_t a = blockIdx.x, lane = threadIdx.x;
+    const HistPickDev* r = rec + (size_t)a * F;
+    double wimp = 0.0;
+    uint32_t wf = 0, whave = 0;
+    for (uint32_t f = lane; f < F; f += 64) {  // ascending: >= keeps the later one
+        if (r[f].valid && (!whave || r[f].imp >= wimp)) whave = 1, wimp = r[f].imp, wf = f;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const double oimp = __shfl_xor(wimp, o);
+        const uint32_t of = __shfl_xor(wf, o), ohave = __shfl_xor(whave, o);
+        if (ohave && (!whave || oimp > wimp || (oimp == wimp && of > wf))) {
+            whave = 1;
+            wimp = oimp;
+            wf = of;
+        }
+    }
+    if (lane == 0) pick[a] = r[whave ? wf : 0];
+}

@@ -21,6 +21,8 @@
 // after the held-out measure's first maximum and returns the trees up to it.
 // split_gain = "newton" (histogram grower only; DESIGN.md section 11, "Newton split gain"): splits are placed by the
 // second-order gain G^2 / (H + lambda_l2) with the floors min_sum_hessian and min_split_gain, leaves are G / (H + lambda_l2).
+// max_leaves >= 2 (histogram grower only; DESIGN.md section 11, "Leaf-wise growth"): a tree is grown leaf by leaf, the open
+// leaf with the largest gain first, until it has max_leaves leaves; 0 (the default) is level-wise growth.
 #pragma once
 #include <chrono>
 #include <cmath>
@@ -53,6 +55,8 @@ struct LambdaMARTParams {
     // the three numbers are read only under "newton"
     bool newton = false;
     double lambda_l2 = 0.0, min_sum_hessian = 0.0, min_split_gain = 0.0;
+    // the leaf budget of leaf-wise growth (optional key, not written at its default): 0 = level-wise growth
+    uint32_t max_leaves = 0;
 
     bool sampling() const { return query_sampling_rate < 1.0 || feature_sampling_rate < 1.0; }
     [[noreturn]] static void invalid(const std::string& what) {
@@ -94,6 +98,7 @@ struct LambdaMARTParams {
         if (const Value* r = v.find("lambda_l2")) p.lambda_l2 = json_f64(*r, "lambda_l2");
         if (const Value* r = v.find("min_sum_hessian")) p.min_sum_hessian = json_f64(*r, "min_sum_hessian");
         if (const Value* r = v.find("min_split_gain")) p.min_split_gain = json_f64(*r, "min_split_gain");
+        if (const Value* r = v.find("max_leaves")) p.max_leaves = json_u32(*r, "max_leaves");
         if (p.num_trees < 1) invalid("num_trees must be at least 1");
         if (!(std::isfinite(p.learning_rate) && p.learning_rate > 0.0)) invalid("learning_rate must be finite and greater than 0");
         if (p.max_depth < 1) invalid("max_depth must be at least 1");
@@ -112,6 +117,8 @@ struct LambdaMARTParams {
             if (!(std::isfinite(kv.second) && kv.second >= 0.0)) invalid(std::string(kv.first) + " must be finite and at least 0");
             if (kv.second != 0.0 && !p.newton) invalid(std::string(kv.first) + " needs split_gain: \"newton\"");
         }
+        if (p.max_leaves == 1) invalid("max_leaves must be 0 (level-wise) or at least 2");
+        if (p.max_leaves >= 2 && !p.histogram) invalid("max_leaves needs grower: \"histogram\" (the exact grower grows level by level)");
         return p;
     }
     Value to_json() const {
@@ -137,6 +144,7 @@ struct LambdaMARTParams {
         if (lambda_l2 != 0.0) o.set("lambda_l2", Value::number(lambda_l2));
         if (min_sum_hessian != 0.0) o.set("min_sum_hessian", Value::number(min_sum_hessian));
         if (min_split_gain != 0.0) o.set("min_split_gain", Value::number(min_split_gain));
+        if (max_leaves != 0) o.set("max_leaves", Value::uint(max_leaves));
         return o;
     }
 };
@@ -231,6 +239,9 @@ struct LambdaMARTStats {
     // the Newton gain (reported only under split_gain = "newton"): the request's keys
     bool newton = false;
     double lambda_l2 = 0.0, min_sum_hessian = 0.0, min_split_gain = 0.0;
+    // leaf-wise growth (reported only when max_leaves is set): the request's key and the trees' mean number of leaves
+    uint32_t max_leaves = 0;
+    uint64_t sum_leaves = 0, pool_bytes = 0;  // pool_bytes: the histogram pool (slots x the tree's features x bins x 12 or 20 B), the largest over the trees
 
     Value to_json() const {
         Value o = Value::object();
@@ -271,6 +282,11 @@ struct LambdaMARTStats {
             o.set("lambda_l2", Value::number(lambda_l2));
             o.set("min_sum_hessian", Value::number(min_sum_hessian));
             o.set("min_split_gain", Value::number(min_split_gain));
+        }
+        if (max_leaves != 0) {
+            o.set("max_leaves", Value::uint(max_leaves));
+            o.set("mean_leaves", Value::number((double)sum_leaves / (trees ? (double)trees : 1.0)));
+            o.set("pool_bytes", Value::uint(pool_bytes));
         }
         return o;
     }
@@ -314,7 +330,8 @@ class LambdaMARTTrainer {
         std::unique_ptr<HistGrower> hist;
         if (p_.histogram) {
             hist.reset(new HistGrower(dev, feats, p_.split_candidates, p_.max_depth, p_.min_leaf_support,
-                                      HistNewton{p_.newton, p_.lambda_l2, p_.min_sum_hessian, p_.min_split_gain}));
+                                      HistNewton{p_.newton, p_.lambda_l2, p_.min_sum_hessian, p_.min_split_gain}, p_.max_leaves));
+            stats_.max_leaves = p_.max_leaves;
             stats_.newton = p_.newton;
             stats_.lambda_l2 = p_.lambda_l2, stats_.min_sum_hessian = p_.min_sum_hessian, stats_.min_split_gain = p_.min_split_gain;
             auto tb0 = tnow();
@@ -409,7 +426,8 @@ class LambdaMARTTrainer {
                 else hist->set_sample(sample_q ? qflags.data() : nullptr, t_n, sample_f ? &smp.features : nullptr);
             }
             double leaf_secs = 0.0;
-            std::shared_ptr<TreeNode> root = hist ? hist->grow(nullptr, nullptr, &leaf_secs)
+            uint32_t n_leaves = 0;
+            std::shared_ptr<TreeNode> root = hist ? hist->grow(nullptr, nullptr, &leaf_secs, &n_leaves)
                                                   : grower.grow_lambda_tree(dev, *off_t, *ids_t, *feats_t, pos_t, rst);
             auto tc = tnow() - std::chrono::duration_cast<std::chrono::steady_clock::duration>(std::chrono::duration<double>(leaf_secs));
             // leaves (exact grower): route every instance through a copy of the tree whose leaves hold their index
@@ -453,6 +471,8 @@ class LambdaMARTTrainer {
             stats_.t_grow += secs(ts, ta) + secs(tb, tc);
             stats_.t_leaves += secs(tc, td);
             stats_.t_update += secs(td, te);
+            stats_.sum_leaves += n_leaves;
+            if (hist) stats_.pool_bytes = hist->pool_bytes();
             stats_.train_measure.push_back(mean);
             out.members.push_back(std::move(tm));
             out.ens_weights.push_back(p_.learning_rate);

@@ -9,7 +9,11 @@
 // split_gain = "newton" ("Newton split gain"): the histograms also carry sum W, a candidate's
 // importance is term(L) + term(R) with term = G G / (H + lambda_l2), a node splits only when that exceeds its own term by
 // more than min_split_gain, and leaves are G / (H + lambda_l2).
+// max_leaves >= 2 ("Leaf-wise growth"): the tree is grown one leaf at a time instead, always the open
+// leaf whose best split gains most, until it has max_leaves leaves; the device keeps a pool of histograms, one per open
+// leaf, and returns one record per searched node (grow_leaves below).  max_leaves = 0 is the level loop, untouched.
 #pragma once
+#include <algorithm>
 #include <cmath>
 
 #include "host.hpp"
@@ -25,8 +29,8 @@ struct HistNewton {
 class HistGrower {
   public:
     HistGrower(frdev::DeviceDataset& dev, std::vector<uint32_t> feats, uint32_t k, uint32_t max_depth, uint32_t min_leaf,
-               HistNewton newton = HistNewton())
-        : dev_(dev), feats_(std::move(feats)), k_(k), max_depth_(max_depth), min_leaf_(min_leaf), newton_(newton) {}
+               HistNewton newton = HistNewton(), uint32_t max_leaves = 0)
+        : dev_(dev), feats_(std::move(feats)), k_(k), max_depth_(max_depth), min_leaf_(min_leaf), newton_(newton), max_leaves_(max_leaves) {}
     ~HistGrower() { dev_.hist_end(); }
 
     // bins for the instance list at `positions`; true when they were built now (false: the view's kept ones were reused)
@@ -62,15 +66,26 @@ class HistGrower {
     }
 
     // One tree for the gradients of the last gradient pass (lam_list == nullptr) or for lam_list / wt_list[n] in
-    // instance-list order.  *leaf_seconds: the share of the leaf sums.
-    std::shared_ptr<TreeNode> grow(const double* lam_list, const double* wt_list, double* leaf_seconds = nullptr) {
+    // instance-list order.  *leaf_seconds: the share of the leaf sums.  *n_leaves: the tree's number of leaves.
+    std::shared_ptr<TreeNode> grow(const double* lam_list, const double* wt_list, double* leaf_seconds = nullptr, uint32_t* n_leaves = nullptr) {
         using Dev = frdev::DeviceDataset;
         std::string err;
         int s_l = 0, s_w = 0;
         bool all_zero = false;
         if (!dev_.hist_quantise(lam_list, wt_list, &s_l, &s_w, &all_zero, &err)) fail_str(err);
         auto root = std::make_shared<TreeNode>();
+        if (n_leaves) *n_leaves = 1;
         if (all_zero) return root;  // one leaf of value 0.0
+        if (max_leaves_ >= 2) {
+            std::vector<TreeNode*> lw_nodes;
+            std::vector<Dev::HistNode> lw_leaves;
+            if (!grow_leaves(root.get(), s_l, s_w, &lw_nodes, &lw_leaves)) {  // (the index list of a tree that never searched: the root's)
+                if (!dev_.hist_root(&err)) fail_str(err);
+            }
+            if (n_leaves) *n_leaves = (uint32_t)lw_nodes.size();
+            leaf_values(lw_nodes, lw_leaves, s_l, s_w, leaf_seconds);
+            return root;
+        }
         struct Open {
             TreeNode* node;
             uint32_t slot, begin, end, depth;
@@ -175,10 +190,128 @@ class HistGrower {
             }
         }
         if (leaf_seconds) *leaf_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (n_leaves) *n_leaves = (uint32_t)leaf_nodes.size();
         return root;
     }
 
+    // leaf-wise growth: the largest histogram pool a tree of this grower asked for, in bytes (0: none yet)
+    uint64_t pool_bytes() const { return pool_bytes_; }
+
   private:
+    // Leaf-wise growth.  Every node has a creation index (the root 0; a split gives its lhs the next one, then its rhs); a
+    // leaf that is enterable is searched when it is made and is open when its record is accepted by the level loop's rule;
+    // the open leaf with the largest gain is split (the smallest creation index among equals) while the tree has fewer than
+    // max_leaves leaves.  Fills leaf_nodes / leaves like the level loop does.  false: the root was not searched, and the
+    // device's index list was not made.
+    bool grow_leaves(TreeNode* root, int s_l, int s_w, std::vector<TreeNode*>* leaf_nodes, std::vector<frdev::DeviceDataset::HistNode>* leaves) {
+        using Dev = frdev::DeviceDataset;
+        std::string err;
+        struct OpenLeaf {
+            TreeNode* node;
+            uint32_t slot, begin, end, depth, index;
+            double gain;
+            Dev::HistPick pick;
+        };
+        std::vector<OpenLeaf> open;
+        auto close = [&](TreeNode* t, uint32_t b, uint32_t e) {
+            leaf_nodes->push_back(t);
+            leaves->push_back({(uint32_t)leaves->size(), b, e});
+        };
+        if (!enterable(n_, 1)) {
+            close(root, 0u, n_);
+            return false;
+        }
+        const size_t F = sel_.empty() ? feats_.size() : sel_.size();
+        auto full = [&](size_t fi) { return sel_.empty() ? fi : (size_t)sel_[fi]; };
+        const Dev::HistLeafSearch how{min_leaf_, newton_.on, s_l, s_w, newton_.lambda_l2, newton_.min_sum_hessian};
+        // live histograms never exceed the leaves, and the leaves neither max_leaves, the instances nor 2^(max_depth - 1)
+        uint32_t slots = std::min(max_leaves_, n_);
+        if (max_depth_ <= 31) slots = std::min(slots, 1u << (max_depth_ - 1));
+        std::vector<uint32_t> free_slots;
+        for (uint32_t s = slots; s-- > 1;) free_slots.push_back(s);  // (slot 0: the root's)
+        // the record of a searched leaf: open with its gain, or closed and its slot free again
+        auto consider = [&](TreeNode* t, uint32_t slot, uint32_t b, uint32_t e, uint32_t depth, uint32_t index, const Dev::HistPick& p) {
+            bool ok = p.valid != 0;
+            double gain = 0.0;
+            if (ok && newton_.on) {
+                const double g = std::ldexp((double)p.qtot, -s_l);
+                gain = p.imp - (g * g) / (std::ldexp((double)p.wtot, -s_w) + newton_.lambda_l2);
+                ok = gain > newton_.min_split_gain;
+            } else if (ok) {  // (ranks only: rounding may leave it slightly below 0)
+                const double sn = (double)p.qtot;
+                gain = p.imp - (sn * sn) / (double)(e - b);
+            }
+            if (ok) {
+                open.push_back({t, slot, b, e, depth, index, gain, p});
+            } else {
+                close(t, b, e);
+                free_slots.push_back(slot);
+            }
+        };
+        Dev::HistPick pick[2];
+        if (!dev_.hist_leaf_begin(slots, how, &pick[0], &err)) fail_str(err);
+        consider(root, 0u, 0u, n_, 1u, 0u, pick[0]);
+        uint32_t n_leaves = 1, next_index = 1;
+        while (n_leaves < max_leaves_ && !open.empty()) {
+            size_t at = 0;
+            for (size_t i = 1; i < open.size(); i++)
+                if (open[i].gain > open[at].gain || (open[i].gain == open[at].gain && open[i].index < open[at].index)) at = i;
+            const OpenLeaf o = open[at];
+            open.erase(open.begin() + (std::ptrdiff_t)at);
+            const uint32_t n = o.end - o.begin, nl = o.pick.nl, nr = n - nl;
+            if (o.pick.fi >= F) fail_str("LambdaMART histogram grower: internal error: an impossible split");
+            const size_t ws = full(o.pick.fi);
+            if (o.pick.edge >= nedges_[ws] || nl == 0 || nl >= n) fail_str("LambdaMART histogram grower: internal error: an impossible split");
+            o.node->leaf = false;
+            o.node->fid = feats_[ws];
+            o.node->value = (double)edges_[ws * 256 + o.pick.edge];
+            o.node->lhs.reset(new TreeNode());
+            o.node->rhs.reset(new TreeNode());
+            n_leaves++;
+            const uint32_t mid = o.begin + nl, il = next_index++, ir = next_index++;
+            const bool more = n_leaves < max_leaves_;  // (the split that reaches max_leaves searches no child)
+            const bool el = more && enterable(nl, o.depth + 1), er = more && enterable(nr, o.depth + 1);
+            const bool left_small = nl <= nr;
+            Dev::HistLeafStep step{{o.begin, o.end, (uint32_t)ws, o.pick.edge, nl}, o.slot, Dev::HIST_NO_SLOT, el, er};
+            if (el || er) {
+                if (free_slots.empty()) fail_str("LambdaMART histogram grower: internal error: the histogram pool is exhausted");
+                step.small_slot = free_slots.back();
+                free_slots.pop_back();
+            }
+            if (!dev_.hist_leaf_step(step, how, pick, &err)) fail_str(err);
+            const uint32_t slot_l = left_small ? step.small_slot : o.slot, slot_r = left_small ? o.slot : step.small_slot;
+            if (el) consider(o.node->lhs.get(), slot_l, o.begin, mid, o.depth + 1, il, pick[0]);
+            else close(o.node->lhs.get(), o.begin, mid);
+            if (er) consider(o.node->rhs.get(), slot_r, mid, o.end, o.depth + 1, ir, pick[1]);
+            else close(o.node->rhs.get(), mid, o.end);
+            // a slot whose child was not searched holds nothing that is read again
+            if (!el && (el || er)) free_slots.push_back(slot_l);
+            if (!er && (el || er)) free_slots.push_back(slot_r);
+            if (!el && !er) free_slots.push_back(o.slot);
+        }
+        for (const OpenLeaf& o : open) close(o.node, o.begin, o.end);
+        pool_bytes_ = std::max(pool_bytes_, (uint64_t)slots * F * k_ * (newton_.on ? 20u : 12u));
+        return true;
+    }
+
+    void leaf_values(const std::vector<TreeNode*>& leaf_nodes, const std::vector<frdev::DeviceDataset::HistNode>& leaves, int s_l, int s_w,
+                     double* leaf_seconds) {
+        std::string err;
+        auto t0 = std::chrono::steady_clock::now();
+        std::vector<long long> qw;
+        if (!dev_.hist_leaf_sums(leaves, &qw, &err)) fail_str(err);
+        for (size_t i = 0; i < leaf_nodes.size(); i++) {
+            const long long q = qw[i * 2], w = qw[i * 2 + 1];
+            if (newton_.on) {
+                const double den = std::ldexp((double)w, -s_w) + newton_.lambda_l2;
+                leaf_nodes[i]->value = den != 0.0 ? std::ldexp((double)q, -s_l) / den : 0.0;
+            } else {
+                leaf_nodes[i]->value = w != 0 ? std::ldexp((double)q, -s_l) / std::ldexp((double)w, -s_w) : 0.0;
+            }
+        }
+        if (leaf_seconds) *leaf_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    }
+
     void check_features(const std::vector<uint32_t>* features) const {
         for (uint32_t s : sel_)
             if (s >= feats_.size()) fail_str("LambdaMART histogram grower: a sampled feature outside the feature list");
@@ -191,6 +324,8 @@ class HistGrower {
     std::vector<uint32_t> feats_;
     uint32_t k_, max_depth_, min_leaf_, n_ = 0, n_full_ = 0;  // n_: the tree's instances (n_full_ of them without a query sample)
     HistNewton newton_;
+    uint32_t max_leaves_ = 0;                                  // 0: level-wise growth
+    uint64_t pool_bytes_ = 0;
     std::vector<uint32_t> sel_;                                // the tree's features as slots of the bins (empty: all)
     std::vector<float> edges_;
     std::vector<uint32_t> nedges_;

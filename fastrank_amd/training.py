@@ -99,7 +99,11 @@ class LambdaMARTParams(_LearnerParams):
     grower only: splits maximise G^2/(H + lambda_l2) over gradient sums G and hessian sums H, leaves are G/(H + lambda_l2)).
     `lambda_l2`, `min_sum_hessian`, `min_split_gain` (finite, >= 0, default 0.0; only with "newton"): the L2 term, the least
     hessian mass of a child, and the gain a split must exceed.  The four keys are written only when they differ from their
-    defaults ("Newton split gain")."""
+    defaults ("Newton split gain").
+    `max_leaves`: 0 (the default: a tree is grown level by level down to `max_depth`) or at least 2 (histogram grower only):
+    the tree is grown leaf-wise, always splitting the open leaf whose best split gains most, until it has `max_leaves`
+    leaves or no leaf can be split; `max_depth` still bounds the depth.  Written only when set (DESIGN.md section 11,
+    "Leaf-wise growth")."""
 
     VARIANT: ClassVar[str] = "LambdaMART"
 
@@ -120,10 +124,12 @@ class LambdaMARTParams(_LearnerParams):
     lambda_l2: float = 0.0
     min_sum_hessian: float = 0.0
     min_split_gain: float = 0.0
+    max_leaves: int = 0
 
     _WIRE_DEFAULTS: ClassVar[Dict[str, Any]] = {"grower": "exact", "query_sampling_rate": 1.0, "feature_sampling_rate": 1.0, "seed": 0,
                                                 "validation_queries": [], "early_stopping_rounds": 0, "split_gain": "variance",
-                                                "lambda_l2": 0.0, "min_sum_hessian": 0.0, "min_split_gain": 0.0}
+                                                "lambda_l2": 0.0, "min_sum_hessian": 0.0, "min_split_gain": 0.0,
+                                                "max_leaves": 0}
 
     def to_dict(self) -> Dict[str, Any]:
         wire = dataclasses.asdict(self)

@@ -212,6 +212,13 @@ const CResult *fr_debug_hist_tree_newton(const CDataset *dataset, uint32_t split
                                          size_t len, const uint32_t *queries, size_t n_queries,
                                          const uint32_t *features, size_t n_features, double lambda_l2,
                                          double min_sum_hessian, double min_split_gain);
+/* One tree grown leaf-wise under a leaf budget max_leaves >= 2 ("Leaf-wise growth"): the open leaf
+ * with the largest gain is split next.  newton != 0: the Newton split gain with the three numbers (0 without it). */
+const CResult *fr_debug_hist_tree_leafwise(const CDataset *dataset, uint32_t split_candidates, uint32_t max_depth,
+                                           uint32_t min_leaf_support, const double *lambda, const double *weight,
+                                           size_t len, const uint32_t *queries, size_t n_queries,
+                                           const uint32_t *features, size_t n_features, int newton, double lambda_l2,
+                                           double min_sum_hessian, double min_split_gain, uint32_t max_leaves);
 /* Full per-query rank order under the reference's total order (src/evaluators.rs:34-49):
  * out_instance_ids[n] grouped by query (device query order), best first; out_offsets[nq+1]. */
 const void *fr_rank_order(const CModel *model, const CDataset *dataset, uint32_t *out_instance_ids,

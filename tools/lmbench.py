@@ -10,6 +10,8 @@
                                                                # a query sample, scaled to the full shape (labelled as such)
     python tools/lmbench.py --shape 30k --trees 100 --grower histogram --split-gain newton --lambda-l2 1
                                                                # the second-order split gain with an L2 term
+    python tools/lmbench.py --shape 30k --trees 100 --grower histogram --max-leaves 32 --max-depth 32
+                                                               # leaf-wise growth under a leaf budget (reports the trees' shape)
 Every other parameter is the LambdaMART default (TrainRequest.lambdamart()).
 """
 import argparse
@@ -48,10 +50,18 @@ def device_run(args, X, y, qid):
     req.params.early_stopping_rounds = args.early_stopping_rounds
     req.params.split_gain = args.split_gain
     req.params.lambda_l2, req.params.min_sum_hessian, req.params.min_split_gain = args.lambda_l2, args.min_sum_hessian, args.min_split_gain
+    if args.max_leaves:
+        req.params.max_leaves = args.max_leaves
+    if args.max_depth:
+        req.params.max_depth = args.max_depth
     # upload and first touch of the device (not part of training)
     native.device_info(ds)
     t_ds = time.perf_counter() - t0
-    native.profile_enable(True)
+    if args.warmup_trees > 0:  # an untimed training first: the device, its allocations and the bins are warm afterwards
+        warm = req.clone()
+        warm.params.num_trees = args.warmup_trees
+        ds.train_model(warm)
+    native.profile_enable(not args.no_kernel_profile)
     native.profile_reset()
     t1 = time.perf_counter()
     model = ds.train_model(req)
@@ -78,6 +88,13 @@ def device_run(args, X, y, qid):
         out["validation"] = {k: st[k] for k in ("validation_queries", "training_queries", "best_iteration", "best_valid_measure",
                                                 "stopped_early", "early_stopping_rounds", "valid_measure", "train_measure")}
         out["model_trees"] = len(model.to_dict()["Ensemble"]["models"])
+    if args.max_leaves:  # (only under leaf-wise growth, like the stats object)
+        def depth(node):
+            return 1 if "LeafNode" in node else 1 + max(depth(node["FeatureSplit"]["lhs"]), depth(node["FeatureSplit"]["rhs"]))
+
+        depths = [depth(m["DecisionTree"]) for m in model.to_dict()["Ensemble"]["models"]]
+        out["leafwise"] = {"max_leaves": st["max_leaves"], "mean_leaves": st["mean_leaves"], "mean_depth": float(np.mean(depths)),
+                           "max_depth": int(np.max(depths)), "pool_bytes": st["pool_bytes"]}
     return out
 
 
@@ -125,6 +142,10 @@ def main():
     ap.add_argument("--lambda-l2", type=float, default=0.0, help="L2 term of the Newton gain and leaves")
     ap.add_argument("--min-sum-hessian", type=float, default=0.0, help="least hessian mass of a child under the Newton gain")
     ap.add_argument("--min-split-gain", type=float, default=0.0, help="gain a split must exceed under the Newton gain")
+    ap.add_argument("--max-leaves", type=int, default=0, help="leaf budget of leaf-wise growth (histogram grower only; 0: level-wise)")
+    ap.add_argument("--max-depth", type=int, default=0, help="max_depth of the request (0: the default)")
+    ap.add_argument("--warmup-trees", type=int, default=0, help="train this many trees untimed before the measured training")
+    ap.add_argument("--no-kernel-profile", action="store_true", help="leave the library's per-kernel event timing off during the timed training")
     ap.add_argument("--cpu-baseline", type=float, default=0.0, help="query fraction for the CPU restatement (0: device run)")
     args = ap.parse_args()
     n, d, q, seed = SHAPES[args.shape]
