@@ -1460,6 +1460,43 @@ const void* fr_debug_lambda_gradients_sampled(const CModel* model, const CDatase
     });
 }
 
+// fr_debug_lambda_gradients under the objective's options ("Truncation and normalisation"):
+// options_json = {"truncation_level": u32, "lambda_norm": bool}, either key optional (0 / false).  queries == NULL: the full
+// pass; else the query sample of fr_debug_lambda_gradients_sampled.  With both options at their defaults this is the pass of
+// the two other hooks.
+const void* fr_debug_lambda_gradients_opts(const CModel* model, const CDataset* dataset, const CQRel* qrel, const void* measure,
+                                           double sigma, const uint32_t* queries, size_t n_queries, const void* options_json,
+                                           double* lambda_out, double* weight_out, size_t out_len) {
+    return status_call([&]() {
+        const CModel& m = require_model(model);
+        const CDataset& ds = require_dataset(dataset);
+        std::string name = accept_str("measure", measure);
+        fr::lambdamart_check_measure(name);
+        const Value opts = parse_json_or_fail(accept_str("options_json", options_json));
+        if (!opts.is_object()) fr::fail_raw("Error(\"invalid type: expected a map of gradient options\", line: 0, column: 0)");
+        uint32_t truncation_level = 0;
+        bool lambda_norm = false;
+        for (const auto& kv : opts.obj) {
+            if (kv.first == "truncation_level") truncation_level = fr::json_u32(kv.second, "truncation_level");
+            else if (kv.first == "lambda_norm") lambda_norm = fr::json_bool(kv.second, "lambda_norm");
+            else fr::fail_raw("Error(\"unknown field `" + kv.first + "`, expected `truncation_level` or `lambda_norm`\", line: 0, column: 0)");
+        }
+        if (out_len && (!lambda_out || !weight_out)) fr::fail_str("NULL pointer: gradient outputs");
+        std::lock_guard<std::mutex> lk(api_mu_of(ds));
+        fr::DatasetView& view = *ds.view;
+        if (view.instances.empty()) return;
+        std::vector<unsigned char> flags;
+        if (queries) flags = debug_query_flags(queries, n_queries, view.host_csr().nq);
+        const unsigned char* fl = queries ? flags.data() : nullptr;
+        fr::Evaluator ev = fr::make_evaluator(view, name, qrel ? &qrel->actual : nullptr);
+        frdev::DeviceDataset& dev = view.device();
+        fr::score_model(view, m.actual);
+        std::string err;
+        if (!dev.lambda_gradients(ev.norms.data(), ev.depth, sigma, &err, fl, false, truncation_level, lambda_norm)) fr::fail_str(err);
+        if (!dev.lambda_download(lambda_out, weight_out, out_len, &err, fl)) fr::fail_str(err);
+    });
+}
+
 // the histogram grower's inputs for a view: its instance list and their positions, its features ascending
 static void hist_debug_lists(fr::DatasetView& view, std::vector<uint32_t>* ids, std::vector<uint32_t>* positions, std::vector<uint32_t>* feats) {
     *ids = fr::lambdamart_instance_list(view.host_csr());

@@ -24,7 +24,8 @@
 //                             and verifying the gaps (the exact kernels of kernels_fullrank.inc redo what fails)
 //   kernels_rf.inc          random-forest TRAINING: level-synchronous split search over a batch of trees (rocPRIM radix sort +
 //                           sequential-association importance kernels)
-//   kernels_lambda.inc      lambda_grad_kernel: LambdaMART's LambdaRank gradients, one workgroup per query
+//   kernels_lambda.inc      lambda_grad_kernel: LambdaMART's LambdaRank gradients, one workgroup per query;
+//                           lambda_grad_trunc_kernel: the same under a truncation level / per-query normalisation
 //   kernels_hist.inc        LambdaMART's histogram grower: one-byte bins, int64 fixed-point gradients, per-node histograms
 //   device_dataset.inc      DeviceDataset: HBM layout (runs, tiles, tables) and every launcher
 #include "device.hpp"

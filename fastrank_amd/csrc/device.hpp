@@ -311,8 +311,11 @@ class DeviceDataset {
     // the full pass gives them, the values of the others are left as they were and must not be read.
     // flags_unchanged: query_flags are those of the previous call (a fixed training split): the filtered query list already
     // on the device is used again, nothing is uploaded.
+    // truncation_level T >= 1: a pair contributes only when the better ranked of its documents is in the top T (0: every
+    // pair); lambda_norm: every query's lambda and w are scaled by log2(1 + S_q) / S_q.  With either set the pass runs
+    // lambda_grad_trunc_kernel, with neither lambda_grad_kernel ("Truncation and normalisation").
     bool lambda_gradients(const double* norms, int64_t depth, double sigma, std::string* err, const unsigned char* query_flags = nullptr,
-                          bool flags_unchanged = false);
+                          bool flags_unchanged = false, uint32_t truncation_level = 0, bool lambda_norm = false);
     // the last pass's lambda / w by padded position ([np] each)
     bool lambda_download_positions(std::vector<double>* lambda, std::vector<double>* weight, std::string* err);
     // ... scattered to original instance ids (ids outside this dataset or >= out_len are left untouched)

@@ -288,6 +288,7 @@ struct DeviceDataset::Impl {
         uint32_t sel_long = 0;                  // ... of which the slab path takes this many
         bool qsel_valid = false;                // qsel holds qsel_h (lambda_gradients' flags_unchanged)
         DevBuf<uint32_t> qsel;                  // [nq] qsel_h on the device
+        DevBuf<double> asum;                    // [np] lambda_norm: every document's pair mass A_p (lambda_grad_trunc_kernel)
     } lm;
     bool lm_build(std::string* err);
     // LambdaMART histogram grower (kernels_hist.inc).  The bin matrix is kept for as long as the instance list, the features
@@ -3963,7 +3964,7 @@ bool DeviceDataset::Impl::lm_build(std::string* err) {
 }
 
 bool DeviceDataset::lambda_gradients(const double* norms, int64_t depth, double sigma, std::string* err, const unsigned char* query_flags,
-                                     bool flags_unchanged) {
+                                     bool flags_unchanged, uint32_t truncation_level, bool lambda_norm) {
     Impl& m = *impl_;
     std::lock_guard<std::mutex> lk(m.mu);
     if (!m.bind(err)) return false;
@@ -3997,6 +3998,27 @@ bool DeviceDataset::lambda_gradients(const double* norms, int64_t depth, double 
         n_long = sel_long, n_lds = (uint32_t)lm.qsel_h.size() - sel_long;
         qorder = lm.qsel.p;
         longest = n_lds ? m.qlen_h[lm.qsel_h[n_long]] : 0;  // (the longest sampled query that is staged in LDS)
+    }
+    if (truncation_level != 0 || lambda_norm) {  // DESIGN.md section 11, "Truncation and normalisation": a kernel of its own
+        const uint32_t trunc = truncation_level != 0 ? truncation_level : 0xFFFFFFFFu;  // (no level: every rank is inside)
+        if (lambda_norm && !lm.asum.ensure(m.np, err)) return false;
+        ProfScope ps("lambda_grad_trunc_kernel", m.stream);
+        for (uint32_t q0 = 0; q0 < n_long; q0 += LM_SLAB_BLOCKS) {
+            const uint32_t cnt = std::min<uint32_t>(LM_SLAB_BLOCKS, n_long - q0);
+            lambda_grad_trunc_kernel<<<cnt, 256, 0, m.stream>>>(m.scores.p, lm.off.p, lm.pos.p, qorder, q0, m.gain.p, m.gexp.p, m.disc.p,
+                                                               m.perm.p, m.norms.p, depth, sigma, trunc, lambda_norm ? 1 : 0, lm.lam.p,
+                                                               lm.wt.p, lm.target.p, lm.asum.p, lm.slab.p, lm.max_len);
+        }
+        if (n_lds != 0) {
+            const size_t bytes = std::max<size_t>(longest * LM_STAGE_BYTES, 64);
+            FR_HIP(hipFuncSetAttribute((const void*)lambda_grad_trunc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+            lambda_grad_trunc_kernel<<<n_lds, 256, bytes, m.stream>>>(m.scores.p, lm.off.p, lm.pos.p, qorder, n_long, m.gain.p, m.gexp.p,
+                                                                        m.disc.p, m.perm.p, m.norms.p, depth, sigma, trunc,
+                                                                        lambda_norm ? 1 : 0, lm.lam.p, lm.wt.p, lm.target.p, lm.asum.p,
+                                                                        nullptr, 0u);
+        }
+        FR_HIP(hipGetLastError());
+        return true;
     }
     ProfScope ps("lambda_grad_kernel", m.stream);
     for (uint32_t q0 = 0; q0 < n_long; q0 += LM_SLAB_BLOCKS) {  // (longest first: these open the pass)

@@ -94,3 +94,195 @@ __global__ __launch_bounds__(256) void lambda_grad_kernel(const double* __restri
         target[p] = (float)l;
     }
 }
+
+// ----------------------------------------------------------------------------------------------------------------------
+// Truncation level T and per-query normalisation (DESIGN.md section 11, "Truncation and normalisation").
+//
+// A pair contributes only when the better ranked of its two documents sits in the top T, so a document outside the top T
+// has at most T partners and the pass costs n T pair terms instead of n^2.  Staging, ranks and discounts are the
+// untruncated kernel's.  Then:
+//   top list  the stored-order indices of the documents with rank < T, compacted in stored order (wave ballots) into
+//             the staging area of the instance ids, which are dead once the ranks are known; m = min(T, n) entries
+//   phase A   every document OUTSIDE the top T walks the top list only: at most T pair terms, one thread per document
+//   phase B   the m long chains of the top documents.  32 of them at a time: all 256 threads produce the signed pair
+//             terms of 32 chains x 16 partners (fewer chains: more partners, 512 terms either way) into an LDS tile, then
+//             the chains' own lanes add their tile row in stored partner order.  A skipped partner's tile entry is +0.0,
+//             which changes no bit of a sum that is never -0.0 (DESIGN.md).  The exp runs 256 wide, the dependent adds
+//             32 chains wide, and no lane waits for another lane's exp.
+//   norm      A_p (the sum of the document's t_pq >= 0, same order) goes to a global scratch, is staged over the dead
+//             score column, thread 0 adds S_q sequentially, and every lambda, w of the query is scaled by log2(1 + S_q) / S_q.
+// LDS: the staging of lambda_grad_kernel (36 B per document, at most 144 KiB) plus the 8.5 KiB tile and 32 B of counters.
+constexpr uint32_t LMT_TILE = 512;             // pair terms produced per step
+constexpr uint32_t LMT_CHAINS = 32;            // top documents per group of chains
+constexpr uint32_t LMT_TILE_SLOTS = LMT_TILE + LMT_CHAINS;  // rows are padded by one slot: 32 x 17 is the largest tile
+
+__global__ __launch_bounds__(256) void lambda_grad_trunc_kernel(
+    const double* __restrict__ scores, const uint32_t* __restrict__ lm_off, const uint32_t* __restrict__ lm_pos,
+    const uint32_t* __restrict__ qorder, uint32_t q_first, const float* __restrict__ gain, const double* __restrict__ gexp,
+    const double* __restrict__ disc, const uint32_t* __restrict__ perm, const double* __restrict__ norms, int64_t depth,
+    double sigma, uint32_t trunc, int normalise, double* lam, double* wt, float* target, double* asum, unsigned char* gslab,
+    uint32_t slab_docs) {
+    extern __shared__ double lm_lds[];
+    __shared__ double2 tile[LMT_TILE_SLOTS];
+    __shared__ uint32_t wave_cnt[4];
+    __shared__ double scale_f;
+    const uint32_t q = qorder[q_first + blockIdx.x];
+    const uint32_t off = lm_off[q], n = lm_off[q + 1] - off;
+    const uint32_t tid = threadIdx.x, bs = blockDim.x;  // (bs == 256: the tile and the ballots count on it)
+    const double z = norms[q];
+    if (!(z > 0.0)) {
+        for (uint32_t i = tid; i < n; i += bs) {
+            const uint32_t p = lm_pos[off + i];
+            lam[p] = 0.0;
+            wt[p] = 0.0;
+            target[p] = 0.0f;
+        }
+        return;
+    }
+    const uint32_t cap = gslab != nullptr ? slab_docs : n;
+    double* base = gslab != nullptr ? (double*)(gslab + (size_t)blockIdx.x * slab_docs * LM_STAGE_BYTES) : lm_lds;
+    double* s = base;
+    double* G = s + cap;
+    double* D = G + cap;
+    uint32_t* id = (uint32_t*)(D + cap);
+    float* g = (float*)(id + cap);
+    uint32_t* rk = (uint32_t*)(g + cap);
+    for (uint32_t i = tid; i < n; i += bs) {
+        const uint32_t p = lm_pos[off + i];
+        s[i] = scores[p];
+        G[i] = gexp[p];
+        id[i] = perm[p];
+        g[i] = gain[p];
+    }
+    __syncthreads();
+    for (uint32_t i = tid; i < n; i += bs) {
+        const double si = s[i];
+        const float gi = g[i];
+        const uint32_t ii = id[i];
+        uint32_t r = 0;
+        for (uint32_t j = 0; j < n; j++) {
+            const double sj = s[j];
+            const float gj = g[j];
+            r += (sj > si || (sj == si && (gj < gi || (gj == gi && id[j] < ii)))) ? 1u : 0u;
+        }
+        rk[i] = r;
+    }
+    __syncthreads();
+    const uint64_t k = depth < 0 ? (uint64_t)n : (uint64_t)depth;
+    for (uint32_t i = tid; i < n; i += bs) D[i] = (uint64_t)rk[i] < k ? 1.0 / disc[rk[i]] : 0.0;
+    __syncthreads();
+    // the top list, in stored order, over the ids (dead from here on)
+    uint32_t* top = id;
+    uint32_t m = 0;
+    for (uint32_t c0 = 0; c0 < n; c0 += bs) {
+        const uint32_t i = c0 + tid, lane = tid & 63u, wv = tid >> 6;
+        const bool in = i < n && rk[i] < trunc;
+        const unsigned long long b = __ballot(in ? 1 : 0);
+        if (lane == 0) wave_cnt[wv] = (uint32_t)__popcll(b);
+        __syncthreads();
+        uint32_t before = m;
+        for (uint32_t x = 0; x < wv; x++) before += wave_cnt[x];
+        if (in) top[before + (uint32_t)__popcll(b & ((1ull << lane) - 1ull))] = i;
+        m += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+        __syncthreads();
+    }
+    const double sigma2 = sigma * sigma;
+    // phase A: a document outside the top T meets the top documents only
+    for (uint32_t i = tid; i < n; i += bs) {
+        if (rk[i] < trunc) continue;
+        const double si = s[i], Gi = G[i], Di = D[i];
+        const float gi = g[i];
+        double l = 0.0, w = 0.0, a = 0.0;
+        for (uint32_t c = 0; c < m; c++) {
+            const uint32_t j = top[c];
+            const float gj = g[j];
+            if (gj == gi) continue;
+            const bool high = gi > gj;
+            const double diff = high ? si - s[j] : s[j] - si;  // s_h - s_l
+            const double delta = fabs(Gi - G[j]) * fabs(Di - D[j]) / z;
+            const double rho = 1.0 / (1.0 + exp(sigma * diff));
+            const double t = sigma * rho * delta;
+            l = high ? l + t : l - t;
+            w = w + sigma2 * rho * (1.0 - rho) * delta;
+            a = a + t;
+        }
+        const uint32_t p = lm_pos[off + i];
+        lam[p] = l;
+        wt[p] = w;
+        if (normalise) asum[p] = a;
+        else target[p] = (float)l;
+    }
+    // phase B: the chains of the top documents, LMT_CHAINS at a time
+    for (uint32_t a0 = 0; a0 < m; a0 += LMT_CHAINS) {
+        const uint32_t rows = min(LMT_CHAINS, m - a0);
+        uint32_t cs = 4;  // the tile is (512 >> cs) rows x (1 << cs) partners, the widest that still holds `rows` rows
+        while (cs < 9 && (LMT_TILE >> (cs + 1)) >= rows) cs++;
+        const uint32_t width = 1u << cs, stride = width + 1;
+        double l = 0.0, w = 0.0, a = 0.0;
+        for (uint32_t c0 = 0; c0 < n; c0 += width) {
+            for (uint32_t e = tid; e < LMT_TILE; e += bs) {
+                const uint32_t row = e >> cs, col = e & (width - 1), j = c0 + col;
+                if (row >= rows) continue;
+                double2 v = make_double2(0.0, 0.0);
+                if (j < n) {
+                    const uint32_t i = top[a0 + row];
+                    const float gi = g[i], gj = g[j];
+                    if (gj != gi) {
+                        const bool high = gi > gj;
+                        const double si = s[i];
+                        const double diff = high ? si - s[j] : s[j] - si;  // s_h - s_l
+                        const double delta = fabs(G[i] - G[j]) * fabs(D[i] - D[j]) / z;
+                        const double rho = 1.0 / (1.0 + exp(sigma * diff));
+                        const double t = sigma * rho * delta;
+                        v.x = high ? t : -t;
+                        v.y = sigma2 * rho * (1.0 - rho) * delta;
+                    }
+                }
+                tile[row * stride + col] = v;
+            }
+            __syncthreads();
+            if (tid < rows) {
+                const uint32_t cw = min(width, n - c0);
+                const double2* r = tile + tid * stride;
+                for (uint32_t c = 0; c < cw; c++) {
+                    const double2 v = r[c];
+                    l = l + v.x;
+                    w = w + v.y;
+                    a = a + fabs(v.x);
+                }
+            }
+            __syncthreads();
+        }
+        if (tid < rows) {
+            const uint32_t p = lm_pos[off + top[a0 + tid]];
+            lam[p] = l;
+            wt[p] = w;
+            if (normalise) asum[p] = a;
+            else target[p] = (float)l;
+        }
+    }
+    if (!normalise) return;
+    // S_q: the A_p in stored order, one after the other; then the query's scale
+    __syncthreads();  // (phase B's last reads of the scores, and every A_p written)
+    for (uint32_t i = tid; i < n; i += bs) s[i] = asum[lm_pos[off + i]];
+    __syncthreads();
+    if (tid == 0) {
+        double S = 0.0;
+        for (uint32_t i = 0; i < n; i++) S = S + s[i];
+        scale_f = S > 0.0 ? log2(1.0 + S) / S : 1.0;
+        wave_cnt[0] = S > 0.0 ? 1u : 0u;
+    }
+    __syncthreads();
+    const double f = scale_f;
+    const bool scaled = wave_cnt[0] != 0;
+    for (uint32_t i = tid; i < n; i += bs) {
+        const uint32_t p = lm_pos[off + i];
+        double l = lam[p];
+        if (scaled) {
+            l = l * f;
+            lam[p] = l;
+            wt[p] = wt[p] * f;
+        }
+        target[p] = (float)l;
+    }
+}

@@ -23,6 +23,9 @@
 // second-order gain G^2 / (H + lambda_l2) with the floors min_sum_hessian and min_split_gain, leaves are G / (H + lambda_l2).
 // max_leaves >= 2 (histogram grower only; DESIGN.md section 11, "Leaf-wise growth"): a tree is grown leaf by leaf, the open
 // leaf with the largest gain first, until it has max_leaves leaves; 0 (the default) is level-wise growth.
+// truncation_level = T >= 1 / lambda_norm (both growers; DESIGN.md section 11, "Truncation and normalisation"): a pair
+// contributes to the gradients only when the better ranked of its documents is in the top T, and every query's lambda and
+// w are scaled by log2(1 + S_q) / S_q; with either set the gradient stage is lambda_grad_trunc_kernel.
 #pragma once
 #include <chrono>
 #include <cmath>
@@ -57,6 +60,9 @@ struct LambdaMARTParams {
     double lambda_l2 = 0.0, min_sum_hessian = 0.0, min_split_gain = 0.0;
     // the leaf budget of leaf-wise growth (optional key, not written at its default): 0 = level-wise growth
     uint32_t max_leaves = 0;
+    // the objective's truncation level and per-query normalisation (optional keys, not written at their defaults): 0 = every pair
+    uint32_t truncation_level = 0;
+    bool lambda_norm = false;
 
     bool sampling() const { return query_sampling_rate < 1.0 || feature_sampling_rate < 1.0; }
     [[noreturn]] static void invalid(const std::string& what) {
@@ -99,6 +105,8 @@ struct LambdaMARTParams {
         if (const Value* r = v.find("min_sum_hessian")) p.min_sum_hessian = json_f64(*r, "min_sum_hessian");
         if (const Value* r = v.find("min_split_gain")) p.min_split_gain = json_f64(*r, "min_split_gain");
         if (const Value* r = v.find("max_leaves")) p.max_leaves = json_u32(*r, "max_leaves");
+        if (const Value* r = v.find("truncation_level")) p.truncation_level = json_u32(*r, "truncation_level");
+        if (const Value* r = v.find("lambda_norm")) p.lambda_norm = json_bool(*r, "lambda_norm");
         if (p.num_trees < 1) invalid("num_trees must be at least 1");
         if (!(std::isfinite(p.learning_rate) && p.learning_rate > 0.0)) invalid("learning_rate must be finite and greater than 0");
         if (p.max_depth < 1) invalid("max_depth must be at least 1");
@@ -145,6 +153,8 @@ struct LambdaMARTParams {
         if (min_sum_hessian != 0.0) o.set("min_sum_hessian", Value::number(min_sum_hessian));
         if (min_split_gain != 0.0) o.set("min_split_gain", Value::number(min_split_gain));
         if (max_leaves != 0) o.set("max_leaves", Value::uint(max_leaves));
+        if (truncation_level != 0) o.set("truncation_level", Value::uint(truncation_level));
+        if (lambda_norm) o.set("lambda_norm", Value::boolean(true));
         return o;
     }
 };
@@ -241,6 +251,9 @@ struct LambdaMARTStats {
     double lambda_l2 = 0.0, min_sum_hessian = 0.0, min_split_gain = 0.0;
     // leaf-wise growth (reported only when max_leaves is set): the request's key and the trees' mean number of leaves
     uint32_t max_leaves = 0;
+    // the objective's options (each reported only when set): the request's keys
+    uint32_t truncation_level = 0;
+    bool lambda_norm = false;
     uint64_t sum_leaves = 0, pool_bytes = 0;  // pool_bytes: the histogram pool (slots x the tree's features x bins x 12 or 20 B), the largest over the trees
 
     Value to_json() const {
@@ -288,6 +301,8 @@ struct LambdaMARTStats {
             o.set("mean_leaves", Value::number((double)sum_leaves / (trees ? (double)trees : 1.0)));
             o.set("pool_bytes", Value::uint(pool_bytes));
         }
+        if (truncation_level != 0) o.set("truncation_level", Value::uint(truncation_level));
+        if (lambda_norm) o.set("lambda_norm", Value::boolean(true));
         return o;
     }
 };
@@ -327,6 +342,7 @@ class LambdaMARTTrainer {
         for (uint32_t id : root_ids) max_id = std::max(max_id, id);
 
         stats_.histogram = p_.histogram;
+        stats_.truncation_level = p_.truncation_level, stats_.lambda_norm = p_.lambda_norm;
         std::unique_ptr<HistGrower> hist;
         if (p_.histogram) {
             hist.reset(new HistGrower(dev, feats, p_.split_candidates, p_.max_depth, p_.min_leaf_support,
@@ -418,7 +434,9 @@ class LambdaMARTTrainer {
             }
             if (subset_q && !hist) ids_t = &t_ids, off_t = &t_off, pos_t = t_pos.data();
             auto ta = tnow();
-            if (!dev.lambda_gradients(ev_.norms.data(), ev_.depth, p_.sigma, &err, subset_q ? qflags.data() : nullptr, fixed_q && t > 0)) fail_str(err);
+            if (!dev.lambda_gradients(ev_.norms.data(), ev_.depth, p_.sigma, &err, subset_q ? qflags.data() : nullptr, fixed_q && t > 0,
+                                      p_.truncation_level, p_.lambda_norm))
+                fail_str(err);
             if (!frdev::device_synchronize(&err)) fail_str(err);
             auto tb = tnow();
             if (sampling && hist) {

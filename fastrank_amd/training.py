@@ -103,7 +103,12 @@ class LambdaMARTParams(_LearnerParams):
     `max_leaves`: 0 (the default: a tree is grown level by level down to `max_depth`) or at least 2 (histogram grower only):
     the tree is grown leaf-wise, always splitting the open leaf whose best split gains most, until it has `max_leaves`
     leaves or no leaf can be split; `max_depth` still bounds the depth.  Written only when set (DESIGN.md section 11,
-    "Leaf-wise growth")."""
+    "Leaf-wise growth").
+    `truncation_level`: 0 (the default: every pair of a query's documents with different labels contributes to the
+    gradients) or T >= 1: a pair contributes only when the better ranked of the two is in the current top T.
+    `lambda_norm` (default False): every query's gradients and weights are scaled by log2(1 + S_q) / S_q, S_q the query's
+    summed pair terms, so that a few long queries do not dominate a tree.  Both growers; both keys are written only when
+    set ("Truncation and normalisation")."""
 
     VARIANT: ClassVar[str] = "LambdaMART"
 
@@ -125,11 +130,13 @@ class LambdaMARTParams(_LearnerParams):
     min_sum_hessian: float = 0.0
     min_split_gain: float = 0.0
     max_leaves: int = 0
+    truncation_level: int = 0
+    lambda_norm: bool = False
 
     _WIRE_DEFAULTS: ClassVar[Dict[str, Any]] = {"grower": "exact", "query_sampling_rate": 1.0, "feature_sampling_rate": 1.0, "seed": 0,
                                                 "validation_queries": [], "early_stopping_rounds": 0, "split_gain": "variance",
                                                 "lambda_l2": 0.0, "min_sum_hessian": 0.0, "min_split_gain": 0.0,
-                                                "max_leaves": 0}
+                                                "max_leaves": 0, "truncation_level": 0, "lambda_norm": False}
 
     def to_dict(self) -> Dict[str, Any]:
         wire = dataclasses.asdict(self)

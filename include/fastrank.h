@@ -219,6 +219,15 @@ const CResult *fr_debug_hist_tree_leafwise(const CDataset *dataset, uint32_t spl
                                            size_t len, const uint32_t *queries, size_t n_queries,
                                            const uint32_t *features, size_t n_features, int newton, double lambda_l2,
                                            double min_sum_hessian, double min_split_gain, uint32_t max_leaves);
+/* fr_debug_lambda_gradients under the LambdaRank objective's options ("Truncation and
+ * normalisation").  options_json = {"truncation_level": T, "lambda_norm": bool}, either key optional: T >= 1 keeps a pair
+ * only when the better ranked of its two documents is in the top T of the pass's ranks (0, the default: every pair);
+ * lambda_norm scales every query's lambda and weight by log2(1 + S_q) / S_q, S_q the query's summed pair terms.
+ * queries[n_queries] as in fr_debug_lambda_gradients_sampled, or NULL for every query. */
+const void *fr_debug_lambda_gradients_opts(const CModel *model, const CDataset *dataset, const CQRel *qrel,
+                                           const void *measure, double sigma, const uint32_t *queries,
+                                           size_t n_queries, const void *options_json, double *lambda_out,
+                                           double *weight_out, size_t out_len);
 /* Full per-query rank order under the reference's total order (src/evaluators.rs:34-49):
  * out_instance_ids[n] grouped by query (device query order), best first; out_offsets[nq+1]. */
 const void *fr_rank_order(const CModel *model, const CDataset *dataset, uint32_t *out_instance_ids,

@@ -14,6 +14,10 @@ score_ensemble; a second run gives the same JSON.  The library's evaluator error
 gains) is a mismatch unless the oracle's evaluator reports an error for the same running scores: "both_error", at most
 10 % of a run.  Any other error, from the device or from a restatement, is a mismatch that ENDS the run: nothing more is
 started on a device that may have faulted.
+--objective: every case also draws a truncation level (0, 1, 2, 5, 30) and lambda_norm ("Truncation
+and normalisation") from a generator of its own, so the cases themselves are those of a run without the flag; gradients
+are then held to tests/lambdamart_trunc_model.py (under lambda_norm at the tolerance derived in
+tests/test_gpu_lambdamart_trunc.py).
 --dry: no device; the restatement trains each generated case on the CPU, and the share of cases on which the oracle's
 evaluator reports an error -- at zero scores or after any tree -- is printed.
 Usage: python tools/fuzz_lambdamart.py --iters 300 [--seed 0]"""
@@ -33,6 +37,7 @@ from fuzz_parity import make_case  # noqa: E402
 from oracle import pyoracle as o  # noqa: E402
 from tests import lambdamart_hist_model as hm  # noqa: E402
 from tests import lambdamart_model as lm  # noqa: E402
+from tests import lambdamart_trunc_model as tm  # noqa: E402
 from tests.conftest import ranksvm_presence  # noqa: E402
 
 LABEL_SETS = [[0.0, 0.0, 1.0, 2.0, 3.0, 4.0], [0.0, 0.0, 0.5, 1.0, 2.0], [0.0, 0.0, 1.0, 30.0]]
@@ -112,6 +117,27 @@ def write_ranksvm(rng, path, X, y, qid):
     return full
 
 
+def draw_objective(rng):
+    """The objective's two keys for a case (none without --objective)."""
+    if rng is None:
+        return {}
+    return dict(truncation_level=int(rng.choice([0, 1, 2, 5, 30])), lambda_norm=bool(rng.random() < 0.5))
+
+
+def expected_gradients(s, y, queries, norms, depth, p):
+    """(lambda, w, per-query rtol) of the restatement for the case's parameters."""
+    T, norm = p.get("truncation_level", 0), p.get("lambda_norm", False)
+    if not T and not norm:
+        elam, ewt = lm.gradients(s, y, queries, norms, depth, p["sigma"])
+        return elam, ewt, np.full(len(queries), 1e-12)
+    elam, ewt, _, S, _ = tm.gradients(s, y, queries, norms, depth, p["sigma"], T, norm, parts=True)
+    rtol = np.full(len(queries), 1e-12)
+    if norm:
+        live = S > 0.0
+        rtol[live] = 3e-12 + 2.0 ** -52 / np.log1p(S[live]) + 12.0 * 2.0 ** -53
+    return elam, ewt, rtol
+
+
 def request(fr, measure, p, num_trees=None):
     req = fr.TrainRequest.lambdamart()
     req.measure = measure
@@ -131,9 +157,10 @@ class Case:
     """One generated case on the device: the view `g`, and the rows / matrix / oracle dataset the restatement works on
     (instance ids renumbered 0.. over the view's rows, ascending)."""
 
-    def __init__(self, fr, native, rng, tmp):
+    def __init__(self, fr, native, rng, tmp, objective_rng=None):
         self.fr, self.native = fr, native
         X, y, qid, self.measure, self.p, self.from_file = make_lm_case(rng)
+        self.p.update(draw_objective(objective_rng))
         self.present, self.views = None, 0
         if self.from_file:
             path = os.path.join(tmp, "case.train")
@@ -185,7 +212,8 @@ class Case:
                            self.present)
 
     def device_gradients(self, model):
-        lam, wt = self.native.lambda_gradients(model, self.g, self.measure, self.p["sigma"], n_total=self.n_total)
+        lam, wt = self.native.lambda_gradients(model, self.g, self.measure, self.p["sigma"], n_total=self.n_total,
+                                               truncation_level=self.p.get("truncation_level", 0), lambda_norm=self.p.get("lambda_norm", False))
         return lam[self.rows], wt[self.rows]
 
     def scores(self, model):
@@ -223,10 +251,13 @@ class Case:
             lam, wt = self.device_gradients(prefix)
             if not (np.all(np.isfinite(lam)) and np.all(np.isfinite(wt))):
                 return "non-finite gradient before tree %d" % t
-            elam, ewt = lm.gradients(s, self.y, self.queries, self.norms, depth, p["sigma"])
+            elam, ewt, rtol_q = expected_gradients(s, self.y, self.queries, self.norms, depth, p)
+            rtol = np.empty(len(s))
+            for q, ids in enumerate(self.queries):
+                rtol[ids] = rtol_q[q]
             for name, got, exp in (("lambda", lam, elam), ("w", wt, ewt)):
                 zero = exp == 0.0
-                if not np.array_equal(got[zero], exp[zero]) or not np.allclose(got, exp, rtol=1e-12, atol=0.0):
+                if not np.array_equal(got[zero], exp[zero]) or not np.all(np.abs(got - exp) <= rtol * np.abs(exp)):
                     return "%s before tree %d" % (name, t)
             for ids in self.queries:
                 if not abs(lam[ids].sum()) <= 1e-9 * max(1.0, np.abs(lam[ids]).sum()):
@@ -257,9 +288,10 @@ class Case:
         return self.c.metric_from_scores(self.measure, s, self.norms)[1] != 0
 
 
-def dry_case(rng):
+def dry_case(rng, objective_rng=None):
     """Does the oracle's evaluator report an error while the restatement trains the case (no views, no file)?"""
     X, y, qid, measure, p, _ = make_lm_case(rng)
+    p.update(draw_objective(objective_rng))
     c = o.Dataset(X, y, qid)
     queries = lm.query_lists(c)
     order_ids, norms, feats = np.concatenate(queries), c.default_norms(measure), list(range(X.shape[1]))
@@ -270,7 +302,7 @@ def dry_case(rng):
             return True
         if t == p["num_trees"]:
             break
-        lam, wt = lm.gradients(s, y, queries, norms, lm.depth_of(measure), p["sigma"])
+        lam, wt, _ = expected_gradients(s, y, queries, norms, lm.depth_of(measure), p)
         args = (X, lam, wt, order_ids, feats, p["max_depth"], p["min_leaf_support"], p["split_candidates"])
         tree = hm.fit_tree(*args, binned) if p["grower"] == "histogram" else lm.fit_tree(*args)
         s = s + p["learning_rate"] * lm.tree_scores(tree, X)
@@ -282,12 +314,14 @@ def main():
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--dry", action="store_true", help="no device: the oracle evaluator's error rate while the restatement trains")
+    ap.add_argument("--objective", action="store_true", help="draw a truncation level and lambda_norm for every case")
     args = ap.parse_args()
     rng = np.random.default_rng(args.seed)
+    objective_rng = np.random.default_rng([args.seed, 1]) if args.objective else None
     o.set_mean_segment(o.DEVICE_MEAN_SEGMENT)
     t0 = time.time()
     if args.dry:
-        errs = sum(dry_case(rng) for _ in range(args.iters))
+        errs = sum(dry_case(rng, objective_rng) for _ in range(args.iters))
         print(json.dumps({"iters": args.iters, "dry": True, "oracle_error_while_training": int(errs), "seconds": round(time.time() - t0, 1)}))
         return 0 if errs * 10 <= args.iters else 1
     import fastrank_amd as fr
@@ -296,7 +330,7 @@ def main():
     growers, ended = {}, None
     with tempfile.TemporaryDirectory() as tmp:
         for it in range(args.iters):
-            case = Case(fr, native, rng, tmp)
+            case = Case(fr, native, rng, tmp, objective_rng)
             growers[case.p["grower"]] = growers.get(case.p["grower"], 0) + 1
             views += case.views
             files += case.from_file

@@ -12,6 +12,8 @@
                                                                # the second-order split gain with an L2 term
     python tools/lmbench.py --shape 30k --trees 100 --grower histogram --max-leaves 32 --max-depth 32
                                                                # leaf-wise growth under a leaf budget (reports the trees' shape)
+    python tools/lmbench.py --shape 30k --trees 100 --grower histogram --truncation-level 30 --lambda-norm
+                                                               # the objective's truncation level and per-query normalisation
 Every other parameter is the LambdaMART default (TrainRequest.lambdamart()).
 """
 import argparse
@@ -54,6 +56,7 @@ def device_run(args, X, y, qid):
         req.params.max_leaves = args.max_leaves
     if args.max_depth:
         req.params.max_depth = args.max_depth
+    req.params.truncation_level, req.params.lambda_norm = args.truncation_level, args.lambda_norm
     # upload and first touch of the device (not part of training)
     native.device_info(ds)
     t_ds = time.perf_counter() - t0
@@ -95,6 +98,8 @@ def device_run(args, X, y, qid):
         depths = [depth(m["DecisionTree"]) for m in model.to_dict()["Ensemble"]["models"]]
         out["leafwise"] = {"max_leaves": st["max_leaves"], "mean_leaves": st["mean_leaves"], "mean_depth": float(np.mean(depths)),
                            "max_depth": int(np.max(depths)), "pool_bytes": st["pool_bytes"]}
+    if args.truncation_level or args.lambda_norm:  # (only when set, like the stats object)
+        out["objective"] = {k: st[k] for k in ("truncation_level", "lambda_norm") if k in st}
     return out
 
 
@@ -144,6 +149,8 @@ def main():
     ap.add_argument("--min-split-gain", type=float, default=0.0, help="gain a split must exceed under the Newton gain")
     ap.add_argument("--max-leaves", type=int, default=0, help="leaf budget of leaf-wise growth (histogram grower only; 0: level-wise)")
     ap.add_argument("--max-depth", type=int, default=0, help="max_depth of the request (0: the default)")
+    ap.add_argument("--truncation-level", type=int, default=0, help="a pair counts only when its better ranked document is in the top T (0: every pair)")
+    ap.add_argument("--lambda-norm", action="store_true", help="scale every query's gradients by log2(1 + S_q) / S_q")
     ap.add_argument("--warmup-trees", type=int, default=0, help="train this many trees untimed before the measured training")
     ap.add_argument("--no-kernel-profile", action="store_true", help="leave the library's per-kernel event timing off during the timed training")
     ap.add_argument("--cpu-baseline", type=float, default=0.0, help="query fraction for the CPU restatement (0: device run)")
