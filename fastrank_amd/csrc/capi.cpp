@@ -605,7 +605,9 @@ fr::Model train_rf(const std::shared_ptr<fr::DatasetView>& view, const ParsedReq
 // devices gets the single-device model
 fr::Model train_lambdamart(const std::shared_ptr<fr::DatasetView>& view, const ParsedRequest& rq) {
     auto t0 = std::chrono::steady_clock::now();
-    fr::Evaluator ev = fr::make_evaluator(*view, rq.measure, rq.has_qrel ? &rq.qrel : nullptr);
+    // under objective = map / mrr the AP / RR evaluator takes over every role of the request's measure (which was checked)
+    const char* objective = rq.lm.objective_measure();
+    fr::Evaluator ev = fr::make_evaluator(*view, objective ? std::string(objective) : rq.measure, rq.has_qrel ? &rq.qrel : nullptr);
     fr::LambdaMARTTrainer trainer(view, std::move(ev), rq.lm);
     fr::Model m = trainer.learn();
     fr::TrainStats st;
@@ -1461,9 +1463,10 @@ const void* fr_debug_lambda_gradients_sampled(const CModel* model, const CDatase
 }
 
 // fr_debug_lambda_gradients under the objective's options ("Truncation and normalisation"):
-// options_json = {"truncation_level": u32, "lambda_norm": bool}, either key optional (0 / false).  queries == NULL: the full
-// pass; else the query sample of fr_debug_lambda_gradients_sampled.  With both options at their defaults this is the pass of
-// the two other hooks.
+// options_json = {"truncation_level": u32, "lambda_norm": bool, "objective": "ndcg" | "map" | "mrr"}, every key optional
+// (0 / false / "ndcg").  queries == NULL: the full pass; else the query sample of fr_debug_lambda_gradients_sampled.  With
+// every option at its default this is the pass of the two other hooks.  `measure` must name NDCG whatever the objective;
+// under "map" / "mrr" the norms are the AP / RR evaluator's ("Objectives").
 const void* fr_debug_lambda_gradients_opts(const CModel* model, const CDataset* dataset, const CQRel* qrel, const void* measure,
                                            double sigma, const uint32_t* queries, size_t n_queries, const void* options_json,
                                            double* lambda_out, double* weight_out, size_t out_len) {
@@ -1476,9 +1479,11 @@ const void* fr_debug_lambda_gradients_opts(const CModel* model, const CDataset* 
         if (!opts.is_object()) fr::fail_raw("Error(\"invalid type: expected a map of gradient options\", line: 0, column: 0)");
         uint32_t truncation_level = 0;
         bool lambda_norm = false;
+        fr::LambdaMARTParams op;
         for (const auto& kv : opts.obj) {
             if (kv.first == "truncation_level") truncation_level = fr::json_u32(kv.second, "truncation_level");
             else if (kv.first == "lambda_norm") lambda_norm = fr::json_bool(kv.second, "lambda_norm");
+            else if (kv.first == "objective") op.objective = fr::LambdaMARTParams::objective_from_json(kv.second);
             else fr::fail_raw("Error(\"unknown field `" + kv.first + "`, expected `truncation_level` or `lambda_norm`\", line: 0, column: 0)");
         }
         if (out_len && (!lambda_out || !weight_out)) fr::fail_str("NULL pointer: gradient outputs");
@@ -1488,11 +1493,11 @@ const void* fr_debug_lambda_gradients_opts(const CModel* model, const CDataset* 
         std::vector<unsigned char> flags;
         if (queries) flags = debug_query_flags(queries, n_queries, view.host_csr().nq);
         const unsigned char* fl = queries ? flags.data() : nullptr;
-        fr::Evaluator ev = fr::make_evaluator(view, name, qrel ? &qrel->actual : nullptr);
+        fr::Evaluator ev = fr::make_evaluator(view, op.objective_measure() ? std::string(op.objective_measure()) : name, qrel ? &qrel->actual : nullptr);
         frdev::DeviceDataset& dev = view.device();
         fr::score_model(view, m.actual);
         std::string err;
-        if (!dev.lambda_gradients(ev.norms.data(), ev.depth, sigma, &err, fl, false, truncation_level, lambda_norm)) fr::fail_str(err);
+        if (!dev.lambda_gradients(ev.norms.data(), ev.depth, sigma, &err, fl, false, truncation_level, lambda_norm, op.objective)) fr::fail_str(err);
         if (!dev.lambda_download(lambda_out, weight_out, out_len, &err, fl)) fr::fail_str(err);
     });
 }

@@ -26,6 +26,7 @@
 //                           sequential-association importance kernels)
 //   kernels_lambda.inc      lambda_grad_kernel: LambdaMART's LambdaRank gradients, one workgroup per query;
 //                           lambda_grad_trunc_kernel: the same under a truncation level / per-query normalisation
+//                           (both are templates over the objective: NDCG, MAP or MRR pair weights)
 //   kernels_hist.inc        LambdaMART's histogram grower: one-byte bins, int64 fixed-point gradients, per-node histograms
 //   device_dataset.inc      DeviceDataset: HBM layout (runs, tiles, tables) and every launcher
 #include "device.hpp"

@@ -314,8 +314,10 @@ class DeviceDataset {
     // truncation_level T >= 1: a pair contributes only when the better ranked of its documents is in the top T (0: every
     // pair); lambda_norm: every query's lambda and w are scaled by log2(1 + S_q) / S_q.  With either set the pass runs
     // lambda_grad_trunc_kernel, with neither lambda_grad_kernel ("Truncation and normalisation").
+    // objective: 0 = NDCG (the pair weight is |delta NDCG|), 1 = MAP, 2 = MRR; norms are then the AP / RR evaluator's and
+    // depth is not read ("Objectives").  The same two kernels, instantiated for the objective.
     bool lambda_gradients(const double* norms, int64_t depth, double sigma, std::string* err, const unsigned char* query_flags = nullptr,
-                          bool flags_unchanged = false, uint32_t truncation_level = 0, bool lambda_norm = false);
+                          bool flags_unchanged = false, uint32_t truncation_level = 0, bool lambda_norm = false, int objective = 0);
     // the last pass's lambda / w by padded position ([np] each)
     bool lambda_download_positions(std::vector<double>* lambda, std::vector<double>* weight, std::string* err);
     // ... scattered to original instance ids (ids outside this dataset or >= out_len are left untouched)

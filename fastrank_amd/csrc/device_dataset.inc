@@ -3964,12 +3964,16 @@ bool DeviceDataset::Impl::lm_build(std::string* err) {
 }
 
 bool DeviceDataset::lambda_gradients(const double* norms, int64_t depth, double sigma, std::string* err, const unsigned char* query_flags,
-                                     bool flags_unchanged, uint32_t truncation_level, bool lambda_norm) {
+                                     bool flags_unchanged, uint32_t truncation_level, bool lambda_norm, int objective) {
     Impl& m = *impl_;
     std::lock_guard<std::mutex> lk(m.mu);
     if (!m.bind(err)) return false;
     if (m.scores_slots < 1 || m.scores.p == nullptr) {
         if (err) *err = "lambda_gradients: no scores resident";
+        return false;
+    }
+    if (objective < LM_OBJ_NDCG || objective > LM_OBJ_MRR) {
+        if (err) *err = "lambda_gradients: unknown objective " + std::to_string(objective);
         return false;
     }
     if (!m.lm_build(err)) return false;
@@ -4003,36 +4007,37 @@ bool DeviceDataset::lambda_gradients(const double* norms, int64_t depth, double 
         const uint32_t trunc = truncation_level != 0 ? truncation_level : 0xFFFFFFFFu;  // (no level: every rank is inside)
         if (lambda_norm && !lm.asum.ensure(m.np, err)) return false;
         ProfScope ps("lambda_grad_trunc_kernel", m.stream);
+        auto* const kernel = objective == LM_OBJ_MAP ? lambda_grad_trunc_kernel<LM_OBJ_MAP>
+                             : objective == LM_OBJ_MRR ? lambda_grad_trunc_kernel<LM_OBJ_MRR> : lambda_grad_trunc_kernel<LM_OBJ_NDCG>;
         for (uint32_t q0 = 0; q0 < n_long; q0 += LM_SLAB_BLOCKS) {
             const uint32_t cnt = std::min<uint32_t>(LM_SLAB_BLOCKS, n_long - q0);
-            lambda_grad_trunc_kernel<<<cnt, 256, 0, m.stream>>>(m.scores.p, lm.off.p, lm.pos.p, qorder, q0, m.gain.p, m.gexp.p, m.disc.p,
-                                                               m.perm.p, m.norms.p, depth, sigma, trunc, lambda_norm ? 1 : 0, lm.lam.p,
-                                                               lm.wt.p, lm.target.p, lm.asum.p, lm.slab.p, lm.max_len);
+            kernel<<<cnt, 256, 0, m.stream>>>(m.scores.p, lm.off.p, lm.pos.p, qorder, q0, m.gain.p, m.gexp.p, m.disc.p, m.perm.p, m.norms.p,
+                                              depth, sigma, trunc, lambda_norm ? 1 : 0, lm.lam.p, lm.wt.p, lm.target.p, lm.asum.p, lm.slab.p,
+                                              lm.max_len);
         }
         if (n_lds != 0) {
             const size_t bytes = std::max<size_t>(longest * LM_STAGE_BYTES, 64);
-            FR_HIP(hipFuncSetAttribute((const void*)lambda_grad_trunc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-            lambda_grad_trunc_kernel<<<n_lds, 256, bytes, m.stream>>>(m.scores.p, lm.off.p, lm.pos.p, qorder, n_long, m.gain.p, m.gexp.p,
-                                                                        m.disc.p, m.perm.p, m.norms.p, depth, sigma, trunc,
-                                                                        lambda_norm ? 1 : 0, lm.lam.p, lm.wt.p, lm.target.p, lm.asum.p,
-                                                                        nullptr, 0u);
+            FR_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+            kernel<<<n_lds, 256, bytes, m.stream>>>(m.scores.p, lm.off.p, lm.pos.p, qorder, n_long, m.gain.p, m.gexp.p, m.disc.p, m.perm.p,
+                                                    m.norms.p, depth, sigma, trunc, lambda_norm ? 1 : 0, lm.lam.p, lm.wt.p, lm.target.p,
+                                                    lm.asum.p, nullptr, 0u);
         }
         FR_HIP(hipGetLastError());
         return true;
     }
     ProfScope ps("lambda_grad_kernel", m.stream);
+    auto* const kernel = objective == LM_OBJ_MAP ? lambda_grad_kernel<LM_OBJ_MAP>
+                         : objective == LM_OBJ_MRR ? lambda_grad_kernel<LM_OBJ_MRR> : lambda_grad_kernel<LM_OBJ_NDCG>;
     for (uint32_t q0 = 0; q0 < n_long; q0 += LM_SLAB_BLOCKS) {  // (longest first: these open the pass)
         const uint32_t cnt = std::min<uint32_t>(LM_SLAB_BLOCKS, n_long - q0);
-        lambda_grad_kernel<<<cnt, 256, 0, m.stream>>>(m.scores.p, lm.off.p, lm.pos.p, qorder, q0, m.gain.p, m.gexp.p, m.disc.p,
-                                                     m.perm.p, m.norms.p, depth, sigma, lm.lam.p, lm.wt.p, lm.target.p, lm.slab.p,
-                                                     lm.max_len);
+        kernel<<<cnt, 256, 0, m.stream>>>(m.scores.p, lm.off.p, lm.pos.p, qorder, q0, m.gain.p, m.gexp.p, m.disc.p, m.perm.p, m.norms.p, depth,
+                                          sigma, lm.lam.p, lm.wt.p, lm.target.p, lm.slab.p, lm.max_len);
     }
     if (n_lds != 0) {
         const size_t bytes = std::max<size_t>(longest * LM_STAGE_BYTES, 64);
-        FR_HIP(hipFuncSetAttribute((const void*)lambda_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-        lambda_grad_kernel<<<n_lds, 256, bytes, m.stream>>>(m.scores.p, lm.off.p, lm.pos.p, qorder, n_long, m.gain.p, m.gexp.p,
-                                                              m.disc.p, m.perm.p, m.norms.p, depth, sigma, lm.lam.p, lm.wt.p,
-                                                              lm.target.p, nullptr, 0u);
+        FR_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        kernel<<<n_lds, 256, bytes, m.stream>>>(m.scores.p, lm.off.p, lm.pos.p, qorder, n_long, m.gain.p, m.gexp.p, m.disc.p, m.perm.p,
+                                                m.norms.p, depth, sigma, lm.lam.p, lm.wt.p, lm.target.p, nullptr, 0u);
     }
     FR_HIP(hipGetLastError());
     return true;

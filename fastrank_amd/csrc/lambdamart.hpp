@@ -26,6 +26,9 @@
 // truncation_level = T >= 1 / lambda_norm (both growers; DESIGN.md section 11, "Truncation and normalisation"): a pair
 // contributes to the gradients only when the better ranked of its documents is in the top T, and every query's lambda and
 // w are scaled by log2(1 + S_q) / S_q; with either set the gradient stage is lambda_grad_trunc_kernel.
+// objective = "map" / "mrr" (both growers; DESIGN.md section 11, "Objectives"): the pair weight is |delta AP| / |delta RR| of
+// swapping a relevant and a non-relevant document, and the trainer's evaluator is the AP / RR one: gradient norms, the
+// reported measures, the best iteration and early stopping all follow it.  The request's `measure` must still name NDCG.
 #pragma once
 #include <chrono>
 #include <cmath>
@@ -63,10 +66,22 @@ struct LambdaMARTParams {
     // the objective's truncation level and per-query normalisation (optional keys, not written at their defaults): 0 = every pair
     uint32_t truncation_level = 0;
     bool lambda_norm = false;
+    // what the gradients optimise (optional key, not written at its default): frdev::M_NDCG, M_AP ("map", "ap") or M_RR ("mrr", "rr")
+    int objective = frdev::M_NDCG;
 
+    static const char* objective_name(int objective) { return objective == frdev::M_AP ? "map" : objective == frdev::M_RR ? "mrr" : "ndcg"; }
+    // the evaluator the trainer gets under `objective` (the request's own measure is then read for nothing else)
+    const char* objective_measure() const { return objective == frdev::M_AP ? "ap" : objective == frdev::M_RR ? "rr" : nullptr; }
     bool sampling() const { return query_sampling_rate < 1.0 || feature_sampling_rate < 1.0; }
     [[noreturn]] static void invalid(const std::string& what) {
         fail_raw("Error(\"invalid value: " + what + "\", line: 0, column: 0)");
+    }
+    static int objective_from_json(const Value& g) {
+        if (!g.is_string()) fail_raw("Error(\"invalid type: expected a string for objective\", line: 0, column: 0)");
+        if (g.s == "ndcg") return frdev::M_NDCG;
+        if (g.s == "map" || g.s == "ap") return frdev::M_AP;
+        if (g.s == "mrr" || g.s == "rr") return frdev::M_RR;
+        invalid("objective must be `ndcg`, `map` or `mrr`, not `" + g.s + "`");
     }
     static LambdaMARTParams from_json(const Value& v) {
         if (!v.is_object()) fail_raw("Error(\"invalid type: expected struct LambdaMARTParams\", line: 0, column: 0)");
@@ -107,6 +122,7 @@ struct LambdaMARTParams {
         if (const Value* r = v.find("max_leaves")) p.max_leaves = json_u32(*r, "max_leaves");
         if (const Value* r = v.find("truncation_level")) p.truncation_level = json_u32(*r, "truncation_level");
         if (const Value* r = v.find("lambda_norm")) p.lambda_norm = json_bool(*r, "lambda_norm");
+        if (const Value* g = v.find("objective")) p.objective = objective_from_json(*g);
         if (p.num_trees < 1) invalid("num_trees must be at least 1");
         if (!(std::isfinite(p.learning_rate) && p.learning_rate > 0.0)) invalid("learning_rate must be finite and greater than 0");
         if (p.max_depth < 1) invalid("max_depth must be at least 1");
@@ -155,6 +171,7 @@ struct LambdaMARTParams {
         if (max_leaves != 0) o.set("max_leaves", Value::uint(max_leaves));
         if (truncation_level != 0) o.set("truncation_level", Value::uint(truncation_level));
         if (lambda_norm) o.set("lambda_norm", Value::boolean(true));
+        if (objective != frdev::M_NDCG) o.set("objective", Value::string(objective_name(objective)));
         return o;
     }
 };
@@ -254,6 +271,7 @@ struct LambdaMARTStats {
     // the objective's options (each reported only when set): the request's keys
     uint32_t truncation_level = 0;
     bool lambda_norm = false;
+    int objective = frdev::M_NDCG;  // (reported only when it is not NDCG)
     uint64_t sum_leaves = 0, pool_bytes = 0;  // pool_bytes: the histogram pool (slots x the tree's features x bins x 12 or 20 B), the largest over the trees
 
     Value to_json() const {
@@ -303,6 +321,7 @@ struct LambdaMARTStats {
         }
         if (truncation_level != 0) o.set("truncation_level", Value::uint(truncation_level));
         if (lambda_norm) o.set("lambda_norm", Value::boolean(true));
+        if (objective != frdev::M_NDCG) o.set("objective", Value::string(LambdaMARTParams::objective_name(objective)));
         return o;
     }
 };
@@ -318,7 +337,9 @@ class LambdaMARTTrainer {
         auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
             return std::chrono::duration<double>(b - a).count();
         };
-        if (ev_.measure != frdev::M_NDCG) fail_str("LambdaMART: only ndcg and ndcg@k have gradients");
+        // gradients exist for NDCG, AP and RR, and the evaluator must be the objective's: the kernels read its norms
+        if (ev_.measure != p_.objective)
+            fail_str(std::string("LambdaMART: the evaluator does not belong to the objective `") + LambdaMARTParams::objective_name(p_.objective) + "`");
         const LambdaSplit split = lambdamart_split(*view_, p_);  // (host only: a bad list fails before any device work)
         const bool hold = !split.held.empty();
         frdev::DeviceDataset& dev = view_->device();
@@ -342,7 +363,7 @@ class LambdaMARTTrainer {
         for (uint32_t id : root_ids) max_id = std::max(max_id, id);
 
         stats_.histogram = p_.histogram;
-        stats_.truncation_level = p_.truncation_level, stats_.lambda_norm = p_.lambda_norm;
+        stats_.truncation_level = p_.truncation_level, stats_.lambda_norm = p_.lambda_norm, stats_.objective = p_.objective;
         std::unique_ptr<HistGrower> hist;
         if (p_.histogram) {
             hist.reset(new HistGrower(dev, feats, p_.split_candidates, p_.max_depth, p_.min_leaf_support,
@@ -435,7 +456,7 @@ class LambdaMARTTrainer {
             if (subset_q && !hist) ids_t = &t_ids, off_t = &t_off, pos_t = t_pos.data();
             auto ta = tnow();
             if (!dev.lambda_gradients(ev_.norms.data(), ev_.depth, p_.sigma, &err, subset_q ? qflags.data() : nullptr, fixed_q && t > 0,
-                                      p_.truncation_level, p_.lambda_norm))
+                                      p_.truncation_level, p_.lambda_norm, p_.objective))
                 fail_str(err);
             if (!frdev::device_synchronize(&err)) fail_str(err);
             auto tb = tnow();

@@ -73,19 +73,24 @@ def lambdamart_sample(dataset: CDataset, params, tree: int) -> Tuple[np.ndarray,
 
 def lambda_gradients(model: CModel, dataset: CDataset, measure: str = "ndcg", sigma: float = 1.0,
                      qrel: Optional[CQRel] = None, n_total: Optional[int] = None, queries=None,
-                     truncation_level: int = 0, lambda_norm: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+                     truncation_level: int = 0, lambda_norm: bool = False, objective: str = "ndcg") -> Tuple[np.ndarray, np.ndarray]:
     """LambdaMART's gradient pass on the scores of `model`: (lambda, weight) indexed by instance id (NaN where the id is
     not part of a sampled dataset).  `queries`: indices of the view's queries (its order) the pass visits, as for a tree's
     query sample; the instances of the others come back NaN.  `truncation_level` >= 1 / `lambda_norm`: the objective's
-    options ("Truncation and normalisation"); at their defaults the call is the one it was."""
+    options ("Truncation and normalisation"); `objective`: "ndcg", "map" or "mrr" (section 11,
+    "Objectives"; `measure` must name NDCG all the same, and the norms are the AP / RR evaluator's).  At their defaults the
+    call is the one it was."""
     n = int(n_total if n_total is not None else _load().fr_dataset_num_instances(dataset.pointer))
     if n_total is None and dataset.is_sampled():
         n = 1 + max(max(ids) for ids in dataset.instances_by_query().values())
     lam = np.full(n, np.nan, dtype=np.float64)
     wt = np.full(n, np.nan, dtype=np.float64)
-    if int(truncation_level) != 0 or bool(lambda_norm):
+    if int(truncation_level) != 0 or bool(lambda_norm) or objective != "ndcg":
         qs = None if queries is None else np.ascontiguousarray(queries, dtype=np.uint32)
-        opts = json.dumps({"truncation_level": int(truncation_level), "lambda_norm": bool(lambda_norm)})
+        opts = {"truncation_level": int(truncation_level), "lambda_norm": bool(lambda_norm)}
+        if objective != "ndcg":
+            opts["objective"] = objective
+        opts = json.dumps(opts)
         _status(
             _load().fr_debug_lambda_gradients_opts(
                 model.pointer, dataset.pointer, None if qrel is None else qrel.pointer, measure.encode("utf-8"), float(sigma),

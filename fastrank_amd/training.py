@@ -108,7 +108,13 @@ class LambdaMARTParams(_LearnerParams):
     gradients) or T >= 1: a pair contributes only when the better ranked of the two is in the current top T.
     `lambda_norm` (default False): every query's gradients and weights are scaled by log2(1 + S_q) / S_q, S_q the query's
     summed pair terms, so that a few long queries do not dominate a tree.  Both growers; both keys are written only when
-    set ("Truncation and normalisation")."""
+    set ("Truncation and normalisation").
+    `objective`: "ndcg" (the default, not written), "map" or "mrr" ("ap" and "rr" are accepted and stored as "map" and
+    "mrr"): what the gradients optimise.  Under "map" / "mrr" a pair is one relevant (label > 0) and one non-relevant
+    document, weighted by the change of AP / RR their swap would make, and AP / RR takes over every role of the training
+    measure: the training stats' `train_measure`, `valid_measure`, `best_iteration`, early stopping and the printed table.
+    The request's `measure` must still name NDCG ("ndcg", "ndcg@k") -- "map" there is refused as before -- and is then read
+    for nothing else.  Both growers, every other key ("Objectives")."""
 
     VARIANT: ClassVar[str] = "LambdaMART"
 
@@ -132,11 +138,17 @@ class LambdaMARTParams(_LearnerParams):
     max_leaves: int = 0
     truncation_level: int = 0
     lambda_norm: bool = False
+    objective: str = "ndcg"
 
     _WIRE_DEFAULTS: ClassVar[Dict[str, Any]] = {"grower": "exact", "query_sampling_rate": 1.0, "feature_sampling_rate": 1.0, "seed": 0,
                                                 "validation_queries": [], "early_stopping_rounds": 0, "split_gain": "variance",
                                                 "lambda_l2": 0.0, "min_sum_hessian": 0.0, "min_split_gain": 0.0,
-                                                "max_leaves": 0, "truncation_level": 0, "lambda_norm": False}
+                                                "max_leaves": 0, "truncation_level": 0, "lambda_norm": False, "objective": "ndcg"}
+    _OBJECTIVES: ClassVar[Dict[str, str]] = {"ap": "map", "rr": "mrr"}
+
+    def __post_init__(self):
+        if isinstance(self.objective, str):  # (anything else is left for the request parser to refuse)
+            self.objective = self._OBJECTIVES.get(self.objective, self.objective)
 
     def to_dict(self) -> Dict[str, Any]:
         wire = dataclasses.asdict(self)

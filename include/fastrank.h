@@ -223,7 +223,12 @@ const CResult *fr_debug_hist_tree_leafwise(const CDataset *dataset, uint32_t spl
  * normalisation").  options_json = {"truncation_level": T, "lambda_norm": bool}, either key optional: T >= 1 keeps a pair
  * only when the better ranked of its two documents is in the top T of the pass's ranks (0, the default: every pair);
  * lambda_norm scales every query's lambda and weight by log2(1 + S_q) / S_q, S_q the query's summed pair terms.
- * queries[n_queries] as in fr_debug_lambda_gradients_sampled, or NULL for every query. */
+ * queries[n_queries] as in fr_debug_lambda_gradients_sampled, or NULL for every query.
+ * A third optional key, "objective": "ndcg" (the default), "map" or "mrr" ("ap" / "rr" are accepted) -- the LambdaMART
+ * variant's `objective` key ("Objectives"): a pair is then one relevant (gain > 0) and one
+ * non-relevant document, weighted by the change of AP / RR their swap would make, and the norms are the AP / RR
+ * evaluator's.  `measure` must still name NDCG (ndcg, ndcg@k) whatever the objective, as in a training request, where
+ * "measure": "map" is refused with or without the key. */
 const void *fr_debug_lambda_gradients_opts(const CModel *model, const CDataset *dataset, const CQRel *qrel,
                                            const void *measure, double sigma, const uint32_t *queries,
                                            size_t n_queries, const void *options_json, double *lambda_out,

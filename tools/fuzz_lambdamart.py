@@ -18,6 +18,9 @@ started on a device that may have faulted.
 and normalisation") from a generator of its own, so the cases themselves are those of a run without the flag; gradients
 are then held to tests/lambdamart_trunc_model.py (under lambda_norm at the tolerance derived in
 tests/test_gpu_lambdamart_trunc.py).
+--rank-objective map | mrr | mixed (off by default; `--objective` was taken by the options above): every case trains with
+that `objective` key ("mixed": drawn per case from ndcg, map, mrr) and is held to tests/lambdamart_objective_model.py; the
+measure every stage reports is then AP / RR ("Objectives").
 --dry: no device; the restatement trains each generated case on the CPU, and the share of cases on which the oracle's
 evaluator reports an error -- at zero scores or after any tree -- is printed.
 Usage: python tools/fuzz_lambdamart.py --iters 300 [--seed 0]"""
@@ -37,6 +40,7 @@ from fuzz_parity import make_case  # noqa: E402
 from oracle import pyoracle as o  # noqa: E402
 from tests import lambdamart_hist_model as hm  # noqa: E402
 from tests import lambdamart_model as lm  # noqa: E402
+from tests import lambdamart_objective_model as om  # noqa: E402
 from tests import lambdamart_trunc_model as tm  # noqa: E402
 from tests.conftest import ranksvm_presence  # noqa: E402
 
@@ -117,16 +121,39 @@ def write_ranksvm(rng, path, X, y, qid):
     return full
 
 
+RANK_OBJECTIVE, RANK_RNG = "ndcg", None  # --rank-objective, and the generator "mixed" draws from
+
+
 def draw_objective(rng):
-    """The objective's two keys for a case (none without --objective)."""
+    """The objective's keys for a case (none without --objective / --rank-objective)."""
+    out = {}
+    if RANK_OBJECTIVE != "ndcg":
+        name = RANK_OBJECTIVE
+        if name == "mixed":
+            name = str(RANK_RNG.choice(["ndcg", "map", "mrr"]))
+        if name != "ndcg":
+            out["objective"] = name
     if rng is None:
-        return {}
-    return dict(truncation_level=int(rng.choice([0, 1, 2, 5, 30])), lambda_norm=bool(rng.random() < 0.5))
+        return out
+    out.update(truncation_level=int(rng.choice([0, 1, 2, 5, 30])), lambda_norm=bool(rng.random() < 0.5))
+    return out
+
+
+def training_measure(measure, p):
+    """The measure the trainer reports: the objective's under map / mrr, else the request's."""
+    return {"map": "ap", "mrr": "rr"}.get(p.get("objective", "ndcg"), measure)
 
 
 def expected_gradients(s, y, queries, norms, depth, p):
     """(lambda, w, per-query rtol) of the restatement for the case's parameters."""
     T, norm = p.get("truncation_level", 0), p.get("lambda_norm", False)
+    if p.get("objective", "ndcg") != "ndcg":
+        elam, ewt, _, S, _ = om.gradients(s, y, queries, norms, p["objective"], p["sigma"], T, norm, parts=True)
+        rtol = np.full(len(queries), 1e-12)
+        if norm:
+            live = S > 0.0
+            rtol[live] = 3e-12 + 2.0 ** -52 / np.log1p(S[live]) + 12.0 * 2.0 ** -53
+        return elam, ewt, rtol
     if not T and not norm:
         elam, ewt = lm.gradients(s, y, queries, norms, depth, p["sigma"])
         return elam, ewt, np.full(len(queries), 1e-12)
@@ -190,7 +217,8 @@ class Case:
         self.c = o.Dataset(self.X, self.y, np.ascontiguousarray(qid[rows]))
         self.queries = lm.query_lists(self.c)
         self.order_ids = np.concatenate(self.queries)
-        self.norms = self.c.default_norms(self.measure)
+        self.reported = training_measure(self.measure, self.p)
+        self.norms = self.c.default_norms(self.reported)
 
     def train(self, req):
         try:
@@ -213,7 +241,8 @@ class Case:
 
     def device_gradients(self, model):
         lam, wt = self.native.lambda_gradients(model, self.g, self.measure, self.p["sigma"], n_total=self.n_total,
-                                               truncation_level=self.p.get("truncation_level", 0), lambda_norm=self.p.get("lambda_norm", False))
+                                               truncation_level=self.p.get("truncation_level", 0), lambda_norm=self.p.get("lambda_norm", False),
+                                               objective=self.p.get("objective", "ndcg"))
         return lam[self.rows], wt[self.rows]
 
     def scores(self, model):
@@ -243,7 +272,7 @@ class Case:
             prefix = self.prefix(trees, t)
             s = self.scores(prefix)
             if t > 0:
-                per_q, err = self.c.metric_from_scores(self.measure, s, self.norms)
+                per_q, err = self.c.metric_from_scores(self.reported, s, self.norms)
                 if err != 0 or st["train_measure"][t - 1] != o.mean(per_q):
                     return "train_measure[%d]" % (t - 1)
             if t == T:
@@ -294,11 +323,12 @@ def dry_case(rng, objective_rng=None):
     p.update(draw_objective(objective_rng))
     c = o.Dataset(X, y, qid)
     queries = lm.query_lists(c)
-    order_ids, norms, feats = np.concatenate(queries), c.default_norms(measure), list(range(X.shape[1]))
+    reported = training_measure(measure, p)
+    order_ids, norms, feats = np.concatenate(queries), c.default_norms(reported), list(range(X.shape[1]))
     binned = hm.bin_matrix(X, order_ids, feats, p["split_candidates"]) if p["grower"] == "histogram" else None
     s = np.zeros(len(y))
     for t in range(p["num_trees"] + 1):
-        if c.metric_from_scores(measure, s, norms)[1] != 0:
+        if c.metric_from_scores(reported, s, norms)[1] != 0:
             return True
         if t == p["num_trees"]:
             break
@@ -315,7 +345,10 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--dry", action="store_true", help="no device: the oracle evaluator's error rate while the restatement trains")
     ap.add_argument("--objective", action="store_true", help="draw a truncation level and lambda_norm for every case")
+    ap.add_argument("--rank-objective", default="ndcg", choices=["ndcg", "map", "mrr", "mixed"], help="the `objective` key of every case (mixed: drawn per case)")
     args = ap.parse_args()
+    global RANK_OBJECTIVE, RANK_RNG
+    RANK_OBJECTIVE, RANK_RNG = args.rank_objective, np.random.default_rng([args.seed, 2])
     rng = np.random.default_rng(args.seed)
     objective_rng = np.random.default_rng([args.seed, 1]) if args.objective else None
     o.set_mean_segment(o.DEVICE_MEAN_SEGMENT)

@@ -14,6 +14,8 @@
                                                                # leaf-wise growth under a leaf budget (reports the trees' shape)
     python tools/lmbench.py --shape 30k --trees 100 --grower histogram --truncation-level 30 --lambda-norm
                                                                # the objective's truncation level and per-query normalisation
+    python tools/lmbench.py --shape 30k --trees 100 --grower histogram --objective map --validation-rate 0.1
+                                                               # gradients for MAP ("mrr": for MRR); reports the held-out AP and RR
 Every other parameter is the LambdaMART default (TrainRequest.lambdamart()).
 """
 import argparse
@@ -57,6 +59,7 @@ def device_run(args, X, y, qid):
     if args.max_depth:
         req.params.max_depth = args.max_depth
     req.params.truncation_level, req.params.lambda_norm = args.truncation_level, args.lambda_norm
+    req.params.objective = args.objective
     # upload and first touch of the device (not part of training)
     native.device_info(ds)
     t_ds = time.perf_counter() - t0
@@ -100,6 +103,14 @@ def device_run(args, X, y, qid):
                            "max_depth": int(np.max(depths)), "pool_bytes": st["pool_bytes"]}
     if args.truncation_level or args.lambda_norm:  # (only when set, like the stats object)
         out["objective"] = {k: st[k] for k in ("truncation_level", "lambda_norm") if k in st}
+    if args.objective != "ndcg":
+        out.setdefault("objective", {})["objective"] = st["objective"]
+    if args.held_out_measures and args.validation_rate > 0:  # AP / RR / NDCG of the model over the held-out queries
+        held = set(req.params.validation_queries)
+        out["held_out"] = {}
+        for name in ("ap", "rr", "ndcg"):
+            by_q = ds.evaluate(model, name)
+            out["held_out"][name] = float(np.mean([v for q, v in sorted(by_q.items()) if q in held]))
     return out
 
 
@@ -151,6 +162,8 @@ def main():
     ap.add_argument("--max-depth", type=int, default=0, help="max_depth of the request (0: the default)")
     ap.add_argument("--truncation-level", type=int, default=0, help="a pair counts only when its better ranked document is in the top T (0: every pair)")
     ap.add_argument("--lambda-norm", action="store_true", help="scale every query's gradients by log2(1 + S_q) / S_q")
+    ap.add_argument("--objective", default="ndcg", choices=["ndcg", "map", "mrr"], help="what the gradients optimise (the measure stays an NDCG spelling)")
+    ap.add_argument("--held-out-measures", action="store_true", help="with --validation-rate: report the model's mean AP, RR and NDCG over the held-out queries")
     ap.add_argument("--warmup-trees", type=int, default=0, help="train this many trees untimed before the measured training")
     ap.add_argument("--no-kernel-profile", action="store_true", help="leave the library's per-kernel event timing off during the timed training")
     ap.add_argument("--cpu-baseline", type=float, default=0.0, help="query fraction for the CPU restatement (0: device run)")
