@@ -21,6 +21,7 @@ from tests import lambdamart_model as lm
 from tests import lambdamart_objective_model as om
 from tests import lambdamart_trunc_model as tm
 from tests import lambdamart_valid_model as vm
+from tests.lambdamart_composed_model import _ensemble, _names, _request
 from tests.conftest import GOLDEN, synth_dataset
 from tests.test_gpu_lambdamart_trunc import _norm_rtol
 
@@ -225,25 +226,6 @@ def test_objective_ndcg_and_the_key_absent_give_the_same_gradient_bytes(edge):
 
 
 # --- training ------------------------------------------------------------------------------------
-
-def _request(measure, grower, **kw):
-    req = fr.TrainRequest.lambdamart()
-    req.measure = measure
-    req.params.quiet = True
-    req.params.grower = grower
-    for k, v in kw.items():
-        setattr(req.params, k, v)
-    return req
-
-
-def _ensemble(trees, lr):
-    return fr.CModel.from_dict({"Ensemble": {"weights": [lr] * len(trees), "models": [{"DecisionTree": x} for x in trees]}})
-
-
-def _names(qid):
-    _, first = np.unique(qid, return_index=True)
-    return [str(int(qid[i])) for i in np.sort(first)]
-
 
 def _stagewise(case, grower, objective, params, trees_n=10, leafwise=None):
     X, y, qid, g, c = case

@@ -15,6 +15,7 @@ from tests import lambdamart_hist_model as hm
 from tests import lambdamart_model as lm
 from tests import lambdamart_sample_model as sm
 from tests import lambdamart_valid_model as vm
+from tests.lambdamart_composed_model import _ensemble, _names, _request
 from tests.conftest import GOLDEN, synth_dataset
 
 pytestmark = pytest.mark.gpu
@@ -22,22 +23,6 @@ pytestmark = pytest.mark.gpu
 VALID_KEYS = {"validation_queries", "training_queries", "valid_measure", "best_iteration", "best_valid_measure", "stopped_early",
               "early_stopping_rounds"}
 GROWERS = ["exact", "histogram"]
-
-
-def _request(measure="ndcg", grower="histogram", **kw):
-    req = fr.TrainRequest.lambdamart()
-    req.measure = measure
-    req.params.quiet = True
-    req.params.grower = grower
-    for k, v in kw.items():
-        setattr(req.params, k, v)
-    return req
-
-
-def _names(qid):
-    """The view's queries in its order (first appearance), as the dataset spells them."""
-    _, first = np.unique(qid, return_index=True)
-    return [str(int(qid[i])) for i in np.sort(first)]
 
 
 @pytest.fixture(scope="module")
@@ -54,10 +39,6 @@ def synth():
     X[::7, 3] = -0.0
     X[:, 9] = 2.5
     return X, y, qid, fr.CDataset.from_numpy(X, y, qid), o.Dataset(X, y, qid)
-
-
-def _ensemble(trees, lr):
-    return fr.CModel.from_dict({"Ensemble": {"weights": [lr] * len(trees), "models": [{"DecisionTree": x} for x in trees]}})
 
 
 def _trees(model):
