@@ -95,6 +95,14 @@ const CResult* c_call(F&& body) {
     return r;
 }
 
+// the model `make` returns as a CModel the caller owns (nothing is left behind when it throws)
+template <typename F>
+CModel* new_model(F&& make) {
+    std::unique_ptr<CModel> out(new CModel());
+    out->actual = make();
+    return out.release();
+}
+
 // NULL on success, else envelope string
 template <typename F>
 const void* status_call(F&& body) {
@@ -868,14 +876,7 @@ const CResult* train_model(void* train_request_json, void* dataset) {
 const CResult* model_from_json(const void* json_str) {
     return c_call<CModel>([&]() {
         Value v = parse_json_or_fail(accept_str("json_str", json_str));
-        auto* out = new CModel();
-        try {
-            out->actual = fr::model_from_json(v);
-        } catch (...) {
-            delete out;
-            throw;
-        }
-        return out;
+        return new_model([&] { return fr::model_from_json(v); });
     });
 }
 
@@ -1341,14 +1342,7 @@ const CResult* fr_select_model(const void* restarts_json, int output_ensemble) {
         // restart order defines "last maximum" (src/coordinate_ascent.rs:244-251)
         std::stable_sort(hist.begin(), hist.end(),
                          [](const fr::RestartResult& a, const fr::RestartResult& b) { return a.restart_id < b.restart_id; });
-        auto* out = new CModel();
-        try {
-            out->actual = fr::ca_select(hist, output_ensemble != 0);
-        } catch (...) {
-            delete out;
-            throw;
-        }
-        return out;
+        return new_model([&] { return fr::ca_select(hist, output_ensemble != 0); });
     });
 }
 
@@ -1377,26 +1371,6 @@ const void* fr_predict_scores_dense(const CModel* model, const CDataset* dataset
         fr::score_model(view, m.actual);
         std::string err;
         if (!dev.download_scores(0, out, out_len, &err)) fr::fail_str(err);
-    });
-}
-
-const void* fr_debug_lambda_gradients(const CModel* model, const CDataset* dataset, const CQRel* qrel, const void* measure,
-                                      double sigma, double* lambda_out, double* weight_out, size_t out_len) {
-    return status_call([&]() {
-        const CModel& m = require_model(model);
-        const CDataset& ds = require_dataset(dataset);
-        std::string name = accept_str("measure", measure);
-        fr::lambdamart_check_measure(name);
-        if (out_len && (!lambda_out || !weight_out)) fr::fail_str("NULL pointer: gradient outputs");
-        std::lock_guard<std::mutex> lk(api_mu_of(ds));
-        fr::DatasetView& view = *ds.view;
-        if (view.instances.empty()) return;
-        fr::Evaluator ev = fr::make_evaluator(view, name, qrel ? &qrel->actual : nullptr);
-        frdev::DeviceDataset& dev = view.device();
-        fr::score_model(view, m.actual);
-        std::string err;
-        if (!dev.lambda_gradients(ev.norms.data(), ev.depth, sigma, &err)) fr::fail_str(err);
-        if (!dev.lambda_download(lambda_out, weight_out, out_len, &err)) fr::fail_str(err);
     });
 }
 
@@ -1437,56 +1411,30 @@ const void* fr_debug_lambdamart_sample(const CDataset* dataset, const void* para
     });
 }
 
-// fr_debug_lambda_gradients for a query sample: queries[n_queries] = indices of the view's queries (its order).  Only their
-// instances are written.
-const void* fr_debug_lambda_gradients_sampled(const CModel* model, const CDataset* dataset, const CQRel* qrel, const void* measure,
-                                              double sigma, const uint32_t* queries, size_t n_queries, double* lambda_out,
-                                              double* weight_out, size_t out_len) {
+// The body of the three gradient hooks below: one gradient pass on the model's scores, downloaded by instance id.  queries ==
+// NULL: every query (need_queries: refused); else only the named queries' instances are computed and written.  options_json:
+// nullptr for a hook that takes no options, else the address of the caller's string (fr_debug_lambda_gradients_opts below).
+static const void* lambda_gradients_debug(const CModel* model, const CDataset* dataset, const CQRel* qrel, const void* measure, double sigma,
+                                          const uint32_t* queries, size_t n_queries, bool need_queries, const void* const* options_json,
+                                          double* lambda_out, double* weight_out, size_t out_len) {
     return status_call([&]() {
         const CModel& m = require_model(model);
         const CDataset& ds = require_dataset(dataset);
         std::string name = accept_str("measure", measure);
         fr::lambdamart_check_measure(name);
-        if (out_len && (!lambda_out || !weight_out)) fr::fail_str("NULL pointer: gradient outputs");
-        if (!queries) fr::fail_str("NULL pointer: query sample");
-        std::lock_guard<std::mutex> lk(api_mu_of(ds));
-        fr::DatasetView& view = *ds.view;
-        if (view.instances.empty()) return;
-        const std::vector<unsigned char> flags = debug_query_flags(queries, n_queries, view.host_csr().nq);
-        fr::Evaluator ev = fr::make_evaluator(view, name, qrel ? &qrel->actual : nullptr);
-        frdev::DeviceDataset& dev = view.device();
-        fr::score_model(view, m.actual);
-        std::string err;
-        if (!dev.lambda_gradients(ev.norms.data(), ev.depth, sigma, &err, flags.data())) fr::fail_str(err);
-        if (!dev.lambda_download(lambda_out, weight_out, out_len, &err, flags.data())) fr::fail_str(err);
-    });
-}
-
-// fr_debug_lambda_gradients under the objective's options (DESIGN.md section 11, "Truncation and normalisation"):
-// options_json = {"truncation_level": u32, "lambda_norm": bool, "objective": "ndcg" | "map" | "mrr"}, every key optional
-// (0 / false / "ndcg").  queries == NULL: the full pass; else the query sample of fr_debug_lambda_gradients_sampled.  With
-// every option at its default this is the pass of the two other hooks.  `measure` must name NDCG whatever the objective;
-// under "map" / "mrr" the norms are the AP / RR evaluator's (DESIGN.md section 11, "Objectives").
-const void* fr_debug_lambda_gradients_opts(const CModel* model, const CDataset* dataset, const CQRel* qrel, const void* measure,
-                                           double sigma, const uint32_t* queries, size_t n_queries, const void* options_json,
-                                           double* lambda_out, double* weight_out, size_t out_len) {
-    return status_call([&]() {
-        const CModel& m = require_model(model);
-        const CDataset& ds = require_dataset(dataset);
-        std::string name = accept_str("measure", measure);
-        fr::lambdamart_check_measure(name);
-        const Value opts = parse_json_or_fail(accept_str("options_json", options_json));
-        if (!opts.is_object()) fr::fail_raw("Error(\"invalid type: expected a map of gradient options\", line: 0, column: 0)");
-        uint32_t truncation_level = 0;
-        bool lambda_norm = false;
         fr::LambdaMARTParams op;
-        for (const auto& kv : opts.obj) {
-            if (kv.first == "truncation_level") truncation_level = fr::json_u32(kv.second, "truncation_level");
-            else if (kv.first == "lambda_norm") lambda_norm = fr::json_bool(kv.second, "lambda_norm");
-            else if (kv.first == "objective") op.objective = fr::LambdaMARTParams::objective_from_json(kv.second);
-            else fr::fail_raw("Error(\"unknown field `" + kv.first + "`, expected `truncation_level` or `lambda_norm`\", line: 0, column: 0)");
+        if (options_json) {
+            const Value opts = parse_json_or_fail(accept_str("options_json", *options_json));
+            if (!opts.is_object()) fr::fail_raw("Error(\"invalid type: expected a map of gradient options\", line: 0, column: 0)");
+            for (const auto& kv : opts.obj) {
+                if (kv.first == "truncation_level") op.truncation_level = fr::json_u32(kv.second, "truncation_level");
+                else if (kv.first == "lambda_norm") op.lambda_norm = fr::json_bool(kv.second, "lambda_norm");
+                else if (kv.first == "objective") op.objective = fr::LambdaMARTParams::objective_from_json(kv.second);
+                else fr::fail_raw("Error(\"unknown field `" + kv.first + "`, expected `truncation_level` or `lambda_norm`\", line: 0, column: 0)");
+            }
         }
         if (out_len && (!lambda_out || !weight_out)) fr::fail_str("NULL pointer: gradient outputs");
+        if (need_queries && !queries) fr::fail_str("NULL pointer: query sample");
         std::lock_guard<std::mutex> lk(api_mu_of(ds));
         fr::DatasetView& view = *ds.view;
         if (view.instances.empty()) return;
@@ -1497,9 +1445,33 @@ const void* fr_debug_lambda_gradients_opts(const CModel* model, const CDataset* 
         frdev::DeviceDataset& dev = view.device();
         fr::score_model(view, m.actual);
         std::string err;
-        if (!dev.lambda_gradients(ev.norms.data(), ev.depth, sigma, &err, fl, false, truncation_level, lambda_norm, op.objective)) fr::fail_str(err);
+        if (!dev.lambda_gradients(ev.norms.data(), ev.depth, sigma, op.pass(fl, false), &err)) fr::fail_str(err);
         if (!dev.lambda_download(lambda_out, weight_out, out_len, &err, fl)) fr::fail_str(err);
     });
+}
+
+const void* fr_debug_lambda_gradients(const CModel* model, const CDataset* dataset, const CQRel* qrel, const void* measure,
+                                      double sigma, double* lambda_out, double* weight_out, size_t out_len) {
+    return lambda_gradients_debug(model, dataset, qrel, measure, sigma, nullptr, 0, false, nullptr, lambda_out, weight_out, out_len);
+}
+
+// fr_debug_lambda_gradients for a query sample: queries[n_queries] = indices of the view's queries (its order).  Only their
+// instances are written.
+const void* fr_debug_lambda_gradients_sampled(const CModel* model, const CDataset* dataset, const CQRel* qrel, const void* measure,
+                                              double sigma, const uint32_t* queries, size_t n_queries, double* lambda_out,
+                                              double* weight_out, size_t out_len) {
+    return lambda_gradients_debug(model, dataset, qrel, measure, sigma, queries, n_queries, true, nullptr, lambda_out, weight_out, out_len);
+}
+
+// fr_debug_lambda_gradients under the objective's options (DESIGN.md section 11, "Truncation and normalisation"):
+// options_json = {"truncation_level": u32, "lambda_norm": bool, "objective": "ndcg" | "map" | "mrr"}, every key optional
+// (0 / false / "ndcg").  queries == NULL: the full pass; else the query sample of fr_debug_lambda_gradients_sampled.  With
+// every option at its default this is the pass of the two other hooks.  `measure` must name NDCG whatever the objective;
+// under "map" / "mrr" the norms are the AP / RR evaluator's (DESIGN.md section 11, "Objectives").
+const void* fr_debug_lambda_gradients_opts(const CModel* model, const CDataset* dataset, const CQRel* qrel, const void* measure,
+                                           double sigma, const uint32_t* queries, size_t n_queries, const void* options_json,
+                                           double* lambda_out, double* weight_out, size_t out_len) {
+    return lambda_gradients_debug(model, dataset, qrel, measure, sigma, queries, n_queries, false, &options_json, lambda_out, weight_out, out_len);
 }
 
 // the histogram grower's inputs for a view: its instance list and their positions, its features ascending
@@ -1535,46 +1507,15 @@ const void* fr_debug_hist_bins(const CDataset* dataset, uint32_t split_candidate
     });
 }
 
-const CResult* fr_debug_hist_tree(const CDataset* dataset, uint32_t split_candidates, uint32_t max_depth, uint32_t min_leaf_support,
-                                  const double* lambda, const double* weight, size_t len) {
+// The body of the four tree hooks below.  who: the exported function's name, for its error messages; opt: what the grower is
+// made with; queries / features: the tree's sample as fr_debug_hist_tree_sampled describes it.
+static const CResult* hist_tree_debug(const std::string& who, const CDataset* dataset, const fr::HistGrowOptions& opt, const double* lambda,
+                                      const double* weight, size_t len, const uint32_t* queries, size_t n_queries, const uint32_t* features,
+                                      size_t n_features) {
     return c_call<CModel>([&]() {
         const CDataset& ds = require_dataset(dataset);
         if (!lambda || !weight) fr::fail_str("NULL pointer: gradient inputs");
-        if (max_depth < 1) fr::fail_str("max_depth must be at least 1");
-        std::lock_guard<std::mutex> lk(api_mu_of(ds));
-        fr::DatasetView& view = *ds.view;
-        std::vector<uint32_t> ids, positions, feats;
-        hist_debug_lists(view, &ids, &positions, &feats);
-        std::vector<double> lam(ids.size()), wt(ids.size());
-        for (size_t i = 0; i < ids.size(); i++) {
-            if (ids[i] >= len) fr::fail_str("fr_debug_hist_tree: the gradient arrays are shorter than the largest instance id");
-            lam[i] = lambda[ids[i]];
-            wt[i] = weight[ids[i]];
-        }
-        fr::HistGrower grower(view.device(), feats, split_candidates, max_depth, min_leaf_support);
-        grower.prepare(positions);
-        auto* out = new CModel();
-        try {
-            out->actual.kind = fr::Model::DecisionTree;
-            out->actual.tree = grower.grow(lam.data(), wt.data());
-        } catch (...) {
-            delete out;
-            throw;
-        }
-        return out;
-    });
-}
-
-// The body of the sampled hooks below.  who: the exported function's name, for its error messages; newton: the split
-// criterion the grower is made with (HistNewton(): the variance criterion); max_leaves: 0 = level-wise growth.
-static const CResult* hist_tree_debug(const std::string& who, const CDataset* dataset, uint32_t split_candidates, uint32_t max_depth,
-                                      uint32_t min_leaf_support, const double* lambda, const double* weight, size_t len,
-                                      const uint32_t* queries, size_t n_queries, const uint32_t* features, size_t n_features,
-                                      const fr::HistNewton& newton, uint32_t max_leaves = 0) {
-    return c_call<CModel>([&]() {
-        const CDataset& ds = require_dataset(dataset);
-        if (!lambda || !weight) fr::fail_str("NULL pointer: gradient inputs");
-        if (max_depth < 1) fr::fail_str("max_depth must be at least 1");
+        if (opt.max_depth < 1) fr::fail_str("max_depth must be at least 1");
         std::lock_guard<std::mutex> lk(api_mu_of(ds));
         fr::DatasetView& view = *ds.view;
         const frdev::HostCSR& csr = view.host_csr();
@@ -1605,13 +1546,13 @@ static const CResult* hist_tree_debug(const std::string& who, const CDataset* da
             for (size_t j = csr.qoff[q]; j < csr.qoff[q + 1]; j++, g++) {
                 if (ids[g] >= len) {
                     if (queries && !flags[q]) continue;
-                    fr::fail_str(who + ": the gradient arrays are shorter than the largest sampled instance id");
+                    fr::fail_str(who + ": the gradient arrays are shorter than the largest " + (queries ? "sampled " : "") + "instance id");
                 }
                 lam[g] = lambda[ids[g]];
                 wt[g] = weight[ids[g]];
             }
         }
-        fr::HistGrower grower(view.device(), feats, split_candidates, max_depth, min_leaf_support, newton, max_leaves);
+        fr::HistGrower grower(view.device(), feats, opt);
         grower.prepare(positions);
         struct Unsample {  // (the bins stay with the view: leave them without a sample, also when growing fails)
             fr::HistGrower& g;
@@ -1623,16 +1564,18 @@ static const CResult* hist_tree_debug(const std::string& who, const CDataset* da
             }
         } unsample{grower};
         grower.set_sample(queries ? flags.data() : nullptr, (uint32_t)n_t, features ? &sel : nullptr);
-        auto* out = new CModel();
-        try {
-            out->actual.kind = fr::Model::DecisionTree;
-            out->actual.tree = grower.grow(lam.data(), wt.data());
-        } catch (...) {
-            delete out;
-            throw;
-        }
-        return out;
+        return new_model([&] {
+            fr::Model tree;
+            tree.kind = fr::Model::DecisionTree;
+            tree.tree = grower.grow(lam.data(), wt.data());
+            return tree;
+        });
     });
+}
+
+const CResult* fr_debug_hist_tree(const CDataset* dataset, uint32_t split_candidates, uint32_t max_depth, uint32_t min_leaf_support,
+                                  const double* lambda, const double* weight, size_t len) {
+    return hist_tree_debug("fr_debug_hist_tree", dataset, {split_candidates, max_depth, min_leaf_support}, lambda, weight, len, nullptr, 0, nullptr, 0);
 }
 
 // fr_debug_hist_tree on a sample: queries[n_queries] = indices of the view's queries (NULL: all), features[n_features] =
@@ -1640,8 +1583,8 @@ static const CResult* hist_tree_debug(const std::string& who, const CDataset* da
 const CResult* fr_debug_hist_tree_sampled(const CDataset* dataset, uint32_t split_candidates, uint32_t max_depth, uint32_t min_leaf_support,
                                           const double* lambda, const double* weight, size_t len, const uint32_t* queries,
                                           size_t n_queries, const uint32_t* features, size_t n_features) {
-    return hist_tree_debug("fr_debug_hist_tree_sampled", dataset, split_candidates, max_depth, min_leaf_support, lambda, weight, len, queries,
-                           n_queries, features, n_features, fr::HistNewton());
+    return hist_tree_debug("fr_debug_hist_tree_sampled", dataset, {split_candidates, max_depth, min_leaf_support}, lambda, weight, len, queries,
+                           n_queries, features, n_features);
 }
 
 // fr_debug_hist_tree_sampled under the Newton split gain ("Newton split gain")
@@ -1653,8 +1596,9 @@ const CResult* fr_debug_hist_tree_newton(const CDataset* dataset, uint32_t split
     for (double x : numbers)
         if (!(std::isfinite(x) && x >= 0.0))
             return c_call<CModel>([&]() -> CModel* { fr::fail_str("fr_debug_hist_tree_newton: lambda_l2, min_sum_hessian and min_split_gain must be finite and at least 0"); });
-    return hist_tree_debug("fr_debug_hist_tree_newton", dataset, split_candidates, max_depth, min_leaf_support, lambda, weight, len, queries,
-                           n_queries, features, n_features, fr::HistNewton{true, lambda_l2, min_sum_hessian, min_split_gain});
+    return hist_tree_debug("fr_debug_hist_tree_newton", dataset,
+                           {split_candidates, max_depth, min_leaf_support, fr::HistNewton{true, lambda_l2, min_sum_hessian, min_split_gain}}, lambda,
+                           weight, len, queries, n_queries, features, n_features);
 }
 
 // One tree grown leaf-wise ("Leaf-wise growth"): fr_debug_hist_tree_sampled / _newton (newton != 0: the
@@ -1669,9 +1613,9 @@ const CResult* fr_debug_hist_tree_leafwise(const CDataset* dataset, uint32_t spl
     for (double x : numbers)
         if (!(std::isfinite(x) && x >= 0.0) || (!newton && x != 0.0))
             return c_call<CModel>([&]() -> CModel* { fr::fail_str("fr_debug_hist_tree_leafwise: lambda_l2, min_sum_hessian and min_split_gain must be finite and at least 0, and 0 without the Newton gain"); });
-    return hist_tree_debug("fr_debug_hist_tree_leafwise", dataset, split_candidates, max_depth, min_leaf_support, lambda, weight, len, queries,
-                           n_queries, features, n_features,
-                           newton ? fr::HistNewton{true, lambda_l2, min_sum_hessian, min_split_gain} : fr::HistNewton(), max_leaves);
+    const fr::HistNewton gain = newton ? fr::HistNewton{true, lambda_l2, min_sum_hessian, min_split_gain} : fr::HistNewton();
+    return hist_tree_debug("fr_debug_hist_tree_leafwise", dataset, {split_candidates, max_depth, min_leaf_support, gain, max_leaves}, lambda, weight,
+                           len, queries, n_queries, features, n_features);
 }
 
 const void* fr_evaluate_dense(const CModel* model, const CDataset* dataset, const CQRel* qrel,

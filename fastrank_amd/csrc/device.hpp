@@ -307,17 +307,23 @@ class DeviceDataset {
     // --- LambdaMART gradients (kernels_lambda.inc) ------------------------------------------------
     // One gradient pass on score slot 0: per document the LambdaRank gradient lambda and weight w (f64) and float(lambda),
     // the split target rf_begin(.., lambda_targets = true) reads.  norms[nq]: the NDCG evaluator's; depth < 0 = None.
-    // query_flags[nq] (optional): only queries with a non-zero flag are visited (still longest first); they get the bits
-    // the full pass gives them, the values of the others are left as they were and must not be read.
-    // flags_unchanged: query_flags are those of the previous call (a fixed training split): the filtered query list already
-    // on the device is used again, nothing is uploaded.
-    // truncation_level T >= 1: a pair contributes only when the better ranked of its documents is in the top T (0: every
-    // pair); lambda_norm: every query's lambda and w are scaled by log2(1 + S_q) / S_q.  With either set the pass runs
-    // lambda_grad_trunc_kernel, with neither lambda_grad_kernel ("Truncation and normalisation").
-    // objective: 0 = NDCG (the pair weight is |delta NDCG|), 1 = MAP, 2 = MRR; norms are then the AP / RR evaluator's and
-    // depth is not read ("Objectives").  The same two kernels, instantiated for the objective.
-    bool lambda_gradients(const double* norms, int64_t depth, double sigma, std::string* err, const unsigned char* query_flags = nullptr,
-                          bool flags_unchanged = false, uint32_t truncation_level = 0, bool lambda_norm = false, int objective = 0);
+    struct LambdaPass {
+        // [nq] (optional): only queries with a non-zero flag are visited (still longest first); they get the bits the full
+        // pass gives them, the values of the others are left as they were and must not be read
+        const unsigned char* query_flags = nullptr;
+        // query_flags are those of the previous call (a fixed training split): the filtered query list already on the device
+        // is used again, nothing is uploaded
+        bool flags_unchanged = false;
+        // T >= 1: a pair contributes only when the better ranked of its documents is in the top T (0: every pair)
+        uint32_t truncation_level = 0;
+        // every query's lambda and w are scaled by log2(1 + S_q) / S_q.  With this or a level set the pass runs
+        // lambda_grad_trunc_kernel, with neither lambda_grad_kernel ("Truncation and normalisation")
+        bool lambda_norm = false;
+        // 0 = NDCG (the pair weight is |delta NDCG|), 1 = MAP, 2 = MRR; norms are then the AP / RR evaluator's and depth is
+        // not read ("Objectives").  The same two kernels, instantiated for the objective
+        int objective = 0;
+    };
+    bool lambda_gradients(const double* norms, int64_t depth, double sigma, const LambdaPass& pass, std::string* err);
     // the last pass's lambda / w by padded position ([np] each)
     bool lambda_download_positions(std::vector<double>* lambda, std::vector<double>* weight, std::string* err);
     // ... scattered to original instance ids (ids outside this dataset or >= out_len are left untouched)

@@ -3963,8 +3963,7 @@ bool DeviceDataset::Impl::lm_build(std::string* err) {
     return true;
 }
 
-bool DeviceDataset::lambda_gradients(const double* norms, int64_t depth, double sigma, std::string* err, const unsigned char* query_flags,
-                                     bool flags_unchanged, uint32_t truncation_level, bool lambda_norm, int objective) {
+bool DeviceDataset::lambda_gradients(const double* norms, int64_t depth, double sigma, const LambdaPass& pass, std::string* err) {
     Impl& m = *impl_;
     std::lock_guard<std::mutex> lk(m.mu);
     if (!m.bind(err)) return false;
@@ -3972,8 +3971,8 @@ bool DeviceDataset::lambda_gradients(const double* norms, int64_t depth, double 
         if (err) *err = "lambda_gradients: no scores resident";
         return false;
     }
-    if (objective < LM_OBJ_NDCG || objective > LM_OBJ_MRR) {
-        if (err) *err = "lambda_gradients: unknown objective " + std::to_string(objective);
+    if (pass.objective < LM_OBJ_NDCG || pass.objective > LM_OBJ_MRR) {
+        if (err) *err = "lambda_gradients: unknown objective " + std::to_string(pass.objective);
         return false;
     }
     if (!m.lm_build(err)) return false;
@@ -3982,14 +3981,14 @@ bool DeviceDataset::lambda_gradients(const double* norms, int64_t depth, double 
     uint32_t n_long = (uint32_t)m.nq - lm.n_lds, n_lds = lm.n_lds;
     const uint32_t* qorder = lm.qorder.p;
     size_t longest = n_long < m.nq ? std::min<size_t>(lm.max_len, LM_LDS_MAX / LM_STAGE_BYTES) : 0;
-    if (query_flags != nullptr) {  // a tree's query sample: qorder filtered, its order kept (slab queries still open the pass)
-        if (!(flags_unchanged && lm.qsel_valid)) {
+    if (pass.query_flags != nullptr) {  // a tree's query sample: qorder filtered, its order kept (slab queries still open the pass)
+        if (!(pass.flags_unchanged && lm.qsel_valid)) {
             lm.qsel_valid = false;
             lm.qsel_h.clear();
             lm.sel_long = 0;
             for (size_t i = 0; i < m.nq; i++) {
                 const uint32_t q = lm.order_h[i];
-                if (!query_flags[q]) continue;
+                if (!pass.query_flags[q]) continue;
                 if (i < n_long) lm.sel_long++;
                 lm.qsel_h.push_back(q);
             }
@@ -4003,31 +4002,31 @@ bool DeviceDataset::lambda_gradients(const double* norms, int64_t depth, double 
         qorder = lm.qsel.p;
         longest = n_lds ? m.qlen_h[lm.qsel_h[n_long]] : 0;  // (the longest sampled query that is staged in LDS)
     }
-    if (truncation_level != 0 || lambda_norm) {  // DESIGN.md section 11, "Truncation and normalisation": a kernel of its own
-        const uint32_t trunc = truncation_level != 0 ? truncation_level : 0xFFFFFFFFu;  // (no level: every rank is inside)
-        if (lambda_norm && !lm.asum.ensure(m.np, err)) return false;
+    if (pass.truncation_level != 0 || pass.lambda_norm) {  // DESIGN.md section 11, "Truncation and normalisation": a kernel of its own
+        const uint32_t trunc = pass.truncation_level != 0 ? pass.truncation_level : 0xFFFFFFFFu;  // (no level: every rank is inside)
+        if (pass.lambda_norm && !lm.asum.ensure(m.np, err)) return false;
         ProfScope ps("lambda_grad_trunc_kernel", m.stream);
-        auto* const kernel = objective == LM_OBJ_MAP ? lambda_grad_trunc_kernel<LM_OBJ_MAP>
-                             : objective == LM_OBJ_MRR ? lambda_grad_trunc_kernel<LM_OBJ_MRR> : lambda_grad_trunc_kernel<LM_OBJ_NDCG>;
+        auto* const kernel = pass.objective == LM_OBJ_MAP ? lambda_grad_trunc_kernel<LM_OBJ_MAP>
+                             : pass.objective == LM_OBJ_MRR ? lambda_grad_trunc_kernel<LM_OBJ_MRR> : lambda_grad_trunc_kernel<LM_OBJ_NDCG>;
         for (uint32_t q0 = 0; q0 < n_long; q0 += LM_SLAB_BLOCKS) {
             const uint32_t cnt = std::min<uint32_t>(LM_SLAB_BLOCKS, n_long - q0);
             kernel<<<cnt, 256, 0, m.stream>>>(m.scores.p, lm.off.p, lm.pos.p, qorder, q0, m.gain.p, m.gexp.p, m.disc.p, m.perm.p, m.norms.p,
-                                              depth, sigma, trunc, lambda_norm ? 1 : 0, lm.lam.p, lm.wt.p, lm.target.p, lm.asum.p, lm.slab.p,
+                                              depth, sigma, trunc, pass.lambda_norm ? 1 : 0, lm.lam.p, lm.wt.p, lm.target.p, lm.asum.p, lm.slab.p,
                                               lm.max_len);
         }
         if (n_lds != 0) {
             const size_t bytes = std::max<size_t>(longest * LM_STAGE_BYTES, 64);
             FR_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
             kernel<<<n_lds, 256, bytes, m.stream>>>(m.scores.p, lm.off.p, lm.pos.p, qorder, n_long, m.gain.p, m.gexp.p, m.disc.p, m.perm.p,
-                                                    m.norms.p, depth, sigma, trunc, lambda_norm ? 1 : 0, lm.lam.p, lm.wt.p, lm.target.p,
+                                                    m.norms.p, depth, sigma, trunc, pass.lambda_norm ? 1 : 0, lm.lam.p, lm.wt.p, lm.target.p,
                                                     lm.asum.p, nullptr, 0u);
         }
         FR_HIP(hipGetLastError());
         return true;
     }
     ProfScope ps("lambda_grad_kernel", m.stream);
-    auto* const kernel = objective == LM_OBJ_MAP ? lambda_grad_kernel<LM_OBJ_MAP>
-                         : objective == LM_OBJ_MRR ? lambda_grad_kernel<LM_OBJ_MRR> : lambda_grad_kernel<LM_OBJ_NDCG>;
+    auto* const kernel = pass.objective == LM_OBJ_MAP ? lambda_grad_kernel<LM_OBJ_MAP>
+                         : pass.objective == LM_OBJ_MRR ? lambda_grad_kernel<LM_OBJ_MRR> : lambda_grad_kernel<LM_OBJ_NDCG>;
     for (uint32_t q0 = 0; q0 < n_long; q0 += LM_SLAB_BLOCKS) {  // (longest first: these open the pass)
         const uint32_t cnt = std::min<uint32_t>(LM_SLAB_BLOCKS, n_long - q0);
         kernel<<<cnt, 256, 0, m.stream>>>(m.scores.p, lm.off.p, lm.pos.p, qorder, q0, m.gain.p, m.gexp.p, m.disc.p, m.perm.p, m.norms.p, depth,

@@ -29,6 +29,8 @@
 // objective = "map" / "mrr" (both growers; DESIGN.md section 11, "Objectives"): the pair weight is |delta AP| / |delta RR| of
 // swapping a relevant and a non-relevant document, and the trainer's evaluator is the AP / RR one: gradient norms, the
 // reported measures, the best iteration and early stopping all follow it.  The request's `measure` must still name NDCG.
+// A request's keys live in LambdaMARTParams alone: the gradient pass and the histogram grower get their options from it
+// (pass(), hist_options()), and the stats keep a copy of it (LambdaMARTStats::request) to report from.
 #pragma once
 #include <chrono>
 #include <cmath>
@@ -73,6 +75,13 @@ struct LambdaMARTParams {
     // the evaluator the trainer gets under `objective` (the request's own measure is then read for nothing else)
     const char* objective_measure() const { return objective == frdev::M_AP ? "ap" : objective == frdev::M_RR ? "rr" : nullptr; }
     bool sampling() const { return query_sampling_rate < 1.0 || feature_sampling_rate < 1.0; }
+    // a gradient pass under this request: over the flagged queries (nullptr: all), `unchanged` since the pass before
+    frdev::DeviceDataset::LambdaPass pass(const unsigned char* flags, bool unchanged) const {
+        return {flags, unchanged, truncation_level, lambda_norm, objective};
+    }
+    HistGrowOptions hist_options() const {
+        return {split_candidates, max_depth, min_leaf_support, HistNewton{newton, lambda_l2, min_sum_hessian, min_split_gain}, max_leaves};
+    }
     [[noreturn]] static void invalid(const std::string& what) {
         fail_raw("Error(\"invalid value: " + what + "\", line: 0, column: 0)");
     }
@@ -248,33 +257,24 @@ inline LambdaSample lambdamart_next_sample(Rand64& master, size_t n_features, si
 }
 
 struct LambdaMARTStats {
+    LambdaMARTParams request;  // what was asked for: the keys reported below are read from it
     uint32_t trees = 0;
     double seconds = 0.0;
     double t_gradient = 0.0, t_grow = 0.0, t_leaves = 0.0, t_update = 0.0;  // wall seconds per stage (device work waited for)
     std::vector<double> train_measure;                                        // evaluator mean of the running scores after each tree
-    bool histogram = false;
-    uint32_t bins = 0;     // histogram grower: k
     double t_bins = 0.0;   // one-off binning (0 when the view's kept bins were reused, and for the exact grower)
-    // per-tree samples (reported only when a rate is below 1): the request's keys and the trees' mean sample sizes
-    bool sampling = false;
-    double query_sampling_rate = 1.0, feature_sampling_rate = 1.0;
-    uint64_t seed = 0, sum_queries = 0, sum_instances = 0, sum_features = 0;
+    // per-tree samples (reported only when a rate is below 1, with the request's keys): the trees' summed sample sizes
+    uint64_t sum_queries = 0, sum_instances = 0, sum_features = 0;
     // held-out queries (reported only when there are any): with them train_measure is the mean over the training queries
-    bool validation = false, stopped_early = false;
-    uint32_t validation_queries = 0, training_queries = 0, best_iteration = 0, early_stopping_rounds = 0;
+    bool stopped_early = false;
+    uint32_t validation_queries = 0, training_queries = 0, best_iteration = 0;
     std::vector<double> valid_measure;  // evaluator mean of the running scores over the held-out queries after each tree
-    // the Newton gain (reported only under split_gain = "newton"): the request's keys
-    bool newton = false;
-    double lambda_l2 = 0.0, min_sum_hessian = 0.0, min_split_gain = 0.0;
-    // leaf-wise growth (reported only when max_leaves is set): the request's key and the trees' mean number of leaves
-    uint32_t max_leaves = 0;
-    // the objective's options (each reported only when set): the request's keys
-    uint32_t truncation_level = 0;
-    bool lambda_norm = false;
-    int objective = frdev::M_NDCG;  // (reported only when it is not NDCG)
-    uint64_t sum_leaves = 0, pool_bytes = 0;  // pool_bytes: the histogram pool (slots x the tree's features x bins x 12 or 20 B), the largest over the trees
+    // leaf-wise growth (reported only when max_leaves is set): the trees' summed numbers of leaves, and the histogram pool
+    // (slots x the tree's features x bins x 12 or 20 B), the largest over the trees
+    uint64_t sum_leaves = 0, pool_bytes = 0;
 
     Value to_json() const {
+        const LambdaMARTParams& r = request;
         Value o = Value::object();
         o.set("trees", Value::uint(trees));
         o.set("seconds", Value::number(seconds));
@@ -282,14 +282,14 @@ struct LambdaMARTStats {
         o.set("grow_ms", Value::number(t_grow * 1e3));
         o.set("leaves_ms", Value::number(t_leaves * 1e3));
         o.set("update_ms", Value::number(t_update * 1e3));
-        o.set("grower", Value::string(histogram ? "histogram" : "exact"));
+        o.set("grower", Value::string(r.histogram ? "histogram" : "exact"));
         o.set("bins_ms", Value::number(t_bins * 1e3));
-        if (histogram) o.set("bins", Value::uint(bins));
-        if (sampling) {
+        if (r.histogram) o.set("bins", Value::uint(r.split_candidates));
+        if (r.sampling()) {
             const double T = trees ? (double)trees : 1.0;
-            o.set("query_sampling_rate", Value::number(query_sampling_rate));
-            o.set("feature_sampling_rate", Value::number(feature_sampling_rate));
-            o.set("seed", Value::uint(seed));
+            o.set("query_sampling_rate", Value::number(r.query_sampling_rate));
+            o.set("feature_sampling_rate", Value::number(r.feature_sampling_rate));
+            o.set("seed", Value::uint(r.seed));
             o.set("sample_queries", Value::number((double)sum_queries / T));
             o.set("sample_instances", Value::number((double)sum_instances / T));
             o.set("sample_features", Value::number((double)sum_features / T));
@@ -297,7 +297,7 @@ struct LambdaMARTStats {
         Value a = Value::array();
         for (double x : train_measure) a.push(Value::number(x));
         o.set("train_measure", std::move(a));
-        if (validation) {
+        if (validation_queries != 0) {
             o.set("validation_queries", Value::uint(validation_queries));
             o.set("training_queries", Value::uint(training_queries));
             Value b = Value::array();
@@ -306,22 +306,23 @@ struct LambdaMARTStats {
             o.set("best_iteration", Value::uint(best_iteration));
             o.set("best_valid_measure", Value::number(best_iteration ? valid_measure[best_iteration - 1] : 0.0));
             o.set("stopped_early", Value::boolean(stopped_early));
-            o.set("early_stopping_rounds", Value::uint(early_stopping_rounds));
+            o.set("early_stopping_rounds", Value::uint(r.early_stopping_rounds));
         }
-        if (newton) {
+        // (the Newton gain and the leaf budget are the histogram grower's: a request sets them with no other)
+        if (r.histogram && r.newton) {
             o.set("split_gain", Value::string("newton"));
-            o.set("lambda_l2", Value::number(lambda_l2));
-            o.set("min_sum_hessian", Value::number(min_sum_hessian));
-            o.set("min_split_gain", Value::number(min_split_gain));
+            o.set("lambda_l2", Value::number(r.lambda_l2));
+            o.set("min_sum_hessian", Value::number(r.min_sum_hessian));
+            o.set("min_split_gain", Value::number(r.min_split_gain));
         }
-        if (max_leaves != 0) {
-            o.set("max_leaves", Value::uint(max_leaves));
+        if (r.histogram && r.max_leaves != 0) {
+            o.set("max_leaves", Value::uint(r.max_leaves));
             o.set("mean_leaves", Value::number((double)sum_leaves / (trees ? (double)trees : 1.0)));
             o.set("pool_bytes", Value::uint(pool_bytes));
         }
-        if (truncation_level != 0) o.set("truncation_level", Value::uint(truncation_level));
-        if (lambda_norm) o.set("lambda_norm", Value::boolean(true));
-        if (objective != frdev::M_NDCG) o.set("objective", Value::string(LambdaMARTParams::objective_name(objective)));
+        if (r.truncation_level != 0) o.set("truncation_level", Value::uint(r.truncation_level));
+        if (r.lambda_norm) o.set("lambda_norm", Value::boolean(true));
+        if (r.objective != frdev::M_NDCG) o.set("objective", Value::string(LambdaMARTParams::objective_name(r.objective)));
         return o;
     }
 };
@@ -333,6 +334,7 @@ class LambdaMARTTrainer {
 
     Model learn() {
         auto t0 = std::chrono::steady_clock::now();
+        stats_.request = p_;
         auto tnow = [] { return std::chrono::steady_clock::now(); };
         auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
             return std::chrono::duration<double>(b - a).count();
@@ -362,18 +364,11 @@ class LambdaMARTTrainer {
         uint32_t max_id = 0;
         for (uint32_t id : root_ids) max_id = std::max(max_id, id);
 
-        stats_.histogram = p_.histogram;
-        stats_.truncation_level = p_.truncation_level, stats_.lambda_norm = p_.lambda_norm, stats_.objective = p_.objective;
         std::unique_ptr<HistGrower> hist;
         if (p_.histogram) {
-            hist.reset(new HistGrower(dev, feats, p_.split_candidates, p_.max_depth, p_.min_leaf_support,
-                                      HistNewton{p_.newton, p_.lambda_l2, p_.min_sum_hessian, p_.min_split_gain}, p_.max_leaves));
-            stats_.max_leaves = p_.max_leaves;
-            stats_.newton = p_.newton;
-            stats_.lambda_l2 = p_.lambda_l2, stats_.min_sum_hessian = p_.min_sum_hessian, stats_.min_split_gain = p_.min_split_gain;
+            hist.reset(new HistGrower(dev, feats, p_.hist_options()));
             auto tb0 = tnow();
             if (hist->prepare(positions)) stats_.t_bins = secs(tb0, tnow());
-            stats_.bins = p_.split_candidates;
         }
         RFParams rp;
         rp.quiet = true;
@@ -404,8 +399,6 @@ class LambdaMARTTrainer {
         // held-out queries: every tree's query list is a subset of T -- T itself, set once, without a query rate
         const bool sampling = p_.sampling(), sample_q = p_.query_sampling_rate < 1.0, sample_f = p_.feature_sampling_rate < 1.0;
         const bool subset_q = sample_q || hold, fixed_q = hold && !sample_q;
-        stats_.sampling = sampling;
-        stats_.query_sampling_rate = p_.query_sampling_rate, stats_.feature_sampling_rate = p_.feature_sampling_rate, stats_.seed = p_.seed;
         Rand64 master(p_.seed);
         std::vector<unsigned char> qflags;
         std::vector<uint32_t> t_ids, t_pos, t_feats, t_off;
@@ -426,9 +419,7 @@ class LambdaMARTTrainer {
             t_off = {0u, (uint32_t)t_ids.size()};
         };
         if (hold) {
-            stats_.validation = true;
             stats_.validation_queries = (uint32_t)split.held.size(), stats_.training_queries = (uint32_t)split.train.size();
-            stats_.early_stopping_rounds = p_.early_stopping_rounds;
             if (!dev.subset_means_set(split.train, split.held, &err)) fail_str(err);
             if (fixed_q) {
                 take_queries(split.train);
@@ -455,8 +446,7 @@ class LambdaMARTTrainer {
             }
             if (subset_q && !hist) ids_t = &t_ids, off_t = &t_off, pos_t = t_pos.data();
             auto ta = tnow();
-            if (!dev.lambda_gradients(ev_.norms.data(), ev_.depth, p_.sigma, &err, subset_q ? qflags.data() : nullptr, fixed_q && t > 0,
-                                      p_.truncation_level, p_.lambda_norm, p_.objective))
+            if (!dev.lambda_gradients(ev_.norms.data(), ev_.depth, p_.sigma, p_.pass(subset_q ? qflags.data() : nullptr, fixed_q && t > 0), &err))
                 fail_str(err);
             if (!frdev::device_synchronize(&err)) fail_str(err);
             auto tb = tnow();

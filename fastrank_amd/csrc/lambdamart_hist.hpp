@@ -26,11 +26,18 @@ struct HistNewton {
     double lambda_l2 = 0.0, min_sum_hessian = 0.0, min_split_gain = 0.0;
 };
 
+// what a grower is made with: k = split_candidates (bins per feature), the depth limit, the least leaf support, the split
+// criterion and the leaf budget (0: level-wise growth)
+struct HistGrowOptions {
+    uint32_t k = 0, max_depth = 0, min_leaf = 0;
+    HistNewton newton;
+    uint32_t max_leaves = 0;
+};
+
 class HistGrower {
   public:
-    HistGrower(frdev::DeviceDataset& dev, std::vector<uint32_t> feats, uint32_t k, uint32_t max_depth, uint32_t min_leaf,
-               HistNewton newton = HistNewton(), uint32_t max_leaves = 0)
-        : dev_(dev), feats_(std::move(feats)), k_(k), max_depth_(max_depth), min_leaf_(min_leaf), newton_(newton), max_leaves_(max_leaves) {}
+    HistGrower(frdev::DeviceDataset& dev, std::vector<uint32_t> feats, const HistGrowOptions& opt)
+        : dev_(dev), feats_(std::move(feats)), k_(opt.k), max_depth_(opt.max_depth), min_leaf_(opt.min_leaf), newton_(opt.newton), max_leaves_(opt.max_leaves) {}
     ~HistGrower() { dev_.hist_end(); }
 
     // bins for the instance list at `positions`; true when they were built now (false: the view's kept ones were reused)
@@ -79,11 +86,9 @@ class HistGrower {
         if (max_leaves_ >= 2) {
             std::vector<TreeNode*> lw_nodes;
             std::vector<Dev::HistNode> lw_leaves;
-            if (!grow_leaves(root.get(), s_l, s_w, &lw_nodes, &lw_leaves)) {  // (the index list of a tree that never searched: the root's)
-                if (!dev_.hist_root(&err)) fail_str(err);
-            }
+            const bool rooted = grow_leaves(root.get(), s_l, s_w, &lw_nodes, &lw_leaves);
             if (n_leaves) *n_leaves = (uint32_t)lw_nodes.size();
-            leaf_values(lw_nodes, lw_leaves, s_l, s_w, leaf_seconds);
+            leaf_values(lw_nodes, lw_leaves, s_l, s_w, rooted, leaf_seconds);
             return root;
         }
         struct Open {
@@ -103,19 +108,13 @@ class HistGrower {
         } else {
             close(root.get(), 0u, n_);
         }
-        const size_t F = sel_.empty() ? feats_.size() : sel_.size();  // the tree's features; slot fi of them is slot full(fi) of the bins
-        auto full = [&](size_t fi) { return sel_.empty() ? fi : (size_t)sel_[fi]; };
+        const size_t F = features();
         std::vector<Dev::HistNode> nodes, builds;
         std::vector<Dev::HistBest> best;
         std::vector<Dev::HistBestNewton> best_n;
-        // (G G) / (H + lambda_l2) of an integer pair, every operation rounded on its own
-        auto term = [&](long long q, long long w) {
-            const double g = std::ldexp((double)q, -s_l);
-            return (g * g) / (std::ldexp((double)w, -s_w) + newton_.lambda_l2);
-        };
         std::vector<Dev::HistSplit> splits;
         std::vector<Dev::HistSub> subs;
-        bool rooted = !open.empty();
+        const bool rooted = !open.empty();
         while (!open.empty()) {
             nodes.clear(), builds.clear(), splits.clear(), subs.clear(), next.clear();
             for (const Open& o : open) nodes.push_back({o.slot, o.begin, o.end});
@@ -140,20 +139,14 @@ class HistGrower {
                 }
                 if (w != nullptr && newton_.on) {  // the node's totals (Qnode, Wnode) arrive with every record of the node
                     const Dev::HistBestNewton& b = best_n[a * F + wf];
-                    if (!(w->imp - term(b.qtot, b.wtot) > newton_.min_split_gain)) w = nullptr;
+                    if (!(newton_gain(w->imp, b.qtot, b.wtot, s_l, s_w) > newton_.min_split_gain)) w = nullptr;
                 }
                 if (w == nullptr) {
                     close(o.node, o.begin, o.end);
                     continue;
                 }
                 const uint32_t n = o.end - o.begin, nl = w->nl, nr = n - nl;
-                const size_t ws = full(wf);
-                if (w->edge >= nedges_[ws] || nl == 0 || nl >= n) fail_str("LambdaMART histogram grower: internal error: an impossible split");
-                o.node->leaf = false;
-                o.node->fid = feats_[ws];
-                o.node->value = (double)edges_[ws * 256 + w->edge];
-                o.node->lhs.reset(new TreeNode());
-                o.node->rhs.reset(new TreeNode());
+                const size_t ws = split_node(o.node, wf, w->edge, n, nl);
                 splits.push_back({o.begin, o.end, (uint32_t)ws, w->edge, nl});  // (the bin matrix's row)
                 const uint32_t mid = o.begin + nl;
                 const bool el = enterable(nl, o.depth + 1), er = enterable(nr, o.depth + 1);
@@ -174,22 +167,7 @@ class HistGrower {
             if (!dev_.hist_split(splits, builds, subs, next_slots, &err, newton_.on)) fail_str(err);
             open.swap(next);
         }
-        auto t0 = std::chrono::steady_clock::now();
-        if (!rooted) {  // (the index list of a tree that never searched: the root's)
-            if (!dev_.hist_root(&err)) fail_str(err);
-        }
-        std::vector<long long> qw;
-        if (!dev_.hist_leaf_sums(leaves, &qw, &err)) fail_str(err);
-        for (size_t i = 0; i < leaf_nodes.size(); i++) {
-            const long long q = qw[i * 2], w = qw[i * 2 + 1];
-            if (newton_.on) {
-                const double den = std::ldexp((double)w, -s_w) + newton_.lambda_l2;
-                leaf_nodes[i]->value = den != 0.0 ? std::ldexp((double)q, -s_l) / den : 0.0;
-            } else {
-                leaf_nodes[i]->value = w != 0 ? std::ldexp((double)q, -s_l) / std::ldexp((double)w, -s_w) : 0.0;
-            }
-        }
-        if (leaf_seconds) *leaf_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        leaf_values(leaf_nodes, leaves, s_l, s_w, rooted, leaf_seconds);
         if (n_leaves) *n_leaves = (uint32_t)leaf_nodes.size();
         return root;
     }
@@ -221,8 +199,6 @@ class HistGrower {
             close(root, 0u, n_);
             return false;
         }
-        const size_t F = sel_.empty() ? feats_.size() : sel_.size();
-        auto full = [&](size_t fi) { return sel_.empty() ? fi : (size_t)sel_[fi]; };
         const Dev::HistLeafSearch how{min_leaf_, newton_.on, s_l, s_w, newton_.lambda_l2, newton_.min_sum_hessian};
         // live histograms never exceed the leaves, and the leaves neither max_leaves, the instances nor 2^(max_depth - 1)
         uint32_t slots = std::min(max_leaves_, n_);
@@ -234,8 +210,7 @@ class HistGrower {
             bool ok = p.valid != 0;
             double gain = 0.0;
             if (ok && newton_.on) {
-                const double g = std::ldexp((double)p.qtot, -s_l);
-                gain = p.imp - (g * g) / (std::ldexp((double)p.wtot, -s_w) + newton_.lambda_l2);
+                gain = newton_gain(p.imp, p.qtot, p.wtot, s_l, s_w);
                 ok = gain > newton_.min_split_gain;
             } else if (ok) {  // (ranks only: rounding may leave it slightly below 0)
                 const double sn = (double)p.qtot;
@@ -259,14 +234,7 @@ class HistGrower {
             const OpenLeaf o = open[at];
             open.erase(open.begin() + (std::ptrdiff_t)at);
             const uint32_t n = o.end - o.begin, nl = o.pick.nl, nr = n - nl;
-            if (o.pick.fi >= F) fail_str("LambdaMART histogram grower: internal error: an impossible split");
-            const size_t ws = full(o.pick.fi);
-            if (o.pick.edge >= nedges_[ws] || nl == 0 || nl >= n) fail_str("LambdaMART histogram grower: internal error: an impossible split");
-            o.node->leaf = false;
-            o.node->fid = feats_[ws];
-            o.node->value = (double)edges_[ws * 256 + o.pick.edge];
-            o.node->lhs.reset(new TreeNode());
-            o.node->rhs.reset(new TreeNode());
+            const size_t ws = split_node(o.node, o.pick.fi, o.pick.edge, n, nl);
             n_leaves++;
             const uint32_t mid = o.begin + nl, il = next_index++, ir = next_index++;
             const bool more = n_leaves < max_leaves_;  // (the split that reaches max_leaves searches no child)
@@ -290,14 +258,44 @@ class HistGrower {
             if (!el && !er) free_slots.push_back(o.slot);
         }
         for (const OpenLeaf& o : open) close(o.node, o.begin, o.end);
-        pool_bytes_ = std::max(pool_bytes_, (uint64_t)slots * F * k_ * (newton_.on ? 20u : 12u));
+        pool_bytes_ = std::max(pool_bytes_, (uint64_t)slots * features() * k_ * (newton_.on ? 20u : 12u));
         return true;
     }
 
+    // The tree's features: their number, and slot fi of them as a slot of the bins.
+    size_t features() const { return sel_.empty() ? feats_.size() : sel_.size(); }
+    size_t full(size_t fi) const { return sel_.empty() ? fi : (size_t)sel_[fi]; }
+
+    // Leaf t, holding n instances, becomes an inner node with two fresh leaves: feature fi of the tree's, bins 0..edge of it
+    // go left, nl instances.  Returns the feature's slot in the bin matrix.
+    size_t split_node(TreeNode* t, size_t fi, uint32_t edge, uint32_t n, uint32_t nl) {
+        if (fi >= features() || edge >= nedges_[full(fi)] || nl == 0 || nl >= n)
+            fail_str("LambdaMART histogram grower: internal error: an impossible split");
+        const size_t ws = full(fi);
+        t->leaf = false;
+        t->fid = feats_[ws];
+        t->value = (double)edges_[ws * 256 + edge];
+        t->lhs.reset(new TreeNode());
+        t->rhs.reset(new TreeNode());
+        return ws;
+    }
+
+    // (G G) / (H + lambda_l2) of an integer pair, every operation rounded on its own
+    double newton_term(long long q, long long w, int s_l, int s_w) const {
+        const double g = std::ldexp((double)q, -s_l);
+        return (g * g) / (std::ldexp((double)w, -s_w) + newton_.lambda_l2);
+    }
+    // what a candidate of importance imp gains over its node's own term (Qnode, Wnode); the node splits only when this
+    // exceeds min_split_gain
+    double newton_gain(double imp, long long qtot, long long wtot, int s_l, int s_w) const { return imp - newton_term(qtot, wtot, s_l, s_w); }
+
+    // Leaf values from the leaves' integer sums.  rooted = false: the tree never searched, and the index list the sums are
+    // taken over is made here, as the root's.
     void leaf_values(const std::vector<TreeNode*>& leaf_nodes, const std::vector<frdev::DeviceDataset::HistNode>& leaves, int s_l, int s_w,
-                     double* leaf_seconds) {
+                     bool rooted, double* leaf_seconds) {
         std::string err;
         auto t0 = std::chrono::steady_clock::now();
+        if (!rooted && !dev_.hist_root(&err)) fail_str(err);
         std::vector<long long> qw;
         if (!dev_.hist_leaf_sums(leaves, &qw, &err)) fail_str(err);
         for (size_t i = 0; i < leaf_nodes.size(); i++) {
