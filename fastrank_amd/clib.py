@@ -110,6 +110,7 @@ def _load():
         "fr_debug_rccl_selftest": (vp, [C.c_int]),
         "fr_debug_walk_tiles": (vp, [vp, vp, vp, sz, vp, vp, sz, sz]),
         "fr_debug_device_form": (vp, [vp, C.c_int, C.c_char_p, vp, sz]),
+        "fr_debug_dataset_layout": (vp, [vp, vp, sz, vp, vp, sz, C.c_char_p, vp, sz]),
     }
     for name, (restype, argtypes) in sigs.items():
         fn = getattr(L, name)

@@ -1206,6 +1206,91 @@ const void* fr_debug_device_form(const CDataset* dataset, int slot, const void* 
     });
 }
 
+// The host-side layout of a dataset (csrc/dataset_layout.hpp) built from its host CSR alone: no device is touched.  Same
+// name / out-buffer protocol as fr_debug_device_form and the same table names, plus termtab, qnpos, qnneg, qlist, fv_qlist and
+// the size classes.  parent_queries: also the tables of the view that holds these queries of the dataset, under "view_" + name;
+// `view` (optional): the dataset whose CSR is the view's own (NULL: cut from `dataset`'s).  row_hash[np] (optional): the
+// row hashes by position (NULL: a host hash of the row bytes).
+const void* fr_debug_dataset_layout(const CDataset* dataset, const uint32_t* parent_queries, size_t n_parent_queries, const CDataset* view,
+                                    const uint64_t* row_hash, size_t n_row_hash, const void* table, void* out, size_t out_bytes) {
+    return json_call([&]() {
+        using namespace frdev;
+        const CDataset& ds = require_dataset(dataset);
+        const HostCSR& csr = ds.view->host_csr();
+        if (csr.n == 0 || csr.nq == 0) fr::fail_str("fr_debug_dataset_layout: empty dataset");
+        std::map<std::string, std::vector<unsigned char>> tables;
+        Value scalars = Value::object();
+        auto put = [&](const std::string& name, const auto& v) {
+            using T = typename std::remove_reference_t<decltype(v)>::value_type;
+            std::vector<unsigned char>& b = tables[name];
+            b.resize(v.size() * sizeof(T));
+            if (!v.empty()) std::memcpy(b.data(), v.data(), b.size());
+        };
+        auto num = [&](const std::string& name, uint64_t v) { scalars.set(name.c_str(), Value::uint(v)); };
+        auto put_runs = [&](const std::string& pre, const RunPlan& r) {
+            put(pre + "qstart", r.qstart), put(pre + "qlen", r.qlen), put(pre + "qtight", r.qtight);
+            put(pre + "run_q0", r.run_q0), put(pre + "run_q1", r.run_q1), put(pre + "run_pos", r.run_pos);
+            put(pre + "run_docs", r.run_docs), put(pre + "run_order", r.run_order);
+            std::vector<uint32_t> qlist, fv_qlist;
+            const std::vector<SizeClass> sc = bucket_queries(r.qlen, pow2_from_64, &qlist), fv = fv_build_classes(r.qlen, &fv_qlist);
+            static_assert(sizeof(SizeClass) == 3 * sizeof(uint32_t), "served as triples of u32");
+            put(pre + "qlist", qlist), put(pre + "fv_qlist", fv_qlist), put(pre + "size_classes", sc), put(pre + "fv_classes", fv);
+            num(pre + "nq", r.qlen.size()), num(pre + "nruns", r.run_q0.size()), num(pre + "maxlen", r.maxlen), num(pre + "np", r.np);
+            num(pre + "n_size_classes", sc.size()), num(pre + "n_fv_classes", fv.size());
+        };
+        std::string err;
+        RunPlan runs;
+        if (!plan_runs(csr.qoff, csr.nq, run_docs_target(), &runs, &err)) fr::fail_str(err);
+        const std::vector<uint32_t> perm_host = position_map(csr, runs.qstart, runs.qlen, runs.np);
+        const GainTables gt = gain_tables(csr, runs.qstart, runs.qlen, perm_host, runs.maxlen);
+        if (row_hash && n_row_hash != runs.np) fr::fail_str("fr_debug_dataset_layout: row_hash must hold one hash per position (" + std::to_string(runs.np) + ")");
+        const std::vector<uint64_t> hashes = row_hash ? std::vector<uint64_t>(row_hash, row_hash + n_row_hash) : host_row_hash(csr, perm_host);
+        const DupGroups dg = duplicate_groups(hashes, csr, perm_host, runs.qstart, runs.qlen, gt.gcls, gt.cls_gain.size(),
+                                              path_env("FR_NO_DUP_GROUPS") != nullptr, 1);
+        const WalkTileLayout wl = build_walk_tiles(runs.run_pos, runs.run_q0, runs.run_q1, runs.qstart, runs.qlen, runs.np);
+        put_runs("", runs);
+        put("run_lo", std::vector<uint32_t>(runs.run_q0.size(), 0u));
+        put("perm_host", perm_host), put("perm", perm_host), put("gain", gt.gain), put("gexp", gt.gexp), put("gcls", gt.gcls);
+        put("dcgtab", gt.dcgtab), put("termtab", gt.termtab), put("qnpos", gt.qnpos), put("qnneg", gt.qnneg), put("gkey", dg.gkey16);
+        put("wt_start", wl.wt_start), put("run_wt0", wl.run_wt0), put("segtab", wl.seg), put("wofs", wl.wofs);
+        num("n", csr.n), num("d", csr.d), num("dq", (csr.d + 3) / 4), num("nwt", wl.wt_start.size() - 1), num("ncls", gt.ncls);
+        num("tablen", gt.tablen), num("termtab_len", gt.termtab.size()), num("relmask", gt.relmask), num("labels_small_int", gt.labels_small_int ? 1u : 0u);
+        num("key_bits", dg.key_bits), num("key_cls_bits", dg.key_cls_bits), num("dup_groups", dg.dup_groups), num("verify_xs", (uint64_t)dg.verify_xs);
+        num("no_document", NO_DOCUMENT), num("walk_tile", WALK_TILE), num("dcg_ranks", (uint64_t)DCG_RANKS);
+        if (parent_queries) {
+            const std::vector<uint32_t> pq(parent_queries, parent_queries + n_parent_queries);
+            HostCSR cut;  // the view's own CSR: the chosen queries of the dataset's, documents in its order
+            cut.d = csr.d, cut.x = csr.x, cut.nq = pq.size();
+            cut.qoff.assign(1, 0);
+            for (uint32_t q : pq) {
+                if (q >= csr.nq) fr::fail_str("fr_debug_dataset_layout: no such query");
+                cut.perm.insert(cut.perm.end(), csr.perm.begin() + csr.qoff[q], csr.perm.begin() + csr.qoff[q + 1]);
+                cut.gain.insert(cut.gain.end(), csr.gain.begin() + csr.qoff[q], csr.gain.begin() + csr.qoff[q + 1]);
+                cut.qoff.push_back((uint32_t)cut.perm.size());
+            }
+            cut.n = cut.perm.size();
+            const HostCSR& vcsr = view ? require_dataset(view).view->host_csr() : cut;
+            if (vcsr.n == 0 || vcsr.nq == 0 || pq.size() != vcsr.nq) fr::fail_str("create_view: empty view");
+            RunPlan v;
+            if (!plan_view_runs(runs.qstart, runs.qlen, perm_host, wl.wt_start, vcsr, pq, run_docs_target(), &v, &err)) fr::fail_str(err);
+            put_runs("view_", v);
+            put("view_run_lo", v.run_lo), put("view_run_wt0", v.run_wt0), put("view_vtiles", v.vtiles), put("view_wlist", v.wlist);
+            put("view_perm_host", v.perm_host);
+            num("view_n", vcsr.n), num("view_nvtiles", v.vtiles.size()), num("view_nwlist", v.wlist.size());
+        }
+        if (!table) return frjson::dump(scalars);
+        const std::string name = accept_str("table", table);
+        const auto it = tables.find(name);
+        if (it == tables.end()) fr::fail_str("fr_debug_dataset_layout: no table named " + name);
+        Value o = Value::object();
+        o.set("bytes", Value::uint(it->second.size()));
+        if (out_bytes != it->second.size() || (!out && out_bytes))
+            fr::fail_str("fr_debug_dataset_layout: table " + name + " holds " + std::to_string(it->second.size()) + " bytes, the buffer " + std::to_string(out_bytes));
+        if (out_bytes) std::memcpy(out, it->second.data(), out_bytes);
+        return frjson::dump(o);
+    });
+}
+
 // The same call sequence on ONE device (a one-rank communicator): librccl.so opens, its symbols bind, ncclCommInitAll /
 // grouped ncclAllGather / ncclCommDestroy run and the data comes back.  What a one-GPU box can check of the exchange.
 const void* fr_debug_rccl_selftest(int device) {

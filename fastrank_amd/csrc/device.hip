@@ -28,7 +28,9 @@
 //                           lambda_grad_trunc_kernel: the same under a truncation level / per-query normalisation
 //                           (both are templates over the objective: NDCG, MAP or MRR pair weights)
 //   kernels_hist.inc        LambdaMART's histogram grower: one-byte bins, int64 fixed-point gradients, per-node histograms
-//   device_dataset.inc      DeviceDataset: HBM layout (runs, tiles, tables) and every launcher
+//   dataset_layout.hpp      (through device.hpp; host only, no HIP) the layout arithmetic of a dataset: runs, size classes, gain
+//                           tables, duplicate groups, walk tiles, a view's tables
+//   device_dataset.inc      DeviceDataset: the uploads of that layout (tiles, tables) and every launcher
 #include "device.hpp"
 
 #include <hip/hip_runtime.h>

@@ -49,30 +49,63 @@ void fullrank_class_of(uint32_t len, uint32_t* nl, uint32_t* pl) {
     *pl = FV_CLASSES[ci].pl;
 }
 
-// queries sorted by class (stable: dataset order inside a class); out[i].npad = index into FV_CLASSES
-template <class SC>
-static void fv_build_classes(const uint32_t* qlen, size_t nq, std::vector<uint32_t>& list, std::vector<SC>& out) {
+// queries sorted by the class of kernels_fullverify.inc that takes them (stable: dataset order inside a class);
+// SizeClass::npad = index into FV_CLASSES
+std::vector<SizeClass> fv_build_classes(const std::vector<uint32_t>& qlen, std::vector<uint32_t>* list) {
     std::vector<int> cls_of_len(2049, -1);
-    auto cls = [&](uint32_t len) {
+    return bucket_queries(qlen, [&](uint32_t len) {
         const uint32_t l = len > 2048 ? 2048 : len;
         if (cls_of_len[l] < 0) cls_of_len[l] = fv_class_of(l);
         return cls_of_len[l];
-    };
-    out.clear();
-    list.resize(nq);
-    for (size_t q = 0; q < nq; q++) list[q] = (uint32_t)q;
-    std::stable_sort(list.begin(), list.end(), [&](uint32_t x, uint32_t y) { return cls(qlen[x]) < cls(qlen[y]); });
-    for (size_t k = 0; k < nq;) {
-        const int c = cls(qlen[list[k]]);
-        size_t e = k;
-        while (e < nq && cls(qlen[list[e]]) == c) e++;
-        out.push_back({(uint32_t)c, (uint32_t)k, (uint32_t)(e - k)});
-        k = e;
-    }
+    }, list);
 }
 
+static_assert(WT == WALK_TILE && LS_KT == DCG_RANKS && IDX_INVALID == NO_DOCUMENT, "the kernels' constants are the host layout's (dataset_layout.hpp)");
 
-struct DeviceDataset::Impl {
+// The host-side description of a dataset: what create() / create_view() work out about it and a replica takes over from
+// its source in one assignment (replicate()).  Impl derives from it, so the members read m.np, m.nq, ... everywhere.
+struct DatasetDesc {
+    size_t n = 0, d = 0, nq = 0, np = 0, dq = 0, maxlen = 0, nruns = 0;
+    bool nonfinite = false;            // X holds inf/NaN: zero-weight masking is not exact -> no fused path
+    bool labels_small_int = false;     // every label is an integer of magnitude <= 2^21: sums of up to 2^31 of them are exact in f64 in ANY order (kernels_rf.inc)
+    std::vector<double> colmax;        // per-column max |x| (error bound of the bound-and-verify line search)
+    int verify_xs = 1;                 // keys beyond K in the verify kernel's lists (1..4, raised on tie-heavy data)
+    std::vector<uint32_t> perm_host;   // [np] original instance id or IDX_INVALID (padding, or not part of this view)
+    std::vector<uint32_t> qstart_h, qlen_h, qnpos_h, qnneg_h;  // host copies (views of this dataset are cut from them)
+    std::vector<uint32_t> wt_start_h;  // [nwt + 1] host copy of wt_start
+    size_t nwt = 0;
+    std::vector<double> colstd;        // per-column standard deviation over the dataset's documents
+    std::vector<uint8_t> colmode;      // bit 0 / 1: more than a tenth of the documents sit at the column's maximum / minimum
+    std::vector<ColStats> colstats_h;  // the records colstd / colmode were made from (read by debug_form_table alone)
+    uint32_t key_bits = 0, key_cls_bits = 0;  // gkey: gain class | duplicate group << key_cls_bits
+    uint64_t dup_groups = 0;           // duplicate groups found at upload, over all queries (whether or not gkey carries their ids)
+    std::vector<SizeClass> size_classes;  // queries bucketed by next power of two of their length
+    std::vector<SizeClass> fv_classes;    // queries bucketed by the cheapest class of kernels_fullverify.inc (npad = index into FV_CLASSES)
+    uint64_t relmask = 0;              // bit c: gain class c has gain > 0
+    size_t ncls = 0, tablen = 0;
+};
+
+// create()'s helper thread tells the tile thread that the main stream exists, or that it could not be made
+struct StreamSignal {
+    std::mutex mu;
+    std::condition_variable cv;
+    bool done = false, ok = true;
+    void set(bool good) {
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            if (!good) ok = false;
+            done = true;
+        }
+        cv.notify_all();
+    }
+    bool wait() {
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&] { return done; });
+        return ok;
+    }
+};
+
+struct DeviceDataset::Impl : DatasetDesc {
     // resident base sums / error bounds shared by the bound-and-verify paths (defined further down)
     // Per-tick parameters of the bound-and-verify paths travel as ONE page-locked block and one copy (the redo
     // counter, zeroed, rides along); results come back into page-locked memory with one synchronisation.
@@ -154,10 +187,6 @@ struct DeviceDataset::Impl {
     RMArgs rank_args(const double* rows, const uint32_t* gncand, double* M, int* flags, size_t gc, size_t ldm, int measure, int64_t depth) const;
     int device = 0;
     hipStream_t stream = nullptr;
-    size_t n = 0, d = 0, nq = 0, np = 0, dq = 0, maxlen = 0, nruns = 0;
-    bool nonfinite = false;            // X holds inf/NaN: zero-weight masking is not exact -> no fused path
-    bool labels_small_int = false;     // every label is an integer of magnitude <= 2^21: sums of up to 2^31 of them are exact in f64 in ANY order (kernels_rf.inc)
-    std::vector<double> colmax;        // per-column max |x| (error bound of the bound-and-verify line search)
     std::vector<double> eps2_host;
     DevBuf<double> res;                // resident base sums: [slots][2][np]
     std::vector<uint8_t> res_half;     // which half of each slot is current
@@ -170,14 +199,11 @@ struct DeviceDataset::Impl {
     unsigned long long approx_redo_entries = 0;            // ... and in 16-candidate slices of them (NDCG@k)
     unsigned long long chain_runs = 0, chain_visits = 0;   // NDCG@k verify kernel: insertion-chain runs / (document, group) visits
     unsigned long long exact_groups = 0;                   // NDCG@k: group line searches routed to the exact kernel
-    int verify_xs = 1;                                     // keys beyond K in the verify kernel's lists (1..4, raised on tie-heavy data)
     unsigned long long audit_values = 0, audit_mismatches = 0;  // FR_VERIFY_AUDIT=1: published values re-derived by the exact kernel
     DevBuf<double> audit;
     DevBuf<unsigned long long> audit_cnt;
     DevBuf<int> audit_flags;  // (the exact kernels' flags of an audit: the published ones are not touched)
     unsigned long long exact_fallbacks = 0;                // line searches evaluated by the exact kernels alone (every group routed there, or approx_skip)
-    std::vector<uint32_t> perm_host;   // [np] original instance id or IDX_INVALID (padding, or not part of this view)
-    std::vector<uint32_t> qstart_h, qlen_h, qnpos_h, qnneg_h;  // host copies (views of this dataset are cut from them)
     std::shared_ptr<DeviceDataset> parent;  // a view: the dataset whose tiles and per-document arrays this one aliases
     DevBuf<uint32_t> run_lo;
     DevBuf<uint32_t> vtiles;           // a view: the 64-position tiles of the parent's position space that hold its documents (ascending)
@@ -193,11 +219,7 @@ struct DeviceDataset::Impl {
     DevBuf<uint32_t> run_wt0;          // [nruns] the walk tile that holds the run's first document
     DevBuf<uint8_t> wofs;              // [np] a position's offset inside its walk tile (the identity visiting order)
     DevBuf<uint32_t> wlist;            // a view: the walk tiles that hold its documents (ascending)
-    std::vector<uint32_t> wt_start_h;
-    size_t nwt = 0, nwlist = 0;
-    std::vector<double> colstd;        // per-column standard deviation over the dataset's documents
-    std::vector<uint8_t> colmode;      // bit 0 / 1: more than a tenth of the documents sit at the column's maximum / minimum
-    std::vector<ColStats> colstats_h;  // the records colstd / colmode were made from (read by debug_form_table alone)
+    size_t nwlist = 0;
     // ... and per trainer
     DevBuf<uint8_t> rslot;             // [slots][np] the same by the resident sum R descending
     std::vector<uint16_t> slot_rank_age;  // line searches since a slot's ranks were made (0xFFFF: never)
@@ -215,26 +237,21 @@ struct DeviceDataset::Impl {
     std::vector<uint16_t> slot_rate_n;        // line searches in the running mean
     std::vector<float> slot_rate;             // running mean of chain runs per visit
     unsigned long long rank_slots_on = 0, rank_slots_off = 0;  // decisions made (statistics)
+    // the main stream, the line-search contexts' streams and res_ready
+    hipError_t open_streams(bool* at_event, StreamSignal* main_stream = nullptr);
+    bool open_streams(std::string* err);
+    static bool upload_tiles(Impl& m, const HostCSR& csr, bool timing, StreamSignal& main_stream, std::string* terr);
     bool build_order_tables(std::string* err);
     DevBuf<float> xcol;                // [d][np] the tiles' columns, column-major: what the resident line search reads (empty: it reads the tiles)
     bool build_columns(std::string* err);
     DevBuf<uint16_t> gkey;             // [np] gain class | duplicate group << key_cls_bits (<= 16 bits wherever the verify kernel runs): the low mantissa bits of its keys
-    uint32_t key_bits = 0, key_cls_bits = 0;
-    uint64_t dup_groups = 0;           // duplicate groups found at upload, over all queries (whether or not gkey carries their ids)
     DevBuf<float> xb, gain;
     DevBuf<double> gexp, disc;
     DevBuf<uint32_t> qstart, qlen, qtight, perm, rank, run_q0, run_q1, run_pos, run_docs, run_order, gcls, qlist;
-    struct SizeClass {
-        uint32_t npad, offset, count;
-    };
-    std::vector<SizeClass> size_classes;  // queries bucketed by next power of two of their length
-    std::vector<SizeClass> fv_classes;  // queries bucketed by the cheapest class of kernels_fullverify.inc (npad = index into FV_CLASSES)
     DevBuf<uint32_t> fv_qlist;
-    uint64_t relmask = 0;              // bit c: gain class c has gain > 0
     DevBuf<uint32_t> qnpos, qnneg, sort_idx;
     DevBuf<double> sort_keys;  // global sort scratch for queries longer than the LDS sort takes
     DevBuf<double> termtab, rows;
-    size_t ncls = 0, tablen = 0;
     DevBuf<double> dcgtab;
     DevBuf<int> flags;
     DevBuf<unsigned long long> dbgc;
@@ -426,172 +443,66 @@ static bool upload(DevBuf<T>& buf, const std::vector<T>& host, std::string* err)
     return true;
 }
 
-std::shared_ptr<DeviceDataset> DeviceDataset::create(const HostCSR& csr, std::string* err) {
-    auto fail = [&](const std::string& m) {
-        if (err) *err = m;
-        return std::shared_ptr<DeviceDataset>();
-    };
-    std::string e2;
-    if (device_count(&e2) <= 0)
-        return fail("no MI355X/HIP device available for the fastrank_amd compute path (" +
-                    (e2.empty() ? std::string("device count is 0") : e2) + ")");
-    if (csr.n == 0 || csr.d == 0 || csr.nq == 0) return fail("empty dataset");
-    if (csr.n >= 0xF0000000ull) return fail("dataset too large for 32-bit document positions");
-    std::shared_ptr<DeviceDataset> ds(new DeviceDataset());
-    Impl& m = *ds->impl_;
-    if (hipGetDevice(&m.device) != hipSuccess) return fail("hipGetDevice failed");
-    // FR_UPLOAD_TIMING=1: stage times of the one-time upload on stderr
-    const bool timing = std::getenv("FR_UPLOAD_TIMING") != nullptr;
-    auto tclock = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
+static std::shared_ptr<DeviceDataset> fail_ds(std::string* err, const std::string& msg) {
+    if (err) *err = msg;
+    return std::shared_ptr<DeviceDataset>();
+}
+static bool hip_ok(hipError_t e, const char* what, std::string* err) {
+    if (e == hipSuccess) return true;
+    if (err) *err = std::string("HIP error: ") + hipGetErrorString(e) + " at " + what;
+    return false;
+}
+struct ThreadJoiner {  // joins on every way out of create()
+    std::thread& t;
+    ~ThreadJoiner() { if (t.joinable()) t.join(); }
+};
+// documents a run takes (FR_RUN_DOCS: tuning sweeps)
+size_t run_docs_target() {
+    const char* t = frdev::pricing_env("FR_RUN_DOCS");
+    return t ? std::max<size_t>(64, (size_t)atoll(t)) : 768;
+}
+
+// Returns the first error; *at_event: it was the event's.  main_stream hears of the main stream before the others are made.
+hipError_t DeviceDataset::Impl::open_streams(bool* at_event, StreamSignal* main_stream) {
+    hipError_t e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+    if (main_stream) main_stream->set(e == hipSuccess);
+    for (int i = 0; i < LS_CONTEXTS && e == hipSuccess; i++) e = hipStreamCreateWithFlags(&ls[i].stream, hipStreamNonBlocking);
+    if (e != hipSuccess) return e;
+    e = hipEventCreateWithFlags(&res_ready, hipEventDisableTiming);
+    *at_event = e != hipSuccess;
+    return e;
+}
+bool DeviceDataset::Impl::open_streams(std::string* err) {
+    bool at_event = false;
+    const hipError_t e = open_streams(&at_event);
+    return hip_ok(e, at_event ? "hipEventCreate" : "hipStreamCreate", err);
+}
+
+// The feature tiles, on create()'s tile thread and the main stream while the caller builds and uploads the per-position tables.
+bool DeviceDataset::Impl::upload_tiles(Impl& m, const HostCSR& csr, bool timing, StreamSignal& main_stream, std::string* terr) {
+    if (hipSetDevice(m.device) != hipSuccess) {
+        *terr = "hipSetDevice failed in the upload thread";
+        return false;
+    }
+    auto tchk = [&](hipError_t e, const char* what) { return hip_ok(e, what, terr); };
+    auto tt = std::chrono::steady_clock::now();
+    double t_fill = 0.0, t_wait = 0.0;  // (FR_UPLOAD_TIMING: the tile thread's own stages)
+    auto tlap = [&](const char* what) {
         if (!timing) return;
         const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[upload] %-28s %7.1f ms\n", what, std::chrono::duration<double, std::milli>(now - tclock).count());
-        tclock = now;
+        fprintf(stderr, "[upload/tiles] %-36s %7.1f ms\n", what, std::chrono::duration<double, std::milli>(now - tt).count());
+        tt = now;
     };
-    auto chk = [&](hipError_t e, const char* what) {
-        if (e == hipSuccess) return true;
-        if (err) *err = std::string("HIP error: ") + hipGetErrorString(e) + " at " + what;
-        return false;
-    };
-    // A stream costs ~20 ms to create (a hardware queue each) and the process's first one ~80 ms (the runtime's first touch of
-    // the device): 96 ms for the five of them used to be the largest single stage of the upload
-    // (profiles/r05_upload_stages.txt).  A helper thread creates them -- the main stream first: the tile thread waits for it,
-    // nothing else needs it before the tiles are up -- while this thread builds the host-side tables; the line-search
-    // contexts' streams are not needed before the first tick.  Joined before create() returns.
-    std::string serr;
-    bool streams_ok = true;
-    std::mutex stream_mu;
-    std::condition_variable stream_cv;
-    bool main_stream_done = false;
-    std::thread stream_thread([&]() {
-        hipError_t e = hipSetDevice(m.device);
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&m.stream, hipStreamNonBlocking);
-        {
-            std::lock_guard<std::mutex> lk(stream_mu);
-            if (e != hipSuccess) streams_ok = false;
-            main_stream_done = true;
-        }
-        stream_cv.notify_all();
-        for (int i = 0; i < LS_CONTEXTS && e == hipSuccess; i++) e = hipStreamCreateWithFlags(&m.ls[i].stream, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&m.res_ready, hipEventDisableTiming);
-        if (e != hipSuccess) {
-            std::lock_guard<std::mutex> lk(stream_mu);
-            streams_ok = false;
-            serr = std::string("HIP error: ") + hipGetErrorString(e) + " at hipStreamCreate";
-        }
-    });
-    auto wait_main_stream = [&]() {
-        std::unique_lock<std::mutex> lk(stream_mu);
-        stream_cv.wait(lk, [&] { return main_stream_done; });
-        return streams_ok;
-    };
-    struct StreamJoiner {
-        std::thread& t;
-        ~StreamJoiner() { if (t.joinable()) t.join(); }
-    } stream_joiner{stream_thread};
-    m.n = csr.n;
-    m.d = csr.d;
-    m.nq = csr.nq;
-    m.dq = (csr.d + 3) / 4;
-
-    lap("helper thread started (streams)");
-    // ---- runs: consecutive queries packed into whole 64-document tiles ----------------------
-    size_t target = 768;
-    if (const char* t = frdev::pricing_env("FR_RUN_DOCS")) target = std::max<size_t>(64, (size_t)atoll(t));
-    std::vector<uint32_t> qstart(m.nq), qlen(m.nq), qtight(m.nq + 1), run_q0, run_q1, run_pos, run_docs;
-    {
-        size_t pos = 0, cur_docs = 0;
-        uint32_t cur_q0 = 0;
-        auto close_run = [&](uint32_t q_end) {
-            run_q0.push_back(cur_q0);
-            run_q1.push_back(q_end);
-            run_pos.push_back((uint32_t)(pos - cur_docs));
-            run_docs.push_back((uint32_t)cur_docs);
-            pos = (pos + 63) / 64 * 64;
-            cur_docs = 0;
-            cur_q0 = q_end;
-        };
-        for (size_t q = 0; q < m.nq; q++) {
-            size_t len = csr.qoff[q + 1] - csr.qoff[q];
-            m.maxlen = std::max(m.maxlen, len);
-            if (cur_docs > 0 && cur_docs + len > target) close_run((uint32_t)q);
-            qstart[q] = (uint32_t)pos;
-            qlen[q] = (uint32_t)len;
-            qtight[q] = csr.qoff[q];
-            pos += len;
-            cur_docs += len;
-        }
-        if (cur_docs > 0) close_run((uint32_t)m.nq);
-        qtight[m.nq] = csr.qoff[m.nq];
-        m.np = pos;
-        if (m.np >= 0xFFFFFF00ull) return fail("dataset too large for 32-bit document positions");
-    }
-    m.nruns = run_q0.size();
-    std::vector<uint32_t> run_order(m.nruns);
-    for (size_t r = 0; r < m.nruns; r++) run_order[r] = (uint32_t)r;
-    // longest-first schedule so the biggest runs do not form the tail of a launch
-    std::stable_sort(run_order.begin(), run_order.end(), [&](uint32_t x, uint32_t y) { return run_docs[x] > run_docs[y]; });
-
-    // ---- size classes for the general (sort) evaluator: LDS sized per class, not per dataset maximum
-    std::vector<uint32_t> qlist(m.nq);
-    {
-        auto npad_of = [](uint32_t len) {
-            uint32_t p2 = 64;
-            while (p2 < len) p2 <<= 1;
-            return p2;
-        };
-        for (size_t q = 0; q < m.nq; q++) qlist[q] = (uint32_t)q;
-        std::stable_sort(qlist.begin(), qlist.end(), [&](uint32_t x, uint32_t y) { return npad_of(qlen[x]) < npad_of(qlen[y]); });
-        for (size_t k = 0; k < m.nq;) {
-            uint32_t np2 = npad_of(qlen[qlist[k]]);
-            size_t e = k;
-            while (e < m.nq && npad_of(qlen[qlist[e]]) == np2) e++;
-            m.size_classes.push_back({np2, (uint32_t)k, (uint32_t)(e - k)});
-            k = e;
-        }
-    }
-
-    // ---- size classes of the full-ranking bound-and-verify kernel (kernels_fullverify.inc): every query goes to the
-    // cheapest (keys per lane, lanes per candidate) class that holds it
-    std::vector<uint32_t> fv_qlist(m.nq);
-    fv_build_classes(qlen.data(), m.nq, fv_qlist, m.fv_classes);
-
-    lap("runs, size classes");
-    // ---- padded per-position arrays ------------------------------------------------------------
-    m.perm_host.assign(m.np, IDX_INVALID);
-    for (size_t q = 0; q < m.nq; q++)
-        for (uint32_t k = 0; k < qlen[q]; k++) m.perm_host[(size_t)qstart[q] + k] = csr.perm[(size_t)csr.qoff[q] + k];
-    // (runs on its own thread and stream while this thread builds and uploads the per-position tables below)
-    std::string terr;
-    auto upload_tiles = [&]() -> bool {
-        if (hipSetDevice(m.device) != hipSuccess) {
-            terr = "hipSetDevice failed in the upload thread";
-            return false;
-        }
-        auto tchk = [&](hipError_t e, const char* what) {
-            if (e == hipSuccess) return true;
-            terr = std::string("HIP error: ") + hipGetErrorString(e) + " at " + what;
-            return false;
-        };
-        auto tt = std::chrono::steady_clock::now();
-        double t_fill = 0.0, t_wait = 0.0;  // (FR_UPLOAD_TIMING: the tile thread's own stages)
-        auto tlap = [&](const char* what) {
-            if (!timing) return;
-            const auto now = std::chrono::steady_clock::now();
-            fprintf(stderr, "[upload/tiles] %-36s %7.1f ms\n", what, std::chrono::duration<double, std::milli>(now - tt).count());
-            tt = now;
-        };
     // ---- feature tiles.  The host only streams the view's rows, row-major as they lie in the caller's matrix, through two
     // pinned slabs (plain memcpy by a pool of threads while the previous slab is on the wire); tile_scatter_kernel moves
     // every row to its padded position in the tile layout and takes the per-column max |x| and the non-finite flag on
     // the way.  One-time cost; SURVEY 8d excludes it from evals/s and bench.py reports it separately.
     const size_t ntiles = m.np / 64;
     const size_t tile_floats = m.dq * 256;
-    if (!m.xb.ensure(ntiles * tile_floats, &terr)) return false;
+    if (!m.xb.ensure(ntiles * tile_floats, terr)) return false;
     {
-        if (!wait_main_stream()) {  // (created by the helper thread)
-            terr = "HIP error: hipStreamCreate failed";
+        if (!main_stream.wait()) {  // (created by the helper thread)
+            *terr = "HIP error: hipStreamCreate failed";
             return false;
         }
         if (!tchk(hipMemsetAsync(m.xb.p, 0, ntiles * tile_floats * sizeof(float), m.stream), "clear feature tiles")) return false;
@@ -617,8 +528,8 @@ std::shared_ptr<DeviceDataset> DeviceDataset::create(const HostCSR& csr, std::st
         size_t slab_mb = 32;
         if (const char* e = frdev::pricing_env("FR_UPLOAD_SLAB_MB")) slab_mb = std::max(1, std::atoi(e));
         const size_t slab_rows = std::max<size_t>(1, std::min<size_t>(rows.size(), (slab_mb << 20) / row_bytes));
-        if (!upload(d_dst, row_dst, &terr) || !d_colmax.ensure(csr.d, &terr) || !d_bad.ensure(1, &terr) ||
-            !d_stage[0].ensure(slab_rows * csr.d, &terr) || !d_stage[1].ensure(slab_rows * csr.d, &terr))
+        if (!upload(d_dst, row_dst, terr) || !d_colmax.ensure(csr.d, terr) || !d_bad.ensure(1, terr) ||
+            !d_stage[0].ensure(slab_rows * csr.d, terr) || !d_stage[1].ensure(slab_rows * csr.d, terr))
             return false;
         if (!tchk(hipMemsetAsync(d_colmax.p, 0, csr.d * sizeof(uint32_t), m.stream), "clear column maxima") ||
             !tchk(hipMemsetAsync(d_bad.p, 0, sizeof(int), m.stream), "clear flags"))
@@ -715,278 +626,147 @@ std::shared_ptr<DeviceDataset> DeviceDataset::create(const HostCSR& csr, std::st
             m.colmax[j] = colbits[j] >= 0x7F800000u ? (double)std::numeric_limits<float>::infinity() : (double)f;
         }
     }
-        return true;
+    return true;
+}
+
+std::shared_ptr<DeviceDataset> DeviceDataset::create(const HostCSR& csr, std::string* err) {
+    std::string e2;
+    if (device_count(&e2) <= 0)
+        return fail_ds(err, "no MI355X/HIP device available for the fastrank_amd compute path (" +
+                                (e2.empty() ? std::string("device count is 0") : e2) + ")");
+    if (csr.n == 0 || csr.d == 0 || csr.nq == 0) return fail_ds(err, "empty dataset");
+    if (csr.n >= 0xF0000000ull) return fail_ds(err, "dataset too large for 32-bit document positions");
+    std::shared_ptr<DeviceDataset> ds(new DeviceDataset());
+    Impl& m = *ds->impl_;
+    if (hipGetDevice(&m.device) != hipSuccess) return fail_ds(err, "hipGetDevice failed");
+    // FR_UPLOAD_TIMING=1: stage times of the one-time upload on stderr
+    const bool timing = std::getenv("FR_UPLOAD_TIMING") != nullptr;
+    auto tclock = std::chrono::steady_clock::now();
+    auto lap = [&](const char* what) {
+        if (!timing) return;
+        const auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "[upload] %-28s %7.1f ms\n", what, std::chrono::duration<double, std::milli>(now - tclock).count());
+        tclock = now;
     };
-    bool tiles_ok = false;
-    std::thread tile_thread([&]() { tiles_ok = upload_tiles(); });
-    struct Joiner {
-        std::thread& t;
-        ~Joiner() { if (t.joinable()) t.join(); }
-    } tile_joiner{tile_thread};
-    std::vector<float> gain(m.np, 0.0f);
-    std::vector<double> gexp(m.np, 0.0);
-    m.labels_small_int = true;
-    {
-        // (2^g - 1) with the platform libm, exactly like 2.0_f64.powf(gain) - 1.0 (src/evaluators.rs:266-270); g is
-        // the f32 gain widened to f64.  Labels repeat: one pow per distinct bit pattern.
-        std::vector<std::pair<uint32_t, double>> memo;
-        auto gexp_of = [&](float g) {
-            uint32_t bits;
-            std::memcpy(&bits, &g, sizeof(bits));
-            for (const auto& e : memo)
-                if (e.first == bits) return e.second;
-            const double v = std::pow(2.0, (double)g) - 1.0;
-            if (memo.size() < 64) memo.emplace_back(bits, v);
-            return v;
-        };
-        for (size_t q = 0; q < m.nq; q++) {
-            for (uint32_t k = 0; k < qlen[q]; k++) {
-                size_t p = (size_t)qstart[q] + k, t = (size_t)csr.qoff[q] + k;
-                m.perm_host[p] = csr.perm[t];
-                gain[p] = csr.gain[t];
-                gexp[p] = gexp_of(csr.gain[t]);
-                const float gl = csr.gain[t];
-                if (!(std::fabs(gl) <= 2097152.0f) || gl != (float)(int32_t)gl) m.labels_small_int = false;
-            }
+    // A stream costs ~20 ms to create (a hardware queue each) and the process's first one ~80 ms (the runtime's first touch of
+    // the device): 96 ms for the five of them used to be the largest single stage of the upload
+    // (profiles/r05_upload_stages.txt).  A helper thread creates them -- the main stream first: the tile thread waits for it,
+    // nothing else needs it before the tiles are up -- while this thread builds the host-side tables; the line-search
+    // contexts' streams are not needed before the first tick.  Joined before create() returns.
+    std::string serr;  // (written by the helper thread, read after its join)
+    StreamSignal main_stream;
+    std::thread stream_thread([&]() {
+        hipError_t e = hipSetDevice(m.device);
+        bool at_event = false;
+        if (e == hipSuccess) e = m.open_streams(&at_event, &main_stream);
+        else main_stream.set(false);
+        if (e != hipSuccess) {
+            std::lock_guard<std::mutex> lk(main_stream.mu);
+            main_stream.ok = false;
+            serr = std::string("HIP error: ") + hipGetErrorString(e) + " at hipStreamCreate";
         }
-    }
+    });
+    ThreadJoiner stream_joiner{stream_thread};
+    m.n = csr.n;
+    m.d = csr.d;
+    m.nq = csr.nq;
+    m.dq = (csr.d + 3) / 4;
+
+    lap("helper thread started (streams)");
+    RunPlan runs;
+    if (!plan_runs(csr.qoff, m.nq, run_docs_target(), &runs, err)) return nullptr;
+    m.maxlen = runs.maxlen;
+    m.np = runs.np;
+    m.nruns = runs.run_q0.size();
+    // size classes for the general (sort) evaluator, and of the full-ranking bound-and-verify kernel
+    // (kernels_fullverify.inc): every query goes to the cheapest (keys per lane, lanes per candidate) class that holds it
+    std::vector<uint32_t> qlist, fv_qlist;
+    m.size_classes = bucket_queries(runs.qlen, pow2_from_64, &qlist);
+    m.fv_classes = fv_build_classes(runs.qlen, &fv_qlist);
+
+    lap("runs, size classes");
+    m.perm_host = position_map(csr, runs.qstart, runs.qlen, m.np);
+    // (runs on its own thread and stream while this thread builds and uploads the per-position tables below)
+    std::string terr;  // (written by the tile thread, read after its join)
+    bool tiles_ok = false;
+    std::thread tile_thread([&]() { tiles_ok = Impl::upload_tiles(m, csr, timing, main_stream, &terr); });
+    ThreadJoiner tile_joiner{tile_thread};
+    GainTables gt;
+    position_gains(csr, runs.qstart, runs.qlen, m.np, &gt);
+    m.labels_small_int = gt.labels_small_int;
 
     lap("perm / gain / gexp");
-    // ---- gain classes and the per-class DCG term table: term(c, i) = (2^g_c - 1) / log2(i + 2), the
-    // exact expression of src/evaluators.rs:266-270 evaluated once per (class, rank) on the host
-    std::vector<uint32_t> gcls(m.np, 0);
-    std::vector<double> dcgtab;
-    size_t cls_gain_count = 1;
-    {
-        // class ids in order of DESCENDING gain: among keys that agree above the class bits -- exact duplicates -- the
-        // lower gain then has the larger key and sorts first, which is the reference's tie-break (gain asc, evaluators.rs:34-49)
-        std::vector<float> cls_gain;
-        {
-            std::vector<uint32_t> seen_bits;
-            uint32_t last_bits = 0;
-            bool have_last = false;
-            for (size_t p = 0; p < m.np; p++) {
-                if (m.perm_host[p] == IDX_INVALID) continue;
-                const float gv = gain[p] == 0.0f ? 0.0f : gain[p];  // -0.0 and +0.0 are one class
-                uint32_t bits;
-                std::memcpy(&bits, &gv, sizeof(bits));
-                if (have_last && bits == last_bits) continue;  // documents are stored gain-descending: long runs of one class
-                last_bits = bits;
-                have_last = true;
-                if (std::find(seen_bits.begin(), seen_bits.end(), bits) == seen_bits.end()) {
-                    if (seen_bits.size() > 4096) break;  // (far too many distinct gains for the class machinery: found below)
-                    seen_bits.push_back(bits);
-                    cls_gain.push_back(gv);
-                }
-            }
-            std::sort(cls_gain.begin(), cls_gain.end(), [](float x, float y) { return x > y; });
-        }
-        std::map<uint32_t, uint32_t> cls_of_bits;
-        for (size_t c = 0; c < cls_gain.size(); c++) {
-            uint32_t bits;
-            std::memcpy(&bits, &cls_gain[c], sizeof(bits));
-            cls_of_bits.emplace(bits, (uint32_t)c);
-        }
-        uint32_t last_bits = 0, last_cls = 0;
-        bool have_last = false;
-        for (size_t p = 0; p < m.np; p++) {
-            if (m.perm_host[p] == IDX_INVALID) continue;
-            float gv = gain[p] == 0.0f ? 0.0f : gain[p];
-            uint32_t bits;
-            std::memcpy(&bits, &gv, sizeof(bits));
-            if (!have_last || bits != last_bits) {
-                auto it = cls_of_bits.find(bits);
-                if (it == cls_of_bits.end()) {  // (only after the 4096 cut above: more classes than any fused path takes)
-                    it = cls_of_bits.emplace(bits, (uint32_t)cls_gain.size()).first;
-                    cls_gain.push_back(gv);
-                }
-                last_bits = bits;
-                last_cls = it->second;
-                have_last = true;
-            }
-            gcls[p] = last_cls;
-        }
-        if (cls_gain.empty()) cls_gain.push_back(0.0f);
-        cls_gain_count = cls_gain.size();
-        for (size_t c = 0; c < cls_gain.size() && c < 64; c++)
-            if (cls_gain[c] > 0.0f) m.relmask |= uint64_t(1) << c;
-        dcgtab.resize(cls_gain.size() * LS_KT);
-        for (size_t c = 0; c < cls_gain.size(); c++)
-            for (int i = 0; i < LS_KT; i++)
-                dcgtab[c * LS_KT + i] = (std::pow(2.0, (double)cls_gain[c]) - 1.0) / std::log2((double)i + 2.0);
-    }
+    gain_classes(m.perm_host, &gt);
+    m.relmask = gt.relmask;
 
     lap("gain classes, dcgtab");
-    // per-query counts of positive / negative gains (documents are stored gain-descending, so these are a
-    // prefix / suffix of the query) and the full-depth term table for the rank-counting evaluator
-    std::vector<uint32_t> qnpos(m.nq, 0), qnneg(m.nq, 0);
-    std::vector<double> termtab;
-    {
-        for (size_t q = 0; q < m.nq; q++)
-            for (uint32_t k = 0; k < qlen[q]; k++) {
-                float gv = gain[(size_t)qstart[q] + k];
-                qnpos[q] += gv > 0.0f;
-                qnneg[q] += gv < 0.0f;
-            }
-        m.ncls = dcgtab.size() / LS_KT;
-        // row length: the padded query length of the longest size class (kernels_fullverify.inc looks up every rank of
-        // a padded query); one more row of zeros = the "padding class" its padding keys carry
-        m.tablen = 16;
-        while (m.tablen < m.maxlen) m.tablen <<= 1;
-        if (m.ncls <= 255 && (m.ncls + 1) * m.tablen <= (size_t(64) << 20)) {
-            termtab.assign((m.ncls + 1) * m.tablen, 0.0);
-            for (size_t c = 0; c < m.ncls; c++) {
-                const double ge = dcgtab[c * LS_KT] * std::log2(2.0);  // = 2^g - 1 (term at rank 0, log2(2) = 1)
-                for (size_t r = 0; r < m.tablen; r++) termtab[c * m.tablen + r] = ge / std::log2((double)r + 2.0);
-            }
-        }
-    }
+    term_tables(runs.qstart, runs.qlen, m.maxlen, &gt);
+    m.ncls = gt.ncls;
+    m.tablen = gt.tablen;
 
     lap("per-position tables (host)");
     {
         size_t nd = std::max<size_t>(m.maxlen, 64);
         std::vector<double> disc(nd);
         for (size_t i = 0; i < nd; i++) disc[i] = std::log2((double)i + 2.0);
-        if (!upload(m.disc, disc, err) || !upload(m.gexp, gexp, err) || !upload(m.gain, gain, err) ||
-            !upload(m.qstart, qstart, err) || !upload(m.qlen, qlen, err) || !upload(m.qtight, qtight, err) ||
-            !upload(m.perm, m.perm_host, err) || !upload(m.run_q0, run_q0, err) || !upload(m.run_q1, run_q1, err) ||
-            !upload(m.run_pos, run_pos, err) || !upload(m.run_docs, run_docs, err) ||
-            !upload(m.run_order, run_order, err) || !upload(m.run_lo, std::vector<uint32_t>(m.nruns, 0u), err) ||
-            !upload(m.gcls, gcls, err) || !upload(m.dcgtab, dcgtab, err) ||
-            !upload(m.qlist, qlist, err) || !upload(m.fv_qlist, fv_qlist, err) || !upload(m.qnpos, qnpos, err) ||
-            !upload(m.qnneg, qnneg, err) ||
-            !upload(m.termtab, termtab, err))
+        if (!upload(m.disc, disc, err) || !upload(m.gexp, gt.gexp, err) || !upload(m.gain, gt.gain, err) ||
+            !upload(m.qstart, runs.qstart, err) || !upload(m.qlen, runs.qlen, err) || !upload(m.qtight, runs.qtight, err) ||
+            !upload(m.perm, m.perm_host, err) || !upload(m.run_q0, runs.run_q0, err) || !upload(m.run_q1, runs.run_q1, err) ||
+            !upload(m.run_pos, runs.run_pos, err) || !upload(m.run_docs, runs.run_docs, err) ||
+            !upload(m.run_order, runs.run_order, err) || !upload(m.run_lo, std::vector<uint32_t>(m.nruns, 0u), err) ||
+            !upload(m.gcls, gt.gcls, err) || !upload(m.dcgtab, gt.dcgtab, err) ||
+            !upload(m.qlist, qlist, err) || !upload(m.fv_qlist, fv_qlist, err) || !upload(m.qnpos, gt.qnpos, err) ||
+            !upload(m.qnneg, gt.qnneg, err) ||
+            !upload(m.termtab, gt.termtab, err))
             return nullptr;
         if (!m.flags.ensure(1, err) || !m.dbgc.ensure(4, err)) return nullptr;
-        if (!chk(hipMemset(m.flags.p, 0, sizeof(int)), "clear flags")) return nullptr;
-        m.qstart_h = qstart;
-        m.qlen_h = qlen;
-        m.qnpos_h = qnpos;
-        m.qnneg_h = qnneg;
+        if (!hip_ok(hipMemset(m.flags.p, 0, sizeof(int)), "clear flags", err)) return nullptr;
+        m.qstart_h = runs.qstart;
+        m.qlen_h = runs.qlen;
+        m.qnpos_h = gt.qnpos;
+        m.qnneg_h = gt.qnneg;
     }
     lap("small tables H2D");
     tile_thread.join();
-    if (!tiles_ok) return fail(terr);
+    if (!tiles_ok) return fail_ds(err, terr);
     lap("feature rows H2D + device tiling (remaining wait)");
-    // ---- duplicate groups: documents of one query with bit-identical feature rows score exactly alike under every
-    // weight vector, so the reference orders them by its tie-break alone.  gkey[p] = class | group << cls_bits rides in the
-    // low mantissa bits of the NDCG@k verify kernel's keys (kernels_verify.inc): two close keys of ONE group are an exact
-    // tie whose order the class bits already give.  Group ids are per query, 1.., 0 = no duplicate.
-    std::vector<uint32_t> gkey(gcls);
     {
-        // a 64-bit hash of every document's feature row, computed on the device from the tiles just uploaded
+        // duplicate groups (dataset_layout.hpp: duplicate_groups) from a 64-bit hash of every document's feature row,
+        // computed on the device from the tiles just uploaded
         std::vector<uint64_t> row_hash(m.np, 0);
         {
             DevBuf<uint64_t> d_hash;
             if (!d_hash.ensure(m.np, err)) return nullptr;
             row_hash_kernel<<<dim3((unsigned)((m.np + 255) / 256)), 256, 0, m.stream>>>((const float4*)m.xb.p, (uint32_t)m.np, (uint32_t)m.dq, d_hash.p);
-            if (!chk(hipGetLastError(), "row_hash_kernel") ||
-                !chk(hipMemcpyAsync(row_hash.data(), d_hash.p, m.np * sizeof(uint64_t), hipMemcpyDeviceToHost, m.stream), "row hashes") ||
-                !chk(hipStreamSynchronize(m.stream), "row hashes"))
+            if (!hip_ok(hipGetLastError(), "row_hash_kernel", err) ||
+                !hip_ok(hipMemcpyAsync(row_hash.data(), d_hash.p, m.np * sizeof(uint64_t), hipMemcpyDeviceToHost, m.stream), "row hashes", err) ||
+                !hip_ok(hipStreamSynchronize(m.stream), "row hashes", err))
                 return nullptr;
         }
-        uint32_t cls_bits = 0;
-        while ((size_t(1) << cls_bits) < std::max<size_t>(cls_gain_count, 1)) cls_bits++;
-        std::vector<uint32_t> dup(m.np, 0);
         unsigned hw = std::thread::hardware_concurrency();
         const size_t nthreads = std::max<size_t>(1, std::min<size_t>(hw ? hw : 1, m.np > 200000 ? 16 : 1));
-        std::vector<uint32_t> tmax(nthreads, 0);
-        std::vector<uint64_t> tsum(nthreads, 0);
-        std::vector<char> tmixed(nthreads, 0);  // some group holds documents of different gain classes
-        const size_t row_bytes = csr.d * sizeof(float);
-        auto work = [&](size_t tid) {
-            std::vector<std::pair<uint64_t, uint32_t>> hk;
-            for (size_t q = tid; q < m.nq; q += nthreads) {
-                const uint32_t n = qlen[q];
-                if (n < 2) continue;
-                hk.clear();
-                for (uint32_t k = 0; k < n; k++) hk.emplace_back(row_hash[(size_t)qstart[q] + k], k);
-                std::sort(hk.begin(), hk.end());
-                uint32_t next_id = 1;
-                for (size_t i = 0; i < hk.size();) {
-                    size_t e = i + 1;
-                    while (e < hk.size() && hk[e].first == hk[i].first) e++;
-                    if (e - i >= 2) {  // equal hashes: confirm by comparing the rows (sub-groups on a collision)
-                        std::vector<char> done(e - i, 0);
-                        for (size_t u = i; u < e; u++) {
-                            if (done[u - i]) continue;
-                            const float* ru = csr.x + (size_t)m.perm_host[(size_t)qstart[q] + hk[u].second] * csr.d;
-                            uint32_t members = 1;
-                            for (size_t v = u + 1; v < e; v++) {
-                                if (done[v - i]) continue;
-                                const float* rv = csr.x + (size_t)m.perm_host[(size_t)qstart[q] + hk[v].second] * csr.d;
-                                if (std::memcmp(ru, rv, row_bytes) == 0) {
-                                    if (gcls[(size_t)qstart[q] + hk[v].second] != gcls[(size_t)qstart[q] + hk[u].second]) tmixed[tid] = 1;
-                                    dup[(size_t)qstart[q] + hk[v].second] = next_id;
-                                    done[v - i] = 1;
-                                    members++;
-                                }
-                            }
-                            if (members > 1) dup[(size_t)qstart[q] + hk[u].second] = next_id++;
-                        }
-                    }
-                    i = e;
-                }
-                tmax[tid] = std::max(tmax[tid], next_id - 1);
-                tsum[tid] += next_id - 1;
-            }
-        };
-        std::vector<std::thread> pool;
-        for (size_t tid = 1; tid < nthreads; tid++) pool.emplace_back(work, tid);
-        work(0);
-        for (auto& th : pool) th.join();
-        uint32_t maxg = 0;
-        for (uint32_t v : tmax) maxg = std::max(maxg, v);
-        for (uint64_t v : tsum) m.dup_groups += v;
-        uint32_t dup_bits = 0;
-        while ((1u << dup_bits) <= maxg) dup_bits++;  // ids 0..maxg
-        bool mixed = false;
-        for (char v : tmixed) mixed = mixed || v;
-        if (!mixed || frdev::path_env("FR_NO_DUP_GROUPS")) dup_bits = 0;  // (groups of one gain class are covered by the class rule)
-        if (cls_bits + dup_bits > 16) dup_bits = cls_bits < 16 ? 16 - cls_bits : 0;  // keep the keys' error term small: late groups lose their id
-        m.key_bits = cls_bits + dup_bits;
-        m.key_cls_bits = cls_bits;
-        if (dup_bits)
-            for (size_t p = 0; p < m.np; p++)
-                if (dup[p] && dup[p] < (1u << dup_bits)) gkey[p] |= dup[p] << cls_bits;
-        // Where the first trainer on this dataset starts with the length of the verify kernel's lists.  At K + 1 keys a
-        // dataset with duplicated rows sends 85 % of the pairs of its first line search to the exact kernel, 16 % of the second
-        // (K + 2) and 1.4 % of the third (K + 3) before the lists reach the length the data needs -- 80 ms at the 30K shape, 5 % of
-        // a whole job (tools/chain_by_tick.py).  More than half a percent of the documents having an exact duplicate inside
-        // their query says so in advance: start at K + 3 (resident_reserve hands a new trainer one below verify_xs; a longer
-        // list than the data needs costs ~4 % per key and is never shortened within a trainer, so not K + 4 outright).
-        size_t dup_docs = 0;
-        for (size_t p = 0; p < m.np; p++) dup_docs += dup[p] != 0;
-        if (dup_docs * 200 > m.n) m.verify_xs = 4;
-    }
-    {
-        // (two bytes per document: the kernel runs with <= 256 classes = 8 bits, and class + group bits are capped at 16 above)
-        std::vector<uint16_t> gkey16(m.np);
-        for (size_t p = 0; p < m.np; p++) gkey16[p] = (uint16_t)gkey[p];
-        if (!upload(m.gkey, gkey16, err)) return nullptr;
+        const DupGroups dg = duplicate_groups(row_hash, csr, m.perm_host, runs.qstart, runs.qlen, gt.gcls, gt.cls_gain.size(),
+                                              frdev::path_env("FR_NO_DUP_GROUPS") != nullptr, nthreads);
+        m.dup_groups = dg.dup_groups;
+        m.key_bits = dg.key_bits;
+        m.key_cls_bits = dg.key_cls_bits;
+        m.verify_xs = dg.verify_xs;
+        if (!upload(m.gkey, dg.gkey16, err)) return nullptr;
     }
     lap("duplicate groups (device hash, host grouping)");
     {
-        // the walk tiles (kernels_order.inc): every run's positions cut into stretches of at most WT, greedily, so that a
-        // query of up to WT documents is never cut (a longer one is cut every WT documents, and what is left of it shares a
-        // tile with the queries behind it); then the (query, walk tile) segment of every position and the static
-        // visiting-order tables
-        // (build_walk_tiles, device.hpp: host arithmetic only -- tests/test_cabi_host.py holds its invariants without a device)
-        static_assert(WT == WALK_TILE, "the kernels' walk tile is the host's");
-        WalkTileLayout wl = build_walk_tiles(run_pos, run_q0, run_q1, qstart, qlen, m.np);
+        // the walk tiles (kernels_order.inc; build_walk_tiles), then the (query, walk tile) segment of every position and the
+        // static visiting-order tables
+        WalkTileLayout wl = build_walk_tiles(runs.run_pos, runs.run_q0, runs.run_q1, runs.qstart, runs.qlen, m.np);
         m.wt_start_h = std::move(wl.wt_start);
         m.nwt = m.wt_start_h.size() - 1;
-        const std::vector<uint32_t>& wts = m.wt_start_h;
-        const std::vector<uint32_t>& run_wt0 = wl.run_wt0;
-        const std::vector<uint16_t>& segh = wl.seg;
-        const std::vector<uint8_t>& wofs = wl.wofs;
-        if (!upload(m.segtab, segh, err) || !upload(m.wt_start, wts, err) || !upload(m.run_wt0, run_wt0, err) || !upload(m.wofs, wofs, err)) return nullptr;
+        if (!upload(m.segtab, wl.seg, err) || !upload(m.wt_start, m.wt_start_h, err) || !upload(m.run_wt0, wl.run_wt0, err) || !upload(m.wofs, wl.wofs, err)) return nullptr;
         if (!m.build_order_tables(err)) return nullptr;
         if (!m.build_columns(err)) return nullptr;
     }
     lap("visiting-order tables (device)");
     stream_thread.join();
-    if (!streams_ok) return fail(serr);
+    if (!main_stream.ok) return fail_ds(err, serr);
     lap("line-search streams (helper thread, remaining wait)");
     return ds;
 }
@@ -1157,24 +937,20 @@ bool DeviceDataset::debug_form_table(const std::string& name, std::vector<unsign
 // The copy starts with empty work buffers and its own streams.  This is how train_model spreads the restarts of one
 // request over the GPUs of a node (src/coordinate_ascent.rs:215-225 does it with rayon over the host's cores).
 std::shared_ptr<DeviceDataset> DeviceDataset::replicate(const std::shared_ptr<DeviceDataset>& src, int device, std::string* err) {
-    auto fail = [&](const std::string& msg) {
-        if (err) *err = msg;
-        return std::shared_ptr<DeviceDataset>();
-    };
-    if (!src || src->impl_->parent) return fail("replicate: the source must own its matrix");
+    if (!src || src->impl_->parent) return fail_ds(err, "replicate: the source must own its matrix");
     Impl& sm = *src->impl_;
     // (no lock on the source for the copies: what create() left in HBM and its host-side description never change
     // afterwards, so the callers' threads -- one per destination -- really copy at the same time, each peer reading
     // the source over its own link; the source may run kernels of its own meanwhile)
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail("replicate: no such device");
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail_ds(err, "replicate: no such device");
     int prev = 0;
     (void)hipGetDevice(&prev);
     struct Restore {
         int d;
         ~Restore() { (void)hipSetDevice(d); }
     } restore{prev};
-    if (hipSetDevice(device) != hipSuccess) return fail("replicate: hipSetDevice failed");
+    if (hipSetDevice(device) != hipSuccess) return fail_ds(err, "replicate: hipSetDevice failed");
     if (device != sm.device) {  // direct peer copies where the link allows them (otherwise the runtime stages through the host)
         int can = 0;
         if (hipDeviceCanAccessPeer(&can, device, sm.device) == hipSuccess && can) {
@@ -1186,27 +962,10 @@ std::shared_ptr<DeviceDataset> DeviceDataset::replicate(const std::shared_ptr<De
     std::shared_ptr<DeviceDataset> ds(new DeviceDataset());
     Impl& m = *ds->impl_;
     m.device = device;
-    auto chk = [&](hipError_t e, const char* what) {
-        if (e == hipSuccess) return true;
-        if (err) *err = std::string("HIP error: ") + hipGetErrorString(e) + " at " + what;
-        return false;
-    };
-    if (!chk(hipStreamCreateWithFlags(&m.stream, hipStreamNonBlocking), "hipStreamCreate")) return nullptr;
-    for (int i = 0; i < LS_CONTEXTS; i++)
-        if (!chk(hipStreamCreateWithFlags(&m.ls[i].stream, hipStreamNonBlocking), "hipStreamCreate")) return nullptr;
-    if (!chk(hipEventCreateWithFlags(&m.res_ready, hipEventDisableTiming), "hipEventCreate")) return nullptr;
-    // ---- host-side description
-    m.n = sm.n, m.d = sm.d, m.nq = sm.nq, m.np = sm.np, m.dq = sm.dq, m.maxlen = sm.maxlen, m.nruns = sm.nruns;
-    m.nonfinite = sm.nonfinite;
-    m.colmax = sm.colmax;
-    m.perm_host = sm.perm_host;
-    m.qstart_h = sm.qstart_h, m.qlen_h = sm.qlen_h, m.qnpos_h = sm.qnpos_h, m.qnneg_h = sm.qnneg_h;
-    m.key_bits = sm.key_bits, m.key_cls_bits = sm.key_cls_bits;
-    m.dup_groups = sm.dup_groups;
-    m.size_classes = sm.size_classes;
-    m.fv_classes = sm.fv_classes;
-    m.relmask = sm.relmask;
-    m.ncls = sm.ncls, m.tablen = sm.tablen;
+    if (!m.open_streams(err)) return nullptr;
+    // ---- host-side description: everything, as the source holds it now (verify_xs included: whatever its trainers raised it
+    // to).  What is not part of it keeps its default: a replica has no parent and visits its whole position space (nvtiles = 0).
+    static_cast<DatasetDesc&>(m) = sm;
     // ---- everything create() left in HBM, device to device
     bool ok = true;
     auto copy = [&](auto& dst, const auto& from, const char* what) {
@@ -1215,11 +974,10 @@ std::shared_ptr<DeviceDataset> DeviceDataset::replicate(const std::shared_ptr<De
             ok = false;
             return;
         }
-        ok = chk(hipMemcpyPeerAsync(dst.p, device, from.p, sm.device, from.bytes(), m.stream), what);
+        ok = hip_ok(hipMemcpyPeerAsync(dst.p, device, from.p, sm.device, from.bytes(), m.stream), what, err);
     };
     copy(m.xb, sm.xb, "replicate feature tiles");
     copy(m.gain, sm.gain, "replicate gain");
-    m.labels_small_int = sm.labels_small_int;
     copy(m.gexp, sm.gexp, "replicate gexp");
     copy(m.disc, sm.disc, "replicate disc");
     copy(m.qstart, sm.qstart, "replicate qstart");
@@ -1238,9 +996,6 @@ std::shared_ptr<DeviceDataset> DeviceDataset::replicate(const std::shared_ptr<De
     copy(m.wt_start, sm.wt_start, "replicate wt_start");
     copy(m.run_wt0, sm.run_wt0, "replicate run_wt0");
     copy(m.wofs, sm.wofs, "replicate wofs");
-    m.wt_start_h = sm.wt_start_h;
-    m.nwt = sm.nwt;
-    m.verify_xs = sm.verify_xs;
     // the optional copies (create() itself goes without them when HBM is short): a replica that cannot hold them is a slower
     // replica, not a failed one -- xcol first, the resident line search cannot do without it
     auto copy_optional = [&](auto& dst, const auto& from, const char* what, const char* degraded) {
@@ -1251,13 +1006,10 @@ std::shared_ptr<DeviceDataset> DeviceDataset::replicate(const std::shared_ptr<De
             warn_degraded(degraded);
             return;
         }
-        ok = chk(hipMemcpyPeerAsync(dst.p, device, from.p, sm.device, from.bytes(), m.stream), what);
+        ok = hip_ok(hipMemcpyPeerAsync(dst.p, device, from.p, sm.device, from.bytes(), m.stream), what, err);
     };
     copy_optional(m.xcol, sm.xcol, "replicate xcol", "a device replica has no HBM for the column-major copy of the matrix: its line searches form their sums from the tiles");
     copy_optional(m.xslot, sm.xslot, "replicate xslot", "a device replica has no HBM for the visiting-order tables: its NDCG@k verify kernel walks in storage order");
-    m.colstd = sm.colstd;
-    m.colmode = sm.colmode;
-    m.colstats_h = sm.colstats_h;
     copy(m.qlist, sm.qlist, "replicate qlist");
     copy(m.fv_qlist, sm.fv_qlist, "replicate fv_qlist");
     copy(m.qnpos, sm.qnpos, "replicate qnpos");
@@ -1266,8 +1018,8 @@ std::shared_ptr<DeviceDataset> DeviceDataset::replicate(const std::shared_ptr<De
     copy(m.dcgtab, sm.dcgtab, "replicate dcgtab");
     if (!ok) return nullptr;
     if (!m.flags.ensure(1, err) || !m.dbgc.ensure(4, err)) return nullptr;
-    if (!chk(hipMemsetAsync(m.flags.p, 0, sizeof(int), m.stream), "clear flags") ||
-        !chk(hipStreamSynchronize(m.stream), "replicate"))
+    if (!hip_ok(hipMemsetAsync(m.flags.p, 0, sizeof(int), m.stream), "clear flags", err) ||
+        !hip_ok(hipStreamSynchronize(m.stream), "replicate", err))
         return nullptr;
     return ds;
 }
@@ -1276,26 +1028,14 @@ int DeviceDataset::device_ordinal() const { return impl_->device; }
 
 std::shared_ptr<DeviceDataset> DeviceDataset::create_view(const std::shared_ptr<DeviceDataset>& parent, const HostCSR& csr,
                                                           const std::vector<uint32_t>& parent_query, std::string* err) {
-    auto fail = [&](const std::string& msg) {
-        if (err) *err = msg;
-        return std::shared_ptr<DeviceDataset>();
-    };
-    if (!parent || parent->impl_->parent) return fail("create_view: the parent must own its matrix");
+    if (!parent || parent->impl_->parent) return fail_ds(err, "create_view: the parent must own its matrix");
     const Impl& pm = *parent->impl_;
-    if (csr.n == 0 || csr.nq == 0 || parent_query.size() != csr.nq) return fail("create_view: empty view");
+    if (csr.n == 0 || csr.nq == 0 || parent_query.size() != csr.nq) return fail_ds(err, "create_view: empty view");
     std::shared_ptr<DeviceDataset> ds(new DeviceDataset());
     Impl& m = *ds->impl_;
     m.device = pm.device;
-    auto chk = [&](hipError_t e, const char* what) {
-        if (e == hipSuccess) return true;
-        if (err) *err = std::string("HIP error: ") + hipGetErrorString(e) + " at " + what;
-        return false;
-    };
-    if (!chk(hipSetDevice(m.device), "hipSetDevice")) return nullptr;
-    if (!chk(hipStreamCreateWithFlags(&m.stream, hipStreamNonBlocking), "hipStreamCreate")) return nullptr;
-    for (int i = 0; i < LS_CONTEXTS; i++)
-        if (!chk(hipStreamCreateWithFlags(&m.ls[i].stream, hipStreamNonBlocking), "hipStreamCreate")) return nullptr;
-    if (!chk(hipEventCreateWithFlags(&m.res_ready, hipEventDisableTiming), "hipEventCreate")) return nullptr;
+    if (!hip_ok(hipSetDevice(m.device), "hipSetDevice", err)) return nullptr;
+    if (!m.open_streams(err)) return nullptr;
     m.parent = parent;
     m.n = csr.n;
     m.d = pm.d;
@@ -1307,93 +1047,20 @@ std::shared_ptr<DeviceDataset> DeviceDataset::create_view(const std::shared_ptr<
     m.ncls = pm.ncls;
     m.tablen = pm.tablen;
     m.relmask = pm.relmask;
-    // ---- the view's queries inside the parent's position space; runs = maximal groups of queries that are consecutive
-    // there (and at most `target` documents), each starting wherever its first query starts: run_lo lanes into a tile
-    size_t target = 768;
-    if (const char* t = frdev::pricing_env("FR_RUN_DOCS")) target = std::max<size_t>(64, (size_t)atoll(t));
-    std::vector<uint32_t> qstart(m.nq), qlen(m.nq), qtight(m.nq + 1), qnpos(m.nq), qnneg(m.nq), run_q0, run_q1, run_pos, run_docs, run_lo;
-    m.perm_host.assign(m.np, IDX_INVALID);
+    // ---- the view's queries, runs, tiles and walk tiles inside the parent's position space
+    RunPlan v;
+    if (!plan_view_runs(pm.qstart_h, pm.qlen_h, pm.perm_host, pm.wt_start_h, csr, parent_query, run_docs_target(), &v, err)) return nullptr;
+    m.maxlen = v.maxlen;
+    m.perm_host = std::move(v.perm_host);
+    m.nruns = v.run_q0.size();
+    std::vector<uint32_t> qnpos(m.nq), qnneg(m.nq);
     for (size_t q = 0; q < m.nq; q++) {
-        const uint32_t pq = parent_query[q];
-        const size_t len = csr.qoff[q + 1] - csr.qoff[q];
-        if (pq >= pm.nq || pm.qlen_h[pq] != len) return fail("create_view: a query of the view differs from the parent's");
-        qstart[q] = pm.qstart_h[pq];
-        qlen[q] = (uint32_t)len;
-        qtight[q] = csr.qoff[q];
-        qnpos[q] = pm.qnpos_h[pq];
-        qnneg[q] = pm.qnneg_h[pq];
-        m.maxlen = std::max(m.maxlen, len);
-        for (size_t k = 0; k < len; k++) {
-            const uint32_t id = pm.perm_host[(size_t)qstart[q] + k];
-            if (id != csr.perm[csr.qoff[q] + k]) return fail("create_view: document order inside a query differs from the parent's");
-            m.perm_host[(size_t)qstart[q] + k] = id;
-        }
+        qnpos[q] = pm.qnpos_h[parent_query[q]];
+        qnneg[q] = pm.qnneg_h[parent_query[q]];
     }
-    qtight[m.nq] = csr.qoff[m.nq];
-    // the tiles of the parent's position space this view touches: position-parallel kernels (exact scoring, resident
-    // refreshes) visit only these
-    std::vector<uint32_t> vtiles;
-    {
-        std::vector<char> touched((m.np + 63) / 64, 0);
-        for (size_t q = 0; q < m.nq; q++)
-            for (size_t t = qstart[q] >> 6; t <= ((size_t)qstart[q] + qlen[q] - 1) >> 6; t++) touched[t] = 1;
-        for (size_t t = 0; t < touched.size(); t++)
-            if (touched[t]) vtiles.push_back((uint32_t)t);
-    }
-    {
-        size_t q0 = 0;
-        while (q0 < m.nq) {
-            size_t q1 = q0 + 1, docs = qlen[q0];
-            while (q1 < m.nq && qstart[q1] == qstart[q1 - 1] + qlen[q1 - 1] && docs + qlen[q1] <= target) {
-                docs += qlen[q1];
-                q1++;
-            }
-            run_q0.push_back((uint32_t)q0);
-            run_q1.push_back((uint32_t)q1);
-            run_pos.push_back(qstart[q0] & ~63u);
-            run_lo.push_back(qstart[q0] & 63u);
-            run_docs.push_back((uint32_t)docs + (qstart[q0] & 63u));
-            q0 = q1;
-        }
-    }
-    m.nruns = run_q0.size();
-    std::vector<uint32_t> run_order(m.nruns);
-    for (size_t r = 0; r < m.nruns; r++) run_order[r] = (uint32_t)r;
-    std::stable_sort(run_order.begin(), run_order.end(), [&](uint32_t x, uint32_t y) { return run_docs[x] > run_docs[y]; });
-    // the parent's walk tiles (kernels_order.inc) as this view meets them: the tile each run starts in, and the tiles that
-    // hold the view's documents (the ones whose R ranks rslot_kernel keeps)
-    std::vector<uint32_t> run_wt0(m.nruns), wlist;
-    {
-        const std::vector<uint32_t>& wts = pm.wt_start_h;
-        auto tile_of = [&](uint32_t p) { return (uint32_t)(std::upper_bound(wts.begin(), wts.begin() + pm.nwt, p) - wts.begin() - 1); };
-        for (size_t r = 0; r < m.nruns; r++) {
-            const uint32_t first = qstart[run_q0[r]], last = qstart[run_q1[r] - 1] + qlen[run_q1[r] - 1] - 1u;
-            run_wt0[r] = tile_of(first);
-            for (uint32_t t = run_wt0[r], te = tile_of(last); t <= te; t++)
-                if (wlist.empty() || wlist.back() < t) wlist.push_back(t);  // (runs ascend in position: so do their tiles)
-        }
-    }
-    std::vector<uint32_t> qlist(m.nq), fv_qlist(m.nq);
-    {
-        auto classes = [&](uint32_t floor_pad, std::vector<uint32_t>& list, std::vector<Impl::SizeClass>& out) {
-            auto npad_of = [floor_pad](uint32_t len) {
-                uint32_t p2 = floor_pad;
-                while (p2 < len) p2 <<= 1;
-                return p2;
-            };
-            for (size_t q = 0; q < m.nq; q++) list[q] = (uint32_t)q;
-            std::stable_sort(list.begin(), list.end(), [&](uint32_t x, uint32_t y) { return npad_of(qlen[x]) < npad_of(qlen[y]); });
-            for (size_t k = 0; k < m.nq;) {
-                const uint32_t np2 = npad_of(qlen[list[k]]);
-                size_t e = k;
-                while (e < m.nq && npad_of(qlen[list[e]]) == np2) e++;
-                out.push_back({np2, (uint32_t)k, (uint32_t)(e - k)});
-                k = e;
-            }
-        };
-        classes(64, qlist, m.size_classes);
-        fv_build_classes(qlen.data(), m.nq, fv_qlist, m.fv_classes);
-    }
+    std::vector<uint32_t> qlist, fv_qlist;
+    m.size_classes = bucket_queries(v.qlen, pow2_from_64, &qlist);
+    m.fv_classes = fv_build_classes(v.qlen, &fv_qlist);
     // ---- shared with the parent: the feature tiles and every per-document / per-class array
     m.xb.alias(pm.xb);
     m.gain.alias(pm.gain);
@@ -1407,7 +1074,7 @@ std::shared_ptr<DeviceDataset> DeviceDataset::create_view(const std::shared_ptr<
     m.wofs.alias(pm.wofs);
     m.wt_start_h = pm.wt_start_h;
     m.nwt = pm.nwt;
-    m.nwlist = wlist.size();
+    m.nwlist = v.wlist.size();
     m.xcol.alias(pm.xcol);
     m.colstd = pm.colstd;
     m.colmode = pm.colmode;
@@ -1420,17 +1087,17 @@ std::shared_ptr<DeviceDataset> DeviceDataset::create_view(const std::shared_ptr<
     m.disc.alias(pm.disc);
     m.dcgtab.alias(pm.dcgtab);
     m.termtab.alias(pm.termtab);
-    if (!upload(m.qstart, qstart, err) || !upload(m.qlen, qlen, err) || !upload(m.qtight, qtight, err) ||
-        !upload(m.run_q0, run_q0, err) || !upload(m.run_q1, run_q1, err) || !upload(m.run_pos, run_pos, err) ||
-        !upload(m.run_docs, run_docs, err) || !upload(m.run_order, run_order, err) || !upload(m.run_lo, run_lo, err) ||
+    if (!upload(m.qstart, v.qstart, err) || !upload(m.qlen, v.qlen, err) || !upload(m.qtight, v.qtight, err) ||
+        !upload(m.run_q0, v.run_q0, err) || !upload(m.run_q1, v.run_q1, err) || !upload(m.run_pos, v.run_pos, err) ||
+        !upload(m.run_docs, v.run_docs, err) || !upload(m.run_order, v.run_order, err) || !upload(m.run_lo, v.run_lo, err) ||
         !upload(m.qlist, qlist, err) || !upload(m.fv_qlist, fv_qlist, err) || !upload(m.qnpos, qnpos, err) ||
-        !upload(m.qnneg, qnneg, err) || !upload(m.vtiles, vtiles, err) || !upload(m.run_wt0, run_wt0, err) || !upload(m.wlist, wlist, err))
+        !upload(m.qnneg, qnneg, err) || !upload(m.vtiles, v.vtiles, err) || !upload(m.run_wt0, v.run_wt0, err) || !upload(m.wlist, v.wlist, err))
         return nullptr;
-    m.nvtiles = frdev::pricing_env("FR_VIEW_ALL_TILES") ? 0 : vtiles.size();  // (FR_VIEW_ALL_TILES=1: round 2's behaviour, for A/B runs)
+    m.nvtiles = frdev::pricing_env("FR_VIEW_ALL_TILES") ? 0 : v.vtiles.size();  // (FR_VIEW_ALL_TILES=1: round 2's behaviour, for A/B runs)
     if (!m.flags.ensure(1, err) || !m.dbgc.ensure(4, err)) return nullptr;
-    if (!chk(hipMemset(m.flags.p, 0, sizeof(int)), "clear flags")) return nullptr;
-    m.qstart_h = qstart;
-    m.qlen_h = qlen;
+    if (!hip_ok(hipMemset(m.flags.p, 0, sizeof(int)), "clear flags", err)) return nullptr;
+    m.qstart_h = std::move(v.qstart);
+    m.qlen_h = std::move(v.qlen);
     m.qnpos_h = qnpos;
     m.qnneg_h = qnneg;
     return ds;

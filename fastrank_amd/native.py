@@ -478,6 +478,50 @@ def device_form(dataset: CDataset, slot: int = 0) -> Dict:
     return f
 
 
+def host_layout(dataset: CDataset, parent_queries=None, row_hash=None, view: Optional[CDataset] = None) -> Dict:
+    """The host-side layout of a dataset (csrc/dataset_layout.hpp) built from its host CSR without a device
+    (fr_debug_dataset_layout): the scalars and tables of device_form that are host arithmetic, by the same names, plus termtab,
+    qnpos, qnneg, qlist, fv_qlist and the size classes (rows of class, offset, count).  parent_queries: the result's "view"
+    holds the tables of the view made of these queries of the dataset (`view`: the dataset whose own regrouping is the
+    view's; default: the dataset's documents in its order).  row_hash[np]: the row hashes by position (default: a host hash)."""
+    L = _load()
+    pq = None if parent_queries is None else np.ascontiguousarray(parent_queries, dtype=np.uint32)
+    rh = None if row_hash is None else np.ascontiguousarray(row_hash, dtype=np.uint64)
+
+    def call(name, arr):
+        return _json_reply(L.fr_debug_dataset_layout(
+            dataset.pointer, None if pq is None else pq.ctypes.data, 0 if pq is None else len(pq), None if view is None else view.pointer,
+            None if rh is None else rh.ctypes.data, 0 if rh is None else len(rh), None if name is None else name.encode("utf-8"),
+            None if arr is None else arr.ctypes.data, 0 if arr is None else arr.nbytes))
+
+    s = {k: int(v) for k, v in call(None, None).items()}
+
+    def tables(pre, extra):
+        out = {k[len(pre):]: v for k, v in s.items() if k.startswith(pre) and (pre or not k.startswith("view_"))}
+        nq, nruns, npos = out["nq"], out["nruns"], out["np"]
+        spec = [(n, np.uint32, nq, None) for n in ("qstart", "qlen", "qlist", "fv_qlist")] + [("qtight", np.uint32, nq + 1, None)]
+        spec += [(n, np.uint32, nruns, None) for n in ("run_q0", "run_q1", "run_pos", "run_docs", "run_lo", "run_order", "run_wt0")]
+        spec += [("perm_host", np.uint32, npos, None), ("size_classes", np.uint32, 3 * out["n_size_classes"], (-1, 3)),
+                 ("fv_classes", np.uint32, 3 * out["n_fv_classes"], (-1, 3))]
+        for name, dtype, count, shape in spec + extra:
+            arr = np.zeros(count, dtype=dtype)
+            call(pre + name, arr)
+            out[name] = arr if shape is None else arr.reshape(shape)
+        return out
+
+    npos, nq, ncls = s["np"], s["nq"], s["ncls"]
+    f = tables("", [(n, t, npos, None) for n, t in (("perm", np.uint32), ("gain", np.float32), ("gexp", np.float64), ("gcls", np.uint32),
+                                                    ("gkey", np.uint16), ("segtab", np.uint16), ("wofs", np.uint8))] +
+               [("wt_start", np.uint32, s["nwt"] + 1, None), ("qnpos", np.uint32, nq, None), ("qnneg", np.uint32, nq, None),
+                ("dcgtab", np.float64, ncls * s["dcg_ranks"], (ncls, s["dcg_ranks"])),
+                # (empty when the dataset has too many gain classes for it)
+                ("termtab", np.float64, s["termtab_len"], (ncls + 1, s["tablen"]) if s["termtab_len"] else None)])
+    f["labels_small_int"] = bool(f["labels_small_int"])
+    if pq is not None:
+        f["view"] = tables("view_", [("vtiles", np.uint32, s["view_nvtiles"], None), ("wlist", np.uint32, s["view_nwlist"], None)])
+    return f
+
+
 def rccl_selftest(device: int = 0) -> Dict:
     """A one-rank RCCL communicator on `device` through the library's exchange code (dlopen, ncclCommInitAll, grouped
     ncclAllGather, compare, destroy): the report of fr_rccl_allgather."""

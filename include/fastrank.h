@@ -328,6 +328,19 @@ const void *fr_debug_walk_tiles(const uint32_t *run_pos, const uint32_t *run_q0,
  * JSON {"present": bool, "bytes": n}; present = false when the dataset has no such table (xcol, xslot and the column
  * statistics are optional), an error when out_bytes is not n or the name is unknown. */
 const void *fr_debug_device_form(const CDataset *dataset, int slot, const void *table, void *out, size_t out_bytes);
+/* The host-side layout of a dataset (csrc/dataset_layout.hpp: runs, size classes, gain tables, duplicate groups, walk tiles)
+ * built from its host CSR alone -- no device is touched, nothing is kept.  The protocol and the table names of
+ * fr_debug_device_form: table == NULL gives the JSON of sizes ("np", "nq", "nruns", "nwt", "ncls", "tablen", "key_bits",
+ * "key_cls_bits", "dup_groups", "verify_xs", "relmask", ...), otherwise the named table is copied to `out` (JSON {"bytes": n};
+ * a wrong out_bytes or an unknown name is an error).  Beyond fr_debug_device_form's names: "termtab", "qnpos", "qnneg",
+ * "qlist", "fv_qlist", "size_classes" / "fv_classes" (u32 triples class, offset, count).  parent_queries[n_parent_queries]
+ * (optional): also the tables of the view that holds these queries of the dataset, as "view_qstart", "view_run_lo",
+ * "view_vtiles", "view_wlist", ... ; `view` (optional) = the dataset whose CSR is the view's own (NULL: cut from `dataset`'s).
+ * row_hash[n_row_hash = np] (optional): the 64-bit row hash of every position, as the device computes them (NULL: a host
+ * hash of the row bytes). */
+const void *fr_debug_dataset_layout(const CDataset *dataset, const uint32_t *parent_queries, size_t n_parent_queries,
+                                    const CDataset *view, const uint64_t *row_hash, size_t n_row_hash, const void *table,
+                                    void *out, size_t out_bytes);
 /* The same call sequence with a one-rank communicator on `device` (what a one-GPU box can run of it): same JSON. */
 const void *fr_debug_rccl_selftest(int device);
 /* Frees the device-to-device copies train_model made of this dataset on other devices / in other contexts (they are kept

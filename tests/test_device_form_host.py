@@ -1,9 +1,19 @@
 """The numpy restatement of the device form (tests/device_form_model.py) held to its own definitions, without a device:
 tests/test_gpu_device_form.py compares the tables the device built with it, so the restatement must not be wrong in the
 same way.  The tile index is a bijection, the restated walk tiles are the library's host rule, every segment's visiting
-order is a permutation of it, and the storage order inside a query reproduces the oracle's total order."""
-import numpy as np
+order is a permutation of it, and the storage order inside a query reproduces the oracle's total order.
 
+The second half holds the library's own host-side layout (csrc/dataset_layout.hpp, read with native.host_layout: what
+DeviceDataset::create / create_view compute before they upload) to the same restatement, again without a device."""
+import math
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import fastrank_amd as fr
 from fastrank_amd import native
 from oracle import pyoracle as o
 from tests import device_form_model as dfm
@@ -121,3 +131,196 @@ def test_gain_tables_and_duplicate_groups_of_a_small_case():
     assert mn.tolist() == [0.0, -3.0] and mx.tolist() == [0.0, 0.0] and at_min.tolist() == [3, 2] and at_max.tolist() == [3, 1]
     assert mode.tolist() == [3, 3]
     assert dfm.colmax(np.array([[1.0, np.nan, -np.inf, -0.0], [-2.0, 1.0, 1.0, 0.0]], dtype=np.float32)).tolist() == [2.0, np.inf, np.inf, 0.0]
+
+
+# ---- the library's host-side layout (csrc/dataset_layout.hpp through native.host_layout) -----------------------------------
+
+
+def _dataset(qlens, d, labels, seed):
+    """Queries of the given lengths with interleaved rows (first appearance in order 0, 1, ...), labels drawn from `labels`."""
+    rng = np.random.default_rng(seed)
+    rest = np.repeat(np.arange(len(qlens), dtype=np.int64), np.asarray(qlens, dtype=np.int64) - 1)
+    qid = np.concatenate([np.arange(len(qlens), dtype=np.int64), rest[rng.permutation(len(rest))]])   # one row of every query first
+    y = rng.choice(np.asarray(labels, dtype=np.float64), size=len(qid))
+    X = rng.normal(size=(len(qid), d)).astype(np.float32)
+    return rng, X, y, qid
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
+
+
+def _partition_matches(h, m, label):
+    """gkey's group ids (0 = no duplicate, ids per query) describe the partition `label` {instance id: group}."""
+    group = h["gkey"].astype(np.int64) >> h["key_cls_bits"]
+    for q, ids in enumerate(m.groups):
+        lo = int(m.lay["qstart"][q])
+        got = group[lo: lo + len(ids)]
+        exp = np.array([label.get(int(i), -1) for i in ids])
+        assert np.array_equal(got == 0, exp == -1), q
+        assert np.array_equal(got[:, None] == got[None, :], exp[:, None] == exp[None, :]), q
+
+
+def test_host_layout_run_and_position_tables_are_the_restatement():
+    for k, qlens in enumerate(_random_layouts()):
+        _, X, y, qid = _dataset(qlens, 2, range(5), 20 + k)
+        h = native.host_layout(fr.CDataset.from_numpy(X, y, qid))
+        m = dfm.Form(X, y, qid, order_tables=False)
+        assert (h["np"], h["nq"], h["n"], h["d"], h["dq"], h["nruns"]) == (m.np, len(qlens), len(y), 2, 1, len(m.lay["run_pos"]))
+        assert h["maxlen"] == max(qlens) and h["no_document"] == dfm.NO_DOCUMENT and h["walk_tile"] == dfm.WALK_TILE
+        for name in ("qstart", "qlen", "run_q0", "run_q1", "run_pos", "run_docs", "run_order"):
+            assert h[name].dtype == np.uint32 and np.array_equal(h[name], m.lay[name]), (name, qlens)
+        assert not h["run_lo"].any() and np.array_equal(h["qtight"], np.concatenate([[0], np.cumsum(qlens)]))
+        assert np.array_equal(h["perm_host"], m.perm) and np.array_equal(h["perm"], m.perm)
+        assert h["nwt"] == len(m.wt_start) - 1 and np.array_equal(h["wt_start"], m.wt_start)
+        assert np.array_equal(h["run_wt0"], m.run_wt0) and np.array_equal(h["segtab"], m.segtab)
+        starts = m.wt_start.astype(np.int64)
+        docs = np.flatnonzero(m.has_document)
+        assert np.array_equal(h["wofs"][docs], docs - starts[np.searchsorted(starts[:-1], docs, side="right") - 1])
+        assert not h["wofs"][~m.has_document].any()
+
+
+@pytest.mark.parametrize("labels", [tuple(range(5)), tuple(range(32)), (-1.5, -0.0, 0.0, 0.25, 2.75, 3.0)], ids=["0..4", "0..31", "fractional"])
+def test_host_layout_gain_tables(labels):
+    _, X, y, qid = _dataset(QLENS, 3, labels, 40 + len(labels))
+    h = native.host_layout(fr.CDataset.from_numpy(X, y, qid))
+    m = dfm.Form(X, y, qid, order_tables=False)
+    assert np.array_equal(_bits(h["gain"]), _bits(m.gain)) and np.array_equal(_bits(h["gexp"]), _bits(m.gexp))
+    assert np.array_equal(h["gcls"], m.gcls) and h["ncls"] == len(m.dcgtab) == len(set(float(v) + 0.0 for v in labels))
+    assert np.array_equal(_bits(h["dcgtab"]), _bits(m.dcgtab))
+    assert h["labels_small_int"] == all(float(v).is_integer() for v in labels)
+    class_gain = np.unique(m.gain[m.has_document] + np.float32(0.0))[::-1]
+    assert h["relmask"] == sum(1 << c for c, g in enumerate(class_gain) if g > 0)
+    for q, ids in enumerate(m.groups):
+        g = np.asarray(y, dtype=np.float32)[ids]
+        assert (h["qnpos"][q], h["qnneg"][q]) == ((g > 0).sum(), (g < 0).sum()), q
+    tablen = 16
+    while tablen < max(QLENS):
+        tablen *= 2
+    assert h["tablen"] == tablen and h["termtab"].shape == (h["ncls"] + 1, tablen)
+    exp = np.array([[m.dcgtab[c, 0] / math.log2(r + 2.0) for r in range(tablen)] for c in range(h["ncls"])])
+    assert np.array_equal(_bits(h["termtab"][:-1]), _bits(exp)) and not _bits(h["termtab"][-1]).any()
+
+
+def _planted_duplicates(across_classes):
+    """About six queries of 2-40 documents, d = 3: rows equal bit for bit inside a query -- inside one gain class, and
+    (across_classes) under different labels -- and rows that differ from another only in the sign of a zero."""
+    qlens = [2, 7, 40, 13, 25, 31]
+    rng, X, y, qid = _dataset(qlens, 3, range(5), 77)
+    X[:, 1] = rng.integers(-1, 2, len(y))                     # a column with zeros to flip
+    rows = [np.flatnonzero(qid == q) for q in range(len(qlens))]
+    for q in (1, 2, 3, 4, 5):
+        a, b, c, e = (int(v) for v in rows[q][:4])
+        X[b], y[b] = X[a], y[a]                               # a duplicate inside one gain class
+        X[a, 1] = X[b, 1] = 0.0
+        X[c], y[c] = X[a], y[a]
+        X[c, 1] = -0.0                                        # equal by value, not bit for bit: another row
+        if across_classes:
+            X[e], y[e] = X[a], (y[a] + 1.0) % 5.0             # a duplicate under another label
+    three = rows[2][10:13]
+    X[three] = X[three[0]]                                    # a group of three
+    y[three] = y[three[0]]
+    return X, y, qid
+
+
+def test_host_layout_duplicate_groups_under_any_row_hash():
+    X, y, qid = _planted_duplicates(across_classes=True)
+    ds = fr.CDataset.from_numpy(X, y, qid)
+    m = dfm.Form(X, y, qid, order_tables=False)
+    label, ngroups = dfm.duplicate_groups(X, m.groups)
+    assert ngroups == 6 and len(label) == 5 * 3 + 3
+    colliding = np.zeros(m.np, dtype=np.uint64)
+    colliding[m.has_document] = (X[m.perm[m.has_document], 1] == 0).astype(np.uint64)   # -0.0 / +0.0 rows and others that hold a zero share a hash
+    for row_hash in (None, np.zeros(m.np, dtype=np.uint64), colliding):
+        h = native.host_layout(ds, row_hash=row_hash)
+        cls_bits = h["key_cls_bits"]
+        assert (1 << cls_bits) >= h["ncls"] > (1 << cls_bits) // 2 and cls_bits < h["key_bits"] <= 16
+        assert np.array_equal(h["gkey"] & ((1 << cls_bits) - 1), m.gcls)
+        assert h["dup_groups"] == ngroups
+        _partition_matches(h, m, label)
+
+
+def test_host_layout_duplicates_inside_one_class_need_no_group_bits_and_verify_xs_starts_by_their_share():
+    X, y, qid = _planted_duplicates(across_classes=False)
+    m = dfm.Form(X, y, qid, order_tables=False)
+    label, ngroups = dfm.duplicate_groups(X, m.groups)
+    h = native.host_layout(fr.CDataset.from_numpy(X, y, qid))
+    assert h["dup_groups"] == ngroups == 6 and h["key_bits"] == h["key_cls_bits"] and np.array_equal(h["gkey"], m.gcls)
+    assert len(label) * 200 > len(y) and h["verify_xs"] == 4
+    # exactly 0.5 % duplicated (2 of 400 documents) stays at 1, one pair more (4 of 400) starts at 4
+    for pairs, xs in ((1, 1), (2, 4)):
+        rng, X, y, qid = _dataset([100, 100, 100, 100], 3, range(5), 5)
+        for q in range(pairs):
+            a, b = (int(v) for v in np.flatnonzero(qid == q)[:2])
+            X[b] = X[a]
+        h = native.host_layout(fr.CDataset.from_numpy(X, y, qid))
+        assert h["dup_groups"] == pairs and h["verify_xs"] == xs, pairs
+
+
+def test_host_layout_views_are_the_restatement_and_refuse_a_view_that_differs():
+    rng, X, y, qid = _dataset(QLENS + [129, 1, 300, 64, 2, 127], 3, range(5), 11)
+    ds = fr.CDataset.from_numpy(X, y, qid)
+    m = dfm.Form(X, y, qid, order_tables=False)
+    nq = len(m.groups)
+    for sel in (np.arange(0, nq, 2), np.arange(3, 11)):       # every second query; a contiguous block
+        v = native.host_layout(ds, parent_queries=sel)["view"]
+        vl = dfm.view_layout(m.lay, m.wt_start, sel)
+        assert (v["np"], v["nq"], v["n"], v["nruns"]) == (m.np, len(sel), int(vl["qlen"].sum()), len(vl["run_q0"]))
+        for name in ("qstart", "qlen", "run_q0", "run_q1", "run_pos", "run_lo", "run_docs", "run_order", "run_wt0", "vtiles", "wlist"):
+            assert np.array_equal(v[name], vl[name]), name
+        assert np.array_equal(v["qtight"], np.concatenate([[0], np.cumsum(vl["qlen"])]))
+        mine = np.zeros(m.np, dtype=bool)
+        for b, n in zip(vl["qstart"], vl["qlen"]):
+            mine[int(b): int(b + n)] = True
+        assert np.array_equal(v["perm_host"], np.where(mine, m.perm, dfm.NO_DOCUMENT))
+    assert native.host_layout(ds, parent_queries=np.arange(3, 11))["view"]["run_lo"].any()
+    # a view whose own regrouping differs from the parent's: another length, then another order inside a query
+    with pytest.raises(Exception, match="create_view: a query of the view differs from the parent's"):
+        native.host_layout(ds, parent_queries=[2, 4], view=ds.subsample_queries(["2", "3"]))
+    y2 = y.copy()
+    ids = m.groups[4]
+    y2[ids] = y[ids][::-1] + 10.0 * (np.arange(len(ids)) == 0)  # (the first stored document can no longer be first)
+    other = fr.CDataset.from_numpy(X, y2, qid)
+    with pytest.raises(Exception, match="create_view: document order inside a query differs from the parent's"):
+        native.host_layout(ds, parent_queries=[2, 4], view=other.subsample_queries(["2", "4"]))
+    same = native.host_layout(ds, parent_queries=[2, 4], view=ds.subsample_queries(["2", "4"]))["view"]
+    assert np.array_equal(same["qstart"], m.lay["qstart"][[2, 4]])
+
+
+def test_size_classes_are_stable_partitions_of_the_queries():
+    qlens = [129, 1, 64, 2049, 65, 128, 1, 129, 64, 65, 2049, 128, 63]
+    _, X, y, qid = _dataset(qlens, 1, range(3), 3)
+    h = native.host_layout(fr.CDataset.from_numpy(X, y, qid), parent_queries=np.arange(1, len(qlens)))
+    pad = lambda n: max(64, 1 << (int(n) - 1).bit_length())
+    assert [pad(n) for n in (1, 64, 65, 128, 129, 2049)] == [64, 64, 128, 128, 256, 4096]
+    for lay, lens in ((h, np.asarray(qlens)), (h["view"], np.asarray(qlens[1:]))):
+        for classes, qlist, rule in ((lay["size_classes"], lay["qlist"], pad), (lay["fv_classes"], lay["fv_qlist"], None)):
+            assert sorted(qlist.tolist()) == list(range(len(lens)))                 # a partition of 0..nq-1 ...
+            assert classes[:, 1].tolist() == np.concatenate([[0], np.cumsum(classes[:, 2])[:-1]]).tolist() and classes[:, 2].sum() == len(lens)
+            assert (np.diff(classes[:, 0].astype(np.int64)) > 0).all()              # ... into ascending classes ...
+            seen = {}
+            for c, off, cnt in classes.tolist():
+                members = qlist[off: off + cnt]
+                assert cnt > 0 and (np.diff(members.astype(np.int64)) > 0).all()    # ... in dataset order inside a class
+                if rule is not None:
+                    assert [rule(n) for n in lens[members]] == [c] * cnt
+                for n in lens[members]:
+                    assert seen.setdefault(min(int(n), 2048), c) == c               # one class per length
+        assert lay["size_classes"][:, 0].tolist() == [64, 128, 256, 4096]
+
+
+def test_dataset_layout_header_under_address_and_undefined_sanitizers(tmp_path):
+    """tests/dataset_layout_sanitize.cpp: a program of its own over csrc/dataset_layout.hpp alone (a query longer than a
+    walk tile, a view), built with -fsanitize=address,undefined and run directly."""
+    cxx = next((c for c in (os.environ.get("CXX"), "c++", "g++", "clang++") if c and shutil.which(c)), None)
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    here = os.path.dirname(os.path.abspath(__file__))
+    exe = str(tmp_path / "dataset_layout_sanitize")
+    build = subprocess.run([cxx, "-std=c++17", "-O0", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-pthread",
+                            "-I", os.path.join(here, "..", "fastrank_amd", "csrc"), os.path.join(here, "dataset_layout_sanitize.cpp"), "-o", exe],
+                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert build.returncode == 0, build.stdout
+    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert run.returncode == 0 and "dataset_layout ok" in run.stdout, run.stdout

@@ -356,6 +356,51 @@ def test_gains_classes_and_duplicate_groups(labels):
         assert np.array_equal(got[:, None] == got[None, :], exp[:, None] == exp[None, :]), q
 
 
+# ---- the host-side layout the library serves without a device is what create() / create_view() uploaded -------------------
+
+
+def test_host_layout_is_what_the_device_holds():
+    qlens = [1, 2, 63, 64, 65, 127, 128, 129, 300, 800]
+    rng = np.random.default_rng(77)
+    qid = np.repeat(np.arange(1, len(qlens) + 1, dtype=np.int64), qlens)[rng.permutation(sum(qlens))]
+    y = rng.choice(np.arange(5.0), size=len(qid))
+    X = _matrix(rng, len(qid), 5)
+    for _ in range(12):                                     # duplicated rows inside a query, some under another label
+        a = int(rng.integers(0, len(qid)))
+        X[int(rng.choice(np.flatnonzero(qid == qid[a])))] = X[a]
+    ds = fr.CDataset.from_numpy(X, y, qid)
+    f = native.device_form(ds)
+    sel = np.arange(0, len(qlens), 2)                       # the view's queries, as indices of the dataset's stored queries
+    keys, _ = dfm.regroup(y, qid)
+    view = ds.subsample_queries([str(q) for q in keys[sel]])
+    vf = native.device_form(view)
+    h = native.host_layout(ds, parent_queries=sel)
+    assert vf["shares_parent_matrix"] and len(h["view"]["vtiles"]) and len(h["view"]["wlist"])
+    shared = sorted(k for k in h if k in f and k != "gkey" and k != "view")
+    assert {"perm", "perm_host", "gain", "gexp", "gcls", "segtab", "wofs", "wt_start", "qstart", "qlen", "qtight", "run_q0", "run_q1",
+            "run_pos", "run_docs", "run_lo", "run_order", "run_wt0", "dcgtab", "np", "nq", "n", "d", "dq", "nruns", "nwt", "maxlen",
+            "ncls", "key_bits", "key_cls_bits", "dup_groups", "no_document", "walk_tile", "dcg_ranks"} <= set(shared)
+    for name in shared:
+        if isinstance(h[name], np.ndarray):
+            assert _same_bytes(h[name], f[name]), name
+        else:
+            assert h[name] == f[name], name
+    for name in sorted(k for k in h["view"] if k in vf):
+        if isinstance(h["view"][name], np.ndarray):
+            assert _same_bytes(h["view"][name], vf[name]), name
+        else:
+            assert h["view"][name] == vf[name], name
+    assert {"qstart", "qlen", "qtight", "run_lo", "run_wt0", "vtiles", "wlist", "perm_host", "nruns", "maxlen"} <= set(h["view"]) & set(vf)
+    # the host hook hashes rows on the host, the device with row_hash_kernel: group ids may be numbered differently, the
+    # groups they name are the same
+    cls_bits = f["key_cls_bits"]
+    assert f["dup_groups"] > 0 and f["key_bits"] > cls_bits
+    assert np.array_equal(h["gkey"] & ((1 << cls_bits) - 1), f["gkey"] & ((1 << cls_bits) - 1))
+    for b, n in zip(f["qstart"], f["qlen"]):
+        got, exp = (g[int(b): int(b + n)].astype(np.int64) >> cls_bits for g in (h["gkey"], f["gkey"]))
+        assert np.array_equal(got == 0, exp == 0) and np.array_equal(got[:, None] == got[None, :], exp[:, None] == exp[None, :])
+
+
 # ---- views -----------------------------------------------------------------------------------------------------------------
 
 
