@@ -30,6 +30,8 @@
 //   kernels_hist.inc        LambdaMART's histogram grower: one-byte bins, int64 fixed-point gradients, per-node histograms
 //   dataset_layout.hpp      (through device.hpp; host only, no HIP) the layout arithmetic of a dataset: runs, size classes, gain
 //                           tables, duplicate groups, walk tiles, a view's tables
+//   linesearch_policy.hpp   (host only, no HIP) the adaptive policies of the bound-and-verify line search: routing / back-off of
+//                           tie-heavy restarts, the R-rank refresh schedule, list length, redo grid, skip counter
 //   device_dataset.inc      DeviceDataset: the uploads of that layout (tiles, tables) and every launcher
 #include "device.hpp"
 
@@ -37,6 +39,7 @@
 #include <hip/hip_ext.h>
 
 #include "fullverify.hpp"
+#include "linesearch_policy.hpp"
 
 #include <cstring>
 #include <dlfcn.h>

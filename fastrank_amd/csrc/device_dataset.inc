@@ -165,6 +165,14 @@ struct DeviceDataset::Impl : DatasetDesc {
     uint32_t sub_na = 0, sub_nb = 0;
     bool ls_submit(LsCtx& c, int path, int measure, int64_t depth, const double* norms, const std::vector<LineGroup>& groups,
                    std::string* err);
+    // what ls_submit's prologue hands the launcher of the line search's kind: the staged groups (routed ones last), of which the
+    // verify kernel may take the first nV, and whether they read the resident sums / carry pending updates of them
+    struct LsTick { const std::vector<LineGroup>& groups; const double* norms; size_t nV; bool resident, any_update; };
+    bool submit_topk(LsCtx& c, const LsTick& t, std::string* err);
+    bool submit_rr(LsCtx& c, const LsTick& t, std::string* err);
+    bool submit_fv(LsCtx& c, const LsTick& t, std::string* err);
+    bool exact_instead(LsCtx& c, const LsTick& t, std::string* err);
+    bool submit_queued(LsCtx& c, const LsTick& t, size_t nverify, std::string* err);
     bool ls_collect(LsCtx& c, std::vector<double>* means, std::string* err);
     bool topk_policy(LsCtx& c, uint32_t nredo, uint32_t nslices, std::string* err);
     bool ls_exact(LsCtx& c, int measure, int64_t depth, const double* norms, const std::vector<LineGroup>& groups, std::string* err);
@@ -185,20 +193,19 @@ struct DeviceDataset::Impl : DatasetDesc {
     bool redo_launch(LsCtx& c, uint32_t off, const uint32_t* count_dev, uint32_t n, std::string* err);
     FSArgs scores_args(const uint32_t* gfeat, const double* gw, const double* gcand, double* rows, int* flags, size_t gc) const;
     RMArgs rank_args(const double* rows, const uint32_t* gncand, double* M, int* flags, size_t gc, size_t ldm, int measure, int64_t depth) const;
+    void topk_args(LsCtx& c, size_t G) const;
+    RRArgs rr_args(LsCtx& c, size_t G) const;
+    FVArgs fv_args(LsCtx& c, size_t G, uint32_t cls_bits, uint32_t dup_bits) const;
     int device = 0;
     hipStream_t stream = nullptr;
     std::vector<double> eps2_host;
     DevBuf<double> res;                // resident base sums: [slots][2][np]
     std::vector<uint8_t> res_half;     // which half of each slot is current
     uint64_t res_owner = 0;            // ticket of the trainer that owns the resident buffers
-    uint32_t approx_skip = 0;          // MRR / full-ranking paths: ticks for which the exact kernels are used directly (after a tick with many redos)
-    // NDCG@k: per resident slot (= restart), line searches still to be sent straight to the exact kernel, and the length of
-    // the current back-off (4, 8, 16: doubled while the verify kernel keeps failing on that restart, halved when it succeeds)
-    std::vector<uint8_t> slot_exact_left, slot_backoff;
+    LsPolicy pol;                      // what the next line searches are asked to do: routing / back-off, R-rank refreshes, skip counter (linesearch_policy.hpp)
     unsigned long long approx_pairs = 0, approx_redo = 0;  // statistics, in (query, group) pairs
     unsigned long long approx_redo_entries = 0;            // ... and in 16-candidate slices of them (NDCG@k)
     unsigned long long chain_runs = 0, chain_visits = 0;   // NDCG@k verify kernel: insertion-chain runs / (document, group) visits
-    unsigned long long exact_groups = 0;                   // NDCG@k: group line searches routed to the exact kernel
     unsigned long long audit_values = 0, audit_mismatches = 0;  // FR_VERIFY_AUDIT=1: published values re-derived by the exact kernel
     DevBuf<double> audit;
     DevBuf<unsigned long long> audit_cnt;
@@ -222,21 +229,7 @@ struct DeviceDataset::Impl : DatasetDesc {
     size_t nwlist = 0;
     // ... and per trainer
     DevBuf<uint8_t> rslot;             // [slots][np] the same by the resident sum R descending
-    std::vector<uint16_t> slot_rank_age;  // line searches since a slot's ranks were made (0xFFFF: never)
-    std::vector<uint16_t> slot_rank_upd;  // accepted candidates (changes of R) since then
-    std::vector<uint16_t> slot_rank_gap;  // line searches until the next refresh: 1, 2, 4, ... up to the period (a young model moves fast)
-    // Does keeping a restart's R ranks pay?  The verify kernel counts, per group, the documents that made it run its insertion
-    // chain; the host keeps a running mean of that count per (document, group) visit for every restart (its features differ
-    // from one line search to the next: the mean is over ~16 of them).  Ranks are made at a restart's first line search -- early
-    // in training nothing else orders the documents -- and refreshed every few line searches WHILE the chain runs often enough
-    // for the upkeep to pay: a restart whose chain runs rarely even so (storage order is gain descending, and where the
-    // labels carry the scores that is nearly R descending already) stops refreshing (mode 2: the last table stays, a stale
-    // order only costs admissions) and starts again if the chain runs creep up.  The two thresholds are measured, on five
-    // kinds of data (profiles/r06_rank_policy.txt).
-    std::vector<uint8_t> slot_rank_mode;      // 1 ranks refreshed, 2 not
-    std::vector<uint16_t> slot_rate_n;        // line searches in the running mean
-    std::vector<float> slot_rate;             // running mean of chain runs per visit
-    unsigned long long rank_slots_on = 0, rank_slots_off = 0;  // decisions made (statistics)
+    // (when they are refreshed: LsPolicy::plan_rank_refresh / observe_chain)
     // the main stream, the line-search contexts' streams and res_ready
     hipError_t open_streams(bool* at_event, StreamSignal* main_stream = nullptr);
     bool open_streams(std::string* err);
@@ -2164,17 +2157,10 @@ static void dispatch_exact(const LSArgs& a, int64_t depth, unsigned nblocks, siz
 
 // pairs of the verify kernel's redo list the exact kernel takes in its first, fixed-size launch (blocks past the
 // device-side count return at once: ~10 us when the list is short); FR_REDO_GRID pins it (tests)
-static constexpr int VERIFY_XS_MAX = 4;  // the longest lists compiled (K + 4 keys)
 static unsigned redo_grid_env() {
     const char* e = frdev::path_env("FR_REDO_GRID");
     return e ? (unsigned)std::min<long>(std::max<long>(std::atol(e), 64), 1 << 20) : 0u;
 }
-
-// Chain runs per (document, group) visit (running mean of a restart) below which its R ranks stop being refreshed, and above
-// which they are again.  Measured (profiles/r06_rank_policy.txt; ranks kept / never made, and what keeping them is worth):
-// mslr 0.148 / 0.195 (-1 %), ties 0.177 / 0.225 (+3 %), tiesmix 0.177 / 0.232 (+6 %), hard 0.180 / 0.319 (+12 %), hardties
-// 0.209 / 0.362 (+21 %).
-static constexpr double RANK_OFF_BELOW = 0.16, RANK_ON_ABOVE = 0.21;
 
 template <int K>
 static void launch_verify(const LSArgs& a, bool resident, bool dupk, int xs, unsigned nruns8, size_t G, size_t dp, size_t tab_lds_kt, hipStream_t st) {
@@ -2214,21 +2200,13 @@ uint64_t DeviceDataset::resident_reserve(size_t slots, std::string* err) {
         if (err) *err = "resident_reserve: the dataset has no column-major copy";
         return 0;
     }
-    m.slot_exact_left.assign(slots, 0);
-    m.slot_backoff.assign(slots, 0);
+    m.pol.reset(slots);
     {
         std::string* e2 = err;
         auto ensure = [&]() -> bool { return m.res.ensure(slots * 2 * m.np, e2); };
         if (!ensure()) return 0;
     }
     m.res_half.assign(slots, 0);
-    // the slots' R-rank tables start as the identity (storage order) and are made on a slot's first line search
-    m.slot_rank_age.assign(slots, 0xFFFF);
-    m.slot_rank_upd.assign(slots, 0);
-    m.slot_rank_gap.assign(slots, 1);
-    m.slot_rank_mode.assign(slots, 1);
-    m.slot_rate_n.assign(slots, 0);
-    m.slot_rate.assign(slots, 0.0f);
     if (m.xslot.p != nullptr) {
         std::string e2;
         if (m.rslot.ensure(slots * m.np, &e2)) {
@@ -2255,10 +2233,7 @@ bool DeviceDataset::resident_store_from_scores(uint64_t owner, size_t slot, size
                           hipMemcpyDeviceToDevice, m.stream));
     FR_HIP(hipEventRecord(m.res_ready, m.stream));
     m.res_ready_set = true;
-    if (slot < m.slot_rank_age.size()) {  // (new sums: the old ranks say nothing about them, and a young model moves fast again)
-        m.slot_rank_age[slot] = 0xFFFF;
-        m.slot_rank_gap[slot] = 1;
-    }
+    m.pol.new_sums(slot);
     return true;
 }
 
@@ -2280,13 +2255,13 @@ void DeviceDataset::chain_counters(unsigned long long* runs, unsigned long long*
     std::lock_guard<std::mutex> lk(impl_->mu);
     *runs = impl_->chain_runs;
     *visits = impl_->chain_visits;
-    if (ranked_on) *ranked_on = impl_->rank_slots_on;
-    if (ranked_off) *ranked_off = impl_->rank_slots_off;
+    if (ranked_on) *ranked_on = impl_->pol.rank_slots_on;
+    if (ranked_off) *ranked_off = impl_->pol.rank_slots_off;
 }
 
 void DeviceDataset::routing_counters(unsigned long long* exact_groups, unsigned long long* redo_entries) const {
     std::lock_guard<std::mutex> lk(impl_->mu);
-    *exact_groups = impl_->exact_groups;
+    *exact_groups = impl_->pol.exact_groups;
     *redo_entries = impl_->approx_redo_entries;
 }
 
@@ -2338,6 +2313,126 @@ RMArgs DeviceDataset::Impl::rank_args(const double* rows, const uint32_t* gnc, d
     a.measure = measure;
     a.depth = depth < 0 ? -1 : (depth > 0x7fffffff ? 0x7fffffff : (int)depth);
     return a;
+}
+
+// arguments of the three verify kernels of a line search whose groups are staged in the context's tick block (tick_begin,
+// stage_resident).  NDCG@k: into c.a, next to stage_resident's resident parameters; what depends on the bound and the
+// routing (gamma, the visiting order, eps2, the verify launch's G) is set by submit_topk
+void DeviceDataset::Impl::topk_args(LsCtx& c, size_t G) const {
+    const Impl& m = *this;
+    const TickStage& ts = c.ts;
+    LSArgs& a = c.a;
+    a.xb = (const float4*)m.xb.p;
+    a.gcls = m.gcls.p;
+    a.dcgtab = m.dcgtab.p;
+    a.qstart = m.qstart.p;
+    a.qlen = m.qlen.p;
+    a.run_q0 = m.run_q0.p;
+    a.run_q1 = m.run_q1.p;
+    a.run_pos = m.run_pos.p;
+    a.run_lo = m.run_lo.p;
+    a.run_docs = m.run_docs.p;
+    a.run_order = m.run_order.p;
+    a.wt_start = m.wt_start.p;
+    a.run_wt0 = m.run_wt0.p;
+    a.norms = m.norms.p;
+    a.disc = m.disc.p;
+    a.gfeat = c.td<uint32_t>(ts.o_gfeat);
+    a.gw = c.td<double>(ts.o_gw);
+    a.gcand = c.td<double>(ts.o_gcand);
+    a.gncand = c.td<uint32_t>(ts.o_gncand);
+    a.M = c.M.p;
+    a.flags = c.flags.p;
+    a.dbg_counters = m.dbgc.p;
+    a.dq = (uint32_t)m.dq;
+    a.d = (uint32_t)m.d;
+    a.nruns = (uint32_t)m.nruns;
+    a.G = (uint32_t)G;
+    a.ldm = (uint32_t)c.ldm;
+    a.depth = (int)c.depth;
+    a.ncls = (uint32_t)m.ncls;
+    a.redo_count = c.td<unsigned long long>(ts.o_count);
+    a.redo_list = c.redo.p;
+    a.chain_count = c.td<uint32_t>(ts.o_gredo) + G;
+    a.cls_mask = (1u << m.key_bits) - 1u;  // class bits + duplicate-group bits ride in the keys' low mantissa
+    a.cls_only_mask = (1u << m.key_cls_bits) - 1u;
+    a.gkey = m.gkey.p;
+}
+
+RRArgs DeviceDataset::Impl::rr_args(LsCtx& c, size_t G) const {
+    const Impl& m = *this;
+    const TickStage& ts = c.ts;
+    const LSArgs& a = c.a;
+    RRArgs ra{};
+    ra.xb = (const float4*)m.xb.p;
+    ra.qstart = m.qstart.p;
+    ra.qlen = m.qlen.p;
+    ra.qnpos = m.qnpos.p;
+    ra.gfeat = c.td<uint32_t>(ts.o_gfeat);
+    ra.gw = c.td<double>(ts.o_gw);
+    ra.gcand = c.td<double>(ts.o_gcand);
+    ra.gncand = c.td<uint32_t>(ts.o_gncand);
+    ra.eps2 = c.td<double>(ts.o_eps2);
+    ra.redo_count = c.td<uint32_t>(ts.o_count);
+    ra.redo_list = c.redo.p;
+    ra.res_cur = m.res.p;
+    ra.rs_slot = a.rs_slot;
+    ra.rs_par = a.rs_par;
+    ra.rs_updf = a.rs_updf;
+    ra.xcol = a.xcol;
+    ra.M = c.M.p;
+    ra.flags = c.flags.p;
+    ra.G = (uint32_t)G;
+    ra.ldm = (uint32_t)c.ldm;
+    ra.dq = (uint32_t)m.dq;
+    ra.d = (uint32_t)m.d;
+    ra.np = (uint32_t)m.np;
+    return ra;
+}
+
+// (cls_bits / dup_bits: low key bits of the gain class / duplicate group)
+FVArgs DeviceDataset::Impl::fv_args(LsCtx& c, size_t G, uint32_t cls_bits, uint32_t dup_bits) const {
+    const Impl& m = *this;
+    const TickStage& ts = c.ts;
+    const LSArgs& a = c.a;
+    FVArgs fa{};
+    fa.xb = (const float4*)m.xb.p;
+    fa.qstart = m.qstart.p;
+    fa.qlen = m.qlen.p;
+    fa.qnpos = m.qnpos.p;
+    fa.gcls = m.gcls.p;
+    fa.gfeat = c.td<uint32_t>(ts.o_gfeat);
+    fa.gw = c.td<double>(ts.o_gw);
+    fa.gcand = c.td<double>(ts.o_gcand);
+    fa.gncand = c.td<uint32_t>(ts.o_gncand);
+    fa.eps2 = c.td<double>(ts.o_eps2);
+    fa.termtab = m.termtab.p;
+    fa.norms = m.norms.p;
+    fa.redo_count = c.td<uint32_t>(ts.o_count);
+    fa.redo_list = c.redo.p;
+    fa.res_cur = m.res.p;
+    fa.rs_slot = a.rs_slot;
+    fa.rs_par = a.rs_par;
+    fa.rs_updf = a.rs_updf;
+    fa.M = c.M.p;
+    fa.flags = c.flags.p;
+    fa.relmask = m.relmask;
+    fa.G = (uint32_t)G;
+    fa.ldm = (uint32_t)c.ldm;
+    fa.dq = (uint32_t)m.dq;
+    fa.d = (uint32_t)m.d;
+    fa.np = (uint32_t)m.np;
+    fa.tablen = (uint32_t)m.tablen;
+    fa.cls_mask = (1u << (cls_bits + dup_bits)) - 1u;
+    fa.cls_only_mask = (1u << cls_bits) - 1u;
+    fa.cls_bits = cls_bits;
+    fa.key_cls_bits = m.key_cls_bits;
+    fa.dup = dup_bits ? 1u : 0u;
+    fa.gkey = m.gkey.p;
+    fa.padcls = (uint32_t)m.ncls;
+    fa.measure = c.measure;
+    fa.depth = c.depth < 0 ? -1 : (c.depth > 0x7fffffff ? 0x7fffffff : (int)c.depth);
+    return fa;
 }
 
 // ---- NDCG of any depth / AP by bound-and-verify (kernels_fullverify.inc) -------------------------------------
@@ -2477,7 +2572,9 @@ bool DeviceDataset::Impl::redo_launch(LsCtx& c, uint32_t off, const uint32_t* co
 // submit: validate, stage the groups and their resident parameters in the tick block, bound the error, then queue the verify
 // kernel and a fixed-size first launch of the exact kernels on its redo list -- or, where bound-and-verify does not apply,
 // the exact kernels alone.  collect: wait, finish a long redo list, count, and set the policies that steer the next line
-// searches.  The three verify kernels differ only in the switches on c.kind.
+// searches.  ls_submit is the prologue the three verify kernels share -- validation, the groups the policy routes, staging --
+// and hands over to the launcher of the line search's kind (submit_topk / submit_rr / submit_fv: bound, fallback decision,
+// launch, redo launch); the policies themselves are in linesearch_policy.hpp.
 
 static constexpr unsigned RR_REDO_GRID = 8192;  // reciprocal rank: redo-list pairs the exact kernel's first launch takes
 
@@ -2511,28 +2608,22 @@ bool DeviceDataset::Impl::ls_submit(LsCtx& c, int path, int measure, int64_t dep
         c.pending = true;
         return true;
     }
-    const size_t ldm = c.ldm, dp = m.dq * 4, nruns8 = ((m.nruns + 7) / 8) * 8;
-    if (c.kind == LSK_TOPK) {
+    const bool topk = c.kind == LSK_TOPK;
+    if (topk) {
         if (m.nq * G >= (size_t(1) << 28)) {  // (a redo entry is (q * G + g) * 16 + slice mask in 32 bits; M itself would be > 130 GB)
             if (err) *err = "linesearch: too many (query, group) pairs for one launch";
             return false;
         }
-        if (!c.M.ensure(m.nq * ldm, err) || !c.redo.ensure(m.nq * G, err)) return false;
+        if (!c.M.ensure(m.nq * c.ldm, err) || !c.redo.ensure(m.nq * G, err)) return false;
     }
     // FR_LS_EXACT=1: the exact kernels only
     const bool exact_only = std::getenv("FR_LS_EXACT") != nullptr;
     c.audit = std::getenv("FR_VERIFY_AUDIT") != nullptr;
-    const unsigned redo_pin = redo_grid_env();
     bool can_verify = !exact_only && m.colmax.size() == m.d;
-    switch (c.kind) {
-        case LSK_TOPK: can_verify = can_verify && m.ncls <= 256; break;
-        case LSK_RR: break;
-        case LSK_FV:  // (AP: the relevance of a class is one bit of a 32-bit mask, the padding class included)
-            can_verify = can_verify && frdev::path_env("FR_FV_OFF") == nullptr && m.ncls <= 256 &&
-                         (measure == M_NDCG ? m.termtab.cap > 0 : m.ncls <= 31);
-            break;
-    }
-    if (!can_verify && c.kind != LSK_TOPK) return m.ls_exact(c, measure, depth, norms, groups_in, err);
+    if (c.kind != LSK_RR) can_verify = can_verify && m.ncls <= 256;
+    if (c.kind == LSK_FV)  // (AP: the relevance of a class is one bit of a 32-bit mask, the padding class included)
+        can_verify = can_verify && frdev::path_env("FR_FV_OFF") == nullptr && (measure == M_NDCG ? m.termtab.cap > 0 : m.ncls <= 31);
+    if (!can_verify && !topk) return m.ls_exact(c, measure, depth, norms, groups_in, err);
     if (c.kind != LSK_RR) {
         // (a trainer's norms never change: its resident-sum ticket + the array's address stand for the contents, so the two
         // 250 KB comparisons a tick used to make happen once.  Evaluator::norms must stay as it is for a trainer's lifetime.)
@@ -2546,400 +2637,275 @@ bool DeviceDataset::Impl::ls_submit(LsCtx& c, int path, int measure, int64_t dep
             m.norms_token_ptr = norms;
         }
     }
-    // Top-k, per-group routing: a restart whose last verified line search left more than a quarter of its pairs undecided
-    // (its weights make many scores tie exactly) sends its next few line searches straight to the exact kernel -- the other
-    // groups of the tick stay on the verify kernel.
+    // top-k: the groups the policy routes to the exact kernel are staged behind the ones the verify kernel takes
     size_t nV = can_verify ? G : 0;  // groups the verify kernel takes (staged first)
     const std::vector<LineGroup>* gp = &groups_in;
-    if (c.kind == LSK_TOPK && can_verify && m.res_owner != 0) {
-        std::vector<char> ex(G, 0);
-        size_t nE = 0;
-        for (size_t g = 0; g < G; g++) {
-            const LineGroup& lg = groups_in[g];
-            if (lg.resident_owner == m.res_owner && lg.resident_slot >= 0 && (size_t)lg.resident_slot < m.slot_exact_left.size() &&
-                m.slot_exact_left[lg.resident_slot] > 0) {
-                ex[g] = 1;
-                nE++;
-            }
-        }
-        if (nE > 0) {
-            // (once per distinct slot and tick: a restart with more than 64 candidates has several groups on one slot)
-            std::vector<char> seen(m.slot_exact_left.size(), 0);
-            for (size_t g = 0; g < G; g++) {
-                if (!ex[g]) continue;
-                const size_t slot = (size_t)groups_in[g].resident_slot;
-                if (seen[slot]) continue;
-                seen[slot] = 1;
-                if (m.slot_exact_left[slot] > 0) m.slot_exact_left[slot]--;
-            }
-            m.exact_groups += nE;
-            nV = G - nE;
-            if (nV > 0) {  // verify groups first, exact groups behind them; collect() puts the columns back
-                c.gorder.resize(G);
-                size_t iv = 0, ie = nV;
-                for (size_t g = 0; g < G; g++) c.gorder[ex[g] ? ie++ : iv++] = (uint32_t)g;
-                c.pgroups.clear();
-                for (size_t k = 0; k < G; k++) c.pgroups.push_back(groups_in[c.gorder[k]]);
-                gp = &c.pgroups;
-            }
+    if (topk && can_verify && m.res_owner != 0) {
+        const size_t nE = m.pol.route(G, [&](size_t g) { return groups_in[g].resident_owner == m.res_owner ? (long)groups_in[g].resident_slot : -1L; });
+        nV = G - nE;
+        if (nE > 0 && nV > 0) {  // verify groups first, exact groups behind them; collect() puts the columns back
+            c.gorder.resize(G);
+            size_t iv = 0, ie = nV;
+            for (size_t g = 0; g < G; g++) c.gorder[m.pol.routed[g] ? ie++ : iv++] = (uint32_t)g;
+            c.pgroups.clear();
+            for (size_t k = 0; k < G; k++) c.pgroups.push_back(groups_in[c.gorder[k]]);
+            gp = &c.pgroups;
         }
     }
-    const std::vector<LineGroup>& groups = *gp;
-    if (c.kind == LSK_TOPK && nV == 0) m.exact_fallbacks++;
-    if (!m.tick_begin(c, groups, err)) return false;
-    const TickStage& ts = c.ts;
-    LSArgs& a = c.a;
-    a = LSArgs{};
-    bool any_update = false;
-    const bool resident = m.stage_resident(c, groups, &any_update);
-    // the error bound of the approximate scores (false: unusable, the exact kernels take the line search)
-    bool approx = false;
-    uint32_t cls_bits = 0, dup_bits = 0;  // full ranking: low key bits of the gain class / duplicate group
-    size_t nrank = 0;                     // top-k: resident slots whose R ranks this tick refreshes
+    if (topk && nV == 0) m.exact_fallbacks++;
+    if (!m.tick_begin(c, *gp, err)) return false;
+    c.a = LSArgs{};
+    LsTick t{*gp, norms, nV, false, false};
+    t.resident = m.stage_resident(c, t.groups, &t.any_update);
     switch (c.kind) {
-        case LSK_TOPK: {
-            a.xb = (const float4*)m.xb.p;
-            a.gcls = m.gcls.p;
-            a.dcgtab = m.dcgtab.p;
-            a.qstart = m.qstart.p;
-            a.qlen = m.qlen.p;
-            a.run_q0 = m.run_q0.p;
-            a.run_q1 = m.run_q1.p;
-            a.run_pos = m.run_pos.p;
-            a.run_lo = m.run_lo.p;
-            a.run_docs = m.run_docs.p;
-            a.run_order = m.run_order.p;
-            a.wt_start = m.wt_start.p;
-            a.run_wt0 = m.run_wt0.p;
-            a.norms = m.norms.p;
-            a.disc = m.disc.p;
-            a.gfeat = c.td<uint32_t>(ts.o_gfeat);
-            a.gw = c.td<double>(ts.o_gw);
-            a.gcand = c.td<double>(ts.o_gcand);
-            a.gncand = c.td<uint32_t>(ts.o_gncand);
-            a.M = c.M.p;
-            a.flags = c.flags.p;
-            a.dbg_counters = m.dbgc.p;
-            a.dq = (uint32_t)m.dq;
-            a.d = (uint32_t)m.d;
-            a.nruns = (uint32_t)m.nruns;
-            a.G = (uint32_t)G;
-            a.ldm = (uint32_t)ldm;
-            a.depth = (int)depth;
-            a.ncls = (uint32_t)m.ncls;
-            a.redo_count = c.td<unsigned long long>(ts.o_count);
-            a.redo_list = c.redo.p;
-            a.chain_count = c.td<uint32_t>(ts.o_gredo) + G;
-            static const int ls_debug = [] {  // FR_LS_DEBUG (timing ablations of the kernels: 1 = no phase K, 2 = no threshold filter, 16 = count rows)
-                const char* dbg = frdev::pricing_env("FR_LS_DEBUG");
-                return dbg ? atoi(dbg) : 0;
-            }();
-            LS_DEBUG_SET(a, ls_debug);
-            if (LS_DEBUG(a) & 16) FR_HIP(hipMemsetAsync(m.dbgc.p, 0, 4 * sizeof(unsigned long long), c.stream));
-            if (nruns8 * G > 0x7fffffffull) {
-                if (err) *err = "linesearch: grid too large";
-                return false;
-            }
-            c.lds = 2 * dp * sizeof(double);
-            approx = nV > 0 && (LS_DEBUG(a) & ~3) == 0;  // (debug 1/2: timing ablations)
-            a.cls_mask = (1u << m.key_bits) - 1u;  // class bits + duplicate-group bits ride in the keys' low mantissa
-            a.cls_only_mask = (1u << m.key_cls_bits) - 1u;
-            a.gkey = m.gkey.p;
-            if (approx) approx = m.compute_eps2(groups, resident, m.key_bits, /*bare_admission=*/true, /*key_relative=*/true);
-            a.gamma = m.eps_gamma;
-            // (sums from the tiles keep two groups' weights in LDS next to the verify kernel's rank-major copy of the DCG term
-            // table: a wide matrix with many gain classes does not fit)
-            const size_t tab_lds = (m.ncls + 1) * (size_t)(LS_KT + 1) * sizeof(double);
-            if (approx && !resident && 2 * dp * sizeof(double) + tab_lds + 2 * (WAVE + 4) * sizeof(uint4) > 64 * 1024) approx = false;
-            if (!approx && nV > 0) {
-                // the verify launch turned out unusable (compute_eps2 refused the weights, the tables do not fit LDS): the exact
-                // kernel takes ALL staged groups; if some were routed, collect() puts the columns back through gorder
-                m.exact_fallbacks++;
-                nV = 0;
-            }
-            // visiting order of the resident verify kernel (kernels_verify.inc): per group the |w_c - base_f| below which a
-            // candidate ranks like the current model -- where the spread its change of w_f adds, |delta| sigma_x(f), stays under
-            // the spread of the current scores, sqrt(sum_j (w_j sigma_j)^2) -- and the mode bits of columns with crowded extremes;
-            // the R ranks of a restart are redone after its first 1, 2, 4, 8 line searches and then every 16 (FR_RANK_PERIOD in a
-            // pricing build; a stale order only costs admissions: 16 against 8 is +1.4 % in the first 25 ticks of a job and level
-            // afterwards, profiles/r06_rank_policy.txt)
-            a.xslot = nullptr;
-            if (approx && resident && m.xslot.p != nullptr && m.rslot.p != nullptr && m.colstd.size() == m.d) {
-                static const double kappa = [] {
-                    const char* e = frdev::pricing_env("FR_ORDER_KAPPA");
-                    return e ? std::atof(e) : 1.0;
-                }();
-                static const unsigned period = [] {
-                    const char* e = frdev::pricing_env("FR_RANK_PERIOD");
-                    return e ? (unsigned)std::max(1, std::atoi(e)) : 16u;
-                }();
-                double* gthr = c.th<double>(ts.o_gthr);
-                uint32_t* gmode = c.th<uint32_t>(ts.o_gmode);
-                int32_t* rank = c.th<int32_t>(ts.o_rank);
-                for (size_t g = 0; g < nV; g++) {
-                    const LineGroup& lg = groups[g];
-                    double var = 0.0;
-                    for (size_t j = 0; j < m.d; j++) {
-                        const double t = lg.weights[j] * m.colstd[j];
-                        var += t * t;
-                    }
-                    const double sx = m.colstd[lg.feature];
-                    gthr[g] = sx > 0.0 ? kappa * std::sqrt(var) / sx : std::numeric_limits<double>::infinity();
-                    gmode[g] = m.colmode[lg.feature];
-                    const size_t slot = (size_t)lg.resident_slot;
-                    if (slot < m.slot_rank_age.size() && m.slot_rank_mode[slot] == 1) {
-                        if (lg.has_update && m.slot_rank_upd[slot] < 0xFFFF) m.slot_rank_upd[slot]++;
-                        // (ranks age only while the sums change: a restart that accepts nothing keeps its order)
-                        // (a restart's first accepted steps move its model the most: ranks made from the initial sums are stale one line
-                        // search later -- 0.32-0.34 chain runs per visit through ticks 1-7 of a job against 0.16-0.19 behind the first refresh,
-                        // tools/chain_by_tick.py -- so the first refreshes come after 1, 2 and 4 line searches, then every `period`)
-                        if (m.slot_rank_age[slot] == 0xFFFF || (m.slot_rank_age[slot] >= std::min<unsigned>(period, m.slot_rank_gap[slot]) && m.slot_rank_upd[slot] > 0)) {
-                            bool listed = false;  // (a restart with more than 64 candidates has several groups)
-                            for (size_t k = 0; k < nrank; k++) listed = listed || (rank[k] >> 1) == (int32_t)slot;
-                            if (!listed) {
-                                rank[G + nrank] = (int32_t)g;  // (rslot_kernel applies this group's pending update to the sums it ranks)
-                                rank[nrank++] = (int32_t)(slot * 2 + m.res_half[slot]);
-                            }
-                            m.slot_rank_upd[slot] = 0;  // (the ranks are made from the sums WITH this tick's pending update applied)
-                        } else if (m.slot_rank_age[slot] < 0xFFFE) {
-                            m.slot_rank_age[slot]++;
-                        }
-                    }
-                }
-                for (size_t k = 0; k < nrank; k++) {
-                    const size_t slot = (size_t)(rank[k] >> 1);
-                    if (m.slot_rank_age[slot] != 0xFFFF && m.slot_rank_gap[slot] < 0x4000) m.slot_rank_gap[slot] *= 2;  // 1, 2, 4, ... line searches to the next refresh
-                    m.slot_rank_age[slot] = 1;
-                }
-                a.xslot = m.xslot.p;
-                a.rslot = m.rslot.p;
-                a.gthr = c.td<double>(ts.o_gthr);
-                a.gmode = c.td<uint32_t>(ts.o_gmode);
-            }
-            break;
-        }
-        case LSK_RR:
-            if (!resident) return m.ls_exact(c, measure, depth, norms, groups, err);
-            approx = m.compute_eps2(groups, true, 0);
-            break;
-        case LSK_FV:
-            while ((size_t(1) << cls_bits) < m.ncls + 1) cls_bits++;  // (+1: the padding class)
-            // duplicate groups with mixed gain classes (found at upload): the DUP instantiations carry the group id in the keys
-            // behind the class and decide pairs of one group by the reference's tie-break (kernels_fullverify.inc)
-            dup_bits = (m.key_bits > m.key_cls_bits && cls_bits + (m.key_bits - m.key_cls_bits) <= 20) ? m.key_bits - m.key_cls_bits : 0u;
-            approx = m.compute_eps2(groups, resident, cls_bits + dup_bits);
-            break;
+        case LSK_TOPK: return m.submit_topk(c, t, err);
+        case LSK_RR: return m.submit_rr(c, t, err);
+        case LSK_FV: return m.submit_fv(c, t, err);
     }
-    if (c.kind != LSK_TOPK && approx && m.approx_skip > 0) {  // a recent line search redid many pairs
-        m.approx_skip--;
+    return false;
+}
+
+// The end of a submit whose kernels are queued: the column means behind them, and what collect needs of the line search
+// (nverify: the verify kernel took the first nverify staged groups; 0: the exact kernel took them all)
+bool DeviceDataset::Impl::submit_queued(LsCtx& c, const LsTick& t, size_t nverify, std::string* err) {
+    Impl& m = *this;
+    const size_t G = t.groups.size();
+    const bool approx = nverify > 0;
+    FR_HIP(hipGetLastError());
+    if (!m.ls_means(c, err)) return false;
+    if (t.resident) m.flip_resident(t.groups);
+    c.gslot.assign(G, -1);  // (top-k: the restarts the policies at collect steer)
+    if (t.resident)
+        for (size_t k = 0; k < G; k++) c.gslot[k] = t.groups[k].resident_slot;
+    c.agroups.clear();
+    if (c.audit && approx && c.kind != LSK_TOPK) c.agroups.assign(t.groups.begin(), t.groups.end());  // (fr_audit scores their weights from the tiles)
+    c.approx = approx;
+    c.nverify = nverify;
+    c.pending = true;
+    return true;
+}
+
+// Full ranking / reciprocal rank: the exact kernels take a staged line search after all -- the resident sums are kept current first
+bool DeviceDataset::Impl::exact_instead(LsCtx& c, const LsTick& t, std::string* err) {
+    Impl& m = *this;
+    if (t.resident && t.any_update) {
+        if (!m.update_resident(c, 0, t.groups.size(), err)) return false;
+        m.flip_resident(t.groups);
+    }
+    FR_HIP(hipStreamSynchronize(c.stream));  // the tick block is reused by the next call; the exact kernels use the main stream
+    return m.ls_exact(c, c.measure, c.depth, t.norms, t.groups, err);
+}
+
+// NDCG@k (kernels_verify.inc / kernels_linesearch.inc)
+bool DeviceDataset::Impl::submit_topk(LsCtx& c, const LsTick& t, std::string* err) {
+    Impl& m = *this;
+    const std::vector<LineGroup>& groups = t.groups;
+    const size_t G = groups.size(), dp = m.dq * 4, nruns8 = ((m.nruns + 7) / 8) * 8, maxc = c.maxc;
+    const int64_t depth = c.depth;
+    const bool resident = t.resident;
+    const TickStage& ts = c.ts;
+    size_t nV = t.nV;
+    LSArgs& a = c.a;
+    m.topk_args(c, G);
+    static const int ls_debug = [] {  // FR_LS_DEBUG (timing ablations of the kernels: 1 = no phase K, 2 = no threshold filter, 16 = count rows)
+        const char* dbg = frdev::pricing_env("FR_LS_DEBUG");
+        return dbg ? atoi(dbg) : 0;
+    }();
+    LS_DEBUG_SET(a, ls_debug);
+    if (LS_DEBUG(a) & 16) FR_HIP(hipMemsetAsync(m.dbgc.p, 0, 4 * sizeof(unsigned long long), c.stream));
+    if (nruns8 * G > 0x7fffffffull) {
+        if (err) *err = "linesearch: grid too large";
+        return false;
+    }
+    c.lds = 2 * dp * sizeof(double);
+    // the error bound of the approximate scores (false: unusable, the exact kernel takes the line search)
+    bool approx = nV > 0 && (LS_DEBUG(a) & ~3) == 0;  // (debug 1/2: timing ablations)
+    if (approx) approx = m.compute_eps2(groups, resident, m.key_bits, /*bare_admission=*/true, /*key_relative=*/true);
+    a.gamma = m.eps_gamma;
+    // (sums from the tiles keep two groups' weights in LDS next to the verify kernel's rank-major copy of the DCG term
+    // table: a wide matrix with many gain classes does not fit)
+    const size_t tab_lds = (m.ncls + 1) * (size_t)(LS_KT + 1) * sizeof(double);
+    if (approx && !resident && 2 * dp * sizeof(double) + tab_lds + 2 * (WAVE + 4) * sizeof(uint4) > 64 * 1024) approx = false;
+    if (!approx && nV > 0) {
+        // the verify launch turned out unusable (compute_eps2 refused the weights, the tables do not fit LDS): the exact
+        // kernel takes ALL staged groups; if some were routed, collect() puts the columns back through gorder
         m.exact_fallbacks++;
-        approx = false;
+        nV = 0;
+    }
+    // visiting order of the resident verify kernel: per group the threshold (order_threshold) and the mode bits of columns
+    // with crowded extremes, and the resident slots whose R ranks this tick refreshes (LsPolicy::plan_rank_refresh)
+    size_t nrank = 0;
+    a.xslot = nullptr;
+    if (approx && resident && m.xslot.p != nullptr && m.rslot.p != nullptr && m.colstd.size() == m.d) {
+        static const double kappa = [] {
+            const char* e = frdev::pricing_env("FR_ORDER_KAPPA");
+            return e ? std::atof(e) : 1.0;
+        }();
+        static const unsigned period = [] {
+            const char* e = frdev::pricing_env("FR_RANK_PERIOD");
+            return e ? (unsigned)std::max(1, std::atoi(e)) : 16u;
+        }();
+        double* gthr = c.th<double>(ts.o_gthr);
+        uint32_t* gmode = c.th<uint32_t>(ts.o_gmode);
+        for (size_t g = 0; g < nV; g++) {
+            gthr[g] = order_threshold(groups[g].weights, m.colstd, groups[g].feature, kappa);
+            gmode[g] = m.colmode[groups[g].feature];
+        }
+        int32_t* rank = c.th<int32_t>(ts.o_rank);
+        nrank = m.pol.plan_rank_refresh(nV, [&](size_t g) { return (size_t)groups[g].resident_slot; }, [&](size_t g) { return groups[g].has_update; },
+                                        period, m.res_half, rank, rank + G);
+        a.xslot = m.xslot.p;
+        a.rslot = m.rslot.p;
+        a.gthr = c.td<double>(ts.o_gthr);
+        a.gmode = c.td<uint32_t>(ts.o_gmode);
     }
     if (!m.tick_upload(c, approx, err)) return false;
-    if (c.kind != LSK_TOPK && !approx) {  // the exact kernels take the line search: keep the resident sums current first
-        if (resident && any_update) {
-            if (!m.update_resident(c, 0, G, err)) return false;
-            m.flip_resident(groups);
+    if (!approx) {  // the exact kernel on every (run, group) pair, the resident updates first (the verify kernel applies them)
+        if (resident && t.any_update && !m.update_resident(c, 0, G, err)) return false;
+        {
+            ProfScope ps("linesearch_ndcg_kernel", c.stream);
+            dispatch_exact(a, depth, (unsigned)(nruns8 * G), maxc, c.lds, c.stream);
         }
-        FR_HIP(hipStreamSynchronize(c.stream));  // the tick block is reused by the next call; the exact kernels use the main stream
-        return m.ls_exact(c, measure, depth, norms, groups, err);
+        return m.submit_queued(c, t, 0, err);
     }
-    if (c.kind != LSK_TOPK && (!c.M.ensure(m.nq * ldm, err) || !c.redo.ensure(m.nq * G, err))) return false;
-    if (!approx) {  // top-k: the exact kernel on every (run, group) pair, the resident updates first (the verify kernel applies them)
-        if (resident && any_update && !m.update_resident(c, 0, G, err)) return false;
+    // the verify kernel, then the exact kernel on its redo list: a fixed-size grid whose blocks compare themselves with the
+    // count on the device, so the host does not wait here (a longer list is finished when the results are collected)
+    if (nrank > 0) {
+        ProfScope ps("rslot_kernel", c.stream);
+        const uint32_t* wl = m.nwlist ? m.wlist.p : nullptr;  // (a view ranks the walk tiles that hold its documents)
+        const unsigned nw = (unsigned)(m.nwlist ? m.nwlist : m.nwt);
+        rslot_kernel<<<dim3((nw + 3) / 4), 256, 0, c.stream>>>(m.res.p, c.td<int32_t>(ts.o_rank), c.td<int32_t>(ts.o_rank) + G, (uint32_t)nrank,
+                                                              a.rs_par, a.rs_updf, m.xcol.p, m.segtab.p, m.wt_start.p, wl, nw, (uint32_t)m.np, m.rslot.p);
+        FR_HIP(hipGetLastError());
+        if (c.audit) {
+            // the permutation invariant of the tables this launch reads (kernels_order.inc): the R ranks just rewritten and
+            // the x_f ranks of the tick's features; an offending document counts as an audit mismatch
+            if (!m.audit_cnt.ensure(1, err)) return false;
+            FR_HIP(hipMemsetAsync(m.audit_cnt.p, 0, sizeof(unsigned long long), c.stream));
+            const int32_t* rk = c.th<int32_t>(ts.o_rank);
+            for (size_t k = 0; k < nrank; k++)
+                order_audit_kernel<<<dim3((nw + 3) / 4), 256, 0, c.stream>>>(m.rslot.p + (size_t)(rk[k] >> 1) * m.np, m.segtab.p, m.wt_start.p, wl, nw, m.audit_cnt.p);
+            for (size_t g = 0; g < nV; g++)
+                order_audit_kernel<<<dim3((nw + 3) / 4), 256, 0, c.stream>>>(m.xslot.p + (size_t)groups[g].feature * m.np, m.segtab.p, m.wt_start.p, wl, nw, m.audit_cnt.p);
+            unsigned long long bad = 0;
+            FR_HIP(hipMemcpyAsync(&bad, m.audit_cnt.p, sizeof(bad), hipMemcpyDeviceToHost, c.stream));
+            FR_HIP(hipStreamSynchronize(c.stream));
+            m.audit_mismatches += bad;
+        }
+    }
+    // keys kept per list: K + 1, or K + 2 / K + 3 once many pairs failed verification (tied clusters at the cut);
+    // FR_VERIFY_XS=1|2|3 pins it (tests)
+    const char* xs_e = frdev::path_env("FR_VERIFY_XS");
+    const int xs = std::min(xs_e ? std::atoi(xs_e) : m.verify_xs, verify_xs_cap(depth));
+    c.xs_used = xs;
+    c.xs_pinned = xs_e != nullptr;
+    a.eps2 = c.td<double>(ts.o_eps2);
+    a.G = (uint32_t)nV;  // (the verify launch and its redo list cover the first nV staged groups)
+    const bool dupk = resident && m.key_bits > m.key_cls_bits;  // duplicate groups with mixed gains exist: the DUP variants
+    {
+        ProfScope ps("linesearch_verify_kernel", c.stream);
+        if (depth <= 5) launch_verify<5>(a, resident, dupk, xs, (unsigned)nruns8, nV, dp, tab_lds, c.stream);
+        else if (depth <= 10) launch_verify<10>(a, resident, dupk, xs, (unsigned)nruns8, nV, dp, tab_lds, c.stream);
+        else launch_verify<20>(a, resident, dupk, xs, (unsigned)nruns8, nV, dp, tab_lds, c.stream);
+    }
+    FR_HIP(hipGetLastError());
+    // (the first launch on the redo list: the grid this context's policy has arrived at, next_redo_grid)
+    a.slice_count = c.td<uint32_t>(ts.o_count) + 1;
+    const unsigned redo_pin = redo_grid_env();
+    c.redo_grid_used = redo_pin ? redo_pin : c.redo_grid;
+    if (!m.redo_launch(c, 0, c.td<uint32_t>(ts.o_count), c.redo_grid_used, err)) return false;
+    if (nV < G) {  // the routed groups: the exact kernel over all their (run, group) pairs
+        if (t.any_update && !m.update_resident(c, nV, G - nV, err)) return false;  // (the verify kernel applies the pending updates of its own groups only)
+        LSArgs x = a;
+        x.work_list = nullptr;
+        x.work_count = nullptr;
+        x.g_base = (uint32_t)nV;
+        x.G = (uint32_t)(G - nV);
         ProfScope ps("linesearch_ndcg_kernel", c.stream);
-        dispatch_exact(a, depth, (unsigned)(nruns8 * G), maxc, c.lds, c.stream);
-    } else {
-        // the verify kernel, then the exact kernels on its redo list: a fixed-size grid whose blocks compare themselves with the
-        // count on the device, so the host does not wait here (a longer list is finished when the results are collected)
-        switch (c.kind) {
-            case LSK_TOPK: {
-                if (nrank > 0) {
-                    ProfScope ps("rslot_kernel", c.stream);
-                    const uint32_t* wl = m.nwlist ? m.wlist.p : nullptr;  // (a view ranks the walk tiles that hold its documents)
-                    const unsigned nw = (unsigned)(m.nwlist ? m.nwlist : m.nwt);
-                    rslot_kernel<<<dim3((nw + 3) / 4), 256, 0, c.stream>>>(m.res.p, c.td<int32_t>(ts.o_rank), c.td<int32_t>(ts.o_rank) + G, (uint32_t)nrank,
-                                                                          a.rs_par, a.rs_updf, m.xcol.p, m.segtab.p, m.wt_start.p, wl, nw, (uint32_t)m.np, m.rslot.p);
-                    FR_HIP(hipGetLastError());
-                    if (c.audit) {
-                        // the permutation invariant of the tables this launch reads (kernels_order.inc): the R ranks just rewritten and
-                        // the x_f ranks of the tick's features; an offending document counts as an audit mismatch
-                        if (!m.audit_cnt.ensure(1, err)) return false;
-                        FR_HIP(hipMemsetAsync(m.audit_cnt.p, 0, sizeof(unsigned long long), c.stream));
-                        const int32_t* rk = c.th<int32_t>(ts.o_rank);
-                        for (size_t k = 0; k < nrank; k++)
-                            order_audit_kernel<<<dim3((nw + 3) / 4), 256, 0, c.stream>>>(m.rslot.p + (size_t)(rk[k] >> 1) * m.np, m.segtab.p, m.wt_start.p, wl, nw, m.audit_cnt.p);
-                        for (size_t g = 0; g < nV; g++)
-                            order_audit_kernel<<<dim3((nw + 3) / 4), 256, 0, c.stream>>>(m.xslot.p + (size_t)groups[g].feature * m.np, m.segtab.p, m.wt_start.p, wl, nw, m.audit_cnt.p);
-                        unsigned long long bad = 0;
-                        FR_HIP(hipMemcpyAsync(&bad, m.audit_cnt.p, sizeof(bad), hipMemcpyDeviceToHost, c.stream));
-                        FR_HIP(hipStreamSynchronize(c.stream));
-                        m.audit_mismatches += bad;
-                    }
-                }
-                // keys kept per list: K + 1, or K + 2 / K + 3 once many pairs failed verification (tied clusters at the cut);
-                // FR_VERIFY_XS=1|2|3 pins it (tests)
-                const char* xs_e = frdev::path_env("FR_VERIFY_XS");
-                const int xs = std::min(xs_e ? std::atoi(xs_e) : m.verify_xs, depth <= 5 ? 3 : VERIFY_XS_MAX);
-                c.xs_used = xs;
-                c.xs_pinned = xs_e != nullptr;
-                a.eps2 = c.td<double>(ts.o_eps2);
-                a.G = (uint32_t)nV;  // (the verify launch and its redo list cover the first nV staged groups)
-                const bool dupk = resident && m.key_bits > m.key_cls_bits;  // duplicate groups with mixed gains exist: the DUP variants
-                const size_t tab_lds = (m.ncls + 1) * (size_t)(LS_KT + 1) * sizeof(double);
-                {
-                    ProfScope ps("linesearch_verify_kernel", c.stream);
-                    if (depth <= 5) launch_verify<5>(a, resident, dupk, xs, (unsigned)nruns8, nV, dp, tab_lds, c.stream);
-                    else if (depth <= 10) launch_verify<10>(a, resident, dupk, xs, (unsigned)nruns8, nV, dp, tab_lds, c.stream);
-                    else launch_verify<20>(a, resident, dupk, xs, (unsigned)nruns8, nV, dp, tab_lds, c.stream);
-                }
-                FR_HIP(hipGetLastError());
-                // (the grid follows the redo counts this context has seen, 512 .. 8192 pairs: a short list wants a short grid --
-                // every block, empty or not, needs a wave slot, and those are contested while another set's verify grid is
-                // dispatching -- a long one (tie-heavy data) must not cost a second round trip)
-                a.slice_count = c.td<uint32_t>(ts.o_count) + 1;
-                c.redo_grid_used = redo_pin ? redo_pin : c.redo_grid;
-                if (!m.redo_launch(c, 0, c.td<uint32_t>(ts.o_count), c.redo_grid_used, err)) return false;
-                if (nV < G) {  // the routed groups: the exact kernel over all their (run, group) pairs
-                    if (any_update && !m.update_resident(c, nV, G - nV, err)) return false;  // (the verify kernel applies the pending updates of its own groups only)
-                    LSArgs x = a;
-                    x.work_list = nullptr;
-                    x.work_count = nullptr;
-                    x.g_base = (uint32_t)nV;
-                    x.G = (uint32_t)(G - nV);
-                    ProfScope ps("linesearch_ndcg_kernel", c.stream);
-                    dispatch_exact(x, depth, (unsigned)(nruns8 * (G - nV)), maxc, c.lds, c.stream);
-                }
-                break;
-            }
-            case LSK_RR: {
-                RRArgs& ra = c.ra;
-                ra = RRArgs{};
-                ra.xb = (const float4*)m.xb.p;
-                ra.qstart = m.qstart.p;
-                ra.qlen = m.qlen.p;
-                ra.qnpos = m.qnpos.p;
-                ra.gfeat = c.td<uint32_t>(ts.o_gfeat);
-                ra.gw = c.td<double>(ts.o_gw);
-                ra.gcand = c.td<double>(ts.o_gcand);
-                ra.gncand = c.td<uint32_t>(ts.o_gncand);
-                ra.eps2 = c.td<double>(ts.o_eps2);
-                ra.redo_count = c.td<uint32_t>(ts.o_count);
-                ra.redo_list = c.redo.p;
-                ra.res_cur = m.res.p;
-                ra.rs_slot = a.rs_slot;
-                ra.rs_par = a.rs_par;
-                ra.rs_updf = a.rs_updf;
-                ra.xcol = a.xcol;
-                ra.M = c.M.p;
-                ra.flags = c.flags.p;
-                ra.G = (uint32_t)G;
-                ra.ldm = (uint32_t)ldm;
-                ra.dq = (uint32_t)m.dq;
-                ra.d = (uint32_t)m.d;
-                ra.np = (uint32_t)m.np;
-                {
-                    ProfScope ps("rr_verify_kernel", c.stream);
-                    FR_HIP(hipFuncSetAttribute((const void*)rr_verify_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-                    for (size_t ci = m.size_classes.size(); ci-- > 0;) {
-                        const auto& sc = m.size_classes[ci];
-                        ra.qlist = m.qlist.p + sc.offset;
-                        rr_verify_kernel<<<dim3((unsigned)sc.count, (unsigned)G), WAVE, (size_t)sc.npad * sizeof(uint4), c.stream>>>(ra);
-                    }
-                }
-                FR_HIP(hipGetLastError());
-                c.redo_grid_used = redo_pin ? redo_pin : RR_REDO_GRID;
-                if (!m.redo_launch(c, 0, c.td<uint32_t>(ts.o_count), c.redo_grid_used, err)) return false;
-                break;
-            }
-            case LSK_FV: {
-                const size_t slot_rows = ((m.maxlen + 63) / 64 + 1) * 64;
-                if (!c.fv_rows.ensure((size_t)FV_REDO_GRID * slot_rows * 64, err)) return false;
-                FVArgs fa{};
-                fa.xb = (const float4*)m.xb.p;
-                fa.qstart = m.qstart.p;
-                fa.qlen = m.qlen.p;
-                fa.qnpos = m.qnpos.p;
-                fa.gcls = m.gcls.p;
-                fa.gfeat = c.td<uint32_t>(ts.o_gfeat);
-                fa.gw = c.td<double>(ts.o_gw);
-                fa.gcand = c.td<double>(ts.o_gcand);
-                fa.gncand = c.td<uint32_t>(ts.o_gncand);
-                fa.eps2 = c.td<double>(ts.o_eps2);
-                fa.termtab = m.termtab.p;
-                fa.norms = m.norms.p;
-                fa.redo_count = c.td<uint32_t>(ts.o_count);
-                fa.redo_list = c.redo.p;
-                fa.res_cur = m.res.p;
-                fa.rs_slot = a.rs_slot;
-                fa.rs_par = a.rs_par;
-                fa.rs_updf = a.rs_updf;
-                fa.M = c.M.p;
-                fa.flags = c.flags.p;
-                fa.relmask = m.relmask;
-                fa.G = (uint32_t)G;
-                fa.ldm = (uint32_t)ldm;
-                fa.dq = (uint32_t)m.dq;
-                fa.d = (uint32_t)m.d;
-                fa.np = (uint32_t)m.np;
-                fa.tablen = (uint32_t)m.tablen;
-                fa.cls_mask = (1u << (cls_bits + dup_bits)) - 1u;
-                fa.cls_only_mask = (1u << cls_bits) - 1u;
-                fa.cls_bits = cls_bits;
-                fa.key_cls_bits = m.key_cls_bits;
-                fa.dup = dup_bits ? 1u : 0u;
-                fa.gkey = m.gkey.p;
-                fa.padcls = (uint32_t)m.ncls;
-                fa.measure = measure;
-                fa.depth = depth < 0 ? -1 : (depth > 0x7fffffff ? 0x7fffffff : (int)depth);
-                {
-                    // longest queries first (fewest blocks, longest running).  FR_FV_PROFILE=1 times every size class on its own.
-                    static const bool per_class = frdev::pricing_env("FR_FV_PROFILE") != nullptr;
-                    ProfScope ps_all(per_class ? "fullrank_verify_all" : "fullrank_verify_kernel", c.stream);
-                    for (size_t ci = m.fv_classes.size(); ci-- > 0;) {
-                        const auto& sc = m.fv_classes[ci];
-                        static std::vector<std::string> names = [] {
-                            std::vector<std::string> v;
-                            for (int i = 0; i < FV_NCLASSES; i++) v.push_back("fullrank_verify_kernel<" + std::to_string(FV_CLASSES[i].nl) + "x" + std::to_string(FV_CLASSES[i].pl) + ">");
-                            return v;
-                        }();
-                        std::unique_ptr<ProfScope> ps(per_class ? new ProfScope(names[sc.npad].c_str(), c.stream) : nullptr);
-                        fa.qlist = m.fv_qlist.p + sc.offset;
-                        if (!fv_launch_class(fa, (int)sc.npad, (unsigned)sc.count, (unsigned)G, (unsigned)maxc, c.stream)) {
-                            if (err) *err = "fullrank_verify_kernel: no instantiation for this size class";
-                            return false;
-                        }
-                    }
-                }
-                FR_HIP(hipGetLastError());
-                FSArgs& fs = c.fsa;
-                fs = m.scores_args(fa.gfeat, fa.gw, fa.gcand, c.fv_rows.p, c.flags.p, G);
-                fs.qstart = m.qstart.p;
-                fs.qlen = m.qlen.p;
-                fs.G = (uint32_t)G;
-                fs.slot_rows = (uint32_t)slot_rows;
-                RMArgs& rm = c.rma;
-                rm = m.rank_args(c.fv_rows.p, fa.gncand, c.M.p, c.flags.p, G, ldm, measure, depth);
-                rm.G = (uint32_t)G;
-                rm.slot_rows = (uint32_t)slot_rows;
-                c.redo_grid_used = FV_REDO_GRID;
-                if (!m.redo_launch(c, 0, c.td<uint32_t>(ts.o_count), FV_REDO_GRID, err)) return false;
-                break;
+        dispatch_exact(x, depth, (unsigned)(nruns8 * (G - nV)), maxc, c.lds, c.stream);
+    }
+    return m.submit_queued(c, t, nV, err);
+}
+
+// reciprocal rank (kernels_rr.inc): resident sums only
+bool DeviceDataset::Impl::submit_rr(LsCtx& c, const LsTick& t, std::string* err) {
+    Impl& m = *this;
+    const size_t G = t.groups.size();
+    if (!t.resident) return m.ls_exact(c, c.measure, c.depth, t.norms, t.groups, err);
+    bool approx = m.compute_eps2(t.groups, true, 0);
+    if (approx && m.pol.take_skip()) m.exact_fallbacks++, approx = false;  // (a recent line search redid many pairs)
+    if (!m.tick_upload(c, approx, err)) return false;
+    if (!approx) return m.exact_instead(c, t, err);
+    if (!c.M.ensure(m.nq * c.ldm, err) || !c.redo.ensure(m.nq * G, err)) return false;
+    RRArgs& ra = c.ra;
+    ra = m.rr_args(c, G);
+    {
+        ProfScope ps("rr_verify_kernel", c.stream);
+        FR_HIP(hipFuncSetAttribute((const void*)rr_verify_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+        for (size_t ci = m.size_classes.size(); ci-- > 0;) {
+            const auto& sc = m.size_classes[ci];
+            ra.qlist = m.qlist.p + sc.offset;
+            rr_verify_kernel<<<dim3((unsigned)sc.count, (unsigned)G), WAVE, (size_t)sc.npad * sizeof(uint4), c.stream>>>(ra);
+        }
+    }
+    FR_HIP(hipGetLastError());
+    const unsigned redo_pin = redo_grid_env();
+    c.redo_grid_used = redo_pin ? redo_pin : RR_REDO_GRID;
+    if (!m.redo_launch(c, 0, c.td<uint32_t>(c.ts.o_count), c.redo_grid_used, err)) return false;
+    return m.submit_queued(c, t, G, err);
+}
+
+// NDCG of any depth / AP (kernels_fullverify.inc)
+bool DeviceDataset::Impl::submit_fv(LsCtx& c, const LsTick& t, std::string* err) {
+    Impl& m = *this;
+    const size_t G = t.groups.size();
+    uint32_t cls_bits = 0;  // low key bits of the gain class / duplicate group
+    while ((size_t(1) << cls_bits) < m.ncls + 1) cls_bits++;  // (+1: the padding class)
+    // duplicate groups with mixed gain classes (found at upload): the DUP instantiations carry the group id in the keys
+    // behind the class and decide pairs of one group by the reference's tie-break (kernels_fullverify.inc)
+    const uint32_t dup_bits = (m.key_bits > m.key_cls_bits && cls_bits + (m.key_bits - m.key_cls_bits) <= 20) ? m.key_bits - m.key_cls_bits : 0u;
+    bool approx = m.compute_eps2(t.groups, t.resident, cls_bits + dup_bits);
+    if (approx && m.pol.take_skip()) m.exact_fallbacks++, approx = false;  // (a recent line search redid many pairs)
+    if (!m.tick_upload(c, approx, err)) return false;
+    if (!approx) return m.exact_instead(c, t, err);
+    if (!c.M.ensure(m.nq * c.ldm, err) || !c.redo.ensure(m.nq * G, err)) return false;
+    const size_t slot_rows = ((m.maxlen + 63) / 64 + 1) * 64;
+    if (!c.fv_rows.ensure((size_t)FV_REDO_GRID * slot_rows * 64, err)) return false;
+    FVArgs fa = m.fv_args(c, G, cls_bits, dup_bits);
+    {
+        // longest queries first (fewest blocks, longest running).  FR_FV_PROFILE=1 times every size class on its own.
+        static const bool per_class = frdev::pricing_env("FR_FV_PROFILE") != nullptr;
+        ProfScope ps_all(per_class ? "fullrank_verify_all" : "fullrank_verify_kernel", c.stream);
+        for (size_t ci = m.fv_classes.size(); ci-- > 0;) {
+            const auto& sc = m.fv_classes[ci];
+            static std::vector<std::string> names = [] {
+                std::vector<std::string> v;
+                for (int i = 0; i < FV_NCLASSES; i++) v.push_back("fullrank_verify_kernel<" + std::to_string(FV_CLASSES[i].nl) + "x" + std::to_string(FV_CLASSES[i].pl) + ">");
+                return v;
+            }();
+            std::unique_ptr<ProfScope> ps(per_class ? new ProfScope(names[sc.npad].c_str(), c.stream) : nullptr);
+            fa.qlist = m.fv_qlist.p + sc.offset;
+            if (!fv_launch_class(fa, (int)sc.npad, (unsigned)sc.count, (unsigned)G, (unsigned)c.maxc, c.stream)) {
+                if (err) *err = "fullrank_verify_kernel: no instantiation for this size class";
+                return false;
             }
         }
     }
     FR_HIP(hipGetLastError());
-    if (!m.ls_means(c, err)) return false;
-    if (resident) m.flip_resident(groups);
-    c.gslot.assign(G, -1);  // (top-k: the restarts the policies at collect steer)
-    if (resident)
-        for (size_t k = 0; k < G; k++) c.gslot[k] = groups[k].resident_slot;
-    c.agroups.clear();
-    if (c.audit && approx && c.kind != LSK_TOPK) c.agroups.assign(groups.begin(), groups.end());  // (fr_audit scores their weights from the tiles)
-    c.approx = approx;
-    c.nverify = approx ? nV : 0;
-    c.pending = true;
-    return true;
+    // the exact kernels on the redo list: a block owns one slot of score rows
+    FSArgs& fs = c.fsa;
+    fs = m.scores_args(fa.gfeat, fa.gw, fa.gcand, c.fv_rows.p, c.flags.p, G);
+    fs.qstart = m.qstart.p;
+    fs.qlen = m.qlen.p;
+    fs.G = (uint32_t)G;
+    fs.slot_rows = (uint32_t)slot_rows;
+    RMArgs& rm = c.rma;
+    rm = m.rank_args(c.fv_rows.p, fa.gncand, c.M.p, c.flags.p, G, c.ldm, c.measure, c.depth);
+    rm.G = (uint32_t)G;
+    rm.slot_rows = (uint32_t)slot_rows;
+    c.redo_grid_used = FV_REDO_GRID;
+    if (!m.redo_launch(c, 0, c.td<uint32_t>(c.ts.o_count), FV_REDO_GRID, err)) return false;
+    return m.submit_queued(c, t, G, err);
 }
 
 // The exact kernels alone (exact_kernels), then the means.  A context of its own hands the groups, their resident updates applied, to the
@@ -3063,8 +3029,8 @@ bool DeviceDataset::Impl::ls_collect(LsCtx& c, std::vector<double>* means, std::
             case LSK_TOPK:
                 if (!m.topk_policy(c, nredo, nslices, err)) return false;
                 break;
-            default:  // many pairs redone: the exact kernels take the next 16 line searches
-                if ((size_t)nredo * 4 > m.nq * G) m.approx_skip = 16;
+            default:
+                m.pol.observe_skip(nredo, m.nq, G);
                 if (c.audit && !m.fr_audit(c, err)) return false;
                 break;
         }
@@ -3125,14 +3091,11 @@ bool DeviceDataset::Impl::topk_policy(LsCtx& c, uint32_t nredo, uint32_t nslices
     const size_t ldm = c.ldm, G = ldm / 64, nV = c.nverify;
     const std::vector<uint32_t>& by_group = c.gredo_h;
     LSArgs& a = c.a;
-    const unsigned grid_used = c.redo_grid_used;
-    if (nredo > grid_used / 2) c.redo_grid = std::min(8192u, std::max(c.redo_grid, 512u) * 4u);
-    else if (nredo < grid_used / 16 && c.redo_grid > 512u) c.redo_grid /= 2u;
+    c.redo_grid = next_redo_grid(c.redo_grid, c.redo_grid_used, nredo);
     m.approx_redo_entries += nslices;
     for (size_t k = 0; k < nV; k++) m.chain_runs += by_group[G + k];
     m.chain_visits += (unsigned long long)m.n * nV;
     {
-        // the restarts' running means of chain runs per visit, and the switch (see slot_rank_mode)
         static const double t_off = [] {
             const char* e = frdev::pricing_env("FR_RANK_OFF_BELOW");
             return e ? std::atof(e) : RANK_OFF_BELOW;
@@ -3141,28 +3104,7 @@ bool DeviceDataset::Impl::topk_policy(LsCtx& c, uint32_t nredo, uint32_t nslices
             const char* e = frdev::pricing_env("FR_RANK_ON_ABOVE");
             return e ? std::atof(e) : RANK_ON_ABOVE;
         }();
-        std::vector<double> runs(m.slot_rank_mode.size(), 0.0), visits(m.slot_rank_mode.size(), 0.0);
-        for (size_t k = 0; k < nV; k++) {
-            const int slot = c.gslot[k];
-            if (slot < 0 || (size_t)slot >= m.slot_rank_mode.size()) continue;
-            runs[slot] += (double)by_group[G + k];
-            visits[slot] += (double)m.n;
-        }
-        for (size_t slot = 0; slot < runs.size(); slot++) {
-            if (visits[slot] == 0.0) continue;
-            const double r = runs[slot] / visits[slot];
-            uint16_t& n = m.slot_rate_n[slot];
-            if (n < 16) n++;
-            m.slot_rate[slot] += (float)((r - (double)m.slot_rate[slot]) / (double)n);  // (plain mean up to 16, exponential from there)
-            if (n < 16) continue;
-            if (m.slot_rank_mode[slot] == 1 && (double)m.slot_rate[slot] < t_off) {
-                m.slot_rank_mode[slot] = 2;
-                m.rank_slots_off++;
-            } else if (m.slot_rank_mode[slot] == 2 && (double)m.slot_rate[slot] > t_on) {
-                m.slot_rank_mode[slot] = 1;
-                m.rank_slots_on++;
-            }
-        }
+        m.pol.observe_chain(nV, [&](size_t k) { return (long)c.gslot[k]; }, [&](size_t k) { return by_group[G + k]; }, m.n, t_off, t_on);
     }
     if (c.audit) {
         // audit: every value this line search published (verified, or recomputed from the redo list) against the
@@ -3185,33 +3127,9 @@ bool DeviceDataset::Impl::topk_policy(LsCtx& c, uint32_t nredo, uint32_t nslices
         m.audit_values += nel;
         m.audit_mismatches += bad;
     }
-    // tie-heavy data (more than 0.4 % of the pairs redone -- a redone pair costs ~12 verified ones, a longer list ~4 % of
-    // the kernel): first keep more keys per list (up to K + 4), so that tied clusters of one
-    // gain class may straddle the cut (raised only; a new trainer starts one below the last one's; launches already in flight used
-    // the old length).  With the longest lists (or a pinned length), a restart whose line search still left more than
-    // a quarter of its pairs undecided -- its weights make scores tie exactly -- sends its next 4 / 8 / 16 line
-    // searches to the exact kernel (doubled while the verify kernel keeps failing on it, halved when it succeeds).
-    size_t total = 0;
-    for (size_t k = 0; k < nV; k++) total += by_group[k];
-    if (total * 250 > m.nq * nV && c.xs_used < (c.depth <= 5 ? 3 : VERIFY_XS_MAX) && !c.xs_pinned) {
-        if (m.verify_xs <= c.xs_used) m.verify_xs = c.xs_used + 1;
-    } else if (LS_DEBUG(a) == 0) {
-        // (per distinct slot: 1 = seen, 2 = one of its groups left more than a quarter of its pairs undecided)
-        std::vector<char> verdict(m.slot_backoff.size(), 0);
-        for (size_t k = 0; k < nV; k++) {
-            const int slot = c.gslot[k];
-            if (slot < 0 || (size_t)slot >= m.slot_backoff.size()) continue;
-            verdict[slot] |= (char)(((size_t)by_group[k] * 4 > m.nq) ? 3 : 1);
-        }
-        for (size_t slot = 0; slot < verdict.size(); slot++) {
-            if (verdict[slot] & 2) {
-                m.slot_backoff[slot] = (uint8_t)std::min<unsigned>(16u, std::max<unsigned>(4u, m.slot_backoff[slot] * 2u));
-                m.slot_exact_left[slot] = m.slot_backoff[slot];
-            } else if (verdict[slot]) {
-                m.slot_backoff[slot] = (uint8_t)(m.slot_backoff[slot] / 2u);
-            }
-        }
-    }
+    // the list length, or else the restarts' back-off (LsPolicy::observe_redo)
+    m.pol.observe_redo(nV, [&](size_t k) { return (long)c.gslot[k]; }, [&](size_t k) { return by_group[k]; }, m.nq, c.xs_used, verify_xs_cap(c.depth),
+                       c.xs_pinned, LS_DEBUG(a), m.verify_xs);
     return true;
 }
 

@@ -324,3 +324,20 @@ def test_dataset_layout_header_under_address_and_undefined_sanitizers(tmp_path):
     assert build.returncode == 0, build.stdout
     run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert run.returncode == 0 and "dataset_layout ok" in run.stdout, run.stdout
+
+
+def test_linesearch_policy_header_under_address_and_undefined_sanitizers(tmp_path):
+    """tests/linesearch_policy_sanitize.cpp: a program of its own over csrc/linesearch_policy.hpp alone (the refresh schedule,
+    the rank-mode switch, routing and back-off, the list-length ramp, the redo grid, the skip counter: sequences worked out by
+    hand), built with -fsanitize=address,undefined and run directly."""
+    cxx = next((c for c in (os.environ.get("CXX"), "c++", "g++", "clang++") if c and shutil.which(c)), None)
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    here = os.path.dirname(os.path.abspath(__file__))
+    exe = str(tmp_path / "linesearch_policy_sanitize")
+    build = subprocess.run([cxx, "-std=c++17", "-O0", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-pthread",
+                            "-I", os.path.join(here, "..", "fastrank_amd", "csrc"), os.path.join(here, "linesearch_policy_sanitize.cpp"), "-o", exe],
+                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert build.returncode == 0, build.stdout
+    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert run.returncode == 0 and "linesearch_policy ok" in run.stdout, run.stdout

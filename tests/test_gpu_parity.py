@@ -980,36 +980,81 @@ def test_duplicate_pairs_tied_with_a_third_document_go_to_the_exact_kernel():
             assert st["verify_pairs"] > 0 and st["verify_redone"] > 0, st
 
 
+_ROUTING_JOB = []
+
+
+def _routing_job():
+    """8000 documents in 80 queries, d = 10, half of them copies of their predecessor with their own label; 6 restarts x 5
+    iterations of NDCG@10 and the oracle's trajectory of that job (computed once)."""
+    if not _ROUTING_JOB:
+        rng = np.random.default_rng(131)
+        X, y, qid = synth_dataset(131, 8000, 10, 80, max_len=200)
+        X = np.abs(X)
+        for i in np.nonzero(rng.random(len(y)) < 0.5)[0]:
+            if i > 0 and qid[i - 1] == qid[i]:
+                X[i] = X[i - 1]            # same features, its own label
+        req = fr.TrainRequest.coordinate_ascent()
+        req.measure = "ndcg@10"
+        p = req.params
+        p.seed, p.quiet, p.num_restarts, p.num_max_iterations = 5, True, 6, 5
+        exp_s, exp_w, exp_e, err = o.Dataset(X, y, qid).ca_learn("ndcg@10", p.to_dict(), threads=3)
+        assert err == 0
+        _ROUTING_JOB.append((X, y, qid, req, exp_s, exp_w, exp_e))
+    return _ROUTING_JOB[0]
+
+
+def _train_routing_job():
+    """One training of _routing_job on a dataset of its own (the list length a dataset's trainers arrived at outlives them),
+    held to the oracle's trajectory; returns the trainer's statistics."""
+    X, y, qid, req, exp_s, exp_w, exp_e = _routing_job()
+    shard, st = _train_stats(fr.CDataset.from_numpy(X, y, qid), req)
+    for r in shard["restarts"]:
+        assert r["score"] == exp_s[r["restart_id"]] and r["weights"] == exp_w[r["restart_id"]].tolist()
+    assert st["useful_evals"] == int(exp_e.sum())
+    return st
+
+
 def test_tie_heavy_restarts_are_routed_to_the_exact_kernel_one_by_one(monkeypatch):
-    """Per-group routing (DeviceDataset::linesearch_ndcg_submit): documents duplicated with DIFFERENT labels tie exactly under
-    every weight vector, so -- with the duplicate groups switched off -- the verify kernel cannot decide most pairs of any
+    """Per-group routing (csrc/linesearch_policy.hpp, LsPolicy::route / observe_redo): documents duplicated with DIFFERENT
+    labels tie exactly under every weight vector, so -- with the duplicate groups switched off -- the verify kernel cannot decide most pairs of any
     restart.  A restart whose verified line search left more than a quarter of its pairs undecided sends its next 4 / 8 /
     16 line searches straight to the exact kernel; the trainer's other sets keep using the verify kernel.  The trajectory
     is the oracle's either way, some group line searches were routed, and not every line search went to the exact kernel
     wholesale (round 4 sent the next 16 line searches of EVERY group there)."""
     monkeypatch.setenv("FR_NO_DUP_GROUPS", "1")
     monkeypatch.setenv("FR_VERIFY_XS", "1")  # (a pinned list length: routing is the first response, not longer lists)
-    rng = np.random.default_rng(131)
-    X, y, qid = synth_dataset(131, 8000, 10, 80, max_len=200)
-    X = np.abs(X)
-    for i in np.nonzero(rng.random(len(y)) < 0.5)[0]:
-        if i > 0 and qid[i - 1] == qid[i]:
-            X[i] = X[i - 1]            # same features, its own label
-    g, c = fr.CDataset.from_numpy(X, y, qid), o.Dataset(X, y, qid)
-    req = fr.TrainRequest.coordinate_ascent()
-    req.measure = "ndcg@10"
-    p = req.params
-    p.seed, p.quiet, p.num_restarts, p.num_max_iterations = 5, True, 6, 5
-    exp_s, exp_w, exp_e, err = c.ca_learn("ndcg@10", p.to_dict(), threads=3)
-    assert err == 0
-    shard, st = _train_stats(g, req)
-    for r in shard["restarts"]:
-        assert r["score"] == exp_s[r["restart_id"]] and r["weights"] == exp_w[r["restart_id"]].tolist()
-    assert st["useful_evals"] == int(exp_e.sum())
+    st = _train_routing_job()
     print("routing:", {k: st[k] for k in ("groups", "exact_groups", "exact_ticks", "line_searches", "verify_pairs", "verify_redone")})
     if _verify_path_on(resident_needed=True):
         assert 0 < st["exact_groups"] < st["groups"], st
         assert st["verify_pairs"] > 0 and st["verify_redone"] * 4 > st["verify_pairs"], st  # (what triggers the routing)
+
+
+# The statistics of _routing_job measured at commit 30d7be4 (the last one whose line-search driver held the policies itself), on an
+# MI355X: two processes gave the same numbers (profiles/ls_policy_split_counters.txt).  pinned: FR_VERIFY_XS=1 -- routing and
+# back-off fire (exact_groups > 0); ramp: no pin -- the dataset starts at K + 4 keys, its first trainer one below, and the ramp raises
+# the lists to K + 4 again (3 verify launches at K + 3, 15 at K + 4: profiles/ls_policy_split_calls.txt).
+_PARENT_POLICY_COUNTERS = {
+    "pinned": {"chain_runs": 33447, "chain_visits": 200000, "exact_groups": 245, "exact_ticks": 155, "groups": 270, "line_searches": 170, "rank_slots_off": 0, "rank_slots_on": 0, "verify_pairs": 2000, "verify_redo_entries": 1996, "verify_redone": 1996},
+    "ramp": {"chain_runs": 48547, "chain_visits": 248000, "exact_groups": 239, "exact_ticks": 152, "groups": 270, "line_searches": 170, "rank_slots_off": 0, "rank_slots_on": 0, "verify_pairs": 2480, "verify_redo_entries": 2471, "verify_redone": 2471},
+}
+
+
+def test_policy_counters_are_the_parents(monkeypatch):
+    """The policies of csrc/linesearch_policy.hpp are integer state driven by bit-exact kernel results: every counter they feed
+    or depend on equals what the driver counted when it held the policies itself, on the routing test's job -- once with the
+    list length pinned (routing / back-off) and once without (the list-length ramp).  Trajectory: the oracle's."""
+    monkeypatch.setenv("FR_NO_DUP_GROUPS", "1")
+    for mode in ("pinned", "ramp"):
+        if mode == "pinned":
+            monkeypatch.setenv("FR_VERIFY_XS", "1")
+        else:
+            monkeypatch.delenv("FR_VERIFY_XS", raising=False)
+        st = _train_routing_job()
+        got = {k: st[k] for k in _PARENT_POLICY_COUNTERS[mode]}
+        print("policy counters,", mode, got)
+        if _verify_path_on(resident_needed=True):
+            assert got == _PARENT_POLICY_COUNTERS[mode], mode
 
 
 def test_redo_unit_is_a_slice_of_sixteen_candidates():
