@@ -77,6 +77,8 @@ def _load():
         "fr_ca_step": (vp, [vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
         "fr_ca_state": (vp, [vp]),
         "fr_ca_free": (None, [vp]),
+        "fr_ca_capture": (vp, [vp, C.c_int]),
+        "fr_ca_capture_take": (vp, [vp, C.c_char_p, vp, sz]),
         "fr_last_train_stats": (vp, []),
         "fr_predict_scores_dense": (vp, [vp, vp, vp, sz]),
         "fr_debug_lambda_gradients": (vp, [vp, vp, vp, C.c_char_p, C.c_double, vp, vp, sz]),

@@ -1337,6 +1337,7 @@ struct FrTrainer {
     std::unique_ptr<fr::CATrainer> t;
     std::chrono::steady_clock::time_point t0;
     std::shared_ptr<fr::DataCore> core;  // (its api_mu serialises the calls on this handle with other jobs on the dataset)
+    std::vector<unsigned char> capture_blob;  // fr_ca_capture_take: the arrays of the events last described, until they are fetched
 };
 
 void* fr_ca_begin(const void* train_request_json, const CDataset* dataset, uint32_t restart_begin,
@@ -1420,6 +1421,116 @@ const void* fr_ca_state(void* trainer) {
 }
 
 void fr_ca_free(void* trainer) { delete (FrTrainer*)trainer; }
+
+// Tick capture (include/fastrank.h; DeviceDataset::capture_enable): a test hook, no product path calls it.
+const void* fr_ca_capture(void* trainer, int on) {
+    return status_call([&]() {
+        if (!trainer) fr::fail_str("trainer pointer is null!");
+        FrTrainer* h = (FrTrainer*)trainer;
+        std::lock_guard<std::mutex> lk(h->core->api_mu);
+        h->t->capture(on != 0);
+        if (!on) h->capture_blob.clear();
+    });
+}
+
+// table == NULL: moves the log out of the device dataset and describes it -- JSON {"events": [...], "bytes": n}, every array
+// of an event as {"off": byte offset into the blob, "n": elements}; table == "blob": the n bytes, after which they are
+// forgotten (the name / out-buffer protocol of fr_debug_device_form).
+const void* fr_ca_capture_take(void* trainer, const void* table, void* out, size_t out_bytes) {
+    return json_call([&]() {
+        if (!trainer) fr::fail_str("trainer pointer is null!");
+        FrTrainer* h = (FrTrainer*)trainer;
+        std::lock_guard<std::mutex> lk(h->core->api_mu);
+        Value o = Value::object();
+        if (table) {
+            const std::string name = accept_str("table", table);
+            if (name != "blob") fr::fail_str("fr_ca_capture_take: no table named " + name);
+            if (out_bytes != h->capture_blob.size() || (!out && out_bytes))
+                fr::fail_str("fr_ca_capture_take: the blob holds " + std::to_string(h->capture_blob.size()) + " bytes, the buffer " + std::to_string(out_bytes));
+            if (out_bytes) std::memcpy(out, h->capture_blob.data(), out_bytes);
+            o.set("bytes", Value::uint(out_bytes));
+            h->capture_blob.clear();
+            h->capture_blob.shrink_to_fit();
+            return frjson::dump(o);
+        }
+        std::vector<frdev::LsCapture> log;
+        h->t->take_capture(&log);
+        std::vector<unsigned char>& blob = h->capture_blob;
+        blob.clear();
+        auto put = [&blob](const auto& v) {
+            using T = typename std::remove_reference_t<decltype(v)>::value_type;
+            blob.resize((blob.size() + 7) & ~size_t(7));
+            Value r = Value::object();
+            r.set("off", Value::uint(blob.size()));
+            r.set("n", Value::uint(v.size()));
+            const size_t at = blob.size();
+            blob.resize(at + v.size() * sizeof(T));
+            if (!v.empty()) std::memcpy(blob.data() + at, v.data(), v.size() * sizeof(T));
+            return r;
+        };
+        Value events = Value::array();
+        for (const frdev::LsCapture& e : log) {
+            Value ev = Value::object();
+            if (e.store) {
+                ev.set("type", Value::string("store"));
+                ev.set("slot", Value::sint(e.slot));
+                ev.set("v", put(e.v));
+                events.push(std::move(ev));
+                continue;
+            }
+            static const char* const kinds[] = {"topk", "rr", "fullrank"};
+            ev.set("type", Value::string("tick"));
+            ev.set("ctx", Value::sint(e.ctx));
+            ev.set("kind", Value::string(kinds[e.kind]));
+            ev.set("measure", Value::sint(e.measure));
+            ev.set("depth", Value::sint(e.depth));
+            Value groups = Value::array();
+            for (const frdev::LineGroup& lg : e.groups) {
+                Value g = Value::object();
+                g.set("feature", Value::uint(lg.feature));
+                g.set("weights", put(lg.weights));
+                g.set("candidates", put(lg.candidates));
+                g.set("resident_slot", Value::sint(lg.resident_slot));
+                g.set("resident_owner", Value::uint(lg.resident_owner));
+                g.set("has_update", Value::boolean(lg.has_update));
+                g.set("upd_feature", Value::uint(lg.upd_feature));
+                // (the doubles travel as bytes: resident_norm, resident_base_f, resident_err, upd_norm, upd_base_f, upd_cand)
+                g.set("params", put(std::vector<double>{lg.resident_norm, lg.resident_base_f, lg.resident_err, lg.upd_norm, lg.upd_base_f, lg.upd_cand}));
+                groups.push(std::move(g));
+            }
+            ev.set("groups", std::move(groups));
+            ev.set("gorder", put(e.gorder));
+            ev.set("nverify", Value::uint(e.nverify));
+            ev.set("approx", Value::boolean(e.approx));
+            ev.set("resident", Value::boolean(e.resident));
+            ev.set("ready", Value::boolean(e.ready));
+            Value inst = Value::object();
+            if (e.kind == 0) {
+                inst.set("k", Value::sint(e.kbucket));
+                inst.set("xs_used", Value::sint(e.xs_used));
+                inst.set("xs_pinned", Value::boolean(e.xs_pinned));
+            } else {
+                inst.set("classes", put(e.classes));
+            }
+            inst.set("dup", Value::boolean(e.dup));
+            ev.set("inst", std::move(inst));
+            ev.set("redo", put(e.redo));
+            ev.set("redo_groups", Value::uint(e.redo_groups));
+            ev.set("means", put(e.means));
+            ev.set("nq", Value::uint(e.nq));
+            ev.set("ldm", Value::uint(e.ldm));
+            ev.set("np", Value::uint(e.np));
+            ev.set("has_matrix", Value::boolean(e.has_matrix));
+            ev.set("matrix", put(e.matrix));
+            ev.set("res_slots", put(e.res_slots));
+            ev.set("res", put(e.res));
+            events.push(std::move(ev));
+        }
+        o.set("events", std::move(events));
+        o.set("bytes", Value::uint(blob.size()));
+        return frjson::dump(o);
+    });
+}
 
 const CResult* fr_select_model(const void* restarts_json, int output_ensemble) {
     return c_call<CModel>([&]() {

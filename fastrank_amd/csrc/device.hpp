@@ -94,6 +94,33 @@ struct LineGroup {
     double upd_norm = 1.0, upd_base_f = 0.0, upd_cand = 0.0;
 };
 
+// One event of the tick capture (a test hook, DeviceDataset::capture_enable): a store of exact resident sums,
+// or one collected line search with what it published.
+struct LsCapture {
+    bool store = false;
+    // store: slot <- the exact ordered sums of the un-normalised weight vector v
+    int slot = -1;
+    std::vector<double> v;
+    // tick
+    int ctx = 0, kind = 0, measure = 0;  // kind: 0 = top-k, 1 = reciprocal rank, 2 = full ranking
+    int64_t depth = 0;
+    std::vector<LineGroup> groups;  // the caller's order
+    std::vector<uint32_t> gorder;   // staged group k = the caller's gorder[k]
+    size_t nverify = 0;             // the verify kernel took the first nverify staged groups
+    bool approx = false, resident = false, ready = false;
+    int kbucket = 0, xs_used = 0;   // top-k: linesearch_verify_kernel<kbucket, ., ., xs_used, dup>
+    bool xs_pinned = false, dup = false;
+    std::vector<uint32_t> classes;  // full ranking / reciprocal rank: (keys per lane, lanes per candidate, queries) of every size class launched
+    std::vector<uint32_t> redo;     // the redo list's entries: (query * redo_groups + staged group) [* 16 + slice mask, top-k]
+    uint32_t redo_groups = 0;
+    std::vector<double> means;      // as published (the caller's order)
+    bool has_matrix = false;
+    size_t nq = 0, ldm = 0, np = 0;
+    std::vector<double> matrix;     // [nq][ldm], staged order, after every redo pass and any audit
+    std::vector<int> res_slots;     // resident slots of the groups, ascending ...
+    std::vector<double> res;        // ... and each one's current half ([np] per slot) after the launch's flip
+};
+
 struct KernelStat {
     std::string name;
     uint64_t launches = 0;
@@ -182,7 +209,15 @@ class DeviceDataset {
     uint64_t resident_reserve(size_t slots, std::string* err);
     // slot <- the scores of score slot b of the last score_linear() call (exact ordered sums); false with an
     // empty *err when the ticket is stale
-    bool resident_store_from_scores(uint64_t owner, size_t slot, size_t b, std::string* err);
+    // (v: the d weights whose sums these are -- read by the tick capture only)
+    bool resident_store_from_scores(uint64_t owner, size_t slot, size_t b, std::string* err, const double* v = nullptr);
+    // Tick capture, a test hook: while on, every resident_store_from_scores and every collected line search
+    // appends an event to a host-side log (copies and synchronisations of its own; nothing it records feeds back).  Off, the
+    // default, costs an untaken branch at each of those points.  capture_take moves the log out.
+    void capture_enable(bool on);
+    // ... a store event for sums that were stored before the capture was switched on (v: the d weights; nothing is copied)
+    void capture_note_store(size_t slot, const double* v);
+    void capture_take(std::vector<LsCapture>* out);
     const std::vector<double>& column_absmax() const;  // per-column max |x|
     // line searches evaluated by the exact kernels alone (NDCG@k: every group of the line search was routed there; the other
     // measures: a recent line search had > 25 % of its pairs redone)

@@ -154,6 +154,10 @@ struct DeviceDataset::Impl : DatasetDesc {
         std::vector<LineGroup> pgroups;
         std::vector<double> exact_means;
         LsCounts counts;  // this line search's verify pairs / redone pairs
+        // what the tick capture reports of the pending line search (cgroups: the caller's groups, copied only while it is on)
+        bool resident = false, dup = false;
+        int kbucket = 0;  // K of the linesearch_verify_kernel<K, ...> launched (0: no verify launch)
+        std::vector<LineGroup> cgroups;
     };
     LsCtx ls[LS_CONTEXTS + 1];
     hipEvent_t res_ready = nullptr;  // recorded on the main stream after a resident-sum store; the contexts wait on it
@@ -178,6 +182,12 @@ struct DeviceDataset::Impl : DatasetDesc {
     bool ls_exact(LsCtx& c, int measure, int64_t depth, const double* norms, const std::vector<LineGroup>& groups, std::string* err);
     bool exact_kernels(const std::vector<LineGroup>& groups, int measure, int64_t depth, size_t maxc, double* M, int* flags, std::string* err);
     bool fr_audit(LsCtx& c, std::string* err);
+    // tick capture (DeviceDataset::capture_enable).  cap_outer: the context whose line search the lock-step context is
+    // evaluating on its behalf (ls_exact): the event is recorded there, with the matrix, under the outer context's name
+    bool cap_on = false;
+    std::vector<LsCapture> cap_log;
+    const LsCtx* cap_outer = nullptr;
+    bool capture_tick(LsCtx& c, const std::vector<double>& means, uint32_t nredo, std::string* err);
     bool ls_means(LsCtx& c, std::string* err);
     bool tick_begin(LsCtx& c, const std::vector<LineGroup>& groups, std::string* err);
     bool tick_upload(LsCtx& c, bool with_eps2, std::string* err);
@@ -2219,7 +2229,7 @@ uint64_t DeviceDataset::resident_reserve(size_t slots, std::string* err) {
     return m.res_owner;
 }
 
-bool DeviceDataset::resident_store_from_scores(uint64_t owner, size_t slot, size_t b, std::string* err) {
+bool DeviceDataset::resident_store_from_scores(uint64_t owner, size_t slot, size_t b, std::string* err, const double* v) {
     Impl& m = *impl_;
     std::lock_guard<std::mutex> lk(m.mu);
     if (err) err->clear();
@@ -2234,7 +2244,37 @@ bool DeviceDataset::resident_store_from_scores(uint64_t owner, size_t slot, size
     FR_HIP(hipEventRecord(m.res_ready, m.stream));
     m.res_ready_set = true;
     m.pol.new_sums(slot);
+    if (m.cap_on) {
+        LsCapture e;
+        e.store = true;
+        e.slot = (int)slot;
+        if (v) e.v.assign(v, v + m.d);
+        m.cap_log.push_back(std::move(e));
+    }
     return true;
+}
+
+void DeviceDataset::capture_enable(bool on) {
+    std::lock_guard<std::mutex> lk(impl_->mu);
+    impl_->cap_on = on;
+    if (!on) impl_->cap_log.clear();
+    for (Impl::LsCtx& c : impl_->ls) std::vector<LineGroup>().swap(c.cgroups);  // (a line search in flight across the switch is not logged)
+}
+
+void DeviceDataset::capture_note_store(size_t slot, const double* v) {
+    std::lock_guard<std::mutex> lk(impl_->mu);
+    if (!impl_->cap_on) return;
+    LsCapture e;
+    e.store = true;
+    e.slot = (int)slot;
+    e.v.assign(v, v + impl_->d);
+    impl_->cap_log.push_back(std::move(e));
+}
+
+void DeviceDataset::capture_take(std::vector<LsCapture>* out) {
+    std::lock_guard<std::mutex> lk(impl_->mu);
+    out->clear();
+    out->swap(impl_->cap_log);
 }
 
 const std::vector<double>& DeviceDataset::column_absmax() const { return impl_->colmax; }
@@ -2601,9 +2641,12 @@ bool DeviceDataset::Impl::ls_submit(LsCtx& c, int path, int measure, int64_t dep
     c.depth = depth;
     c.measure = measure;
     c.approx = c.ready = false;
+    c.resident = c.dup = false;
+    c.kbucket = 0;
     c.nverify = 0;
     c.gorder.clear();
     c.counts = LsCounts{};
+    if (m.cap_on) c.cgroups = groups_in;
     if (G == 0) {
         c.pending = true;
         return true;
@@ -2657,6 +2700,7 @@ bool DeviceDataset::Impl::ls_submit(LsCtx& c, int path, int measure, int64_t dep
     c.a = LSArgs{};
     LsTick t{*gp, norms, nV, false, false};
     t.resident = m.stage_resident(c, t.groups, &t.any_update);
+    c.resident = t.resident;
     switch (c.kind) {
         case LSK_TOPK: return m.submit_topk(c, t, err);
         case LSK_RR: return m.submit_rr(c, t, err);
@@ -2802,11 +2846,12 @@ bool DeviceDataset::Impl::submit_topk(LsCtx& c, const LsTick& t, std::string* er
     a.eps2 = c.td<double>(ts.o_eps2);
     a.G = (uint32_t)nV;  // (the verify launch and its redo list cover the first nV staged groups)
     const bool dupk = resident && m.key_bits > m.key_cls_bits;  // duplicate groups with mixed gains exist: the DUP variants
+    c.dup = dupk;
     {
         ProfScope ps("linesearch_verify_kernel", c.stream);
-        if (depth <= 5) launch_verify<5>(a, resident, dupk, xs, (unsigned)nruns8, nV, dp, tab_lds, c.stream);
-        else if (depth <= 10) launch_verify<10>(a, resident, dupk, xs, (unsigned)nruns8, nV, dp, tab_lds, c.stream);
-        else launch_verify<20>(a, resident, dupk, xs, (unsigned)nruns8, nV, dp, tab_lds, c.stream);
+        if (depth <= 5) launch_verify<5>(a, resident, dupk, xs, (unsigned)nruns8, nV, dp, tab_lds, c.stream), c.kbucket = 5;
+        else if (depth <= 10) launch_verify<10>(a, resident, dupk, xs, (unsigned)nruns8, nV, dp, tab_lds, c.stream), c.kbucket = 10;
+        else launch_verify<20>(a, resident, dupk, xs, (unsigned)nruns8, nV, dp, tab_lds, c.stream), c.kbucket = 20;
     }
     FR_HIP(hipGetLastError());
     // (the first launch on the redo list: the grid this context's policy has arrived at, next_redo_grid)
@@ -2872,6 +2917,7 @@ bool DeviceDataset::Impl::submit_fv(LsCtx& c, const LsTick& t, std::string* err)
     const size_t slot_rows = ((m.maxlen + 63) / 64 + 1) * 64;
     if (!c.fv_rows.ensure((size_t)FV_REDO_GRID * slot_rows * 64, err)) return false;
     FVArgs fa = m.fv_args(c, G, cls_bits, dup_bits);
+    c.dup = dup_bits != 0;
     {
         // longest queries first (fewest blocks, longest running).  FR_FV_PROFILE=1 times every size class on its own.
         static const bool per_class = frdev::pricing_env("FR_FV_PROFILE") != nullptr;
@@ -2918,7 +2964,10 @@ bool DeviceDataset::Impl::ls_exact(LsCtx& c, int measure, int64_t depth, const d
         c.pgroups.assign(groups.begin(), groups.end());
         for (LineGroup& lg : c.pgroups) lg.has_update = false;
         LsCtx& l = m.ls[LS_CONTEXTS];
-        if (!m.ls_submit(l, LS_FULLRANK, measure, depth, norms, c.pgroups, err) || !m.ls_collect(l, &c.exact_means, err)) return false;
+        m.cap_outer = &c;
+        const bool done = m.ls_submit(l, LS_FULLRANK, measure, depth, norms, c.pgroups, err) && m.ls_collect(l, &c.exact_means, err);
+        m.cap_outer = nullptr;
+        if (!done) return false;
         c.counts = l.counts;
         c.ready = c.pending = true;
         return true;
@@ -3005,6 +3054,7 @@ bool DeviceDataset::Impl::ls_collect(LsCtx& c, std::vector<double>* means, std::
     c.pending = false;
     if (c.ready) {
         *means = c.exact_means;
+        if (m.cap_on) return m.capture_tick(c, *means, 0, err);
         return true;
     }
     const size_t ldm = c.ldm, G = ldm / 64;
@@ -3049,6 +3099,73 @@ bool DeviceDataset::Impl::ls_collect(LsCtx& c, std::vector<double>* means, std::
         fprintf(stderr, "[FR_LS_DEBUG] docs=%llu rows=%llu (%.3f of docs) batches=%llu insertion_rows=%llu\n", cnt[3], cnt[0],
                 (double)cnt[0] / (double)cnt[3], cnt[1], cnt[2]);
     }
+    if (m.cap_on) return m.capture_tick(c, *means, c.approx ? nredo : 0, err);
+    return true;
+}
+
+// Tick capture: the collected line search of context c as one event of the log -- its groups and how they were staged, the
+// path it took, the instantiation, the redo list, and copies of what it published and of the resident sums it left.  Reads
+// only; the copies and the synchronisation are its own.  A line search the lock-step context evaluated for another context
+// (ls_exact) was recorded there, matrix included, under that context's index with its groups and their pending updates.
+bool DeviceDataset::Impl::capture_tick(LsCtx& c, const std::vector<double>& means, uint32_t nredo, std::string* err) {
+    Impl& m = *this;
+    const bool lockstep = &c == &m.ls[LS_CONTEXTS];
+    if (c.ready && !lockstep) return true;
+    const LsCtx& who = (lockstep && m.cap_outer) ? *m.cap_outer : c;
+    if (who.cgroups.size() * 64 != c.ldm) return true;  // (submitted before the capture was switched on: its groups were not kept)
+    LsCapture e;
+    e.ctx = (int)(&who - m.ls);
+    e.kind = (int)c.kind;
+    e.measure = c.measure;
+    e.depth = c.depth;
+    e.groups = who.cgroups;
+    const size_t G = e.groups.size();
+    e.gorder = c.gorder;
+    if (e.gorder.empty())
+        for (size_t g = 0; g < G; g++) e.gorder.push_back((uint32_t)g);
+    e.nverify = c.approx ? c.nverify : 0;
+    e.approx = c.approx;
+    e.resident = who.resident;
+    e.ready = c.ready;
+    hipStream_t st = c.ready ? m.stream : c.stream;
+    if (c.kind == LSK_TOPK) {
+        e.kbucket = c.kbucket;  // (all zero when the exact kernel took the line search whole: no verify launch)
+        e.xs_used = c.kbucket ? c.xs_used : 0;
+        e.xs_pinned = c.kbucket ? c.xs_pinned : false;
+    } else if (c.approx) {
+        if (c.kind == LSK_FV)
+            for (const auto& sc : m.fv_classes) e.classes.insert(e.classes.end(), {FV_CLASSES[sc.npad].nl, FV_CLASSES[sc.npad].pl, sc.count});
+        else
+            for (const auto& sc : m.size_classes) e.classes.insert(e.classes.end(), {sc.npad, 1u, sc.count});
+    }
+    e.dup = c.dup;
+    e.redo_groups = (uint32_t)(c.kind == LSK_TOPK ? c.nverify : G);
+    if (c.approx && nredo > 0) {
+        e.redo.resize(nredo);
+        FR_HIP(hipMemcpyAsync(e.redo.data(), c.redo.p, nredo * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    }
+    e.means = means;
+    e.nq = m.nq;
+    e.ldm = G * 64;
+    e.np = m.np;
+    const double* M = c.ready ? m.M.p : c.M.p;
+    e.has_matrix = M != nullptr;
+    if (e.has_matrix) {
+        e.matrix.resize(e.nq * e.ldm);
+        FR_HIP(hipMemcpyAsync(e.matrix.data(), M, e.matrix.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    if (e.resident) {
+        for (const LineGroup& lg : e.groups) e.res_slots.push_back(lg.resident_slot);
+        std::sort(e.res_slots.begin(), e.res_slots.end());
+        e.res_slots.erase(std::unique(e.res_slots.begin(), e.res_slots.end()), e.res_slots.end());
+        e.res.resize(e.res_slots.size() * m.np);
+        for (size_t i = 0; i < e.res_slots.size(); i++) {
+            const size_t slot = (size_t)e.res_slots[i];
+            FR_HIP(hipMemcpyAsync(e.res.data() + i * m.np, m.res.p + (slot * 2 + m.res_half[slot]) * m.np, m.np * sizeof(double), hipMemcpyDeviceToHost, st));
+        }
+    }
+    FR_HIP(hipStreamSynchronize(st));
+    m.cap_log.push_back(std::move(e));
     return true;
 }
 

@@ -1359,6 +1359,17 @@ class CATrainer {
     }
 
     TrainStats& stats() { return stats_; }
+    // tick capture (test hook): the device dataset this trainer runs on logs its resident stores and line searches
+    // (switched on, the log opens with a store event for every live restart whose resident sums are still the exact ones
+    // last stored -- all of them right after the constructor -- so that a replay has where to start)
+    void capture(bool on) {
+        frdev::DeviceDataset& dev = view_->device(slot_, device_);
+        dev.capture_enable(on);
+        if (on && resident_)
+            for (const Restart& r : rs_)
+                if (!r.done && r.slot >= 0 && r.res_updates == 0 && !r.pend) dev.capture_note_store((size_t)r.slot, r.best_w.data());
+    }
+    void take_capture(std::vector<frdev::LsCapture>* out) { view_->device(slot_, device_).capture_take(out); }
     const CAParams& params() const { return p_; }
 
   private:
@@ -1407,7 +1418,7 @@ class CATrainer {
             if (!dev.score_linear(bn, w.data(), &_err)) fail_str(_err);
             for (size_t k = 0; k < bn; k++) {
                 Restart& r = rs_[which[b0 + k]];
-                if (!dev.resident_store_from_scores(res_owner_, (size_t)r.slot, k, &_err)) {
+                if (!dev.resident_store_from_scores(res_owner_, (size_t)r.slot, k, &_err, w.data() + k * d_)) {
                     if (!_err.empty()) fail_str(_err);
                     resident_ = false;  // another trainer took the buffers over: form the sums from the tiles from now on
                     return;

@@ -289,6 +289,54 @@ class CoordinateAscentRun:
     def state(self) -> Dict:
         return _json_reply(_load().fr_ca_state(self.pointer))
 
+    def capture(self, on: bool = True) -> None:
+        """Tick capture (fr_ca_capture, a test hook): while on, every store of exact resident sums and every collected
+        line search of this trainer's device dataset is logged; take_capture() hands the log over."""
+        _status(_load().fr_ca_capture(self.pointer, 1 if on else 0))
+
+    def take_capture(self) -> List[Dict]:
+        """The events logged since the last call, oldest first (fr_ca_capture_take), arrays as numpy:
+        {"type": "store", "slot", "v"} and {"type": "tick", "ctx", "kind", "measure", "depth", "groups" (every LineGroup
+        field, the caller's order), "gorder", "nverify", "approx", "resident", "ready", "inst", "redo", "redo_groups",
+        "means", "matrix" ([nq, ldm] in staged order, or None), "resident_sums" ({slot: [np]})}."""
+        L = _load()
+        head = _json_reply(L.fr_ca_capture_take(self.pointer, None, None, 0))
+        blob = np.zeros(int(head["bytes"]), dtype=np.uint8)
+        _json_reply(L.fr_ca_capture_take(self.pointer, b"blob", blob.ctypes.data if blob.size else None, blob.nbytes))
+
+        def arr(ref, dtype):
+            dt = np.dtype(dtype)
+            return np.frombuffer(blob, dtype=dt, count=int(ref["n"]), offset=int(ref["off"])).copy()
+
+        out = []
+        for ev in head["events"]:
+            if ev["type"] == "store":
+                out.append({"type": "store", "slot": int(ev["slot"]), "v": arr(ev["v"], np.float64)})
+                continue
+            groups = []
+            for g in ev["groups"]:
+                par = arr(g["params"], np.float64)
+                groups.append({"feature": int(g["feature"]), "weights": arr(g["weights"], np.float64),
+                               "candidates": arr(g["candidates"], np.float64), "resident_slot": int(g["resident_slot"]),
+                               "resident_owner": int(g["resident_owner"]), "has_update": bool(g["has_update"]),
+                               "upd_feature": int(g["upd_feature"]), "resident_norm": float(par[0]),
+                               "resident_base_f": float(par[1]), "resident_err": float(par[2]), "upd_norm": float(par[3]),
+                               "upd_base_f": float(par[4]), "upd_cand": float(par[5])})
+            inst = dict(ev["inst"])
+            if "classes" in inst:
+                inst["classes"] = arr(inst["classes"], np.uint32).reshape(-1, 3).tolist()
+            nq, ldm, npos = int(ev["nq"]), int(ev["ldm"]), int(ev["np"])
+            slots = arr(ev["res_slots"], np.int32)
+            res = arr(ev["res"], np.float64).reshape(len(slots), npos) if len(slots) else np.zeros((0, npos))
+            out.append({"type": "tick", "ctx": int(ev["ctx"]), "kind": ev["kind"], "measure": int(ev["measure"]),
+                        "depth": int(ev["depth"]), "groups": groups, "gorder": arr(ev["gorder"], np.uint32),
+                        "nverify": int(ev["nverify"]), "approx": bool(ev["approx"]), "resident": bool(ev["resident"]),
+                        "ready": bool(ev["ready"]), "inst": inst, "redo": arr(ev["redo"], np.uint32),
+                        "redo_groups": int(ev["redo_groups"]), "means": arr(ev["means"], np.float64),
+                        "matrix": arr(ev["matrix"], np.float64).reshape(nq, ldm) if ev["has_matrix"] else None,
+                        "resident_sums": {int(s): res[i] for i, s in enumerate(slots)}})
+        return out
+
     def close(self):
         if self.pointer:
             _load().fr_ca_free(self.pointer)

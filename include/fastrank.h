@@ -141,6 +141,15 @@ const void *fr_ca_step(void *trainer, uint64_t max_ticks, uint64_t *ticks_done, 
 /* JSON {"restarts":[...],"stats":{...},"finished":bool} (free_str). */
 const void *fr_ca_state(void *trainer);
 void fr_ca_free(void *trainer);
+/* Tick capture, a test hook: while on (off is the default and costs an untaken branch), the device
+ * dataset of this trainer appends an event to a host-side log at every store of exact resident sums and at every collected
+ * line search -- its groups, staging order, path, kernel instantiation, redo list, published means and per-query matrix, and
+ * the resident sums it left.  It reads only: no counter, policy decision or published value changes.  NULL on success. */
+const void *fr_ca_capture(void *trainer, int on);
+/* Hands the log over and clears it, with the name / out-buffer protocol of fr_debug_device_form.  table == NULL: JSON
+ * {"events": [...], "bytes": n}, every array of an event given as {"off": byte offset, "n": elements} into one blob of n
+ * bytes; table == "blob": the blob is copied to `out` (out_bytes must be n) and forgotten. */
+const void *fr_ca_capture_take(void *trainer, const void *table, void *out, size_t out_bytes);
 
 /* Selection rule of src/coordinate_ascent.rs:232-252 over gathered restarts.
  * restarts_json: JSON list of {"restart_id","score","weights"}; returns a CModel. */

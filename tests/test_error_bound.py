@@ -58,12 +58,14 @@ def _bound(which, a, b, c=0.0):
     return float(clib._load().fr_debug_resident_bound(int(which), float(a), float(b), float(c)))
 
 
-def _replay(seed, n, d, updates, normalize, col_gen, weight_gen, cand_gen, refresh=None):
+def _replay(seed, n, d, updates, normalize, col_gen, weight_gen, cand_gen, refresh=None, trace=None):
     """Replays what the trainer and the verify kernel do to ONE restart's resident sums over a chain of accepted
     candidates -- best_w -> base = best_w / sum|best_w| (each entry divided separately, coordinate_ascent.rs:72-82)
     -> best_w' = base with [f] = cand, R' = fma(x_f, cand, fma(-x_f, base_f, R * fl(1/norm))) -- and holds the host's
     bound E (the product's own constants, through fr_debug_resident_bound) against |R - sum_j x_j best_w_j| in
-    extended precision at every step.  Returns (max observed error / E, final E / T)."""
+    extended precision at every step.  Returns (max observed error / E, final E / T).  trace (a list): the chain is
+    written down as it happens -- ("data", X), ("store", {w, R}) at every exact refresh, ("update", {f, cand, base_f,
+    norm, R}) after every update -- for tests/test_linesearch_capture_host.py, which replays it from a capture log."""
     rng = np.random.default_rng(seed)
     X = col_gen(rng, n, d).astype(np.float32)
     XL = X.astype(np.longdouble)
@@ -71,9 +73,15 @@ def _replay(seed, n, d, updates, normalize, col_gen, weight_gen, cand_gen, refre
     w = weight_gen(rng, d)
     ds = o.Dataset(X, np.zeros(n), np.zeros(n, dtype=np.int64))
 
+    if trace is not None:
+        trace.append(("data", X))
+
     def exact_refresh(w):
         T = float((np.abs(w) * colmax).sum())
-        return ds.score_linear(w).copy(), _bound(0, d, T)
+        R = ds.score_linear(w).copy()
+        if trace is not None:
+            trace.append(("store", {"w": w.copy(), "R": R.copy()}))
+        return R, _bound(0, d, T)
 
     R, E = exact_refresh(w)
     worst = 0.0
@@ -94,6 +102,8 @@ def _replay(seed, n, d, updates, normalize, col_gen, weight_gen, cand_gen, refre
         w2 = base.copy()
         w2[f] = cand
         o.resident_update(R, np.ascontiguousarray(X[:, f]), cand, base[f], 1.0 / norm)
+        if trace is not None:
+            trace.append(("update", {"f": f, "cand": cand, "base_f": float(base[f]), "norm": norm, "R": R.copy()}))
         T = abs(base[f]) * colmax[f] + float((np.abs(w2) * colmax).sum())
         E = _bound(1, E, norm, T)
         w = w2
