@@ -22,9 +22,9 @@ OBJ_DIR = os.path.join(_HERE, "build")
 LIB_PATH = os.path.join(_HERE, "libfastrank_amd.so")
 INCLUDE = os.path.join("..", "..", "include", "fastrank.h")
 DEVICE_INCS = ["device.hpp", "dataset_layout.hpp", "linesearch_policy.hpp", "fullverify.hpp", "device_plumbing.inc", "kernels_score.inc", "kernels_tree.inc", "kernels_treerank.inc", "kernels_metric.inc",
-               "kernels_linesearch.inc", "kernels_chain.inc", "kernels_fillnet.inc", "kernels_order.inc", "kernels_verify.inc", "kernels_fullrank.inc", "kernels_rr.inc", "kernels_rf.inc", "kernels_lambda.inc", "kernels_hist.inc", "device_dataset.inc", "rccl_exchange.inc"]
+               "kernels_linesearch.inc", "kernels_chain.inc", "kernels_fillnet.inc", "kernels_order.inc", "kernels_verify.inc", "kernels_fullrank.inc", "kernels_rr.inc", "kernels_rf.inc", "kernels_lambda.inc", "kernels_hist.inc", "kernels_dart.inc", "device_dataset.inc", "rccl_exchange.inc"]
 FV_INCS = ["device.hpp", "fullverify.hpp", "kernels_sortnet.inc", "kernels_fullverify.inc"]
-HOST_INCS = ["device.hpp", "dataset_layout.hpp", "host.hpp", "loader.hpp", "rf_train.hpp", "lambdamart.hpp", "lambdamart_hist.hpp", "json.hpp", INCLUDE]
+HOST_INCS = ["device.hpp", "dataset_layout.hpp", "host.hpp", "loader.hpp", "rf_train.hpp", "lambdamart.hpp", "lambdamart_dart.hpp", "lambdamart_hist.hpp", "json.hpp", INCLUDE]
 
 
 def fv_parts() -> int:

@@ -85,6 +85,8 @@ def _load():
         "fr_debug_hist_bins": (vp, [vp, C.c_uint32, sz, sz, vp, vp, vp, vp, vp]),
         "fr_debug_hist_tree": (res, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, sz]),
         "fr_debug_lambdamart_sample": (vp, [vp, C.c_char_p, C.c_uint32]),
+        "fr_debug_lambdamart_dart_plan": (vp, [C.c_char_p, C.c_uint32]),
+        "fr_debug_dart_scores": (vp, [vp, vp, vp, sz, vp, sz, vp, vp, sz]),
         "fr_debug_lambda_gradients_sampled": (vp, [vp, vp, vp, C.c_char_p, C.c_double, vp, sz, vp, vp, sz]),
         "fr_debug_hist_tree_sampled": (res, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, sz, vp, sz, vp, sz]),
         "fr_debug_hist_tree_newton": (res, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, sz, vp, sz, vp, sz, C.c_double, C.c_double, C.c_double]),

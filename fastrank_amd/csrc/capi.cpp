@@ -1607,6 +1607,77 @@ const void* fr_debug_lambdamart_sample(const CDataset* dataset, const void* para
     });
 }
 
+// LambdaMART's DART plan (csrc/lambdamart_dart.hpp) for the first `num_trees` trees of the request parameters `params_json`
+// (the LambdaMART variant's payload; its own num_trees is not read): [{"dropped": [tree indices ascending], "before": [the
+// weights w_0 .. w_{t-1}], "after": [w_0 .. w_t]}, ...], one entry per tree.  No device is touched.
+const void* fr_debug_lambdamart_dart_plan(const void* params_json, uint32_t num_trees) {
+    return json_call([&]() {
+        const fr::LambdaMARTParams p = fr::LambdaMARTParams::from_json(parse_json_or_fail(accept_str("params_json", params_json)));
+        fr::DartPlan plan(p.seed, p.drop_rate, p.max_drop, p.skip_drop);
+        std::vector<double> w;
+        Value out = Value::array();
+        auto numbers = [](const std::vector<double>& v) {
+            Value a = Value::array();
+            for (double x : v) a.push(Value::number(x));
+            return a;
+        };
+        for (uint32_t t = 0; t < num_trees; t++) {
+            const std::vector<uint32_t> dropped = p.dart() ? plan.next(t) : std::vector<uint32_t>();
+            Value o = Value::object(), d = Value::array();
+            for (uint32_t i : dropped) d.push(Value::uint(i));
+            o.set("dropped", std::move(d));
+            o.set("before", numbers(w));
+            fr::dart_reweight(w, dropped, p.learning_rate);
+            o.set("after", numbers(w));
+            out.push(std::move(o));
+        }
+        return frjson::dump(out);
+    });
+}
+
+// dart_rescore_kernel on its own: `model` must be an Ensemble of DecisionTrees (its own weights are not read).  The leaf cache
+// is filled for its trees as the trainer fills it, then the scores s = sum over include[k] (ascending tree indices) of
+// weights[include[k]] * tree(x) are formed once.  scores_out[out_len]: by instance id; cache_out[n_weights][out_len]: the
+// cache's rows by instance id (entries of instances outside the dataset are left as they are).  n_weights = the number of trees.
+const void* fr_debug_dart_scores(const CDataset* dataset, const CModel* model, const double* weights, size_t n_weights,
+                                 const uint32_t* include, size_t n_include, double* scores_out, uint16_t* cache_out, size_t out_len) {
+    return status_call([&]() {
+        const CModel& m = require_model(model);
+        const CDataset& ds = require_dataset(dataset);
+        const fr::Model& ens = m.actual;
+        bool trees = ens.kind == fr::Model::Ensemble && !ens.members.empty();
+        for (const auto& mm : ens.members) trees = trees && mm.kind == fr::Model::DecisionTree;
+        if (!trees) fr::fail_str("fr_debug_dart_scores: the model must be an Ensemble of DecisionTrees");
+        if (n_weights != ens.members.size()) fr::fail_str("fr_debug_dart_scores: one weight per tree of the model");
+        if ((n_weights && !weights) || (n_include && !include) || (out_len && (!scores_out || !cache_out)))
+            fr::fail_str("NULL pointer: fr_debug_dart_scores");
+        std::lock_guard<std::mutex> lk(api_mu_of(ds));
+        fr::DatasetView& view = *ds.view;
+        if (view.instances.empty()) return;
+        frdev::DeviceDataset& dev = view.device();
+        std::string err;
+        struct End {
+            frdev::DeviceDataset& d;
+            ~End() { d.dart_end(); }
+        } end{dev};
+        if (!dev.dart_begin(n_weights, nullptr, &err)) fr::fail_str(err);
+        for (size_t t = 0; t < n_weights; t++) {
+            std::vector<fr::TreeNode*> leaves;
+            fr::Model rm;
+            rm.kind = fr::Model::DecisionTree;
+            rm.tree = fr::LambdaMARTTrainer::number_leaves(*ens.members[t].tree, leaves);
+            fr::score_model(view, rm, &dev);
+            std::vector<double> values(leaves.size());
+            for (size_t L = 0; L < leaves.size(); L++) values[L] = leaves[L]->value;
+            if (!dev.dart_fill(t, values.data(), values.size(), &err)) fr::fail_str(err);
+        }
+        if (!dev.dart_rescore(weights, n_weights, include, n_include, &err)) fr::fail_str(err);
+        if (!dev.download_scores(0, scores_out, out_len, &err)) fr::fail_str(err);
+        for (size_t t = 0; t < n_weights; t++)
+            if (!dev.dart_download_row(t, cache_out + t * out_len, out_len, &err)) fr::fail_str(err);
+    });
+}
+
 // The body of the three gradient hooks below: one gradient pass on the model's scores, downloaded by instance id.  queries ==
 // NULL: every query (need_queries: refused); else only the named queries' instances are computed and written.  options_json:
 // nullptr for a hook that takes no options, else the address of the caller's string (fr_debug_lambda_gradients_opts below).

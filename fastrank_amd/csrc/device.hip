@@ -28,6 +28,8 @@
 //                           lambda_grad_trunc_kernel: the same under a truncation level / per-query normalisation
 //                           (both are templates over the objective: NDCG, MAP or MRR pair weights)
 //   kernels_hist.inc        LambdaMART's histogram grower: one-byte bins, int64 fixed-point gradients, per-node histograms
+//   kernels_dart.inc        LambdaMART's DART boosting: the u16 leaf cache and dart_rescore_kernel, which re-forms the scores
+//                           of any weighting of the trees from it
 //   dataset_layout.hpp      (through device.hpp; host only, no HIP) the layout arithmetic of a dataset: runs, size classes, gain
 //                           tables, duplicate groups, walk tiles, a view's tables
 //   linesearch_policy.hpp   (host only, no HIP) the adaptive policies of the bound-and-verify line search: routing / back-off of
@@ -77,6 +79,7 @@ namespace frdev {
 #include "kernels_rf.inc"
 #include "kernels_lambda.inc"
 #include "kernels_hist.inc"
+#include "kernels_dart.inc"
 #include "device_dataset.inc"
 #include "rccl_exchange.inc"
 

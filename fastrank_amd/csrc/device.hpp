@@ -294,6 +294,23 @@ class DeviceDataset {
     bool lambda_download(double* lambda_by_instance, double* weight_by_instance, size_t out_len, std::string* err,
                          const unsigned char* query_flags = nullptr);
 
+    // --- LambdaMART's DART boosting (kernels_dart.inc; DESIGN.md section 11, "DART") -----------------
+    // A cache of the leaf (u16, depth-first numbering) every document reaches in every tree, by the documents' logical index
+    // (a sampled view: its own tiles), next to a table of the trees' leaf values; the scores of any weighting of any subset
+    // of the trees are re-formed from it without walking a tree.
+    // dart_begin: an empty cache of `rows` trees, allocated after a check against the device's free memory (*cache_bytes:
+    // its size); dart_end frees it.
+    bool dart_begin(size_t rows, uint64_t* cache_bytes, std::string* err);
+    // Row `row` (rows are filled in order, 0 first) from score slot 0, which must hold the documents' leaf numbers: the scores
+    // of a copy of the tree whose leaves hold their own index.  leaf_values[n_leaves] (at most 65536): the tree's leaf values.
+    bool dart_fill(size_t row, const double* leaf_values, size_t n_leaves, std::string* err);
+    // score slot 0 = ensemble accumulator = s, per document: s = +0.0; for k ascending s = s + weights[trees[k]] * tree_{trees[k]}(x),
+    // product and sum rounded separately (dart_rescore_kernel).  trees[n_trees]: ascending, every entry < n_weights <= filled rows.
+    bool dart_rescore(const double* weights, size_t n_weights, const uint32_t* trees, size_t n_trees, std::string* err);
+    // a row scattered to original instance ids (ids >= out_len are left out)
+    bool dart_download_row(size_t row, uint16_t* out_by_instance, size_t out_len, std::string* err);
+    void dart_end();
+
     // --- LambdaMART histogram grower (kernels_hist.inc) ----------------------
     // The host (lambdamart_hist.hpp) keeps the tree and decides; the device keeps the bin matrix, the fixed-point gradients,
     // an index list partitioned by node, and one level's histograms [slot][feature][bin] of (count u32, sum Q i64).

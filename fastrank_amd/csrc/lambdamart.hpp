@@ -29,6 +29,10 @@
 // objective = "map" / "mrr" (both growers; DESIGN.md section 11, "Objectives"): the pair weight is |delta AP| / |delta RR| of
 // swapping a relevant and a non-relevant document, and the trainer's evaluator is the AP / RR one: gradient norms, the
 // reported measures, the best iteration and early stopping all follow it.  The request's `measure` must still name NDCG.
+// drop_rate > 0 (both growers; DESIGN.md section 11, "DART"; lambdamart_dart.hpp): a tree is fitted to the ensemble without a
+// random subset of its trees, then it and the dropped trees are re-weighted.  The scores are re-formed from tree 0 by
+// dart_rescore_kernel (kernels_dart.inc) from a cache of every (tree, document)'s leaf: after every tree, and once more before
+// a tree that drops.
 // A request's keys live in LambdaMARTParams alone: the gradient pass and the histogram grower get their options from it
 // (pass(), hist_options()), and the stats keep a copy of it (LambdaMARTStats::request) to report from.
 #pragma once
@@ -38,6 +42,7 @@
 #include <unordered_map>
 
 #include "host.hpp"
+#include "lambdamart_dart.hpp"
 #include "lambdamart_hist.hpp"
 #include "rf_train.hpp"
 
@@ -70,7 +75,13 @@ struct LambdaMARTParams {
     bool lambda_norm = false;
     // what the gradients optimise (optional key, not written at its default): frdev::M_NDCG, M_AP ("map", "ap") or M_RR ("mrr", "rr")
     int objective = frdev::M_NDCG;
+    // DART (optional keys, not written at their defaults): the chance of every earlier tree to be dropped (0 = plain boosting),
+    // the most trees one step drops (0 = no cap), the chance of a step to drop nothing
+    double drop_rate = 0.0;
+    uint32_t max_drop = 50;
+    double skip_drop = 0.5;
 
+    bool dart() const { return drop_rate > 0.0; }
     static const char* objective_name(int objective) { return objective == frdev::M_AP ? "map" : objective == frdev::M_RR ? "mrr" : "ndcg"; }
     // the evaluator the trainer gets under `objective` (the request's own measure is then read for nothing else)
     const char* objective_measure() const { return objective == frdev::M_AP ? "ap" : objective == frdev::M_RR ? "rr" : nullptr; }
@@ -132,6 +143,9 @@ struct LambdaMARTParams {
         if (const Value* r = v.find("truncation_level")) p.truncation_level = json_u32(*r, "truncation_level");
         if (const Value* r = v.find("lambda_norm")) p.lambda_norm = json_bool(*r, "lambda_norm");
         if (const Value* g = v.find("objective")) p.objective = objective_from_json(*g);
+        if (const Value* r = v.find("drop_rate")) p.drop_rate = json_f64(*r, "drop_rate");
+        if (const Value* r = v.find("max_drop")) p.max_drop = json_u32(*r, "max_drop");
+        if (const Value* r = v.find("skip_drop")) p.skip_drop = json_f64(*r, "skip_drop");
         if (p.num_trees < 1) invalid("num_trees must be at least 1");
         if (!(std::isfinite(p.learning_rate) && p.learning_rate > 0.0)) invalid("learning_rate must be finite and greater than 0");
         if (p.max_depth < 1) invalid("max_depth must be at least 1");
@@ -152,6 +166,12 @@ struct LambdaMARTParams {
         }
         if (p.max_leaves == 1) invalid("max_leaves must be 0 (level-wise) or at least 2");
         if (p.max_leaves >= 2 && !p.histogram) invalid("max_leaves needs grower: \"histogram\" (the exact grower grows level by level)");
+        if (!(p.drop_rate >= 0.0 && p.drop_rate <= 1.0)) invalid("drop_rate must be at least 0 and at most 1");
+        if (!(p.skip_drop >= 0.0 && p.skip_drop <= 1.0)) invalid("skip_drop must be at least 0 and at most 1");
+        if (p.max_drop != 50 && !p.dart()) invalid("max_drop needs drop_rate greater than 0");
+        if (p.skip_drop != 0.5 && !p.dart()) invalid("skip_drop needs drop_rate greater than 0");
+        if (p.early_stopping_rounds > 0 && p.dart())
+            invalid("early_stopping_rounds cannot be combined with drop_rate greater than 0 (earlier trees' weights keep changing: the trees up to the best iteration are not a model the training measured)");
         return p;
     }
     Value to_json() const {
@@ -181,6 +201,9 @@ struct LambdaMARTParams {
         if (truncation_level != 0) o.set("truncation_level", Value::uint(truncation_level));
         if (lambda_norm) o.set("lambda_norm", Value::boolean(true));
         if (objective != frdev::M_NDCG) o.set("objective", Value::string(objective_name(objective)));
+        if (drop_rate != 0.0) o.set("drop_rate", Value::number(drop_rate));
+        if (max_drop != 50) o.set("max_drop", Value::uint(max_drop));
+        if (skip_drop != 0.5) o.set("skip_drop", Value::number(skip_drop));
         return o;
     }
 };
@@ -272,6 +295,11 @@ struct LambdaMARTStats {
     // leaf-wise growth (reported only when max_leaves is set): the trees' summed numbers of leaves, and the histogram pool
     // (slots x the tree's features x bins x 12 or 20 B), the largest over the trees
     uint64_t sum_leaves = 0, pool_bytes = 0;
+    // DART (reported only when drop_rate > 0): the trees each tree was fitted without, the wall seconds of the re-formings of
+    // the scores and of the leaf cache's fills (kept out of t_update), the cache's bytes
+    std::vector<uint32_t> dropped;
+    double t_dart = 0.0;
+    uint64_t dart_cache_bytes = 0;
 
     Value to_json() const {
         const LambdaMARTParams& r = request;
@@ -323,6 +351,16 @@ struct LambdaMARTStats {
         if (r.truncation_level != 0) o.set("truncation_level", Value::uint(r.truncation_level));
         if (r.lambda_norm) o.set("lambda_norm", Value::boolean(true));
         if (r.objective != frdev::M_NDCG) o.set("objective", Value::string(LambdaMARTParams::objective_name(r.objective)));
+        if (r.dart()) {
+            o.set("drop_rate", Value::number(r.drop_rate));
+            o.set("max_drop", Value::uint(r.max_drop));
+            o.set("skip_drop", Value::number(r.skip_drop));
+            Value k = Value::array();
+            for (uint32_t x : dropped) k.push(Value::uint(x));
+            o.set("dropped", std::move(k));
+            o.set("dart_ms", Value::number(t_dart * 1e3));
+            o.set("dart_cache_bytes", Value::uint(dart_cache_bytes));
+        }
         return o;
     }
 };
@@ -428,7 +466,29 @@ class LambdaMARTTrainer {
         }
         uint32_t trained = 0, best_it = 0;
         double best_valid = 0.0;
+        // DART: the drop plan, the leaf cache (one row per tree) and the weights so far; without drop_rate none of it exists
+        const bool dart = p_.dart();
+        DartPlan plan(p_.seed, p_.drop_rate, p_.max_drop, p_.skip_drop);
+        struct DartGuard {
+            frdev::DeviceDataset& d;
+            bool on;
+            ~DartGuard() {
+                if (on) d.dart_end();
+            }
+        } dart_guard{dev, dart};
+        if (dart) {
+            if (!dev.dart_begin(p_.num_trees, &stats_.dart_cache_bytes, &err)) fail_str(err);
+        }
+        // the scores become sum_{i in trees} w_i tree_i(x), re-formed from tree 0 (slot 0 and the accumulator); waited for
+        auto reform = [&](const std::vector<uint32_t>& trees) {
+            auto t_a = tnow();
+            if (!dev.dart_rescore(out.ens_weights.data(), out.ens_weights.size(), trees.data(), trees.size(), &err)) fail_str(err);
+            if (!frdev::device_synchronize(&err)) fail_str(err);
+            stats_.t_dart += secs(t_a, tnow());
+        };
         for (uint32_t t = 0; t < p_.num_trees; t++) {
+            const std::vector<uint32_t> dropped = dart ? plan.next(t) : std::vector<uint32_t>();
+            if (!dropped.empty()) reform(dart_kept(t, dropped));  // the tree is fitted to the ensemble without the dropped trees
             auto ts = tnow();  // (drawing the sample and handing it to the grower count as grow time)
             LambdaSample smp;
             // the tree's instance list (a subsequence of the full one), feature list and positions
@@ -480,12 +540,40 @@ class LambdaMARTTrainer {
                 for (size_t L = 0; L < leaves.size(); L++) leaves[L]->value = sw[L] != 0.0 ? sl[L] / sw[L] : 0.0;
             }
             auto td = tnow();
-            // update: slot 0 = tree(x); acc = acc + learning_rate * slot 0; slot 0 = acc
+            auto tu = td;  // where the update stage begins (DART: after the cache fill and the re-forming)
             Model tm;
             tm.kind = Model::DecisionTree;
             tm.tree = root;
-            score_model(*view_, tm, &dev);
-            if (!dev.ensemble_accumulate(p_.learning_rate, &err) || !dev.ensemble_finish(&err)) fail_str(err);
+            if (dart) {  // the tree's row of the leaf cache: the routing copy's scores (slot 0) are the documents' leaf numbers
+                if (hist) {
+                    Model rm;
+                    rm.kind = Model::DecisionTree;
+                    rm.tree = number_leaves(*root, leaves);
+                    score_model(*view_, rm, &dev);
+                }
+                std::vector<double> values(leaves.size());
+                for (size_t L = 0; L < leaves.size(); L++) values[L] = leaves[L]->value;
+                if (!dev.dart_fill(t, values.data(), values.size(), &err)) fail_str(err);
+                if (!frdev::device_synchronize(&err)) fail_str(err);
+                stats_.t_dart += secs(td, tnow());
+                tu = tnow();
+                dart_reweight(out.ens_weights, dropped, p_.learning_rate);
+                stats_.dropped.push_back((uint32_t)dropped.size());
+            } else {
+                out.ens_weights.push_back(p_.learning_rate);
+            }
+            if (dart) {
+                // the running scores under the new weights, from tree 0.  Without a drop that is acc + learning_rate * tree(x) bit
+                // for bit, and streaming the cache is still the cheaper way to it (a single tree's walk costs several re-formings)
+                std::vector<uint32_t> all(t + 1);
+                for (uint32_t i = 0; i <= t; i++) all[i] = i;
+                reform(all);
+                tu = tnow();
+            } else {
+                // update: slot 0 = tree(x); acc = acc + learning_rate * slot 0; slot 0 = acc
+                score_model(*view_, tm, &dev);
+                if (!dev.ensemble_accumulate(p_.learning_rate, &err) || !dev.ensemble_finish(&err)) fail_str(err);
+            }
             double mean = 0.0, two[2] = {0.0, 0.0};
             if (!dev.metric_from_scores(ev_.measure, ev_.depth, ev_.norms.data(), 1, false, &err)) fail_str(err);
             if (hold) {  // the means over T and H, from the one per-query pass
@@ -499,12 +587,11 @@ class LambdaMARTTrainer {
             stats_.t_gradient += secs(ta, tb);
             stats_.t_grow += secs(ts, ta) + secs(tb, tc);
             stats_.t_leaves += secs(tc, td);
-            stats_.t_update += secs(td, te);
+            stats_.t_update += secs(tu, te);
             stats_.sum_leaves += n_leaves;
             if (hist) stats_.pool_bytes = hist->pool_bytes();
             stats_.train_measure.push_back(mean);
             out.members.push_back(std::move(tm));
-            out.ens_weights.push_back(p_.learning_rate);
             if (!p_.quiet) {
                 if (hold) printf("|%7u|%15.6f|%15.6f|\n", t + 1, mean, two[1]);
                 else printf("|%7u|%15.6f|\n", t + 1, mean);
@@ -533,13 +620,14 @@ class LambdaMARTTrainer {
 
     const LambdaMARTStats& stats() const { return stats_; }
 
-  private:
     // a copy of `n` whose leaves hold 0, 1, 2, ... in depth-first order; leaves[i] = the original leaf numbered i
     static std::shared_ptr<TreeNode> number_leaves(TreeNode& n, std::vector<TreeNode*>& leaves) {
         auto c = std::make_shared<TreeNode>();
         copy_numbered(n, *c, leaves);
         return c;
     }
+
+  private:
     static void copy_numbered(TreeNode& n, TreeNode& c, std::vector<TreeNode*>& leaves) {
         c.leaf = n.leaf;
         c.fid = n.fid;

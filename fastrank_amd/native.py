@@ -71,6 +71,37 @@ def lambdamart_sample(dataset: CDataset, params, tree: int) -> Tuple[np.ndarray,
     return np.asarray(rep["features"], dtype=np.uint32), np.asarray(rep["queries"], dtype=np.uint32)
 
 
+def lambdamart_dart_plan(params, num_trees: int) -> List[Dict]:
+    """LambdaMART's DART plan ("DART") for the first `num_trees` trees of `params` (LambdaMARTParams or
+    its wire dict): per tree {"dropped": the tree indices it is fitted without (ascending), "before": the weights of the
+    earlier trees, "after": the weights including its own}.  Needs no device."""
+    wire = params if isinstance(params, dict) else params.to_dict()
+    rep = _json_reply(_load().fr_debug_lambdamart_dart_plan(json.dumps(wire).encode("utf-8"), int(num_trees)))
+    return [{"dropped": [int(i) for i in r["dropped"]], "before": np.asarray(r["before"], dtype=np.float64),
+             "after": np.asarray(r["after"], dtype=np.float64)} for r in rep]
+
+
+def dart_scores(dataset: CDataset, model: CModel, weights, include, n_total: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """dart_rescore_kernel on its own: `model` is any Ensemble of DecisionTrees (its own weights are not read).  Fills the
+    leaf cache for its trees, then forms s = sum over the trees `include` (ascending indices) of weights[t] * tree_t(x), the
+    sequential unfused recurrence, once.  Returns (scores by instance id, NaN where the id is not part of a sampled dataset;
+    the cache's rows uint16[trees, n] by instance id, 0xFFFF where the id is not part)."""
+    n = int(n_total if n_total is not None else _load().fr_dataset_num_instances(dataset.pointer))
+    if n_total is None and dataset.is_sampled():
+        n = 1 + max(max(ids) for ids in dataset.instances_by_query().values())
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    inc = np.ascontiguousarray(include, dtype=np.uint32)
+    scores = np.full(n, np.nan, dtype=np.float64)
+    cache = np.full((len(w), n), 0xFFFF, dtype=np.uint16)
+    _status(
+        _load().fr_debug_dart_scores(
+            dataset.pointer, model.pointer, w.ctypes.data if len(w) else None, len(w), inc.ctypes.data if len(inc) else None, len(inc),
+            scores.ctypes.data, cache.ctypes.data, n,
+        )
+    )
+    return scores, cache
+
+
 def lambda_gradients(model: CModel, dataset: CDataset, measure: str = "ndcg", sigma: float = 1.0,
                      qrel: Optional[CQRel] = None, n_total: Optional[int] = None, queries=None,
                      truncation_level: int = 0, lambda_norm: bool = False, objective: str = "ndcg") -> Tuple[np.ndarray, np.ndarray]:

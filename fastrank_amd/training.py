@@ -114,7 +114,15 @@ class LambdaMARTParams(_LearnerParams):
     document, weighted by the change of AP / RR their swap would make, and AP / RR takes over every role of the training
     measure: the training stats' `train_measure`, `valid_measure`, `best_iteration`, early stopping and the printed table.
     The request's `measure` must still name NDCG ("ndcg", "ndcg@k") -- "map" there is refused as before -- and is then read
-    for nothing else.  Both growers, every other key ("Objectives")."""
+    for nothing else.  Both growers, every other key ("Objectives").
+    `drop_rate` (0 <= r <= 1, default 0.0 = off): DART boosting.  Before tree t >= 1 is fitted, with probability
+    1 - `skip_drop` (default 0.5) every earlier tree is dropped with probability `drop_rate`, at most `max_drop` of them
+    (default 50, 0 = no cap, the smallest indices are kept); the tree is fitted to the ensemble without the k dropped trees,
+    gets the weight learning_rate / (k + 1), and the dropped trees' weights are scaled by k / (k + 1).  The drops are a
+    function of `seed` (a stream of their own: the per-tree samples do not move).  The model's weights are then no longer
+    uniform; the training stats report `dropped` (k per tree), `dart_ms` and `dart_cache_bytes`.  `max_drop` / `skip_drop`
+    need `drop_rate` > 0, and `early_stopping_rounds` cannot be combined with it (`validation_queries` can).  Both growers,
+    every other key; the three keys are written only when they differ from their defaults ("DART")."""
 
     VARIANT: ClassVar[str] = "LambdaMART"
 
@@ -139,11 +147,15 @@ class LambdaMARTParams(_LearnerParams):
     truncation_level: int = 0
     lambda_norm: bool = False
     objective: str = "ndcg"
+    drop_rate: float = 0.0
+    max_drop: int = 50
+    skip_drop: float = 0.5
 
     _WIRE_DEFAULTS: ClassVar[Dict[str, Any]] = {"grower": "exact", "query_sampling_rate": 1.0, "feature_sampling_rate": 1.0, "seed": 0,
                                                 "validation_queries": [], "early_stopping_rounds": 0, "split_gain": "variance",
                                                 "lambda_l2": 0.0, "min_sum_hessian": 0.0, "min_split_gain": 0.0,
-                                                "max_leaves": 0, "truncation_level": 0, "lambda_norm": False, "objective": "ndcg"}
+                                                "max_leaves": 0, "truncation_level": 0, "lambda_norm": False, "objective": "ndcg",
+                                                "drop_rate": 0.0, "max_drop": 50, "skip_drop": 0.5}
     _OBJECTIVES: ClassVar[Dict[str, str]] = {"ap": "map", "rr": "mrr"}
 
     def __post_init__(self):

@@ -242,6 +242,18 @@ const void *fr_debug_lambda_gradients_opts(const CModel *model, const CDataset *
                                            const void *measure, double sigma, const uint32_t *queries,
                                            size_t n_queries, const void *options_json, double *lambda_out,
                                            double *weight_out, size_t out_len);
+/* LambdaMART's DART boosting, test hooks ("DART"; the variant's optional keys drop_rate, max_drop,
+ * skip_drop).  fr_debug_lambdamart_dart_plan: JSON [{"dropped": [tree indices ascending], "before": [w_0 .. w_{t-1}],
+ * "after": [w_0 .. w_t]}, ...] for the first num_trees trees of the LambdaMART parameters params_json (their own
+ * num_trees is not read); no device is touched.  fr_debug_dart_scores: `model` is an Ensemble of DecisionTrees (its
+ * weights are not read), weights[n_weights] one weight per tree, include[n_include] ascending tree indices; the leaf
+ * cache is filled for the trees as the trainer fills it and dart_rescore_kernel runs once: scores_out[i] = the
+ * sequential unfused sum over the included trees of weights[t] * tree_t(x_i), cache_out[t * out_len + i] = the leaf
+ * (depth-first numbering) instance i reaches in tree t (instances outside the view are left untouched). */
+const void *fr_debug_lambdamart_dart_plan(const void *params_json, uint32_t num_trees);
+const void *fr_debug_dart_scores(const CDataset *dataset, const CModel *model, const double *weights, size_t n_weights,
+                                 const uint32_t *include, size_t n_include, double *scores_out, uint16_t *cache_out,
+                                 size_t out_len);
 /* Full per-query rank order under the reference's total order (src/evaluators.rs:34-49):
  * out_instance_ids[n] grouped by query (device query order), best first; out_offsets[nq+1]. */
 const void *fr_rank_order(const CModel *model, const CDataset *dataset, uint32_t *out_instance_ids,

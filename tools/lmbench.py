@@ -60,6 +60,9 @@ def device_run(args, X, y, qid):
         req.params.max_depth = args.max_depth
     req.params.truncation_level, req.params.lambda_norm = args.truncation_level, args.lambda_norm
     req.params.objective = args.objective
+    req.params.drop_rate = args.drop_rate
+    if args.drop_rate > 0:  # (the two other keys need a drop rate)
+        req.params.max_drop, req.params.skip_drop = args.max_drop, args.skip_drop
     # upload and first touch of the device (not part of training)
     native.device_info(ds)
     t_ds = time.perf_counter() - t0
@@ -85,7 +88,7 @@ def device_run(args, X, y, qid):
         "grower": st["grower"], "bins_ms": st["bins_ms"],
         "per_tree_ms": {k: st[k + "_ms"] / T for k in ("gradient", "grow", "leaves", "update")},
         "train_measure_first": st["train_measure"][0], "train_measure_last": st["train_measure"][-1],
-        "kernel_profile": {k: v for k, v in prof.items() if "lambda" in k or "rf_" in k or "tree" in k or "hist_" in k},
+        "kernel_profile": {k: v for k, v in prof.items() if "lambda" in k or "rf_" in k or "tree" in k or "hist_" in k or "dart_" in k},
         "model_nodes": len(json.dumps(model.to_dict())),
     }
     if sample:  # (only when a rate is below 1, like the stats object)
@@ -105,6 +108,22 @@ def device_run(args, X, y, qid):
         out["objective"] = {k: st[k] for k in ("truncation_level", "lambda_norm") if k in st}
     if args.objective != "ndcg":
         out.setdefault("objective", {})["objective"] = st["objective"]
+    if args.drop_rate > 0:  # (only under DART, like the stats object)
+        out["dart"] = {"drop_rate": st["drop_rate"], "max_drop": st["max_drop"], "skip_drop": st["skip_drop"], "dropped": st["dropped"],
+                       "dart_ms": st["dart_ms"], "dart_ms_per_tree": st["dart_ms"] / T, "dart_cache_bytes": st["dart_cache_bytes"],
+                       "weights_min": float(np.min(model.to_dict()["Ensemble"]["weights"])),
+                       "weights_max": float(np.max(model.to_dict()["Ensemble"]["weights"]))}
+        # the same re-forming by re-traversal: the finished model scored by score_trees (scores left on the device), three times
+        native.profile_enable(True)
+        native.profile_reset()
+        walls = []
+        for _ in range(3):
+            tw = time.perf_counter()
+            native.predict_scores_dense(model, ds, n_total=0)
+            walls.append((time.perf_counter() - tw) * 1e3)
+        out["dart"]["retraverse_wall_ms"] = walls
+        out["dart"]["retraverse_kernels"] = {k: v for k, v in native.profile_stats().items() if "tree" in k}
+        native.profile_enable(False)
     if args.held_out_measures and args.validation_rate > 0:  # AP / RR / NDCG of the model over the held-out queries
         held = set(req.params.validation_queries)
         out["held_out"] = {}
@@ -163,6 +182,9 @@ def main():
     ap.add_argument("--truncation-level", type=int, default=0, help="a pair counts only when its better ranked document is in the top T (0: every pair)")
     ap.add_argument("--lambda-norm", action="store_true", help="scale every query's gradients by log2(1 + S_q) / S_q")
     ap.add_argument("--objective", default="ndcg", choices=["ndcg", "map", "mrr"], help="what the gradients optimise (the measure stays an NDCG spelling)")
+    ap.add_argument("--drop-rate", type=float, default=0.0, help="DART: the chance of every earlier tree to be dropped before a tree is fitted (0: plain boosting)")
+    ap.add_argument("--max-drop", type=int, default=50, help="DART: the most trees one step drops (0: no cap)")
+    ap.add_argument("--skip-drop", type=float, default=0.5, help="DART: the chance of a step to drop nothing")
     ap.add_argument("--held-out-measures", action="store_true", help="with --validation-rate: report the model's mean AP, RR and NDCG over the held-out queries")
     ap.add_argument("--warmup-trees", type=int, default=0, help="train this many trees untimed before the measured training")
     ap.add_argument("--no-kernel-profile", action="store_true", help="leave the library's per-kernel event timing off during the timed training")
