@@ -1774,11 +1774,14 @@ const void* fr_debug_hist_bins(const CDataset* dataset, uint32_t split_candidate
     });
 }
 
-// The body of the four tree hooks below.  who: the exported function's name, for its error messages; opt: what the grower is
-// made with; queries / features: the tree's sample as fr_debug_hist_tree_sampled describes it.
-static const CResult* hist_tree_debug(const std::string& who, const CDataset* dataset, const fr::HistGrowOptions& opt, const double* lambda,
+// The body of the five tree hooks below.  who: the exported function's name, for its error messages; opt: what the grower is
+// made with; queries / features: the tree's sample as fr_debug_hist_tree_sampled describes it.  mono_features / mono_signs
+// [n_mono]: monotone signs by feature id of the view (fr_debug_hist_tree_monotone; opt.monotone is made from them);
+// *clamped_out: the leaves a bound moved.
+static const CResult* hist_tree_debug(const std::string& who, const CDataset* dataset, fr::HistGrowOptions opt, const double* lambda,
                                       const double* weight, size_t len, const uint32_t* queries, size_t n_queries, const uint32_t* features,
-                                      size_t n_features) {
+                                      size_t n_features, const uint32_t* mono_features = nullptr, const int32_t* mono_signs = nullptr,
+                                      size_t n_mono = 0, uint32_t* clamped_out = nullptr) {
     return c_call<CModel>([&]() {
         const CDataset& ds = require_dataset(dataset);
         if (!lambda || !weight) fr::fail_str("NULL pointer: gradient inputs");
@@ -1804,6 +1807,16 @@ static const CResult* hist_tree_debug(const std::string& who, const CDataset* da
                 if (it == feats.end() || *it != want[i] || (i > 0 && want[i] == want[i - 1]))
                     fr::fail_str(who + ": feature " + std::to_string(want[i]) + " is not in the view, or is named twice");
                 sel.push_back((uint32_t)(it - feats.begin()));
+            }
+        }
+        if (n_mono != 0) {
+            if (!mono_features || !mono_signs) fr::fail_str("NULL pointer: monotone constraints");
+            opt.monotone.assign(feats.size(), 0);
+            for (size_t i = 0; i < n_mono; i++) {
+                const auto it = std::lower_bound(feats.begin(), feats.end(), mono_features[i]);
+                if (it == feats.end() || *it != mono_features[i]) fr::fail_str(who + ": feature " + std::to_string(mono_features[i]) + " is not in the view");
+                if (mono_signs[i] < -1 || mono_signs[i] > 1) fr::fail_str(who + ": a monotone sign must be -1, 0 or 1");
+                opt.monotone[(size_t)(it - feats.begin())] = (int)mono_signs[i];
             }
         }
         // the caller's values go to the device as they are, also outside the query sample: the grower must not read those
@@ -1835,6 +1848,7 @@ static const CResult* hist_tree_debug(const std::string& who, const CDataset* da
             fr::Model tree;
             tree.kind = fr::Model::DecisionTree;
             tree.tree = grower.grow(lam.data(), wt.data());
+            if (clamped_out) *clamped_out = grower.clamped_leaves();
             return tree;
         });
     });
@@ -1883,6 +1897,27 @@ const CResult* fr_debug_hist_tree_leafwise(const CDataset* dataset, uint32_t spl
     const fr::HistNewton gain = newton ? fr::HistNewton{true, lambda_l2, min_sum_hessian, min_split_gain} : fr::HistNewton();
     return hist_tree_debug("fr_debug_hist_tree_leafwise", dataset, {split_candidates, max_depth, min_leaf_support, gain, max_leaves}, lambda, weight,
                            len, queries, n_queries, features, n_features);
+}
+
+// One tree under monotone constraints ("Monotone constraints"): the Newton gain's numbers as
+// fr_debug_hist_tree_newton takes them, max_leaves = 0 (level-wise) or >= 2 (leaf-wise), and mono_features / mono_signs[n_mono]:
+// feature ids of the view and their signs in {-1, 0, 1}.  *clamped_leaves_out (may be NULL): the leaves a bound moved.
+const CResult* fr_debug_hist_tree_monotone(const CDataset* dataset, uint32_t split_candidates, uint32_t max_depth, uint32_t min_leaf_support,
+                                           const double* lambda, const double* weight, size_t len, const uint32_t* queries,
+                                           size_t n_queries, const uint32_t* features, size_t n_features, double lambda_l2,
+                                           double min_sum_hessian, double min_split_gain, uint32_t max_leaves,
+                                           const uint32_t* mono_features, const int32_t* mono_signs, size_t n_mono,
+                                           uint32_t* clamped_leaves_out) {
+    if (max_leaves == 1)
+        return c_call<CModel>([&]() -> CModel* { fr::fail_str("fr_debug_hist_tree_monotone: max_leaves must be 0 (level-wise) or at least 2"); });
+    const double numbers[3] = {lambda_l2, min_sum_hessian, min_split_gain};
+    for (double x : numbers)
+        if (!(std::isfinite(x) && x >= 0.0))
+            return c_call<CModel>([&]() -> CModel* { fr::fail_str("fr_debug_hist_tree_monotone: lambda_l2, min_sum_hessian and min_split_gain must be finite and at least 0"); });
+    if (clamped_leaves_out) *clamped_leaves_out = 0;
+    return hist_tree_debug("fr_debug_hist_tree_monotone", dataset,
+                           {split_candidates, max_depth, min_leaf_support, fr::HistNewton{true, lambda_l2, min_sum_hessian, min_split_gain}, max_leaves, {}},
+                           lambda, weight, len, queries, n_queries, features, n_features, mono_features, mono_signs, n_mono, clamped_leaves_out);
 }
 
 const void* fr_evaluate_dense(const CModel* model, const CDataset* dataset, const CQRel* qrel,

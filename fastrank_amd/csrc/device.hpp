@@ -346,6 +346,15 @@ class DeviceDataset {
     // with G = ldexp(Q, -s_l), H = ldexp(W, -s_w); a candidate also needs H >= min_sum_hessian and H + lambda_l2 > 0 on both sides
     bool hist_search_newton(const std::vector<HistNode>& nodes, uint32_t min_leaf, int s_l, int s_w, double lambda_l2,
                             double min_sum_hessian, std::vector<HistBestNewton>* best, std::string* err);
+    // Monotone constraints ("Monotone constraints"; Newton gain only).  hist_monotone: signs[features] in {-1, 0, +1}, one per
+    // row of the bin matrix, kept until the next call or the next bins.  hist_search_monotone: hist_search_newton with node
+    // a's interval bounds[a] for the two sides' clamped outputs, a clamped side's term (2 G) v - ((H + lambda_l2) v) v, and
+    // the order vL <= vR (sign +1) / vL >= vR (sign -1) among a candidate's conditions.  The leaf-wise calls do the same
+    // when HistLeafSearch::monotone is set (the root's interval is the whole line, the children's come with the step).
+    struct HistBounds { double lo, hi; };
+    bool hist_monotone(const int* signs, size_t features, std::string* err);
+    bool hist_search_monotone(const std::vector<HistNode>& nodes, const std::vector<HistBounds>& bounds, uint32_t min_leaf, int s_l, int s_w,
+                              double lambda_l2, double min_sum_hessian, std::vector<HistBestNewton>* best, std::string* err);
     // stable partition of the splitting nodes' stretches, then the next level (next_slots histograms; 0: none): `builds` are
     // built from their stretches, `subs` by subtraction from the level just searched
     bool hist_split(const std::vector<HistSplit>& splits, const std::vector<HistNode>& builds, const std::vector<HistSub>& subs,
@@ -355,14 +364,15 @@ class DeviceDataset {
     // Leaf-wise growth ("Leaf-wise growth"): a pool of `slots` histograms replaces the level arrays, one leaf is split per
     // step and one record per searched node comes back (hist_pick_kernel reduces the features on the device).
     struct HistPick { double imp; long long ql, qtot, wl, wtot; uint32_t edge, nl, valid, fi; };  // fi: index among the tree's features
-    struct HistLeafSearch { uint32_t min_leaf; bool newton; int s_l, s_w; double lambda_l2, min_sum_hessian; };
+    struct HistLeafSearch { uint32_t min_leaf; bool newton; int s_l, s_w; double lambda_l2, min_sum_hessian; bool monotone = false; };
     // index list = the sample's root list; the root's histogram into slot 0 of a fresh pool; *root: the root's record
     bool hist_leaf_begin(uint32_t slots, const HistLeafSearch& how, HistPick* root, std::string* err);
     // One split step: the stable partition of split's stretch alone; then, when small_slot != HIST_NO_SLOT, the smaller child's
     // histogram is built into small_slot; a searched larger child is derived in place in parent_slot (parent - smaller) and a
     // searched child is scanned.  pick[0]: the lhs's record, pick[1]: the rhs's (written for the searched ones only).
     static constexpr uint32_t HIST_NO_SLOT = 0xffffffffu;
-    struct HistLeafStep { HistSplit split; uint32_t parent_slot, small_slot; bool search_lhs, search_rhs; };
+    // (bounds[0] / bounds[1]: the lhs's / rhs's interval, read only when how.monotone)
+    struct HistLeafStep { HistSplit split; uint32_t parent_slot, small_slot; bool search_lhs, search_rhs; HistBounds bounds[2] = {}; };
     bool hist_leaf_step(const HistLeafStep& step, const HistLeafSearch& how, HistPick pick[2], std::string* err);
 
     int take_flags();  // returns and clears the accumulated kernel error bits

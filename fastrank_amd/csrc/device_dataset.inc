@@ -358,6 +358,10 @@ struct DeviceDataset::Impl : DatasetDesc {
         DevBuf<HistSubDev> subs;
         DevBuf<HistBestDev> best;
         DevBuf<HistBestNewtonDev> best_n;
+        // monotone constraints: the signs by row of the bin matrix (mono_F of them; 0: none set for these bins), the level's intervals
+        DevBuf<int> mono;
+        uint32_t mono_F = 0;
+        DevBuf<HistBoundsDev> bounds;
         // host staging of the tables above: overwritten only after the stream was waited for
         std::vector<HistItemDev> items_h, items_bh, nodes_h;
         std::vector<HistSplitDev> splits_h;
@@ -368,7 +372,7 @@ struct DeviceDataset::Impl : DatasetDesc {
     void hist_build(uint32_t* cnt, unsigned long long* sum);  // hist_build_kernel over hist.items_b into a level's histograms
     void hist_build_newton(uint32_t* cnt, unsigned long long* sum, unsigned long long* wsum);
     bool hist_leaf_scan(const HistLeafKids& kids, uint32_t count, const DeviceDataset::HistLeafSearch& how, DeviceDataset::HistPick* out,
-                        std::string* err);
+                        std::string* err, const HistLeafBoundsDev* bounds = nullptr);
     DevBuf<uint64_t> forest;
     DevBuf<uint32_t> tree_fdesc;  // tree_ensemble_rank_kernel: per-feature descriptors, Eytzinger threshold tables
     DevBuf<float> tree_tables;
@@ -4002,6 +4006,7 @@ bool DeviceDataset::hist_bins(const uint32_t* positions, size_t n, const std::ve
     for (size_t s = 0; s < F; s++)
         if (h.nedges_host[s] >= k) return hist_fail(err, "internal error: more edges than bins");
     h.qof_built = false;  // (made for these bins by the first query sample: hist_qof)
+    h.mono_F = 0;
     h.feats = feats;
     h.n = n32, h.F = (uint32_t)F, h.k = k;
     h.nt = n32, h.Ft = (uint32_t)F, h.q_sampled = h.f_sampled = false;
@@ -4288,6 +4293,59 @@ bool DeviceDataset::hist_search_newton(const std::vector<HistNode>& nodes, uint3
     return true;
 }
 
+bool DeviceDataset::hist_monotone(const int* signs, size_t features, std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    if (h.k == 0) return hist_fail(err, "no bins built");
+    if (signs == nullptr || features != h.F) return hist_fail(err, "internal error: the monotone signs do not cover the bin matrix's rows");
+    for (size_t i = 0; i < features; i++)
+        if (signs[i] < -1 || signs[i] > 1) return hist_fail(err, "internal error: a monotone sign outside {-1, 0, 1}");
+    h.mono_F = 0;
+    if (!h.mono.ensure(features, err)) return false;
+    FR_HIP(hipMemcpyAsync(h.mono.p, signs, features * sizeof(int), hipMemcpyHostToDevice, m.stream));
+    FR_HIP(hipStreamSynchronize(m.stream));  // (signs is the caller's pageable memory)
+    h.mono_F = (uint32_t)features;
+    return true;
+}
+
+bool DeviceDataset::hist_search_monotone(const std::vector<HistNode>& nodes, const std::vector<HistBounds>& bounds, uint32_t min_leaf, int s_l,
+                                         int s_w, double lambda_l2, double min_sum_hessian, std::vector<HistBestNewton>* best,
+                                         std::string* err) {
+    static_assert(sizeof(HistBounds) == sizeof(HistBoundsDev), "host and device records differ");
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    const size_t A = nodes.size();
+    best->assign(A * h.Ft, HistBestNewton{});
+    if (A == 0) return true;
+    if (bounds.size() != A) return hist_fail(err, "internal error: one interval per node is needed");
+    if (h.mono_F == 0 || h.mono_F != h.F) return hist_fail(err, "internal error: no monotone signs set for these bins");
+    const size_t fk = (size_t)h.Ft * h.k;
+    h.nodes_h.resize(A);
+    for (size_t a = 0; a < A; a++) {
+        if ((size_t)(nodes[a].slot + 1) * fk > h.cnt.cap || (size_t)(nodes[a].slot + 1) * fk > h.wsum.cap || nodes[a].end > h.nt ||
+            nodes[a].begin > nodes[a].end)
+            return hist_fail(err, "internal error: a node outside the level's histograms");
+        h.nodes_h[a] = {nodes[a].slot, nodes[a].begin, nodes[a].end};
+    }
+    if (!h.nodes.ensure(A, err) || !h.bounds.ensure(A, err) || !h.best_n.ensure(A * h.Ft, err)) return false;
+    FR_HIP(hipMemcpyAsync(h.nodes.p, h.nodes_h.data(), A * sizeof(HistItemDev), hipMemcpyHostToDevice, m.stream));
+    FR_HIP(hipMemcpyAsync(h.bounds.p, bounds.data(), A * sizeof(HistBoundsDev), hipMemcpyHostToDevice, m.stream));
+    {
+        ProfScope ps("hist_scan_monotone_kernel", m.stream);
+        hist_scan_monotone_kernel<<<(unsigned)(A * h.Ft), 64, 0, m.stream>>>(h.nodes.p, h.bounds.p, h.Ft, h.k, h.nedges.p, h.mono.p,
+                                                                             h.f_sampled ? h.fsel.p : nullptr, h.cnt.p, h.sum.p, h.wsum.p, min_leaf,
+                                                                             s_l, s_w, lambda_l2, min_sum_hessian, h.best_n.p);
+    }
+    FR_HIP(hipGetLastError());
+    FR_HIP(hipMemcpyAsync(best->data(), h.best_n.p, A * h.Ft * sizeof(HistBestNewtonDev), hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipStreamSynchronize(m.stream));  // (bounds is the caller's, read by the copy above until here)
+    return true;
+}
+
 bool DeviceDataset::hist_split(const std::vector<HistSplit>& splits, const std::vector<HistNode>& builds, const std::vector<HistSub>& subs,
                                uint32_t next_slots, std::string* err, bool newton) {
     static_assert(sizeof(HistSplit) == sizeof(HistSplitDev) && sizeof(HistSub) == sizeof(HistSubDev), "host and device records differ");
@@ -4401,7 +4459,7 @@ void DeviceDataset::hist_end() {
     auto& h = m.hist;
     (void)hipStreamSynchronize(m.stream);
     h.cnt.release(), h.cnt_o.release(), h.sum.release(), h.sum_o.release(), h.wsum.release(), h.wsum_o.release(), h.best.release(), h.best_n.release(), h.lam_in.release(), h.wt_in.release();
-    h.pcnt.release(), h.psum.release(), h.pwsum.release(), h.rec.release(), h.pick.release();
+    h.pcnt.release(), h.psum.release(), h.pwsum.release(), h.rec.release(), h.pick.release(), h.bounds.release();
     h.pool_slots = 0;
 }
 
@@ -4409,12 +4467,19 @@ void DeviceDataset::hist_end() {
 
 // scan (after deriving where asked) and pick of `count` children, their records to out[0..count); waits for the stream
 bool DeviceDataset::Impl::hist_leaf_scan(const HistLeafKids& kids, uint32_t count, const DeviceDataset::HistLeafSearch& how,
-                                         DeviceDataset::HistPick* out, std::string* err) {
+                                         DeviceDataset::HistPick* out, std::string* err, const HistLeafBoundsDev* bounds) {
     static_assert(sizeof(DeviceDataset::HistPick) == sizeof(HistPickDev), "host and device records differ");
     auto& h = hist;
     if (!h.rec.ensure((size_t)2 * h.Ft, err) || !h.pick.ensure(2, err)) return false;
     const uint32_t* fsel = h.f_sampled ? h.fsel.p : nullptr;
-    {
+    if (how.monotone) {
+        if (!how.newton || bounds == nullptr || h.mono_F == 0 || h.mono_F != h.F)
+            return hist_fail(err, "internal error: no monotone signs set for these bins");
+        ProfScope ps("hist_leaf_scan_monotone_kernel", stream);
+        hist_leaf_scan_monotone_kernel<<<dim3(h.Ft, count), 64, 0, stream>>>(kids, *bounds, h.Ft, h.k, h.nedges.p, h.mono.p, fsel, h.pcnt.p, h.psum.p,
+                                                                             h.pwsum.p, how.min_leaf, how.s_l, how.s_w, how.lambda_l2,
+                                                                             how.min_sum_hessian, h.rec.p);
+    } else {
         ProfScope ps(how.newton ? "hist_leaf_scan_kernel<newton>" : "hist_leaf_scan_kernel", stream);
         const dim3 grid(h.Ft, count);
         if (how.newton)
@@ -4468,7 +4533,10 @@ bool DeviceDataset::hist_leaf_begin(uint32_t slots, const HistLeafSearch& how, H
     FR_HIP(hipGetLastError());
     HistLeafKids kids{};
     kids.slot[0] = 0, kids.n[0] = n;
-    return m.hist_leaf_scan(kids, 1, how, root, err);
+    HistLeafBoundsDev whole{};  // (the root's interval: the whole line)
+    whole.lo[0] = whole.lo[1] = -std::numeric_limits<double>::infinity();
+    whole.hi[0] = whole.hi[1] = std::numeric_limits<double>::infinity();
+    return m.hist_leaf_scan(kids, 1, how, root, err, &whole);
 }
 
 bool DeviceDataset::hist_leaf_step(const HistLeafStep& step, const HistLeafSearch& how, HistPick pick[2], std::string* err) {
@@ -4515,6 +4583,7 @@ bool DeviceDataset::hist_leaf_step(const HistLeafStep& step, const HistLeafSearc
     FR_HIP(hipGetLastError());
     // the children to scan, the lhs first; the larger one is derived in place in its parent's slot
     HistLeafKids kids{};
+    HistLeafBoundsDev bounds{};
     uint32_t count = 0;
     int where[2] = {-1, -1};
     for (int side = 0; side < 2; side++) {
@@ -4524,11 +4593,12 @@ bool DeviceDataset::hist_leaf_step(const HistLeafStep& step, const HistLeafSearc
         kids.n[count] = side == 0 ? s.nl : nr;
         kids.derive[count] = small ? 0u : 1u;
         kids.other[count] = step.small_slot;
+        bounds.lo[count] = step.bounds[side].lo, bounds.hi[count] = step.bounds[side].hi;
         where[side] = (int)count++;
     }
     if (count == 0) return true;
     HistPick got[2];
-    if (!m.hist_leaf_scan(kids, count, how, got, err)) return false;
+    if (!m.hist_leaf_scan(kids, count, how, got, err, &bounds)) return false;
     for (int side = 0; side < 2; side++)
         if (where[side] >= 0) pick[side] = got[where[side]];
     return true;

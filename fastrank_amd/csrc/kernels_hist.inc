@@ -709,3 +709,227 @@ __global__ __launch_bounds__(64) void hist_pick_kernel(const HistPickDev* __rest
     }
     if (lane == 0) pick[a] = r[whave ? wf : 0];
 }
+
+// --- Monotone constraints (DESIGN.md section 11, "Monotone constraints") --------------------------------------------------
+// Some feature carries a sign c in {-1, 0, +1} (sign[] by row of the bin matrix, indexed like nedges) and every node an
+// interval [lo, hi] of f64 for its output.  A side's output G / (H + lambda_l2) is clamped to the interval; a side that was
+// not clamped keeps the Newton term bit for bit, a clamped one has (2 G) v - ((H + lambda_l2) v) v; a candidate on a feature
+// with c = +1 also needs vL <= vR, with c = -1 vL >= vR.  The records are the Newton kernels' (the host derives vL, vR and
+// the children's intervals again from ql, qtot, wl, wtot).  The kernels above keep their code; these stand next to them and
+// run only when some sign is not 0.
+//
+//   hist_scan_monotone_kernel       hist_scan_newton_kernel with bounds[node] and sign[feature]
+//   hist_leaf_scan_monotone_kernel  hist_leaf_scan_kernel<true> with one interval per child
+
+struct HistBoundsDev {
+    double lo, hi;
+};
+// the intervals of the (at most two) children a leaf-wise step scans
+struct HistLeafBoundsDev {
+    double lo[2], hi[2];
+};
+
+// term of one side of a candidate (h + l2 > 0) under [lo, hi]; *v: its clamped output.  Both terms are computed and one is
+// selected: the lanes of a wave disagree about which one they need
+__device__ __forceinline__ double hist_monotone_term(long long q, double h, int s_l, double l2, double lo, double hi, double* v) {
+    const double g = ldexp((double)q, -s_l), den = h + l2;
+    const double out = g / den;
+    double c = out < lo ? lo : out;
+    c = c > hi ? hi : c;
+    const double plain = (g * g) / den;
+    const double bound = (2.0 * g) * c - (den * c) * c;
+    *v = c;
+    return c == out ? plain : bound;
+}
+
+// (validity as hist_scan_newton_kernel's; false: no candidate)
+__device__ __forceinline__ bool hist_monotone_candidate(long long ql, long long wl, long long qtot, long long wtot, int s_l, int s_w, double l2,
+                                                        double min_hess, double lo, double hi, int sign, double* imp) {
+    const double hl = ldexp((double)wl, -s_w), hr = ldexp((double)(wtot - wl), -s_w);
+    if (!(hl >= min_hess && hr >= min_hess && hl + l2 > 0.0 && hr + l2 > 0.0)) return false;
+    double vl, vr;
+    const double tl = hist_monotone_term(ql, hl, s_l, l2, lo, hi, &vl), tr = hist_monotone_term(qtot - ql, hr, s_l, l2, lo, hi, &vr);
+    if ((sign > 0 && !(vl <= vr)) || (sign < 0 && !(vl >= vr))) return false;
+    *imp = tl + tr;
+    return true;
+}
+
+// one wave per (node, feature), as hist_scan_newton_kernel.  bounds[a]: node a's interval
+__global__ __launch_bounds__(64) void hist_scan_monotone_kernel(const HistItemDev* __restrict__ nodes, const HistBoundsDev* __restrict__ bounds,
+                                                                uint32_t F, uint32_t k, const uint32_t* __restrict__ nedges,
+                                                                const int* __restrict__ sign, const uint32_t* __restrict__ fsel,
+                                                                const uint32_t* __restrict__ cnt, const unsigned long long* __restrict__ sum,
+                                                                const unsigned long long* __restrict__ wsum, uint32_t min_leaf, int s_l, int s_w,
+                                                                double l2, double min_hess, HistBestNewtonDev* __restrict__ best) {
+    const uint32_t a = blockIdx.x / F, f = blockIdx.x % F, lane = threadIdx.x;
+    const HistItemDev nd = nodes[a];
+    const HistBoundsDev bd = bounds[a];
+    const uint32_t n = nd.end - nd.begin;
+    const uint32_t row = fsel ? fsel[f] : f;
+    const uint32_t ne = min(nedges[row], k - 1);
+    const int sg = sign[row];
+    const size_t base = ((size_t)nd.slot * F + f) * k;
+    const uint32_t B = (k + 63) / 64;  // bins per lane (<= 4)
+    uint32_t c[4];
+    long long s[4], w[4];
+    uint32_t tc = 0;
+    long long ts = 0, tw = 0;
+    for (uint32_t u = 0; u < 4; u++) {
+        const uint32_t b = lane * B + u;
+        const bool in = u < B && b < k;
+        c[u] = in ? cnt[base + b] : 0u;
+        s[u] = in ? (long long)sum[base + b] : 0ll;
+        w[u] = in ? (long long)wsum[base + b] : 0ll;
+        tc += c[u];
+        ts += s[u];
+        tw += w[u];
+    }
+    uint32_t ic = tc;
+    long long is = ts, iw = tw;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t oc = __shfl_up(ic, o);
+        const long long os = __shfl_up(is, o), ow = __shfl_up(iw, o);
+        if ((int)lane >= o) {
+            ic += oc;
+            is += os;
+            iw += ow;
+        }
+    }
+    const long long qtot = __shfl(is, 63), wtot = __shfl(iw, 63);
+    uint32_t rc = ic - tc;  // counts / sums of the bins before this lane's
+    long long rs = is - ts, rw = iw - tw;
+    double bimp = 0.0;
+    uint32_t bj = 0, bnl = 0, have = 0;
+    long long bql = 0, bwl = 0;
+    for (uint32_t u = 0; u < B; u++) {
+        const uint32_t j = lane * B + u;
+        rc += c[u];
+        rs += s[u];
+        rw += w[u];
+        if (j >= ne) break;
+        const uint32_t nl = rc, nr = n - rc;
+        if (nl == 0 || nr == 0 || nl < min_leaf || nr < min_leaf) continue;
+        double imp;
+        if (!hist_monotone_candidate(rs, rw, qtot, wtot, s_l, s_w, l2, min_hess, bd.lo, bd.hi, sg, &imp)) continue;
+        if (!have || imp >= bimp) {
+            have = 1;
+            bimp = imp;
+            bj = j;
+            bnl = nl;
+            bql = rs;
+            bwl = rw;
+        }
+    }
+    // the last maximum over the lanes: larger importance, then the later edge
+    double wimp = bimp;
+    uint32_t wj = bj, whave = have;
+    for (int o = 32; o > 0; o >>= 1) {
+        const double oimp = __shfl_xor(wimp, o);
+        const uint32_t oj = __shfl_xor(wj, o), ohave = __shfl_xor(whave, o);
+        if (ohave && (!whave || oimp > wimp || (oimp == wimp && oj > wj))) {
+            whave = 1;
+            wimp = oimp;
+            wj = oj;
+        }
+    }
+    HistBestNewtonDev* out = best + (size_t)a * F + f;
+    if (!whave) {
+        if (lane == 0) *out = HistBestNewtonDev{0.0, 0ll, qtot, 0ll, wtot, 0u, 0u, 0u, 0u};
+    } else if (have && bj == wj) {
+        *out = HistBestNewtonDev{bimp, bql, qtot, bwl, wtot, bj, bnl, 1u, 0u};
+    }
+}
+
+// grid (F, children), as hist_leaf_scan_kernel<true>: the in-place parent - sibling derivation, then the scan under the child's
+// own interval.  rec[child * F + f]
+__global__ __launch_bounds__(64) void hist_leaf_scan_monotone_kernel(HistLeafKids kids, HistLeafBoundsDev bounds, uint32_t F, uint32_t k,
+                                                                     const uint32_t* __restrict__ nedges, const int* __restrict__ sign,
+                                                                     const uint32_t* __restrict__ fsel, uint32_t* cnt, unsigned long long* sum,
+                                                                     unsigned long long* wsum, uint32_t min_leaf, int s_l, int s_w, double l2,
+                                                                     double min_hess, HistPickDev* __restrict__ rec) {
+    const uint32_t f = blockIdx.x, a = blockIdx.y, lane = threadIdx.x;
+    const uint32_t n = kids.n[a];
+    const double lo = bounds.lo[a], hi = bounds.hi[a];
+    const uint32_t row = fsel ? fsel[f] : f;
+    const uint32_t ne = min(nedges[row], k - 1);
+    const int sg = sign[row];
+    const size_t base = ((size_t)kids.slot[a] * F + f) * k, obase = ((size_t)kids.other[a] * F + f) * k;
+    const bool derive = kids.derive[a] != 0;
+    const uint32_t B = (k + 63) / 64;  // bins per lane (<= 4)
+    uint32_t c[4];
+    long long s[4], w[4];
+    uint32_t tc = 0;
+    long long ts = 0, tw = 0;
+    for (uint32_t u = 0; u < 4; u++) {
+        const uint32_t b = lane * B + u;
+        const bool in = u < B && b < k;
+        c[u] = in ? cnt[base + b] : 0u;
+        s[u] = in ? (long long)sum[base + b] : 0ll;
+        w[u] = in ? (long long)wsum[base + b] : 0ll;
+        if (derive && in) {  // (this wave alone reads and writes the bins of (slot, f))
+            c[u] -= cnt[obase + b];
+            s[u] -= (long long)sum[obase + b];
+            w[u] -= (long long)wsum[obase + b];
+            cnt[base + b] = c[u];
+            sum[base + b] = (unsigned long long)s[u];
+            wsum[base + b] = (unsigned long long)w[u];
+        }
+        tc += c[u];
+        ts += s[u];
+        tw += w[u];
+    }
+    uint32_t ic = tc;
+    long long is = ts, iw = tw;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t oc = __shfl_up(ic, o);
+        const long long os = __shfl_up(is, o), ow = __shfl_up(iw, o);
+        if ((int)lane >= o) {
+            ic += oc;
+            is += os;
+            iw += ow;
+        }
+    }
+    const long long qtot = __shfl(is, 63), wtot = __shfl(iw, 63);
+    uint32_t rc = ic - tc;  // counts / sums of the bins before this lane's
+    long long rs = is - ts, rw = iw - tw;
+    double bimp = 0.0;
+    uint32_t bj = 0, bnl = 0, have = 0;
+    long long bql = 0, bwl = 0;
+    for (uint32_t u = 0; u < B; u++) {
+        const uint32_t j = lane * B + u;
+        rc += c[u];
+        rs += s[u];
+        rw += w[u];
+        if (j >= ne) break;
+        const uint32_t nl = rc, nr = n - rc;
+        if (nl == 0 || nr == 0 || nl < min_leaf || nr < min_leaf) continue;
+        double imp;
+        if (!hist_monotone_candidate(rs, rw, qtot, wtot, s_l, s_w, l2, min_hess, lo, hi, sg, &imp)) continue;
+        if (!have || imp >= bimp) {
+            have = 1;
+            bimp = imp;
+            bj = j;
+            bnl = nl;
+            bql = rs;
+            bwl = rw;
+        }
+    }
+    // the last maximum over the lanes: larger importance, then the later edge
+    double wimp = bimp;
+    uint32_t wj = bj, whave = have;
+    for (int o = 32; o > 0; o >>= 1) {
+        const double oimp = __shfl_xor(wimp, o);
+        const uint32_t oj = __shfl_xor(wj, o), ohave = __shfl_xor(whave, o);
+        if (ohave && (!whave || oimp > wimp || (oimp == wimp && oj > wj))) {
+            whave = 1;
+            wimp = oimp;
+            wj = oj;
+        }
+    }
+    HistPickDev* out = rec + (size_t)a * F + f;
+    if (!whave) {
+        if (lane == 0) *out = HistPickDev{0.0, 0ll, qtot, 0ll, wtot, 0u, 0u, 0u, f};
+    } else if (have && bj == wj) {
+        *out = HistPickDev{bimp, bql, qtot, bwl, wtot, bj, bnl, 1u, f};
+    }
+}

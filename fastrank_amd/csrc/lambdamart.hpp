@@ -33,6 +33,9 @@
 // random subset of its trees, then it and the dropped trees are re-weighted.  The scores are re-formed from tree 0 by
 // dart_rescore_kernel (kernels_dart.inc) from a cache of every (tree, document)'s leaf: after every tree, and once more before
 // a tree that drops.
+// monotone_constraints (histogram grower under the Newton gain only; DESIGN.md section 11, "Monotone constraints"): feature
+// name -> +1 / -1: with every other feature fixed the model's score never falls / never rises as that feature rises.  Every
+// node carries an interval for its output, the scan kernels are the monotone ones, leaves are clamped to their intervals.
 // A request's keys live in LambdaMARTParams alone: the gradient pass and the histogram grower get their options from it
 // (pass(), hist_options()), and the stats keep a copy of it (LambdaMARTStats::request) to report from.
 #pragma once
@@ -80,6 +83,9 @@ struct LambdaMARTParams {
     double drop_rate = 0.0;
     uint32_t max_drop = 50;
     double skip_drop = 0.5;
+    // monotone constraints (optional key, written only when some entry is not 0): feature name (as the dataset spells it) ->
+    // +1 / -1, in the request's order; entries of 0 are dropped when the request is read
+    std::vector<std::pair<std::string, int>> monotone_constraints;
 
     bool dart() const { return drop_rate > 0.0; }
     static const char* objective_name(int objective) { return objective == frdev::M_AP ? "map" : objective == frdev::M_RR ? "mrr" : "ndcg"; }
@@ -90,8 +96,10 @@ struct LambdaMARTParams {
     frdev::DeviceDataset::LambdaPass pass(const unsigned char* flags, bool unchanged) const {
         return {flags, unchanged, truncation_level, lambda_norm, objective};
     }
-    HistGrowOptions hist_options() const {
-        return {split_candidates, max_depth, min_leaf_support, HistNewton{newton, lambda_l2, min_sum_hessian, min_split_gain}, max_leaves};
+    // (monotone: the signs resolved against the ascending feature list, lambdamart_monotone_signs; empty without the key)
+    HistGrowOptions hist_options(std::vector<int> monotone = {}) const {
+        return {split_candidates, max_depth, min_leaf_support, HistNewton{newton, lambda_l2, min_sum_hessian, min_split_gain}, max_leaves,
+                std::move(monotone)};
     }
     [[noreturn]] static void invalid(const std::string& what) {
         fail_raw("Error(\"invalid value: " + what + "\", line: 0, column: 0)");
@@ -146,6 +154,20 @@ struct LambdaMARTParams {
         if (const Value* r = v.find("drop_rate")) p.drop_rate = json_f64(*r, "drop_rate");
         if (const Value* r = v.find("max_drop")) p.max_drop = json_u32(*r, "max_drop");
         if (const Value* r = v.find("skip_drop")) p.skip_drop = json_f64(*r, "skip_drop");
+        if (const Value* m = v.find("monotone_constraints")) {
+            if (!m->is_object()) fail_raw("Error(\"invalid type: expected an object from feature name to -1, 0 or 1 for monotone_constraints\", line: 0, column: 0)");
+            for (const auto& kv : m->obj) {
+                const Value& e = kv.second;
+                if (e.kind != Value::UInt && e.kind != Value::Int)
+                    fail_raw("Error(\"invalid type: expected an integer for every entry of monotone_constraints\", line: 0, column: 0)");
+                const bool ok = e.kind == Value::UInt ? e.u <= 1 : (e.i >= -1 && e.i <= 1);
+                if (!ok) invalid("monotone_constraints must map feature `" + kv.first + "` to -1, 0 or 1");
+                const int sign = e.kind == Value::UInt ? (int)e.u : (int)e.i;
+                for (const auto& seen : p.monotone_constraints)
+                    if (seen.first == kv.first) invalid("monotone_constraints names feature `" + kv.first + "` more than once");
+                if (sign != 0) p.monotone_constraints.emplace_back(kv.first, sign);
+            }
+        }
         if (p.num_trees < 1) invalid("num_trees must be at least 1");
         if (!(std::isfinite(p.learning_rate) && p.learning_rate > 0.0)) invalid("learning_rate must be finite and greater than 0");
         if (p.max_depth < 1) invalid("max_depth must be at least 1");
@@ -172,6 +194,10 @@ struct LambdaMARTParams {
         if (p.skip_drop != 0.5 && !p.dart()) invalid("skip_drop needs drop_rate greater than 0");
         if (p.early_stopping_rounds > 0 && p.dart())
             invalid("early_stopping_rounds cannot be combined with drop_rate greater than 0 (earlier trees' weights keep changing: the trees up to the best iteration are not a model the training measured)");
+        if (!p.monotone_constraints.empty() && !p.histogram)
+            invalid("monotone_constraints needs grower: \"histogram\" (the exact grower has no hessian sums)");
+        if (!p.monotone_constraints.empty() && !p.newton)
+            invalid("monotone_constraints needs split_gain: \"newton\" (the variance criterion has no hessian sums)");
         return p;
     }
     Value to_json() const {
@@ -204,6 +230,11 @@ struct LambdaMARTParams {
         if (drop_rate != 0.0) o.set("drop_rate", Value::number(drop_rate));
         if (max_drop != 50) o.set("max_drop", Value::uint(max_drop));
         if (skip_drop != 0.5) o.set("skip_drop", Value::number(skip_drop));
+        if (!monotone_constraints.empty()) {
+            Value m = Value::object();
+            for (const auto& kv : monotone_constraints) m.set(kv.first, Value::sint(kv.second));
+            o.set("monotone_constraints", std::move(m));
+        }
         return o;
     }
 };
@@ -249,6 +280,21 @@ inline LambdaSplit lambdamart_split(DatasetView& view, const LambdaMARTParams& p
     }
     for (size_t q = 0; q < nq; q++) (out[q] ? sp.held : sp.train).push_back((uint32_t)q);
     return sp;
+}
+
+// The request's monotone constraints against the view: one sign per entry of the view's ascending feature list `feats`
+// (empty without the key).  Host only: a name the view does not hold fails before any device work.
+inline std::vector<int> lambdamart_monotone_signs(const DatasetView& view, const std::vector<uint32_t>& feats, const LambdaMARTParams& p) {
+    if (p.monotone_constraints.empty()) return {};
+    std::vector<int> signs(feats.size(), 0);
+    for (const auto& kv : p.monotone_constraints) {
+        size_t at = feats.size();
+        for (size_t i = 0; i < feats.size() && at == feats.size(); i++)
+            if (view.core->feature_name(feats[i]) == kv.first) at = i;
+        if (at == feats.size()) LambdaMARTParams::invalid("monotone_constraints names `" + kv.first + "`, which is not a feature of the dataset");
+        signs[at] = kv.second;
+    }
+    return signs;
 }
 
 // A tree's sample ("Sampling"): indices into the view's ascending feature list and into the view's
@@ -300,6 +346,9 @@ struct LambdaMARTStats {
     std::vector<uint32_t> dropped;
     double t_dart = 0.0;
     uint64_t dart_cache_bytes = 0;
+    // monotone constraints (reported only when the key is set): feature id -> sign, and per tree the leaves a bound moved
+    std::vector<std::pair<uint32_t, int>> monotone;
+    std::vector<uint32_t> clamped_leaves;
 
     Value to_json() const {
         const LambdaMARTParams& r = request;
@@ -361,6 +410,14 @@ struct LambdaMARTStats {
             o.set("dart_ms", Value::number(t_dart * 1e3));
             o.set("dart_cache_bytes", Value::uint(dart_cache_bytes));
         }
+        if (!r.monotone_constraints.empty()) {
+            Value m = Value::object();
+            for (const auto& kv : monotone) m.set(std::to_string(kv.first), Value::sint(kv.second));
+            o.set("monotone_constraints", std::move(m));
+            Value k = Value::array();
+            for (uint32_t x : clamped_leaves) k.push(Value::uint(x));
+            o.set("monotone_clamped_leaves", std::move(k));
+        }
         return o;
     }
 };
@@ -382,12 +439,15 @@ class LambdaMARTTrainer {
             fail_str(std::string("LambdaMART: the evaluator does not belong to the objective `") + LambdaMARTParams::objective_name(p_.objective) + "`");
         const LambdaSplit split = lambdamart_split(*view_, p_);  // (host only: a bad list fails before any device work)
         const bool hold = !split.held.empty();
+        std::vector<uint32_t> feats = view_->features;
+        std::sort(feats.begin(), feats.end());
+        const std::vector<int> signs = lambdamart_monotone_signs(*view_, feats, p_);  // (host only as well)
+        for (size_t i = 0; i < signs.size(); i++)
+            if (signs[i] != 0) stats_.monotone.emplace_back(feats[i], signs[i]);
         frdev::DeviceDataset& dev = view_->device();
         const frdev::HostCSR& csr = view_->host_csr();
         const DataCore& core = *view_->core;
         std::string err;
-        std::vector<uint32_t> feats = view_->features;
-        std::sort(feats.begin(), feats.end());
         if (feats.empty()) fail_str("assertion failed: !features.is_empty()");
         if (csr.nq == 0) fail_str("assertion failed: !data.queries().is_empty()");
         // the instance list: queries in the view's order, ids ascending inside each (RFTrainer's order)
@@ -404,7 +464,7 @@ class LambdaMARTTrainer {
 
         std::unique_ptr<HistGrower> hist;
         if (p_.histogram) {
-            hist.reset(new HistGrower(dev, feats, p_.hist_options()));
+            hist.reset(new HistGrower(dev, feats, p_.hist_options(signs)));
             auto tb0 = tnow();
             if (hist->prepare(positions)) stats_.t_bins = secs(tb0, tnow());
         }
@@ -590,6 +650,7 @@ class LambdaMARTTrainer {
             stats_.t_update += secs(tu, te);
             stats_.sum_leaves += n_leaves;
             if (hist) stats_.pool_bytes = hist->pool_bytes();
+            if (hist && !signs.empty()) stats_.clamped_leaves.push_back(hist->clamped_leaves());
             stats_.train_measure.push_back(mean);
             out.members.push_back(std::move(tm));
             if (!p_.quiet) {

@@ -12,9 +12,14 @@
 // max_leaves >= 2 ("Leaf-wise growth"): the tree is grown one leaf at a time instead, always the open
 // leaf whose best split gains most, until it has max_leaves leaves; the device keeps a pool of histograms, one per open
 // leaf, and returns one record per searched node (grow_leaves below).  max_leaves = 0 is the level loop, untouched.
+// monotone constraints ("Monotone constraints"; Newton gain only): some feature carries a sign, every
+// node an interval [lo, hi] for its output; the device's candidates are those of the monotone scan kernels, and the host
+// derives the children's intervals from the winning record's integer sums by the same two-case rule (monotone_term below).
+// Without a non-zero sign nothing here differs.
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <limits>
 
 #include "host.hpp"
 
@@ -27,17 +32,26 @@ struct HistNewton {
 };
 
 // what a grower is made with: k = split_candidates (bins per feature), the depth limit, the least leaf support, the split
-// criterion and the leaf budget (0: level-wise growth)
+// criterion, the leaf budget (0: level-wise growth) and the monotone signs: one of {-1, 0, +1} per entry of the ascending
+// feature list (empty, or all 0: no constraint; a non-zero one needs the Newton gain)
 struct HistGrowOptions {
     uint32_t k = 0, max_depth = 0, min_leaf = 0;
     HistNewton newton;
     uint32_t max_leaves = 0;
+    std::vector<int> monotone;
 };
 
 class HistGrower {
   public:
     HistGrower(frdev::DeviceDataset& dev, std::vector<uint32_t> feats, const HistGrowOptions& opt)
-        : dev_(dev), feats_(std::move(feats)), k_(opt.k), max_depth_(opt.max_depth), min_leaf_(opt.min_leaf), newton_(opt.newton), max_leaves_(opt.max_leaves) {}
+        : dev_(dev), feats_(std::move(feats)), k_(opt.k), max_depth_(opt.max_depth), min_leaf_(opt.min_leaf), newton_(opt.newton), max_leaves_(opt.max_leaves) {
+        for (int c : opt.monotone) mono_on_ = mono_on_ || c != 0;
+        if (mono_on_) {
+            if (!newton_.on) fail_str("LambdaMART histogram grower: monotone constraints need the Newton gain");
+            if (opt.monotone.size() != feats_.size()) fail_str("LambdaMART histogram grower: one monotone sign per feature is needed");
+            mono_ = opt.monotone;
+        }
+    }
     ~HistGrower() { dev_.hist_end(); }
 
     // bins for the instance list at `positions`; true when they were built now (false: the view's kept ones were reused)
@@ -46,6 +60,7 @@ class HistGrower {
         bool built = false;
         if (!dev_.hist_bins(positions.data(), positions.size(), feats_, k_, &built, &err)) fail_str(err);
         if (!dev_.hist_edges(&edges_, &nedges_, &err)) fail_str(err);
+        if (mono_on_ && !dev_.hist_monotone(mono_.data(), mono_.size(), &err)) fail_str(err);
         n_ = n_full_ = (uint32_t)positions.size();
         sel_.clear();
         return built;
@@ -82,31 +97,36 @@ class HistGrower {
         if (!dev_.hist_quantise(lam_list, wt_list, &s_l, &s_w, &all_zero, &err)) fail_str(err);
         auto root = std::make_shared<TreeNode>();
         if (n_leaves) *n_leaves = 1;
+        clamped_ = 0;
         if (all_zero) return root;  // one leaf of value 0.0
         if (max_leaves_ >= 2) {
             std::vector<TreeNode*> lw_nodes;
             std::vector<Dev::HistNode> lw_leaves;
-            const bool rooted = grow_leaves(root.get(), s_l, s_w, &lw_nodes, &lw_leaves);
+            std::vector<Dev::HistBounds> lw_bounds;
+            const bool rooted = grow_leaves(root.get(), s_l, s_w, &lw_nodes, &lw_leaves, &lw_bounds);
             if (n_leaves) *n_leaves = (uint32_t)lw_nodes.size();
-            leaf_values(lw_nodes, lw_leaves, s_l, s_w, rooted, leaf_seconds);
+            leaf_values(lw_nodes, lw_leaves, lw_bounds, s_l, s_w, rooted, leaf_seconds);
             return root;
         }
         struct Open {
             TreeNode* node;
             uint32_t slot, begin, end, depth;
+            Dev::HistBounds bd;  // (read only under monotone constraints)
         };
         std::vector<Open> open, next;
         std::vector<TreeNode*> leaf_nodes;
         std::vector<Dev::HistNode> leaves;
-        auto close = [&](TreeNode* t, uint32_t b, uint32_t e) {
+        std::vector<Dev::HistBounds> leaf_bounds, node_bounds;
+        auto close = [&](TreeNode* t, uint32_t b, uint32_t e, const Dev::HistBounds& bd) {
             leaf_nodes.push_back(t);
             leaves.push_back({(uint32_t)leaves.size(), b, e});
+            leaf_bounds.push_back(bd);
         };
         if (enterable(n_, 1)) {
             if (!dev_.hist_root(&err, newton_.on)) fail_str(err);
-            open.push_back({root.get(), 0u, 0u, n_, 1u});
+            open.push_back({root.get(), 0u, 0u, n_, 1u, whole_line()});
         } else {
-            close(root.get(), 0u, n_);
+            close(root.get(), 0u, n_, whole_line());
         }
         const size_t F = features();
         std::vector<Dev::HistNode> nodes, builds;
@@ -119,7 +139,14 @@ class HistGrower {
             nodes.clear(), builds.clear(), splits.clear(), subs.clear(), next.clear();
             for (const Open& o : open) nodes.push_back({o.slot, o.begin, o.end});
             if (newton_.on) {  // the selection below reads the fields the two records share
-                if (!dev_.hist_search_newton(nodes, min_leaf_, s_l, s_w, newton_.lambda_l2, newton_.min_sum_hessian, &best_n, &err)) fail_str(err);
+                if (mono_on_) {
+                    node_bounds.clear();
+                    for (const Open& o : open) node_bounds.push_back(o.bd);
+                    if (!dev_.hist_search_monotone(nodes, node_bounds, min_leaf_, s_l, s_w, newton_.lambda_l2, newton_.min_sum_hessian, &best_n, &err))
+                        fail_str(err);
+                } else if (!dev_.hist_search_newton(nodes, min_leaf_, s_l, s_w, newton_.lambda_l2, newton_.min_sum_hessian, &best_n, &err)) {
+                    fail_str(err);
+                }
                 best.resize(best_n.size());
                 for (size_t i = 0; i < best_n.size(); i++) {
                     const Dev::HistBestNewton& b = best_n[i];
@@ -139,19 +166,25 @@ class HistGrower {
                 }
                 if (w != nullptr && newton_.on) {  // the node's totals (Qnode, Wnode) arrive with every record of the node
                     const Dev::HistBestNewton& b = best_n[a * F + wf];
-                    if (!(newton_gain(w->imp, b.qtot, b.wtot, s_l, s_w) > newton_.min_split_gain)) w = nullptr;
+                    const double gain = mono_on_ ? w->imp - monotone_term(b.qtot, b.wtot, s_l, s_w, o.bd) : newton_gain(w->imp, b.qtot, b.wtot, s_l, s_w);
+                    if (!(gain > newton_.min_split_gain)) w = nullptr;
                 }
                 if (w == nullptr) {
-                    close(o.node, o.begin, o.end);
+                    close(o.node, o.begin, o.end, o.bd);
                     continue;
+                }
+                Dev::HistBounds bl = o.bd, br = o.bd;
+                if (mono_on_) {
+                    const Dev::HistBestNewton& b = best_n[a * F + wf];
+                    child_bounds(o.bd, mono_[full(wf)], b.ql, b.wl, b.qtot, b.wtot, s_l, s_w, &bl, &br);
                 }
                 const uint32_t n = o.end - o.begin, nl = w->nl, nr = n - nl;
                 const size_t ws = split_node(o.node, wf, w->edge, n, nl);
                 splits.push_back({o.begin, o.end, (uint32_t)ws, w->edge, nl});  // (the bin matrix's row)
                 const uint32_t mid = o.begin + nl;
                 const bool el = enterable(nl, o.depth + 1), er = enterable(nr, o.depth + 1);
-                if (!el) close(o.node->lhs.get(), o.begin, mid);
-                if (!er) close(o.node->rhs.get(), mid, o.end);
+                if (!el) close(o.node->lhs.get(), o.begin, mid, bl);
+                if (!er) close(o.node->rhs.get(), mid, o.end, br);
                 if (!el && !er) continue;
                 const bool left_small = nl <= nr;
                 const uint32_t small_slot = next_slots++;
@@ -161,16 +194,19 @@ class HistGrower {
                     large_slot = next_slots++;
                     subs.push_back({o.slot, small_slot, large_slot});
                 }
-                if (el) next.push_back({o.node->lhs.get(), left_small ? small_slot : large_slot, o.begin, mid, o.depth + 1});
-                if (er) next.push_back({o.node->rhs.get(), left_small ? large_slot : small_slot, mid, o.end, o.depth + 1});
+                if (el) next.push_back({o.node->lhs.get(), left_small ? small_slot : large_slot, o.begin, mid, o.depth + 1, bl});
+                if (er) next.push_back({o.node->rhs.get(), left_small ? large_slot : small_slot, mid, o.end, o.depth + 1, br});
             }
             if (!dev_.hist_split(splits, builds, subs, next_slots, &err, newton_.on)) fail_str(err);
             open.swap(next);
         }
-        leaf_values(leaf_nodes, leaves, s_l, s_w, rooted, leaf_seconds);
+        leaf_values(leaf_nodes, leaves, leaf_bounds, s_l, s_w, rooted, leaf_seconds);
         if (n_leaves) *n_leaves = (uint32_t)leaf_nodes.size();
         return root;
     }
+
+    // monotone constraints: the leaves of the last tree whose value a bound moved
+    uint32_t clamped_leaves() const { return clamped_; }
 
     // leaf-wise growth: the largest histogram pool a tree of this grower asked for, in bytes (0: none yet)
     uint64_t pool_bytes() const { return pool_bytes_; }
@@ -181,7 +217,8 @@ class HistGrower {
     // the open leaf with the largest gain is split (the smallest creation index among equals) while the tree has fewer than
     // max_leaves leaves.  Fills leaf_nodes / leaves like the level loop does.  false: the root was not searched, and the
     // device's index list was not made.
-    bool grow_leaves(TreeNode* root, int s_l, int s_w, std::vector<TreeNode*>* leaf_nodes, std::vector<frdev::DeviceDataset::HistNode>* leaves) {
+    bool grow_leaves(TreeNode* root, int s_l, int s_w, std::vector<TreeNode*>* leaf_nodes, std::vector<frdev::DeviceDataset::HistNode>* leaves,
+                     std::vector<frdev::DeviceDataset::HistBounds>* leaf_bounds) {
         using Dev = frdev::DeviceDataset;
         std::string err;
         struct OpenLeaf {
@@ -189,43 +226,46 @@ class HistGrower {
             uint32_t slot, begin, end, depth, index;
             double gain;
             Dev::HistPick pick;
+            Dev::HistBounds bd;  // (read only under monotone constraints)
         };
         std::vector<OpenLeaf> open;
-        auto close = [&](TreeNode* t, uint32_t b, uint32_t e) {
+        auto close = [&](TreeNode* t, uint32_t b, uint32_t e, const Dev::HistBounds& bd) {
             leaf_nodes->push_back(t);
             leaves->push_back({(uint32_t)leaves->size(), b, e});
+            leaf_bounds->push_back(bd);
         };
         if (!enterable(n_, 1)) {
-            close(root, 0u, n_);
+            close(root, 0u, n_, whole_line());
             return false;
         }
-        const Dev::HistLeafSearch how{min_leaf_, newton_.on, s_l, s_w, newton_.lambda_l2, newton_.min_sum_hessian};
+        const Dev::HistLeafSearch how{min_leaf_, newton_.on, s_l, s_w, newton_.lambda_l2, newton_.min_sum_hessian, mono_on_};
         // live histograms never exceed the leaves, and the leaves neither max_leaves, the instances nor 2^(max_depth - 1)
         uint32_t slots = std::min(max_leaves_, n_);
         if (max_depth_ <= 31) slots = std::min(slots, 1u << (max_depth_ - 1));
         std::vector<uint32_t> free_slots;
         for (uint32_t s = slots; s-- > 1;) free_slots.push_back(s);  // (slot 0: the root's)
         // the record of a searched leaf: open with its gain, or closed and its slot free again
-        auto consider = [&](TreeNode* t, uint32_t slot, uint32_t b, uint32_t e, uint32_t depth, uint32_t index, const Dev::HistPick& p) {
+        auto consider = [&](TreeNode* t, uint32_t slot, uint32_t b, uint32_t e, uint32_t depth, uint32_t index, const Dev::HistPick& p,
+                            const Dev::HistBounds& bd) {
             bool ok = p.valid != 0;
             double gain = 0.0;
             if (ok && newton_.on) {
-                gain = newton_gain(p.imp, p.qtot, p.wtot, s_l, s_w);
+                gain = mono_on_ ? p.imp - monotone_term(p.qtot, p.wtot, s_l, s_w, bd) : newton_gain(p.imp, p.qtot, p.wtot, s_l, s_w);
                 ok = gain > newton_.min_split_gain;
             } else if (ok) {  // (ranks only: rounding may leave it slightly below 0)
                 const double sn = (double)p.qtot;
                 gain = p.imp - (sn * sn) / (double)(e - b);
             }
             if (ok) {
-                open.push_back({t, slot, b, e, depth, index, gain, p});
+                open.push_back({t, slot, b, e, depth, index, gain, p, bd});
             } else {
-                close(t, b, e);
+                close(t, b, e, bd);
                 free_slots.push_back(slot);
             }
         };
         Dev::HistPick pick[2];
         if (!dev_.hist_leaf_begin(slots, how, &pick[0], &err)) fail_str(err);
-        consider(root, 0u, 0u, n_, 1u, 0u, pick[0]);
+        consider(root, 0u, 0u, n_, 1u, 0u, pick[0], whole_line());
         uint32_t n_leaves = 1, next_index = 1;
         while (n_leaves < max_leaves_ && !open.empty()) {
             size_t at = 0;
@@ -241,6 +281,8 @@ class HistGrower {
             const bool el = more && enterable(nl, o.depth + 1), er = more && enterable(nr, o.depth + 1);
             const bool left_small = nl <= nr;
             Dev::HistLeafStep step{{o.begin, o.end, (uint32_t)ws, o.pick.edge, nl}, o.slot, Dev::HIST_NO_SLOT, el, er};
+            step.bounds[0] = step.bounds[1] = o.bd;
+            if (mono_on_) child_bounds(o.bd, mono_[ws], o.pick.ql, o.pick.wl, o.pick.qtot, o.pick.wtot, s_l, s_w, &step.bounds[0], &step.bounds[1]);
             if (el || er) {
                 if (free_slots.empty()) fail_str("LambdaMART histogram grower: internal error: the histogram pool is exhausted");
                 step.small_slot = free_slots.back();
@@ -248,16 +290,16 @@ class HistGrower {
             }
             if (!dev_.hist_leaf_step(step, how, pick, &err)) fail_str(err);
             const uint32_t slot_l = left_small ? step.small_slot : o.slot, slot_r = left_small ? o.slot : step.small_slot;
-            if (el) consider(o.node->lhs.get(), slot_l, o.begin, mid, o.depth + 1, il, pick[0]);
-            else close(o.node->lhs.get(), o.begin, mid);
-            if (er) consider(o.node->rhs.get(), slot_r, mid, o.end, o.depth + 1, ir, pick[1]);
-            else close(o.node->rhs.get(), mid, o.end);
+            if (el) consider(o.node->lhs.get(), slot_l, o.begin, mid, o.depth + 1, il, pick[0], step.bounds[0]);
+            else close(o.node->lhs.get(), o.begin, mid, step.bounds[0]);
+            if (er) consider(o.node->rhs.get(), slot_r, mid, o.end, o.depth + 1, ir, pick[1], step.bounds[1]);
+            else close(o.node->rhs.get(), mid, o.end, step.bounds[1]);
             // a slot whose child was not searched holds nothing that is read again
             if (!el && (el || er)) free_slots.push_back(slot_l);
             if (!er && (el || er)) free_slots.push_back(slot_r);
             if (!el && !er) free_slots.push_back(o.slot);
         }
-        for (const OpenLeaf& o : open) close(o.node, o.begin, o.end);
+        for (const OpenLeaf& o : open) close(o.node, o.begin, o.end, o.bd);
         pool_bytes_ = std::max(pool_bytes_, (uint64_t)slots * features() * k_ * (newton_.on ? 20u : 12u));
         return true;
     }
@@ -289,10 +331,38 @@ class HistGrower {
     // exceeds min_split_gain
     double newton_gain(double imp, long long qtot, long long wtot, int s_l, int s_w) const { return imp - newton_term(qtot, wtot, s_l, s_w); }
 
+    // Monotone constraints.  The root's interval; an output G / (H + lambda_l2) (the leaf rule's 0.0 for a zero denominator)
+    // clamped to an interval; and term(G, H, v): the Newton term when nothing was clamped, else (2 G) v - ((H + lambda_l2) v) v,
+    // every operation rounded on its own, as the monotone scan kernels do.
+    static frdev::DeviceDataset::HistBounds whole_line() {
+        return {-std::numeric_limits<double>::infinity(), std::numeric_limits<double>::infinity()};
+    }
+    double monotone_term(long long q, long long w, int s_l, int s_w, const frdev::DeviceDataset::HistBounds& bd, double* v_out = nullptr) const {
+        const double g = std::ldexp((double)q, -s_l), den = std::ldexp((double)w, -s_w) + newton_.lambda_l2;
+        const double out = den != 0.0 ? g / den : 0.0;
+        double v = out < bd.lo ? bd.lo : out;
+        v = v > bd.hi ? bd.hi : v;
+        if (v_out) *v_out = v;
+        return v == out ? (g * g) / den : (2.0 * g) * v - (den * v) * v;
+    }
+    // the children's intervals after a split on a feature of sign c: mid = (vL + vR) 0.5 cuts the node's interval
+    void child_bounds(const frdev::DeviceDataset::HistBounds& bd, int c, long long ql, long long wl, long long qtot, long long wtot, int s_l, int s_w,
+                      frdev::DeviceDataset::HistBounds* lhs, frdev::DeviceDataset::HistBounds* rhs) const {
+        *lhs = *rhs = bd;
+        if (c == 0) return;
+        double vl = 0.0, vr = 0.0;
+        (void)monotone_term(ql, wl, s_l, s_w, bd, &vl);
+        (void)monotone_term(qtot - ql, wtot - wl, s_l, s_w, bd, &vr);
+        const double mid = (vl + vr) * 0.5;
+        if (c > 0) lhs->hi = mid, rhs->lo = mid;
+        else lhs->lo = mid, rhs->hi = mid;
+    }
+
     // Leaf values from the leaves' integer sums.  rooted = false: the tree never searched, and the index list the sums are
     // taken over is made here, as the root's.
-    void leaf_values(const std::vector<TreeNode*>& leaf_nodes, const std::vector<frdev::DeviceDataset::HistNode>& leaves, int s_l, int s_w,
-                     bool rooted, double* leaf_seconds) {
+    // Under monotone constraints a value is clamped to its leaf's interval (bounds[i]), and the moved ones are counted.
+    void leaf_values(const std::vector<TreeNode*>& leaf_nodes, const std::vector<frdev::DeviceDataset::HistNode>& leaves,
+                     const std::vector<frdev::DeviceDataset::HistBounds>& bounds, int s_l, int s_w, bool rooted, double* leaf_seconds) {
         std::string err;
         auto t0 = std::chrono::steady_clock::now();
         if (!rooted && !dev_.hist_root(&err)) fail_str(err);
@@ -303,6 +373,13 @@ class HistGrower {
             if (newton_.on) {
                 const double den = std::ldexp((double)w, -s_w) + newton_.lambda_l2;
                 leaf_nodes[i]->value = den != 0.0 ? std::ldexp((double)q, -s_l) / den : 0.0;
+                if (mono_on_) {
+                    const double out = leaf_nodes[i]->value;
+                    double v = out < bounds[i].lo ? bounds[i].lo : out;
+                    v = v > bounds[i].hi ? bounds[i].hi : v;
+                    if (v != out) clamped_++;
+                    leaf_nodes[i]->value = v;
+                }
             } else {
                 leaf_nodes[i]->value = w != 0 ? std::ldexp((double)q, -s_l) / std::ldexp((double)w, -s_w) : 0.0;
             }
@@ -324,6 +401,9 @@ class HistGrower {
     HistNewton newton_;
     uint32_t max_leaves_ = 0;                                  // 0: level-wise growth
     uint64_t pool_bytes_ = 0;
+    bool mono_on_ = false;                                     // some monotone sign is not 0
+    std::vector<int> mono_;                                    // (then) the signs, by entry of feats_
+    uint32_t clamped_ = 0;
     std::vector<uint32_t> sel_;                                // the tree's features as slots of the bins (empty: all)
     std::vector<float> edges_;
     std::vector<uint32_t> nedges_;

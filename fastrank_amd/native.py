@@ -169,12 +169,16 @@ def hist_bins(dataset: CDataset, split_candidates: int):
 
 def hist_tree(dataset: CDataset, lam: np.ndarray, wt: np.ndarray, split_candidates: int, max_depth: int,
               min_leaf_support: int, queries=None, features=None, split_gain: str = "variance", lambda_l2: float = 0.0,
-              min_sum_hessian: float = 0.0, min_split_gain: float = 0.0, max_leaves: int = 0) -> CModel:
+              min_sum_hessian: float = 0.0, min_split_gain: float = 0.0, max_leaves: int = 0, monotone=None,
+              clamped_out: Optional[list] = None) -> CModel:
     """One tree of LambdaMART's histogram grower for the gradients lam / wt (indexed by instance id).  `queries` (indices of
     the view's queries) / `features` (feature ids): the tree's sample; gradients outside the query sample are not read.
     `split_gain` = "newton": the second-order gain with `lambda_l2`, `min_sum_hessian` and `min_split_gain` (DESIGN.md
     section 11, "Newton split gain").  `max_leaves` >= 2: the tree is grown leaf-wise under that leaf budget (DESIGN.md
-    section 11, "Leaf-wise growth"), 0: level-wise.  At the defaults the call is the one it was."""
+    section 11, "Leaf-wise growth"), 0: level-wise.  `monotone` = {feature id: sign in -1, 0, +1} with some non-zero sign
+    (needs `split_gain` = "newton"): the tree is grown under monotone constraints ("Monotone
+    constraints"), level-wise or leaf-wise, and the number of leaves a bound moved is appended to `clamped_out` when that is
+    a list.  At the defaults the call is the one it was."""
     lam = np.ascontiguousarray(lam, dtype=np.float64)
     wt = np.ascontiguousarray(wt, dtype=np.float64)
     if lam.shape != wt.shape or lam.ndim != 1:
@@ -185,6 +189,26 @@ def hist_tree(dataset: CDataset, lam: np.ndarray, wt: np.ndarray, split_candidat
     fs = None if features is None else np.ascontiguousarray(features, dtype=np.uint32)
     sample = (None if qs is None else qs.ctypes.data, 0 if qs is None else len(qs),
               None if fs is None else fs.ctypes.data, 0 if fs is None else len(fs))
+    if monotone is not None and any(int(c) != 0 for c in monotone.values()):
+        if split_gain != "newton":
+            raise ValueError("monotone constraints need split_gain='newton'")
+        if int(max_leaves) == 1:
+            raise ValueError("max_leaves must be 0 (level-wise) or at least 2")
+        mf = np.ascontiguousarray([int(f) for f in monotone.keys()], dtype=np.uint32)
+        ms = np.ascontiguousarray([int(c) for c in monotone.values()], dtype=np.int32)
+        clamped = np.zeros(1, dtype=np.uint32)
+        model = CModel(
+            _unwrap(
+                _load().fr_debug_hist_tree_monotone(
+                    dataset.pointer, int(split_candidates), int(max_depth), int(min_leaf_support), lam.ctypes.data,
+                    wt.ctypes.data, lam.shape[0], *sample, float(lambda_l2), float(min_sum_hessian), float(min_split_gain),
+                    int(max_leaves), mf.ctypes.data, ms.ctypes.data, len(mf), clamped.ctypes.data,
+                )
+            )
+        )
+        if clamped_out is not None:
+            clamped_out.append(int(clamped[0]))
+        return model
     if int(max_leaves) != 0:
         if int(max_leaves) < 2:
             raise ValueError("max_leaves must be 0 (level-wise) or at least 2")

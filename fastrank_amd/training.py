@@ -122,7 +122,14 @@ class LambdaMARTParams(_LearnerParams):
     function of `seed` (a stream of their own: the per-tree samples do not move).  The model's weights are then no longer
     uniform; the training stats report `dropped` (k per tree), `dart_ms` and `dart_cache_bytes`.  `max_drop` / `skip_drop`
     need `drop_rate` > 0, and `early_stopping_rounds` cannot be combined with it (`validation_queries` can).  Both growers,
-    every other key; the three keys are written only when they differ from their defaults ("DART")."""
+    every other key; the three keys are written only when they differ from their defaults ("DART").
+    `monotone_constraints` (default none): feature name, as `CDataset.feature_names()` spells it, to +1 (with every other
+    feature fixed the model's score never falls as this feature rises), -1 (it never rises) or 0 (no constraint; such
+    entries are dropped from the wire form, and the key is written only when an entry is left).  Histogram grower under
+    `split_gain` = "newton" only, level-wise and leaf-wise, with every other key; a name the dataset does not hold is an
+    error when training starts.  The training stats then report `monotone_constraints` (feature id -> sign) and
+    `monotone_clamped_leaves` (per tree, the leaves whose value a bound moved) ("Monotone
+    constraints")."""
 
     VARIANT: ClassVar[str] = "LambdaMART"
 
@@ -150,12 +157,13 @@ class LambdaMARTParams(_LearnerParams):
     drop_rate: float = 0.0
     max_drop: int = 50
     skip_drop: float = 0.5
+    monotone_constraints: Dict[str, int] = dataclasses.field(default_factory=dict)
 
     _WIRE_DEFAULTS: ClassVar[Dict[str, Any]] = {"grower": "exact", "query_sampling_rate": 1.0, "feature_sampling_rate": 1.0, "seed": 0,
                                                 "validation_queries": [], "early_stopping_rounds": 0, "split_gain": "variance",
                                                 "lambda_l2": 0.0, "min_sum_hessian": 0.0, "min_split_gain": 0.0,
                                                 "max_leaves": 0, "truncation_level": 0, "lambda_norm": False, "objective": "ndcg",
-                                                "drop_rate": 0.0, "max_drop": 50, "skip_drop": 0.5}
+                                                "drop_rate": 0.0, "max_drop": 50, "skip_drop": 0.5, "monotone_constraints": {}}
     _OBJECTIVES: ClassVar[Dict[str, str]] = {"ap": "map", "rr": "mrr"}
 
     def __post_init__(self):
@@ -164,6 +172,8 @@ class LambdaMARTParams(_LearnerParams):
 
     def to_dict(self) -> Dict[str, Any]:
         wire = dataclasses.asdict(self)
+        if isinstance(wire["monotone_constraints"], dict):  # (anything else is left for the request parser to refuse)
+            wire["monotone_constraints"] = {k: v for k, v in wire["monotone_constraints"].items() if not (type(v) is int and v == 0)}
         for key, default in self._WIRE_DEFAULTS.items():  # serde: skip_serializing_if
             if wire[key] == default:
                 del wire[key]

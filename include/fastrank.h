@@ -228,6 +228,17 @@ const CResult *fr_debug_hist_tree_leafwise(const CDataset *dataset, uint32_t spl
                                            size_t len, const uint32_t *queries, size_t n_queries,
                                            const uint32_t *features, size_t n_features, int newton, double lambda_l2,
                                            double min_sum_hessian, double min_split_gain, uint32_t max_leaves);
+/* One tree under monotone constraints ("Monotone constraints"; Newton gain only): the numbers of
+ * fr_debug_hist_tree_newton, max_leaves = 0 (level-wise) or >= 2 (leaf-wise), and mono_features / mono_signs[n_mono] =
+ * feature ids of the view and their signs in {-1, 0, 1}.  *clamped_leaves_out (may be NULL): the leaves whose value a
+ * bound moved. */
+const CResult *fr_debug_hist_tree_monotone(const CDataset *dataset, uint32_t split_candidates, uint32_t max_depth,
+                                           uint32_t min_leaf_support, const double *lambda, const double *weight,
+                                           size_t len, const uint32_t *queries, size_t n_queries,
+                                           const uint32_t *features, size_t n_features, double lambda_l2,
+                                           double min_sum_hessian, double min_split_gain, uint32_t max_leaves,
+                                           const uint32_t *mono_features, const int32_t *mono_signs, size_t n_mono,
+                                           uint32_t *clamped_leaves_out);
 /* fr_debug_lambda_gradients under the LambdaRank objective's options ("Truncation and
  * normalisation").  options_json = {"truncation_level": T, "lambda_norm": bool}, either key optional: T >= 1 keeps a pair
  * only when the better ranked of its two documents is in the top T of the pass's ranks (0, the default: every pair);

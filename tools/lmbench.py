@@ -16,6 +16,8 @@
                                                                # the objective's truncation level and per-query normalisation
     python tools/lmbench.py --shape 30k --trees 100 --grower histogram --objective map --validation-rate 0.1
                                                                # gradients for MAP ("mrr": for MRR); reports the held-out AP and RR
+    python tools/lmbench.py --shape 30k --trees 100 --grower histogram --split-gain newton --monotone 8
+                                                               # monotone constraints on the first 8 features, signs +1, -1, +1, ...
 Every other parameter is the LambdaMART default (TrainRequest.lambdamart()).
 """
 import argparse
@@ -63,6 +65,10 @@ def device_run(args, X, y, qid):
     req.params.drop_rate = args.drop_rate
     if args.drop_rate > 0:  # (the two other keys need a drop rate)
         req.params.max_drop, req.params.skip_drop = args.max_drop, args.skip_drop
+    if args.monotone:  # the first N features of the dataset, alternating signs from +1
+        names = ds.feature_index_to_name()
+        first = sorted(names)[:args.monotone]
+        req.params.monotone_constraints = {names[f]: (1 if i % 2 == 0 else -1) for i, f in enumerate(first)}
     # upload and first touch of the device (not part of training)
     native.device_info(ds)
     t_ds = time.perf_counter() - t0
@@ -124,6 +130,9 @@ def device_run(args, X, y, qid):
         out["dart"]["retraverse_wall_ms"] = walls
         out["dart"]["retraverse_kernels"] = {k: v for k, v in native.profile_stats().items() if "tree" in k}
         native.profile_enable(False)
+    if args.monotone:  # (only with the key, like the stats object)
+        out["monotone"] = {"features": len(st["monotone_constraints"]), "clamped_leaves_per_tree": float(np.mean(st["monotone_clamped_leaves"])),
+                           "clamped_leaves_max": int(np.max(st["monotone_clamped_leaves"]))}
     if args.held_out_measures and args.validation_rate > 0:  # AP / RR / NDCG of the model over the held-out queries
         held = set(req.params.validation_queries)
         out["held_out"] = {}
@@ -185,6 +194,7 @@ def main():
     ap.add_argument("--drop-rate", type=float, default=0.0, help="DART: the chance of every earlier tree to be dropped before a tree is fitted (0: plain boosting)")
     ap.add_argument("--max-drop", type=int, default=50, help="DART: the most trees one step drops (0: no cap)")
     ap.add_argument("--skip-drop", type=float, default=0.5, help="DART: the chance of a step to drop nothing")
+    ap.add_argument("--monotone", type=int, default=0, help="monotone constraints on the first N features, signs alternating from +1 (needs --split-gain newton)")
     ap.add_argument("--held-out-measures", action="store_true", help="with --validation-rate: report the model's mean AP, RR and NDCG over the held-out queries")
     ap.add_argument("--warmup-trees", type=int, default=0, help="train this many trees untimed before the measured training")
     ap.add_argument("--no-kernel-profile", action="store_true", help="leave the library's per-kernel event timing off during the timed training")
