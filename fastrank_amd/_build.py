@@ -24,7 +24,8 @@ INCLUDE = os.path.join("..", "..", "include", "fastrank.h")
 DEVICE_INCS = ["device.hpp", "dataset_layout.hpp", "linesearch_policy.hpp", "fullverify.hpp", "device_plumbing.inc", "kernels_score.inc", "kernels_tree.inc", "kernels_treerank.inc", "kernels_metric.inc",
                "kernels_linesearch.inc", "kernels_chain.inc", "kernels_fillnet.inc", "kernels_order.inc", "kernels_verify.inc", "kernels_fullrank.inc", "kernels_rr.inc", "kernels_rf.inc", "kernels_lambda.inc", "kernels_hist.inc", "kernels_dart.inc", "device_dataset.inc", "rccl_exchange.inc"]
 FV_INCS = ["device.hpp", "fullverify.hpp", "kernels_sortnet.inc", "kernels_fullverify.inc"]
-HOST_INCS = ["device.hpp", "dataset_layout.hpp", "host.hpp", "loader.hpp", "rf_train.hpp", "lambdamart.hpp", "lambdamart_dart.hpp", "lambdamart_hist.hpp", "json.hpp", INCLUDE]
+EXPLAIN_INCS = ["explain.hpp"]
+HOST_INCS = ["device.hpp", "dataset_layout.hpp", "host.hpp", "loader.hpp", "rf_train.hpp", "lambdamart.hpp", "lambdamart_dart.hpp", "lambdamart_hist.hpp", "explain.hpp", "explain_host.hpp", "json.hpp", INCLUDE]
 
 
 def fv_parts() -> int:
@@ -34,7 +35,7 @@ def fv_parts() -> int:
 
 def units():
     """(object name, source, extra flags, dependencies)"""
-    out = [("device.o", "device.hip", [], DEVICE_INCS), ("capi.o", "capi.cpp", [], HOST_INCS)]
+    out = [("device.o", "device.hip", [], DEVICE_INCS), ("capi.o", "capi.cpp", [], HOST_INCS), ("explain.o", "explain.hip", [], EXPLAIN_INCS)]
     for k in range(fv_parts()):
         out.append(("fullverify_%d.o" % k, "fullverify.hip", ["-DFV_PART=%d" % k], FV_INCS))
     return out

@@ -81,6 +81,9 @@ def _load():
         "fr_ca_capture_take": (vp, [vp, C.c_char_p, vp, sz]),
         "fr_last_train_stats": (vp, []),
         "fr_predict_scores_dense": (vp, [vp, vp, vp, sz]),
+        "fr_explain_dense": (vp, [vp, vp, vp, vp, sz, sz]),
+        "fr_feature_importance": (vp, [vp, vp, vp, vp, sz]),
+        "fr_debug_explain_table": (vp, [vp, vp, sz, C.c_uint32]),
         "fr_debug_lambda_gradients": (vp, [vp, vp, vp, C.c_char_p, C.c_double, vp, vp, sz]),
         "fr_debug_hist_bins": (vp, [vp, C.c_uint32, sz, sz, vp, vp, vp, vp, vp]),
         "fr_debug_hist_tree": (res, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, sz]),
@@ -280,6 +283,23 @@ class CModel:
 
     def to_dict(self):
         return self._query_json("to_json")
+
+    def explain(self, dataset: "CDataset", background: Optional["CDataset"] = None):
+        """Exact TreeSHAP feature contributions of a tree model for every document of `dataset`:
+        an object with `values` (n x F float64 by instance id, NaN rows outside a sampled view), `feature_ids`,
+        `feature_names` and `expected_value`; values.sum(1) + expected_value is the model's score.  The covers are
+        counted on `background` (default: `dataset` itself)."""
+        from . import native
+
+        return native.explain_dense(self, dataset, background)
+
+    def feature_importance(self, dataset: "CDataset", background: Optional["CDataset"] = None) -> Dict[str, float]:
+        """{feature name: mean |contribution|} over the documents of `dataset`, reduced on the device."""
+        from . import native
+
+        ids, mean_abs, _ = native.feature_importance(self, dataset, background)
+        names = dataset.feature_index_to_name()
+        return dict((names[int(f)], float(v)) for f, v in zip(ids, mean_abs))
 
     def __str__(self):
         return str(self.to_dict())

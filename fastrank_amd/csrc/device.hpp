@@ -375,6 +375,20 @@ class DeviceDataset {
     struct HistLeafStep { HistSplit split; uint32_t parent_slot, small_slot; bool search_lhs, search_rhs; HistBounds bounds[2] = {}; };
     bool hist_leaf_step(const HistLeafStep& step, const HistLeafSearch& how, HistPick pick[2], std::string* err);
 
+    // --- model explanation (explain.hip, a translation unit of its own) ---------
+    // What that unit reads of a dataset, once this dataset's stream has drained: the feature tiles (kernels_score.inc:
+    // float index(p, j) = ((p >> 6) * dq + (j >> 2)) * 256 + (p & 63) * 4 + (j & 3)) and, per padded position, the
+    // instance id of this dataset's document there (IDX_INVALID: padding, or a document of the parent that a sampled view
+    // does not hold).  Read only; the pointers live as long as the dataset.
+    struct TileForm {
+        const float* xb = nullptr;
+        size_t np = 0, dq = 0, d = 0, n = 0;
+        int device = 0;
+        bool nonfinite = false;
+        const uint32_t* perm_host = nullptr;  // [np]
+    };
+    bool tile_form(TileForm* out, std::string* err);
+
     int take_flags();  // returns and clears the accumulated kernel error bits
 
     // --- read-back of the device form, for the tests that hold every table to its definition ------

@@ -439,6 +439,18 @@ DeviceDataset::~DeviceDataset() {
 size_t DeviceDataset::n() const { return impl_->n; }
 size_t DeviceDataset::d() const { return impl_->d; }
 size_t DeviceDataset::nq() const { return impl_->nq; }
+bool DeviceDataset::tile_form(TileForm* out, std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    FR_HIP(hipStreamSynchronize(m.stream));
+    out->xb = m.xb.p;
+    out->np = m.np, out->dq = m.dq, out->d = m.d, out->n = m.n;
+    out->device = m.device;
+    out->nonfinite = m.nonfinite;
+    out->perm_host = m.perm_host.data();
+    return true;
+}
 size_t DeviceDataset::max_query_len() const { return impl_->maxlen; }
 size_t DeviceDataset::hbm_bytes() const {
     // bytes of dataset arrays this object OWNS (aliases of a parent's buffers are the parent's)

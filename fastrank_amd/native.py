@@ -50,6 +50,50 @@ def predict_scores_dense(model: CModel, dataset: CDataset, n_total: Optional[int
     return out
 
 
+class Explanation:
+    """What CModel.explain returns: values[n, F] (float64, by instance id; NaN rows where the id is not part of a sampled
+    dataset), the columns' feature_ids / feature_names, expected_value (the bias: values.sum(1) + expected_value is the
+    score) and the call's status (timings, sizes)."""
+
+    def __init__(self, values, feature_ids, feature_names, expected_value, status):
+        self.values, self.feature_ids, self.feature_names = values, feature_ids, feature_names
+        self.expected_value, self.status = expected_value, status
+
+
+def explain_dense(model: CModel, dataset: CDataset, background: Optional[CDataset] = None, n_total: Optional[int] = None) -> Explanation:
+    """fr_explain_dense: exact TreeSHAP contributions by instance id (include/fastrank.h)."""
+    n = int(n_total if n_total is not None else _load().fr_dataset_num_instances(dataset.pointer))
+    if n_total is None and dataset.is_sampled():
+        n = 1 + max(max(ids) for ids in dataset.instances_by_query().values())
+    names = dataset.feature_index_to_name()
+    ids = sorted(names)
+    out = np.full((n, len(ids) + 1), np.nan, dtype=np.float64)
+    rep = _json_reply(_load().fr_explain_dense(model.pointer, dataset.pointer, None if background is None else background.pointer,
+                                               out.ctypes.data, n, len(ids) + 1))
+    assert [int(f) for f in rep["feature_ids"]] == ids
+    return Explanation(out[:, :-1], np.asarray(ids, dtype=np.uint32), [names[f] for f in ids], float(rep["expected_value"]), rep)
+
+
+def feature_importance(model: CModel, dataset: CDataset, background: Optional[CDataset] = None) -> Tuple[np.ndarray, np.ndarray, Dict]:
+    """fr_feature_importance: (feature ids ascending, mean |contribution| per feature, the status with "split_counts")."""
+    ids = sorted(dataset.feature_ids())
+    out = np.zeros(len(ids), dtype=np.float64)
+    rep = _json_reply(_load().fr_feature_importance(model.pointer, dataset.pointer, None if background is None else background.pointer,
+                                                    out.ctypes.data, len(ids)))
+    assert [int(f) for f in rep["feature_ids"]] == ids
+    return np.asarray(ids, dtype=np.uint32), out, rep
+
+
+def explain_table(model: CModel, leaf_counts, dataset_features: int) -> Dict:
+    """fr_debug_explain_table: the explain kernel's path table for given leaf counts (no device).  Doubles come back as
+    float64 arrays (they cross as the hex of their bits)."""
+    lc = np.ascontiguousarray(leaf_counts, dtype=np.uint32)
+    rep = _json_reply(_load().fr_debug_explain_table(model.pointer, lc.ctypes.data if len(lc) else None, len(lc), int(dataset_features)))
+    for key in ("weight", "value", "lo", "hi", "z", "bias"):
+        rep[key] = np.asarray([int(h, 16) for h in rep[key]], dtype=np.uint64).view(np.float64)
+    return rep
+
+
 def evaluate_dense(model: CModel, dataset: CDataset, evaluator: str, qrel: Optional[CQRel] = None) -> Tuple[List[str], np.ndarray]:
     nq = num_queries(dataset)
     out = np.zeros(nq, dtype=np.float64)

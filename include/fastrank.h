@@ -180,6 +180,27 @@ const void *fr_predict_scores_dense(const CModel *model, const CDataset *dataset
 const void *fr_evaluate_dense(const CModel *model, const CDataset *dataset, const CQRel *qrel,
                               const void *evaluator_name, double *out_values, size_t out_len,
                               const void **out_qids_json);
+/* Model explanation: exact TreeSHAP feature contributions of a DecisionTree or an Ensemble of
+ * DecisionTrees, path-dependent, with the covers counted on `background_or_null` (NULL: the explained dataset itself).
+ * out[id * cols + c], id = instance id as in fr_predict_scores_dense (rows outside the dataset view, and ids >= rows, are
+ * left as the caller filled them); the columns are the dataset's feature ids ascending, then the bias, so cols must be
+ * num_features + 1.  A row's sum is the model's score of the document up to rounding.  Returns JSON (free_str):
+ * {"feature_ids": [...], "split_counts": [...], "expected_value": bias, "trees", "leaf_paths", "max_path", "documents",
+ *  "cover_ms", "kernel_ms", "copy_ms"}, or the error envelope.  Refused: Linear and SingleFeature models, nested ensembles,
+ * a background with no instance, a root-to-leaf path with more than 32 distinct features, an output that does not fit the
+ * device's free memory (or FR_EXPLAIN_MAX_BYTES, if that is smaller). */
+const void *fr_explain_dense(const CModel *model, const CDataset *dataset, const CDataset *background_or_null,
+                             double *out, size_t rows, size_t cols);
+/* out_mean_abs[f] = the mean over the dataset's documents of |phi_f|, columns as above without the bias; the documents
+ * are explained and reduced on the device 65 536 at a time in a fixed shape (same bytes every run), the matrix is never
+ * kept or downloaded.  The same JSON; "split_counts" = split nodes per feature over all trees. */
+const void *fr_feature_importance(const CModel *model, const CDataset *dataset, const CDataset *background_or_null,
+                                  double *out_mean_abs, size_t n_features);
+/* Test hook, no device: the path table the explain kernel would read for `model` when leaf_counts[n_leaves] documents of
+ * the background reach its leaves (depth first, tree after tree) on a dataset of dataset_features features.  JSON; doubles
+ * travel as the hex of their bits. */
+const void *fr_debug_explain_table(const CModel *model, const uint32_t *leaf_counts, size_t n_leaves,
+                                   uint32_t dataset_features);
 /* LambdaMART test hook: one gradient pass on the scores of `model` for `measure` (ndcg or ndcg@k;
  * qrel-judged norms when qrel is given) with sigmoid scale sigma.  lambda_out / weight_out[i] = the
  * LambdaRank gradient / weight of instance i (instances outside the view are left untouched).
