@@ -20,12 +20,19 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 OBJ_DIR = os.path.join(_HERE, "build")
 LIB_PATH = os.path.join(_HERE, "libfastrank_amd.so")
-INCLUDE = os.path.join("..", "..", "include", "fastrank.h")
-DEVICE_INCS = ["device.hpp", "dataset_layout.hpp", "linesearch_policy.hpp", "fullverify.hpp", "device_plumbing.inc", "kernels_score.inc", "kernels_tree.inc", "kernels_treerank.inc", "kernels_metric.inc",
-               "kernels_linesearch.inc", "kernels_chain.inc", "kernels_fillnet.inc", "kernels_order.inc", "kernels_verify.inc", "kernels_fullrank.inc", "kernels_rr.inc", "kernels_rf.inc", "kernels_lambda.inc", "kernels_hist.inc", "kernels_dart.inc", "device_dataset.inc", "rccl_exchange.inc"]
-FV_INCS = ["device.hpp", "fullverify.hpp", "kernels_sortnet.inc", "kernels_fullverify.inc"]
-EXPLAIN_INCS = ["explain.hpp"]
-HOST_INCS = ["device.hpp", "dataset_layout.hpp", "host.hpp", "loader.hpp", "rf_train.hpp", "lambdamart.hpp", "lambdamart_dart.hpp", "lambdamart_hist.hpp", "explain.hpp", "explain_host.hpp", "json.hpp", INCLUDE]
+
+
+def _deps(src, seen=None):
+    """Everything `src` includes, directly or through what it includes: its #include "..." lines (those behind #if too: a
+    superset is harmless) resolved against the including file, as paths relative to CSRC in the order first met.  Derived
+    from the sources, so that a new header cannot be left out of the digests below."""
+    seen = [] if seen is None else seen
+    for inc in re.findall(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', open(os.path.join(CSRC, src)).read(), re.M):
+        name = os.path.normpath(os.path.join(os.path.dirname(src), inc))
+        if name not in seen and os.path.exists(os.path.join(CSRC, name)):
+            seen.append(name)
+            _deps(name, seen)
+    return seen
 
 
 def fv_parts() -> int:
@@ -35,10 +42,9 @@ def fv_parts() -> int:
 
 def units():
     """(object name, source, extra flags, dependencies)"""
-    out = [("device.o", "device.hip", [], DEVICE_INCS), ("capi.o", "capi.cpp", [], HOST_INCS), ("explain.o", "explain.hip", [], EXPLAIN_INCS)]
-    for k in range(fv_parts()):
-        out.append(("fullverify_%d.o" % k, "fullverify.hip", ["-DFV_PART=%d" % k], FV_INCS))
-    return out
+    out = [("device.o", "device.hip", []), ("capi.o", "capi.cpp", []), ("explain.o", "explain.hip", [])]
+    out += [("fullverify_%d.o" % k, "fullverify.hip", ["-DFV_PART=%d" % k]) for k in range(fv_parts())]
+    return [(obj, src, extra, _deps(src)) for obj, src, extra in out]
 
 
 # -ffp-contract=off is a correctness flag, not a tuning flag: the reference's dot product is an

@@ -34,7 +34,12 @@
 //                           tables, duplicate groups, walk tiles, a view's tables
 //   linesearch_policy.hpp   (host only, no HIP) the adaptive policies of the bound-and-verify line search: routing / back-off of
 //                           tie-heavy restarts, the R-rank refresh schedule, list length, redo grid, skip counter
-//   device_dataset.inc      DeviceDataset: the uploads of that layout (tiles, tables) and every launcher
+//   device_dataset.inc      DeviceDataset: its state (Impl), the scoring, tree and metric launchers, the whole line search; includes
+//     dataset_build.inc       the uploads of that layout (tiles, tables): create, replicate, views
+//     train_rf.inc            the launchers of kernels_rf.inc
+//     train_lambda.inc        the launchers of kernels_lambda.inc
+//     train_dart.inc          the launchers of kernels_dart.inc
+//     train_hist.inc          the launchers of kernels_hist.inc, level-wise and leaf-wise
 #include "device.hpp"
 
 #include <hip/hip_runtime.h>

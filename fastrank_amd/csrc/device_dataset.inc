@@ -1,4 +1,7 @@
-// Part of device.hip (single translation unit; see that file's header).  DeviceDataset: HBM layout construction and every kernel launcher.
+// Part of device.hip (single translation unit; see that file's header).  DeviceDataset: its state (Impl), the scoring, tree and metric
+// launchers and the line search.  The dataset build (dataset_build.inc) and the trainers' launchers (train_*.inc) are included at the
+// places their text had.  The scoring, tree-launch and line-search code stays in this file because bench.py keys its static counter
+// captures to this file's hash: moved out, it could change without marking those captures stale.
 // ----------------------------------------------------------------------------------------------
 // DeviceDataset
 // ----------------------------------------------------------------------------------------------
@@ -369,8 +372,11 @@ struct DeviceDataset::Impl : DatasetDesc {
     } hist;
     bool hist_items(const std::vector<HistItemDev>& stretches, std::vector<HistItemDev>& host, DevBuf<HistItemDev>& dev, std::string* err);
     bool hist_qof(std::string* err);
-    void hist_build(uint32_t* cnt, unsigned long long* sum);  // hist_build_kernel over hist.items_b into a level's histograms
-    void hist_build_newton(uint32_t* cnt, unsigned long long* sum, unsigned long long* wsum);
+    // histograms as (cnt, sum, wsum) arrays; wsum == nullptr: the plain gain, which keeps no third array
+    void hist_build(uint32_t* cnt, unsigned long long* sum, unsigned long long* wsum);  // over hist.items_b into a level's histograms
+    bool hist_zero(uint32_t* cnt, unsigned long long* sum, unsigned long long* wsum, size_t off, size_t cells, std::string* err);
+    bool hist_flag_scan(uint32_t begin, uint32_t count, std::string* err);  // hist.scan = exclusive prefix sums of hist.flag over [begin, begin + count)
+    bool hist_stage_nodes(const std::vector<DeviceDataset::HistNode>& nodes, bool newton, std::string* err);
     bool hist_leaf_scan(const HistLeafKids& kids, uint32_t count, const DeviceDataset::HistLeafSearch& how, DeviceDataset::HistPick* out,
                         std::string* err, const HistLeafBoundsDev* bounds = nullptr);
     DevBuf<uint64_t> forest;
@@ -467,673 +473,7 @@ int DeviceDataset::take_flags() {
     return v;
 }
 
-template <typename T>
-static bool upload(DevBuf<T>& buf, const std::vector<T>& host, std::string* err) {
-    if (!buf.ensure(std::max<size_t>(host.size(), 1), err)) return false;
-    if (!host.empty()) FR_HIP(hipMemcpy(buf.p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
-    return true;
-}
-
-static std::shared_ptr<DeviceDataset> fail_ds(std::string* err, const std::string& msg) {
-    if (err) *err = msg;
-    return std::shared_ptr<DeviceDataset>();
-}
-static bool hip_ok(hipError_t e, const char* what, std::string* err) {
-    if (e == hipSuccess) return true;
-    if (err) *err = std::string("HIP error: ") + hipGetErrorString(e) + " at " + what;
-    return false;
-}
-struct ThreadJoiner {  // joins on every way out of create()
-    std::thread& t;
-    ~ThreadJoiner() { if (t.joinable()) t.join(); }
-};
-// documents a run takes (FR_RUN_DOCS: tuning sweeps)
-size_t run_docs_target() {
-    const char* t = frdev::pricing_env("FR_RUN_DOCS");
-    return t ? std::max<size_t>(64, (size_t)atoll(t)) : 768;
-}
-
-// Returns the first error; *at_event: it was the event's.  main_stream hears of the main stream before the others are made.
-hipError_t DeviceDataset::Impl::open_streams(bool* at_event, StreamSignal* main_stream) {
-    hipError_t e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
-    if (main_stream) main_stream->set(e == hipSuccess);
-    for (int i = 0; i < LS_CONTEXTS && e == hipSuccess; i++) e = hipStreamCreateWithFlags(&ls[i].stream, hipStreamNonBlocking);
-    if (e != hipSuccess) return e;
-    e = hipEventCreateWithFlags(&res_ready, hipEventDisableTiming);
-    *at_event = e != hipSuccess;
-    return e;
-}
-bool DeviceDataset::Impl::open_streams(std::string* err) {
-    bool at_event = false;
-    const hipError_t e = open_streams(&at_event);
-    return hip_ok(e, at_event ? "hipEventCreate" : "hipStreamCreate", err);
-}
-
-// The feature tiles, on create()'s tile thread and the main stream while the caller builds and uploads the per-position tables.
-bool DeviceDataset::Impl::upload_tiles(Impl& m, const HostCSR& csr, bool timing, StreamSignal& main_stream, std::string* terr) {
-    if (hipSetDevice(m.device) != hipSuccess) {
-        *terr = "hipSetDevice failed in the upload thread";
-        return false;
-    }
-    auto tchk = [&](hipError_t e, const char* what) { return hip_ok(e, what, terr); };
-    auto tt = std::chrono::steady_clock::now();
-    double t_fill = 0.0, t_wait = 0.0;  // (FR_UPLOAD_TIMING: the tile thread's own stages)
-    auto tlap = [&](const char* what) {
-        if (!timing) return;
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[upload/tiles] %-36s %7.1f ms\n", what, std::chrono::duration<double, std::milli>(now - tt).count());
-        tt = now;
-    };
-    // ---- feature tiles.  The host only streams the view's rows, row-major as they lie in the caller's matrix, through two
-    // pinned slabs (plain memcpy by a pool of threads while the previous slab is on the wire); tile_scatter_kernel moves
-    // every row to its padded position in the tile layout and takes the per-column max |x| and the non-finite flag on
-    // the way.  One-time cost; SURVEY 8d excludes it from evals/s and bench.py reports it separately.
-    const size_t ntiles = m.np / 64;
-    const size_t tile_floats = m.dq * 256;
-    if (!m.xb.ensure(ntiles * tile_floats, terr)) return false;
-    {
-        if (!main_stream.wait()) {  // (created by the helper thread)
-            *terr = "HIP error: hipStreamCreate failed";
-            return false;
-        }
-        if (!tchk(hipMemsetAsync(m.xb.p, 0, ntiles * tile_floats * sizeof(float), m.stream), "clear feature tiles")) return false;
-        // rows of the view in ascending row id (sequential reads of the caller's matrix) and where each one goes
-        uint32_t maxrow = 0;
-        for (size_t t = 0; t < csr.n; t++) maxrow = std::max(maxrow, csr.perm[t]);
-        std::vector<uint32_t> pos_of_row((size_t)maxrow + 1, IDX_INVALID);
-        for (size_t p = 0; p < m.np; p++)
-            if (m.perm_host[p] != IDX_INVALID) pos_of_row[m.perm_host[p]] = (uint32_t)p;
-        std::vector<uint32_t> rows, row_dst;
-        rows.reserve(csr.n);
-        row_dst.reserve(csr.n);
-        for (size_t id = 0; id <= maxrow; id++)
-            if (pos_of_row[id] != IDX_INVALID) {
-                rows.push_back((uint32_t)id);
-                row_dst.push_back(pos_of_row[id]);
-            }
-        tlap("clear tiles queued, row lists");
-        DevBuf<uint32_t> d_dst, d_colmax;
-        DevBuf<float> d_stage[2];
-        DevBuf<int> d_bad;
-        const size_t row_bytes = csr.d * sizeof(float);
-        size_t slab_mb = 32;
-        if (const char* e = frdev::pricing_env("FR_UPLOAD_SLAB_MB")) slab_mb = std::max(1, std::atoi(e));
-        const size_t slab_rows = std::max<size_t>(1, std::min<size_t>(rows.size(), (slab_mb << 20) / row_bytes));
-        if (!upload(d_dst, row_dst, terr) || !d_colmax.ensure(csr.d, terr) || !d_bad.ensure(1, terr) ||
-            !d_stage[0].ensure(slab_rows * csr.d, terr) || !d_stage[1].ensure(slab_rows * csr.d, terr))
-            return false;
-        if (!tchk(hipMemsetAsync(d_colmax.p, 0, csr.d * sizeof(uint32_t), m.stream), "clear column maxima") ||
-            !tchk(hipMemsetAsync(d_bad.p, 0, sizeof(int), m.stream), "clear flags"))
-            return false;
-        float* slabs[2] = {nullptr, nullptr};
-        hipEvent_t done[2] = {nullptr, nullptr};
-        bool pinned = hipHostMalloc((void**)&slabs[0], slab_rows * row_bytes, hipHostMallocDefault) == hipSuccess &&
-                      hipHostMalloc((void**)&slabs[1], slab_rows * row_bytes, hipHostMallocDefault) == hipSuccess &&
-                      hipEventCreateWithFlags(&done[0], hipEventDisableTiming) == hipSuccess &&
-                      hipEventCreateWithFlags(&done[1], hipEventDisableTiming) == hipSuccess;
-        std::vector<float> pageable;
-        if (!pinned) {  // (no pinned memory left: one pageable slab, synchronous copies)
-            (void)hipGetLastError();
-            for (int i = 0; i < 2; i++) {
-                if (slabs[i]) (void)hipHostFree(slabs[i]);
-                if (done[i]) (void)hipEventDestroy(done[i]);
-                slabs[i] = nullptr;
-                done[i] = nullptr;
-            }
-            pageable.resize(slab_rows * csr.d);
-            slabs[0] = slabs[1] = pageable.data();
-        }
-        auto release = [&]() {
-            if (!pinned) return;
-            for (int i = 0; i < 2; i++) {
-                (void)hipHostFree(slabs[i]);
-                (void)hipEventDestroy(done[i]);
-            }
-        };
-        tlap("staging buffers, pinned slabs");
-        unsigned hw = std::thread::hardware_concurrency();
-        size_t want_threads = 12;
-        if (const char* e = frdev::pricing_env("FR_UPLOAD_THREADS")) want_threads = std::max(1, std::atoi(e));
-        const size_t nthreads = std::max<size_t>(1, std::min<size_t>(hw ? hw : 1, rows.size() > 100000 ? want_threads : 1));
-        bool used[2] = {false, false};
-        size_t turn = 0;
-        for (size_t k0 = 0; k0 < rows.size(); k0 += slab_rows, turn ^= 1) {
-            const size_t kn = std::min(slab_rows, rows.size() - k0);
-            float* slab = slabs[turn];
-            // (the slab's previous copy AND the kernel that read its staging buffer are behind this event)
-            const auto w0 = std::chrono::steady_clock::now();
-            if (pinned && used[turn] && !tchk(hipEventSynchronize(done[turn]), "upload feature rows")) {
-                release();
-                return false;
-            }
-            const auto w1 = std::chrono::steady_clock::now();
-            t_wait += std::chrono::duration<double, std::milli>(w1 - w0).count();
-            auto work = [&](size_t tid) {
-                const size_t b0 = k0 + kn * tid / nthreads, b1 = k0 + kn * (tid + 1) / nthreads;
-                for (size_t k = b0; k < b1;) {
-                    size_t e = k + 1;  // a run of consecutive row ids is one memcpy
-                    while (e < b1 && rows[e] == rows[e - 1] + 1) e++;
-                    std::memcpy(slab + (k - k0) * csr.d, csr.x + (size_t)rows[k] * csr.d, (e - k) * row_bytes);
-                    k = e;
-                }
-            };
-            std::vector<std::thread> pool;
-            for (size_t tid = 1; tid < nthreads; tid++) pool.emplace_back(work, tid);
-            work(0);
-            for (auto& th : pool) th.join();
-            t_fill += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w1).count();
-            bool ok = pinned ? tchk(hipMemcpyAsync(d_stage[turn].p, slab, kn * row_bytes, hipMemcpyHostToDevice, m.stream), "upload feature rows")
-                             : tchk(hipMemcpy(d_stage[turn].p, slab, kn * row_bytes, hipMemcpyHostToDevice), "upload feature rows");
-            if (ok) {
-                const size_t work_items = kn * m.dq;
-                tile_scatter_kernel<<<dim3((unsigned)std::min<size_t>((work_items + 255) / 256, 65535)), 256, 4 * m.dq * sizeof(uint32_t), m.stream>>>(
-                    d_stage[turn].p, (uint32_t)kn, (uint32_t)csr.d, (uint32_t)m.dq, d_dst.p + k0, m.xb.p, d_colmax.p, d_bad.p);
-                ok = tchk(hipGetLastError(), "tile_scatter_kernel");
-            }
-            if (ok && pinned) {
-                ok = tchk(hipEventRecord(done[turn], m.stream), "upload feature rows");
-                used[turn] = true;
-            }
-            if (!ok) {
-                release();
-                return false;
-            }
-        }
-        tlap("slab loop (fill + queue + waits)");
-        if (timing) fprintf(stderr, "[upload/tiles]   of which filling the slabs %.1f ms, waiting for a slab's turn %.1f ms (%u threads)\n", t_fill, t_wait, (unsigned)nthreads);
-        std::vector<uint32_t> colbits(csr.d, 0);
-        int bad = 0;
-        const bool ok = tchk(hipMemcpyAsync(colbits.data(), d_colmax.p, csr.d * sizeof(uint32_t), hipMemcpyDeviceToHost, m.stream), "column maxima") &&
-                        tchk(hipMemcpyAsync(&bad, d_bad.p, sizeof(int), hipMemcpyDeviceToHost, m.stream), "flags") &&
-                        tchk(hipStreamSynchronize(m.stream), "upload feature rows");
-        tlap("last copies + scatter kernels drained");
-        release();
-        if (!ok) return false;
-        m.nonfinite = bad != 0;
-        m.colmax.assign(csr.d, 0.0);
-        for (size_t j = 0; j < csr.d; j++) {
-            float f;
-            std::memcpy(&f, &colbits[j], sizeof(f));
-            m.colmax[j] = colbits[j] >= 0x7F800000u ? (double)std::numeric_limits<float>::infinity() : (double)f;
-        }
-    }
-    return true;
-}
-
-std::shared_ptr<DeviceDataset> DeviceDataset::create(const HostCSR& csr, std::string* err) {
-    std::string e2;
-    if (device_count(&e2) <= 0)
-        return fail_ds(err, "no MI355X/HIP device available for the fastrank_amd compute path (" +
-                                (e2.empty() ? std::string("device count is 0") : e2) + ")");
-    if (csr.n == 0 || csr.d == 0 || csr.nq == 0) return fail_ds(err, "empty dataset");
-    if (csr.n >= 0xF0000000ull) return fail_ds(err, "dataset too large for 32-bit document positions");
-    std::shared_ptr<DeviceDataset> ds(new DeviceDataset());
-    Impl& m = *ds->impl_;
-    if (hipGetDevice(&m.device) != hipSuccess) return fail_ds(err, "hipGetDevice failed");
-    // FR_UPLOAD_TIMING=1: stage times of the one-time upload on stderr
-    const bool timing = std::getenv("FR_UPLOAD_TIMING") != nullptr;
-    auto tclock = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!timing) return;
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[upload] %-28s %7.1f ms\n", what, std::chrono::duration<double, std::milli>(now - tclock).count());
-        tclock = now;
-    };
-    // A stream costs ~20 ms to create (a hardware queue each) and the process's first one ~80 ms (the runtime's first touch of
-    // the device): 96 ms for the five of them used to be the largest single stage of the upload
-    // (profiles/r05_upload_stages.txt).  A helper thread creates them -- the main stream first: the tile thread waits for it,
-    // nothing else needs it before the tiles are up -- while this thread builds the host-side tables; the line-search
-    // contexts' streams are not needed before the first tick.  Joined before create() returns.
-    std::string serr;  // (written by the helper thread, read after its join)
-    StreamSignal main_stream;
-    std::thread stream_thread([&]() {
-        hipError_t e = hipSetDevice(m.device);
-        bool at_event = false;
-        if (e == hipSuccess) e = m.open_streams(&at_event, &main_stream);
-        else main_stream.set(false);
-        if (e != hipSuccess) {
-            std::lock_guard<std::mutex> lk(main_stream.mu);
-            main_stream.ok = false;
-            serr = std::string("HIP error: ") + hipGetErrorString(e) + " at hipStreamCreate";
-        }
-    });
-    ThreadJoiner stream_joiner{stream_thread};
-    m.n = csr.n;
-    m.d = csr.d;
-    m.nq = csr.nq;
-    m.dq = (csr.d + 3) / 4;
-
-    lap("helper thread started (streams)");
-    RunPlan runs;
-    if (!plan_runs(csr.qoff, m.nq, run_docs_target(), &runs, err)) return nullptr;
-    m.maxlen = runs.maxlen;
-    m.np = runs.np;
-    m.nruns = runs.run_q0.size();
-    // size classes for the general (sort) evaluator, and of the full-ranking bound-and-verify kernel
-    // (kernels_fullverify.inc): every query goes to the cheapest (keys per lane, lanes per candidate) class that holds it
-    std::vector<uint32_t> qlist, fv_qlist;
-    m.size_classes = bucket_queries(runs.qlen, pow2_from_64, &qlist);
-    m.fv_classes = fv_build_classes(runs.qlen, &fv_qlist);
-
-    lap("runs, size classes");
-    m.perm_host = position_map(csr, runs.qstart, runs.qlen, m.np);
-    // (runs on its own thread and stream while this thread builds and uploads the per-position tables below)
-    std::string terr;  // (written by the tile thread, read after its join)
-    bool tiles_ok = false;
-    std::thread tile_thread([&]() { tiles_ok = Impl::upload_tiles(m, csr, timing, main_stream, &terr); });
-    ThreadJoiner tile_joiner{tile_thread};
-    GainTables gt;
-    position_gains(csr, runs.qstart, runs.qlen, m.np, &gt);
-    m.labels_small_int = gt.labels_small_int;
-
-    lap("perm / gain / gexp");
-    gain_classes(m.perm_host, &gt);
-    m.relmask = gt.relmask;
-
-    lap("gain classes, dcgtab");
-    term_tables(runs.qstart, runs.qlen, m.maxlen, &gt);
-    m.ncls = gt.ncls;
-    m.tablen = gt.tablen;
-
-    lap("per-position tables (host)");
-    {
-        size_t nd = std::max<size_t>(m.maxlen, 64);
-        std::vector<double> disc(nd);
-        for (size_t i = 0; i < nd; i++) disc[i] = std::log2((double)i + 2.0);
-        if (!upload(m.disc, disc, err) || !upload(m.gexp, gt.gexp, err) || !upload(m.gain, gt.gain, err) ||
-            !upload(m.qstart, runs.qstart, err) || !upload(m.qlen, runs.qlen, err) || !upload(m.qtight, runs.qtight, err) ||
-            !upload(m.perm, m.perm_host, err) || !upload(m.run_q0, runs.run_q0, err) || !upload(m.run_q1, runs.run_q1, err) ||
-            !upload(m.run_pos, runs.run_pos, err) || !upload(m.run_docs, runs.run_docs, err) ||
-            !upload(m.run_order, runs.run_order, err) || !upload(m.run_lo, std::vector<uint32_t>(m.nruns, 0u), err) ||
-            !upload(m.gcls, gt.gcls, err) || !upload(m.dcgtab, gt.dcgtab, err) ||
-            !upload(m.qlist, qlist, err) || !upload(m.fv_qlist, fv_qlist, err) || !upload(m.qnpos, gt.qnpos, err) ||
-            !upload(m.qnneg, gt.qnneg, err) ||
-            !upload(m.termtab, gt.termtab, err))
-            return nullptr;
-        if (!m.flags.ensure(1, err) || !m.dbgc.ensure(4, err)) return nullptr;
-        if (!hip_ok(hipMemset(m.flags.p, 0, sizeof(int)), "clear flags", err)) return nullptr;
-        m.qstart_h = runs.qstart;
-        m.qlen_h = runs.qlen;
-        m.qnpos_h = gt.qnpos;
-        m.qnneg_h = gt.qnneg;
-    }
-    lap("small tables H2D");
-    tile_thread.join();
-    if (!tiles_ok) return fail_ds(err, terr);
-    lap("feature rows H2D + device tiling (remaining wait)");
-    {
-        // duplicate groups (dataset_layout.hpp: duplicate_groups) from a 64-bit hash of every document's feature row,
-        // computed on the device from the tiles just uploaded
-        std::vector<uint64_t> row_hash(m.np, 0);
-        {
-            DevBuf<uint64_t> d_hash;
-            if (!d_hash.ensure(m.np, err)) return nullptr;
-            row_hash_kernel<<<dim3((unsigned)((m.np + 255) / 256)), 256, 0, m.stream>>>((const float4*)m.xb.p, (uint32_t)m.np, (uint32_t)m.dq, d_hash.p);
-            if (!hip_ok(hipGetLastError(), "row_hash_kernel", err) ||
-                !hip_ok(hipMemcpyAsync(row_hash.data(), d_hash.p, m.np * sizeof(uint64_t), hipMemcpyDeviceToHost, m.stream), "row hashes", err) ||
-                !hip_ok(hipStreamSynchronize(m.stream), "row hashes", err))
-                return nullptr;
-        }
-        unsigned hw = std::thread::hardware_concurrency();
-        const size_t nthreads = std::max<size_t>(1, std::min<size_t>(hw ? hw : 1, m.np > 200000 ? 16 : 1));
-        const DupGroups dg = duplicate_groups(row_hash, csr, m.perm_host, runs.qstart, runs.qlen, gt.gcls, gt.cls_gain.size(),
-                                              frdev::path_env("FR_NO_DUP_GROUPS") != nullptr, nthreads);
-        m.dup_groups = dg.dup_groups;
-        m.key_bits = dg.key_bits;
-        m.key_cls_bits = dg.key_cls_bits;
-        m.verify_xs = dg.verify_xs;
-        if (!upload(m.gkey, dg.gkey16, err)) return nullptr;
-    }
-    lap("duplicate groups (device hash, host grouping)");
-    {
-        // the walk tiles (kernels_order.inc; build_walk_tiles), then the (query, walk tile) segment of every position and the
-        // static visiting-order tables
-        WalkTileLayout wl = build_walk_tiles(runs.run_pos, runs.run_q0, runs.run_q1, runs.qstart, runs.qlen, m.np);
-        m.wt_start_h = std::move(wl.wt_start);
-        m.nwt = m.wt_start_h.size() - 1;
-        if (!upload(m.segtab, wl.seg, err) || !upload(m.wt_start, m.wt_start_h, err) || !upload(m.run_wt0, wl.run_wt0, err) || !upload(m.wofs, wl.wofs, err)) return nullptr;
-        if (!m.build_order_tables(err)) return nullptr;
-        if (!m.build_columns(err)) return nullptr;
-    }
-    lap("visiting-order tables (device)");
-    stream_thread.join();
-    if (!main_stream.ok) return fail_ds(err, serr);
-    lap("line-search streams (helper thread, remaining wait)");
-    return ds;
-}
-
-// One line on stderr, once per process and message, when an optional device copy could not be made and a slower path takes
-// over (results are the same; INTEGRATION.md section 6 lists what a dataset takes in HBM).
-static void warn_degraded(const char* what) {
-    static std::mutex mu;
-    static std::vector<std::string> said;
-    std::lock_guard<std::mutex> lk(mu);
-    for (const std::string& s : said)
-        if (s == what) return;
-    said.emplace_back(what);
-    fprintf(stderr, "[fastrank_amd] warning: %s\n", what);
-}
-
-// xslot + the column statistics of the host's lane-class rule, from the tiles (a dataset that owns its matrix).
-// FR_VERIFY_ORDER=0, or no HBM for the table (a quarter of the tiles' size): the verify kernel walks in storage order.
-bool DeviceDataset::Impl::build_order_tables(std::string* err) {
-    Impl& m = *this;
-    const char* oe = std::getenv("FR_VERIFY_ORDER");
-    if ((oe != nullptr && oe[0] == '0') || m.nonfinite || m.dq * 4 > 2048) return true;
-    {
-        std::string e2;
-        if (!m.xslot.ensure(m.d * m.np, &e2)) {
-            (void)hipGetLastError();
-            warn_degraded("no HBM for the visiting-order tables (a quarter of the matrix): the NDCG@k verify kernel walks in storage order");
-            return true;
-        }
-    }
-    const uint32_t ntiles = (uint32_t)(m.np / 64);
-    {
-        ProfScope ps("xslot_kernel", m.stream);
-        xslot_kernel<<<dim3((unsigned)m.nwt, (unsigned)((m.dq + ORDER_OQ - 1) / ORDER_OQ)), WAVE, 0, m.stream>>>(
-            (const float4*)m.xb.p, m.segtab.p, m.wt_start.p, (uint32_t)m.np, (uint32_t)m.dq, (uint32_t)m.d, m.xslot.p);
-    }
-    FR_HIP(hipGetLastError());
-    std::vector<ColStats> init(m.d);
-    for (ColStats& c : init) {
-        c.sum = c.sumsq = 0.0;
-        c.mn = std::numeric_limits<float>::infinity();
-        c.mx = -std::numeric_limits<float>::infinity();
-        c.at_min = c.at_max = 0;
-    }
-    DevBuf<ColStats> dst;
-    if (!upload(dst, init, err)) return false;
-    for (int pass = 0; pass < 2; pass++)
-        colstats_kernel<<<dim3(128, (unsigned)m.dq), 256, 0, m.stream>>>((const float4*)m.xb.p, m.segtab.p, ntiles, (uint32_t)m.dq, (uint32_t)m.d, pass, dst.p);
-    FR_HIP(hipGetLastError());
-    FR_HIP(hipMemcpyAsync(init.data(), dst.p, m.d * sizeof(ColStats), hipMemcpyDeviceToHost, m.stream));
-    FR_HIP(hipStreamSynchronize(m.stream));
-    m.colstd.assign(m.d, 0.0);
-    m.colmode.assign(m.d, 0);
-    const double nd = (double)std::max<size_t>(m.n, 1);
-    for (size_t j = 0; j < m.d; j++) {
-        const double mean = init[j].sum / nd, var = init[j].sumsq / nd - mean * mean;
-        m.colstd[j] = var > 0.0 ? std::sqrt(var) : 0.0;
-        m.colmode[j] = (uint8_t)(((double)init[j].at_max > 0.1 * nd ? 1 : 0) | ((double)init[j].at_min > 0.1 * nd ? 2 : 0));
-    }
-    m.colstats_h = std::move(init);
-    return true;
-}
-
-// The column-major copy of the tiles (kernels_order.inc: xcol_kernel): as large as the matrix again -- HBM is what this
-// device has.  FR_XCOL=0, or no room for it: the resident line search reads its column out of the tiles.
-bool DeviceDataset::Impl::build_columns(std::string* err) {
-    Impl& m = *this;
-    const char* xe = std::getenv("FR_XCOL");
-    if ((xe != nullptr && xe[0] == '0') || m.np == 0 || m.d == 0) return true;
-    {
-        std::string e2;
-        if (!m.xcol.ensure(m.d * m.np, &e2)) {
-            (void)hipGetLastError();
-            warn_degraded("no HBM for the column-major copy of the matrix (as large as the matrix again): coordinate ascent runs without "
-                          "resident sums -- every line search forms its sums from the tiles, several times slower");
-            return true;
-        }
-    }
-    ProfScope ps("xcol_kernel", m.stream);
-    xcol_kernel<<<dim3((unsigned)(m.np / 64), (unsigned)((m.dq + ORDER_OQ - 1) / ORDER_OQ)), WAVE, 0, m.stream>>>((const float4*)m.xb.p, (uint32_t)m.np,
-                                                                                                               (uint32_t)m.dq, (uint32_t)m.d, m.xcol.p);
-    FR_HIP(hipGetLastError());
-    return true;
-}
-
-bool DeviceDataset::shares_parent_matrix() const { return (bool)impl_->parent; }
-
-// ---- read-back of the device form (device.hpp: for the tests that hold every table to its definition) ------------------
-std::vector<std::pair<std::string, uint64_t>> DeviceDataset::debug_form_scalars() const {
-    const Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(impl_->mu);
-    auto addr = [](const auto& b) { return (uint64_t) reinterpret_cast<uintptr_t>(b.p); };
-    return {{"np", m.np}, {"dq", m.dq}, {"d", m.d}, {"n", m.n}, {"nq", m.nq}, {"nonfinite", m.nonfinite ? 1u : 0u},
-            {"nruns", m.nruns}, {"nwt", m.nwt}, {"nvtiles", m.nvtiles}, {"nwlist", m.nwlist}, {"maxlen", m.maxlen},
-            {"ncls", m.ncls}, {"key_bits", m.key_bits}, {"key_cls_bits", m.key_cls_bits}, {"dup_groups", m.dup_groups},
-            {"no_document", IDX_INVALID}, {"walk_tile", WT}, {"dcg_ranks", (uint64_t)LS_KT}, {"colstats_bytes", sizeof(ColStats)},
-            {"shares_parent_matrix", m.parent ? 1u : 0u}, {"device", (uint64_t)m.device},
-            // (addresses, to be compared and never followed: a view's tables ARE its parent's)
-            {"xb_addr", addr(m.xb)}, {"xcol_addr", addr(m.xcol)}, {"xslot_addr", addr(m.xslot)}, {"segtab_addr", addr(m.segtab)},
-            {"gkey_addr", addr(m.gkey)}, {"perm_addr", addr(m.perm)}};
-}
-
-bool DeviceDataset::debug_form_table(const std::string& name, std::vector<unsigned char>* out, bool* present, std::string* err) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    // what create() queued last (xcol_kernel) may still be running; a view's tables were written on its parent's stream
-    if (m.parent) FR_HIP(hipStreamSynchronize(m.parent->impl_->stream));
-    FR_HIP(hipStreamSynchronize(m.stream));
-    out->clear();
-    *present = true;
-    auto dev = [&](const auto& b, size_t count) {  // `count` elements of a device table (absent: an optional copy that was not made)
-        using T = std::remove_pointer_t<decltype(b.p)>;
-        if (b.p == nullptr || count == 0 || count > b.cap) {
-            *present = false;
-            return true;
-        }
-        out->resize(count * sizeof(T));
-        FR_HIP(hipMemcpy(out->data(), b.p, out->size(), hipMemcpyDeviceToHost));
-        return true;
-    };
-    auto host = [&](const auto& v) {
-        using T = typename std::remove_reference_t<decltype(v)>::value_type;
-        if (v.empty()) {
-            *present = false;
-            return true;
-        }
-        out->resize(v.size() * sizeof(T));
-        std::memcpy(out->data(), v.data(), out->size());
-        return true;
-    };
-    if (name == "xb") return dev(m.xb, m.np / 64 * m.dq * 256);
-    if (name == "xcol") return dev(m.xcol, m.d * m.np);
-    if (name == "xslot") return dev(m.xslot, m.d * m.np);
-    if (name == "perm") return dev(m.perm, m.np);
-    if (name == "perm_host") return host(m.perm_host);
-    if (name == "gain") return dev(m.gain, m.np);
-    if (name == "gexp") return dev(m.gexp, m.np);
-    if (name == "gcls") return dev(m.gcls, m.np);
-    if (name == "gkey") return dev(m.gkey, m.np);
-    if (name == "segtab") return dev(m.segtab, m.np);
-    if (name == "wofs") return dev(m.wofs, m.np);
-    if (name == "wt_start") return dev(m.wt_start, m.nwt + 1);
-    if (name == "qstart") return dev(m.qstart, m.nq);
-    if (name == "qlen") return dev(m.qlen, m.nq);
-    if (name == "qtight") return dev(m.qtight, m.nq + 1);
-    if (name == "run_q0") return dev(m.run_q0, m.nruns);
-    if (name == "run_q1") return dev(m.run_q1, m.nruns);
-    if (name == "run_pos") return dev(m.run_pos, m.nruns);
-    if (name == "run_docs") return dev(m.run_docs, m.nruns);
-    if (name == "run_lo") return dev(m.run_lo, m.nruns);
-    if (name == "run_order") return dev(m.run_order, m.nruns);
-    if (name == "run_wt0") return dev(m.run_wt0, m.nruns);
-    if (name == "vtiles") return dev(m.vtiles, m.nvtiles);
-    if (name == "wlist") return dev(m.wlist, m.nwlist);
-    if (name == "dcgtab") return dev(m.dcgtab, m.ncls * LS_KT);
-    if (name == "colmax") return host(m.colmax);
-    if (name == "colstd") return host(m.colstd);
-    if (name == "colmode") return host(m.colmode);
-    if (name == "colstats") return host(m.colstats_h);
-    if (err) *err = "debug_form_table: no table named " + name;
-    return false;
-}
-
-// A second copy of a dataset that owns its matrix, on another device (or a second context on the same one): everything
-// create() built -- the feature tiles, the per-position and per-query tables -- is copied device to device
-// (hipMemcpyPeer: over xGMI between two GPUs of a node), nothing is uploaded or recomputed from the host's matrix.
-// The copy starts with empty work buffers and its own streams.  This is how train_model spreads the restarts of one
-// request over the GPUs of a node (src/coordinate_ascent.rs:215-225 does it with rayon over the host's cores).
-std::shared_ptr<DeviceDataset> DeviceDataset::replicate(const std::shared_ptr<DeviceDataset>& src, int device, std::string* err) {
-    if (!src || src->impl_->parent) return fail_ds(err, "replicate: the source must own its matrix");
-    Impl& sm = *src->impl_;
-    // (no lock on the source for the copies: what create() left in HBM and its host-side description never change
-    // afterwards, so the callers' threads -- one per destination -- really copy at the same time, each peer reading
-    // the source over its own link; the source may run kernels of its own meanwhile)
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail_ds(err, "replicate: no such device");
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    struct Restore {
-        int d;
-        ~Restore() { (void)hipSetDevice(d); }
-    } restore{prev};
-    if (hipSetDevice(device) != hipSuccess) return fail_ds(err, "replicate: hipSetDevice failed");
-    if (device != sm.device) {  // direct peer copies where the link allows them (otherwise the runtime stages through the host)
-        int can = 0;
-        if (hipDeviceCanAccessPeer(&can, device, sm.device) == hipSuccess && can) {
-            const hipError_t e = hipDeviceEnablePeerAccess(sm.device, 0);
-            if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) (void)hipGetLastError();
-            (void)hipGetLastError();
-        }
-    }
-    std::shared_ptr<DeviceDataset> ds(new DeviceDataset());
-    Impl& m = *ds->impl_;
-    m.device = device;
-    if (!m.open_streams(err)) return nullptr;
-    // ---- host-side description: everything, as the source holds it now (verify_xs included: whatever its trainers raised it
-    // to).  What is not part of it keeps its default: a replica has no parent and visits its whole position space (nvtiles = 0).
-    static_cast<DatasetDesc&>(m) = sm;
-    // ---- everything create() left in HBM, device to device
-    bool ok = true;
-    auto copy = [&](auto& dst, const auto& from, const char* what) {
-        if (!ok || from.p == nullptr || from.cap == 0) return;
-        if (!dst.ensure(from.cap, err)) {
-            ok = false;
-            return;
-        }
-        ok = hip_ok(hipMemcpyPeerAsync(dst.p, device, from.p, sm.device, from.bytes(), m.stream), what, err);
-    };
-    copy(m.xb, sm.xb, "replicate feature tiles");
-    copy(m.gain, sm.gain, "replicate gain");
-    copy(m.gexp, sm.gexp, "replicate gexp");
-    copy(m.disc, sm.disc, "replicate disc");
-    copy(m.qstart, sm.qstart, "replicate qstart");
-    copy(m.qlen, sm.qlen, "replicate qlen");
-    copy(m.qtight, sm.qtight, "replicate qtight");
-    copy(m.perm, sm.perm, "replicate perm");
-    copy(m.run_q0, sm.run_q0, "replicate run_q0");
-    copy(m.run_q1, sm.run_q1, "replicate run_q1");
-    copy(m.run_pos, sm.run_pos, "replicate run_pos");
-    copy(m.run_docs, sm.run_docs, "replicate run_docs");
-    copy(m.run_order, sm.run_order, "replicate run_order");
-    copy(m.run_lo, sm.run_lo, "replicate run_lo");
-    copy(m.gcls, sm.gcls, "replicate gcls");
-    copy(m.gkey, sm.gkey, "replicate gkey");
-    copy(m.segtab, sm.segtab, "replicate segtab");
-    copy(m.wt_start, sm.wt_start, "replicate wt_start");
-    copy(m.run_wt0, sm.run_wt0, "replicate run_wt0");
-    copy(m.wofs, sm.wofs, "replicate wofs");
-    // the optional copies (create() itself goes without them when HBM is short): a replica that cannot hold them is a slower
-    // replica, not a failed one -- xcol first, the resident line search cannot do without it
-    auto copy_optional = [&](auto& dst, const auto& from, const char* what, const char* degraded) {
-        if (!ok || from.p == nullptr || from.cap == 0) return;
-        std::string e2;
-        if (!dst.ensure(from.cap, &e2)) {
-            (void)hipGetLastError();
-            warn_degraded(degraded);
-            return;
-        }
-        ok = hip_ok(hipMemcpyPeerAsync(dst.p, device, from.p, sm.device, from.bytes(), m.stream), what, err);
-    };
-    copy_optional(m.xcol, sm.xcol, "replicate xcol", "a device replica has no HBM for the column-major copy of the matrix: its line searches form their sums from the tiles");
-    copy_optional(m.xslot, sm.xslot, "replicate xslot", "a device replica has no HBM for the visiting-order tables: its NDCG@k verify kernel walks in storage order");
-    copy(m.qlist, sm.qlist, "replicate qlist");
-    copy(m.fv_qlist, sm.fv_qlist, "replicate fv_qlist");
-    copy(m.qnpos, sm.qnpos, "replicate qnpos");
-    copy(m.qnneg, sm.qnneg, "replicate qnneg");
-    copy(m.termtab, sm.termtab, "replicate termtab");
-    copy(m.dcgtab, sm.dcgtab, "replicate dcgtab");
-    if (!ok) return nullptr;
-    if (!m.flags.ensure(1, err) || !m.dbgc.ensure(4, err)) return nullptr;
-    if (!hip_ok(hipMemsetAsync(m.flags.p, 0, sizeof(int), m.stream), "clear flags", err) ||
-        !hip_ok(hipStreamSynchronize(m.stream), "replicate", err))
-        return nullptr;
-    return ds;
-}
-
-int DeviceDataset::device_ordinal() const { return impl_->device; }
-
-std::shared_ptr<DeviceDataset> DeviceDataset::create_view(const std::shared_ptr<DeviceDataset>& parent, const HostCSR& csr,
-                                                          const std::vector<uint32_t>& parent_query, std::string* err) {
-    if (!parent || parent->impl_->parent) return fail_ds(err, "create_view: the parent must own its matrix");
-    const Impl& pm = *parent->impl_;
-    if (csr.n == 0 || csr.nq == 0 || parent_query.size() != csr.nq) return fail_ds(err, "create_view: empty view");
-    std::shared_ptr<DeviceDataset> ds(new DeviceDataset());
-    Impl& m = *ds->impl_;
-    m.device = pm.device;
-    if (!hip_ok(hipSetDevice(m.device), "hipSetDevice", err)) return nullptr;
-    if (!m.open_streams(err)) return nullptr;
-    m.parent = parent;
-    m.n = csr.n;
-    m.d = pm.d;
-    m.dq = pm.dq;
-    m.nq = csr.nq;
-    m.np = pm.np;  // the parent's position space
-    m.nonfinite = pm.nonfinite;
-    m.colmax = pm.colmax;  // maxima over a superset of the view's documents: still upper bounds
-    m.ncls = pm.ncls;
-    m.tablen = pm.tablen;
-    m.relmask = pm.relmask;
-    // ---- the view's queries, runs, tiles and walk tiles inside the parent's position space
-    RunPlan v;
-    if (!plan_view_runs(pm.qstart_h, pm.qlen_h, pm.perm_host, pm.wt_start_h, csr, parent_query, run_docs_target(), &v, err)) return nullptr;
-    m.maxlen = v.maxlen;
-    m.perm_host = std::move(v.perm_host);
-    m.nruns = v.run_q0.size();
-    std::vector<uint32_t> qnpos(m.nq), qnneg(m.nq);
-    for (size_t q = 0; q < m.nq; q++) {
-        qnpos[q] = pm.qnpos_h[parent_query[q]];
-        qnneg[q] = pm.qnneg_h[parent_query[q]];
-    }
-    std::vector<uint32_t> qlist, fv_qlist;
-    m.size_classes = bucket_queries(v.qlen, pow2_from_64, &qlist);
-    m.fv_classes = fv_build_classes(v.qlen, &fv_qlist);
-    // ---- shared with the parent: the feature tiles and every per-document / per-class array
-    m.xb.alias(pm.xb);
-    m.gain.alias(pm.gain);
-    m.labels_small_int = pm.labels_small_int;
-    m.gexp.alias(pm.gexp);
-    m.gcls.alias(pm.gcls);
-    m.gkey.alias(pm.gkey);
-    m.xslot.alias(pm.xslot);    // (segments are (query, walk tile) pairs of the parent's position space: the view's queries keep theirs)
-    m.segtab.alias(pm.segtab);
-    m.wt_start.alias(pm.wt_start);
-    m.wofs.alias(pm.wofs);
-    m.wt_start_h = pm.wt_start_h;
-    m.nwt = pm.nwt;
-    m.nwlist = v.wlist.size();
-    m.xcol.alias(pm.xcol);
-    m.colstd = pm.colstd;
-    m.colmode = pm.colmode;
-    m.colstats_h = pm.colstats_h;
-    m.dup_groups = pm.dup_groups;
-    m.key_bits = pm.key_bits;
-    m.key_cls_bits = pm.key_cls_bits;
-    m.verify_xs = pm.verify_xs;
-    m.perm.alias(pm.perm);
-    m.disc.alias(pm.disc);
-    m.dcgtab.alias(pm.dcgtab);
-    m.termtab.alias(pm.termtab);
-    if (!upload(m.qstart, v.qstart, err) || !upload(m.qlen, v.qlen, err) || !upload(m.qtight, v.qtight, err) ||
-        !upload(m.run_q0, v.run_q0, err) || !upload(m.run_q1, v.run_q1, err) || !upload(m.run_pos, v.run_pos, err) ||
-        !upload(m.run_docs, v.run_docs, err) || !upload(m.run_order, v.run_order, err) || !upload(m.run_lo, v.run_lo, err) ||
-        !upload(m.qlist, qlist, err) || !upload(m.fv_qlist, fv_qlist, err) || !upload(m.qnpos, qnpos, err) ||
-        !upload(m.qnneg, qnneg, err) || !upload(m.vtiles, v.vtiles, err) || !upload(m.run_wt0, v.run_wt0, err) || !upload(m.wlist, v.wlist, err))
-        return nullptr;
-    m.nvtiles = frdev::pricing_env("FR_VIEW_ALL_TILES") ? 0 : v.vtiles.size();  // (FR_VIEW_ALL_TILES=1: round 2's behaviour, for A/B runs)
-    if (!m.flags.ensure(1, err) || !m.dbgc.ensure(4, err)) return nullptr;
-    if (!hip_ok(hipMemset(m.flags.p, 0, sizeof(int)), "clear flags", err)) return nullptr;
-    m.qstart_h = std::move(v.qstart);
-    m.qlen_h = std::move(v.qlen);
-    m.qnpos_h = qnpos;
-    m.qnneg_h = qnneg;
-    return ds;
-}
-
+#include "dataset_build.inc"
 static bool launch_means(const double* M, size_t ldm, size_t ncols, size_t nq, bool sums_only, DevBuf<double>& partial,
                          DevBuf<double>& means, hipStream_t st, std::string* err, const void* tail_count = nullptr,
                          const int* tail_flags = nullptr, double* host_copy = nullptr, const uint32_t* tail_groups = nullptr) {
@@ -3323,1295 +2663,7 @@ bool DeviceDataset::linesearch(int measure, int64_t depth, const double* norms, 
 
 
 
-// ----------------------------------------------------------------------------------------------
-// random-forest training (kernels_rf.inc)
-// ----------------------------------------------------------------------------------------------
-void DeviceDataset::Impl::rf_args(RFArgs& a) {
-    a.xb = xb.p;
-    a.gain = rf.targets != nullptr ? rf.targets : gain.p;
-    a.dq = (uint32_t)dq;
-    a.roff = rf.roff.p;
-    a.pos = rf.pos.p;
-    a.gain_r = rf.gain_r.p;
-    a.node_of = rf.node_of.p;
-    a.side_r = rf.side_r.p;
-    a.feats = rf.feats.p;
-    a.T = rf.T;
-    a.nf = rf.nf;
-    a.total = rf.total;
-    a.slot_of_key = rf.slot_of_key.p;
-    a.A = rf.A;
-    a.act_tree = rf.act_tree.p;
-    a.act_n = rf.act_n.p;
-    a.act_off = rf.act_off.p;
-    a.keys = rf.keys_a.p;
-    a.vals = rf.vals_a.p;
-    a.skeys = rf.keys_b.p;
-    a.svals = rf.vals_b.p;
-    a.sg = rf.sg.p;
-    a.sv = rf.sv.p;
-    a.sg_o = rf.sg_o.p;
-    a.sv_o = rf.sv_o.p;
-    a.pres = rf.pw ? rf.pres.p : nullptr;
-    a.pw = rf.pw;
-    const char* int_env = frdev::path_env("FR_RF_INT_SUMS");
-    const bool int_off = int_env != nullptr && int_env[0] == '0';
-    a.labels_int = (labels_small_int && !int_off && a.gain == gain.p) ? 1u : 0u;
-}
-
-// which features every instance holds, by instance id ([n_instances][words]; nullptr / 0 words: all of them): random-forest
-// training places its thresholds on the range of the HELD values (src/normalizers.rs:24-29)
-bool DeviceDataset::rf_set_presence(const uint32_t* bits_by_instance, size_t words, size_t n_instances, std::string* err) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    auto& rf = m.rf;
-    rf.pw = 0;
-    if (bits_by_instance == nullptr || words == 0) return true;
-    std::vector<uint32_t> by_pos(m.np * words, 0xFFFFFFFFu);  // (padding positions are never sampled)
-    for (size_t p = 0; p < m.np; p++) {
-        const uint32_t id = m.perm_host[p];
-        if (id != IDX_INVALID && id < n_instances) std::memcpy(&by_pos[p * words], bits_by_instance + (size_t)id * words, words * sizeof(uint32_t));
-    }
-    if (!upload(rf.pres, by_pos, err)) return false;
-    rf.pw = (uint32_t)words;
-    return true;
-}
-
-bool DeviceDataset::rf_positions(const std::vector<uint32_t>& root_ids, uint32_t* positions, std::string* err) {
-    Impl& m = *impl_;
-    auto& rf = m.rf;
-    {
-        std::lock_guard<std::mutex> lk(rf.pos_mu);  // (its own lock: the device jobs of a batch hold m.mu for tens of milliseconds)
-        if (rf.pos_of_id.empty()) {
-            uint32_t maxid = 0;
-            for (uint32_t id : m.perm_host)
-                if (id != IDX_INVALID) maxid = std::max(maxid, id);
-            rf.pos_of_id.assign((size_t)maxid + 1, IDX_INVALID);
-            for (size_t p = 0; p < m.perm_host.size(); p++)
-                if (m.perm_host[p] != IDX_INVALID) rf.pos_of_id[m.perm_host[p]] = (uint32_t)p;
-        }
-    }
-    const std::vector<uint32_t>& tab = rf.pos_of_id;  // (read-only from here on)
-    for (size_t g = 0; g < root_ids.size(); g++) {
-        const uint32_t id = root_ids[g];
-        if (id >= tab.size() || tab[id] == IDX_INVALID) {
-            if (err) *err = "rf_begin: instance id outside the dataset";
-            return false;
-        }
-        positions[g] = tab[id];
-    }
-    return true;
-}
-
-bool DeviceDataset::rf_begin(const std::vector<uint32_t>& root_off, const std::vector<uint32_t>& root_ids, uint32_t nf,
-                             const std::vector<uint32_t>& feats, std::string* err, const uint32_t* positions, bool lambda_targets) {
-    std::vector<uint32_t> pos_own;
-    if (positions == nullptr) {
-        pos_own.resize(root_ids.size());
-        if (!rf_positions(root_ids, pos_own.data(), err)) return false;
-        positions = pos_own.data();
-    }
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    auto& rf = m.rf;
-    const size_t T = root_off.size() - 1, total = root_ids.size();
-    if (T == 0 || nf == 0 || feats.size() != T * nf || root_off.back() != total || (uint64_t)total * nf >= (1ull << 31)) {
-        if (err) *err = "rf_begin: bad batch shape";
-        return false;
-    }
-    for (uint32_t f : feats)
-        if (f >= m.d) {
-            if (err) *err = "rf_begin: feature id outside the dataset";
-            return false;
-        }
-    rf.T = (uint32_t)T;
-    rf.nf = nf;
-    rf.total = (uint32_t)total;
-    rf.roff_h = root_off;
-    const size_t items = total * (size_t)nf;
-    if (!rf.roff.ensure(T + 1, err) || !rf.pos.ensure(std::max<size_t>(total, 1), err) || !rf.node_of.ensure(std::max<size_t>(total, 1), err) ||
-        !rf.feats.ensure(T * nf, err) || !rf.keys_a.ensure(std::max<size_t>(items, 1), err) || !rf.keys_b.ensure(std::max<size_t>(items, 1), err) ||
-        !rf.vals_a.ensure(std::max<size_t>(items, 1), err) || !rf.vals_b.ensure(std::max<size_t>(items, 1), err) ||
-        !rf.sg.ensure(std::max<size_t>(items, 1), err) || !rf.sv.ensure(std::max<size_t>(items, 1), err) ||
-        !rf.sg_o.ensure(std::max<size_t>(items, 1), err) || !rf.sv_o.ensure(std::max<size_t>(items, 1), err) ||
-        !rf.gain_r.ensure(std::max<size_t>(total, 1), err) || !rf.side_r.ensure(std::max<size_t>(total, 1), err))
-        return false;
-    FR_HIP(hipMemcpyAsync(rf.roff.p, root_off.data(), (T + 1) * 4, hipMemcpyHostToDevice, m.stream));
-    FR_HIP(hipMemcpyAsync(rf.pos.p, positions, total * 4, hipMemcpyHostToDevice, m.stream));
-    FR_HIP(hipMemcpyAsync(rf.feats.p, feats.data(), T * nf * 4, hipMemcpyHostToDevice, m.stream));
-    // (the instances' first node keys -- their tree's root, key t -- are written on the device: no second 4-byte-per-instance upload)
-    if (lambda_targets && !m.lm.built) {
-        if (err) *err = "rf_begin: no LambdaMART gradients computed";
-        return false;
-    }
-    rf.targets = lambda_targets ? m.lm.target.p : m.gain.p;
-    if (total != 0) rf_gainr_kernel<<<grid1d(total, 256), 256, 0, m.stream>>>(rf.targets, rf.pos.p, rf.roff.p, (uint32_t)T, rf.gain_r.p, rf.node_of.p, (uint32_t)total);
-    FR_HIP(hipGetLastError());
-    FR_HIP(hipStreamSynchronize(m.stream));
-    rf.A = 0;
-    rf.prev_items = 0;
-    rf.prev_A = 0;
-    rf.prev_act_n.clear();
-    rf.splits_for_A = 0;
-    return true;
-}
-
-bool DeviceDataset::rf_root_outputs(std::vector<double>* out, std::string* err) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    auto& rf = m.rf;
-    if (!rf.child.ensure(std::max<size_t>(rf.T, 2), err)) return false;
-    RFArgs a;
-    m.rf_args(a);
-    {
-        ProfScope ps("rf_rootsum_kernel", m.stream);
-        rf_rootsum_kernel<<<dim3(rf.T), 64, 0, m.stream>>>(a, rf.child.p);
-    }
-    out->assign(rf.T, 0.0);
-    FR_HIP(hipMemcpyAsync(out->data(), rf.child.p, rf.T * sizeof(double), hipMemcpyDeviceToHost, m.stream));
-    FR_HIP(hipStreamSynchronize(m.stream));
-    return true;
-}
-
-bool DeviceDataset::rf_level(const std::vector<RfActive>& active, const std::vector<uint32_t>& slot_of_key, uint32_t k, int method,
-                             uint32_t min_leaf, std::vector<RfCand>* cands, std::vector<float>* label_minmax, std::string* err) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    auto& rf = m.rf;
-    const size_t A = active.size();
-    cands->clear();
-    label_minmax->clear();
-    // (fewer than two split candidates: no thresholds, random_forest.rs:236 -- nothing is evaluated and a following
-    // rf_split has nothing to move; the level's tables are only valid when they were uploaded for THIS set of nodes)
-    rf.A = (A == 0 || k < 2) ? 0u : (uint32_t)A;
-    if (rf.A == 0) return true;
-    std::vector<uint32_t> act_tree(A), act_n(A);
-    std::vector<uint64_t> act_off(A + 1, 0), act_first(A + 1, 0);
-    for (size_t i = 0; i < A; i++) {
-        act_tree[i] = active[i].tree;
-        act_n[i] = active[i].n;
-        act_off[i + 1] = act_off[i] + (uint64_t)active[i].n * rf.nf;
-        act_first[i + 1] = act_first[i] + active[i].n;
-    }
-    rf.items = act_off[A];
-    rf.node_items = act_first[A];
-    const uint64_t ncand = (uint64_t)A * rf.nf * (k - 1);
-    if ((uint64_t)A * rf.nf >= 0x7FFFFFFFull || ncand >= (1ull << 31)) {
-        if (err) *err = "rf_level: too many segments";
-        return false;
-    }
-    // the tables of the level before stay intact for rf_rekey_kernel (ensure() below may reallocate)
-    std::swap(rf.act_tree.p, rf.act_tree_o.p), std::swap(rf.act_tree.cap, rf.act_tree_o.cap);
-    std::swap(rf.act_n.p, rf.act_n_o.p), std::swap(rf.act_n.cap, rf.act_n_o.cap);
-    std::swap(rf.act_off.p, rf.act_off_o.p), std::swap(rf.act_off.cap, rf.act_off_o.cap);
-    if (!rf.slot_of_key.ensure(std::max<size_t>(slot_of_key.size(), 1), err) || !rf.act_tree.ensure(A, err) || !rf.act_n.ensure(A, err) ||
-        !rf.act_off.ensure(A + 1, err) || !rf.act_first.ensure(A + 1, err) || !rf.cands.ensure(ncand, err) || !rf.label.ensure(A * 2, err))
-        return false;
-    FR_HIP(hipMemcpyAsync(rf.slot_of_key.p, slot_of_key.data(), slot_of_key.size() * 4, hipMemcpyHostToDevice, m.stream));
-    RFArgs a;
-    m.rf_args(a);
-    const bool from_scratch = rf.prev_items == 0 || frdev::path_env("FR_RF_RESORT");
-    // levels after the first: the children's segments by a stable partition of the parents' (kernels_rf.inc); FR_RF_PARTITION=0:
-    // by rewriting the segment ids and a stable radix sort on them
-    const char* part_env = frdev::path_env("FR_RF_PARTITION");  // (read per level: the tests compare both paths in one process)
-    const bool partition_on = part_env == nullptr || part_env[0] != '0';
-    const bool partition = !from_scratch && partition_on && rf.splits_for_A == rf.prev_A && rf.prev_act_n.size() == rf.prev_A;
-    std::vector<uint64_t> tile_first;
-    if (partition) {
-        tile_first.assign((size_t)rf.prev_A + 1, 0);
-        for (uint32_t i = 0; i < rf.prev_A; i++) tile_first[i + 1] = tile_first[i] + (uint64_t)rf.nf * ((rf.prev_act_n[i] + RF_PT - 1) / RF_PT);
-        if (tile_first.back() >= 0x7FFFFFFFull || !rf.tile_first_o.ensure(tile_first.size(), err) || !rf.tile_cnt.ensure(std::max<size_t>(2 * tile_first.back(), 2), err) ||
-            !rf.side.ensure(std::max<size_t>(rf.prev_items, 1), err))
-            return false;
-        FR_HIP(hipMemcpyAsync(rf.tile_first_o.p, tile_first.data(), tile_first.size() * 8, hipMemcpyHostToDevice, m.stream));
-    } else if (!from_scratch) {  // (reads the PREVIOUS level's tables, which the copies below overwrite afterwards, in stream order)
-        RFArgs ao = a;
-        ao.act_tree = rf.act_tree_o.p;
-        ao.act_n = rf.act_n_o.p;
-        ao.act_off = rf.act_off_o.p;
-        ProfScope ps("rf_rekey_kernel", m.stream);
-        rf_rekey_kernel<<<grid1d(rf.prev_items, 256), 256, 0, m.stream>>>(ao, rf.prev_items, rf.prev_A, (uint32_t)A);
-    }
-    FR_HIP(hipMemcpyAsync(rf.act_tree.p, act_tree.data(), A * 4, hipMemcpyHostToDevice, m.stream));
-    FR_HIP(hipMemcpyAsync(rf.act_n.p, act_n.data(), A * 4, hipMemcpyHostToDevice, m.stream));
-    FR_HIP(hipMemcpyAsync(rf.act_off.p, act_off.data(), (A + 1) * 8, hipMemcpyHostToDevice, m.stream));
-    FR_HIP(hipMemcpyAsync(rf.act_first.p, act_first.data(), (A + 1) * 8, hipMemcpyHostToDevice, m.stream));
-    const size_t all_items = (size_t)rf.total * rf.nf;
-    if (from_scratch) {
-        ProfScope ps("rf_key_kernel", m.stream);
-        rf_key_kernel<<<grid1d(rf.total, 256), 256, 0, m.stream>>>(a);
-    }
-    if (partition) {
-        // the previous level's sorted gains / values become the scatter's input, this level's are written beside them
-        std::swap(rf.sg.p, rf.sg_o.p), std::swap(rf.sg.cap, rf.sg_o.cap);
-        std::swap(rf.sv.p, rf.sv_o.p), std::swap(rf.sv.cap, rf.sv_o.cap);
-        m.rf_args(a);
-        RFPart pp;
-        pp.o_tree = rf.act_tree_o.p;
-        pp.o_n = rf.act_n_o.p;
-        pp.o_off = rf.act_off_o.p;
-        pp.o_tile_first = rf.tile_first_o.p;
-        pp.o_A = rf.prev_A;
-        pp.sp = rf.splits.p;
-        pp.tile_cnt = rf.tile_cnt.p;
-        pp.side = rf.side.p;
-        const unsigned tiles = (unsigned)tile_first.back();
-        {
-            ProfScope ps("rf_part_count_kernel", m.stream);
-            rf_part_count_kernel<<<dim3(tiles), 256, 0, m.stream>>>(a, pp);
-        }
-        {
-            ProfScope ps("rf_part_scan_kernel", m.stream);
-            rf_part_scan_kernel<<<dim3(rf.prev_A * rf.nf), 64, 0, m.stream>>>(a, pp);
-        }
-        {
-            ProfScope ps("rf_part_scatter_kernel", m.stream);
-            rf_part_scatter_kernel<<<dim3(tiles), 256, 0, m.stream>>>(a, pp);
-        }
-        FR_HIP(hipGetLastError());
-        // the partition wrote keys_a / vals_a: they are the sorted arrays now
-        std::swap(rf.keys_a.p, rf.keys_b.p), std::swap(rf.keys_a.cap, rf.keys_b.cap);
-        std::swap(rf.vals_a.p, rf.vals_b.p), std::swap(rf.vals_a.cap, rf.vals_b.cap);
-        m.rf_args(a);
-    } else {
-        // stable LSD radix sort of (segment << 32 | value bits), only the bits in use: all of them the first time,
-        // the segment bits alone afterwards (the value order inside a node survives a stable sort by child)
-        unsigned seg_bits = 1;
-        while ((1ull << seg_bits) <= (uint64_t)A * rf.nf) seg_bits++;
-        const size_t count = from_scratch ? all_items : (size_t)rf.prev_items;
-        const unsigned begin_bit = from_scratch ? 0u : 32u;
-        size_t temp_bytes = 0;
-        FR_HIP(rocprim::radix_sort_pairs(nullptr, temp_bytes, rf.keys_a.p, rf.keys_b.p, rf.vals_a.p, rf.vals_b.p, count, begin_bit, 32u + seg_bits,
-                                         m.stream));
-        if (!rf.temp.ensure(std::max<size_t>(temp_bytes, 16), err)) return false;
-        ProfScope ps("rf_radix_sort", m.stream);
-        FR_HIP(rocprim::radix_sort_pairs((void*)rf.temp.p, temp_bytes, rf.keys_a.p, rf.keys_b.p, rf.vals_a.p, rf.vals_b.p, count, begin_bit,
-                                         32u + seg_bits, m.stream));
-    }
-    rf.prev_act_n = act_n;
-    rf.splits_for_A = 0;  // (set again by the rf_split that decides THIS level)
-    rf.prev_items = rf.items;
-    rf.prev_A = (uint32_t)A;
-    if (!partition) {  // (the partition's scatter writes the sorted gains and values itself)
-        ProfScope ps("rf_gather_kernel", m.stream);
-        rf_gather_kernel<<<grid1d(rf.items, 256), 256, 0, m.stream>>>(a, rf.items);
-    }
-    {
-        ProfScope ps("rf_label_kernel", m.stream);
-        rf_label_kernel<<<dim3((unsigned)A), RF_LABEL_THREADS, 0, m.stream>>>(a, rf.label.p);
-    }
-    {
-        ProfScope ps("rf_eval_kernel", m.stream);
-        rf_eval_kernel<<<dim3((unsigned)(A * rf.nf)), 64, 0, m.stream>>>(a, k, method, min_leaf, rf.cands.p);
-    }
-    FR_HIP(hipGetLastError());
-    static_assert(sizeof(RfCand) == sizeof(RfCandDev), "host / device candidate records differ");
-    cands->resize(ncand);
-    label_minmax->resize(A * 2);
-    FR_HIP(hipMemcpyAsync(cands->data(), rf.cands.p, ncand * sizeof(RfCandDev), hipMemcpyDeviceToHost, m.stream));
-    FR_HIP(hipMemcpyAsync(label_minmax->data(), rf.label.p, A * 2 * sizeof(float), hipMemcpyDeviceToHost, m.stream));
-    FR_HIP(hipStreamSynchronize(m.stream));
-    return true;
-}
-
-bool DeviceDataset::rf_split(const std::vector<RfSplit>& splits, std::vector<double>* child_out, std::string* err) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    auto& rf = m.rf;
-    const size_t A = rf.A;
-    if (child_out) child_out->assign(splits.size() * 2, 0.0);  // (nullptr: the caller has the children's sums from the candidates, method 0)
-    if (A == 0 || rf.node_items == 0) return true;
-    if (splits.size() != A) {
-        if (err) *err = "rf_split: one decision per active node expected";
-        return false;
-    }
-    static_assert(sizeof(RfSplit) == sizeof(RfSplitDev), "host / device split records differ");
-    if (!rf.splits.ensure(A, err) || !rf.child.ensure(std::max<size_t>(A * 2, rf.T), err)) return false;
-    FR_HIP(hipMemcpyAsync(rf.splits.p, splits.data(), A * sizeof(RfSplitDev), hipMemcpyHostToDevice, m.stream));
-    rf.splits_for_A = (uint32_t)A;
-    RFArgs a;
-    m.rf_args(a);
-    {
-        ProfScope ps("rf_assign_kernel", m.stream);
-        rf_assign_kernel<<<grid1d(rf.node_items, 256), 256, 0, m.stream>>>(a, rf.splits.p, rf.node_items, rf.act_first.p);
-    }
-    if (child_out) {
-        ProfScope ps("rf_childsum_kernel", m.stream);
-        rf_childsum_kernel<<<dim3((unsigned)A), 64, 0, m.stream>>>(a, rf.splits.p, rf.child.p);
-    }
-    FR_HIP(hipGetLastError());
-    if (child_out) FR_HIP(hipMemcpyAsync(child_out->data(), rf.child.p, A * 2 * sizeof(double), hipMemcpyDeviceToHost, m.stream));
-    FR_HIP(hipStreamSynchronize(m.stream));  // (also without child sums: `splits` is the caller's pageable memory)
-    return true;
-}
-
-void DeviceDataset::rf_end() {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    auto& rf = m.rf;
-    rf.keys_a.release(), rf.keys_b.release(), rf.vals_a.release(), rf.vals_b.release(), rf.sg.release(), rf.sv.release(), rf.sg_o.release(), rf.sv_o.release(), rf.temp.release(), rf.side.release(), rf.tile_cnt.release();
-    rf.cands.release();
-}
-
-// ----------------------------------------------------------------------------------------------
-// LambdaMART gradient pass (kernels_lambda.inc)
-// ----------------------------------------------------------------------------------------------
-// per query the positions of its documents in stored order (instance ids ascending), and the launch order (longest first)
-bool DeviceDataset::Impl::lm_build(std::string* err) {
-    if (lm.built) return true;
-    std::vector<uint32_t> off(nq + 1, 0), pos, order(nq);
-    pos.reserve(n);
-    uint32_t maxl = 0;
-    for (size_t q = 0; q < nq; q++) {
-        const size_t b = pos.size();
-        for (uint32_t k = 0; k < qlen_h[q]; k++) pos.push_back(qstart_h[q] + k);
-        std::sort(pos.begin() + b, pos.end(), [&](uint32_t x, uint32_t y) { return perm_host[x] < perm_host[y]; });
-        off[q + 1] = (uint32_t)pos.size();
-        maxl = std::max(maxl, qlen_h[q]);
-        order[q] = (uint32_t)q;
-    }
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return qlen_h[a] > qlen_h[b]; });
-    // queries beyond the LDS budget (4096 documents, 144 KiB) are staged in a per-block global slab; they come first in
-    // the longest-first order
-    uint32_t n_long = 0;
-    while (n_long < nq && (size_t)qlen_h[order[n_long]] * LM_STAGE_BYTES > LM_LDS_MAX) n_long++;
-    if (!upload(lm.off, off, err) || !upload(lm.pos, pos, err) || !upload(lm.qorder, order, err)) return false;
-    if (!lm.lam.ensure(np, err) || !lm.wt.ensure(np, err) || !lm.target.ensure(np, err)) return false;
-    FR_HIP(hipMemsetAsync(lm.lam.p, 0, np * sizeof(double), stream));
-    FR_HIP(hipMemsetAsync(lm.wt.p, 0, np * sizeof(double), stream));
-    FR_HIP(hipMemsetAsync(lm.target.p, 0, np * sizeof(float), stream));
-    lm.n_lds = (uint32_t)nq - n_long;
-    lm.max_len = maxl;
-    lm.order_h = order;
-    if (n_long && !lm.slab.ensure((size_t)LM_SLAB_BLOCKS * maxl * LM_STAGE_BYTES, err)) return false;
-    lm.built = true;
-    return true;
-}
-
-bool DeviceDataset::lambda_gradients(const double* norms, int64_t depth, double sigma, const LambdaPass& pass, std::string* err) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    if (m.scores_slots < 1 || m.scores.p == nullptr) {
-        if (err) *err = "lambda_gradients: no scores resident";
-        return false;
-    }
-    if (pass.objective < LM_OBJ_NDCG || pass.objective > LM_OBJ_MRR) {
-        if (err) *err = "lambda_gradients: unknown objective " + std::to_string(pass.objective);
-        return false;
-    }
-    if (!m.lm_build(err)) return false;
-    if (!m.norms.ensure(m.nq, err) || !m.upload_norms(norms, err)) return false;
-    auto& lm = m.lm;
-    uint32_t n_long = (uint32_t)m.nq - lm.n_lds, n_lds = lm.n_lds;
-    const uint32_t* qorder = lm.qorder.p;
-    size_t longest = n_long < m.nq ? std::min<size_t>(lm.max_len, LM_LDS_MAX / LM_STAGE_BYTES) : 0;
-    if (pass.query_flags != nullptr) {  // a tree's query sample: qorder filtered, its order kept (slab queries still open the pass)
-        if (!(pass.flags_unchanged && lm.qsel_valid)) {
-            lm.qsel_valid = false;
-            lm.qsel_h.clear();
-            lm.sel_long = 0;
-            for (size_t i = 0; i < m.nq; i++) {
-                const uint32_t q = lm.order_h[i];
-                if (!pass.query_flags[q]) continue;
-                if (i < n_long) lm.sel_long++;
-                lm.qsel_h.push_back(q);
-            }
-            if (lm.qsel_h.empty()) return true;
-            if (!lm.qsel.ensure(m.nq, err)) return false;
-            FR_HIP(hipMemcpyAsync(lm.qsel.p, lm.qsel_h.data(), lm.qsel_h.size() * sizeof(uint32_t), hipMemcpyHostToDevice, m.stream));
-            lm.qsel_valid = true;
-        }
-        const uint32_t sel_long = lm.sel_long;
-        n_long = sel_long, n_lds = (uint32_t)lm.qsel_h.size() - sel_long;
-        qorder = lm.qsel.p;
-        longest = n_lds ? m.qlen_h[lm.qsel_h[n_long]] : 0;  // (the longest sampled query that is staged in LDS)
-    }
-    if (pass.truncation_level != 0 || pass.lambda_norm) {  // DESIGN.md section 11, "Truncation and normalisation": a kernel of its own
-        const uint32_t trunc = pass.truncation_level != 0 ? pass.truncation_level : 0xFFFFFFFFu;  // (no level: every rank is inside)
-        if (pass.lambda_norm && !lm.asum.ensure(m.np, err)) return false;
-        ProfScope ps("lambda_grad_trunc_kernel", m.stream);
-        auto* const kernel = pass.objective == LM_OBJ_MAP ? lambda_grad_trunc_kernel<LM_OBJ_MAP>
-                             : pass.objective == LM_OBJ_MRR ? lambda_grad_trunc_kernel<LM_OBJ_MRR> : lambda_grad_trunc_kernel<LM_OBJ_NDCG>;
-        for (uint32_t q0 = 0; q0 < n_long; q0 += LM_SLAB_BLOCKS) {
-            const uint32_t cnt = std::min<uint32_t>(LM_SLAB_BLOCKS, n_long - q0);
-            kernel<<<cnt, 256, 0, m.stream>>>(m.scores.p, lm.off.p, lm.pos.p, qorder, q0, m.gain.p, m.gexp.p, m.disc.p, m.perm.p, m.norms.p,
-                                              depth, sigma, trunc, pass.lambda_norm ? 1 : 0, lm.lam.p, lm.wt.p, lm.target.p, lm.asum.p, lm.slab.p,
-                                              lm.max_len);
-        }
-        if (n_lds != 0) {
-            const size_t bytes = std::max<size_t>(longest * LM_STAGE_BYTES, 64);
-            FR_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-            kernel<<<n_lds, 256, bytes, m.stream>>>(m.scores.p, lm.off.p, lm.pos.p, qorder, n_long, m.gain.p, m.gexp.p, m.disc.p, m.perm.p,
-                                                    m.norms.p, depth, sigma, trunc, pass.lambda_norm ? 1 : 0, lm.lam.p, lm.wt.p, lm.target.p,
-                                                    lm.asum.p, nullptr, 0u);
-        }
-        FR_HIP(hipGetLastError());
-        return true;
-    }
-    ProfScope ps("lambda_grad_kernel", m.stream);
-    auto* const kernel = pass.objective == LM_OBJ_MAP ? lambda_grad_kernel<LM_OBJ_MAP>
-                         : pass.objective == LM_OBJ_MRR ? lambda_grad_kernel<LM_OBJ_MRR> : lambda_grad_kernel<LM_OBJ_NDCG>;
-    for (uint32_t q0 = 0; q0 < n_long; q0 += LM_SLAB_BLOCKS) {  // (longest first: these open the pass)
-        const uint32_t cnt = std::min<uint32_t>(LM_SLAB_BLOCKS, n_long - q0);
-        kernel<<<cnt, 256, 0, m.stream>>>(m.scores.p, lm.off.p, lm.pos.p, qorder, q0, m.gain.p, m.gexp.p, m.disc.p, m.perm.p, m.norms.p, depth,
-                                          sigma, lm.lam.p, lm.wt.p, lm.target.p, lm.slab.p, lm.max_len);
-    }
-    if (n_lds != 0) {
-        const size_t bytes = std::max<size_t>(longest * LM_STAGE_BYTES, 64);
-        FR_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-        kernel<<<n_lds, 256, bytes, m.stream>>>(m.scores.p, lm.off.p, lm.pos.p, qorder, n_long, m.gain.p, m.gexp.p, m.disc.p, m.perm.p,
-                                                m.norms.p, depth, sigma, lm.lam.p, lm.wt.p, lm.target.p, nullptr, 0u);
-    }
-    FR_HIP(hipGetLastError());
-    return true;
-}
-
-bool DeviceDataset::lambda_download_positions(std::vector<double>* lambda, std::vector<double>* weight, std::string* err) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    if (!m.lm.built) {
-        if (err) *err = "lambda_download: no gradients computed";
-        return false;
-    }
-    lambda->resize(m.np);
-    weight->resize(m.np);
-    FR_HIP(hipMemcpyAsync(lambda->data(), m.lm.lam.p, m.np * sizeof(double), hipMemcpyDeviceToHost, m.stream));
-    FR_HIP(hipMemcpyAsync(weight->data(), m.lm.wt.p, m.np * sizeof(double), hipMemcpyDeviceToHost, m.stream));
-    FR_HIP(hipStreamSynchronize(m.stream));
-    return true;
-}
-
-bool DeviceDataset::lambda_download(double* lambda_by_instance, double* weight_by_instance, size_t out_len, std::string* err,
-                                    const unsigned char* query_flags) {
-    std::vector<double> lam, wt;
-    if (!lambda_download_positions(&lam, &wt, err)) return false;
-    Impl& m = *impl_;
-    std::vector<char> in_query(m.np, 0);
-    for (size_t q = 0; q < m.nq; q++) {
-        if (query_flags != nullptr && !query_flags[q]) continue;
-        for (uint32_t k = 0; k < m.qlen_h[q]; k++) in_query[m.qstart_h[q] + k] = 1;
-    }
-    for (size_t p = 0; p < m.np; p++) {
-        const uint32_t id = m.perm_host[p];
-        if (!in_query[p] || id == IDX_INVALID || id >= out_len) continue;
-        lambda_by_instance[id] = lam[p];
-        weight_by_instance[id] = wt[p];
-    }
-    return true;
-}
-
-// ----------------------------------------------------------------------------------------------
-// LambdaMART's DART boosting (kernels_dart.inc)
-// ----------------------------------------------------------------------------------------------
-static bool dart_fail(std::string* err, const std::string& what) {
-    if (err) *err = "LambdaMART DART: " + what;
-    return false;
-}
-
-bool DeviceDataset::dart_begin(size_t rows, uint64_t* cache_bytes, std::string* err) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    Impl::DartState& d = m.dart;
-    d.rows = d.filled = 0;
-    d.stride = m.pos_threads();
-    d.vals_h.clear();
-    d.voff_h.assign(1, 0u);
-    if (rows == 0 || d.stride == 0 || d.stride % 64 != 0) return dart_fail(err, "no trees or no documents to cache leaves for");
-    if (d.stride > 0xFFFFFFFFull - (size_t)DART_MAX_GRID * DART_BLOCK * DART_DOCS) return dart_fail(err, "too many documents for the kernel's 32-bit document index");
-    const size_t need = rows * d.stride;  // u16 entries
-    if (need > d.leaf.cap) {
-        // the one large allocation of a training: checked against what is free (with room for the growers' scratch) first
-        const size_t free_b = device_free_bytes(), margin = (size_t)256 << 20;
-        d.leaf.release();
-        if (free_b != 0 && need * sizeof(uint16_t) + margin > free_b)
-            return dart_fail(err, "the leaf cache of " + std::to_string(rows) + " trees x " + std::to_string(d.stride) + " documents needs " +
-                                      std::to_string(need * sizeof(uint16_t)) + " bytes, " + std::to_string(free_b) + " are free on the device");
-        if (!d.leaf.ensure(need, err)) return false;
-    }
-    if (!d.voff.ensure(rows + 1, err) || !d.w.ensure(rows, err) || !d.trees.ensure(rows, err) || !d.bad.ensure(1, err)) return false;
-    if (!m.scores.ensure(m.np, err) || !m.acc.ensure(m.np, err)) return false;
-    FR_HIP(hipMemsetAsync(d.voff.p, 0, sizeof(uint32_t), m.stream));
-    FR_HIP(hipMemsetAsync(d.bad.p, 0, sizeof(int), m.stream));
-    d.rows = rows;
-    if (cache_bytes) *cache_bytes = (uint64_t)(need * sizeof(uint16_t));
-    return true;
-}
-
-bool DeviceDataset::dart_fill(size_t row, const double* leaf_values, size_t n_leaves, std::string* err) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    Impl::DartState& d = m.dart;
-    if (row != d.filled || row >= d.rows) return dart_fail(err, "the leaf cache is filled one tree after the other (row " + std::to_string(row) + ")");
-    if (n_leaves == 0 || n_leaves > DART_MAX_LEAVES)
-        return dart_fail(err, "a tree of " + std::to_string(n_leaves) + " leaves does not fit the leaf cache's 16-bit entries (at most 65536)");
-    if (m.scores_slots < 1) return dart_fail(err, "no leaf numbers in score slot 0");
-    // the leaf values join the table (a table that has to grow is uploaded again as a whole)
-    FR_HIP(hipStreamSynchronize(m.stream));  // (earlier copies out of vals_h are done before it may move)
-    const size_t at = d.vals_h.size();
-    d.vals_h.insert(d.vals_h.end(), leaf_values, leaf_values + n_leaves);
-    d.voff_h.push_back((uint32_t)d.vals_h.size());
-    if (d.vals_h.size() > d.vals.cap) {
-        if (!d.vals.ensure(std::max<size_t>(2 * d.vals_h.size(), 4096), err)) return false;
-        FR_HIP(hipMemcpyAsync(d.vals.p, d.vals_h.data(), d.vals_h.size() * sizeof(double), hipMemcpyHostToDevice, m.stream));
-    } else {
-        FR_HIP(hipMemcpyAsync(d.vals.p + at, d.vals_h.data() + at, n_leaves * sizeof(double), hipMemcpyHostToDevice, m.stream));
-    }
-    FR_HIP(hipMemcpyAsync(d.voff.p + row + 1, d.voff_h.data() + row + 1, sizeof(uint32_t), hipMemcpyHostToDevice, m.stream));
-    {
-        ProfScope ps("dart_fill_kernel", m.stream);
-        dart_fill_kernel<<<grid1d(d.stride, 256), 256, 0, m.stream>>>(m.scores.p, m.posmap(), (uint32_t)d.stride, (uint32_t)n_leaves, m.perm.p,
-                                                                     d.leaf.p + row * d.stride, d.bad.p);
-    }
-    FR_HIP(hipGetLastError());
-    int bad = 0;
-    FR_HIP(hipMemcpyAsync(&bad, d.bad.p, sizeof(int), hipMemcpyDeviceToHost, m.stream));
-    FR_HIP(hipStreamSynchronize(m.stream));
-    if (bad) {
-        FR_HIP(hipMemsetAsync(d.bad.p, 0, sizeof(int), m.stream));
-        return dart_fail(err, "a document was routed to no leaf of the tree");
-    }
-    d.filled = row + 1;
-    return true;
-}
-
-bool DeviceDataset::dart_rescore(const double* weights, size_t n_weights, const uint32_t* trees, size_t n_trees, std::string* err) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    Impl::DartState& d = m.dart;
-    if (d.rows == 0) return dart_fail(err, "no leaf cache");
-    if (n_weights > d.filled || n_trees > d.rows) return dart_fail(err, "more weights or trees than the leaf cache has rows");
-    for (size_t k = 0; k < n_trees; k++)
-        if (trees[k] >= n_weights || (k > 0 && trees[k] <= trees[k - 1]))
-            return dart_fail(err, "the tree list must be ascending and name trees that have a weight and a cache row");
-    FR_HIP(hipStreamSynchronize(m.stream));  // (the staging copies of the last call are done)
-    d.w_h.assign(weights, weights + n_weights);
-    d.trees_h.assign(trees, trees + n_trees);
-    if (n_weights) FR_HIP(hipMemcpyAsync(d.w.p, d.w_h.data(), n_weights * sizeof(double), hipMemcpyHostToDevice, m.stream));
-    if (n_trees) FR_HIP(hipMemcpyAsync(d.trees.p, d.trees_h.data(), n_trees * sizeof(uint32_t), hipMemcpyHostToDevice, m.stream));
-    const uint32_t n_vals = (uint32_t)d.vals_h.size();
-    const bool in_lds = n_vals <= DART_LDS_VALUES;  // (else the lanes gather the leaf values from global memory)
-    const dim3 grid(std::min<unsigned>(grid1d(d.stride, DART_BLOCK * DART_DOCS).x, DART_MAX_GRID));
-    {
-        ProfScope ps("dart_rescore_kernel", m.stream);
-        if (in_lds)
-            dart_rescore_kernel<true><<<grid, DART_BLOCK, (size_t)n_vals * sizeof(double), m.stream>>>(
-                d.leaf.p, (uint32_t)d.stride, d.vals.p, d.voff.p, n_vals, d.w.p, d.trees.p, (uint32_t)n_trees, m.posmap(), m.scores.p, m.acc.p);
-        else
-            dart_rescore_kernel<false><<<grid, DART_BLOCK, 0, m.stream>>>(
-                d.leaf.p, (uint32_t)d.stride, d.vals.p, d.voff.p, n_vals, d.w.p, d.trees.p, (uint32_t)n_trees, m.posmap(), m.scores.p, m.acc.p);
-    }
-    FR_HIP(hipGetLastError());
-    m.scores_slots = 1;
-    return true;
-}
-
-bool DeviceDataset::dart_download_row(size_t row, uint16_t* out_by_instance, size_t out_len, std::string* err) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    Impl::DartState& d = m.dart;
-    if (row >= d.filled) return dart_fail(err, "no such row in the leaf cache");
-    std::vector<uint16_t> tmp(d.stride);
-    FR_HIP(hipMemcpyAsync(tmp.data(), d.leaf.p + row * d.stride, d.stride * sizeof(uint16_t), hipMemcpyDeviceToHost, m.stream));
-    std::vector<uint32_t> tiles(m.nvtiles);
-    if (m.nvtiles) FR_HIP(hipMemcpyAsync(tiles.data(), m.vtiles.p, m.nvtiles * sizeof(uint32_t), hipMemcpyDeviceToHost, m.stream));
-    FR_HIP(hipStreamSynchronize(m.stream));
-    for (size_t i = 0; i < d.stride; i++) {
-        const size_t p = m.nvtiles ? (size_t)tiles[i >> 6] * 64 + (i & 63) : i;
-        const size_t id = m.perm_host[p];
-        if (id != IDX_INVALID && id < out_len) out_by_instance[id] = tmp[i];
-    }
-    return true;
-}
-
-void DeviceDataset::dart_end() {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    (void)hipSetDevice(m.device);
-    if (m.stream) (void)hipStreamSynchronize(m.stream);
-    Impl::DartState& d = m.dart;
-    d.leaf.release(), d.vals.release(), d.w.release(), d.voff.release(), d.trees.release(), d.bad.release();
-    d.rows = d.filled = d.stride = 0;
-    d.vals_h.clear(), d.voff_h.clear(), d.w_h.clear(), d.trees_h.clear();
-}
-
-// ----------------------------------------------------------------------------------------------
-// LambdaMART histogram grower (kernels_hist.inc)
-// ----------------------------------------------------------------------------------------------
-static bool hist_fail(std::string* err, const std::string& what) {
-    if (err) *err = "LambdaMART histogram grower: " + what;
-    return false;
-}
-
-bool DeviceDataset::hist_bins(const uint32_t* positions, size_t n, const std::vector<uint32_t>& feats, uint32_t k, bool* built,
-                              std::string* err) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    auto& h = m.hist;
-    if (built) *built = false;
-    if (k < 2 || k > HIST_MAX_BINS) return hist_fail(err, "split_candidates must be between 2 and 256");
-    if (n == 0 || feats.empty()) return hist_fail(err, "no instances or no features");
-    if (n >= (1ull << 31)) return hist_fail(err, "more instances than the index list can hold");
-    for (uint32_t f : feats)
-        if (f >= m.d) return hist_fail(err, "feature id outside the dataset");
-    if (h.k == k && h.n == n && h.feats == feats && std::equal(h.pos_host.begin(), h.pos_host.end(), positions)) {
-        h.nt = h.n, h.Ft = h.F, h.q_sampled = h.f_sampled = false;  // (no sample until hist_sample says so)
-        return true;
-    }
-    h.k = 0;  // (nothing valid until the end of this function)
-    const size_t F = feats.size();
-    for (size_t i = 0; i < n; i++)
-        if (positions[i] >= m.np) return hist_fail(err, "instance position outside the dataset");
-    {
-        const size_t need = F * n + 3 * n * sizeof(float) + ((size_t)64 << 20), have = device_free_bytes() + h.xbin.bytes();
-        if (have != h.xbin.bytes() && have < need)
-            return hist_fail(err, "the bin matrix needs " + std::to_string(need >> 20) + " MB of device memory, " +
-                                      std::to_string(have >> 20) + " MB are free");
-    }
-    h.pos_host.assign(positions, positions + n);
-    if (!h.pos.ensure(n, err) || !h.xbin.ensure(F * n, err) || !h.edges.ensure(F * HIST_MAX_BINS, err) || !h.nedges.ensure(F, err)) return false;
-    DevBuf<float> col, sorted, firsts;
-    DevBuf<uint32_t> count;
-    DevBuf<int> nan_flag;
-    if (!col.ensure(n, err) || !sorted.ensure(n, err) || !firsts.ensure(F * (HIST_MAX_BINS + 1), err) || !count.ensure(F, err) || !nan_flag.ensure(1, err))
-        return false;
-    FR_HIP(hipMemcpyAsync(h.pos.p, h.pos_host.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, m.stream));
-    FR_HIP(hipMemsetAsync(count.p, 0, F * sizeof(uint32_t), m.stream));
-    FR_HIP(hipMemsetAsync(nan_flag.p, 0, sizeof(int), m.stream));
-    FR_HIP(hipMemsetAsync(h.edges.p, 0, F * HIST_MAX_BINS * sizeof(float), m.stream));
-    size_t temp_bytes = 0;
-    FR_HIP(rocprim::radix_sort_keys(nullptr, temp_bytes, col.p, sorted.p, n, 0u, 32u, m.stream));
-    if (!h.temp.ensure(std::max<size_t>(temp_bytes, 16), err)) return false;
-    const uint32_t n32 = (uint32_t)n;
-    {
-        ProfScope ps("hist_binning", m.stream);
-        for (size_t s = 0; s < F; s++) {
-            hist_column_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(m.xb.p, (uint32_t)m.dq, h.pos.p, n32, feats[s], col.p, nan_flag.p);
-            size_t tb = h.temp.bytes();
-            FR_HIP(rocprim::radix_sort_keys((void*)h.temp.p, tb, col.p, sorted.p, n, 0u, 32u, m.stream));
-            hist_distinct_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(sorted.p, n32, count.p + s, firsts.p + s * (HIST_MAX_BINS + 1));
-            hist_edges_kernel<<<1, 256, 0, m.stream>>>(sorted.p, n32, k, count.p + s, firsts.p + s * (HIST_MAX_BINS + 1),
-                                                       h.edges.p + s * HIST_MAX_BINS, h.nedges.p + s);
-            hist_bin_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(col.p, n32, h.edges.p + s * HIST_MAX_BINS, h.nedges.p + s, h.xbin.p + s * n);
-        }
-    }
-    FR_HIP(hipGetLastError());
-    h.edges_host.assign(F * HIST_MAX_BINS, 0.0f);
-    h.nedges_host.assign(F, 0);
-    int bad = 0;
-    FR_HIP(hipMemcpyAsync(h.edges_host.data(), h.edges.p, F * HIST_MAX_BINS * sizeof(float), hipMemcpyDeviceToHost, m.stream));
-    FR_HIP(hipMemcpyAsync(h.nedges_host.data(), h.nedges.p, F * sizeof(uint32_t), hipMemcpyDeviceToHost, m.stream));
-    FR_HIP(hipMemcpyAsync(&bad, nan_flag.p, sizeof(int), hipMemcpyDeviceToHost, m.stream));
-    FR_HIP(hipStreamSynchronize(m.stream));
-    if (bad) return hist_fail(err, "a feature value is NaN; NaN has no bin (use the exact grower, or clean the data)");
-    for (size_t s = 0; s < F; s++)
-        if (h.nedges_host[s] >= k) return hist_fail(err, "internal error: more edges than bins");
-    h.qof_built = false;  // (made for these bins by the first query sample: hist_qof)
-    h.mono_F = 0;
-    h.feats = feats;
-    h.n = n32, h.F = (uint32_t)F, h.k = k;
-    h.nt = n32, h.Ft = (uint32_t)F, h.q_sampled = h.f_sampled = false;
-    if (built) *built = true;
-    return true;
-}
-
-bool DeviceDataset::hist_edges(std::vector<float>* edges, std::vector<uint32_t>* nedges, std::string* err) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (m.hist.k == 0) return hist_fail(err, "no bins built");
-    *edges = m.hist.edges_host;
-    *nedges = m.hist.nedges_host;
-    return true;
-}
-
-bool DeviceDataset::hist_download_bins(uint8_t* out, size_t len, std::string* err) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    auto& h = m.hist;
-    if (h.k == 0) return hist_fail(err, "no bins built");
-    if (len != (size_t)h.F * h.n) return hist_fail(err, "bin matrix output has the wrong length");
-    FR_HIP(hipMemcpyAsync(out, h.xbin.p, len, hipMemcpyDeviceToHost, m.stream));
-    FR_HIP(hipStreamSynchronize(m.stream));
-    return true;
-}
-
-// the query of every instance-list entry, for the trees' query samples: made once per bin matrix, by the first tree that
-// samples queries (4 ms of host work at the 30K shape that a request without samples does not pay)
-bool DeviceDataset::Impl::hist_qof(std::string* err) {
-    auto& h = hist;
-    if (h.qof_built) return true;
-    std::vector<uint32_t> q_of_pos(np, IDX_INVALID), qof(h.n);
-    for (size_t q = 0; q < nq; q++)
-        for (uint32_t j = 0; j < qlen_h[q]; j++) q_of_pos[qstart_h[q] + j] = (uint32_t)q;
-    h.qof_ok = true;
-    for (size_t i = 0; i < h.n; i++) {
-        qof[i] = q_of_pos[h.pos_host[i]];
-        if (qof[i] == IDX_INVALID) h.qof_ok = false, qof[i] = 0;
-    }
-    if (!upload(h.qof, qof, err)) return false;
-    h.qof_built = true;
-    return true;
-}
-
-bool DeviceDataset::hist_sample(const unsigned char* query_flags, uint32_t n_t, const uint32_t* fsel, size_t f_t, std::string* err,
-                                bool keep_queries) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    auto& h = m.hist;
-    if (h.k == 0) return hist_fail(err, "no bins built");
-    const uint32_t n = h.n;
-    if (keep_queries && query_flags == nullptr && h.q_sampled) {  // (the root list and its length stay)
-        n_t = h.nt;
-        h.Ft = h.F, h.f_sampled = false;
-    } else {
-        h.nt = n, h.Ft = h.F, h.q_sampled = h.f_sampled = false;
-    }
-    if (fsel != nullptr) {
-        if (f_t == 0 || f_t > h.F) return hist_fail(err, "a feature sample must hold between 1 and all of the features");
-        for (size_t i = 0; i < f_t; i++)
-            if (fsel[i] >= h.F || (i > 0 && fsel[i] <= fsel[i - 1])) return hist_fail(err, "a feature sample must be ascending slots of the bin matrix");
-        if (!h.fsel.ensure(h.F, err)) return false;
-        FR_HIP(hipMemcpyAsync(h.fsel.p, fsel, f_t * sizeof(uint32_t), hipMemcpyHostToDevice, m.stream));
-    }
-    uint32_t total = n_t;
-    if (query_flags != nullptr) {
-        if (!m.hist_qof(err)) return false;
-        if (!h.qof_ok) return hist_fail(err, "an instance of the list belongs to no query of the dataset: no query sample");
-        if (n_t == 0 || n_t > n) return hist_fail(err, "a query sample must hold between 1 and all of the instances");
-        if (!h.qflag.ensure(m.nq, err) || !h.root.ensure(n, err) || !h.flag.ensure(n, err) || !h.scan.ensure(n, err) || !h.total.ensure(1, err))
-            return false;
-        FR_HIP(hipMemcpyAsync(h.qflag.p, query_flags, m.nq, hipMemcpyHostToDevice, m.stream));
-        ProfScope ps("hist_rootlist", m.stream);
-        hist_qflag_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(h.qof.p, h.qflag.p, n, h.flag.p);
-        size_t tb = 0;
-        FR_HIP(rocprim::exclusive_scan(nullptr, tb, h.flag.p, h.scan.p, 0u, (size_t)n, rocprim::plus<uint32_t>(), m.stream));
-        if (tb > h.temp.bytes()) {
-            FR_HIP(hipStreamSynchronize(m.stream));  // (no earlier user of the scratch is in flight)
-            if (!h.temp.ensure(tb, err)) return false;
-        }
-        FR_HIP(rocprim::exclusive_scan((void*)h.temp.p, tb, h.flag.p, h.scan.p, 0u, (size_t)n, rocprim::plus<uint32_t>(), m.stream));
-        hist_rootlist_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(h.flag.p, h.scan.p, n, n_t, h.root.p, h.total.p);
-        FR_HIP(hipGetLastError());
-        FR_HIP(hipMemcpyAsync(&total, h.total.p, sizeof(uint32_t), hipMemcpyDeviceToHost, m.stream));
-    }
-    FR_HIP(hipStreamSynchronize(m.stream));  // (query_flags / fsel are the caller's pageable memory)
-    if (total != n_t) return hist_fail(err, "internal error: the query sample holds " + std::to_string(total) + " instances, not " + std::to_string(n_t));
-    if (query_flags != nullptr) h.nt = n_t, h.q_sampled = true;
-    if (fsel != nullptr) h.Ft = (uint32_t)f_t, h.f_sampled = true;
-    return true;
-}
-
-bool DeviceDataset::hist_quantise(const double* lam_list, const double* wt_list, int* s_l, int* s_w, bool* all_zero, std::string* err) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    auto& h = m.hist;
-    if (h.k == 0) return hist_fail(err, "no bins built");
-    const uint32_t n = h.n, nt = h.nt;  // (host arrays and Q / W: the full list; the maxima, c and the quantisation: the tree's)
-    const double *lam = nullptr, *wt = nullptr;
-    const uint32_t *pos = nullptr, *root = h.q_sampled ? h.root.p : nullptr;
-    if (lam_list != nullptr) {
-        if (!h.lam_in.ensure(n, err) || !h.wt_in.ensure(n, err)) return false;
-        FR_HIP(hipMemcpyAsync(h.lam_in.p, lam_list, n * sizeof(double), hipMemcpyHostToDevice, m.stream));
-        FR_HIP(hipMemcpyAsync(h.wt_in.p, wt_list, n * sizeof(double), hipMemcpyHostToDevice, m.stream));
-        lam = h.lam_in.p, wt = h.wt_in.p;
-    } else {
-        if (!m.lm.built) return hist_fail(err, "no gradients computed");
-        lam = m.lm.lam.p, wt = m.lm.wt.p, pos = h.pos.p;
-    }
-    if (!h.absmax.ensure(2, err) || !h.Q.ensure(n, err) || !h.W.ensure(n, err)) return false;
-    FR_HIP(hipMemsetAsync(h.absmax.p, 0, 2 * sizeof(unsigned long long), m.stream));
-    {
-        ProfScope ps("hist_absmax_kernel", m.stream);
-        hist_absmax_kernel<<<std::min<unsigned>(grid1d(nt, 256).x, 1024u), 256, 0, m.stream>>>(lam, wt, pos, root, nt, h.absmax.p);
-    }
-    unsigned long long bits[2] = {0, 0};
-    FR_HIP(hipMemcpyAsync(bits, h.absmax.p, sizeof(bits), hipMemcpyDeviceToHost, m.stream));
-    FR_HIP(hipStreamSynchronize(m.stream));
-    double mx[2];
-    std::memcpy(mx, bits, sizeof(mx));
-    if (!std::isfinite(mx[0]) || !std::isfinite(mx[1])) return hist_fail(err, "a gradient is not finite");
-    *all_zero = mx[0] == 0.0;
-    *s_l = *s_w = 0;
-    if (*all_zero) return true;
-    uint32_t c = 0;  // ceil(log2(n + 1)) = the bit length of n
-    for (uint32_t x = nt; x != 0; x >>= 1) c++;
-    int e = 0;
-    (void)std::frexp(mx[0], &e);
-    *s_l = 61 - e - (int)c;
-    if (mx[1] != 0.0) {
-        (void)std::frexp(mx[1], &e);
-        *s_w = 61 - e - (int)c;
-    }
-    ProfScope ps("hist_quant_kernel", m.stream);
-    hist_quant_kernel<<<grid1d(nt, 256), 256, 0, m.stream>>>(lam, wt, pos, root, nt, *s_l, *s_w, mx[1] == 0.0 ? 1 : 0, h.Q.p, h.W.p);
-    FR_HIP(hipGetLastError());
-    return true;
-}
-
-// the stretches cut into pieces of at most HIST_CHUNK entries (slot carried along): one workgroup each
-bool DeviceDataset::Impl::hist_items(const std::vector<HistItemDev>& stretches, std::vector<HistItemDev>& host, DevBuf<HistItemDev>& dev,
-                                     std::string* err) {
-    host.clear();
-    for (const HistItemDev& s : stretches)
-        for (uint32_t b = s.begin; b < s.end; b += HIST_CHUNK) host.push_back({s.slot, b, std::min(s.end, b + HIST_CHUNK)});
-    if (host.empty()) return true;
-    if (!dev.ensure(host.size(), err)) return false;
-    FR_HIP(hipMemcpyAsync(dev.p, host.data(), host.size() * sizeof(HistItemDev), hipMemcpyHostToDevice, stream));
-    return true;
-}
-
-void DeviceDataset::Impl::hist_build(uint32_t* cnt, unsigned long long* sum) {
-    auto& h = hist;
-    ProfScope ps("hist_build_kernel", stream);
-    const dim3 grid((unsigned)h.items_bh.size(), (h.Ft + HIST_FB - 1) / HIST_FB);
-    const size_t lds = (size_t)HIST_FB * h.k * 12;
-    if (h.f_sampled)
-        hist_build_kernel<true><<<grid, 256, lds, stream>>>(h.items_b.p, h.xbin.p, h.n, h.idx.p, h.Q.p, h.fsel.p, h.Ft, h.k, cnt, sum);
-    else
-        hist_build_kernel<false><<<grid, 256, lds, stream>>>(h.items_b.p, h.xbin.p, h.n, h.idx.p, h.Q.p, nullptr, h.Ft, h.k, cnt, sum);
-}
-
-void DeviceDataset::Impl::hist_build_newton(uint32_t* cnt, unsigned long long* sum, unsigned long long* wsum) {
-    auto& h = hist;
-    ProfScope ps("hist_build_newton_kernel", stream);
-    const dim3 grid((unsigned)h.items_bh.size(), (h.Ft + HIST_FB_NEWTON - 1) / HIST_FB_NEWTON);
-    const size_t lds = (size_t)HIST_FB_NEWTON * h.k * 20;
-    if (h.f_sampled)
-        hist_build_newton_kernel<true><<<grid, 256, lds, stream>>>(h.items_b.p, h.xbin.p, h.n, h.idx.p, h.Q.p, h.W.p, h.fsel.p, h.Ft, h.k, cnt, sum, wsum);
-    else
-        hist_build_newton_kernel<false><<<grid, 256, lds, stream>>>(h.items_b.p, h.xbin.p, h.n, h.idx.p, h.Q.p, h.W.p, nullptr, h.Ft, h.k, cnt, sum, wsum);
-}
-
-static bool hist_level_alloc(DevBuf<uint32_t>& cnt, DevBuf<unsigned long long>& sum, size_t cells, std::string* err) {
-    std::string e2;
-    if (!cnt.ensure(cells, &e2) || !sum.ensure(cells, &e2)) {
-        (void)hipGetLastError();
-        return hist_fail(err, "no device memory for a level's histograms (" + std::to_string((cells * 12) >> 20) +
-                                  " MB: open nodes x features x bins x 12 bytes); lower max_depth or split_candidates");
-    }
-    return true;
-}
-
-// the Newton gain's third array of a level: the same plain error when it does not fit
-static bool hist_level_alloc_w(DevBuf<unsigned long long>& wsum, size_t cells, std::string* err) {
-    std::string e2;
-    if (!wsum.ensure(cells, &e2)) {
-        (void)hipGetLastError();
-        return hist_fail(err, "no device memory for a level's histograms (" + std::to_string((cells * 20) >> 20) +
-                                  " MB: open nodes x features x bins x 20 bytes under the Newton gain); lower max_depth or split_candidates");
-    }
-    return true;
-}
-
-bool DeviceDataset::hist_root(std::string* err, bool newton) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    auto& h = m.hist;
-    if (h.k == 0) return hist_fail(err, "no bins built");
-    const uint32_t n = h.nt;  // the tree's instances: the index list's length (the bin matrix's rows hold h.n)
-    const size_t fk = (size_t)h.Ft * h.k;
-    if (!h.idx.ensure(h.n, err) || !h.idx_o.ensure(h.n, err) || !h.flag.ensure(h.n, err) || !h.scan.ensure(h.n, err)) return false;
-    if (!hist_level_alloc(h.cnt, h.sum, fk, err)) return false;
-    if (newton && !hist_level_alloc_w(h.wsum, fk, err)) return false;
-    FR_HIP(hipMemsetAsync(h.flag.p, 0, n * sizeof(uint32_t), m.stream));
-    FR_HIP(hipMemsetAsync(h.cnt.p, 0, fk * sizeof(uint32_t), m.stream));
-    FR_HIP(hipMemsetAsync(h.sum.p, 0, fk * sizeof(unsigned long long), m.stream));
-    if (newton) FR_HIP(hipMemsetAsync(h.wsum.p, 0, fk * sizeof(unsigned long long), m.stream));
-    if (h.q_sampled) {
-        FR_HIP(hipMemcpyAsync(h.idx.p, h.root.p, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, m.stream));
-    } else {
-        hist_iota_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(h.idx.p, n);
-    }
-    if (!m.hist_items({{0u, 0u, n}}, h.items_bh, h.items_b, err)) return false;
-    if (newton) m.hist_build_newton(h.cnt.p, h.sum.p, h.wsum.p);
-    else m.hist_build(h.cnt.p, h.sum.p);
-    FR_HIP(hipGetLastError());
-    return true;
-}
-
-bool DeviceDataset::hist_search(const std::vector<HistNode>& nodes, uint32_t min_leaf, std::vector<HistBest>* best, std::string* err) {
-    static_assert(sizeof(HistBest) == sizeof(HistBestDev) && sizeof(HistNode) == sizeof(HistItemDev), "host and device records differ");
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    auto& h = m.hist;
-    const size_t A = nodes.size();
-    best->assign(A * h.Ft, HistBest{});
-    if (A == 0) return true;
-    const size_t fk = (size_t)h.Ft * h.k;
-    h.nodes_h.resize(A);
-    for (size_t a = 0; a < A; a++) {
-        if ((size_t)(nodes[a].slot + 1) * fk > h.cnt.cap || nodes[a].end > h.nt || nodes[a].begin > nodes[a].end)
-            return hist_fail(err, "internal error: a node outside the level's histograms");
-        h.nodes_h[a] = {nodes[a].slot, nodes[a].begin, nodes[a].end};
-    }
-    if (!h.nodes.ensure(A, err) || !h.best.ensure(A * h.Ft, err)) return false;
-    FR_HIP(hipMemcpyAsync(h.nodes.p, h.nodes_h.data(), A * sizeof(HistItemDev), hipMemcpyHostToDevice, m.stream));
-    {
-        ProfScope ps("hist_scan_kernel", m.stream);
-        hist_scan_kernel<<<(unsigned)(A * h.Ft), 64, 0, m.stream>>>(h.nodes.p, h.Ft, h.k, h.nedges.p, h.f_sampled ? h.fsel.p : nullptr, h.cnt.p,
-                                                                    h.sum.p, min_leaf, h.best.p);
-    }
-    FR_HIP(hipGetLastError());
-    FR_HIP(hipMemcpyAsync(best->data(), h.best.p, A * h.Ft * sizeof(HistBestDev), hipMemcpyDeviceToHost, m.stream));
-    FR_HIP(hipStreamSynchronize(m.stream));
-    return true;
-}
-
-bool DeviceDataset::hist_search_newton(const std::vector<HistNode>& nodes, uint32_t min_leaf, int s_l, int s_w, double lambda_l2,
-                                       double min_sum_hessian, std::vector<HistBestNewton>* best, std::string* err) {
-    static_assert(sizeof(HistBestNewton) == sizeof(HistBestNewtonDev), "host and device records differ");
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    auto& h = m.hist;
-    const size_t A = nodes.size();
-    best->assign(A * h.Ft, HistBestNewton{});
-    if (A == 0) return true;
-    const size_t fk = (size_t)h.Ft * h.k;
-    h.nodes_h.resize(A);
-    for (size_t a = 0; a < A; a++) {
-        if ((size_t)(nodes[a].slot + 1) * fk > h.cnt.cap || (size_t)(nodes[a].slot + 1) * fk > h.wsum.cap || nodes[a].end > h.nt ||
-            nodes[a].begin > nodes[a].end)
-            return hist_fail(err, "internal error: a node outside the level's histograms");
-        h.nodes_h[a] = {nodes[a].slot, nodes[a].begin, nodes[a].end};
-    }
-    if (!h.nodes.ensure(A, err) || !h.best_n.ensure(A * h.Ft, err)) return false;
-    FR_HIP(hipMemcpyAsync(h.nodes.p, h.nodes_h.data(), A * sizeof(HistItemDev), hipMemcpyHostToDevice, m.stream));
-    {
-        ProfScope ps("hist_scan_newton_kernel", m.stream);
-        hist_scan_newton_kernel<<<(unsigned)(A * h.Ft), 64, 0, m.stream>>>(h.nodes.p, h.Ft, h.k, h.nedges.p, h.f_sampled ? h.fsel.p : nullptr,
-                                                                           h.cnt.p, h.sum.p, h.wsum.p, min_leaf, s_l, s_w, lambda_l2,
-                                                                           min_sum_hessian, h.best_n.p);
-    }
-    FR_HIP(hipGetLastError());
-    FR_HIP(hipMemcpyAsync(best->data(), h.best_n.p, A * h.Ft * sizeof(HistBestNewtonDev), hipMemcpyDeviceToHost, m.stream));
-    FR_HIP(hipStreamSynchronize(m.stream));
-    return true;
-}
-
-bool DeviceDataset::hist_monotone(const int* signs, size_t features, std::string* err) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    auto& h = m.hist;
-    if (h.k == 0) return hist_fail(err, "no bins built");
-    if (signs == nullptr || features != h.F) return hist_fail(err, "internal error: the monotone signs do not cover the bin matrix's rows");
-    for (size_t i = 0; i < features; i++)
-        if (signs[i] < -1 || signs[i] > 1) return hist_fail(err, "internal error: a monotone sign outside {-1, 0, 1}");
-    h.mono_F = 0;
-    if (!h.mono.ensure(features, err)) return false;
-    FR_HIP(hipMemcpyAsync(h.mono.p, signs, features * sizeof(int), hipMemcpyHostToDevice, m.stream));
-    FR_HIP(hipStreamSynchronize(m.stream));  // (signs is the caller's pageable memory)
-    h.mono_F = (uint32_t)features;
-    return true;
-}
-
-bool DeviceDataset::hist_search_monotone(const std::vector<HistNode>& nodes, const std::vector<HistBounds>& bounds, uint32_t min_leaf, int s_l,
-                                         int s_w, double lambda_l2, double min_sum_hessian, std::vector<HistBestNewton>* best,
-                                         std::string* err) {
-    static_assert(sizeof(HistBounds) == sizeof(HistBoundsDev), "host and device records differ");
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    auto& h = m.hist;
-    const size_t A = nodes.size();
-    best->assign(A * h.Ft, HistBestNewton{});
-    if (A == 0) return true;
-    if (bounds.size() != A) return hist_fail(err, "internal error: one interval per node is needed");
-    if (h.mono_F == 0 || h.mono_F != h.F) return hist_fail(err, "internal error: no monotone signs set for these bins");
-    const size_t fk = (size_t)h.Ft * h.k;
-    h.nodes_h.resize(A);
-    for (size_t a = 0; a < A; a++) {
-        if ((size_t)(nodes[a].slot + 1) * fk > h.cnt.cap || (size_t)(nodes[a].slot + 1) * fk > h.wsum.cap || nodes[a].end > h.nt ||
-            nodes[a].begin > nodes[a].end)
-            return hist_fail(err, "internal error: a node outside the level's histograms");
-        h.nodes_h[a] = {nodes[a].slot, nodes[a].begin, nodes[a].end};
-    }
-    if (!h.nodes.ensure(A, err) || !h.bounds.ensure(A, err) || !h.best_n.ensure(A * h.Ft, err)) return false;
-    FR_HIP(hipMemcpyAsync(h.nodes.p, h.nodes_h.data(), A * sizeof(HistItemDev), hipMemcpyHostToDevice, m.stream));
-    FR_HIP(hipMemcpyAsync(h.bounds.p, bounds.data(), A * sizeof(HistBoundsDev), hipMemcpyHostToDevice, m.stream));
-    {
-        ProfScope ps("hist_scan_monotone_kernel", m.stream);
-        hist_scan_monotone_kernel<<<(unsigned)(A * h.Ft), 64, 0, m.stream>>>(h.nodes.p, h.bounds.p, h.Ft, h.k, h.nedges.p, h.mono.p,
-                                                                             h.f_sampled ? h.fsel.p : nullptr, h.cnt.p, h.sum.p, h.wsum.p, min_leaf,
-                                                                             s_l, s_w, lambda_l2, min_sum_hessian, h.best_n.p);
-    }
-    FR_HIP(hipGetLastError());
-    FR_HIP(hipMemcpyAsync(best->data(), h.best_n.p, A * h.Ft * sizeof(HistBestNewtonDev), hipMemcpyDeviceToHost, m.stream));
-    FR_HIP(hipStreamSynchronize(m.stream));  // (bounds is the caller's, read by the copy above until here)
-    return true;
-}
-
-bool DeviceDataset::hist_split(const std::vector<HistSplit>& splits, const std::vector<HistNode>& builds, const std::vector<HistSub>& subs,
-                               uint32_t next_slots, std::string* err, bool newton) {
-    static_assert(sizeof(HistSplit) == sizeof(HistSplitDev) && sizeof(HistSub) == sizeof(HistSubDev), "host and device records differ");
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    auto& h = m.hist;
-    const uint32_t n = h.nt;  // the index list's length; the bin matrix's rows hold h.n entries
-    const size_t fk = (size_t)h.Ft * h.k;
-    if (!splits.empty()) {
-        std::vector<HistItemDev> stretches(splits.size());
-        h.splits_h.resize(splits.size());
-        for (size_t i = 0; i < splits.size(); i++) {
-            const HistSplit& s = splits[i];
-            if (s.begin >= s.end || s.end > n || s.nl > s.end - s.begin || s.fslot >= h.F || s.edge >= h.k)
-                return hist_fail(err, "internal error: a split outside the index list");
-            h.splits_h[i] = {s.begin, s.end, s.fslot, s.edge, s.nl};
-            stretches[i] = {(uint32_t)i, s.begin, s.end};
-        }
-        if (!h.splits.ensure(splits.size(), err) || !m.hist_items(stretches, h.items_h, h.items, err)) return false;
-        FR_HIP(hipMemcpyAsync(h.splits.p, h.splits_h.data(), splits.size() * sizeof(HistSplitDev), hipMemcpyHostToDevice, m.stream));
-        const unsigned g = (unsigned)h.items_h.size();
-        ProfScope ps("hist_partition", m.stream);
-        hist_flag_kernel<<<g, 256, 0, m.stream>>>(h.items.p, h.splits.p, h.xbin.p, h.n, h.idx.p, h.flag.p);
-        size_t tb = 0;
-        FR_HIP(rocprim::exclusive_scan(nullptr, tb, h.flag.p, h.scan.p, 0u, (size_t)n, rocprim::plus<uint32_t>(), m.stream));
-        if (tb > h.temp.bytes()) {
-            FR_HIP(hipStreamSynchronize(m.stream));  // (the sort's scratch is not in use: binning has been waited for)
-            if (!h.temp.ensure(tb, err)) return false;
-        }
-        FR_HIP(rocprim::exclusive_scan((void*)h.temp.p, tb, h.flag.p, h.scan.p, 0u, (size_t)n, rocprim::plus<uint32_t>(), m.stream));
-        hist_scatter_kernel<<<g, 256, 0, m.stream>>>(h.items.p, h.splits.p, h.flag.p, h.scan.p, h.idx.p, h.idx_o.p);
-        hist_copy_kernel<<<g, 256, 0, m.stream>>>(h.items.p, h.idx_o.p, h.idx.p);
-        FR_HIP(hipGetLastError());
-    }
-    if (next_slots == 0) return true;
-    // the next level's histograms: the smaller child of every pair from its stretch, the larger by subtraction
-    if (!hist_level_alloc(h.cnt_o, h.sum_o, (size_t)next_slots * fk, err)) return false;
-    FR_HIP(hipMemsetAsync(h.cnt_o.p, 0, (size_t)next_slots * fk * sizeof(uint32_t), m.stream));
-    FR_HIP(hipMemsetAsync(h.sum_o.p, 0, (size_t)next_slots * fk * sizeof(unsigned long long), m.stream));
-    if (newton) {
-        if (!hist_level_alloc_w(h.wsum_o, (size_t)next_slots * fk, err)) return false;
-        FR_HIP(hipMemsetAsync(h.wsum_o.p, 0, (size_t)next_slots * fk * sizeof(unsigned long long), m.stream));
-    }
-    std::vector<HistItemDev> stretches(builds.size());
-    for (size_t i = 0; i < builds.size(); i++) {
-        if (builds[i].slot >= next_slots || builds[i].end > n || builds[i].begin > builds[i].end)
-            return hist_fail(err, "internal error: a child outside the next level");
-        stretches[i] = {builds[i].slot, builds[i].begin, builds[i].end};
-    }
-    if (!m.hist_items(stretches, h.items_bh, h.items_b, err)) return false;
-    if (!h.items_bh.empty()) {
-        if (newton) m.hist_build_newton(h.cnt_o.p, h.sum_o.p, h.wsum_o.p);
-        else m.hist_build(h.cnt_o.p, h.sum_o.p);
-    }
-    if (!subs.empty()) {
-        h.subs_h.resize(subs.size());
-        for (size_t i = 0; i < subs.size(); i++) {
-            if ((size_t)(subs[i].parent + 1) * fk > h.cnt.cap || (newton && (size_t)(subs[i].parent + 1) * fk > h.wsum.cap) || subs[i].small >= next_slots || subs[i].large >= next_slots)
-                return hist_fail(err, "internal error: a subtraction outside the histograms");
-            h.subs_h[i] = {subs[i].parent, subs[i].small, subs[i].large};
-        }
-        if (!h.subs.ensure(subs.size(), err)) return false;
-        FR_HIP(hipMemcpyAsync(h.subs.p, h.subs_h.data(), subs.size() * sizeof(HistSubDev), hipMemcpyHostToDevice, m.stream));
-        if (newton) {
-            ProfScope ps("hist_sub_newton_kernel", m.stream);
-            hist_sub_newton_kernel<<<dim3((unsigned)subs.size(), (unsigned)((fk + 255) / 256)), 256, 0, m.stream>>>(
-                h.subs.p, (uint32_t)fk, h.cnt.p, h.sum.p, h.wsum.p, h.cnt_o.p, h.sum_o.p, h.wsum_o.p);
-        } else {
-            ProfScope ps("hist_sub_kernel", m.stream);
-            hist_sub_kernel<<<dim3((unsigned)subs.size(), (unsigned)((fk + 255) / 256)), 256, 0, m.stream>>>(h.subs.p, (uint32_t)fk, h.cnt.p, h.sum.p,
-                                                                                                           h.cnt_o.p, h.sum_o.p);
-        }
-    }
-    FR_HIP(hipGetLastError());
-    std::swap(h.cnt.p, h.cnt_o.p), std::swap(h.cnt.cap, h.cnt_o.cap);
-    std::swap(h.sum.p, h.sum_o.p), std::swap(h.sum.cap, h.sum_o.cap);
-    if (newton) std::swap(h.wsum.p, h.wsum_o.p), std::swap(h.wsum.cap, h.wsum_o.cap);
-    return true;
-}
-
-bool DeviceDataset::hist_leaf_sums(const std::vector<HistNode>& leaves, std::vector<long long>* qw, std::string* err) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    auto& h = m.hist;
-    const size_t L = leaves.size();
-    qw->assign(L * 2, 0);
-    if (L == 0) return true;
-    std::vector<HistItemDev> stretches(L);
-    for (size_t i = 0; i < L; i++) {
-        if (leaves[i].end > h.nt || leaves[i].begin > leaves[i].end) return hist_fail(err, "internal error: a leaf outside the index list");
-        stretches[i] = {(uint32_t)i, leaves[i].begin, leaves[i].end};
-    }
-    FR_HIP(hipStreamSynchronize(m.stream));  // (hist.items is about to be rewritten)
-    if (!h.leaf.ensure(L * 2, err) || !m.hist_items(stretches, h.items_h, h.items, err)) return false;
-    FR_HIP(hipMemsetAsync(h.leaf.p, 0, L * 2 * sizeof(unsigned long long), m.stream));
-    if (!h.items_h.empty()) {
-        ProfScope ps("hist_leafsum_kernel", m.stream);
-        hist_leafsum_kernel<<<(unsigned)h.items_h.size(), 256, 0, m.stream>>>(h.items.p, h.idx.p, h.Q.p, h.W.p, h.leaf.p);
-    }
-    FR_HIP(hipGetLastError());
-    FR_HIP(hipMemcpyAsync(qw->data(), h.leaf.p, L * 2 * sizeof(long long), hipMemcpyDeviceToHost, m.stream));
-    FR_HIP(hipStreamSynchronize(m.stream));
-    return true;
-}
-
-void DeviceDataset::hist_end() {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    auto& h = m.hist;
-    (void)hipStreamSynchronize(m.stream);
-    h.cnt.release(), h.cnt_o.release(), h.sum.release(), h.sum_o.release(), h.wsum.release(), h.wsum_o.release(), h.best.release(), h.best_n.release(), h.lam_in.release(), h.wt_in.release();
-    h.pcnt.release(), h.psum.release(), h.pwsum.release(), h.rec.release(), h.pick.release(), h.bounds.release();
-    h.pool_slots = 0;
-}
-
-// --- leaf-wise growth (kernels_hist.inc, "Leaf-wise growth") ---
-
-// scan (after deriving where asked) and pick of `count` children, their records to out[0..count); waits for the stream
-bool DeviceDataset::Impl::hist_leaf_scan(const HistLeafKids& kids, uint32_t count, const DeviceDataset::HistLeafSearch& how,
-                                         DeviceDataset::HistPick* out, std::string* err, const HistLeafBoundsDev* bounds) {
-    static_assert(sizeof(DeviceDataset::HistPick) == sizeof(HistPickDev), "host and device records differ");
-    auto& h = hist;
-    if (!h.rec.ensure((size_t)2 * h.Ft, err) || !h.pick.ensure(2, err)) return false;
-    const uint32_t* fsel = h.f_sampled ? h.fsel.p : nullptr;
-    if (how.monotone) {
-        if (!how.newton || bounds == nullptr || h.mono_F == 0 || h.mono_F != h.F)
-            return hist_fail(err, "internal error: no monotone signs set for these bins");
-        ProfScope ps("hist_leaf_scan_monotone_kernel", stream);
-        hist_leaf_scan_monotone_kernel<<<dim3(h.Ft, count), 64, 0, stream>>>(kids, *bounds, h.Ft, h.k, h.nedges.p, h.mono.p, fsel, h.pcnt.p, h.psum.p,
-                                                                             h.pwsum.p, how.min_leaf, how.s_l, how.s_w, how.lambda_l2,
-                                                                             how.min_sum_hessian, h.rec.p);
-    } else {
-        ProfScope ps(how.newton ? "hist_leaf_scan_kernel<newton>" : "hist_leaf_scan_kernel", stream);
-        const dim3 grid(h.Ft, count);
-        if (how.newton)
-            hist_leaf_scan_kernel<true><<<grid, 64, 0, stream>>>(kids, h.Ft, h.k, h.nedges.p, fsel, h.pcnt.p, h.psum.p, h.pwsum.p, how.min_leaf,
-                                                                 how.s_l, how.s_w, how.lambda_l2, how.min_sum_hessian, h.rec.p);
-        else
-            hist_leaf_scan_kernel<false><<<grid, 64, 0, stream>>>(kids, h.Ft, h.k, h.nedges.p, fsel, h.pcnt.p, h.psum.p, nullptr, how.min_leaf, 0, 0,
-                                                                  0.0, 0.0, h.rec.p);
-    }
-    {
-        ProfScope ps("hist_pick_kernel", stream);
-        hist_pick_kernel<<<count, 64, 0, stream>>>(h.rec.p, h.Ft, h.pick.p);
-    }
-    FR_HIP(hipGetLastError());
-    FR_HIP(hipMemcpyAsync(out, h.pick.p, count * sizeof(HistPickDev), hipMemcpyDeviceToHost, stream));
-    FR_HIP(hipStreamSynchronize(stream));
-    return true;
-}
-
-bool DeviceDataset::hist_leaf_begin(uint32_t slots, const HistLeafSearch& how, HistPick* root, std::string* err) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    auto& h = m.hist;
-    if (h.k == 0) return hist_fail(err, "no bins built");
-    if (slots == 0) return hist_fail(err, "internal error: an empty histogram pool");
-    const uint32_t n = h.nt;
-    const size_t fk = (size_t)h.Ft * h.k, cells = (size_t)slots * fk;
-    if (!h.idx.ensure(h.n, err) || !h.idx_o.ensure(h.n, err) || !h.flag.ensure(h.n, err) || !h.scan.ensure(h.n, err)) return false;
-    {
-        std::string e2;
-        if (!h.pcnt.ensure(cells, &e2) || !h.psum.ensure(cells, &e2) || (how.newton && !h.pwsum.ensure(cells, &e2))) {
-            (void)hipGetLastError();
-            h.pool_slots = 0;
-            return hist_fail(err, "no device memory for the leaf-wise histogram pool (" + std::to_string((cells * (how.newton ? 20 : 12)) >> 20) +
-                                      " MB: max_leaves x features x bins x " + (how.newton ? "20" : "12") + " bytes); lower max_leaves or split_candidates");
-        }
-    }
-    h.pool_slots = slots;
-    FR_HIP(hipMemsetAsync(h.pcnt.p, 0, fk * sizeof(uint32_t), m.stream));
-    FR_HIP(hipMemsetAsync(h.psum.p, 0, fk * sizeof(unsigned long long), m.stream));
-    if (how.newton) FR_HIP(hipMemsetAsync(h.pwsum.p, 0, fk * sizeof(unsigned long long), m.stream));
-    if (h.q_sampled) {
-        FR_HIP(hipMemcpyAsync(h.idx.p, h.root.p, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, m.stream));
-    } else {
-        hist_iota_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(h.idx.p, n);
-    }
-    if (!m.hist_items({{0u, 0u, n}}, h.items_bh, h.items_b, err)) return false;
-    if (how.newton) m.hist_build_newton(h.pcnt.p, h.psum.p, h.pwsum.p);
-    else m.hist_build(h.pcnt.p, h.psum.p);
-    FR_HIP(hipGetLastError());
-    HistLeafKids kids{};
-    kids.slot[0] = 0, kids.n[0] = n;
-    HistLeafBoundsDev whole{};  // (the root's interval: the whole line)
-    whole.lo[0] = whole.lo[1] = -std::numeric_limits<double>::infinity();
-    whole.hi[0] = whole.hi[1] = std::numeric_limits<double>::infinity();
-    return m.hist_leaf_scan(kids, 1, how, root, err, &whole);
-}
-
-bool DeviceDataset::hist_leaf_step(const HistLeafStep& step, const HistLeafSearch& how, HistPick pick[2], std::string* err) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    auto& h = m.hist;
-    const HistSplit& s = step.split;
-    const size_t fk = (size_t)h.Ft * h.k;
-    const bool build = step.small_slot != HIST_NO_SLOT;
-    if (s.begin >= s.end || s.end > h.nt || s.nl == 0 || s.nl >= s.end - s.begin || s.fslot >= h.F || s.edge >= h.k)
-        return hist_fail(err, "internal error: a split outside the index list");
-    if (h.pool_slots == 0 || step.parent_slot >= h.pool_slots || (build && (step.small_slot >= h.pool_slots || step.small_slot == step.parent_slot)) ||
-        ((step.search_lhs || step.search_rhs) && !build))
-        return hist_fail(err, "internal error: a step outside the histogram pool");
-    const uint32_t n = s.end - s.begin, nr = n - s.nl;
-    {
-        ProfScope ps("hist_leaf_partition", m.stream);
-        const dim3 g = grid1d(n, 256);
-        hist_leaf_flag_kernel<<<g, 256, 0, m.stream>>>(s.begin, s.end, h.xbin.p + (size_t)s.fslot * h.n, s.edge, h.idx.p, h.flag.p);
-        size_t tb = 0;
-        FR_HIP(rocprim::exclusive_scan(nullptr, tb, h.flag.p + s.begin, h.scan.p + s.begin, 0u, (size_t)n, rocprim::plus<uint32_t>(), m.stream));
-        if (tb > h.temp.bytes()) {
-            FR_HIP(hipStreamSynchronize(m.stream));
-            if (!h.temp.ensure(tb, err)) return false;
-        }
-        FR_HIP(rocprim::exclusive_scan((void*)h.temp.p, tb, h.flag.p + s.begin, h.scan.p + s.begin, 0u, (size_t)n, rocprim::plus<uint32_t>(), m.stream));
-        hist_leaf_scatter_kernel<<<g, 256, 0, m.stream>>>(s.begin, s.end, s.nl, h.flag.p, h.scan.p, h.idx.p, h.idx_o.p);
-        FR_HIP(hipMemcpyAsync(h.idx.p + s.begin, h.idx_o.p + s.begin, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, m.stream));
-        FR_HIP(hipGetLastError());
-    }
-    if (!build) return true;
-    // the smaller child from its stretch (the lhs when the two are equal)
-    const bool left_small = s.nl <= nr;
-    const size_t off = (size_t)step.small_slot * fk;
-    FR_HIP(hipMemsetAsync(h.pcnt.p + off, 0, fk * sizeof(uint32_t), m.stream));
-    FR_HIP(hipMemsetAsync(h.psum.p + off, 0, fk * sizeof(unsigned long long), m.stream));
-    if (how.newton) FR_HIP(hipMemsetAsync(h.pwsum.p + off, 0, fk * sizeof(unsigned long long), m.stream));
-    const uint32_t mid = s.begin + s.nl;
-    if (!m.hist_items({left_small ? HistItemDev{step.small_slot, s.begin, mid} : HistItemDev{step.small_slot, mid, s.end}}, h.items_bh, h.items_b, err))
-        return false;
-    if (how.newton) m.hist_build_newton(h.pcnt.p, h.psum.p, h.pwsum.p);
-    else m.hist_build(h.pcnt.p, h.psum.p);
-    FR_HIP(hipGetLastError());
-    // the children to scan, the lhs first; the larger one is derived in place in its parent's slot
-    HistLeafKids kids{};
-    HistLeafBoundsDev bounds{};
-    uint32_t count = 0;
-    int where[2] = {-1, -1};
-    for (int side = 0; side < 2; side++) {
-        if (!(side == 0 ? step.search_lhs : step.search_rhs)) continue;
-        const bool small = (side == 0) == left_small;
-        kids.slot[count] = small ? step.small_slot : step.parent_slot;
-        kids.n[count] = side == 0 ? s.nl : nr;
-        kids.derive[count] = small ? 0u : 1u;
-        kids.other[count] = step.small_slot;
-        bounds.lo[count] = step.bounds[side].lo, bounds.hi[count] = step.bounds[side].hi;
-        where[side] = (int)count++;
-    }
-    if (count == 0) return true;
-    HistPick got[2];
-    if (!m.hist_leaf_scan(kids, count, how, got, err, &bounds)) return false;
-    for (int side = 0; side < 2; side++)
-        if (where[side] >= 0) pick[side] = got[where[side]];
-    return true;
-}
+#include "train_rf.inc"
+#include "train_lambda.inc"
+#include "train_dart.inc"
+#include "train_hist.inc"

@@ -1,0 +1,647 @@
+// Part of device.hip (single translation unit; see that file's header).  LambdaMART's histogram grower, level-wise and leaf-wise: the launchers of kernels_hist.inc.
+// ----------------------------------------------------------------------------------------------
+// LambdaMART histogram grower (kernels_hist.inc)
+// ----------------------------------------------------------------------------------------------
+static bool hist_fail(std::string* err, const std::string& what) {
+    if (err) *err = "LambdaMART histogram grower: " + what;
+    return false;
+}
+
+bool DeviceDataset::hist_bins(const uint32_t* positions, size_t n, const std::vector<uint32_t>& feats, uint32_t k, bool* built,
+                              std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    if (built) *built = false;
+    if (k < 2 || k > HIST_MAX_BINS) return hist_fail(err, "split_candidates must be between 2 and 256");
+    if (n == 0 || feats.empty()) return hist_fail(err, "no instances or no features");
+    if (n >= (1ull << 31)) return hist_fail(err, "more instances than the index list can hold");
+    for (uint32_t f : feats)
+        if (f >= m.d) return hist_fail(err, "feature id outside the dataset");
+    if (h.k == k && h.n == n && h.feats == feats && std::equal(h.pos_host.begin(), h.pos_host.end(), positions)) {
+        h.nt = h.n, h.Ft = h.F, h.q_sampled = h.f_sampled = false;  // (no sample until hist_sample says so)
+        return true;
+    }
+    h.k = 0;  // (nothing valid until the end of this function)
+    const size_t F = feats.size();
+    for (size_t i = 0; i < n; i++)
+        if (positions[i] >= m.np) return hist_fail(err, "instance position outside the dataset");
+    {
+        const size_t need = F * n + 3 * n * sizeof(float) + ((size_t)64 << 20), have = device_free_bytes() + h.xbin.bytes();
+        if (have != h.xbin.bytes() && have < need)
+            return hist_fail(err, "the bin matrix needs " + std::to_string(need >> 20) + " MB of device memory, " +
+                                      std::to_string(have >> 20) + " MB are free");
+    }
+    h.pos_host.assign(positions, positions + n);
+    if (!h.pos.ensure(n, err) || !h.xbin.ensure(F * n, err) || !h.edges.ensure(F * HIST_MAX_BINS, err) || !h.nedges.ensure(F, err)) return false;
+    DevBuf<float> col, sorted, firsts;
+    DevBuf<uint32_t> count;
+    DevBuf<int> nan_flag;
+    if (!col.ensure(n, err) || !sorted.ensure(n, err) || !firsts.ensure(F * (HIST_MAX_BINS + 1), err) || !count.ensure(F, err) || !nan_flag.ensure(1, err))
+        return false;
+    FR_HIP(hipMemcpyAsync(h.pos.p, h.pos_host.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, m.stream));
+    FR_HIP(hipMemsetAsync(count.p, 0, F * sizeof(uint32_t), m.stream));
+    FR_HIP(hipMemsetAsync(nan_flag.p, 0, sizeof(int), m.stream));
+    FR_HIP(hipMemsetAsync(h.edges.p, 0, F * HIST_MAX_BINS * sizeof(float), m.stream));
+    size_t temp_bytes = 0;
+    FR_HIP(rocprim::radix_sort_keys(nullptr, temp_bytes, col.p, sorted.p, n, 0u, 32u, m.stream));
+    if (!h.temp.ensure(std::max<size_t>(temp_bytes, 16), err)) return false;
+    const uint32_t n32 = (uint32_t)n;
+    {
+        ProfScope ps("hist_binning", m.stream);
+        for (size_t s = 0; s < F; s++) {
+            hist_column_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(m.xb.p, (uint32_t)m.dq, h.pos.p, n32, feats[s], col.p, nan_flag.p);
+            size_t tb = h.temp.bytes();
+            FR_HIP(rocprim::radix_sort_keys((void*)h.temp.p, tb, col.p, sorted.p, n, 0u, 32u, m.stream));
+            hist_distinct_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(sorted.p, n32, count.p + s, firsts.p + s * (HIST_MAX_BINS + 1));
+            hist_edges_kernel<<<1, 256, 0, m.stream>>>(sorted.p, n32, k, count.p + s, firsts.p + s * (HIST_MAX_BINS + 1),
+                                                       h.edges.p + s * HIST_MAX_BINS, h.nedges.p + s);
+            hist_bin_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(col.p, n32, h.edges.p + s * HIST_MAX_BINS, h.nedges.p + s, h.xbin.p + s * n);
+        }
+    }
+    FR_HIP(hipGetLastError());
+    h.edges_host.assign(F * HIST_MAX_BINS, 0.0f);
+    h.nedges_host.assign(F, 0);
+    int bad = 0;
+    FR_HIP(hipMemcpyAsync(h.edges_host.data(), h.edges.p, F * HIST_MAX_BINS * sizeof(float), hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipMemcpyAsync(h.nedges_host.data(), h.nedges.p, F * sizeof(uint32_t), hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipMemcpyAsync(&bad, nan_flag.p, sizeof(int), hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipStreamSynchronize(m.stream));
+    if (bad) return hist_fail(err, "a feature value is NaN; NaN has no bin (use the exact grower, or clean the data)");
+    for (size_t s = 0; s < F; s++)
+        if (h.nedges_host[s] >= k) return hist_fail(err, "internal error: more edges than bins");
+    h.qof_built = false;  // (made for these bins by the first query sample: hist_qof)
+    h.mono_F = 0;
+    h.feats = feats;
+    h.n = n32, h.F = (uint32_t)F, h.k = k;
+    h.nt = n32, h.Ft = (uint32_t)F, h.q_sampled = h.f_sampled = false;
+    if (built) *built = true;
+    return true;
+}
+
+bool DeviceDataset::hist_edges(std::vector<float>* edges, std::vector<uint32_t>* nedges, std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (m.hist.k == 0) return hist_fail(err, "no bins built");
+    *edges = m.hist.edges_host;
+    *nedges = m.hist.nedges_host;
+    return true;
+}
+
+bool DeviceDataset::hist_download_bins(uint8_t* out, size_t len, std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    if (h.k == 0) return hist_fail(err, "no bins built");
+    if (len != (size_t)h.F * h.n) return hist_fail(err, "bin matrix output has the wrong length");
+    FR_HIP(hipMemcpyAsync(out, h.xbin.p, len, hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipStreamSynchronize(m.stream));
+    return true;
+}
+
+// the query of every instance-list entry, for the trees' query samples: made once per bin matrix, by the first tree that
+// samples queries (4 ms of host work at the 30K shape that a request without samples does not pay)
+bool DeviceDataset::Impl::hist_qof(std::string* err) {
+    auto& h = hist;
+    if (h.qof_built) return true;
+    std::vector<uint32_t> q_of_pos(np, IDX_INVALID), qof(h.n);
+    for (size_t q = 0; q < nq; q++)
+        for (uint32_t j = 0; j < qlen_h[q]; j++) q_of_pos[qstart_h[q] + j] = (uint32_t)q;
+    h.qof_ok = true;
+    for (size_t i = 0; i < h.n; i++) {
+        qof[i] = q_of_pos[h.pos_host[i]];
+        if (qof[i] == IDX_INVALID) h.qof_ok = false, qof[i] = 0;
+    }
+    if (!upload(h.qof, qof, err)) return false;
+    h.qof_built = true;
+    return true;
+}
+
+bool DeviceDataset::Impl::hist_flag_scan(uint32_t begin, uint32_t count, std::string* err) {
+    auto& h = hist;
+    size_t tb = 0;
+    FR_HIP(rocprim::exclusive_scan(nullptr, tb, h.flag.p + begin, h.scan.p + begin, 0u, (size_t)count, rocprim::plus<uint32_t>(), stream));
+    if (tb > h.temp.bytes()) {
+        FR_HIP(hipStreamSynchronize(stream));  // (no earlier user of the scratch -- binning's sort, an earlier scan -- is in flight)
+        if (!h.temp.ensure(tb, err)) return false;
+    }
+    FR_HIP(rocprim::exclusive_scan((void*)h.temp.p, tb, h.flag.p + begin, h.scan.p + begin, 0u, (size_t)count, rocprim::plus<uint32_t>(), stream));
+    return true;
+}
+
+bool DeviceDataset::hist_sample(const unsigned char* query_flags, uint32_t n_t, const uint32_t* fsel, size_t f_t, std::string* err,
+                                bool keep_queries) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    if (h.k == 0) return hist_fail(err, "no bins built");
+    const uint32_t n = h.n;
+    if (keep_queries && query_flags == nullptr && h.q_sampled) {  // (the root list and its length stay)
+        n_t = h.nt;
+        h.Ft = h.F, h.f_sampled = false;
+    } else {
+        h.nt = n, h.Ft = h.F, h.q_sampled = h.f_sampled = false;
+    }
+    if (fsel != nullptr) {
+        if (f_t == 0 || f_t > h.F) return hist_fail(err, "a feature sample must hold between 1 and all of the features");
+        for (size_t i = 0; i < f_t; i++)
+            if (fsel[i] >= h.F || (i > 0 && fsel[i] <= fsel[i - 1])) return hist_fail(err, "a feature sample must be ascending slots of the bin matrix");
+        if (!h.fsel.ensure(h.F, err)) return false;
+        FR_HIP(hipMemcpyAsync(h.fsel.p, fsel, f_t * sizeof(uint32_t), hipMemcpyHostToDevice, m.stream));
+    }
+    uint32_t total = n_t;
+    if (query_flags != nullptr) {
+        if (!m.hist_qof(err)) return false;
+        if (!h.qof_ok) return hist_fail(err, "an instance of the list belongs to no query of the dataset: no query sample");
+        if (n_t == 0 || n_t > n) return hist_fail(err, "a query sample must hold between 1 and all of the instances");
+        if (!h.qflag.ensure(m.nq, err) || !h.root.ensure(n, err) || !h.flag.ensure(n, err) || !h.scan.ensure(n, err) || !h.total.ensure(1, err))
+            return false;
+        FR_HIP(hipMemcpyAsync(h.qflag.p, query_flags, m.nq, hipMemcpyHostToDevice, m.stream));
+        ProfScope ps("hist_rootlist", m.stream);
+        hist_qflag_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(h.qof.p, h.qflag.p, n, h.flag.p);
+        if (!m.hist_flag_scan(0, n, err)) return false;
+        hist_rootlist_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(h.flag.p, h.scan.p, n, n_t, h.root.p, h.total.p);
+        FR_HIP(hipGetLastError());
+        FR_HIP(hipMemcpyAsync(&total, h.total.p, sizeof(uint32_t), hipMemcpyDeviceToHost, m.stream));
+    }
+    FR_HIP(hipStreamSynchronize(m.stream));  // (query_flags / fsel are the caller's pageable memory)
+    if (total != n_t) return hist_fail(err, "internal error: the query sample holds " + std::to_string(total) + " instances, not " + std::to_string(n_t));
+    if (query_flags != nullptr) h.nt = n_t, h.q_sampled = true;
+    if (fsel != nullptr) h.Ft = (uint32_t)f_t, h.f_sampled = true;
+    return true;
+}
+
+bool DeviceDataset::hist_quantise(const double* lam_list, const double* wt_list, int* s_l, int* s_w, bool* all_zero, std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    if (h.k == 0) return hist_fail(err, "no bins built");
+    const uint32_t n = h.n, nt = h.nt;  // (host arrays and Q / W: the full list; the maxima, c and the quantisation: the tree's)
+    const double *lam = nullptr, *wt = nullptr;
+    const uint32_t *pos = nullptr, *root = h.q_sampled ? h.root.p : nullptr;
+    if (lam_list != nullptr) {
+        if (!h.lam_in.ensure(n, err) || !h.wt_in.ensure(n, err)) return false;
+        FR_HIP(hipMemcpyAsync(h.lam_in.p, lam_list, n * sizeof(double), hipMemcpyHostToDevice, m.stream));
+        FR_HIP(hipMemcpyAsync(h.wt_in.p, wt_list, n * sizeof(double), hipMemcpyHostToDevice, m.stream));
+        lam = h.lam_in.p, wt = h.wt_in.p;
+    } else {
+        if (!m.lm.built) return hist_fail(err, "no gradients computed");
+        lam = m.lm.lam.p, wt = m.lm.wt.p, pos = h.pos.p;
+    }
+    if (!h.absmax.ensure(2, err) || !h.Q.ensure(n, err) || !h.W.ensure(n, err)) return false;
+    FR_HIP(hipMemsetAsync(h.absmax.p, 0, 2 * sizeof(unsigned long long), m.stream));
+    {
+        ProfScope ps("hist_absmax_kernel", m.stream);
+        hist_absmax_kernel<<<std::min<unsigned>(grid1d(nt, 256).x, 1024u), 256, 0, m.stream>>>(lam, wt, pos, root, nt, h.absmax.p);
+    }
+    unsigned long long bits[2] = {0, 0};
+    FR_HIP(hipMemcpyAsync(bits, h.absmax.p, sizeof(bits), hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipStreamSynchronize(m.stream));
+    double mx[2];
+    std::memcpy(mx, bits, sizeof(mx));
+    if (!std::isfinite(mx[0]) || !std::isfinite(mx[1])) return hist_fail(err, "a gradient is not finite");
+    *all_zero = mx[0] == 0.0;
+    *s_l = *s_w = 0;
+    if (*all_zero) return true;
+    uint32_t c = 0;  // ceil(log2(n + 1)) = the bit length of n
+    for (uint32_t x = nt; x != 0; x >>= 1) c++;
+    int e = 0;
+    (void)std::frexp(mx[0], &e);
+    *s_l = 61 - e - (int)c;
+    if (mx[1] != 0.0) {
+        (void)std::frexp(mx[1], &e);
+        *s_w = 61 - e - (int)c;
+    }
+    ProfScope ps("hist_quant_kernel", m.stream);
+    hist_quant_kernel<<<grid1d(nt, 256), 256, 0, m.stream>>>(lam, wt, pos, root, nt, *s_l, *s_w, mx[1] == 0.0 ? 1 : 0, h.Q.p, h.W.p);
+    FR_HIP(hipGetLastError());
+    return true;
+}
+
+// the stretches cut into pieces of at most HIST_CHUNK entries (slot carried along): one workgroup each
+bool DeviceDataset::Impl::hist_items(const std::vector<HistItemDev>& stretches, std::vector<HistItemDev>& host, DevBuf<HistItemDev>& dev,
+                                     std::string* err) {
+    host.clear();
+    for (const HistItemDev& s : stretches)
+        for (uint32_t b = s.begin; b < s.end; b += HIST_CHUNK) host.push_back({s.slot, b, std::min(s.end, b + HIST_CHUNK)});
+    if (host.empty()) return true;
+    if (!dev.ensure(host.size(), err)) return false;
+    FR_HIP(hipMemcpyAsync(dev.p, host.data(), host.size() * sizeof(HistItemDev), hipMemcpyHostToDevice, stream));
+    return true;
+}
+
+void DeviceDataset::Impl::hist_build(uint32_t* cnt, unsigned long long* sum, unsigned long long* wsum) {
+    auto& h = hist;
+    const uint32_t* fsel = h.f_sampled ? h.fsel.p : nullptr;
+    if (wsum == nullptr) {
+        ProfScope ps("hist_build_kernel", stream);
+        const dim3 grid((unsigned)h.items_bh.size(), (h.Ft + HIST_FB - 1) / HIST_FB);
+        const size_t lds = (size_t)HIST_FB * h.k * 12;
+        if (h.f_sampled)
+            hist_build_kernel<true><<<grid, 256, lds, stream>>>(h.items_b.p, h.xbin.p, h.n, h.idx.p, h.Q.p, fsel, h.Ft, h.k, cnt, sum);
+        else
+            hist_build_kernel<false><<<grid, 256, lds, stream>>>(h.items_b.p, h.xbin.p, h.n, h.idx.p, h.Q.p, fsel, h.Ft, h.k, cnt, sum);
+    } else {
+        ProfScope ps("hist_build_newton_kernel", stream);
+        const dim3 grid((unsigned)h.items_bh.size(), (h.Ft + HIST_FB_NEWTON - 1) / HIST_FB_NEWTON);
+        const size_t lds = (size_t)HIST_FB_NEWTON * h.k * 20;
+        if (h.f_sampled)
+            hist_build_newton_kernel<true><<<grid, 256, lds, stream>>>(h.items_b.p, h.xbin.p, h.n, h.idx.p, h.Q.p, h.W.p, fsel, h.Ft, h.k, cnt, sum, wsum);
+        else
+            hist_build_newton_kernel<false><<<grid, 256, lds, stream>>>(h.items_b.p, h.xbin.p, h.n, h.idx.p, h.Q.p, h.W.p, fsel, h.Ft, h.k, cnt, sum, wsum);
+    }
+}
+
+// zeroes `cells` cells from cell `off` on of the histograms
+bool DeviceDataset::Impl::hist_zero(uint32_t* cnt, unsigned long long* sum, unsigned long long* wsum, size_t off, size_t cells, std::string* err) {
+    FR_HIP(hipMemsetAsync(cnt + off, 0, cells * sizeof(uint32_t), stream));
+    FR_HIP(hipMemsetAsync(sum + off, 0, cells * sizeof(unsigned long long), stream));
+    if (wsum != nullptr) FR_HIP(hipMemsetAsync(wsum + off, 0, cells * sizeof(unsigned long long), stream));
+    return true;
+}
+
+// the nodes of a search into hist.nodes (their staging: hist.nodes_h), each held to the level's histograms (to the Newton
+// gain's third array too when `newton`) and to the index list
+bool DeviceDataset::Impl::hist_stage_nodes(const std::vector<DeviceDataset::HistNode>& nodes, bool newton, std::string* err) {
+    static_assert(sizeof(DeviceDataset::HistNode) == sizeof(HistItemDev), "host and device records differ");
+    auto& h = hist;
+    const size_t A = nodes.size(), fk = (size_t)h.Ft * h.k;
+    h.nodes_h.resize(A);
+    for (size_t a = 0; a < A; a++) {
+        const size_t cells = (size_t)(nodes[a].slot + 1) * fk;
+        if (cells > h.cnt.cap || (newton && cells > h.wsum.cap) || nodes[a].end > h.nt || nodes[a].begin > nodes[a].end)
+            return hist_fail(err, "internal error: a node outside the level's histograms");
+        h.nodes_h[a] = {nodes[a].slot, nodes[a].begin, nodes[a].end};
+    }
+    if (!h.nodes.ensure(A, err)) return false;
+    FR_HIP(hipMemcpyAsync(h.nodes.p, h.nodes_h.data(), A * sizeof(HistItemDev), hipMemcpyHostToDevice, stream));
+    return true;
+}
+
+// a search's records back to the host; waits for the stream
+template <typename Host, typename Dev>
+static bool hist_fetch(std::vector<Host>* out, const DevBuf<Dev>& dev, hipStream_t stream, std::string* err) {
+    static_assert(sizeof(Host) == sizeof(Dev), "host and device records differ");
+    FR_HIP(hipMemcpyAsync(out->data(), dev.p, out->size() * sizeof(Dev), hipMemcpyDeviceToHost, stream));
+    FR_HIP(hipStreamSynchronize(stream));
+    return true;
+}
+
+// a level's arrays (under the Newton gain its third one too): a plain error when they do not fit
+static bool hist_level_alloc(DevBuf<uint32_t>& cnt, DevBuf<unsigned long long>& sum, DevBuf<unsigned long long>& wsum, size_t cells, bool newton,
+                             std::string* err) {
+    std::string e2;
+    if (!cnt.ensure(cells, &e2) || !sum.ensure(cells, &e2)) {
+        (void)hipGetLastError();
+        return hist_fail(err, "no device memory for a level's histograms (" + std::to_string((cells * 12) >> 20) +
+                                  " MB: open nodes x features x bins x 12 bytes); lower max_depth or split_candidates");
+    }
+    if (newton && !wsum.ensure(cells, &e2)) {
+        (void)hipGetLastError();
+        return hist_fail(err, "no device memory for a level's histograms (" + std::to_string((cells * 20) >> 20) +
+                                  " MB: open nodes x features x bins x 20 bytes under the Newton gain); lower max_depth or split_candidates");
+    }
+    return true;
+}
+
+bool DeviceDataset::hist_root(std::string* err, bool newton) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    if (h.k == 0) return hist_fail(err, "no bins built");
+    const uint32_t n = h.nt;  // the tree's instances: the index list's length (the bin matrix's rows hold h.n)
+    const size_t fk = (size_t)h.Ft * h.k;
+    if (!h.idx.ensure(h.n, err) || !h.idx_o.ensure(h.n, err) || !h.flag.ensure(h.n, err) || !h.scan.ensure(h.n, err)) return false;
+    if (!hist_level_alloc(h.cnt, h.sum, h.wsum, fk, newton, err)) return false;
+    unsigned long long* const wsum = newton ? h.wsum.p : nullptr;
+    FR_HIP(hipMemsetAsync(h.flag.p, 0, n * sizeof(uint32_t), m.stream));
+    if (!m.hist_zero(h.cnt.p, h.sum.p, wsum, 0, fk, err)) return false;
+    if (h.q_sampled) {
+        FR_HIP(hipMemcpyAsync(h.idx.p, h.root.p, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, m.stream));
+    } else {
+        hist_iota_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(h.idx.p, n);
+    }
+    if (!m.hist_items({{0u, 0u, n}}, h.items_bh, h.items_b, err)) return false;
+    m.hist_build(h.cnt.p, h.sum.p, wsum);
+    FR_HIP(hipGetLastError());
+    return true;
+}
+
+bool DeviceDataset::hist_search(const std::vector<HistNode>& nodes, uint32_t min_leaf, std::vector<HistBest>* best, std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    const size_t A = nodes.size();
+    best->assign(A * h.Ft, HistBest{});
+    if (A == 0) return true;
+    if (!m.hist_stage_nodes(nodes, false, err) || !h.best.ensure(A * h.Ft, err)) return false;
+    {
+        ProfScope ps("hist_scan_kernel", m.stream);
+        hist_scan_kernel<<<(unsigned)(A * h.Ft), 64, 0, m.stream>>>(h.nodes.p, h.Ft, h.k, h.nedges.p, h.f_sampled ? h.fsel.p : nullptr, h.cnt.p,
+                                                                    h.sum.p, min_leaf, h.best.p);
+    }
+    FR_HIP(hipGetLastError());
+    return hist_fetch(best, h.best, m.stream, err);
+}
+
+bool DeviceDataset::hist_search_newton(const std::vector<HistNode>& nodes, uint32_t min_leaf, int s_l, int s_w, double lambda_l2,
+                                       double min_sum_hessian, std::vector<HistBestNewton>* best, std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    const size_t A = nodes.size();
+    best->assign(A * h.Ft, HistBestNewton{});
+    if (A == 0) return true;
+    if (!m.hist_stage_nodes(nodes, true, err) || !h.best_n.ensure(A * h.Ft, err)) return false;
+    {
+        ProfScope ps("hist_scan_newton_kernel", m.stream);
+        hist_scan_newton_kernel<<<(unsigned)(A * h.Ft), 64, 0, m.stream>>>(h.nodes.p, h.Ft, h.k, h.nedges.p, h.f_sampled ? h.fsel.p : nullptr,
+                                                                           h.cnt.p, h.sum.p, h.wsum.p, min_leaf, s_l, s_w, lambda_l2,
+                                                                           min_sum_hessian, h.best_n.p);
+    }
+    FR_HIP(hipGetLastError());
+    return hist_fetch(best, h.best_n, m.stream, err);
+}
+
+bool DeviceDataset::hist_monotone(const int* signs, size_t features, std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    if (h.k == 0) return hist_fail(err, "no bins built");
+    if (signs == nullptr || features != h.F) return hist_fail(err, "internal error: the monotone signs do not cover the bin matrix's rows");
+    for (size_t i = 0; i < features; i++)
+        if (signs[i] < -1 || signs[i] > 1) return hist_fail(err, "internal error: a monotone sign outside {-1, 0, 1}");
+    h.mono_F = 0;
+    if (!h.mono.ensure(features, err)) return false;
+    FR_HIP(hipMemcpyAsync(h.mono.p, signs, features * sizeof(int), hipMemcpyHostToDevice, m.stream));
+    FR_HIP(hipStreamSynchronize(m.stream));  // (signs is the caller's pageable memory)
+    h.mono_F = (uint32_t)features;
+    return true;
+}
+
+bool DeviceDataset::hist_search_monotone(const std::vector<HistNode>& nodes, const std::vector<HistBounds>& bounds, uint32_t min_leaf, int s_l,
+                                         int s_w, double lambda_l2, double min_sum_hessian, std::vector<HistBestNewton>* best,
+                                         std::string* err) {
+    static_assert(sizeof(HistBounds) == sizeof(HistBoundsDev), "host and device records differ");
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    const size_t A = nodes.size();
+    best->assign(A * h.Ft, HistBestNewton{});
+    if (A == 0) return true;
+    if (bounds.size() != A) return hist_fail(err, "internal error: one interval per node is needed");
+    if (h.mono_F == 0 || h.mono_F != h.F) return hist_fail(err, "internal error: no monotone signs set for these bins");
+    if (!m.hist_stage_nodes(nodes, true, err) || !h.bounds.ensure(A, err) || !h.best_n.ensure(A * h.Ft, err)) return false;
+    FR_HIP(hipMemcpyAsync(h.bounds.p, bounds.data(), A * sizeof(HistBoundsDev), hipMemcpyHostToDevice, m.stream));
+    {
+        ProfScope ps("hist_scan_monotone_kernel", m.stream);
+        hist_scan_monotone_kernel<<<(unsigned)(A * h.Ft), 64, 0, m.stream>>>(h.nodes.p, h.bounds.p, h.Ft, h.k, h.nedges.p, h.mono.p,
+                                                                             h.f_sampled ? h.fsel.p : nullptr, h.cnt.p, h.sum.p, h.wsum.p, min_leaf,
+                                                                             s_l, s_w, lambda_l2, min_sum_hessian, h.best_n.p);
+    }
+    FR_HIP(hipGetLastError());
+    return hist_fetch(best, h.best_n, m.stream, err);  // (bounds is the caller's, read by the copy above until this has waited)
+}
+
+bool DeviceDataset::hist_split(const std::vector<HistSplit>& splits, const std::vector<HistNode>& builds, const std::vector<HistSub>& subs,
+                               uint32_t next_slots, std::string* err, bool newton) {
+    static_assert(sizeof(HistSplit) == sizeof(HistSplitDev) && sizeof(HistSub) == sizeof(HistSubDev), "host and device records differ");
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    const uint32_t n = h.nt;  // the index list's length; the bin matrix's rows hold h.n entries
+    const size_t fk = (size_t)h.Ft * h.k;
+    if (!splits.empty()) {
+        std::vector<HistItemDev> stretches(splits.size());
+        h.splits_h.resize(splits.size());
+        for (size_t i = 0; i < splits.size(); i++) {
+            const HistSplit& s = splits[i];
+            if (s.begin >= s.end || s.end > n || s.nl > s.end - s.begin || s.fslot >= h.F || s.edge >= h.k)
+                return hist_fail(err, "internal error: a split outside the index list");
+            h.splits_h[i] = {s.begin, s.end, s.fslot, s.edge, s.nl};
+            stretches[i] = {(uint32_t)i, s.begin, s.end};
+        }
+        if (!h.splits.ensure(splits.size(), err) || !m.hist_items(stretches, h.items_h, h.items, err)) return false;
+        FR_HIP(hipMemcpyAsync(h.splits.p, h.splits_h.data(), splits.size() * sizeof(HistSplitDev), hipMemcpyHostToDevice, m.stream));
+        const unsigned g = (unsigned)h.items_h.size();
+        ProfScope ps("hist_partition", m.stream);
+        hist_flag_kernel<<<g, 256, 0, m.stream>>>(h.items.p, h.splits.p, h.xbin.p, h.n, h.idx.p, h.flag.p);
+        if (!m.hist_flag_scan(0, n, err)) return false;
+        hist_scatter_kernel<<<g, 256, 0, m.stream>>>(h.items.p, h.splits.p, h.flag.p, h.scan.p, h.idx.p, h.idx_o.p);
+        hist_copy_kernel<<<g, 256, 0, m.stream>>>(h.items.p, h.idx_o.p, h.idx.p);
+        FR_HIP(hipGetLastError());
+    }
+    if (next_slots == 0) return true;
+    // the next level's histograms: the smaller child of every pair from its stretch, the larger by subtraction
+    if (!hist_level_alloc(h.cnt_o, h.sum_o, h.wsum_o, (size_t)next_slots * fk, newton, err)) return false;
+    unsigned long long* const wsum_o = newton ? h.wsum_o.p : nullptr;
+    if (!m.hist_zero(h.cnt_o.p, h.sum_o.p, wsum_o, 0, (size_t)next_slots * fk, err)) return false;
+    std::vector<HistItemDev> stretches(builds.size());
+    for (size_t i = 0; i < builds.size(); i++) {
+        if (builds[i].slot >= next_slots || builds[i].end > n || builds[i].begin > builds[i].end)
+            return hist_fail(err, "internal error: a child outside the next level");
+        stretches[i] = {builds[i].slot, builds[i].begin, builds[i].end};
+    }
+    if (!m.hist_items(stretches, h.items_bh, h.items_b, err)) return false;
+    if (!h.items_bh.empty()) m.hist_build(h.cnt_o.p, h.sum_o.p, wsum_o);
+    if (!subs.empty()) {
+        h.subs_h.resize(subs.size());
+        for (size_t i = 0; i < subs.size(); i++) {
+            if ((size_t)(subs[i].parent + 1) * fk > h.cnt.cap || (newton && (size_t)(subs[i].parent + 1) * fk > h.wsum.cap) || subs[i].small >= next_slots || subs[i].large >= next_slots)
+                return hist_fail(err, "internal error: a subtraction outside the histograms");
+            h.subs_h[i] = {subs[i].parent, subs[i].small, subs[i].large};
+        }
+        if (!h.subs.ensure(subs.size(), err)) return false;
+        FR_HIP(hipMemcpyAsync(h.subs.p, h.subs_h.data(), subs.size() * sizeof(HistSubDev), hipMemcpyHostToDevice, m.stream));
+        if (newton) {
+            ProfScope ps("hist_sub_newton_kernel", m.stream);
+            hist_sub_newton_kernel<<<dim3((unsigned)subs.size(), (unsigned)((fk + 255) / 256)), 256, 0, m.stream>>>(
+                h.subs.p, (uint32_t)fk, h.cnt.p, h.sum.p, h.wsum.p, h.cnt_o.p, h.sum_o.p, h.wsum_o.p);
+        } else {
+            ProfScope ps("hist_sub_kernel", m.stream);
+            hist_sub_kernel<<<dim3((unsigned)subs.size(), (unsigned)((fk + 255) / 256)), 256, 0, m.stream>>>(h.subs.p, (uint32_t)fk, h.cnt.p, h.sum.p,
+                                                                                                           h.cnt_o.p, h.sum_o.p);
+        }
+    }
+    FR_HIP(hipGetLastError());
+    std::swap(h.cnt.p, h.cnt_o.p), std::swap(h.cnt.cap, h.cnt_o.cap);
+    std::swap(h.sum.p, h.sum_o.p), std::swap(h.sum.cap, h.sum_o.cap);
+    if (newton) std::swap(h.wsum.p, h.wsum_o.p), std::swap(h.wsum.cap, h.wsum_o.cap);
+    return true;
+}
+
+bool DeviceDataset::hist_leaf_sums(const std::vector<HistNode>& leaves, std::vector<long long>* qw, std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    const size_t L = leaves.size();
+    qw->assign(L * 2, 0);
+    if (L == 0) return true;
+    std::vector<HistItemDev> stretches(L);
+    for (size_t i = 0; i < L; i++) {
+        if (leaves[i].end > h.nt || leaves[i].begin > leaves[i].end) return hist_fail(err, "internal error: a leaf outside the index list");
+        stretches[i] = {(uint32_t)i, leaves[i].begin, leaves[i].end};
+    }
+    FR_HIP(hipStreamSynchronize(m.stream));  // (hist.items is about to be rewritten)
+    if (!h.leaf.ensure(L * 2, err) || !m.hist_items(stretches, h.items_h, h.items, err)) return false;
+    FR_HIP(hipMemsetAsync(h.leaf.p, 0, L * 2 * sizeof(unsigned long long), m.stream));
+    if (!h.items_h.empty()) {
+        ProfScope ps("hist_leafsum_kernel", m.stream);
+        hist_leafsum_kernel<<<(unsigned)h.items_h.size(), 256, 0, m.stream>>>(h.items.p, h.idx.p, h.Q.p, h.W.p, h.leaf.p);
+    }
+    FR_HIP(hipGetLastError());
+    FR_HIP(hipMemcpyAsync(qw->data(), h.leaf.p, L * 2 * sizeof(long long), hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipStreamSynchronize(m.stream));
+    return true;
+}
+
+void DeviceDataset::hist_end() {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    auto& h = m.hist;
+    (void)hipStreamSynchronize(m.stream);
+    h.cnt.release(), h.cnt_o.release(), h.sum.release(), h.sum_o.release(), h.wsum.release(), h.wsum_o.release(), h.best.release(), h.best_n.release(), h.lam_in.release(), h.wt_in.release();
+    h.pcnt.release(), h.psum.release(), h.pwsum.release(), h.rec.release(), h.pick.release(), h.bounds.release();
+    h.pool_slots = 0;
+}
+
+// --- leaf-wise growth (kernels_hist.inc, "Leaf-wise growth") ---
+
+// scan (after deriving where asked) and pick of `count` children, their records to out[0..count); waits for the stream
+bool DeviceDataset::Impl::hist_leaf_scan(const HistLeafKids& kids, uint32_t count, const DeviceDataset::HistLeafSearch& how,
+                                         DeviceDataset::HistPick* out, std::string* err, const HistLeafBoundsDev* bounds) {
+    static_assert(sizeof(DeviceDataset::HistPick) == sizeof(HistPickDev), "host and device records differ");
+    auto& h = hist;
+    if (!h.rec.ensure((size_t)2 * h.Ft, err) || !h.pick.ensure(2, err)) return false;
+    const uint32_t* fsel = h.f_sampled ? h.fsel.p : nullptr;
+    if (how.monotone) {
+        if (!how.newton || bounds == nullptr || h.mono_F == 0 || h.mono_F != h.F)
+            return hist_fail(err, "internal error: no monotone signs set for these bins");
+        ProfScope ps("hist_leaf_scan_monotone_kernel", stream);
+        hist_leaf_scan_monotone_kernel<<<dim3(h.Ft, count), 64, 0, stream>>>(kids, *bounds, h.Ft, h.k, h.nedges.p, h.mono.p, fsel, h.pcnt.p, h.psum.p,
+                                                                             h.pwsum.p, how.min_leaf, how.s_l, how.s_w, how.lambda_l2,
+                                                                             how.min_sum_hessian, h.rec.p);
+    } else {
+        ProfScope ps(how.newton ? "hist_leaf_scan_kernel<newton>" : "hist_leaf_scan_kernel", stream);
+        const dim3 grid(h.Ft, count);
+        if (how.newton)
+            hist_leaf_scan_kernel<true><<<grid, 64, 0, stream>>>(kids, h.Ft, h.k, h.nedges.p, fsel, h.pcnt.p, h.psum.p, h.pwsum.p, how.min_leaf,
+                                                                 how.s_l, how.s_w, how.lambda_l2, how.min_sum_hessian, h.rec.p);
+        else
+            hist_leaf_scan_kernel<false><<<grid, 64, 0, stream>>>(kids, h.Ft, h.k, h.nedges.p, fsel, h.pcnt.p, h.psum.p, nullptr, how.min_leaf, 0, 0,
+                                                                  0.0, 0.0, h.rec.p);
+    }
+    {
+        ProfScope ps("hist_pick_kernel", stream);
+        hist_pick_kernel<<<count, 64, 0, stream>>>(h.rec.p, h.Ft, h.pick.p);
+    }
+    FR_HIP(hipGetLastError());
+    FR_HIP(hipMemcpyAsync(out, h.pick.p, count * sizeof(HistPickDev), hipMemcpyDeviceToHost, stream));
+    FR_HIP(hipStreamSynchronize(stream));
+    return true;
+}
+
+bool DeviceDataset::hist_leaf_begin(uint32_t slots, const HistLeafSearch& how, HistPick* root, std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    if (h.k == 0) return hist_fail(err, "no bins built");
+    if (slots == 0) return hist_fail(err, "internal error: an empty histogram pool");
+    const uint32_t n = h.nt;
+    const size_t fk = (size_t)h.Ft * h.k, cells = (size_t)slots * fk;
+    if (!h.idx.ensure(h.n, err) || !h.idx_o.ensure(h.n, err) || !h.flag.ensure(h.n, err) || !h.scan.ensure(h.n, err)) return false;
+    {
+        std::string e2;
+        if (!h.pcnt.ensure(cells, &e2) || !h.psum.ensure(cells, &e2) || (how.newton && !h.pwsum.ensure(cells, &e2))) {
+            (void)hipGetLastError();
+            h.pool_slots = 0;
+            return hist_fail(err, "no device memory for the leaf-wise histogram pool (" + std::to_string((cells * (how.newton ? 20 : 12)) >> 20) +
+                                      " MB: max_leaves x features x bins x " + (how.newton ? "20" : "12") + " bytes); lower max_leaves or split_candidates");
+        }
+    }
+    h.pool_slots = slots;
+    unsigned long long* const pwsum = how.newton ? h.pwsum.p : nullptr;
+    if (!m.hist_zero(h.pcnt.p, h.psum.p, pwsum, 0, fk, err)) return false;
+    if (h.q_sampled) {
+        FR_HIP(hipMemcpyAsync(h.idx.p, h.root.p, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, m.stream));
+    } else {
+        hist_iota_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(h.idx.p, n);
+    }
+    if (!m.hist_items({{0u, 0u, n}}, h.items_bh, h.items_b, err)) return false;
+    m.hist_build(h.pcnt.p, h.psum.p, pwsum);
+    FR_HIP(hipGetLastError());
+    HistLeafKids kids{};
+    kids.slot[0] = 0, kids.n[0] = n;
+    HistLeafBoundsDev whole{};  // (the root's interval: the whole line)
+    whole.lo[0] = whole.lo[1] = -std::numeric_limits<double>::infinity();
+    whole.hi[0] = whole.hi[1] = std::numeric_limits<double>::infinity();
+    return m.hist_leaf_scan(kids, 1, how, root, err, &whole);
+}
+
+bool DeviceDataset::hist_leaf_step(const HistLeafStep& step, const HistLeafSearch& how, HistPick pick[2], std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    const HistSplit& s = step.split;
+    const size_t fk = (size_t)h.Ft * h.k;
+    const bool build = step.small_slot != HIST_NO_SLOT;
+    if (s.begin >= s.end || s.end > h.nt || s.nl == 0 || s.nl >= s.end - s.begin || s.fslot >= h.F || s.edge >= h.k)
+        return hist_fail(err, "internal error: a split outside the index list");
+    if (h.pool_slots == 0 || step.parent_slot >= h.pool_slots || (build && (step.small_slot >= h.pool_slots || step.small_slot == step.parent_slot)) ||
+        ((step.search_lhs || step.search_rhs) && !build))
+        return hist_fail(err, "internal error: a step outside the histogram pool");
+    const uint32_t n = s.end - s.begin, nr = n - s.nl;
+    {
+        ProfScope ps("hist_leaf_partition", m.stream);
+        const dim3 g = grid1d(n, 256);
+        hist_leaf_flag_kernel<<<g, 256, 0, m.stream>>>(s.begin, s.end, h.xbin.p + (size_t)s.fslot * h.n, s.edge, h.idx.p, h.flag.p);
+        if (!m.hist_flag_scan(s.begin, n, err)) return false;
+        hist_leaf_scatter_kernel<<<g, 256, 0, m.stream>>>(s.begin, s.end, s.nl, h.flag.p, h.scan.p, h.idx.p, h.idx_o.p);
+        FR_HIP(hipMemcpyAsync(h.idx.p + s.begin, h.idx_o.p + s.begin, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, m.stream));
+        FR_HIP(hipGetLastError());
+    }
+    if (!build) return true;
+    // the smaller child from its stretch (the lhs when the two are equal)
+    const bool left_small = s.nl <= nr;
+    unsigned long long* const pwsum = how.newton ? h.pwsum.p : nullptr;
+    if (!m.hist_zero(h.pcnt.p, h.psum.p, pwsum, (size_t)step.small_slot * fk, fk, err)) return false;
+    const uint32_t mid = s.begin + s.nl;
+    if (!m.hist_items({left_small ? HistItemDev{step.small_slot, s.begin, mid} : HistItemDev{step.small_slot, mid, s.end}}, h.items_bh, h.items_b, err))
+        return false;
+    m.hist_build(h.pcnt.p, h.psum.p, pwsum);
+    FR_HIP(hipGetLastError());
+    // the children to scan, the lhs first; the larger one is derived in place in its parent's slot
+    HistLeafKids kids{};
+    HistLeafBoundsDev bounds{};
+    uint32_t count = 0;
+    int where[2] = {-1, -1};
+    for (int side = 0; side < 2; side++) {
+        if (!(side == 0 ? step.search_lhs : step.search_rhs)) continue;
+        const bool small = (side == 0) == left_small;
+        kids.slot[count] = small ? step.small_slot : step.parent_slot;
+        kids.n[count] = side == 0 ? s.nl : nr;
+        kids.derive[count] = small ? 0u : 1u;
+        kids.other[count] = step.small_slot;
+        bounds.lo[count] = step.bounds[side].lo, bounds.hi[count] = step.bounds[side].hi;
+        where[side] = (int)count++;
+    }
+    if (count == 0) return true;
+    HistPick got[2];
+    if (!m.hist_leaf_scan(kids, count, how, got, err, &bounds)) return false;
+    for (int side = 0; side < 2; side++)
+        if (where[side] >= 0) pick[side] = got[where[side]];
+    return true;
+}
