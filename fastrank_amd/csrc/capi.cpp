@@ -1888,6 +1888,7 @@ static const void* lambda_gradients_debug(const CModel* model, const CDataset* d
         std::string name = accept_str("measure", measure);
         fr::lambdamart_check_measure(name);
         fr::LambdaMARTParams op;
+        uint64_t xe_key = 0;
         if (options_json) {
             const Value opts = parse_json_or_fail(accept_str("options_json", *options_json));
             if (!opts.is_object()) fr::fail_raw("Error(\"invalid type: expected a map of gradient options\", line: 0, column: 0)");
@@ -1895,8 +1896,10 @@ static const void* lambda_gradients_debug(const CModel* model, const CDataset* d
                 if (kv.first == "truncation_level") op.truncation_level = fr::json_u32(kv.second, "truncation_level");
                 else if (kv.first == "lambda_norm") op.lambda_norm = fr::json_bool(kv.second, "lambda_norm");
                 else if (kv.first == "objective") op.objective = fr::LambdaMARTParams::objective_from_json(kv.second);
+                else if (kv.first == "xe_key") xe_key = fr::json_u64(kv.second, "xe_key");
                 else fr::fail_raw("Error(\"unknown field `" + kv.first + "`, expected `truncation_level` or `lambda_norm`\", line: 0, column: 0)");
             }
+            op.check_objective_options();  // (before any device work, as the request parser does)
         }
         if (out_len && (!lambda_out || !weight_out)) fr::fail_str("NULL pointer: gradient outputs");
         if (need_queries && !queries) fr::fail_str("NULL pointer: query sample");
@@ -1910,7 +1913,7 @@ static const void* lambda_gradients_debug(const CModel* model, const CDataset* d
         frdev::DeviceDataset& dev = view.device();
         fr::score_model(view, m.actual);
         std::string err;
-        if (!dev.lambda_gradients(ev.norms.data(), ev.depth, sigma, op.pass(fl, false), &err)) fr::fail_str(err);
+        if (!dev.lambda_gradients(ev.norms.data(), ev.depth, sigma, op.pass(fl, false, xe_key), &err)) fr::fail_str(err);
         if (!dev.lambda_download(lambda_out, weight_out, out_len, &err, fl)) fr::fail_str(err);
     });
 }
@@ -1929,10 +1932,12 @@ const void* fr_debug_lambda_gradients_sampled(const CModel* model, const CDatase
 }
 
 // fr_debug_lambda_gradients under the objective's options ("Truncation and normalisation"):
-// options_json = {"truncation_level": u32, "lambda_norm": bool, "objective": "ndcg" | "map" | "mrr"}, every key optional
-// (0 / false / "ndcg").  queries == NULL: the full pass; else the query sample of fr_debug_lambda_gradients_sampled.  With
+// options_json = {"truncation_level": u32, "lambda_norm": bool, "objective": "ndcg" | "map" | "mrr" | "xendcg", "xe_key": u64},
+// every key optional (0 / false / "ndcg" / 0).  queries == NULL: the full pass; else the query sample of fr_debug_lambda_gradients_sampled.  With
 // every option at its default this is the pass of the two other hooks.  `measure` must name NDCG whatever the objective;
-// under "map" / "mrr" the norms are the AP / RR evaluator's ("Objectives").
+// under "map" / "mrr" the norms are the AP / RR evaluator's ("Objectives").  "objective": "xendcg" is
+// the listwise pass (section 11, "Listwise objective") under the key "xe_key" (u64, default 0; read under "xendcg" only); it
+// keeps the NDCG norms, reads neither sigma nor the measure's depth, and refuses truncation_level != 0 and lambda_norm.
 const void* fr_debug_lambda_gradients_opts(const CModel* model, const CDataset* dataset, const CQRel* qrel, const void* measure,
                                            double sigma, const uint32_t* queries, size_t n_queries, const void* options_json,
                                            double* lambda_out, double* weight_out, size_t out_len) {

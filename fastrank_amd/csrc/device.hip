@@ -27,6 +27,7 @@
 //   kernels_lambda.inc      lambda_grad_kernel: LambdaMART's LambdaRank gradients, one workgroup per query;
 //                           lambda_grad_trunc_kernel: the same under a truncation level / per-query normalisation
 //                           (both are templates over the objective: NDCG, MAP or MRR pair weights)
+//   kernels_xendcg.inc      lambda_grad_xe_kernel: LambdaMART's listwise objective, one wave per query, O(n) per query
 //   kernels_hist.inc        LambdaMART's histogram grower: one-byte bins, int64 fixed-point gradients, per-node histograms
 //   kernels_dart.inc        LambdaMART's DART boosting: the u16 leaf cache and dart_rescore_kernel, which re-forms the scores
 //                           of any weighting of the trees from it
@@ -37,7 +38,7 @@
 //   device_dataset.inc      DeviceDataset: its state (Impl), the scoring, tree and metric launchers, the whole line search; includes
 //     dataset_build.inc       the uploads of that layout (tiles, tables): create, replicate, views
 //     train_rf.inc            the launchers of kernels_rf.inc
-//     train_lambda.inc        the launchers of kernels_lambda.inc
+//     train_lambda.inc        the launchers of kernels_lambda.inc and kernels_xendcg.inc
 //     train_dart.inc          the launchers of kernels_dart.inc
 //     train_hist.inc          the launchers of kernels_hist.inc, level-wise and leaf-wise
 #include "device.hpp"
@@ -83,6 +84,7 @@ namespace frdev {
 #include "kernels_rr.inc"
 #include "kernels_rf.inc"
 #include "kernels_lambda.inc"
+#include "kernels_xendcg.inc"
 #include "kernels_hist.inc"
 #include "kernels_dart.inc"
 #include "device_dataset.inc"

@@ -43,6 +43,8 @@ inline const char* pricing_env(const char* name) {
 }
 
 enum Measure : int { M_NDCG = 0, M_AP = 1, M_RR = 2 };
+// LambdaMART's objectives are spelled as their measures; the listwise objective "xendcg" has no measure of its own
+constexpr int LM_OBJECTIVE_XENDCG = 3;
 
 // Error bound E >= |R - sum_j x_j v_j| of a trainer's resident sums, u = 2^-53, T from column
 // maxima.  One place for the constants: the trainer (host.hpp), compute_eps2 (device_dataset.inc) and the CPU test
@@ -285,6 +287,10 @@ class DeviceDataset {
         // 0 = NDCG (the pair weight is |delta NDCG|), 1 = MAP, 2 = MRR; norms are then the AP / RR evaluator's and depth is
         // not read ("Objectives").  The same two kernels, instantiated for the objective
         int objective = 0;
+        // objective = LM_OBJECTIVE_XENDCG (3; DESIGN.md section 11, "Listwise objective"): the listwise cross-entropy pass,
+        // lambda_grad_xe_kernel; norms are the NDCG evaluator's (read for `> 0` only), depth and sigma are not read, and
+        // truncation_level / lambda_norm must be at their defaults.  xe_key: the tree's key of the gamma stream
+        uint64_t xe_key = 0;
     };
     bool lambda_gradients(const double* norms, int64_t depth, double sigma, const LambdaPass& pass, std::string* err);
     // the last pass's lambda / w by padded position ([np] each)

@@ -33,6 +33,9 @@
 // random subset of its trees, then it and the dropped trees are re-weighted.  The scores are re-formed from tree 0 by
 // dart_rescore_kernel (kernels_dart.inc) from a cache of every (tree, document)'s leaf: after every tree, and once more before
 // a tree that drops.
+// objective = "xendcg" (both growers; DESIGN.md section 11, "Listwise objective"): the gradients are the listwise cross-entropy
+// surrogate's, O(n) per query (lambda_grad_xe_kernel, kernels_xendcg.inc), under a per-tree key k_t of a generator of its own;
+// the request's NDCG evaluator keeps every role of the training measure.  truncation_level / lambda_norm are refused.
 // monotone_constraints (histogram grower under the Newton gain only; DESIGN.md section 11, "Monotone constraints"): feature
 // name -> +1 / -1: with every other feature fixed the model's score never falls / never rises as that feature rises.  Every
 // node carries an interval for its output, the scan kernels are the monotone ones, leaves are clamped to their intervals.
@@ -50,6 +53,10 @@
 #include "rf_train.hpp"
 
 namespace fr {
+
+// The listwise objective's key stream ("Listwise objective"): tree t's key k_t is the t-th rand_u64()
+// of Rand64(seed ^ XENDCG_STREAM); the per-tree samples (Rand64(seed)) and the DART plan (seed ^ DART_STREAM) do not move.
+constexpr uint64_t XENDCG_STREAM = 0x58454E4443475845ull;  // "XENDCGXE"
 
 struct LambdaMARTParams {
     uint32_t num_trees = 100;
@@ -76,7 +83,8 @@ struct LambdaMARTParams {
     // the objective's truncation level and per-query normalisation (optional keys, not written at their defaults): 0 = every pair
     uint32_t truncation_level = 0;
     bool lambda_norm = false;
-    // what the gradients optimise (optional key, not written at its default): frdev::M_NDCG, M_AP ("map", "ap") or M_RR ("mrr", "rr")
+    // what the gradients optimise (optional key, not written at its default): frdev::M_NDCG, M_AP ("map", "ap"), M_RR ("mrr", "rr")
+    // or frdev::LM_OBJECTIVE_XENDCG ("xendcg": no measure of its own, the NDCG evaluator stays)
     int objective = frdev::M_NDCG;
     // DART (optional keys, not written at their defaults): the chance of every earlier tree to be dropped (0 = plain boosting),
     // the most trees one step drops (0 = no cap), the chance of a step to drop nothing
@@ -88,13 +96,25 @@ struct LambdaMARTParams {
     std::vector<std::pair<std::string, int>> monotone_constraints;
 
     bool dart() const { return drop_rate > 0.0; }
-    static const char* objective_name(int objective) { return objective == frdev::M_AP ? "map" : objective == frdev::M_RR ? "mrr" : "ndcg"; }
+    bool xendcg() const { return objective == frdev::LM_OBJECTIVE_XENDCG; }
+    static const char* objective_name(int objective) {
+        return objective == frdev::M_AP ? "map" : objective == frdev::M_RR ? "mrr" : objective == frdev::LM_OBJECTIVE_XENDCG ? "xendcg" : "ndcg";
+    }
+    // the measure whose evaluator the trainer needs under `objective`
+    int objective_evaluator() const { return xendcg() ? (int)frdev::M_NDCG : objective; }
     // the evaluator the trainer gets under `objective` (the request's own measure is then read for nothing else)
     const char* objective_measure() const { return objective == frdev::M_AP ? "ap" : objective == frdev::M_RR ? "rr" : nullptr; }
     bool sampling() const { return query_sampling_rate < 1.0 || feature_sampling_rate < 1.0; }
-    // a gradient pass under this request: over the flagged queries (nullptr: all), `unchanged` since the pass before
-    frdev::DeviceDataset::LambdaPass pass(const unsigned char* flags, bool unchanged) const {
-        return {flags, unchanged, truncation_level, lambda_norm, objective};
+    // a gradient pass under this request: over the flagged queries (nullptr: all), `unchanged` since the pass before;
+    // xe_key: the tree's key under "xendcg" (not read otherwise)
+    frdev::DeviceDataset::LambdaPass pass(const unsigned char* flags, bool unchanged, uint64_t xe_key = 0) const {
+        return {flags, unchanged, truncation_level, lambda_norm, objective, xe_key};
+    }
+    // what "xendcg" cannot be combined with (the keys speak of pairs, and there are none)
+    void check_objective_options() const {
+        if (!xendcg()) return;
+        if (truncation_level != 0) invalid("truncation_level cannot be combined with objective `xendcg` (a listwise objective has no pairs to truncate)");
+        if (lambda_norm) invalid("lambda_norm cannot be combined with objective `xendcg` (a listwise objective has no pair terms to normalise by)");
     }
     // (monotone: the signs resolved against the ascending feature list, lambdamart_monotone_signs; empty without the key)
     HistGrowOptions hist_options(std::vector<int> monotone = {}) const {
@@ -109,6 +129,8 @@ struct LambdaMARTParams {
         if (g.s == "ndcg") return frdev::M_NDCG;
         if (g.s == "map" || g.s == "ap") return frdev::M_AP;
         if (g.s == "mrr" || g.s == "rr") return frdev::M_RR;
+        if (g.s == "xendcg") return frdev::LM_OBJECTIVE_XENDCG;
+        // (the text predates the fourth value and is kept byte for byte: DESIGN.md section 11, "Listwise objective")
         invalid("objective must be `ndcg`, `map` or `mrr`, not `" + g.s + "`");
     }
     static LambdaMARTParams from_json(const Value& v) {
@@ -198,6 +220,7 @@ struct LambdaMARTParams {
             invalid("monotone_constraints needs grower: \"histogram\" (the exact grower has no hessian sums)");
         if (!p.monotone_constraints.empty() && !p.newton)
             invalid("monotone_constraints needs split_gain: \"newton\" (the variance criterion has no hessian sums)");
+        p.check_objective_options();
         return p;
     }
     Value to_json() const {
@@ -435,7 +458,8 @@ class LambdaMARTTrainer {
             return std::chrono::duration<double>(b - a).count();
         };
         // gradients exist for NDCG, AP and RR, and the evaluator must be the objective's: the kernels read its norms
-        if (ev_.measure != p_.objective)
+        // (the listwise objective keeps the NDCG evaluator)
+        if (ev_.measure != p_.objective_evaluator())
             fail_str(std::string("LambdaMART: the evaluator does not belong to the objective `") + LambdaMARTParams::objective_name(p_.objective) + "`");
         const LambdaSplit split = lambdamart_split(*view_, p_);  // (host only: a bad list fails before any device work)
         const bool hold = !split.held.empty();
@@ -529,6 +553,7 @@ class LambdaMARTTrainer {
         // DART: the drop plan, the leaf cache (one row per tree) and the weights so far; without drop_rate none of it exists
         const bool dart = p_.dart();
         DartPlan plan(p_.seed, p_.drop_rate, p_.max_drop, p_.skip_drop);
+        Rand64 xe_keys(p_.seed ^ XENDCG_STREAM);  // the listwise objective's keys: a stream of its own, like the plan's
         struct DartGuard {
             frdev::DeviceDataset& d;
             bool on;
@@ -547,6 +572,7 @@ class LambdaMARTTrainer {
             stats_.t_dart += secs(t_a, tnow());
         };
         for (uint32_t t = 0; t < p_.num_trees; t++) {
+            const uint64_t xe_key = p_.xendcg() ? xe_keys.rand_u64() : 0;  // k_t: one per tree, before anything else of the tree
             const std::vector<uint32_t> dropped = dart ? plan.next(t) : std::vector<uint32_t>();
             if (!dropped.empty()) reform(dart_kept(t, dropped));  // the tree is fitted to the ensemble without the dropped trees
             auto ts = tnow();  // (drawing the sample and handing it to the grower count as grow time)
@@ -566,7 +592,7 @@ class LambdaMARTTrainer {
             }
             if (subset_q && !hist) ids_t = &t_ids, off_t = &t_off, pos_t = t_pos.data();
             auto ta = tnow();
-            if (!dev.lambda_gradients(ev_.norms.data(), ev_.depth, p_.sigma, p_.pass(subset_q ? qflags.data() : nullptr, fixed_q && t > 0), &err))
+            if (!dev.lambda_gradients(ev_.norms.data(), ev_.depth, p_.sigma, p_.pass(subset_q ? qflags.data() : nullptr, fixed_q && t > 0, xe_key), &err))
                 fail_str(err);
             if (!frdev::device_synchronize(&err)) fail_str(err);
             auto tb = tnow();

@@ -1,6 +1,6 @@
-// Part of device.hip (single translation unit; see that file's header).  LambdaMART's gradient pass: the launchers of kernels_lambda.inc.
+// Part of device.hip (single translation unit; see that file's header).  LambdaMART's gradient pass: the launchers of kernels_lambda.inc and kernels_xendcg.inc.
 // ----------------------------------------------------------------------------------------------
-// LambdaMART gradient pass (kernels_lambda.inc)
+// LambdaMART gradient pass (kernels_lambda.inc, kernels_xendcg.inc)
 // ----------------------------------------------------------------------------------------------
 // per query the positions of its documents in stored order (instance ids ascending), and the launch order (longest first)
 bool DeviceDataset::Impl::lm_build(std::string* err) {
@@ -42,8 +42,12 @@ bool DeviceDataset::lambda_gradients(const double* norms, int64_t depth, double 
         if (err) *err = "lambda_gradients: no scores resident";
         return false;
     }
-    if (pass.objective < LM_OBJ_NDCG || pass.objective > LM_OBJ_MRR) {
+    if (pass.objective < LM_OBJ_NDCG || pass.objective > LM_OBJ_XENDCG) {
         if (err) *err = "lambda_gradients: unknown objective " + std::to_string(pass.objective);
+        return false;
+    }
+    if (pass.objective == LM_OBJ_XENDCG && (pass.truncation_level != 0 || pass.lambda_norm)) {
+        if (err) *err = "lambda_gradients: the listwise objective has no pairs to truncate or normalise";
         return false;
     }
     if (!m.lm_build(err)) return false;
@@ -72,6 +76,15 @@ bool DeviceDataset::lambda_gradients(const double* norms, int64_t depth, double 
         n_long = sel_long, n_lds = (uint32_t)lm.qsel_h.size() - sel_long;
         qorder = lm.qsel.p;
         longest = n_lds ? m.qlen_h[lm.qsel_h[n_long]] : 0;  // (the longest sampled query that is staged in LDS)
+    }
+    if (pass.objective == LM_OBJ_XENDCG) {  // DESIGN.md section 11, "Listwise objective": one wave per query, long queries included
+        const uint32_t n_q = n_long + n_lds;
+        if (n_q == 0) return true;
+        ProfScope ps("lambda_grad_xe_kernel", m.stream);
+        lambda_grad_xe_kernel<<<(n_q + XE_WAVES - 1) / XE_WAVES, 64 * XE_WAVES, 0, m.stream>>>(
+            m.scores.p, lm.off.p, lm.pos.p, qorder, n_q, m.gexp.p, m.perm.p, m.norms.p, pass.xe_key, lm.lam.p, lm.wt.p, lm.target.p);
+        FR_HIP(hipGetLastError());
+        return true;
     }
     if (pass.truncation_level != 0 || pass.lambda_norm) {  // DESIGN.md section 11, "Truncation and normalisation": a kernel of its own
         const uint32_t trunc = pass.truncation_level != 0 ? pass.truncation_level : 0xFFFFFFFFu;  // (no level: every rank is inside)

@@ -148,13 +148,15 @@ def dart_scores(dataset: CDataset, model: CModel, weights, include, n_total: Opt
 
 def lambda_gradients(model: CModel, dataset: CDataset, measure: str = "ndcg", sigma: float = 1.0,
                      qrel: Optional[CQRel] = None, n_total: Optional[int] = None, queries=None,
-                     truncation_level: int = 0, lambda_norm: bool = False, objective: str = "ndcg") -> Tuple[np.ndarray, np.ndarray]:
+                     truncation_level: int = 0, lambda_norm: bool = False, objective: str = "ndcg",
+                     xe_key: int = 0) -> Tuple[np.ndarray, np.ndarray]:
     """LambdaMART's gradient pass on the scores of `model`: (lambda, weight) indexed by instance id (NaN where the id is
     not part of a sampled dataset).  `queries`: indices of the view's queries (its order) the pass visits, as for a tree's
     query sample; the instances of the others come back NaN.  `truncation_level` >= 1 / `lambda_norm`: the objective's
     options ("Truncation and normalisation"); `objective`: "ndcg", "map" or "mrr" (section 11,
-    "Objectives"; `measure` must name NDCG all the same, and the norms are the AP / RR evaluator's).  At their defaults the
-    call is the one it was."""
+    "Objectives"; `measure` must name NDCG all the same, and the norms are the AP / RR evaluator's) or "xendcg" (section 11,
+    "Listwise objective": the listwise pass under the tree key `xe_key`, a u64; `sigma` and the measure's depth are not read,
+    a truncation level or `lambda_norm` is refused).  At their defaults the call is the one it was."""
     n = int(n_total if n_total is not None else _load().fr_dataset_num_instances(dataset.pointer))
     if n_total is None and dataset.is_sampled():
         n = 1 + max(max(ids) for ids in dataset.instances_by_query().values())
@@ -165,6 +167,8 @@ def lambda_gradients(model: CModel, dataset: CDataset, measure: str = "ndcg", si
         opts = {"truncation_level": int(truncation_level), "lambda_norm": bool(lambda_norm)}
         if objective != "ndcg":
             opts["objective"] = objective
+        if objective == "xendcg":
+            opts["xe_key"] = int(xe_key)
         opts = json.dumps(opts)
         _status(
             _load().fr_debug_lambda_gradients_opts(

@@ -115,6 +115,12 @@ class LambdaMARTParams(_LearnerParams):
     measure: the training stats' `train_measure`, `valid_measure`, `best_iteration`, early stopping and the printed table.
     The request's `measure` must still name NDCG ("ndcg", "ndcg@k") -- "map" there is refused as before -- and is then read
     for nothing else.  Both growers, every other key ("Objectives").
+    "xendcg" (lower case only) is the listwise cross-entropy objective: every document's gradient comes from the softmax of
+    its query's scores against the randomised targets 2^label - gamma, at a cost linear in the query's length, where the
+    pairwise objectives are quadratic.  gamma is a function of `seed`, the tree and the document.  The request's NDCG measure
+    (with its `@k` and judgments) keeps every role of the training measure; `sigma` is accepted and not read;
+    `truncation_level` != 0 and `lambda_norm` are refused with it, every other key composes (DESIGN.md section 11,
+    "Listwise objective").
     `drop_rate` (0 <= r <= 1, default 0.0 = off): DART boosting.  Before tree t >= 1 is fitted, with probability
     1 - `skip_drop` (default 0.5) every earlier tree is dropped with probability `drop_rate`, at most `max_drop` of them
     (default 50, 0 = no cap, the smallest indices are kept); the tree is fitted to the ensemble without the k dropped trees,
@@ -164,7 +170,7 @@ class LambdaMARTParams(_LearnerParams):
                                                 "lambda_l2": 0.0, "min_sum_hessian": 0.0, "min_split_gain": 0.0,
                                                 "max_leaves": 0, "truncation_level": 0, "lambda_norm": False, "objective": "ndcg",
                                                 "drop_rate": 0.0, "max_drop": 50, "skip_drop": 0.5, "monotone_constraints": {}}
-    _OBJECTIVES: ClassVar[Dict[str, str]] = {"ap": "map", "rr": "mrr"}
+    _OBJECTIVES: ClassVar[Dict[str, str]] = {"ap": "map", "rr": "mrr", "xendcg": "xendcg"}
 
     def __post_init__(self):
         if isinstance(self.objective, str):  # (anything else is left for the request parser to refuse)

@@ -269,7 +269,11 @@ const CResult *fr_debug_hist_tree_monotone(const CDataset *dataset, uint32_t spl
  * variant's `objective` key ("Objectives"): a pair is then one relevant (gain > 0) and one
  * non-relevant document, weighted by the change of AP / RR their swap would make, and the norms are the AP / RR
  * evaluator's.  `measure` must still name NDCG (ndcg, ndcg@k) whatever the objective, as in a training request, where
- * "measure": "map" is refused with or without the key. */
+ * "measure": "map" is refused with or without the key.
+ * "objective": "xendcg" (lower case only) is the listwise cross-entropy pass ("Listwise
+ * objective"; lambda_grad_xe_kernel) under the tree key "xe_key" (a fourth optional key: u64, default 0, read under
+ * "xendcg" only).  The norms stay the NDCG evaluator's; sigma and the measure's depth are not read; a truncation_level
+ * other than 0 or lambda_norm: true with it is an `invalid value` error, raised before any device work. */
 const void *fr_debug_lambda_gradients_opts(const CModel *model, const CDataset *dataset, const CQRel *qrel,
                                            const void *measure, double sigma, const uint32_t *queries,
                                            size_t n_queries, const void *options_json, double *lambda_out,

@@ -16,6 +16,8 @@
                                                                # the objective's truncation level and per-query normalisation
     python tools/lmbench.py --shape 30k --trees 100 --grower histogram --objective map --validation-rate 0.1
                                                                # gradients for MAP ("mrr": for MRR); reports the held-out AP and RR
+    python tools/lmbench.py --shape 30k --trees 100 --grower histogram --objective xendcg --validation-rate 0.1 --held-out-measures
+                                                               # the listwise objective; the held-out NDCG next to AP and RR
     python tools/lmbench.py --shape 30k --trees 100 --grower histogram --split-gain newton --monotone 8
                                                                # monotone constraints on the first 8 features, signs +1, -1, +1, ...
 Every other parameter is the LambdaMART default (TrainRequest.lambdamart()).
@@ -190,7 +192,7 @@ def main():
     ap.add_argument("--max-depth", type=int, default=0, help="max_depth of the request (0: the default)")
     ap.add_argument("--truncation-level", type=int, default=0, help="a pair counts only when its better ranked document is in the top T (0: every pair)")
     ap.add_argument("--lambda-norm", action="store_true", help="scale every query's gradients by log2(1 + S_q) / S_q")
-    ap.add_argument("--objective", default="ndcg", choices=["ndcg", "map", "mrr"], help="what the gradients optimise (the measure stays an NDCG spelling)")
+    ap.add_argument("--objective", default="ndcg", choices=["ndcg", "map", "mrr", "xendcg"], help="what the gradients optimise (the measure stays an NDCG spelling)")
     ap.add_argument("--drop-rate", type=float, default=0.0, help="DART: the chance of every earlier tree to be dropped before a tree is fitted (0: plain boosting)")
     ap.add_argument("--max-drop", type=int, default=50, help="DART: the most trees one step drops (0: no cap)")
     ap.add_argument("--skip-drop", type=float, default=0.5, help="DART: the chance of a step to drop nothing")
