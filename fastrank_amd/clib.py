@@ -95,6 +95,9 @@ def _load():
         "fr_debug_hist_tree_newton": (res, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, sz, vp, sz, vp, sz, C.c_double, C.c_double, C.c_double]),
         "fr_debug_hist_tree_leafwise": (res, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, sz, vp, sz, vp, sz, C.c_int, C.c_double, C.c_double, C.c_double, C.c_uint32]),
         "fr_debug_hist_tree_monotone": (res, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, sz, vp, sz, vp, sz, C.c_double, C.c_double, C.c_double, C.c_uint32, vp, vp, sz, vp]),
+        "fr_debug_hist_tree_goss": (res, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, sz, vp, sz, vp, sz, C.c_double, C.c_double, C.c_double, C.c_uint32, vp, vp, sz,
+                                          C.c_double, C.c_double, C.c_uint64, C.c_uint32]),
+        "fr_debug_goss_select": (vp, [vp, vp, sz, C.c_double, C.c_double, C.c_uint64, C.c_uint32, vp, sz, vp, vp, sz, vp, vp]),
         "fr_debug_lambda_gradients_opts": (vp, [vp, vp, vp, C.c_char_p, C.c_double, vp, sz, C.c_char_p, vp, vp, sz]),
         "fr_evaluate_dense": (vp, [vp, vp, vp, C.c_char_p, vp, sz, C.POINTER(vp)]),
         "fr_rank_order": (vp, [vp, vp, vp, sz, vp, sz]),

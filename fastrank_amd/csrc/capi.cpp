@@ -1980,11 +1980,11 @@ const void* fr_debug_hist_bins(const CDataset* dataset, uint32_t split_candidate
 // The body of the five tree hooks below.  who: the exported function's name, for its error messages; opt: what the grower is
 // made with; queries / features: the tree's sample as fr_debug_hist_tree_sampled describes it.  mono_features / mono_signs
 // [n_mono]: monotone signs by feature id of the view (fr_debug_hist_tree_monotone; opt.monotone is made from them);
-// *clamped_out: the leaves a bound moved.
+// *clamped_out: the leaves a bound moved.  goss: the tree is a GOSS one (fr_debug_hist_tree_goss).
 static const CResult* hist_tree_debug(const std::string& who, const CDataset* dataset, fr::HistGrowOptions opt, const double* lambda,
                                       const double* weight, size_t len, const uint32_t* queries, size_t n_queries, const uint32_t* features,
                                       size_t n_features, const uint32_t* mono_features = nullptr, const int32_t* mono_signs = nullptr,
-                                      size_t n_mono = 0, uint32_t* clamped_out = nullptr) {
+                                      size_t n_mono = 0, uint32_t* clamped_out = nullptr, const fr::HistGoss* goss = nullptr) {
     return c_call<CModel>([&]() {
         const CDataset& ds = require_dataset(dataset);
         if (!lambda || !weight) fr::fail_str("NULL pointer: gradient inputs");
@@ -2050,7 +2050,7 @@ static const CResult* hist_tree_debug(const std::string& who, const CDataset* da
         return new_model([&] {
             fr::Model tree;
             tree.kind = fr::Model::DecisionTree;
-            tree.tree = grower.grow(lam.data(), wt.data());
+            tree.tree = grower.grow(lam.data(), wt.data(), nullptr, nullptr, goss);
             if (clamped_out) *clamped_out = grower.clamped_leaves();
             return tree;
         });
@@ -2121,6 +2121,93 @@ const CResult* fr_debug_hist_tree_monotone(const CDataset* dataset, uint32_t spl
     return hist_tree_debug("fr_debug_hist_tree_monotone", dataset,
                            {split_candidates, max_depth, min_leaf_support, fr::HistNewton{true, lambda_l2, min_sum_hessian, min_split_gain}, max_leaves, {}},
                            lambda, weight, len, queries, n_queries, features, n_features, mono_features, mono_signs, n_mono, clamped_leaves_out);
+}
+
+// the two GOSS rates as a debug hook takes them: the request parser's ranges, and top_rate > 0
+static bool goss_debug_rates_ok(double top_rate, double other_rate) {
+    return std::isfinite(top_rate) && top_rate > 0.0 && top_rate < 1.0 && std::isfinite(other_rate) && other_rate > 0.0 && other_rate <= 1.0 &&
+           top_rate + other_rate <= 1.0;
+}
+static const char* const GOSS_DEBUG_RATES = ": top_rate must lie in (0, 1), other_rate in (0, 1], and their sum must be at most 1";
+
+// One GOSS tree ("GOSS"): fr_debug_hist_tree_monotone (n_mono = 0: no constraint) fitted to the GOSS list
+// of the sample's list under the two rates and the key of tree `tree` of `seed`, from amplified gradients.
+const CResult* fr_debug_hist_tree_goss(const CDataset* dataset, uint32_t split_candidates, uint32_t max_depth, uint32_t min_leaf_support,
+                                       const double* lambda, const double* weight, size_t len, const uint32_t* queries, size_t n_queries,
+                                       const uint32_t* features, size_t n_features, double lambda_l2, double min_sum_hessian,
+                                       double min_split_gain, uint32_t max_leaves, const uint32_t* mono_features,
+                                       const int32_t* mono_signs, size_t n_mono, double top_rate, double other_rate, uint64_t seed,
+                                       uint32_t tree) {
+    const double numbers[3] = {lambda_l2, min_sum_hessian, min_split_gain};
+    bool ok = max_leaves != 1;
+    for (double x : numbers) ok = ok && std::isfinite(x) && x >= 0.0;
+    if (!ok)
+        return c_call<CModel>([&]() -> CModel* { fr::fail_str("fr_debug_hist_tree_goss: max_leaves must be 0 or at least 2; lambda_l2, min_sum_hessian and min_split_gain must be finite and at least 0"); });
+    if (!goss_debug_rates_ok(top_rate, other_rate))
+        return c_call<CModel>([&]() -> CModel* { fr::fail_str(std::string("fr_debug_hist_tree_goss") + GOSS_DEBUG_RATES); });
+    const fr::HistGoss goss{top_rate, other_rate, fr::GossKeys::of_tree(seed, tree)};
+    return hist_tree_debug("fr_debug_hist_tree_goss", dataset,
+                           {split_candidates, max_depth, min_leaf_support, fr::HistNewton{true, lambda_l2, min_sum_hessian, min_split_gain}, max_leaves, {}},
+                           lambda, weight, len, queries, n_queries, features, n_features, mono_features, mono_signs, n_mono, nullptr, &goss);
+}
+
+// The GOSS selection on its own: lambda[len] by instance id; queries[n_queries] (NULL: all) = the tree's query sample, whose
+// instances are the list L.  list_out / top_out[cap] (cap >= the view's instances): the GOSS list as indices into the view's
+// full instance list, ascending, and per entry whether it is in the top set; *n_g_out: its length; *tau_out: the n_top-th
+// largest key.
+const void* fr_debug_goss_select(const CDataset* dataset, const double* lambda, size_t len, double top_rate, double other_rate, uint64_t seed,
+                                 uint32_t tree, const uint32_t* queries, size_t n_queries, uint32_t* list_out, uint8_t* top_out, size_t cap,
+                                 uint32_t* n_g_out, uint64_t* tau_out) {
+    return status_call([&]() {
+        const CDataset& ds = require_dataset(dataset);
+        if (!lambda || !list_out || !top_out || !n_g_out || !tau_out) fr::fail_str("NULL pointer: fr_debug_goss_select");
+        if (!goss_debug_rates_ok(top_rate, other_rate)) fr::fail_str(std::string("fr_debug_goss_select") + GOSS_DEBUG_RATES);
+        std::lock_guard<std::mutex> lk(api_mu_of(ds));
+        fr::DatasetView& view = *ds.view;
+        const frdev::HostCSR& csr = view.host_csr();
+        std::vector<uint32_t> ids, positions, feats;
+        hist_debug_lists(view, &ids, &positions, &feats);
+        if (cap < ids.size()) fr::fail_str("fr_debug_goss_select: the outputs are shorter than the instance list");
+        std::vector<unsigned char> flags;
+        size_t n_t = ids.size();
+        if (queries) {
+            flags = debug_query_flags(queries, n_queries, csr.nq);
+            n_t = 0;
+            for (size_t q = 0; q < csr.nq; q++)
+                if (flags[q]) n_t += csr.qoff[q + 1] - csr.qoff[q];
+        }
+        std::vector<double> lam(ids.size(), 0.0);
+        size_t g = 0;
+        for (size_t q = 0; q < csr.nq; q++)
+            for (size_t j = csr.qoff[q]; j < csr.qoff[q + 1]; j++, g++) {
+                if (ids[g] >= len) {
+                    if (queries && !flags[q]) continue;
+                    fr::fail_str("fr_debug_goss_select: the gradient array is shorter than the largest instance id");
+                }
+                lam[g] = lambda[ids[g]];
+                if (!std::isfinite(lam[g]) && !(queries && !flags[q])) fr::fail_str("fr_debug_goss_select: a gradient is not finite");
+            }
+        frdev::DeviceDataset& dev = view.device();
+        // (the selection reads no bin: the smallest bin matrix there is keeps the hook cheap on a view that has none yet)
+        fr::HistGrower grower(dev, feats, {2u, 1u, 1u, fr::HistNewton{true, 0.0, 0.0, 0.0}, 0u, {}});
+        grower.prepare(positions);
+        struct Unsample {
+            fr::HistGrower& g;
+            ~Unsample() {
+                try {
+                    g.set_sample(nullptr, 0, nullptr);
+                } catch (...) {
+                }
+            }
+        } unsample{grower};
+        grower.set_sample(queries ? flags.data() : nullptr, (uint32_t)n_t, nullptr);
+        const fr::GossPlan plan = fr::goss_plan(n_t, top_rate, other_rate);
+        std::string err;
+        uint32_t n_g = 0;
+        if (!dev.hist_goss(lam.data(), plan.n_top, plan.p, plan.amp, fr::GossKeys::of_tree(seed, tree), &n_g, tau_out, &err)) fr::fail_str(err);
+        if (!dev.hist_goss_download(list_out, top_out, n_g, &err)) fr::fail_str(err);
+        *n_g_out = n_g;
+    });
 }
 
 const void* fr_evaluate_dense(const CModel* model, const CDataset* dataset, const CQRel* qrel,

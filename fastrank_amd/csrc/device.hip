@@ -29,6 +29,8 @@
 //                           (both are templates over the objective: NDCG, MAP or MRR pair weights)
 //   kernels_xendcg.inc      lambda_grad_xe_kernel: LambdaMART's listwise objective, one wave per query, O(n) per query
 //   kernels_hist.inc        LambdaMART's histogram grower: one-byte bins, int64 fixed-point gradients, per-node histograms
+//   kernels_goss.inc        LambdaMART's gradient-based one-side sampling: an on-device radix select of the n-th largest |lambda|,
+//                           the kept documents' list, amplified fixed-point gradients
 //   kernels_dart.inc        LambdaMART's DART boosting: the u16 leaf cache and dart_rescore_kernel, which re-forms the scores
 //                           of any weighting of the trees from it
 //   dataset_layout.hpp      (through device.hpp; host only, no HIP) the layout arithmetic of a dataset: runs, size classes, gain
@@ -40,7 +42,7 @@
 //     train_rf.inc            the launchers of kernels_rf.inc
 //     train_lambda.inc        the launchers of kernels_lambda.inc and kernels_xendcg.inc
 //     train_dart.inc          the launchers of kernels_dart.inc
-//     train_hist.inc          the launchers of kernels_hist.inc, level-wise and leaf-wise
+//     train_hist.inc          the launchers of kernels_hist.inc, level-wise and leaf-wise, and of kernels_goss.inc
 #include "device.hpp"
 
 #include <hip/hip_runtime.h>
@@ -86,6 +88,7 @@ namespace frdev {
 #include "kernels_lambda.inc"
 #include "kernels_xendcg.inc"
 #include "kernels_hist.inc"
+#include "kernels_goss.inc"
 #include "kernels_dart.inc"
 #include "device_dataset.inc"
 #include "rccl_exchange.inc"

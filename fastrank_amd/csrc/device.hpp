@@ -341,6 +341,15 @@ class DeviceDataset {
     // per-tree feature samples); only the feature sample changes.
     bool hist_sample(const unsigned char* query_flags, uint32_t n_t, const uint32_t* fsel, size_t f_t, std::string* err,
                      bool keep_queries = false);
+    // GOSS ("GOSS"; kernels_goss.inc) for the next tree, on top of the sample: of the sample's list L (lambda from the last
+    // gradient pass, or lam_list in instance-list order) the n_top entries with the largest |lambda| (ties in list order) and
+    // every other entry whose uniform u(tree_key, original instance id) is below p are the tree's list; hist_quantise then
+    // multiplies the kept others' lambda and w by amp.  *n_g: the list's length; *tau (may be nullptr): the n_top-th largest
+    // key.  Holds until the next hist_sample, hist_bins or hist_goss.
+    bool hist_goss(const double* lam_list, uint32_t n_top, double p, double amp, uint64_t tree_key, uint32_t* n_g, uint64_t* tau,
+                   std::string* err);
+    // the list hist_goss made (list[n_g], full-list indices ascending) and per entry of it whether it is in the top set
+    bool hist_goss_download(uint32_t* list, uint8_t* top, size_t len, std::string* err);
     // Q / W of the tree to grow, from the last gradient pass (lam_list == nullptr) or from host arrays in instance-list
     // order.  *all_zero: every lambda is 0 (nothing was quantised); s_l / s_w: the exponents S of the definition
     bool hist_quantise(const double* lam_list, const double* wt_list, int* s_l, int* s_w, bool* all_zero, std::string* err);

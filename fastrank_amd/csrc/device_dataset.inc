@@ -336,6 +336,18 @@ struct DeviceDataset::Impl : DatasetDesc {
         bool q_sampled = false, f_sampled = false, qof_built = false, qof_ok = false;
         DevBuf<uint32_t> qof, root, fsel, total;  // qof[n]: the query of every instance-list entry (hist_qof: once per bin matrix)
         DevBuf<uint8_t> qflag;                     // [nq]
+        // GOSS (hist_goss; kernels_goss.inc): set for the tree being grown, on top of the sample above.  The tree's list is then
+        // groot[ng] (full-list indices ascending), gtop[r] != 0 marks the top set, the others' gradients are multiplied by g_amp
+        bool g_on = false;
+        uint32_t ng = 0;
+        double g_amp = 1.0;
+        DevBuf<unsigned long long> gkeys;  // [nt] the keys of the sample's list, in its order
+        DevBuf<uint32_t> ghist, groot;     // [GOSS_PASSES][GOSS_BINS]; [n]
+        DevBuf<GossStateDev> gstate;
+        DevBuf<uint8_t> gtop;              // [n] by full-list index
+        // the tree's list: its length and the list itself (nullptr: 0..n-1)
+        uint32_t tree_n() const { return g_on ? ng : nt; }
+        const uint32_t* tree_root() const { return g_on ? groot.p : q_sampled ? root.p : nullptr; }
         std::vector<uint32_t> feats, pos_host;
         std::vector<float> edges_host;      // [F][HIST_MAX_BINS]
         std::vector<uint32_t> nedges_host;  // [F]

@@ -39,6 +39,10 @@
 // monotone_constraints (histogram grower under the Newton gain only; DESIGN.md section 11, "Monotone constraints"): feature
 // name -> +1 / -1: with every other feature fixed the model's score never falls / never rises as that feature rises.  Every
 // node carries an interval for its output, the scan kernels are the monotone ones, leaves are clamped to their intervals.
+// goss_top_rate = a > 0 (histogram grower under the Newton gain only; DESIGN.md section 11, "GOSS"; lambdamart_goss.hpp,
+// kernels_goss.inc): a tree is fitted to the a-share of its instance list with the largest |lambda| and to a random
+// goss_other_rate-share of the rest, whose lambda and w are multiplied by (1 - a) / b; gradient, update and measure still cover
+// every document.  The selection is an on-device radix select under a per-tree key of a generator of its own.
 // A request's keys live in LambdaMARTParams alone: the gradient pass and the histogram grower get their options from it
 // (pass(), hist_options()), and the stats keep a copy of it (LambdaMARTStats::request) to report from.
 #pragma once
@@ -94,7 +98,11 @@ struct LambdaMARTParams {
     // monotone constraints (optional key, written only when some entry is not 0): feature name (as the dataset spells it) ->
     // +1 / -1, in the request's order; entries of 0 are dropped when the request is read
     std::vector<std::pair<std::string, int>> monotone_constraints;
+    // GOSS (optional keys, not written at their defaults): the share of a tree's instances kept for their |lambda| (0 = off),
+    // the share of the tree's instances drawn from the others
+    double goss_top_rate = 0.0, goss_other_rate = 0.1;
 
+    bool goss() const { return goss_top_rate > 0.0; }
     bool dart() const { return drop_rate > 0.0; }
     bool xendcg() const { return objective == frdev::LM_OBJECTIVE_XENDCG; }
     static const char* objective_name(int objective) {
@@ -190,6 +198,8 @@ struct LambdaMARTParams {
                 if (sign != 0) p.monotone_constraints.emplace_back(kv.first, sign);
             }
         }
+        if (const Value* r = v.find("goss_top_rate")) p.goss_top_rate = json_f64(*r, "goss_top_rate");
+        if (const Value* r = v.find("goss_other_rate")) p.goss_other_rate = json_f64(*r, "goss_other_rate");
         if (p.num_trees < 1) invalid("num_trees must be at least 1");
         if (!(std::isfinite(p.learning_rate) && p.learning_rate > 0.0)) invalid("learning_rate must be finite and greater than 0");
         if (p.max_depth < 1) invalid("max_depth must be at least 1");
@@ -220,6 +230,15 @@ struct LambdaMARTParams {
             invalid("monotone_constraints needs grower: \"histogram\" (the exact grower has no hessian sums)");
         if (!p.monotone_constraints.empty() && !p.newton)
             invalid("monotone_constraints needs split_gain: \"newton\" (the variance criterion has no hessian sums)");
+        if (!(std::isfinite(p.goss_top_rate) && p.goss_top_rate >= 0.0 && p.goss_top_rate < 1.0))
+            invalid("goss_top_rate must be finite, at least 0 and less than 1");
+        if (!(std::isfinite(p.goss_other_rate) && p.goss_other_rate > 0.0 && p.goss_other_rate <= 1.0))
+            invalid("goss_other_rate must be finite, greater than 0 and at most 1");
+        if (!(p.goss_top_rate + p.goss_other_rate <= 1.0)) invalid("goss_top_rate + goss_other_rate must be at most 1");
+        if (p.goss_other_rate != 0.1 && !p.goss()) invalid("goss_other_rate needs goss_top_rate greater than 0");
+        if (p.goss() && !p.histogram) invalid("goss_top_rate needs grower: \"histogram\" (the exact grower has no hessian sums)");
+        if (p.goss() && !p.newton)
+            invalid("goss_top_rate needs split_gain: \"newton\" (the variance criterion divides by counts, which amplification does not reach)");
         p.check_objective_options();
         return p;
     }
@@ -258,6 +277,8 @@ struct LambdaMARTParams {
             for (const auto& kv : monotone_constraints) m.set(kv.first, Value::sint(kv.second));
             o.set("monotone_constraints", std::move(m));
         }
+        if (goss_top_rate != 0.0) o.set("goss_top_rate", Value::number(goss_top_rate));
+        if (goss_other_rate != 0.1) o.set("goss_other_rate", Value::number(goss_other_rate));
         return o;
     }
 };
@@ -372,6 +393,10 @@ struct LambdaMARTStats {
     // monotone constraints (reported only when the key is set): feature id -> sign, and per tree the leaves a bound moved
     std::vector<std::pair<uint32_t, int>> monotone;
     std::vector<uint32_t> clamped_leaves;
+    // GOSS (reported only when goss_top_rate > 0): the wall seconds of making the trees' lists (a share of t_grow), and per
+    // tree the list's length n_g and the top set's size n_top
+    double t_goss = 0.0;
+    std::vector<uint32_t> goss_instances, goss_top;
 
     Value to_json() const {
         const LambdaMARTParams& r = request;
@@ -440,6 +465,16 @@ struct LambdaMARTStats {
             Value k = Value::array();
             for (uint32_t x : clamped_leaves) k.push(Value::uint(x));
             o.set("monotone_clamped_leaves", std::move(k));
+        }
+        if (r.goss()) {
+            o.set("goss_top_rate", Value::number(r.goss_top_rate));
+            o.set("goss_other_rate", Value::number(r.goss_other_rate));
+            o.set("goss_ms", Value::number(t_goss * 1e3));
+            Value a = Value::array(), b = Value::array();
+            for (uint32_t x : goss_instances) a.push(Value::uint(x));
+            for (uint32_t x : goss_top) b.push(Value::uint(x));
+            o.set("goss_instances", std::move(a));
+            o.set("goss_top", std::move(b));
         }
         return o;
     }
@@ -554,6 +589,8 @@ class LambdaMARTTrainer {
         const bool dart = p_.dart();
         DartPlan plan(p_.seed, p_.drop_rate, p_.max_drop, p_.skip_drop);
         Rand64 xe_keys(p_.seed ^ XENDCG_STREAM);  // the listwise objective's keys: a stream of its own, like the plan's
+        GossKeys goss_keys(p_.seed);               // GOSS: one more stream of its own (lambdamart_goss.hpp)
+        const bool goss = p_.goss();
         struct DartGuard {
             frdev::DeviceDataset& d;
             bool on;
@@ -573,6 +610,7 @@ class LambdaMARTTrainer {
         };
         for (uint32_t t = 0; t < p_.num_trees; t++) {
             const uint64_t xe_key = p_.xendcg() ? xe_keys.rand_u64() : 0;  // k_t: one per tree, before anything else of the tree
+            const HistGoss goss_t{p_.goss_top_rate, p_.goss_other_rate, goss ? goss_keys.next() : 0};  // K_t: one per tree as well
             const std::vector<uint32_t> dropped = dart ? plan.next(t) : std::vector<uint32_t>();
             if (!dropped.empty()) reform(dart_kept(t, dropped));  // the tree is fitted to the ensemble without the dropped trees
             auto ts = tnow();  // (drawing the sample and handing it to the grower count as grow time)
@@ -602,7 +640,7 @@ class LambdaMARTTrainer {
             }
             double leaf_secs = 0.0;
             uint32_t n_leaves = 0;
-            std::shared_ptr<TreeNode> root = hist ? hist->grow(nullptr, nullptr, &leaf_secs, &n_leaves)
+            std::shared_ptr<TreeNode> root = hist ? hist->grow(nullptr, nullptr, &leaf_secs, &n_leaves, goss ? &goss_t : nullptr)
                                                   : grower.grow_lambda_tree(dev, *off_t, *ids_t, *feats_t, pos_t, rst);
             auto tc = tnow() - std::chrono::duration_cast<std::chrono::steady_clock::duration>(std::chrono::duration<double>(leaf_secs));
             // leaves (exact grower): route every instance through a copy of the tree whose leaves hold their index
@@ -677,6 +715,11 @@ class LambdaMARTTrainer {
             stats_.sum_leaves += n_leaves;
             if (hist) stats_.pool_bytes = hist->pool_bytes();
             if (hist && !signs.empty()) stats_.clamped_leaves.push_back(hist->clamped_leaves());
+            if (goss) {
+                stats_.t_goss += hist->goss_seconds();
+                stats_.goss_instances.push_back(hist->goss_instances());
+                stats_.goss_top.push_back(hist->goss_top());
+            }
             stats_.train_measure.push_back(mean);
             out.members.push_back(std::move(tm));
             if (!p_.quiet) {

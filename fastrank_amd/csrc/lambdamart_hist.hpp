@@ -16,12 +16,16 @@
 // node an interval [lo, hi] for its output; the device's candidates are those of the monotone scan kernels, and the host
 // derives the children's intervals from the winning record's integer sums by the same two-case rule (monotone_term below).
 // Without a non-zero sign nothing here differs.
+// GOSS ("GOSS"; lambdamart_goss.hpp, kernels_goss.inc; Newton gain only): grow() is handed the two
+// rates and the tree's key; the device cuts the sample's list down to the top set and a Bernoulli sample of the others, and
+// the tree is grown over that list (n_ is then its length) from amplified gradients.  Without the argument nothing differs.
 #pragma once
 #include <algorithm>
 #include <cmath>
 #include <limits>
 
 #include "host.hpp"
+#include "lambdamart_goss.hpp"
 
 namespace fr {
 
@@ -34,6 +38,12 @@ struct HistNewton {
 // what a grower is made with: k = split_candidates (bins per feature), the depth limit, the least leaf support, the split
 // criterion, the leaf budget (0: level-wise growth) and the monotone signs: one of {-1, 0, +1} per entry of the ascending
 // feature list (empty, or all 0: no constraint; a non-zero one needs the Newton gain)
+// GOSS for one tree: the two rates and the tree's key K_t
+struct HistGoss {
+    double top_rate = 0.0, other_rate = 0.1;
+    uint64_t key = 0;
+};
+
 struct HistGrowOptions {
     uint32_t k = 0, max_depth = 0, min_leaf = 0;
     HistNewton newton;
@@ -61,7 +71,7 @@ class HistGrower {
         if (!dev_.hist_bins(positions.data(), positions.size(), feats_, k_, &built, &err)) fail_str(err);
         if (!dev_.hist_edges(&edges_, &nedges_, &err)) fail_str(err);
         if (mono_on_ && !dev_.hist_monotone(mono_.data(), mono_.size(), &err)) fail_str(err);
-        n_ = n_full_ = (uint32_t)positions.size();
+        n_ = n_sample_ = n_full_ = (uint32_t)positions.size();
         sel_.clear();
         return built;
     }
@@ -77,23 +87,36 @@ class HistGrower {
             if (features) sel_ = *features;
             else sel_.clear();
             check_features(features);
-            if (!dev_.hist_sample(nullptr, n_, features ? sel_.data() : nullptr, sel_.size(), &err, true)) fail_str(err);
+            if (!dev_.hist_sample(nullptr, n_sample_, features ? sel_.data() : nullptr, sel_.size(), &err, true)) fail_str(err);
             return;
         }
         if (features) sel_ = *features;
         else sel_.clear();
         check_features(features);
         if (!dev_.hist_sample(query_flags, query_flags ? n_t : n_full_, features ? sel_.data() : nullptr, sel_.size(), &err)) fail_str(err);
-        n_ = query_flags ? n_t : n_full_;
+        n_ = n_sample_ = query_flags ? n_t : n_full_;
     }
 
     // One tree for the gradients of the last gradient pass (lam_list == nullptr) or for lam_list / wt_list[n] in
     // instance-list order.  *leaf_seconds: the share of the leaf sums.  *n_leaves: the tree's number of leaves.
-    std::shared_ptr<TreeNode> grow(const double* lam_list, const double* wt_list, double* leaf_seconds = nullptr, uint32_t* n_leaves = nullptr) {
+    // goss (Newton gain only): the tree is fitted to the GOSS list of the sample's list; goss_instances() / goss_top() /
+    // goss_seconds() / goss_tau() then speak of this tree.
+    std::shared_ptr<TreeNode> grow(const double* lam_list, const double* wt_list, double* leaf_seconds = nullptr, uint32_t* n_leaves = nullptr,
+                                   const HistGoss* goss = nullptr) {
         using Dev = frdev::DeviceDataset;
         std::string err;
         int s_l = 0, s_w = 0;
         bool all_zero = false;
+        n_ = n_sample_;
+        if (goss != nullptr) {
+            if (!newton_.on) fail_str("LambdaMART histogram grower: GOSS needs the Newton gain");
+            auto t0 = std::chrono::steady_clock::now();
+            const GossPlan plan = goss_plan(n_sample_, goss->top_rate, goss->other_rate);
+            if (!dev_.hist_goss(lam_list, plan.n_top, plan.p, plan.amp, goss->key, &goss_n_, &goss_tau_, &err)) fail_str(err);
+            goss_top_ = plan.n_top;
+            n_ = goss_n_;
+            goss_secs_ = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        }
         if (!dev_.hist_quantise(lam_list, wt_list, &s_l, &s_w, &all_zero, &err)) fail_str(err);
         auto root = std::make_shared<TreeNode>();
         if (n_leaves) *n_leaves = 1;
@@ -204,6 +227,12 @@ class HistGrower {
         if (n_leaves) *n_leaves = (uint32_t)leaf_nodes.size();
         return root;
     }
+
+    // GOSS: the last tree's list length, top-set size, tau and the wall seconds of making the list
+    uint32_t goss_instances() const { return goss_n_; }
+    uint32_t goss_top() const { return goss_top_; }
+    uint64_t goss_tau() const { return goss_tau_; }
+    double goss_seconds() const { return goss_secs_; }
 
     // monotone constraints: the leaves of the last tree whose value a bound moved
     uint32_t clamped_leaves() const { return clamped_; }
@@ -398,6 +427,10 @@ class HistGrower {
     frdev::DeviceDataset& dev_;
     std::vector<uint32_t> feats_;
     uint32_t k_, max_depth_, min_leaf_, n_ = 0, n_full_ = 0;  // n_: the tree's instances (n_full_ of them without a query sample)
+    uint32_t n_sample_ = 0;                                    // the sample's instances: n_ unless the tree is a GOSS one
+    uint32_t goss_n_ = 0, goss_top_ = 0;
+    uint64_t goss_tau_ = 0;
+    double goss_secs_ = 0.0;
     HistNewton newton_;
     uint32_t max_leaves_ = 0;                                  // 0: level-wise growth
     uint64_t pool_bytes_ = 0;

@@ -20,7 +20,7 @@ bool DeviceDataset::hist_bins(const uint32_t* positions, size_t n, const std::ve
     for (uint32_t f : feats)
         if (f >= m.d) return hist_fail(err, "feature id outside the dataset");
     if (h.k == k && h.n == n && h.feats == feats && std::equal(h.pos_host.begin(), h.pos_host.end(), positions)) {
-        h.nt = h.n, h.Ft = h.F, h.q_sampled = h.f_sampled = false;  // (no sample until hist_sample says so)
+        h.nt = h.n, h.Ft = h.F, h.q_sampled = h.f_sampled = h.g_on = false;  // (no sample until hist_sample says so)
         return true;
     }
     h.k = 0;  // (nothing valid until the end of this function)
@@ -75,7 +75,7 @@ bool DeviceDataset::hist_bins(const uint32_t* positions, size_t n, const std::ve
     h.mono_F = 0;
     h.feats = feats;
     h.n = n32, h.F = (uint32_t)F, h.k = k;
-    h.nt = n32, h.Ft = (uint32_t)F, h.q_sampled = h.f_sampled = false;
+    h.nt = n32, h.Ft = (uint32_t)F, h.q_sampled = h.f_sampled = h.g_on = false;
     if (built) *built = true;
     return true;
 }
@@ -139,6 +139,7 @@ bool DeviceDataset::hist_sample(const unsigned char* query_flags, uint32_t n_t, 
     auto& h = m.hist;
     if (h.k == 0) return hist_fail(err, "no bins built");
     const uint32_t n = h.n;
+    h.g_on = false;  // (GOSS is a tree's: hist_goss sets it after the sample)
     if (keep_queries && query_flags == nullptr && h.q_sampled) {  // (the root list and its length stay)
         n_t = h.nt;
         h.Ft = h.F, h.f_sampled = false;
@@ -180,9 +181,9 @@ bool DeviceDataset::hist_quantise(const double* lam_list, const double* wt_list,
     if (!m.bind(err)) return false;
     auto& h = m.hist;
     if (h.k == 0) return hist_fail(err, "no bins built");
-    const uint32_t n = h.n, nt = h.nt;  // (host arrays and Q / W: the full list; the maxima, c and the quantisation: the tree's)
+    const uint32_t n = h.n, nt = h.tree_n();  // (host arrays and Q / W: the full list; the maxima, c and the quantisation: the tree's)
     const double *lam = nullptr, *wt = nullptr;
-    const uint32_t *pos = nullptr, *root = h.q_sampled ? h.root.p : nullptr;
+    const uint32_t *pos = nullptr, *root = h.tree_root();
     if (lam_list != nullptr) {
         if (!h.lam_in.ensure(n, err) || !h.wt_in.ensure(n, err)) return false;
         FR_HIP(hipMemcpyAsync(h.lam_in.p, lam_list, n * sizeof(double), hipMemcpyHostToDevice, m.stream));
@@ -194,7 +195,10 @@ bool DeviceDataset::hist_quantise(const double* lam_list, const double* wt_list,
     }
     if (!h.absmax.ensure(2, err) || !h.Q.ensure(n, err) || !h.W.ensure(n, err)) return false;
     FR_HIP(hipMemsetAsync(h.absmax.p, 0, 2 * sizeof(unsigned long long), m.stream));
-    {
+    if (h.g_on) {  // (the kept others amplified before the maximum: kernels_goss.inc)
+        ProfScope ps("goss_absmax_kernel", m.stream);
+        goss_absmax_kernel<<<std::min<unsigned>(grid1d(nt, 256).x, 1024u), 256, 0, m.stream>>>(lam, wt, pos, root, h.gtop.p, h.g_amp, nt, h.absmax.p);
+    } else {
         ProfScope ps("hist_absmax_kernel", m.stream);
         hist_absmax_kernel<<<std::min<unsigned>(grid1d(nt, 256).x, 1024u), 256, 0, m.stream>>>(lam, wt, pos, root, nt, h.absmax.p);
     }
@@ -216,9 +220,88 @@ bool DeviceDataset::hist_quantise(const double* lam_list, const double* wt_list,
         (void)std::frexp(mx[1], &e);
         *s_w = 61 - e - (int)c;
     }
-    ProfScope ps("hist_quant_kernel", m.stream);
-    hist_quant_kernel<<<grid1d(nt, 256), 256, 0, m.stream>>>(lam, wt, pos, root, nt, *s_l, *s_w, mx[1] == 0.0 ? 1 : 0, h.Q.p, h.W.p);
+    if (h.g_on) {
+        ProfScope ps("goss_quant_kernel", m.stream);
+        goss_quant_kernel<<<grid1d(nt, 256), 256, 0, m.stream>>>(lam, wt, pos, root, h.gtop.p, h.g_amp, nt, *s_l, *s_w, mx[1] == 0.0 ? 1 : 0, h.Q.p, h.W.p);
+    } else {
+        ProfScope ps("hist_quant_kernel", m.stream);
+        hist_quant_kernel<<<grid1d(nt, 256), 256, 0, m.stream>>>(lam, wt, pos, root, nt, *s_l, *s_w, mx[1] == 0.0 ? 1 : 0, h.Q.p, h.W.p);
+    }
     FR_HIP(hipGetLastError());
+    return true;
+}
+
+// GOSS (kernels_goss.inc): select chain, the two flag stages, the list.  One wait at the end, for the list's length.
+bool DeviceDataset::hist_goss(const double* lam_list, uint32_t n_top, double p, double amp, uint64_t tree_key, uint32_t* n_g, uint64_t* tau,
+                              std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    if (h.k == 0) return hist_fail(err, "no bins built");
+    h.g_on = false;
+    const uint32_t n = h.n, nt = h.nt;
+    const uint32_t* root = h.q_sampled ? h.root.p : nullptr;
+    if (nt == 0 || n_top == 0 || n_top > nt) return hist_fail(err, "internal error: GOSS needs between 1 and all of the tree's instances in the top set");
+    if (!(p > 0.0) || !std::isfinite(p) || !(amp > 0.0) || !std::isfinite(amp)) return hist_fail(err, "internal error: GOSS rates outside their range");
+    const double* lam = nullptr;
+    const uint32_t* pos = nullptr;
+    if (lam_list != nullptr) {
+        if (!h.lam_in.ensure(n, err)) return false;
+        FR_HIP(hipMemcpyAsync(h.lam_in.p, lam_list, n * sizeof(double), hipMemcpyHostToDevice, m.stream));
+        lam = h.lam_in.p;
+    } else {
+        if (!m.lm.built) return hist_fail(err, "no gradients computed");
+        lam = m.lm.lam.p, pos = h.pos.p;
+    }
+    if (!h.gkeys.ensure(n, err) || !h.ghist.ensure((size_t)GOSS_PASSES * GOSS_BINS, err) || !h.gstate.ensure(1, err) || !h.gtop.ensure(n, err) ||
+        !h.groot.ensure(n, err) || !h.flag.ensure(n, err) || !h.scan.ensure(n, err) || !h.total.ensure(1, err))
+        return false;
+    FR_HIP(hipMemsetAsync(h.ghist.p, 0, (size_t)GOSS_PASSES * GOSS_BINS * sizeof(uint32_t), m.stream));
+    {
+        ProfScope ps("goss_select", m.stream);
+        const unsigned g = (nt + GOSS_SHARE - 1) / GOSS_SHARE;
+        for (uint32_t pass = 0; pass < GOSS_PASSES; pass++) {
+            if (pass == 0) goss_hist_kernel<true><<<g, 256, 0, m.stream>>>(lam, pos, root, nt, pass, h.gstate.p, h.gkeys.p, h.ghist.p);
+            else goss_hist_kernel<false><<<g, 256, 0, m.stream>>>(lam, pos, root, nt, pass, h.gstate.p, h.gkeys.p, h.ghist.p);
+            goss_pick_kernel<<<1, 64, 0, m.stream>>>(h.ghist.p, pass, n_top, h.gstate.p);
+        }
+        FR_HIP(hipGetLastError());
+    }
+    uint32_t total = 0;
+    GossStateDev st{};
+    {
+        ProfScope ps("goss_flag", m.stream);
+        if (root != nullptr) FR_HIP(hipMemsetAsync(h.flag.p, 0, n * sizeof(uint32_t), m.stream));  // (entries outside the list: never kept)
+        goss_tie_kernel<<<grid1d(nt, 256), 256, 0, m.stream>>>(h.gkeys.p, root, nt, h.gstate.p, h.flag.p);
+        if (!m.hist_flag_scan(0, n, err)) return false;
+        goss_flag_kernel<<<grid1d(nt, 256), 256, 0, m.stream>>>(h.gkeys.p, root, nt, h.gstate.p, h.scan.p, h.pos.p, m.perm.p, tree_key, p, h.gtop.p, h.flag.p);
+        if (!m.hist_flag_scan(0, n, err)) return false;
+        hist_rootlist_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(h.flag.p, h.scan.p, n, nt, h.groot.p, h.total.p);
+        FR_HIP(hipGetLastError());
+        FR_HIP(hipMemcpyAsync(&total, h.total.p, sizeof(uint32_t), hipMemcpyDeviceToHost, m.stream));
+        if (tau != nullptr) FR_HIP(hipMemcpyAsync(&st, h.gstate.p, sizeof(st), hipMemcpyDeviceToHost, m.stream));
+    }
+    FR_HIP(hipStreamSynchronize(m.stream));  // (lam_list is the caller's pageable memory as well)
+    if (total < n_top || total > nt)
+        return hist_fail(err, "internal error: the GOSS list holds " + std::to_string(total) + " instances for a top set of " + std::to_string(n_top));
+    if (tau != nullptr) *tau = st.prefix;
+    *n_g = total;
+    h.g_on = true, h.ng = total, h.g_amp = amp;
+    return true;
+}
+
+bool DeviceDataset::hist_goss_download(uint32_t* list, uint8_t* top, size_t len, std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    if (!h.g_on || len != h.ng) return hist_fail(err, "no GOSS list of that length");
+    std::vector<uint8_t> by_index(h.n);
+    FR_HIP(hipMemcpyAsync(list, h.groot.p, len * sizeof(uint32_t), hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipMemcpyAsync(by_index.data(), h.gtop.p, h.n, hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipStreamSynchronize(m.stream));
+    for (size_t i = 0; i < len; i++) top[i] = by_index[list[i]];
     return true;
 }
 
@@ -273,7 +356,7 @@ bool DeviceDataset::Impl::hist_stage_nodes(const std::vector<DeviceDataset::Hist
     h.nodes_h.resize(A);
     for (size_t a = 0; a < A; a++) {
         const size_t cells = (size_t)(nodes[a].slot + 1) * fk;
-        if (cells > h.cnt.cap || (newton && cells > h.wsum.cap) || nodes[a].end > h.nt || nodes[a].begin > nodes[a].end)
+        if (cells > h.cnt.cap || (newton && cells > h.wsum.cap) || nodes[a].end > h.tree_n() || nodes[a].begin > nodes[a].end)
             return hist_fail(err, "internal error: a node outside the level's histograms");
         h.nodes_h[a] = {nodes[a].slot, nodes[a].begin, nodes[a].end};
     }
@@ -314,15 +397,15 @@ bool DeviceDataset::hist_root(std::string* err, bool newton) {
     if (!m.bind(err)) return false;
     auto& h = m.hist;
     if (h.k == 0) return hist_fail(err, "no bins built");
-    const uint32_t n = h.nt;  // the tree's instances: the index list's length (the bin matrix's rows hold h.n)
+    const uint32_t n = h.tree_n();  // the tree's instances: the index list's length (the bin matrix's rows hold h.n)
     const size_t fk = (size_t)h.Ft * h.k;
     if (!h.idx.ensure(h.n, err) || !h.idx_o.ensure(h.n, err) || !h.flag.ensure(h.n, err) || !h.scan.ensure(h.n, err)) return false;
     if (!hist_level_alloc(h.cnt, h.sum, h.wsum, fk, newton, err)) return false;
     unsigned long long* const wsum = newton ? h.wsum.p : nullptr;
     FR_HIP(hipMemsetAsync(h.flag.p, 0, n * sizeof(uint32_t), m.stream));
     if (!m.hist_zero(h.cnt.p, h.sum.p, wsum, 0, fk, err)) return false;
-    if (h.q_sampled) {
-        FR_HIP(hipMemcpyAsync(h.idx.p, h.root.p, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, m.stream));
+    if (h.tree_root() != nullptr) {
+        FR_HIP(hipMemcpyAsync(h.idx.p, h.tree_root(), n * sizeof(uint32_t), hipMemcpyDeviceToDevice, m.stream));
     } else {
         hist_iota_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(h.idx.p, n);
     }
@@ -419,7 +502,7 @@ bool DeviceDataset::hist_split(const std::vector<HistSplit>& splits, const std::
     std::lock_guard<std::mutex> lk(m.mu);
     if (!m.bind(err)) return false;
     auto& h = m.hist;
-    const uint32_t n = h.nt;  // the index list's length; the bin matrix's rows hold h.n entries
+    const uint32_t n = h.tree_n();  // the index list's length; the bin matrix's rows hold h.n entries
     const size_t fk = (size_t)h.Ft * h.k;
     if (!splits.empty()) {
         std::vector<HistItemDev> stretches(splits.size());
@@ -490,7 +573,7 @@ bool DeviceDataset::hist_leaf_sums(const std::vector<HistNode>& leaves, std::vec
     if (L == 0) return true;
     std::vector<HistItemDev> stretches(L);
     for (size_t i = 0; i < L; i++) {
-        if (leaves[i].end > h.nt || leaves[i].begin > leaves[i].end) return hist_fail(err, "internal error: a leaf outside the index list");
+        if (leaves[i].end > h.tree_n() || leaves[i].begin > leaves[i].end) return hist_fail(err, "internal error: a leaf outside the index list");
         stretches[i] = {(uint32_t)i, leaves[i].begin, leaves[i].end};
     }
     FR_HIP(hipStreamSynchronize(m.stream));  // (hist.items is about to be rewritten)
@@ -559,7 +642,7 @@ bool DeviceDataset::hist_leaf_begin(uint32_t slots, const HistLeafSearch& how, H
     auto& h = m.hist;
     if (h.k == 0) return hist_fail(err, "no bins built");
     if (slots == 0) return hist_fail(err, "internal error: an empty histogram pool");
-    const uint32_t n = h.nt;
+    const uint32_t n = h.tree_n();
     const size_t fk = (size_t)h.Ft * h.k, cells = (size_t)slots * fk;
     if (!h.idx.ensure(h.n, err) || !h.idx_o.ensure(h.n, err) || !h.flag.ensure(h.n, err) || !h.scan.ensure(h.n, err)) return false;
     {
@@ -574,8 +657,8 @@ bool DeviceDataset::hist_leaf_begin(uint32_t slots, const HistLeafSearch& how, H
     h.pool_slots = slots;
     unsigned long long* const pwsum = how.newton ? h.pwsum.p : nullptr;
     if (!m.hist_zero(h.pcnt.p, h.psum.p, pwsum, 0, fk, err)) return false;
-    if (h.q_sampled) {
-        FR_HIP(hipMemcpyAsync(h.idx.p, h.root.p, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, m.stream));
+    if (h.tree_root() != nullptr) {
+        FR_HIP(hipMemcpyAsync(h.idx.p, h.tree_root(), n * sizeof(uint32_t), hipMemcpyDeviceToDevice, m.stream));
     } else {
         hist_iota_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(h.idx.p, n);
     }
@@ -598,7 +681,7 @@ bool DeviceDataset::hist_leaf_step(const HistLeafStep& step, const HistLeafSearc
     const HistSplit& s = step.split;
     const size_t fk = (size_t)h.Ft * h.k;
     const bool build = step.small_slot != HIST_NO_SLOT;
-    if (s.begin >= s.end || s.end > h.nt || s.nl == 0 || s.nl >= s.end - s.begin || s.fslot >= h.F || s.edge >= h.k)
+    if (s.begin >= s.end || s.end > h.tree_n() || s.nl == 0 || s.nl >= s.end - s.begin || s.fslot >= h.F || s.edge >= h.k)
         return hist_fail(err, "internal error: a split outside the index list");
     if (h.pool_slots == 0 || step.parent_slot >= h.pool_slots || (build && (step.small_slot >= h.pool_slots || step.small_slot == step.parent_slot)) ||
         ((step.search_lhs || step.search_rhs) && !build))

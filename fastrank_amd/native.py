@@ -218,7 +218,7 @@ def hist_bins(dataset: CDataset, split_candidates: int):
 def hist_tree(dataset: CDataset, lam: np.ndarray, wt: np.ndarray, split_candidates: int, max_depth: int,
               min_leaf_support: int, queries=None, features=None, split_gain: str = "variance", lambda_l2: float = 0.0,
               min_sum_hessian: float = 0.0, min_split_gain: float = 0.0, max_leaves: int = 0, monotone=None,
-              clamped_out: Optional[list] = None) -> CModel:
+              clamped_out: Optional[list] = None, goss=None) -> CModel:
     """One tree of LambdaMART's histogram grower for the gradients lam / wt (indexed by instance id).  `queries` (indices of
     the view's queries) / `features` (feature ids): the tree's sample; gradients outside the query sample are not read.
     `split_gain` = "newton": the second-order gain with `lambda_l2`, `min_sum_hessian` and `min_split_gain` (DESIGN.md
@@ -226,7 +226,9 @@ def hist_tree(dataset: CDataset, lam: np.ndarray, wt: np.ndarray, split_candidat
     section 11, "Leaf-wise growth"), 0: level-wise.  `monotone` = {feature id: sign in -1, 0, +1} with some non-zero sign
     (needs `split_gain` = "newton"): the tree is grown under monotone constraints ("Monotone
     constraints"), level-wise or leaf-wise, and the number of leaves a bound moved is appended to `clamped_out` when that is
-    a list.  At the defaults the call is the one it was."""
+    a list.  `goss` = (top_rate, other_rate, seed, tree) (needs `split_gain` = "newton"): the tree is fitted to the GOSS list
+    of the sample's instances under the key of tree `tree` of `seed`, the kept others' gradients amplified (DESIGN.md section
+    11, "GOSS"); level-wise or leaf-wise, with or without monotone signs.  At the defaults the call is the one it was."""
     lam = np.ascontiguousarray(lam, dtype=np.float64)
     wt = np.ascontiguousarray(wt, dtype=np.float64)
     if lam.shape != wt.shape or lam.ndim != 1:
@@ -237,6 +239,23 @@ def hist_tree(dataset: CDataset, lam: np.ndarray, wt: np.ndarray, split_candidat
     fs = None if features is None else np.ascontiguousarray(features, dtype=np.uint32)
     sample = (None if qs is None else qs.ctypes.data, 0 if qs is None else len(qs),
               None if fs is None else fs.ctypes.data, 0 if fs is None else len(fs))
+    if goss is not None:
+        if split_gain != "newton":
+            raise ValueError("goss needs split_gain='newton'")
+        top_rate, other_rate, seed, tree = goss
+        mono = {} if monotone is None else {int(f): int(c) for f, c in monotone.items() if int(c) != 0}
+        mf = np.ascontiguousarray(list(mono.keys()), dtype=np.uint32)
+        ms = np.ascontiguousarray(list(mono.values()), dtype=np.int32)
+        return CModel(
+            _unwrap(
+                _load().fr_debug_hist_tree_goss(
+                    dataset.pointer, int(split_candidates), int(max_depth), int(min_leaf_support), lam.ctypes.data,
+                    wt.ctypes.data, lam.shape[0], *sample, float(lambda_l2), float(min_sum_hessian), float(min_split_gain),
+                    int(max_leaves), mf.ctypes.data if len(mf) else None, ms.ctypes.data if len(ms) else None, len(mf),
+                    float(top_rate), float(other_rate), int(seed), int(tree),
+                )
+            )
+        )
     if monotone is not None and any(int(c) != 0 for c in monotone.values()):
         if split_gain != "newton":
             raise ValueError("monotone constraints need split_gain='newton'")
@@ -299,6 +318,29 @@ def hist_tree(dataset: CDataset, lam: np.ndarray, wt: np.ndarray, split_candidat
             )
         )
     )
+
+
+def goss_select(dataset: CDataset, lam: np.ndarray, top_rate: float, other_rate: float, seed: int, tree: int,
+                queries=None) -> Tuple[np.ndarray, np.ndarray, int]:
+    """LambdaMART's GOSS selection on its own ("GOSS") for the gradients `lam` (by instance id) under
+    the key of tree `tree` of `seed`; `queries` (indices of the view's queries): the tree's query sample, whose instances are
+    the list the selection runs over.  Returns (the GOSS list as ascending indices into the view's instance list, per entry
+    whether it belongs to the top set, tau: the n_top-th largest 64-bit pattern of |lambda|)."""
+    lam = np.ascontiguousarray(lam, dtype=np.float64)
+    n = sum(len(ids) for ids in dataset.instances_by_query().values())
+    qs = None if queries is None else np.ascontiguousarray(queries, dtype=np.uint32)
+    rows = np.zeros(n, dtype=np.uint32)
+    top = np.zeros(n, dtype=np.uint8)
+    n_g = C.c_uint32(0)
+    tau = C.c_uint64(0)
+    _status(
+        _load().fr_debug_goss_select(
+            dataset.pointer, lam.ctypes.data, lam.shape[0], float(top_rate), float(other_rate), int(seed), int(tree),
+            None if qs is None else qs.ctypes.data, 0 if qs is None else len(qs), rows.ctypes.data, top.ctypes.data, n,
+            C.byref(n_g), C.byref(tau),
+        )
+    )
+    return rows[: n_g.value].copy(), top[: n_g.value].astype(bool), int(tau.value)
 
 
 def rank_order(model: CModel, dataset: CDataset) -> Tuple[np.ndarray, np.ndarray]:

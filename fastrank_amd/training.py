@@ -135,7 +135,15 @@ class LambdaMARTParams(_LearnerParams):
     `split_gain` = "newton" only, level-wise and leaf-wise, with every other key; a name the dataset does not hold is an
     error when training starts.  The training stats then report `monotone_constraints` (feature id -> sign) and
     `monotone_clamped_leaves` (per tree, the leaves whose value a bound moved) ("Monotone
-    constraints")."""
+    constraints").
+    `goss_top_rate` = a (0 <= a < 1, default 0.0 = off) and `goss_other_rate` = b (0 < b <= 1, default 0.1; a + b <= 1):
+    gradient-based one-side sampling.  Every tree is fitted to the a-share of its documents with the largest |gradient| and
+    to a random b-share of the others, whose gradients and hessians are multiplied by (1 - a) / b so that the sums the split
+    gain reads stay unbiased; the gradient pass, the score update and the measures still cover every document.  The random
+    part is a function of `seed`, the tree and the document (a stream of its own).  Histogram grower under `split_gain` =
+    "newton" only, with every other key; `goss_other_rate` needs `goss_top_rate` > 0; both keys are written only when they
+    differ from their defaults.  The training stats then report `goss_ms`, `goss_instances` and `goss_top` (per tree: the
+    documents the tree was fitted to, and how many of them for their gradient) ("GOSS")."""
 
     VARIANT: ClassVar[str] = "LambdaMART"
 
@@ -164,12 +172,15 @@ class LambdaMARTParams(_LearnerParams):
     max_drop: int = 50
     skip_drop: float = 0.5
     monotone_constraints: Dict[str, int] = dataclasses.field(default_factory=dict)
+    goss_top_rate: float = 0.0
+    goss_other_rate: float = 0.1
 
     _WIRE_DEFAULTS: ClassVar[Dict[str, Any]] = {"grower": "exact", "query_sampling_rate": 1.0, "feature_sampling_rate": 1.0, "seed": 0,
                                                 "validation_queries": [], "early_stopping_rounds": 0, "split_gain": "variance",
                                                 "lambda_l2": 0.0, "min_sum_hessian": 0.0, "min_split_gain": 0.0,
                                                 "max_leaves": 0, "truncation_level": 0, "lambda_norm": False, "objective": "ndcg",
-                                                "drop_rate": 0.0, "max_drop": 50, "skip_drop": 0.5, "monotone_constraints": {}}
+                                                "drop_rate": 0.0, "max_drop": 50, "skip_drop": 0.5, "monotone_constraints": {},
+                                                "goss_top_rate": 0.0, "goss_other_rate": 0.1}
     _OBJECTIVES: ClassVar[Dict[str, str]] = {"ap": "map", "rr": "mrr", "xendcg": "xendcg"}
 
     def __post_init__(self):

@@ -260,6 +260,22 @@ const CResult *fr_debug_hist_tree_monotone(const CDataset *dataset, uint32_t spl
                                            double min_sum_hessian, double min_split_gain, uint32_t max_leaves,
                                            const uint32_t *mono_features, const int32_t *mono_signs, size_t n_mono,
                                            uint32_t *clamped_leaves_out);
+/* LambdaMART's gradient-based one-side sampling, test hooks ("GOSS").  top_rate in (0, 1),
+ * other_rate in (0, 1], their sum at most 1; the tree's key is that of tree `tree` of the request seed `seed`.
+ * fr_debug_hist_tree_goss: fr_debug_hist_tree_monotone (n_mono = 0: no constraint) fitted to the GOSS list of the sample's
+ * instance list, the kept others' lambda / weight amplified.
+ * fr_debug_goss_select: the selection alone for lambda[len] by instance id.  list_out / top_out[cap] (cap >= the view's
+ * instances): the GOSS list as ascending indices into the view's instance list, and per entry whether it belongs to the
+ * top set; *n_g_out: the list's length; *tau_out: the n_top-th largest of the 64-bit patterns of |lambda|. */
+const CResult *fr_debug_hist_tree_goss(const CDataset *dataset, uint32_t split_candidates, uint32_t max_depth,
+                                       uint32_t min_leaf_support, const double *lambda, const double *weight, size_t len,
+                                       const uint32_t *queries, size_t n_queries, const uint32_t *features,
+                                       size_t n_features, double lambda_l2, double min_sum_hessian, double min_split_gain,
+                                       uint32_t max_leaves, const uint32_t *mono_features, const int32_t *mono_signs,
+                                       size_t n_mono, double top_rate, double other_rate, uint64_t seed, uint32_t tree);
+const void *fr_debug_goss_select(const CDataset *dataset, const double *lambda, size_t len, double top_rate,
+                                 double other_rate, uint64_t seed, uint32_t tree, const uint32_t *queries, size_t n_queries,
+                                 uint32_t *list_out, uint8_t *top_out, size_t cap, uint32_t *n_g_out, uint64_t *tau_out);
 /* fr_debug_lambda_gradients under the LambdaRank objective's options ("Truncation and
  * normalisation").  options_json = {"truncation_level": T, "lambda_norm": bool}, either key optional: T >= 1 keeps a pair
  * only when the better ranked of its two documents is in the top T of the pass's ranks (0, the default: every pair);

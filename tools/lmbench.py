@@ -20,6 +20,8 @@
                                                                # the listwise objective; the held-out NDCG next to AP and RR
     python tools/lmbench.py --shape 30k --trees 100 --grower histogram --split-gain newton --monotone 8
                                                                # monotone constraints on the first 8 features, signs +1, -1, +1, ...
+    python tools/lmbench.py --shape 30k --trees 100 --grower histogram --split-gain newton --goss-top-rate 0.2 --goss-other-rate 0.1
+                                                               # gradient-based one-side sampling (reports goss_ms and the lists' sizes)
 Every other parameter is the LambdaMART default (TrainRequest.lambdamart()).
 """
 import argparse
@@ -67,6 +69,8 @@ def device_run(args, X, y, qid):
     req.params.drop_rate = args.drop_rate
     if args.drop_rate > 0:  # (the two other keys need a drop rate)
         req.params.max_drop, req.params.skip_drop = args.max_drop, args.skip_drop
+    if args.goss_top_rate > 0:  # (the other rate needs a top rate)
+        req.params.goss_top_rate, req.params.goss_other_rate = args.goss_top_rate, args.goss_other_rate
     if args.monotone:  # the first N features of the dataset, alternating signs from +1
         names = ds.feature_index_to_name()
         first = sorted(names)[:args.monotone]
@@ -96,7 +100,7 @@ def device_run(args, X, y, qid):
         "grower": st["grower"], "bins_ms": st["bins_ms"],
         "per_tree_ms": {k: st[k + "_ms"] / T for k in ("gradient", "grow", "leaves", "update")},
         "train_measure_first": st["train_measure"][0], "train_measure_last": st["train_measure"][-1],
-        "kernel_profile": {k: v for k, v in prof.items() if "lambda" in k or "rf_" in k or "tree" in k or "hist_" in k or "dart_" in k},
+        "kernel_profile": {k: v for k, v in prof.items() if "lambda" in k or "rf_" in k or "tree" in k or "hist_" in k or "dart_" in k or "goss_" in k},
         "model_nodes": len(json.dumps(model.to_dict())),
     }
     if sample:  # (only when a rate is below 1, like the stats object)
@@ -135,6 +139,10 @@ def device_run(args, X, y, qid):
     if args.monotone:  # (only with the key, like the stats object)
         out["monotone"] = {"features": len(st["monotone_constraints"]), "clamped_leaves_per_tree": float(np.mean(st["monotone_clamped_leaves"])),
                            "clamped_leaves_max": int(np.max(st["monotone_clamped_leaves"]))}
+    if args.goss_top_rate > 0:  # (only under GOSS, like the stats object)
+        out["goss"] = {"goss_top_rate": st["goss_top_rate"], "goss_other_rate": st["goss_other_rate"], "goss_ms_per_tree": st["goss_ms"] / T,
+                       "instances_mean": float(np.mean(st["goss_instances"])), "instances_min": int(np.min(st["goss_instances"])),
+                       "instances_max": int(np.max(st["goss_instances"])), "top": int(st["goss_top"][0])}
     if args.held_out_measures and args.validation_rate > 0:  # AP / RR / NDCG of the model over the held-out queries
         held = set(req.params.validation_queries)
         out["held_out"] = {}
@@ -173,7 +181,7 @@ def cpu_run(args, X, y, qid):
     }
 
 
-def main():
+def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shape", default="30k", choices=sorted(SHAPES))
     ap.add_argument("--trees", type=int, default=100)
@@ -197,11 +205,17 @@ def main():
     ap.add_argument("--max-drop", type=int, default=50, help="DART: the most trees one step drops (0: no cap)")
     ap.add_argument("--skip-drop", type=float, default=0.5, help="DART: the chance of a step to drop nothing")
     ap.add_argument("--monotone", type=int, default=0, help="monotone constraints on the first N features, signs alternating from +1 (needs --split-gain newton)")
+    ap.add_argument("--goss-top-rate", type=float, default=0.0, help="GOSS: the share of a tree's documents kept for their |gradient| (0: off; needs --split-gain newton)")
+    ap.add_argument("--goss-other-rate", type=float, default=0.1, help="GOSS: the share of a tree's documents drawn from the others")
     ap.add_argument("--held-out-measures", action="store_true", help="with --validation-rate: report the model's mean AP, RR and NDCG over the held-out queries")
     ap.add_argument("--warmup-trees", type=int, default=0, help="train this many trees untimed before the measured training")
     ap.add_argument("--no-kernel-profile", action="store_true", help="leave the library's per-kernel event timing off during the timed training")
     ap.add_argument("--cpu-baseline", type=float, default=0.0, help="query fraction for the CPU restatement (0: device run)")
-    args = ap.parse_args()
+    return ap
+
+
+def main():
+    args = parser().parse_args()
     n, d, q, seed = SHAPES[args.shape]
     X, y, qid = gen_mslr_shaped(seed, n, d, q)
     out = cpu_run(args, X, y, qid) if args.cpu_baseline > 0 else device_run(args, X, y, qid)
