@@ -94,6 +94,7 @@ def _load():
         "fr_debug_hist_tree_sampled": (res, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, sz, vp, sz, vp, sz]),
         "fr_debug_hist_tree_newton": (res, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, sz, vp, sz, vp, sz, C.c_double, C.c_double, C.c_double]),
         "fr_debug_hist_tree_leafwise": (res, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, sz, vp, sz, vp, sz, C.c_int, C.c_double, C.c_double, C.c_double, C.c_uint32]),
+        "fr_debug_hist_tree_symmetric": (res, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, sz, vp, sz, vp, sz, C.c_int, C.c_double, C.c_double, C.c_double]),
         "fr_debug_hist_tree_monotone": (res, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, sz, vp, sz, vp, sz, C.c_double, C.c_double, C.c_double, C.c_uint32, vp, vp, sz, vp]),
         "fr_debug_hist_tree_goss": (res, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, sz, vp, sz, vp, sz, C.c_double, C.c_double, C.c_double, C.c_uint32, vp, vp, sz,
                                           C.c_double, C.c_double, C.c_uint64, C.c_uint32]),

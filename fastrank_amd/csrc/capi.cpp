@@ -2123,6 +2123,21 @@ const CResult* fr_debug_hist_tree_monotone(const CDataset* dataset, uint32_t spl
                            lambda, weight, len, queries, n_queries, features, n_features, mono_features, mono_signs, n_mono, clamped_leaves_out);
 }
 
+// One symmetric tree ("Symmetric trees"): fr_debug_hist_tree_sampled / _newton (newton != 0: the three
+// numbers are read) with every node of a level split on the level's one winning candidate.
+const CResult* fr_debug_hist_tree_symmetric(const CDataset* dataset, uint32_t split_candidates, uint32_t max_depth, uint32_t min_leaf_support,
+                                            const double* lambda, const double* weight, size_t len, const uint32_t* queries,
+                                            size_t n_queries, const uint32_t* features, size_t n_features, int newton, double lambda_l2,
+                                            double min_sum_hessian, double min_split_gain) {
+    const double numbers[3] = {lambda_l2, min_sum_hessian, min_split_gain};
+    for (double x : numbers)
+        if (!(std::isfinite(x) && x >= 0.0) || (!newton && x != 0.0))
+            return c_call<CModel>([&]() -> CModel* { fr::fail_str("fr_debug_hist_tree_symmetric: lambda_l2, min_sum_hessian and min_split_gain must be finite and at least 0, and 0 without the Newton gain"); });
+    const fr::HistNewton gain = newton ? fr::HistNewton{true, lambda_l2, min_sum_hessian, min_split_gain} : fr::HistNewton();
+    return hist_tree_debug("fr_debug_hist_tree_symmetric", dataset, {split_candidates, max_depth, min_leaf_support, gain, 0u, {}, true}, lambda,
+                           weight, len, queries, n_queries, features, n_features);
+}
+
 // the two GOSS rates as a debug hook takes them: the request parser's ranges, and top_rate > 0
 static bool goss_debug_rates_ok(double top_rate, double other_rate) {
     return std::isfinite(top_rate) && top_rate > 0.0 && top_rate < 1.0 && std::isfinite(other_rate) && other_rate > 0.0 && other_rate <= 1.0 &&

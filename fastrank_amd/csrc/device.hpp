@@ -370,6 +370,15 @@ class DeviceDataset {
     bool hist_monotone(const int* signs, size_t features, std::string* err);
     bool hist_search_monotone(const std::vector<HistNode>& nodes, const std::vector<HistBounds>& bounds, uint32_t min_leaf, int s_l, int s_w,
                               double lambda_l2, double min_sum_hessian, std::vector<HistBestNewton>* best, std::string* err);
+    // Symmetric trees ("Symmetric trees").  hist_search_symmetric: best[f] = the last-maximum candidate of feature f of the
+    // tree's by its level importance I over `nodes` in their order (key: I, -inf for a NaN one; valid = 0: no node splits
+    // under any edge of f).  hist_symmetric_apply: out[a] = node a's record under the candidate (feature fi of the tree's,
+    // edge), valid = the node splits under it; under the variance criterion wl = wtot = 0.
+    struct HistSymBest { double key; uint32_t edge, valid; };
+    struct HistSymSearch { uint32_t min_leaf; bool newton; int s_l, s_w; double lambda_l2, min_sum_hessian, min_split_gain; };
+    bool hist_search_symmetric(const std::vector<HistNode>& nodes, const HistSymSearch& how, std::vector<HistSymBest>* best, std::string* err);
+    bool hist_symmetric_apply(const std::vector<HistNode>& nodes, const HistSymSearch& how, uint32_t fi, uint32_t edge,
+                              std::vector<HistBestNewton>* out, std::string* err);
     // stable partition of the splitting nodes' stretches, then the next level (next_slots histograms; 0: none): `builds` are
     // built from their stretches, `subs` by subtraction from the level just searched
     bool hist_split(const std::vector<HistSplit>& splits, const std::vector<HistNode>& builds, const std::vector<HistSub>& subs,

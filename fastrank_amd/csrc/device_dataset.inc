@@ -373,6 +373,7 @@ struct DeviceDataset::Impl : DatasetDesc {
         DevBuf<HistSubDev> subs;
         DevBuf<HistBestDev> best;
         DevBuf<HistBestNewtonDev> best_n;
+        DevBuf<HistSymBestDev> best_sym;  // symmetric trees: one record per feature of the tree
         // monotone constraints: the signs by row of the bin matrix (mono_F of them; 0: none set for these bins), the level's intervals
         DevBuf<int> mono;
         uint32_t mono_F = 0;

@@ -933,3 +933,193 @@ __global__ __launch_bounds__(64) void hist_leaf_scan_monotone_kernel(HistLeafKid
         *out = HistPickDev{bimp, bql, qtot, bwl, wtot, bj, bnl, 1u, f};
     }
 }
+
+// --- Symmetric trees (DESIGN.md section 11, "Symmetric trees") -----------------------------------------------------------
+// symmetric_trees: every node of a level splits on one (feature, edge).  A candidate's level importance I(f, j) is the
+// sequential f64 sum, over the level's open nodes in their order, of the node's own candidate importance where the node
+// splits under (f, j) by the plain rule and of the node's unsplit term where it does not; the candidate is valid when some
+// node splits under it; the last maximum of I over the valid candidates wins (a NaN I compares as -inf).  The kernels above
+// keep their code; these run only for symmetric_trees.
+//
+//   hist_scan_sym_kernel<NEWTON>   one workgroup per feature: each wave takes every fourth open node of a tile of
+//                                  HIST_SYM_TILE and writes its terms per edge into LDS, then thread e adds the tile's terms
+//                                  of edge e to its running I in node order; the last maximum over the edges as above
+//   hist_sym_apply_kernel<NEWTON>  one wave per open node: the node's record under the level's winner (valid: it splits)
+
+constexpr uint32_t HIST_SYM_TILE = 16;  // open nodes per LDS tile: 16 x 256 edges x (8 + 1) B = 36 KiB, four workgroups per CU
+
+struct HistSymBestDev {
+    double key;  // I of the feature's last-maximum candidate (-inf for a NaN I)
+    uint32_t edge, valid;
+};
+
+// a node's unsplit term: (s s) / n, or the Newton term of its totals
+template <bool NEWTON>
+__device__ __forceinline__ double hist_sym_own(uint32_t n, long long qtot, long long wtot, int s_l, int s_w, double l2) {
+    if (NEWTON) return hist_newton_term(qtot, ldexp((double)wtot, -s_w), s_l, l2);
+    const double s = (double)qtot;
+    return (s * s) / (double)n;
+}
+
+// t_a of one candidate: the importance hist_scan_kernel / hist_scan_newton_kernel give it where the node splits under it
+// (*splits = true; under the Newton gain that includes gain > min_gain), else the node's own term
+template <bool NEWTON>
+__device__ __forceinline__ double hist_sym_term(uint32_t nl, uint32_t n, long long ql, long long wl, long long qtot, long long wtot,
+                                                uint32_t min_leaf, int s_l, int s_w, double l2, double min_hess, double min_gain, double own,
+                                                bool* splits) {
+    *splits = false;
+    const uint32_t nr = n - nl;
+    if (nl == 0 || nr == 0 || nl < min_leaf || nr < min_leaf) return own;
+    double imp;
+    if (NEWTON) {
+        const double hl = ldexp((double)wl, -s_w), hr = ldexp((double)(wtot - wl), -s_w);
+        if (!(hl >= min_hess && hr >= min_hess && hl + l2 > 0.0 && hr + l2 > 0.0)) return own;
+        imp = hist_newton_term(ql, hl, s_l, l2) + hist_newton_term(qtot - ql, hr, s_l, l2);
+        if (!(imp - own > min_gain)) return own;
+    } else {
+        const double sl = (double)ql, sr = (double)(qtot - ql);
+        imp = (sl * sl) / (double)nl + (sr * sr) / (double)nr;
+    }
+    *splits = true;
+    return imp;
+}
+
+// grid F, 256 threads.  nodes[A]: the level's open nodes in order; best[f]
+template <bool NEWTON>
+__global__ __launch_bounds__(256) void hist_scan_sym_kernel(const HistItemDev* __restrict__ nodes, uint32_t A, uint32_t F, uint32_t k,
+                                                            const uint32_t* __restrict__ nedges, const uint32_t* __restrict__ fsel,
+                                                            const uint32_t* __restrict__ cnt, const unsigned long long* __restrict__ sum,
+                                                            const unsigned long long* __restrict__ wsum, uint32_t min_leaf, int s_l, int s_w,
+                                                            double l2, double min_hess, double min_gain, HistSymBestDev* __restrict__ best) {
+    __shared__ double tile[HIST_SYM_TILE][HIST_MAX_BINS];
+    __shared__ uint8_t took[HIST_SYM_TILE][HIST_MAX_BINS];
+    __shared__ double red_key[4];
+    __shared__ uint32_t red_j[4], red_have[4];
+    const uint32_t f = blockIdx.x, e = threadIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t ne = min(nedges[fsel ? fsel[f] : f], k - 1);
+    const uint32_t B = (k + 63) / 64;  // bins per lane (<= 4)
+    double I = 0.0;
+    uint32_t any = 0;
+    for (uint32_t a0 = 0; a0 < A; a0 += HIST_SYM_TILE) {
+        const uint32_t na = min(HIST_SYM_TILE, A - a0);
+        for (uint32_t t = wave; t < na; t += 4) {  // (uniform in a wave: the shuffles below see all 64 lanes)
+            const HistItemDev nd = nodes[a0 + t];
+            const uint32_t n = nd.end - nd.begin;
+            const size_t base = ((size_t)nd.slot * F + f) * k;
+            uint32_t c[4];
+            long long s[4], w[4];
+            uint32_t tc = 0;
+            long long ts = 0, tw = 0;
+            for (uint32_t u = 0; u < 4; u++) {
+                const uint32_t b = lane * B + u;
+                const bool in = u < B && b < k;
+                c[u] = in ? cnt[base + b] : 0u;
+                s[u] = in ? (long long)sum[base + b] : 0ll;
+                w[u] = NEWTON && in ? (long long)wsum[base + b] : 0ll;
+                tc += c[u];
+                ts += s[u];
+                tw += w[u];
+            }
+            uint32_t ic = tc;
+            long long is = ts, iw = tw;
+            for (int o = 1; o < 64; o <<= 1) {
+                const uint32_t oc = __shfl_up(ic, o);
+                const long long os = __shfl_up(is, o), ow = __shfl_up(iw, o);
+                if ((int)lane >= o) {
+                    ic += oc;
+                    is += os;
+                    iw += ow;
+                }
+            }
+            const long long qtot = __shfl(is, 63), wtot = __shfl(iw, 63);
+            const double own = hist_sym_own<NEWTON>(n, qtot, wtot, s_l, s_w, l2);
+            uint32_t rc = ic - tc;  // counts / sums of the bins before this lane's
+            long long rs = is - ts, rw = iw - tw;
+            for (uint32_t u = 0; u < B; u++) {
+                const uint32_t j = lane * B + u;
+                rc += c[u];
+                rs += s[u];
+                rw += w[u];
+                if (j >= ne) break;  // (ne <= 255: j stays inside the tile's row)
+                bool sp;
+                tile[t][j] = hist_sym_term<NEWTON>(rc, n, rs, rw, qtot, wtot, min_leaf, s_l, s_w, l2, min_hess, min_gain, own, &sp);
+                took[t][j] = sp ? 1 : 0;
+            }
+        }
+        __syncthreads();
+        if (e < ne) {
+            for (uint32_t t = 0; t < na; t++) {  // node order: the sum's order is the definition's
+                const double term = tile[t][e];
+                I = (a0 + t == 0) ? term : I + term;
+                any |= took[t][e];
+            }
+        }
+        __syncthreads();
+    }
+    // the last maximum over the edges: larger key, then the later edge
+    double wkey = (I != I) ? -INFINITY : I;
+    uint32_t wj = e, whave = (e < ne && any) ? 1u : 0u;
+    for (int o = 32; o > 0; o >>= 1) {
+        const double okey = __shfl_xor(wkey, o);
+        const uint32_t oj = __shfl_xor(wj, o), ohave = __shfl_xor(whave, o);
+        if (ohave && (!whave || okey > wkey || (okey == wkey && oj > wj))) {
+            whave = 1;
+            wkey = okey;
+            wj = oj;
+        }
+    }
+    if (lane == 0) {
+        red_key[wave] = wkey;
+        red_j[wave] = wj;
+        red_have[wave] = whave;
+    }
+    __syncthreads();
+    if (e == 0) {
+        for (uint32_t v = 1; v < 4; v++) {
+            if (red_have[v] && (!whave || red_key[v] > wkey || (red_key[v] == wkey && red_j[v] > wj))) {
+                whave = 1;
+                wkey = red_key[v];
+                wj = red_j[v];
+            }
+        }
+        best[f] = whave ? HistSymBestDev{wkey, wj, 1u} : HistSymBestDev{0.0, 0u, 0u};
+    }
+}
+
+// grid A, one wave per open node; f: the winner's index among the tree's F, j: its edge.  out[a]: node a's record under the
+// winner (wl, wtot: 0 under the variance criterion)
+template <bool NEWTON>
+__global__ __launch_bounds__(64) void hist_sym_apply_kernel(const HistItemDev* __restrict__ nodes, uint32_t F, uint32_t k, uint32_t f, uint32_t j,
+                                                            const uint32_t* __restrict__ cnt, const unsigned long long* __restrict__ sum,
+                                                            const unsigned long long* __restrict__ wsum, uint32_t min_leaf, int s_l, int s_w,
+                                                            double l2, double min_hess, double min_gain, HistBestNewtonDev* __restrict__ out) {
+    const uint32_t a = blockIdx.x, lane = threadIdx.x;
+    const HistItemDev nd = nodes[a];
+    const uint32_t n = nd.end - nd.begin;
+    const size_t base = ((size_t)nd.slot * F + f) * k;
+    uint32_t nl = 0;
+    long long ql = 0, wl = 0, qtot = 0, wtot = 0;
+    for (uint32_t b = lane; b < k; b += 64) {
+        const uint32_t c = cnt[base + b];
+        const long long s = (long long)sum[base + b], w = NEWTON ? (long long)wsum[base + b] : 0ll;
+        qtot += s;
+        wtot += w;
+        if (b <= j) {
+            nl += c;
+            ql += s;
+            wl += w;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {  // (integer sums: any order)
+        nl += __shfl_xor(nl, o);
+        ql += __shfl_xor(ql, o);
+        wl += __shfl_xor(wl, o);
+        qtot += __shfl_xor(qtot, o);
+        wtot += __shfl_xor(wtot, o);
+    }
+    if (lane != 0) return;
+    const double own = hist_sym_own<NEWTON>(n, qtot, wtot, s_l, s_w, l2);
+    bool sp;
+    const double imp = hist_sym_term<NEWTON>(nl, n, ql, wl, qtot, wtot, min_leaf, s_l, s_w, l2, min_hess, min_gain, own, &sp);
+    out[a] = HistBestNewtonDev{imp, ql, qtot, wl, wtot, j, nl, sp ? 1u : 0u, 0u};
+}

@@ -43,6 +43,9 @@
 // kernels_goss.inc): a tree is fitted to the a-share of its instance list with the largest |lambda| and to a random
 // goss_other_rate-share of the rest, whose lambda and w are multiplied by (1 - a) / b; gradient, update and measure still cover
 // every document.  The selection is an on-device radix select under a per-tree key of a generator of its own.
+// symmetric_trees (histogram grower, level-wise, no monotone constraints; DESIGN.md section 11, "Symmetric trees"): every node
+// of a level splits on the one (feature, threshold) with the largest importance summed over the level's open nodes; a node
+// that cannot split under it becomes a leaf.  The trees are ordinary DecisionTrees; everything upstream of the grower composes.
 // A request's keys live in LambdaMARTParams alone: the gradient pass and the histogram grower get their options from it
 // (pass(), hist_options()), and the stats keep a copy of it (LambdaMARTStats::request) to report from.
 #pragma once
@@ -101,6 +104,8 @@ struct LambdaMARTParams {
     // GOSS (optional keys, not written at their defaults): the share of a tree's instances kept for their |lambda| (0 = off),
     // the share of the tree's instances drawn from the others
     double goss_top_rate = 0.0, goss_other_rate = 0.1;
+    // symmetric (oblivious) trees (optional key, written only when set): every node of a level splits on the same candidate
+    bool symmetric_trees = false;
 
     bool goss() const { return goss_top_rate > 0.0; }
     bool dart() const { return drop_rate > 0.0; }
@@ -127,7 +132,7 @@ struct LambdaMARTParams {
     // (monotone: the signs resolved against the ascending feature list, lambdamart_monotone_signs; empty without the key)
     HistGrowOptions hist_options(std::vector<int> monotone = {}) const {
         return {split_candidates, max_depth, min_leaf_support, HistNewton{newton, lambda_l2, min_sum_hessian, min_split_gain}, max_leaves,
-                std::move(monotone)};
+                std::move(monotone), symmetric_trees};
     }
     [[noreturn]] static void invalid(const std::string& what) {
         fail_raw("Error(\"invalid value: " + what + "\", line: 0, column: 0)");
@@ -200,6 +205,7 @@ struct LambdaMARTParams {
         }
         if (const Value* r = v.find("goss_top_rate")) p.goss_top_rate = json_f64(*r, "goss_top_rate");
         if (const Value* r = v.find("goss_other_rate")) p.goss_other_rate = json_f64(*r, "goss_other_rate");
+        if (const Value* r = v.find("symmetric_trees")) p.symmetric_trees = json_bool(*r, "symmetric_trees");
         if (p.num_trees < 1) invalid("num_trees must be at least 1");
         if (!(std::isfinite(p.learning_rate) && p.learning_rate > 0.0)) invalid("learning_rate must be finite and greater than 0");
         if (p.max_depth < 1) invalid("max_depth must be at least 1");
@@ -239,6 +245,12 @@ struct LambdaMARTParams {
         if (p.goss() && !p.histogram) invalid("goss_top_rate needs grower: \"histogram\" (the exact grower has no hessian sums)");
         if (p.goss() && !p.newton)
             invalid("goss_top_rate needs split_gain: \"newton\" (the variance criterion divides by counts, which amplification does not reach)");
+        if (p.symmetric_trees && !p.histogram)
+            invalid("symmetric_trees needs grower: \"histogram\" (the exact grower searches every node on its own)");
+        if (p.symmetric_trees && p.max_leaves != 0)
+            invalid("symmetric_trees cannot be combined with max_leaves (a symmetric tree is grown level by level)");
+        if (p.symmetric_trees && !p.monotone_constraints.empty())
+            invalid("symmetric_trees cannot be combined with monotone_constraints (a level's one split cannot honour every node's interval)");
         p.check_objective_options();
         return p;
     }
@@ -279,6 +291,7 @@ struct LambdaMARTParams {
         }
         if (goss_top_rate != 0.0) o.set("goss_top_rate", Value::number(goss_top_rate));
         if (goss_other_rate != 0.1) o.set("goss_other_rate", Value::number(goss_other_rate));
+        if (symmetric_trees) o.set("symmetric_trees", Value::boolean(true));
         return o;
     }
 };
@@ -397,6 +410,8 @@ struct LambdaMARTStats {
     // tree the list's length n_g and the top set's size n_top
     double t_goss = 0.0;
     std::vector<uint32_t> goss_instances, goss_top;
+    // symmetric trees (reported only when the key is set): per tree the levels that split
+    std::vector<uint32_t> levels;
 
     Value to_json() const {
         const LambdaMARTParams& r = request;
@@ -475,6 +490,12 @@ struct LambdaMARTStats {
             for (uint32_t x : goss_top) b.push(Value::uint(x));
             o.set("goss_instances", std::move(a));
             o.set("goss_top", std::move(b));
+        }
+        if (r.symmetric_trees) {
+            o.set("symmetric_trees", Value::boolean(true));
+            Value a = Value::array();
+            for (uint32_t x : levels) a.push(Value::uint(x));
+            o.set("levels", std::move(a));
         }
         return o;
     }
@@ -720,6 +741,7 @@ class LambdaMARTTrainer {
                 stats_.goss_instances.push_back(hist->goss_instances());
                 stats_.goss_top.push_back(hist->goss_top());
             }
+            if (hist && p_.symmetric_trees) stats_.levels.push_back(hist->levels());
             stats_.train_measure.push_back(mean);
             out.members.push_back(std::move(tm));
             if (!p_.quiet) {

@@ -19,6 +19,10 @@
 // GOSS ("GOSS"; lambdamart_goss.hpp, kernels_goss.inc; Newton gain only): grow() is handed the two
 // rates and the tree's key; the device cuts the sample's list down to the top set and a Bernoulli sample of the others, and
 // the tree is grown over that list (n_ is then its length) from amplified gradients.  Without the argument nothing differs.
+// symmetric trees ("Symmetric trees"; level-wise, no monotone signs): a level's open nodes all split on
+// one candidate, the last maximum of the level importance (hist_scan_sym_kernel: one record per feature); a second launch
+// (hist_sym_apply_kernel) returns every node's own record under that winner, and the level loop goes on as ever: a node that
+// does not split under the winner closes into a leaf.  Without the option the loop launches what it launched before.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -49,13 +53,16 @@ struct HistGrowOptions {
     HistNewton newton;
     uint32_t max_leaves = 0;
     std::vector<int> monotone;
+    bool symmetric = false;
 };
 
 class HistGrower {
   public:
     HistGrower(frdev::DeviceDataset& dev, std::vector<uint32_t> feats, const HistGrowOptions& opt)
-        : dev_(dev), feats_(std::move(feats)), k_(opt.k), max_depth_(opt.max_depth), min_leaf_(opt.min_leaf), newton_(opt.newton), max_leaves_(opt.max_leaves) {
+        : dev_(dev), feats_(std::move(feats)), k_(opt.k), max_depth_(opt.max_depth), min_leaf_(opt.min_leaf), newton_(opt.newton), max_leaves_(opt.max_leaves), symmetric_(opt.symmetric) {
         for (int c : opt.monotone) mono_on_ = mono_on_ || c != 0;
+        if (symmetric_ && max_leaves_ != 0) fail_str("LambdaMART histogram grower: symmetric trees are grown level by level (max_leaves must be 0)");
+        if (symmetric_ && mono_on_) fail_str("LambdaMART histogram grower: symmetric trees take no monotone constraints");
         if (mono_on_) {
             if (!newton_.on) fail_str("LambdaMART histogram grower: monotone constraints need the Newton gain");
             if (opt.monotone.size() != feats_.size()) fail_str("LambdaMART histogram grower: one monotone sign per feature is needed");
@@ -121,6 +128,7 @@ class HistGrower {
         auto root = std::make_shared<TreeNode>();
         if (n_leaves) *n_leaves = 1;
         clamped_ = 0;
+        levels_ = 0;
         if (all_zero) return root;  // one leaf of value 0.0
         if (max_leaves_ >= 2) {
             std::vector<TreeNode*> lw_nodes;
@@ -155,13 +163,34 @@ class HistGrower {
         std::vector<Dev::HistNode> nodes, builds;
         std::vector<Dev::HistBest> best;
         std::vector<Dev::HistBestNewton> best_n;
+        std::vector<Dev::HistSymBest> level;
         std::vector<Dev::HistSplit> splits;
         std::vector<Dev::HistSub> subs;
         const bool rooted = !open.empty();
         while (!open.empty()) {
             nodes.clear(), builds.clear(), splits.clear(), subs.clear(), next.clear();
             for (const Open& o : open) nodes.push_back({o.slot, o.begin, o.end});
-            if (newton_.on) {  // the selection below reads the fields the two records share
+            size_t sym_f = 0;  // (symmetric trees) the level's winning feature; best[a]: node a's record under the winner
+            if (symmetric_) {
+                const Dev::HistSymSearch how{min_leaf_, newton_.on, s_l, s_w, newton_.lambda_l2, newton_.min_sum_hessian, newton_.min_split_gain};
+                if (!dev_.hist_search_symmetric(nodes, how, &level, &err)) fail_str(err);
+                const Dev::HistSymBest* lw = nullptr;
+                for (size_t fi = 0; fi < F; fi++)  // the last maximum: a later feature wins among equals
+                    if (level[fi].valid && (lw == nullptr || level[fi].key >= lw->key)) lw = &level[fi], sym_f = fi;
+                best_n.assign(open.size(), Dev::HistBestNewton{});
+                if (lw != nullptr) {
+                    if (!dev_.hist_symmetric_apply(nodes, how, (uint32_t)sym_f, lw->edge, &best_n, &err)) fail_str(err);
+                    bool some = false;
+                    for (const Dev::HistBestNewton& b : best_n) some = some || b.valid;
+                    if (!some) fail_str("LambdaMART histogram grower: internal error: no node splits under the level's winner");
+                    levels_++;
+                }
+                best.resize(best_n.size());
+                for (size_t i = 0; i < best_n.size(); i++) {
+                    const Dev::HistBestNewton& b = best_n[i];
+                    best[i] = {b.imp, b.ql, b.qtot, b.edge, b.nl, b.valid, 0u};
+                }
+            } else if (newton_.on) {  // the selection below reads the fields the two records share
                 if (mono_on_) {
                     node_bounds.clear();
                     for (const Open& o : open) node_bounds.push_back(o.bd);
@@ -183,11 +212,15 @@ class HistGrower {
                 const Open& o = open[a];
                 const Dev::HistBest* w = nullptr;
                 size_t wf = 0;
-                for (size_t fi = 0; fi < F; fi++) {  // the last maximum: a later feature wins among equals
-                    const Dev::HistBest& b = best[a * F + fi];
-                    if (b.valid && (w == nullptr || b.imp >= w->imp)) w = &b, wf = fi;
+                if (symmetric_) {  // (the record's valid already holds the whole rule, the Newton gain's floor included)
+                    if (best[a].valid) w = &best[a], wf = sym_f;
+                } else {
+                    for (size_t fi = 0; fi < F; fi++) {  // the last maximum: a later feature wins among equals
+                        const Dev::HistBest& b = best[a * F + fi];
+                        if (b.valid && (w == nullptr || b.imp >= w->imp)) w = &b, wf = fi;
+                    }
                 }
-                if (w != nullptr && newton_.on) {  // the node's totals (Qnode, Wnode) arrive with every record of the node
+                if (w != nullptr && newton_.on && !symmetric_) {  // the node's totals (Qnode, Wnode) arrive with every record of the node
                     const Dev::HistBestNewton& b = best_n[a * F + wf];
                     const double gain = mono_on_ ? w->imp - monotone_term(b.qtot, b.wtot, s_l, s_w, o.bd) : newton_gain(w->imp, b.qtot, b.wtot, s_l, s_w);
                     if (!(gain > newton_.min_split_gain)) w = nullptr;
@@ -236,6 +269,9 @@ class HistGrower {
 
     // monotone constraints: the leaves of the last tree whose value a bound moved
     uint32_t clamped_leaves() const { return clamped_; }
+
+    // symmetric trees: the levels of the last tree that split (its depth in splits)
+    uint32_t levels() const { return levels_; }
 
     // leaf-wise growth: the largest histogram pool a tree of this grower asked for, in bytes (0: none yet)
     uint64_t pool_bytes() const { return pool_bytes_; }
@@ -437,6 +473,8 @@ class HistGrower {
     bool mono_on_ = false;                                     // some monotone sign is not 0
     std::vector<int> mono_;                                    // (then) the signs, by entry of feats_
     uint32_t clamped_ = 0;
+    bool symmetric_ = false;                                   // every node of a level splits on one candidate
+    uint32_t levels_ = 0;
     std::vector<uint32_t> sel_;                                // the tree's features as slots of the bins (empty: all)
     std::vector<float> edges_;
     std::vector<uint32_t> nedges_;

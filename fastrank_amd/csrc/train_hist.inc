@@ -495,6 +495,60 @@ bool DeviceDataset::hist_search_monotone(const std::vector<HistNode>& nodes, con
     return hist_fetch(best, h.best_n, m.stream, err);  // (bounds is the caller's, read by the copy above until this has waited)
 }
 
+bool DeviceDataset::hist_search_symmetric(const std::vector<HistNode>& nodes, const HistSymSearch& how, std::vector<HistSymBest>* best,
+                                          std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    const size_t A = nodes.size();
+    best->assign(h.Ft, HistSymBest{});
+    if (A == 0 || h.Ft == 0) return true;
+    if (h.k < 2 || h.k > HIST_MAX_BINS) return hist_fail(err, "internal error: no bins built");
+    if (!m.hist_stage_nodes(nodes, how.newton, err) || !h.best_sym.ensure(h.Ft, err)) return false;
+    const uint32_t* fsel = h.f_sampled ? h.fsel.p : nullptr;
+    {
+        ProfScope ps("hist_scan_sym_kernel", m.stream);
+        if (how.newton)
+            hist_scan_sym_kernel<true><<<h.Ft, 256, 0, m.stream>>>(h.nodes.p, (uint32_t)A, h.Ft, h.k, h.nedges.p, fsel, h.cnt.p, h.sum.p, h.wsum.p,
+                                                                   how.min_leaf, how.s_l, how.s_w, how.lambda_l2, how.min_sum_hessian,
+                                                                   how.min_split_gain, h.best_sym.p);
+        else
+            hist_scan_sym_kernel<false><<<h.Ft, 256, 0, m.stream>>>(h.nodes.p, (uint32_t)A, h.Ft, h.k, h.nedges.p, fsel, h.cnt.p, h.sum.p, nullptr,
+                                                                    how.min_leaf, 0, 0, 0.0, 0.0, 0.0, h.best_sym.p);
+    }
+    FR_HIP(hipGetLastError());
+    return hist_fetch(best, h.best_sym, m.stream, err);
+}
+
+bool DeviceDataset::hist_symmetric_apply(const std::vector<HistNode>& nodes, const HistSymSearch& how, uint32_t fi, uint32_t edge,
+                                         std::vector<HistBestNewton>* out, std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    const size_t A = nodes.size();
+    out->assign(A, HistBestNewton{});
+    if (A == 0) return true;
+    if (h.k < 2 || h.k > HIST_MAX_BINS || fi >= h.Ft || edge + 1 >= h.k) return hist_fail(err, "internal error: a level's split outside the histograms");
+    // (the level's search has staged these very nodes, and has waited for the stream: they are uploaded again only if they differ)
+    static_assert(sizeof(HistNode) == sizeof(HistItemDev), "host and device records differ");
+    const bool staged = h.nodes_h.size() == A && std::memcmp(h.nodes_h.data(), nodes.data(), A * sizeof(HistItemDev)) == 0;
+    if ((!staged && !m.hist_stage_nodes(nodes, how.newton, err)) || !h.best_n.ensure(A, err)) return false;
+    {
+        ProfScope ps("hist_sym_apply_kernel", m.stream);
+        if (how.newton)
+            hist_sym_apply_kernel<true><<<(unsigned)A, 64, 0, m.stream>>>(h.nodes.p, h.Ft, h.k, fi, edge, h.cnt.p, h.sum.p, h.wsum.p, how.min_leaf,
+                                                                          how.s_l, how.s_w, how.lambda_l2, how.min_sum_hessian, how.min_split_gain,
+                                                                          h.best_n.p);
+        else
+            hist_sym_apply_kernel<false><<<(unsigned)A, 64, 0, m.stream>>>(h.nodes.p, h.Ft, h.k, fi, edge, h.cnt.p, h.sum.p, nullptr, how.min_leaf, 0, 0,
+                                                                           0.0, 0.0, 0.0, h.best_n.p);
+    }
+    FR_HIP(hipGetLastError());
+    return hist_fetch(out, h.best_n, m.stream, err);
+}
+
 bool DeviceDataset::hist_split(const std::vector<HistSplit>& splits, const std::vector<HistNode>& builds, const std::vector<HistSub>& subs,
                                uint32_t next_slots, std::string* err, bool newton) {
     static_assert(sizeof(HistSplit) == sizeof(HistSplitDev) && sizeof(HistSub) == sizeof(HistSubDev), "host and device records differ");
@@ -594,7 +648,7 @@ void DeviceDataset::hist_end() {
     std::lock_guard<std::mutex> lk(m.mu);
     auto& h = m.hist;
     (void)hipStreamSynchronize(m.stream);
-    h.cnt.release(), h.cnt_o.release(), h.sum.release(), h.sum_o.release(), h.wsum.release(), h.wsum_o.release(), h.best.release(), h.best_n.release(), h.lam_in.release(), h.wt_in.release();
+    h.cnt.release(), h.cnt_o.release(), h.sum.release(), h.sum_o.release(), h.wsum.release(), h.wsum_o.release(), h.best.release(), h.best_n.release(), h.best_sym.release(), h.lam_in.release(), h.wt_in.release();
     h.pcnt.release(), h.psum.release(), h.pwsum.release(), h.rec.release(), h.pick.release(), h.bounds.release();
     h.pool_slots = 0;
 }

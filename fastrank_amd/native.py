@@ -218,7 +218,7 @@ def hist_bins(dataset: CDataset, split_candidates: int):
 def hist_tree(dataset: CDataset, lam: np.ndarray, wt: np.ndarray, split_candidates: int, max_depth: int,
               min_leaf_support: int, queries=None, features=None, split_gain: str = "variance", lambda_l2: float = 0.0,
               min_sum_hessian: float = 0.0, min_split_gain: float = 0.0, max_leaves: int = 0, monotone=None,
-              clamped_out: Optional[list] = None, goss=None) -> CModel:
+              clamped_out: Optional[list] = None, goss=None, symmetric: bool = False) -> CModel:
     """One tree of LambdaMART's histogram grower for the gradients lam / wt (indexed by instance id).  `queries` (indices of
     the view's queries) / `features` (feature ids): the tree's sample; gradients outside the query sample are not read.
     `split_gain` = "newton": the second-order gain with `lambda_l2`, `min_sum_hessian` and `min_split_gain` (DESIGN.md
@@ -228,7 +228,9 @@ def hist_tree(dataset: CDataset, lam: np.ndarray, wt: np.ndarray, split_candidat
     constraints"), level-wise or leaf-wise, and the number of leaves a bound moved is appended to `clamped_out` when that is
     a list.  `goss` = (top_rate, other_rate, seed, tree) (needs `split_gain` = "newton"): the tree is fitted to the GOSS list
     of the sample's instances under the key of tree `tree` of `seed`, the kept others' gradients amplified (DESIGN.md section
-    11, "GOSS"); level-wise or leaf-wise, with or without monotone signs.  At the defaults the call is the one it was."""
+    11, "GOSS"); level-wise or leaf-wise, with or without monotone signs.  `symmetric` = True (level-wise, without monotone
+    signs or GOSS): every node of a level splits on the level's one winning candidate ("Symmetric
+    trees"), under either gain.  At the defaults the call is the one it was."""
     lam = np.ascontiguousarray(lam, dtype=np.float64)
     wt = np.ascontiguousarray(wt, dtype=np.float64)
     if lam.shape != wt.shape or lam.ndim != 1:
@@ -239,6 +241,20 @@ def hist_tree(dataset: CDataset, lam: np.ndarray, wt: np.ndarray, split_candidat
     fs = None if features is None else np.ascontiguousarray(features, dtype=np.uint32)
     sample = (None if qs is None else qs.ctypes.data, 0 if qs is None else len(qs),
               None if fs is None else fs.ctypes.data, 0 if fs is None else len(fs))
+    if symmetric:
+        if goss is not None or int(max_leaves) != 0 or (monotone is not None and any(int(c) != 0 for c in monotone.values())):
+            raise ValueError("symmetric trees are grown level-wise, without monotone constraints or goss")
+        if split_gain != "newton" and (lambda_l2 != 0.0 or min_sum_hessian != 0.0 or min_split_gain != 0.0):
+            raise ValueError("lambda_l2, min_sum_hessian and min_split_gain need split_gain='newton'")
+        return CModel(
+            _unwrap(
+                _load().fr_debug_hist_tree_symmetric(
+                    dataset.pointer, int(split_candidates), int(max_depth), int(min_leaf_support), lam.ctypes.data,
+                    wt.ctypes.data, lam.shape[0], *sample, 1 if split_gain == "newton" else 0, float(lambda_l2),
+                    float(min_sum_hessian), float(min_split_gain),
+                )
+            )
+        )
     if goss is not None:
         if split_gain != "newton":
             raise ValueError("goss needs split_gain='newton'")

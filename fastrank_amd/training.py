@@ -143,7 +143,14 @@ class LambdaMARTParams(_LearnerParams):
     part is a function of `seed`, the tree and the document (a stream of its own).  Histogram grower under `split_gain` =
     "newton" only, with every other key; `goss_other_rate` needs `goss_top_rate` > 0; both keys are written only when they
     differ from their defaults.  The training stats then report `goss_ms`, `goss_instances` and `goss_top` (per tree: the
-    documents the tree was fitted to, and how many of them for their gradient) ("GOSS")."""
+    documents the tree was fitted to, and how many of them for their gradient) ("GOSS").
+    `symmetric_trees` (default False; written only when set): symmetric (oblivious) trees.  Every node of a level splits on
+    the same (feature, threshold), the candidate whose importance summed over the level's open nodes is largest; a node
+    that cannot split under it becomes a leaf, so leaves may sit at any depth and every leaf still honours
+    `min_leaf_support`.  One split has to pay off across a whole level, which regularises strongly.  Histogram grower,
+    level-wise (`max_leaves` = 0) and without `monotone_constraints`; both split gains and every other key compose.  The
+    trees are ordinary decision trees; the training stats then report `symmetric_trees` and `levels` (per tree, the levels
+    that split) ("Symmetric trees")."""
 
     VARIANT: ClassVar[str] = "LambdaMART"
 
@@ -174,13 +181,14 @@ class LambdaMARTParams(_LearnerParams):
     monotone_constraints: Dict[str, int] = dataclasses.field(default_factory=dict)
     goss_top_rate: float = 0.0
     goss_other_rate: float = 0.1
+    symmetric_trees: bool = False
 
     _WIRE_DEFAULTS: ClassVar[Dict[str, Any]] = {"grower": "exact", "query_sampling_rate": 1.0, "feature_sampling_rate": 1.0, "seed": 0,
                                                 "validation_queries": [], "early_stopping_rounds": 0, "split_gain": "variance",
                                                 "lambda_l2": 0.0, "min_sum_hessian": 0.0, "min_split_gain": 0.0,
                                                 "max_leaves": 0, "truncation_level": 0, "lambda_norm": False, "objective": "ndcg",
                                                 "drop_rate": 0.0, "max_drop": 50, "skip_drop": 0.5, "monotone_constraints": {},
-                                                "goss_top_rate": 0.0, "goss_other_rate": 0.1}
+                                                "goss_top_rate": 0.0, "goss_other_rate": 0.1, "symmetric_trees": False}
     _OBJECTIVES: ClassVar[Dict[str, str]] = {"ap": "map", "rr": "mrr", "xendcg": "xendcg"}
 
     def __post_init__(self):

@@ -249,6 +249,13 @@ const CResult *fr_debug_hist_tree_leafwise(const CDataset *dataset, uint32_t spl
                                            size_t len, const uint32_t *queries, size_t n_queries,
                                            const uint32_t *features, size_t n_features, int newton, double lambda_l2,
                                            double min_sum_hessian, double min_split_gain, uint32_t max_leaves);
+/* One symmetric tree ("Symmetric trees"): every node of a level splits on the level's one winning
+ * candidate.  newton != 0: the Newton split gain with the three numbers (0 without it). */
+const CResult *fr_debug_hist_tree_symmetric(const CDataset *dataset, uint32_t split_candidates, uint32_t max_depth,
+                                            uint32_t min_leaf_support, const double *lambda, const double *weight,
+                                            size_t len, const uint32_t *queries, size_t n_queries,
+                                            const uint32_t *features, size_t n_features, int newton, double lambda_l2,
+                                            double min_sum_hessian, double min_split_gain);
 /* One tree under monotone constraints ("Monotone constraints"; Newton gain only): the numbers of
  * fr_debug_hist_tree_newton, max_leaves = 0 (level-wise) or >= 2 (leaf-wise), and mono_features / mono_signs[n_mono] =
  * feature ids of the view and their signs in {-1, 0, 1}.  *clamped_leaves_out (may be NULL): the leaves whose value a

@@ -33,12 +33,16 @@ early_stopping_rounds 0, 1 or 2; and for the histogram grower split_gain "newton
 min_split_gain (0, the feature tests' values, one that refuses the root, and now and then a floor exactly on the edge of
 its comparison: the hessian sum of the left side of the first tree's root split, or that split's gain) and max_leaves 2, 3, 5, 12, 31 or 255 (then
 now and then a max_depth up to 32).  The three flags combine freely.
+--symmetric (off by default): about half of the histogram-grower cases without a leaf budget also set symmetric_trees
+("Symmetric trees"), drawn from a fourth generator of its own, so the committed seeds' cases do not
+move; their trees are held to tests/lambdamart_symmetric_model.py on the tree's sample, under either gain, and the stats must
+carry `symmetric_trees` and one `levels` entry per tree.  The closing line counts them as "symmetric".
 The closing JSON line counts, per key, the cases that DREW it (set it away from its default) and those in which it BOUND
 (tests/lambdamart_composed_model.py says what that means), both from the restatement's side.
 --dry: no device; the composed restatement trains each generated case (views and files included) on the CPU, and the share
 of cases on which the oracle's evaluator reports an error -- at zero scores or after any tree -- is printed with the same
 drawn and bound counts.
-Usage: python tools/fuzz_lambdamart.py --iters 300 [--seed 0] [--objective] [--rank-objective mixed] [--compose] [--dry]"""
+Usage: python tools/fuzz_lambdamart.py --iters 300 [--seed 0] [--objective] [--rank-objective mixed] [--compose] [--symmetric] [--dry]"""
 import argparse
 import json
 import os
@@ -55,6 +59,8 @@ from fuzz_parity import make_case  # noqa: E402
 from oracle import pyoracle as o  # noqa: E402
 from tests import lambdamart_composed_model as cm  # noqa: E402
 from tests import lambdamart_leafwise_model as lw  # noqa: E402
+from tests import lambdamart_sample_model as sm  # noqa: E402
+from tests import lambdamart_symmetric_model as sy  # noqa: E402
 from tests.conftest import ranksvm_presence  # noqa: E402
 from tests.lambdamart_composed_model import expected_gradients, training_measure  # noqa: E402,F401
 
@@ -196,6 +202,20 @@ def request(fr, measure, p, num_trees=None):
     return req
 
 
+class SymmetricComposed(cm.Composed):
+    """The composed restatement of a case that sets symmetric_trees: only the tree changes."""
+
+    def tree(self, lam, wt, fsel, qsel, **override):
+        p = dict(self.p, **override)
+        rows = sm.instance_rows(self.queries, qsel)
+        return sy.tree_on_sample(self.X, lam, wt, self.order_ids, self.feats, self.binned, rows, fsel, p["max_depth"], p["min_leaf_support"],
+                                 p["split_candidates"], split_gain=p["split_gain"], **{k: p[k] for k in cm.NEWTON_NUMBERS})
+
+
+def composed(p):
+    return SymmetricComposed if p.get("symmetric_trees") else cm.Composed
+
+
 class EvaluatorError(Exception):
     """The library refused a training run because some query's DCG exceeds its ideal DCG."""
 
@@ -205,7 +225,7 @@ class CaseData:
     rows / matrix / oracle dataset / composed restatement the checks work on (instance ids renumbered 0.. over the view's
     rows, ascending)."""
 
-    def __init__(self, rng, tmp, objective_rng=None, compose_rng=None):
+    def __init__(self, rng, tmp, objective_rng=None, compose_rng=None, symmetric_rng=None):
         X, y, qid, self.measure, self.p, self.from_file = make_lm_case(rng)
         self.p.update(draw_objective(objective_rng))
         self.present, self.views, self.path = None, 0, None
@@ -238,7 +258,9 @@ class CaseData:
         self.names = cm._names(qid[rows])
         if compose_rng is not None:
             self.p.update(draw_compose(compose_rng, self.p, self.names))
-        self.model = cm.Composed(self.X, self.y, self.c, self.measure, self.p, self.feats, self.present, self.names)
+        if symmetric_rng is not None and symmetric_rng.random() < 0.5 and self.p["grower"] == "histogram" and not self.p.get("max_leaves"):
+            self.p["symmetric_trees"] = True
+        self.model = composed(self.p)(self.X, self.y, self.c, self.measure, self.p, self.feats, self.present, self.names)
         if compose_rng is not None and self.p.get("split_gain") == "newton" and compose_rng.random() < 0.75:
             # a floor exactly on the edge of its comparison: the hessian sum of the left side of the first tree's root split
             # (still admitted), or that split's gain (refused)
@@ -247,7 +269,7 @@ class CaseData:
             value = None if edge is None else edge[key == "min_split_gain"]
             if value is not None and np.isfinite(value) and value > 0.0:
                 self.p[key] = value
-                self.model = cm.Composed(self.X, self.y, self.c, self.measure, self.p, self.feats, self.present, self.names, self.model.binned)
+                self.model = composed(self.p)(self.X, self.y, self.c, self.measure, self.p, self.feats, self.present, self.names, self.model.binned)
         self.queries, self.order_ids = self.model.queries, self.model.order_ids
         self.reported, self.norms = self.model.reported, self.model.norms
 
@@ -263,8 +285,8 @@ class CaseData:
 class Case(CaseData):
     """The case on the device: the view `g`."""
 
-    def __init__(self, fr, native, rng, tmp, objective_rng=None, compose_rng=None):
-        CaseData.__init__(self, rng, tmp, objective_rng, compose_rng)
+    def __init__(self, fr, native, rng, tmp, objective_rng=None, compose_rng=None, symmetric_rng=None):
+        CaseData.__init__(self, rng, tmp, objective_rng, compose_rng, symmetric_rng)
         self.fr, self.native = fr, native
         X, y, qid = self.input
         g = fr.CDataset.open_ranksvm(self.path) if self.from_file else fr.CDataset.from_numpy(X, y, qid)
@@ -304,6 +326,10 @@ class Case(CaseData):
             return "stats keys: %s" % sorted((set(st) & cm.OPTIONAL_STATS) ^ set(exp))
         if st["grower"] != self.p["grower"] or any(v is not None and st[k] != v for k, v in exp.items()):
             return "stats do not echo the request"
+        if ("symmetric_trees" in st or "levels" in st) != bool(self.p.get("symmetric_trees")):
+            return "stats keys: symmetric_trees / levels"
+        if self.p.get("symmetric_trees") and (st["symmetric_trees"] is not True or len(st["levels"]) != st["trees"]):
+            return "stats do not echo symmetric_trees"
         return None
 
     def check(self):
@@ -446,19 +472,22 @@ def main():
     ap.add_argument("--objective", action="store_true", help="draw a truncation level and lambda_norm for every case")
     ap.add_argument("--rank-objective", default="ndcg", choices=["ndcg", "map", "mrr", "mixed"], help="the `objective` key of every case (mixed: drawn per case)")
     ap.add_argument("--compose", action="store_true", help="draw the sampling, validation, Newton and leaf-budget keys for every case")
+    ap.add_argument("--symmetric", action="store_true", help="set symmetric_trees for about half of the histogram-grower cases without a leaf budget")
     args = ap.parse_args()
     global RANK_OBJECTIVE, RANK_RNG
     RANK_OBJECTIVE, RANK_RNG = args.rank_objective, np.random.default_rng([args.seed, 2])
     rng = np.random.default_rng(args.seed)
     objective_rng = np.random.default_rng([args.seed, 1]) if args.objective else None
     compose_rng = np.random.default_rng([args.seed, 3]) if args.compose else None
+    symmetric_rng = np.random.default_rng([args.seed, 4]) if args.symmetric else None
     counts = Counts(args.compose, args.objective, args.rank_objective)
     o.set_mean_segment(o.DEVICE_MEAN_SEGMENT)
     t0 = time.time()
-    growers, views, files = {}, 0, 0
+    growers, views, files, symmetric = {}, 0, 0, 0
 
     def tally(case):
-        nonlocal views, files
+        nonlocal views, files, symmetric
+        symmetric += bool(case.p.get("symmetric_trees"))
         growers[case.p["grower"]] = growers.get(case.p["grower"], 0) + 1
         views += case.views
         files += case.from_file
@@ -467,12 +496,13 @@ def main():
         errs = 0
         with tempfile.TemporaryDirectory() as tmp:
             for _ in range(args.iters):
-                case = CaseData(rng, tmp, objective_rng, compose_rng)
+                case = CaseData(rng, tmp, objective_rng, compose_rng, symmetric_rng)
                 tally(case)
                 errs += case.model.train(observe=True)["oracle_error"]
                 counts.add(case)
         print(json.dumps({"iters": args.iters, "dry": True, "oracle_error_while_training": int(errs), "growers": growers, "sampled_views": views,
-                          "file_loaded": int(files), "drawn": counts.drawn, "bound": counts.bound, "seconds": round(time.time() - t0, 1)}))
+                          "file_loaded": int(files), "drawn": counts.drawn, "bound": counts.bound, **({"symmetric": symmetric} if args.symmetric else {}),
+                          "seconds": round(time.time() - t0, 1)}))
         return 0 if errs * 10 <= args.iters else 1
     import fastrank_amd as fr
     from fastrank_amd import native
@@ -480,7 +510,7 @@ def main():
     ended = None
     with tempfile.TemporaryDirectory() as tmp:
         for it in range(args.iters):
-            case = Case(fr, native, rng, tmp, objective_rng, compose_rng)
+            case = Case(fr, native, rng, tmp, objective_rng, compose_rng, symmetric_rng)
             tally(case)
             what = None
             try:
@@ -505,7 +535,7 @@ def main():
         print("too many cases where device and oracle both report an error: %d of %d" % (errs, args.iters))
     print(json.dumps({"iters": args.iters, "mismatches": bad, "both_error": errs, "split_nodes": nodes, "growers": growers,
                       "sampled_views": views, "file_loaded": int(files), "drawn": counts.drawn, "bound": counts.bound, "ended_at_iter": ended,
-                      "seconds": round(time.time() - t0, 1)}))
+                      **({"symmetric": symmetric} if args.symmetric else {}), "seconds": round(time.time() - t0, 1)}))
     return 1 if bad or errs * 10 > args.iters else 0
 
 

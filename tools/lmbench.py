@@ -22,6 +22,8 @@
                                                                # monotone constraints on the first 8 features, signs +1, -1, +1, ...
     python tools/lmbench.py --shape 30k --trees 100 --grower histogram --split-gain newton --goss-top-rate 0.2 --goss-other-rate 0.1
                                                                # gradient-based one-side sampling (reports goss_ms and the lists' sizes)
+    python tools/lmbench.py --shape 30k --trees 100 --grower histogram --symmetric --validation-rate 0.1
+                                                               # symmetric trees (reports the levels that split per tree)
 Every other parameter is the LambdaMART default (TrainRequest.lambdamart()).
 """
 import argparse
@@ -71,6 +73,8 @@ def device_run(args, X, y, qid):
         req.params.max_drop, req.params.skip_drop = args.max_drop, args.skip_drop
     if args.goss_top_rate > 0:  # (the other rate needs a top rate)
         req.params.goss_top_rate, req.params.goss_other_rate = args.goss_top_rate, args.goss_other_rate
+    if args.symmetric:
+        req.params.symmetric_trees = True
     if args.monotone:  # the first N features of the dataset, alternating signs from +1
         names = ds.feature_index_to_name()
         first = sorted(names)[:args.monotone]
@@ -143,6 +147,9 @@ def device_run(args, X, y, qid):
         out["goss"] = {"goss_top_rate": st["goss_top_rate"], "goss_other_rate": st["goss_other_rate"], "goss_ms_per_tree": st["goss_ms"] / T,
                        "instances_mean": float(np.mean(st["goss_instances"])), "instances_min": int(np.min(st["goss_instances"])),
                        "instances_max": int(np.max(st["goss_instances"])), "top": int(st["goss_top"][0])}
+    if args.symmetric:  # (only with the key, like the stats object)
+        out["symmetric"] = {"levels_mean": float(np.mean(st["levels"])), "levels_min": int(np.min(st["levels"])),
+                            "levels_max": int(np.max(st["levels"]))}
     if args.held_out_measures and args.validation_rate > 0:  # AP / RR / NDCG of the model over the held-out queries
         held = set(req.params.validation_queries)
         out["held_out"] = {}
@@ -207,6 +214,7 @@ def parser():
     ap.add_argument("--monotone", type=int, default=0, help="monotone constraints on the first N features, signs alternating from +1 (needs --split-gain newton)")
     ap.add_argument("--goss-top-rate", type=float, default=0.0, help="GOSS: the share of a tree's documents kept for their |gradient| (0: off; needs --split-gain newton)")
     ap.add_argument("--goss-other-rate", type=float, default=0.1, help="GOSS: the share of a tree's documents drawn from the others")
+    ap.add_argument("--symmetric", action="store_true", help="symmetric trees: every node of a level splits on one candidate (histogram grower, level-wise)")
     ap.add_argument("--held-out-measures", action="store_true", help="with --validation-rate: report the model's mean AP, RR and NDCG over the held-out queries")
     ap.add_argument("--warmup-trees", type=int, default=0, help="train this many trees untimed before the measured training")
     ap.add_argument("--no-kernel-profile", action="store_true", help="leave the library's per-kernel event timing off during the timed training")
