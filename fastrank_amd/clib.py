@@ -25,6 +25,13 @@ class _CResult(C.Structure):
     _fields_ = [("error_message", C.c_void_p), ("success", C.c_void_p)]
 
 
+class HistTreeOptions(C.Structure):  # FrHistTreeOptions (include/fastrank.h); a fresh one is all zeros
+    _fields_ = [("split_candidates", C.c_uint32), ("max_depth", C.c_uint32), ("min_leaf_support", C.c_uint32), ("newton", C.c_int32), ("lambda_l2", C.c_double),
+                ("min_sum_hessian", C.c_double), ("min_split_gain", C.c_double), ("max_leaves", C.c_uint32), ("symmetric", C.c_int32), ("queries", C.c_void_p),
+                ("n_queries", C.c_size_t), ("features", C.c_void_p), ("n_features", C.c_size_t), ("mono_features", C.c_void_p), ("mono_signs", C.c_void_p),
+                ("n_mono", C.c_size_t), ("goss", C.c_int32), ("top_rate", C.c_double), ("other_rate", C.c_double), ("seed", C.c_uint64), ("tree", C.c_uint32)]
+
+
 _lib = None
 
 
@@ -86,18 +93,11 @@ def _load():
         "fr_debug_explain_table": (vp, [vp, vp, sz, C.c_uint32]),
         "fr_debug_lambda_gradients": (vp, [vp, vp, vp, C.c_char_p, C.c_double, vp, vp, sz]),
         "fr_debug_hist_bins": (vp, [vp, C.c_uint32, sz, sz, vp, vp, vp, vp, vp]),
-        "fr_debug_hist_tree": (res, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, sz]),
+        "fr_debug_hist_tree": (res, [vp, C.POINTER(HistTreeOptions), vp, vp, sz, vp]),
         "fr_debug_lambdamart_sample": (vp, [vp, C.c_char_p, C.c_uint32]),
         "fr_debug_lambdamart_dart_plan": (vp, [C.c_char_p, C.c_uint32]),
         "fr_debug_dart_scores": (vp, [vp, vp, vp, sz, vp, sz, vp, vp, sz]),
         "fr_debug_lambda_gradients_sampled": (vp, [vp, vp, vp, C.c_char_p, C.c_double, vp, sz, vp, vp, sz]),
-        "fr_debug_hist_tree_sampled": (res, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, sz, vp, sz, vp, sz]),
-        "fr_debug_hist_tree_newton": (res, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, sz, vp, sz, vp, sz, C.c_double, C.c_double, C.c_double]),
-        "fr_debug_hist_tree_leafwise": (res, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, sz, vp, sz, vp, sz, C.c_int, C.c_double, C.c_double, C.c_double, C.c_uint32]),
-        "fr_debug_hist_tree_symmetric": (res, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, sz, vp, sz, vp, sz, C.c_int, C.c_double, C.c_double, C.c_double]),
-        "fr_debug_hist_tree_monotone": (res, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, sz, vp, sz, vp, sz, C.c_double, C.c_double, C.c_double, C.c_uint32, vp, vp, sz, vp]),
-        "fr_debug_hist_tree_goss": (res, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, sz, vp, sz, vp, sz, C.c_double, C.c_double, C.c_double, C.c_uint32, vp, vp, sz,
-                                          C.c_double, C.c_double, C.c_uint64, C.c_uint32]),
         "fr_debug_goss_select": (vp, [vp, vp, sz, C.c_double, C.c_double, C.c_uint64, C.c_uint32, vp, sz, vp, vp, sz, vp, vp]),
         "fr_debug_lambda_gradients_opts": (vp, [vp, vp, vp, C.c_char_p, C.c_double, vp, sz, C.c_char_p, vp, vp, sz]),
         "fr_evaluate_dense": (vp, [vp, vp, vp, C.c_char_p, vp, sz, C.POINTER(vp)]),
@@ -130,9 +130,6 @@ def _load():
         fn.argtypes = argtypes
     _lib = L
     return L
-
-
-EXPORTED_SYMBOLS = None  # filled lazily by exported_symbols()
 
 
 def exported_symbols() -> List[str]:

@@ -1977,33 +1977,96 @@ const void* fr_debug_hist_bins(const CDataset* dataset, uint32_t split_candidate
     });
 }
 
-// The body of the five tree hooks below.  who: the exported function's name, for its error messages; opt: what the grower is
-// made with; queries / features: the tree's sample as fr_debug_hist_tree_sampled describes it.  mono_features / mono_signs
-// [n_mono]: monotone signs by feature id of the view (fr_debug_hist_tree_monotone; opt.monotone is made from them);
-// *clamped_out: the leaves a bound moved.  goss: the tree is a GOSS one (fr_debug_hist_tree_goss).
-static const CResult* hist_tree_debug(const std::string& who, const CDataset* dataset, fr::HistGrowOptions opt, const double* lambda,
-                                      const double* weight, size_t len, const uint32_t* queries, size_t n_queries, const uint32_t* features,
-                                      size_t n_features, const uint32_t* mono_features = nullptr, const int32_t* mono_signs = nullptr,
-                                      size_t n_mono = 0, uint32_t* clamped_out = nullptr, const fr::HistGoss* goss = nullptr) {
+// What the tree hook and the selection hook below share: the view's lists, a query sample (queries == NULL: every query) as
+// flags with its instance count, and values by instance id gathered into instance-list order.
+struct HistDebugInput {
+    const frdev::HostCSR& csr;
+    std::vector<uint32_t> ids, positions, feats;
+    const bool sampled;
+    std::vector<unsigned char> flags;  // [nq] when sampled
+    size_t n_t;                        // the sample's instances
+    HistDebugInput(fr::DatasetView& view, const uint32_t* queries, size_t n_queries) : csr(view.host_csr()), sampled(queries != nullptr) {
+        hist_debug_lists(view, &ids, &positions, &feats);
+        n_t = ids.size();
+        if (!sampled) return;
+        flags = debug_query_flags(queries, n_queries, csr.nq);
+        n_t = 0;
+        for (size_t q = 0; q < csr.nq; q++)
+            if (flags[q]) n_t += csr.qoff[q + 1] - csr.qoff[q];
+    }
+    const unsigned char* query_flags() const { return sampled ? flags.data() : nullptr; }
+    // The caller's values go to the device as they are, also outside the query sample: the grower must not read those.  An
+    // id past len is refused (too_short) inside the sample only; so is, when not_finite is given, a value that is not finite.
+    std::vector<double> gather(const double* values, size_t len, const std::string& too_short, const char* not_finite = nullptr) const {
+        std::vector<double> out(ids.size(), 0.0);
+        size_t g = 0;
+        for (size_t q = 0; q < csr.nq; q++) {
+            const bool read = !sampled || flags[q];
+            for (size_t j = csr.qoff[q]; j < csr.qoff[q + 1]; j++, g++) {
+                if (ids[g] >= len) {
+                    if (!read) continue;
+                    fr::fail_str(too_short);
+                }
+                out[g] = values[ids[g]];
+                if (not_finite && read && !std::isfinite(out[g])) fr::fail_str(not_finite);
+            }
+        }
+        return out;
+    }
+};
+// (the bins stay with the view: leave them without a sample, also when the hook fails)
+struct HistDebugUnsample {
+    fr::HistGrower& g;
+    ~HistDebugUnsample() {
+        try {
+            g.set_sample(nullptr, 0, nullptr);
+        } catch (...) {
+        }
+    }
+};
+
+// the two GOSS rates as a debug hook takes them: the request parser's ranges, and top_rate > 0
+static bool goss_debug_rates_ok(double top_rate, double other_rate) {
+    return std::isfinite(top_rate) && top_rate > 0.0 && top_rate < 1.0 && std::isfinite(other_rate) && other_rate > 0.0 && other_rate <= 1.0 &&
+           top_rate + other_rate <= 1.0;
+}
+static const char* const GOSS_DEBUG_RATES = "top_rate must lie in (0, 1), other_rate in (0, 1], and their sum must be at most 1";
+
+// what is wrong with the tree hook's options (nullptr: nothing): every rule that can be held without the dataset
+static const char* hist_tree_options_error(const FrHistTreeOptions& o) {
+    if (o.max_depth < 1) return "max_depth must be at least 1";
+    if (o.max_leaves == 1) return "max_leaves must be 0 (level-wise) or at least 2";
+    for (double x : {o.lambda_l2, o.min_sum_hessian, o.min_split_gain})
+        if (!(std::isfinite(x) && x >= 0.0) || (!o.newton && x != 0.0))
+            return "lambda_l2, min_sum_hessian and min_split_gain must be finite and at least 0, and 0 without the Newton gain";
+    if (o.goss && !goss_debug_rates_ok(o.top_rate, o.other_rate)) return GOSS_DEBUG_RATES;
+    if ((o.n_mono != 0 || o.goss) && !o.newton) return "monotone constraints and GOSS need the Newton gain";
+    if (o.symmetric && (o.max_leaves != 0 || o.n_mono != 0 || o.goss))
+        return "symmetric trees are grown level-wise (max_leaves = 0), without monotone constraints or GOSS";
+    return nullptr;
+}
+
+// One tree of the histogram grower for lambda / weight by instance id, under the options
+// include/fastrank.h describes; *clamped_leaves_out (may be NULL): the leaves a monotone bound moved.
+const CResult* fr_debug_hist_tree(const CDataset* dataset, const FrHistTreeOptions* opt, const double* lambda, const double* weight, size_t len,
+                                  uint32_t* clamped_leaves_out) {
     return c_call<CModel>([&]() {
+        const std::string who = "fr_debug_hist_tree";
+        if (!opt) fr::fail_str("NULL pointer: tree options");
+        const FrHistTreeOptions& o = *opt;
+        if (const char* wrong = hist_tree_options_error(o)) fr::fail_str(who + ": " + wrong);
+        if (clamped_leaves_out) *clamped_leaves_out = 0;
         const CDataset& ds = require_dataset(dataset);
         if (!lambda || !weight) fr::fail_str("NULL pointer: gradient inputs");
-        if (opt.max_depth < 1) fr::fail_str("max_depth must be at least 1");
         std::lock_guard<std::mutex> lk(api_mu_of(ds));
         fr::DatasetView& view = *ds.view;
-        const frdev::HostCSR& csr = view.host_csr();
-        std::vector<uint32_t> ids, positions, feats, sel;
-        hist_debug_lists(view, &ids, &positions, &feats);
-        std::vector<unsigned char> flags;
-        size_t n_t = ids.size();
-        if (queries) {
-            flags = debug_query_flags(queries, n_queries, csr.nq);
-            n_t = 0;
-            for (size_t q = 0; q < csr.nq; q++)
-                if (flags[q]) n_t += csr.qoff[q + 1] - csr.qoff[q];
-        }
-        if (features) {
-            std::vector<uint32_t> want(features, features + n_features);
+        const HistDebugInput in(view, o.queries, o.n_queries);
+        const std::vector<uint32_t>& feats = in.feats;
+        fr::HistGrowOptions grow{o.split_candidates, o.max_depth, o.min_leaf_support, fr::HistNewton(), o.max_leaves, {}, o.symmetric != 0};
+        if (o.newton) grow.newton = {true, o.lambda_l2, o.min_sum_hessian, o.min_split_gain};
+        std::vector<uint32_t> sel;
+        if (o.features) {
+            std::vector<uint32_t> want(o.features, o.features + o.n_features);
             std::sort(want.begin(), want.end());
             for (size_t i = 0; i < want.size(); i++) {
                 const auto it = std::lower_bound(feats.begin(), feats.end(), want[i]);
@@ -2012,158 +2075,32 @@ static const CResult* hist_tree_debug(const std::string& who, const CDataset* da
                 sel.push_back((uint32_t)(it - feats.begin()));
             }
         }
-        if (n_mono != 0) {
-            if (!mono_features || !mono_signs) fr::fail_str("NULL pointer: monotone constraints");
-            opt.monotone.assign(feats.size(), 0);
-            for (size_t i = 0; i < n_mono; i++) {
-                const auto it = std::lower_bound(feats.begin(), feats.end(), mono_features[i]);
-                if (it == feats.end() || *it != mono_features[i]) fr::fail_str(who + ": feature " + std::to_string(mono_features[i]) + " is not in the view");
-                if (mono_signs[i] < -1 || mono_signs[i] > 1) fr::fail_str(who + ": a monotone sign must be -1, 0 or 1");
-                opt.monotone[(size_t)(it - feats.begin())] = (int)mono_signs[i];
+        if (o.n_mono != 0) {
+            if (!o.mono_features || !o.mono_signs) fr::fail_str("NULL pointer: monotone constraints");
+            grow.monotone.assign(feats.size(), 0);
+            for (size_t i = 0; i < o.n_mono; i++) {
+                const auto it = std::lower_bound(feats.begin(), feats.end(), o.mono_features[i]);
+                if (it == feats.end() || *it != o.mono_features[i]) fr::fail_str(who + ": feature " + std::to_string(o.mono_features[i]) + " is not in the view");
+                if (o.mono_signs[i] < -1 || o.mono_signs[i] > 1) fr::fail_str(who + ": a monotone sign must be -1, 0 or 1");
+                grow.monotone[(size_t)(it - feats.begin())] = (int)o.mono_signs[i];
             }
         }
-        // the caller's values go to the device as they are, also outside the query sample: the grower must not read those
-        std::vector<double> lam(ids.size(), 0.0), wt(ids.size(), 0.0);
-        size_t g = 0;
-        for (size_t q = 0; q < csr.nq; q++) {
-            for (size_t j = csr.qoff[q]; j < csr.qoff[q + 1]; j++, g++) {
-                if (ids[g] >= len) {
-                    if (queries && !flags[q]) continue;
-                    fr::fail_str(who + ": the gradient arrays are shorter than the largest " + (queries ? "sampled " : "") + "instance id");
-                }
-                lam[g] = lambda[ids[g]];
-                wt[g] = weight[ids[g]];
-            }
-        }
-        fr::HistGrower grower(view.device(), feats, opt);
-        grower.prepare(positions);
-        struct Unsample {  // (the bins stay with the view: leave them without a sample, also when growing fails)
-            fr::HistGrower& g;
-            ~Unsample() {
-                try {
-                    g.set_sample(nullptr, 0, nullptr);
-                } catch (...) {
-                }
-            }
-        } unsample{grower};
-        grower.set_sample(queries ? flags.data() : nullptr, (uint32_t)n_t, features ? &sel : nullptr);
+        const std::string too_short = who + ": the gradient arrays are shorter than the largest " + (in.sampled ? "sampled " : "") + "instance id";
+        const std::vector<double> lam = in.gather(lambda, len, too_short), wt = in.gather(weight, len, too_short);
+        const fr::HistGoss goss{o.top_rate, o.other_rate, fr::GossKeys::of_tree(o.seed, o.tree)};
+        fr::HistGrower grower(view.device(), feats, grow);
+        grower.prepare(in.positions);
+        HistDebugUnsample unsample{grower};
+        grower.set_sample(in.query_flags(), (uint32_t)in.n_t, o.features ? &sel : nullptr);
         return new_model([&] {
             fr::Model tree;
             tree.kind = fr::Model::DecisionTree;
-            tree.tree = grower.grow(lam.data(), wt.data(), nullptr, nullptr, goss);
-            if (clamped_out) *clamped_out = grower.clamped_leaves();
+            fr::HistTreeReport rep;
+            tree.tree = grower.grow(lam.data(), wt.data(), o.goss ? &goss : nullptr, &rep);
+            if (clamped_leaves_out) *clamped_leaves_out = rep.clamped_leaves;
             return tree;
         });
     });
-}
-
-const CResult* fr_debug_hist_tree(const CDataset* dataset, uint32_t split_candidates, uint32_t max_depth, uint32_t min_leaf_support,
-                                  const double* lambda, const double* weight, size_t len) {
-    return hist_tree_debug("fr_debug_hist_tree", dataset, {split_candidates, max_depth, min_leaf_support}, lambda, weight, len, nullptr, 0, nullptr, 0);
-}
-
-// fr_debug_hist_tree on a sample: queries[n_queries] = indices of the view's queries (NULL: all), features[n_features] =
-// feature ids of the view (NULL: all).  Gradients of instances outside the query sample are not read.
-const CResult* fr_debug_hist_tree_sampled(const CDataset* dataset, uint32_t split_candidates, uint32_t max_depth, uint32_t min_leaf_support,
-                                          const double* lambda, const double* weight, size_t len, const uint32_t* queries,
-                                          size_t n_queries, const uint32_t* features, size_t n_features) {
-    return hist_tree_debug("fr_debug_hist_tree_sampled", dataset, {split_candidates, max_depth, min_leaf_support}, lambda, weight, len, queries,
-                           n_queries, features, n_features);
-}
-
-// fr_debug_hist_tree_sampled under the Newton split gain ("Newton split gain")
-const CResult* fr_debug_hist_tree_newton(const CDataset* dataset, uint32_t split_candidates, uint32_t max_depth, uint32_t min_leaf_support,
-                                         const double* lambda, const double* weight, size_t len, const uint32_t* queries,
-                                         size_t n_queries, const uint32_t* features, size_t n_features, double lambda_l2,
-                                         double min_sum_hessian, double min_split_gain) {
-    const double numbers[3] = {lambda_l2, min_sum_hessian, min_split_gain};
-    for (double x : numbers)
-        if (!(std::isfinite(x) && x >= 0.0))
-            return c_call<CModel>([&]() -> CModel* { fr::fail_str("fr_debug_hist_tree_newton: lambda_l2, min_sum_hessian and min_split_gain must be finite and at least 0"); });
-    return hist_tree_debug("fr_debug_hist_tree_newton", dataset,
-                           {split_candidates, max_depth, min_leaf_support, fr::HistNewton{true, lambda_l2, min_sum_hessian, min_split_gain}}, lambda,
-                           weight, len, queries, n_queries, features, n_features);
-}
-
-// One tree grown leaf-wise ("Leaf-wise growth"): fr_debug_hist_tree_sampled / _newton (newton != 0: the
-// three numbers are read) under a leaf budget max_leaves >= 2.
-const CResult* fr_debug_hist_tree_leafwise(const CDataset* dataset, uint32_t split_candidates, uint32_t max_depth, uint32_t min_leaf_support,
-                                           const double* lambda, const double* weight, size_t len, const uint32_t* queries,
-                                           size_t n_queries, const uint32_t* features, size_t n_features, int newton, double lambda_l2,
-                                           double min_sum_hessian, double min_split_gain, uint32_t max_leaves) {
-    if (max_leaves < 2)
-        return c_call<CModel>([&]() -> CModel* { fr::fail_str("fr_debug_hist_tree_leafwise: max_leaves must be at least 2"); });
-    const double numbers[3] = {lambda_l2, min_sum_hessian, min_split_gain};
-    for (double x : numbers)
-        if (!(std::isfinite(x) && x >= 0.0) || (!newton && x != 0.0))
-            return c_call<CModel>([&]() -> CModel* { fr::fail_str("fr_debug_hist_tree_leafwise: lambda_l2, min_sum_hessian and min_split_gain must be finite and at least 0, and 0 without the Newton gain"); });
-    const fr::HistNewton gain = newton ? fr::HistNewton{true, lambda_l2, min_sum_hessian, min_split_gain} : fr::HistNewton();
-    return hist_tree_debug("fr_debug_hist_tree_leafwise", dataset, {split_candidates, max_depth, min_leaf_support, gain, max_leaves}, lambda, weight,
-                           len, queries, n_queries, features, n_features);
-}
-
-// One tree under monotone constraints ("Monotone constraints"): the Newton gain's numbers as
-// fr_debug_hist_tree_newton takes them, max_leaves = 0 (level-wise) or >= 2 (leaf-wise), and mono_features / mono_signs[n_mono]:
-// feature ids of the view and their signs in {-1, 0, 1}.  *clamped_leaves_out (may be NULL): the leaves a bound moved.
-const CResult* fr_debug_hist_tree_monotone(const CDataset* dataset, uint32_t split_candidates, uint32_t max_depth, uint32_t min_leaf_support,
-                                           const double* lambda, const double* weight, size_t len, const uint32_t* queries,
-                                           size_t n_queries, const uint32_t* features, size_t n_features, double lambda_l2,
-                                           double min_sum_hessian, double min_split_gain, uint32_t max_leaves,
-                                           const uint32_t* mono_features, const int32_t* mono_signs, size_t n_mono,
-                                           uint32_t* clamped_leaves_out) {
-    if (max_leaves == 1)
-        return c_call<CModel>([&]() -> CModel* { fr::fail_str("fr_debug_hist_tree_monotone: max_leaves must be 0 (level-wise) or at least 2"); });
-    const double numbers[3] = {lambda_l2, min_sum_hessian, min_split_gain};
-    for (double x : numbers)
-        if (!(std::isfinite(x) && x >= 0.0))
-            return c_call<CModel>([&]() -> CModel* { fr::fail_str("fr_debug_hist_tree_monotone: lambda_l2, min_sum_hessian and min_split_gain must be finite and at least 0"); });
-    if (clamped_leaves_out) *clamped_leaves_out = 0;
-    return hist_tree_debug("fr_debug_hist_tree_monotone", dataset,
-                           {split_candidates, max_depth, min_leaf_support, fr::HistNewton{true, lambda_l2, min_sum_hessian, min_split_gain}, max_leaves, {}},
-                           lambda, weight, len, queries, n_queries, features, n_features, mono_features, mono_signs, n_mono, clamped_leaves_out);
-}
-
-// One symmetric tree ("Symmetric trees"): fr_debug_hist_tree_sampled / _newton (newton != 0: the three
-// numbers are read) with every node of a level split on the level's one winning candidate.
-const CResult* fr_debug_hist_tree_symmetric(const CDataset* dataset, uint32_t split_candidates, uint32_t max_depth, uint32_t min_leaf_support,
-                                            const double* lambda, const double* weight, size_t len, const uint32_t* queries,
-                                            size_t n_queries, const uint32_t* features, size_t n_features, int newton, double lambda_l2,
-                                            double min_sum_hessian, double min_split_gain) {
-    const double numbers[3] = {lambda_l2, min_sum_hessian, min_split_gain};
-    for (double x : numbers)
-        if (!(std::isfinite(x) && x >= 0.0) || (!newton && x != 0.0))
-            return c_call<CModel>([&]() -> CModel* { fr::fail_str("fr_debug_hist_tree_symmetric: lambda_l2, min_sum_hessian and min_split_gain must be finite and at least 0, and 0 without the Newton gain"); });
-    const fr::HistNewton gain = newton ? fr::HistNewton{true, lambda_l2, min_sum_hessian, min_split_gain} : fr::HistNewton();
-    return hist_tree_debug("fr_debug_hist_tree_symmetric", dataset, {split_candidates, max_depth, min_leaf_support, gain, 0u, {}, true}, lambda,
-                           weight, len, queries, n_queries, features, n_features);
-}
-
-// the two GOSS rates as a debug hook takes them: the request parser's ranges, and top_rate > 0
-static bool goss_debug_rates_ok(double top_rate, double other_rate) {
-    return std::isfinite(top_rate) && top_rate > 0.0 && top_rate < 1.0 && std::isfinite(other_rate) && other_rate > 0.0 && other_rate <= 1.0 &&
-           top_rate + other_rate <= 1.0;
-}
-static const char* const GOSS_DEBUG_RATES = ": top_rate must lie in (0, 1), other_rate in (0, 1], and their sum must be at most 1";
-
-// One GOSS tree ("GOSS"): fr_debug_hist_tree_monotone (n_mono = 0: no constraint) fitted to the GOSS list
-// of the sample's list under the two rates and the key of tree `tree` of `seed`, from amplified gradients.
-const CResult* fr_debug_hist_tree_goss(const CDataset* dataset, uint32_t split_candidates, uint32_t max_depth, uint32_t min_leaf_support,
-                                       const double* lambda, const double* weight, size_t len, const uint32_t* queries, size_t n_queries,
-                                       const uint32_t* features, size_t n_features, double lambda_l2, double min_sum_hessian,
-                                       double min_split_gain, uint32_t max_leaves, const uint32_t* mono_features,
-                                       const int32_t* mono_signs, size_t n_mono, double top_rate, double other_rate, uint64_t seed,
-                                       uint32_t tree) {
-    const double numbers[3] = {lambda_l2, min_sum_hessian, min_split_gain};
-    bool ok = max_leaves != 1;
-    for (double x : numbers) ok = ok && std::isfinite(x) && x >= 0.0;
-    if (!ok)
-        return c_call<CModel>([&]() -> CModel* { fr::fail_str("fr_debug_hist_tree_goss: max_leaves must be 0 or at least 2; lambda_l2, min_sum_hessian and min_split_gain must be finite and at least 0"); });
-    if (!goss_debug_rates_ok(top_rate, other_rate))
-        return c_call<CModel>([&]() -> CModel* { fr::fail_str(std::string("fr_debug_hist_tree_goss") + GOSS_DEBUG_RATES); });
-    const fr::HistGoss goss{top_rate, other_rate, fr::GossKeys::of_tree(seed, tree)};
-    return hist_tree_debug("fr_debug_hist_tree_goss", dataset,
-                           {split_candidates, max_depth, min_leaf_support, fr::HistNewton{true, lambda_l2, min_sum_hessian, min_split_gain}, max_leaves, {}},
-                           lambda, weight, len, queries, n_queries, features, n_features, mono_features, mono_signs, n_mono, nullptr, &goss);
 }
 
 // The GOSS selection on its own: lambda[len] by instance id; queries[n_queries] (NULL: all) = the tree's query sample, whose
@@ -2176,47 +2113,20 @@ const void* fr_debug_goss_select(const CDataset* dataset, const double* lambda, 
     return status_call([&]() {
         const CDataset& ds = require_dataset(dataset);
         if (!lambda || !list_out || !top_out || !n_g_out || !tau_out) fr::fail_str("NULL pointer: fr_debug_goss_select");
-        if (!goss_debug_rates_ok(top_rate, other_rate)) fr::fail_str(std::string("fr_debug_goss_select") + GOSS_DEBUG_RATES);
+        if (!goss_debug_rates_ok(top_rate, other_rate)) fr::fail_str(std::string("fr_debug_goss_select: ") + GOSS_DEBUG_RATES);
         std::lock_guard<std::mutex> lk(api_mu_of(ds));
         fr::DatasetView& view = *ds.view;
-        const frdev::HostCSR& csr = view.host_csr();
-        std::vector<uint32_t> ids, positions, feats;
-        hist_debug_lists(view, &ids, &positions, &feats);
-        if (cap < ids.size()) fr::fail_str("fr_debug_goss_select: the outputs are shorter than the instance list");
-        std::vector<unsigned char> flags;
-        size_t n_t = ids.size();
-        if (queries) {
-            flags = debug_query_flags(queries, n_queries, csr.nq);
-            n_t = 0;
-            for (size_t q = 0; q < csr.nq; q++)
-                if (flags[q]) n_t += csr.qoff[q + 1] - csr.qoff[q];
-        }
-        std::vector<double> lam(ids.size(), 0.0);
-        size_t g = 0;
-        for (size_t q = 0; q < csr.nq; q++)
-            for (size_t j = csr.qoff[q]; j < csr.qoff[q + 1]; j++, g++) {
-                if (ids[g] >= len) {
-                    if (queries && !flags[q]) continue;
-                    fr::fail_str("fr_debug_goss_select: the gradient array is shorter than the largest instance id");
-                }
-                lam[g] = lambda[ids[g]];
-                if (!std::isfinite(lam[g]) && !(queries && !flags[q])) fr::fail_str("fr_debug_goss_select: a gradient is not finite");
-            }
+        const HistDebugInput in(view, queries, n_queries);
+        if (cap < in.ids.size()) fr::fail_str("fr_debug_goss_select: the outputs are shorter than the instance list");
+        const std::vector<double> lam = in.gather(lambda, len, "fr_debug_goss_select: the gradient array is shorter than the largest instance id",
+                                                  "fr_debug_goss_select: a gradient is not finite");
         frdev::DeviceDataset& dev = view.device();
         // (the selection reads no bin: the smallest bin matrix there is keeps the hook cheap on a view that has none yet)
-        fr::HistGrower grower(dev, feats, {2u, 1u, 1u, fr::HistNewton{true, 0.0, 0.0, 0.0}, 0u, {}});
-        grower.prepare(positions);
-        struct Unsample {
-            fr::HistGrower& g;
-            ~Unsample() {
-                try {
-                    g.set_sample(nullptr, 0, nullptr);
-                } catch (...) {
-                }
-            }
-        } unsample{grower};
-        grower.set_sample(queries ? flags.data() : nullptr, (uint32_t)n_t, nullptr);
-        const fr::GossPlan plan = fr::goss_plan(n_t, top_rate, other_rate);
+        fr::HistGrower grower(dev, in.feats, {2u, 1u, 1u, fr::HistNewton{true, 0.0, 0.0, 0.0}, 0u, {}});
+        grower.prepare(in.positions);
+        HistDebugUnsample unsample{grower};
+        grower.set_sample(in.query_flags(), (uint32_t)in.n_t, nullptr);
+        const fr::GossPlan plan = fr::goss_plan(in.n_t, top_rate, other_rate);
         std::string err;
         uint32_t n_g = 0;
         if (!dev.hist_goss(lam.data(), plan.n_top, plan.p, plan.amp, fr::GossKeys::of_tree(seed, tree), &n_g, tau_out, &err)) fr::fail_str(err);

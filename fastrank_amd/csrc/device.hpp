@@ -323,9 +323,17 @@ class DeviceDataset {
     struct HistNode { uint32_t slot, begin, end; };             // a node's histogram slot and its stretch of the index list
     struct HistSplit { uint32_t begin, end, fslot, edge, nl; }; // bins 0..edge of feature slot fslot go left: nl of them
     struct HistSub { uint32_t parent, small, large; };          // next level's slot `large` = this level's `parent` - next level's `small`
-    struct HistBest { double imp; long long ql, qtot; uint32_t edge, nl, valid, pad; };
-    // split_gain = "newton" ("Newton split gain"): the histograms also hold sum W, the record also the candidate's and the node's
-    struct HistBestNewton { double imp; long long ql, qtot, wl, wtot; uint32_t edge, nl, valid, pad; };
+    struct HistBounds { double lo, hi; };                       // a node's interval for its output ("Monotone constraints")
+    // What a tree's searches are made with.  newton ("Newton split gain"): the histograms also hold sum W, imp = term(L) +
+    // term(R), term = G G / (H + lambda_l2) with G = ldexp(Q, -s_l), H = ldexp(W, -s_w), and a candidate also needs
+    // H >= min_sum_hessian and H + lambda_l2 > 0 on both sides; without it min_leaf alone is read.  min_split_gain is read by
+    // the symmetric pair only (elsewhere the host applies it).  monotone ("Monotone constraints"; Newton gain only): the two
+    // sides' outputs are clamped to the node's interval, a clamped side's term is (2 G) v - ((H + lambda_l2) v) v, and the
+    // order vL <= vR (sign +1) / vL >= vR (sign -1) is among a candidate's conditions.
+    struct HistSearch { uint32_t min_leaf; bool newton; int s_l, s_w; double lambda_l2, min_sum_hessian, min_split_gain; bool monotone; };
+    // A candidate (valid = 0: none): bins 0..edge go left, nl instances of sums (ql, wl); (qtot, wtot): the node's.  Under the
+    // variance criterion wl = wtot = 0.  fi: the feature's index among the tree's, from the leaf-wise calls only (else 0).
+    struct HistCand { double imp; long long ql, qtot, wl, wtot; uint32_t edge, nl, valid, fi; };
     // bins of the instance list (positions[n], rf_positions' output) for the features `feats` and k = split_candidates
     // (2..256); kept until any of the three changes.  *built = false when the kept ones were reused.
     bool hist_bins(const uint32_t* positions, size_t n, const std::vector<uint32_t>& feats, uint32_t k, bool* built, std::string* err);
@@ -335,8 +343,8 @@ class DeviceDataset {
     // The sample of the trees grown from now on, until hist_bins is called again.  query_flags[nq] (nullptr: every query):
     // the root's index list becomes the ascending list of the instance-list indices whose query is flagged, made on the
     // device; n_t must be their number.  fsel[f_t] (nullptr: every feature): ascending slots of the bin matrix; a level's
-    // histograms are then [slot][f_t][bin] and HistBest is indexed by these f_t features.  HistSplit::fslot stays a slot of
-    // the bin matrix.  Bins and edges are never rebuilt.
+    // histograms are then [slot][f_t][bin] and a search's records are indexed by these f_t features.  HistSplit::fslot
+    // stays a slot of the bin matrix.  Bins and edges are never rebuilt.
     // keep_queries (with query_flags == nullptr): the query sample of the previous call stays (a fixed training split under
     // per-tree feature samples); only the feature sample changes.
     bool hist_sample(const unsigned char* query_flags, uint32_t n_t, const uint32_t* fsel, size_t f_t, std::string* err,
@@ -353,51 +361,40 @@ class DeviceDataset {
     // Q / W of the tree to grow, from the last gradient pass (lam_list == nullptr) or from host arrays in instance-list
     // order.  *all_zero: every lambda is 0 (nothing was quantised); s_l / s_w: the exponents S of the definition
     bool hist_quantise(const double* lam_list, const double* wt_list, int* s_l, int* s_w, bool* all_zero, std::string* err);
-    // index list = 0..n-1 (the sample's root list); the level holds the root's histogram in slot 0.  newton: with sum W
-    bool hist_root(std::string* err, bool newton = false);
-    // best[a * features + slot]: node a's last-maximum candidate of that feature (valid = 0: none)
-    bool hist_search(const std::vector<HistNode>& nodes, uint32_t min_leaf, std::vector<HistBest>* best, std::string* err);
-    // the same under the Newton gain (a level made with newton = true): imp = term(L) + term(R), term = G G / (H + lambda_l2)
-    // with G = ldexp(Q, -s_l), H = ldexp(W, -s_w); a candidate also needs H >= min_sum_hessian and H + lambda_l2 > 0 on both sides
-    bool hist_search_newton(const std::vector<HistNode>& nodes, uint32_t min_leaf, int s_l, int s_w, double lambda_l2,
-                            double min_sum_hessian, std::vector<HistBestNewton>* best, std::string* err);
-    // Monotone constraints ("Monotone constraints"; Newton gain only).  hist_monotone: signs[features] in {-1, 0, +1}, one per
-    // row of the bin matrix, kept until the next call or the next bins.  hist_search_monotone: hist_search_newton with node
-    // a's interval bounds[a] for the two sides' clamped outputs, a clamped side's term (2 G) v - ((H + lambda_l2) v) v, and
-    // the order vL <= vR (sign +1) / vL >= vR (sign -1) among a candidate's conditions.  The leaf-wise calls do the same
-    // when HistLeafSearch::monotone is set (the root's interval is the whole line, the children's come with the step).
-    struct HistBounds { double lo, hi; };
+    // index list = the sample's root list (0..n-1 without one); the level holds the root's histogram in slot 0.  newton: with sum W
+    bool hist_root(bool newton, std::string* err);
+    // One level's search.  best[a * features + slot]: node a's last-maximum candidate of that feature (the level was made
+    // with how.newton); bounds: nullptr unless how.monotone, then node a's interval is (*bounds)[a]
+    bool hist_search(const std::vector<HistNode>& nodes, const HistSearch& how, const std::vector<HistBounds>* bounds,
+                     std::vector<HistCand>* best, std::string* err);
+    // signs[features] in {-1, 0, +1}, one per row of the bin matrix, kept until the next call or the next bins
     bool hist_monotone(const int* signs, size_t features, std::string* err);
-    bool hist_search_monotone(const std::vector<HistNode>& nodes, const std::vector<HistBounds>& bounds, uint32_t min_leaf, int s_l, int s_w,
-                              double lambda_l2, double min_sum_hessian, std::vector<HistBestNewton>* best, std::string* err);
     // Symmetric trees ("Symmetric trees").  hist_search_symmetric: best[f] = the last-maximum candidate of feature f of the
     // tree's by its level importance I over `nodes` in their order (key: I, -inf for a NaN one; valid = 0: no node splits
     // under any edge of f).  hist_symmetric_apply: out[a] = node a's record under the candidate (feature fi of the tree's,
-    // edge), valid = the node splits under it; under the variance criterion wl = wtot = 0.
+    // edge), valid = the node splits under it.
     struct HistSymBest { double key; uint32_t edge, valid; };
-    struct HistSymSearch { uint32_t min_leaf; bool newton; int s_l, s_w; double lambda_l2, min_sum_hessian, min_split_gain; };
-    bool hist_search_symmetric(const std::vector<HistNode>& nodes, const HistSymSearch& how, std::vector<HistSymBest>* best, std::string* err);
-    bool hist_symmetric_apply(const std::vector<HistNode>& nodes, const HistSymSearch& how, uint32_t fi, uint32_t edge,
-                              std::vector<HistBestNewton>* out, std::string* err);
+    bool hist_search_symmetric(const std::vector<HistNode>& nodes, const HistSearch& how, std::vector<HistSymBest>* best, std::string* err);
+    bool hist_symmetric_apply(const std::vector<HistNode>& nodes, const HistSearch& how, uint32_t fi, uint32_t edge, std::vector<HistCand>* out,
+                              std::string* err);
     // stable partition of the splitting nodes' stretches, then the next level (next_slots histograms; 0: none): `builds` are
     // built from their stretches, `subs` by subtraction from the level just searched
     bool hist_split(const std::vector<HistSplit>& splits, const std::vector<HistNode>& builds, const std::vector<HistSub>& subs,
-                    uint32_t next_slots, std::string* err, bool newton = false);
+                    uint32_t next_slots, bool newton, std::string* err);
     bool hist_leaf_sums(const std::vector<HistNode>& leaves, std::vector<long long>* qw /*[leaf][2]*/, std::string* err);
     void hist_end();  // frees the level histograms and the leaf-wise pool (the bins stay)
     // Leaf-wise growth ("Leaf-wise growth"): a pool of `slots` histograms replaces the level arrays, one leaf is split per
     // step and one record per searched node comes back (hist_pick_kernel reduces the features on the device).
-    struct HistPick { double imp; long long ql, qtot, wl, wtot; uint32_t edge, nl, valid, fi; };  // fi: index among the tree's features
-    struct HistLeafSearch { uint32_t min_leaf; bool newton; int s_l, s_w; double lambda_l2, min_sum_hessian; bool monotone = false; };
-    // index list = the sample's root list; the root's histogram into slot 0 of a fresh pool; *root: the root's record
-    bool hist_leaf_begin(uint32_t slots, const HistLeafSearch& how, HistPick* root, std::string* err);
+    // index list = the sample's root list; the root's histogram into slot 0 of a fresh pool; *root: the root's record (under
+    // how.monotone its interval is the whole line, the children's come with the step)
+    bool hist_leaf_begin(uint32_t slots, const HistSearch& how, HistCand* root, std::string* err);
     // One split step: the stable partition of split's stretch alone; then, when small_slot != HIST_NO_SLOT, the smaller child's
     // histogram is built into small_slot; a searched larger child is derived in place in parent_slot (parent - smaller) and a
     // searched child is scanned.  pick[0]: the lhs's record, pick[1]: the rhs's (written for the searched ones only).
     static constexpr uint32_t HIST_NO_SLOT = 0xffffffffu;
     // (bounds[0] / bounds[1]: the lhs's / rhs's interval, read only when how.monotone)
     struct HistLeafStep { HistSplit split; uint32_t parent_slot, small_slot; bool search_lhs, search_rhs; HistBounds bounds[2] = {}; };
-    bool hist_leaf_step(const HistLeafStep& step, const HistLeafSearch& how, HistPick pick[2], std::string* err);
+    bool hist_leaf_step(const HistLeafStep& step, const HistSearch& how, HistCand pick[2], std::string* err);
 
     // --- model explanation (explain.hip, a translation unit of its own) ---------
     // What that unit reads of a dataset, once this dataset's stream has drained: the feature tiles (kernels_score.inc:

@@ -382,6 +382,7 @@ struct DeviceDataset::Impl : DatasetDesc {
         std::vector<HistItemDev> items_h, items_bh, nodes_h;
         std::vector<HistSplitDev> splits_h;
         std::vector<HistSubDev> subs_h;
+        std::vector<HistBestDev> best_h;  // (the other way: a variance level's records as fetched, before they are widened)
     } hist;
     bool hist_items(const std::vector<HistItemDev>& stretches, std::vector<HistItemDev>& host, DevBuf<HistItemDev>& dev, std::string* err);
     bool hist_qof(std::string* err);
@@ -390,7 +391,8 @@ struct DeviceDataset::Impl : DatasetDesc {
     bool hist_zero(uint32_t* cnt, unsigned long long* sum, unsigned long long* wsum, size_t off, size_t cells, std::string* err);
     bool hist_flag_scan(uint32_t begin, uint32_t count, std::string* err);  // hist.scan = exclusive prefix sums of hist.flag over [begin, begin + count)
     bool hist_stage_nodes(const std::vector<DeviceDataset::HistNode>& nodes, bool newton, std::string* err);
-    bool hist_leaf_scan(const HistLeafKids& kids, uint32_t count, const DeviceDataset::HistLeafSearch& how, DeviceDataset::HistPick* out,
+    bool hist_root_build(uint32_t* cnt, unsigned long long* sum, unsigned long long* wsum, std::string* err);  // the root's index list and histogram
+    bool hist_leaf_scan(const HistLeafKids& kids, uint32_t count, const DeviceDataset::HistSearch& how, DeviceDataset::HistCand* out,
                         std::string* err, const HistLeafBoundsDev* bounds = nullptr);
     DevBuf<uint64_t> forest;
     DevBuf<uint32_t> tree_fdesc;  // tree_ensemble_rank_kernel: per-feature descriptors, Eytzinger threshold tables

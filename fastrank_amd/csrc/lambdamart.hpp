@@ -659,11 +659,10 @@ class LambdaMARTTrainer {
                 if (fixed_q) hist->set_sample(nullptr, t_n, sample_f ? &smp.features : nullptr, true);  // (T's root list stays)
                 else hist->set_sample(sample_q ? qflags.data() : nullptr, t_n, sample_f ? &smp.features : nullptr);
             }
-            double leaf_secs = 0.0;
-            uint32_t n_leaves = 0;
-            std::shared_ptr<TreeNode> root = hist ? hist->grow(nullptr, nullptr, &leaf_secs, &n_leaves, goss ? &goss_t : nullptr)
+            HistTreeReport rep;
+            std::shared_ptr<TreeNode> root = hist ? hist->grow(nullptr, nullptr, goss ? &goss_t : nullptr, &rep)
                                                   : grower.grow_lambda_tree(dev, *off_t, *ids_t, *feats_t, pos_t, rst);
-            auto tc = tnow() - std::chrono::duration_cast<std::chrono::steady_clock::duration>(std::chrono::duration<double>(leaf_secs));
+            auto tc = tnow() - std::chrono::duration_cast<std::chrono::steady_clock::duration>(std::chrono::duration<double>(rep.leaf_seconds));
             // leaves (exact grower): route every instance through a copy of the tree whose leaves hold their index
             std::vector<TreeNode*> leaves;
             std::shared_ptr<TreeNode> routing = hist ? nullptr : number_leaves(*root, leaves);
@@ -733,15 +732,15 @@ class LambdaMARTTrainer {
             stats_.t_grow += secs(ts, ta) + secs(tb, tc);
             stats_.t_leaves += secs(tc, td);
             stats_.t_update += secs(tu, te);
-            stats_.sum_leaves += n_leaves;
+            if (hist) stats_.sum_leaves += rep.leaves;
             if (hist) stats_.pool_bytes = hist->pool_bytes();
-            if (hist && !signs.empty()) stats_.clamped_leaves.push_back(hist->clamped_leaves());
+            if (hist && !signs.empty()) stats_.clamped_leaves.push_back(rep.clamped_leaves);
             if (goss) {
-                stats_.t_goss += hist->goss_seconds();
-                stats_.goss_instances.push_back(hist->goss_instances());
-                stats_.goss_top.push_back(hist->goss_top());
+                stats_.t_goss += rep.goss_seconds;
+                stats_.goss_instances.push_back(rep.goss_instances);
+                stats_.goss_top.push_back(rep.goss_top);
             }
-            if (hist && p_.symmetric_trees) stats_.levels.push_back(hist->levels());
+            if (hist && p_.symmetric_trees) stats_.levels.push_back(rep.levels);
             stats_.train_measure.push_back(mean);
             out.members.push_back(std::move(tm));
             if (!p_.quiet) {

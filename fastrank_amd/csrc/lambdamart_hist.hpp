@@ -39,15 +39,15 @@ struct HistNewton {
     double lambda_l2 = 0.0, min_sum_hessian = 0.0, min_split_gain = 0.0;
 };
 
-// what a grower is made with: k = split_candidates (bins per feature), the depth limit, the least leaf support, the split
-// criterion, the leaf budget (0: level-wise growth) and the monotone signs: one of {-1, 0, +1} per entry of the ascending
-// feature list (empty, or all 0: no constraint; a non-zero one needs the Newton gain)
 // GOSS for one tree: the two rates and the tree's key K_t
 struct HistGoss {
     double top_rate = 0.0, other_rate = 0.1;
     uint64_t key = 0;
 };
 
+// what a grower is made with: k = split_candidates (bins per feature), the depth limit, the least leaf support, the split
+// criterion, the leaf budget (0: level-wise growth) and the monotone signs: one of {-1, 0, +1} per entry of the ascending
+// feature list (empty, or all 0: no constraint; a non-zero one needs the Newton gain)
 struct HistGrowOptions {
     uint32_t k = 0, max_depth = 0, min_leaf = 0;
     HistNewton newton;
@@ -56,9 +56,23 @@ struct HistGrowOptions {
     bool symmetric = false;
 };
 
+// what grow() reports of the tree it made, next to the tree
+struct HistTreeReport {
+    uint32_t leaves = 1;
+    double leaf_seconds = 0.0;    // the share of the leaf sums
+    uint32_t clamped_leaves = 0;  // monotone constraints: the leaves whose value a bound moved
+    uint32_t levels = 0;          // symmetric trees: the levels that split (the tree's depth in splits)
+    // GOSS: the list's length, the top set's size, tau and the wall seconds of making the list
+    uint32_t goss_instances = 0, goss_top = 0;
+    uint64_t goss_tau = 0;
+    double goss_seconds = 0.0;
+};
+
 class HistGrower {
+    using Dev = frdev::DeviceDataset;
+
   public:
-    HistGrower(frdev::DeviceDataset& dev, std::vector<uint32_t> feats, const HistGrowOptions& opt)
+    HistGrower(Dev& dev, std::vector<uint32_t> feats, const HistGrowOptions& opt)
         : dev_(dev), feats_(std::move(feats)), k_(opt.k), max_depth_(opt.max_depth), min_leaf_(opt.min_leaf), newton_(opt.newton), max_leaves_(opt.max_leaves), symmetric_(opt.symmetric) {
         for (int c : opt.monotone) mono_on_ = mono_on_ || c != 0;
         if (symmetric_ && max_leaves_ != 0) fail_str("LambdaMART histogram grower: symmetric trees are grown level by level (max_leaves must be 0)");
@@ -105,142 +119,130 @@ class HistGrower {
     }
 
     // One tree for the gradients of the last gradient pass (lam_list == nullptr) or for lam_list / wt_list[n] in
-    // instance-list order.  *leaf_seconds: the share of the leaf sums.  *n_leaves: the tree's number of leaves.
-    // goss (Newton gain only): the tree is fitted to the GOSS list of the sample's list; goss_instances() / goss_top() /
-    // goss_seconds() / goss_tau() then speak of this tree.
-    std::shared_ptr<TreeNode> grow(const double* lam_list, const double* wt_list, double* leaf_seconds = nullptr, uint32_t* n_leaves = nullptr,
-                                   const HistGoss* goss = nullptr) {
-        using Dev = frdev::DeviceDataset;
+    // instance-list order.  goss (nullptr: none; Newton gain only): the tree is fitted to the GOSS list of the sample's list.
+    // *report (may be nullptr): what else the tree left behind.
+    // The calls a tree makes, in order: hist_goss (GOSS only), hist_quantise; level-wise hist_root, then per level
+    // hist_search (symmetric trees: hist_search_symmetric and hist_symmetric_apply) and hist_split; leaf-wise
+    // hist_leaf_begin, then one hist_leaf_step per split; at the end hist_leaf_sums (after hist_root, when nothing was searched).
+    std::shared_ptr<TreeNode> grow(const double* lam_list, const double* wt_list, const HistGoss* goss = nullptr, HistTreeReport* report = nullptr) {
         std::string err;
-        int s_l = 0, s_w = 0;
+        HistTreeReport rep;
         bool all_zero = false;
         n_ = n_sample_;
         if (goss != nullptr) {
             if (!newton_.on) fail_str("LambdaMART histogram grower: GOSS needs the Newton gain");
             auto t0 = std::chrono::steady_clock::now();
             const GossPlan plan = goss_plan(n_sample_, goss->top_rate, goss->other_rate);
-            if (!dev_.hist_goss(lam_list, plan.n_top, plan.p, plan.amp, goss->key, &goss_n_, &goss_tau_, &err)) fail_str(err);
-            goss_top_ = plan.n_top;
-            n_ = goss_n_;
-            goss_secs_ = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            if (!dev_.hist_goss(lam_list, plan.n_top, plan.p, plan.amp, goss->key, &rep.goss_instances, &rep.goss_tau, &err)) fail_str(err);
+            rep.goss_top = plan.n_top;
+            n_ = rep.goss_instances;
+            rep.goss_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         }
-        if (!dev_.hist_quantise(lam_list, wt_list, &s_l, &s_w, &all_zero, &err)) fail_str(err);
+        how_ = {min_leaf_, newton_.on, 0, 0, newton_.lambda_l2, newton_.min_sum_hessian, newton_.min_split_gain, mono_on_};
+        if (!dev_.hist_quantise(lam_list, wt_list, &how_.s_l, &how_.s_w, &all_zero, &err)) fail_str(err);
         auto root = std::make_shared<TreeNode>();
-        if (n_leaves) *n_leaves = 1;
-        clamped_ = 0;
-        levels_ = 0;
-        if (all_zero) return root;  // one leaf of value 0.0
-        if (max_leaves_ >= 2) {
-            std::vector<TreeNode*> lw_nodes;
-            std::vector<Dev::HistNode> lw_leaves;
-            std::vector<Dev::HistBounds> lw_bounds;
-            const bool rooted = grow_leaves(root.get(), s_l, s_w, &lw_nodes, &lw_leaves, &lw_bounds);
-            if (n_leaves) *n_leaves = (uint32_t)lw_nodes.size();
-            leaf_values(lw_nodes, lw_leaves, lw_bounds, s_l, s_w, rooted, leaf_seconds);
-            return root;
+        if (!all_zero) {  // (else one leaf of value 0.0)
+            Leaves lv;
+            const bool rooted = max_leaves_ >= 2 ? grow_leaves(root.get(), &lv) : grow_levels(root.get(), &lv, &rep.levels);
+            rep.leaves = (uint32_t)lv.nodes.size();
+            leaf_values(lv, rooted, &rep);
         }
-        struct Open {
-            TreeNode* node;
-            uint32_t slot, begin, end, depth;
-            Dev::HistBounds bd;  // (read only under monotone constraints)
-        };
-        std::vector<Open> open, next;
-        std::vector<TreeNode*> leaf_nodes;
-        std::vector<Dev::HistNode> leaves;
-        std::vector<Dev::HistBounds> leaf_bounds, node_bounds;
-        auto close = [&](TreeNode* t, uint32_t b, uint32_t e, const Dev::HistBounds& bd) {
-            leaf_nodes.push_back(t);
-            leaves.push_back({(uint32_t)leaves.size(), b, e});
-            leaf_bounds.push_back(bd);
-        };
-        if (enterable(n_, 1)) {
-            if (!dev_.hist_root(&err, newton_.on)) fail_str(err);
-            open.push_back({root.get(), 0u, 0u, n_, 1u, whole_line()});
-        } else {
-            close(root.get(), 0u, n_, whole_line());
+        if (report) *report = rep;
+        return root;
+    }
+
+    // leaf-wise growth: the largest histogram pool a tree of this grower asked for, in bytes (0: none yet)
+    uint64_t pool_bytes() const { return pool_bytes_; }
+
+  private:
+    // A node that may still split.  Leaf-wise growth also keeps its creation index and the record and gain it is open with.
+    struct Open {
+        TreeNode* node;
+        uint32_t slot, begin, end, depth;
+        Dev::HistBounds bd;  // (read only under monotone constraints)
+        uint32_t index = 0;
+        double gain = 0.0;
+        Dev::HistCand pick = {};
+    };
+    // the tree's leaves in the order they were closed: node, stretch of the index list (slot: its number), interval
+    struct Leaves {
+        std::vector<TreeNode*> nodes;
+        std::vector<Dev::HistNode> stretches;
+        std::vector<Dev::HistBounds> bounds;
+        void close(TreeNode* t, uint32_t b, uint32_t e, const Dev::HistBounds& bd) {
+            nodes.push_back(t);
+            stretches.push_back({(uint32_t)stretches.size(), b, e});
+            bounds.push_back(bd);
         }
+    };
+
+    // Level-wise growth.  false: the root was not searched, and the device's index list was not made.
+    bool grow_levels(TreeNode* root, Leaves* lv, uint32_t* levels) {
+        std::string err;
+        if (!enterable(n_, 1)) {
+            lv->close(root, 0u, n_, whole_line());
+            return false;
+        }
+        if (!dev_.hist_root(newton_.on, &err)) fail_str(err);
+        std::vector<Open> open{{root, 0u, 0u, n_, 1u, whole_line()}}, next;
         const size_t F = features();
         std::vector<Dev::HistNode> nodes, builds;
-        std::vector<Dev::HistBest> best;
-        std::vector<Dev::HistBestNewton> best_n;
+        std::vector<Dev::HistBounds> node_bounds;
+        std::vector<Dev::HistCand> best;
         std::vector<Dev::HistSymBest> level;
         std::vector<Dev::HistSplit> splits;
         std::vector<Dev::HistSub> subs;
-        const bool rooted = !open.empty();
         while (!open.empty()) {
-            nodes.clear(), builds.clear(), splits.clear(), subs.clear(), next.clear();
+            nodes.clear(), builds.clear(), splits.clear(), subs.clear(), next.clear(), node_bounds.clear();
             for (const Open& o : open) nodes.push_back({o.slot, o.begin, o.end});
             size_t sym_f = 0;  // (symmetric trees) the level's winning feature; best[a]: node a's record under the winner
             if (symmetric_) {
-                const Dev::HistSymSearch how{min_leaf_, newton_.on, s_l, s_w, newton_.lambda_l2, newton_.min_sum_hessian, newton_.min_split_gain};
-                if (!dev_.hist_search_symmetric(nodes, how, &level, &err)) fail_str(err);
+                if (!dev_.hist_search_symmetric(nodes, how_, &level, &err)) fail_str(err);
                 const Dev::HistSymBest* lw = nullptr;
                 for (size_t fi = 0; fi < F; fi++)  // the last maximum: a later feature wins among equals
                     if (level[fi].valid && (lw == nullptr || level[fi].key >= lw->key)) lw = &level[fi], sym_f = fi;
-                best_n.assign(open.size(), Dev::HistBestNewton{});
+                best.assign(open.size(), Dev::HistCand{});
                 if (lw != nullptr) {
-                    if (!dev_.hist_symmetric_apply(nodes, how, (uint32_t)sym_f, lw->edge, &best_n, &err)) fail_str(err);
+                    if (!dev_.hist_symmetric_apply(nodes, how_, (uint32_t)sym_f, lw->edge, &best, &err)) fail_str(err);
                     bool some = false;
-                    for (const Dev::HistBestNewton& b : best_n) some = some || b.valid;
+                    for (const Dev::HistCand& b : best) some = some || b.valid;
                     if (!some) fail_str("LambdaMART histogram grower: internal error: no node splits under the level's winner");
-                    levels_++;
+                    (*levels)++;
                 }
-                best.resize(best_n.size());
-                for (size_t i = 0; i < best_n.size(); i++) {
-                    const Dev::HistBestNewton& b = best_n[i];
-                    best[i] = {b.imp, b.ql, b.qtot, b.edge, b.nl, b.valid, 0u};
-                }
-            } else if (newton_.on) {  // the selection below reads the fields the two records share
-                if (mono_on_) {
-                    node_bounds.clear();
+            } else {
+                if (mono_on_)
                     for (const Open& o : open) node_bounds.push_back(o.bd);
-                    if (!dev_.hist_search_monotone(nodes, node_bounds, min_leaf_, s_l, s_w, newton_.lambda_l2, newton_.min_sum_hessian, &best_n, &err))
-                        fail_str(err);
-                } else if (!dev_.hist_search_newton(nodes, min_leaf_, s_l, s_w, newton_.lambda_l2, newton_.min_sum_hessian, &best_n, &err)) {
-                    fail_str(err);
-                }
-                best.resize(best_n.size());
-                for (size_t i = 0; i < best_n.size(); i++) {
-                    const Dev::HistBestNewton& b = best_n[i];
-                    best[i] = {b.imp, b.ql, b.qtot, b.edge, b.nl, b.valid, 0u};
-                }
-            } else if (!dev_.hist_search(nodes, min_leaf_, &best, &err)) {
-                fail_str(err);
+                if (!dev_.hist_search(nodes, how_, mono_on_ ? &node_bounds : nullptr, &best, &err)) fail_str(err);
             }
             uint32_t next_slots = 0;
             for (size_t a = 0; a < open.size(); a++) {
                 const Open& o = open[a];
-                const Dev::HistBest* w = nullptr;
+                const uint32_t n = o.end - o.begin;
+                const Dev::HistCand* w = nullptr;
                 size_t wf = 0;
                 if (symmetric_) {  // (the record's valid already holds the whole rule, the Newton gain's floor included)
                     if (best[a].valid) w = &best[a], wf = sym_f;
                 } else {
                     for (size_t fi = 0; fi < F; fi++) {  // the last maximum: a later feature wins among equals
-                        const Dev::HistBest& b = best[a * F + fi];
+                        const Dev::HistCand& b = best[a * F + fi];
                         if (b.valid && (w == nullptr || b.imp >= w->imp)) w = &b, wf = fi;
                     }
-                }
-                if (w != nullptr && newton_.on && !symmetric_) {  // the node's totals (Qnode, Wnode) arrive with every record of the node
-                    const Dev::HistBestNewton& b = best_n[a * F + wf];
-                    const double gain = mono_on_ ? w->imp - monotone_term(b.qtot, b.wtot, s_l, s_w, o.bd) : newton_gain(w->imp, b.qtot, b.wtot, s_l, s_w);
-                    if (!(gain > newton_.min_split_gain)) w = nullptr;
+                    double gain = 0.0;  // the node's totals (Qnode, Wnode) arrive with every record of the node
+                    if (w != nullptr && !may_split(*w, n, o.bd, &gain)) w = nullptr;
                 }
                 if (w == nullptr) {
-                    close(o.node, o.begin, o.end, o.bd);
+                    lv->close(o.node, o.begin, o.end, o.bd);
                     continue;
                 }
                 Dev::HistBounds bl = o.bd, br = o.bd;
-                if (mono_on_) {
-                    const Dev::HistBestNewton& b = best_n[a * F + wf];
-                    child_bounds(o.bd, mono_[full(wf)], b.ql, b.wl, b.qtot, b.wtot, s_l, s_w, &bl, &br);
-                }
-                const uint32_t n = o.end - o.begin, nl = w->nl, nr = n - nl;
+                if (mono_on_) child_bounds(o.bd, mono_[full(wf)], *w, &bl, &br);
+                const uint32_t nl = w->nl, nr = n - nl;
                 const size_t ws = split_node(o.node, wf, w->edge, n, nl);
                 splits.push_back({o.begin, o.end, (uint32_t)ws, w->edge, nl});  // (the bin matrix's row)
                 const uint32_t mid = o.begin + nl;
                 const bool el = enterable(nl, o.depth + 1), er = enterable(nr, o.depth + 1);
-                if (!el) close(o.node->lhs.get(), o.begin, mid, bl);
-                if (!er) close(o.node->rhs.get(), mid, o.end, br);
+                if (!el) lv->close(o.node->lhs.get(), o.begin, mid, bl);
+                if (!er) lv->close(o.node->rhs.get(), mid, o.end, br);
                 if (!el && !er) continue;
                 const bool left_small = nl <= nr;
                 const uint32_t small_slot = next_slots++;
@@ -253,90 +255,47 @@ class HistGrower {
                 if (el) next.push_back({o.node->lhs.get(), left_small ? small_slot : large_slot, o.begin, mid, o.depth + 1, bl});
                 if (er) next.push_back({o.node->rhs.get(), left_small ? large_slot : small_slot, mid, o.end, o.depth + 1, br});
             }
-            if (!dev_.hist_split(splits, builds, subs, next_slots, &err, newton_.on)) fail_str(err);
+            if (!dev_.hist_split(splits, builds, subs, next_slots, newton_.on, &err)) fail_str(err);
             open.swap(next);
         }
-        leaf_values(leaf_nodes, leaves, leaf_bounds, s_l, s_w, rooted, leaf_seconds);
-        if (n_leaves) *n_leaves = (uint32_t)leaf_nodes.size();
-        return root;
+        return true;
     }
 
-    // GOSS: the last tree's list length, top-set size, tau and the wall seconds of making the list
-    uint32_t goss_instances() const { return goss_n_; }
-    uint32_t goss_top() const { return goss_top_; }
-    uint64_t goss_tau() const { return goss_tau_; }
-    double goss_seconds() const { return goss_secs_; }
-
-    // monotone constraints: the leaves of the last tree whose value a bound moved
-    uint32_t clamped_leaves() const { return clamped_; }
-
-    // symmetric trees: the levels of the last tree that split (its depth in splits)
-    uint32_t levels() const { return levels_; }
-
-    // leaf-wise growth: the largest histogram pool a tree of this grower asked for, in bytes (0: none yet)
-    uint64_t pool_bytes() const { return pool_bytes_; }
-
-  private:
     // Leaf-wise growth.  Every node has a creation index (the root 0; a split gives its lhs the next one, then its rhs); a
     // leaf that is enterable is searched when it is made and is open when its record is accepted by the level loop's rule;
     // the open leaf with the largest gain is split (the smallest creation index among equals) while the tree has fewer than
-    // max_leaves leaves.  Fills leaf_nodes / leaves like the level loop does.  false: the root was not searched, and the
-    // device's index list was not made.
-    bool grow_leaves(TreeNode* root, int s_l, int s_w, std::vector<TreeNode*>* leaf_nodes, std::vector<frdev::DeviceDataset::HistNode>* leaves,
-                     std::vector<frdev::DeviceDataset::HistBounds>* leaf_bounds) {
-        using Dev = frdev::DeviceDataset;
+    // max_leaves leaves.  Fills *lv like the level loop does.  false: the root was not searched, and the device's index list
+    // was not made.
+    bool grow_leaves(TreeNode* root, Leaves* lv) {
         std::string err;
-        struct OpenLeaf {
-            TreeNode* node;
-            uint32_t slot, begin, end, depth, index;
-            double gain;
-            Dev::HistPick pick;
-            Dev::HistBounds bd;  // (read only under monotone constraints)
-        };
-        std::vector<OpenLeaf> open;
-        auto close = [&](TreeNode* t, uint32_t b, uint32_t e, const Dev::HistBounds& bd) {
-            leaf_nodes->push_back(t);
-            leaves->push_back({(uint32_t)leaves->size(), b, e});
-            leaf_bounds->push_back(bd);
-        };
+        std::vector<Open> open;
         if (!enterable(n_, 1)) {
-            close(root, 0u, n_, whole_line());
+            lv->close(root, 0u, n_, whole_line());
             return false;
         }
-        const Dev::HistLeafSearch how{min_leaf_, newton_.on, s_l, s_w, newton_.lambda_l2, newton_.min_sum_hessian, mono_on_};
         // live histograms never exceed the leaves, and the leaves neither max_leaves, the instances nor 2^(max_depth - 1)
         uint32_t slots = std::min(max_leaves_, n_);
         if (max_depth_ <= 31) slots = std::min(slots, 1u << (max_depth_ - 1));
         std::vector<uint32_t> free_slots;
         for (uint32_t s = slots; s-- > 1;) free_slots.push_back(s);  // (slot 0: the root's)
-        // the record of a searched leaf: open with its gain, or closed and its slot free again
-        auto consider = [&](TreeNode* t, uint32_t slot, uint32_t b, uint32_t e, uint32_t depth, uint32_t index, const Dev::HistPick& p,
-                            const Dev::HistBounds& bd) {
-            bool ok = p.valid != 0;
-            double gain = 0.0;
-            if (ok && newton_.on) {
-                gain = mono_on_ ? p.imp - monotone_term(p.qtot, p.wtot, s_l, s_w, bd) : newton_gain(p.imp, p.qtot, p.wtot, s_l, s_w);
-                ok = gain > newton_.min_split_gain;
-            } else if (ok) {  // (ranks only: rounding may leave it slightly below 0)
-                const double sn = (double)p.qtot;
-                gain = p.imp - (sn * sn) / (double)(e - b);
-            }
-            if (ok) {
-                open.push_back({t, slot, b, e, depth, index, gain, p, bd});
+        // a searched leaf with its record: open with its gain, or closed and its slot free again
+        auto consider = [&](Open o) {
+            if (may_split(o.pick, o.end - o.begin, o.bd, &o.gain)) {
+                open.push_back(o);
             } else {
-                close(t, b, e, bd);
-                free_slots.push_back(slot);
+                lv->close(o.node, o.begin, o.end, o.bd);
+                free_slots.push_back(o.slot);
             }
         };
-        Dev::HistPick pick[2];
-        if (!dev_.hist_leaf_begin(slots, how, &pick[0], &err)) fail_str(err);
-        consider(root, 0u, 0u, n_, 1u, 0u, pick[0], whole_line());
+        Dev::HistCand pick[2];
+        if (!dev_.hist_leaf_begin(slots, how_, &pick[0], &err)) fail_str(err);
+        consider({root, 0u, 0u, n_, 1u, whole_line(), 0u, 0.0, pick[0]});
         uint32_t n_leaves = 1, next_index = 1;
         while (n_leaves < max_leaves_ && !open.empty()) {
             size_t at = 0;
             for (size_t i = 1; i < open.size(); i++)
                 if (open[i].gain > open[at].gain || (open[i].gain == open[at].gain && open[i].index < open[at].index)) at = i;
-            const OpenLeaf o = open[at];
+            const Open o = open[at];
             open.erase(open.begin() + (std::ptrdiff_t)at);
             const uint32_t n = o.end - o.begin, nl = o.pick.nl, nr = n - nl;
             const size_t ws = split_node(o.node, o.pick.fi, o.pick.edge, n, nl);
@@ -347,24 +306,24 @@ class HistGrower {
             const bool left_small = nl <= nr;
             Dev::HistLeafStep step{{o.begin, o.end, (uint32_t)ws, o.pick.edge, nl}, o.slot, Dev::HIST_NO_SLOT, el, er};
             step.bounds[0] = step.bounds[1] = o.bd;
-            if (mono_on_) child_bounds(o.bd, mono_[ws], o.pick.ql, o.pick.wl, o.pick.qtot, o.pick.wtot, s_l, s_w, &step.bounds[0], &step.bounds[1]);
+            if (mono_on_) child_bounds(o.bd, mono_[ws], o.pick, &step.bounds[0], &step.bounds[1]);
             if (el || er) {
                 if (free_slots.empty()) fail_str("LambdaMART histogram grower: internal error: the histogram pool is exhausted");
                 step.small_slot = free_slots.back();
                 free_slots.pop_back();
             }
-            if (!dev_.hist_leaf_step(step, how, pick, &err)) fail_str(err);
+            if (!dev_.hist_leaf_step(step, how_, pick, &err)) fail_str(err);
             const uint32_t slot_l = left_small ? step.small_slot : o.slot, slot_r = left_small ? o.slot : step.small_slot;
-            if (el) consider(o.node->lhs.get(), slot_l, o.begin, mid, o.depth + 1, il, pick[0], step.bounds[0]);
-            else close(o.node->lhs.get(), o.begin, mid, step.bounds[0]);
-            if (er) consider(o.node->rhs.get(), slot_r, mid, o.end, o.depth + 1, ir, pick[1], step.bounds[1]);
-            else close(o.node->rhs.get(), mid, o.end, step.bounds[1]);
+            if (el) consider({o.node->lhs.get(), slot_l, o.begin, mid, o.depth + 1, step.bounds[0], il, 0.0, pick[0]});
+            else lv->close(o.node->lhs.get(), o.begin, mid, step.bounds[0]);
+            if (er) consider({o.node->rhs.get(), slot_r, mid, o.end, o.depth + 1, step.bounds[1], ir, 0.0, pick[1]});
+            else lv->close(o.node->rhs.get(), mid, o.end, step.bounds[1]);
             // a slot whose child was not searched holds nothing that is read again
             if (!el && (el || er)) free_slots.push_back(slot_l);
             if (!er && (el || er)) free_slots.push_back(slot_r);
             if (!el && !er) free_slots.push_back(o.slot);
         }
-        for (const OpenLeaf& o : open) close(o.node, o.begin, o.end, o.bd);
+        for (const Open& o : open) lv->close(o.node, o.begin, o.end, o.bd);
         pool_bytes_ = std::max(pool_bytes_, (uint64_t)slots * features() * k_ * (newton_.on ? 20u : 12u));
         return true;
     }
@@ -387,37 +346,48 @@ class HistGrower {
         return ws;
     }
 
-    // (G G) / (H + lambda_l2) of an integer pair, every operation rounded on its own
-    double newton_term(long long q, long long w, int s_l, int s_w) const {
-        const double g = std::ldexp((double)q, -s_l);
-        return (g * g) / (std::ldexp((double)w, -s_w) + newton_.lambda_l2);
+    // The selection rule's second half, one place for the level loop and the leaf-wise one: *gain = what record b gains over
+    // its own node (n instances, interval bd); returns whether the node may split on it.  Newton gain: imp less the node's
+    // own term (Qnode, Wnode; under monotone constraints the clamped one), which must exceed min_split_gain.  Variance:
+    // imp less Qnode^2 / n, for ranking the open leaves only (rounding may leave it slightly below 0): any valid record splits.
+    bool may_split(const Dev::HistCand& b, uint32_t n, const Dev::HistBounds& bd, double* gain) const {
+        if (!b.valid) return false;
+        if (newton_.on) {
+            *gain = b.imp - (mono_on_ ? monotone_term(b.qtot, b.wtot, bd) : newton_term(b.qtot, b.wtot));
+            return *gain > newton_.min_split_gain;
+        }
+        const double sn = (double)b.qtot;
+        *gain = b.imp - (sn * sn) / (double)n;
+        return true;
     }
-    // what a candidate of importance imp gains over its node's own term (Qnode, Wnode); the node splits only when this
-    // exceeds min_split_gain
-    double newton_gain(double imp, long long qtot, long long wtot, int s_l, int s_w) const { return imp - newton_term(qtot, wtot, s_l, s_w); }
 
-    // Monotone constraints.  The root's interval; an output G / (H + lambda_l2) (the leaf rule's 0.0 for a zero denominator)
-    // clamped to an interval; and term(G, H, v): the Newton term when nothing was clamped, else (2 G) v - ((H + lambda_l2) v) v,
-    // every operation rounded on its own, as the monotone scan kernels do.
-    static frdev::DeviceDataset::HistBounds whole_line() {
-        return {-std::numeric_limits<double>::infinity(), std::numeric_limits<double>::infinity()};
+    // (G G) / (H + lambda_l2) of an integer pair, every operation rounded on its own
+    double newton_term(long long q, long long w) const {
+        const double g = std::ldexp((double)q, -how_.s_l);
+        return (g * g) / (std::ldexp((double)w, -how_.s_w) + newton_.lambda_l2);
     }
-    double monotone_term(long long q, long long w, int s_l, int s_w, const frdev::DeviceDataset::HistBounds& bd, double* v_out = nullptr) const {
-        const double g = std::ldexp((double)q, -s_l), den = std::ldexp((double)w, -s_w) + newton_.lambda_l2;
-        const double out = den != 0.0 ? g / den : 0.0;
-        double v = out < bd.lo ? bd.lo : out;
-        v = v > bd.hi ? bd.hi : v;
+
+    // Monotone constraints.  The root's interval; a value clamped to an interval; and term(G, H, v) of an output
+    // G / (H + lambda_l2) (the leaf rule's 0.0 for a zero denominator) clamped to v: the Newton term when nothing was clamped,
+    // else (2 G) v - ((H + lambda_l2) v) v, every operation rounded on its own, as the monotone scan kernels do.
+    static Dev::HistBounds whole_line() { return {-std::numeric_limits<double>::infinity(), std::numeric_limits<double>::infinity()}; }
+    static double clamp(double out, const Dev::HistBounds& bd) {
+        const double v = out < bd.lo ? bd.lo : out;
+        return v > bd.hi ? bd.hi : v;
+    }
+    double monotone_term(long long q, long long w, const Dev::HistBounds& bd, double* v_out = nullptr) const {
+        const double g = std::ldexp((double)q, -how_.s_l), den = std::ldexp((double)w, -how_.s_w) + newton_.lambda_l2;
+        const double out = den != 0.0 ? g / den : 0.0, v = clamp(out, bd);
         if (v_out) *v_out = v;
         return v == out ? (g * g) / den : (2.0 * g) * v - (den * v) * v;
     }
-    // the children's intervals after a split on a feature of sign c: mid = (vL + vR) 0.5 cuts the node's interval
-    void child_bounds(const frdev::DeviceDataset::HistBounds& bd, int c, long long ql, long long wl, long long qtot, long long wtot, int s_l, int s_w,
-                      frdev::DeviceDataset::HistBounds* lhs, frdev::DeviceDataset::HistBounds* rhs) const {
+    // the children's intervals after the split b of a node on a feature of sign c: mid = (vL + vR) 0.5 cuts the node's interval
+    void child_bounds(const Dev::HistBounds& bd, int c, const Dev::HistCand& b, Dev::HistBounds* lhs, Dev::HistBounds* rhs) const {
         *lhs = *rhs = bd;
         if (c == 0) return;
         double vl = 0.0, vr = 0.0;
-        (void)monotone_term(ql, wl, s_l, s_w, bd, &vl);
-        (void)monotone_term(qtot - ql, wtot - wl, s_l, s_w, bd, &vr);
+        (void)monotone_term(b.ql, b.wl, bd, &vl);
+        (void)monotone_term(b.qtot - b.ql, b.wtot - b.wl, bd, &vr);
         const double mid = (vl + vr) * 0.5;
         if (c > 0) lhs->hi = mid, rhs->lo = mid;
         else lhs->lo = mid, rhs->hi = mid;
@@ -425,31 +395,26 @@ class HistGrower {
 
     // Leaf values from the leaves' integer sums.  rooted = false: the tree never searched, and the index list the sums are
     // taken over is made here, as the root's.
-    // Under monotone constraints a value is clamped to its leaf's interval (bounds[i]), and the moved ones are counted.
-    void leaf_values(const std::vector<TreeNode*>& leaf_nodes, const std::vector<frdev::DeviceDataset::HistNode>& leaves,
-                     const std::vector<frdev::DeviceDataset::HistBounds>& bounds, int s_l, int s_w, bool rooted, double* leaf_seconds) {
+    // Under monotone constraints a value is clamped to its leaf's interval, and the moved ones are counted.
+    void leaf_values(const Leaves& lv, bool rooted, HistTreeReport* rep) {
         std::string err;
         auto t0 = std::chrono::steady_clock::now();
-        if (!rooted && !dev_.hist_root(&err)) fail_str(err);
+        if (!rooted && !dev_.hist_root(false, &err)) fail_str(err);
         std::vector<long long> qw;
-        if (!dev_.hist_leaf_sums(leaves, &qw, &err)) fail_str(err);
-        for (size_t i = 0; i < leaf_nodes.size(); i++) {
+        if (!dev_.hist_leaf_sums(lv.stretches, &qw, &err)) fail_str(err);
+        for (size_t i = 0; i < lv.nodes.size(); i++) {
             const long long q = qw[i * 2], w = qw[i * 2 + 1];
             if (newton_.on) {
-                const double den = std::ldexp((double)w, -s_w) + newton_.lambda_l2;
-                leaf_nodes[i]->value = den != 0.0 ? std::ldexp((double)q, -s_l) / den : 0.0;
-                if (mono_on_) {
-                    const double out = leaf_nodes[i]->value;
-                    double v = out < bounds[i].lo ? bounds[i].lo : out;
-                    v = v > bounds[i].hi ? bounds[i].hi : v;
-                    if (v != out) clamped_++;
-                    leaf_nodes[i]->value = v;
-                }
+                const double den = std::ldexp((double)w, -how_.s_w) + newton_.lambda_l2;
+                const double out = den != 0.0 ? std::ldexp((double)q, -how_.s_l) / den : 0.0;
+                const double v = mono_on_ ? clamp(out, lv.bounds[i]) : out;
+                if (mono_on_ && v != out) rep->clamped_leaves++;
+                lv.nodes[i]->value = v;
             } else {
-                leaf_nodes[i]->value = w != 0 ? std::ldexp((double)q, -s_l) / std::ldexp((double)w, -s_w) : 0.0;
+                lv.nodes[i]->value = w != 0 ? std::ldexp((double)q, -how_.s_l) / std::ldexp((double)w, -how_.s_w) : 0.0;
             }
         }
-        if (leaf_seconds) *leaf_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        rep->leaf_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     }
 
     void check_features(const std::vector<uint32_t>* features) const {
@@ -460,21 +425,17 @@ class HistGrower {
     // rf_train.hpp's rule: may a node be searched at all?
     bool enterable(uint32_t n, uint32_t depth) const { return n >= 2 && depth < max_depth_ && n >= min_leaf_; }
 
-    frdev::DeviceDataset& dev_;
+    Dev& dev_;
     std::vector<uint32_t> feats_;
     uint32_t k_, max_depth_, min_leaf_, n_ = 0, n_full_ = 0;  // n_: the tree's instances (n_full_ of them without a query sample)
     uint32_t n_sample_ = 0;                                    // the sample's instances: n_ unless the tree is a GOSS one
-    uint32_t goss_n_ = 0, goss_top_ = 0;
-    uint64_t goss_tau_ = 0;
-    double goss_secs_ = 0.0;
     HistNewton newton_;
+    Dev::HistSearch how_{};                                    // the tree's search parameters, its exponents s_l / s_w among them
     uint32_t max_leaves_ = 0;                                  // 0: level-wise growth
     uint64_t pool_bytes_ = 0;
     bool mono_on_ = false;                                     // some monotone sign is not 0
     std::vector<int> mono_;                                    // (then) the signs, by entry of feats_
-    uint32_t clamped_ = 0;
     bool symmetric_ = false;                                   // every node of a level splits on one candidate
-    uint32_t levels_ = 0;
     std::vector<uint32_t> sel_;                                // the tree's features as slots of the bins (empty: all)
     std::vector<float> edges_;
     std::vector<uint32_t> nedges_;

@@ -391,66 +391,81 @@ static bool hist_level_alloc(DevBuf<uint32_t>& cnt, DevBuf<unsigned long long>& 
     return true;
 }
 
-bool DeviceDataset::hist_root(std::string* err, bool newton) {
+// The root of a tree: the index list (a copy of the tree's root list, or 0..n-1), the one root item, and the root's histogram
+// zeroed and built into cell 0 on of the given arrays
+bool DeviceDataset::Impl::hist_root_build(uint32_t* cnt, unsigned long long* sum, unsigned long long* wsum, std::string* err) {
+    auto& h = hist;
+    const uint32_t n = h.tree_n();  // the tree's instances: the index list's length (the bin matrix's rows hold h.n)
+    if (!hist_zero(cnt, sum, wsum, 0, (size_t)h.Ft * h.k, err)) return false;
+    if (h.tree_root() != nullptr) {
+        FR_HIP(hipMemcpyAsync(h.idx.p, h.tree_root(), n * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+    } else {
+        hist_iota_kernel<<<grid1d(n, 256), 256, 0, stream>>>(h.idx.p, n);
+    }
+    if (!hist_items({{0u, 0u, n}}, h.items_bh, h.items_b, err)) return false;
+    hist_build(cnt, sum, wsum);
+    FR_HIP(hipGetLastError());
+    return true;
+}
+
+bool DeviceDataset::hist_root(bool newton, std::string* err) {
     Impl& m = *impl_;
     std::lock_guard<std::mutex> lk(m.mu);
     if (!m.bind(err)) return false;
     auto& h = m.hist;
     if (h.k == 0) return hist_fail(err, "no bins built");
-    const uint32_t n = h.tree_n();  // the tree's instances: the index list's length (the bin matrix's rows hold h.n)
-    const size_t fk = (size_t)h.Ft * h.k;
     if (!h.idx.ensure(h.n, err) || !h.idx_o.ensure(h.n, err) || !h.flag.ensure(h.n, err) || !h.scan.ensure(h.n, err)) return false;
-    if (!hist_level_alloc(h.cnt, h.sum, h.wsum, fk, newton, err)) return false;
-    unsigned long long* const wsum = newton ? h.wsum.p : nullptr;
-    FR_HIP(hipMemsetAsync(h.flag.p, 0, n * sizeof(uint32_t), m.stream));
-    if (!m.hist_zero(h.cnt.p, h.sum.p, wsum, 0, fk, err)) return false;
-    if (h.tree_root() != nullptr) {
-        FR_HIP(hipMemcpyAsync(h.idx.p, h.tree_root(), n * sizeof(uint32_t), hipMemcpyDeviceToDevice, m.stream));
+    if (!hist_level_alloc(h.cnt, h.sum, h.wsum, (size_t)h.Ft * h.k, newton, err)) return false;
+    FR_HIP(hipMemsetAsync(h.flag.p, 0, h.tree_n() * sizeof(uint32_t), m.stream));
+    return m.hist_root_build(h.cnt.p, h.sum.p, newton ? h.wsum.p : nullptr, err);
+}
+
+bool DeviceDataset::hist_search(const std::vector<HistNode>& nodes, const HistSearch& how, const std::vector<HistBounds>* bounds,
+                                std::vector<HistCand>* best, std::string* err) {
+    static_assert(sizeof(HistBounds) == sizeof(HistBoundsDev), "host and device records differ");
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    const size_t A = nodes.size();
+    best->assign(A * h.Ft, HistCand{});
+    if (A == 0) return true;
+    if (how.monotone) {
+        if (!how.newton || bounds == nullptr || bounds->size() != A) return hist_fail(err, "internal error: one interval per node is needed");
+        if (h.mono_F == 0 || h.mono_F != h.F) return hist_fail(err, "internal error: no monotone signs set for these bins");
+    }
+    if (!m.hist_stage_nodes(nodes, how.newton, err)) return false;
+    const unsigned grid = (unsigned)(A * h.Ft);
+    const uint32_t* fsel = h.f_sampled ? h.fsel.p : nullptr;
+    if (!how.newton) {  // the variance criterion's shorter record, widened: wl = wtot = 0
+        if (!h.best.ensure(A * h.Ft, err)) return false;
+        {
+            ProfScope ps("hist_scan_kernel", m.stream);
+            hist_scan_kernel<<<grid, 64, 0, m.stream>>>(h.nodes.p, h.Ft, h.k, h.nedges.p, fsel, h.cnt.p, h.sum.p, how.min_leaf, h.best.p);
+        }
+        FR_HIP(hipGetLastError());
+        h.best_h.resize(A * h.Ft);
+        if (!hist_fetch(&h.best_h, h.best, m.stream, err)) return false;
+        for (size_t i = 0; i < h.best_h.size(); i++) {
+            const HistBestDev& b = h.best_h[i];
+            (*best)[i] = {b.imp, b.ql, b.qtot, 0ll, 0ll, b.edge, b.nl, b.valid, 0u};
+        }
+        return true;
+    }
+    if (!h.best_n.ensure(A * h.Ft, err)) return false;
+    if (how.monotone) {
+        if (!h.bounds.ensure(A, err)) return false;
+        FR_HIP(hipMemcpyAsync(h.bounds.p, bounds->data(), A * sizeof(HistBoundsDev), hipMemcpyHostToDevice, m.stream));
+        ProfScope ps("hist_scan_monotone_kernel", m.stream);
+        hist_scan_monotone_kernel<<<grid, 64, 0, m.stream>>>(h.nodes.p, h.bounds.p, h.Ft, h.k, h.nedges.p, h.mono.p, fsel, h.cnt.p, h.sum.p, h.wsum.p,
+                                                             how.min_leaf, how.s_l, how.s_w, how.lambda_l2, how.min_sum_hessian, h.best_n.p);
     } else {
-        hist_iota_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(h.idx.p, n);
-    }
-    if (!m.hist_items({{0u, 0u, n}}, h.items_bh, h.items_b, err)) return false;
-    m.hist_build(h.cnt.p, h.sum.p, wsum);
-    FR_HIP(hipGetLastError());
-    return true;
-}
-
-bool DeviceDataset::hist_search(const std::vector<HistNode>& nodes, uint32_t min_leaf, std::vector<HistBest>* best, std::string* err) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    auto& h = m.hist;
-    const size_t A = nodes.size();
-    best->assign(A * h.Ft, HistBest{});
-    if (A == 0) return true;
-    if (!m.hist_stage_nodes(nodes, false, err) || !h.best.ensure(A * h.Ft, err)) return false;
-    {
-        ProfScope ps("hist_scan_kernel", m.stream);
-        hist_scan_kernel<<<(unsigned)(A * h.Ft), 64, 0, m.stream>>>(h.nodes.p, h.Ft, h.k, h.nedges.p, h.f_sampled ? h.fsel.p : nullptr, h.cnt.p,
-                                                                    h.sum.p, min_leaf, h.best.p);
-    }
-    FR_HIP(hipGetLastError());
-    return hist_fetch(best, h.best, m.stream, err);
-}
-
-bool DeviceDataset::hist_search_newton(const std::vector<HistNode>& nodes, uint32_t min_leaf, int s_l, int s_w, double lambda_l2,
-                                       double min_sum_hessian, std::vector<HistBestNewton>* best, std::string* err) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    auto& h = m.hist;
-    const size_t A = nodes.size();
-    best->assign(A * h.Ft, HistBestNewton{});
-    if (A == 0) return true;
-    if (!m.hist_stage_nodes(nodes, true, err) || !h.best_n.ensure(A * h.Ft, err)) return false;
-    {
         ProfScope ps("hist_scan_newton_kernel", m.stream);
-        hist_scan_newton_kernel<<<(unsigned)(A * h.Ft), 64, 0, m.stream>>>(h.nodes.p, h.Ft, h.k, h.nedges.p, h.f_sampled ? h.fsel.p : nullptr,
-                                                                           h.cnt.p, h.sum.p, h.wsum.p, min_leaf, s_l, s_w, lambda_l2,
-                                                                           min_sum_hessian, h.best_n.p);
+        hist_scan_newton_kernel<<<grid, 64, 0, m.stream>>>(h.nodes.p, h.Ft, h.k, h.nedges.p, fsel, h.cnt.p, h.sum.p, h.wsum.p, how.min_leaf, how.s_l,
+                                                           how.s_w, how.lambda_l2, how.min_sum_hessian, h.best_n.p);
     }
     FR_HIP(hipGetLastError());
-    return hist_fetch(best, h.best_n, m.stream, err);
+    return hist_fetch(best, h.best_n, m.stream, err);  // (*bounds is the caller's, read by the copy above until this has waited)
 }
 
 bool DeviceDataset::hist_monotone(const int* signs, size_t features, std::string* err) {
@@ -470,32 +485,7 @@ bool DeviceDataset::hist_monotone(const int* signs, size_t features, std::string
     return true;
 }
 
-bool DeviceDataset::hist_search_monotone(const std::vector<HistNode>& nodes, const std::vector<HistBounds>& bounds, uint32_t min_leaf, int s_l,
-                                         int s_w, double lambda_l2, double min_sum_hessian, std::vector<HistBestNewton>* best,
-                                         std::string* err) {
-    static_assert(sizeof(HistBounds) == sizeof(HistBoundsDev), "host and device records differ");
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    auto& h = m.hist;
-    const size_t A = nodes.size();
-    best->assign(A * h.Ft, HistBestNewton{});
-    if (A == 0) return true;
-    if (bounds.size() != A) return hist_fail(err, "internal error: one interval per node is needed");
-    if (h.mono_F == 0 || h.mono_F != h.F) return hist_fail(err, "internal error: no monotone signs set for these bins");
-    if (!m.hist_stage_nodes(nodes, true, err) || !h.bounds.ensure(A, err) || !h.best_n.ensure(A * h.Ft, err)) return false;
-    FR_HIP(hipMemcpyAsync(h.bounds.p, bounds.data(), A * sizeof(HistBoundsDev), hipMemcpyHostToDevice, m.stream));
-    {
-        ProfScope ps("hist_scan_monotone_kernel", m.stream);
-        hist_scan_monotone_kernel<<<(unsigned)(A * h.Ft), 64, 0, m.stream>>>(h.nodes.p, h.bounds.p, h.Ft, h.k, h.nedges.p, h.mono.p,
-                                                                             h.f_sampled ? h.fsel.p : nullptr, h.cnt.p, h.sum.p, h.wsum.p, min_leaf,
-                                                                             s_l, s_w, lambda_l2, min_sum_hessian, h.best_n.p);
-    }
-    FR_HIP(hipGetLastError());
-    return hist_fetch(best, h.best_n, m.stream, err);  // (bounds is the caller's, read by the copy above until this has waited)
-}
-
-bool DeviceDataset::hist_search_symmetric(const std::vector<HistNode>& nodes, const HistSymSearch& how, std::vector<HistSymBest>* best,
+bool DeviceDataset::hist_search_symmetric(const std::vector<HistNode>& nodes, const HistSearch& how, std::vector<HistSymBest>* best,
                                           std::string* err) {
     Impl& m = *impl_;
     std::lock_guard<std::mutex> lk(m.mu);
@@ -521,14 +511,14 @@ bool DeviceDataset::hist_search_symmetric(const std::vector<HistNode>& nodes, co
     return hist_fetch(best, h.best_sym, m.stream, err);
 }
 
-bool DeviceDataset::hist_symmetric_apply(const std::vector<HistNode>& nodes, const HistSymSearch& how, uint32_t fi, uint32_t edge,
-                                         std::vector<HistBestNewton>* out, std::string* err) {
+bool DeviceDataset::hist_symmetric_apply(const std::vector<HistNode>& nodes, const HistSearch& how, uint32_t fi, uint32_t edge,
+                                         std::vector<HistCand>* out, std::string* err) {
     Impl& m = *impl_;
     std::lock_guard<std::mutex> lk(m.mu);
     if (!m.bind(err)) return false;
     auto& h = m.hist;
     const size_t A = nodes.size();
-    out->assign(A, HistBestNewton{});
+    out->assign(A, HistCand{});
     if (A == 0) return true;
     if (h.k < 2 || h.k > HIST_MAX_BINS || fi >= h.Ft || edge + 1 >= h.k) return hist_fail(err, "internal error: a level's split outside the histograms");
     // (the level's search has staged these very nodes, and has waited for the stream: they are uploaded again only if they differ)
@@ -550,7 +540,7 @@ bool DeviceDataset::hist_symmetric_apply(const std::vector<HistNode>& nodes, con
 }
 
 bool DeviceDataset::hist_split(const std::vector<HistSplit>& splits, const std::vector<HistNode>& builds, const std::vector<HistSub>& subs,
-                               uint32_t next_slots, std::string* err, bool newton) {
+                               uint32_t next_slots, bool newton, std::string* err) {
     static_assert(sizeof(HistSplit) == sizeof(HistSplitDev) && sizeof(HistSub) == sizeof(HistSubDev), "host and device records differ");
     Impl& m = *impl_;
     std::lock_guard<std::mutex> lk(m.mu);
@@ -656,9 +646,9 @@ void DeviceDataset::hist_end() {
 // --- leaf-wise growth (kernels_hist.inc, "Leaf-wise growth") ---
 
 // scan (after deriving where asked) and pick of `count` children, their records to out[0..count); waits for the stream
-bool DeviceDataset::Impl::hist_leaf_scan(const HistLeafKids& kids, uint32_t count, const DeviceDataset::HistLeafSearch& how,
-                                         DeviceDataset::HistPick* out, std::string* err, const HistLeafBoundsDev* bounds) {
-    static_assert(sizeof(DeviceDataset::HistPick) == sizeof(HistPickDev), "host and device records differ");
+bool DeviceDataset::Impl::hist_leaf_scan(const HistLeafKids& kids, uint32_t count, const DeviceDataset::HistSearch& how,
+                                         DeviceDataset::HistCand* out, std::string* err, const HistLeafBoundsDev* bounds) {
+    static_assert(sizeof(DeviceDataset::HistCand) == sizeof(HistPickDev), "host and device records differ");
     auto& h = hist;
     if (!h.rec.ensure((size_t)2 * h.Ft, err) || !h.pick.ensure(2, err)) return false;
     const uint32_t* fsel = h.f_sampled ? h.fsel.p : nullptr;
@@ -689,15 +679,14 @@ bool DeviceDataset::Impl::hist_leaf_scan(const HistLeafKids& kids, uint32_t coun
     return true;
 }
 
-bool DeviceDataset::hist_leaf_begin(uint32_t slots, const HistLeafSearch& how, HistPick* root, std::string* err) {
+bool DeviceDataset::hist_leaf_begin(uint32_t slots, const HistSearch& how, HistCand* root, std::string* err) {
     Impl& m = *impl_;
     std::lock_guard<std::mutex> lk(m.mu);
     if (!m.bind(err)) return false;
     auto& h = m.hist;
     if (h.k == 0) return hist_fail(err, "no bins built");
     if (slots == 0) return hist_fail(err, "internal error: an empty histogram pool");
-    const uint32_t n = h.tree_n();
-    const size_t fk = (size_t)h.Ft * h.k, cells = (size_t)slots * fk;
+    const size_t cells = (size_t)slots * h.Ft * h.k;
     if (!h.idx.ensure(h.n, err) || !h.idx_o.ensure(h.n, err) || !h.flag.ensure(h.n, err) || !h.scan.ensure(h.n, err)) return false;
     {
         std::string e2;
@@ -709,25 +698,16 @@ bool DeviceDataset::hist_leaf_begin(uint32_t slots, const HistLeafSearch& how, H
         }
     }
     h.pool_slots = slots;
-    unsigned long long* const pwsum = how.newton ? h.pwsum.p : nullptr;
-    if (!m.hist_zero(h.pcnt.p, h.psum.p, pwsum, 0, fk, err)) return false;
-    if (h.tree_root() != nullptr) {
-        FR_HIP(hipMemcpyAsync(h.idx.p, h.tree_root(), n * sizeof(uint32_t), hipMemcpyDeviceToDevice, m.stream));
-    } else {
-        hist_iota_kernel<<<grid1d(n, 256), 256, 0, m.stream>>>(h.idx.p, n);
-    }
-    if (!m.hist_items({{0u, 0u, n}}, h.items_bh, h.items_b, err)) return false;
-    m.hist_build(h.pcnt.p, h.psum.p, pwsum);
-    FR_HIP(hipGetLastError());
+    if (!m.hist_root_build(h.pcnt.p, h.psum.p, how.newton ? h.pwsum.p : nullptr, err)) return false;
     HistLeafKids kids{};
-    kids.slot[0] = 0, kids.n[0] = n;
+    kids.slot[0] = 0, kids.n[0] = h.tree_n();
     HistLeafBoundsDev whole{};  // (the root's interval: the whole line)
     whole.lo[0] = whole.lo[1] = -std::numeric_limits<double>::infinity();
     whole.hi[0] = whole.hi[1] = std::numeric_limits<double>::infinity();
     return m.hist_leaf_scan(kids, 1, how, root, err, &whole);
 }
 
-bool DeviceDataset::hist_leaf_step(const HistLeafStep& step, const HistLeafSearch& how, HistPick pick[2], std::string* err) {
+bool DeviceDataset::hist_leaf_step(const HistLeafStep& step, const HistSearch& how, HistCand pick[2], std::string* err) {
     Impl& m = *impl_;
     std::lock_guard<std::mutex> lk(m.mu);
     if (!m.bind(err)) return false;
@@ -776,7 +756,7 @@ bool DeviceDataset::hist_leaf_step(const HistLeafStep& step, const HistLeafSearc
         where[side] = (int)count++;
     }
     if (count == 0) return true;
-    HistPick got[2];
+    HistCand got[2];
     if (!m.hist_leaf_scan(kids, count, how, got, err, &bounds)) return false;
     for (int side = 0; side < 2; side++)
         if (where[side] >= 0) pick[side] = got[where[side]];

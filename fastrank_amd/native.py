@@ -7,7 +7,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .clib import ALLREDUCE_SUM_FN, CDataset, CModel, CQRel, _json_reply, _load, _status, _take_str, _unwrap
+from .clib import ALLREDUCE_SUM_FN, CDataset, CModel, CQRel, HistTreeOptions, _json_reply, _load, _status, _take_str, _unwrap
 
 
 def device_count() -> int:
@@ -230,110 +230,48 @@ def hist_tree(dataset: CDataset, lam: np.ndarray, wt: np.ndarray, split_candidat
     of the sample's instances under the key of tree `tree` of `seed`, the kept others' gradients amplified (DESIGN.md section
     11, "GOSS"); level-wise or leaf-wise, with or without monotone signs.  `symmetric` = True (level-wise, without monotone
     signs or GOSS): every node of a level splits on the level's one winning candidate ("Symmetric
-    trees"), under either gain.  At the defaults the call is the one it was."""
+    trees"), under either gain.  Arguments that contradict each other raise ValueError before the one native call."""
     lam = np.ascontiguousarray(lam, dtype=np.float64)
     wt = np.ascontiguousarray(wt, dtype=np.float64)
+    newton = split_gain == "newton"
+    mono = {} if monotone is None else {int(f): int(c) for f, c in monotone.items()}
+    if not any(c != 0 for c in mono.values()):
+        mono = {}
     if lam.shape != wt.shape or lam.ndim != 1:
         raise ValueError("lam and wt must be 1-d arrays of the same length")
     if split_gain not in ("variance", "newton"):
         raise ValueError("split_gain must be 'variance' or 'newton', not {!r}".format(split_gain))
+    if symmetric and (goss is not None or int(max_leaves) != 0 or mono):
+        raise ValueError("symmetric trees are grown level-wise, without monotone constraints or goss")
+    if goss is not None and not newton:
+        raise ValueError("goss needs split_gain='newton'")
+    if mono and not newton:
+        raise ValueError("monotone constraints need split_gain='newton'")
+    if int(max_leaves) != 0 and int(max_leaves) < 2:
+        raise ValueError("max_leaves must be 0 (level-wise) or at least 2")
+    if not newton and (lambda_l2 != 0.0 or min_sum_hessian != 0.0 or min_split_gain != 0.0):
+        raise ValueError("lambda_l2, min_sum_hessian and min_split_gain need split_gain='newton'")
     qs = None if queries is None else np.ascontiguousarray(queries, dtype=np.uint32)
     fs = None if features is None else np.ascontiguousarray(features, dtype=np.uint32)
-    sample = (None if qs is None else qs.ctypes.data, 0 if qs is None else len(qs),
-              None if fs is None else fs.ctypes.data, 0 if fs is None else len(fs))
-    if symmetric:
-        if goss is not None or int(max_leaves) != 0 or (monotone is not None and any(int(c) != 0 for c in monotone.values())):
-            raise ValueError("symmetric trees are grown level-wise, without monotone constraints or goss")
-        if split_gain != "newton" and (lambda_l2 != 0.0 or min_sum_hessian != 0.0 or min_split_gain != 0.0):
-            raise ValueError("lambda_l2, min_sum_hessian and min_split_gain need split_gain='newton'")
-        return CModel(
-            _unwrap(
-                _load().fr_debug_hist_tree_symmetric(
-                    dataset.pointer, int(split_candidates), int(max_depth), int(min_leaf_support), lam.ctypes.data,
-                    wt.ctypes.data, lam.shape[0], *sample, 1 if split_gain == "newton" else 0, float(lambda_l2),
-                    float(min_sum_hessian), float(min_split_gain),
-                )
-            )
-        )
-    if goss is not None:
-        if split_gain != "newton":
-            raise ValueError("goss needs split_gain='newton'")
-        top_rate, other_rate, seed, tree = goss
-        mono = {} if monotone is None else {int(f): int(c) for f, c in monotone.items() if int(c) != 0}
-        mf = np.ascontiguousarray(list(mono.keys()), dtype=np.uint32)
-        ms = np.ascontiguousarray(list(mono.values()), dtype=np.int32)
-        return CModel(
-            _unwrap(
-                _load().fr_debug_hist_tree_goss(
-                    dataset.pointer, int(split_candidates), int(max_depth), int(min_leaf_support), lam.ctypes.data,
-                    wt.ctypes.data, lam.shape[0], *sample, float(lambda_l2), float(min_sum_hessian), float(min_split_gain),
-                    int(max_leaves), mf.ctypes.data if len(mf) else None, ms.ctypes.data if len(ms) else None, len(mf),
-                    float(top_rate), float(other_rate), int(seed), int(tree),
-                )
-            )
-        )
-    if monotone is not None and any(int(c) != 0 for c in monotone.values()):
-        if split_gain != "newton":
-            raise ValueError("monotone constraints need split_gain='newton'")
-        if int(max_leaves) == 1:
-            raise ValueError("max_leaves must be 0 (level-wise) or at least 2")
-        mf = np.ascontiguousarray([int(f) for f in monotone.keys()], dtype=np.uint32)
-        ms = np.ascontiguousarray([int(c) for c in monotone.values()], dtype=np.int32)
-        clamped = np.zeros(1, dtype=np.uint32)
-        model = CModel(
-            _unwrap(
-                _load().fr_debug_hist_tree_monotone(
-                    dataset.pointer, int(split_candidates), int(max_depth), int(min_leaf_support), lam.ctypes.data,
-                    wt.ctypes.data, lam.shape[0], *sample, float(lambda_l2), float(min_sum_hessian), float(min_split_gain),
-                    int(max_leaves), mf.ctypes.data, ms.ctypes.data, len(mf), clamped.ctypes.data,
-                )
-            )
-        )
-        if clamped_out is not None:
-            clamped_out.append(int(clamped[0]))
-        return model
-    if int(max_leaves) != 0:
-        if int(max_leaves) < 2:
-            raise ValueError("max_leaves must be 0 (level-wise) or at least 2")
-        if split_gain != "newton" and (lambda_l2 != 0.0 or min_sum_hessian != 0.0 or min_split_gain != 0.0):
-            raise ValueError("lambda_l2, min_sum_hessian and min_split_gain need split_gain='newton'")
-        return CModel(
-            _unwrap(
-                _load().fr_debug_hist_tree_leafwise(
-                    dataset.pointer, int(split_candidates), int(max_depth), int(min_leaf_support), lam.ctypes.data,
-                    wt.ctypes.data, lam.shape[0], *sample, 1 if split_gain == "newton" else 0, float(lambda_l2),
-                    float(min_sum_hessian), float(min_split_gain), int(max_leaves),
-                )
-            )
-        )
-    if split_gain == "newton":
-        return CModel(
-            _unwrap(
-                _load().fr_debug_hist_tree_newton(
-                    dataset.pointer, int(split_candidates), int(max_depth), int(min_leaf_support), lam.ctypes.data,
-                    wt.ctypes.data, lam.shape[0], *sample, float(lambda_l2), float(min_sum_hessian), float(min_split_gain),
-                )
-            )
-        )
-    if lambda_l2 != 0.0 or min_sum_hessian != 0.0 or min_split_gain != 0.0:
-        raise ValueError("lambda_l2, min_sum_hessian and min_split_gain need split_gain='newton'")
-    if queries is not None or features is not None:
-        return CModel(
-            _unwrap(
-                _load().fr_debug_hist_tree_sampled(
-                    dataset.pointer, int(split_candidates), int(max_depth), int(min_leaf_support), lam.ctypes.data,
-                    wt.ctypes.data, lam.shape[0], *sample,
-                )
-            )
-        )
-    return CModel(
-        _unwrap(
-            _load().fr_debug_hist_tree(
-                dataset.pointer, int(split_candidates), int(max_depth), int(min_leaf_support), lam.ctypes.data,
-                wt.ctypes.data, lam.shape[0],
-            )
-        )
+    mf = np.ascontiguousarray(list(mono.keys()), dtype=np.uint32)
+    ms = np.ascontiguousarray(list(mono.values()), dtype=np.int32)
+    top_rate, other_rate, seed, tree = (0.0, 0.0, 0, 0) if goss is None else goss
+    opt = HistTreeOptions(
+        split_candidates=int(split_candidates), max_depth=int(max_depth), min_leaf_support=int(min_leaf_support),
+        newton=1 if newton else 0, lambda_l2=float(lambda_l2), min_sum_hessian=float(min_sum_hessian),
+        min_split_gain=float(min_split_gain), max_leaves=int(max_leaves), symmetric=1 if symmetric else 0,
+        queries=None if qs is None else qs.ctypes.data, n_queries=0 if qs is None else len(qs),
+        features=None if fs is None else fs.ctypes.data, n_features=0 if fs is None else len(fs),
+        mono_features=mf.ctypes.data if mono else None, mono_signs=ms.ctypes.data if mono else None, n_mono=len(mono),
+        goss=0 if goss is None else 1, top_rate=float(top_rate), other_rate=float(other_rate), seed=int(seed), tree=int(tree),
     )
+    clamped = C.c_uint32(0)
+    model = CModel(
+        _unwrap(_load().fr_debug_hist_tree(dataset.pointer, C.byref(opt), lam.ctypes.data, wt.ctypes.data, lam.shape[0], C.byref(clamped)))
+    )
+    if mono and clamped_out is not None:
+        clamped_out.append(int(clamped.value))
+    return model
 
 
 def goss_select(dataset: CDataset, lam: np.ndarray, top_rate: float, other_rate: float, seed: int, tree: int,

@@ -215,71 +215,57 @@ const void *fr_debug_lambda_gradients(const CModel *model, const CDataset *datas
 const void *fr_debug_hist_bins(const CDataset *dataset, uint32_t split_candidates, size_t n, size_t f,
                                uint32_t *ids_out, uint32_t *feats_out, float *edges_out,
                                uint32_t *nedges_out, uint8_t *bins_out);
-/* One histogram tree (a DecisionTree model) grown from lambda / weight indexed by instance id (len entries). */
-const CResult *fr_debug_hist_tree(const CDataset *dataset, uint32_t split_candidates, uint32_t max_depth,
-                                  uint32_t min_leaf_support, const double *lambda, const double *weight,
-                                  size_t len);
 /* LambdaMART per-tree samples, test hooks ("Sampling").  fr_debug_lambdamart_sample: JSON
  * {"features": [feature ids ascending], "queries": [indices of the view's queries, ascending]} the trainer uses for
- * tree `tree` of the LambdaMART parameters params_json on this view; no device is touched.  The _sampled forms of
- * the two hooks above take queries[n_queries] = indices of the view's queries (fr_debug_hist_tree_sampled: NULL = all)
- * and features[n_features] = feature ids of the view (NULL = all); only instances of the named queries are written
- * (gradients) or read (tree). */
+ * tree `tree` of the LambdaMART parameters params_json on this view; no device is touched.
+ * fr_debug_lambda_gradients_sampled takes queries[n_queries] = indices of the view's queries; only instances of the
+ * named queries are written. */
 const void *fr_debug_lambdamart_sample(const CDataset *dataset, const void *params_json, uint32_t tree);
 const void *fr_debug_lambda_gradients_sampled(const CModel *model, const CDataset *dataset, const CQRel *qrel,
                                               const void *measure, double sigma, const uint32_t *queries,
                                               size_t n_queries, double *lambda_out, double *weight_out,
                                               size_t out_len);
-const CResult *fr_debug_hist_tree_sampled(const CDataset *dataset, uint32_t split_candidates, uint32_t max_depth,
-                                          uint32_t min_leaf_support, const double *lambda, const double *weight,
-                                          size_t len, const uint32_t *queries, size_t n_queries,
-                                          const uint32_t *features, size_t n_features);
-/* fr_debug_hist_tree_sampled under the Newton split gain ("Newton split gain"): splits by
- * G^2 / (H + lambda_l2) with the floors min_sum_hessian and min_split_gain, leaves G / (H + lambda_l2); the three
- * numbers finite and >= 0. */
-const CResult *fr_debug_hist_tree_newton(const CDataset *dataset, uint32_t split_candidates, uint32_t max_depth,
-                                         uint32_t min_leaf_support, const double *lambda, const double *weight,
-                                         size_t len, const uint32_t *queries, size_t n_queries,
-                                         const uint32_t *features, size_t n_features, double lambda_l2,
-                                         double min_sum_hessian, double min_split_gain);
-/* One tree grown leaf-wise under a leaf budget max_leaves >= 2 ("Leaf-wise growth"): the open leaf
- * with the largest gain is split next.  newton != 0: the Newton split gain with the three numbers (0 without it). */
-const CResult *fr_debug_hist_tree_leafwise(const CDataset *dataset, uint32_t split_candidates, uint32_t max_depth,
-                                           uint32_t min_leaf_support, const double *lambda, const double *weight,
-                                           size_t len, const uint32_t *queries, size_t n_queries,
-                                           const uint32_t *features, size_t n_features, int newton, double lambda_l2,
-                                           double min_sum_hessian, double min_split_gain, uint32_t max_leaves);
-/* One symmetric tree ("Symmetric trees"): every node of a level splits on the level's one winning
- * candidate.  newton != 0: the Newton split gain with the three numbers (0 without it). */
-const CResult *fr_debug_hist_tree_symmetric(const CDataset *dataset, uint32_t split_candidates, uint32_t max_depth,
-                                            uint32_t min_leaf_support, const double *lambda, const double *weight,
-                                            size_t len, const uint32_t *queries, size_t n_queries,
-                                            const uint32_t *features, size_t n_features, int newton, double lambda_l2,
-                                            double min_sum_hessian, double min_split_gain);
-/* One tree under monotone constraints ("Monotone constraints"; Newton gain only): the numbers of
- * fr_debug_hist_tree_newton, max_leaves = 0 (level-wise) or >= 2 (leaf-wise), and mono_features / mono_signs[n_mono] =
- * feature ids of the view and their signs in {-1, 0, 1}.  *clamped_leaves_out (may be NULL): the leaves whose value a
- * bound moved. */
-const CResult *fr_debug_hist_tree_monotone(const CDataset *dataset, uint32_t split_candidates, uint32_t max_depth,
-                                           uint32_t min_leaf_support, const double *lambda, const double *weight,
-                                           size_t len, const uint32_t *queries, size_t n_queries,
-                                           const uint32_t *features, size_t n_features, double lambda_l2,
-                                           double min_sum_hessian, double min_split_gain, uint32_t max_leaves,
-                                           const uint32_t *mono_features, const int32_t *mono_signs, size_t n_mono,
-                                           uint32_t *clamped_leaves_out);
-/* LambdaMART's gradient-based one-side sampling, test hooks ("GOSS").  top_rate in (0, 1),
- * other_rate in (0, 1], their sum at most 1; the tree's key is that of tree `tree` of the request seed `seed`.
- * fr_debug_hist_tree_goss: fr_debug_hist_tree_monotone (n_mono = 0: no constraint) fitted to the GOSS list of the sample's
- * instance list, the kept others' lambda / weight amplified.
- * fr_debug_goss_select: the selection alone for lambda[len] by instance id.  list_out / top_out[cap] (cap >= the view's
- * instances): the GOSS list as ascending indices into the view's instance list, and per entry whether it belongs to the
- * top set; *n_g_out: the list's length; *tau_out: the n_top-th largest of the 64-bit patterns of |lambda|. */
-const CResult *fr_debug_hist_tree_goss(const CDataset *dataset, uint32_t split_candidates, uint32_t max_depth,
-                                       uint32_t min_leaf_support, const double *lambda, const double *weight, size_t len,
-                                       const uint32_t *queries, size_t n_queries, const uint32_t *features,
-                                       size_t n_features, double lambda_l2, double min_sum_hessian, double min_split_gain,
-                                       uint32_t max_leaves, const uint32_t *mono_features, const int32_t *mono_signs,
-                                       size_t n_mono, double top_rate, double other_rate, uint64_t seed, uint32_t tree);
+/* What fr_debug_hist_tree grows its one tree with; a zeroed struct with the first three fields set is a plain level-wise
+ * tree under the variance criterion. */
+typedef struct FrHistTreeOptions {
+    uint32_t split_candidates, max_depth, min_leaf_support; /* max_depth >= 1 */
+    /* newton != 0: the Newton split gain ("Newton split gain"): splits by G^2 / (H + lambda_l2) with the floors
+     * min_sum_hessian and min_split_gain, leaves G / (H + lambda_l2).  The three numbers finite and >= 0, and 0 without it. */
+    int32_t newton;
+    double lambda_l2, min_sum_hessian, min_split_gain;
+    /* 0: level-wise; >= 2: leaf-wise under that leaf budget ("Leaf-wise growth"): the open leaf with the largest gain is
+     * split next */
+    uint32_t max_leaves;
+    /* != 0 ("Symmetric trees"; level-wise, without monotone signs or GOSS): every node of a level splits on the level's
+     * one winning candidate */
+    int32_t symmetric;
+    /* the tree's sample ("Sampling"): indices of the view's queries / feature ids of the view (NULL = all); gradients of
+     * instances outside the query sample are not read */
+    const uint32_t *queries;
+    size_t n_queries;
+    const uint32_t *features;
+    size_t n_features;
+    /* "Monotone constraints" (Newton gain only): feature ids of the view and their signs in {-1, 0, 1} */
+    const uint32_t *mono_features;
+    const int32_t *mono_signs;
+    size_t n_mono;
+    /* goss != 0 ("GOSS"; Newton gain only): the tree is fitted to the GOSS list of the sample's instance list, the kept
+     * others' lambda / weight amplified.  top_rate in (0, 1), other_rate in (0, 1], their sum at most 1; the tree's key is
+     * that of tree `tree` of the request seed `seed`. */
+    int32_t goss;
+    double top_rate, other_rate;
+    uint64_t seed;
+    uint32_t tree;
+} FrHistTreeOptions;
+/* One histogram tree (a DecisionTree model) grown from lambda / weight indexed by instance id (len
+ * entries).  Options that contradict each other or are out of range are refused before the dataset is looked at.
+ * *clamped_leaves_out (may be NULL): the leaves whose value a monotone bound moved. */
+const CResult *fr_debug_hist_tree(const CDataset *dataset, const FrHistTreeOptions *opt, const double *lambda,
+                                  const double *weight, size_t len, uint32_t *clamped_leaves_out);
+/* The GOSS selection alone (rates, seed and tree as in FrHistTreeOptions) for lambda[len] by instance id, over the
+ * instances of queries[n_queries] (NULL = all).  list_out / top_out[cap] (cap >= the view's instances): the GOSS list as
+ * ascending indices into the view's instance list, and per entry whether it belongs to the top set; *n_g_out: the list's
+ * length; *tau_out: the n_top-th largest of the 64-bit patterns of |lambda|. */
 const void *fr_debug_goss_select(const CDataset *dataset, const double *lambda, size_t len, double top_rate,
                                  double other_rate, uint64_t seed, uint32_t tree, const uint32_t *queries, size_t n_queries,
                                  uint32_t *list_out, uint8_t *top_out, size_t cap, uint32_t *n_g_out, uint64_t *tau_out);

@@ -32,6 +32,9 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), "missing export: " + name
     for name in clib.exported_symbols():  # the 20 reference symbols (src/lib.rs:78-326)
         assert name in syms
+    # one histogram-tree hook taking an options record, not one hook per grower mode
+    assert hasattr(lib, "fr_debug_hist_tree") and not any(
+        hasattr(lib, "fr_debug_hist_tree_" + mode) for mode in ("sampled", "newton", "leafwise", "symmetric", "monotone", "goss"))
 
 
 def test_pricing_switches_are_not_in_the_shipped_library():

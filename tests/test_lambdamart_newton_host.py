@@ -173,7 +173,7 @@ def test_accepted_requests_reach_the_later_checks(params):
 @pytest.mark.parametrize("key", NUMBERS)
 @pytest.mark.parametrize("value", [float("nan"), float("inf"), float("-inf"), -1.0])
 def test_debug_hook_rejects_a_number_that_is_not_finite_or_negative(key, value):
-    """The one entry point a non-finite number can reach as a double: fr_debug_hist_tree_newton refuses it before it looks at
+    """The one entry point a non-finite number can reach as a double: fr_debug_hist_tree's options refuse it before it looks at
     the dataset."""
     from fastrank_amd import native
 
