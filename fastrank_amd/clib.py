@@ -87,6 +87,7 @@ def _load():
         "fr_ca_capture": (vp, [vp, C.c_int]),
         "fr_ca_capture_take": (vp, [vp, C.c_char_p, vp, sz]),
         "fr_last_train_stats": (vp, []),
+        "fr_debug_tree_plan": (vp, []),
         "fr_predict_scores_dense": (vp, [vp, vp, vp, sz]),
         "fr_explain_dense": (vp, [vp, vp, vp, vp, sz, sz]),
         "fr_feature_importance": (vp, [vp, vp, vp, vp, sz]),

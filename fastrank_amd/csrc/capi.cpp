@@ -1557,6 +1557,32 @@ const void* fr_last_train_stats(void) {
     });
 }
 
+const void* fr_debug_tree_plan(void) {
+    return json_call([&]() {
+        const frdev::TreePlan p = frdev::last_tree_plan();
+        Value o = Value::object();
+        if (p.path == frdev::TreePlan::NONE) {
+            o.set("path", Value::null());
+            return frjson::dump(o);
+        }
+        o.set("path", Value::string(p.path == frdev::TreePlan::RANK ? "rank" : p.path == frdev::TreePlan::LDS ? "lds" : "l2"));
+        o.set("cache_hit", Value::boolean(p.cache_hit));
+        if (p.path == frdev::TreePlan::LDS) o.set("docs", Value::uint(p.docs)), o.set("parts", Value::uint(p.parts));
+        if (p.path == frdev::TreePlan::L2) o.set("rows_in_lds", Value::boolean(p.rows_in_lds));
+        if (p.path == frdev::TreePlan::RANK) o.set("nslots", Value::uint(p.nslots)), o.set("nrounds", Value::uint(p.nrounds));
+        if (p.path != frdev::TreePlan::L2) {
+            Value a = Value::array();
+            for (const auto& b : p.batches) {
+                Value pair = Value::array();
+                pair.push(Value::uint(b.first)), pair.push(Value::uint(b.second));
+                a.push(std::move(pair));
+            }
+            o.set("batches", std::move(a));
+        }
+        return frjson::dump(o);
+    });
+}
+
 const void* fr_predict_scores_dense(const CModel* model, const CDataset* dataset, double* out, size_t out_len) {
     return status_call([&]() {
         const CModel& m = require_model(model);

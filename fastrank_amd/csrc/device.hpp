@@ -75,6 +75,19 @@ struct FlatTrees {
     bool raw_single = false;      // a bare DecisionTree model: output = leaf value
 };
 
+// What the process's last DeviceDataset::score_trees call ran (fr_debug_tree_plan): which of the three
+// encodings took the forest and in what shape.  Host bookkeeping alone: no timing, no launch of its own.
+struct TreePlan {
+    enum Path { NONE, RANK, LDS, L2 };
+    Path path = NONE;
+    bool cache_hit = false;             // RANK: launched from the buffers the call before left
+    bool rows_in_lds = false;           // L2: tree_ensemble_kernel<true, 8> (rows staged in LDS) or <false, 8>
+    uint32_t docs = 0, parts = 0;       // LDS: the block shape that took the forest
+    uint32_t nslots = 0, nrounds = 0;   // RANK: features in use, ranking rounds
+    std::vector<std::pair<uint32_t, uint32_t>> batches;  // RANK, LDS: (walks per thread, levels) of every batch
+};
+TreePlan last_tree_plan();
+
 // One line-search group: every candidate shares (feature f, base weights w) and differs only in
 // the weight of f (src/coordinate_ascent.rs:131-171).
 struct LineGroup {

@@ -406,6 +406,7 @@ struct DeviceDataset::Impl : DatasetDesc {
     uint64_t tree_rank_hash = 0;
     uint32_t tree_rank_nrounds = 0, tree_rank_nslots = 0, tree_rank_nbatch = 0;
     size_t tree_rank_lds = 0;
+    std::vector<std::pair<uint32_t, uint32_t>> tree_rank_batches;  // (walks per thread, levels), for the plan of a cache hit
     size_t scores_slots = 0;
     bool sums_only = false;  // reductions over queries return sums instead of means
     size_t last_ldm = 0, last_cols = 0;
@@ -560,6 +561,24 @@ bool DeviceDataset::score_single_feature(uint32_t fid, double dir, std::string* 
     }
     FR_HIP(hipGetLastError());
     return true;
+}
+
+// The last score_trees call's plan (device.hpp: TreePlan), written by whichever path launched.
+static std::mutex g_tree_plan_mu;
+static TreePlan g_tree_plan;
+static void set_tree_plan(TreePlan&& p) {
+    std::lock_guard<std::mutex> lk(g_tree_plan_mu);
+    g_tree_plan = std::move(p);
+}
+TreePlan last_tree_plan() {
+    std::lock_guard<std::mutex> lk(g_tree_plan_mu);
+    return g_tree_plan;
+}
+// (walks per thread, levels) of every batch of a descriptor list {start, n, levels, ..} x nbatch + terminator
+static std::vector<std::pair<uint32_t, uint32_t>> tree_plan_batches(const std::vector<uint32_t>& desc) {
+    std::vector<std::pair<uint32_t, uint32_t>> out;
+    for (size_t b = 0; b + 1 < desc.size() / 4; b++) out.emplace_back(desc[b * 4 + 1], desc[b * 4 + 2]);
+    return out;
 }
 
 // Largest f32 <= split: (f64(x) <= split) <=> (x <= thr) for every non-NaN f32 x.
@@ -749,12 +768,16 @@ bool DeviceDataset::try_score_trees_lds_shape(const FlatTrees& t, const void* sh
         launch_tree_lds(*shape, lds, m.stream, m.posmap(), m.pos_threads(), m.xb.p, (uint32_t)m.dq, f16, m.batch_off.p, (uint32_t)nbatch, raw, m.leafprod.p, m.scores.p);
     }
     FR_HIP(hipGetLastError());
+    TreePlan plan;
+    plan.path = TreePlan::LDS, plan.docs = shape->docs, plan.parts = shape->parts, plan.batches = tree_plan_batches(desc);
+    set_tree_plan(std::move(plan));
     return true;
 }
 
 // Scores a forest with tree_ensemble_rank_kernel (kernels_treerank.inc: threshold ranks instead of features).  Returns
 // false with an empty *err when the forest does not fit that encoding: a single bare tree (raw output), a leaf deeper
-// than 10 levels, more than 1023 distinct thresholds on one feature, or more than 168 features in use -- the caller then
+// than 10 levels, more than 1023 distinct thresholds on one feature, or more than 170 features in use (85 pairs of u16 codes
+// x 768 bytes + the two constant codes end at 65282 < 2^16) -- the caller then
 // takes the f32 LDS walk.  FR_TREE_RANK=0 switches the path off (A/B, and the parity tests of the other paths).
 bool DeviceDataset::try_score_trees_rank(const FlatTrees& t, std::string* err) {
     Impl& m = *impl_;
@@ -805,9 +828,12 @@ bool DeviceDataset::try_score_trees_rank(const FlatTrees& t, std::string* err) {
     if (!cache_off && hash == m.tree_rank_hash) {
         launch(m.tree_rank_nrounds, m.tree_rank_nslots, m.tree_rank_nbatch, m.tree_rank_lds);
         FR_HIP(hipGetLastError());
+        TreePlan plan;
+        plan.path = TreePlan::RANK, plan.cache_hit = true, plan.nslots = m.tree_rank_nslots, plan.nrounds = m.tree_rank_nrounds;
+        plan.batches = m.tree_rank_batches;
+        set_tree_plan(std::move(plan));
         return true;
     }
-    m.tree_rank_hash = 0;
 
     // ---- distinct thresholds per feature, as f32 (largest f32 <= split), -0.0 folded onto +0.0
     std::vector<std::vector<float>> thr(nf);
@@ -992,6 +1018,7 @@ bool DeviceDataset::try_score_trees_rank(const FlatTrees& t, std::string* err) {
     }
     desc.insert(desc.end(), {(uint32_t)(forest.size() / 4), 0u, 0u, 0u});
     const size_t nbatch = desc.size() / 4 - 1;
+    m.tree_rank_hash = 0;  // only now: a forest refused above has touched no buffer, and the forest kept from before still launches
     if (!m.forest.ensure((forest.size() + 1) / 2, err) || !m.batch_off.ensure(desc.size(), err) ||
         !m.leafprod.ensure(leafprod.size() + (frdev::pricing_env("FR_TREE_NOWALK") ? 65536 : 0), err) || !m.tree_fdesc.ensure(fdesc.size(), err) || !m.tree_tables.ensure(std::max<size_t>(tables.size(), 1), err) ||
         !m.tree_rdesc.ensure(std::max<size_t>(rdesc.size(), 1), err))
@@ -1010,6 +1037,10 @@ bool DeviceDataset::try_score_trees_rank(const FlatTrees& t, std::string* err) {
     m.tree_rank_nslots = nslots;
     m.tree_rank_nbatch = (uint32_t)nbatch;
     m.tree_rank_lds = lds;
+    m.tree_rank_batches = tree_plan_batches(desc);
+    TreePlan plan;
+    plan.path = TreePlan::RANK, plan.nslots = nslots, plan.nrounds = nrounds, plan.batches = m.tree_rank_batches;
+    set_tree_plan(std::move(plan));
     return true;
 }
 
@@ -1063,6 +1094,11 @@ bool DeviceDataset::score_trees(const FlatTrees& t, std::string* err) {
     FR_HIP(hipStreamSynchronize(m.stream));
     const unsigned bs = 64;  // one tile per block (np is a multiple of 64)
     size_t lds = (size_t)bs * (m.dq * 4 + 1) * sizeof(float);
+    {
+        TreePlan plan;
+        plan.path = TreePlan::L2, plan.rows_in_lds = lds <= 150 * 1024;
+        set_tree_plan(std::move(plan));
+    }
     {
         ProfScope ps("tree_ensemble_kernel", m.stream);
         if (lds <= 150 * 1024) {

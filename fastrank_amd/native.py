@@ -356,6 +356,12 @@ def last_train_stats() -> Dict:
     return _json_reply(_load().fr_last_train_stats())
 
 
+def last_tree_plan() -> Dict:
+    """What the last forest-scoring call of this process ran (fr_debug_tree_plan): {"path": "rank" | "lds" | "l2",
+    "cache_hit", and per path "docs", "parts" / "rows_in_lds" / "nslots", "nrounds"; "batches": [[walks, levels], ...]}."""
+    return _json_reply(_load().fr_debug_tree_plan())
+
+
 def train_model_shard(dataset: CDataset, train_req, restart_begin: int, restart_end: int) -> Dict:
     """Train restarts [begin, end) of the request on this process's GPU."""
     request = json.dumps(train_req.to_dict()).encode("utf-8")

@@ -171,6 +171,11 @@ const CResult *fr_select_model(const void *restarts_json, int output_ensemble);
  * bound-and-verify line search publishes (NDCG@k, full ranking, reciprocal rank) is recomputed by the exact kernels and
  * compared bit for bit -- values compared / values that differed). */
 const void *fr_last_train_stats(void);
+/* What the process's last forest-scoring call ran, a test hook; JSON (free_str), no timing in it and
+ * no launch behind it: {"path": "rank" | "lds" | "l2" (null before the first call), "cache_hit": the rank path launched from
+ * the buffers the call before left; lds: "docs", "parts" (the block shape); l2: "rows_in_lds"; rank: "nslots" (features in
+ * use), "nrounds"; rank and lds: "batches": [[walks per thread, levels], ...]}. */
+const void *fr_debug_tree_plan(void);
 
 /* Dense results without JSON.  out[i] = score of instance i (instances outside the dataset
  * view are left untouched).  Returns NULL on success or an error-envelope string. */

@@ -32,6 +32,8 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), "missing export: " + name
     for name in clib.exported_symbols():  # the 20 reference symbols (src/lib.rs:78-326)
         assert name in syms
+    # the forest-scoring report is declared, exported and bound (tests/test_gpu_tree_scoring.py reads it after every call)
+    assert "fr_debug_tree_plan" in syms and hasattr(lib, "fr_debug_tree_plan") and "path" in native.last_tree_plan()
     # one histogram-tree hook taking an options record, not one hook per grower mode
     assert hasattr(lib, "fr_debug_hist_tree") and not any(
         hasattr(lib, "fr_debug_hist_tree_" + mode) for mode in ("sampled", "newton", "leafwise", "symmetric", "monotone", "goss"))

@@ -632,7 +632,13 @@ def test_tree_kernel_block_shapes(mslr_small, shape, monkeypatch):
     trees = [_rand_tree(rng, X, 7, nfeat=X.shape[1] + 4) for _ in range(77)]
     weights = rng.uniform(-1.0, 1.0, len(trees)).tolist()
     got = native.predict_scores_dense(_ensemble(trees, weights), g)
+    plan = native.last_tree_plan()
     assert np.array_equal(got, c.score_ensemble(trees, weights))
+    if shape:  # the pinned shape is the one that ran: a shape that did not fit would have fallen through to the L2 walk
+        docs, parts = (int(v) for v in shape.split(","))
+        assert plan["path"] == "lds" and (plan["docs"], plan["parts"]) == (docs, parts), plan
+    else:
+        assert plan["path"] == "rank", plan
 
 
 def _tree_kernels_used(model, g):
@@ -1762,3 +1768,7 @@ def test_randomised_forest_scoring_soak():
     last = out.stdout.strip().splitlines()[-1]
     assert out.returncode == 0, out.stdout[-2000:]
     assert json.loads(last)["mismatches"] == 0
+    # all three encodings, the LDS walk's small-block shapes (wide matrices) and both variants of the L2 walk were reached
+    paths = set(json.loads(last)["paths"])
+    assert {"rank", "l2_rows_in_lds", "l2_rows_in_hbm"} <= paths, paths
+    assert any(p.startswith("lds_128x") for p in paths) and any(p.startswith("lds_64x") for p in paths), paths
