@@ -79,6 +79,7 @@ def _load():
         "fr_version": (C.c_char_p, []),
         "fr_train_model_shard": (vp, [C.c_char_p, vp, C.c_uint32, C.c_uint32]),
         "fr_select_model": (res, [C.c_char_p, C.c_int]),
+        "fr_train_model_with": (res, [C.c_char_p, vp, vp, vp]),
         "fr_ca_begin": (vp, [C.c_char_p, vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]),
         "fr_ca_begin_query_shard": (vp, [C.c_char_p, vp, C.c_uint64, ALLREDUCE_SUM_FN, vp, C.POINTER(vp)]),
         "fr_ca_step": (vp, [vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
@@ -374,10 +375,21 @@ class CDataset:
         child.numpy_arrays_to_keep = self.numpy_arrays_to_keep
         return child
 
-    def train_model(self, train_req: "TrainRequest") -> CModel:  # noqa: F821
+    def train_model(self, train_req: "TrainRequest", valid: Optional["CDataset"] = None,  # noqa: F821
+                    init_model: Optional[CModel] = None) -> CModel:
+        """Train on this dataset.  LambdaMART requests only: `valid` is a second dataset the held-out measure and early
+        stopping are read from (no tree sees it); `init_model` is an Ensemble of DecisionTrees training continues from
+        (num_trees then counts new trees).  DESIGN.md section 11, "Validation dataset" and "Continued training"."""
         self._require_init()
         request = json.dumps(train_req.to_dict()).encode("utf-8")
-        return CModel(_unwrap(_load().train_model(request, self.pointer)), train_req)
+        if valid is None and init_model is None:
+            return CModel(_unwrap(_load().train_model(request, self.pointer)), train_req)
+        if valid is not None:
+            valid._require_init()
+        if init_model is not None:
+            init_model._require_init()
+        return CModel(_unwrap(_load().fr_train_model_with(request, self.pointer, None if valid is None else valid.pointer,
+                                                          None if init_model is None else init_model.pointer)), train_req)
 
     def _query_json(self, message="num_features"):
         self._require_init()

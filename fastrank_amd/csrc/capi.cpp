@@ -210,7 +210,8 @@ struct ParsedRequest {
 };
 
 // src/json_api.rs:13-34 TrainRequest
-ParsedRequest parse_train_request(const std::string& text) {
+// (has_valid: the call brings a validation dataset, LambdaMARTParams::from_json)
+ParsedRequest parse_train_request(const std::string& text, bool has_valid = false) {
     Value v = parse_json_or_fail(text);
     if (!v.is_object()) fr::fail_raw("Error(\"invalid type: expected struct TrainRequest\", line: 1, column: 1)");
     ParsedRequest rq;
@@ -226,7 +227,7 @@ ParsedRequest parse_train_request(const std::string& text) {
         rq.rf = fr::RFParams::from_json(var.second);
     } else if (var.first == "LambdaMART") {
         rq.learner = Learner::LambdaMART;
-        rq.lm = fr::LambdaMARTParams::from_json(var.second);
+        rq.lm = fr::LambdaMARTParams::from_json(var.second, has_valid);
         fr::lambdamart_check_measure(rq.measure);
     } else {
         fr::fail_raw("Error(\"unknown variant `" + var.first +
@@ -612,12 +613,16 @@ fr::Model train_rf(const std::shared_ptr<fr::DatasetView>& view, const ParsedReq
 
 // LambdaMART trains on the view's primary device only: its trees depend on each other, and a request that names several
 // devices gets the single-device model
-fr::Model train_lambdamart(const std::shared_ptr<fr::DatasetView>& view, const ParsedRequest& rq) {
+// (valid / init: fr_train_model_with's validation dataset and init model, or null)
+fr::Model train_lambdamart(const std::shared_ptr<fr::DatasetView>& view, const ParsedRequest& rq, const std::shared_ptr<fr::DatasetView>& valid = nullptr,
+                           const fr::Model* init = nullptr) {
     auto t0 = std::chrono::steady_clock::now();
     // under objective = map / mrr the AP / RR evaluator takes over every role of the request's measure (which was checked)
     const char* objective = rq.lm.objective_measure();
     fr::Evaluator ev = fr::make_evaluator(*view, objective ? std::string(objective) : rq.measure, rq.has_qrel ? &rq.qrel : nullptr);
     fr::LambdaMARTTrainer trainer(view, std::move(ev), rq.lm);
+    if (valid) trainer.set_valid(valid, fr::make_evaluator(*valid, objective ? std::string(objective) : rq.measure, rq.has_qrel ? &rq.qrel : nullptr));
+    trainer.set_init(init);
     fr::Model m = trainer.learn();
     fr::TrainStats st;
     st.devices = 1;
@@ -1702,6 +1707,23 @@ struct ExplainLocks {
 };
 
 }  // namespace
+
+const CResult* fr_train_model_with(const void* train_request_json, const CDataset* dataset, const CDataset* valid_dataset_or_null,
+                                   const CModel* init_model_or_null) {
+    if (!valid_dataset_or_null && !init_model_or_null) return train_model((void*)train_request_json, (void*)dataset);
+    return c_call<CModel>([&]() {
+        const CDataset& ds = require_dataset(dataset);
+        ParsedRequest rq = parse_train_request(accept_str("train_request_json", train_request_json), valid_dataset_or_null != nullptr);
+        if (rq.learner != Learner::LambdaMART)
+            fr::fail_str(std::string("fr_train_model_with: a validation dataset and an init model are LambdaMART's; the request's learner is ") +
+                         (rq.learner == Learner::CoordinateAscent ? "CoordinateAscent" : "RandomForest"));
+        ExplainLocks lk(ds, valid_dataset_or_null);
+        return new_model([&] {
+            return train_lambdamart(ds.view, rq, valid_dataset_or_null ? valid_dataset_or_null->view : nullptr,
+                                    init_model_or_null ? &init_model_or_null->actual : nullptr);
+        });
+    });
+}
 
 const void* fr_explain_dense(const CModel* model, const CDataset* dataset, const CDataset* background_or_null, double* out, size_t rows, size_t cols) {
     return json_call([&]() {

@@ -46,6 +46,11 @@
 // symmetric_trees (histogram grower, level-wise, no monotone constraints; DESIGN.md section 11, "Symmetric trees"): every node
 // of a level splits on the one (feature, threshold) with the largest importance summed over the level's open nodes; a node
 // that cannot split under it becomes a leaf.  The trees are ordinary DecisionTrees; everything upstream of the grower composes.
+// A validation dataset B ("Validation dataset"): a second view, scored tree by tree on its own device form
+// (score slot, accumulator, metric pass, mean; under DART a leaf cache of its own); no tree reads it.  Its plain mean over
+// all of its queries is the held-out measure the stopping rule reads.
+// An init model ("Continued training"): an Ensemble of T0 DecisionTrees.  The scores start at its forest
+// scores, new tree j is tree T0 + j of the result and takes every per-tree stream at that index, num_trees counts new trees.
 // A request's keys live in LambdaMARTParams alone: the gradient pass and the histogram grower get their options from it
 // (pass(), hist_options()), and the stats keep a copy of it (LambdaMARTStats::request) to report from.
 #pragma once
@@ -146,7 +151,8 @@ struct LambdaMARTParams {
         // (the text predates the fourth value and is kept byte for byte: DESIGN.md section 11, "Listwise objective")
         invalid("objective must be `ndcg`, `map` or `mrr`, not `" + g.s + "`");
     }
-    static LambdaMARTParams from_json(const Value& v) {
+    // has_valid: the call brings a validation dataset, which is a source of the held-out measure like validation_queries
+    static LambdaMARTParams from_json(const Value& v, bool has_valid = false) {
         if (!v.is_object()) fail_raw("Error(\"invalid type: expected struct LambdaMARTParams\", line: 0, column: 0)");
         LambdaMARTParams p;
         p.num_trees = json_u32(json_field(v, "num_trees"), "num_trees");
@@ -216,7 +222,7 @@ struct LambdaMARTParams {
             invalid("feature_sampling_rate must be greater than 0 and at most 1");
         if (p.histogram && (p.split_candidates < 2 || p.split_candidates > 256))
             invalid("split_candidates must be between 2 and 256 for the histogram grower (bins are one byte)");
-        if (p.early_stopping_rounds > 0 && p.validation_queries.empty())
+        if (p.early_stopping_rounds > 0 && p.validation_queries.empty() && !has_valid)
             invalid("early_stopping_rounds needs at least one validation query (validation_queries is empty)");
         if (p.newton && !p.histogram) invalid("split_gain `newton` needs grower: \"histogram\" (the exact grower keeps the random-forest criterion)");
         const std::pair<const char*, double> numbers[] = {{"lambda_l2", p.lambda_l2}, {"min_sum_hessian", p.min_sum_hessian}, {"min_split_gain", p.min_split_gain}};
@@ -382,6 +388,54 @@ inline LambdaSample lambdamart_next_sample(Rand64& master, size_t n_features, si
     return smp;
 }
 
+// A validation dataset against the training view and the request (host only: refused before any device work).
+inline void lambdamart_check_valid(DatasetView& view, DatasetView& valid, const LambdaMARTParams& p) {
+    if (!p.validation_queries.empty())
+        LambdaMARTParams::invalid("validation_queries cannot be combined with a validation dataset (there is one source of the held-out measure)");
+    bool all_a = true, all_b = true;
+    DatasetView *own_a = view.matrix_owner(&all_a), *own_b = valid.matrix_owner(&all_b);
+    if (&view == &valid || (own_a == own_b && all_a && all_b))
+        LambdaMARTParams::invalid("the validation dataset is the dataset being trained on (hold queries of it out with validation_queries)");
+    std::set<uint32_t> have(valid.features.begin(), valid.features.end());
+    std::vector<uint32_t> feats = view.features;
+    std::sort(feats.begin(), feats.end());
+    for (uint32_t f : feats)
+        if (!have.count(f))
+            LambdaMARTParams::invalid("the validation dataset does not hold feature `" + view.core->feature_name(f) + "` of the training dataset");
+    if (valid.host_csr().nq == 0) LambdaMARTParams::invalid("the validation dataset holds no query");
+    const int da = view.built_on_device(), db = valid.built_on_device();
+    if (da >= 0 && db >= 0 && da != db)
+        LambdaMARTParams::invalid("the validation dataset lives on device " + std::to_string(db) + ", the training dataset on device " +
+                                  std::to_string(da) + " (a validation dataset on another device is not supported)");
+}
+
+// An init model against the request (host only): an Ensemble of DecisionTrees with finite numbers, one weight per tree.
+inline void lambdamart_check_init(const Model& m, const LambdaMARTParams& p) {
+    auto refuse = [](const std::string& what) { fail_str("LambdaMART: init_model must be an Ensemble of DecisionTrees, not " + what); };
+    if (m.kind == Model::Linear) refuse("a Linear model");
+    if (m.kind == Model::SingleFeature) refuse("a SingleFeature model");
+    if (m.kind == Model::DecisionTree) refuse("a bare DecisionTree (wrap it in an Ensemble with a weight)");
+    if (m.members.size() != m.ens_weights.size())
+        fail_str("LambdaMART: init_model has " + std::to_string(m.ens_weights.size()) + " weights for " + std::to_string(m.members.size()) + " models");
+    for (size_t t = 0; t < m.members.size(); t++) {
+        const Model& mm = m.members[t];
+        if (mm.kind == Model::Ensemble) refuse("an Ensemble with a nested Ensemble (member " + std::to_string(t) + ")");
+        if (mm.kind != Model::DecisionTree) refuse(std::string("an Ensemble with a ") + (mm.kind == Model::Linear ? "Linear" : "SingleFeature") + " member (member " + std::to_string(t) + ")");
+        if (!std::isfinite(m.ens_weights[t])) fail_str("LambdaMART: init_model has a non-finite weight (tree " + std::to_string(t) + ")");
+        std::vector<const TreeNode*> work{mm.tree.get()};
+        while (!work.empty()) {
+            const TreeNode* n = work.back();
+            work.pop_back();
+            if (!n) fail_str("LambdaMART: init_model has an empty tree (tree " + std::to_string(t) + ")");
+            if (!std::isfinite(n->value))
+                fail_str(std::string("LambdaMART: init_model has a non-finite ") + (n->leaf ? "leaf" : "split") + " (tree " + std::to_string(t) + ")");
+            if (!n->leaf) work.push_back(n->lhs.get()), work.push_back(n->rhs.get());
+        }
+    }
+    if (p.dart())
+        LambdaMARTParams::invalid("init_model cannot be combined with drop_rate greater than 0 (dropping or re-weighting the given trees needs their leaf caches and changes a model the caller owns)");
+}
+
 struct LambdaMARTStats {
     LambdaMARTParams request;  // what was asked for: the keys reported below are read from it
     uint32_t trees = 0;
@@ -412,6 +466,16 @@ struct LambdaMARTStats {
     std::vector<uint32_t> goss_instances, goss_top;
     // symmetric trees (reported only when the key is set): per tree the levels that split
     std::vector<uint32_t> levels;
+    double best_valid_measure = 0.0;  // the held-out measure at best_iteration
+    // a validation dataset (reported only when one is given): its sizes and the wall seconds of its side of every tree
+    bool valid_dataset = false;
+    uint32_t valid_dataset_queries = 0, valid_dataset_instances = 0;
+    double t_valid = 0.0;
+    uint64_t valid_dart_cache_bytes = 0;  // under DART: the bytes of the validation dataset's own leaf cache
+    // an init model (reported only when one is given): its trees, the measures of its scores, the wall seconds of forming them
+    bool init_model = false;
+    uint32_t init_trees = 0;
+    double init_train_measure = 0.0, init_valid_measure = 0.0, t_init = 0.0;
 
     Value to_json() const {
         const LambdaMARTParams& r = request;
@@ -437,16 +501,29 @@ struct LambdaMARTStats {
         Value a = Value::array();
         for (double x : train_measure) a.push(Value::number(x));
         o.set("train_measure", std::move(a));
-        if (validation_queries != 0) {
-            o.set("validation_queries", Value::uint(validation_queries));
-            o.set("training_queries", Value::uint(training_queries));
+        if (validation_queries != 0 || valid_dataset) {
+            if (valid_dataset) {
+                o.set("valid_dataset_queries", Value::uint(valid_dataset_queries));
+                o.set("valid_dataset_instances", Value::uint(valid_dataset_instances));
+                o.set("valid_ms", Value::number(t_valid * 1e3));
+                if (r.dart()) o.set("valid_dart_cache_bytes", Value::uint(valid_dart_cache_bytes));
+            } else {
+                o.set("validation_queries", Value::uint(validation_queries));
+                o.set("training_queries", Value::uint(training_queries));
+            }
             Value b = Value::array();
             for (double x : valid_measure) b.push(Value::number(x));
             o.set("valid_measure", std::move(b));
             o.set("best_iteration", Value::uint(best_iteration));
-            o.set("best_valid_measure", Value::number(best_iteration ? valid_measure[best_iteration - 1] : 0.0));
+            o.set("best_valid_measure", Value::number(best_valid_measure));
             o.set("stopped_early", Value::boolean(stopped_early));
             o.set("early_stopping_rounds", Value::uint(r.early_stopping_rounds));
+        }
+        if (init_model) {
+            o.set("init_trees", Value::uint(init_trees));
+            o.set("init_train_measure", Value::number(init_train_measure));
+            if (validation_queries != 0 || valid_dataset) o.set("init_valid_measure", Value::number(init_valid_measure));
+            o.set("init_ms", Value::number(t_init * 1e3));
         }
         // (the Newton gain and the leaf budget are the histogram grower's: a request sets them with no other)
         if (r.histogram && r.newton) {
@@ -505,6 +582,10 @@ class LambdaMARTTrainer {
   public:
     LambdaMARTTrainer(std::shared_ptr<DatasetView> view, Evaluator ev, LambdaMARTParams p)
         : view_(std::move(view)), ev_(std::move(ev)), p_(p) {}
+    // a validation dataset with its own evaluator (the request's measure and judgments over ITS queries)
+    void set_valid(std::shared_ptr<DatasetView> valid, Evaluator ev) { valid_ = std::move(valid), vev_ = std::move(ev); }
+    // the model training continues from (checked by lambdamart_check_init; must outlive learn())
+    void set_init(const Model* init) { init_ = init; }
 
     Model learn() {
         auto t0 = std::chrono::steady_clock::now();
@@ -519,6 +600,12 @@ class LambdaMARTTrainer {
             fail_str(std::string("LambdaMART: the evaluator does not belong to the objective `") + LambdaMARTParams::objective_name(p_.objective) + "`");
         const LambdaSplit split = lambdamart_split(*view_, p_);  // (host only: a bad list fails before any device work)
         const bool hold = !split.held.empty();
+        const bool vd = (bool)valid_;                      // a validation dataset: `hold` is then false (checked)
+        const bool held_measure = hold || vd;              // there is a held-out measure for the stopping rule
+        const uint32_t T0 = init_ ? (uint32_t)init_->members.size() : 0u;
+        if (vd) lambdamart_check_valid(*view_, *valid_, p_);
+        if (init_) lambdamart_check_init(*init_, p_);
+        if (vd && vev_.measure != ev_.measure) fail_str("LambdaMART: the validation dataset's evaluator is not the training one's");
         std::vector<uint32_t> feats = view_->features;
         std::sort(feats.begin(), feats.end());
         const std::vector<int> signs = lambdamart_monotone_signs(*view_, feats, p_);  // (host only as well)
@@ -562,14 +649,60 @@ class LambdaMARTTrainer {
             frdev::DeviceDataset& d;
             ~EndGuard() { d.rf_end(), d.subset_means_end(); }
         } end_guard{dev};
+        // the validation dataset's device form, on the training view's device (built there when it does not exist yet)
+        frdev::DeviceDataset* vdev = nullptr;
+        if (vd) {
+            if (!frdev::set_device(dev.device_ordinal(), &err)) fail_str(err);
+            vdev = &valid_->device();
+            if (vdev == &dev) LambdaMARTParams::invalid("the validation dataset is the dataset being trained on (hold queries of it out with validation_queries)");
+            if (vdev->device_ordinal() != dev.device_ordinal())
+                LambdaMARTParams::invalid("the validation dataset lives on device " + std::to_string(vdev->device_ordinal()) + ", the training dataset on device " +
+                                          std::to_string(dev.device_ordinal()) + " (a validation dataset on another device is not supported)");
+            stats_.valid_dataset = true;
+            stats_.valid_dataset_queries = (uint32_t)vdev->nq(), stats_.valid_dataset_instances = (uint32_t)vdev->n();
+        }
+        struct ValidGuard {  // (the validation side holds nothing but its leaf cache beyond a call)
+            frdev::DeviceDataset* d;
+            bool dart;
+            ~ValidGuard() {
+                if (d && dart) d->dart_end();
+            }
+        } valid_guard{vdev, p_.dart()};
 
         Model out;
         out.kind = Model::Ensemble;
-        // running scores: acc = 0, slot 0 = acc
-        if (!dev.ensemble_begin(&err) || !dev.ensemble_finish(&err)) fail_str(err);
-        const char* rule = hold ? "---------------------------------------\n" : "-----------------------\n";
+        // running scores: acc = 0, slot 0 = acc; with an init model acc = 0 + 1.0 * forest scores (exact), slot 0 = acc
+        auto start_scores = [&](DatasetView& v, frdev::DeviceDataset& d) {
+            if (!d.ensemble_begin(&err)) fail_str(err);
+            if (T0 > 0) {
+                score_model(v, *init_, &d);
+                if (!d.ensemble_accumulate(1.0, &err)) fail_str(err);
+            }
+            if (!d.ensemble_finish(&err)) fail_str(err);
+        };
+        // the mean of the validation dataset's running scores over all of its queries, in its order
+        auto valid_mean = [&]() {
+            double m = 0.0;
+            if (!vdev->metric_from_scores(vev_.measure, vev_.depth, vev_.norms.data(), 1, false, &err)) fail_str(err);
+            if (!vdev->reduce_means(1, &m, &err)) fail_str(err);
+            check_flags(*vdev);
+            return m;
+        };
+        if (init_) {
+            auto ti = tnow();
+            out.members = init_->members, out.ens_weights = init_->ens_weights;
+            start_scores(*view_, dev);
+            if (vd) start_scores(*valid_, *vdev);
+            if (!frdev::device_synchronize(&err)) fail_str(err);
+            stats_.t_init = secs(ti, tnow());
+            stats_.init_model = true, stats_.init_trees = T0;
+        } else {
+            start_scores(*view_, dev);
+            if (vd) start_scores(*valid_, *vdev);
+        }
+        const char* rule = held_measure ? "---------------------------------------\n" : "-----------------------\n";
         if (!p_.quiet) {
-            if (hold) printf("%s|%7s|%15s|%15s|\n%s", rule, "Tree", ev_.name.c_str(), "validation", rule);
+            if (held_measure) printf("%s|%7s|%15s|%15s|\n%s", rule, "Tree", ev_.name.c_str(), "validation", rule);
             else printf("%s|%7s|%15s|\n%s", rule, "Tree", ev_.name.c_str(), rule);
         }
         std::vector<double> lam, wt, leaf_of(max_id + 1, 0.0);
@@ -578,6 +711,8 @@ class LambdaMARTTrainer {
         const bool sampling = p_.sampling(), sample_q = p_.query_sampling_rate < 1.0, sample_f = p_.feature_sampling_rate < 1.0;
         const bool subset_q = sample_q || hold, fixed_q = hold && !sample_q;
         Rand64 master(p_.seed);
+        if (sampling)  // (an init model's trees have taken their seeds: two each)
+            for (uint32_t i = 0; i < 2 * T0; i++) (void)master.rand_u64();
         std::vector<unsigned char> qflags;
         std::vector<uint32_t> t_ids, t_pos, t_feats, t_off;
         uint32_t t_n = 0;  // the tree's number of instances
@@ -604,14 +739,35 @@ class LambdaMARTTrainer {
                 if (hist) hist->set_sample(qflags.data(), t_n, nullptr);
             }
         }
+        // best_it: a tree count of the returned model (init trees included); 0 = no measure seen yet
         uint32_t trained = 0, best_it = 0;
         double best_valid = 0.0;
+        if (init_) {  // the init model's own measures, from one metric pass: with a held-out measure it is the first best
+            double mean = 0.0, two[2] = {0.0, 0.0};
+            if (!dev.metric_from_scores(ev_.measure, ev_.depth, ev_.norms.data(), 1, false, &err)) fail_str(err);
+            if (hold) {
+                if (!dev.reduce_subset_means(two, &err)) fail_str(err);
+                mean = two[0];
+            } else if (!dev.reduce_means(1, &mean, &err)) {
+                fail_str(err);
+            }
+            check_flags(dev);
+            stats_.init_train_measure = mean;
+            if (held_measure) {
+                stats_.init_valid_measure = hold ? two[1] : valid_mean();
+                if (T0 > 0) best_it = T0, best_valid = stats_.init_valid_measure;
+            }
+        }
         // DART: the drop plan, the leaf cache (one row per tree) and the weights so far; without drop_rate none of it exists
         const bool dart = p_.dart();
         DartPlan plan(p_.seed, p_.drop_rate, p_.max_drop, p_.skip_drop);
         Rand64 xe_keys(p_.seed ^ XENDCG_STREAM);  // the listwise objective's keys: a stream of its own, like the plan's
         GossKeys goss_keys(p_.seed);               // GOSS: one more stream of its own (lambdamart_goss.hpp)
         const bool goss = p_.goss();
+        for (uint32_t i = 0; i < T0; i++) {  // (an init model's trees have taken their keys: one each)
+            if (p_.xendcg()) (void)xe_keys.rand_u64();
+            if (goss) (void)goss_keys.next();
+        }
         struct DartGuard {
             frdev::DeviceDataset& d;
             bool on;
@@ -621,6 +777,7 @@ class LambdaMARTTrainer {
         } dart_guard{dev, dart};
         if (dart) {
             if (!dev.dart_begin(p_.num_trees, &stats_.dart_cache_bytes, &err)) fail_str(err);
+            if (vd && !vdev->dart_begin(p_.num_trees, &stats_.valid_dart_cache_bytes, &err)) fail_str(err);
         }
         // the scores become sum_{i in trees} w_i tree_i(x), re-formed from tree 0 (slot 0 and the accumulator); waited for
         auto reform = [&](const std::vector<uint32_t>& trees) {
@@ -688,14 +845,17 @@ class LambdaMARTTrainer {
             Model tm;
             tm.kind = Model::DecisionTree;
             tm.tree = root;
+            // DART: the tree's leaf values and the list of every tree so far, shared by the training and the validation side
+            std::vector<double> values;
+            std::vector<uint32_t> all;
             if (dart) {  // the tree's row of the leaf cache: the routing copy's scores (slot 0) are the documents' leaf numbers
                 if (hist) {
                     Model rm;
                     rm.kind = Model::DecisionTree;
-                    rm.tree = number_leaves(*root, leaves);
+                    rm.tree = routing = number_leaves(*root, leaves);
                     score_model(*view_, rm, &dev);
                 }
-                std::vector<double> values(leaves.size());
+                values.resize(leaves.size());
                 for (size_t L = 0; L < leaves.size(); L++) values[L] = leaves[L]->value;
                 if (!dev.dart_fill(t, values.data(), values.size(), &err)) fail_str(err);
                 if (!frdev::device_synchronize(&err)) fail_str(err);
@@ -709,7 +869,7 @@ class LambdaMARTTrainer {
             if (dart) {
                 // the running scores under the new weights, from tree 0.  Without a drop that is acc + learning_rate * tree(x) bit
                 // for bit, and streaming the cache is still the cheaper way to it (a single tree's walk costs several re-formings)
-                std::vector<uint32_t> all(t + 1);
+                all.resize(t + 1);
                 for (uint32_t i = 0; i <= t; i++) all[i] = i;
                 reform(all);
                 tu = tnow();
@@ -728,6 +888,23 @@ class LambdaMARTTrainer {
             }
             check_flags(dev);
             auto te = tnow();
+            // the validation dataset's side, a stage of its own: the same update on its own device form, then its plain mean
+            double vmean = 0.0;
+            if (vd) {
+                if (dart) {
+                    Model rm;
+                    rm.kind = Model::DecisionTree;
+                    rm.tree = routing;
+                    score_model(*valid_, rm, vdev);
+                    if (!vdev->dart_fill(t, values.data(), values.size(), &err)) fail_str(err);
+                    if (!vdev->dart_rescore(out.ens_weights.data(), out.ens_weights.size(), all.data(), all.size(), &err)) fail_str(err);
+                } else {
+                    score_model(*valid_, tm, vdev);
+                    if (!vdev->ensemble_accumulate(p_.learning_rate, &err) || !vdev->ensemble_finish(&err)) fail_str(err);
+                }
+                vmean = valid_mean();
+                stats_.t_valid += secs(te, tnow());
+            }
             stats_.t_gradient += secs(ta, tb);
             stats_.t_grow += secs(ts, ta) + secs(tb, tc);
             stats_.t_leaves += secs(tc, td);
@@ -744,15 +921,17 @@ class LambdaMARTTrainer {
             stats_.train_measure.push_back(mean);
             out.members.push_back(std::move(tm));
             if (!p_.quiet) {
-                if (hold) printf("|%7u|%15.6f|%15.6f|\n", t + 1, mean, two[1]);
-                else printf("|%7u|%15.6f|\n", t + 1, mean);
+                if (held_measure) printf("|%7u|%15.6f|%15.6f|\n", T0 + t + 1, mean, hold ? two[1] : vmean);
+                else printf("|%7u|%15.6f|\n", T0 + t + 1, mean);
                 fflush(stdout);
             }
             trained = t + 1;
-            if (hold) {
-                stats_.valid_measure.push_back(two[1]);
-                if (best_it == 0 || two[1] > best_valid) best_it = trained, best_valid = two[1];  // the FIRST maximum
-                if (p_.early_stopping_rounds > 0 && trained - best_it >= p_.early_stopping_rounds) {
+            if (held_measure) {
+                const double v = hold ? two[1] : vmean;
+                const uint32_t iteration = T0 + trained;
+                stats_.valid_measure.push_back(v);
+                if (best_it == 0 || v > best_valid) best_it = iteration, best_valid = v;  // the FIRST maximum
+                if (p_.early_stopping_rounds > 0 && iteration - best_it >= p_.early_stopping_rounds) {
                     stats_.stopped_early = trained < p_.num_trees;
                     break;
                 }
@@ -761,7 +940,8 @@ class LambdaMARTTrainer {
         if (!p_.quiet) printf("%s", rule);
         stats_.trees = trained;
         stats_.best_iteration = best_it;
-        if (hold && p_.early_stopping_rounds > 0) {  // the ensemble up to the best tree (trees depend on their predecessors only)
+        stats_.best_valid_measure = best_valid;
+        if (held_measure && p_.early_stopping_rounds > 0) {  // the ensemble up to the best tree (trees depend on their predecessors only)
             out.members.resize(best_it);
             out.ens_weights.resize(best_it);
         }
@@ -794,8 +974,9 @@ class LambdaMARTTrainer {
         copy_numbered(*n.rhs, *c.rhs, leaves);
     }
 
-    std::shared_ptr<DatasetView> view_;
-    Evaluator ev_;
+    std::shared_ptr<DatasetView> view_, valid_;
+    Evaluator ev_, vev_;
+    const Model* init_ = nullptr;
     LambdaMARTParams p_;
     LambdaMARTStats stats_;
 };

@@ -150,7 +150,11 @@ class LambdaMARTParams(_LearnerParams):
     `min_leaf_support`.  One split has to pay off across a whole level, which regularises strongly.  Histogram grower,
     level-wise (`max_leaves` = 0) and without `monotone_constraints`; both split gains and every other key compose.  The
     trees are ordinary decision trees; the training stats then report `symmetric_trees` and `levels` (per tree, the levels
-    that split) ("Symmetric trees")."""
+    that split) ("Symmetric trees").
+    Two things are arguments of `CDataset.train_model`, not keys: `valid` (a second dataset the held-out measure and early
+    stopping are read from; `validation_queries` must then be empty and `early_stopping_rounds` needs no held-out query)
+    and `init_model` (an Ensemble of DecisionTrees training continues from: `num_trees` counts new trees, and the per-tree
+    streams of `seed` resume at the model's tree count) ("Validation dataset", "Continued training")."""
 
     VARIANT: ClassVar[str] = "LambdaMART"
 

@@ -154,6 +154,16 @@ const void *fr_ca_capture_take(void *trainer, const void *table, void *out, size
 /* Selection rule of src/coordinate_ascent.rs:232-252 over gathered restarts.
  * restarts_json: JSON list of {"restart_id","score","weights"}; returns a CModel. */
 const CResult *fr_select_model(const void *restarts_json, int output_ensemble);
+/* train_model with a validation dataset and / or a model to continue from (LambdaMART requests only; DESIGN.md section 11,
+ * "Validation dataset" and "Continued training").  With both NULL it is train_model.  valid_dataset_or_null: a second dataset
+ * (file-loaded, from arrays, or a sampled view -- a sibling view of the trained one's parent included) that no tree reads; it
+ * is scored after every tree on its own device form, and the mean of the request's measure over all of its queries is the
+ * held-out measure early_stopping_rounds reads (validation_queries must then be empty).  It must hold every feature of the
+ * trained view and live on the same device.  init_model_or_null: an Ensemble of DecisionTrees (T0 of them); num_trees counts
+ * NEW trees, new tree j takes every per-tree random stream at index T0 + j, and the result is the init model's trees and
+ * weights followed by the new ones (not with drop_rate > 0).  Returns a CModel; both datasets' locks are held for the call. */
+const CResult *fr_train_model_with(const void *train_request_json, const CDataset *dataset, const CDataset *valid_dataset_or_null,
+                                   const CModel *init_model_or_null);
 /* JSON stats of the most recent train_model / fr_train_model_shard call in this process:
  * {"useful_evals","raw_evals","ticks","groups","seconds","path","restarts","verify_pairs","verify_redone",
  *  "exact_ticks","exact_groups","verify_redo_entries","line_searches","audit_values","audit_mismatches","devices",
@@ -169,7 +179,14 @@ const CResult *fr_select_model(const void *restarts_json, int output_ensemble);
  * line_searches batched line searches went to the exact kernels alone, exact_groups of groups single restarts' line
  * searches were routed there while the rest of their tick stayed on the verify kernel; audit_*: with FR_VERIFY_AUDIT=1 every value a
  * bound-and-verify line search publishes (NDCG@k, full ranking, reciprocal rank) is recomputed by the exact kernels and
- * compared bit for bit -- values compared / values that differed). */
+ * compared bit for bit -- values compared / values that differed).
+ * fr_train_model_with sets the stats as train_model does.  After a LambdaMART request a "lambdamart" object is added (DESIGN.md
+ * section 11 lists its keys); fr_train_model_with adds to it, only with a validation dataset: "valid_dataset_queries",
+ * "valid_dataset_instances", "valid_ms" (the validation side's wall time, outside "update_ms"), "valid_measure" (per new tree),
+ * "best_iteration", "best_valid_measure", "stopped_early", "early_stopping_rounds" and, under DART, "valid_dart_cache_bytes" (that
+ * dataset's own leaf cache, next to "dart_cache_bytes"); only with an init model: "init_trees", "init_train_measure",
+ * "init_valid_measure" (with a validation dataset or validation_queries), "init_ms" (forming the initial scores); "trees",
+ * "train_measure" and "valid_measure" then count new trees, "best_iteration" counts the returned model's. */
 const void *fr_last_train_stats(void);
 /* What the process's last forest-scoring call ran, a test hook; JSON (free_str), no timing in it and
  * no launch behind it: {"path": "rank" | "lds" | "l2" (null before the first call), "cache_hit": the rank path launched from

@@ -24,6 +24,12 @@
                                                                # gradient-based one-side sampling (reports goss_ms and the lists' sizes)
     python tools/lmbench.py --shape 30k --trees 100 --grower histogram --symmetric --validation-rate 0.1
                                                                # symmetric trees (reports the levels that split per tree)
+    python tools/lmbench.py --shape 30k --trees 100 --grower histogram --valid-dataset-rate 0.1
+                                                               # a second generated dataset of a tenth of the queries as the validation
+                                                               # dataset (reports valid_ms per tree)
+    python tools/lmbench.py --shape 30k --trees 50 --grower histogram --init-trees 50
+                                                               # 50 trees first, then --trees more from that model (reports the
+                                                               # one-off cost of forming the initial scores)
 Every other parameter is the LambdaMART default (TrainRequest.lambdamart()).
 """
 import argparse
@@ -82,14 +88,28 @@ def device_run(args, X, y, qid):
     # upload and first touch of the device (not part of training)
     native.device_info(ds)
     t_ds = time.perf_counter() - t0
+    extra, valid_info, init_info = {}, None, None
+    if args.valid_dataset_rate > 0:  # a second dataset of its own: that share of the shape's queries and documents, another seed
+        n, d, q, gen_seed = SHAPES[args.shape]
+        Xv, yv, qv = gen_mslr_shaped(gen_seed + 1, max(1, int(n * args.valid_dataset_rate)), d, max(1, int(q * args.valid_dataset_rate)))
+        tv = time.perf_counter()
+        extra["valid"] = fr.CDataset.from_numpy(Xv, yv, qv)
+        native.device_info(extra["valid"])
+        valid_info = {"n": int(Xv.shape[0]), "queries": int(len(np.unique(qv))), "dataset_seconds": time.perf_counter() - tv}
+    if args.init_trees > 0:  # the model the timed training continues from (its own training is timed, kernels unprofiled)
+        first = req.clone()
+        first.params.num_trees = args.init_trees
+        ti = time.perf_counter()
+        extra["init_model"] = ds.train_model(first, **extra)
+        init_info = {"init_train_seconds": time.perf_counter() - ti}
     if args.warmup_trees > 0:  # an untimed training first: the device, its allocations and the bins are warm afterwards
         warm = req.clone()
         warm.params.num_trees = args.warmup_trees
-        ds.train_model(warm)
+        ds.train_model(warm, **extra)
     native.profile_enable(not args.no_kernel_profile)
     native.profile_reset()
     t1 = time.perf_counter()
-    model = ds.train_model(req)
+    model = ds.train_model(req, **extra) if extra else ds.train_model(req)
     wall = time.perf_counter() - t1
     st = native.last_train_stats()["lambdamart"]
     prof = native.profile_stats()
@@ -109,7 +129,14 @@ def device_run(args, X, y, qid):
     }
     if sample:  # (only when a rate is below 1, like the stats object)
         out["sample"] = sample
-    if "valid_measure" in st:  # (only with held-out queries, like the stats object)
+    if valid_info is not None:  # (only with a validation dataset, like the stats object)
+        out["valid_dataset"] = dict(valid_info, valid_ms_per_tree=st["valid_ms"] / T, update_ms_per_tree=st["update_ms"] / T,
+                                    **{k: st[k] for k in ("valid_dataset_queries", "valid_dataset_instances", "best_iteration",
+                                                          "best_valid_measure", "stopped_early", "early_stopping_rounds", "valid_measure")})
+    if init_info is not None:  # (only with an init model, like the stats object)
+        out["init_model"] = dict(init_info, **{k: st[k] for k in ("init_trees", "init_train_measure", "init_valid_measure", "init_ms") if k in st})
+        out["model_trees"] = len(model.to_dict()["Ensemble"]["models"])
+    if "validation_queries" in st:  # (only with held-out queries, like the stats object)
         out["validation"] = {k: st[k] for k in ("validation_queries", "training_queries", "best_iteration", "best_valid_measure",
                                                 "stopped_early", "early_stopping_rounds", "valid_measure", "train_measure")}
         out["model_trees"] = len(model.to_dict()["Ensemble"]["models"])
@@ -198,6 +225,9 @@ def parser():
     ap.add_argument("--feature-sampling-rate", type=float, default=1.0, help="share of the features every tree may split on")
     ap.add_argument("--seed", type=int, default=0, help="master seed of the per-tree samples")
     ap.add_argument("--validation-rate", type=float, default=0.0, help="share of the queries held out (hold_out_queries under --seed; 0: none)")
+    ap.add_argument("--valid-dataset-rate", type=float, default=0.0,
+                    help="a second generated dataset of this share of the shape's queries as the validation dataset (0: none)")
+    ap.add_argument("--init-trees", type=int, default=0, help="train this many trees first, then continue from them with --trees new ones (0: from nothing)")
     ap.add_argument("--early-stopping-rounds", type=int, default=0, help="stop this many trees after the held-out measure's best (0: never)")
     ap.add_argument("--split-gain", default="variance", choices=["variance", "newton"], help="the split criterion (newton: histogram grower only)")
     ap.add_argument("--lambda-l2", type=float, default=0.0, help="L2 term of the Newton gain and leaves")
