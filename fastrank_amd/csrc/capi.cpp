@@ -2091,6 +2091,10 @@ static const char* hist_tree_options_error(const FrHistTreeOptions& o) {
     if ((o.n_mono != 0 || o.goss) && !o.newton) return "monotone constraints and GOSS need the Newton gain";
     if (o.symmetric && (o.max_leaves != 0 || o.n_mono != 0 || o.goss))
         return "symmetric trees are grown level-wise (max_leaves = 0), without monotone constraints or GOSS";
+    for (double x : {o.lambda_l1, o.max_delta_step, o.path_smooth})
+        if (!(std::isfinite(x) && x >= 0.0) || (!o.newton && x != 0.0))
+            return "lambda_l1, max_delta_step and path_smooth must be finite and at least 0, and 0 without the Newton gain";
+    if (o.symmetric && o.path_smooth != 0.0) return "symmetric trees take no path_smooth";
     return nullptr;
 }
 
@@ -2112,6 +2116,7 @@ const CResult* fr_debug_hist_tree(const CDataset* dataset, const FrHistTreeOptio
         const std::vector<uint32_t>& feats = in.feats;
         fr::HistGrowOptions grow{o.split_candidates, o.max_depth, o.min_leaf_support, fr::HistNewton(), o.max_leaves, {}, o.symmetric != 0};
         if (o.newton) grow.newton = {true, o.lambda_l2, o.min_sum_hessian, o.min_split_gain};
+        grow.reg = {o.lambda_l1, o.max_delta_step, o.path_smooth};
         std::vector<uint32_t> sel;
         if (o.features) {
             std::vector<uint32_t> want(o.features, o.features + o.n_features);
@@ -2148,6 +2153,18 @@ const CResult* fr_debug_hist_tree(const CDataset* dataset, const FrHistTreeOptio
             if (clamped_leaves_out) *clamped_leaves_out = rep.clamped_leaves;
             return tree;
         });
+    });
+}
+
+// lambdamart_reg.hpp's output and term of one integer pair, without a device
+const void* fr_debug_hist_reg_term(int64_t q, int64_t w, uint32_t n, int32_t s_l, int32_t s_w, double lambda_l1, double lambda_l2,
+                                   double max_delta_step, double path_smooth, int32_t has_parent, double parent, double lo, double hi, double* v_out,
+                                   double* term_out) {
+    return status_call([&]() {
+        if (!v_out || !term_out) fr::fail_str("NULL pointer: fr_debug_hist_reg_term");
+        const fr::HistReg reg{lambda_l1, max_delta_step, path_smooth};
+        const fr::RegSide s = fr::reg_side((long long)q, (long long)w, n, s_l, s_w, lambda_l2, reg, has_parent ? &parent : nullptr, lo, hi);
+        *v_out = s.v, *term_out = s.term;
     });
 }
 

@@ -29,6 +29,7 @@
 //                           (both are templates over the objective: NDCG, MAP or MRR pair weights)
 //   kernels_xendcg.inc      lambda_grad_xe_kernel: LambdaMART's listwise objective, one wave per query, O(n) per query
 //   kernels_hist.inc        LambdaMART's histogram grower: one-byte bins, int64 fixed-point gradients, per-node histograms
+//   kernels_histreg.inc     the histogram grower's scan kernels under lambda_l1 / max_delta_step / path_smooth
 //   kernels_goss.inc        LambdaMART's gradient-based one-side sampling: an on-device radix select of the n-th largest |lambda|,
 //                           the kept documents' list, amplified fixed-point gradients
 //   kernels_dart.inc        LambdaMART's DART boosting: the u16 leaf cache and dart_rescore_kernel, which re-forms the scores
@@ -42,7 +43,7 @@
 //     train_rf.inc            the launchers of kernels_rf.inc
 //     train_lambda.inc        the launchers of kernels_lambda.inc and kernels_xendcg.inc
 //     train_dart.inc          the launchers of kernels_dart.inc
-//     train_hist.inc          the launchers of kernels_hist.inc, level-wise and leaf-wise, and of kernels_goss.inc
+//     train_hist.inc          the launchers of kernels_hist.inc and kernels_histreg.inc, level-wise and leaf-wise, and of kernels_goss.inc
 #include "device.hpp"
 
 #include <hip/hip_runtime.h>
@@ -88,6 +89,7 @@ namespace frdev {
 #include "kernels_lambda.inc"
 #include "kernels_xendcg.inc"
 #include "kernels_hist.inc"
+#include "kernels_histreg.inc"
 #include "kernels_goss.inc"
 #include "kernels_dart.inc"
 #include "device_dataset.inc"

@@ -343,7 +343,17 @@ class DeviceDataset {
     // the symmetric pair only (elsewhere the host applies it).  monotone ("Monotone constraints"; Newton gain only): the two
     // sides' outputs are clamped to the node's interval, a clamped side's term is (2 G) v - ((H + lambda_l2) v) v, and the
     // order vL <= vR (sign +1) / vL >= vR (sign -1) is among a candidate's conditions.
-    struct HistSearch { uint32_t min_leaf; bool newton; int s_l, s_w; double lambda_l2, min_sum_hessian, min_split_gain; bool monotone; };
+    // lambda_l1 / max_delta_step / path_smooth ("Leaf regularisation"; Newton gain only; all 0: off): a side's output is the
+    // soft-thresholded gradient sum over H + lambda_l2, capped, pulled toward the parent's output and clamped, and a moved
+    // side's term is the clamped one's; with any of them set the scan kernels are those of kernels_histreg.inc, with or
+    // without monotone signs, and a node's record is a HistRegNode.
+    struct HistSearch {
+        uint32_t min_leaf; bool newton; int s_l, s_w; double lambda_l2, min_sum_hessian, min_split_gain; bool monotone;
+        double lambda_l1 = 0.0, max_delta_step = 0.0, path_smooth = 0.0;
+        bool reg() const { return lambda_l1 != 0.0 || max_delta_step != 0.0 || path_smooth != 0.0; }
+    };
+    // a node's interval, its parent's output and whether it has one ("Leaf regularisation")
+    struct HistRegNode { double lo, hi, parent; uint32_t has_parent, pad; };
     // A candidate (valid = 0: none): bins 0..edge go left, nl instances of sums (ql, wl); (qtot, wtot): the node's.  Under the
     // variance criterion wl = wtot = 0.  fi: the feature's index among the tree's, from the leaf-wise calls only (else 0).
     struct HistCand { double imp; long long ql, qtot, wl, wtot; uint32_t edge, nl, valid, fi; };
@@ -377,9 +387,10 @@ class DeviceDataset {
     // index list = the sample's root list (0..n-1 without one); the level holds the root's histogram in slot 0.  newton: with sum W
     bool hist_root(bool newton, std::string* err);
     // One level's search.  best[a * features + slot]: node a's last-maximum candidate of that feature (the level was made
-    // with how.newton); bounds: nullptr unless how.monotone, then node a's interval is (*bounds)[a]
+    // with how.newton); bounds: nullptr unless how.monotone, then node a's interval is (*bounds)[a]; reg: nullptr unless
+    // how.reg(), then node a's record is (*reg)[a] and bounds is not read (signs must be set, all zero without a constraint)
     bool hist_search(const std::vector<HistNode>& nodes, const HistSearch& how, const std::vector<HistBounds>* bounds,
-                     std::vector<HistCand>* best, std::string* err);
+                     std::vector<HistCand>* best, std::string* err, const std::vector<HistRegNode>* reg = nullptr);
     // signs[features] in {-1, 0, +1}, one per row of the bin matrix, kept until the next call or the next bins
     bool hist_monotone(const int* signs, size_t features, std::string* err);
     // Symmetric trees ("Symmetric trees").  hist_search_symmetric: best[f] = the last-maximum candidate of feature f of the
@@ -405,8 +416,9 @@ class DeviceDataset {
     // histogram is built into small_slot; a searched larger child is derived in place in parent_slot (parent - smaller) and a
     // searched child is scanned.  pick[0]: the lhs's record, pick[1]: the rhs's (written for the searched ones only).
     static constexpr uint32_t HIST_NO_SLOT = 0xffffffffu;
-    // (bounds[0] / bounds[1]: the lhs's / rhs's interval, read only when how.monotone)
-    struct HistLeafStep { HistSplit split; uint32_t parent_slot, small_slot; bool search_lhs, search_rhs; HistBounds bounds[2] = {}; };
+    // (bounds[0] / bounds[1]: the lhs's / rhs's interval, read only when how.monotone or how.reg(); parent_out: the output of
+    // the node being split, both children's parent output, read only when how.reg())
+    struct HistLeafStep { HistSplit split; uint32_t parent_slot, small_slot; bool search_lhs, search_rhs; HistBounds bounds[2] = {}; double parent_out = 0.0; };
     bool hist_leaf_step(const HistLeafStep& step, const HistSearch& how, HistCand pick[2], std::string* err);
 
     // --- model explanation (explain.hip, a translation unit of its own) ---------

@@ -378,6 +378,7 @@ struct DeviceDataset::Impl : DatasetDesc {
         DevBuf<int> mono;
         uint32_t mono_F = 0;
         DevBuf<HistBoundsDev> bounds;
+        DevBuf<HistRegNodeDev> regn;  // leaf regularisation: the level's records (interval, parent output)
         // host staging of the tables above: overwritten only after the stream was waited for
         std::vector<HistItemDev> items_h, items_bh, nodes_h;
         std::vector<HistSplitDev> splits_h;
@@ -393,7 +394,7 @@ struct DeviceDataset::Impl : DatasetDesc {
     bool hist_stage_nodes(const std::vector<DeviceDataset::HistNode>& nodes, bool newton, std::string* err);
     bool hist_root_build(uint32_t* cnt, unsigned long long* sum, unsigned long long* wsum, std::string* err);  // the root's index list and histogram
     bool hist_leaf_scan(const HistLeafKids& kids, uint32_t count, const DeviceDataset::HistSearch& how, DeviceDataset::HistCand* out,
-                        std::string* err, const HistLeafBoundsDev* bounds = nullptr);
+                        std::string* err, const HistLeafBoundsDev* bounds = nullptr, const HistLeafRegDev* reg = nullptr);
     DevBuf<uint64_t> forest;
     DevBuf<uint32_t> tree_fdesc;  // tree_ensemble_rank_kernel: per-feature descriptors, Eytzinger threshold tables
     DevBuf<float> tree_tables;

@@ -46,6 +46,10 @@
 // symmetric_trees (histogram grower, level-wise, no monotone constraints; DESIGN.md section 11, "Symmetric trees"): every node
 // of a level splits on the one (feature, threshold) with the largest importance summed over the level's open nodes; a node
 // that cannot split under it becomes a leaf.  The trees are ordinary DecisionTrees; everything upstream of the grower composes.
+// lambda_l1 / max_delta_step / path_smooth (histogram grower under the Newton gain only; DESIGN.md section 11, "Leaf
+// regularisation"; lambdamart_reg.hpp, kernels_histreg.inc): the gradient sum is soft-thresholded before it becomes an output
+// or a gain, an output's magnitude is capped, a child's output is pulled toward its parent's; every node carries its output,
+// and the scan kernels are the regularised ones.  path_smooth is refused with symmetric_trees.
 // A validation dataset B ("Validation dataset"): a second view, scored tree by tree on its own device form
 // (score slot, accumulator, metric pass, mean; under DART a leaf cache of its own); no tree reads it.  Its plain mean over
 // all of its queries is the held-out measure the stopping rule reads.
@@ -111,7 +115,11 @@ struct LambdaMARTParams {
     double goss_top_rate = 0.0, goss_other_rate = 0.1;
     // symmetric (oblivious) trees (optional key, written only when set): every node of a level splits on the same candidate
     bool symmetric_trees = false;
+    // leaf regularisation (optional keys, not written at their defaults; read only under "newton"): the soft threshold of the
+    // gradient sum, the cap of an output's magnitude (0 = none), the pull of a child's output toward its parent's (0 = none)
+    double lambda_l1 = 0.0, max_delta_step = 0.0, path_smooth = 0.0;
 
+    bool leaf_reg() const { return lambda_l1 != 0.0 || max_delta_step != 0.0 || path_smooth != 0.0; }
     bool goss() const { return goss_top_rate > 0.0; }
     bool dart() const { return drop_rate > 0.0; }
     bool xendcg() const { return objective == frdev::LM_OBJECTIVE_XENDCG; }
@@ -137,7 +145,7 @@ struct LambdaMARTParams {
     // (monotone: the signs resolved against the ascending feature list, lambdamart_monotone_signs; empty without the key)
     HistGrowOptions hist_options(std::vector<int> monotone = {}) const {
         return {split_candidates, max_depth, min_leaf_support, HistNewton{newton, lambda_l2, min_sum_hessian, min_split_gain}, max_leaves,
-                std::move(monotone), symmetric_trees};
+                std::move(monotone), symmetric_trees, HistReg{lambda_l1, max_delta_step, path_smooth}};
     }
     [[noreturn]] static void invalid(const std::string& what) {
         fail_raw("Error(\"invalid value: " + what + "\", line: 0, column: 0)");
@@ -212,6 +220,9 @@ struct LambdaMARTParams {
         if (const Value* r = v.find("goss_top_rate")) p.goss_top_rate = json_f64(*r, "goss_top_rate");
         if (const Value* r = v.find("goss_other_rate")) p.goss_other_rate = json_f64(*r, "goss_other_rate");
         if (const Value* r = v.find("symmetric_trees")) p.symmetric_trees = json_bool(*r, "symmetric_trees");
+        if (const Value* r = v.find("lambda_l1")) p.lambda_l1 = json_f64(*r, "lambda_l1");
+        if (const Value* r = v.find("max_delta_step")) p.max_delta_step = json_f64(*r, "max_delta_step");
+        if (const Value* r = v.find("path_smooth")) p.path_smooth = json_f64(*r, "path_smooth");
         if (p.num_trees < 1) invalid("num_trees must be at least 1");
         if (!(std::isfinite(p.learning_rate) && p.learning_rate > 0.0)) invalid("learning_rate must be finite and greater than 0");
         if (p.max_depth < 1) invalid("max_depth must be at least 1");
@@ -257,6 +268,14 @@ struct LambdaMARTParams {
             invalid("symmetric_trees cannot be combined with max_leaves (a symmetric tree is grown level by level)");
         if (p.symmetric_trees && !p.monotone_constraints.empty())
             invalid("symmetric_trees cannot be combined with monotone_constraints (a level's one split cannot honour every node's interval)");
+        const std::pair<const char*, double> leaf_numbers[] = {{"lambda_l1", p.lambda_l1}, {"max_delta_step", p.max_delta_step}, {"path_smooth", p.path_smooth}};
+        for (const auto& kv : leaf_numbers) {
+            if (!(std::isfinite(kv.second) && kv.second >= 0.0)) invalid(std::string(kv.first) + " must be finite and at least 0");
+            if (kv.second != 0.0 && !p.histogram) invalid(std::string(kv.first) + " needs grower: \"histogram\" (the exact grower has no hessian sums)");
+            if (kv.second != 0.0 && !p.newton) invalid(std::string(kv.first) + " needs split_gain: \"newton\"");
+        }
+        if (p.path_smooth != 0.0 && p.symmetric_trees)
+            invalid("path_smooth cannot be combined with symmetric_trees (a level's one split is priced over every node, each with a parent of its own)");
         p.check_objective_options();
         return p;
     }
@@ -298,6 +317,9 @@ struct LambdaMARTParams {
         if (goss_top_rate != 0.0) o.set("goss_top_rate", Value::number(goss_top_rate));
         if (goss_other_rate != 0.1) o.set("goss_other_rate", Value::number(goss_other_rate));
         if (symmetric_trees) o.set("symmetric_trees", Value::boolean(true));
+        if (lambda_l1 != 0.0) o.set("lambda_l1", Value::number(lambda_l1));
+        if (max_delta_step != 0.0) o.set("max_delta_step", Value::number(max_delta_step));
+        if (path_smooth != 0.0) o.set("path_smooth", Value::number(path_smooth));
         return o;
     }
 };
@@ -573,6 +595,11 @@ struct LambdaMARTStats {
             Value a = Value::array();
             for (uint32_t x : levels) a.push(Value::uint(x));
             o.set("levels", std::move(a));
+        }
+        if (r.leaf_reg()) {
+            o.set("lambda_l1", Value::number(r.lambda_l1));
+            o.set("max_delta_step", Value::number(r.max_delta_step));
+            o.set("path_smooth", Value::number(r.path_smooth));
         }
         return o;
     }

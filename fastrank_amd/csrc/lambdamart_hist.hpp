@@ -23,6 +23,11 @@
 // one candidate, the last maximum of the level importance (hist_scan_sym_kernel: one record per feature); a second launch
 // (hist_sym_apply_kernel) returns every node's own record under that winner, and the level loop goes on as ever: a node that
 // does not split under the winner closes into a leaf.  Without the option the loop launches what it launched before.
+// leaf regularisation ("Leaf regularisation"; lambdamart_reg.hpp, kernels_histreg.inc; Newton gain only):
+// lambda_l1, max_delta_step, path_smooth move a node's output off G / (H + lambda_l2); every node then carries its output next to
+// its interval, the device's candidates are those of the regularised scan kernels (with or without monotone signs), and the
+// host prices a node's own term, the children's outputs and intervals and the leaves by lambdamart_reg.hpp.  With all three at
+// 0 nothing here differs.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -30,6 +35,7 @@
 
 #include "host.hpp"
 #include "lambdamart_goss.hpp"
+#include "lambdamart_reg.hpp"
 
 namespace fr {
 
@@ -54,6 +60,7 @@ struct HistGrowOptions {
     uint32_t max_leaves = 0;
     std::vector<int> monotone;
     bool symmetric = false;
+    HistReg reg;  // leaf regularisation (all 0: off; a non-zero one needs the Newton gain)
 };
 
 // what grow() reports of the tree it made, next to the tree
@@ -73,7 +80,7 @@ class HistGrower {
 
   public:
     HistGrower(Dev& dev, std::vector<uint32_t> feats, const HistGrowOptions& opt)
-        : dev_(dev), feats_(std::move(feats)), k_(opt.k), max_depth_(opt.max_depth), min_leaf_(opt.min_leaf), newton_(opt.newton), max_leaves_(opt.max_leaves), symmetric_(opt.symmetric) {
+        : dev_(dev), feats_(std::move(feats)), k_(opt.k), max_depth_(opt.max_depth), min_leaf_(opt.min_leaf), newton_(opt.newton), max_leaves_(opt.max_leaves), symmetric_(opt.symmetric), reg_(opt.reg), reg_on_(opt.reg.on()) {
         for (int c : opt.monotone) mono_on_ = mono_on_ || c != 0;
         if (symmetric_ && max_leaves_ != 0) fail_str("LambdaMART histogram grower: symmetric trees are grown level by level (max_leaves must be 0)");
         if (symmetric_ && mono_on_) fail_str("LambdaMART histogram grower: symmetric trees take no monotone constraints");
@@ -81,6 +88,11 @@ class HistGrower {
             if (!newton_.on) fail_str("LambdaMART histogram grower: monotone constraints need the Newton gain");
             if (opt.monotone.size() != feats_.size()) fail_str("LambdaMART histogram grower: one monotone sign per feature is needed");
             mono_ = opt.monotone;
+        }
+        if (reg_on_) {
+            if (!newton_.on) fail_str("LambdaMART histogram grower: lambda_l1, max_delta_step and path_smooth need the Newton gain");
+            if (symmetric_ && reg_.path_smooth != 0.0) fail_str("LambdaMART histogram grower: symmetric trees take no path_smooth");
+            if (!mono_on_) mono_.assign(feats_.size(), 0);  // (the regularised scan kernels read a sign per feature)
         }
     }
     ~HistGrower() { dev_.hist_end(); }
@@ -91,7 +103,7 @@ class HistGrower {
         bool built = false;
         if (!dev_.hist_bins(positions.data(), positions.size(), feats_, k_, &built, &err)) fail_str(err);
         if (!dev_.hist_edges(&edges_, &nedges_, &err)) fail_str(err);
-        if (mono_on_ && !dev_.hist_monotone(mono_.data(), mono_.size(), &err)) fail_str(err);
+        if ((mono_on_ || reg_on_) && !dev_.hist_monotone(mono_.data(), mono_.size(), &err)) fail_str(err);
         n_ = n_sample_ = n_full_ = (uint32_t)positions.size();
         sel_.clear();
         return built;
@@ -138,7 +150,8 @@ class HistGrower {
             n_ = rep.goss_instances;
             rep.goss_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         }
-        how_ = {min_leaf_, newton_.on, 0, 0, newton_.lambda_l2, newton_.min_sum_hessian, newton_.min_split_gain, mono_on_};
+        how_ = {min_leaf_, newton_.on, 0, 0, newton_.lambda_l2, newton_.min_sum_hessian, newton_.min_split_gain, mono_on_,
+                reg_.lambda_l1, reg_.max_delta_step, reg_.path_smooth};
         if (!dev_.hist_quantise(lam_list, wt_list, &how_.s_l, &how_.s_w, &all_zero, &err)) fail_str(err);
         auto root = std::make_shared<TreeNode>();
         if (!all_zero) {  // (else one leaf of value 0.0)
@@ -159,21 +172,31 @@ class HistGrower {
     struct Open {
         TreeNode* node;
         uint32_t slot, begin, end, depth;
-        Dev::HistBounds bd;  // (read only under monotone constraints)
+        Dev::HistBounds bd;  // (read only under monotone constraints and leaf regularisation)
         uint32_t index = 0;
         double gain = 0.0;
         Dev::HistCand pick = {};
+        // leaf regularisation: the node's parent's output (has_parent = false: the root) and its own, set by may_split
+        double parent_out = 0.0;
+        bool has_parent = false;
+        double out = 0.0;
     };
-    // the tree's leaves in the order they were closed: node, stretch of the index list (slot: its number), interval
+    // the tree's leaves in the order they were closed: node, stretch of the index list (slot: its number), interval, and
+    // (leaf regularisation) its parent's output
     struct Leaves {
         std::vector<TreeNode*> nodes;
         std::vector<Dev::HistNode> stretches;
         std::vector<Dev::HistBounds> bounds;
-        void close(TreeNode* t, uint32_t b, uint32_t e, const Dev::HistBounds& bd) {
+        std::vector<double> parent_out;
+        std::vector<unsigned char> has_parent;
+        void close(TreeNode* t, uint32_t b, uint32_t e, const Dev::HistBounds& bd, double parent = 0.0, bool with_parent = false) {
             nodes.push_back(t);
             stretches.push_back({(uint32_t)stretches.size(), b, e});
             bounds.push_back(bd);
+            parent_out.push_back(parent);
+            has_parent.push_back(with_parent ? 1 : 0);
         }
+        void close(const Open& o) { close(o.node, o.begin, o.end, o.bd, o.parent_out, o.has_parent); }
     };
 
     // Level-wise growth.  false: the root was not searched, and the device's index list was not made.
@@ -188,12 +211,13 @@ class HistGrower {
         const size_t F = features();
         std::vector<Dev::HistNode> nodes, builds;
         std::vector<Dev::HistBounds> node_bounds;
+        std::vector<Dev::HistRegNode> node_regs;
         std::vector<Dev::HistCand> best;
         std::vector<Dev::HistSymBest> level;
         std::vector<Dev::HistSplit> splits;
         std::vector<Dev::HistSub> subs;
         while (!open.empty()) {
-            nodes.clear(), builds.clear(), splits.clear(), subs.clear(), next.clear(), node_bounds.clear();
+            nodes.clear(), builds.clear(), splits.clear(), subs.clear(), next.clear(), node_bounds.clear(), node_regs.clear();
             for (const Open& o : open) nodes.push_back({o.slot, o.begin, o.end});
             size_t sym_f = 0;  // (symmetric trees) the level's winning feature; best[a]: node a's record under the winner
             if (symmetric_) {
@@ -210,13 +234,16 @@ class HistGrower {
                     (*levels)++;
                 }
             } else {
-                if (mono_on_)
+                if (reg_on_)
+                    for (const Open& o : open) node_regs.push_back({o.bd.lo, o.bd.hi, o.parent_out, o.has_parent ? 1u : 0u, 0u});
+                else if (mono_on_)
                     for (const Open& o : open) node_bounds.push_back(o.bd);
-                if (!dev_.hist_search(nodes, how_, mono_on_ ? &node_bounds : nullptr, &best, &err)) fail_str(err);
+                if (!dev_.hist_search(nodes, how_, mono_on_ && !reg_on_ ? &node_bounds : nullptr, &best, &err, reg_on_ ? &node_regs : nullptr))
+                    fail_str(err);
             }
             uint32_t next_slots = 0;
             for (size_t a = 0; a < open.size(); a++) {
-                const Open& o = open[a];
+                Open& o = open[a];
                 const uint32_t n = o.end - o.begin;
                 const Dev::HistCand* w = nullptr;
                 size_t wf = 0;
@@ -228,21 +255,22 @@ class HistGrower {
                         if (b.valid && (w == nullptr || b.imp >= w->imp)) w = &b, wf = fi;
                     }
                     double gain = 0.0;  // the node's totals (Qnode, Wnode) arrive with every record of the node
-                    if (w != nullptr && !may_split(*w, n, o.bd, &gain)) w = nullptr;
+                    if (w != nullptr && !may_split(*w, n, &o, &gain)) w = nullptr;
                 }
                 if (w == nullptr) {
-                    lv->close(o.node, o.begin, o.end, o.bd);
+                    lv->close(o);
                     continue;
                 }
+                if (symmetric_ && reg_on_) o.out = node_output(*w, n, o);  // (may_split was not asked)
                 Dev::HistBounds bl = o.bd, br = o.bd;
-                if (mono_on_) child_bounds(o.bd, mono_[full(wf)], *w, &bl, &br);
+                if (mono_on_) child_bounds(o, n, mono_[full(wf)], *w, &bl, &br);
                 const uint32_t nl = w->nl, nr = n - nl;
                 const size_t ws = split_node(o.node, wf, w->edge, n, nl);
                 splits.push_back({o.begin, o.end, (uint32_t)ws, w->edge, nl});  // (the bin matrix's row)
                 const uint32_t mid = o.begin + nl;
                 const bool el = enterable(nl, o.depth + 1), er = enterable(nr, o.depth + 1);
-                if (!el) lv->close(o.node->lhs.get(), o.begin, mid, bl);
-                if (!er) lv->close(o.node->rhs.get(), mid, o.end, br);
+                if (!el) lv->close(o.node->lhs.get(), o.begin, mid, bl, o.out, true);
+                if (!er) lv->close(o.node->rhs.get(), mid, o.end, br, o.out, true);
                 if (!el && !er) continue;
                 const bool left_small = nl <= nr;
                 const uint32_t small_slot = next_slots++;
@@ -252,8 +280,8 @@ class HistGrower {
                     large_slot = next_slots++;
                     subs.push_back({o.slot, small_slot, large_slot});
                 }
-                if (el) next.push_back({o.node->lhs.get(), left_small ? small_slot : large_slot, o.begin, mid, o.depth + 1, bl});
-                if (er) next.push_back({o.node->rhs.get(), left_small ? large_slot : small_slot, mid, o.end, o.depth + 1, br});
+                if (el) next.push_back({o.node->lhs.get(), left_small ? small_slot : large_slot, o.begin, mid, o.depth + 1, bl, 0u, 0.0, {}, o.out, true});
+                if (er) next.push_back({o.node->rhs.get(), left_small ? large_slot : small_slot, mid, o.end, o.depth + 1, br, 0u, 0.0, {}, o.out, true});
             }
             if (!dev_.hist_split(splits, builds, subs, next_slots, newton_.on, &err)) fail_str(err);
             open.swap(next);
@@ -280,10 +308,10 @@ class HistGrower {
         for (uint32_t s = slots; s-- > 1;) free_slots.push_back(s);  // (slot 0: the root's)
         // a searched leaf with its record: open with its gain, or closed and its slot free again
         auto consider = [&](Open o) {
-            if (may_split(o.pick, o.end - o.begin, o.bd, &o.gain)) {
+            if (may_split(o.pick, o.end - o.begin, &o, &o.gain)) {
                 open.push_back(o);
             } else {
-                lv->close(o.node, o.begin, o.end, o.bd);
+                lv->close(o);
                 free_slots.push_back(o.slot);
             }
         };
@@ -306,7 +334,8 @@ class HistGrower {
             const bool left_small = nl <= nr;
             Dev::HistLeafStep step{{o.begin, o.end, (uint32_t)ws, o.pick.edge, nl}, o.slot, Dev::HIST_NO_SLOT, el, er};
             step.bounds[0] = step.bounds[1] = o.bd;
-            if (mono_on_) child_bounds(o.bd, mono_[ws], o.pick, &step.bounds[0], &step.bounds[1]);
+            step.parent_out = o.out;
+            if (mono_on_) child_bounds(o, n, mono_[ws], o.pick, &step.bounds[0], &step.bounds[1]);
             if (el || er) {
                 if (free_slots.empty()) fail_str("LambdaMART histogram grower: internal error: the histogram pool is exhausted");
                 step.small_slot = free_slots.back();
@@ -314,16 +343,16 @@ class HistGrower {
             }
             if (!dev_.hist_leaf_step(step, how_, pick, &err)) fail_str(err);
             const uint32_t slot_l = left_small ? step.small_slot : o.slot, slot_r = left_small ? o.slot : step.small_slot;
-            if (el) consider({o.node->lhs.get(), slot_l, o.begin, mid, o.depth + 1, step.bounds[0], il, 0.0, pick[0]});
-            else lv->close(o.node->lhs.get(), o.begin, mid, step.bounds[0]);
-            if (er) consider({o.node->rhs.get(), slot_r, mid, o.end, o.depth + 1, step.bounds[1], ir, 0.0, pick[1]});
-            else lv->close(o.node->rhs.get(), mid, o.end, step.bounds[1]);
+            if (el) consider({o.node->lhs.get(), slot_l, o.begin, mid, o.depth + 1, step.bounds[0], il, 0.0, pick[0], o.out, true});
+            else lv->close(o.node->lhs.get(), o.begin, mid, step.bounds[0], o.out, true);
+            if (er) consider({o.node->rhs.get(), slot_r, mid, o.end, o.depth + 1, step.bounds[1], ir, 0.0, pick[1], o.out, true});
+            else lv->close(o.node->rhs.get(), mid, o.end, step.bounds[1], o.out, true);
             // a slot whose child was not searched holds nothing that is read again
             if (!el && (el || er)) free_slots.push_back(slot_l);
             if (!er && (el || er)) free_slots.push_back(slot_r);
             if (!el && !er) free_slots.push_back(o.slot);
         }
-        for (const Open& o : open) lv->close(o.node, o.begin, o.end, o.bd);
+        for (const Open& o : open) lv->close(o);
         pool_bytes_ = std::max(pool_bytes_, (uint64_t)slots * features() * k_ * (newton_.on ? 20u : 12u));
         return true;
     }
@@ -350,10 +379,16 @@ class HistGrower {
     // its own node (n instances, interval bd); returns whether the node may split on it.  Newton gain: imp less the node's
     // own term (Qnode, Wnode; under monotone constraints the clamped one), which must exceed min_split_gain.  Variance:
     // imp less Qnode^2 / n, for ranking the open leaves only (rounding may leave it slightly below 0): any valid record splits.
-    bool may_split(const Dev::HistCand& b, uint32_t n, const Dev::HistBounds& bd, double* gain) const {
+    // Leaf regularisation: the node's own term is the one at its carried output, which is left in o->out.
+    bool may_split(const Dev::HistCand& b, uint32_t n, Open* o, double* gain) const {
         if (!b.valid) return false;
+        if (newton_.on && reg_on_) {
+            o->out = node_output(b, n, *o);
+            *gain = b.imp - reg_own_term(b.qtot, b.wtot, how_.s_l, how_.s_w, newton_.lambda_l2, reg_, o->out);
+            return *gain > newton_.min_split_gain;
+        }
         if (newton_.on) {
-            *gain = b.imp - (mono_on_ ? monotone_term(b.qtot, b.wtot, bd) : newton_term(b.qtot, b.wtot));
+            *gain = b.imp - (mono_on_ ? monotone_term(b.qtot, b.wtot, o->bd) : newton_term(b.qtot, b.wtot));
             return *gain > newton_.min_split_gain;
         }
         const double sn = (double)b.qtot;
@@ -381,13 +416,25 @@ class HistGrower {
         if (v_out) *v_out = v;
         return v == out ? (g * g) / den : (2.0 * g) * v - (den * v) * v;
     }
-    // the children's intervals after the split b of a node on a feature of sign c: mid = (vL + vR) 0.5 cuts the node's interval
-    void child_bounds(const Dev::HistBounds& bd, int c, const Dev::HistCand& b, Dev::HistBounds* lhs, Dev::HistBounds* rhs) const {
+    // Leaf regularisation.  The output node o (n instances, totals in record b) carries: its own v, the parent's pull included
+    // (for the root, which has no parent, without it).  The children inherit it as their parent's output.
+    double node_output(const Dev::HistCand& b, uint32_t n, const Open& o) const {
+        return reg_side(b.qtot, b.wtot, n, how_.s_l, how_.s_w, newton_.lambda_l2, reg_, o.has_parent ? &o.parent_out : nullptr, o.bd.lo, o.bd.hi).v;
+    }
+    // the children's intervals after the split b of node o (n instances) on a feature of sign c: mid = (vL + vR) 0.5 cuts the
+    // node's interval
+    void child_bounds(const Open& o, uint32_t n, int c, const Dev::HistCand& b, Dev::HistBounds* lhs, Dev::HistBounds* rhs) const {
+        const Dev::HistBounds& bd = o.bd;
         *lhs = *rhs = bd;
         if (c == 0) return;
         double vl = 0.0, vr = 0.0;
-        (void)monotone_term(b.ql, b.wl, bd, &vl);
-        (void)monotone_term(b.qtot - b.ql, b.wtot - b.wl, bd, &vr);
+        if (reg_on_) {  // (both sides are pulled toward the splitting node's carried output)
+            vl = reg_side(b.ql, b.wl, b.nl, how_.s_l, how_.s_w, newton_.lambda_l2, reg_, &o.out, bd.lo, bd.hi).v;
+            vr = reg_side(b.qtot - b.ql, b.wtot - b.wl, n - b.nl, how_.s_l, how_.s_w, newton_.lambda_l2, reg_, &o.out, bd.lo, bd.hi).v;
+        } else {
+            (void)monotone_term(b.ql, b.wl, bd, &vl);
+            (void)monotone_term(b.qtot - b.ql, b.wtot - b.wl, bd, &vr);
+        }
         const double mid = (vl + vr) * 0.5;
         if (c > 0) lhs->hi = mid, rhs->lo = mid;
         else lhs->lo = mid, rhs->hi = mid;
@@ -404,7 +451,14 @@ class HistGrower {
         if (!dev_.hist_leaf_sums(lv.stretches, &qw, &err)) fail_str(err);
         for (size_t i = 0; i < lv.nodes.size(); i++) {
             const long long q = qw[i * 2], w = qw[i * 2 + 1];
-            if (newton_.on) {
+            if (newton_.on && reg_on_) {
+                const uint32_t n = lv.stretches[i].end - lv.stretches[i].begin;
+                const double* parent = lv.has_parent[i] ? &lv.parent_out[i] : nullptr;
+                const Dev::HistBounds line = whole_line();
+                const double v = reg_side(q, w, n, how_.s_l, how_.s_w, newton_.lambda_l2, reg_, parent, lv.bounds[i].lo, lv.bounds[i].hi).v;
+                if (mono_on_ && v != reg_side(q, w, n, how_.s_l, how_.s_w, newton_.lambda_l2, reg_, parent, line.lo, line.hi).v) rep->clamped_leaves++;
+                lv.nodes[i]->value = v;
+            } else if (newton_.on) {
                 const double den = std::ldexp((double)w, -how_.s_w) + newton_.lambda_l2;
                 const double out = den != 0.0 ? std::ldexp((double)q, -how_.s_l) / den : 0.0;
                 const double v = mono_on_ ? clamp(out, lv.bounds[i]) : out;
@@ -436,6 +490,8 @@ class HistGrower {
     bool mono_on_ = false;                                     // some monotone sign is not 0
     std::vector<int> mono_;                                    // (then) the signs, by entry of feats_
     bool symmetric_ = false;                                   // every node of a level splits on one candidate
+    HistReg reg_;                                              // leaf regularisation's three numbers
+    bool reg_on_ = false;                                      // one of them is not 0
     std::vector<uint32_t> sel_;                                // the tree's features as slots of the bins (empty: all)
     std::vector<float> edges_;
     std::vector<uint32_t> nedges_;

@@ -420,9 +420,15 @@ bool DeviceDataset::hist_root(bool newton, std::string* err) {
     return m.hist_root_build(h.cnt.p, h.sum.p, newton ? h.wsum.p : nullptr, err);
 }
 
+// the numbers of a regularised search as its kernels take them
+static HistRegDev hist_reg_numbers(const DeviceDataset::HistSearch& how) {
+    return {how.lambda_l1, how.lambda_l2, how.max_delta_step, how.path_smooth, how.min_sum_hessian};
+}
+
 bool DeviceDataset::hist_search(const std::vector<HistNode>& nodes, const HistSearch& how, const std::vector<HistBounds>* bounds,
-                                std::vector<HistCand>* best, std::string* err) {
+                                std::vector<HistCand>* best, std::string* err, const std::vector<HistRegNode>* reg) {
     static_assert(sizeof(HistBounds) == sizeof(HistBoundsDev), "host and device records differ");
+    static_assert(sizeof(HistRegNode) == sizeof(HistRegNodeDev), "host and device records differ");
     Impl& m = *impl_;
     std::lock_guard<std::mutex> lk(m.mu);
     if (!m.bind(err)) return false;
@@ -430,7 +436,10 @@ bool DeviceDataset::hist_search(const std::vector<HistNode>& nodes, const HistSe
     const size_t A = nodes.size();
     best->assign(A * h.Ft, HistCand{});
     if (A == 0) return true;
-    if (how.monotone) {
+    if (how.reg()) {
+        if (!how.newton || reg == nullptr || reg->size() != A) return hist_fail(err, "internal error: one regularisation record per node is needed");
+        if (h.mono_F == 0 || h.mono_F != h.F) return hist_fail(err, "internal error: no monotone signs set for these bins");
+    } else if (how.monotone) {
         if (!how.newton || bounds == nullptr || bounds->size() != A) return hist_fail(err, "internal error: one interval per node is needed");
         if (h.mono_F == 0 || h.mono_F != h.F) return hist_fail(err, "internal error: no monotone signs set for these bins");
     }
@@ -453,7 +462,13 @@ bool DeviceDataset::hist_search(const std::vector<HistNode>& nodes, const HistSe
         return true;
     }
     if (!h.best_n.ensure(A * h.Ft, err)) return false;
-    if (how.monotone) {
+    if (how.reg()) {
+        if (!h.regn.ensure(A, err)) return false;
+        FR_HIP(hipMemcpyAsync(h.regn.p, reg->data(), A * sizeof(HistRegNodeDev), hipMemcpyHostToDevice, m.stream));
+        ProfScope ps("hist_scan_reg_kernel", m.stream);
+        hist_scan_reg_kernel<<<grid, 64, 0, m.stream>>>(h.nodes.p, h.regn.p, h.Ft, h.k, h.nedges.p, h.mono.p, fsel, h.cnt.p, h.sum.p, h.wsum.p, how.min_leaf,
+                                                        how.s_l, how.s_w, hist_reg_numbers(how), h.best_n.p);
+    } else if (how.monotone) {
         if (!h.bounds.ensure(A, err)) return false;
         FR_HIP(hipMemcpyAsync(h.bounds.p, bounds->data(), A * sizeof(HistBoundsDev), hipMemcpyHostToDevice, m.stream));
         ProfScope ps("hist_scan_monotone_kernel", m.stream);
@@ -465,7 +480,7 @@ bool DeviceDataset::hist_search(const std::vector<HistNode>& nodes, const HistSe
                                                            how.s_w, how.lambda_l2, how.min_sum_hessian, h.best_n.p);
     }
     FR_HIP(hipGetLastError());
-    return hist_fetch(best, h.best_n, m.stream, err);  // (*bounds is the caller's, read by the copy above until this has waited)
+    return hist_fetch(best, h.best_n, m.stream, err);  // (*bounds / *reg is the caller's, read by the copy above until this has waited)
 }
 
 bool DeviceDataset::hist_monotone(const int* signs, size_t features, std::string* err) {
@@ -495,11 +510,16 @@ bool DeviceDataset::hist_search_symmetric(const std::vector<HistNode>& nodes, co
     best->assign(h.Ft, HistSymBest{});
     if (A == 0 || h.Ft == 0) return true;
     if (h.k < 2 || h.k > HIST_MAX_BINS) return hist_fail(err, "internal error: no bins built");
+    if (how.reg() && (!how.newton || how.path_smooth != 0.0)) return hist_fail(err, "internal error: a symmetric level takes lambda_l1 and max_delta_step under the Newton gain only");
     if (!m.hist_stage_nodes(nodes, how.newton, err) || !h.best_sym.ensure(h.Ft, err)) return false;
     const uint32_t* fsel = h.f_sampled ? h.fsel.p : nullptr;
     {
-        ProfScope ps("hist_scan_sym_kernel", m.stream);
-        if (how.newton)
+        ProfScope ps(how.reg() ? "hist_scan_sym_reg_kernel" : "hist_scan_sym_kernel", m.stream);
+        if (how.reg())
+            hist_scan_sym_reg_kernel<<<h.Ft, 256, 0, m.stream>>>(h.nodes.p, (uint32_t)A, h.Ft, h.k, h.nedges.p, fsel, h.cnt.p, h.sum.p, h.wsum.p,
+                                                                 how.min_leaf, how.s_l, how.s_w, hist_reg_numbers(how), how.min_split_gain,
+                                                                 h.best_sym.p);
+        else if (how.newton)
             hist_scan_sym_kernel<true><<<h.Ft, 256, 0, m.stream>>>(h.nodes.p, (uint32_t)A, h.Ft, h.k, h.nedges.p, fsel, h.cnt.p, h.sum.p, h.wsum.p,
                                                                    how.min_leaf, how.s_l, how.s_w, how.lambda_l2, how.min_sum_hessian,
                                                                    how.min_split_gain, h.best_sym.p);
@@ -521,13 +541,17 @@ bool DeviceDataset::hist_symmetric_apply(const std::vector<HistNode>& nodes, con
     out->assign(A, HistCand{});
     if (A == 0) return true;
     if (h.k < 2 || h.k > HIST_MAX_BINS || fi >= h.Ft || edge + 1 >= h.k) return hist_fail(err, "internal error: a level's split outside the histograms");
+    if (how.reg() && (!how.newton || how.path_smooth != 0.0)) return hist_fail(err, "internal error: a symmetric level takes lambda_l1 and max_delta_step under the Newton gain only");
     // (the level's search has staged these very nodes, and has waited for the stream: they are uploaded again only if they differ)
     static_assert(sizeof(HistNode) == sizeof(HistItemDev), "host and device records differ");
     const bool staged = h.nodes_h.size() == A && std::memcmp(h.nodes_h.data(), nodes.data(), A * sizeof(HistItemDev)) == 0;
     if ((!staged && !m.hist_stage_nodes(nodes, how.newton, err)) || !h.best_n.ensure(A, err)) return false;
     {
-        ProfScope ps("hist_sym_apply_kernel", m.stream);
-        if (how.newton)
+        ProfScope ps(how.reg() ? "hist_sym_apply_reg_kernel" : "hist_sym_apply_kernel", m.stream);
+        if (how.reg())
+            hist_sym_apply_reg_kernel<<<(unsigned)A, 64, 0, m.stream>>>(h.nodes.p, h.Ft, h.k, fi, edge, h.cnt.p, h.sum.p, h.wsum.p, how.min_leaf, how.s_l,
+                                                                        how.s_w, hist_reg_numbers(how), how.min_split_gain, h.best_n.p);
+        else if (how.newton)
             hist_sym_apply_kernel<true><<<(unsigned)A, 64, 0, m.stream>>>(h.nodes.p, h.Ft, h.k, fi, edge, h.cnt.p, h.sum.p, h.wsum.p, how.min_leaf,
                                                                           how.s_l, how.s_w, how.lambda_l2, how.min_sum_hessian, how.min_split_gain,
                                                                           h.best_n.p);
@@ -639,7 +663,7 @@ void DeviceDataset::hist_end() {
     auto& h = m.hist;
     (void)hipStreamSynchronize(m.stream);
     h.cnt.release(), h.cnt_o.release(), h.sum.release(), h.sum_o.release(), h.wsum.release(), h.wsum_o.release(), h.best.release(), h.best_n.release(), h.best_sym.release(), h.lam_in.release(), h.wt_in.release();
-    h.pcnt.release(), h.psum.release(), h.pwsum.release(), h.rec.release(), h.pick.release(), h.bounds.release();
+    h.pcnt.release(), h.psum.release(), h.pwsum.release(), h.rec.release(), h.pick.release(), h.bounds.release(), h.regn.release();
     h.pool_slots = 0;
 }
 
@@ -647,12 +671,18 @@ void DeviceDataset::hist_end() {
 
 // scan (after deriving where asked) and pick of `count` children, their records to out[0..count); waits for the stream
 bool DeviceDataset::Impl::hist_leaf_scan(const HistLeafKids& kids, uint32_t count, const DeviceDataset::HistSearch& how,
-                                         DeviceDataset::HistCand* out, std::string* err, const HistLeafBoundsDev* bounds) {
+                                         DeviceDataset::HistCand* out, std::string* err, const HistLeafBoundsDev* bounds, const HistLeafRegDev* reg) {
     static_assert(sizeof(DeviceDataset::HistCand) == sizeof(HistPickDev), "host and device records differ");
     auto& h = hist;
     if (!h.rec.ensure((size_t)2 * h.Ft, err) || !h.pick.ensure(2, err)) return false;
     const uint32_t* fsel = h.f_sampled ? h.fsel.p : nullptr;
-    if (how.monotone) {
+    if (how.reg()) {
+        if (!how.newton || reg == nullptr || h.mono_F == 0 || h.mono_F != h.F)
+            return hist_fail(err, "internal error: no monotone signs set for these bins");
+        ProfScope ps("hist_leaf_scan_reg_kernel", stream);
+        hist_leaf_scan_reg_kernel<<<dim3(h.Ft, count), 64, 0, stream>>>(kids, *reg, h.Ft, h.k, h.nedges.p, h.mono.p, fsel, h.pcnt.p, h.psum.p, h.pwsum.p,
+                                                                        how.min_leaf, how.s_l, how.s_w, hist_reg_numbers(how), h.rec.p);
+    } else if (how.monotone) {
         if (!how.newton || bounds == nullptr || h.mono_F == 0 || h.mono_F != h.F)
             return hist_fail(err, "internal error: no monotone signs set for these bins");
         ProfScope ps("hist_leaf_scan_monotone_kernel", stream);
@@ -704,7 +734,9 @@ bool DeviceDataset::hist_leaf_begin(uint32_t slots, const HistSearch& how, HistC
     HistLeafBoundsDev whole{};  // (the root's interval: the whole line)
     whole.lo[0] = whole.lo[1] = -std::numeric_limits<double>::infinity();
     whole.hi[0] = whole.hi[1] = std::numeric_limits<double>::infinity();
-    return m.hist_leaf_scan(kids, 1, how, root, err, &whole);
+    HistLeafRegDev rootless{};  // (and no parent)
+    rootless.lo[0] = rootless.lo[1] = whole.lo[0], rootless.hi[0] = rootless.hi[1] = whole.hi[0];
+    return m.hist_leaf_scan(kids, 1, how, root, err, &whole, &rootless);
 }
 
 bool DeviceDataset::hist_leaf_step(const HistLeafStep& step, const HistSearch& how, HistCand pick[2], std::string* err) {
@@ -743,6 +775,7 @@ bool DeviceDataset::hist_leaf_step(const HistLeafStep& step, const HistSearch& h
     // the children to scan, the lhs first; the larger one is derived in place in its parent's slot
     HistLeafKids kids{};
     HistLeafBoundsDev bounds{};
+    HistLeafRegDev reg{};
     uint32_t count = 0;
     int where[2] = {-1, -1};
     for (int side = 0; side < 2; side++) {
@@ -752,12 +785,13 @@ bool DeviceDataset::hist_leaf_step(const HistLeafStep& step, const HistSearch& h
         kids.n[count] = side == 0 ? s.nl : nr;
         kids.derive[count] = small ? 0u : 1u;
         kids.other[count] = step.small_slot;
-        bounds.lo[count] = step.bounds[side].lo, bounds.hi[count] = step.bounds[side].hi;
+        bounds.lo[count] = reg.lo[count] = step.bounds[side].lo, bounds.hi[count] = reg.hi[count] = step.bounds[side].hi;
+        reg.parent[count] = step.parent_out, reg.has_parent[count] = 1u;
         where[side] = (int)count++;
     }
     if (count == 0) return true;
     HistCand got[2];
-    if (!m.hist_leaf_scan(kids, count, how, got, err, &bounds)) return false;
+    if (!m.hist_leaf_scan(kids, count, how, got, err, &bounds, &reg)) return false;
     for (int side = 0; side < 2; side++)
         if (where[side] >= 0) pick[side] = got[where[side]];
     return true;

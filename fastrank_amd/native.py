@@ -3,6 +3,7 @@ dense result buffers, the batched line-search evaluator, restart-sharded and que
 training and HIP-event kernel timing.  numpy is used only to hold buffers that cross the ABI."""
 import ctypes as C
 import json
+import math
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
@@ -218,7 +219,8 @@ def hist_bins(dataset: CDataset, split_candidates: int):
 def hist_tree(dataset: CDataset, lam: np.ndarray, wt: np.ndarray, split_candidates: int, max_depth: int,
               min_leaf_support: int, queries=None, features=None, split_gain: str = "variance", lambda_l2: float = 0.0,
               min_sum_hessian: float = 0.0, min_split_gain: float = 0.0, max_leaves: int = 0, monotone=None,
-              clamped_out: Optional[list] = None, goss=None, symmetric: bool = False) -> CModel:
+              clamped_out: Optional[list] = None, goss=None, symmetric: bool = False, lambda_l1: float = 0.0,
+              max_delta_step: float = 0.0, path_smooth: float = 0.0) -> CModel:
     """One tree of LambdaMART's histogram grower for the gradients lam / wt (indexed by instance id).  `queries` (indices of
     the view's queries) / `features` (feature ids): the tree's sample; gradients outside the query sample are not read.
     `split_gain` = "newton": the second-order gain with `lambda_l2`, `min_sum_hessian` and `min_split_gain` (DESIGN.md
@@ -230,7 +232,9 @@ def hist_tree(dataset: CDataset, lam: np.ndarray, wt: np.ndarray, split_candidat
     of the sample's instances under the key of tree `tree` of `seed`, the kept others' gradients amplified (DESIGN.md section
     11, "GOSS"); level-wise or leaf-wise, with or without monotone signs.  `symmetric` = True (level-wise, without monotone
     signs or GOSS): every node of a level splits on the level's one winning candidate ("Symmetric
-    trees"), under either gain.  Arguments that contradict each other raise ValueError before the one native call."""
+    trees"), under either gain.  `lambda_l1`, `max_delta_step`, `path_smooth` (need `split_gain` = "newton"; `path_smooth` not
+    with `symmetric`): the leaf regularisation ("Leaf regularisation"); all 0.0: off.  Arguments that
+    contradict each other raise ValueError before the one native call."""
     lam = np.ascontiguousarray(lam, dtype=np.float64)
     wt = np.ascontiguousarray(wt, dtype=np.float64)
     newton = split_gain == "newton"
@@ -251,6 +255,13 @@ def hist_tree(dataset: CDataset, lam: np.ndarray, wt: np.ndarray, split_candidat
         raise ValueError("max_leaves must be 0 (level-wise) or at least 2")
     if not newton and (lambda_l2 != 0.0 or min_sum_hessian != 0.0 or min_split_gain != 0.0):
         raise ValueError("lambda_l2, min_sum_hessian and min_split_gain need split_gain='newton'")
+    reg = (float(lambda_l1), float(max_delta_step), float(path_smooth))
+    if any(not (math.isfinite(x) and x >= 0.0) for x in reg):
+        raise ValueError("lambda_l1, max_delta_step and path_smooth must be finite and at least 0")
+    if not newton and any(x != 0.0 for x in reg):
+        raise ValueError("lambda_l1, max_delta_step and path_smooth need split_gain='newton'")
+    if symmetric and reg[2] != 0.0:
+        raise ValueError("symmetric trees take no path_smooth")
     qs = None if queries is None else np.ascontiguousarray(queries, dtype=np.uint32)
     fs = None if features is None else np.ascontiguousarray(features, dtype=np.uint32)
     mf = np.ascontiguousarray(list(mono.keys()), dtype=np.uint32)
@@ -264,6 +275,7 @@ def hist_tree(dataset: CDataset, lam: np.ndarray, wt: np.ndarray, split_candidat
         features=None if fs is None else fs.ctypes.data, n_features=0 if fs is None else len(fs),
         mono_features=mf.ctypes.data if mono else None, mono_signs=ms.ctypes.data if mono else None, n_mono=len(mono),
         goss=0 if goss is None else 1, top_rate=float(top_rate), other_rate=float(other_rate), seed=int(seed), tree=int(tree),
+        lambda_l1=reg[0], max_delta_step=reg[1], path_smooth=reg[2],
     )
     clamped = C.c_uint32(0)
     model = CModel(
@@ -272,6 +284,21 @@ def hist_tree(dataset: CDataset, lam: np.ndarray, wt: np.ndarray, split_candidat
     if mono and clamped_out is not None:
         clamped_out.append(int(clamped.value))
     return model
+
+
+def hist_reg_term(q: int, w: int, n: int, s_l: int, s_w: int, l1: float, l2: float, mds: float, smooth: float, parent, lo: float,
+                  hi: float) -> Tuple[float, float]:
+    """(v, term) of the leaf regularisation ("Leaf regularisation") for the integer sums (q, w) of a
+    node or side of n instances under the exponents s_l / s_w: the host's own arithmetic, no device is touched.  `parent`:
+    the parent's output, or None for the root; [lo, hi]: the node's interval."""
+    v, term = C.c_double(0.0), C.c_double(0.0)
+    _status(
+        _load().fr_debug_hist_reg_term(
+            int(q), int(w), int(n), int(s_l), int(s_w), float(l1), float(l2), float(mds), float(smooth), 0 if parent is None else 1,
+            0.0 if parent is None else float(parent), float(lo), float(hi), C.byref(v), C.byref(term),
+        )
+    )
+    return v.value, term.value
 
 
 def goss_select(dataset: CDataset, lam: np.ndarray, top_rate: float, other_rate: float, seed: int, tree: int,

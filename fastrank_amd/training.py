@@ -151,6 +151,14 @@ class LambdaMARTParams(_LearnerParams):
     level-wise (`max_leaves` = 0) and without `monotone_constraints`; both split gains and every other key compose.  The
     trees are ordinary decision trees; the training stats then report `symmetric_trees` and `levels` (per tree, the levels
     that split) ("Symmetric trees").
+    `lambda_l1`, `max_delta_step`, `path_smooth` (finite, >= 0, default 0.0 = off; written only when set): regularisation
+    of the leaf outputs.  A node's gradient sum is soft-thresholded by `lambda_l1` before it becomes an output or a gain
+    (small sums give a leaf of exactly 0); an output's magnitude is capped at `max_delta_step`, which bounds the leaves of
+    nodes whose hessian sum is tiny (LambdaRank's hessians vanish for pairs the model already orders confidently);
+    `path_smooth` pulls a child's output toward its parent's, the more strongly the fewer documents the child holds, which
+    steadies small, deep leaves.  Histogram grower under `split_gain` = "newton" only, level-wise and leaf-wise, with
+    every other key; `path_smooth` cannot be combined with `symmetric_trees`.  The training stats then report the three
+    keys ("Leaf regularisation").
     Two things are arguments of `CDataset.train_model`, not keys: `valid` (a second dataset the held-out measure and early
     stopping are read from; `validation_queries` must then be empty and `early_stopping_rounds` needs no held-out query)
     and `init_model` (an Ensemble of DecisionTrees training continues from: `num_trees` counts new trees, and the per-tree
@@ -186,13 +194,17 @@ class LambdaMARTParams(_LearnerParams):
     goss_top_rate: float = 0.0
     goss_other_rate: float = 0.1
     symmetric_trees: bool = False
+    lambda_l1: float = 0.0
+    max_delta_step: float = 0.0
+    path_smooth: float = 0.0
 
     _WIRE_DEFAULTS: ClassVar[Dict[str, Any]] = {"grower": "exact", "query_sampling_rate": 1.0, "feature_sampling_rate": 1.0, "seed": 0,
                                                 "validation_queries": [], "early_stopping_rounds": 0, "split_gain": "variance",
                                                 "lambda_l2": 0.0, "min_sum_hessian": 0.0, "min_split_gain": 0.0,
                                                 "max_leaves": 0, "truncation_level": 0, "lambda_norm": False, "objective": "ndcg",
                                                 "drop_rate": 0.0, "max_drop": 50, "skip_drop": 0.5, "monotone_constraints": {},
-                                                "goss_top_rate": 0.0, "goss_other_rate": 0.1, "symmetric_trees": False}
+                                                "goss_top_rate": 0.0, "goss_other_rate": 0.1, "symmetric_trees": False,
+                                                "lambda_l1": 0.0, "max_delta_step": 0.0, "path_smooth": 0.0}
     _OBJECTIVES: ClassVar[Dict[str, str]] = {"ap": "map", "rr": "mrr", "xendcg": "xendcg"}
 
     def __post_init__(self):

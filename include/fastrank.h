@@ -278,6 +278,10 @@ typedef struct FrHistTreeOptions {
     double top_rate, other_rate;
     uint64_t seed;
     uint32_t tree;
+    /* "Leaf regularisation" (Newton gain only; finite and >= 0, all 0: off): the gradient sum is soft-thresholded by
+     * lambda_l1, an output's magnitude is capped at max_delta_step, a child's output is pulled toward its parent's by
+     * path_smooth (not with symmetric). */
+    double lambda_l1, max_delta_step, path_smooth;
 } FrHistTreeOptions;
 /* One histogram tree (a DecisionTree model) grown from lambda / weight indexed by instance id (len
  * entries).  Options that contradict each other or are out of range are refused before the dataset is looked at.
@@ -288,6 +292,12 @@ const CResult *fr_debug_hist_tree(const CDataset *dataset, const FrHistTreeOptio
  * instances of queries[n_queries] (NULL = all).  list_out / top_out[cap] (cap >= the view's instances): the GOSS list as
  * ascending indices into the view's instance list, and per entry whether it belongs to the top set; *n_g_out: the list's
  * length; *tau_out: the n_top-th largest of the 64-bit patterns of |lambda|. */
+/* The leaf regularisation's host arithmetic for one integer pair (q, w) of n instances ("Leaf
+ * regularisation"; no device is touched): *v_out = the output, *term_out = its term.  has_parent == 0: the root, parent is
+ * not read.  [lo, hi]: the node's interval (-inf, +inf: none). */
+const void *fr_debug_hist_reg_term(int64_t q, int64_t w, uint32_t n, int32_t s_l, int32_t s_w, double lambda_l1,
+                                   double lambda_l2, double max_delta_step, double path_smooth, int32_t has_parent,
+                                   double parent, double lo, double hi, double *v_out, double *term_out);
 const void *fr_debug_goss_select(const CDataset *dataset, const double *lambda, size_t len, double top_rate,
                                  double other_rate, uint64_t seed, uint32_t tree, const uint32_t *queries, size_t n_queries,
                                  uint32_t *list_out, uint8_t *top_out, size_t cap, uint32_t *n_g_out, uint64_t *tau_out);

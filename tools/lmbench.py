@@ -81,6 +81,7 @@ def device_run(args, X, y, qid):
         req.params.goss_top_rate, req.params.goss_other_rate = args.goss_top_rate, args.goss_other_rate
     if args.symmetric:
         req.params.symmetric_trees = True
+    req.params.lambda_l1, req.params.max_delta_step, req.params.path_smooth = args.lambda_l1, args.max_delta_step, args.path_smooth
     if args.monotone:  # the first N features of the dataset, alternating signs from +1
         names = ds.feature_index_to_name()
         first = sorted(names)[:args.monotone]
@@ -177,6 +178,8 @@ def device_run(args, X, y, qid):
     if args.symmetric:  # (only with the key, like the stats object)
         out["symmetric"] = {"levels_mean": float(np.mean(st["levels"])), "levels_min": int(np.min(st["levels"])),
                             "levels_max": int(np.max(st["levels"]))}
+    if args.lambda_l1 or args.max_delta_step or args.path_smooth:  # (only with a key, like the stats object)
+        out["leaf_regularisation"] = {k: st[k] for k in ("lambda_l1", "max_delta_step", "path_smooth")}
     if args.held_out_measures and args.validation_rate > 0:  # AP / RR / NDCG of the model over the held-out queries
         held = set(req.params.validation_queries)
         out["held_out"] = {}
@@ -245,6 +248,9 @@ def parser():
     ap.add_argument("--goss-top-rate", type=float, default=0.0, help="GOSS: the share of a tree's documents kept for their |gradient| (0: off; needs --split-gain newton)")
     ap.add_argument("--goss-other-rate", type=float, default=0.1, help="GOSS: the share of a tree's documents drawn from the others")
     ap.add_argument("--symmetric", action="store_true", help="symmetric trees: every node of a level splits on one candidate (histogram grower, level-wise)")
+    ap.add_argument("--lambda-l1", type=float, default=0.0, help="leaf regularisation: soft threshold of a node's gradient sum (needs --split-gain newton)")
+    ap.add_argument("--max-delta-step", type=float, default=0.0, help="leaf regularisation: cap of an output's magnitude (0: none; needs --split-gain newton)")
+    ap.add_argument("--path-smooth", type=float, default=0.0, help="leaf regularisation: pull of a child's output toward its parent's (0: none; needs --split-gain newton)")
     ap.add_argument("--held-out-measures", action="store_true", help="with --validation-rate: report the model's mean AP, RR and NDCG over the held-out queries")
     ap.add_argument("--warmup-trees", type=int, default=0, help="train this many trees untimed before the measured training")
     ap.add_argument("--no-kernel-profile", action="store_true", help="leave the library's per-kernel event timing off during the timed training")
