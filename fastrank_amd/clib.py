@@ -30,6 +30,7 @@ class HistTreeOptions(C.Structure):  # FrHistTreeOptions (include/fastrank.h); a
                 ("min_sum_hessian", C.c_double), ("min_split_gain", C.c_double), ("max_leaves", C.c_uint32), ("symmetric", C.c_int32), ("queries", C.c_void_p),
                 ("n_queries", C.c_size_t), ("features", C.c_void_p), ("n_features", C.c_size_t), ("mono_features", C.c_void_p), ("mono_signs", C.c_void_p),
                 ("n_mono", C.c_size_t), ("goss", C.c_int32), ("top_rate", C.c_double), ("other_rate", C.c_double), ("seed", C.c_uint64), ("tree", C.c_uint32),
+                ("quant_bits", C.c_uint32), ("quant_seed", C.c_uint64), ("quant_tree", C.c_uint32),
                 ("lambda_l1", C.c_double), ("max_delta_step", C.c_double), ("path_smooth", C.c_double)]
 
 
@@ -102,6 +103,9 @@ def _load():
         "fr_debug_dart_scores": (vp, [vp, vp, vp, sz, vp, sz, vp, vp, sz]),
         "fr_debug_lambda_gradients_sampled": (vp, [vp, vp, vp, C.c_char_p, C.c_double, vp, sz, vp, vp, sz]),
         "fr_debug_goss_select": (vp, [vp, vp, sz, C.c_double, C.c_double, C.c_uint64, C.c_uint32, vp, sz, vp, vp, sz, vp, vp]),
+        "fr_debug_hist_quantise": (vp, [vp, vp, vp, sz, C.c_uint32, C.c_uint64, C.c_uint32, vp, sz, C.c_int32, C.c_double, C.c_double, C.c_uint64, C.c_uint32,
+                                        vp, vp, sz, vp, vp]),
+        "fr_debug_hist_root_histogram": (vp, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, vp, sz, vp, vp, vp, sz]),
         "fr_debug_hist_reg_term": (vp, [C.c_int64, C.c_int64, C.c_uint32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double,
                                         C.c_int32, C.c_double, C.c_double, C.c_double, vp, vp]),
         "fr_debug_lambda_gradients_opts": (vp, [vp, vp, vp, C.c_char_p, C.c_double, vp, sz, C.c_char_p, vp, vp, sz]),

@@ -2095,6 +2095,9 @@ static const char* hist_tree_options_error(const FrHistTreeOptions& o) {
         if (!(std::isfinite(x) && x >= 0.0) || (!o.newton && x != 0.0))
             return "lambda_l1, max_delta_step and path_smooth must be finite and at least 0, and 0 without the Newton gain";
     if (o.symmetric && o.path_smooth != 0.0) return "symmetric trees take no path_smooth";
+    if (!fr::quant_bits_ok(o.quant_bits)) return "quant_bits must be 0 (off) or between 2 and 8";
+    if (o.quant_bits != 0 && (!o.newton || o.n_mono != 0 || o.lambda_l1 != 0.0 || o.max_delta_step != 0.0 || o.path_smooth != 0.0))
+        return "quantised gradients need the Newton gain, and take no monotone constraints, lambda_l1, max_delta_step or path_smooth";
     return nullptr;
 }
 
@@ -2117,6 +2120,7 @@ const CResult* fr_debug_hist_tree(const CDataset* dataset, const FrHistTreeOptio
         fr::HistGrowOptions grow{o.split_candidates, o.max_depth, o.min_leaf_support, fr::HistNewton(), o.max_leaves, {}, o.symmetric != 0};
         if (o.newton) grow.newton = {true, o.lambda_l2, o.min_sum_hessian, o.min_split_gain};
         grow.reg = {o.lambda_l1, o.max_delta_step, o.path_smooth};
+        grow.quant_bits = o.quant_bits;
         std::vector<uint32_t> sel;
         if (o.features) {
             std::vector<uint32_t> want(o.features, o.features + o.n_features);
@@ -2149,7 +2153,8 @@ const CResult* fr_debug_hist_tree(const CDataset* dataset, const FrHistTreeOptio
             fr::Model tree;
             tree.kind = fr::Model::DecisionTree;
             fr::HistTreeReport rep;
-            tree.tree = grower.grow(lam.data(), wt.data(), o.goss ? &goss : nullptr, &rep);
+            tree.tree = grower.grow(lam.data(), wt.data(), o.goss ? &goss : nullptr, &rep,
+                                    o.quant_bits != 0 ? fr::QuantKeys::of_tree(o.quant_seed, o.quant_tree) : 0);
             if (clamped_leaves_out) *clamped_leaves_out = rep.clamped_leaves;
             return tree;
         });
@@ -2197,6 +2202,93 @@ const void* fr_debug_goss_select(const CDataset* dataset, const double* lambda, 
         if (!dev.hist_goss(lam.data(), plan.n_top, plan.p, plan.amp, fr::GossKeys::of_tree(seed, tree), &n_g, tau_out, &err)) fr::fail_str(err);
         if (!dev.hist_goss_download(list_out, top_out, n_g, &err)) fr::fail_str(err);
         *n_g_out = n_g;
+    });
+}
+
+// The fixed-point step and the quantised gradients of one tree on their own ("Quantised gradients").
+const void* fr_debug_hist_quantise(const CDataset* dataset, const double* lambda, const double* weight, size_t len, uint32_t bits, uint64_t seed,
+                                   uint32_t tree, const uint32_t* queries, size_t n_queries, int32_t goss, double top_rate, double other_rate,
+                                   uint64_t goss_seed, uint32_t goss_tree, int32_t* q_out, uint32_t* w_out, size_t cap, uint32_t* n_out,
+                                   int32_t* numbers_out) {
+    return status_call([&]() {
+        const std::string who = "fr_debug_hist_quantise";
+        const CDataset& ds = require_dataset(dataset);
+        if (!lambda || !weight || !q_out || !w_out || !n_out || !numbers_out) fr::fail_str("NULL pointer: " + who);
+        if (bits < fr::QUANT_MIN_BITS || bits > fr::QUANT_MAX_BITS) fr::fail_str(who + ": bits must be between 2 and 8");
+        if (goss && !goss_debug_rates_ok(top_rate, other_rate)) fr::fail_str(who + ": " + GOSS_DEBUG_RATES);
+        std::lock_guard<std::mutex> lk(api_mu_of(ds));
+        fr::DatasetView& view = *ds.view;
+        const HistDebugInput in(view, queries, n_queries);
+        if (cap < in.ids.size()) fr::fail_str(who + ": the outputs are shorter than the instance list");
+        const std::string too_short = who + ": the gradient arrays are shorter than the largest instance id";
+        const std::vector<double> lam = in.gather(lambda, len, too_short), wt = in.gather(weight, len, too_short);
+        frdev::DeviceDataset& dev = view.device();
+        // (no bin is read: the smallest bin matrix there is keeps the hook cheap on a view that has none yet)
+        fr::HistGrower grower(dev, in.feats, {2u, 1u, 1u, fr::HistNewton{true, 0.0, 0.0, 0.0}, 0u, {}});
+        grower.prepare(in.positions);
+        HistDebugUnsample unsample{grower};
+        grower.set_sample(in.query_flags(), (uint32_t)in.n_t, nullptr);
+        std::string err;
+        uint32_t n = (uint32_t)in.n_t;
+        if (goss) {
+            const fr::GossPlan plan = fr::goss_plan(in.n_t, top_rate, other_rate);
+            if (!dev.hist_goss(lam.data(), plan.n_top, plan.p, plan.amp, fr::GossKeys::of_tree(goss_seed, goss_tree), &n, nullptr, &err)) fr::fail_str(err);
+        }
+        int s_l = 0, s_w = 0, d = 0, d_w = 0;
+        bool all_zero = false;
+        if (!dev.hist_quantise(lam.data(), wt.data(), &s_l, &s_w, &all_zero, &err)) fr::fail_str(err);
+        if (all_zero) fr::fail_str(who + ": every lambda is zero (the tree is one leaf, nothing is quantised)");
+        if (!dev.hist_quantq(bits, fr::QuantKeys::of_tree(seed, tree), &d, &d_w, &err)) fr::fail_str(err);
+        if (!dev.hist_quantq_download(q_out, w_out, n, &err)) fr::fail_str(err);
+        *n_out = n;
+        const int32_t numbers[6] = {s_l, s_w, s_l - d, s_w - d_w, d, d_w};
+        std::copy(numbers, numbers + 6, numbers_out);
+    });
+}
+
+// The root's histogram of one tree (count, sum Q, sum W as [features][k]) for lambda / weight by instance id: bits == 0 by the
+// Newton build over Q / W, else by the packed build over the quantised values of tree `tree` of `seed`.
+const void* fr_debug_hist_root_histogram(const CDataset* dataset, const double* lambda, const double* weight, size_t len, uint32_t split_candidates,
+                                         uint32_t bits, uint64_t seed, uint32_t tree, const uint32_t* features, size_t n_features,
+                                         uint32_t* count_out, int64_t* sum_out, int64_t* wsum_out, size_t cells) {
+    return status_call([&]() {
+        const std::string who = "fr_debug_hist_root_histogram";
+        const CDataset& ds = require_dataset(dataset);
+        if (!lambda || !weight || !count_out || !sum_out || !wsum_out) fr::fail_str("NULL pointer: " + who);
+        if (!fr::quant_bits_ok(bits)) fr::fail_str(who + ": bits must be 0 or between 2 and 8");
+        std::lock_guard<std::mutex> lk(api_mu_of(ds));
+        fr::DatasetView& view = *ds.view;
+        const HistDebugInput in(view, nullptr, 0);
+        const std::vector<uint32_t>& feats = in.feats;
+        std::vector<uint32_t> sel;
+        if (features) {
+            std::vector<uint32_t> want(features, features + n_features);
+            std::sort(want.begin(), want.end());
+            for (size_t i = 0; i < want.size(); i++) {
+                const auto it = std::lower_bound(feats.begin(), feats.end(), want[i]);
+                if (it == feats.end() || *it != want[i] || (i > 0 && want[i] == want[i - 1]))
+                    fr::fail_str(who + ": feature " + std::to_string(want[i]) + " is not in the view, or is named twice");
+                sel.push_back((uint32_t)(it - feats.begin()));
+            }
+        }
+        const size_t Ft = features ? sel.size() : feats.size();
+        if (cells != Ft * (size_t)split_candidates) fr::fail_str(who + ": the outputs must hold features x split_candidates cells");
+        const std::string too_short = who + ": the gradient arrays are shorter than the largest instance id";
+        const std::vector<double> lam = in.gather(lambda, len, too_short), wt = in.gather(weight, len, too_short);
+        frdev::DeviceDataset& dev = view.device();
+        fr::HistGrower grower(dev, feats, {split_candidates, 1u, 1u, fr::HistNewton{true, 0.0, 0.0, 0.0}, 0u, {}});
+        grower.prepare(in.positions);
+        HistDebugUnsample unsample{grower};
+        grower.set_sample(nullptr, (uint32_t)in.n_t, features ? &sel : nullptr);
+        std::string err;
+        int s_l = 0, s_w = 0, d = 0, d_w = 0;
+        bool all_zero = false;
+        if (!dev.hist_quantise(lam.data(), wt.data(), &s_l, &s_w, &all_zero, &err)) fr::fail_str(err);
+        if (all_zero) fr::fail_str(who + ": every lambda is zero (no fixed-point values are made)");
+        if (bits != 0 && !dev.hist_quantq(bits, fr::QuantKeys::of_tree(seed, tree), &d, &d_w, &err)) fr::fail_str(err);
+        if (!dev.hist_root(true, &err)) fr::fail_str(err);
+        static_assert(sizeof(long long) == sizeof(int64_t), "the histograms' sums are 64-bit");
+        if (!dev.hist_root_download(count_out, reinterpret_cast<long long*>(sum_out), reinterpret_cast<long long*>(wsum_out), cells, &err)) fr::fail_str(err);
     });
 }
 

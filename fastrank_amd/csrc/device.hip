@@ -32,6 +32,8 @@
 //   kernels_histreg.inc     the histogram grower's scan kernels under lambda_l1 / max_delta_step / path_smooth
 //   kernels_goss.inc        LambdaMART's gradient-based one-side sampling: an on-device radix select of the n-th largest |lambda|,
 //                           the kept documents' list, amplified fixed-point gradients
+//   kernels_histquant.inc   LambdaMART's quantised gradients: (q, w) of a few bits per entry under a per-tree key, and the histogram
+//                           build over them with one packed 64-bit LDS atomic per update (arithmetic: lambdamart_quant.hpp)
 //   kernels_dart.inc        LambdaMART's DART boosting: the u16 leaf cache and dart_rescore_kernel, which re-forms the scores
 //                           of any weighting of the trees from it
 //   dataset_layout.hpp      (through device.hpp; host only, no HIP) the layout arithmetic of a dataset: runs, size classes, gain
@@ -43,7 +45,7 @@
 //     train_rf.inc            the launchers of kernels_rf.inc
 //     train_lambda.inc        the launchers of kernels_lambda.inc and kernels_xendcg.inc
 //     train_dart.inc          the launchers of kernels_dart.inc
-//     train_hist.inc          the launchers of kernels_hist.inc and kernels_histreg.inc, level-wise and leaf-wise, and of kernels_goss.inc
+//     train_hist.inc          the launchers of kernels_hist.inc and kernels_histreg.inc, level-wise and leaf-wise, of kernels_goss.inc and kernels_histquant.inc
 #include "device.hpp"
 
 #include <hip/hip_runtime.h>
@@ -51,6 +53,8 @@
 
 #include "fullverify.hpp"
 #include "linesearch_policy.hpp"
+#define FR_QUANT_ARITHMETIC_ONLY  // (lambdamart_quant.hpp without host.hpp: the integer arithmetic the kernels share with the host)
+#include "lambdamart_quant.hpp"
 
 #include <cstring>
 #include <dlfcn.h>
@@ -91,6 +95,7 @@ namespace frdev {
 #include "kernels_hist.inc"
 #include "kernels_histreg.inc"
 #include "kernels_goss.inc"
+#include "kernels_histquant.inc"
 #include "kernels_dart.inc"
 #include "device_dataset.inc"
 #include "rccl_exchange.inc"

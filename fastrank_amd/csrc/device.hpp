@@ -384,6 +384,15 @@ class DeviceDataset {
     // Q / W of the tree to grow, from the last gradient pass (lam_list == nullptr) or from host arrays in instance-list
     // order.  *all_zero: every lambda is 0 (nothing was quantised); s_l / s_w: the exponents S of the definition
     bool hist_quantise(const double* lam_list, const double* wt_list, int* s_l, int* s_w, bool* all_zero, std::string* err);
+    // Quantised gradients ("Quantised gradients"; kernels_histquant.inc; Newton gain only) for the tree hist_quantise has just
+    // prepared: (q, w) of `bits` bits (2..8) per entry of the tree's list under tree_key and the documents' original instance
+    // ids.  *d / *d_w: the two shifts: the sums the searches read are then under the exponents s_l - d and s_w - d_w, the leaf
+    // sums stay under (s_l, s_w).  Holds until the next hist_quantise, hist_sample or hist_bins.  Waits for the stream.
+    bool hist_quantq(uint32_t bits, uint64_t tree_key, int* d, int* d_w, std::string* err);
+    // the values hist_quantq made, by index of the tree's list (len = its length)
+    bool hist_quantq_download(int32_t* q, uint32_t* w, size_t len, std::string* err);
+    // the level's slot 0 after hist_root(true): count, sum Q and sum W as [features][k] (cells = their product)
+    bool hist_root_download(uint32_t* cnt, long long* sum, long long* wsum, size_t cells, std::string* err);
     // index list = the sample's root list (0..n-1 without one); the level holds the root's histogram in slot 0.  newton: with sum W
     bool hist_root(bool newton, std::string* err);
     // One level's search.  best[a * features + slot]: node a's last-maximum candidate of that feature (the level was made

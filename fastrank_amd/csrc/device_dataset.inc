@@ -356,6 +356,10 @@ struct DeviceDataset::Impl : DatasetDesc {
         DevBuf<uint8_t> xbin;  // [F][n]
         DevBuf<double> lam_in, wt_in;
         DevBuf<long long> Q, W;
+        // quantised gradients (hist_quantq; kernels_histquant.inc): set for the tree being grown, after hist_quantise.  The
+        // Newton builds then read packed[r] (by full-list index) instead of Q / W; the leaf sums still read Q / W.
+        bool qz_on = false;
+        DevBuf<uint32_t> packed;
         DevBuf<unsigned long long> absmax, leaf;
         DevBuf<uint32_t> idx, idx_o, flag, scan;
         DevBuf<unsigned char> temp;

@@ -50,6 +50,11 @@
 // regularisation"; lambdamart_reg.hpp, kernels_histreg.inc): the gradient sum is soft-thresholded before it becomes an output
 // or a gain, an output's magnitude is capped, a child's output is pulled toward its parent's; every node carries its output,
 // and the scan kernels are the regularised ones.  path_smooth is refused with symmetric_trees.
+// grad_quant_bits = b in 2..8 (histogram grower under the Newton gain only; DESIGN.md section 11, "Quantised gradients";
+// lambdamart_quant.hpp, kernels_histquant.inc): a tree's fixed-point gradients are rounded stochastically to b bits under a
+// per-tree key of a generator of its own, the searches read sums of those small integers (one packed LDS atomic per update in
+// the build kernel), and the leaves are renewed from the full-precision sums.  Refused with monotone_constraints, lambda_l1,
+// max_delta_step and path_smooth.
 // A validation dataset B ("Validation dataset"): a second view, scored tree by tree on its own device form
 // (score slot, accumulator, metric pass, mean; under DART a leaf cache of its own); no tree reads it.  Its plain mean over
 // all of its queries is the held-out measure the stopping rule reads.
@@ -118,6 +123,8 @@ struct LambdaMARTParams {
     // leaf regularisation (optional keys, not written at their defaults; read only under "newton"): the soft threshold of the
     // gradient sum, the cap of an output's magnitude (0 = none), the pull of a child's output toward its parent's (0 = none)
     double lambda_l1 = 0.0, max_delta_step = 0.0, path_smooth = 0.0;
+    // quantised gradients (optional key, not written at its default): bits per quantised gradient, 2..8 (0 = off)
+    uint32_t grad_quant_bits = 0;
 
     bool leaf_reg() const { return lambda_l1 != 0.0 || max_delta_step != 0.0 || path_smooth != 0.0; }
     bool goss() const { return goss_top_rate > 0.0; }
@@ -145,7 +152,7 @@ struct LambdaMARTParams {
     // (monotone: the signs resolved against the ascending feature list, lambdamart_monotone_signs; empty without the key)
     HistGrowOptions hist_options(std::vector<int> monotone = {}) const {
         return {split_candidates, max_depth, min_leaf_support, HistNewton{newton, lambda_l2, min_sum_hessian, min_split_gain}, max_leaves,
-                std::move(monotone), symmetric_trees, HistReg{lambda_l1, max_delta_step, path_smooth}};
+                std::move(monotone), symmetric_trees, HistReg{lambda_l1, max_delta_step, path_smooth}, grad_quant_bits};
     }
     [[noreturn]] static void invalid(const std::string& what) {
         fail_raw("Error(\"invalid value: " + what + "\", line: 0, column: 0)");
@@ -223,6 +230,7 @@ struct LambdaMARTParams {
         if (const Value* r = v.find("lambda_l1")) p.lambda_l1 = json_f64(*r, "lambda_l1");
         if (const Value* r = v.find("max_delta_step")) p.max_delta_step = json_f64(*r, "max_delta_step");
         if (const Value* r = v.find("path_smooth")) p.path_smooth = json_f64(*r, "path_smooth");
+        if (const Value* r = v.find("grad_quant_bits")) p.grad_quant_bits = json_u32(*r, "grad_quant_bits");
         if (p.num_trees < 1) invalid("num_trees must be at least 1");
         if (!(std::isfinite(p.learning_rate) && p.learning_rate > 0.0)) invalid("learning_rate must be finite and greater than 0");
         if (p.max_depth < 1) invalid("max_depth must be at least 1");
@@ -276,6 +284,15 @@ struct LambdaMARTParams {
         }
         if (p.path_smooth != 0.0 && p.symmetric_trees)
             invalid("path_smooth cannot be combined with symmetric_trees (a level's one split is priced over every node, each with a parent of its own)");
+        if (!quant_bits_ok(p.grad_quant_bits)) invalid("grad_quant_bits must be 0 (off) or between 2 and 8");
+        if (p.grad_quant_bits != 0) {
+            if (!p.histogram) invalid("grad_quant_bits needs grower: \"histogram\" (the exact grower builds no histograms)");
+            if (!p.newton) invalid("grad_quant_bits needs split_gain: \"newton\" (the variance criterion has no hessian sums to quantise)");
+            const char* undecided = " (their nodes carry outputs computed from sums, and it is not decided whether those would read the quantised sums or the full-precision ones)";
+            if (!p.monotone_constraints.empty()) invalid(std::string("grad_quant_bits cannot be combined with monotone_constraints") + undecided);
+            for (const auto& kv : leaf_numbers)
+                if (kv.second != 0.0) invalid(std::string("grad_quant_bits cannot be combined with ") + kv.first + undecided);
+        }
         p.check_objective_options();
         return p;
     }
@@ -320,6 +337,7 @@ struct LambdaMARTParams {
         if (lambda_l1 != 0.0) o.set("lambda_l1", Value::number(lambda_l1));
         if (max_delta_step != 0.0) o.set("max_delta_step", Value::number(max_delta_step));
         if (path_smooth != 0.0) o.set("path_smooth", Value::number(path_smooth));
+        if (grad_quant_bits != 0) o.set("grad_quant_bits", Value::uint(grad_quant_bits));
         return o;
     }
 };
@@ -488,6 +506,8 @@ struct LambdaMARTStats {
     std::vector<uint32_t> goss_instances, goss_top;
     // symmetric trees (reported only when the key is set): per tree the levels that split
     std::vector<uint32_t> levels;
+    // quantised gradients (reported only when grad_quant_bits is set): the wall seconds of the quantise launches (a share of t_grow)
+    double t_quant = 0.0;
     double best_valid_measure = 0.0;  // the held-out measure at best_iteration
     // a validation dataset (reported only when one is given): its sizes and the wall seconds of its side of every tree
     bool valid_dataset = false;
@@ -600,6 +620,10 @@ struct LambdaMARTStats {
             o.set("lambda_l1", Value::number(r.lambda_l1));
             o.set("max_delta_step", Value::number(r.max_delta_step));
             o.set("path_smooth", Value::number(r.path_smooth));
+        }
+        if (r.grad_quant_bits != 0) {
+            o.set("grad_quant_bits", Value::uint(r.grad_quant_bits));
+            o.set("quant_ms", Value::number(t_quant * 1e3));
         }
         return o;
     }
@@ -791,9 +815,12 @@ class LambdaMARTTrainer {
         Rand64 xe_keys(p_.seed ^ XENDCG_STREAM);  // the listwise objective's keys: a stream of its own, like the plan's
         GossKeys goss_keys(p_.seed);               // GOSS: one more stream of its own (lambdamart_goss.hpp)
         const bool goss = p_.goss();
+        QuantKeys quant_keys(p_.seed);             // quantised gradients: and one more (lambdamart_quant.hpp)
+        const bool quant = p_.grad_quant_bits != 0;
         for (uint32_t i = 0; i < T0; i++) {  // (an init model's trees have taken their keys: one each)
             if (p_.xendcg()) (void)xe_keys.rand_u64();
             if (goss) (void)goss_keys.next();
+            if (quant) (void)quant_keys.next();
         }
         struct DartGuard {
             frdev::DeviceDataset& d;
@@ -816,6 +843,7 @@ class LambdaMARTTrainer {
         for (uint32_t t = 0; t < p_.num_trees; t++) {
             const uint64_t xe_key = p_.xendcg() ? xe_keys.rand_u64() : 0;  // k_t: one per tree, before anything else of the tree
             const HistGoss goss_t{p_.goss_top_rate, p_.goss_other_rate, goss ? goss_keys.next() : 0};  // K_t: one per tree as well
+            const uint64_t quant_key = quant ? quant_keys.next() : 0;
             const std::vector<uint32_t> dropped = dart ? plan.next(t) : std::vector<uint32_t>();
             if (!dropped.empty()) reform(dart_kept(t, dropped));  // the tree is fitted to the ensemble without the dropped trees
             auto ts = tnow();  // (drawing the sample and handing it to the grower count as grow time)
@@ -844,7 +872,7 @@ class LambdaMARTTrainer {
                 else hist->set_sample(sample_q ? qflags.data() : nullptr, t_n, sample_f ? &smp.features : nullptr);
             }
             HistTreeReport rep;
-            std::shared_ptr<TreeNode> root = hist ? hist->grow(nullptr, nullptr, goss ? &goss_t : nullptr, &rep)
+            std::shared_ptr<TreeNode> root = hist ? hist->grow(nullptr, nullptr, goss ? &goss_t : nullptr, &rep, quant_key)
                                                   : grower.grow_lambda_tree(dev, *off_t, *ids_t, *feats_t, pos_t, rst);
             auto tc = tnow() - std::chrono::duration_cast<std::chrono::steady_clock::duration>(std::chrono::duration<double>(rep.leaf_seconds));
             // leaves (exact grower): route every instance through a copy of the tree whose leaves hold their index
@@ -944,6 +972,7 @@ class LambdaMARTTrainer {
                 stats_.goss_instances.push_back(rep.goss_instances);
                 stats_.goss_top.push_back(rep.goss_top);
             }
+            if (quant) stats_.t_quant += rep.quant_seconds;
             if (hist && p_.symmetric_trees) stats_.levels.push_back(rep.levels);
             stats_.train_measure.push_back(mean);
             out.members.push_back(std::move(tm));

@@ -28,6 +28,11 @@
 // its interval, the device's candidates are those of the regularised scan kernels (with or without monotone signs), and the
 // host prices a node's own term, the children's outputs and intervals and the leaves by lambdamart_reg.hpp.  With all three at
 // 0 nothing here differs.
+// quantised gradients ("Quantised gradients"; lambdamart_quant.hpp, kernels_histquant.inc; Newton gain
+// only, without monotone signs or leaf regularisation): grow() is handed the tree's key; after the fixed-point step the device
+// rounds every entry's (Q, W) stochastically to quant_bits bits, and the tree carries two exponent pairs: the search's
+// (how_.s_l / s_w = S - d, S_w - d_w: every sum a search returns is one of the small integers) and the leaves' (leaf_s_l_ /
+// leaf_s_w_ = S, S_w: the leaf sums are still those of Q and W).  With quant_bits = 0 the two pairs are equal and nothing differs.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -35,6 +40,7 @@
 
 #include "host.hpp"
 #include "lambdamart_goss.hpp"
+#include "lambdamart_quant.hpp"
 #include "lambdamart_reg.hpp"
 
 namespace fr {
@@ -61,6 +67,7 @@ struct HistGrowOptions {
     std::vector<int> monotone;
     bool symmetric = false;
     HistReg reg;  // leaf regularisation (all 0: off; a non-zero one needs the Newton gain)
+    uint32_t quant_bits = 0;  // quantised gradients (0: off; 2..8 need the Newton gain, no monotone sign and no leaf regularisation)
 };
 
 // what grow() reports of the tree it made, next to the tree
@@ -73,6 +80,7 @@ struct HistTreeReport {
     uint32_t goss_instances = 0, goss_top = 0;
     uint64_t goss_tau = 0;
     double goss_seconds = 0.0;
+    double quant_seconds = 0.0;  // quantised gradients: the wall seconds of the quantise launch
 };
 
 class HistGrower {
@@ -80,7 +88,7 @@ class HistGrower {
 
   public:
     HistGrower(Dev& dev, std::vector<uint32_t> feats, const HistGrowOptions& opt)
-        : dev_(dev), feats_(std::move(feats)), k_(opt.k), max_depth_(opt.max_depth), min_leaf_(opt.min_leaf), newton_(opt.newton), max_leaves_(opt.max_leaves), symmetric_(opt.symmetric), reg_(opt.reg), reg_on_(opt.reg.on()) {
+        : dev_(dev), feats_(std::move(feats)), k_(opt.k), max_depth_(opt.max_depth), min_leaf_(opt.min_leaf), newton_(opt.newton), max_leaves_(opt.max_leaves), symmetric_(opt.symmetric), reg_(opt.reg), reg_on_(opt.reg.on()), quant_bits_(opt.quant_bits) {
         for (int c : opt.monotone) mono_on_ = mono_on_ || c != 0;
         if (symmetric_ && max_leaves_ != 0) fail_str("LambdaMART histogram grower: symmetric trees are grown level by level (max_leaves must be 0)");
         if (symmetric_ && mono_on_) fail_str("LambdaMART histogram grower: symmetric trees take no monotone constraints");
@@ -93,6 +101,12 @@ class HistGrower {
             if (!newton_.on) fail_str("LambdaMART histogram grower: lambda_l1, max_delta_step and path_smooth need the Newton gain");
             if (symmetric_ && reg_.path_smooth != 0.0) fail_str("LambdaMART histogram grower: symmetric trees take no path_smooth");
             if (!mono_on_) mono_.assign(feats_.size(), 0);  // (the regularised scan kernels read a sign per feature)
+        }
+        if (quant_bits_ != 0) {
+            if (!quant_bits_ok(quant_bits_)) fail_str("LambdaMART histogram grower: grad_quant_bits must be 0 or between 2 and 8");
+            if (!newton_.on) fail_str("LambdaMART histogram grower: quantised gradients need the Newton gain");
+            if (mono_on_ || reg_on_)
+                fail_str("LambdaMART histogram grower: quantised gradients take no monotone constraints, lambda_l1, max_delta_step or path_smooth");
         }
     }
     ~HistGrower() { dev_.hist_end(); }
@@ -132,11 +146,13 @@ class HistGrower {
 
     // One tree for the gradients of the last gradient pass (lam_list == nullptr) or for lam_list / wt_list[n] in
     // instance-list order.  goss (nullptr: none; Newton gain only): the tree is fitted to the GOSS list of the sample's list.
-    // *report (may be nullptr): what else the tree left behind.
-    // The calls a tree makes, in order: hist_goss (GOSS only), hist_quantise; level-wise hist_root, then per level
+    // *report (may be nullptr): what else the tree left behind.  quant_key: the tree's key under quantised gradients (read only
+    // when the grower was made with quant_bits != 0).
+    // The calls a tree makes, in order: hist_goss (GOSS only), hist_quantise, hist_quantq (quantised gradients only); level-wise hist_root, then per level
     // hist_search (symmetric trees: hist_search_symmetric and hist_symmetric_apply) and hist_split; leaf-wise
     // hist_leaf_begin, then one hist_leaf_step per split; at the end hist_leaf_sums (after hist_root, when nothing was searched).
-    std::shared_ptr<TreeNode> grow(const double* lam_list, const double* wt_list, const HistGoss* goss = nullptr, HistTreeReport* report = nullptr) {
+    std::shared_ptr<TreeNode> grow(const double* lam_list, const double* wt_list, const HistGoss* goss = nullptr, HistTreeReport* report = nullptr,
+                                   uint64_t quant_key = 0) {
         std::string err;
         HistTreeReport rep;
         bool all_zero = false;
@@ -153,8 +169,16 @@ class HistGrower {
         how_ = {min_leaf_, newton_.on, 0, 0, newton_.lambda_l2, newton_.min_sum_hessian, newton_.min_split_gain, mono_on_,
                 reg_.lambda_l1, reg_.max_delta_step, reg_.path_smooth};
         if (!dev_.hist_quantise(lam_list, wt_list, &how_.s_l, &how_.s_w, &all_zero, &err)) fail_str(err);
+        leaf_s_l_ = how_.s_l, leaf_s_w_ = how_.s_w;
         auto root = std::make_shared<TreeNode>();
         if (!all_zero) {  // (else one leaf of value 0.0)
+            if (quant_bits_ != 0) {  // the searches read sums of (1, q, w) under (S - d, S_w - d_w); the leaves stay with Q / W
+                auto t0 = std::chrono::steady_clock::now();
+                int d = 0, d_w = 0;
+                if (!dev_.hist_quantq(quant_bits_, quant_key, &d, &d_w, &err)) fail_str(err);
+                how_.s_l -= d, how_.s_w -= d_w;
+                rep.quant_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            }
             Leaves lv;
             const bool rooted = max_leaves_ >= 2 ? grow_leaves(root.get(), &lv) : grow_levels(root.get(), &lv, &rep.levels);
             rep.leaves = (uint32_t)lv.nodes.size();
@@ -440,7 +464,8 @@ class HistGrower {
         else lhs->lo = mid, rhs->hi = mid;
     }
 
-    // Leaf values from the leaves' integer sums.  rooted = false: the tree never searched, and the index list the sums are
+    // Leaf values from the leaves' integer sums of Q and W, under the leaves' exponents (the search's own unless the gradients
+    // are quantised).  rooted = false: the tree never searched, and the index list the sums are
     // taken over is made here, as the root's.
     // Under monotone constraints a value is clamped to its leaf's interval, and the moved ones are counted.
     void leaf_values(const Leaves& lv, bool rooted, HistTreeReport* rep) {
@@ -455,17 +480,17 @@ class HistGrower {
                 const uint32_t n = lv.stretches[i].end - lv.stretches[i].begin;
                 const double* parent = lv.has_parent[i] ? &lv.parent_out[i] : nullptr;
                 const Dev::HistBounds line = whole_line();
-                const double v = reg_side(q, w, n, how_.s_l, how_.s_w, newton_.lambda_l2, reg_, parent, lv.bounds[i].lo, lv.bounds[i].hi).v;
-                if (mono_on_ && v != reg_side(q, w, n, how_.s_l, how_.s_w, newton_.lambda_l2, reg_, parent, line.lo, line.hi).v) rep->clamped_leaves++;
+                const double v = reg_side(q, w, n, leaf_s_l_, leaf_s_w_, newton_.lambda_l2, reg_, parent, lv.bounds[i].lo, lv.bounds[i].hi).v;
+                if (mono_on_ && v != reg_side(q, w, n, leaf_s_l_, leaf_s_w_, newton_.lambda_l2, reg_, parent, line.lo, line.hi).v) rep->clamped_leaves++;
                 lv.nodes[i]->value = v;
             } else if (newton_.on) {
-                const double den = std::ldexp((double)w, -how_.s_w) + newton_.lambda_l2;
-                const double out = den != 0.0 ? std::ldexp((double)q, -how_.s_l) / den : 0.0;
+                const double den = std::ldexp((double)w, -leaf_s_w_) + newton_.lambda_l2;
+                const double out = den != 0.0 ? std::ldexp((double)q, -leaf_s_l_) / den : 0.0;
                 const double v = mono_on_ ? clamp(out, lv.bounds[i]) : out;
                 if (mono_on_ && v != out) rep->clamped_leaves++;
                 lv.nodes[i]->value = v;
             } else {
-                lv.nodes[i]->value = w != 0 ? std::ldexp((double)q, -how_.s_l) / std::ldexp((double)w, -how_.s_w) : 0.0;
+                lv.nodes[i]->value = w != 0 ? std::ldexp((double)q, -leaf_s_l_) / std::ldexp((double)w, -leaf_s_w_) : 0.0;
             }
         }
         rep->leaf_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -485,6 +510,7 @@ class HistGrower {
     uint32_t n_sample_ = 0;                                    // the sample's instances: n_ unless the tree is a GOSS one
     HistNewton newton_;
     Dev::HistSearch how_{};                                    // the tree's search parameters, its exponents s_l / s_w among them
+    int leaf_s_l_ = 0, leaf_s_w_ = 0;                          // the exponents of the leaf sums (quantised gradients: not the search's)
     uint32_t max_leaves_ = 0;                                  // 0: level-wise growth
     uint64_t pool_bytes_ = 0;
     bool mono_on_ = false;                                     // some monotone sign is not 0
@@ -492,6 +518,7 @@ class HistGrower {
     bool symmetric_ = false;                                   // every node of a level splits on one candidate
     HistReg reg_;                                              // leaf regularisation's three numbers
     bool reg_on_ = false;                                      // one of them is not 0
+    uint32_t quant_bits_ = 0;                                  // quantised gradients: bits per value (0: off)
     std::vector<uint32_t> sel_;                                // the tree's features as slots of the bins (empty: all)
     std::vector<float> edges_;
     std::vector<uint32_t> nedges_;

@@ -20,7 +20,7 @@ bool DeviceDataset::hist_bins(const uint32_t* positions, size_t n, const std::ve
     for (uint32_t f : feats)
         if (f >= m.d) return hist_fail(err, "feature id outside the dataset");
     if (h.k == k && h.n == n && h.feats == feats && std::equal(h.pos_host.begin(), h.pos_host.end(), positions)) {
-        h.nt = h.n, h.Ft = h.F, h.q_sampled = h.f_sampled = h.g_on = false;  // (no sample until hist_sample says so)
+        h.nt = h.n, h.Ft = h.F, h.q_sampled = h.f_sampled = h.g_on = h.qz_on = false;  // (no sample until hist_sample says so)
         return true;
     }
     h.k = 0;  // (nothing valid until the end of this function)
@@ -75,7 +75,7 @@ bool DeviceDataset::hist_bins(const uint32_t* positions, size_t n, const std::ve
     h.mono_F = 0;
     h.feats = feats;
     h.n = n32, h.F = (uint32_t)F, h.k = k;
-    h.nt = n32, h.Ft = (uint32_t)F, h.q_sampled = h.f_sampled = h.g_on = false;
+    h.nt = n32, h.Ft = (uint32_t)F, h.q_sampled = h.f_sampled = h.g_on = h.qz_on = false;
     if (built) *built = true;
     return true;
 }
@@ -139,7 +139,7 @@ bool DeviceDataset::hist_sample(const unsigned char* query_flags, uint32_t n_t, 
     auto& h = m.hist;
     if (h.k == 0) return hist_fail(err, "no bins built");
     const uint32_t n = h.n;
-    h.g_on = false;  // (GOSS is a tree's: hist_goss sets it after the sample)
+    h.g_on = h.qz_on = false;  // (GOSS and the quantised gradients are a tree's: hist_goss / hist_quantq set them after the sample)
     if (keep_queries && query_flags == nullptr && h.q_sampled) {  // (the root list and its length stay)
         n_t = h.nt;
         h.Ft = h.F, h.f_sampled = false;
@@ -181,6 +181,7 @@ bool DeviceDataset::hist_quantise(const double* lam_list, const double* wt_list,
     if (!m.bind(err)) return false;
     auto& h = m.hist;
     if (h.k == 0) return hist_fail(err, "no bins built");
+    h.qz_on = false;  // (a tree's: hist_quantq sets it after this)
     const uint32_t n = h.n, nt = h.tree_n();  // (host arrays and Q / W: the full list; the maxima, c and the quantisation: the tree's)
     const double *lam = nullptr, *wt = nullptr;
     const uint32_t *pos = nullptr, *root = h.tree_root();
@@ -228,6 +229,62 @@ bool DeviceDataset::hist_quantise(const double* lam_list, const double* wt_list,
         hist_quant_kernel<<<grid1d(nt, 256), 256, 0, m.stream>>>(lam, wt, pos, root, nt, *s_l, *s_w, mx[1] == 0.0 ? 1 : 0, h.Q.p, h.W.p);
     }
     FR_HIP(hipGetLastError());
+    return true;
+}
+
+// Quantised gradients (kernels_histquant.inc): one launch over the tree's list; waited for, so that quant_ms is its time
+bool DeviceDataset::hist_quantq(uint32_t bits, uint64_t tree_key, int* d, int* d_w, std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    if (h.k == 0) return hist_fail(err, "no bins built");
+    h.qz_on = false;
+    if (bits < fr::QUANT_MIN_BITS || bits > fr::QUANT_MAX_BITS) return hist_fail(err, "internal error: grad_quant_bits outside 2..8");
+    const uint32_t nt = h.tree_n();
+    if (nt == 0 || h.Q.cap < h.n || h.W.cap < h.n) return hist_fail(err, "internal error: no fixed-point gradients to quantise");
+    const fr::QuantShifts sh = fr::quant_shifts(nt, bits);
+    if (sh.d < 1 || sh.d > 63 || sh.d_w < 1 || sh.d_w > 63) return hist_fail(err, "internal error: a quantisation shift outside 1..63");
+    if (!h.packed.ensure(h.n, err)) return false;
+    {
+        ProfScope ps("hist_quantq_kernel", m.stream);
+        hist_quantq_kernel<<<grid1d(nt, 256), 256, 0, m.stream>>>(h.Q.p, h.W.p, h.tree_root(), h.pos.p, m.perm.p, nt, tree_key, sh.d, sh.d_w, h.packed.p);
+    }
+    FR_HIP(hipGetLastError());
+    FR_HIP(hipStreamSynchronize(m.stream));
+    *d = sh.d, *d_w = sh.d_w;
+    h.qz_on = true;
+    return true;
+}
+
+bool DeviceDataset::hist_quantq_download(int32_t* q, uint32_t* w, size_t len, std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    if (!h.qz_on || len != h.tree_n()) return hist_fail(err, "no quantised gradients of that length");
+    std::vector<uint32_t> by_index(h.n), list(h.tree_root() != nullptr ? len : 0);
+    FR_HIP(hipMemcpyAsync(by_index.data(), h.packed.p, (size_t)h.n * sizeof(uint32_t), hipMemcpyDeviceToHost, m.stream));
+    if (!list.empty()) FR_HIP(hipMemcpyAsync(list.data(), h.tree_root(), len * sizeof(uint32_t), hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipStreamSynchronize(m.stream));
+    for (size_t i = 0; i < len; i++) {
+        const uint32_t p = by_index[list.empty() ? i : list[i]];
+        q[i] = fr::quant_unpack_q(p), w[i] = fr::quant_unpack_w(p);
+    }
+    return true;
+}
+
+bool DeviceDataset::hist_root_download(uint32_t* cnt, long long* sum, long long* wsum, size_t cells, std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& h = m.hist;
+    if (h.k == 0 || cells != (size_t)h.Ft * h.k || h.cnt.cap < cells || h.sum.cap < cells || h.wsum.cap < cells)
+        return hist_fail(err, "no root histogram of that size");
+    FR_HIP(hipMemcpyAsync(cnt, h.cnt.p, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipMemcpyAsync(sum, h.sum.p, cells * sizeof(long long), hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipMemcpyAsync(wsum, h.wsum.p, cells * sizeof(long long), hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipStreamSynchronize(m.stream));
     return true;
 }
 
@@ -328,6 +385,14 @@ void DeviceDataset::Impl::hist_build(uint32_t* cnt, unsigned long long* sum, uns
             hist_build_kernel<true><<<grid, 256, lds, stream>>>(h.items_b.p, h.xbin.p, h.n, h.idx.p, h.Q.p, fsel, h.Ft, h.k, cnt, sum);
         else
             hist_build_kernel<false><<<grid, 256, lds, stream>>>(h.items_b.p, h.xbin.p, h.n, h.idx.p, h.Q.p, fsel, h.Ft, h.k, cnt, sum);
+    } else if (h.qz_on) {  // (quantised gradients: the packed values instead of Q / W, the same three arrays out)
+        ProfScope ps("hist_build_packed_kernel", stream);
+        const dim3 grid((unsigned)h.items_bh.size(), (h.Ft + HIST_FB_PACKED - 1) / HIST_FB_PACKED);
+        const size_t lds = (size_t)HIST_FB_PACKED * h.k * 8;
+        if (h.f_sampled)
+            hist_build_packed_kernel<true><<<grid, 256, lds, stream>>>(h.items_b.p, h.xbin.p, h.n, h.idx.p, h.packed.p, fsel, h.Ft, h.k, cnt, sum, wsum);
+        else
+            hist_build_packed_kernel<false><<<grid, 256, lds, stream>>>(h.items_b.p, h.xbin.p, h.n, h.idx.p, h.packed.p, fsel, h.Ft, h.k, cnt, sum, wsum);
     } else {
         ProfScope ps("hist_build_newton_kernel", stream);
         const dim3 grid((unsigned)h.items_bh.size(), (h.Ft + HIST_FB_NEWTON - 1) / HIST_FB_NEWTON);

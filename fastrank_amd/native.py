@@ -220,7 +220,7 @@ def hist_tree(dataset: CDataset, lam: np.ndarray, wt: np.ndarray, split_candidat
               min_leaf_support: int, queries=None, features=None, split_gain: str = "variance", lambda_l2: float = 0.0,
               min_sum_hessian: float = 0.0, min_split_gain: float = 0.0, max_leaves: int = 0, monotone=None,
               clamped_out: Optional[list] = None, goss=None, symmetric: bool = False, lambda_l1: float = 0.0,
-              max_delta_step: float = 0.0, path_smooth: float = 0.0) -> CModel:
+              max_delta_step: float = 0.0, path_smooth: float = 0.0, quant=None) -> CModel:
     """One tree of LambdaMART's histogram grower for the gradients lam / wt (indexed by instance id).  `queries` (indices of
     the view's queries) / `features` (feature ids): the tree's sample; gradients outside the query sample are not read.
     `split_gain` = "newton": the second-order gain with `lambda_l2`, `min_sum_hessian` and `min_split_gain` (DESIGN.md
@@ -233,8 +233,10 @@ def hist_tree(dataset: CDataset, lam: np.ndarray, wt: np.ndarray, split_candidat
     11, "GOSS"); level-wise or leaf-wise, with or without monotone signs.  `symmetric` = True (level-wise, without monotone
     signs or GOSS): every node of a level splits on the level's one winning candidate ("Symmetric
     trees"), under either gain.  `lambda_l1`, `max_delta_step`, `path_smooth` (need `split_gain` = "newton"; `path_smooth` not
-    with `symmetric`): the leaf regularisation ("Leaf regularisation"); all 0.0: off.  Arguments that
-    contradict each other raise ValueError before the one native call."""
+    with `symmetric`): the leaf regularisation ("Leaf regularisation"); all 0.0: off.  `quant` = (bits, seed, tree) (needs
+    `split_gain` = "newton"; no monotone sign, no leaf regularisation): the searches read gradients quantised to `bits` bits
+    (2..8) under the key of tree `tree` of `seed`, the leaves are renewed from the full-precision sums (DESIGN.md section 11,
+    "Quantised gradients").  Arguments that contradict each other raise ValueError before the one native call."""
     lam = np.ascontiguousarray(lam, dtype=np.float64)
     wt = np.ascontiguousarray(wt, dtype=np.float64)
     newton = split_gain == "newton"
@@ -262,6 +264,11 @@ def hist_tree(dataset: CDataset, lam: np.ndarray, wt: np.ndarray, split_candidat
         raise ValueError("lambda_l1, max_delta_step and path_smooth need split_gain='newton'")
     if symmetric and reg[2] != 0.0:
         raise ValueError("symmetric trees take no path_smooth")
+    quant_bits, quant_seed, quant_tree = (0, 0, 0) if quant is None else (int(x) for x in quant)
+    if quant is not None and not 2 <= quant_bits <= 8:
+        raise ValueError("quant bits must be between 2 and 8")
+    if quant is not None and (not newton or mono or any(x != 0.0 for x in reg)):
+        raise ValueError("quant needs split_gain='newton', and takes no monotone constraints or leaf regularisation")
     qs = None if queries is None else np.ascontiguousarray(queries, dtype=np.uint32)
     fs = None if features is None else np.ascontiguousarray(features, dtype=np.uint32)
     mf = np.ascontiguousarray(list(mono.keys()), dtype=np.uint32)
@@ -275,7 +282,7 @@ def hist_tree(dataset: CDataset, lam: np.ndarray, wt: np.ndarray, split_candidat
         features=None if fs is None else fs.ctypes.data, n_features=0 if fs is None else len(fs),
         mono_features=mf.ctypes.data if mono else None, mono_signs=ms.ctypes.data if mono else None, n_mono=len(mono),
         goss=0 if goss is None else 1, top_rate=float(top_rate), other_rate=float(other_rate), seed=int(seed), tree=int(tree),
-        lambda_l1=reg[0], max_delta_step=reg[1], path_smooth=reg[2],
+        lambda_l1=reg[0], max_delta_step=reg[1], path_smooth=reg[2], quant_bits=quant_bits, quant_seed=quant_seed, quant_tree=quant_tree,
     )
     clamped = C.c_uint32(0)
     model = CModel(
@@ -322,6 +329,63 @@ def goss_select(dataset: CDataset, lam: np.ndarray, top_rate: float, other_rate:
         )
     )
     return rows[: n_g.value].copy(), top[: n_g.value].astype(bool), int(tau.value)
+
+
+def hist_quantise(dataset: CDataset, lam: np.ndarray, wt: np.ndarray, bits: int, seed: int, tree: int, queries=None, goss=None) -> dict:
+    """The fixed-point step and the quantised gradients of one tree on their own ("Quantised
+    gradients") for lam / wt (by instance id) under the key of tree `tree` of `seed`.  `queries` (indices of the view's
+    queries): the tree's query sample; `goss` = (top_rate, other_rate, seed, tree): the tree's list is the GOSS list of the
+    sample's instances, its values the amplified ones.  Returns dict(q, w: int64 arrays by index of the tree's list; s_l, s_w:
+    the exponents S and S_w; search_s_l, search_s_w: S - d and S_w - d_w; d, d_w: the two shifts)."""
+    lam = np.ascontiguousarray(lam, dtype=np.float64)
+    wt = np.ascontiguousarray(wt, dtype=np.float64)
+    if lam.shape != wt.shape or lam.ndim != 1:
+        raise ValueError("lam and wt must be 1-d arrays of the same length")
+    n = sum(len(ids) for ids in dataset.instances_by_query().values())
+    qs = None if queries is None else np.ascontiguousarray(queries, dtype=np.uint32)
+    top_rate, other_rate, goss_seed, goss_tree = (0.0, 0.0, 0, 0) if goss is None else goss
+    q = np.zeros(n, dtype=np.int32)
+    w = np.zeros(n, dtype=np.uint32)
+    n_out = C.c_uint32(0)
+    numbers = np.zeros(6, dtype=np.int32)
+    _status(
+        _load().fr_debug_hist_quantise(
+            dataset.pointer, lam.ctypes.data, wt.ctypes.data, lam.shape[0], int(bits), int(seed), int(tree),
+            None if qs is None else qs.ctypes.data, 0 if qs is None else len(qs), 0 if goss is None else 1, float(top_rate), float(other_rate),
+            int(goss_seed), int(goss_tree), q.ctypes.data, w.ctypes.data, n, C.byref(n_out), numbers.ctypes.data,
+        )
+    )
+    names = ("s_l", "s_w", "search_s_l", "search_s_w", "d", "d_w")
+    out = {k: int(v) for k, v in zip(names, numbers)}
+    out["q"], out["w"] = q[: n_out.value].astype(np.int64), w[: n_out.value].astype(np.int64)
+    return out
+
+
+def hist_root_histogram(dataset: CDataset, lam: np.ndarray, wt: np.ndarray, split_candidates: int, quant=None, features=None):
+    """The root's histogram of one tree over every instance of the view, for lam / wt (by instance id): (count, sum Q, sum W)
+    as int64 arrays [features][split_candidates].  `quant` = (bits, seed, tree): the packed build over the quantised values
+    ("Quantised gradients"); None: the Newton build over the fixed-point values.  `features` (feature
+    ids): the tree's feature sample."""
+    lam = np.ascontiguousarray(lam, dtype=np.float64)
+    wt = np.ascontiguousarray(wt, dtype=np.float64)
+    if lam.shape != wt.shape or lam.ndim != 1:
+        raise ValueError("lam and wt must be 1-d arrays of the same length")
+    bits, seed, tree = (0, 0, 0) if quant is None else (int(x) for x in quant)
+    if quant is not None and not 2 <= bits <= 8:
+        raise ValueError("quant bits must be between 2 and 8")
+    fs = None if features is None else np.ascontiguousarray(features, dtype=np.uint32)
+    F = len(dataset.feature_ids()) if fs is None else len(fs)
+    k = int(split_candidates)
+    cnt = np.zeros(F * k, dtype=np.uint32)
+    qs = np.zeros(F * k, dtype=np.int64)
+    ws = np.zeros(F * k, dtype=np.int64)
+    _status(
+        _load().fr_debug_hist_root_histogram(
+            dataset.pointer, lam.ctypes.data, wt.ctypes.data, lam.shape[0], k, bits, seed, tree, None if fs is None else fs.ctypes.data,
+            0 if fs is None else len(fs), cnt.ctypes.data, qs.ctypes.data, ws.ctypes.data, F * k,
+        )
+    )
+    return cnt.astype(np.int64).reshape(F, k), qs.reshape(F, k), ws.reshape(F, k)
 
 
 def rank_order(model: CModel, dataset: CDataset) -> Tuple[np.ndarray, np.ndarray]:

@@ -159,6 +159,13 @@ class LambdaMARTParams(_LearnerParams):
     steadies small, deep leaves.  Histogram grower under `split_gain` = "newton" only, level-wise and leaf-wise, with
     every other key; `path_smooth` cannot be combined with `symmetric_trees`.  The training stats then report the three
     keys ("Leaf regularisation").
+    `grad_quant_bits` = b (0, the default, = off, or 2..8; written only when set): quantised training.  After the gradient
+    pass every tree rounds its gradients and hessians stochastically (unbiased) to b bits, searches its splits over
+    histograms of those small integers, which the device builds with one packed atomic per update, and renews its leaves
+    from the full-precision sums.  The rounding is a function of `seed`, the tree and the document (a stream of its own),
+    so two runs give the same model.  Histogram grower under `split_gain` = "newton" only; composes with every other key
+    but `monotone_constraints`, `lambda_l1`, `max_delta_step` and `path_smooth`, which are refused.  The training stats then
+    report `grad_quant_bits` and `quant_ms` ("Quantised gradients").
     Two things are arguments of `CDataset.train_model`, not keys: `valid` (a second dataset the held-out measure and early
     stopping are read from; `validation_queries` must then be empty and `early_stopping_rounds` needs no held-out query)
     and `init_model` (an Ensemble of DecisionTrees training continues from: `num_trees` counts new trees, and the per-tree
@@ -197,6 +204,7 @@ class LambdaMARTParams(_LearnerParams):
     lambda_l1: float = 0.0
     max_delta_step: float = 0.0
     path_smooth: float = 0.0
+    grad_quant_bits: int = 0
 
     _WIRE_DEFAULTS: ClassVar[Dict[str, Any]] = {"grower": "exact", "query_sampling_rate": 1.0, "feature_sampling_rate": 1.0, "seed": 0,
                                                 "validation_queries": [], "early_stopping_rounds": 0, "split_gain": "variance",
@@ -204,7 +212,7 @@ class LambdaMARTParams(_LearnerParams):
                                                 "max_leaves": 0, "truncation_level": 0, "lambda_norm": False, "objective": "ndcg",
                                                 "drop_rate": 0.0, "max_drop": 50, "skip_drop": 0.5, "monotone_constraints": {},
                                                 "goss_top_rate": 0.0, "goss_other_rate": 0.1, "symmetric_trees": False,
-                                                "lambda_l1": 0.0, "max_delta_step": 0.0, "path_smooth": 0.0}
+                                                "lambda_l1": 0.0, "max_delta_step": 0.0, "path_smooth": 0.0, "grad_quant_bits": 0}
     _OBJECTIVES: ClassVar[Dict[str, str]] = {"ap": "map", "rr": "mrr", "xendcg": "xendcg"}
 
     def __post_init__(self):

@@ -278,6 +278,12 @@ typedef struct FrHistTreeOptions {
     double top_rate, other_rate;
     uint64_t seed;
     uint32_t tree;
+    /* quant_bits != 0 ("Quantised gradients"; 2..8; Newton gain only, without monotone signs or leaf regularisation): the
+     * searches read sums of gradients rounded stochastically to quant_bits bits under the key of tree quant_tree of the request
+     * seed quant_seed; the leaves are renewed from the full-precision sums.  (The record still ends with the three doubles.) */
+    uint32_t quant_bits;
+    uint64_t quant_seed;
+    uint32_t quant_tree;
     /* "Leaf regularisation" (Newton gain only; finite and >= 0, all 0: off): the gradient sum is soft-thresholded by
      * lambda_l1, an output's magnitude is capped at max_delta_step, a child's output is pulled toward its parent's by
      * path_smooth (not with symmetric). */
@@ -301,6 +307,22 @@ const void *fr_debug_hist_reg_term(int64_t q, int64_t w, uint32_t n, int32_t s_l
 const void *fr_debug_goss_select(const CDataset *dataset, const double *lambda, size_t len, double top_rate,
                                  double other_rate, uint64_t seed, uint32_t tree, const uint32_t *queries, size_t n_queries,
                                  uint32_t *list_out, uint8_t *top_out, size_t cap, uint32_t *n_g_out, uint64_t *tau_out);
+/* Quantised gradients, test hooks ("Quantised gradients").  fr_debug_hist_quantise: the fixed-point step
+ * and the quantisation to `bits` bits (2..8) under the key of tree `tree` of `seed`, for lambda / weight[len] by instance id
+ * over the instances of queries[n_queries] (NULL = all) and, when goss != 0, over the GOSS list of those (rates, seed and tree
+ * as in FrHistTreeOptions) with amplified values.  q_out / w_out[cap] (cap >= the view's instances): the values by index of the
+ * tree's list; *n_out: its length; numbers_out[6] = S, S_w, the search's two exponents S - d and S_w - d_w, d, d_w.
+ * fr_debug_hist_root_histogram: the root's histogram over every instance for the features features[n_features] (NULL = all):
+ * count_out / sum_out / wsum_out[cells], cells = features x split_candidates, laid out [feature][bin]; bits == 0: the Newton
+ * build over the fixed-point values, else the packed build over the quantised ones. */
+const void *fr_debug_hist_quantise(const CDataset *dataset, const double *lambda, const double *weight, size_t len,
+                                   uint32_t bits, uint64_t seed, uint32_t tree, const uint32_t *queries, size_t n_queries,
+                                   int32_t goss, double top_rate, double other_rate, uint64_t goss_seed, uint32_t goss_tree,
+                                   int32_t *q_out, uint32_t *w_out, size_t cap, uint32_t *n_out, int32_t *numbers_out);
+const void *fr_debug_hist_root_histogram(const CDataset *dataset, const double *lambda, const double *weight, size_t len,
+                                         uint32_t split_candidates, uint32_t bits, uint64_t seed, uint32_t tree,
+                                         const uint32_t *features, size_t n_features, uint32_t *count_out, int64_t *sum_out,
+                                         int64_t *wsum_out, size_t cells);
 /* fr_debug_lambda_gradients under the LambdaRank objective's options ("Truncation and
  * normalisation").  options_json = {"truncation_level": T, "lambda_norm": bool}, either key optional: T >= 1 keeps a pair
  * only when the better ranked of its two documents is in the top T of the pass's ranks (0, the default: every pair);

@@ -22,6 +22,8 @@
                                                                # monotone constraints on the first 8 features, signs +1, -1, +1, ...
     python tools/lmbench.py --shape 30k --trees 100 --grower histogram --split-gain newton --goss-top-rate 0.2 --goss-other-rate 0.1
                                                                # gradient-based one-side sampling (reports goss_ms and the lists' sizes)
+    python tools/lmbench.py --shape 30k --trees 100 --grower histogram --split-gain newton --grad-quant-bits 4
+                                                               # quantised gradients: 4 bits per gradient (reports quant_ms)
     python tools/lmbench.py --shape 30k --trees 100 --grower histogram --symmetric --validation-rate 0.1
                                                                # symmetric trees (reports the levels that split per tree)
     python tools/lmbench.py --shape 30k --trees 100 --grower histogram --valid-dataset-rate 0.1
@@ -82,6 +84,7 @@ def device_run(args, X, y, qid):
     if args.symmetric:
         req.params.symmetric_trees = True
     req.params.lambda_l1, req.params.max_delta_step, req.params.path_smooth = args.lambda_l1, args.max_delta_step, args.path_smooth
+    req.params.grad_quant_bits = args.grad_quant_bits
     if args.monotone:  # the first N features of the dataset, alternating signs from +1
         names = ds.feature_index_to_name()
         first = sorted(names)[:args.monotone]
@@ -178,6 +181,8 @@ def device_run(args, X, y, qid):
     if args.symmetric:  # (only with the key, like the stats object)
         out["symmetric"] = {"levels_mean": float(np.mean(st["levels"])), "levels_min": int(np.min(st["levels"])),
                             "levels_max": int(np.max(st["levels"]))}
+    if args.grad_quant_bits:  # (only with the key, like the stats object)
+        out["grad_quant"] = {"grad_quant_bits": st["grad_quant_bits"], "quant_ms_per_tree": st["quant_ms"] / T}
     if args.lambda_l1 or args.max_delta_step or args.path_smooth:  # (only with a key, like the stats object)
         out["leaf_regularisation"] = {k: st[k] for k in ("lambda_l1", "max_delta_step", "path_smooth")}
     if args.held_out_measures and args.validation_rate > 0:  # AP / RR / NDCG of the model over the held-out queries
@@ -247,6 +252,7 @@ def parser():
     ap.add_argument("--monotone", type=int, default=0, help="monotone constraints on the first N features, signs alternating from +1 (needs --split-gain newton)")
     ap.add_argument("--goss-top-rate", type=float, default=0.0, help="GOSS: the share of a tree's documents kept for their |gradient| (0: off; needs --split-gain newton)")
     ap.add_argument("--goss-other-rate", type=float, default=0.1, help="GOSS: the share of a tree's documents drawn from the others")
+    ap.add_argument("--grad-quant-bits", type=int, default=0, help="quantised gradients: bits per gradient, 2..8 (0: off; needs --split-gain newton)")
     ap.add_argument("--symmetric", action="store_true", help="symmetric trees: every node of a level splits on one candidate (histogram grower, level-wise)")
     ap.add_argument("--lambda-l1", type=float, default=0.0, help="leaf regularisation: soft threshold of a node's gradient sum (needs --split-gain newton)")
     ap.add_argument("--max-delta-step", type=float, default=0.0, help="leaf regularisation: cap of an output's magnitude (0: none; needs --split-gain newton)")
