@@ -173,7 +173,8 @@ struct RfCandDev {
     double position;    // the threshold (random_forest.rs:238)
     double importance;  // methods 0 / 3; NaN marks "the reference would have panicked" (variance of < 2 labels)
     uint32_t ids_i;     // instances strictly below the threshold
-    uint32_t flags;     // 1: evaluated (a new position with both sides >= min_leaf_support)
+    uint32_t flags;     // 1: evaluated (a new position with both sides >= min_leaf_support); the reference panics on this
+                        // (node, feature) if the node's labels differ -- 2: a NaN among its values, 4: a NaN position (rf_eval_kernel)
     uint32_t pos_l, pos_r;  // instances with gain > 0 on each side (methods 1 / 2)
     double sum_l, sum_r;    // method 0: the sequential gain sums of both sides in this segment's order -- what compute_output of
                             // the children divides by their sizes (random_forest.rs:32-41, 395-398) if this candidate is chosen
@@ -285,13 +286,26 @@ __global__ __launch_bounds__(64) void rf_eval_kernel(RFArgs a, uint32_t k, int m
     const float* g = a.sg + off;
     // FeatureStats of this (node, feature): min / max over the values the node's instances hold and how many there are.
     // Everything held (the usual case): the ends of the sorted segment.
+    // Non-finite values: StreamingStats::push (stats.rs:46-47, 74-79) starts at min = f64::MAX, max = f64::MIN and compares with
+    // > and <, so a NaN is counted but becomes neither, a segment of nothing but +inf keeps min = f64::MAX and one of nothing but
+    // -inf keeps max = f64::MIN.  A NaN among the segment's values (Scored::new, random_forest.rs:228) or a NaN position
+    // (NotNan::new(..).unwrap(), :238 -- a minimum of -inf) is a panic there: flags 2 and 4 of every candidate of the segment, for the
+    // host to raise once it knows that the node's labels differ.  rf_float_key sorts a NaN of the sign bit's side below -inf and the
+    // others above +inf, so the ends of the sorted segment show one of either kind.
     double fmin = 0.0, fmax = 0.0;
     uint32_t held = n;
+    bool has_nan = false;
     if (a.pres == nullptr) {
-        if (n > 0) fmin = (double)v[0], fmax = (double)v[n - 1];
+        if (n > 0) {
+            const float v0 = v[0], v1 = v[n - 1];
+            has_nan = v0 != v0 || v1 != v1;
+            fmin = v0 == __builtin_huge_valf() ? 1.7976931348623157e308 : (double)v0;
+            fmax = v1 == -__builtin_huge_valf() ? -1.7976931348623157e308 : (double)v1;
+        }
     } else {
+        // (an absent value reads 0.0 in the reference's sort, never NaN: only held values are looked at)
         float lo = 3.4028234663852886e38f, hi = -3.4028234663852886e38f;
-        uint32_t cnt = 0;
+        uint32_t cnt = 0, nans = 0;
         for (uint32_t i = lane; i < n; i += 64) {
             const float x = v[i];
             const bool absent = __float_as_uint(x) == 0x80000000u;
@@ -299,14 +313,17 @@ __global__ __launch_bounds__(64) void rf_eval_kernel(RFArgs a, uint32_t k, int m
                 lo = fminf(lo, x);
                 hi = fmaxf(hi, x);
                 cnt++;
+                nans += x != x ? 1u : 0u;
             }
         }
         for (int o = 32; o > 0; o >>= 1) {
             lo = fminf(lo, __shfl_xor(lo, o));
             hi = fmaxf(hi, __shfl_xor(hi, o));
             cnt += __shfl_xor(cnt, o);
+            nans += __shfl_xor(nans, o);
         }
         held = cnt;
+        has_nan = nans != 0;
         fmin = (double)lo, fmax = (double)hi;
     }
     for (uint32_t cb = 0; cb < km1; cb += 64) {
@@ -328,6 +345,7 @@ __global__ __launch_bounds__(64) void rf_eval_kernel(RFArgs a, uint32_t k, int m
             const uint32_t ids_i = rf_lower_bound(v, n, position);
             r.position = position;
             r.ids_i = ids_i;
+            r.flags = (has_nan ? 2u : 0u) | (position != position ? 4u : 0u);
             bool fresh = true;  // random_forest.rs:249-253: a position equal to the previously pushed one is skipped
             if (c > 1) {
                 const double fprev = (double)(c - 1) / (double)k;
@@ -339,7 +357,7 @@ __global__ __launch_bounds__(64) void rf_eval_kernel(RFArgs a, uint32_t k, int m
         if (__any(valid)) {  // (uniform: the loops below contain block barriers)
             RfStream st;
             const uint32_t nr = n - nl;
-            if (valid) r.flags = 1;
+            if (valid) r.flags |= 1;
             if (method == 0) {  // SquaredError: -(sum_l (mean_l - g)^2 + sum_r (mean_r - g)^2), random_forest.rs:42-51,97-99
                 // A chunk lies entirely on one side of a lane's split except for the one chunk that contains it: when no
                 // lane's split falls into the chunk (the common case) every lane adds the whole chunk to ONE of its two

@@ -686,6 +686,18 @@ class LambdaMARTTrainer {
             auto tb0 = tnow();
             if (hist->prepare(positions)) stats_.t_bins = secs(tb0, tnow());
         }
+        // Non-finite feature values are refused, whichever grower: the histogram grower's edges are data values, so -inf can
+        // become a split, and the exact grower puts +inf where the reference's position rule does (random_forest.rs:238) --
+        // a tree that to_json writes as null, init_model refuses and explain refuses.  (A NaN under the histogram grower has
+        // failed above with the binning's own message.)  Read from the device form's per-column max |x|, which a query view
+        // inherits from the dataset it was sampled from: a view is refused by its parent's column.
+        {
+            const std::vector<double>& absmax = dev.column_absmax();
+            for (uint32_t f : feats)
+                if (f < absmax.size() && !std::isfinite(absmax[f]))
+                    fail_str("LambdaMART: feature " + std::to_string(f) + " holds an inf or NaN value (in this dataset, or in the dataset it is a query "
+                             "view of); trees are only trained on finite feature values");
+        }
         RFParams rp;
         rp.quiet = true;
         rp.num_trees = 1;

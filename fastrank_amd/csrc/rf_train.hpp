@@ -341,7 +341,13 @@ class RFTrainer {
         const uint32_t k = p_.split_candidates;
         // split_candidates < 2: `(1..k)` is empty (random_forest.rs:236), no feature yields a candidate and every node
         // stays the leaf it is -- nothing to ask the device
-        if (k < 2) open.clear();
+        if (k < 2) {
+            // (the values are still sorted before the empty list of thresholds is made: a NaN among them is the reference's
+            // panic here too, Scored::new at random_forest.rs:228.  Only roots are reached; read on the host.)
+            if (!lambda_targets_)
+                for (const Open& o : open) root_nan_check(root_ids.data() + root_off[o.tree], o.n, feats.data() + (size_t)o.tree * nf, nf);
+            open.clear();
+        }
         while (!open.empty()) {
             std::vector<frdev::DeviceDataset::RfActive> active(open.size());
             std::vector<uint32_t> slot_of_key(next_key, 0xFFFFFFFFu);
@@ -380,6 +386,20 @@ class RFTrainer {
                     bool fhave = false;
                     double fimp = 0.0, fsplit = 0.0, fsl = 0.0, fsr = 0.0;
                     uint32_t fpos = 0;
+                    {
+                        // Non-finite feature values (rf_eval_kernel sets these on every candidate of a segment with more than
+                        // one held value): the node's labels differ, so the reference goes on to sort this feature's values
+                        // and to place its thresholds, and panics -- in whichever tree, the whole call (random_forest.rs:305)
+                        const uint32_t bad = cands[((size_t)a * nf + fi) * km1].flags & 6u;
+                        if (bad) {
+                            const std::string where = "random forest: feature " + std::to_string(feats[(size_t)o.tree * nf + fi]) + ": ";
+                            if (bad & 2u)  // Scored::new, random_forest.rs:228
+                                fail_str(where + "NaN found!: FloatIsNan (a NaN feature value in a node that looks for a split)");
+                            // NotNan::new(f * range + stats.min).unwrap(), random_forest.rs:238
+                            fail_str(where + "called `Result::unwrap()` on an `Err` value: FloatIsNan (a split position is NaN: the "
+                                             "node's smallest value of the feature is -inf)");
+                        }
+                    }
                     for (uint32_t c = 0; c < km1; c++) {
                         const auto& cd = cands[((size_t)a * nf + fi) * km1 + c];
                         if (!(cd.flags & 1)) continue;
@@ -471,6 +491,29 @@ class RFTrainer {
                 if (p_.weight_trees) out.ens_weights[t0 + t] = mean;
                 if (!p_.quiet) printf("|%7u|%7u|%7.3f|\n", t0 + t + 1, tree_depth(*roots[t]), mean);
             }
+        }
+    }
+
+    // split_candidates < 2, where no kernel runs: a root whose labels differ (random_forest.rs:218-221) and that holds more than
+    // one value of a feature (stats.rs:98-103) has that feature's values wrapped in Scored::new (random_forest.rs:228, an
+    // absent value as 0.0) -- "NaN found!" on a NaN
+    void root_nan_check(const uint32_t* ids, uint32_t n, const uint32_t* feats, uint32_t nf) const {
+        const DataCore& core = *view_->core;
+        bool differ = false;
+        for (uint32_t i = 1; i < n && !differ; i++) differ = core.gain[ids[i]] != core.gain[ids[0]];
+        if (!differ) return;
+        for (uint32_t fi = 0; fi < nf; fi++) {
+            const uint32_t f = feats[fi];
+            uint32_t held = 0;
+            bool nan = false;
+            for (uint32_t i = 0; i < n; i++) {
+                if (!core.present_bits.empty() && ((core.present_bits[(size_t)ids[i] * core.present_words + (f >> 5)] >> (f & 31u)) & 1u) == 0u) continue;
+                const float x = core.x[(size_t)ids[i] * core.d + f];
+                held++;
+                nan = nan || x != x;
+            }
+            if (held > 1 && nan)
+                fail_str("random forest: feature " + std::to_string(f) + ": NaN found!: FloatIsNan (a NaN feature value in a node that looks for a split)");
         }
     }
 

@@ -867,7 +867,8 @@ typedef struct {
     double *split;
     int32_t *lhs, *rhs;
     size_t n, cap;
-    int err; /* 1: out of node capacity, 2: the reference would have panicked (NaN importance, variance of < 2 labels) */
+    int err; /* 1: out of node capacity, 2: the reference would have panicked (NaN importance, variance of < 2 labels, a NaN
+                feature value or split position reached by a node that looks for a split) */
 } rf_out;
 
 typedef struct {
@@ -1008,13 +1009,31 @@ static int32_t rf_learn_recursive(const oracle_dataset *ds, const oracle_rf_para
             keys[i].v = v;
             keys[i].pos = ridx[i];
             keys[i].id = ids[i];
-            if (ds->present && !ds->present[(size_t)ids[i] * ds->d + f]) continue;
+            if (ds->present && !ds->present[(size_t)ids[i] * ds->d + f]) {
+                keys[i].v = 0.0; /* unwrap_or(0.0), random_forest.rs:228: whatever the matrix carries there is never read */
+                continue;
+            }
             held++;
             if (fmax < v) fmax = v;
             if (fmin > v) fmin = v;
         }
         if (held <= 1) continue;
         const double range = fmax - fmin;
+        /* Non-finite feature values.  The min / max above are StreamingStats::push's (stats.rs:74-79, starting from
+           f64::MIN / f64::MAX, :46-47): a NaN is counted but never becomes either, +inf never lowers the minimum and
+           -inf never raises the maximum.  From here on the reference panics
+             * on a NaN value of ANY instance of the node: Scored::new, random_forest.rs:228 ("NaN found!");
+             * on a NaN position: NotNan::new(f * range + stats.min).unwrap(), random_forest.rs:238 -- a minimum of
+               -inf (inf + -inf).  Every position is NaN or none is (f > 0, range is NaN-free), so the first one tells;
+               split_candidates < 2 makes no position at all.
+           Both come before the sort, which is never handed a NaN (cmp_rf_key is no order on them). */
+        int bad = 0;
+        for (size_t i = 0; i < n; i++) bad |= isnan(keys[i].v);
+        if (k > 1 && isnan((1.0 / (double)k) * range + fmin)) bad = 1;
+        if (bad) {
+            o->err |= 2;
+            break;
+        }
         qsort(keys, n, sizeof(rf_key), cmp_rf_key); /* random_forest.rs:225-233 */
         for (size_t i = 0; i < n; i++) sorted[i] = keys[i].id, sorted_r[i] = keys[i].pos;
         /* random_forest.rs:236-273: k-1 thresholds, their positions, the surviving candidates' importances */
@@ -1052,7 +1071,7 @@ static int32_t rf_learn_recursive(const oracle_dataset *ds, const oracle_rf_para
     free(sorted);
     free(sorted_r);
     int32_t node = -1;
-    if (have) {
+    if (have && !o->err) { /* (after a panic the call has no result: nothing below this node is looked at) */
         node = rf_new_node(o);
         if (node >= 0) {
             int32_t l = rf_learn_recursive(ds, p, best_ids, best_r, best_pos, fids, nf, depth + 1, o);

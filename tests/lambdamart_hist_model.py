@@ -27,6 +27,8 @@ def bin_edges(col, k):
     v = canon(col)
     if np.isnan(v).any():
         raise ValueError("NaN feature value")
+    if np.isinf(v).any():  # (an edge is a data value: -inf would become a split no model file can hold; training refuses both)
+        raise ValueError("infinite feature value")
     s = np.sort(v)
     n = len(s)
     if n == 0:

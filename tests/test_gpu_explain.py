@@ -264,3 +264,24 @@ def test_refusals(monkeypatch):
     ok = ds.subsample_feature_names([n for n in ds.feature_names() if ds.feature_name_to_index()[n] != 3])
     ex = model.explain(ok)
     assert list(ex.feature_ids) == [0, 1, 2] and np.array_equal(_bits(ex.values), _bits(model.explain(ds).values[:, :3]))
+
+
+@pytest.mark.parametrize("bad", [np.inf, -np.inf, np.nan])
+def test_a_dataset_with_inf_or_nan_is_refused_and_its_finite_copy_explains_as_before(bad):
+    """One non-finite value anywhere -- also in a column the model does not read, also as the background -- and the dataset
+    is refused; the same rows with that value replaced explain to the restatement's bytes, before and after the refusal."""
+    trees, weights, _ = em.random_forest_model(24, d=5, trees=3, depth=4, n=16)
+    X = np.random.default_rng(6).normal(0, 1, (130, 5)).astype(np.float32)
+    model = _model(trees, weights)
+    fine = _dataset(X)
+    before = _check(model, fine, X)
+    for col in range(5):
+        Xb = X.copy()
+        Xb[77, col] = bad
+        ds = _dataset(Xb)
+        with pytest.raises(Exception, match="holds inf or NaN"):
+            model.explain(ds)
+        with pytest.raises(Exception, match="holds inf or NaN"):
+            model.explain(fine, ds)
+    after = model.explain(fine)
+    assert np.array_equal(_bits(after.values), _bits(before.values)) and _bits(after.expected_value) == _bits(before.expected_value)

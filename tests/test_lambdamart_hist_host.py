@@ -147,6 +147,15 @@ def test_nan_is_refused_by_the_restatement():
         hm.bin_edges(np.array([1.0, np.nan, 2.0], dtype=np.float32), 4)
 
 
+@pytest.mark.parametrize("col", [[-np.inf, -np.inf, 1, 2, 3, 4, np.inf], [1, 2, np.inf], [-np.inf, 1, 2]])
+def test_infinite_values_are_refused_by_the_restatement(col):
+    """Every distinct value but the largest is an edge, so -inf would become a split: a tree that cannot be written down
+    (JSON has null for it), continued or explained.  Training refuses +-inf like NaN, and so does the restatement."""
+    with pytest.raises(ValueError, match="infinite feature value"):
+        hm.bin_edges(np.array(col, dtype=np.float32), 4)
+    assert len(hm.bin_edges(np.array([1, 2, 3.4e38], dtype=np.float32), 4)) == 2  # (the largest finite float is a value like any)
+
+
 def test_fixed_point_sums_do_not_depend_on_order():
     rng = np.random.default_rng(9)
     n = 100_000
