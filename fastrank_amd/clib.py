@@ -132,6 +132,10 @@ def _load():
         "fr_debug_walk_tiles": (vp, [vp, vp, vp, sz, vp, vp, sz, sz]),
         "fr_debug_device_form": (vp, [vp, C.c_int, C.c_char_p, vp, sz]),
         "fr_debug_dataset_layout": (vp, [vp, vp, sz, vp, vp, sz, C.c_char_p, vp, sz]),
+        "fr_load_ranksvm": (res, [C.c_char_p, C.c_char_p, C.c_char_p]),
+        "fr_last_load_stats": (vp, []),
+        "fr_debug_dataset_core": (vp, [vp, C.c_char_p, vp, sz]),
+        "fr_debug_text_number": (vp, [C.c_char_p, sz, vp, vp, vp]),
     }
     for name, (restype, argtypes) in sigs.items():
         fn = getattr(L, name)
@@ -330,9 +334,15 @@ class CDataset:
         self.numpy_arrays_to_keep = []
 
     @staticmethod
-    def open_ranksvm(data_path, feature_names_path=None) -> "CDataset":
+    def open_ranksvm(data_path, feature_names_path=None, parser="auto") -> "CDataset":
+        """parser: "auto" (the device parser for texts of 32 MiB and more when a device is present), "host" or "device";
+        the dataset and the errors are the same whichever runs ("Text loading")."""
         names = feature_names_path.encode("utf-8") if feature_names_path is not None else None
-        return CDataset(_unwrap(_load().load_ranksvm_format(data_path.encode("utf-8"), names)))
+        if parser == "auto":
+            return CDataset(_unwrap(_load().load_ranksvm_format(data_path.encode("utf-8"), names)))
+        if parser not in ("host", "device"):
+            raise ValueError('unknown parser {0!r}: expected one of "auto", "host", "device"'.format(parser))
+        return CDataset(_unwrap(_load().fr_load_ranksvm(data_path.encode("utf-8"), names, parser.encode("utf-8"))))
 
     @staticmethod
     def from_numpy(X, y, qid) -> "CDataset":

@@ -34,6 +34,8 @@ namespace {
 // not per process: two host threads that train on different datasets -- each on its own devices -- do not wait for
 // each other.  (Round 2 had one process-wide lock.)
 std::mutex g_stats_mu;  // fr_last_train_stats
+std::mutex g_load_mu;   // fr_last_load_stats
+fr::LoadStats g_last_load;
 static std::mutex& api_mu_of(const CDataset& ds) { return ds.view->core->api_mu; }
 fr::TrainStats g_last_stats;
 
@@ -703,9 +705,10 @@ const void* cqrel_query_json(const CQRel* cqrel, const void* query_str) {
     });
 }
 
-const CResult* load_ranksvm_format(void* data_path, void* feature_names_path) {
+const CResult* fr_load_ranksvm(const void* data_path, const void* feature_names_path, const void* parser) {
     return c_call<CDataset>([&]() {
         std::string path = accept_str("data_path", data_path);
+        const std::string word = accept_str("parser", parser);
         std::map<uint32_t, std::string> names;
         bool has_names = false;
         if (feature_names_path) {
@@ -713,13 +716,110 @@ const CResult* load_ranksvm_format(void* data_path, void* feature_names_path) {
             has_names = true;
         }
         auto* d = new CDataset();
+        fr::LoadStats st;
         try {
-            d->view = fr::load_ranksvm(path, has_names ? &names : nullptr);
+            d->view = fr::load_ranksvm_with(path, has_names ? &names : nullptr, word, &st);
         } catch (...) {
             delete d;
             throw;
         }
+        std::lock_guard<std::mutex> lk(g_load_mu);
+        g_last_load = st;
         return d;
+    });
+}
+
+const CResult* load_ranksvm_format(void* data_path, void* feature_names_path) { return fr_load_ranksvm(data_path, feature_names_path, "auto"); }
+
+// what the last successful fr_load_ranksvm / load_ranksvm_format of this process did (include/fastrank.h)
+const void* fr_last_load_stats(void) {
+    return json_call([&]() {
+        std::lock_guard<std::mutex> lk(g_load_mu);
+        const fr::LoadStats& s = g_last_load;
+        Value o = Value::object();
+        o.set("parser", Value::string(s.parser));
+        o.set("reason", Value::string(s.reason));
+        o.set("bytes", Value::uint(s.bytes));
+        o.set("lines", Value::uint(s.lines));
+        o.set("host_lines", Value::uint(s.host_lines));
+        Value r = Value::object();
+        for (uint32_t k = 1; k < frtext::R_COUNT; k++) r.set(frtext::reason_name(k), Value::uint(s.reasons[k]));
+        o.set("host_line_reasons", std::move(r));
+        Value t = Value::object();
+        t.set("read", Value::number(s.read)), t.set("upload", Value::number(s.dev.upload)), t.set("line_scan", Value::number(s.dev.line_scan));
+        t.set("pass1", Value::number(s.dev.pass1)), t.set("pass2", Value::number(s.dev.pass2)), t.set("download", Value::number(s.dev.download));
+        t.set("host_merge", Value::number(s.merge)), t.set("total", Value::number(s.total));
+        o.set("seconds", std::move(t));
+        o.set("scan_slice", Value::uint(frdev::TEXT_SCAN_SLICE));
+        o.set("stage_limit", Value::uint(frdev::TEXT_STAGE_LIMIT));
+        o.set("auto_threshold", Value::uint(fr::TEXT_DEVICE_THRESHOLD));
+        return frjson::dump(o);
+    });
+}
+
+// The DataCore of a file-loaded dataset, for the tests (include/fastrank.h).  field == NULL: JSON of the scalars and the
+// string lists; else the named array's bytes into out[out_bytes] (the protocol of fr_debug_device_form).
+const void* fr_debug_dataset_core(const CDataset* dataset, const void* field, void* out, size_t out_bytes) {
+    return json_call([&]() {
+        const fr::DataCore& c = *require_dataset(dataset).view->core;
+        Value o = Value::object();
+        if (!field) {
+            o.set("n", Value::uint(c.n)), o.set("d", Value::uint(c.d)), o.set("present_words", Value::uint(c.present_words));
+            o.set("has_docids", Value::boolean(c.has_docids)), o.set("present_bits_len", Value::uint(c.present_bits.size()));
+            o.set("features_len", Value::uint(c.features.size()));
+            Value q = Value::array(), dn = Value::array();
+            // (names are bytes of the file, not always UTF-8: served in hex)
+            auto hex = [](const std::string& s) {
+                static const char* dig = "0123456789abcdef";
+                std::string h;
+                for (unsigned char ch : s) h += dig[ch >> 4], h += dig[ch & 15];
+                return h;
+            };
+            for (const auto& s : c.qnames) q.push(Value::string(hex(s)));
+            for (const auto& s : c.docids) dn.push(Value::string(hex(s)));
+            o.set("qnames_hex", std::move(q)), o.set("docids_hex", std::move(dn));
+            return frjson::dump(o);
+        }
+        const std::string name = accept_str("field", field);
+        const void* p = nullptr;
+        size_t bytes = 0;
+        if (name == "x") p = c.x, bytes = c.n * c.d * sizeof(float);
+        else if (name == "gain") p = c.gain.data(), bytes = c.gain.size() * sizeof(float);
+        else if (name == "qix") p = c.qix.data(), bytes = c.qix.size() * sizeof(uint32_t);
+        else if (name == "doc_present") p = c.doc_present.data(), bytes = c.doc_present.size();
+        else if (name == "features") p = c.features.data(), bytes = c.features.size() * sizeof(uint32_t);
+        else if (name == "present_bits") p = c.present_bits.data(), bytes = c.present_bits.size() * sizeof(uint32_t);
+        else fr::fail_str("fr_debug_dataset_core: no field named " + name);
+        if (out_bytes != bytes || (!out && bytes)) fr::fail_str("fr_debug_dataset_core: field " + name + " holds " + std::to_string(bytes) + " bytes, the buffer " + std::to_string(out_bytes));
+        if (bytes) std::memcpy(out, p, bytes);
+        o.set("bytes", Value::uint(bytes));
+        return frjson::dump(o);
+    });
+}
+
+// The host compile of the device parser's number rule (csrc/text_number.hpp) on n tokens, one per line of `tokens`:
+// reasons[i] (frtext::Reason; the reply lists their names by code) and, where it is 0, the f64 / f32 the rule gives.
+// The CPU tests hold it to their Python restatement.
+const void* fr_debug_text_number(const void* tokens, size_t n, uint32_t* reasons, double* value64, float* value32) {
+    return json_call([&]() {
+        const std::string text = accept_str("tokens", tokens);
+        if (n && (!reasons || !value64 || !value32)) fr::fail_str("NULL pointer: fr_debug_text_number arrays");
+        size_t at = 0, i = 0;
+        for (; i < n && at <= text.size(); i++) {
+            size_t end = text.find('\n', at);
+            if (end == std::string::npos) end = text.size();
+            double v = 0.0;
+            reasons[i] = frtext::fast_number((const unsigned char*)text.data() + at, (uint32_t)(end - at), &v);
+            value64[i] = reasons[i] == frtext::R_NONE ? v : 0.0;
+            value32[i] = reasons[i] == frtext::R_NONE ? (float)v : 0.0f;
+            at = end + 1;
+        }
+        if (i != n) fr::fail_str("fr_debug_text_number: fewer tokens than n");
+        Value names = Value::array();
+        for (uint32_t k = 0; k < frtext::R_COUNT; k++) names.push(Value::string(frtext::reason_name(k)));
+        Value o = Value::object();
+        o.set("reasons", std::move(names));
+        return frjson::dump(o);
     });
 }
 

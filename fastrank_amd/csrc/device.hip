@@ -46,6 +46,8 @@
 //     train_lambda.inc        the launchers of kernels_lambda.inc and kernels_xendcg.inc
 //     train_dart.inc          the launchers of kernels_dart.inc
 //     train_hist.inc          the launchers of kernels_hist.inc and kernels_histreg.inc, level-wise and leaf-wise, of kernels_goss.inc and kernels_histquant.inc
+//   kernels_text.inc        the device text parser's kernels (line scan, the two parsing passes); text_parse.inc launches them
+//                           (text_parse.hpp: the interface loader.hpp uses; text_number.hpp: grammar and value rule)
 #include "device.hpp"
 
 #include <hip/hip_runtime.h>
@@ -55,6 +57,7 @@
 #include "linesearch_policy.hpp"
 #define FR_QUANT_ARITHMETIC_ONLY  // (lambdamart_quant.hpp without host.hpp: the integer arithmetic the kernels share with the host)
 #include "lambdamart_quant.hpp"
+#include "text_parse.hpp"
 
 #include <cstring>
 #include <dlfcn.h>
@@ -99,5 +102,7 @@ namespace frdev {
 #include "kernels_dart.inc"
 #include "device_dataset.inc"
 #include "rccl_exchange.inc"
+#include "kernels_text.inc"
+#include "text_parse.inc"
 
 }  // namespace frdev

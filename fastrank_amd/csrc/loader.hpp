@@ -10,6 +10,8 @@
 #include <cstring>
 
 #include "host.hpp"
+#include "ranksvm_line.hpp"
+#include "text_parse.hpp"
 
 namespace fr {
 
@@ -50,38 +52,7 @@ class LineReader {
     gzFile f_ = nullptr;
 };
 
-inline std::vector<std::string> split_ws(const std::string& s) {
-    std::vector<std::string> out;
-    size_t i = 0, n = s.size();
-    while (i < n) {
-        while (i < n && isspace((unsigned char)s[i])) i++;
-        size_t j = i;
-        while (j < n && !isspace((unsigned char)s[j])) j++;
-        if (j > i) out.emplace_back(s, i, j - i);
-        i = j;
-    }
-    return out;
-}
-
-inline std::string trim(const std::string& s) {
-    size_t a = 0, b = s.size();
-    while (a < b && isspace((unsigned char)s[a])) a++;
-    while (b > a && isspace((unsigned char)s[b - 1])) b--;
-    return s.substr(a, b - a);
-}
-
-inline bool parse_f64_strict(const std::string& t, double* out) {
-    if (t.empty()) return false;
-    char* end = nullptr;
-    *out = strtod(t.c_str(), &end);
-    return end == t.c_str() + t.size();
-}
-inline bool parse_f32_strict(const std::string& t, float* out) {
-    if (t.empty()) return false;
-    char* end = nullptr;
-    *out = strtof(t.c_str(), &end);  // correctly rounded, like fast_float::parse::<f32>
-    return end == t.c_str() + t.size();
-}
+// (split_ws, trim, parse_f64_strict, parse_f32_strict: ranksvm_line.hpp)
 
 // dataset.rs:14-25 load_feature_names_json: {"1": "name", ...}
 inline std::map<uint32_t, std::string> load_feature_names(const std::string& path) {
@@ -107,8 +78,31 @@ inline std::map<uint32_t, std::string> load_feature_names(const std::string& pat
     return out;
 }
 
-inline std::shared_ptr<DatasetView> load_ranksvm(const std::string& path,
-                                                 const std::map<uint32_t, std::string>* names) {
+// What the last open of a feature file did (fr_last_load_stats).
+struct LoadStats {
+    std::string parser = "host", reason;
+    uint64_t bytes = 0, lines = 0, host_lines = 0;
+    uint64_t reasons[frtext::R_COUNT] = {0, 0, 0, 0, 0, 0, 0};  // host_lines by frtext::Reason
+    double read = 0, merge = 0, total = 0;                      // wall seconds; the device's stages in `dev`
+    frdev::TextTimes dev;
+};
+
+// The (inflated) text from which parser = "auto" takes the device parser when a device is present.  A condition, not a
+// tuning result: DESIGN.md ("Text loading") has the measured crossover, which lies below it.
+constexpr size_t TEXT_DEVICE_THRESHOLD = size_t(32) << 20;
+
+inline std::shared_ptr<DatasetView> view_of_core(const std::shared_ptr<DataCore>& core, const std::map<uint32_t, std::string>* names) {
+    if (names) core->feature_names = *names;
+    auto view = std::make_shared<DatasetView>();
+    view->core = core;
+    view->features = core->features;
+    view->instances.resize(core->n);
+    for (size_t i = 0; i < core->n; i++) view->instances[i] = (uint32_t)i;
+    return view;
+}
+
+inline std::shared_ptr<DatasetView> load_ranksvm(const std::string& path, const std::map<uint32_t, std::string>* names,
+                                                 LoadStats* stats = nullptr) {
     struct Row {
         std::vector<std::pair<uint32_t, float>> feats;
         uint32_t dense_len = 0;  // >0: Dense32 of this length (instance.rs:108-115)
@@ -118,87 +112,39 @@ inline std::shared_ptr<DatasetView> load_ranksvm(const std::string& path,
     std::unordered_map<std::string, uint32_t> qslot;
     std::set<uint32_t> present;
     bool any_docid = false;
-    auto lerr = [&](uint64_t line_no, const std::string& kind) {
-        fail_str(path + ": LineParseError(" + std::to_string(line_no) + ", " + kind + ")");
-    };
-    try {
+    {
         LineReader rd(path);
         std::string line;
         uint64_t line_no = 0;
         while (rd.next(line)) {
             line_no++;
-            std::string data = line, comment;
-            bool has_comment = false;
-            size_t hash = line.find('#');
-            if (hash != std::string::npos) {
-                data = line.substr(0, hash);
-                comment = trim(line.substr(hash + 1));
-                has_comment = true;
-            }
-            std::vector<std::string> toks = split_ws(data);
-            if (toks.empty()) lerr(line_no, "EmptyLine");
-            double label64;
-            if (!parse_f64_strict(toks[0], &label64)) lerr(line_no, "Label(ParseFloatError { kind: Invalid })");
-            float label = (float)label64;
-            if (label != label) lerr(line_no, "LabelIsNan(FloatIsNan)");
-            size_t t = 1;
-            std::string qid;
-            bool has_q = false;
-            if (t < toks.size() && toks[t].compare(0, 4, "qid:") == 0) {
-                qid = toks[t];
-                while (qid.compare(0, 4, "qid:") == 0) qid.erase(0, 4);  // trim_start_matches
-                has_q = true;
-                t++;
+            if (stats) stats->bytes += line.size(), stats->lines = line_no;
+            RanksvmLine parsed;
+            try {
+                parsed = parse_ranksvm_line(line, line_no);
+            } catch (const RanksvmLineError& e) {
+                fail_str(path + ": " + e.what);
             }
             Row row;
-            for (; t < toks.size(); t++) {
-                size_t colon = toks[t].find(':');
-                if (colon == std::string::npos) lerr(line_no, "FeatureNoColon");
-                std::string fs = toks[t].substr(0, colon), vs = toks[t].substr(colon + 1);
-                char* end = nullptr;
-                unsigned long long fid = strtoull(fs.c_str(), &end, 10);
-                if (fs.empty() || end != fs.c_str() + fs.size() || fid > 0xFFFFFFFFull || fs[0] == '-')
-                    lerr(line_no, "FeatureNum(ParseIntError { kind: InvalidDigit })");
-                float val;
-                if (!parse_f32_strict(vs, &val)) lerr(line_no, "FeatureValNotFloat(Error)");
-                row.feats.emplace_back((uint32_t)fid, val);
-            }
-            if (row.feats.empty()) lerr(line_no, "NoFeatures");
-            bool needs_sort = false;
-            for (size_t k = 0; k + 1 < row.feats.size(); k++)
-                if (row.feats[k].first >= row.feats[k + 1].first) needs_sort = true;
-            if (needs_sort) {
-                std::sort(row.feats.begin(), row.feats.end(),
-                          [](const auto& a, const auto& b) { return a.first < b.first; });
-                for (size_t k = 0; k + 1 < row.feats.size(); k++)
-                    if (row.feats[k].first == row.feats[k + 1].first)
-                        lerr(line_no, "MultipleDefinitions(Feature { idx: " + std::to_string(row.feats[k].first) + " })");
-            }
-            if (!has_q) fail_str(path + ": \"Missing qid\"");
-            // instance.rs:104-130: dense when len / max_feature >= 0.5
-            uint32_t max_feature = 0;
-            for (const auto& fv : row.feats) max_feature = std::max(max_feature, fv.first);
-            double density = (double)row.feats.size() / (double)max_feature;
-            if (density >= 0.5) {
-                row.dense_len = max_feature + 1;
-                for (uint32_t j = 0; j <= max_feature; j++) present.insert(j);
+            row.feats = std::move(parsed.feats);
+            row.dense_len = parsed.dense_len;
+            if (row.dense_len > 0) {
+                for (uint32_t j = 0; j < row.dense_len; j++) present.insert(j);
             } else {
                 for (const auto& fv : row.feats) present.insert(fv.first);
             }
-            auto it = qslot.find(qid);
+            auto it = qslot.find(parsed.qid);
             if (it == qslot.end()) {
-                it = qslot.emplace(qid, (uint32_t)core->qnames.size()).first;
-                core->qnames.push_back(qid);
+                it = qslot.emplace(parsed.qid, (uint32_t)core->qnames.size()).first;
+                core->qnames.push_back(parsed.qid);
             }
             core->qix.push_back(it->second);
-            core->gain.push_back(label);
-            core->docids.push_back(comment);
-            core->doc_present.push_back(has_comment ? 1 : 0);  // document_name() is Some only then
-            any_docid = any_docid || has_comment;
+            core->gain.push_back(parsed.label);
+            core->docids.push_back(parsed.comment);
+            core->doc_present.push_back(parsed.has_comment ? 1 : 0);  // document_name() is Some only then
+            any_docid = any_docid || parsed.has_comment;
             rows.push_back(std::move(row));
         }
-    } catch (FrError&) {
-        throw;
     }
     if (rows.empty() || present.empty()) fail_str(path + ": No features defined!");
     core->n = rows.size();
@@ -229,12 +175,139 @@ inline std::shared_ptr<DatasetView> load_ranksvm(const std::string& path,
         }
     }
     core->has_docids = any_docid;
-    if (names) core->feature_names = *names;
-    auto view = std::make_shared<DatasetView>();
-    view->core = core;
-    view->features = core->features;
-    view->instances.resize(core->n);
-    for (size_t i = 0; i < core->n; i++) view->instances[i] = (uint32_t)i;
+    return view_of_core(core, names);
+}
+
+// The file whole, inflated through zlib as LineReader reads it (same refusals, same error for a file that does not open).
+inline std::vector<char> read_text_whole(const std::string& path) {
+    auto ends = [&](const char* suf) {
+        size_t n = strlen(suf);
+        return path.size() >= n && path.compare(path.size() - n, n, suf) == 0;
+    };
+    if (ends(".bz2") || ends(".zst"))
+        fail_str(path + ": bzip2/zstd inputs are not supported by the MI355X build (use .gz or plain text)");
+    gzFile f = gzopen(path.c_str(), "rb");
+    if (!f) {
+        fail_raw("Os { code: " + std::to_string(errno) + ", kind: " + (errno == ENOENT ? "NotFound" : "Other") +
+                 ", message: " + frjson::rust_debug_str(strerror(errno)) + " }");
+    }
+    gzbuffer(f, 1 << 20);
+    std::vector<char> text;
+    size_t used = 0;
+    for (;;) {
+        if (text.size() - used < (size_t(1) << 24)) text.resize(std::max<size_t>(text.size() * 2, size_t(1) << 25));
+        const int got = gzread(f, text.data() + used, (unsigned)std::min<size_t>(text.size() - used, size_t(1) << 30));
+        if (got <= 0) break;
+        used += (size_t)got;
+    }
+    gzclose(f);
+    text.resize(used);
+    return text;
+}
+
+// The device parser ("Text loading"): text in `text`; nullptr when it hands the file to the host parser
+// (stats->reason says why).  Errors are the host parser's, word for word.
+inline std::shared_ptr<DatasetView> load_ranksvm_text_device(const std::string& path, const std::vector<char>& text,
+                                                             const std::map<uint32_t, std::string>* names, LoadStats* stats) {
+    using Clock = std::chrono::steady_clock;
+    auto secs = [](Clock::time_point a) { return std::chrono::duration<double>(Clock::now() - a).count(); };
+    if (!text.empty() && memchr(text.data(), 0, text.size())) {
+        stats->reason = "the text holds a NUL byte";
+        return nullptr;
+    }
+    frdev::TextParser parser;
+    std::vector<uint64_t> starts;
+    std::vector<frtext::TextLineRec> recs;
+    bool fits = true;
+    std::string err;
+    if (!parser.pass1(text.data(), text.size(), &starts, &recs, &fits, &stats->dev, &err)) fail_str(err);
+    if (!fits) {
+        stats->reason = "the device lacks the memory for the text and its line tables";
+        return nullptr;
+    }
+    auto t0 = Clock::now();
+    frtext::MergedText mt;
+    frtext::TextMergePlan plan;
+    try {
+        plan = frtext::merge_lines(text.data(), starts.data(), recs.size(), recs.data(), &mt);
+    } catch (const RanksvmLineError& e) {
+        fail_str(path + ": " + e.what);
+    }
+    mt.x.assign(mt.n * mt.d, 0.0f);
+    if (mt.present_words) mt.present_bits.assign(mt.n * mt.present_words, 0u);
+    std::vector<uint32_t> feature_bits(plan.device_sparse ? (mt.d + 31) / 32 : 0, 0u);
+    stats->merge += secs(t0);
+    if (!parser.pass2(mt.d, mt.present_words, mt.x.data(), mt.present_bits.data(), plan.device_sparse ? feature_bits.data() : nullptr, &fits,
+                      &stats->dev, &err))
+        fail_str(err);
+    if (!fits) {
+        stats->reason = "the device lacks the memory for the n x d matrix";
+        return nullptr;
+    }
+    t0 = Clock::now();
+    frtext::merge_finish(plan, plan.device_sparse ? feature_bits.data() : nullptr, &mt);
+    auto core = std::make_shared<DataCore>();
+    core->n = mt.n, core->d = mt.d;
+    core->x_own = std::move(mt.x);
+    core->x = core->x_own.data();
+    core->gain = std::move(mt.gain), core->qix = std::move(mt.qix), core->qnames = std::move(mt.qnames);
+    core->docids = std::move(mt.docids), core->doc_present = std::move(mt.doc_present), core->has_docids = mt.has_docids;
+    core->features = std::move(mt.features);
+    core->present_bits = std::move(mt.present_bits), core->present_words = mt.present_words;
+    stats->merge += secs(t0);
+    stats->lines = mt.n;
+    stats->host_lines = plan.host_lines.size();
+    for (uint32_t r = 0; r < frtext::R_COUNT; r++) stats->reasons[r] = plan.reasons[r];
+    return view_of_core(core, names);
+}
+
+// parser: "auto" (the device parser when a device is present and the text is at least TEXT_DEVICE_THRESHOLD), "host", "device"
+inline std::shared_ptr<DatasetView> load_ranksvm_with(const std::string& path, const std::map<uint32_t, std::string>* names,
+                                                      const std::string& parser, LoadStats* stats) {
+    using Clock = std::chrono::steady_clock;
+    const auto t0 = Clock::now();
+    auto secs = [](Clock::time_point a) { return std::chrono::duration<double>(Clock::now() - a).count(); };
+    *stats = LoadStats();
+    if (parser != "auto" && parser != "host" && parser != "device")
+        fail_str("unknown parser \"" + parser + "\": expected one of \"auto\", \"host\", \"device\"");
+    auto host = [&](const std::string& why) {
+        LoadStats st;
+        st.reason = why, st.read = stats->read, st.dev = stats->dev;
+        *stats = st;
+        auto view = load_ranksvm(path, names, stats);
+        stats->total = secs(t0);
+        return view;
+    };
+    if (parser == "host") return host("parser = host");
+    std::string e2;
+    const bool have_device = frdev::device_count(&e2) > 0;
+    if (!have_device) {
+        if (parser == "device")
+            fail_str("no MI355X/HIP device available for the fastrank_amd compute path (" + (e2.empty() ? std::string("device count is 0") : e2) + ")");
+        return host("no device");
+    }
+    if (parser == "auto") {
+        // a plain file shorter than the threshold is the host's without being read twice; a gzip stream is inflated to find out
+        FILE* fh = fopen(path.c_str(), "rb");
+        if (fh) {
+            unsigned char magic[2] = {0, 0};
+            const size_t got = fread(magic, 1, 2, fh);
+            const bool gz = got == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
+            fseek(fh, 0, SEEK_END);
+            const long size = ftell(fh);
+            fclose(fh);
+            if (!gz && size >= 0 && (size_t)size < TEXT_DEVICE_THRESHOLD) return host("the text is shorter than the threshold");
+        }
+    }
+    const std::vector<char> text = read_text_whole(path);
+    stats->read = secs(t0);
+    stats->bytes = text.size();
+    if (parser == "auto" && text.size() < TEXT_DEVICE_THRESHOLD) return host("the text is shorter than the threshold");
+    stats->parser = "device";
+    stats->reason = parser == "device" ? "parser = device" : "a device is present and the text reaches the threshold";
+    auto view = load_ranksvm_text_device(path, text, names, stats);
+    if (!view) return host(stats->reason);
+    stats->total = secs(t0);
     return view;
 }
 

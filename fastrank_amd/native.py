@@ -447,6 +447,39 @@ def last_train_stats() -> Dict:
     return _json_reply(_load().fr_last_train_stats())
 
 
+def last_load_stats() -> Dict:
+    """What the last CDataset.open_ranksvm of this process did (fr_last_load_stats): "parser" that ran and "reason", "bytes",
+    "lines", "host_lines", "host_line_reasons", "seconds" per stage, and the parser's constants "scan_slice", "stage_limit",
+    "auto_threshold"."""
+    return _json_reply(_load().fr_last_load_stats())
+
+
+def loaded_arrays(dataset: CDataset) -> Dict:
+    """The host arrays of a file-loaded dataset (fr_debug_dataset_core), for the tests: x (n x d), gain, qix, qnames, docids,
+    doc_present, features, present_bits, present_words, has_docids.  qnames / docids are bytes (a comment need not be UTF-8)."""
+    L = _load()
+    s = _json_reply(L.fr_debug_dataset_core(dataset.pointer, None, None, 0))
+    n, d = int(s["n"]), int(s["d"])
+    out = {"n": n, "d": d, "present_words": int(s["present_words"]), "has_docids": bool(s["has_docids"]),
+           "qnames": [bytes.fromhex(h) for h in s["qnames_hex"]], "docids": [bytes.fromhex(h) for h in s["docids_hex"]]}
+    for name, dtype, count in (("x", np.float32, n * d), ("gain", np.float32, n), ("qix", np.uint32, n), ("doc_present", np.uint8, n),
+                               ("features", np.uint32, int(s["features_len"])), ("present_bits", np.uint32, int(s["present_bits_len"]))):
+        arr = np.empty(count, dtype=dtype)
+        _json_reply(L.fr_debug_dataset_core(dataset.pointer, name.encode("utf-8"), arr.ctypes.data if count else None, arr.nbytes))
+        out[name] = arr
+    out["x"] = out["x"].reshape(n, d)
+    return out
+
+
+def text_numbers(tokens: List[str]):
+    """The device parser's number rule as the library's host compile runs it (fr_debug_text_number): (reason names per token,
+    float64 values, float32 values); a value is meaningful where the reason is "none".  Tokens hold no newline."""
+    n = len(tokens)
+    reasons, v64, v32 = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.float32)
+    rep = _json_reply(_load().fr_debug_text_number("\n".join(tokens).encode("utf-8"), n, reasons.ctypes.data, v64.ctypes.data, v32.ctypes.data))
+    return [rep["reasons"][r] for r in reasons], v64, v32
+
+
 def last_tree_plan() -> Dict:
     """What the last forest-scoring call of this process ran (fr_debug_tree_plan): {"path": "rank" | "lds" | "l2",
     "cache_hit", and per path "docs", "parts" / "rows_in_lds" / "nslots", "nrounds"; "batches": [[walks, levels], ...]}."""

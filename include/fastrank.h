@@ -470,6 +470,28 @@ const void *fr_debug_rccl_selftest(int device);
  * the same copied matrix -- and are released the same way, each through its own handle. */
 size_t fr_dataset_release_replicas(const CDataset *dataset);
 
+/* ---- Text loading ("Text loading") ----
+ * load_ranksvm_format with a choice of parser: "host" = the line-by-line host parser; "device" = the HIP parser (line scan,
+ * two parsing passes, host merge), which hands every line outside its fast grammar back to the host parser and gives the
+ * same dataset and the same errors -- without a HIP device it returns the `no MI355X/HIP device available...` envelope;
+ * "auto" (what load_ranksvm_format passes) = the device parser when a device is present and the inflated text is at least
+ * 32 MiB, the host parser otherwise.  Any other word is an error that names the three. */
+const CResult *fr_load_ranksvm(const void *data_path, const void *feature_names_path_or_null, const void *parser);
+/* What the last successful load of this process did, as JSON: "parser" that ran ("host" | "device") and "reason", "bytes",
+ * "lines", "host_lines" (lines handed back to the host parser), "host_line_reasons" {"too_long", "grammar", "number",
+ * "unsorted", "range", "near_tie": counts}, "seconds" {"read", "upload", "line_scan", "pass1", "pass2", "download",
+ * "host_merge", "total"} (wall), and the constants "scan_slice", "stage_limit", "auto_threshold" (bytes). */
+const void *fr_last_load_stats(void);
+/* The host arrays of a file-loaded dataset, for the tests.  field == NULL: JSON {"n", "d", "present_words", "has_docids",
+ * "present_bits_len", "features_len", "qnames_hex", "docids_hex" (the strings' bytes in hex)}; otherwise "x" (f32 n * d),
+ * "gain" (f32), "qix" (u32), "doc_present" (u8), "features" (u32) or "present_bits" (u32) is copied to `out`
+ * (JSON {"bytes": n}; a wrong out_bytes or an unknown name is an error). */
+const void *fr_debug_dataset_core(const CDataset *dataset, const void *field, void *out, size_t out_bytes);
+/* The device parser's number rule (csrc/text_number.hpp), compiled for the host, on the n tokens of `tokens` (one per line):
+ * reasons[i] = 0 and value64[i] / value32[i] = the value, or the code of the reason the token is declined with.  The JSON
+ * reply lists the reasons' names by code. */
+const void *fr_debug_text_number(const void *tokens, size_t n, uint32_t *reasons, double *value64, float *value32);
+
 #ifdef __cplusplus
 }
 #endif
