@@ -103,6 +103,7 @@ def _load():
         "fr_debug_dart_scores": (vp, [vp, vp, vp, sz, vp, sz, vp, vp, sz]),
         "fr_debug_lambda_gradients_sampled": (vp, [vp, vp, vp, C.c_char_p, C.c_double, vp, sz, vp, vp, sz]),
         "fr_debug_goss_select": (vp, [vp, vp, sz, C.c_double, C.c_double, C.c_uint64, C.c_uint32, vp, sz, vp, vp, sz, vp, vp]),
+        "fr_debug_rf_levels": (vp, [vp, vp, sz, vp, vp, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32, vp, sz]),
         "fr_debug_hist_quantise": (vp, [vp, vp, vp, sz, C.c_uint32, C.c_uint64, C.c_uint32, vp, sz, C.c_int32, C.c_double, C.c_double, C.c_uint64, C.c_uint32,
                                         vp, vp, sz, vp, vp]),
         "fr_debug_hist_root_histogram": (vp, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, vp, sz, vp, vp, vp, sz]),

@@ -2305,6 +2305,98 @@ const void* fr_debug_goss_select(const CDataset* dataset, const double* lambda, 
     });
 }
 
+// One batch of random-forest trees grown by the trainer's own grow_batch with every level recorded (include/fastrank.h;
+// DESIGN.md section 5.6).  out == NULL: grow, keep the record, return its JSON header; else hand the kept record's bytes over.
+static std::mutex g_rf_levels_mu;
+static std::vector<unsigned char> g_rf_levels_blob;
+const void* fr_debug_rf_levels(const CDataset* dataset, const uint32_t* root_off, size_t n_trees, const uint32_t* root_ids, const uint32_t* feats,
+                               uint32_t nf, uint32_t split_candidates, int32_t split_method, uint32_t min_leaf_support, uint32_t max_depth, void* out,
+                               size_t out_bytes) {
+    return json_call([&]() {
+        const std::string who = "fr_debug_rf_levels";
+        if (out) {
+            std::lock_guard<std::mutex> lk(g_rf_levels_mu);
+            if (out_bytes != g_rf_levels_blob.size())
+                fr::fail_str(who + ": the record holds " + std::to_string(g_rf_levels_blob.size()) + " bytes, the buffer " + std::to_string(out_bytes));
+            if (out_bytes) std::memcpy(out, g_rf_levels_blob.data(), out_bytes);
+            std::vector<unsigned char>().swap(g_rf_levels_blob);
+            return frjson::dump(Value::object());
+        }
+        const CDataset& ds = require_dataset(dataset);
+        if (!root_off || !root_ids || !feats) fr::fail_str("NULL pointer: " + who);
+        if (n_trees == 0 || nf == 0 || split_method < 0 || split_method > 3) fr::fail_str(who + ": at least one tree and one feature, split_method 0..3");
+        for (size_t t = 0; t < n_trees; t++)
+            if (root_off[t + 1] < root_off[t]) fr::fail_str(who + ": root_off must not decrease");
+        if (root_off[0] != 0) fr::fail_str(who + ": root_off must start at 0");
+        std::lock_guard<std::mutex> lk(api_mu_of(ds));
+        const std::vector<uint32_t> off(root_off, root_off + n_trees + 1), ids(root_ids, root_ids + root_off[n_trees]), fl(feats, feats + n_trees * nf);
+        for (uint32_t f : fl)
+            if (std::find(ds.view->features.begin(), ds.view->features.end(), f) == ds.view->features.end())
+                fr::fail_str(who + ": feature " + std::to_string(f) + " is not in the view");
+        {
+            std::vector<char> in_view(ds.view->core->n, 0);
+            for (uint32_t id : ds.view->instances)
+                if (id < in_view.size()) in_view[id] = 1;
+            for (uint32_t id : ids)
+                if (id >= in_view.size() || !in_view[id]) fr::fail_str(who + ": instance " + std::to_string(id) + " is not in the view");
+        }
+        fr::RFParams p;
+        p.quiet = true;
+        p.num_trees = (uint32_t)n_trees;
+        p.split_method = split_method;
+        p.min_leaf_support = min_leaf_support;
+        p.split_candidates = split_candidates;
+        p.max_depth = max_depth;
+        fr::RFTrainer trainer(ds.view, fr::Evaluator(), p);
+        fr::RFRecorder rec;
+        const fr::Model forest = trainer.grow_recorded(off, ids, nf, fl, rec);
+        std::vector<unsigned char> blob;
+        Value sections = Value::array();
+        auto put = [&](size_t level, const char* name, const void* data, size_t bytes) {
+            Value s = Value::object();
+            s.set("level", Value::uint(level));
+            s.set("name", Value::string(name));
+            s.set("offset", Value::uint(blob.size()));
+            s.set("bytes", Value::uint(bytes));
+            sections.push(s);
+            const unsigned char* b = static_cast<const unsigned char*>(data);
+            if (bytes) blob.insert(blob.end(), b, b + bytes);
+        };
+        Value levels = Value::array();
+        for (size_t i = 0; i < rec.levels.size(); i++) {
+            const fr::RFLevelRecord& lv = rec.levels[i];
+            Value l = Value::object();
+            l.set("A", Value::uint(lv.active.size()));
+            l.set("items", Value::uint(lv.svals.size()));
+            l.set("children_from", Value::string(lv.children_from_cands ? "candidates" : "rf_childsum_kernel"));
+            levels.push(l);
+            put(i, "active", lv.active.data(), lv.active.size() * sizeof(lv.active[0]));
+            put(i, "depth", lv.depth.data(), lv.depth.size() * 4);
+            put(i, "label_minmax", lv.label_minmax.data(), lv.label_minmax.size() * 4);
+            put(i, "cands", lv.cands.data(), lv.cands.size() * sizeof(lv.cands[0]));
+            put(i, "svals", lv.svals.data(), lv.svals.size() * 4);
+            put(i, "sv", lv.sv.data(), lv.sv.size() * 4);
+            put(i, "sg", lv.sg.data(), lv.sg.size() * 4);
+            put(i, "splits", lv.splits.data(), lv.splits.size() * sizeof(lv.splits[0]));
+            put(i, "child_out", lv.child_out.data(), lv.child_out.size() * 8);
+        }
+        put(rec.levels.size(), "root_out", rec.root_out.data(), rec.root_out.size() * 8);
+        Value o = Value::object();
+        o.set("cand_bytes", Value::uint(sizeof(frdev::DeviceDataset::RfCand)));
+        o.set("levels", levels);
+        o.set("sections", sections);
+        o.set("bytes", Value::uint(blob.size()));
+        Value trees = Value::array();
+        for (const fr::Model& m : forest.members) trees.push(fr::model_to_json(m));
+        o.set("trees", trees);
+        {
+            std::lock_guard<std::mutex> blk(g_rf_levels_mu);
+            g_rf_levels_blob.swap(blob);
+        }
+        return frjson::dump(o);
+    });
+}
+
 // The fixed-point step and the quantised gradients of one tree on their own ("Quantised gradients").
 const void* fr_debug_hist_quantise(const CDataset* dataset, const double* lambda, const double* weight, size_t len, uint32_t bits, uint64_t seed,
                                    uint32_t tree, const uint32_t* queries, size_t n_queries, int32_t goss, double top_rate, double other_rate,

@@ -277,6 +277,8 @@ class DeviceDataset {
     // the host's decisions for the level just evaluated: instances move to the children's keys; child_out[slot*2 + side]
     // = compute_output of that child (random_forest.rs:32-41)
     bool rf_split(const std::vector<RfSplit>& splits, std::vector<double>* child_out, std::string* err);
+    // test hook: the sorted arrays of the level rf_level just evaluated, as the device holds them (payloads, values, gains)
+    bool rf_debug_sorted(std::vector<uint32_t>* svals, std::vector<float>* sv, std::vector<float>* sg, std::string* err);
     void rf_end();
     // device bytes per (sampled instance x sampled feature) of a batch: two key and two payload arrays (8 + 8 + 4 + 4), the sorted
     // gains and values of this level and the one before (4 x 4), the side byte of the stable partition

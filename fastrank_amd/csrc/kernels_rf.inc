@@ -479,9 +479,10 @@ __global__ __launch_bounds__(64) void rf_eval_kernel(RFArgs a, uint32_t k, int m
                 r.pos_l = pl;
                 r.pos_r = ptot - pl;
             }
-            if (!valid) {
+            if (!valid) {  // (a lane that only walked along with its block: nothing of its walk is part of the record)
                 r.importance = 0.0;
                 r.pos_l = r.pos_r = 0;
+                r.sum_l = r.sum_r = 0.0;
             }
         }
         if (have) out[s * km1 + (c - 1)] = r;
@@ -514,7 +515,8 @@ __global__ __launch_bounds__(256) void rf_assign_kernel(RFArgs a, const RfSplitD
 // three passes over 12-byte items and a library sort; these three kernels do it with one and a half: count per tile of RF_PT
 // items (the side of every item is kept as one byte), an exclusive scan of the tiles of each segment, and a scatter to
 //     new offset of the child + feature slot * child size + items of that child earlier in the segment.
-// Same arrays as the sort would leave (tests: the forests are unchanged; FR_RF_PARTITION=0 takes the sort).
+// Same arrays as the sort would leave (tests/test_gpu_rf_levels.py compares svals / sv / sg of every level with the sort's, under
+// FR_RF_PARTITION=0, and with tests/rf_level_model.py's definition).
 constexpr uint32_t RF_PT = 2048;  // items per tile: 256 threads x 8
 struct RFPart {
     const uint32_t* o_tree;         // the PREVIOUS level's tables

@@ -94,6 +94,24 @@ inline double rf_entropy(uint32_t n, uint32_t positive) {
     return -rf_plogp(p_yes) - rf_plogp(p_no);
 }
 
+// What one grow_batch call saw and decided, level by level (the test hook fr_debug_rf_levels; tests/test_gpu_rf_levels.py holds
+// every field to tests/rf_level_model.py).  grow_batch fills it when handed one and is otherwise unchanged.
+struct RFLevelRecord {
+    std::vector<frdev::DeviceDataset::RfActive> active;
+    std::vector<uint32_t> depth;                       // [A]
+    std::vector<float> label_minmax;                   // [A][2]
+    std::vector<frdev::DeviceDataset::RfCand> cands;   // [A][nf][k-1]
+    std::vector<uint32_t> svals;                       // [items] the level's sorted arrays as the device holds them
+    std::vector<float> sv, sg;
+    std::vector<frdev::DeviceDataset::RfSplit> splits; // [A]
+    std::vector<double> child_out;                     // [A][2] the children's outputs (0.0 where the node did not split)
+    bool children_from_cands = false;                  // from the chosen candidate's sums, else rf_childsum_kernel
+};
+struct RFRecorder {
+    std::vector<RFLevelRecord> levels;
+    std::vector<double> root_out;  // [T] where rf_rootsum_kernel ran (some root did not split), else empty
+};
+
 class RFTrainer {
   public:
     RFTrainer(std::shared_ptr<DatasetView> view, Evaluator ev, RFParams p) : view_(std::move(view)), ev_(std::move(ev)), p_(p) {}
@@ -201,7 +219,8 @@ class RFTrainer {
             const size_t free_b = frdev::device_free_bytes();
             if (free_b != 0) budget = std::min(budget, std::max<size_t>((size_t)64 << 20, free_b / 5 * 2));
         }
-        if (const char* e = frdev::path_env("FR_RF_BATCH_BYTES")) budget = std::max<size_t>(1 << 20, (size_t)atoll(e));
+        // (no floor: a batch always takes its first tree -- `t1 > t0` below -- so a budget below one tree means one tree per batch)
+        if (const char* e = frdev::path_env("FR_RF_BATCH_BYTES")) budget = std::max<size_t>(1, (size_t)atoll(e));
         struct EndGuard {  // the batch buffers (GBs) go back to the device also when a batch fails
             frdev::DeviceDataset& d;
             ~EndGuard() { d.rf_end(); }
@@ -289,6 +308,27 @@ class RFTrainer {
 
     const RFStats& stats() const { return stats_; }
 
+    // The test hook's entry: ONE batch of trees over the given instance lists and feature lists, grown by grow_batch as
+    // learn_part grows a batch it sampled itself, with every level recorded.
+    Model grow_recorded(const std::vector<uint32_t>& root_off, const std::vector<uint32_t>& root_ids, uint32_t nf,
+                        const std::vector<uint32_t>& feats, RFRecorder& rec) {
+        frdev::DeviceDataset& dev = view_->device();
+        const DataCore& core = *view_->core;
+        std::string perr;
+        if (!dev.rf_set_presence(core.present_bits.empty() ? nullptr : core.present_bits.data(), core.present_words, core.n, &perr)) fail_str(perr);
+        struct EndGuard {
+            frdev::DeviceDataset& d;
+            ~EndGuard() { d.rf_end(); }
+        } end_guard{dev};
+        const uint32_t T = (uint32_t)root_off.size() - 1;
+        Model out;
+        out.kind = Model::Ensemble;
+        out.members.resize(T);
+        out.ens_weights.assign(T, 1.0);
+        grow_batch(dev, 0, T, root_off, root_ids, nf, feats, nullptr, out, stats_, &rec);
+        return out;
+    }
+
     // One tree over root_ids (one root: root_off = {0, n}) and the features feats, fitted to the LambdaMART gradients of the
     // device's last lambda_gradients() pass instead of the gains (lambdamart.hpp).  Leaf values are the grower's means.
     std::shared_ptr<TreeNode> grow_lambda_tree(frdev::DeviceDataset& dev, const std::vector<uint32_t>& root_off,
@@ -321,7 +361,7 @@ class RFTrainer {
 
     void grow_batch(frdev::DeviceDataset& dev, uint32_t t0, uint32_t t1, const std::vector<uint32_t>& root_off,
                     const std::vector<uint32_t>& root_ids, uint32_t nf, const std::vector<uint32_t>& feats,
-                    const uint32_t* positions, Model& out, RFStats& stats_) {
+                    const uint32_t* positions, Model& out, RFStats& stats_, RFRecorder* rec = nullptr) {
         const uint32_t T = t1 - t0;
         std::string err;
         auto tnow = [] { return std::chrono::steady_clock::now(); };
@@ -364,6 +404,15 @@ class RFTrainer {
             stats_.t_level += secs(tl0, tl1);
             stats_.levels++;
             stats_.candidates += cands.size();
+            if (rec) {
+                rec->levels.emplace_back();
+                RFLevelRecord& lv = rec->levels.back();
+                lv.active = active;
+                for (const Open& o : open) lv.depth.push_back(o.depth);
+                lv.label_minmax = lab;
+                lv.cands = cands;
+                if (!dev.rf_debug_sorted(&lv.svals, &lv.sv, &lv.sg, &err)) fail_str(err);
+            }
             std::vector<frdev::DeviceDataset::RfSplit> splits(open.size());
             std::vector<Open> next;
             struct Pending { size_t a; uint32_t left_n, right_n; double sum_l, sum_r; };
@@ -448,6 +497,12 @@ class RFTrainer {
             stats_.t_select += secs(tl1, tp0);
             if (!dev.rf_split(splits, sums_from_cands ? nullptr : &child_out, &err)) fail_str(err);
             stats_.t_split += secs(tp0, tnow());
+            if (rec) {
+                RFLevelRecord& lv = rec->levels.back();
+                lv.splits = splits;
+                lv.children_from_cands = sums_from_cands;
+                lv.child_out.assign(open.size() * 2, 0.0);
+            }
             for (const Pending& pd : pend) {
                 const Open& o = open[pd.a];
                 TreeNode* kids[2] = {o.node->lhs.get(), o.node->rhs.get()};
@@ -456,6 +511,7 @@ class RFTrainer {
                     kids[side]->leaf = true;
                     // random_forest.rs:395-398 (gain_sum / len, 0.0 for an empty side: rf_childsum_kernel's formula)
                     kids[side]->value = sums_from_cands ? (ns[side] ? (side ? pd.sum_r : pd.sum_l) / (double)ns[side] : 0.0) : child_out[pd.a * 2 + side];
+                    if (rec) rec->levels.back().child_out[pd.a * 2 + side] = kids[side]->value;
                     const uint32_t key = side ? splits[pd.a].right : splits[pd.a].left;
                     if (enterable(ns[side], o.depth + 1)) next.push_back({o.tree, key, ns[side], kids[side], kids[side]->value, o.depth + 1});
                 }
@@ -470,6 +526,7 @@ class RFTrainer {
             if (need) {
                 std::vector<double> root_out;
                 if (!dev.rf_root_outputs(&root_out, &err)) fail_str(err);
+                if (rec) rec->root_out = root_out;
                 for (uint32_t t = 0; t < T; t++)
                     if (roots[t]->leaf) roots[t]->value = root_out[t];
             }

@@ -326,6 +326,23 @@ bool DeviceDataset::rf_split(const std::vector<RfSplit>& splits, std::vector<dou
     return true;
 }
 
+bool DeviceDataset::rf_debug_sorted(std::vector<uint32_t>* svals, std::vector<float>* sv, std::vector<float>* sg, std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    auto& rf = m.rf;
+    const size_t items = rf.A == 0 ? 0 : (size_t)rf.items;
+    svals->assign(items, 0u), sv->assign(items, 0.0f), sg->assign(items, 0.0f);
+    if (items == 0) return true;
+    RFArgs a;
+    m.rf_args(a);
+    FR_HIP(hipMemcpyAsync(svals->data(), a.svals, items * 4, hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipMemcpyAsync(sv->data(), a.sv, items * 4, hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipMemcpyAsync(sg->data(), a.sg, items * 4, hipMemcpyDeviceToHost, m.stream));
+    FR_HIP(hipStreamSynchronize(m.stream));
+    return true;
+}
+
 void DeviceDataset::rf_end() {
     Impl& m = *impl_;
     std::lock_guard<std::mutex> lk(m.mu);

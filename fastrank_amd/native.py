@@ -443,6 +443,55 @@ def profile_stats() -> Dict[str, Dict[str, float]]:
     }
 
 
+# RfCandDev of csrc/kernels_rf.inc (48 bytes), as the device writes it
+RF_CAND_DTYPE = np.dtype([("position", "<f8"), ("importance", "<f8"), ("ids_i", "<u4"), ("flags", "<u4"), ("pos_l", "<u4"), ("pos_r", "<u4"),
+                          ("sum_l", "<f8"), ("sum_r", "<f8")])
+RF_ACTIVE_DTYPE = np.dtype([("tree", "<u4"), ("key", "<u4"), ("n", "<u4")])
+RF_SPLIT_DTYPE = np.dtype([("fslot", "<i4"), ("pos", "<u4"), ("left", "<u4"), ("right", "<u4")])
+RF_SPLIT_METHODS = ("SquaredError", "BinaryGiniImpurity", "InformationGain", "TrueVarianceReduction")
+
+
+def rf_levels(dataset: CDataset, root_off, root_ids, feats, split_candidates: int, split_method: int, min_leaf_support: int,
+              max_depth: int) -> Dict:
+    """One batch of random-forest trees grown by the trainer's own level loop with every level recorded (fr_debug_rf_levels;
+    DESIGN.md section 5.6).  Tree t grows over the instance ids root_ids[root_off[t]:root_off[t + 1]], in that order, and the
+    features feats[t] (T x nf).  Returns {"levels": [per level: active (tree, key, n), depth, label_minmax [A, 2], cands
+    [A, nf, k - 1] (RF_CAND_DTYPE), svals / sv / sg [items], splits [A], child_out [A, 2], children_from], "root_out": [T] or
+    empty, "trees": the DecisionTree dicts}."""
+    L = _load()
+    off = np.ascontiguousarray(root_off, dtype=np.uint32)
+    ids = np.ascontiguousarray(root_ids, dtype=np.uint32)
+    fl = np.ascontiguousarray(feats, dtype=np.uint32)
+    T = len(off) - 1
+    if fl.ndim != 2 or fl.shape[0] != T or len(ids) != int(off[-1]):
+        raise ValueError("rf_levels: feats must be [trees][nf] and root_ids as long as root_off says")
+    nf, k = fl.shape[1], int(split_candidates)
+    if RF_CAND_DTYPE.itemsize != 48:
+        raise RuntimeError("rf_levels: the candidate record is not 48 bytes")
+    head = _json_reply(L.fr_debug_rf_levels(dataset.pointer, off.ctypes.data, T, ids.ctypes.data, fl.ctypes.data, nf, k, int(split_method),
+                                            int(min_leaf_support), int(max_depth), None, 0))
+    if head["cand_bytes"] != RF_CAND_DTYPE.itemsize:
+        raise RuntimeError("rf_levels: the library's candidate record is not the one this module describes")
+    blob = np.zeros(max(int(head["bytes"]), 1), dtype=np.uint8)
+    _json_reply(L.fr_debug_rf_levels(None, None, 0, None, None, 0, 0, 0, 0, 0, blob.ctypes.data, int(head["bytes"])))
+    dtypes = {"active": RF_ACTIVE_DTYPE, "depth": np.uint32, "label_minmax": np.float32, "cands": RF_CAND_DTYPE, "svals": np.uint32,
+              "sv": np.float32, "sg": np.float32, "splits": RF_SPLIT_DTYPE, "child_out": np.float64, "root_out": np.float64}
+    levels = [dict(children_from=l["children_from"]) for l in head["levels"]]
+    root_out = np.zeros(0)
+    for s in head["sections"]:
+        arr = blob[s["offset"]:s["offset"] + s["bytes"]].copy().view(dtypes[s["name"]])
+        if s["name"] == "root_out":
+            root_out = arr
+            continue
+        A = head["levels"][s["level"]]["A"]
+        if s["name"] in ("label_minmax", "child_out"):
+            arr = arr.reshape(A, 2)
+        elif s["name"] == "cands":
+            arr = arr.reshape(A, nf, max(k - 1, 0))
+        levels[s["level"]][s["name"]] = arr
+    return {"levels": levels, "root_out": root_out, "trees": [t["DecisionTree"] for t in head["trees"]]}
+
+
 def last_train_stats() -> Dict:
     return _json_reply(_load().fr_last_train_stats())
 

@@ -307,6 +307,20 @@ const void *fr_debug_hist_reg_term(int64_t q, int64_t w, uint32_t n, int32_t s_l
 const void *fr_debug_goss_select(const CDataset *dataset, const double *lambda, size_t len, double top_rate,
                                  double other_rate, uint64_t seed, uint32_t tree, const uint32_t *queries, size_t n_queries,
                                  uint32_t *list_out, uint8_t *top_out, size_t cap, uint32_t *n_g_out, uint64_t *tau_out);
+/* Random-forest training, test hook: ONE batch of n_trees trees grown by the trainer's own level loop
+ * with every level recorded.  Tree t grows over the instance ids root_ids[root_off[t] .. root_off[t + 1]) in that order
+ * (root_off[0] = 0) and the features feats[t * nf .. t * nf + nf).  out == NULL: grows, keeps the record and returns a JSON
+ * header -- "levels": per level {"A", "items", "children_from": "candidates" | "rf_childsum_kernel"}; "sections": per array
+ * {"level", "name", "offset", "bytes"} inside the record, names active ([A] x (tree, key, n) u32), depth ([A] u32),
+ * label_minmax ([A][2] f32), cands ([A][nf][k-1] x the 48-byte candidate record: position f64, importance f64, ids_i u32,
+ * flags u32, pos_l u32, pos_r u32, sum_l f64, sum_r f64), svals / sv / sg ([items] u32 / f32 / f32: the level's sorted arrays
+ * as the device holds them), splits ([A] x (fslot i32, pos, left, right u32)), child_out ([A][2] f64), and after the last level
+ * root_out ([n_trees] f64 where a root did not split, else empty); "trees": the finished DecisionTree models; "bytes": the
+ * record's size.  out != NULL: copies the kept record (out_bytes must be its size) and forgets it; the other arguments are
+ * not read. */
+const void *fr_debug_rf_levels(const CDataset *dataset, const uint32_t *root_off, size_t n_trees, const uint32_t *root_ids,
+                               const uint32_t *feats, uint32_t nf, uint32_t split_candidates, int32_t split_method,
+                               uint32_t min_leaf_support, uint32_t max_depth, void *out, size_t out_bytes);
 /* Quantised gradients, test hooks ("Quantised gradients").  fr_debug_hist_quantise: the fixed-point step
  * and the quantisation to `bits` bits (2..8) under the key of tree `tree` of `seed`, for lambda / weight[len] by instance id
  * over the instances of queries[n_queries] (NULL = all) and, when goss != 0, over the GOSS list of those (rates, seed and tree

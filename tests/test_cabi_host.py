@@ -37,6 +37,10 @@ def test_library_exports_every_declared_symbol():
     # one histogram-tree hook taking an options record, not one hook per grower mode
     assert hasattr(lib, "fr_debug_hist_tree") and not any(
         hasattr(lib, "fr_debug_hist_tree_" + mode) for mode in ("sampled", "newton", "leafwise", "symmetric", "monotone", "goss"))
+    # one random-forest level hook through the trainer's own grow_batch, declared, exported and bound -- not one per kernel
+    assert "fr_debug_rf_levels" in syms and hasattr(lib, "fr_debug_rf_levels") and callable(native.rf_levels)
+    assert not any(hasattr(lib, "fr_debug_rf_" + part) for part in ("eval", "partition", "childsum", "label", "level"))
+    assert native.RF_CAND_DTYPE.itemsize == 48 and native.RF_SPLIT_DTYPE.itemsize == 16 and native.RF_ACTIVE_DTYPE.itemsize == 12
 
 
 def test_pricing_switches_are_not_in_the_shipped_library():

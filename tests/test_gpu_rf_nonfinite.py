@@ -99,7 +99,7 @@ def test_plus_inf_through_the_three_block_candidate_loop():
 
 
 def test_plus_inf_cut_into_batches(monkeypatch):
-    monkeypatch.setenv("FR_RF_BATCH_BYTES", "1")  # (the trainer's floor, 1 MiB: seven of these trees)
+    monkeypatch.setenv("FR_RF_BATCH_BYTES", "1")  # (below one tree's size: every tree is a batch of its own)
     X, y, qid = nf.four_hundred()
     X = nf.edit_column(X, "plus_inf")
     _check(fr.CDataset.from_numpy(X, y, qid), o.Dataset(X, y, qid), _request(nf.two_hundred_params(num_trees=16)), infinite=True)

@@ -214,6 +214,96 @@ def test_file_loaded_dataset_feature_stats_skip_absent_values(method):
     assert dense_exp != exp
 
 
+def _expected_stats(trees, sample, k, max_depth, budget=None):
+    """last_train_stats()'s groups / ticks / raw_evals of a forest, from the forest itself.  With min_leaf_support >= 2 every
+    child holds two instances or more, so exactly the nodes above max_depth looked for a split: a batch takes one level step
+    per depth that holds such a node in any of its trees, and a step evaluates nf x (k - 1) candidates for each of them.
+    Batches: a tree joins the batch while the batch's instances x nf x 41 bytes stay within the budget (the first always)."""
+    def by_depth(node, depth, out):
+        if depth < max_depth:
+            out[depth] = out.get(depth, 0) + 1
+        if "FeatureSplit" in node:
+            by_depth(node["FeatureSplit"]["lhs"], depth + 1, out)
+            by_depth(node["FeatureSplit"]["rhs"], depth + 1, out)
+        return out
+    nf = int(sample[0][0])
+    batches, cur, items = [], [], 0
+    for t in range(len(trees)):
+        if cur and budget is not None and (items + int(sample[t][1])) * nf * 41 > budget:
+            batches.append(cur)
+            cur, items = [], 0
+        cur.append(t)
+        items += int(sample[t][1])
+    batches.append(cur)
+    ticks = evals = 0
+    for b in batches:
+        counts = [by_depth(trees[t], 1, {}) for t in b]
+        ticks += max(max(c) for c in counts)
+        evals += sum(sum(c.values()) for c in counts) * nf * (k - 1)
+    return {"groups": len(batches), "ticks": ticks, "raw_evals": evals}
+
+
+def _stats_now():
+    st = native.last_train_stats()
+    return {key: st[key] for key in ("groups", "ticks", "raw_evals")}
+
+
+@pytest.mark.parametrize("method", ["SquaredError", "BinaryGiniImpurity"])
+def test_a_node_of_more_than_64_partition_tiles(method):
+    """131 073 instances in one node: the carry loop of rf_part_scan_kernel (segments of more than 64 tiles of 2 048 items)
+    places the second level's items; two trees over everything, their feature lists in different orders."""
+    rng = np.random.default_rng(7)
+    n = 64 * 2048 + 1
+    X = np.stack([rng.random(n), np.floor(rng.exponential(3.0, n))], axis=1).astype(np.float32)
+    y = rng.choice(5, size=n, p=[0.4, 0.3, 0.15, 0.1, 0.05]).astype(np.float64)
+    y = np.where(X[:, 0] > 0.55, np.minimum(y + 1.0, 4.0), y)
+    qid = (np.arange(n) // 100 + 1).astype(np.int64)
+    g, c = fr.CDataset.from_numpy(X, y, qid), o.Dataset(X, y, qid)
+    req = _request("ndcg@10", seed=3, num_trees=2, split_candidates=3, max_depth=4, min_leaf_support=10, split_method=method,
+                   instance_sampling_rate=1.0, feature_sampling_rate=1.0)
+    exp, sample = _oracle(c, req)
+    assert g.train_model(req).to_dict() == exp
+    assert (sample[:, 1] == n).all() and (n + 2047) // 2048 == 65
+    trees = [m["DecisionTree"] for m in exp["Ensemble"]["models"]]
+    assert all(json.dumps(t).count("FeatureSplit") >= 3 for t in trees), "both children of the root are partitioned out of it and split"
+    assert _stats_now() == _expected_stats(trees, sample, 3, 4)
+
+
+@pytest.mark.parametrize("method", ["SquaredError", "TrueVarianceReduction"])
+def test_three_candidate_blocks_on_real_valued_columns(method):
+    """split_candidates = 130 on real-valued columns: three trips of rf_eval_kernel's candidate loop, most lanes evaluated."""
+    X, y, qid = synth_dataset(91, 3000, 8, 40, max_len=200)
+    X[:, 1::2] = np.random.default_rng(1).normal(size=(3000, 4)).astype(np.float32)
+    g, c = fr.CDataset.from_numpy(X, y, qid), o.Dataset(X, y, qid)
+    req = _request("ndcg@10", seed=13, num_trees=4, split_candidates=130, max_depth=6, min_leaf_support=2, split_method=method)
+    exp, sample = _oracle(c, req)
+    assert g.train_model(req).to_dict() == exp
+    trees = [m["DecisionTree"] for m in exp["Ensemble"]["models"]]
+    assert min(json.dumps(t).count("FeatureSplit") for t in trees) > 10
+    assert _stats_now() == _expected_stats(trees, sample, 130, 6)
+
+
+@pytest.mark.parametrize("batch_bytes", [None, 4000000])
+def test_four_partitioned_levels_under_sampling_batching_and_weights(batch_bytes, monkeypatch):
+    """Sampling rates below one, weighted trees, nodes of several partition tiles over four levels after the root -- in one
+    batch and cut into batches of a few trees."""
+    if batch_bytes:
+        monkeypatch.setenv("FR_RF_BATCH_BYTES", str(batch_bytes))
+    X, y, qid = synth_dataset(55, 20000, 6, 100, max_len=400)
+    g, c = fr.CDataset.from_numpy(X, y, qid), o.Dataset(X, y, qid)
+    req = _request("ndcg@10", seed=21, num_trees=6, split_candidates=8, max_depth=6, min_leaf_support=3, weight_trees=True,
+                   instance_sampling_rate=0.6, feature_sampling_rate=0.5)
+    exp, sample = _oracle(c, req)
+    got = g.train_model(req).to_dict()
+    assert got["Ensemble"]["weights"] == exp["Ensemble"]["weights"] and got == exp
+    assert (sample[:, 0] == 3).all() and (sample[:, 1] > 4 * 2048).all() and (sample[:, 1] < 20000).all()
+    trees = [m["DecisionTree"] for m in exp["Ensemble"]["models"]]
+    want = _expected_stats(trees, sample, 8, 6, batch_bytes)
+    assert want["ticks"] == 5 * want["groups"], "five level steps per batch: four of them partition"
+    assert (want["groups"] > 1) == bool(batch_bytes) and want["groups"] < 6
+    assert _stats_now() == want
+
+
 def test_randomised_rf_training_soak():
     """tools/fuzz_rf.py: random small datasets and random RandomForestParams (all four split methods, sampled views, cut batches,
     several contexts); the device trainer must return the oracle's forest bit for bit."""

@@ -3,6 +3,10 @@
 gains), random RandomForestParams (all four split methods, weighted trees, sampling rates, depths, leaf supports, 2..40
 split candidates, batches cut by FR_RF_BATCH_BYTES), full datasets and query / feature samples; the device trainer must
 return the oracle's forest -- structure, thresholds, leaf values, weights -- bit for bit.
+FR_RF_BATCH_BYTES is drawn from 20 000 to 400 000 on half of the iterations.  A batch takes trees while its sampled instances x
+sampled features x 41 bytes stay within the budget, and always its first tree; the trainer applies no floor to the budget (it
+used to raise it to 1 MiB, which made every draw the same budget and cut only forests beyond it), so the draw decides how
+many trees share a batch.  The last line counts the iterations that ran in more batches than device contexts ("cut_batches").
 Usage: python tools/fuzz_rf.py --iters 300 [--seed 0]"""
 import argparse
 import json
@@ -16,6 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import fastrank_amd as fr  # noqa: E402
+from fastrank_amd import native  # noqa: E402
 from fuzz_parity import make_case  # noqa: E402
 from oracle import pyoracle as o  # noqa: E402
 
@@ -28,7 +33,7 @@ def main():
     rng = np.random.default_rng(args.seed)
     o.set_mean_segment(o.DEVICE_MEAN_SEGMENT)
     t0 = time.time()
-    bad = errs = nodes = sampled = fanned = 0
+    bad = errs = nodes = sampled = fanned = cut = 0
     methods = {}
     for it in range(args.iters):
         X, y, qid, measure, _ = make_case(rng)
@@ -79,6 +84,8 @@ def main():
             continue
         try:
             got = g.train_model(req).to_dict()
+            st = native.last_train_stats()
+            cut += int(st["groups"] > st["devices"])
         except Exception as exc:
             bad += 1
             print("MISMATCH iter", it, "device error", str(exc)[:120])
@@ -89,7 +96,7 @@ def main():
             bad += 1
             print("MISMATCH iter", it, json.dumps({"n": len(y), "d": X.shape[1], "measure": measure, "params": p.to_dict()}))
     print(json.dumps({"iters": args.iters, "mismatches": bad, "both_error": errs, "split_nodes": nodes, "methods": methods,
-                      "sampled_views": sampled, "over_several_contexts": fanned, "seconds": round(time.time() - t0, 1)}))
+                      "sampled_views": sampled, "over_several_contexts": fanned, "cut_batches": cut, "seconds": round(time.time() - t0, 1)}))
     return 1 if bad else 0
 
 
