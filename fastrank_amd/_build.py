@@ -47,6 +47,17 @@ def units():
     return [(obj, src, extra, _deps(src)) for obj, src, extra in out]
 
 
+def feature_units():
+    """Translation units added after tests/test_build_host.py pinned the list above, in the same form: feature normalisation
+    (DESIGN.md section 14).  tests/test_build_units_host.py holds them to the rules that test holds units() to."""
+    return [(obj, src, extra, _deps(src)) for obj, src, extra in [("normalize.o", "normalize.hip", [])]]
+
+
+def all_units():
+    """what the library is built from"""
+    return units() + feature_units()
+
+
 # -ffp-contract=off is a correctness flag, not a tuning flag: the reference's dot product is an
 # unfused f64 multiply-then-add (src/dense_dataset.rs:71-74) and rank order must be bit-exact.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
@@ -81,7 +92,7 @@ def _digest(src, extra, deps) -> str:
 
 def _lib_digest() -> str:
     h = hashlib.sha1()
-    for obj, src, extra, deps in units():
+    for obj, src, extra, deps in all_units():
         h.update((obj + ":" + _digest(src, extra, deps) + "\n").encode())
     return h.hexdigest()
 
@@ -135,14 +146,14 @@ def build(force: bool = False, verbose: bool = False) -> str:
 def _build_locked(force: bool, verbose: bool) -> str:
     hipcc = hipcc_path()
     lib_digest = _lib_digest()
-    todo = [(o, s, e, d) for o, s, e, d in units() if force or _stale(o, s, e, d)]
+    todo = [(o, s, e, d) for o, s, e, d in all_units() if force or _stale(o, s, e, d)]
     jobs = max(1, min(len(todo), int(os.environ.get("FR_BUILD_JOBS", str(os.cpu_count() or 4)))))
     if todo:
         with concurrent.futures.ThreadPoolExecutor(max_workers=jobs) as pool:
             futs = [pool.submit(_compile, hipcc, o, s, e, d, verbose) for o, s, e, d in todo]
             for f in futs:
                 f.result()
-    objs = [os.path.join(OBJ_DIR, o) for o, _, _, _ in units()]
+    objs = [os.path.join(OBJ_DIR, o) for o, _, _, _ in all_units()]
     tmp = "%s.%d.tmp" % (LIB_PATH, os.getpid())
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", tmp, "-lz", "-ldl"]
     if verbose:

@@ -137,6 +137,8 @@ def _load():
         "fr_last_load_stats": (vp, []),
         "fr_debug_dataset_core": (vp, [vp, C.c_char_p, vp, sz]),
         "fr_debug_text_number": (vp, [C.c_char_p, sz, vp, vp, vp]),
+        "fr_fit_normalizer": (vp, [vp, C.c_char_p]),
+        "fr_normalize_dataset": (res, [vp, C.c_char_p]),
     }
     for name, (restype, argtypes) in sigs.items():
         fn = getattr(L, name)
@@ -440,6 +442,16 @@ class CDataset:
     def instances_by_query(self) -> Dict[str, List[int]]:
         return self._query_json("instances_by_query")
 
+    def feature_stats(self) -> Dict[int, Dict[str, float]]:
+        """{feature id: {"num_elements", "mean", "variance", "max", "min", "total"}} over the values this dataset or view
+        holds, taken on the device: the records of Normalizer.fit(self, "zscore").  A feature held
+        by fewer than two instances has no record."""
+        return Normalizer.fit(self, "zscore").feature_stats()
+
+    def normalization(self) -> Optional[dict]:
+        """The normaliser that made this dataset (Normalizer.apply), as its wire form; None for any other dataset."""
+        return self._query_json("normalization")
+
     def evaluate(self, model: CModel, evaluator: str, qrel: CQRel = None) -> Dict[str, float]:
         self._require_init()
         model._require_init()
@@ -466,6 +478,98 @@ class CDataset:
         if not quiet:
             print("Wrote {} records to {} as {}.".format(response, output_path, system_name))
         return response
+
+
+_STAT_KEYS = ("num_elements", "mean", "variance", "max", "min", "total")
+
+
+class Normalizer:
+    """Feature normalisation (the reference's Normalizer, src/normalizers.rs): zscore and maxmin
+    fitted on a dataset or a view of one, the same two per query (RankLib's scope, nothing fitted), and sigmoid.  It holds
+    its wire form; statistics and transform run on the device."""
+
+    def __init__(self, wire: dict):
+        self._wire = Normalizer._checked(wire)
+
+    @staticmethod
+    def _method(method: str) -> str:
+        if method in ("maxmin", "linear"):
+            return "maxmin"
+        if method in ("zscore", "sigmoid"):
+            return method
+        raise Exception("Unsupported Normalizer: {0}".format(method))
+
+    @staticmethod
+    def _checked(wire: dict) -> dict:
+        import math
+
+        if not isinstance(wire, dict) or len(wire) != 1:
+            raise Exception("Unsupported Normalizer: {0!r}".format(wire))
+        [(name, body)] = wire.items()
+        if name == "SigmoidNormalizer":
+            if body != []:
+                raise Exception("Unsupported Normalizer: SigmoidNormalizer takes []")
+            return {"SigmoidNormalizer": []}
+        if name == "PerQuery":
+            if not isinstance(body, str) or Normalizer._method(body) == "sigmoid":
+                raise Exception("Unsupported Normalizer: {0}".format(body))
+            return {"PerQuery": Normalizer._method(body)}
+        if name not in ("ZScoreNormalizer", "MaxMinNormalizer"):
+            raise Exception("Unsupported Normalizer: {0}".format(name))
+        if not isinstance(body, dict) or not isinstance(body.get("feature_stats"), dict):
+            raise Exception("Normalizer: missing field `feature_stats`")
+        stats = {}
+        for fid, rec in body["feature_stats"].items():
+            if not isinstance(rec, dict) or int(fid) < 0:
+                raise Exception("Normalizer: feature {0} has no record".format(fid))
+            n = rec.get("num_elements")
+            if not isinstance(n, int) or isinstance(n, bool) or n < 0:
+                raise Exception("Normalizer: feature {0} has no count num_elements".format(fid))
+            out = {"num_elements": n}
+            for key in _STAT_KEYS[1:]:
+                v = rec.get(key)
+                if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+                    raise Exception("Normalizer: feature {0} has no finite number for {1}".format(fid, key))
+                out[key] = float(v)
+            stats[str(int(fid))] = out
+        return {name: {"feature_stats": stats}}
+
+    @staticmethod
+    def fit(dataset: CDataset, method: str) -> "Normalizer":
+        """The statistics of the values `dataset` (often a view: the training queries) holds, feature by feature."""
+        dataset._require_init()
+        Normalizer._method(method)
+        return Normalizer(_json_reply(_load().fr_fit_normalizer(dataset.pointer, method.encode("utf-8"))))
+
+    @staticmethod
+    def per_query(method: str) -> "Normalizer":
+        method = Normalizer._method(method)
+        if method == "sigmoid":
+            raise Exception("Unsupported Normalizer: sigmoid")
+        return Normalizer({"PerQuery": method})
+
+    @staticmethod
+    def sigmoid() -> "Normalizer":
+        return Normalizer({"SigmoidNormalizer": []})
+
+    @staticmethod
+    def from_dict(wire: dict) -> "Normalizer":
+        return Normalizer(wire)
+
+    def to_dict(self) -> dict:
+        return json.loads(json.dumps(self._wire))
+
+    def feature_stats(self) -> Dict[int, Dict[str, float]]:
+        [body] = self._wire.values()
+        if not isinstance(body, dict):
+            return {}
+        return dict((int(fid), dict(rec)) for fid, rec in body["feature_stats"].items())
+
+    def apply(self, dataset: CDataset) -> CDataset:
+        """A new unsampled dataset that owns its matrix: `dataset`'s rows with every held value transformed.  `dataset`
+        must be unsampled and must not be the result of an apply itself."""
+        dataset._require_init()
+        return CDataset(_unwrap(_load().fr_normalize_dataset(dataset.pointer, json.dumps(self._wire).encode("utf-8"))))
 
 
 def query_json(message: str):

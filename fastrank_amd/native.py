@@ -504,14 +504,15 @@ def last_load_stats() -> Dict:
 
 
 def loaded_arrays(dataset: CDataset) -> Dict:
-    """The host arrays of a file-loaded dataset (fr_debug_dataset_core), for the tests: x (n x d), gain, qix, qnames, docids,
-    doc_present, features, present_bits, present_words, has_docids.  qnames / docids are bytes (a comment need not be UTF-8)."""
+    """The host arrays of a file-loaded dataset, or of one Normalizer.apply made (fr_debug_dataset_core), for the tests: x
+    (n x d), gain, qix, qnames, docids, doc_present (empty for a dataset without document ids), features, present_bits,
+    present_words, has_docids.  qnames / docids are bytes (a comment need not be UTF-8)."""
     L = _load()
     s = _json_reply(L.fr_debug_dataset_core(dataset.pointer, None, None, 0))
     n, d = int(s["n"]), int(s["d"])
     out = {"n": n, "d": d, "present_words": int(s["present_words"]), "has_docids": bool(s["has_docids"]),
            "qnames": [bytes.fromhex(h) for h in s["qnames_hex"]], "docids": [bytes.fromhex(h) for h in s["docids_hex"]]}
-    for name, dtype, count in (("x", np.float32, n * d), ("gain", np.float32, n), ("qix", np.uint32, n), ("doc_present", np.uint8, n),
+    for name, dtype, count in (("x", np.float32, n * d), ("gain", np.float32, n), ("qix", np.uint32, n), ("doc_present", np.uint8, int(s["doc_present_len"])),
                                ("features", np.uint32, int(s["features_len"])), ("present_bits", np.uint32, int(s["present_bits_len"]))):
         arr = np.empty(count, dtype=dtype)
         _json_reply(L.fr_debug_dataset_core(dataset.pointer, name.encode("utf-8"), arr.ctypes.data if count else None, arr.nbytes))

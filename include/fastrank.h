@@ -496,8 +496,9 @@ const CResult *fr_load_ranksvm(const void *data_path, const void *feature_names_
  * "unsorted", "range", "near_tie": counts}, "seconds" {"read", "upload", "line_scan", "pass1", "pass2", "download",
  * "host_merge", "total"} (wall), and the constants "scan_slice", "stage_limit", "auto_threshold" (bytes). */
 const void *fr_last_load_stats(void);
-/* The host arrays of a file-loaded dataset, for the tests.  field == NULL: JSON {"n", "d", "present_words", "has_docids",
- * "present_bits_len", "features_len", "qnames_hex", "docids_hex" (the strings' bytes in hex)}; otherwise "x" (f32 n * d),
+/* The host arrays of a file-loaded dataset (or of one fr_normalize_dataset made), for the tests.  field == NULL: JSON {"n",
+ * "d", "present_words", "has_docids", "present_bits_len", "features_len", "doc_present_len", "qnames_hex", "docids_hex" (the
+ * strings' bytes in hex)}; otherwise "x" (f32 n * d),
  * "gain" (f32), "qix" (u32), "doc_present" (u8), "features" (u32) or "present_bits" (u32) is copied to `out`
  * (JSON {"bytes": n}; a wrong out_bytes or an unknown name is an error). */
 const void *fr_debug_dataset_core(const CDataset *dataset, const void *field, void *out, size_t out_bytes);
@@ -505,6 +506,24 @@ const void *fr_debug_dataset_core(const CDataset *dataset, const void *field, vo
  * reasons[i] = 0 and value64[i] / value32[i] = the value, or the code of the reason the token is declined with.  The JSON
  * reply lists the reasons' names by code. */
 const void *fr_debug_text_number(const void *tokens, size_t n, uint32_t *reasons, double *value64, float *value32);
+
+/* ---- Feature normalisation (the reference's Normalizer, src/normalizers.rs) ----
+ * fr_fit_normalizer: the normaliser of `method` ("zscore" | "maxmin" | "linear" | "sigmoid"; anything else is
+ * `Unsupported Normalizer: <method>`) fitted on the instances and features of `dataset` (a dataset or any view of one), as
+ * JSON in the reference's serde shape: {"ZScoreNormalizer": {"feature_stats": {"<fid>": {"num_elements", "mean", "variance",
+ * "max", "min", "total"}}}}, {"MaxMinNormalizer": {...}}, {"SigmoidNormalizer": []}; or an error envelope.  The statistics
+ * are taken on the device over the values the instances hold; a held NaN or infinity is refused (`non-finite value in
+ * feature F, instance I: feature statistics need finite values`).
+ * fr_normalize_dataset: a new unsampled dataset that owns its matrix -- `dataset`'s instances, gains, queries, document
+ * ids, feature names and presence bits, every held value transformed on the device by the normaliser `normalizer_json` (one
+ * of the three shapes above, or {"PerQuery": "zscore" | "maxmin"}: statistics per query and feature, nothing fitted).
+ * Refused: a sampled view (`normalise the whole dataset, then sample it`), a dataset that is itself the result of this call
+ * (`Cannot apply normalization twice!`), a result that is NaN (`Normalization.<method> NaN: feature F, instance I`).
+ * dataset_query_json learns "normalization" (the remembered normaliser's JSON, null for any other dataset) and
+ * "normalization_stats" (where the call that made the dataset spent its time: {"prepare_seconds", "allocate_seconds",
+ * "kernel_seconds", "download_seconds", "device_other_seconds", "core_build_seconds", "total_seconds"}, or null).  Without a HIP device both return the `no MI355X/HIP device available...` envelope. */
+const void *fr_fit_normalizer(const CDataset *dataset, const void *method);
+const CResult *fr_normalize_dataset(const CDataset *dataset, const void *normalizer_json);
 
 #ifdef __cplusplus
 }
