@@ -120,6 +120,7 @@ def _load():
         "fr_profile_reset": (None, []),
         "fr_profile_json": (vp, []),
         "fr_debug_resident_bound": (C.c_double, [C.c_int, C.c_double, C.c_double, C.c_double]),
+        "fr_debug_verify_end": (C.c_int, [C.c_int, sz, vp, vp, vp, vp, vp]),
         "fr_synchronize": (C.c_int, []),
         "fr_debug_device_plan": (vp, [C.c_char_p, C.c_int, C.c_uint32, C.c_int]),
         "fr_debug_fullrank_class": (C.c_uint32, [C.c_uint32]),

@@ -15,6 +15,7 @@
 #include "normalize_host.hpp"
 #include "lambdamart.hpp"
 #include "rf_train.hpp"
+#include "verify_end.hpp"
 
 using fr::FrError;
 using frjson::Value;
@@ -2785,6 +2786,75 @@ double fr_debug_resident_bound(int which, double a, double b, double c) {
         case 2: return frdev::resident_eps_extra(a, b, c);
         default: return std::numeric_limits<double>::quiet_NaN();
     }
+}
+
+// one norm against n dcg values: how many quotients differ bitwise from the division (*first: one of them).  3 * 10^10 pairs
+// in tests/test_verify_end_host.py: the loop is compiled a second time for hosts with FMA instructions, where
+// verify_quotient's five FMAs are five instructions instead of five calls into libm
+static inline __attribute__((always_inline)) size_t verify_end_row_body(const double* a, size_t n, double norm, size_t* first) {
+    const double rn = frdev::verify_rnorm(norm, true);
+    size_t bad = 0;
+    for (size_t i = 0; i < n; i++) {
+        const double got = rn == rn ? frdev::verify_quotient(a[i], norm, rn) : a[i] / norm, exp = a[i] / norm;
+        uint64_t gb, eb;
+        std::memcpy(&gb, &got, 8);
+        std::memcpy(&eb, &exp, 8);
+        if (gb != eb && bad++ == 0) *first = i;
+    }
+    return bad;
+}
+#if defined(__x86_64__)
+__attribute__((target("avx2,fma"))) static size_t verify_end_row_fma(const double* a, size_t n, double norm, size_t* first) {
+    return verify_end_row_body(a, n, norm, first);
+}
+#endif
+static size_t verify_end_row(const double* a, size_t n, double norm, size_t* first) {
+#if defined(__x86_64__)
+    if (__builtin_cpu_supports("avx2") && __builtin_cpu_supports("fma")) return verify_end_row_fma(a, n, norm, first);
+#endif
+    return verify_end_row_body(a, n, norm, first);
+}
+
+int fr_debug_verify_end(int which, size_t n, const double* a, const double* b, const double* c, const double* d, double* out) {
+    if (which == 0) {
+        for (size_t i = 0; i < n; i++) {
+            const double rn = frdev::verify_rnorm(b[i], true);
+            out[i] = rn == rn ? frdev::verify_quotient(a[i], b[i], rn) : a[i] / b[i];
+        }
+        return 0;
+    }
+    if (which == 1) {
+        for (size_t i = 0; i < n; i++) out[i] = frdev::verify_gap_bound(a[i], b[i], c[i], d[i]);
+        return 0;
+    }
+    if (which == 2) {
+        for (size_t i = 0; i < n; i++) out[i] = std::fma(a[i], b[i], c[i]);
+        return 0;
+    }
+    if (which == 3) {
+        // every a[i] against every b[j], j < m = (size_t)c[0]: how many quotients differ from the division, and the first pair
+        const size_t m = (size_t)c[0];
+        const unsigned nt = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+        std::vector<size_t> bad(nt, 0), first(nt, (size_t)-1);
+        std::vector<std::thread> pool;
+        for (unsigned t = 0; t < nt; t++)
+            pool.emplace_back([&, t]() {
+                for (size_t j = t; j < m; j += nt) {
+                    size_t f = (size_t)-1;
+                    const size_t k = verify_end_row(a, n, b[j], &f);
+                    if (k != 0 && bad[t] == 0) first[t] = j * n + f;
+                    bad[t] += k;
+                }
+            });
+        for (auto& th : pool) th.join();
+        size_t total = 0, f = (size_t)-1;
+        for (unsigned t = 0; t < nt; t++) total += bad[t], f = std::min(f, first[t]);
+        out[0] = (double)total;
+        out[1] = total ? a[f % n] : 0.0;
+        out[2] = total ? b[f / n] : 0.0;
+        return 0;
+    }
+    return -1;
 }
 
 const void* fr_profile_json(void) {

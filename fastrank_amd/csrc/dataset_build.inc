@@ -269,6 +269,7 @@ std::shared_ptr<DeviceDataset> DeviceDataset::create(const HostCSR& csr, std::st
     term_tables(runs.qstart, runs.qlen, m.maxlen, &gt);
     m.ncls = gt.ncls;
     m.tablen = gt.tablen;
+    m.dcg_terms_in_range = verify_terms_in_range(gt.dcgtab.data(), gt.dcgtab.size());
 
     lap("per-position tables (host)");
     {
@@ -612,6 +613,7 @@ std::shared_ptr<DeviceDataset> DeviceDataset::create_view(const std::shared_ptr<
     m.colmax = pm.colmax;  // maxima over a superset of the view's documents: still upper bounds
     m.ncls = pm.ncls;
     m.tablen = pm.tablen;
+    m.dcg_terms_in_range = pm.dcg_terms_in_range;
     m.relmask = pm.relmask;
     // ---- the view's queries, runs, tiles and walk tiles inside the parent's position space
     RunPlan v;

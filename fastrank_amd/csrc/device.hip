@@ -55,6 +55,7 @@
 
 #include "fullverify.hpp"
 #include "linesearch_policy.hpp"
+#include "verify_end.hpp"
 #define FR_QUANT_ARITHMETIC_ONLY  // (lambdamart_quant.hpp without host.hpp: the integer arithmetic the kernels share with the host)
 #include "lambdamart_quant.hpp"
 #include "text_parse.hpp"

@@ -86,6 +86,7 @@ struct DatasetDesc {
     std::vector<SizeClass> fv_classes;    // queries bucketed by the cheapest class of kernels_fullverify.inc (npad = index into FV_CLASSES)
     uint64_t relmask = 0;              // bit c: gain class c has gain > 0
     size_t ncls = 0, tablen = 0;
+    bool dcg_terms_in_range = false;   // every term of dcgtab is 0 or of a magnitude verify_quotient is proven for (verify_end.hpp)
 };
 
 // create()'s helper thread tells the tile thread that the main stream exists, or that it could not be made
@@ -262,7 +263,7 @@ struct DeviceDataset::Impl : DatasetDesc {
     DevBuf<int> flags;
     DevBuf<unsigned long long> dbgc;
     // work buffers
-    DevBuf<double> scores, acc, weights, M, means, partial, norms, gw, gcand;
+    DevBuf<double> scores, acc, weights, M, means, partial, norms, rnorms, gw, gcand;
     DevBuf<uint32_t> gfeat, gncand;
     DevBuf<TreeNodeDev> nodes;
     DevBuf<int32_t> roots;
@@ -426,11 +427,18 @@ struct DeviceDataset::Impl : DatasetDesc {
     std::vector<double> norms_cache;
     uint64_t norms_token = 0;               // resident-sum ticket of the trainer whose norms array (norms_token_ptr) is on the device
     const double* norms_token_ptr = nullptr;
+    // ... and beside them their reciprocals for the NDCG@k verify kernel's quotient (verify_end.hpp: IEEE division here, once
+    // per query; NaN where the kernel must divide) -- always uploaded together, so what holds for one array holds for both
+    std::vector<double> rnorms_cache;
     bool upload_norms(const double* v, std::string* err) {
         if (norms_cache.size() == nq && std::memcmp(norms_cache.data(), v, nq * sizeof(double)) == 0) return true;
+        if (!rnorms.ensure(nq, err)) return false;
         norms_token = 0;  // (other contents: whatever stood for the old ones no longer does)
         norms_cache.assign(v, v + nq);
+        rnorms_cache.resize(nq);
+        for (size_t q = 0; q < nq; q++) rnorms_cache[q] = verify_rnorm(norms_cache[q], dcg_terms_in_range);
         FR_HIP(hipMemcpyAsync(norms.p, norms_cache.data(), nq * sizeof(double), hipMemcpyHostToDevice, stream));
+        FR_HIP(hipMemcpyAsync(rnorms.p, rnorms_cache.data(), nq * sizeof(double), hipMemcpyHostToDevice, stream));
         return true;
     }
     bool pull_flags(std::string* err) {
@@ -1800,6 +1808,7 @@ void DeviceDataset::Impl::topk_args(LsCtx& c, size_t G) const {
     a.wt_start = m.wt_start.p;
     a.run_wt0 = m.run_wt0.p;
     a.norms = m.norms.p;
+    a.rnorms = m.rnorms.p;
     a.disc = m.disc.p;
     a.gfeat = c.td<uint32_t>(ts.o_gfeat);
     a.gw = c.td<double>(ts.o_gw);

@@ -14,6 +14,7 @@ struct LSArgs {
     const uint32_t* wt_start; // [walk tiles + 1] RESIDENT verify kernel: first position of every walk tile (kernels_order.inc)
     const uint32_t* run_wt0;  // [nruns] ... and the walk tile that holds the run's first document
     const double* norms;
+    const double* rnorms;     // [nq] verify kernel: fl(1 / norms[q]) where verify_quotient (verify_end.hpp) stands for the division, NaN elsewhere
     const double* disc;
     const uint32_t* gfeat;    // [G]
     const double* gw;         // [G][4*dq] zero padded

@@ -187,6 +187,12 @@ template <int K, int GW, bool RESIDENT, int XS = 1, bool DUP = false>
 __global__ __launch_bounds__(WAVE, (RESIDENT && GW == 1) ? (K >= 20 ? (XS > 1 ? VERIFY_RES_WAVES_20_LONG : VERIFY_RES_WAVES_20) : (XS > 2 ? VERIFY_RES_WAVES_LONG : VERIFY_RES_WAVES)) : (GW >= 4 ? 2 : ((K >= 20 && GW == 2) ? 3 : 4)))
 void linesearch_verify_kernel(LSArgs a) {
     constexpr int KS = K + XS;
+    // The fast query end -- one gap bound per query in front of the exact pair tests, the quotient without the division (both
+    // below, "the current query is complete") -- is compiled into the plain K = 10, XS = 1 variants only: the others are at the
+    // edge of their registers, and either part moves them over it (measured by their ISA, profiles/verify_query_end_isa.txt:
+    // K = 5 loses its eighth wave, K = 20 spills 120 bytes, the XS > 1 and DUP variants read up to 156 more spilled scalars
+    // back with v_readlane).  They keep the walk and the division as they were.
+    constexpr bool FAST_END = K == 10 && XS == 1 && !DUP;
     // positions staged per step: a 64-document tile of the feature matrix, or (RESIDENT) a walk tile of up to WT positions that
     // holds whole queries where it can (kernels_order.inc), DPL documents per lane in phase S
     constexpr uint32_t VT = RESIDENT ? WT : (uint32_t)WAVE;
@@ -494,6 +500,8 @@ void linesearch_verify_kernel(LSArgs a) {
             if (q_end - pb > nvalid) break;  // the query continues in the next tile (q_end never lies behind the run's end)
             // ---- the current query is complete: NDCG@k (src/evaluators.rs:255-272,350-380) ----
             const double norm = a.norms[q];
+            double rnorm = 0.0;  // (its reciprocal, or NaN where the quotient below must be a division)
+            if constexpr (FAST_END) rnorm = a.rnorms[q];
             const double gam = a.gamma;  // (the relative part of a key's error bound: uniform)
             const uint32_t Ld = (uint32_t)a.depth < qn ? (uint32_t)a.depth : qn;
 #pragma unroll
@@ -565,21 +573,64 @@ void linesearch_verify_kernel(LSArgs a) {
                             // row: adding +0.0 leaves the sum as it is -- it starts at +0.0 and is never -0.0); the pair
                             // (i, i + 1) must be far apart, or inside the cut of one class, if a document i + 1 exists.  The
                             // list is sorted, so the finiteness test of its largest key covers all of them.
+                            //
+                            // The pair test, cheap first.  In almost every wave every tested pair lies far apart, and then
+                            // neither the exact bound nor the classes decide anything.  So each lane forms ONE bound for the
+                            // whole query, tau >= verify_far's right-hand side for every pair its walk tests (verify_end.hpp:
+                            // verify_gap_bound, from the larger magnitude of the first and the last key counted -- the list is
+                            // sorted), and a rank costs the difference and one compare.  Only where some lane's pair is not
+                            // beyond tau does the wave execute, for that rank alone, the test as it always stood -- verify_far,
+                            // the class compare, the cut rule -- so what is decided is what was decided before, bit for bit:
+                            // `diff > tau` implies `far`, and with `far` the rank leaves ok as it is.
                             ok = slot[gi][0] < __builtin_huge_val();
+                            if constexpr (FAST_END) {
+                                // the pairs tested: (i, i + 1) with i < Ld and i + 1 < qn, i.e. i < npair; the last key one of them
+                                // reads is slot npair -- K for every query longer than a full-depth cut, and never a -inf of a
+                                // short query's padding
+                                const uint32_t npair = Ld < qn - 1u ? Ld : qn - 1u;  // (uniform)
+                                double k_last = slot[gi][K];
+                                if (npair < (uint32_t)K) {
 #pragma unroll
-                            for (int i = 0; i < K; i++) {
-                                const bool counts = (uint32_t)i < Ld;
-                                const uint32_t lo_i = (uint32_t)__double_as_longlong(slot[gi][i]);
-                                const uint32_t lo_n = (uint32_t)__double_as_longlong(slot[gi][i + 1]);
-                                const uint32_t roff = (counts ? (uint32_t)i : (uint32_t)K) * ts;  // (uniform)
-                                const double term = dtab[roff + (lo_i & cmask_plain)];
-                                const bool need = counts && (uint32_t)(i + 1) < qn;
-                                const bool incut = (uint32_t)(i + 1) < Ld;
-                                const bool far = verify_far(slot[gi][i], slot[gi][i + 1], my_eps2[gi], gam);
-                                const bool same = ((lo_i ^ lo_n) & cmask_plain) == 0u;
-                                ok &= !need | far | (incut & same);
-                                dcg = dcg + term;
-                                if constexpr (K <= 10) { VERIFY_RANK_BARRIER }  // (K = 20: the serialised ranks cost more vector registers than the kernel has)
+                                    for (int m = 0; m < K; m++)
+                                        if (npair == (uint32_t)m) k_last = slot[gi][m];
+                                }
+                                const double tau = verify_gap_bound(slot[gi][0], k_last, gam, my_eps2[gi]);
+#pragma unroll
+                                for (int i = 0; i < K; i++) {
+                                    const bool counts = (uint32_t)i < Ld;
+                                    const uint32_t lo_i = (uint32_t)__double_as_longlong(slot[gi][i]);
+                                    const uint32_t roff = (counts ? (uint32_t)i : (uint32_t)K) * ts;  // (uniform)
+                                    const double term = dtab[roff + (lo_i & cmask_plain)];
+                                    const bool need = (uint32_t)i < npair;  // (uniform: ranks past a short query's end test nothing)
+                                    const bool cheap_far = (slot[gi][i] - slot[gi][i + 1]) > tau;
+                                    if (__builtin_expect(__ballot(need & !cheap_far) != 0ull, 0)) {
+                                        const uint32_t lo_n = (uint32_t)__double_as_longlong(slot[gi][i + 1]);
+                                        const bool incut = (uint32_t)(i + 1) < Ld;
+                                        const bool far = verify_far(slot[gi][i], slot[gi][i + 1], my_eps2[gi], gam);
+                                        const bool same = ((lo_i ^ lo_n) & cmask_plain) == 0u;
+                                        ok &= far | (incut & same);
+                                    }
+                                    dcg = dcg + term;
+                                    VERIFY_RANK_BARRIER
+                                }
+                            } else {
+                                // (K = 5 and K = 20 keep every rank's exact test, see FAST_END; the ranks of K = 20 are not serialised
+                                // either -- that costs more vector registers than the kernel has)
+#pragma unroll
+                                for (int i = 0; i < K; i++) {
+                                    const bool counts = (uint32_t)i < Ld;
+                                    const uint32_t lo_i = (uint32_t)__double_as_longlong(slot[gi][i]);
+                                    const uint32_t lo_n = (uint32_t)__double_as_longlong(slot[gi][i + 1]);
+                                    const uint32_t roff = (counts ? (uint32_t)i : (uint32_t)K) * ts;  // (uniform)
+                                    const double term = dtab[roff + (lo_i & cmask_plain)];
+                                    const bool need = counts && (uint32_t)(i + 1) < qn;
+                                    const bool incut = (uint32_t)(i + 1) < Ld;
+                                    const bool far = verify_far(slot[gi][i], slot[gi][i + 1], my_eps2[gi], gam);
+                                    const bool same = ((lo_i ^ lo_n) & cmask_plain) == 0u;
+                                    ok &= !need | far | (incut & same);
+                                    dcg = dcg + term;
+                                    if constexpr (K <= 10) { VERIFY_RANK_BARRIER }
+                                }
                             }
                         } else {
     #pragma unroll
@@ -615,7 +666,10 @@ void linesearch_verify_kernel(LSArgs a) {
                     double val = 0.0;
                     if (norm == norm) {
                         if (ok && dcg > norm) atomicOr(a.flags, FLAG_ACTUAL_GT_IDEAL);
-                        val = dcg / norm;
+                        // dcg / norm without the division where the host proved it (rnorm = fl(1 / norm); NaN = divide):
+                        // five FMAs give the correctly rounded quotient, verify_end.hpp states the argument and its ranges
+                        if constexpr (FAST_END) val = (rnorm == rnorm) ? verify_quotient(dcg, norm, rnorm) : dcg / norm;  // (uniform)
+                        else val = dcg / norm;
                     }
                     a.M[(size_t)q * a.ldm + (size_t)(g0 + gi) * 64 + lane] = val;
                     qbad[gi] = !ok && !(LS_DEBUG(a) & 1);  // (debug 1: the walk's verdict is meaningless without phase K -- nothing is listed)

@@ -409,6 +409,16 @@ int fr_synchronize(void);
  * 2: the term a candidate key's error bound gains from the resident form (a = bound, b = norm, c = T).
  * No device needed.  NaN for an unknown `which`. */
 double fr_debug_resident_bound(int which, double a, double b, double c);
+/* The arithmetic of a query's end in the NDCG@k bound-and-verify kernel (csrc/verify_end.hpp), over n entries, so that a
+ * CPU test can hold the code the kernel compiles to the expressions it stands for.  which = 0: out[i] = the division-free
+ * quotient a[i] / b[i] (a = dcg, b = norm) with the reciprocal the host uploads for b[i]; where that is "divide" (norm out of
+ * range, zero, NaN), the division itself.  c and d are not read.  which = 1: out[i] = the per-query gap bound from the first
+ * and last counted key a[i], b[i], the relative part c[i] and the absolute part d[i] of a pair's error bound.
+ * which = 2: out[i] = fma(a[i], b[i], c[i]), the primitive a numpy restatement of either needs.  which = 3: every dcg a[i],
+ * i < n, against every norm b[j], j < c[0]: out[0] = the number of pairs whose quotient differs bitwise from a[i] / b[j],
+ * out[1], out[2] = one such pair (on a few host threads; out holds three entries).
+ * No device needed.  Returns 0, or -1 for an unknown `which`. */
+int fr_debug_verify_end(int which, size_t n, const double* a, const double* b, const double* c, const double* d, double* out);
 /* Size class of the full-ranking bound-and-verify kernel (depth-less NDCG, MAP, NDCG@>20) for a query of `len` documents:
  * (keys per lane << 16) | lanes per candidate.  No device needed (the CPU tests check that every length has a class that
  * holds it and that classes grow with the length). */
