@@ -4,10 +4,11 @@ Same names as the reference package (fastrank/__init__.py:2-7): CQRel, CDataset,
 query_json, TrainRequest.  All computation happens in libfastrank_amd.so (HIP, gfx950).
 """
 from .clib import CDataset, CModel, CQRel, Normalizer, query_json
+from .compare import compare_models
 from .training import CoordinateAscentParams, LambdaMARTParams, RandomForestParams, TrainRequest
 
 VERSION_TUPLE = (0, 7, 0)
 __version__ = "{}.{}.{}".format(*VERSION_TUPLE)
 
-__all__ = ["clib", "training", "native", "CQRel", "CDataset", "CModel", "Normalizer", "query_json", "TrainRequest",
+__all__ = ["clib", "training", "native", "CQRel", "CDataset", "CModel", "Normalizer", "query_json", "compare_models", "TrainRequest",
            "CoordinateAscentParams", "RandomForestParams", "LambdaMARTParams"]

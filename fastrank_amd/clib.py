@@ -140,6 +140,8 @@ def _load():
         "fr_debug_text_number": (vp, [C.c_char_p, sz, vp, vp, vp]),
         "fr_fit_normalizer": (vp, [vp, C.c_char_p]),
         "fr_normalize_dataset": (res, [vp, C.c_char_p]),
+        "fr_resample": (vp, [vp, sz, sz, C.c_char_p, vp, vp]),
+        "fr_compare_models": (vp, [C.POINTER(vp), sz, vp, vp, C.c_char_p, C.c_char_p]),
     }
     for name, (restype, argtypes) in sigs.items():
         fn = getattr(L, name)
@@ -463,6 +465,19 @@ class CDataset:
         return _json_reply(
             _load().evaluate_by_query(model.pointer, self.pointer, qrel_pointer, evaluator.encode("utf-8"))
         )
+
+    def bootstrap_eval(self, model: CModel, evaluator: str, qrel: CQRel = None, trials: int = 200, seed: int = 0) -> Dict:
+        """The reference's SetEvaluator::bootstrap_eval (src/evaluators.rs:157-171) with PercentileStats::summary: the
+        model's per-query values resampled with replacement `trials` times on the device.  Returns
+        {"mean": the observed mean, "summary": {"p5", "p25", "p50", "p75", "p95"} of the trials' means, "interval": [lo, hi]
+        at level 0.95 from order statistics}.  The percentiles are the reference's PercentileStats::percentile exactly as
+        written, including its interpolation weights, which give the NEARER of the two order statistics the smaller
+        weight.  The random numbers cannot be the reference's: it draws from oorandom's Rand64(0xdeadbeef), whose source is
+        not available; the draws here are a function of `seed`, the trial and the number of queries."""
+        from .compare import compare_models
+
+        rep = compare_models(self, {"model": model}, evaluator, qrel=qrel, trials=trials, seed=seed)
+        return {"mean": rep["means"]["model"], "summary": rep["summary"]["model"], "interval": rep["intervals"]["model"]}
 
     def predict_scores(self, model: CModel) -> Dict[int, float]:
         return model.predict_scores(self)

@@ -48,6 +48,9 @@
 //     train_hist.inc          the launchers of kernels_hist.inc and kernels_histreg.inc, level-wise and leaf-wise, of kernels_goss.inc and kernels_histquant.inc
 //   kernels_text.inc        the device text parser's kernels (line scan, the two parsing passes); text_parse.inc launches them
 //                           (text_parse.hpp: the interface loader.hpp uses; text_number.hpp: grammar and value rule)
+//   kernels_resample.inc    resample_boot_kernel / resample_perm_kernel: paired bootstrap and per-query permutation of a table of
+//                           per-query values, a lane per trial; resample.inc launches them (resample.hpp: the interface and the
+//                           definition; resample_host.hpp: the report the host makes of their output)
 #include "device.hpp"
 
 #include <hip/hip_runtime.h>
@@ -59,6 +62,7 @@
 #define FR_QUANT_ARITHMETIC_ONLY  // (lambdamart_quant.hpp without host.hpp: the integer arithmetic the kernels share with the host)
 #include "lambdamart_quant.hpp"
 #include "text_parse.hpp"
+#include "resample.hpp"
 
 #include <cstring>
 #include <dlfcn.h>
@@ -105,5 +109,7 @@ namespace frdev {
 #include "rccl_exchange.inc"
 #include "kernels_text.inc"
 #include "text_parse.inc"
+#include "kernels_resample.inc"
+#include "resample.inc"
 
 }  // namespace frdev

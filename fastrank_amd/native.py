@@ -108,6 +108,25 @@ def evaluate_dense(model: CModel, dataset: CDataset, evaluator: str, qrel: Optio
     return json.loads(_take_str(qids_ptr.value)), out
 
 
+def resample(V, trials: int, seed: int, alpha: float = 0.05, boot: bool = True, perm: bool = True) -> Tuple[Dict, Optional[np.ndarray], Optional[np.ndarray]]:
+    """fr_resample (include/fastrank.h): V[Q, M] float64, row q one query's value under each of M
+    systems.  Returns (report, boot, perm): the host's report with the call's stats, and the paired bootstrap's and the
+    per-query permutation's means, trials x M float64 in trial order (None where boot / perm is False: that kernel is skipped)."""
+    V = np.asarray(V, dtype=np.float64)
+    if V.ndim != 2:
+        raise ValueError("resample takes a table V[Q, M]")
+    V = np.ascontiguousarray(V)
+    nq, ncols = V.shape
+    t = int(trials)
+    rows = t if 0 < t <= (1 << 20) else 0  # (out of range: refused by the call before it writes)
+    out_b = np.zeros((rows, ncols), dtype=np.float64) if boot else None
+    out_p = np.zeros((rows, ncols), dtype=np.float64) if perm else None
+    options = {"trials": t, "seed": int(seed), "alpha": float(alpha)}
+    rep = _json_reply(_load().fr_resample(V.ctypes.data if V.size else None, nq, ncols, json.dumps(options).encode("utf-8"),
+                                          out_b.ctypes.data if boot and rows else None, out_p.ctypes.data if perm and rows else None))
+    return rep, out_b, out_p
+
+
 def lambdamart_sample(dataset: CDataset, params, tree: int) -> Tuple[np.ndarray, np.ndarray]:
     """The sample LambdaMART's trainer uses for tree `tree` of `params` (LambdaMARTParams or its wire dict) on `dataset`:
     (feature ids ascending, indices of the view's queries ascending).  Needs no device."""

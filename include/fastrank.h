@@ -535,6 +535,25 @@ const void *fr_debug_text_number(const void *tokens, size_t n, uint32_t *reasons
 const void *fr_fit_normalizer(const CDataset *dataset, const void *method);
 const CResult *fr_normalize_dataset(const CDataset *dataset, const void *normalizer_json);
 
+/* ---- Model comparison: bootstrap intervals and permutation tests (the reference's
+ * SetEvaluator::bootstrap_eval and PercentileStats, src/evaluators.rs:157-171, src/stats.rs:126-165) ----
+ * fr_resample: `values` is a row-major f64 table of nq rows (queries) and ncols columns (systems, 1..8), every value finite
+ * (`non-finite value in row R, column C: ...` otherwise).  options_json: {"trials": 1..2^20 (10000), "seed": u64 (0),
+ * "alpha": 0 < a < 1 (0.05)}, each optional, any other key refused by name.  On the current device: the paired bootstrap into
+ * out_boot and the per-query permutation (randomised Tukey HSD; two systems: the paired randomisation test) into out_perm,
+ * trials x ncols f64 each in trial order; either may be NULL, which skips its kernel and its parts of the report.  Streams and
+ * the sums' shape: csrc/resample.hpp.  Returns JSON: {"means": [..], "intervals": [[lo, hi], ..], "summary": [{"p5", "p25",
+ * "p50", "p75", "p95"}, ..] (the reference's percentile, interpolation as written), "pairs": [{"i", "j", "diff",
+ * "diff_interval": [lo, hi], "p", "wins", "losses", "ties"}, ..] for i < j, "trials", "seed", "alpha", "boot_path": "lds" |
+ * "global", "boot_ms", "perm_ms", "upload_ms", "download_ms", "device_call_ms", "report_ms"}, or an error envelope (without a
+ * HIP device: `no MI355X/HIP device available...`).
+ * fr_compare_models: evaluates each of the n_models models (1..8) on `dataset` (a dataset or any view: the same queries in the
+ * same order for all) through fr_evaluate_dense's path, makes the table of per-query values, and returns fr_resample's report
+ * of it plus "queries" (their number).  With one model the permutation is skipped. */
+const void *fr_resample(const double *values, size_t nq, size_t ncols, const void *options_json, double *out_boot, double *out_perm);
+const void *fr_compare_models(const CModel *const *models, size_t n_models, const CDataset *dataset, const CQRel *qrel_or_null,
+                              const void *evaluator_name, const void *options_json);
+
 #ifdef __cplusplus
 }
 #endif
