@@ -5,10 +5,11 @@ query_json, TrainRequest.  All computation happens in libfastrank_amd.so (HIP, g
 """
 from .clib import CDataset, CModel, CQRel, Normalizer, query_json
 from .compare import compare_models
+from .importance import permutation_importance
 from .training import CoordinateAscentParams, LambdaMARTParams, RandomForestParams, TrainRequest
 
 VERSION_TUPLE = (0, 7, 0)
 __version__ = "{}.{}.{}".format(*VERSION_TUPLE)
 
-__all__ = ["clib", "training", "native", "CQRel", "CDataset", "CModel", "Normalizer", "query_json", "compare_models", "TrainRequest",
+__all__ = ["clib", "training", "native", "CQRel", "CDataset", "CModel", "Normalizer", "query_json", "compare_models", "permutation_importance", "TrainRequest",
            "CoordinateAscentParams", "RandomForestParams", "LambdaMARTParams"]

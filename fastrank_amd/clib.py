@@ -142,6 +142,8 @@ def _load():
         "fr_normalize_dataset": (res, [vp, C.c_char_p]),
         "fr_resample": (vp, [vp, sz, sz, C.c_char_p, vp, vp]),
         "fr_compare_models": (vp, [C.POINTER(vp), sz, vp, vp, C.c_char_p, C.c_char_p]),
+        "fr_permutation_importance": (vp, [vp, vp, vp, C.c_char_p, C.c_char_p, vp, sz, vp]),
+        "fr_debug_permutation_sources": (vp, [vp, C.c_uint64, C.c_uint32, C.c_char_p, vp, sz]),
     }
     for name, (restype, argtypes) in sigs.items():
         fn = getattr(L, name)
@@ -320,6 +322,13 @@ class CModel:
         ids, mean_abs, _ = native.feature_importance(self, dataset, background)
         names = dataset.feature_index_to_name()
         return dict((names[int(f)], float(v)) for f, v in zip(ids, mean_abs))
+
+    def permutation_importance(self, dataset: "CDataset", evaluator: str, **kw) -> Dict:
+        """How far `evaluator` falls on `dataset` when one feature at a time is shuffled: fastrank_amd.permutation_importance
+         with this model; `kw`: qrel, repeats, seed, scope, features."""
+        from .importance import permutation_importance
+
+        return permutation_importance(dataset, self, evaluator, **kw)
 
     def __str__(self):
         return str(self.to_dict())

@@ -51,6 +51,9 @@
 //   kernels_resample.inc    resample_boot_kernel / resample_perm_kernel: paired bootstrap and per-query permutation of a table of
 //                           per-query values, a lane per trial; resample.inc launches them (resample.hpp: the interface and the
 //                           definition; resample_host.hpp: the report the host makes of their output)
+//   kernels_permute.inc     permute_linear_kernel / permute_trees_kernel / permute_single_kernel: a model's scores on the dataset
+//                           with one column read from other rows, a chunk of columns and every repeat at once; permute.inc launches
+//                           them (permute.hpp: the interface and the definition; permute_host.hpp: stream, options, report)
 #include "device.hpp"
 
 #include <hip/hip_runtime.h>
@@ -111,5 +114,7 @@ namespace frdev {
 #include "text_parse.inc"
 #include "kernels_resample.inc"
 #include "resample.inc"
+#include "kernels_permute.inc"
+#include "permute.inc"
 
 }  // namespace frdev

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "dataset_layout.hpp"  // HostCSR, the walk tiles and the rest of the host-side layout arithmetic
+#include "permute.hpp"         // PermuteMember, PermuteStats (permutation importance)
 
 namespace frdev {
 
@@ -447,6 +448,22 @@ class DeviceDataset {
     bool tile_form(TileForm* out, std::string* err);
 
     int take_flags();  // returns and clears the accumulated kernel error bits
+
+    // --- permutation importance (kernels_permute.inc + permute.inc; DESIGN.md section 16, permute.hpp) -----------
+    // [np] per padded position the instance id of this dataset's document there (IDX_INVALID: none); host memory
+    const uint32_t* position_instances(size_t* np) const;
+    // src_pos[r * np + p]: the position whose value of the permuted feature position p reads in repeat r (p itself wherever
+    // no document of this dataset sits); uploaded once per call
+    bool permute_begin(const uint32_t* src_pos, uint32_t R, PermuteStats* stats, std::string* err);
+    // how many features a chunk may hold: max_slots (0: half of the free HBM) over R slots each, `sets` sets of score slots
+    // beside the nq x B result matrix
+    size_t permute_chunk_features(size_t nfeat, uint32_t R, size_t max_slots, size_t sets) const;
+    // score slot fi * R + r = the model's scores on D_{feats[fi], r} (feats ascending); with `ensemble` the members are added
+    // in order, else there is one member.  Waits for the stream.
+    bool permute_score(const uint32_t* feats, size_t nf, const std::vector<PermuteMember>& members, bool ensemble, PermuteStats* stats,
+                       std::string* err);
+    // frees what permute_begin and permute_score allocated, the grown score slots included
+    void permute_end();
 
     // --- read-back of the device form, for the tests that hold every table to its definition ------
     // Read only, used by no product path: sizes, switches and buffer addresses (to compare, never to follow) by name, and

@@ -109,6 +109,8 @@ struct StreamSignal {
     }
 };
 
+struct PermuteState;  // permute.inc: what a permutation-importance call keeps on the device between its chunks
+
 struct DeviceDataset::Impl : DatasetDesc {
     // resident base sums / error bounds shared by the bound-and-verify paths (defined further down)
     // Per-tick parameters of the bound-and-verify paths travel as ONE page-locked block and one copy (the redo
@@ -417,6 +419,7 @@ struct DeviceDataset::Impl : DatasetDesc {
     bool sums_only = false;  // reductions over queries return sums instead of means
     size_t last_ldm = 0, last_cols = 0;
     int host_flags = 0;
+    std::shared_ptr<PermuteState> permute;
     std::mutex mu;
 
     bool bind(std::string* err) {
@@ -1057,20 +1060,12 @@ bool DeviceDataset::try_score_trees_rank(const FlatTrees& t, std::string* err) {
     return true;
 }
 
-bool DeviceDataset::score_trees(const FlatTrees& t, std::string* err) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    if (!m.scores.ensure(m.np, err)) return false;
-    m.scores_slots = 1;
-    if (try_score_trees_rank(t, err)) return true;
-    if (err && !err->empty()) return false;
-    if (try_score_trees_lds(t, err)) return true;
-    if (err && !err->empty()) return false;
+// The forest re-laid so that the two children of a node are adjacent (rhs = lhs + 1): what tree_ensemble_kernel and
+// permute_trees_kernel walk.  A tree's nodes are contiguous, from roots[k] to the next tree's root.
+static void adjacent_children_layout(const FlatTrees& t, std::vector<TreeNodeDev>& nodes, std::vector<int32_t>& roots) {
     const size_t nt = t.root.size();
-    // re-lay the forest out so that the two children of a node are adjacent (rhs = lhs + 1)
-    std::vector<TreeNodeDev> nodes;
-    std::vector<int32_t> roots(nt);
+    nodes.clear();
+    roots.assign(nt, 0);
     nodes.reserve(t.fid.size() + nt);
     {
         std::vector<std::pair<int32_t, int32_t>> work;  // (source node, destination slot)
@@ -1095,6 +1090,22 @@ bool DeviceDataset::score_trees(const FlatTrees& t, std::string* err) {
             }
         }
     }
+}
+
+bool DeviceDataset::score_trees(const FlatTrees& t, std::string* err) {
+    Impl& m = *impl_;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.bind(err)) return false;
+    if (!m.scores.ensure(m.np, err)) return false;
+    m.scores_slots = 1;
+    if (try_score_trees_rank(t, err)) return true;
+    if (err && !err->empty()) return false;
+    if (try_score_trees_lds(t, err)) return true;
+    if (err && !err->empty()) return false;
+    const size_t nt = t.root.size();
+    std::vector<TreeNodeDev> nodes;
+    std::vector<int32_t> roots;
+    adjacent_children_layout(t, nodes, roots);
     const size_t nn = nodes.size();
     if (!m.nodes.ensure(std::max<size_t>(nn, 1), err) || !m.roots.ensure(std::max<size_t>(nt, 1), err) ||
         !m.tweights.ensure(std::max<size_t>(nt, 1), err))

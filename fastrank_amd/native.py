@@ -127,6 +127,40 @@ def resample(V, trials: int, seed: int, alpha: float = 0.05, boot: bool = True, 
     return rep, out_b, out_p
 
 
+def permutation_importance_dense(model: CModel, dataset: CDataset, evaluator: str, qrel: Optional[CQRel] = None, repeats: int = 5, seed: int = 0,
+                                 scope: str = "dataset", features=None, skip_unused: bool = True, max_slots: Optional[int] = None,
+                                 per_query: bool = True) -> Tuple[Dict, np.ndarray, Optional[np.ndarray]]:
+    """fr_permutation_importance (include/fastrank.h).  features: ids (default: all of the view's, ascending).
+    Returns (report, values, per_query): values[F, R] = the mean of `evaluator` with feature f permuted in repeat r; per_query
+    [F * R + 1, nq] in evaluate_dense's query order, row f * R + r behind values[f, r], the last row the baseline's (None when
+    per_query is False)."""
+    options = {"repeats": int(repeats), "seed": int(seed), "scope": scope, "skip_unused": bool(skip_unused)}
+    if features is not None:
+        options["features"] = [int(f) for f in features]
+    if max_slots is not None:
+        options["max_slots"] = int(max_slots)
+    F = len(options["features"]) if features is not None else len(dataset.feature_ids())
+    R = int(repeats) if 0 < int(repeats) <= 64 else 0  # (out of range: refused by the call before it writes)
+    nq = num_queries(dataset) if per_query and R else 0
+    values = np.zeros((F, R), dtype=np.float64)
+    rows = np.zeros((F * R + 1, nq), dtype=np.float64) if per_query and R else None
+    rep = _json_reply(_load().fr_permutation_importance(model.pointer, dataset.pointer, None if qrel is None else qrel.pointer, evaluator.encode("utf-8"),
+                                                        json.dumps(options).encode("utf-8"), values.ctypes.data if values.size else None, values.size,
+                                                        rows.ctypes.data if rows is not None and rows.size else None))
+    return rep, values, rows
+
+
+def permutation_sources(dataset: CDataset, seed: int, repeat: int, scope: str = "dataset", n_total: Optional[int] = None) -> np.ndarray:
+    """fr_debug_permutation_sources: uint32[n_total] by instance id, the instance whose value of a permuted feature each
+    instance reads in repeat `repeat` (0xFFFFFFFF: not in the view).  Needs no device."""
+    if n_total is None:
+        held = [int(i) for ids in dataset.instances_by_query().values() for i in ids]
+        n_total = max(held) + 1 if held else 0
+    out = np.zeros(max(1, n_total), dtype=np.uint32)
+    _json_reply(_load().fr_debug_permutation_sources(dataset.pointer, int(seed), int(repeat), scope.encode("utf-8"), out.ctypes.data, n_total))
+    return out[:n_total]
+
+
 def lambdamart_sample(dataset: CDataset, params, tree: int) -> Tuple[np.ndarray, np.ndarray]:
     """The sample LambdaMART's trainer uses for tree `tree` of `params` (LambdaMARTParams or its wire dict) on `dataset`:
     (feature ids ascending, indices of the view's queries ascending).  Needs no device."""

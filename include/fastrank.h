@@ -554,6 +554,32 @@ const void *fr_resample(const double *values, size_t nq, size_t ncols, const voi
 const void *fr_compare_models(const CModel *const *models, size_t n_models, const CDataset *dataset, const CQRel *qrel_or_null,
                               const void *evaluator_name, const void *options_json);
 
+/* ---- Permutation importance: any model, any measure (the definition: csrc/permute.hpp) ----
+ * fr_permutation_importance: how far the mean of `evaluator_name` over the queries of `dataset` (a dataset or any view) falls
+ * when one feature column is read from other rows.  options_json, each key optional, any other refused by name: {"repeats":
+ * 1..64 (5), "seed": u64 (0), "scope": "dataset" | "query" ("dataset": rows move across the whole view; "query": inside their
+ * query), "features": [ids of the view's features, none twice] (all of them, ascending), "skip_unused": bool (true: a feature
+ * the model cannot read -- no tree splits on it, a SingleFeature's other features, a Linear weight that is exactly 0 on a
+ * finite column -- is never launched for; its values are the baseline, its importance and std 0.0), "max_slots": >= 1 (from
+ * free memory; score slots per launch, never under one feature's repeats)}.  One permutation per (seed, repeat) is shared by
+ * all features.  Models: Linear, SingleFeature, DecisionTree, an Ensemble of DecisionTrees, an Ensemble of Linear /
+ * SingleFeature members; any other shape is refused by name.  Refused before the device is touched: bad options, a feature
+ * the view does not hold or lists twice, an empty view, the model's shape; out_len < F * R.
+ * out_values[f * R + r] (F = the features in the order asked for): the mean on the dataset with feature f permuted in repeat
+ * r.  out_per_query_or_null: (F * R + 1) rows of nq values in the device's query order (fr_evaluate_dense's), row f * R + r
+ * the per-query values behind out_values[f * R + r], the last row the baseline's.
+ * Returns JSON: {"features": [ids], "names": [..], "baseline", "importance": [..], "std": [..], "skipped": [ids],
+ * "repeats", "seed", "scope", "evaluator", "queries", "stats": {"gather": "xcol" | "tiles", "rows": "lds" | "global", "chunks", "slots", "score_ms",
+ * "metric_ms", "upload_ms", "baseline_ms", "sources_ms", "launches": {"linear", "single", "trees", "axpy"}}}, or an error
+ * envelope (a bad evaluator name: fr_evaluate_dense's texts; a NaN score: `Model.predict -> NaN`).
+ * fr_debug_permutation_sources: host only, works with no device.  out_src_by_instance[id] = the instance whose value instance
+ * id reads in repeat `repeat` under `scope`, 0xFFFFFFFF for ids the view does not hold; out_len > the view's largest id.
+ * Returns {"n": the view's instances}. */
+const void *fr_permutation_importance(const CModel *model, const CDataset *dataset, const CQRel *qrel_or_null, const void *evaluator_name,
+                                      const void *options_json, double *out_values, size_t out_len, double *out_per_query_or_null);
+const void *fr_debug_permutation_sources(const CDataset *dataset, uint64_t seed, uint32_t repeat, const void *scope,
+                                         uint32_t *out_src_by_instance, size_t out_len);
+
 #ifdef __cplusplus
 }
 #endif
