@@ -3,7 +3,7 @@
 Same names as the reference package (fastrank/__init__.py:2-7): CQRel, CDataset, CModel,
 query_json, TrainRequest.  All computation happens in libfastrank_amd.so (HIP, gfx950).
 """
-from .clib import CDataset, CModel, CQRel, Normalizer, query_json
+from .clib import CDataset, CModel, CQRel, Normalizer, measures, query_json
 from .compare import compare_models
 from .importance import permutation_importance
 from .training import CoordinateAscentParams, LambdaMARTParams, RandomForestParams, TrainRequest
@@ -11,5 +11,5 @@ from .training import CoordinateAscentParams, LambdaMARTParams, RandomForestPara
 VERSION_TUPLE = (0, 7, 0)
 __version__ = "{}.{}.{}".format(*VERSION_TUPLE)
 
-__all__ = ["clib", "training", "native", "CQRel", "CDataset", "CModel", "Normalizer", "query_json", "compare_models", "permutation_importance", "TrainRequest",
+__all__ = ["clib", "training", "native", "CQRel", "CDataset", "CModel", "Normalizer", "query_json", "measures", "compare_models", "permutation_importance", "TrainRequest",
            "CoordinateAscentParams", "RandomForestParams", "LambdaMARTParams"]

@@ -91,6 +91,9 @@ def _load():
         "fr_ca_capture_take": (vp, [vp, C.c_char_p, vp, sz]),
         "fr_last_train_stats": (vp, []),
         "fr_debug_tree_plan": (vp, []),
+        "fr_debug_metric_plan": (vp, []),
+        "fr_debug_measure_ranked": (vp, [C.c_char_p, vp, sz, C.c_double, vp]),
+        "fr_debug_metric_topk_pays": (C.c_int, [C.c_int64, C.c_uint32]),
         "fr_predict_scores_dense": (vp, [vp, vp, vp, sz]),
         "fr_explain_dense": (vp, [vp, vp, vp, vp, sz, sz]),
         "fr_feature_importance": (vp, [vp, vp, vp, vp, sz]),
@@ -598,5 +601,11 @@ class Normalizer:
 
 
 def query_json(message: str):
-    """Global JSON query: 'coordinate_ascent_defaults' | 'random_forest_defaults'."""
+    """Global JSON query: 'coordinate_ascent_defaults' | 'random_forest_defaults' | 'lambdamart_defaults' | 'measures'."""
     return _json_reply(_load().query_json(message.encode("utf-8")))
+
+
+def measures():
+    """The evaluators every call takes by name: [{"name", "aliases", "display", "cutoff": "optional" | "required" | "ignored"}, ...]
+    ("precision@10": name@k; names are matched without regard to case)."""
+    return query_json("measures")

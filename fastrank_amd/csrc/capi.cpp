@@ -968,6 +968,21 @@ const void* query_json(const void* json_cmd_str) {
             o.set("judgments", Value::null());
             return frjson::dump(o);
         }
+        if (cmd == "measures") {  // the evaluators every call takes by name (measures_host.hpp)
+            Value a = Value::array();
+            const frmeasure::MeasureInfo* t = frmeasure::measure_table();
+            for (int i = 0; i < frmeasure::MEASURE_COUNT; i++) {
+                Value o = Value::object();
+                o.set("name", Value::string(t[i].names[0]));
+                Value al = Value::array();
+                if (t[i].names[1] != nullptr) al.push(Value::string(t[i].names[1]));
+                o.set("aliases", std::move(al));
+                o.set("display", Value::string(t[i].display));
+                o.set("cutoff", Value::string(frmeasure::cutoff_name(t[i].cutoff)));
+                a.push(std::move(o));
+            }
+            return frjson::dump(a);
+        }
         return frjson::dump(unknown_cmd("unknown_query_str", cmd));
     });
 }
@@ -1717,6 +1732,54 @@ const void* fr_debug_tree_plan(void) {
         return frjson::dump(o);
     });
 }
+
+const void* fr_debug_metric_plan(void) {
+    return json_call([&]() {
+        const frdev::MetricPlan p = frdev::last_metric_plan();
+        Value o = Value::object();
+        if (p.measure < 0) {
+            o.set("measure", Value::null());
+            return frjson::dump(o);
+        }
+        o.set("measure", Value::string(frmeasure::measure_table()[p.measure].names[0]));
+        o.set("depth", p.depth < 0 ? Value::null() : Value::uint((uint64_t)p.depth));
+        o.set("slots", Value::uint(p.slots));
+        Value a = Value::array();
+        for (const auto& c : p.classes) {
+            Value e = Value::object();
+            e.set("npad", Value::uint(c.npad)), e.set("queries", Value::uint(c.queries));
+            e.set("kernel", Value::string(c.topk ? "topk" : "sort"));
+            a.push(std::move(e));
+        }
+        o.set("classes", std::move(a));
+        return frjson::dump(o);
+    });
+}
+
+// measures_host.hpp's scalar form of one of the five cut-off measures over a RANKED list of n gains (no device): what the
+// kernels are held to.  measure: the evaluator's name; norm: the query's entry of the norms (measures_host.hpp lists them).
+const void* fr_debug_measure_ranked(const void* evaluator, const float* gains, size_t n, double norm, double* out) {
+    return status_call([&]() {
+        std::string name = accept_str("evaluator_name", evaluator);
+        if ((n && !gains) || !out) fr::fail_str("NULL pointer: ranked gains");
+        int64_t depth = -1;
+        const size_t at = name.find('@');
+        if (at != std::string::npos) {
+            depth = (int64_t)std::strtoull(name.c_str() + at + 1, nullptr, 10);
+            name.resize(at);
+        }
+        for (auto& ch : name) ch = (char)std::tolower((unsigned char)ch);
+        frmeasure::Resolved res;
+        std::string rule;
+        if (!frmeasure::resolve(name, depth, &res, &rule) || !frmeasure::is_cut_measure(res.measure))
+            fr::fail_str(rule.empty() ? "fr_debug_measure_ranked: not one of dcg, precision, recall, success, err: \"" + name + "\"" : rule);
+        std::vector<double> gexp(n);
+        for (size_t i = 0; i < n; i++) gexp[i] = std::pow(2.0, (double)gains[i]) - 1.0;
+        *out = frmeasure::cut_measure_at(res.measure, gains, gexp.data(), n, depth, norm);
+    });
+}
+
+int fr_debug_metric_topk_pays(int64_t depth, uint32_t npad) { return frmeasure::metric_topk_pays(depth, npad) ? 1 : 0; }
 
 const void* fr_predict_scores_dense(const CModel* model, const CDataset* dataset, double* out, size_t out_len) {
     return status_call([&]() {
@@ -3058,11 +3121,16 @@ const void* fr_evaluate_candidates(const CDataset* dataset, const CQRel* qrel, c
                     w[off + features[g]] = candidates[g * 64 + c];
                     slot.push_back(g * 64 + c);
                 }
-            if (out_per_query) fr::fail_str("fr_evaluate_candidates: per-query output is not available on the general sort path");
-            std::vector<double> means;
-            fr::evaluate_means_generic(view.device(), ev, w, slot.size(), means);
+            std::vector<double> means, pq;
+            fr::evaluate_means_generic(view.device(), ev, w, slot.size(), means, out_per_query ? &pq : nullptr);
             for (size_t g = 0; g < n_groups * 64; g++) out_means[g] = 0.0;
             for (size_t k = 0; k < slot.size(); k++) out_means[slot[k]] = means[k];
+            if (out_per_query) {  // [nq][n_groups * 64] as the fused paths give it; slots no candidate fills hold 0
+                const size_t ld = n_groups * 64, B = slot.size();
+                std::fill(out_per_query, out_per_query + dev.nq() * ld, 0.0);
+                for (size_t q = 0; q < dev.nq(); q++)
+                    for (size_t k = 0; k < B; k++) out_per_query[q * ld + slot[k]] = pq[q * B + k];
+            }
         }
     });
 }

@@ -11,7 +11,9 @@
 //   kernels_treerank.inc    tree_ensemble_rank_kernel (threshold ranks instead of features: u16 codes, 32-bit heap nodes)
 //                           and tree_ensemble_kernel (L2 fallback)
 //   kernels_metric.inc      metric_sort_kernel (LDS bitonic sort + NDCG/AP/RR in the reference's
-//                           summation order) and the fixed-shape mean reduction
+//                           summation order, and DCG / precision / recall / success / ERR) and the fixed-shape mean reduction
+//   kernels_metric_topk.inc metric_topk_kernel: the five cut-off measures by selecting the first k ranks, one wave per
+//                           (query, slot), no sort (measures_host.hpp: names, norms, definitions, the routing rule; host only)
 //   kernels_linesearch.inc  linesearch_ndcg_kernel: the exact fused NDCG@k line search
 //   kernels_verify.inc      linesearch_verify_kernel: bound-and-verify NDCG@k line search (the hot path; the exact
 //                           kernel recomputes the pairs it cannot verify)
@@ -61,6 +63,7 @@
 
 #include "fullverify.hpp"
 #include "linesearch_policy.hpp"
+#include "measures_host.hpp"
 #include "verify_end.hpp"
 #define FR_QUANT_ARITHMETIC_ONLY  // (lambdamart_quant.hpp without host.hpp: the integer arithmetic the kernels share with the host)
 #include "lambdamart_quant.hpp"
@@ -84,6 +87,7 @@
 #include <map>
 #include <condition_variable>
 #include <mutex>
+#include <optional>
 #include <thread>
 #include <type_traits>
 
@@ -94,6 +98,7 @@ namespace frdev {
 #include "kernels_tree.inc"
 #include "kernels_treerank.inc"
 #include "kernels_metric.inc"
+#include "kernels_metric_topk.inc"
 #include "kernels_linesearch.inc"
 #include "kernels_chain.inc"
 #include "kernels_order.inc"

@@ -43,7 +43,8 @@ inline const char* pricing_env(const char* name) {
 #endif
 }
 
-enum Measure : int { M_NDCG = 0, M_AP = 1, M_RR = 2 };
+// (0..2 are LambdaMART's objectives too, kernels_lambda.inc; the five after them are defined in measures_host.hpp)
+enum Measure : int { M_NDCG = 0, M_AP = 1, M_RR = 2, M_DCG = 3, M_PRECISION = 4, M_RECALL = 5, M_SUCCESS = 6, M_ERR = 7 };
 // LambdaMART's objectives are spelled as their measures; the listwise objective "xendcg" has no measure of its own
 constexpr int LM_OBJECTIVE_XENDCG = 3;
 
@@ -88,6 +89,20 @@ struct TreePlan {
     std::vector<std::pair<uint32_t, uint32_t>> batches;  // RANK, LDS: (walks per thread, levels) of every batch
 };
 TreePlan last_tree_plan();
+
+// What the process's last DeviceDataset::metric_from_scores call launched (fr_debug_metric_plan): the
+// kernel that took each size class.  Host bookkeeping alone.
+struct MetricPlan {
+    struct Class {
+        uint32_t npad = 0, queries = 0;
+        bool topk = false;  // metric_topk_kernel; else metric_sort_kernel
+    };
+    int measure = -1;  // -1: no call yet
+    int64_t depth = -1;
+    size_t slots = 0;
+    std::vector<Class> classes;
+};
+MetricPlan last_metric_plan();
 
 // One line-search group: every candidate shares (feature f, base weights w) and differs only in
 // the weight of f (src/coordinate_ascent.rs:131-171).

@@ -1192,6 +1192,31 @@ bool DeviceDataset::download_scores(size_t b, double* out, size_t out_len, std::
     return true;
 }
 
+static std::mutex g_metric_plan_mu;
+static MetricPlan g_metric_plan;
+static void set_metric_plan(MetricPlan&& p) {
+    std::lock_guard<std::mutex> lk(g_metric_plan_mu);
+    g_metric_plan = std::move(p);
+}
+MetricPlan last_metric_plan() {
+    std::lock_guard<std::mutex> lk(g_metric_plan_mu);
+    return g_metric_plan;
+}
+
+// the profile's name of one size class's launch: "metric_sort_npad<N>" / "metric_topk_npad<N>" (tools/metricbench.py prices
+// the two kernels class by class with these); the names live as long as the process, as ProfScope needs
+static const char* metric_class_scope(uint32_t npad, bool topk) {
+    static const std::vector<std::string> names = [] {
+        std::vector<std::string> v;
+        for (int k = 0; k < 2; k++)
+            for (uint32_t lg = 0; lg < 32; lg++) v.push_back(std::string(k ? "metric_topk_npad" : "metric_sort_npad") + std::to_string(1u << lg));
+        return v;
+    }();
+    uint32_t lg = 0;
+    while (lg < 31 && (1u << lg) < npad) lg++;
+    return names[(topk ? 32 : 0) + lg].c_str();
+}
+
 bool DeviceDataset::metric_from_scores(int measure, int64_t depth, const double* norms, size_t B, bool want_rank,
                                        std::string* err) {
     Impl& m = *impl_;
@@ -1215,9 +1240,31 @@ bool DeviceDataset::metric_from_scores(int measure, int64_t depth, const double*
     FR_HIP(hipFuncSetAttribute((const void*)metric_sort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)lds));
     int dd = depth < 0 ? -1 : (depth > 0x7fffffff ? 0x7fffffff : (int)depth);
+    // The five cut-off measures at a depth of 1 .. 64 may select instead of sorting (kernels_metric_topk.inc), a size class at
+    // a time where measures_host.hpp's rule says it pays; FR_METRIC_KERNEL=sort|topk forces one kernel wherever it is legal.
+    const bool topk_legal = frmeasure::metric_topk_legal(measure, depth, want_rank);
+    const char* force = frdev::path_env("FR_METRIC_KERNEL");
+    const bool force_sort = force != nullptr && std::strcmp(force, "sort") == 0;
+    const bool force_topk = force != nullptr && std::strcmp(force, "topk") == 0;
+    MetricPlan plan;
+    plan.measure = measure, plan.depth = depth, plan.slots = B;
     {
         ProfScope ps("metric_sort_kernel", m.stream);
         for (const auto& sc : m.size_classes) {
+            const bool topk = topk_legal && !force_sort && (force_topk || frmeasure::metric_topk_pays(depth, sc.npad));
+            MetricPlan::Class pc;
+            pc.npad = sc.npad, pc.queries = (uint32_t)sc.count, pc.topk = topk;
+            plan.classes.push_back(pc);
+            std::optional<ProfScope> pcs;  // (NDCG, AP and RR are profiled exactly as before: the outer scope alone)
+            if (frmeasure::is_cut_measure(measure)) pcs.emplace(metric_class_scope(sc.npad, topk), m.stream);
+            if (topk) {
+                dim3 grid((unsigned)((sc.count + TOPK_WAVES - 1) / TOPK_WAVES), (unsigned)B);
+                metric_topk_kernel<<<grid, 64 * TOPK_WAVES, 0, m.stream>>>(m.scores.p, (uint32_t)m.np, m.qstart.p, m.qlen.p, m.gexp.p,
+                                                                          m.gain.p, m.disc.p, m.norms.p, measure, (uint32_t)dd,
+                                                                          (uint32_t)B, m.M.p, m.flags.p, m.qlist.p + sc.offset,
+                                                                          (uint32_t)sc.count);
+                continue;
+            }
             const size_t cls_lds = (size_t)sc.npad * (sizeof(double) + sizeof(uint32_t));
             unsigned bs = sc.npad >= 512 ? 256 : 64;
             if (cls_lds <= lds_limit) {
@@ -1244,6 +1291,7 @@ bool DeviceDataset::metric_from_scores(int measure, int64_t depth, const double*
         }
     }
     FR_HIP(hipGetLastError());
+    set_metric_plan(std::move(plan));
     m.last_ldm = B;
     m.last_cols = B;
     m.last_M = m.M.p;

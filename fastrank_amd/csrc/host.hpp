@@ -23,6 +23,12 @@
 
 #include "device.hpp"
 #include "json.hpp"
+#include "measures_host.hpp"
+
+static_assert(frmeasure::NDCG == frdev::M_NDCG && frmeasure::AP == frdev::M_AP && frmeasure::RR == frdev::M_RR &&
+                  frmeasure::DCG == frdev::M_DCG && frmeasure::PRECISION == frdev::M_PRECISION && frmeasure::RECALL == frdev::M_RECALL &&
+                  frmeasure::SUCCESS == frdev::M_SUCCESS && frmeasure::ERR == frdev::M_ERR,
+              "measures_host.hpp numbers the measures as device.hpp does");
 
 namespace fr {
 
@@ -622,21 +628,26 @@ inline Evaluator make_evaluator(DatasetView& view, const std::string& orig_name,
         name = orig_name.substr(0, at);
     }
     for (auto& ch : name) ch = (char)std::tolower((unsigned char)ch);
-    if (name == "ap" || name == "map") {
-        ev.measure = frdev::M_AP;
-        ev.name = "AP";
-    } else if (name == "rr" || name == "mrr") {
-        ev.measure = frdev::M_RR;
-        ev.name = "RR";
-    } else if (name == "ndcg") {
-        ev.measure = frdev::M_NDCG;
-        ev.name = ev.depth >= 0 ? "NDCG@" + std::to_string(ev.depth) : "NDCG";
-    } else {
-        fail_str("Invalid training measure: \"" + orig_name + "\"");
-    }
+    // names, aliases and cut-off rules: measures_host.hpp
+    frmeasure::Resolved res;
+    std::string rule;
+    if (!frmeasure::resolve(name, ev.depth, &res, &rule)) fail_str(rule.empty() ? "Invalid training measure: \"" + orig_name + "\"" : rule);
+    ev.measure = res.measure;
+    ev.name = res.display;
     const frdev::HostCSR& csr = view.host_csr();
     const DataCore& c = *view.core;
     ev.norms.assign(csr.nq, 0.0);
+    if (ev.measure == frdev::M_PRECISION) ev.norms.assign(csr.nq, (double)ev.depth);
+    if (ev.measure == frdev::M_ERR) {
+        // den = 2^gmax over the CORE's gains, not the view's: a query-sampled view gives its parent's per-query values
+        float gmax = frmeasure::gmax_of(c.gain.data(), c.gain.size());
+        if (qrel)
+            for (const auto& qd : qrel->queries)
+                for (const auto& dg : qd.second) gmax = frmeasure::gmax_of(&dg.second, 1, gmax);
+        double den = 1.0;
+        if (!frmeasure::err_den(gmax, &den, &rule)) fail_str(rule);
+        ev.norms.assign(csr.nq, den);
+    }
     for (size_t q = 0; q < csr.nq; q++) {
         const std::string& qid = c.qnames[view.csr_query[q]];
         const std::vector<std::pair<std::string, float>>* judged = qrel ? qrel->get(qid) : nullptr;
@@ -653,7 +664,7 @@ inline Evaluator make_evaluator(DatasetView& view, const std::string& orig_name,
             size_t pos = 0;
             for (float g : gains) pos += g > 0.0f;
             ev.norms[q] = pos == 0 ? std::nan("") : ideal_dcg_sorted_desc(gains, ev.depth);
-        } else if (ev.measure == frdev::M_AP) {
+        } else if (ev.measure == frdev::M_AP || ev.measure == frdev::M_RECALL) {
             uint32_t nr = 0;
             if (judged) {
                 for (const auto& dg : *judged) nr += dg.second > 0.0f;
@@ -918,10 +929,13 @@ inline void line_candidates(double orig, const CAParams& p, std::vector<double>&
 }
 
 // Batched evaluate_mean of arbitrary weight vectors through the general sort path.
+// per_query (optional): the values themselves, [nq][B] in the device's query order.
 inline void evaluate_means_generic(frdev::DeviceDataset& dev, const Evaluator& ev, const std::vector<double>& weights,
-                                   size_t B, std::vector<double>& means) {
+                                   size_t B, std::vector<double>& means, std::vector<double>* per_query = nullptr) {
     const size_t d = dev.d();
     means.assign(B, 0.0);
+    if (per_query) per_query->assign(dev.nq() * B, 0.0);
+    std::vector<double> rows;
     // bound the score scratch to ~2 GiB
     size_t ld = (dev.n() + 63) / 64 * 64;
     size_t chunk = std::max<size_t>(1, std::min<size_t>(512, (size_t(2) << 30) / (ld * sizeof(double))));
@@ -932,6 +946,11 @@ inline void evaluate_means_generic(frdev::DeviceDataset& dev, const Evaluator& e
         if (!dev.metric_from_scores(ev.measure, ev.depth, ev.norms.data(), bn, false, &_err)) fail_str(_err);
         if (!dev.reduce_means(bn, means.data() + b0, &_err)) fail_str(_err);
         check_flags(dev);
+        if (per_query) {
+            rows.resize(dev.nq() * bn);
+            if (!dev.download_per_query(bn, rows.data(), &_err)) fail_str(_err);
+            for (size_t q = 0; q < dev.nq(); q++) std::copy(rows.begin() + q * bn, rows.begin() + (q + 1) * bn, per_query->begin() + q * B + b0);
+        }
     }
 }
 

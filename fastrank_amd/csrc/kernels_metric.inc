@@ -9,7 +9,9 @@ __device__ __forceinline__ bool key_before(double sa, uint32_t ia, double sb, ui
     return ia > ib;
 }
 
-// General evaluator for one (query, score slot): bitonic sort + metric.
+// General evaluator for one (query, score slot): bitonic sort + metric (NDCG, AP, RR in the reference's summation order; DCG,
+// precision, recall, success and ERR as measures_host.hpp defines them -- at a cut-off of 1 .. 64 metric_topk_kernel,
+// kernels_metric_topk.inc, gives the same bytes without the sort).
 // dynamic LDS: double keys[npad]; uint32 idx[npad]; (npad = pow2 >= longest query of the size class).
 // Queries too long for LDS (> 8192 documents) sort in a global scratch slab instead (gkeys/gidx,
 // one slab of npad_max entries per block): same code, one block per query, __syncthreads() orders
@@ -87,6 +89,44 @@ __global__ __launch_bounds__(256) void metric_sort_kernel(
                 result = dcg / norm;
             }
         }
+    } else if (measure >= M_DCG) {
+        // the five measures of measures_host.hpp, its operands in its order
+        const uint32_t L = depth >= 0 ? ((uint32_t)depth < n ? (uint32_t)depth : n) : n;
+        const double norm = norms[q];
+        if (measure == M_DCG) {
+            for (uint32_t i = tid; i < L; i += nt) keys[i] = gexp[base + idx[i]] / disc[i];
+        } else if (measure == M_ERR) {
+            for (uint32_t i = tid; i < L; i += nt) keys[i] = gain[base + idx[i]] > 0.0f ? gexp[base + idx[i]] / norm : 0.0;
+        } else {
+            // (recall's fallback counts the whole list)
+            for (uint32_t i = tid; i < n; i += nt) keys[i] = gain[base + idx[i]] > 0.0f ? 1.0 : 0.0;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            if (measure == M_DCG) {
+                for (uint32_t i = 0; i < L; i++) result = result + keys[i];
+            } else if (measure == M_ERR) {
+                double p = 1.0;
+                for (uint32_t i = 0; i < L; i++) {
+                    const double R = keys[i];
+                    result = result + (p * R) / (double)(i + 1);
+                    p = p * (1.0 - R);
+                }
+            } else {
+                uint32_t c = 0;
+                for (uint32_t i = 0; i < L; i++) c += keys[i] != 0.0;
+                if (measure == M_PRECISION) {
+                    result = (double)c / norm;
+                } else if (measure == M_SUCCESS) {
+                    result = c != 0 ? 1.0 : 0.0;
+                } else {
+                    uint32_t num_rel = (uint32_t)norm;
+                    if (num_rel == 0)
+                        for (uint32_t i = 0; i < n; i++) num_rel += keys[i] != 0.0;
+                    if (num_rel != 0) result = (double)c / (double)num_rel;
+                }
+            }
+        }
     } else {
         // relevance flags in rank order (src/evaluators.rs:94-96 is_relevant: gain > 0)
         for (uint32_t i = tid; i < n; i += nt) keys[i] = gain[base + idx[i]] > 0.0f ? 1.0 : 0.0;
@@ -99,7 +139,7 @@ __global__ __launch_bounds__(256) void metric_sort_kernel(
                     c += keys[i] != 0.0;
                     idx[i] = keys[i] != 0.0 ? c : 0u;
                 }
-            } else {
+            } else if (measure == M_RR) {
                 // src/evaluators.rs:239-252
                 for (uint32_t i = 0; i < n; i++) {
                     if (keys[i] != 0.0) {

@@ -589,6 +589,28 @@ def last_tree_plan() -> Dict:
     return _json_reply(_load().fr_debug_tree_plan())
 
 
+def last_metric_plan() -> Dict:
+    """What the last general metric pass of this process launched (fr_debug_metric_plan): {"measure", "depth", "slots",
+    "classes": [{"npad", "queries", "kernel": "sort" | "topk"}, ...]}; {"measure": None} before the first one."""
+    return _json_reply(_load().fr_debug_metric_plan())
+
+
+def measure_ranked(evaluator: str, gains, norm: float = 0.0) -> float:
+    """The library's scalar definition (csrc/measures_host.hpp) of dcg[@k], precision@k, recall[@k], success@k or err[@k] over a
+    ranked list of gains, on the host; norm: precision: k, recall: the number of relevant documents (0: the list's own), err:
+    2^(largest gain)."""
+    g = np.ascontiguousarray(gains, dtype=np.float32)
+    out = np.zeros(1, dtype=np.float64)
+    _status(_load().fr_debug_measure_ranked(evaluator.encode("utf-8"), g.ctypes.data, len(g), float(norm), out.ctypes.data))
+    return float(out[0])
+
+
+def metric_topk_pays(depth: int, npad: int) -> bool:
+    """The routing rule of the general metric pass: does a size class of npad documents go to the selection kernel at this
+    cut-off?"""
+    return bool(_load().fr_debug_metric_topk_pays(int(depth), int(npad)))
+
+
 def train_model_shard(dataset: CDataset, train_req, restart_begin: int, restart_end: int) -> Dict:
     """Train restarts [begin, end) of the request on this process's GPU."""
     request = json.dumps(train_req.to_dict()).encode("utf-8")

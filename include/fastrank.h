@@ -193,6 +193,19 @@ const void *fr_last_train_stats(void);
  * the buffers the call before left; lds: "docs", "parts" (the block shape); l2: "rows_in_lds"; rank: "nslots" (features in
  * use), "nrounds"; rank and lds: "batches": [[walks per thread, levels], ...]}. */
 const void *fr_debug_tree_plan(void);
+/* What the process's last general metric pass launched, a test hook; JSON (free_str), host
+ * bookkeeping alone: {"measure": the measure's first name (null before the first call), "depth": the cut-off or null,
+ * "slots": score slots evaluated at once, "classes": [{"npad": the size class, "queries", "kernel": "sort" | "topk"}, ...]}.
+ * "topk" is the selection kernel, which only dcg, precision, recall, success and err at a cut-off of 1 .. 64 can take;
+ * FR_METRIC_KERNEL=sort|topk in the environment forces one kernel wherever it is legal (same results). */
+const void *fr_debug_metric_plan(void);
+/* The scalar definition (csrc/measures_host.hpp) of dcg[@k], precision@k, recall[@k], success@k or err[@k] over a RANKED list
+ * of n gains, on the host: *out = the value.  norm: what the query's norm would be -- precision: k; recall: the number of
+ * relevant documents (0: the list's own); err: 2^(largest gain); else unused.  Returns NULL, or an error text (free_str). */
+const void *fr_debug_measure_ranked(const void *evaluator, const float *gains, size_t n, double norm, double *out);
+/* 1 if the general metric pass gives a size class of npad documents (a power of two >= 64) to the selection kernel at this
+ * cut-off when nothing forces a kernel, else 0. */
+int fr_debug_metric_topk_pays(int64_t depth, uint32_t npad);
 
 /* Dense results without JSON.  out[i] = score of instance i (instances outside the dataset
  * view are left untouched).  Returns NULL on success or an error-envelope string. */
