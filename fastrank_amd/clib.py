@@ -91,6 +91,7 @@ def _load():
         "fr_ca_capture_take": (vp, [vp, C.c_char_p, vp, sz]),
         "fr_last_train_stats": (vp, []),
         "fr_debug_tree_plan": (vp, []),
+        "fr_debug_forest_pack": (vp, [vp, C.c_uint32, C.c_char_p, C.c_char_p, vp, sz]),
         "fr_debug_metric_plan": (vp, []),
         "fr_debug_measure_ranked": (vp, [C.c_char_p, vp, sz, C.c_double, vp]),
         "fr_debug_metric_topk_pays": (C.c_int, [C.c_int64, C.c_uint32]),

@@ -15,6 +15,7 @@
 #include "normalize_host.hpp"
 #include "resample_host.hpp"
 #include "permute_host.hpp"
+#include "forest_pack.hpp"
 #include "lambdamart.hpp"
 #include "rf_train.hpp"
 #include "verify_end.hpp"
@@ -1728,6 +1729,84 @@ const void* fr_debug_tree_plan(void) {
                 a.push(std::move(pair));
             }
             o.set("batches", std::move(a));
+        }
+        return frjson::dump(o);
+    });
+}
+
+// `model`'s forest packed for one of the three encodings (csrc/forest_pack.hpp) on a dataset of dataset_features features,
+// with the packers' options unset: what score_trees would upload.  No device is touched.  The name / out-buffer protocol of
+// fr_debug_device_form.
+const void* fr_debug_forest_pack(const CModel* model, uint32_t dataset_features, const void* encoding, const void* table, void* out, size_t out_bytes) {
+    return json_call([&]() {
+        const CModel& m = require_model(model);
+        frdev::FlatTrees ft;
+        if (!fr::flat_trees_of(m.actual, &ft)) fr::fail_str("fr_debug_forest_pack: the model is neither a DecisionTree nor an Ensemble of DecisionTrees");
+        const std::string enc = accept_str("encoding", encoding);
+        const uint32_t d = dataset_features, dq = (d + 3) / 4;
+        std::vector<std::pair<std::string, std::pair<const void*, size_t>>> tables;  // name -> (bytes, count of bytes)
+        auto add = [&](const char* name, const auto& v) { tables.push_back({name, {v.data(), v.size() * sizeof(v[0])}}); };
+        frdev::RankForest rank;
+        frdev::LdsForest lds;
+        std::vector<frdev::TreeNodeDev> nodes;
+        std::vector<int32_t> roots;
+        std::vector<double> tweights;
+        Value o = Value::object();
+        bool admitted = true;
+        const std::vector<uint32_t>* desc = nullptr;
+        unsigned docs = 0, parts = 0;
+        if (enc == "rank") {
+            admitted = frdev::pack_forest_rank(ft, d, dq, frdev::ForestPackOptions(), &rank);
+            if (admitted) {
+                add("fdesc", rank.fdesc), add("tables", rank.tables), add("rdesc", rank.rdesc), add("forest", rank.forest);
+                add("desc", rank.desc), add("leafprod", rank.leafprod);
+                o.set("lds_bytes", Value::uint(rank.lds_bytes)), o.set("nslots", Value::uint(rank.nslots)), o.set("nrounds", Value::uint(rank.nrounds));
+                desc = &rank.desc;
+            }
+        } else if (std::sscanf(enc.c_str(), "lds:%u,%u", &docs, &parts) == 2) {
+            const frdev::TreeShape* shape = nullptr;
+            for (const frdev::TreeShape& sh : frdev::TREE_SHAPES)
+                if (sh.docs == docs && sh.parts == parts) shape = &sh;
+            if (!shape) fr::fail_str("fr_debug_forest_pack: no block shape " + enc.substr(4));
+            admitted = frdev::pack_forest_lds(ft, *shape, d, dq, frdev::ForestPackOptions(), &lds);
+            if (admitted) {
+                add("forest", lds.forest), add("desc", lds.desc), add("leafprod", lds.leafprod);
+                o.set("lds_bytes", Value::uint(lds.lds_bytes));
+                desc = &lds.desc;
+            }
+        } else if (enc == "l2") {
+            frdev::adjacent_children_layout(ft, nodes, roots);
+            tweights = ft.weight;
+            tweights.resize(ft.root.size(), 1.0);
+            add("nodes", nodes), add("roots", roots), add("tweights", tweights);
+        } else {
+            fr::fail_str("fr_debug_forest_pack: encoding is \"rank\", \"lds:DOCS,PARTS\" or \"l2\", not " + enc);
+        }
+        o.set("admitted", Value::boolean(admitted));
+        char hash[24];
+        snprintf(hash, sizeof hash, "%016llx", (unsigned long long)frdev::forest_hash(ft));
+        o.set("hash", Value::string(hash));  // the packed-forest cache's key, as hex
+        Value sizes = Value::object();
+        for (const auto& kv : tables) sizes.set(kv.first.c_str(), Value::uint(kv.second.second));
+        o.set("tables", std::move(sizes));
+        if (desc) {
+            Value a = Value::array();
+            for (const auto& b : frdev::tree_plan_batches(*desc)) {
+                Value pair = Value::array();
+                pair.push(Value::uint(b.first)), pair.push(Value::uint(b.second));
+                a.push(std::move(pair));
+            }
+            o.set("batches", std::move(a));
+        }
+        if (table) {
+            const std::string name = accept_str("table", table);
+            const std::pair<const void*, size_t>* found = nullptr;
+            for (const auto& kv : tables)
+                if (kv.first == name) found = &kv.second;
+            if (!found) fr::fail_str("fr_debug_forest_pack: encoding " + enc + (admitted ? " has no table " : " refused the forest: no table ") + name);
+            if (found->second && (!out || out_bytes != found->second))
+                fr::fail_str("fr_debug_forest_pack: table " + name + " holds " + std::to_string(found->second) + " bytes, the buffer " + std::to_string(out_bytes));
+            if (found->second) std::memcpy(out, found->first, found->second);
         }
         return frjson::dump(o);
     });

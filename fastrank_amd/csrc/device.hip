@@ -42,8 +42,13 @@
 //                           tables, duplicate groups, walk tiles, a view's tables
 //   linesearch_policy.hpp   (host only, no HIP) the adaptive policies of the bound-and-verify line search: routing / back-off of
 //                           tie-heavy restarts, the R-rank refresh schedule, list length, redo grid, skip counter
-//   device_dataset.inc      DeviceDataset: its state (Impl), the scoring, tree and metric launchers, the whole line search; includes
+//   forest_pack.hpp         (host only, no HIP) the three encodings of a forest the tree kernels read and their limits: the packers
+//                           for tree_ensemble_rank_kernel and tree_ensemble_lds_kernel (block shapes, try-orders), the adjacent-children
+//                           layout of the L2 walk and of permute_trees_kernel, the packed-forest cache's hash
+//   device_dataset.inc      DeviceDataset: its state (Impl), the scoring and metric launchers, the whole line search; includes
 //     dataset_build.inc       the uploads of that layout (tiles, tables): create, replicate, views
+//     score_trees.inc         forest scoring: the launchers of kernels_treerank.inc and kernels_tree.inc over forest_pack.hpp's buffers,
+//                             the packed-forest cache, the plan of the last call
 //     train_rf.inc            the launchers of kernels_rf.inc
 //     train_lambda.inc        the launchers of kernels_lambda.inc and kernels_xendcg.inc
 //     train_dart.inc          the launchers of kernels_dart.inc
@@ -61,6 +66,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include "forest_pack.hpp"
 #include "fullverify.hpp"
 #include "linesearch_policy.hpp"
 #include "measures_host.hpp"

@@ -76,6 +76,7 @@ struct FlatTrees {
     std::vector<double> weight;   // per tree (ignored when raw_single)
     bool raw_single = false;      // a bare DecisionTree model: output = leaf value
 };
+struct TreeShape;  // forest_pack.hpp: a block shape of the f32 LDS walk
 
 // What the process's last DeviceDataset::score_trees call ran (fr_debug_tree_plan): which of the three
 // encodings took the forest and in what shape.  Host bookkeeping alone: no timing, no launch of its own.
@@ -491,7 +492,7 @@ class DeviceDataset {
     DeviceDataset();
     bool try_score_trees_rank(const FlatTrees& trees, std::string* err);
     bool try_score_trees_lds(const FlatTrees& trees, std::string* err);
-    bool try_score_trees_lds_shape(const FlatTrees& trees, const void* shape, std::string* err);
+    bool try_score_trees_lds_shape(const FlatTrees& trees, const TreeShape& shape, std::string* err);
     struct Impl;
     Impl* impl_;
 };

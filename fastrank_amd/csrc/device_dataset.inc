@@ -1,7 +1,8 @@
-// Part of device.hip (single translation unit; see that file's header).  DeviceDataset: its state (Impl), the scoring, tree and metric
-// launchers and the line search.  The dataset build (dataset_build.inc) and the trainers' launchers (train_*.inc) are included at the
-// places their text had.  The scoring, tree-launch and line-search code stays in this file because bench.py keys its static counter
-// captures to this file's hash: moved out, it could change without marking those captures stale.
+// Part of device.hip (single translation unit; see that file's header).  DeviceDataset: its state (Impl), the scoring and metric
+// launchers and the line search.  The dataset build (dataset_build.inc), forest scoring (score_trees.inc) and the trainers' launchers
+// (train_*.inc) are included at the places their text had.  The scoring and line-search code stays in this file because bench.py
+// keys its static counter captures to this file's hash: moved out, it could change without marking those captures stale (the tree
+// captures are keyed to this file too: a change of score_trees.inc or forest_pack.hpp does not mark them).
 // ----------------------------------------------------------------------------------------------
 // DeviceDataset
 // ----------------------------------------------------------------------------------------------
@@ -411,10 +412,12 @@ struct DeviceDataset::Impl : DatasetDesc {
     // the forest last packed for tree_ensemble_rank_kernel (threshold tables, heap images, leaf products are a function of
     // the forest alone): scoring the same forest again -- evaluate after predict, a forest over several calls -- skips the
     // host's 3 ms of packing and the uploads.  Invalidated by any other use of the forest buffers.
-    uint64_t tree_rank_hash = 0;
-    uint32_t tree_rank_nrounds = 0, tree_rank_nslots = 0, tree_rank_nbatch = 0;
-    size_t tree_rank_lds = 0;
-    std::vector<std::pair<uint32_t, uint32_t>> tree_rank_batches;  // (walks per thread, levels), for the plan of a cache hit
+    struct RankKept {
+        uint64_t hash = 0;  // forest_hash of the kept forest; 0: none
+        uint32_t nrounds = 0, nslots = 0, nbatch = 0;
+        size_t lds = 0;
+        std::vector<std::pair<uint32_t, uint32_t>> batches;  // (walks per thread, levels), for the plan of a cache hit
+    } tree_rank;
     size_t scores_slots = 0;
     bool sums_only = false;  // reductions over queries return sums instead of means
     size_t last_ldm = 0, last_cols = 0;
@@ -579,567 +582,7 @@ bool DeviceDataset::score_single_feature(uint32_t fid, double dir, std::string* 
     return true;
 }
 
-// The last score_trees call's plan (device.hpp: TreePlan), written by whichever path launched.
-static std::mutex g_tree_plan_mu;
-static TreePlan g_tree_plan;
-static void set_tree_plan(TreePlan&& p) {
-    std::lock_guard<std::mutex> lk(g_tree_plan_mu);
-    g_tree_plan = std::move(p);
-}
-TreePlan last_tree_plan() {
-    std::lock_guard<std::mutex> lk(g_tree_plan_mu);
-    return g_tree_plan;
-}
-// (walks per thread, levels) of every batch of a descriptor list {start, n, levels, ..} x nbatch + terminator
-static std::vector<std::pair<uint32_t, uint32_t>> tree_plan_batches(const std::vector<uint32_t>& desc) {
-    std::vector<std::pair<uint32_t, uint32_t>> out;
-    for (size_t b = 0; b + 1 < desc.size() / 4; b++) out.emplace_back(desc[b * 4 + 1], desc[b * 4 + 2]);
-    return out;
-}
-
-// Largest f32 <= split: (f64(x) <= split) <=> (x <= thr) for every non-NaN f32 x.
-static float floor_to_f32(double split) {
-    float t = (float)split;
-    if ((double)t > split) t = std::nextafterf(t, -std::numeric_limits<float>::infinity());
-    return t;
-}
-
-// Block shapes of tree_ensemble_lds_kernel: DOCS documents x H parts, PF 16-byte prefetch words
-// per thread (x2 batches in flight; bounds the batch size), NMAX walks per thread.
-struct TreeShape {
-    unsigned docs, parts, pf, nmax;
-};
-static const TreeShape TREE_SHAPES[] = {
-    {256, 1, 6, 16}, {256, 2, 3, 16}, {256, 4, 4, 8}, {192, 2, 8, 16}, {192, 4, 4, 16}, {128, 1, 24, 16}, {128, 2, 24, 16},
-    {128, 4, 12, 16}, {64, 1, 24, 16}, {64, 4, 24, 16},
-};
-
-static void launch_tree_lds(const TreeShape& sh, size_t lds, hipStream_t stream, PosMap pm, size_t pos_threads, const float* xb, uint32_t dq,
-                            const fr_u32x4* forest, const uint32_t* desc, uint32_t nbatch, int raw_single, const double* leafprod,
-                            double* scores) {
-    auto go = [&](auto kern) {
-        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        kern<<<grid1d(pos_threads, sh.docs), sh.docs * sh.parts, lds, stream>>>(xb, pm, dq, forest, desc, nbatch, raw_single, leafprod, scores);
-    };
-    const unsigned key = sh.docs * 10 + sh.parts;
-    if (key == 2561) go(tree_ensemble_lds_kernel<256, 1, 6>);
-    else if (key == 2562) go(tree_ensemble_lds_kernel<256, 2, 3>);
-    else if (key == 2564) go(tree_ensemble_lds_kernel<256, 4, 4>);
-    else if (key == 1922) go(tree_ensemble_lds_kernel<192, 2, 8>);
-    else if (key == 1924) go(tree_ensemble_lds_kernel<192, 4, 4>);
-    else if (key == 1281) go(tree_ensemble_lds_kernel<128, 1, 24>);
-    else if (key == 1282) go(tree_ensemble_lds_kernel<128, 2, 24>);
-    else if (key == 1284) go(tree_ensemble_lds_kernel<128, 4, 12>);
-    else if (key == 641) go(tree_ensemble_lds_kernel<64, 1, 24>);
-    else go(tree_ensemble_lds_kernel<64, 4, 24>);
-}
-
-// Scores a forest with tree_ensemble_lds_kernel.  Returns false with an empty *err when the forest
-// does not fit the compact encoding in any block shape (caller falls back to the L2 walk).
-// Shapes are tried in order of measured speed at the 30K shape (tools/ab/treeshapes.sh, 500 trees: 192 x 4 parts
-// 5.4 ms (8 walks per thread), 192 x 2 6.9, 128 x 4 7.4, 256 x 2 7.8); smaller blocks leave more LDS
-// for big trees.  FR_TREE_SHAPE="docs,parts" pins one shape (benchmarking).
-bool DeviceDataset::try_score_trees_lds(const FlatTrees& t, std::string* err) {
-    if (err) err->clear();
-    unsigned want_docs = 0, want_parts = 0;
-    if (const char* e = frdev::path_env("FR_TREE_SHAPE")) std::sscanf(e, "%u,%u", &want_docs, &want_parts);
-    static const unsigned order_multi[][2] = {{192, 4}, {192, 2}, {128, 4}, {256, 2}, {256, 4}, {128, 2}, {64, 4}};
-    static const unsigned order_single[][2] = {{256, 1}, {128, 1}, {64, 1}};
-    // a single-tree model returns the bare leaf (no 0.0 + 1.0 * leaf), which only one-part blocks do
-    const auto* order = t.raw_single ? order_single : order_multi;
-    const size_t norder = t.raw_single ? 3 : 7;
-    for (size_t i = 0; i < norder; i++) {
-        if (want_docs && !t.raw_single && (order[i][0] != want_docs || order[i][1] != want_parts)) continue;
-        for (const TreeShape& sh : TREE_SHAPES) {
-            if (sh.docs != order[i][0] || sh.parts != order[i][1]) continue;
-            if (try_score_trees_lds_shape(t, &sh, err)) return true;
-            if (err && !err->empty()) return false;
-        }
-    }
-    if (want_docs && !t.raw_single) {  // pinned shape outside the default order (e.g. 256,1)
-        for (const TreeShape& sh : TREE_SHAPES)
-            if (sh.docs == want_docs && sh.parts == want_parts && try_score_trees_lds_shape(t, &sh, err)) return true;
-    }
-    return false;
-}
-
-// Packs the forest for one block shape (layout: see kernels_tree.inc) and launches the kernel.
-bool DeviceDataset::try_score_trees_lds_shape(const FlatTrees& t, const void* shape_ptr, std::string* err) {
-    Impl& m = *impl_;
-    const TreeShape* shape = (const TreeShape*)shape_ptr;
-    const size_t nt = t.root.size();
-    const uint32_t pad_slot = (uint32_t)m.dq * 4;  // the 0.0 slot that follows the feature columns in LDS
-    if (nt == 0) return false;
-    const size_t lds_cap = 160 * 1024;
-    const size_t fixed_bytes = ((size_t)shape->docs * (m.dq * 4 + 1) * sizeof(float) + 15) / 16 * 16 +
-                               (shape->parts > 1 ? (size_t)shape->docs * 8 : 0);
-    if (fixed_bytes + 8 * 1024 > lds_cap) return false;
-    size_t tree_bytes_cap = std::min<size_t>((size_t)shape->pf * 16 * shape->docs * shape->parts, (lds_cap - fixed_bytes) / 16 * 16);
-    if (const char* e = frdev::pricing_env("FR_TREE_CAP_KB")) tree_bytes_cap = std::min<size_t>(tree_bytes_cap, std::atoi(e) * 1024);
-    size_t H = shape->parts, max_n = shape->nmax;
-    if (const char* e = frdev::pricing_env("FR_TREE_NMAX")) max_n = std::max(1, std::min((int)max_n, std::atoi(e)));  // (benchmarking)
-    const uint32_t slot_bytes = shape->docs * 4, pad_off = pad_slot * slot_bytes;  // node words carry LDS byte offsets
-    const size_t words_cap = tree_bytes_cap / 8;
-    struct Packed {
-        std::vector<uint64_t> words;  // node words (indices relative to the tree's first word); a leaf's lo32 = index of
-        uint32_t nodes = 0, levels = 0;  // its product in `leafprod`
-    };
-    std::vector<double> leafprod(1, 0.0);  // [0] = +0.0: the padding trees' product
-    std::vector<double> tw = t.weight;
-    tw.resize(nt, 1.0);
-    std::vector<Packed> packed(nt + 1);  // [nt] = the padding tree: one leaf, product +0.0
-    for (size_t k = 0; k <= nt; k++) {
-        Packed& pk = packed[k];
-        std::vector<uint64_t> nodes;
-        const double w = k < nt ? tw[k] : 0.0;
-        if (k == nt) {
-            nodes.push_back((uint64_t)pad_off << 32);  // product index 0
-        } else {
-            struct Item { int32_t src; uint32_t dst; uint32_t depth; };
-            std::vector<Item> work;  // FIFO: breadth-first, so one level's nodes are contiguous in LDS and
-            nodes.push_back(0);      // the lanes of a wave (all on the same level) spread over the banks
-            work.push_back({t.root[k], 0u, 0u});
-            for (size_t head = 0; head < work.size(); head++) {
-                const Item it = work[head];
-                pk.levels = std::max(pk.levels, it.depth);
-                if (t.fid[it.src] < 0) {
-                    if (leafprod.size() >= (size_t(1) << 23)) return false;  // the index rides in an f32's bits as a small non-negative number
-                    nodes[it.dst] = ((uint64_t)pad_off << 32) | (uint64_t)leafprod.size();
-                    // out += weight * leaf (src/model.rs:104-112): the product does not depend on the document
-                    leafprod.push_back(t.raw_single ? t.split[it.src] : w * t.split[it.src]);
-                } else {
-                    const uint32_t left = (uint32_t)nodes.size();
-                    const uint32_t rel = left - it.dst;
-                    if (rel > 0xFF || nodes.size() + 2 > words_cap) return false;  // rel is 8 bits (a level of <= 255 nodes)
-                    const uint32_t slot = ((uint32_t)t.fid[it.src] < m.d ? (uint32_t)t.fid[it.src] : pad_slot) * slot_bytes;
-                    float thr = floor_to_f32(t.split[it.src]);
-                    uint32_t tb;
-                    std::memcpy(&tb, &thr, 4);
-                    nodes[it.dst] = ((uint64_t)rel << 56) | ((uint64_t)slot << 32) | tb;
-                    nodes.push_back(0);
-                    nodes.push_back(0);
-                    work.push_back({t.lhs[it.src], left, it.depth + 1});
-                    work.push_back({t.rhs[it.src], left + 1, it.depth + 1});
-                }
-            }
-        }
-        pk.nodes = (uint32_t)nodes.size();
-        pk.words = std::move(nodes);
-        if (pk.words.size() + 1 + (H - 1) * 2 > words_cap) return false;  // must fit beside H-1 padding trees
-    }
-    // Cut into batches of H*N trees, N the largest of 16/8/4/2/1 whose trees fit; when not even H
-    // trees fit (or fewer than H remain) the batch is N = 1 with padding trees.
-    std::vector<uint64_t> forest;
-    std::vector<uint32_t> desc;
-    size_t k0 = 0;
-    while (k0 < nt) {
-        std::vector<size_t> members;  // tree ids; nt = padding
-        size_t n = 0;
-        for (size_t cand = max_n; cand >= 1 && n == 0; cand /= 2) {
-            if (k0 + H * cand > nt) continue;
-            size_t words = 0;
-            for (size_t k = k0; k < k0 + H * cand; k++) words += packed[k].words.size() + 1;
-            if (words <= words_cap) n = cand;
-        }
-        if (n > 0) {
-            for (size_t k = k0; k < k0 + H * n; k++) members.push_back(k);
-        } else {
-            n = 1;
-            size_t words = H * 2;  // as if all padding (a padding tree is 1 word + 1 header word)
-            for (size_t k = k0; k < nt && members.size() < H; k++) {
-                if (words - 2 + packed[k].words.size() + 1 > words_cap) break;
-                words += packed[k].words.size() + 1 - 2;
-                members.push_back(k);
-            }
-            while (members.size() < H) members.push_back(nt);
-        }
-        const size_t ntb = members.size(), start = forest.size();
-        uint32_t levels = 0;
-        desc.insert(desc.end(), {(uint32_t)(start / 2), (uint32_t)n, 0u, 0u});
-        forest.resize(start + ntb);
-        for (size_t i = 0; i < ntb; i++) {
-            const size_t k = members[i];
-            const std::vector<uint64_t>& words = packed[k].words;
-            forest[start + i] = (uint32_t)(forest.size() - start);  // root
-            forest.insert(forest.end(), words.begin(), words.end());
-            levels = std::max(levels, packed[k].levels);
-            if (k < nt) k0 = k + 1;
-        }
-        desc[desc.size() - 2] = frdev::pricing_env("FR_TREE_NOWALK") ? 0u : levels;
-        if (forest.size() & 1) forest.push_back(0);
-    }
-    desc.insert(desc.end(), {(uint32_t)(forest.size() / 2), 0u, 0u, 0u});
-    const size_t nbatch = desc.size() / 4 - 1;
-    m.tree_rank_hash = 0;  // (the forest buffers are about to hold another layout)
-    if (!m.forest.ensure(forest.size(), err) || !m.batch_off.ensure(desc.size(), err) || !m.leafprod.ensure(leafprod.size(), err)) return false;
-    FR_HIP(hipMemcpyAsync(m.forest.p, forest.data(), forest.size() * 8, hipMemcpyHostToDevice, m.stream));
-    FR_HIP(hipMemcpyAsync(m.leafprod.p, leafprod.data(), leafprod.size() * 8, hipMemcpyHostToDevice, m.stream));
-    FR_HIP(hipMemcpyAsync(m.batch_off.p, desc.data(), desc.size() * 4, hipMemcpyHostToDevice, m.stream));
-    FR_HIP(hipStreamSynchronize(m.stream));
-    const size_t lds = fixed_bytes + words_cap * 8;
-    {
-        ProfScope ps("tree_ensemble_kernel", m.stream);
-        const fr_u32x4* f16 = (const fr_u32x4*)m.forest.p;
-        const int raw = t.raw_single ? 1 : 0;
-        launch_tree_lds(*shape, lds, m.stream, m.posmap(), m.pos_threads(), m.xb.p, (uint32_t)m.dq, f16, m.batch_off.p, (uint32_t)nbatch, raw, m.leafprod.p, m.scores.p);
-    }
-    FR_HIP(hipGetLastError());
-    TreePlan plan;
-    plan.path = TreePlan::LDS, plan.docs = shape->docs, plan.parts = shape->parts, plan.batches = tree_plan_batches(desc);
-    set_tree_plan(std::move(plan));
-    return true;
-}
-
-// Scores a forest with tree_ensemble_rank_kernel (kernels_treerank.inc: threshold ranks instead of features).  Returns
-// false with an empty *err when the forest does not fit that encoding: a single bare tree (raw output), a leaf deeper
-// than 10 levels, more than 1023 distinct thresholds on one feature, or more than 170 features in use (85 pairs of u16 codes
-// x 768 bytes + the two constant codes end at 65282 < 2^16) -- the caller then
-// takes the f32 LDS walk.  FR_TREE_RANK=0 switches the path off (A/B, and the parity tests of the other paths).
-bool DeviceDataset::try_score_trees_rank(const FlatTrees& t, std::string* err) {
-    Impl& m = *impl_;
-    if (err) err->clear();
-    if (const char* e = frdev::path_env("FR_TREE_RANK"))
-        if (std::atoi(e) == 0) return false;
-    const size_t nt = t.root.size();
-    if (nt == 0 || t.raw_single) return false;
-    constexpr unsigned DOCS = 192, H = 4, PF = 2;
-    constexpr size_t area_bytes = (size_t)PF * 16 * DOCS * H;  // batch area = what two prefetch slots of a block carry
-    const size_t nf = (size_t)m.dq * 4;
-    auto launch = [&](uint32_t nrounds, uint32_t nslots, size_t nbatch, size_t lds) {
-        ProfScope ps("tree_rank_kernel", m.stream);
-        auto kern = tree_ensemble_rank_kernel<DOCS, H, PF>;
-        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (frdev::pricing_env("FR_TREE_INFO")) {
-            int occ = -1;
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)kern, (int)(DOCS * H), lds);
-            fprintf(stderr, "[tree_rank] slots %u rounds %u batches %zu lds %zu B blocks/CU %d\n", nslots, nrounds, nbatch, lds, occ);
-        }
-        kern<<<grid1d(m.pos_threads(), DOCS), DOCS * H, lds, m.stream>>>(m.xb.p, m.posmap(), (uint32_t)m.dq, (const uint4*)m.tree_fdesc.p, m.tree_tables.p,
-                                                             (const uint4*)m.tree_rdesc.p, nrounds, nslots, (const fr_u32x4*)m.forest.p, m.batch_off.p, (uint32_t)nbatch,
-                                                             m.leafprod.p, m.scores.p);
-    };
-    // the same forest as last time? (FNV-1a over its nodes, roots and weights; FR_TREE_CACHE=0 turns the cache off)
-    uint64_t hash = 0xcbf29ce484222325ull;
-    {
-        auto mix = [&](const void* p, size_t bytes) {
-            const uint64_t* w = (const uint64_t*)p;
-            for (size_t i = 0; i < bytes / 8; i++) hash = (hash ^ w[i]) * 0x100000001b3ull;
-            const unsigned char* b = (const unsigned char*)p + bytes / 8 * 8;
-            for (size_t i = 0; i < bytes % 8; i++) hash = (hash ^ b[i]) * 0x100000001b3ull;
-        };
-        mix(t.fid.data(), t.fid.size() * sizeof(int32_t));
-        mix(t.lhs.data(), t.lhs.size() * sizeof(int32_t));
-        mix(t.rhs.data(), t.rhs.size() * sizeof(int32_t));
-        mix(t.split.data(), t.split.size() * sizeof(double));
-        mix(t.root.data(), t.root.size() * sizeof(int32_t));
-        mix(t.weight.data(), t.weight.size() * sizeof(double));
-        const uint64_t shape[2] = {t.fid.size(), t.root.size()};
-        mix(shape, sizeof(shape));
-        if (hash == 0) hash = 1;
-    }
-    static const bool cache_off = [] {
-        const char* e = frdev::pricing_env("FR_TREE_CACHE");
-        return e != nullptr && e[0] == '0';
-    }();
-    if (!cache_off && hash == m.tree_rank_hash) {
-        launch(m.tree_rank_nrounds, m.tree_rank_nslots, m.tree_rank_nbatch, m.tree_rank_lds);
-        FR_HIP(hipGetLastError());
-        TreePlan plan;
-        plan.path = TreePlan::RANK, plan.cache_hit = true, plan.nslots = m.tree_rank_nslots, plan.nrounds = m.tree_rank_nrounds;
-        plan.batches = m.tree_rank_batches;
-        set_tree_plan(std::move(plan));
-        return true;
-    }
-
-    // ---- distinct thresholds per feature, as f32 (largest f32 <= split), -0.0 folded onto +0.0
-    std::vector<std::vector<float>> thr(nf);
-    for (size_t i = 0; i < t.fid.size(); i++) {
-        if (t.fid[i] < 0 || (uint32_t)t.fid[i] >= m.d) continue;
-        float v = floor_to_f32(t.split[i]);
-        if (v != v) continue;  // NaN threshold: the node always goes right
-        if (v == 0.0f) v = 0.0f;
-        thr[(size_t)t.fid[i]].push_back(v);
-    }
-    std::vector<uint32_t> fdesc(nf * 4, 0u), slotoff(nf, 0xFFFFFFFFu);
-    std::vector<float> tables;
-    uint32_t nslots = 0;
-    for (size_t f = 0; f < nf; f++) {
-        std::vector<float>& v = thr[f];
-        fdesc[f * 4] = 0xFFFFFFFFu;
-        if (v.empty()) continue;
-        std::sort(v.begin(), v.end());
-        v.erase(std::unique(v.begin(), v.end()), v.end());
-        uint32_t logp = 1;
-        while ((size_t(1) << logp) <= v.size()) logp++;  // P = 2^logp > count
-        if (logp > 10) return false;
-        const uint32_t P = 1u << logp;
-        slotoff[f] = (nslots >> 1) * DOCS * 4 + (nslots & 1) * 2;  // half (slot & 1) of word slot / 2 of the document's column
-        fdesc[f * 4 + 0] = slotoff[f];
-        fdesc[f * 4 + 2] = logp;
-        fdesc[f * 4 + 3] = P;
-        nslots++;
-    }
-    if ((((size_t)nslots + 1) >> 1) * DOCS * 4 + 2 > 0xFFFF) return false;  // slot offsets ride in 16 bits
-    const uint32_t off_p0 = (nslots >> 1) * DOCS * 4 + (nslots & 1) * 2, off_p1 = ((nslots + 1) >> 1) * DOCS * 4 + ((nslots + 1) & 1) * 2;
-    // Ranking rounds (see the kernel): part h of a round ranks features of float4 group row * H + h; a group's tables go
-    // into as few chunks of <= 8 * DOCS floats as they need (one, unless several of its features have > 255 thresholds),
-    // a row of H groups takes as many rounds as its largest group.  Table = Eytzinger order: node i = 2^k + j (level
-    // k) holds the sorted element (2j + 1) * P / 2^(k+1) - 1, +inf where there is none.
-    constexpr uint32_t chunk_cap = 8 * DOCS;
-    static_assert((size_t)H * chunk_cap * 4 <= area_bytes, "the parts' table areas share the batch area");
-    std::vector<uint32_t> rdesc;
-    for (size_t row = 0; row * H < m.dq; row++) {
-        struct Sub { uint32_t len = 0; uint32_t off[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}; };
-        std::vector<Sub> subs[H];
-        size_t nsub = 1;
-        for (size_t h = 0; h < H; h++) {
-            const size_t j4 = row * H + h;
-            if (j4 >= m.dq) continue;
-            for (size_t c = 0; c < 4; c++) {
-                const size_t f = j4 * 4 + c;
-                if (thr[f].empty()) continue;
-                const uint32_t P = fdesc[f * 4 + 3];
-                if (subs[h].empty() || subs[h].back().len + P > chunk_cap) subs[h].emplace_back();
-                subs[h].back().off[c] = subs[h].back().len;
-                subs[h].back().len += P;
-            }
-            nsub = std::max(nsub, subs[h].size());
-        }
-        for (size_t sub = 0; sub < nsub; sub++)
-            for (size_t h = 0; h < H; h++) {
-                const size_t j4 = row * H + h;
-                if (sub >= subs[h].size()) {
-                    rdesc.insert(rdesc.end(), {0u, 0u, 0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu});
-                    continue;
-                }
-                const Sub& sb = subs[h][sub];
-                const size_t base = tables.size();
-                const uint32_t padded_len = (sb.len + DOCS - 1) / DOCS * DOCS;  // whole rows of DOCS floats (<= chunk_cap), +inf beyond the tables
-                tables.resize(base + padded_len, std::numeric_limits<float>::infinity());
-                for (size_t c = 0; c < 4; c++) {
-                    if (sb.off[c] == 0xFFFFFFFFu) continue;
-                    const size_t f = j4 * 4 + c;
-                    const std::vector<float>& v = thr[f];
-                    const uint32_t logp = fdesc[f * 4 + 2], P = fdesc[f * 4 + 3];
-                    for (uint32_t k = 0; k < logp; k++)
-                        for (uint32_t j = 0; j < (1u << k); j++) {
-                            const size_t idx = (size_t)(2 * j + 1) * (P >> (k + 1)) - 1;
-                            if (idx < v.size()) tables[base + sb.off[c] + (1u << k) + j] = v[idx];
-                        }
-                }
-                // the round's features by table depth, deepest first, absent ones last (the kernel's search loops
-                // run 1, 2, 3, 4 interleaved chains that end together)
-                uint32_t order[4] = {0, 1, 2, 3};
-                auto depth_of = [&](uint32_t c) { return sb.off[c] == 0xFFFFFFFFu ? 0u : fdesc[(j4 * 4 + c) * 4 + 2]; };
-                std::stable_sort(order, order + 4, [&](uint32_t a, uint32_t b) { return depth_of(a) > depth_of(b); });
-                uint32_t flags = sub == 0 ? 1u : 0u;
-                for (uint32_t j = 0; j < 4; j++) flags |= order[j] << (8 + 2 * j);
-                rdesc.insert(rdesc.end(), {(uint32_t)base, padded_len, (uint32_t)j4, flags, sb.off[order[0]], sb.off[order[1]], sb.off[order[2]], sb.off[order[3]]});
-            }
-    }
-    uint32_t nrounds = (uint32_t)(rdesc.size() / (8 * H));
-    if (frdev::pricing_env("FR_TREE_NOSTAGE")) nrounds = 0;  // (timing experiments: garbage codes, same walk cost)
-    const size_t codes_bytes = (((size_t)nslots + 3) / 2 * DOCS * 4 + 15) / 16 * 16;
-    const size_t lds = codes_bytes + (size_t)DOCS * 8 + area_bytes;
-
-    // ---- depth of every tree (steps that surely reach a leaf)
-    std::vector<uint32_t> depth(nt, 0);
-    {
-        std::vector<std::pair<int32_t, uint32_t>> work;
-        for (size_t k = 0; k < nt; k++) {
-            work.assign(1, {t.root[k], 0u});
-            while (!work.empty()) {
-                auto [src, dd] = work.back();
-                work.pop_back();
-                if (t.fid[src] < 0) {
-                    depth[k] = std::max(depth[k], dd);
-                } else {
-                    if (dd >= 10) return false;
-                    work.emplace_back(t.lhs[src], dd + 1);
-                    work.emplace_back(t.rhs[src], dd + 1);
-                }
-            }
-        }
-    }
-    std::vector<double> tw = t.weight;
-    tw.resize(nt, 1.0);
-    size_t max_n = 8;
-    if (const char* e = frdev::pricing_env("FR_TREE_NMAX")) max_n = std::max(1, std::min(8, std::atoi(e)));  // (benchmarking)
-
-    // ---- batches of H*N trees laid out as heaps of the batch's depth
-    std::vector<uint32_t> forest, desc;  // forest: 32-bit words, every batch a multiple of 16 bytes
-    std::vector<double> leafprod;
-    auto node_word = [&](int32_t src) -> uint32_t {
-        const uint32_t f = (uint32_t)t.fid[src];
-        const float v0 = floor_to_f32(t.split[src]);
-        if (v0 != v0) return off_p1;                                 // x <= NaN is false: right
-        if (f >= m.d) return (0.0f <= v0) ? off_p0 : off_p1;         // the feature reads 0.0
-        const float v = v0 == 0.0f ? 0.0f : v0;
-        const std::vector<float>& tv = thr[f];
-        const uint32_t j = (uint32_t)(std::lower_bound(tv.begin(), tv.end(), v) - tv.begin());
-        return (j << 16) | slotoff[f];
-    };
-    size_t k0 = 0;
-    while (k0 < nt) {
-        size_t n = 0, count = 0;
-        uint32_t L = 1;
-        for (size_t cand = max_n; cand >= 1 && n == 0; cand /= 2) {
-            if (k0 + H * cand > nt) continue;
-            uint32_t l = 1;
-            for (size_t k = k0; k < k0 + H * cand; k++) l = std::max(l, depth[k]);
-            if (H * cand * (size_t(6) << l) <= area_bytes) n = cand, L = l, count = H * cand;
-        }
-        if (n == 0) {  // fewer than H trees left, or deep trees: one walk per part, padding trees fill the parts
-            n = 1;
-            for (size_t k = k0; k < nt && count < H; k++) {
-                const uint32_t l = std::max(L, depth[k]);
-                if (H * (size_t(6) << l) > area_bytes) break;
-                L = l;
-                count++;
-            }
-            if (count == 0) return false;
-        }
-        const size_t start = forest.size(), leafbase = leafprod.size();
-        const size_t tw_words = (size_t(6) << L) / 4, bottom = size_t(1) << L;
-        desc.insert(desc.end(), {(uint32_t)(start / 4), (uint32_t)n, L, (uint32_t)leafbase});
-        if (frdev::pricing_env("FR_TREE_NOWALK")) desc[desc.size() - 2] = 0;  // (timing experiments: staging + batch streaming only)
-        forest.resize(start + (H * n * tw_words + 3) / 4 * 4, 0u);
-        leafprod.push_back(0.0);  // id 0: the padding trees' product, +0.0
-        for (size_t i = 0; i < H * n; i++) {
-            uint32_t* nodes = forest.data() + start + i * tw_words;
-            uint16_t* ids = (uint16_t*)(nodes + bottom);
-            for (size_t h = 0; h < bottom; h++) nodes[h] = off_p0;  // "stay left": code 0 > 0 is false
-            for (size_t h = 0; h < bottom; h++) ids[h] = 0;
-            if (i >= count) continue;
-            const size_t k = k0 + i;
-            struct Item { int32_t src; uint32_t h, dd; };
-            std::vector<Item> work(1, Item{t.root[k], 1u, 0u});
-            while (!work.empty()) {
-                const Item it = work.back();
-                work.pop_back();
-                if (t.fid[it.src] < 0) {
-                    const size_t id = leafprod.size() - leafbase;
-                    if (id > 0xFFFF) return false;
-                    leafprod.push_back(tw[k] * t.split[it.src]);  // out += weight * leaf (src/model.rs:104-112)
-                    const size_t span = size_t(1) << (L - it.dd), first = ((size_t)it.h << (L - it.dd)) - bottom;
-                    for (size_t b = 0; b < span; b++) ids[first + b] = (uint16_t)id;
-                } else {
-                    nodes[it.h] = node_word(it.src);
-                    work.push_back(Item{t.lhs[it.src], 2 * it.h, it.dd + 1});
-                    work.push_back(Item{t.rhs[it.src], 2 * it.h + 1, it.dd + 1});
-                }
-            }
-        }
-        k0 += count;
-    }
-    desc.insert(desc.end(), {(uint32_t)(forest.size() / 4), 0u, 0u, 0u});
-    const size_t nbatch = desc.size() / 4 - 1;
-    m.tree_rank_hash = 0;  // only now: a forest refused above has touched no buffer, and the forest kept from before still launches
-    if (!m.forest.ensure((forest.size() + 1) / 2, err) || !m.batch_off.ensure(desc.size(), err) ||
-        !m.leafprod.ensure(leafprod.size() + (frdev::pricing_env("FR_TREE_NOWALK") ? 65536 : 0), err) || !m.tree_fdesc.ensure(fdesc.size(), err) || !m.tree_tables.ensure(std::max<size_t>(tables.size(), 1), err) ||
-        !m.tree_rdesc.ensure(std::max<size_t>(rdesc.size(), 1), err))
-        return false;
-    FR_HIP(hipMemcpyAsync(m.forest.p, forest.data(), forest.size() * 4, hipMemcpyHostToDevice, m.stream));
-    FR_HIP(hipMemcpyAsync(m.leafprod.p, leafprod.data(), leafprod.size() * 8, hipMemcpyHostToDevice, m.stream));
-    FR_HIP(hipMemcpyAsync(m.batch_off.p, desc.data(), desc.size() * 4, hipMemcpyHostToDevice, m.stream));
-    FR_HIP(hipMemcpyAsync(m.tree_fdesc.p, fdesc.data(), fdesc.size() * 4, hipMemcpyHostToDevice, m.stream));
-    if (!tables.empty()) FR_HIP(hipMemcpyAsync(m.tree_tables.p, tables.data(), tables.size() * 4, hipMemcpyHostToDevice, m.stream));
-    if (!rdesc.empty()) FR_HIP(hipMemcpyAsync(m.tree_rdesc.p, rdesc.data(), rdesc.size() * 4, hipMemcpyHostToDevice, m.stream));
-    FR_HIP(hipStreamSynchronize(m.stream));
-    launch(nrounds, nslots, nbatch, lds);
-    FR_HIP(hipGetLastError());
-    m.tree_rank_hash = hash;
-    m.tree_rank_nrounds = nrounds;
-    m.tree_rank_nslots = nslots;
-    m.tree_rank_nbatch = (uint32_t)nbatch;
-    m.tree_rank_lds = lds;
-    m.tree_rank_batches = tree_plan_batches(desc);
-    TreePlan plan;
-    plan.path = TreePlan::RANK, plan.nslots = nslots, plan.nrounds = nrounds, plan.batches = m.tree_rank_batches;
-    set_tree_plan(std::move(plan));
-    return true;
-}
-
-// The forest re-laid so that the two children of a node are adjacent (rhs = lhs + 1): what tree_ensemble_kernel and
-// permute_trees_kernel walk.  A tree's nodes are contiguous, from roots[k] to the next tree's root.
-static void adjacent_children_layout(const FlatTrees& t, std::vector<TreeNodeDev>& nodes, std::vector<int32_t>& roots) {
-    const size_t nt = t.root.size();
-    nodes.clear();
-    roots.assign(nt, 0);
-    nodes.reserve(t.fid.size() + nt);
-    {
-        std::vector<std::pair<int32_t, int32_t>> work;  // (source node, destination slot)
-        for (size_t k = 0; k < nt; k++) {
-            roots[k] = (int32_t)nodes.size();
-            nodes.push_back(TreeNodeDev{0.0, -1, 0});
-            work.emplace_back(t.root[k], roots[k]);
-            while (!work.empty()) {
-                auto [src, dst] = work.back();
-                work.pop_back();
-                nodes[dst].split = t.split[src];
-                nodes[dst].fid = t.fid[src];
-                nodes[dst].lhs = 0;
-                if (t.fid[src] >= 0) {
-                    int32_t kids = (int32_t)nodes.size();
-                    nodes[dst].lhs = kids;
-                    nodes.push_back(TreeNodeDev{0.0, -1, 0});
-                    nodes.push_back(TreeNodeDev{0.0, -1, 0});
-                    work.emplace_back(t.lhs[src], kids);
-                    work.emplace_back(t.rhs[src], kids + 1);
-                }
-            }
-        }
-    }
-}
-
-bool DeviceDataset::score_trees(const FlatTrees& t, std::string* err) {
-    Impl& m = *impl_;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (!m.bind(err)) return false;
-    if (!m.scores.ensure(m.np, err)) return false;
-    m.scores_slots = 1;
-    if (try_score_trees_rank(t, err)) return true;
-    if (err && !err->empty()) return false;
-    if (try_score_trees_lds(t, err)) return true;
-    if (err && !err->empty()) return false;
-    const size_t nt = t.root.size();
-    std::vector<TreeNodeDev> nodes;
-    std::vector<int32_t> roots;
-    adjacent_children_layout(t, nodes, roots);
-    const size_t nn = nodes.size();
-    if (!m.nodes.ensure(std::max<size_t>(nn, 1), err) || !m.roots.ensure(std::max<size_t>(nt, 1), err) ||
-        !m.tweights.ensure(std::max<size_t>(nt, 1), err))
-        return false;
-    FR_HIP(hipMemcpyAsync(m.nodes.p, nodes.data(), nn * sizeof(TreeNodeDev), hipMemcpyHostToDevice, m.stream));
-    FR_HIP(hipMemcpyAsync(m.roots.p, roots.data(), nt * sizeof(int32_t), hipMemcpyHostToDevice, m.stream));
-    std::vector<double> tw = t.weight;
-    tw.resize(nt, 1.0);
-    FR_HIP(hipMemcpyAsync(m.tweights.p, tw.data(), nt * sizeof(double), hipMemcpyHostToDevice, m.stream));
-    FR_HIP(hipStreamSynchronize(m.stream));
-    const unsigned bs = 64;  // one tile per block (np is a multiple of 64)
-    size_t lds = (size_t)bs * (m.dq * 4 + 1) * sizeof(float);
-    {
-        TreePlan plan;
-        plan.path = TreePlan::L2, plan.rows_in_lds = lds <= 150 * 1024;
-        set_tree_plan(std::move(plan));
-    }
-    {
-        ProfScope ps("tree_ensemble_kernel", m.stream);
-        if (lds <= 150 * 1024) {
-            FR_HIP(hipFuncSetAttribute((const void*)tree_ensemble_kernel<true, 8>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            tree_ensemble_kernel<true, 8><<<grid1d(m.pos_threads(), bs), bs, lds, m.stream>>>(
-                m.xb.p, m.posmap(), (uint32_t)m.dq, (uint32_t)m.d, m.nodes.p, m.roots.p, m.tweights.p, (uint32_t)nt,
-                t.raw_single ? 1 : 0, m.scores.p);
-        } else {
-            tree_ensemble_kernel<false, 8><<<grid1d(m.pos_threads(), bs), bs, 0, m.stream>>>(
-                m.xb.p, m.posmap(), (uint32_t)m.dq, (uint32_t)m.d, m.nodes.p, m.roots.p, m.tweights.p, (uint32_t)nt,
-                t.raw_single ? 1 : 0, m.scores.p);
-        }
-    }
-    FR_HIP(hipGetLastError());
-    return true;
-}
+#include "score_trees.inc"
 
 bool DeviceDataset::ensemble_begin(std::string* err) {
     Impl& m = *impl_;

@@ -690,6 +690,29 @@ inline void check_flags(frdev::DeviceDataset& dev) {
         if (!(call)) fr::fail_str(_err);  \
     } while (0)
 
+// `m` as DeviceDataset::score_trees takes it: a bare DecisionTree, or an Ensemble of nothing but DecisionTrees.  false (and *ft
+// untouched): a model of another kind.
+inline bool flat_trees_of(const Model& m, frdev::FlatTrees* ft) {
+    if (m.kind == Model::DecisionTree) {
+        ft->raw_single = true;
+        ft->root.push_back(flatten_tree(*m.tree, *ft));
+        ft->weight.push_back(1.0);
+        return true;
+    }
+    bool all_trees = m.kind == Model::Ensemble && !m.members.empty();
+    for (const auto& mm : m.members) all_trees = all_trees && mm.kind == Model::DecisionTree;
+    if (!all_trees) return false;
+    for (size_t t = 0; t < m.members.size(); t++) {
+        ft->root.push_back(flatten_tree(*m.members[t].tree, *ft));
+        ft->weight.push_back(t < m.ens_weights.size() ? m.ens_weights[t] : 0.0);
+    }
+    // zip(weights, models) stops at the shorter (src/model.rs:106)
+    size_t nt = std::min(m.members.size(), m.ens_weights.size());
+    ft->root.resize(nt);
+    ft->weight.resize(nt);
+    return true;
+}
+
 // Score `model` for every document of the view into device score slot 0.
 inline void score_model(DatasetView& view, const Model& m, frdev::DeviceDataset* on = nullptr) {
     frdev::DeviceDataset& dev = on ? *on : view.device();  // (on: one of the view's device-side copies, DatasetView::device_ptr(slot, ..))
@@ -706,25 +729,13 @@ inline void score_model(DatasetView& view, const Model& m, frdev::DeviceDataset*
             break;
         case Model::DecisionTree: {
             frdev::FlatTrees ft;
-            ft.raw_single = true;
-            ft.root.push_back(flatten_tree(*m.tree, ft));
-            ft.weight.push_back(1.0);
+            flat_trees_of(m, &ft);
             if (!dev.score_trees(ft, &_err)) fail_str(_err);
             break;
         }
         case Model::Ensemble: {
-            bool all_trees = !m.members.empty();
-            for (const auto& mm : m.members) all_trees = all_trees && mm.kind == Model::DecisionTree;
-            if (all_trees) {
-                frdev::FlatTrees ft;
-                for (size_t t = 0; t < m.members.size(); t++) {
-                    ft.root.push_back(flatten_tree(*m.members[t].tree, ft));
-                    ft.weight.push_back(t < m.ens_weights.size() ? m.ens_weights[t] : 0.0);
-                }
-                // zip(weights, models) stops at the shorter (src/model.rs:106)
-                size_t nt = std::min(m.members.size(), m.ens_weights.size());
-                ft.root.resize(nt);
-                ft.weight.resize(nt);
+            frdev::FlatTrees ft;
+            if (flat_trees_of(m, &ft)) {
                 if (!dev.score_trees(ft, &_err)) fail_str(_err);
             } else {
                 if (!dev.ensemble_begin(&_err)) fail_str(_err);

@@ -1,9 +1,5 @@
 // Part of device.hip (single translation unit; see that file's header).  Tree-ensemble scoring kernels (config 5 of BASELINE.json).
-struct TreeNodeDev {
-    double split;  // threshold, or the leaf value when fid < 0
-    int32_t fid;   // < 0: leaf
-    int32_t lhs;   // left child; the right child is lhs + 1 (children are stored adjacently)
-};
+// (TreeNodeDev, the node record of the L2 walk, is forest_pack.hpp's, with the packers of the layouts described below.)
 
 // Batched tree-ensemble scoring (src/model.rs:64-84,104-112; config 5 of BASELINE.json).
 // One thread = one document, one 64-document tile per block.  The block first stages its

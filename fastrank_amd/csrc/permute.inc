@@ -1,6 +1,7 @@
 // Part of device.hip (single translation unit; see that file's header).  The launchers of kernels_permute.inc (DESIGN.md
 // section 16): the source positions uploaded once per call, then per chunk of columns one scoring pass into score slots
-// k * R + r, which metric_from_scores and reduce_means take as they take any B slots.
+// k * R + r, which metric_from_scores and reduce_means take as they take any B slots.  The trees' layout (TreeNodeDev,
+// adjacent_children_layout) is forest_pack.hpp's, which device.hip includes ahead of every part.
 
 struct PermuteState {
     DevBuf<uint32_t> src, feats, uses;

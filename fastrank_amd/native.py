@@ -589,6 +589,26 @@ def last_tree_plan() -> Dict:
     return _json_reply(_load().fr_debug_tree_plan())
 
 
+_FOREST_TABLE_DTYPES = {"fdesc": np.uint32, "tables": np.float32, "rdesc": np.uint32, "desc": np.uint32, "leafprod": np.float64,
+                        "roots": np.int32, "tweights": np.float64,
+                        "nodes": np.dtype([("split", np.float64), ("fid", np.int32), ("lhs", np.int32)])}
+
+
+def forest_pack(model: CModel, dataset_features: int, encoding: str) -> Dict:
+    """fr_debug_forest_pack: the forest of `model` packed on the host (no device) for encoding "rank", "lds:DOCS,PARTS" or
+    "l2" on a dataset of dataset_features features: the hook's JSON, its "tables" read back as numpy arrays ("forest": uint32
+    words for "rank", uint64 words for an LDS shape)."""
+    L, enc = _load(), encoding.encode("utf-8")
+    rep = _json_reply(L.fr_debug_forest_pack(model.pointer, int(dataset_features), enc, None, None, 0))
+    sizes, rep["tables"] = rep["tables"], {}
+    for name, nbytes in sizes.items():
+        dtype = np.dtype(_FOREST_TABLE_DTYPES.get(name, np.uint32 if encoding == "rank" else np.uint64))
+        arr = np.zeros(int(nbytes) // dtype.itemsize, dtype=dtype)
+        _json_reply(L.fr_debug_forest_pack(model.pointer, int(dataset_features), enc, name.encode("utf-8"), arr.ctypes.data if arr.size else None, arr.nbytes))
+        rep["tables"][name] = arr
+    return rep
+
+
 def last_metric_plan() -> Dict:
     """What the last general metric pass of this process launched (fr_debug_metric_plan): {"measure", "depth", "slots",
     "classes": [{"npad", "queries", "kernel": "sort" | "topk"}, ...]}; {"measure": None} before the first one."""

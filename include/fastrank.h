@@ -193,6 +193,16 @@ const void *fr_last_train_stats(void);
  * the buffers the call before left; lds: "docs", "parts" (the block shape); l2: "rows_in_lds"; rank: "nslots" (features in
  * use), "nrounds"; rank and lds: "batches": [[walks per thread, levels], ...]}. */
 const void *fr_debug_tree_plan(void);
+/* Test hook, no device: `model`'s forest (a DecisionTree or an Ensemble of DecisionTrees) packed on the host for one encoding of
+ * DESIGN.md section 5.6 (csrc/forest_pack.hpp) on a dataset of dataset_features features -- the buffers a scoring call would
+ * upload.  encoding: "rank", "lds:DOCS,PARTS" (one block shape of the f32 LDS walk) or "l2".  JSON (free_str): {"admitted":
+ * false when the forest lies outside a limit of the encoding, "hash": the packed-forest cache's key as hex, "tables": {name:
+ * bytes} (rank: "fdesc", "tables", "rdesc", "forest", "desc", "leafprod"; lds: "forest", "desc", "leafprod"; l2: "nodes",
+ * "roots", "tweights"), rank and lds: "lds_bytes", "batches": [[walks per thread, levels], ...]; rank: "nslots", "nrounds"}.
+ * table == NULL: the JSON alone; else also the named table's bytes into out[out_bytes], with the name / out-buffer protocol
+ * of fr_debug_device_form (a wrong out_bytes or a name the encoding does not have is an error). */
+const void *fr_debug_forest_pack(const CModel *model, uint32_t dataset_features, const void *encoding, const void *table,
+                                 void *out, size_t out_bytes);
 /* What the process's last general metric pass launched, a test hook; JSON (free_str), host
  * bookkeeping alone: {"measure": the measure's first name (null before the first call), "depth": the cut-off or null,
  * "slots": score slots evaluated at once, "classes": [{"npad": the size class, "queries", "kernel": "sort" | "topk"}, ...]}.

@@ -34,7 +34,9 @@ def test_every_unit_depends_on_the_closure_of_its_includes():
     assert [u[3] for u in units] == [u[3] for u in _build.units()], "the order is deterministic"
     by_obj = {u[0]: set(u[3]) for u in units}
     assert {"dataset_build.inc", "train_rf.inc", "train_lambda.inc", "train_dart.inc", "train_hist.inc", "device_dataset.inc",
+            "score_trees.inc", "forest_pack.hpp",
             "kernels_fillnet.inc"} <= by_obj["device.o"]  # (kernels_fillnet.inc: through kernels_verify.inc only)
+    assert "forest_pack.hpp" in by_obj["capi.o"]
     assert os.path.join("..", "..", "include", "fastrank.h") in by_obj["capi.o"]
     assert "dataset_layout.hpp" in by_obj["fullverify_0.o"]  # (through device.hpp)
 

@@ -268,10 +268,10 @@ for _leaves in (255, 32):
 @functools.lru_cache(maxsize=None)
 def lds_shape_table():
     """(TREE_SHAPES as {(docs, parts): prefetch words}, the order multi-tree forests try them in), read from the packer."""
-    src = open(os.path.join(ROOT, "fastrank_amd", "csrc", "device_dataset.inc")).read()
+    src = open(os.path.join(ROOT, "fastrank_amd", "csrc", "forest_pack.hpp")).read()
     table = re.search(r"TREE_SHAPES\[\] = \{(.*?)\};", src, re.S).group(1)
     shapes = {(int(a), int(b)): int(c) for a, b, c, _ in re.findall(r"\{(\d+), (\d+), (\d+), (\d+)\}", table)}
-    order = re.search(r"order_multi\[\]\[2\] = \{(.*?)\};", src, re.S).group(1)
+    order = re.search(r"TREE_ORDER_MULTI\[\]\[2\] = \{(.*?)\};", src, re.S).group(1)
     order = [(int(a), int(b)) for a, b in re.findall(r"\{(\d+), (\d+)\}", order)]
     assert len(shapes) == 10 and len(order) == 7 and all(s in shapes for s in order)
     return shapes, order
