@@ -4,6 +4,7 @@
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <memory>
 #include <utility>
 #include <vector>
 
@@ -112,6 +113,50 @@ inline PermuteShape permute_model_shape(const Model& m) {
     if (flat) return PermuteShape::ENSEMBLE_LINEAR;
     fail_str("permutation importance takes a Linear, SingleFeature or DecisionTree model, an Ensemble of DecisionTrees or an Ensemble of Linear / "
              "SingleFeature models, not " + permute_shape_name(m));
+}
+
+// The model as the kernels take it (DeviceDataset::permute_score): its members in order, and what they point into.  Both
+// stores keep their heap blocks when the record moves, so the members' pointers hold; it cannot be copied.
+struct PermuteModel {
+    std::vector<frdev::PermuteMember> members;
+    std::vector<std::vector<double>> weights;  // the LINEAR members' weights over the matrix's d columns, in member order
+    std::unique_ptr<frdev::FlatTrees> trees;   // the TREES member's forest
+};
+
+// `m` of shape `shape` for a matrix of d columns.  Linear weights past d are dropped and missing ones are 0.0; an Ensemble's
+// zip(weights, models) stops at the shorter (src/model.rs:106).
+inline PermuteModel permute_model(const Model& m, PermuteShape shape, size_t d) {
+    PermuteModel pm;
+    if (shape == PermuteShape::TREES) {
+        pm.trees = std::make_unique<frdev::FlatTrees>();
+        flat_trees_of(m, pm.trees.get());
+        frdev::PermuteMember mem;
+        mem.kind = frdev::PermuteMember::TREES, mem.trees = pm.trees.get();
+        pm.members.push_back(mem);
+        return pm;
+    }
+    auto add_flat = [&](const Model& mm, double ens_w) {
+        frdev::PermuteMember mem;
+        mem.ens_weight = ens_w;
+        if (mm.kind == Model::Linear) {
+            pm.weights.emplace_back(d, 0.0);
+            for (size_t j = 0; j < d && j < mm.weights.size(); j++) pm.weights.back()[j] = mm.weights[j];
+            mem.kind = frdev::PermuteMember::LINEAR;
+        } else {
+            mem.kind = frdev::PermuteMember::SINGLE, mem.fid = mm.fid, mem.dir = mm.dir;
+        }
+        pm.members.push_back(mem);
+    };
+    if (shape == PermuteShape::ENSEMBLE_LINEAR) {
+        const size_t nt = std::min(m.members.size(), m.ens_weights.size());
+        for (size_t t = 0; t < nt; t++) add_flat(m.members[t], m.ens_weights[t]);
+    } else {
+        add_flat(m, 1.0);
+    }
+    size_t k = 0;  // (the store no longer grows: its vectors' addresses hold)
+    for (auto& mem : pm.members)
+        if (mem.kind == frdev::PermuteMember::LINEAR) mem.weights = pm.weights[k++].data();
+    return pm;
 }
 
 inline bool permute_tree_uses(const TreeNode& n, uint32_t f) {

@@ -211,6 +211,64 @@ int main() {
         CHECK(!fr::permute_feature_used(forest, 3, colmax));
         CHECK(fr::permute_feature_used(flat, 2, colmax));
     }
+
+    // the model as the kernels take it, at its edges
+    {
+        using PM = frdev::PermuteMember;
+        fr::Model lin, single, tree, forest, flat;
+        lin.kind = fr::Model::Linear, lin.weights = {0.5, -1.0};
+        single.kind = fr::Model::SingleFeature, single.fid = 2, single.dir = -1.0;
+        tree.kind = fr::Model::DecisionTree, tree.tree = stump(1);
+        // a bare tree: one TREES member over one root, taken raw
+        fr::PermuteModel pm = fr::permute_model(tree, fr::permute_model_shape(tree), 4);
+        CHECK(pm.members.size() == 1 && pm.members[0].kind == PM::TREES && pm.members[0].trees == pm.trees.get() && pm.weights.empty());
+        CHECK(pm.trees->raw_single && pm.trees->root.size() == 1 && pm.trees->root[0] == 0 && pm.trees->fid.size() == 3 && pm.trees->fid[0] == 1);
+        // a forest with fewer weights than members, and the reverse: zip stops at the shorter
+        forest.kind = fr::Model::Ensemble, forest.members = {tree, tree, tree}, forest.ens_weights = {2.0, 3.0};
+        forest.members[1].tree = stump(3);
+        pm = fr::permute_model(forest, fr::permute_model_shape(forest), 4);
+        CHECK(pm.members.size() == 1 && pm.members[0].kind == PM::TREES && pm.members[0].trees == pm.trees.get() && !pm.trees->raw_single);
+        CHECK(pm.trees->root.size() == 2 && pm.trees->weight.size() == 2 && pm.trees->weight[0] == 2.0 && pm.trees->weight[1] == 3.0);
+        CHECK(pm.trees->fid[(size_t)pm.trees->root[0]] == 1 && pm.trees->fid[(size_t)pm.trees->root[1]] == 3);
+        forest.members.resize(1), forest.ens_weights = {2.0, 3.0, 4.0};
+        pm = fr::permute_model(forest, fr::permute_model_shape(forest), 4);
+        CHECK(pm.trees->root.size() == 1 && pm.trees->weight.size() == 1 && pm.trees->weight[0] == 2.0);
+        // a linear model with fewer weights than d (the rest are 0.0) and with more (the rest are dropped)
+        pm = fr::permute_model(lin, fr::permute_model_shape(lin), 4);
+        CHECK(pm.members.size() == 1 && pm.members[0].kind == PM::LINEAR && pm.members[0].ens_weight == 1.0 && !pm.trees);
+        CHECK(pm.weights.size() == 1 && pm.weights[0].size() == 4 && pm.members[0].weights == pm.weights[0].data());
+        CHECK(pm.weights[0][0] == 0.5 && pm.weights[0][1] == -1.0 && pm.weights[0][2] == 0.0 && pm.weights[0][3] == 0.0);
+        pm = fr::permute_model(lin, fr::permute_model_shape(lin), 1);
+        CHECK(pm.weights[0].size() == 1 && pm.weights[0][0] == 0.5 && pm.members[0].weights == pm.weights[0].data());
+        pm = fr::permute_model(lin, fr::permute_model_shape(lin), 0);
+        CHECK(pm.members.size() == 1 && pm.weights[0].empty());
+        pm = fr::permute_model(single, fr::permute_model_shape(single), 4);
+        CHECK(pm.members.size() == 1 && pm.members[0].kind == PM::SINGLE && pm.members[0].fid == 2 && pm.members[0].dir == -1.0 && pm.weights.empty());
+        // a mixed ensemble, more members than weights: each LINEAR member points at its own weights, in member order, after
+        // the store has grown (many members) and after the record has moved
+        flat.kind = fr::Model::Ensemble;
+        for (int k = 0; k < 40; k++) {
+            flat.members.push_back(k % 3 == 1 ? single : lin);
+            flat.members.back().weights.assign(lin.weights.size(), (double)k);
+            flat.ens_weights.push_back(0.25 * k);
+        }
+        flat.ens_weights.resize(37);
+        fr::PermuteModel moved = fr::permute_model(flat, fr::permute_model_shape(flat), 3);
+        pm = std::move(moved);
+        CHECK(pm.members.size() == 37 && pm.weights.size() == 25 && !pm.trees);
+        size_t at = 0;
+        for (size_t k = 0; k < pm.members.size(); k++) {
+            CHECK(pm.members[k].ens_weight == 0.25 * (double)k);
+            if (k % 3 == 1) {
+                CHECK(pm.members[k].kind == PM::SINGLE && pm.members[k].weights == nullptr && pm.members[k].fid == 2);
+                continue;
+            }
+            CHECK(pm.members[k].kind == PM::LINEAR && pm.members[k].weights == pm.weights[at].data() && pm.weights[at].size() == 3);
+            CHECK(pm.members[k].weights[0] == (double)k && pm.members[k].weights[1] == (double)k && pm.members[k].weights[2] == 0.0);
+            at++;
+        }
+        CHECK(at == pm.weights.size());
+    }
     std::printf("permute_host ok\n");
     return 0;
 }

@@ -458,3 +458,155 @@ def test_nan_label_does_not_unwind_through_the_c_abi():
     ds = fr.CDataset.from_numpy(X, y, qid)
     with pytest.raises(ValueError, match="NaN label"):  # no abort: SIZE_MAX flags the bad dataset
         native.num_queries(ds)
+
+
+NO_GPU = "no MI355X/HIP device"  # (test_compute_without_gpu_fails_loudly)
+
+
+def _error_of(reply):
+    """the context of an error envelope (None: the reply is none)"""
+    if reply is None:
+        return None
+    try:
+        payload = json.loads(reply)
+    except ValueError:
+        return None
+    return payload.get("context") if isinstance(payload, dict) and "error" in payload else None
+
+
+def _wins(reply, message):
+    got = _error_of(reply)
+    assert got is not None and message in got, (message, reply)
+
+
+def test_refusal_order_of_the_evaluate_train_and_load_entries(trec, tmp_path):
+    """Which message wins when several inputs of one call are bad at once, for the entries that had no such test: every call
+    below is wrong in more than one way, and each step mends the refusal that just won.  Refusals that need no device come
+    before any device is touched, in the order of the reference's argument checks; the missing device is reported last of all
+    (only a box without a GPU can show that: with one, the fully mended calls are the GPU suite's business)."""
+    L = clib._load()
+    T = clib._take_str
+    no_gpu = native.device_count() == 0
+    ds = fr.CDataset.from_numpy(trec["train_X"], trec["train_y"], trec["train_qid"])
+    empty = fr.CDataset(clib._unwrap(L.dataset_query_sampling(ds.pointer, b"[]")))  # a view without instances
+    assert empty.num_instances() == 0
+    m = fr.CModel.from_dict({"Linear": {"weights": [1.0] * 6}})
+    unknown = "Invalid training measure"
+
+    # evaluate_by_query: model, dataset, name; an unknown evaluator before the empty view's empty reply
+    _wins(T(L.evaluate_by_query(None, None, None, None)), "Model pointer is null!")
+    _wins(T(L.evaluate_by_query(m.pointer, None, None, None)), "Dataset pointer is null!")
+    _wins(T(L.evaluate_by_query(m.pointer, ds.pointer, None, None)), "NULL pointer: evaluator_name")
+    _wins(T(L.evaluate_by_query(m.pointer, empty.pointer, None, b"nope")), unknown)
+    assert T(L.evaluate_by_query(m.pointer, empty.pointer, None, b"ndcg")) == "{}"
+    if no_gpu:
+        _wins(T(L.evaluate_by_query(m.pointer, ds.pointer, None, b"ndcg")), NO_GPU)
+
+    # predict_to_trecrun: model, dataset, both names, the file, and only then the view
+    nowhere = os.path.join(str(tmp_path), "no-such-directory", "x.run").encode()
+    run = os.path.join(str(tmp_path), "x.run").encode()
+    _wins(T(L.predict_to_trecrun(None, None, None, None, 0)), "Model pointer is null!")
+    _wins(T(L.predict_to_trecrun(m.pointer, None, None, None, 0)), "Dataset pointer is null!")
+    _wins(T(L.predict_to_trecrun(m.pointer, ds.pointer, None, None, 0)), "NULL pointer: output_path")
+    _wins(T(L.predict_to_trecrun(m.pointer, ds.pointer, nowhere, None, 0)), "NULL pointer: system_name")
+    _wins(T(L.predict_to_trecrun(m.pointer, ds.pointer, nowhere, b"sys", 0)), "could not open")
+    assert T(L.predict_to_trecrun(m.pointer, empty.pointer, run, b"sys", 0)) == "0"
+    if no_gpu:
+        _wins(T(L.predict_to_trecrun(m.pointer, ds.pointer, run, b"sys", 0)), NO_GPU)
+
+    # fr_evaluate_dense: model, dataset, name, the evaluator -- all before the device, the output's size after it
+    _wins(T(L.fr_evaluate_dense(None, None, None, None, None, 0, None)), "Model pointer is null!")
+    _wins(T(L.fr_evaluate_dense(m.pointer, None, None, None, None, 0, None)), "Dataset pointer is null!")
+    _wins(T(L.fr_evaluate_dense(m.pointer, ds.pointer, None, None, None, 0, None)), "NULL pointer: evaluator_name")
+    _wins(T(L.fr_evaluate_dense(m.pointer, empty.pointer, None, b"nope", None, 0, None)), unknown)
+    if no_gpu:
+        _wins(T(L.fr_evaluate_dense(m.pointer, ds.pointer, None, b"nope", None, 0, None)), unknown)
+        _wins(T(L.fr_evaluate_dense(m.pointer, ds.pointer, None, b"ndcg", None, 0, None)), NO_GPU)  # (not "buffer too small")
+
+    # fr_rank_order: model, dataset, the device, the outputs' sizes
+    _wins(T(L.fr_rank_order(None, None, None, 0, None, 0)), "Model pointer is null!")
+    _wins(T(L.fr_rank_order(m.pointer, None, None, 0, None, 0)), "Dataset pointer is null!")
+    if no_gpu:
+        _wins(T(L.fr_rank_order(m.pointer, ds.pointer, None, 0, None, 0)), NO_GPU)  # (not "buffers too small")
+
+    # fr_compare_models: the dataset first, the two strings, the options, the count, the list, each model, the evaluator, the view
+    one = (ctypes.c_void_p * 1)(m.pointer)
+    null = (ctypes.c_void_p * 1)(None)
+    _wins(T(L.fr_compare_models(None, 0, None, None, None, None)), "Dataset pointer is null!")
+    _wins(T(L.fr_compare_models(None, 0, empty.pointer, None, None, None)), "NULL pointer: evaluator_name")
+    _wins(T(L.fr_compare_models(None, 0, empty.pointer, None, b"nope", None)), "NULL pointer: options_json")
+    _wins(T(L.fr_compare_models(None, 0, empty.pointer, None, b"nope", b"{")), "key must be a string")
+    _wins(T(L.fr_compare_models(None, 0, empty.pointer, None, b"nope", b'{"trails": 1}')), "unknown field")
+    _wins(T(L.fr_compare_models(None, 0, empty.pointer, None, b"nope", b"{}")), "between 1 and 8 systems, not 0")
+    _wins(T(L.fr_compare_models(None, 1, empty.pointer, None, b"nope", b"{}")), "NULL pointer: models")
+    _wins(T(L.fr_compare_models(null, 1, empty.pointer, None, b"nope", b"{}")), "Model pointer is null!")
+    _wins(T(L.fr_compare_models(one, 1, empty.pointer, None, b"nope", b"{}")), unknown)
+    _wins(T(L.fr_compare_models(one, 1, empty.pointer, None, b"ndcg", b"{}")), "a comparison needs at least one query")
+    if no_gpu:
+        _wins(T(L.fr_compare_models(one, 1, ds.pointer, None, b"ndcg", b"{}")), NO_GPU)
+
+    # the two trainer constructors: dataset, request, learner, (callback,) evaluator, "no queries" -- each entry's own condition
+    ca = fr.TrainRequest.coordinate_ascent().to_dict()
+    rf = fr.TrainRequest.random_forest().to_dict()
+    rf["params"]["RandomForest"]["split_method"] = {"SquaredError": []}
+    wire = lambda req, measure: json.dumps(dict(req, measure=measure)).encode()
+
+    def begin(*args):
+        err = ctypes.c_void_p()
+        handle = L.fr_ca_begin(*args, ctypes.byref(err))
+        assert not handle
+        return T(err.value)
+
+    def begin_shard(*args):
+        err = ctypes.c_void_p()
+        handle = L.fr_ca_begin_query_shard(*args, ctypes.byref(err))
+        assert not handle
+        return T(err.value)
+
+    assert not L.fr_ca_begin(None, None, 0, 1, None)  # (no place for the message: still refused)
+    _wins(begin(None, None, 0, 1), "Dataset pointer is null!")
+    _wins(begin(None, empty.pointer, 0, 1), "NULL pointer: train_request_json")
+    _wins(begin(b"{", empty.pointer, 0, 1), "key must be a string")
+    _wins(begin(wire(rf, "nope"), empty.pointer, 0, 1), "fr_ca_begin: only CoordinateAscent")
+    _wins(begin(wire(ca, "nope"), empty.pointer, 0, 1), unknown)
+    _wins(begin(wire(ca, "ndcg"), empty.pointer, 0, 1), "assertion failed: !data.queries().is_empty()")
+    if no_gpu:
+        _wins(begin(wire(ca, "ndcg"), ds.pointer, 0, 1), NO_GPU)
+
+    no_callback = clib.ALLREDUCE_SUM_FN()
+    callback = clib.ALLREDUCE_SUM_FN(lambda ctx, values, n: 0)
+    _wins(begin_shard(None, None, 0, no_callback, None), "Dataset pointer is null!")
+    _wins(begin_shard(None, ds.pointer, 0, no_callback, None), "NULL pointer: train_request_json")
+    _wins(begin_shard(wire(rf, "nope"), ds.pointer, 0, no_callback, None), "fr_ca_begin_query_shard: only CoordinateAscent")
+    _wins(begin_shard(wire(ca, "nope"), ds.pointer, 0, no_callback, None), "fr_ca_begin_query_shard: allreduce callback is null!")
+    _wins(begin_shard(wire(ca, "nope"), ds.pointer, 0, callback, None), unknown)
+    # (its "no queries" is the job's total, not this shard's: a full view with total 0 is refused, an empty one with total 5 gets
+    # as far as the trainer, which has its own word for it)
+    _wins(begin_shard(wire(ca, "ndcg"), ds.pointer, 0, callback, None), "assertion failed: !data.queries().is_empty()")
+    _wins(begin_shard(wire(ca, "ndcg"), empty.pointer, 5, callback, None), "assertion failed: !data.instances().is_empty()")
+    if no_gpu:
+        _wins(begin_shard(wire(ca, "ndcg"), ds.pointer, 5, callback, None), NO_GPU)
+
+    # the three handle constructors: the strings in argument order, the names file before the parser's word, that before the data
+    def refused(result, message):
+        with pytest.raises(Exception) as exc:
+            clib._unwrap(result)
+        assert message in str(exc.value), (message, str(exc.value))
+
+    data = os.path.join(GOLDEN, "data", "trec_news_2018.train").encode()
+    refused(L.fr_load_ranksvm(None, None, None), "NULL pointer: data_path")
+    refused(L.fr_load_ranksvm(b"/nonexistent/a.train", b"/nonexistent/names.json", None), "NULL pointer: parser")
+    refused(L.fr_load_ranksvm(data, b"/nonexistent/names.json", b"bogus"), "NotFound")
+    refused(L.fr_load_ranksvm(b"/nonexistent/a.train", None, b"bogus"), 'unknown parser \\"bogus\\"')
+    refused(L.fr_load_ranksvm(data, None, b"bogus"), 'unknown parser \\"bogus\\"')
+    refused(L.fr_load_ranksvm(b"/nonexistent/a.train", None, b"host"), "NotFound")
+    refused(L.load_ranksvm_format(b"/nonexistent/a.train", None), "NotFound")
+    refused(L.load_cqrel(None), "NULL pointer: data_path")
+    refused(L.load_cqrel(b"/nonexistent/qrel"), "NotFound")
+    refused(L.cqrel_from_json(None), "NULL pointer: json_str")
+    refused(L.cqrel_from_json(b"{"), "key must be a string")
+    refused(L.cqrel_from_json(b"[1]"), "invalid type: expected a map")
+    refused(L.cqrel_from_json(b'{"q": {"d": "x"}}'), "expected f64 for gain")
+    # (a refused constructor leaves nothing behind, and a later good call is not disturbed)
+    assert fr.CQRel.from_dict({"q": {"d": 1.0}}).to_dict() == {"q": {"d": 1.0}}
+    assert fr.CDataset(clib._unwrap(L.fr_load_ranksvm(data, None, b"host"))).num_instances() > 0
