@@ -190,11 +190,18 @@ const void* fr_evaluate_candidates(const CDataset* dataset, const CQRel* qrel, c
             if (!dev.linesearch(ev.measure, ev.depth, ev.norms.data(), groups, &means, nullptr, &err)) fr::fail_str(err);
             fr::check_flags(dev);
             std::copy(means.begin(), means.end(), out_means);
+            // Slots no candidate fills hold 0, as on the generic path below: the device matrix is a grow-only work buffer, and
+            // the kernels write only the candidates a group has, so those columns keep what an earlier, wider line search on
+            // this dataset left there.
+            for (size_t g = 0; g < n_groups; g++) std::fill(out_means + g * 64 + n_cand[g], out_means + (g + 1) * 64, 0.0);
             if (out_per_query) {
                 std::vector<double> M;
                 size_t ldm = 0;
                 if (!dev.download_last_matrix(&M, &ldm, &err)) fr::fail_str(err);
                 std::copy(M.begin(), M.end(), out_per_query);
+                for (size_t q = 0; q < dev.nq() && ldm == n_groups * 64; q++)
+                    for (size_t g = 0; g < n_groups; g++)
+                        std::fill(out_per_query + q * ldm + g * 64 + n_cand[g], out_per_query + q * ldm + (g + 1) * 64, 0.0);
             }
         } else {
             std::vector<double> w;
