@@ -365,3 +365,235 @@ def random_forest_model(seed, d=6, trees=3, depth=6, n=16, p_leaf=0.25):
         return S(f, thr, grow(dd - 1), grow(dd - 1))
 
     return [grow(depth) for _ in range(trees)], [float(w) for w in rng.uniform(-1.5, 1.5, trees)], X
+
+
+# --- models at the limits of the kernels (csrc/explain.hpp, explain.hip) ---------------------------------------------------
+# Data only: path_table / restate above stay the reference.  The constants are the headers'; tests/test_explain_host.py reads
+# them from the sources and holds these copies to them.
+
+EX_LDS_MAX = 156 * 1024  # bytes of LDS the explain kernel's one-wave workgroup may take
+EX_REG_PATH = 8          # paths of up to this many elements keep their permutation weights in registers
+EX_CHUNK_TILES = 1024    # feature importance: 64-document tiles per launch
+EX_COVER_LDS = 4096      # cover pass: a tree of up to this many leaves is counted in LDS
+EX_COVER_GRID = 256      # cover pass: at most this many workgroups of 256 documents per tree
+EX_COVER_TREES = 65535   # cover pass: trees per launch (gridDim.y)
+
+
+def lds_bytes(max_path, max_tree_feats):
+    """ex_lds_bytes of csrc/explain.hpp: W rows only when some path is longer than EX_REG_PATH"""
+    w_rows = max_path + 1 if max_path > EX_REG_PATH else 0
+    return w_rows * 64 * 8 + max_tree_feats * 64 * (8 + 4)
+
+
+def chain(n_feats):
+    """x0 <= 0 ? 0 : (x1 <= 0 ? -0.5 : ( ... : 1)): one path through n_feats distinct features"""
+    node = L(1.0)
+    for f in reversed(range(n_feats)):
+        node = S(f, 0.0, L(float(-f) * 0.5), node)
+    return node
+
+
+def balanced_tree(depth, feats, rng, extra_split=False, lo=-2.0, hi=2.0):
+    """A complete binary tree of 2^depth leaves whose levels cycle through `feats`.  Every threshold is drawn from what the
+    splits above it left of [lo, hi] for its feature, so both children can be reached; the leaves' volumes differ by orders
+    of magnitude, so a background of a few documents per leaf on average leaves many of them empty.  extra_split: one leaf
+    (drawn) is split once more, on the next feature of the cycle: 2^depth + 1 leaves."""
+    extra = int(rng.integers(0, 1 << depth)) if extra_split else -1
+    counter = [0]
+
+    def split(level, box):
+        f = feats[level % len(feats)]
+        a, b = box[f]
+        thr = float(rng.uniform(a, b))
+        return f, thr, {**box, f: (a, thr)}, {**box, f: (thr, b)}
+
+    def grow(level, box):
+        if level == depth:
+            counter[0] += 1
+            if counter[0] - 1 == extra:
+                f, thr, _, _ = split(level, box)
+                return S(f, thr, L(rng.uniform(-2, 4)), L(rng.uniform(-2, 4)))
+            return L(rng.uniform(-2, 4))
+        f, thr, left, right = split(level, box)
+        return S(f, thr, grow(level + 1, left), grow(level + 1, right))
+
+    return grow(0, {f: (float(lo), float(hi)) for f in feats})
+
+
+def _balanced_fids(depth, fids):
+    """a complete tree of 2^depth - 1 splits, numbered depth first; split k is on fids[k % len(fids)].  Thresholds and leaf
+    values are fixed patterns around 0 (no generator: the tree is a function of its arguments)."""
+    k, j = [0], [0]
+
+    def grow(level):
+        if level == depth:
+            j[0] += 1
+            return L(((j[0] * 29) % 17 - 8) * 0.25 + j[0] / 64.0)
+        at = k[0]
+        k[0] += 1
+        return S(fids[at % len(fids)], ((at * 37) % 21 - 10) / 16.0, grow(level + 1), grow(level + 1))
+
+    return grow(0)
+
+
+def wide_tree(n_feats, long_path=False):
+    """A tree that splits on exactly n_feats distinct features.  long_path=False: a complete depth-8 tree (255 splits on
+    features 0 .. n_feats-1, then repeating: n_feats <= 255), every path of at most 8 elements.  long_path=True: chain(32)
+    on features 0 .. 31, whose first node's left leaf is replaced by a complete depth-8 tree on features 32 .. n_feats-1:
+    max_path = 32, and no path with more than 32 distinct features (the subtree's have feature 0 and at most 8 more)."""
+    if not long_path:
+        assert 1 <= n_feats <= 255
+        return _balanced_fids(8, list(range(n_feats)))
+    assert 32 < n_feats <= 32 + 255
+    root = chain(32)
+    root["FeatureSplit"]["lhs"] = _balanced_fids(8, list(range(32, n_feats)))
+    return root
+
+
+def stumps(count, rng):
+    """(trees, weights): `count` trees, one split each on feature 0 or 1 with a threshold among standard-normal data, about
+    one in sixteen a bare leaf; weights of both signs, about one in eight exactly 0.0"""
+    fids = rng.integers(0, 2, count)
+    thr = rng.normal(0, 1, count)
+    vals = rng.uniform(-2, 2, (count, 2))
+    bare = rng.random(count) < 1.0 / 16
+    weights = np.where(rng.random(count) < 1.0 / 8, 0.0, rng.uniform(-1.5, 1.5, count))
+    trees = [L(vals[t, 0]) if bare[t] else S(fids[t], thr[t], L(vals[t, 0]), L(vals[t, 1])) for t in range(count)]
+    return trees, [float(w) for w in weights]
+
+
+def _stump_arrays(trees):
+    """(is a split, fid, threshold, left value or the bare leaf's, right value) per tree"""
+    split = np.array([not is_leaf(t) for t in trees])
+    fid = np.array([0 if is_leaf(t) else t["FeatureSplit"]["fid"] for t in trees])
+    thr = np.array([0.0 if is_leaf(t) else t["FeatureSplit"]["split"] for t in trees], dtype=np.float64)
+    vl = np.array([t["LeafNode"] if is_leaf(t) else t["FeatureSplit"]["lhs"]["LeafNode"] for t in trees], dtype=np.float64)
+    vr = np.array([0.0 if is_leaf(t) else t["FeatureSplit"]["rhs"]["LeafNode"] for t in trees], dtype=np.float64)
+    return split, fid, thr, vl, vr
+
+
+def predict_stumps(trees, weights, X):
+    """predict() for one-split trees and bare leaves, vectorised over the trees: the sum in tree order"""
+    split, fid, thr, vl, vr = _stump_arrays(trees)
+    val = np.repeat(vl[:, None], len(X), axis=1)
+    for f in sorted(set(fid[split].tolist())):
+        sel = split & (fid == f)
+        val[sel] = np.where(column(X, f)[None, :] <= thr[sel, None], vl[sel, None], vr[sel, None])
+    return np.cumsum(np.concatenate([np.zeros((1, len(X))), np.asarray(weights, dtype=np.float64)[:, None] * val]), axis=0)[-1]
+
+
+def restate_stumps(trees, weights, X, XB=None):
+    """(phi[n, |F|], F, bias, leaf counts) of a model of one-split trees and bare leaves, vectorised over the trees: what
+    path_table + restate give for it, by the kernel's operations on a one-element path (m = 1).  Per split tree
+        sum = 0.0 + 1.0 (W[0]);  add = (sum * (o - z)) * leaf  for the left leaf, then the right one;
+        c = (0.0 + add_lhs) + add_rhs;  phi[col] = phi[col] + w * c, trees ascending (a bare leaf adds nothing),
+    with z = the leaf's share of the background and o = the document is on the leaf's side; bias = bias + w * (rl * vl + rr * vr),
+    a bare leaf's w * v.  np.cumsum over the trees is the running sum, one addition after the other."""
+    XB = X if XB is None else XB
+    split, fid, thr, vl, vr = _stump_arrays(trees)
+    w = np.asarray(weights, dtype=np.float64)
+    feats = sorted(set(fid[split].tolist()))
+    n, nb = len(X), len(XB)
+    cl = np.zeros(len(trees), dtype=np.int64)
+    for f in feats:
+        sel = split & (fid == f)
+        cl[sel] = (column(XB, f)[None, :] <= thr[sel, None]).sum(1)
+    cr = nb - cl
+    rl, rr = np.float64(cl) / np.float64(nb), np.float64(cr) / np.float64(nb)  # (nb > 0: the background holds a document)
+    v0 = np.where(split, rl * vl + rr * vr, vl)
+    bias = np.cumsum(np.concatenate([[0.0], w * v0]))[-1]
+    phi = np.zeros((n, len(feats)))
+    for c, f in enumerate(feats):
+        sel = split & (fid == f)
+        left = (column(X, f)[None, :] <= thr[sel, None]).astype(np.float64)  # [trees, n]
+        add_l = (np.float64(1.0) * (left - rl[sel, None])) * vl[sel, None]
+        add_r = (np.float64(1.0) * ((1.0 - left) - rr[sel, None])) * vr[sel, None]
+        cc = (0.0 + add_l) + add_r
+        prod = w[sel, None] * cc
+        phi[:, c] = np.cumsum(np.concatenate([np.zeros((1, n)), prod]), axis=0)[-1]
+    counts = np.where(split[:, None], np.stack([cl, cr], 1), np.stack([np.full(len(trees), nb), np.full(len(trees), -1)], 1)).ravel()
+    return phi, feats, np.float64(bias), [int(c) for c in counts if c >= 0]
+
+
+def importance_restate(values):
+    """mean |phi| per column in the shape of explain_abs_tile_kernel / explain_abs_sum_kernel.  values[n, F]: the
+    contributions in the order of the explained document list.  Per 64-document tile a sum from 0.0 of |phi| over the lanes
+    that hold a document, in lane order (vectorised across the tiles, one addition per lane); then one running sum from 0.0
+    over the tiles, ascending (np.cumsum: one addition after the other); then / n."""
+    n, F = values.shape
+    tiles = (n + 63) // 64
+    a = np.zeros((tiles * 64, F))
+    a[:n] = np.abs(values)
+    a = a.reshape(tiles, 64, F)
+    part = np.zeros((tiles, F))
+    full = n // 64  # whole tiles; the last one, if partial, holds n - 64 * full documents
+    for j in range(64):
+        rows = tiles if j < n - 64 * full else full
+        part[:rows] = part[:rows] + a[:rows, j]
+    total = np.cumsum(np.concatenate([np.zeros((1, F)), part]), axis=0)[-1]
+    return total / np.float64(n)
+
+
+# --- the cases of the limit tests, shared by tests/test_explain_host.py (which shows that each sits where it claims) and
+# tests/test_gpu_explain.py (which holds the device to the restatement on them) ------------------------------------------------
+
+_LIMIT_CACHE = {}
+
+
+def cover_limit_case():
+    """(X[70, 4], XB[70 000, 4], {name: (trees, weights, single)}): trees on both sides of EX_COVER_LDS leaves, and a
+    background of more than EX_COVER_GRID * 256 documents (the cover pass's stride loop)"""
+    if "cover" not in _LIMIT_CACHE:
+        rng = np.random.default_rng(4096)
+        XB = rng.normal(0, 1, (70000, 4)).astype(np.float32)
+        X = rng.normal(0, 1, (70, 4)).astype(np.float32)
+        feats = [0, 1, 2, 3]
+        t4096 = balanced_tree(12, feats, rng)
+        t4097 = balanced_tree(12, feats, rng, extra_split=True)
+        other = balanced_tree(12, [2, 0, 3, 1], rng, extra_split=True)
+        models = {"leaves_4096": ([t4096], [1.0], True), "leaves_4097": ([t4097], [1.0], True),
+                  "mixed": ([S(1, 0.25, L(-1.0), L(2.0)), t4097, balanced_tree(5, feats, rng), other], [1.0, -0.5, 0.75, 0.25], False)}
+        _LIMIT_CACHE["cover"] = (X, XB, models)
+    return _LIMIT_CACHE["cover"]
+
+
+WIDE_ROWS, WIDE_COLS = 70, 212
+# wide_N: wide_tree(N); long_N: wide_tree(N, long_path=True).  The refused ones are one feature past EX_LDS_MAX.
+WIDE_FITS = ["wide_63", "wide_64", "wide_65", "wide_136", "wide_208", "wide_136_chain_9", "long_186"]
+WIDE_REFUSED = ["wide_209", "long_187"]
+
+
+def wide_case(name):
+    """(trees, weights, single) of one of the names above, over WIDE_COLS features"""
+    if name not in _LIMIT_CACHE:
+        kind, n = name.split("_")[0], int(name.split("_")[1])
+        if name == "wide_136_chain_9":
+            _LIMIT_CACHE[name] = ([wide_tree(136), chain(9)], [1.0, -0.75], False)
+        else:
+            _LIMIT_CACHE[name] = ([wide_tree(n, long_path=(kind == "long"))], [1.0], True)
+    return _LIMIT_CACHE[name]
+
+
+def wide_data():
+    if "wide_data" not in _LIMIT_CACHE:
+        _LIMIT_CACHE["wide_data"] = np.random.default_rng(212).normal(0.1, 0.5, (WIDE_ROWS, WIDE_COLS)).astype(np.float32)
+    return _LIMIT_CACHE["wide_data"]
+
+
+STUMP_TREES = EX_COVER_TREES + 1 + 3  # 65 536 is the smallest count that reaches the cover pass's second launch
+
+
+def stumps_case():
+    """(trees, weights, X[200, 2]): more trees than one launch of the cover pass takes; rows 0 .. 63 are explained"""
+    if "stumps" not in _LIMIT_CACHE:
+        rng = np.random.default_rng(65535)
+        X = rng.normal(0, 1, (200, 2)).astype(np.float32)
+        trees, weights = stumps(STUMP_TREES, rng)
+        # the trees around the launch's end split the documents, with a weight: a cover pass that skips one of them, or
+        # counts it at another tree's leaves, changes the bias and the contributions (a bare leaf's cover is never read, and
+        # a tree counted twice keeps its ratios)
+        for k, t in enumerate(range(EX_COVER_TREES - 2, EX_COVER_TREES + 3)):
+            trees[t] = S(k % 2, -0.6 + 0.3 * k, L(1.0 + k), L(-2.0 - 0.5 * k))
+            weights[t] = 0.5 + 0.25 * k
+        _LIMIT_CACHE["stumps"] = (trees, weights, X)
+    return _LIMIT_CACHE["stumps"]

@@ -1,6 +1,7 @@
 """Model explanation without a device: the numpy restatement of the algorithm
 (tests/explain_model.py) against the definition in exact rationals, on designed and seeded random small models; the path
-table the library builds against the restatement's; wire and argument errors."""
+table the library builds against the restatement's; the models of the device's limit tests shown to sit at their limits;
+wire and argument errors."""
 from fractions import Fraction
 
 import numpy as np
@@ -163,6 +164,134 @@ def test_path_limit():
     assert rep["max_path"] == 32 and rep["lds_bytes"] == 33 * 512 + 32 * 768
     with pytest.raises(Exception, match="more than 32 distinct features"):
         native.explain_table(_model([_chain(33)], [1.0], single=True), [1] * 34, 40)
+
+
+# --- the models of the device's limit tests sit where they claim (tests/test_gpu_explain.py relies on every line) ---------
+
+def test_limit_constants_are_the_sources():
+    """tests/explain_model.py's copies of the kernels' limits are what csrc/explain.hpp and explain.hip say"""
+    import os
+    import re
+
+    csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "fastrank_amd", "csrc")
+    text = open(os.path.join(csrc, "explain.hpp")).read() + open(os.path.join(csrc, "explain.hip")).read()
+
+    def const(name):
+        expr = re.search(r"constexpr\s+\w+\s+%s\s*=\s*([0-9u* ]+);" % name, text).group(1)
+        out = 1
+        for factor in expr.replace("u", "").split("*"):
+            out *= int(factor)
+        return out
+
+    for name in ("EX_LDS_MAX", "EX_REG_PATH", "EX_CHUNK_TILES", "EX_COVER_LDS", "EX_COVER_GRID"):
+        print("%s = %d" % (name, const(name)))
+        assert const(name) == getattr(em, name), name
+    assert const("EX_MAX_PATH") == em.MAX_PATH
+    assert re.search(r"t0 \+= %d\)" % em.EX_COVER_TREES, text) and em.EX_COVER_TREES == 65535  # (gridDim.y's limit)
+    assert em.EX_LDS_MAX == 159744 and em.EX_LDS_MAX > 48 * 1024
+
+
+def test_cover_limit_models():
+    X, XB, models = em.cover_limit_case()
+    assert X.shape == (70, 4) and len(XB) == 70000 and len(XB) > em.EX_COVER_GRID * 256  # the stride loop runs
+    want = {"leaves_4096": [4096], "leaves_4097": [4097], "mixed": [2, 4097, 32, 4097]}
+    for name, (trees, weights, single) in models.items():
+        leaves = [len(em.leaves_of(t)) for t in trees]
+        counts = em.leaf_counts(trees, XB)
+        tab = em.path_table(trees, weights, counts, 4)
+        zero, reached = sum(c == 0 for c in counts), sum(c > 0 for c in counts)
+        print("%s: leaves %s, max_tree_feats %d, max_path %d, LDS %d bytes; %d leaves without a background document, %d with, at most %d"
+              % (name, leaves, tab["max_tree_feats"], tab["max_path"], em.lds_bytes(tab["max_path"], tab["max_tree_feats"]), zero, reached, max(counts)))
+        assert leaves == want[name] and sum(counts) == len(XB) * len(trees)
+        assert tab["max_tree_feats"] == 4 and tab["max_path"] == 4
+        assert zero >= 500 and reached >= 1000  # many leaves of either kind: a lost or doubled count changes a ratio
+    assert em.EX_COVER_LDS == 4096  # 4096 leaves are counted in LDS, 4097 in the global counters
+    # the two large trees of the mixed model differ (other features per level, other thresholds); LDS and global alternate
+    mixed = models["mixed"][0]
+    assert [len(em.leaves_of(t)) > em.EX_COVER_LDS for t in mixed] == [False, True, False, True] and mixed[1] != mixed[3]
+    # every document the device explains reaches a leaf some background document reaches, or not: both happen
+    counts = em.leaf_counts(models["leaves_4097"][0], XB)
+    at = em.route(models["leaves_4097"][0][0], X)
+    print("explained rows at leaves with covers", sorted(counts[i] for i in at)[:5], "...")
+
+
+WIDE_EXPECTED = {  # name: (max_tree_feats, max_path, LDS bytes)
+    "wide_63": (63, 8, 48384), "wide_64": (64, 8, 49152), "wide_65": (65, 8, 49920), "wide_136": (136, 8, 104448),
+    "wide_208": (208, 8, 159744), "wide_209": (209, 8, 160512), "wide_136_chain_9": (136, 9, 10 * 512 + 104448),
+    "long_186": (186, 32, 159744), "long_187": (187, 32, 160512),
+}
+
+
+@pytest.mark.parametrize("name", em.WIDE_FITS + em.WIDE_REFUSED)
+def test_wide_models(name):
+    trees, weights, single = em.wide_case(name)
+    leaves = sum(len(em.leaves_of(t)) for t in trees)
+    counts = em.leaf_counts(trees, em.wide_data())
+    tab = em.path_table(trees, weights, counts, em.WIDE_COLS)
+    lds = em.lds_bytes(tab["max_path"], tab["max_tree_feats"])
+    print("%s: %d leaves, max_tree_feats %d, max_path %d, LDS %d bytes (48 KiB = %d, limit %d)"
+          % (name, leaves, tab["max_tree_feats"], tab["max_path"], lds, 48 * 1024, em.EX_LDS_MAX))
+    assert (tab["max_tree_feats"], tab["max_path"], lds) == WIDE_EXPECTED[name]
+    assert len(em.model_features(trees)) == WIDE_EXPECTED[name][0] and max(em.model_features(trees)) < em.WIDE_COLS
+    assert (lds <= em.EX_LDS_MAX) == (name in em.WIDE_FITS)
+    rep = native.explain_table(_model(trees, weights, single), counts, em.WIDE_COLS)
+    assert rep["lds_bytes"] == lds
+    _same_table(rep, tab)
+
+
+def test_wide_models_straddle_the_lines():
+    """64 features are the last that need no attribute (not above 48 KiB), 208 and 186 fill the limit to the byte"""
+    lds = {name: v[2] for name, v in WIDE_EXPECTED.items()}
+    assert lds["wide_63"] < lds["wide_64"] == 48 * 1024 < lds["wide_65"]
+    assert lds["wide_208"] == lds["long_186"] == em.EX_LDS_MAX and lds["wide_209"] > em.EX_LDS_MAX and lds["long_187"] > em.EX_LDS_MAX
+    # the long tree holds chain(32) whole: its last 32 leaves are the chain's, with 1, 2, .. 32, 32 elements
+    trees, weights, _ = em.wide_case("long_186")
+    tab = em.path_table(trees, weights, [1] * 288, em.WIDE_COLS)
+    assert tab["m"][256:] == list(range(2, 33)) + [32] and max(tab["m"][:256]) == 9
+
+
+def test_stumps_restatement():
+    """The vectorised restatement of one-element paths equals path_table + restate, bit for bit, on the first 200 trees
+    (and on 200 others), covers and bias included."""
+    trees, weights, X = em.stumps_case()
+    assert len(trees) == em.STUMP_TREES == 65539 and len(trees) > em.EX_COVER_TREES
+    bare = sum(em.is_leaf(t) for t in trees)
+    w = np.asarray(weights)
+    print("%d trees, %d bare leaves, weights: %d negative, %d zero, %d positive" % (len(trees), bare, (w < 0).sum(), (w == 0).sum(), (w > 0).sum()))
+    assert bare > 100 and (w < 0).sum() > 1000 and (w == 0).sum() > 1000 and (w > 0).sum() > 1000
+    # the last trees of the cover pass's first launch and the first of its second read their covers: a split with documents
+    # on both sides and a weight (a bare leaf's cover is never read, a zero weight hides the tree)
+    for t in range(em.EX_COVER_TREES - 2, em.EX_COVER_TREES + 3):
+        assert not em.is_leaf(trees[t]) and weights[t] != 0.0 and min(em.leaf_counts([trees[t]], X)) > 0, t
+    for lo in (0, 65400):
+        tt, ww = trees[lo:lo + 200], weights[lo:lo + 200]
+        assert any(em.is_leaf(t) for t in tt) and any(v == 0.0 for v in ww)
+        counts = em.leaf_counts(tt, X)
+        tab = em.path_table(tt, ww, counts, 2)
+        assert tab["max_path"] == 1 and tab["max_tree_feats"] == 1 and tab["features"] == [0, 1]
+        want = em.restate(tab, X[:64])
+        phi, feats, bias, cnt = em.restate_stumps(tt, ww, X[:64], X)
+        assert feats == tab["features"] and cnt == counts
+        assert np.array_equal(phi.view(np.uint64), want.view(np.uint64))
+        assert np.float64(bias).view(np.uint64) == np.float64(tab["bias"]).view(np.uint64)
+        assert np.array_equal(em.predict_stumps(tt, ww, X[:64]).view(np.uint64), em.predict(tt, ww, X[:64]).view(np.uint64))
+    print("max_tree_feats 1, max_path 1, LDS %d bytes" % em.lds_bytes(1, 1))
+
+
+def test_importance_restatement_is_sequential():
+    """importance_restate against the same sums written as plain loops, on a row count with a partial last tile"""
+    rng = np.random.default_rng(6)
+    for n in (64, 130, 191):
+        v = rng.normal(0, 1, (n, 3)) * 10.0 ** rng.integers(-8, 8, (n, 3))
+        total = [0.0, 0.0, 0.0]
+        for t0 in range(0, n, 64):
+            for c in range(3):
+                s = 0.0
+                for i in range(t0, min(t0 + 64, n)):
+                    s = s + abs(float(v[i, c]))
+                total[c] = total[c] + s
+        want = np.array([t / n for t in total])
+        assert np.array_equal(em.importance_restate(v).view(np.uint64), want.view(np.uint64))
 
 
 # --- errors that need no device ------------------------------------------------------------------------------------------

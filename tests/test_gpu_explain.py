@@ -1,6 +1,8 @@
 """Model explanation on the device: the bytes of fr_explain_dense against the numpy restatement
 (tests/explain_model.py) on the designed models of the host test, odd row counts, a sampled view, a separate background, a
-path at the kernel's limit and trained models; local accuracy, unused features, the reduced feature importance, refusals."""
+path at the kernel's limit and trained models; local accuracy, unused features, the reduced feature importance, refusals;
+and every limit of the three kernels from both sides: the cover pass's LDS table, grid and tree count, the contribution
+kernel's LDS size, the importance reduction's chunk boundary."""
 import math
 import os
 
@@ -43,14 +45,16 @@ def _bits(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
-def _check(model, ds, X, rows=None, bg=None, XB=None, ids=None):
+def _check(model, ds, X, rows=None, bg=None, XB=None, ids=None, counts=None, local=True):
     """Device bytes = restatement's on `rows` (indices into X; None: all), unused columns exactly 0.0, local accuracy on every
-    row.  ids: the instance ids X's rows have in `ds` (None: 0..n-1)."""
+    row.  ids: the instance ids X's rows have in `ds` (None: 0..n-1).  counts: em.leaf_counts of the background, where the
+    caller has them.  local=False: the local-accuracy ratio is printed, not held to BOUND (a model far larger than those
+    BOUND was measured on: the limit tests say which)."""
     trees, weights, single = _trees_of(model)
     ex = model.explain(ds, bg)
     ids = np.arange(len(X)) if ids is None else np.asarray(ids)
     rows = np.arange(len(X)) if rows is None else np.asarray(rows)
-    tab = em.path_table(trees, weights, em.leaf_counts(trees, X if XB is None else XB), X.shape[1])
+    tab = em.path_table(trees, weights, em.leaf_counts(trees, X if XB is None else XB) if counts is None else counts, X.shape[1])
     want = em.restate(tab, X[rows])
     got = ex.values[ids[rows]]
     feats = tab["features"]
@@ -71,7 +75,7 @@ def _check(model, ds, X, rows=None, bg=None, XB=None, ids=None):
     sc = em.scale(trees, weights)
     worst = max(abs(math.fsum(list(ex.values[i]) + [ex.expected_value]) - s) for i, s in zip(ids, scores))
     print("local accuracy: worst |sum phi + bias - f(x)| = %.3e = %.3e x scale (bound %.3e)" % (worst, worst / sc if sc else 0.0, BOUND))
-    assert worst <= BOUND * sc
+    assert not local or worst <= BOUND * sc
     return ex
 
 
@@ -82,7 +86,7 @@ def test_designed(name):
     _check(_model(trees, weights, single), _dataset(X), X, bg=bg, XB=XB)
 
 
-@pytest.mark.parametrize("n", [1, 63, 65, 257])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 128, 257])
 def test_row_counts(n):
     trees, weights, _ = em.random_forest_model(21, d=6, trees=4, depth=5, n=16)
     X = np.random.default_rng(n).normal(0, 1, (n, 6)).astype(np.float32)
@@ -136,6 +140,129 @@ def test_register_and_lds_paths():
     assert ex.status["max_path"] == 12
     ex = _check(_model([_chain(8), _chain(7)], [1.0, 0.3]), ds, X)
     assert ex.status["max_path"] == 8
+
+
+# --- the kernels' limits (tests/test_explain_host.py shows that every model below sits where it claims) ----------------------
+# Local accuracy against BOUND: BOUND is 8 x the restatement's measured error on models of at most 6 trees and 64 leaves a
+# tree.  It is kept for the wide trees (256 to 288 leaves, like the depth-8 forest of test_trained_random_forest, and the
+# chain of test_path_limit) and the small trees of the view tests; the 4096- and 4097-leaf trees and the 65 539-tree model
+# add thousands of terms to one accumulator, which no case of that measurement does: there the ratio is printed and only
+# the bytes are held.
+
+@pytest.fixture(scope="module")
+def cover_limit():
+    X, XB, _ = em.cover_limit_case()
+    return X, XB, _dataset(X), _dataset(XB, queries=700)
+
+
+@pytest.mark.parametrize("name", ["leaves_4096", "leaves_4097", "mixed"])
+def test_cover_pass_on_both_sides_of_the_lds_limit(cover_limit, name):
+    """4096 leaves are counted in LDS, 4097 in the global counters; `mixed` alternates the two over blockIdx.y.  70 000
+    background documents: more than the grid's 256 x 256, so every workgroup takes a second stretch.  The covers' reference
+    is numpy's count on the 70 000 rows: the bias and every contribution depend on all of them."""
+    X, XB, ds, bg = cover_limit
+    trees, weights, single = em.cover_limit_case()[2][name]
+    counts = em.leaf_counts(trees, XB)
+    zero, reached = sum(c == 0 for c in counts), sum(c > 0 for c in counts)
+    print("%s: %d leaves, %d without a background document, %d with" % (name, len(counts), zero, reached))
+    assert zero >= 500 and reached >= 1000 and len(XB) > em.EX_COVER_GRID * 256
+    ex = _check(_model(trees, weights, single), ds, X, bg=bg, XB=XB, counts=counts, local=False)
+    assert ex.status["leaf_paths"] == len(counts)
+
+
+def _view_rows(view):
+    return np.array(sorted(i for ids in view.instances_by_query().values() for i in ids))
+
+
+@pytest.fixture(scope="module")
+def big3():
+    X = np.random.default_rng(140).normal(0, 1, (140000, 3)).astype(np.float32)
+    ds = _dataset(X, queries=1400)
+    view = ds.subsample_queries([str(q) for q in range(1, 1401) if q % 3])  # two queries of every three
+    return X, ds, view, _view_rows(view)
+
+
+def test_cover_pass_background_is_a_sampled_view(cover_limit, big3):
+    """The background's position list with gaps: every other query of the 70 000 documents (more than half the grid's
+    reach), and two queries of three of 140 000 (more than the grid's reach: the stride loop over a list with gaps)."""
+    X, XB, ds, bg = cover_limit
+    trees, weights, _ = em.random_forest_model(25, d=4, trees=2, depth=4, n=16, p_leaf=0.1)
+    view = bg.subsample_queries([str(q) for q in range(1, 701, 2)])
+    rows = _view_rows(view)
+    assert len(rows) == 35000 and len(rows) > em.EX_COVER_GRID * 256 // 2 and np.any(np.diff(rows) > 1)
+    _check(_model(trees, weights), ds, X, bg=view, XB=XB[rows])
+    X3, _, view3, rows3 = big3
+    assert len(rows3) > em.EX_COVER_GRID * 256 and np.any(np.diff(rows3) > 1)
+    trees, weights, _ = em.random_forest_model(26, d=3, trees=2, depth=4, n=16, p_leaf=0.1)
+    _check(_model(trees, weights), _dataset(X[:, :3]), X[:, :3], bg=view3, XB=X3[rows3])
+
+
+def test_more_trees_than_one_cover_launch():
+    """65 539 trees: gridDim.y takes 65 535, so the cover pass launches twice, the second time from offset pointers.  The
+    reference is em.restate_stumps (held to path_table + restate by tests/test_explain_host.py::test_stumps_restatement)."""
+    import time
+
+    trees, weights, X = em.stumps_case()
+    assert len(trees) > em.EX_COVER_TREES
+    ds = _dataset(X)
+    model = _model(trees, weights)
+    t0 = time.perf_counter()
+    ex = model.explain(ds)
+    took = time.perf_counter() - t0
+    print("explain of 200 documents x %d trees: %.2f s (cover pass %.1f ms, kernel %.1f ms)" % (len(trees), took, ex.status["cover_ms"], ex.status["kernel_ms"]))
+    phi, feats, bias, counts = em.restate_stumps(trees, weights, X[:64], X)
+    assert feats == [0, 1] and list(ex.feature_ids) == [0, 1]
+    for c in range(2):
+        assert np.array_equal(_bits(ex.values[:64, c]), _bits(phi[:, c])), "feature %d" % c
+    assert _bits(ex.expected_value) == _bits(bias)
+    assert ex.status["trees"] == len(trees) and ex.status["leaf_paths"] == len(counts) and ex.status["max_path"] == 1
+    # local accuracy, printed (see the note above): f(x) in numpy, the sum in tree order
+    score = em.predict_stumps(trees, weights, X[:64])
+    sc = em.scale(trees, weights)
+    worst = max(abs(math.fsum(list(ex.values[i]) + [ex.expected_value]) - s) for i, s in enumerate(score))
+    print("local accuracy: worst |sum phi + bias - f(x)| = %.3e = %.3e x scale (BOUND %.3e, not asserted)" % (worst, worst / sc, BOUND))
+
+
+@pytest.fixture(scope="module")
+def wide():
+    X = em.wide_data()
+    return X, _dataset(X)
+
+
+@pytest.mark.parametrize("name", em.WIDE_FITS)
+def test_contribution_kernel_lds_sizes(wide, name):
+    """Dynamic LDS of 48 384 B (63 features), 49 152 B (64: exactly 48 KiB, the last size that needs no attribute), 49 920 B
+    (65: the first that does), 104 448 B (all 136 of MSLR), a wide tree beside W rows, and 159 744 B = the limit to the byte,
+    without W rows (208) and with all 33 of them (186 features and the 32-element chain)."""
+    X, ds = wide
+    trees, weights, single = em.wide_case(name)
+    _check(_model(trees, weights, single), ds, X)
+
+
+def test_lds_refusals_leave_nothing_behind(wide):
+    X, ds = wide
+    m208 = _model(*em.wide_case("wide_208"))
+    before = _check(m208, ds, X)
+    for name, n, need in (("wide_209", 209, 160512), ("long_187", 187, 160512)):
+        refused = _model(*em.wide_case(name))
+        what = "a tree that splits on %d distinct features needs %d bytes of LDS per wave, the explain kernel has %d" % (n, need, em.EX_LDS_MAX)
+        with pytest.raises(Exception, match=what):
+            refused.explain(ds)
+        with pytest.raises(Exception, match=what):
+            native.feature_importance(refused, ds)
+        after = m208.explain(ds)
+        assert np.array_equal(_bits(after.values), _bits(before.values)) and _bits(after.expected_value) == _bits(before.expected_value)
+
+
+def test_lds_attribute_is_set_per_call(wide):
+    # above 48 KiB, then far below it, then above again: each launch gets the LDS it asked for
+    X, ds = wide
+    m65 = _model(*em.wide_case("wide_65"))
+    small = _model([em.S(0, 0.1, em.S(1, 0.0, em.L(1.0), em.L(-2.0)), em.S(2, 0.3, em.L(0.5), em.L(4.0)))], [1.0], single=True)
+    first = _check(m65, ds, X)
+    _check(small, ds, X)
+    again = m65.explain(ds)
+    assert np.array_equal(_bits(again.values), _bits(first.values)) and _bits(again.expected_value) == _bits(first.expected_value)
 
 
 # --- trained models ------------------------------------------------------------------------------------------------------
@@ -234,6 +361,54 @@ def test_feature_importance_chunks():
     n = len(X)
     gamma = n * 2.0 ** -53 / (1 - n * 2.0 ** -53)
     assert np.all(np.abs(a - ref) <= gamma * ref) and a[2] == 0.0 and a[0] > 0.0
+
+
+def _document_order(ds):
+    """the instance ids in the order of the explained document list: positions ascending"""
+    perm = native.device_form(ds)["perm_host"]
+    return perm[perm != 0xFFFFFFFF].astype(np.int64)
+
+
+def _importance_bits(model, ds, n):
+    """feature_importance = em.importance_restate of the device's own contributions (which the tests above hold to the
+    restatement), bit for bit: a tile or a lane dropped or doubled is one part in n, inside gamma_n but not inside this"""
+    values = model.explain(ds).values
+    order = _document_order(ds)
+    assert len(order) == n and len(set(order.tolist())) == n and not np.any(np.isnan(values[order]))
+    want = em.importance_restate(values[order])
+    _, a, rep = native.feature_importance(model, ds)
+    assert rep["documents"] == n
+    print("n = %d (%d tiles, %d in the last): device %s, restated %s" % (n, (n + 63) // 64, n - (n - 1) // 64 * 64, a, want))
+    assert np.array_equal(_bits(a), _bits(want))
+    ref = np.abs(values[order]).mean(0)
+    gamma = n * 2.0 ** -53 / (1 - n * 2.0 ** -53)
+    assert np.all(np.abs(a - ref) <= gamma * ref)
+    return a
+
+
+IMPORTANCE_TREE = em.S(0, 0.0, em.S(1, 0.5, em.L(1.0), em.L(-2.0)), em.L(3.0))  # (test_feature_importance_chunks')
+
+
+@pytest.mark.parametrize("n", [65535, 65536, 65537, 65600, 131073])
+def test_feature_importance_reduction_at_the_chunk_boundary(n):
+    """One launch is 1024 tiles = 65 536 documents: a partial tile that ends the first launch, the exact boundary, one lane
+    and a partial tile in a second launch, one lane in a third."""
+    assert em.EX_CHUNK_TILES * 64 == 65536
+    X = np.random.default_rng(n).normal(0, 1, (n, 3)).astype(np.float32)
+    ds = _dataset(X, queries=600)
+    a = _importance_bits(_model([IMPORTANCE_TREE], [1.0], single=True), ds, n)
+    assert a[2] == 0.0 and a[0] > 0.0 and a[1] > 0.0
+    if n == 65600:
+        two = _model([IMPORTANCE_TREE, em.S(2, -0.25, em.L(0.5), em.S(0, 1.0, em.L(-1.5), em.L(2.5)))], [0.75, -1.25])
+        assert np.all(_importance_bits(two, ds, n) > 0.0)
+
+
+def test_feature_importance_reduction_on_a_sampled_view(big3):
+    X, ds, view, rows = big3
+    assert len(rows) > em.EX_CHUNK_TILES * 64
+    order = _document_order(view)
+    assert np.array_equal(np.sort(order), rows)
+    _importance_bits(_model([IMPORTANCE_TREE], [1.0], single=True), view, len(rows))
 
 
 # --- refusals --------------------------------------------------------------------------------------------------------------
