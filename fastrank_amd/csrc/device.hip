@@ -42,6 +42,9 @@
 //                           tables, duplicate groups, walk tiles, a view's tables
 //   linesearch_policy.hpp   (host only, no HIP) the adaptive policies of the bound-and-verify line search: routing / back-off of
 //                           tie-heavy restarts, the R-rank refresh schedule, list length, redo grid, skip counter
+//   ca_restart.hpp          (host only, no HIP; through host.hpp) the reference's coordinate ascent itself: its parameters, one
+//                           restart's search as stage / replay over scores the trainer brings back from the kernels above, the
+//                           selection over the restarts (rand64.hpp: the generator and shuffle; model.hpp: models and their wire form)
 //   forest_pack.hpp         (host only, no HIP) the three encodings of a forest the tree kernels read and their limits: the packers
 //                           for tree_ensemble_rank_kernel and tree_ensemble_lds_kernel (block shapes, try-orders), the adjacent-children
 //                           layout of the L2 walk and of permute_trees_kernel, the packed-forest cache's hash

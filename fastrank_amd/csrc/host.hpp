@@ -2,6 +2,8 @@
 // the coordinate-ascent trainer.  All arithmetic that decides a ranking runs on the device
 // (device.hip); the host keeps the reference's *sequential control semantics*
 // (src/coordinate_ascent.rs:87-254) and feeds the device batches of candidates.
+// Plain parts in headers of their own: rand64.hpp (Rand64, shuffle, sample_count), model.hpp (models, their wire form,
+// FrError and the json_* field helpers), ca_restart.hpp (CAParams, one restart's search, ca_select).
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -21,9 +23,12 @@
 #include <unordered_map>
 #include <vector>
 
+#include "ca_restart.hpp"
 #include "device.hpp"
 #include "json.hpp"
 #include "measures_host.hpp"
+#include "model.hpp"
+#include "rand64.hpp"
 
 static_assert(frmeasure::NDCG == frdev::M_NDCG && frmeasure::AP == frdev::M_AP && frmeasure::RR == frdev::M_RR &&
                   frmeasure::DCG == frdev::M_DCG && frmeasure::PRECISION == frdev::M_PRECISION && frmeasure::RECALL == frdev::M_RECALL &&
@@ -32,231 +37,7 @@ static_assert(frmeasure::NDCG == frdev::M_NDCG && frmeasure::AP == frdev::M_AP &
 
 namespace fr {
 
-using frjson::Value;
-
-// Error carried to the C boundary; `debug` is already in Rust `{:?}` form (src/ffi.rs:45-74).
-struct FrError {
-    std::string debug;
-};
-[[noreturn]] inline void fail_str(const std::string& msg) { throw FrError{frjson::rust_debug_str(msg)}; }
-[[noreturn]] inline void fail_raw(const std::string& debug) { throw FrError{debug}; }
-
-// ---------------------------------------------------------------------------------------------
-// Rand64 -- oorandom =11.1.0 (Cargo.toml:18-19), third-party, source absent from the reference
-// tree: restated from the crate's published PCG algorithm.  Seed->trajectory parity with the
-// Rust build is UNPINNED (DESIGN.md "Parity status").
-// ---------------------------------------------------------------------------------------------
-class Rand64 {
-  public:
-    explicit Rand64(uint64_t seed) {
-        state_ = 0;
-        inc_ = (default_inc() << 1) | 1;
-        (void)rand_u64();
-        state_ += (u128)seed;
-        (void)rand_u64();
-    }
-    uint64_t rand_u64() {
-        u128 old = state_;
-        state_ = old * multiplier() + inc_;
-        uint64_t xorshifted = (uint64_t)(((old >> 29) ^ old) >> 58);
-        uint32_t rot = (uint32_t)(old >> 122);
-        return (xorshifted >> rot) | (xorshifted << ((64 - rot) & 63));
-    }
-    double rand_float() {
-        uint64_t u = rand_u64() >> (64 - 54);
-        return (double)u * (1.0 / 18014398509481984.0);
-    }
-    uint64_t rand_range(uint64_t lo, uint64_t hi) {
-        uint64_t s = hi - lo;
-        u128 m = (u128)rand_u64() * (u128)s;
-        uint64_t leftover = (uint64_t)m;
-        if (leftover < s) {
-            uint64_t threshold = (0 - s) % s;
-            while (leftover < threshold) {
-                m = (u128)rand_u64() * (u128)s;
-                leftover = (uint64_t)m;
-            }
-        }
-        return (uint64_t)(m >> 64) + lo;
-    }
-
-  private:
-    typedef unsigned __int128 u128;
-    static u128 multiplier() { return (((u128)2549297995355413924ULL) << 64) | (u128)4865540595714422341ULL; }
-    static u128 default_inc() { return (((u128)0x2FE0E169FFBD06E3ULL) << 64) | (u128)0x5BC307BD4D2F814FULL; }
-    u128 state_, inc_;
-};
-
-// src/randutil.rs:21-27
-template <typename T>
-inline void shuffle(std::vector<T>& v, Rand64& rand) {
-    uint64_t n = v.size();
-    for (uint64_t i = 0; i < n; i++) {
-        uint64_t j = rand.rand_range(i, n);
-        std::swap(v[i], v[j]);
-    }
-}
-
-// sampling.rs:49-50: how many of `len` items a sampling rate keeps: max(1, (len as f64 * rate) as usize), at most len.
-// Rust's cast saturates (NaN / negative -> 0); a C++ cast of such a value is undefined behaviour.  Shared by the
-// random-forest trainer and LambdaMART's per-tree samples.
-inline size_t sample_count(size_t len, double rate) {
-    const double x = (double)len * rate;
-    const size_t c = (x != x || x <= 0.0) ? 0 : (x >= (double)len ? len : (size_t)x);
-    return std::min(len, std::max<size_t>(1, c));
-}
-
-// ---------------------------------------------------------------------------------------------
-// Models (src/model.rs:10-112) and their serde wire form
-// ---------------------------------------------------------------------------------------------
-struct TreeNode {
-    bool leaf = true;
-    double value = 0.0;  // leaf value or split threshold
-    uint32_t fid = 0;
-    std::unique_ptr<TreeNode> lhs, rhs;
-};
-
-struct Model {
-    enum Kind { SingleFeature, Linear, DecisionTree, Ensemble } kind = Linear;
-    uint32_t fid = 0;
-    double dir = 0.0;
-    std::vector<double> weights;
-    std::shared_ptr<TreeNode> tree;
-    std::vector<double> ens_weights;
-    std::vector<Model> members;
-};
-
-inline double json_f64(const Value& v, const char* what) {
-    if (!v.is_number()) fail_raw(std::string("Error(\"invalid type: expected f64 for ") + what + "\", line: 0, column: 0)");
-    return v.as_double();
-}
-inline uint64_t json_u64(const Value& v, const char* what) {
-    if (v.kind == Value::UInt) return v.u;
-    if (v.kind == Value::Int && v.i >= 0) return (uint64_t)v.i;
-    fail_raw(std::string("Error(\"invalid type: expected unsigned integer for ") + what + "\", line: 0, column: 0)");
-}
-// serde rejects integers that do not fit the field's type instead of truncating them
-inline uint32_t json_u32(const Value& v, const char* what) {
-    const uint64_t x = json_u64(v, what);
-    if (x > (uint64_t)UINT32_MAX)
-        fail_raw("Error(\"invalid value: integer `" + std::to_string(x) + "`, expected u32\", line: 0, column: 0)");
-    return (uint32_t)x;
-}
-inline bool json_bool(const Value& v, const char* what) {
-    if (v.kind != Value::Bool) fail_raw(std::string("Error(\"invalid type: expected a boolean for ") + what + "\", line: 0, column: 0)");
-    return v.b;
-}
-inline const Value& json_field(const Value& obj, const char* key) {
-    const Value* f = obj.find(key);
-    if (!f) fail_raw(std::string("Error(\"missing field `") + key + "`\", line: 0, column: 0)");
-    return *f;
-}
-// serde externally-tagged enum: {"Variant": payload}
-inline const frjson::Member& json_variant(const Value& v, const char* what) {
-    if (!v.is_object() || v.obj.size() != 1)
-        fail_raw(std::string("Error(\"expected a single-key map for enum ") + what + "\", line: 0, column: 0)");
-    return v.obj[0];
-}
-
-inline std::unique_ptr<TreeNode> tree_from_json(const Value& v) {
-    const auto& var = json_variant(v, "TreeNode");
-    auto node = std::make_unique<TreeNode>();
-    if (var.first == "LeafNode") {
-        node->leaf = true;
-        node->value = json_f64(var.second, "LeafNode");
-    } else if (var.first == "FeatureSplit") {
-        node->leaf = false;
-        node->fid = json_u32(json_field(var.second, "fid"), "fid");
-        node->value = json_f64(json_field(var.second, "split"), "split");
-        node->lhs = tree_from_json(json_field(var.second, "lhs"));
-        node->rhs = tree_from_json(json_field(var.second, "rhs"));
-    } else {
-        fail_raw("Error(\"unknown variant `" + var.first + "`, expected `FeatureSplit` or `LeafNode`\", line: 0, column: 0)");
-    }
-    return node;
-}
-
-inline Value tree_to_json(const TreeNode& n) {
-    Value v = Value::object();
-    if (n.leaf) {
-        v.set("LeafNode", Value::number(n.value));
-    } else {
-        Value fs = Value::object();
-        fs.set("fid", Value::uint(n.fid));
-        fs.set("split", Value::number(n.value));
-        fs.set("lhs", tree_to_json(*n.lhs));
-        fs.set("rhs", tree_to_json(*n.rhs));
-        v.set("FeatureSplit", std::move(fs));
-    }
-    return v;
-}
-
-inline Model model_from_json(const Value& v) {
-    const auto& var = json_variant(v, "ModelEnum");
-    Model m;
-    if (var.first == "Linear") {
-        m.kind = Model::Linear;
-        const Value& w = json_field(var.second, "weights");
-        if (!w.is_array()) fail_raw("Error(\"invalid type: expected a sequence for weights\", line: 0, column: 0)");
-        for (const auto& x : w.arr) m.weights.push_back(json_f64(x, "weights"));
-    } else if (var.first == "SingleFeature") {
-        m.kind = Model::SingleFeature;
-        m.fid = json_u32(json_field(var.second, "fid"), "fid");
-        m.dir = json_f64(json_field(var.second, "dir"), "dir");
-    } else if (var.first == "DecisionTree") {
-        m.kind = Model::DecisionTree;
-        m.tree = std::shared_ptr<TreeNode>(tree_from_json(var.second).release());
-    } else if (var.first == "Ensemble") {
-        m.kind = Model::Ensemble;
-        const Value& w = json_field(var.second, "weights");
-        const Value& ms = json_field(var.second, "models");
-        if (!w.is_array() || !ms.is_array())
-            fail_raw("Error(\"invalid type: expected sequences in Ensemble\", line: 0, column: 0)");
-        for (const auto& x : w.arr) m.ens_weights.push_back(json_f64(x, "weights"));
-        for (const auto& x : ms.arr) m.members.push_back(model_from_json(x));
-    } else {
-        fail_raw("Error(\"unknown variant `" + var.first +
-                 "`, expected one of `SingleFeature`, `Linear`, `DecisionTree`, `Ensemble`\", line: 0, column: 0)");
-    }
-    return m;
-}
-
-inline Value model_to_json(const Model& m) {
-    Value v = Value::object();
-    switch (m.kind) {
-        case Model::Linear: {
-            Value inner = Value::object();
-            Value w = Value::array();
-            for (double x : m.weights) w.push(Value::number(x));
-            inner.set("weights", std::move(w));
-            v.set("Linear", std::move(inner));
-            break;
-        }
-        case Model::SingleFeature: {
-            Value inner = Value::object();
-            inner.set("fid", Value::uint(m.fid));
-            inner.set("dir", Value::number(m.dir));
-            v.set("SingleFeature", std::move(inner));
-            break;
-        }
-        case Model::DecisionTree:
-            v.set("DecisionTree", tree_to_json(*m.tree));
-            break;
-        case Model::Ensemble: {
-            Value inner = Value::object();
-            Value w = Value::array();
-            for (double x : m.ens_weights) w.push(Value::number(x));
-            Value ms = Value::array();
-            for (const auto& mm : m.members) ms.push(model_to_json(mm));
-            inner.set("weights", std::move(w));
-            inner.set("models", std::move(ms));
-            v.set("Ensemble", std::move(inner));
-            break;
-        }
-    }
-    return v;
-}
-
+// a tree (model.hpp) as the arrays the scoring kernels walk; returns its root's index
 inline int32_t flatten_tree(const TreeNode& n, frdev::FlatTrees& out) {
     int32_t idx = (int32_t)out.fid.size();
     out.fid.push_back(-1);
@@ -759,62 +540,8 @@ inline void score_model(DatasetView& view, const Model& m, frdev::DeviceDataset*
 }
 
 // ---------------------------------------------------------------------------------------------
-// Coordinate ascent (src/coordinate_ascent.rs)
+// Coordinate ascent (src/coordinate_ascent.rs): the reference's own logic is ca_restart.hpp; here, what runs it on the device
 // ---------------------------------------------------------------------------------------------
-struct CAParams {
-    uint32_t num_restarts = 5;
-    uint32_t num_max_iterations = 25;
-    double step_base = 0.05;
-    double step_scale = 2.0;
-    double tolerance = 0.001;
-    uint64_t seed = 0;
-    bool normalize = true;
-    bool quiet = false;
-    bool init_random = true;
-    bool output_ensemble = false;
-
-    static CAParams defaults() {
-        CAParams p;
-        Rand64 rand(0xdeadbeefULL);
-        p.seed = rand.rand_u64();  // coordinate_ascent.rs:27,34
-        return p;
-    }
-    static CAParams from_json(const Value& v) {
-        CAParams p;
-        p.num_restarts = json_u32(json_field(v, "num_restarts"), "num_restarts");
-        p.num_max_iterations = json_u32(json_field(v, "num_max_iterations"), "num_max_iterations");
-        p.step_base = json_f64(json_field(v, "step_base"), "step_base");
-        p.step_scale = json_f64(json_field(v, "step_scale"), "step_scale");
-        p.tolerance = json_f64(json_field(v, "tolerance"), "tolerance");
-        p.seed = json_u64(json_field(v, "seed"), "seed");
-        p.normalize = json_bool(json_field(v, "normalize"), "normalize");
-        p.quiet = json_bool(json_field(v, "quiet"), "quiet");
-        p.init_random = json_bool(json_field(v, "init_random"), "init_random");
-        p.output_ensemble = json_bool(json_field(v, "output_ensemble"), "output_ensemble");
-        return p;
-    }
-    Value to_json() const {
-        Value o = Value::object();
-        o.set("num_restarts", Value::uint(num_restarts));
-        o.set("num_max_iterations", Value::uint(num_max_iterations));
-        o.set("step_base", Value::number(step_base));
-        o.set("step_scale", Value::number(step_scale));
-        o.set("tolerance", Value::number(tolerance));
-        o.set("seed", Value::uint(seed));
-        o.set("normalize", Value::boolean(normalize));
-        o.set("quiet", Value::boolean(quiet));
-        o.set("init_random", Value::boolean(init_random));
-        o.set("output_ensemble", Value::boolean(output_ensemble));
-        return o;
-    }
-};
-
-struct RestartResult {
-    uint32_t restart_id = 0;
-    double score = 0.0;
-    std::vector<double> weights;
-};
-
 // The exchange records of the job's one all-gather (src/coordinate_ascent.rs:232-252 selects from them): a
 // rank's restarts as a fixed-size block of `cap` records of 3 + d doubles -- valid (1.0 / 0.0 padding), restart id, score,
 // weights[d] -- the same layout native.gather_restarts puts through torch.distributed and rccl_allgather puts through RCCL.
@@ -882,61 +609,38 @@ struct TrainStats {
 
 // adds the exact-only line searches of a scope to the trainer's statistics (also when the scope unwinds)
 struct ExactTickCount {
+    // the dataset's running counters (they count over every trainer it has had) at one moment
+    struct Snapshot {
+        unsigned long long exact = 0, audit_values = 0, audit_mismatches = 0, exact_groups = 0, redo_entries = 0, chain_runs = 0,
+                           chain_visits = 0, slots_on = 0, slots_off = 0;
+        explicit Snapshot(const frdev::DeviceDataset& d) : exact(d.exact_fallbacks()) {
+            d.audit_counters(&audit_values, &audit_mismatches);
+            d.routing_counters(&exact_groups, &redo_entries);
+            d.chain_counters(&chain_runs, &chain_visits, &slots_on, &slots_off);
+        }
+    };
     frdev::DeviceDataset& dev;
     TrainStats& st;
-    unsigned long long base, av0 = 0, am0 = 0, eg0 = 0, re0 = 0, cr0 = 0, cv0 = 0, on0 = 0, off0 = 0;
-    ExactTickCount(frdev::DeviceDataset& d, TrainStats& s) : dev(d), st(s), base(d.exact_fallbacks()) {
-        d.audit_counters(&av0, &am0);
-        d.routing_counters(&eg0, &re0);
-        d.chain_counters(&cr0, &cv0, &on0, &off0);
-    }
+    const Snapshot at0;
+    ExactTickCount(frdev::DeviceDataset& d, TrainStats& s) : dev(d), st(s), at0(d) {}
     ~ExactTickCount() {
-        unsigned long long av1 = 0, am1 = 0, eg1 = 0, re1 = 0, cr1 = 0, cv1 = 0, on1 = 0, off1 = 0;
-        dev.audit_counters(&av1, &am1);
-        dev.routing_counters(&eg1, &re1);
-        dev.chain_counters(&cr1, &cv1, &on1, &off1);
-        st.rank_slots_on += on1 - on0;
-        st.rank_slots_off += off1 - off0;
-        st.chain_runs += cr1 - cr0;
-        st.chain_visits += cv1 - cv0;
-        st.exact_groups += eg1 - eg0;
-        st.verify_redo_entries += re1 - re0;
-        st.exact_ticks += dev.exact_fallbacks() - base;
-        st.audit_values += av1 - av0;
-        st.audit_mismatches += am1 - am0;
+        const Snapshot at1(dev);
+        st.rank_slots_on += at1.slots_on - at0.slots_on;
+        st.rank_slots_off += at1.slots_off - at0.slots_off;
+        st.chain_runs += at1.chain_runs - at0.chain_runs;
+        st.chain_visits += at1.chain_visits - at0.chain_visits;
+        st.exact_groups += at1.exact_groups - at0.exact_groups;
+        st.verify_redo_entries += at1.redo_entries - at0.redo_entries;
+        st.exact_ticks += at1.exact - at0.exact;
+        st.audit_values += at1.audit_values - at0.audit_values;
+        st.audit_mismatches += at1.audit_mismatches - at0.audit_mismatches;
     }
 };
 
-// coordinate_ascent.rs:72-82
-inline void l1_normalize(std::vector<double>& w) {
-    double sum = 0.0;
-    for (double x : w) sum += std::fabs(x);
-    if (sum > 0.0)
-        for (double& x : w) x /= sum;
-}
-
-// Candidate weights of one line search in evaluation order (coordinate_ascent.rs:145-171):
-// block 0 = dir 0 (1 candidate), block 1 = dir -1, block 2 = dir +1.
-inline void line_candidates(double orig, const CAParams& p, std::vector<double>& out, uint32_t block_len[3]) {
-    static const int SIGN[3] = {0, -1, 1};
-    out.clear();
-    for (int s = 0; s < 3; s++) {
-        double dir = (double)SIGN[s];
-        double step = p.step_base * dir;
-        if (orig != 0.0 && std::fabs(step) > 0.5 * std::fabs(orig)) step = p.step_base * std::fabs(orig) * dir;
-        double total = step;
-        uint32_t iters = p.num_max_iterations;
-        if (SIGN[s] == 0) {
-            iters = 1;
-            total = -orig;
-        }
-        block_len[s] = iters;
-        for (uint32_t it = 0; it < iters; it++) {
-            out.push_back(orig + total);
-            step *= p.step_scale;
-            total += step;
-        }
-    }
+// weight vectors one score_linear call may take: the score scratch (8 bytes per padded document and vector) stays within ~2 GiB
+inline size_t score_chunk(const frdev::DeviceDataset& dev) {
+    const size_t ld = (dev.n() + 63) / 64 * 64;
+    return std::max<size_t>(1, std::min<size_t>(512, (size_t(2) << 30) / (ld * sizeof(double))));
 }
 
 // Batched evaluate_mean of arbitrary weight vectors through the general sort path.
@@ -947,9 +651,7 @@ inline void evaluate_means_generic(frdev::DeviceDataset& dev, const Evaluator& e
     means.assign(B, 0.0);
     if (per_query) per_query->assign(dev.nq() * B, 0.0);
     std::vector<double> rows;
-    // bound the score scratch to ~2 GiB
-    size_t ld = (dev.n() + 63) / 64 * 64;
-    size_t chunk = std::max<size_t>(1, std::min<size_t>(512, (size_t(2) << 30) / (ld * sizeof(double))));
+    const size_t chunk = score_chunk(dev);
     for (size_t b0 = 0; b0 < B; b0 += chunk) {
         size_t bn = std::min(chunk, B - b0);
         std::string _err;
@@ -1095,20 +797,15 @@ class CATrainer {
         if (!build_groups(-1, groups_, &gen_B)) return false;
         stats_.line_searches++;
         dev.set_sums_only((bool)shard_.allreduce);  // the dataset object may be shared with other callers
+        frdev::DeviceDataset::LsCounts cnt;
         if (path_ != LS_NONE) {
             std::string _err;
-            frdev::DeviceDataset::LsCounts cnt;
             if (!dev.linesearch(ev_.measure, ev_.depth, ev_.norms.data(), groups_, &means_, &cnt, &_err)) fail_str(_err);
-            stats_.verify_pairs += cnt.pairs;
-            stats_.verify_redone += cnt.redone;
-            check_flags(dev);
         } else {
             evaluate_means_generic(dev, ev_, gen_w_, gen_B, means_);
         }
-        global_means(means_);
+        collected(dev, -1, cnt, path_ != LS_NONE ? groups_.size() : gen_B, means_);
         stats_.ticks++;
-        stats_.groups += path_ != LS_NONE ? groups_.size() : gen_B;
-        apply_results(-1, means_);
         return true;
     }
 
@@ -1182,14 +879,7 @@ class CATrainer {
                             std::string _err;
                             if (!dev.linesearch_collect(h, &means_h_[h], &cnt, &_err)) fail_str(_err);
                         }
-                        stats_.verify_pairs += cnt.pairs;
-                        stats_.verify_redone += cnt.redone;
-                        check_flags(dev);
-                        stats_.groups += groups_h_[h].size();
-                        {
-                            HostTimer ht_(host_us_[2]);
-                            apply_results(h, means_h_[h]);
-                        }
+                        collected(dev, h, cnt, groups_h_[h].size(), means_h_[h]);
                         host_calls_++;
                         steps[h]++;
                         if (newly_done_ > 0) done_wait_++;
@@ -1246,9 +936,20 @@ class CATrainer {
         return k >= R * (size_t)part / P && k < R * ((size_t)part + 1) / P;
     }
 
-    // Stages the next line search of every live restart of the half: shuffles at the start of a pass
-    // (coordinate_ascent.rs:113-116), normalises (:131-143), lists the candidates (:145-171).  Returns false when
-    // the half has no live restart.
+    // What follows a line search's results in tick() and run() alike: its counts, the device's flags, the replay.
+    void collected(frdev::DeviceDataset& dev, int part, const frdev::DeviceDataset::LsCounts& cnt, size_t n_groups, std::vector<double>& means) {
+        stats_.verify_pairs += cnt.pairs;
+        stats_.verify_redone += cnt.redone;
+        check_flags(dev);
+        global_means(means);
+        stats_.groups += n_groups;
+        HostTimer ht_(host_us_[2]);
+        apply_results(part, means);
+    }
+
+    // Stages the next line search of every live restart of the part (CARestart::stage) as the device takes it: groups of
+    // 64 candidates with the restart's resident fields, or whole weight vectors for the general path.  Returns false when
+    // the part has no live restart.
     bool build_groups(int part, std::vector<frdev::LineGroup>& groups, size_t* gen_B_out) {
         groups.clear();
         gen_w_.clear();
@@ -1264,27 +965,11 @@ class CATrainer {
             Restart& r = rs_[k];
             if (r.done || !in_part(k, part)) continue;
             any = true;
-            if (r.pos == 0 && r.order.empty()) {
-                r.order = fids_;
-                shuffle(r.order, r.rand);  // :113-116
-                r.successes = 0;
-                if (!p_.quiet)
-                    printf("[restart %u] shuffle features and optimize (%s=%.6f)\n", r.id, ev_.name.c_str(), r.best_score);
-            }
-            uint32_t f = r.order[r.pos];
-            r.start_score = r.best_score;
-            r.base = r.best_w;
-            r.norm = 1.0;
-            if (p_.normalize) {  // l1_normalize (entries >= model_dim are 0 and stay 0), keeping the divisor
-                double sum = 0.0;
-                for (double x : r.base) sum += std::fabs(x);
-                if (sum > 0.0) {
-                    for (double& x : r.base) x /= sum;
-                    r.norm = sum;
-                }
-            }
-            double orig = r.base[f];
-            line_candidates(orig, p_, r.cands, r.block_len);
+            const CARestart::Staged st = r.stage(fids_, p_);
+            if (st.new_pass && !p_.quiet)
+                printf("[restart %u] shuffle features and optimize (%s=%.6f)\n", r.id, ev_.name.c_str(), r.best_score);
+            const uint32_t f = st.feature;
+            const double orig = r.base[f];
             if (path_ != LS_NONE) {
                 r.first_group = groups.size();
                 for (size_t c0 = 0; c0 < r.cands.size(); c0 += 64) {
@@ -1323,59 +1008,36 @@ class CATrainer {
         return any;
     }
 
-    // Replays coordinate_ascent.rs:145-186 over the batched results of the half's line searches.
+    // Hands every live restart of the part the means of its staged line search (CARestart::replay), from where the device
+    // put them, and lets the resident bookkeeping follow what was accepted.
     void apply_results(int part, const std::vector<double>& means) {
         frdev::DeviceDataset& dev = view_->device(slot_, device_);
         for (size_t k = 0; k < rs_.size(); k++) {
             Restart& r = rs_[k];
             if (r.done || !in_part(k, part)) continue;
-            uint32_t f = r.order[r.pos];
-            size_t c = 0;
-            long accepted = -1;  // index of the last accepted candidate of this line search
-            for (int s = 0; s < 3; s++) {
-                for (uint32_t it = 0; it < r.block_len[s]; it++, c++) {
-                    double sc = path_ != LS_NONE ? means[(r.first_group + c / 64) * 64 + (c % 64)]
-                                                      : means[r.first_group + c];
-                    stats_.useful_evals++;
-                    if (sc == sc && sc > r.best_score) {  // core.rs:57-66: NaN rejected, strict >
-                        r.best_score = sc;
-                        r.best_w = r.base;
-                        r.best_w[f] = r.cands[c];
-                        accepted = (long)c;
-                        if (!p_.quiet)
-                            printf("%4u|%-16s|%9.3f|%9.3f\n", r.id, view_->core->feature_name(f).c_str(), r.cands[c], sc);
-                    }
-                }
-                if (r.best_score - r.start_score > p_.tolerance) break;  // :174
-            }
+            const uint32_t f = r.feature();
+            const double* m = means.data() + (path_ != LS_NONE ? r.first_group * 64 : r.first_group);  // (a group's 64 places follow each other)
+            const CARestart::Replayed rep = r.replay(p_, [m](size_t c) { return m[c]; });
+            stats_.useful_evals += rep.evaluated;
             stats_.raw_evals += r.cands.size();
-            if (resident_ && accepted >= 0) {
+            if (!p_.quiet)
+                for (const CARestart::Accepted& a : r.accepted)
+                    printf("%4u|%-16s|%9.3f|%9.3f\n", r.id, view_->core->feature_name(f).c_str(), r.cands[a.cand], a.score);
+            if (resident_ && !r.accepted.empty()) {
                 // best_w became base with [f] = cand: the resident sum follows on the device at the next visit,
                 //   R' = fma(x_f, cand, fma(-x_f, base_f, R * (1/norm)))  ~  sum_j x_j * best_w'_j,
                 // and its error bound follows here: the old one shrinks by 1/norm, the reciprocal, the two products
                 // and the two roundings add at most 8 u * T (T = sum_j |x_j best_w'_j| + |x_f base_f|, via column maxima)
                 const std::vector<double>& X = dev.column_absmax();
-                double T = std::fabs(r.base[f]) * X[f];
-                for (size_t j = 0; j < d_; j++) T += std::fabs(r.best_w[j]) * X[j];
-                r.res_err = frdev::resident_err_update(r.res_err, r.norm, T);
+                r.res_err = frdev::resident_err_update(r.res_err, r.norm, abs_weighted_sum(r.best_w, X, std::fabs(r.base[f]) * X[f]));
                 r.res_updates++;
                 r.pend = true;
                 r.pend_f = f;
                 r.pend_norm = r.norm;
                 r.pend_base_f = r.base[f];
-                r.pend_cand = r.cands[(size_t)accepted];
+                r.pend_cand = r.cands[r.accepted.back().cand];
             }
-            if (r.best_score - r.start_score > p_.tolerance) r.successes++;  // :179-182
-            r.pos++;
-            if (r.pos == r.order.size()) {
-                if (r.successes == 0) {
-                    r.done = true;  // :185
-                    newly_done_++;
-                } else {
-                    r.pos = 0;
-                    r.order.clear();
-                }
-            }
+            if (rep.finished) newly_done_++;
         }
     }
 
@@ -1410,12 +1072,7 @@ class CATrainer {
         std::vector<double> w0(R * d_, 0.0);
         for (size_t i = 0; i < R; i++) {
             Restart& r = rs_[which[i]];
-            r.best_w.assign(d_, 0.0);
-            if (p_.init_random) {
-                for (uint32_t f : fids_) r.best_w[f] = r.rand.rand_float() * 2.0 - 1.0;  // :50-54
-            } else {
-                for (uint32_t f : fids_) r.best_w[f] = 1.0 / (double)fids_.size();  // :60-70
-            }
+            r.init_weights(fids_, d_, p_.init_random);
             std::copy(r.best_w.begin(), r.best_w.end(), w0.begin() + i * d_);
         }
         std::vector<double> means;
@@ -1437,8 +1094,7 @@ class CATrainer {
     void refresh_resident(const std::vector<size_t>& which) {
         frdev::DeviceDataset& dev = view_->device(slot_, device_);
         const std::vector<double>& X = dev.column_absmax();
-        const size_t ld = (dev.n() + 63) / 64 * 64;
-        const size_t chunk = std::max<size_t>(1, std::min<size_t>(512, (size_t(2) << 30) / (ld * sizeof(double))));
+        const size_t chunk = score_chunk(dev);
         std::vector<double> w;
         for (size_t b0 = 0; b0 < which.size(); b0 += chunk) {
             const size_t bn = std::min(chunk, which.size() - b0);
@@ -1453,9 +1109,7 @@ class CATrainer {
                     resident_ = false;  // another trainer took the buffers over: form the sums from the tiles from now on
                     return;
                 }
-                double T = 0.0;
-                for (size_t j = 0; j < d_; j++) T += std::fabs(r.best_w[j]) * X[j];
-                r.res_err = frdev::resident_err_refresh((uint32_t)d_, T);  // gamma_D * T of an ordered sum
+                r.res_err = frdev::resident_err_refresh((uint32_t)d_, abs_weighted_sum(r.best_w, X));  // gamma_D * T of an ordered sum
                 r.res_updates = 0;
                 r.pend = false;
             }
@@ -1468,30 +1122,23 @@ class CATrainer {
         const double q = (double)shard_.total_queries;
         for (double& x : v) x = shard_.total_queries ? x / q : 0.0;
     }
-    struct Restart {
-        uint32_t id;
-        Rand64 rand;
-        std::vector<double> best_w;  // length d (entries >= model_dim stay 0)
-        double best_score = 0.0;
-        std::vector<uint32_t> order;
-        size_t pos = 0;
-        size_t successes = 0;
-        bool done = false;
-        // current line search
-        std::vector<double> base;
-        std::vector<double> cands;
-        uint32_t block_len[3] = {0, 0, 0};
-        size_t first_group = 0;
-        double start_score = 0.0;
+    // T = t0 + sum_j |w_j| X_j, added in feature order (X: the column maxima): what a resident sum's error bound is taken over
+    static double abs_weighted_sum(const std::vector<double>& w, const std::vector<double>& X, double t0 = 0.0) {
+        double T = t0;
+        for (size_t j = 0; j < w.size(); j++) T += std::fabs(w[j]) * X[j];
+        return T;
+    }
+    // a restart's search (ca_restart.hpp) and what the device side keeps for it
+    struct Restart : CARestart {
+        using CARestart::CARestart;
+        size_t first_group = 0;  // of the staged line search: its first group (general path: its first weight vector)
         // resident base sum of this restart on the device (see the constructor)
         int slot = -1;
-        double norm = 1.0;         // l1 norm the current base was divided by
         double res_err = 0.0;      // bound on |R - sum_j x_j best_w_j| over all documents (incl. a pending update)
         uint32_t res_updates = 0;  // incremental updates since the last exact refresh
         bool pend = false;         // best_w changed last tick: the device still has to update R
         uint32_t pend_f = 0;
         double pend_norm = 1.0, pend_base_f = 0.0, pend_cand = 0.0;
-        Restart(uint32_t i, uint64_t seed) : id(i), rand(seed) {}
     };
     std::shared_ptr<DatasetView> view_;
     Evaluator ev_;
@@ -1527,30 +1174,5 @@ class CATrainer {
     std::vector<double> gen_w_, means_;
     TrainStats stats_;
 };
-
-// coordinate_ascent.rs:232-252 selection over a restart-ordered history
-inline Model ca_select(const std::vector<RestartResult>& hist, bool output_ensemble) {
-    if (hist.empty()) fail_str("Should be at least 1 restart!");
-    if (output_ensemble && hist.size() > 1) {
-        Model ens;
-        ens.kind = Model::Ensemble;
-        for (const auto& h : hist) {
-            Model lin;
-            lin.kind = Model::Linear;
-            lin.weights = h.weights;
-            l1_normalize(lin.weights);
-            ens.ens_weights.push_back(h.score);
-            ens.members.push_back(std::move(lin));
-        }
-        return ens;
-    }
-    size_t best = 0;
-    for (size_t k = 0; k < hist.size(); k++)
-        if (hist[k].score >= hist[best].score) best = k;  // Iterator::max = last maximum
-    Model lin;
-    lin.kind = Model::Linear;
-    lin.weights = hist[best].weights;
-    return lin;
-}
 
 }  // namespace fr

@@ -141,7 +141,7 @@ class RFTrainer {
         std::sort(queries_.begin(), queries_.end(), [&](uint32_t a, uint32_t b) {
             return core.qnames[view_->csr_query[a]] < core.qnames[view_->csr_query[b]];
         });
-        // sampling.rs:49-50 (host.hpp: sample_count), then take(n) from a list of len items
+        // sampling.rs:49-50 (rand64.hpp: sample_count), then take(n) from a list of len items
         n_features_ = sample_count(features_.size(), p_.feature_sampling_rate);
         n_queries_ = sample_count(queries_.size(), p_.instance_sampling_rate);
         if (features_.empty()) fail_str("assertion failed: !features.is_empty()");

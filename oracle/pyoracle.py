@@ -102,6 +102,11 @@ def lib():
     L.oracle_check_div_identity.argtypes = [C.c_int]
     L.oracle_rand64_stream.argtypes = [u64, sz, vp]
     L.oracle_shuffle_with_seed.argtypes = [u64, vp, sz]
+    L.oracle_rand64_new.argtypes = [vp, u64]
+    L.oracle_rand64_float.restype = dbl
+    L.oracle_rand64_float.argtypes = [vp]
+    L.oracle_rand64_range.restype = u64
+    L.oracle_rand64_range.argtypes = [vp, u64, u64]
     L.oracle_rf_learn.restype = i64
     L.oracle_rf_learn.argtypes = [vp, C.POINTER(RFParams), C.c_int, i64, vp, vp, sz, vp, vp, vp, vp, sz, vp, vp, vp]
     L.oracle_resident_update.restype = None
@@ -379,6 +384,21 @@ def rand64_stream(seed, n):
     out = np.zeros(n, dtype=np.uint64)
     lib().oracle_rand64_stream(seed, n, _p(out))
     return out
+
+
+class Rand64:
+    """One generator of the oracle's (oracle_rand64: two 128-bit words, held here at a 16-byte boundary)."""
+
+    def __init__(self, seed):
+        self._mem = C.create_string_buffer(48)
+        self._p = C.c_void_p((C.addressof(self._mem) + 15) & ~15)
+        lib().oracle_rand64_new(self._p, int(seed))
+
+    def rand_float(self):
+        return float(lib().oracle_rand64_float(self._p))
+
+    def rand_range(self, lo, hi):
+        return int(lib().oracle_rand64_range(self._p, int(lo), int(hi)))
 
 
 def shuffle_with_seed(seed, n):

@@ -1678,6 +1678,48 @@ def test_randomised_parity_soak():
     assert json.loads(last)["mismatches"] == 0
 
 
+_PRINTED_TRAINING = """
+import sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+import fastrank_amd as fr
+d = np.load(sys.argv[2])
+g = fr.CDataset.from_numpy(d["train_X"], d["train_y"], d["train_qid"])
+req = fr.TrainRequest.coordinate_ascent()
+req.measure = "ndcg@5"
+p = req.params
+p.seed, p.quiet, p.num_restarts, p.num_max_iterations = 42, False, 4, 3
+g.train_model(req)
+"""
+
+
+def printed_training_output(pipeline):
+    """stdout of a fresh process that trains 4 restarts on the trec example with quiet=false on one device (NDCG@5,
+    num_max_iterations=3); pipeline: a value for FR_LS_PIPELINE, or None for the default."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, FR_DEVICES="0")
+    env.pop("FR_LS_PIPELINE", None)
+    if pipeline is not None:
+        env["FR_LS_PIPELINE"] = pipeline
+    out = subprocess.run([sys.executable, "-c", _PRINTED_TRAINING, root, os.path.join(GOLDEN, "trec_news_2018.npz")],
+                         stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=600)
+    assert out.returncode == 0, out.stderr.decode()[-2000:]
+    return out.stdout
+
+
+@pytest.mark.parametrize("pipeline,recording", [(None, "ca_printed_pipelined.txt"), ("0", "ca_printed_lockstep.txt")])
+def test_printed_training_lines_are_the_recorded_ones(pipeline, recording):
+    """With quiet=false the trainer prints `[restart r] shuffle features and optimize (..)` at the start of every pass and
+    `id|feature|weight|score` for every accepted candidate (coordinate_ascent.rs:117-124, :160-168).  The recordings under
+    tests/golden/ are the whole stdout of such a run, stepped as pipelined sets and in plain lock step: every byte, in order."""
+    with open(os.path.join(GOLDEN, recording), "rb") as fh:
+        expected = fh.read()
+    assert expected.count(b"shuffle features and optimize") >= 4 and expected.count(b"|") >= 3 * 4
+    assert printed_training_output(pipeline) == expected
+
+
 def test_sampled_views_share_the_parents_matrix_and_match_the_oracle(monkeypatch):
     """dataset_query_sampling / dataset_feature_sampling views do not tile a second copy of X:
     a query sample owns only query / run tables over the parent's tiles -- its runs start wherever its first query
