@@ -114,6 +114,8 @@ def _load():
         "fr_debug_hist_reg_term": (vp, [C.c_int64, C.c_int64, C.c_uint32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double,
                                         C.c_int32, C.c_double, C.c_double, C.c_double, vp, vp]),
         "fr_debug_lambda_gradients_opts": (vp, [vp, vp, vp, C.c_char_p, C.c_double, vp, sz, C.c_char_p, vp, vp, sz]),
+        "fr_debug_weighted_gram": (vp, [vp, vp, vp, sz, vp, sz, vp, vp, sz]),
+        "fr_debug_newton_step": (vp, [vp, vp, sz, C.c_double, vp]),
         "fr_evaluate_dense": (vp, [vp, vp, vp, C.c_char_p, vp, sz, C.POINTER(vp)]),
         "fr_rank_order": (vp, [vp, vp, vp, sz, vp, sz]),
         "fr_dataset_num_queries": (sz, [vp]),

@@ -17,6 +17,7 @@
 #include "permute_host.hpp"
 #include "forest_pack.hpp"
 #include "lambdamart.hpp"
+#include "linear_lambda.hpp"
 #include "rf_train.hpp"
 #include "verify_end.hpp"
 
@@ -44,6 +45,7 @@ struct CQRel {
 #include "capi_permute.inc"
 #include "capi_debug.inc"
 #include "capi_debug_trees.inc"
+#include "train_linear_lambda.inc"
 
 namespace {
 
@@ -248,7 +250,7 @@ const void* query_json(const void* json_cmd_str) {
     return json_call([&]() {
         std::string cmd = accept_str("query_json_str", json_cmd_str);
         // src/ffi.rs:215-236
-        if (cmd == "coordinate_ascent_defaults" || cmd == "random_forest_defaults" || cmd == "lambdamart_defaults") {
+        if (cmd == "coordinate_ascent_defaults" || cmd == "random_forest_defaults" || cmd == "lambdamart_defaults" || cmd == "linear_lambdarank_defaults") {
             Value o = Value::object();
             o.set("measure", Value::string("ndcg"));
             Value params = Value::object();
@@ -256,6 +258,8 @@ const void* query_json(const void* json_cmd_str) {
                 params.set("CoordinateAscent", fr::CAParams::defaults().to_json());
             else if (cmd == "lambdamart_defaults")
                 params.set("LambdaMART", fr::LambdaMARTParams().to_json());
+            else if (cmd == "linear_lambdarank_defaults")
+                params.set("LinearLambdaRank", fr::LinearLambdaRankParams().to_json());
             else
                 params.set("RandomForest", random_forest_defaults_json());
             o.set("params", std::move(params));
@@ -300,6 +304,7 @@ const CResult* train_model(void* train_request_json, void* dataset) {
             switch (rq.learner) {
                 case Learner::CoordinateAscent: return train_ca_devices(ds.view, rq);
                 case Learner::RandomForest: return train_rf(ds.view, rq);
+                case Learner::LinearLambdaRank: return train_linear_lambdarank(ds.view, rq);
                 case Learner::LambdaMART: break;
             }
             return train_lambdamart(ds.view, rq);

@@ -38,6 +38,9 @@
 //                           build over them with one packed 64-bit LDS atomic per update (arithmetic: lambdamart_quant.hpp)
 //   kernels_dart.inc        LambdaMART's DART boosting: the u16 leaf cache and dart_rescore_kernel, which re-forms the scores
 //                           of any weighting of the trees from it
+//   kernels_gram.inc        weighted_gram_kernel / gram_fold_kernel: H = X^T diag(w) X and g = X^T lambda of the linear LambdaRank
+//                           trainer on the FP64 matrix units (v_mfma_f64_16x16x4_f64), per-workgroup slabs folded in order; gram.inc
+//                           plans and launches them
 //   dataset_layout.hpp      (through device.hpp; host only, no HIP) the layout arithmetic of a dataset: runs, size classes, gain
 //                           tables, duplicate groups, walk tiles, a view's tables
 //   linesearch_policy.hpp   (host only, no HIP) the adaptive policies of the bound-and-verify line search: routing / back-off of
@@ -130,5 +133,7 @@ namespace frdev {
 #include "resample.inc"
 #include "kernels_permute.inc"
 #include "permute.inc"
+#include "kernels_gram.inc"
+#include "gram.inc"
 
 }  // namespace frdev

@@ -332,6 +332,18 @@ class DeviceDataset {
     bool lambda_download(double* lambda_by_instance, double* weight_by_instance, size_t out_len, std::string* err,
                          const unsigned char* query_flags = nullptr);
 
+    // --- weighted Gram matrix and gradient (kernels_gram.inc + gram.inc) ----------------------
+    // H[i * d + j] = sum_p x_pi w_p x_pj and g[i] = sum_p x_pi lambda_p over the documents of this dataset's queries (with
+    // query_flags[nq]: of the flagged ones), all in f64 on the matrix units.  lam_pos / wt_pos: [np] by padded position, uploaded
+    // for the call; both nullptr: the lambda and w the last lambda_gradients pass left resident.  Values at positions that hold
+    // no document of a visited query are never read.  Waits for the stream; the same call gives the same bytes.
+    struct GramPlan {
+        uint32_t blocks_a = 0, blocks_b = 0, passes = 0, stretch = 0, workgroups = 0, tiles = 0;
+        uint64_t slab_bytes = 0, tile_bytes = 0;  // the slabs' size; the feature bytes one call streams
+    };
+    bool weighted_gram(const double* lam_pos, const double* wt_pos, const unsigned char* query_flags, double* H /*[d*d]*/, double* g /*[d]*/,
+                       std::string* err, GramPlan* plan = nullptr);
+
     // --- LambdaMART's DART boosting (kernels_dart.inc; DESIGN.md section 11, "DART") -----------------
     // A cache of the leaf (u16, depth-first numbering) every document reaches in every tree, by the documents' logical index
     // (a sampled view: its own tiles), next to a table of the trees' leaf values; the scores of any weighting of any subset

@@ -111,6 +111,7 @@ struct StreamSignal {
 };
 
 struct PermuteState;  // permute.inc: what a permutation-importance call keeps on the device between its chunks
+struct GramState;     // gram.inc: the weighted Gram pass's plan, tables, slabs and outputs
 
 struct DeviceDataset::Impl : DatasetDesc {
     // resident base sums / error bounds shared by the bound-and-verify paths (defined further down)
@@ -423,6 +424,7 @@ struct DeviceDataset::Impl : DatasetDesc {
     size_t last_ldm = 0, last_cols = 0;
     int host_flags = 0;
     std::shared_ptr<PermuteState> permute;
+    std::shared_ptr<GramState> gram;
     std::mutex mu;
 
     bool bind(std::string* err) {

@@ -441,6 +441,42 @@ def hist_root_histogram(dataset: CDataset, lam: np.ndarray, wt: np.ndarray, spli
     return cnt.astype(np.int64).reshape(F, k), qs.reshape(F, k), ws.reshape(F, k)
 
 
+def weighted_gram(dataset: CDataset, lam: np.ndarray, wt: np.ndarray, queries=None, plan: Optional[Dict] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """The linear LambdaRank trainer's Gram kernel pair on lam / wt by instance id:
+    (H[d, d] = sum_p x_pi wt_p x_pj, g[d] = sum_p x_pi lam_p) in float64 over the documents of the view's queries, or of
+    `queries` (indices of the view's queries, its order); the entries of other documents are never read.  `plan`: a dict that
+    receives the launch plan (passes, workgroups, stretch_tiles, tiles, slab_bytes, tile_bytes)."""
+    lam = np.ascontiguousarray(lam, dtype=np.float64)
+    wt = np.ascontiguousarray(wt, dtype=np.float64)
+    if lam.shape != wt.shape or lam.ndim != 1:
+        raise ValueError("lam and wt must be 1-d arrays of the same length")
+    qs = None if queries is None else np.ascontiguousarray(queries, dtype=np.uint32)
+    d = int(_json_reply(_load().fr_debug_weighted_gram(dataset.pointer, None, None, 0, None, 0, None, None, 0))["d"])
+    H = np.zeros((d, d), dtype=np.float64)
+    g = np.zeros(d, dtype=np.float64)
+    rep = _json_reply(
+        _load().fr_debug_weighted_gram(
+            dataset.pointer, lam.ctypes.data, wt.ctypes.data, lam.shape[0], None if qs is None else qs.ctypes.data,
+            0 if qs is None else len(qs), H.ctypes.data, g.ctypes.data, d,
+        )
+    )
+    if plan is not None:
+        plan.update(rep)
+    return H, g
+
+
+def newton_step(H: np.ndarray, g: np.ndarray, lambda_l2: float) -> np.ndarray:
+    """The linear LambdaRank trainer's host solver alone (no device): delta of (H + lambda_l2 I) delta = g by Cholesky in a
+    fixed order.  A pivot that is not positive raises, naming the column and suggesting a larger lambda_l2."""
+    H = np.ascontiguousarray(H, dtype=np.float64)
+    g = np.ascontiguousarray(g, dtype=np.float64)
+    if H.ndim != 2 or H.shape[0] != H.shape[1] or g.shape != (H.shape[0],):
+        raise ValueError("H must be square and g of its size")
+    delta = np.zeros(H.shape[0], dtype=np.float64)
+    _status(_load().fr_debug_newton_step(H.ctypes.data, g.ctypes.data, H.shape[0], float(lambda_l2), delta.ctypes.data))
+    return delta
+
+
 def rank_order(model: CModel, dataset: CDataset) -> Tuple[np.ndarray, np.ndarray]:
     """(instance ids grouped by query, best first; offsets[nq+1]) under the reference's
     (score desc, gain asc, id asc) order."""

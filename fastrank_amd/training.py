@@ -229,6 +229,45 @@ class LambdaMARTParams(_LearnerParams):
         return wire
 
 
+@dataclasses.dataclass
+class LinearLambdaRankParams(_LearnerParams):
+    """A linear model trained by Newton steps on LambdaRank gradients, on the device (csrc/linear_lambda.hpp,
+    train_linear_lambda.inc, kernels_gram.inc).  The wire form requires the first five keys.  Measures:
+    ndcg and ndcg@k.  Weights start at 0; each of `num_iterations` iterations scores the current model, takes one gradient
+    pass (LambdaMART's: `sigma`, `objective` "ndcg" / "map" / "mrr" / "xendcg", `truncation_level`, `lambda_norm` mean what
+    they mean there and are refused where they are refused there), forms H = X^T diag(w) X and g = X^T lambda in float64 on
+    the matrix units, solves (H + `lambda_l2` I) delta = g on the host and adds `learning_rate` * delta.  The model is the
+    iteration with the largest training measure (the first of equals; the first iteration when none beats all-zero weights).
+    `lambda_l2` must be large enough for H + lambda_l2 I to be positive definite: a constant-zero column needs it above 0.
+    The training stats' "linear_lambdarank" object reports `train_measure`, `best_iteration`, the `weights` after every
+    iteration and milliseconds per stage.  Held-out queries, a validation dataset and `init_model` are refused; a request
+    that names several devices trains on one.  The last three keys are written only when they differ from their defaults."""
+
+    VARIANT: ClassVar[str] = "LinearLambdaRank"
+
+    num_iterations: int = 20
+    learning_rate: float = 1.0
+    lambda_l2: float = 1.0
+    sigma: float = 1.0
+    quiet: bool = False
+    objective: str = "ndcg"
+    truncation_level: int = 0
+    lambda_norm: bool = False
+
+    _WIRE_DEFAULTS: ClassVar[Dict[str, Any]] = {"objective": "ndcg", "truncation_level": 0, "lambda_norm": False}
+
+    def __post_init__(self):
+        if isinstance(self.objective, str):  # (anything else is left for the request parser to refuse)
+            self.objective = LambdaMARTParams._OBJECTIVES.get(self.objective, self.objective)
+
+    def to_dict(self) -> Dict[str, Any]:
+        wire = dataclasses.asdict(self)
+        for key, default in self._WIRE_DEFAULTS.items():  # serde: skip_serializing_if
+            if wire[key] == default:
+                del wire[key]
+        return wire
+
+
 def hold_out_queries(queries: Sequence[str], rate: float, seed: int = 0) -> List[str]:
     """A validation split for `LambdaMARTParams.validation_queries`: about `rate` of `queries` (e.g. `dataset.queries()`),
     at least one and at most all but one, chosen by numpy's `default_rng(seed)`; the result keeps the order of `queries`.
@@ -294,3 +333,7 @@ class TrainRequest:
     @staticmethod
     def lambdamart() -> "TrainRequest":
         return TrainRequest._defaults("lambdamart_defaults")
+
+    @staticmethod
+    def linear_lambdarank() -> "TrainRequest":
+        return TrainRequest._defaults("linear_lambdarank_defaults")

@@ -390,6 +390,17 @@ const void *fr_debug_lambdamart_dart_plan(const void *params_json, uint32_t num_
 const void *fr_debug_dart_scores(const CDataset *dataset, const CModel *model, const double *weights, size_t n_weights,
                                  const uint32_t *include, size_t n_include, double *scores_out, uint16_t *cache_out,
                                  size_t out_len);
+/* The linear LambdaRank trainer ({"LinearLambdaRank": {...}} requests), test hooks.
+ * fr_debug_weighted_gram: the Gram kernel pair on uploaded arrays.  lambda / weight[len] by instance id (every id of the view
+ * must be below len), queries[n_queries] = indices of the view's queries to visit (NULL: all; the others' entries are never
+ * read).  h_out[d * d] row-major = sum_p x_pi w_p x_pj and g_out[d] = sum_p x_pi lambda_p in f64, d = the dataset's columns.
+ * Returns JSON {"passes","workgroups","stretch_tiles","tiles","slab_bytes","tile_bytes"}: the plan that ran.  With h_out and
+ * g_out both NULL nothing runs and the reply is {"d": the dataset's columns}.
+ * fr_debug_newton_step: the trainer's host solver alone, no device: delta_out[n] of (h + lambda_l2 I) delta = g by Cholesky
+ * in a fixed order; a pivot that is not positive is an error that names the column and suggests a larger lambda_l2. */
+const void *fr_debug_weighted_gram(const CDataset *dataset, const double *lambda, const double *weight, size_t len,
+                                   const uint32_t *queries, size_t n_queries, double *h_out, double *g_out, size_t d);
+const void *fr_debug_newton_step(const double *h, const double *g, size_t n, double lambda_l2, double *delta_out);
 /* Full per-query rank order under the reference's total order (src/evaluators.rs:34-49):
  * out_instance_ids[n] grouped by query (device query order), best first; out_offsets[nq+1]. */
 const void *fr_rank_order(const CModel *model, const CDataset *dataset, uint32_t *out_instance_ids,
