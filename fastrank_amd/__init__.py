@@ -6,10 +6,10 @@ query_json, TrainRequest.  All computation happens in libfastrank_amd.so (HIP, g
 from .clib import CDataset, CModel, CQRel, Normalizer, measures, query_json
 from .compare import compare_models
 from .importance import permutation_importance
-from .training import CoordinateAscentParams, LambdaMARTParams, LinearLambdaRankParams, RandomForestParams, TrainRequest
+from .training import CoordinateAscentParams, LambdaMARTParams, LinearLambdaRankParams, NeuralLambdaRankParams, RandomForestParams, TrainRequest
 
 VERSION_TUPLE = (0, 7, 0)
 __version__ = "{}.{}.{}".format(*VERSION_TUPLE)
 
 __all__ = ["clib", "training", "native", "CQRel", "CDataset", "CModel", "Normalizer", "query_json", "measures", "compare_models", "permutation_importance", "TrainRequest",
-           "CoordinateAscentParams", "RandomForestParams", "LambdaMARTParams", "LinearLambdaRankParams"]
+           "CoordinateAscentParams", "RandomForestParams", "LambdaMARTParams", "LinearLambdaRankParams", "NeuralLambdaRankParams"]

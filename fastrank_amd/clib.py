@@ -14,7 +14,7 @@ from typing import Dict, List, Optional, Set
 from . import _build
 
 # model.rs:10-16 ModelEnum variants (clib.py:6 keeps the same list)
-_MODEL_TYPES = ["SingleFeature", "Linear", "DecisionTree", "Ensemble"]
+_MODEL_TYPES = ["SingleFeature", "Linear", "DecisionTree", "Ensemble", "NeuralNet"]
 
 
 # int (*fr_allreduce_sum_fn)(void *ctx, double *values, size_t n)  (include/fastrank.h)
@@ -116,6 +116,8 @@ def _load():
         "fr_debug_lambda_gradients_opts": (vp, [vp, vp, vp, C.c_char_p, C.c_double, vp, sz, C.c_char_p, vp, vp, sz]),
         "fr_debug_weighted_gram": (vp, [vp, vp, vp, sz, vp, sz, vp, vp, sz]),
         "fr_debug_newton_step": (vp, [vp, vp, sz, C.c_double, vp]),
+        "fr_debug_mlp_gradients": (vp, [vp, vp, vp, sz, vp, sz, vp, vp, vp, vp]),
+        "fr_debug_adam_step": (vp, [vp, vp, vp, vp, sz, vp, C.c_uint32, C.c_double, C.c_double]),
         "fr_evaluate_dense": (vp, [vp, vp, vp, C.c_char_p, vp, sz, C.POINTER(vp)]),
         "fr_rank_order": (vp, [vp, vp, vp, sz, vp, sz]),
         "fr_dataset_num_queries": (sz, [vp]),

@@ -18,6 +18,7 @@
 #include "forest_pack.hpp"
 #include "lambdamart.hpp"
 #include "linear_lambda.hpp"
+#include "neural_lambda.hpp"
 #include "rf_train.hpp"
 #include "verify_end.hpp"
 
@@ -46,6 +47,7 @@ struct CQRel {
 #include "capi_debug.inc"
 #include "capi_debug_trees.inc"
 #include "train_linear_lambda.inc"
+#include "train_neural_lambda.inc"
 
 namespace {
 
@@ -250,7 +252,8 @@ const void* query_json(const void* json_cmd_str) {
     return json_call([&]() {
         std::string cmd = accept_str("query_json_str", json_cmd_str);
         // src/ffi.rs:215-236
-        if (cmd == "coordinate_ascent_defaults" || cmd == "random_forest_defaults" || cmd == "lambdamart_defaults" || cmd == "linear_lambdarank_defaults") {
+        if (cmd == "coordinate_ascent_defaults" || cmd == "random_forest_defaults" || cmd == "lambdamart_defaults" || cmd == "linear_lambdarank_defaults" ||
+            cmd == "neural_lambdarank_defaults") {
             Value o = Value::object();
             o.set("measure", Value::string("ndcg"));
             Value params = Value::object();
@@ -260,6 +263,8 @@ const void* query_json(const void* json_cmd_str) {
                 params.set("LambdaMART", fr::LambdaMARTParams().to_json());
             else if (cmd == "linear_lambdarank_defaults")
                 params.set("LinearLambdaRank", fr::LinearLambdaRankParams().to_json());
+            else if (cmd == "neural_lambdarank_defaults")
+                params.set("NeuralLambdaRank", fr::NeuralLambdaRankParams().to_json());
             else
                 params.set("RandomForest", random_forest_defaults_json());
             o.set("params", std::move(params));
@@ -305,6 +310,7 @@ const CResult* train_model(void* train_request_json, void* dataset) {
                 case Learner::CoordinateAscent: return train_ca_devices(ds.view, rq);
                 case Learner::RandomForest: return train_rf(ds.view, rq);
                 case Learner::LinearLambdaRank: return train_linear_lambdarank(ds.view, rq);
+                case Learner::NeuralLambdaRank: return train_neural_lambdarank(ds.view, rq);
                 case Learner::LambdaMART: break;
             }
             return train_lambdamart(ds.view, rq);

@@ -467,6 +467,7 @@ const void* fr_debug_forest_pack(const CModel* model, uint32_t dataset_features,
     return json_call([&]() {
         const CModel& m = require_model(model);
         frdev::FlatTrees ft;
+        if (m.actual.kind == fr::Model::NeuralNet) fr::fail_str("fr_debug_forest_pack: a NeuralNet model has no forest to pack");
         if (!fr::flat_trees_of(m.actual, &ft)) fr::fail_str("fr_debug_forest_pack: the model is neither a DecisionTree nor an Ensemble of DecisionTrees");
         const std::string enc = accept_str("encoding", encoding);
         const uint32_t d = dataset_features, dq = (d + 3) / 4;

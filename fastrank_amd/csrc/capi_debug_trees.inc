@@ -78,6 +78,7 @@ const void* fr_debug_dart_scores(const CDataset* dataset, const CModel* model, c
         const fr::Model& ens = m.actual;
         bool trees = ens.kind == fr::Model::Ensemble && !ens.members.empty();
         for (const auto& mm : ens.members) trees = trees && mm.kind == fr::Model::DecisionTree;
+        if (ens.kind == fr::Model::NeuralNet) fr::fail_str("fr_debug_dart_scores: a NeuralNet model has no trees to rescore");
         if (!trees) fr::fail_str("fr_debug_dart_scores: the model must be an Ensemble of DecisionTrees");
         if (n_weights != ens.members.size()) fr::fail_str("fr_debug_dart_scores: one weight per tree of the model");
         if ((n_weights && !weights) || (n_include && !include) || (out_len && (!scores_out || !cache_out)))

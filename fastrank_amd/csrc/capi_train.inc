@@ -53,7 +53,7 @@ Value stats_to_json(const fr::TrainStats& s) {
     return o;
 }
 
-enum class Learner { CoordinateAscent, RandomForest, LambdaMART, LinearLambdaRank };
+enum class Learner { CoordinateAscent, RandomForest, LambdaMART, LinearLambdaRank, NeuralLambdaRank };
 
 struct ParsedRequest {
     std::string measure;
@@ -62,6 +62,7 @@ struct ParsedRequest {
     fr::RFParams rf;
     fr::LambdaMARTParams lm;
     fr::LinearLambdaRankParams ll;
+    fr::NeuralLambdaRankParams nl;
     bool has_qrel = false;
     fr::QRel qrel;
 };
@@ -90,9 +91,13 @@ ParsedRequest parse_train_request(const std::string& text, bool has_valid = fals
         rq.learner = Learner::LinearLambdaRank;
         rq.ll = fr::LinearLambdaRankParams::from_json(var.second);
         fr::lambdamart_check_measure(rq.measure);  // (the gradients are LambdaMART's: the same measures, the same words)
+    } else if (var.first == "NeuralLambdaRank") {
+        rq.learner = Learner::NeuralLambdaRank;
+        rq.nl = fr::NeuralLambdaRankParams::from_json(var.second);
+        fr::lambdamart_check_measure(rq.measure);
     } else {
         fr::fail_raw("Error(\"unknown variant `" + var.first +
-                     "`, expected one of `CoordinateAscent`, `RandomForest`, `LambdaMART`, `LinearLambdaRank`\", line: 1, column: 1)");
+                     "`, expected one of `CoordinateAscent`, `RandomForest`, `LambdaMART`, `LinearLambdaRank`, `NeuralLambdaRank`\", line: 1, column: 1)");
     }
     const Value* j = v.find("judgments");
     if (j && !j->is_null()) {
@@ -105,12 +110,14 @@ ParsedRequest parse_train_request(const std::string& text, bool has_valid = fals
 std::vector<fr::TrainStats> g_last_per_device;  // one entry per device of the last multi-device train_model call
 Value g_last_lambdamart;                         // the last LambdaMART training's own numbers (null after any other training)
 Value g_last_linear_lambdarank;                  // ... and the last LinearLambdaRank training's (train_linear_lambda.inc)
+Value g_last_neural_lambdarank;                  // ... and the last NeuralLambdaRank training's (train_neural_lambda.inc)
 static void set_last_stats(const fr::TrainStats& st, std::vector<fr::TrainStats> per_device = {}) {
     std::lock_guard<std::mutex> lk(g_stats_mu);
     g_last_stats = st;
     g_last_per_device = std::move(per_device);
     g_last_lambdamart = Value::null();
     g_last_linear_lambdarank = Value::null();
+    g_last_neural_lambdarank = Value::null();
 }
 
 // Per-trainer bound on the restarts kept live at once (FR_RESTART_SLOTS, default 64): a request with more restarts than
@@ -635,6 +642,7 @@ const void* fr_last_train_stats(void) {
         }
         if (!g_last_lambdamart.is_null()) o.set("lambdamart", g_last_lambdamart);
         if (!g_last_linear_lambdarank.is_null()) o.set("linear_lambdarank", g_last_linear_lambdarank);
+        if (!g_last_neural_lambdarank.is_null()) o.set("neural_lambdarank", g_last_neural_lambdarank);
         return frjson::dump(o);
     });
 }
@@ -648,6 +656,9 @@ const CResult* fr_train_model_with(const void* train_request_json, const CDatase
         if (rq.learner == Learner::LinearLambdaRank)
             fr::fail_str("fr_train_model_with: a validation dataset and an init model are not supported by LinearLambdaRank (it trains from all-zero "
                          "weights and returns its best training iteration)");
+        if (rq.learner == Learner::NeuralLambdaRank)
+            fr::fail_str("fr_train_model_with: a validation dataset and an init model are not supported by NeuralLambdaRank (it trains from its "
+                         "seeded initial net and returns its best training iteration)");
         if (rq.learner != Learner::LambdaMART)
             fr::fail_str(std::string("fr_train_model_with: a validation dataset and an init model are LambdaMART's; the request's learner is ") +
                          (rq.learner == Learner::CoordinateAscent ? "CoordinateAscent" : "RandomForest"));

@@ -41,6 +41,9 @@
 //   kernels_gram.inc        weighted_gram_kernel / gram_fold_kernel: H = X^T diag(w) X and g = X^T lambda of the linear LambdaRank
 //                           trainer on the FP64 matrix units (v_mfma_f64_16x16x4_f64), per-workgroup slabs folded in order; gram.inc
 //                           plans and launches them
+//   kernels_mlp.inc         mlp_score_kernel / mlp_backprop_kernel / mlp_fold_kernel: the one-hidden-layer ReLU net of the NeuralNet
+//                           model and the neural LambdaRank trainer, two chained tile products on the FP64 matrix units; mlp.inc
+//                           plans and launches them
 //   dataset_layout.hpp      (through device.hpp; host only, no HIP) the layout arithmetic of a dataset: runs, size classes, gain
 //                           tables, duplicate groups, walk tiles, a view's tables
 //   linesearch_policy.hpp   (host only, no HIP) the adaptive policies of the bound-and-verify line search: routing / back-off of
@@ -135,5 +138,7 @@ namespace frdev {
 #include "permute.inc"
 #include "kernels_gram.inc"
 #include "gram.inc"
+#include "kernels_mlp.inc"
+#include "mlp.inc"
 
 }  // namespace frdev

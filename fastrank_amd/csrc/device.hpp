@@ -344,6 +344,24 @@ class DeviceDataset {
     bool weighted_gram(const double* lam_pos, const double* wt_pos, const unsigned char* query_flags, double* H /*[d*d]*/, double* g /*[d]*/,
                        std::string* err, GramPlan* plan = nullptr);
 
+    // --- one-hidden-layer ReLU net (kernels_mlp.inc + mlp.inc) --------------------------------
+    // W1: h rows of dm numbers (row j = hidden unit j, column i = feature i; columns the model lacks read as 0, columns past d
+    // are not read), b1[h], w2[h], b2.  score_mlp: score slot 0 <- b2 + sum_j relu(b1_j + sum_i x_pi W1_ji) w2_j for every
+    // document of this dataset, all in f64 on the matrix units (not waited for).  mlp_backprop: the ascent direction of the
+    // parameters for lambda by padded position (lam_pos[np], uploaded for the call; nullptr: what the last lambda_gradients pass
+    // left resident) over the documents of this dataset's queries (query_flags[nq]: of the flagged ones): g_w1[h * d], g_b1[h],
+    // g_w2[h], g_b2[1].  Values at positions that hold no document of a visited query are never read.  Waits for the stream;
+    // the same call gives the same bytes.
+    struct MlpPlan {
+        uint32_t feature_panels = 0, hidden_panels = 0, stretch = 0, workgroups = 0, tiles = 0;
+        bool resident = false;                    // the W1 fragments stayed in registers
+        uint64_t slab_bytes = 0, tile_bytes = 0;  // the records' size; the feature bytes one pass over the tiles streams
+    };
+    bool score_mlp(size_t h, size_t dm, const double* W1, const double* b1, const double* w2, double b2, std::string* err, MlpPlan* plan = nullptr);
+    bool mlp_backprop(size_t h, size_t dm, const double* W1, const double* b1, const double* w2, const double* lam_pos,
+                      const unsigned char* query_flags, double* g_w1, double* g_b1, double* g_w2, double* g_b2, std::string* err,
+                      MlpPlan* plan = nullptr);
+
     // --- LambdaMART's DART boosting (kernels_dart.inc; DESIGN.md section 11, "DART") -----------------
     // A cache of the leaf (u16, depth-first numbering) every document reaches in every tree, by the documents' logical index
     // (a sampled view: its own tiles), next to a table of the trees' leaf values; the scores of any weighting of any subset

@@ -32,6 +32,7 @@ inline ExplainModel explain_model(const Model& m) {
     switch (m.kind) {
         case Model::Linear: fail_str("explain: a Linear model has no trees to explain (its contributions are weight * value)");
         case Model::SingleFeature: fail_str("explain: a SingleFeature model has no trees to explain");
+        case Model::NeuralNet: fail_str("explain: a NeuralNet model has no trees to explain");
         case Model::DecisionTree:
             out.trees.push_back(m.tree.get());
             out.weights.push_back(1.0);

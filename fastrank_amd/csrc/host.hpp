@@ -508,6 +508,9 @@ inline void score_model(DatasetView& view, const Model& m, frdev::DeviceDataset*
         case Model::SingleFeature:
             if (!dev.score_single_feature(m.fid, m.dir, &_err)) fail_str(_err);
             break;
+        case Model::NeuralNet:
+            if (!dev.score_mlp(m.nn_b1.size(), m.nn_cols, m.nn_w1.data(), m.nn_b1.data(), m.nn_w2.data(), m.nn_b2, &_err)) fail_str(_err);
+            break;
         case Model::DecisionTree: {
             frdev::FlatTrees ft;
             flat_trees_of(m, &ft);

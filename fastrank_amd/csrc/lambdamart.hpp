@@ -454,13 +454,14 @@ inline void lambdamart_check_init(const Model& m, const LambdaMARTParams& p) {
     auto refuse = [](const std::string& what) { fail_str("LambdaMART: init_model must be an Ensemble of DecisionTrees, not " + what); };
     if (m.kind == Model::Linear) refuse("a Linear model");
     if (m.kind == Model::SingleFeature) refuse("a SingleFeature model");
+    if (m.kind == Model::NeuralNet) refuse("a NeuralNet model");
     if (m.kind == Model::DecisionTree) refuse("a bare DecisionTree (wrap it in an Ensemble with a weight)");
     if (m.members.size() != m.ens_weights.size())
         fail_str("LambdaMART: init_model has " + std::to_string(m.ens_weights.size()) + " weights for " + std::to_string(m.members.size()) + " models");
     for (size_t t = 0; t < m.members.size(); t++) {
         const Model& mm = m.members[t];
         if (mm.kind == Model::Ensemble) refuse("an Ensemble with a nested Ensemble (member " + std::to_string(t) + ")");
-        if (mm.kind != Model::DecisionTree) refuse(std::string("an Ensemble with a ") + (mm.kind == Model::Linear ? "Linear" : "SingleFeature") + " member (member " + std::to_string(t) + ")");
+        if (mm.kind != Model::DecisionTree) refuse(std::string("an Ensemble with a ") + (mm.kind == Model::Linear ? "Linear" : mm.kind == Model::NeuralNet ? "NeuralNet" : "SingleFeature") + " member (member " + std::to_string(t) + ")");
         if (!std::isfinite(m.ens_weights[t])) fail_str("LambdaMART: init_model has a non-finite weight (tree " + std::to_string(t) + ")");
         std::vector<const TreeNode*> work{mm.tree.get()};
         while (!work.empty()) {

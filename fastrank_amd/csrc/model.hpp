@@ -2,6 +2,7 @@
 // boundary, and the field helpers every wire form is read with.  Plain C++ over json.hpp: host.hpp and ca_restart.hpp
 // both include it.
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <memory>
 #include <string>
@@ -28,13 +29,18 @@ struct TreeNode {
 };
 
 struct Model {
-    enum Kind { SingleFeature, Linear, DecisionTree, Ensemble } kind = Linear;
+    enum Kind { SingleFeature, Linear, DecisionTree, Ensemble, NeuralNet } kind = Linear;
     uint32_t fid = 0;
     double dir = 0.0;
     std::vector<double> weights;
     std::shared_ptr<TreeNode> tree;
     std::vector<double> ens_weights;
     std::vector<Model> members;
+    // NeuralNet: s = b2 + sum_j relu(b1_j + sum_i x_i W1_ji) w2_j.  nn_w1: nn_b1.size() rows of nn_cols
+    // numbers, row j = hidden unit j, column i = feature id i.
+    size_t nn_cols = 0;
+    std::vector<double> nn_w1, nn_b1, nn_w2;
+    double nn_b2 = 0.0;
 };
 
 inline double json_f64(const Value& v, const char* what) {
@@ -125,9 +131,33 @@ inline Model model_from_json(const Value& v) {
             fail_raw("Error(\"invalid type: expected sequences in Ensemble\", line: 0, column: 0)");
         for (const auto& x : w.arr) m.ens_weights.push_back(json_f64(x, "weights"));
         for (const auto& x : ms.arr) m.members.push_back(model_from_json(x));
+    } else if (var.first == "NeuralNet") {
+        m.kind = Model::NeuralNet;
+        const Value& act = json_field(var.second, "activation");
+        if (!act.is_string() || act.s != "relu") fail_str("NeuralNet: the activation must be \"relu\"");
+        const Value& w1 = json_field(var.second, "hidden_weights");
+        const Value& b1 = json_field(var.second, "hidden_bias");
+        const Value& w2 = json_field(var.second, "output_weights");
+        if (!w1.is_array() || !b1.is_array() || !w2.is_array()) fail_raw("Error(\"invalid type: expected sequences in NeuralNet\", line: 0, column: 0)");
+        if (w1.arr.empty()) fail_str("NeuralNet: at least one hidden unit is needed");
+        if (b1.arr.size() != w1.arr.size() || w2.arr.size() != w1.arr.size())
+            fail_str("NeuralNet: hidden_bias and output_weights must hold one number per row of hidden_weights");
+        auto finite = [](double x) {
+            if (!std::isfinite(x)) fail_str("NeuralNet: every number must be finite");
+            return x;
+        };
+        for (const auto& row : w1.arr) {
+            if (!row.is_array()) fail_raw("Error(\"invalid type: expected a sequence for hidden_weights\", line: 0, column: 0)");
+            if (&row == &w1.arr[0]) m.nn_cols = row.arr.size();
+            if (row.arr.size() != m.nn_cols) fail_str("NeuralNet: the rows of hidden_weights must have one length");
+            for (const auto& x : row.arr) m.nn_w1.push_back(finite(json_f64(x, "hidden_weights")));
+        }
+        for (const auto& x : b1.arr) m.nn_b1.push_back(finite(json_f64(x, "hidden_bias")));
+        for (const auto& x : w2.arr) m.nn_w2.push_back(finite(json_f64(x, "output_weights")));
+        m.nn_b2 = finite(json_f64(json_field(var.second, "output_bias"), "output_bias"));
     } else {
         fail_raw("Error(\"unknown variant `" + var.first +
-                 "`, expected one of `SingleFeature`, `Linear`, `DecisionTree`, `Ensemble`\", line: 0, column: 0)");
+                 "`, expected one of `SingleFeature`, `Linear`, `DecisionTree`, `Ensemble`, `NeuralNet`\", line: 0, column: 0)");
     }
     return m;
 }
@@ -162,6 +192,24 @@ inline Value model_to_json(const Model& m) {
             inner.set("weights", std::move(w));
             inner.set("models", std::move(ms));
             v.set("Ensemble", std::move(inner));
+            break;
+        }
+        case Model::NeuralNet: {
+            Value inner = Value::object();
+            inner.set("activation", Value::string("relu"));
+            Value w1 = Value::array(), b1 = Value::array(), w2 = Value::array();
+            for (size_t j = 0; j < m.nn_b1.size(); j++) {
+                Value row = Value::array();
+                for (size_t i = 0; i < m.nn_cols; i++) row.push(Value::number(m.nn_w1[j * m.nn_cols + i]));
+                w1.push(std::move(row));
+                b1.push(Value::number(m.nn_b1[j]));
+                w2.push(Value::number(m.nn_w2[j]));
+            }
+            inner.set("hidden_weights", std::move(w1));
+            inner.set("hidden_bias", std::move(b1));
+            inner.set("output_weights", std::move(w2));
+            inner.set("output_bias", Value::number(m.nn_b2));
+            v.set("NeuralNet", std::move(inner));
             break;
         }
     }

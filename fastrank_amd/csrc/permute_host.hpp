@@ -84,6 +84,7 @@ inline std::string permute_shape_name(const Model& m, int depth = 0) {
         case Model::Linear: return "Linear";
         case Model::SingleFeature: return "SingleFeature";
         case Model::DecisionTree: return "DecisionTree";
+        case Model::NeuralNet: return "NeuralNet";
         case Model::Ensemble: break;
     }
     std::string s = "Ensemble[";
@@ -102,6 +103,7 @@ inline PermuteShape permute_model_shape(const Model& m) {
         case Model::Linear: return PermuteShape::LINEAR;
         case Model::SingleFeature: return PermuteShape::SINGLE;
         case Model::DecisionTree: return PermuteShape::TREES;
+        case Model::NeuralNet: fail_str("permutation importance does not take a NeuralNet model (there is no permuting kernel for it)");
         case Model::Ensemble: break;
     }
     bool trees = !m.members.empty(), flat = !m.members.empty();
@@ -173,6 +175,7 @@ inline bool permute_feature_used(const Model& m, uint32_t f, const std::vector<d
             return !(f >= m.weights.size() || m.weights[f] == 0.0) || !std::isfinite(colmax[f]);
         case Model::SingleFeature: return m.fid == f && f < colmax.size();
         case Model::DecisionTree: return f < colmax.size() && permute_tree_uses(*m.tree, f);
+        case Model::NeuralNet: return f < colmax.size();
         case Model::Ensemble: {
             const size_t nt = std::min(m.members.size(), m.ens_weights.size());
             for (size_t k = 0; k < nt; k++)

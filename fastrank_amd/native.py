@@ -477,6 +477,45 @@ def newton_step(H: np.ndarray, g: np.ndarray, lambda_l2: float) -> np.ndarray:
     return delta
 
 
+def mlp_gradients(dataset: CDataset, model: CModel, lam: np.ndarray, queries=None, plan: Optional[Dict] = None) -> Dict[str, np.ndarray]:
+    """Back-propagation of `lam` (by instance id) through the NeuralNet `model` (mlp_backprop_kernel) in
+    float64 over the documents of the view's queries, or of `queries` (indices of the view's queries, its order); the entries
+    of other documents are never read.  Returns {"hidden_weights": [h, d] over the dataset's d columns, "hidden_bias": [h],
+    "output_weights": [h], "output_bias": float}: the ascent direction of each parameter.  `plan`: a dict that receives the
+    launch plan (feature_panels, hidden_panels, workgroups, stretch_tiles, tiles, resident, slab_bytes, tile_bytes)."""
+    lam = np.ascontiguousarray(lam, dtype=np.float64)
+    if lam.ndim != 1:
+        raise ValueError("lam must be a 1-d array")
+    qs = None if queries is None else np.ascontiguousarray(queries, dtype=np.uint32)
+    size = _json_reply(_load().fr_debug_mlp_gradients(dataset.pointer, model.pointer, None, 0, None, 0, None, None, None, None))
+    h, d = int(size["h"]), int(size["d"])
+    gw1, gb1, gw2, gb2 = np.zeros((h, d)), np.zeros(h), np.zeros(h), np.zeros(1)
+    rep = _json_reply(
+        _load().fr_debug_mlp_gradients(
+            dataset.pointer, model.pointer, lam.ctypes.data, lam.shape[0], None if qs is None else qs.ctypes.data,
+            0 if qs is None else len(qs), gw1.ctypes.data, gb1.ctypes.data, gw2.ctypes.data, gb2.ctypes.data,
+        )
+    )
+    if plan is not None:
+        plan.update(rep)
+    return {"hidden_weights": gw1, "hidden_bias": gb1, "output_weights": gw2, "output_bias": float(gb2[0])}
+
+
+def adam_step(theta, grad, m, v, t: int, learning_rate: float, lambda_l2: float = 0.0, decays=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The neural LambdaRank trainer's Adam ascent step alone (no device; csrc/neural_lambda.hpp): step `t` (1-based) on flat
+    float64 arrays; `decays`: a mask of the parameters `lambda_l2` applies to (None: none).  Returns the new (theta, m, v)."""
+    theta, m, v = (np.array(a, dtype=np.float64).ravel() for a in (theta, m, v))
+    grad = np.ascontiguousarray(grad, dtype=np.float64).ravel()
+    if not (theta.shape == grad.shape == m.shape == v.shape):
+        raise ValueError("theta, grad, m and v must have one size")
+    dec = None if decays is None else np.ascontiguousarray(decays, dtype=np.uint8).ravel()
+    if dec is not None and dec.shape != theta.shape:
+        raise ValueError("decays must have the parameters' size")
+    _status(_load().fr_debug_adam_step(theta.ctypes.data, grad.ctypes.data, m.ctypes.data, v.ctypes.data, theta.shape[0],
+                                       None if dec is None else dec.ctypes.data, int(t), float(learning_rate), float(lambda_l2)))
+    return theta, m, v
+
+
 def rank_order(model: CModel, dataset: CDataset) -> Tuple[np.ndarray, np.ndarray]:
     """(instance ids grouped by query, best first; offsets[nq+1]) under the reference's
     (score desc, gain asc, id asc) order."""

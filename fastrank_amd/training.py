@@ -268,6 +268,41 @@ class LinearLambdaRankParams(_LearnerParams):
         return wire
 
 
+@dataclasses.dataclass
+class NeuralLambdaRankParams(_LearnerParams):
+    """A one-hidden-layer ReLU net, s = b2 + sum_j relu(b1_j + x . W1_j) w2_j, trained by full-batch Adam ascent on LambdaRank
+    gradients, on the device (csrc/neural_lambda.hpp, train_neural_lambda.inc, kernels_mlp.inc).  The
+    wire form requires the first seven keys.  Measures: ndcg and ndcg@k.  The net starts from a Glorot-uniform draw of a
+    counter-based stream of `seed`; each of `num_iterations` iterations scores the current net, takes one gradient pass
+    (LambdaMART's: `sigma`, `objective` "ndcg" / "map" / "mrr" / "xendcg", `truncation_level`, `lambda_norm` mean what they
+    mean there and are refused where they are refused there), back-propagates lambda through the net in float64 on the matrix
+    units and takes one Adam step on the host (`learning_rate`; `lambda_l2` decays W1 and w2).  Normalise raw columns first
+    (`Normalizer`).  The model is the NeuralNet iterate with the largest training measure (the first of equals; the first
+    iterate when none beats the initial net).  The training stats' "neural_lambdarank" object reports `initial_measure`,
+    `train_measure`, `best_iteration`, milliseconds per stage, the kernels' plans and, under `trace`, the `initial` net and
+    all `iterates` as models.  Held-out queries, a validation dataset and `init_model` are refused; a request that names
+    several devices trains on one.  The last four keys are written only when they differ from their defaults."""
+
+    VARIANT: ClassVar[str] = "NeuralLambdaRank"
+
+    hidden: int = 64
+    num_iterations: int = 100
+    learning_rate: float = 0.03
+    lambda_l2: float = 0.0
+    sigma: float = 1.0
+    seed: int = 0
+    quiet: bool = False
+    objective: str = "ndcg"
+    truncation_level: int = 0
+    lambda_norm: bool = False
+    trace: bool = False
+
+    _WIRE_DEFAULTS: ClassVar[Dict[str, Any]] = {"objective": "ndcg", "truncation_level": 0, "lambda_norm": False, "trace": False}
+
+    __post_init__ = LinearLambdaRankParams.__post_init__
+    to_dict = LinearLambdaRankParams.to_dict
+
+
 def hold_out_queries(queries: Sequence[str], rate: float, seed: int = 0) -> List[str]:
     """A validation split for `LambdaMARTParams.validation_queries`: about `rate` of `queries` (e.g. `dataset.queries()`),
     at least one and at most all but one, chosen by numpy's `default_rng(seed)`; the result keeps the order of `queries`.
@@ -337,3 +372,7 @@ class TrainRequest:
     @staticmethod
     def linear_lambdarank() -> "TrainRequest":
         return TrainRequest._defaults("linear_lambdarank_defaults")
+
+    @staticmethod
+    def neural_lambdarank() -> "TrainRequest":
+        return TrainRequest._defaults("neural_lambdarank_defaults")

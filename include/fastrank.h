@@ -401,6 +401,18 @@ const void *fr_debug_dart_scores(const CDataset *dataset, const CModel *model, c
 const void *fr_debug_weighted_gram(const CDataset *dataset, const double *lambda, const double *weight, size_t len,
                                    const uint32_t *queries, size_t n_queries, double *h_out, double *g_out, size_t d);
 const void *fr_debug_newton_step(const double *h, const double *g, size_t n, double lambda_l2, double *delta_out);
+/* The NeuralNet model and the neural LambdaRank trainer ({"NeuralLambdaRank": {...}} requests), test
+ * hooks.  fr_debug_mlp_gradients: back-propagation of lambda[len] (by instance id; every id of the view must be below len)
+ * through `model`, a NeuralNet, over the documents of the view's queries or of queries[n_queries] (indices of the view's
+ * queries; the others' entries are never read): g_w1[h * d] row-major over the dataset's d columns, g_b1[h], g_w2[h], g_b2[1]
+ * in f64.  Returns JSON {"h","d","feature_panels","hidden_panels","workgroups","stretch_tiles","tiles","resident",
+ * "slab_bytes","tile_bytes"}: the sizes and the plan that ran.  With the four outputs NULL nothing runs and the reply is
+ * {"h","d"}.  fr_debug_adam_step: the trainer's Adam ascent step alone, no device, in place on theta / m / v[n]; decays[n]
+ * (NULL: none): 1 where lambda_l2 applies; t: the 1-based step. */
+const void *fr_debug_mlp_gradients(const CDataset *dataset, const CModel *model, const double *lambda, size_t len,
+                                   const uint32_t *queries, size_t n_queries, double *g_w1, double *g_b1, double *g_w2, double *g_b2);
+const void *fr_debug_adam_step(double *theta, const double *grad, double *m, double *v, size_t n, const unsigned char *decays,
+                               uint32_t t, double learning_rate, double lambda_l2);
 /* Full per-query rank order under the reference's total order (src/evaluators.rs:34-49):
  * out_instance_ids[n] grouped by query (device query order), best first; out_offsets[nq+1]. */
 const void *fr_rank_order(const CModel *model, const CDataset *dataset, uint32_t *out_instance_ids,
