@@ -117,6 +117,7 @@ def _load():
         "fr_debug_weighted_gram": (vp, [vp, vp, vp, sz, vp, sz, vp, vp, sz]),
         "fr_debug_newton_step": (vp, [vp, vp, sz, C.c_double, vp]),
         "fr_debug_mlp_gradients": (vp, [vp, vp, vp, sz, vp, sz, vp, vp, vp, vp]),
+        "fr_debug_mlp2_gradients": (vp, [vp, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp]),
         "fr_debug_adam_step": (vp, [vp, vp, vp, vp, sz, vp, C.c_uint32, C.c_double, C.c_double]),
         "fr_evaluate_dense": (vp, [vp, vp, vp, C.c_char_p, vp, sz, C.POINTER(vp)]),
         "fr_rank_order": (vp, [vp, vp, vp, sz, vp, sz]),

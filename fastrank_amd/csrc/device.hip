@@ -44,6 +44,9 @@
 //   kernels_mlp.inc         mlp_score_kernel / mlp_backprop_kernel / mlp_fold_kernel: the one-hidden-layer ReLU net of the NeuralNet
 //                           model and the neural LambdaRank trainer, two chained tile products on the FP64 matrix units; mlp.inc
 //                           plans and launches them
+//   kernels_mlp2.inc        mlp2_score_kernel / mlp2_backprop_kernel / mlp2_fold_kernel: the same net with a second hidden layer,
+//                           three and five chained tile products, the a1 / d2 tile handed between the waves through LDS; mlp2.inc
+//                           packs W2 and launches them
 //   dataset_layout.hpp      (through device.hpp; host only, no HIP) the layout arithmetic of a dataset: runs, size classes, gain
 //                           tables, duplicate groups, walk tiles, a view's tables
 //   linesearch_policy.hpp   (host only, no HIP) the adaptive policies of the bound-and-verify line search: routing / back-off of
@@ -140,5 +143,7 @@ namespace frdev {
 #include "gram.inc"
 #include "kernels_mlp.inc"
 #include "mlp.inc"
+#include "kernels_mlp2.inc"
+#include "mlp2.inc"
 
 }  // namespace frdev

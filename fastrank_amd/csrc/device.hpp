@@ -354,6 +354,7 @@ class DeviceDataset {
     // the same call gives the same bytes.
     struct MlpPlan {
         uint32_t feature_panels = 0, hidden_panels = 0, stretch = 0, workgroups = 0, tiles = 0;
+        uint32_t hidden2 = 0;                     // the second hidden layer's units (0: a one-hidden-layer net)
         bool resident = false;                    // the W1 fragments stayed in registers
         uint64_t slab_bytes = 0, tile_bytes = 0;  // the records' size; the feature bytes one pass over the tiles streams
     };
@@ -361,6 +362,18 @@ class DeviceDataset {
     bool mlp_backprop(size_t h, size_t dm, const double* W1, const double* b1, const double* w2, const double* lam_pos,
                       const unsigned char* query_flags, double* g_w1, double* g_b1, double* g_w2, double* g_b2, std::string* err,
                       MlpPlan* plan = nullptr);
+    // The same net with a second hidden ReLU layer (kernels_mlp2.inc + mlp2.inc): W2: h2 rows of h numbers (row k = unit k of
+    // the second layer), c[h2], w3[h2], b_out; 1 <= h2 <= 64.  score_mlp2: score slot 0 <- b_out + sum_k fl(relu(c_k + sum_j
+    // relu(z1_pj) W2_kj) w3_k).  mlp2_backprop: as mlp_backprop, into grad[h * d + h + h2 * h + 2 * h2 + 1] = G_W1 (over the
+    // dataset's d columns) | G_b1 | G_W2 | G_c | G_w3 | G_bout, the trainer's parameter order.
+    struct Mlp2Net {
+        size_t h = 0, h2 = 0, dm = 0;
+        const double *W1 = nullptr, *b1 = nullptr, *W2 = nullptr, *c = nullptr, *w3 = nullptr;
+        double b_out = 0.0;
+    };
+    bool score_mlp2(const Mlp2Net& net, std::string* err, MlpPlan* plan = nullptr);
+    bool mlp2_backprop(const Mlp2Net& net, const double* lam_pos, const unsigned char* query_flags, double* grad, std::string* err,
+                       MlpPlan* plan = nullptr);
 
     // --- LambdaMART's DART boosting (kernels_dart.inc; DESIGN.md section 11, "DART") -----------------
     // A cache of the leaf (u16, depth-first numbering) every document reaches in every tree, by the documents' logical index

@@ -113,6 +113,7 @@ struct StreamSignal {
 struct PermuteState;  // permute.inc: what a permutation-importance call keeps on the device between its chunks
 struct GramState;     // gram.inc: the weighted Gram pass's plan, tables, slabs and outputs
 struct MlpState;      // mlp.inc: the one-hidden-layer net's tables, packed parameters, records and outputs
+struct Mlp2State;     // mlp2.inc: the two-hidden-layer net's packed parameters, records and outputs
 
 struct DeviceDataset::Impl : DatasetDesc {
     // resident base sums / error bounds shared by the bound-and-verify paths (defined further down)
@@ -427,6 +428,7 @@ struct DeviceDataset::Impl : DatasetDesc {
     std::shared_ptr<PermuteState> permute;
     std::shared_ptr<GramState> gram;
     std::shared_ptr<MlpState> mlp;
+    std::shared_ptr<Mlp2State> mlp2;
     std::mutex mu;
 
     bool bind(std::string* err) {

@@ -494,6 +494,14 @@ inline bool flat_trees_of(const Model& m, frdev::FlatTrees* ft) {
     return true;
 }
 
+// a two-hidden-layer NeuralNet as the device calls take it (pointers into `m`)
+inline frdev::DeviceDataset::Mlp2Net mlp2_net_of(const Model& m) {
+    frdev::DeviceDataset::Mlp2Net n;
+    n.h = m.nn_b1.size(), n.h2 = m.nn_hidden2(), n.dm = m.nn_cols;
+    n.W1 = m.nn_w1.data(), n.b1 = m.nn_b1.data(), n.W2 = m.nn_hw2.data(), n.c = m.nn_hb2.data(), n.w3 = m.nn_w2.data(), n.b_out = m.nn_b2;
+    return n;
+}
+
 // Score `model` for every document of the view into device score slot 0.
 inline void score_model(DatasetView& view, const Model& m, frdev::DeviceDataset* on = nullptr) {
     frdev::DeviceDataset& dev = on ? *on : view.device();  // (on: one of the view's device-side copies, DatasetView::device_ptr(slot, ..))
@@ -509,7 +517,11 @@ inline void score_model(DatasetView& view, const Model& m, frdev::DeviceDataset*
             if (!dev.score_single_feature(m.fid, m.dir, &_err)) fail_str(_err);
             break;
         case Model::NeuralNet:
-            if (!dev.score_mlp(m.nn_b1.size(), m.nn_cols, m.nn_w1.data(), m.nn_b1.data(), m.nn_w2.data(), m.nn_b2, &_err)) fail_str(_err);
+            if (m.nn_hidden2() != 0) {
+                if (!dev.score_mlp2(mlp2_net_of(m), &_err)) fail_str(_err);
+            } else if (!dev.score_mlp(m.nn_b1.size(), m.nn_cols, m.nn_w1.data(), m.nn_b1.data(), m.nn_w2.data(), m.nn_b2, &_err)) {
+                fail_str(_err);
+            }
             break;
         case Model::DecisionTree: {
             frdev::FlatTrees ft;

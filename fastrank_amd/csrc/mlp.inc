@@ -42,6 +42,19 @@ static bool mlp_build(ImplT& m, std::string* err) {
     return true;
 }
 
+// wf[hp][fp][ks][wave][lane] (the header) from the first `cols` columns of W1's h rows of dm numbers
+static std::vector<double> mlp_pack_w1(uint32_t nfp, size_t h, size_t dm, size_t cols, const double* W1) {
+    std::vector<double> wf((h + MLP_HP - 1) / MLP_HP * nfp * MLP_FRAG, 0.0);
+    for (size_t j = 0; j < h; j++) {
+        const size_t hp = j / MLP_HP, wave = (j % MLP_HP) / 16, c = j % 16;
+        for (size_t i = 0; i < cols; i++) {
+            const size_t fp = i / MLP_FP, ks = (i % MLP_FP) / 4, k = i % 4;
+            wf[(hp * nfp + fp) * MLP_FRAG + (ks * MLP_WAVES + wave) * 64 + 16 * k + c] = W1[j * dm + i];
+        }
+    }
+    return wf;
+}
+
 // the parameters as the kernels read them; fills the plan's shape.  W1: h rows of dm numbers (columns >= d are not read).
 template <typename ImplT>
 static bool mlp_upload(ImplT& m, size_t h, size_t dm, const double* W1, const double* b1, const double* w2, uint32_t* nhp_out, std::string* err) {
@@ -51,16 +64,8 @@ static bool mlp_upload(ImplT& m, size_t h, size_t dm, const double* W1, const do
         return false;
     }
     const uint32_t nhp = (uint32_t)((h + MLP_HP - 1) / MLP_HP), nfp = ms.nfp;
-    std::vector<double> wf((size_t)nhp * nfp * MLP_FRAG, 0.0), bias((size_t)2 * nhp * MLP_HP, 0.0);
-    const size_t cols = std::min(dm, m.d);
-    for (size_t j = 0; j < h; j++) {
-        const size_t hp = j / MLP_HP, wave = (j % MLP_HP) / 16, c = j % 16;
-        for (size_t i = 0; i < cols; i++) {
-            const size_t fp = i / MLP_FP, ks = (i % MLP_FP) / 4, k = i % 4;
-            wf[(hp * nfp + fp) * MLP_FRAG + (ks * MLP_WAVES + wave) * 64 + 16 * k + c] = W1[j * dm + i];
-        }
-        bias[j] = b1[j], bias[(size_t)nhp * MLP_HP + j] = w2[j];
-    }
+    std::vector<double> wf = mlp_pack_w1(nfp, h, dm, std::min(dm, m.d), W1), bias((size_t)2 * nhp * MLP_HP, 0.0);
+    for (size_t j = 0; j < h; j++) bias[j] = b1[j], bias[(size_t)nhp * MLP_HP + j] = w2[j];
     if (!ms.wf.ensure(wf.size(), err) || !ms.bias.ensure(bias.size(), err)) return false;
     FR_HIP(hipMemcpyAsync(ms.wf.p, wf.data(), wf.size() * sizeof(double), hipMemcpyHostToDevice, m.stream));
     FR_HIP(hipMemcpyAsync(ms.bias.p, bias.data(), bias.size() * sizeof(double), hipMemcpyHostToDevice, m.stream));

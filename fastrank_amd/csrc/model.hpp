@@ -41,6 +41,11 @@ struct Model {
     size_t nn_cols = 0;
     std::vector<double> nn_w1, nn_b1, nn_w2;
     double nn_b2 = 0.0;
+    // ... with a second hidden layer (nn_hb2 not empty): s = b2 + sum_k fl(relu(c_k + sum_j relu(z_j) W2_kj) w2_k).  nn_hw2: W2,
+    // nn_hb2.size() rows of nn_b1.size() numbers, row k = unit k of the second layer; nn_hb2: c; nn_w2 then holds one number per
+    // unit of the second layer.
+    std::vector<double> nn_hw2, nn_hb2;
+    size_t nn_hidden2() const { return nn_hb2.size(); }
 };
 
 inline double json_f64(const Value& v, const char* what) {
@@ -140,8 +145,18 @@ inline Model model_from_json(const Value& v) {
         const Value& w2 = json_field(var.second, "output_weights");
         if (!w1.is_array() || !b1.is_array() || !w2.is_array()) fail_raw("Error(\"invalid type: expected sequences in NeuralNet\", line: 0, column: 0)");
         if (w1.arr.empty()) fail_str("NeuralNet: at least one hidden unit is needed");
-        if (b1.arr.size() != w1.arr.size() || w2.arr.size() != w1.arr.size())
-            fail_str("NeuralNet: hidden_bias and output_weights must hold one number per row of hidden_weights");
+        const Value *hw2 = var.second.find("hidden2_weights"), *hb2 = var.second.find("hidden2_bias");
+        if ((hw2 == nullptr) != (hb2 == nullptr)) fail_str("NeuralNet: hidden2_weights and hidden2_bias must appear together");
+        if (hw2 == nullptr) {
+            if (b1.arr.size() != w1.arr.size() || w2.arr.size() != w1.arr.size())
+                fail_str("NeuralNet: hidden_bias and output_weights must hold one number per row of hidden_weights");
+        } else {
+            if (!hw2->is_array() || !hb2->is_array()) fail_raw("Error(\"invalid type: expected sequences in NeuralNet\", line: 0, column: 0)");
+            if (hw2->arr.size() < 1 || hw2->arr.size() > 64) fail_str("NeuralNet: hidden2_weights must have between 1 and 64 rows");
+            if (b1.arr.size() != w1.arr.size()) fail_str("NeuralNet: hidden_bias must hold one number per row of hidden_weights");
+            if (hb2->arr.size() != hw2->arr.size() || w2.arr.size() != hw2->arr.size())
+                fail_str("NeuralNet: hidden2_bias and output_weights must hold one number per row of hidden2_weights");
+        }
         auto finite = [](double x) {
             if (!std::isfinite(x)) fail_str("NeuralNet: every number must be finite");
             return x;
@@ -153,6 +168,14 @@ inline Model model_from_json(const Value& v) {
             for (const auto& x : row.arr) m.nn_w1.push_back(finite(json_f64(x, "hidden_weights")));
         }
         for (const auto& x : b1.arr) m.nn_b1.push_back(finite(json_f64(x, "hidden_bias")));
+        if (hw2 != nullptr) {
+            for (const auto& row : hw2->arr) {
+                if (!row.is_array()) fail_raw("Error(\"invalid type: expected a sequence for hidden2_weights\", line: 0, column: 0)");
+                if (row.arr.size() != m.nn_b1.size()) fail_str("NeuralNet: every row of hidden2_weights must hold one number per row of hidden_weights");
+                for (const auto& x : row.arr) m.nn_hw2.push_back(finite(json_f64(x, "hidden2_weights")));
+            }
+            for (const auto& x : hb2->arr) m.nn_hb2.push_back(finite(json_f64(x, "hidden2_bias")));
+        }
         for (const auto& x : w2.arr) m.nn_w2.push_back(finite(json_f64(x, "output_weights")));
         m.nn_b2 = finite(json_f64(json_field(var.second, "output_bias"), "output_bias"));
     } else {
@@ -198,15 +221,27 @@ inline Value model_to_json(const Model& m) {
             Value inner = Value::object();
             inner.set("activation", Value::string("relu"));
             Value w1 = Value::array(), b1 = Value::array(), w2 = Value::array();
-            for (size_t j = 0; j < m.nn_b1.size(); j++) {
+            const size_t h = m.nn_b1.size();
+            for (size_t j = 0; j < h; j++) {
                 Value row = Value::array();
                 for (size_t i = 0; i < m.nn_cols; i++) row.push(Value::number(m.nn_w1[j * m.nn_cols + i]));
                 w1.push(std::move(row));
                 b1.push(Value::number(m.nn_b1[j]));
-                w2.push(Value::number(m.nn_w2[j]));
             }
+            for (double x : m.nn_w2) w2.push(Value::number(x));
             inner.set("hidden_weights", std::move(w1));
             inner.set("hidden_bias", std::move(b1));
+            if (m.nn_hidden2() != 0) {
+                Value hw2 = Value::array(), hb2 = Value::array();
+                for (size_t k = 0; k < m.nn_hidden2(); k++) {
+                    Value row = Value::array();
+                    for (size_t j = 0; j < h; j++) row.push(Value::number(m.nn_hw2[k * h + j]));
+                    hw2.push(std::move(row));
+                    hb2.push(Value::number(m.nn_hb2[k]));
+                }
+                inner.set("hidden2_weights", std::move(hw2));
+                inner.set("hidden2_bias", std::move(hb2));
+            }
             inner.set("output_weights", std::move(w2));
             inner.set("output_bias", Value::number(m.nn_b2));
             v.set("NeuralNet", std::move(inner));

@@ -15,6 +15,11 @@
 //   mh = m / (1 - 0.9^t)    vh = v / (1 - 0.999^t)     (the powers by t - 1 successive multiplications)
 //   theta = theta + fl(fl(learning_rate * mh) / fl(sqrt(vh) + 1e-8))
 // W1 and w2 decay, the biases do not; columns the view does not hold are not updated.
+//
+// With `hidden2` (a second hidden layer of h2 units; DESIGN.md section 19, "Two hidden layers") the numbering goes on after b1:
+// h d + h + k h + j for W2[k][j], then h2 numbers c[k], h2 numbers w3[k] (the model's output_weights), then b_out.  W1 is drawn
+// as above, bit for bit; W2[k][j] = fl(fl(fl(2 u_c) - 1) * s2) with s2 = sqrt(fl(6 / (h + h2))), w3[k] likewise with
+// s3 = sqrt(fl(6 / (h2 + 1))), each under its own number c.  W1, W2 and w3 decay.
 #pragma once
 #include <cmath>
 #include <string>
@@ -39,6 +44,7 @@ struct NeuralLambdaRankParams {
     uint32_t truncation_level = 0;
     bool lambda_norm = false;
     bool trace = false;
+    uint32_t hidden2 = 0;  // units of a second hidden layer (0: none; optional, written only when it is set)
 
     bool xendcg() const { return objective == frdev::LM_OBJECTIVE_XENDCG; }
     int objective_evaluator() const { return xendcg() ? (int)frdev::M_NDCG : objective; }
@@ -67,14 +73,17 @@ struct NeuralLambdaRankParams {
         if (const Value* r = v.find("truncation_level")) p.truncation_level = json_u32(*r, "truncation_level");
         if (const Value* r = v.find("lambda_norm")) p.lambda_norm = json_bool(*r, "lambda_norm");
         if (const Value* r = v.find("trace")) p.trace = json_bool(*r, "trace");
+        const Value* h2 = v.find("hidden2");
+        if (h2) p.hidden2 = json_u32(*h2, "hidden2");
         for (const auto& kv : v.obj) {
             static const char* known[] = {"hidden", "num_iterations", "learning_rate", "lambda_l2", "sigma", "seed", "quiet", "objective",
-                                          "truncation_level", "lambda_norm", "trace"};
+                                          "truncation_level", "lambda_norm", "trace", "hidden2"};
             bool ok = false;
             for (const char* k : known) ok = ok || kv.first == k;
             if (!ok) fail_raw("Error(\"unknown field `" + kv.first + "` of NeuralLambdaRankParams\", line: 0, column: 0)");
         }
         if (p.hidden < 1 || p.hidden > 1024) LambdaMARTParams::invalid("hidden must be between 1 and 1024");
+        if (h2 && (p.hidden2 < 1 || p.hidden2 > 64)) LambdaMARTParams::invalid("hidden2 must be between 1 and 64");
         if (p.num_iterations < 1) LambdaMARTParams::invalid("num_iterations must be at least 1");
         if (!(std::isfinite(p.learning_rate) && p.learning_rate > 0.0)) LambdaMARTParams::invalid("learning_rate must be finite and greater than 0");
         if (!(std::isfinite(p.lambda_l2) && p.lambda_l2 >= 0.0)) LambdaMARTParams::invalid("lambda_l2 must be finite and at least 0");
@@ -97,6 +106,7 @@ struct NeuralLambdaRankParams {
         if (truncation_level != 0) o.set("truncation_level", Value::uint(truncation_level));
         if (lambda_norm) o.set("lambda_norm", Value::boolean(true));
         if (trace) o.set("trace", Value::boolean(true));
+        if (hidden2 != 0) o.set("hidden2", Value::uint(hidden2));
         return o;
     }
 };
@@ -106,15 +116,18 @@ constexpr unsigned char ADAM_UPDATED = 1, ADAM_DECAYS = 2;  // a parameter's fla
 inline uint64_t neural_init_key(uint64_t seed) { return frresample::mix(seed + 4ull * frresample::GOLDEN); }
 inline double neural_init_uniform(uint64_t key, uint64_t c) { return (double)(frresample::mix(key + c) >> 11) * 0x1p-53; }
 
-// The initial net over d columns of which the view holds `feats`, and every parameter's flags in wire order.
-inline Model neural_init(uint64_t seed, size_t h, size_t d, const std::vector<uint32_t>& feats, std::vector<unsigned char>* flags) {
+// The initial net over d columns of which the view holds `feats`, and every parameter's flags in wire order; h2 != 0: with a
+// second hidden layer of h2 units.
+inline Model neural_init(uint64_t seed, size_t h, size_t d, const std::vector<uint32_t>& feats, std::vector<unsigned char>* flags, size_t h2 = 0) {
     Model m;
     m.kind = Model::NeuralNet;
     m.nn_cols = d;
-    m.nn_w1.assign(h * d, 0.0), m.nn_b1.assign(h, 0.0), m.nn_w2.assign(h, 0.0), m.nn_b2 = 0.0;
-    if (flags) flags->assign(h * d + 2 * h + 1, 0);
+    const size_t nout = h2 ? h2 : h;  // the output layer's inputs
+    m.nn_w1.assign(h * d, 0.0), m.nn_b1.assign(h, 0.0), m.nn_w2.assign(nout, 0.0), m.nn_b2 = 0.0;
+    m.nn_hw2.assign(h2 * h, 0.0), m.nn_hb2.assign(h2, 0.0);
+    if (flags) flags->assign(h * d + h + h2 * h + h2 + nout + 1, 0);
     const uint64_t key = neural_init_key(seed);
-    const double r1 = 6.0 / (double)(feats.size() + h), r2 = 6.0 / (double)(h + 1);
+    const double r1 = 6.0 / (double)(feats.size() + h), r2 = 6.0 / (double)(nout + 1);
     const double s1 = std::sqrt(r1), s2 = std::sqrt(r2);
     auto draw = [&](uint64_t c, double scale) {
         const double twice = 2.0 * neural_init_uniform(key, c);
@@ -127,10 +140,23 @@ inline Model neural_init(uint64_t seed, size_t h, size_t d, const std::vector<ui
             m.nn_w1[j * d + f] = draw(j * d + f, s1);
             if (flags) (*flags)[j * d + f] = ADAM_UPDATED | ADAM_DECAYS;
         }
-        m.nn_w2[j] = draw(h * d + h + j, s2);
-        if (flags) (*flags)[h * d + j] = ADAM_UPDATED, (*flags)[h * d + h + j] = ADAM_UPDATED | ADAM_DECAYS;
+        if (flags) (*flags)[h * d + j] = ADAM_UPDATED;
     }
-    if (flags) (*flags)[h * d + 2 * h] = ADAM_UPDATED;
+    const size_t cw2 = h * d + h, cc = cw2 + h2 * h, cw3 = cc + h2;  // where W2, c and the output weights start
+    if (h2 != 0) {
+        const double r12 = 6.0 / (double)(h + h2);
+        const double s12 = std::sqrt(r12);
+        for (size_t c = 0; c < h2 * h; c++) {
+            m.nn_hw2[c] = draw(cw2 + c, s12);
+            if (flags) (*flags)[cw2 + c] = ADAM_UPDATED | ADAM_DECAYS;
+        }
+        for (size_t k = 0; flags && k < h2; k++) (*flags)[cc + k] = ADAM_UPDATED;
+    }
+    for (size_t k = 0; k < nout; k++) {
+        m.nn_w2[k] = draw(cw3 + k, s2);
+        if (flags) (*flags)[cw3 + k] = ADAM_UPDATED | ADAM_DECAYS;
+    }
+    if (flags) (*flags)[cw3 + nout] = ADAM_UPDATED;
     return m;
 }
 
@@ -175,6 +201,8 @@ inline uint32_t neural_lambda_best(double initial_measure, const std::vector<dou
 inline std::vector<double> neural_flatten(const Model& m) {
     std::vector<double> th(m.nn_w1);
     th.insert(th.end(), m.nn_b1.begin(), m.nn_b1.end());
+    th.insert(th.end(), m.nn_hw2.begin(), m.nn_hw2.end());
+    th.insert(th.end(), m.nn_hb2.begin(), m.nn_hb2.end());
     th.insert(th.end(), m.nn_w2.begin(), m.nn_w2.end());
     th.push_back(m.nn_b2);
     return th;
@@ -183,14 +211,19 @@ inline void neural_unflatten(const std::vector<double>& th, Model* m) {
     const size_t h = m->nn_b1.size(), nw = h * m->nn_cols;
     std::copy(th.begin(), th.begin() + nw, m->nn_w1.begin());
     std::copy(th.begin() + nw, th.begin() + nw + h, m->nn_b1.begin());
-    std::copy(th.begin() + nw + h, th.begin() + nw + 2 * h, m->nn_w2.begin());
-    m->nn_b2 = th[nw + 2 * h];
+    auto at = th.begin() + nw + h;
+    for (std::vector<double>* part : {&m->nn_hw2, &m->nn_hb2, &m->nn_w2}) {
+        std::copy(at, at + part->size(), part->begin());
+        at += part->size();
+    }
+    m->nn_b2 = *at;
 }
 
 inline Value mlp_plan_json(const frdev::DeviceDataset::MlpPlan& plan) {
     Value g = Value::object();
     g.set("feature_panels", Value::uint(plan.feature_panels));
     g.set("hidden_panels", Value::uint(plan.hidden_panels));
+    if (plan.hidden2 != 0) g.set("hidden2", Value::uint(plan.hidden2));
     g.set("workgroups", Value::uint(plan.workgroups));
     g.set("stretch_tiles", Value::uint(plan.stretch));
     g.set("tiles", Value::uint(plan.tiles));

@@ -21,7 +21,7 @@ fr::Model train_neural_lambdarank(const std::shared_ptr<fr::DatasetView>& view, 
     if (feats.empty()) fr::fail_str("assertion failed: !features.is_empty()");
     if (view->host_csr().nq == 0) fr::fail_str("assertion failed: !data.queries().is_empty()");
     frdev::DeviceDataset& dev = view->device();
-    const size_t d = dev.d(), h = p.hidden;
+    const size_t d = dev.d(), h = p.hidden, h2 = p.hidden2;
     {
         const std::vector<double>& absmax = dev.column_absmax();
         for (uint32_t f : feats)
@@ -32,12 +32,16 @@ fr::Model train_neural_lambdarank(const std::shared_ptr<fr::DatasetView>& view, 
     st.features = (uint32_t)feats.size();
     std::string err;
     std::vector<unsigned char> flags;
-    fr::Model net = fr::neural_init(p.seed, h, d, feats, &flags);
+    fr::Model net = fr::neural_init(p.seed, h, d, feats, &flags, h2);
     const size_t n = flags.size(), nw = h * d;
     std::vector<double> theta = fr::neural_flatten(net), grad(n, 0.0), am(n, 0.0), av(n, 0.0);
     // scores of the net into slot 0, waited for
     auto score = [&]() {
-        if (!dev.score_mlp(h, d, net.nn_w1.data(), net.nn_b1.data(), net.nn_w2.data(), net.nn_b2, &err, &st.score_plan)) fr::fail_str(err);
+        if (h2 != 0) {
+            if (!dev.score_mlp2(fr::mlp2_net_of(net), &err, &st.score_plan)) fr::fail_str(err);
+        } else if (!dev.score_mlp(h, d, net.nn_w1.data(), net.nn_b1.data(), net.nn_w2.data(), net.nn_b2, &err, &st.score_plan)) {
+            fr::fail_str(err);
+        }
         if (!frdev::device_synchronize(&err)) fr::fail_str(err);
     };
     // the measure's mean of the scores in slot 0
@@ -63,9 +67,12 @@ fr::Model train_neural_lambdarank(const std::shared_ptr<fr::DatasetView>& view, 
         if (!frdev::device_synchronize(&err)) fr::fail_str(err);
         tb = tnow();
         st.t_gradient += secs(ta, tb);
-        if (!dev.mlp_backprop(h, d, net.nn_w1.data(), net.nn_b1.data(), net.nn_w2.data(), nullptr, nullptr, grad.data(), grad.data() + nw,
-                              grad.data() + nw + h, grad.data() + nw + 2 * h, &err, &st.backprop_plan))
+        if (h2 != 0) {  // (the record's order is the parameters')
+            if (!dev.mlp2_backprop(fr::mlp2_net_of(net), nullptr, nullptr, grad.data(), &err, &st.backprop_plan)) fr::fail_str(err);
+        } else if (!dev.mlp_backprop(h, d, net.nn_w1.data(), net.nn_b1.data(), net.nn_w2.data(), nullptr, nullptr, grad.data(), grad.data() + nw,
+                                     grad.data() + nw + h, grad.data() + nw + 2 * h, &err, &st.backprop_plan)) {
             fr::fail_str(err);
+        }
         ta = tnow();
         st.t_backprop += secs(tb, ta);
         fr::adam_step(theta.data(), grad.data(), am.data(), av.data(), n, flags.data(), t + 1, p.learning_rate, p.lambda_l2);
@@ -115,6 +122,9 @@ const void* fr_debug_mlp_gradients(const CDataset* dataset, const CModel* model,
         const CModel& cm = require_model(model);
         if (cm.actual.kind != fr::Model::NeuralNet) fr::fail_str("fr_debug_mlp_gradients: the model must be a NeuralNet");
         const fr::Model& net = cm.actual;
+        // nn_w2 of a two-layer net holds h2 numbers, not h: the one-layer launcher must not see it
+        if (net.nn_hidden2() != 0)
+            fr::fail_str("fr_debug_mlp_gradients: the model has hidden2_weights; its gradients come from fr_debug_mlp2_gradients");
         std::lock_guard<std::mutex> lk(api_mu_of(ds));
         fr::DatasetView& view = *ds.view;
         if (view.instances.empty()) fr::fail_str("fr_debug_mlp_gradients: the dataset holds no instance");
@@ -140,6 +150,55 @@ const void* fr_debug_mlp_gradients(const CDataset* dataset, const CModel* model,
         if (!dev.mlp_backprop(net.nn_b1.size(), net.nn_cols, net.nn_w1.data(), net.nn_b1.data(), net.nn_w2.data(), lam.data(),
                               queries ? flags.data() : nullptr, g_w1, g_b1, g_w2, g_b2, &err, &plan))
             fr::fail_str(err);
+        const Value pj = fr::mlp_plan_json(plan);
+        for (const auto& kv : pj.obj) o.set(kv.first.c_str(), kv.second);
+        return frjson::dump(o);
+    });
+}
+
+// fr_debug_mlp_gradients for a NeuralNet with a second hidden layer: the six arrays under the model's key names, g_w1[h * d]
+// row-major over the dataset's d columns, g_b1[h], g_w2[h2 * h] row-major, g_c[h2], g_w3[h2], g_bout[1].  Returns the plan as
+// JSON with "h", "h2" and "d"; with the outputs NULL nothing runs and the reply holds only the sizes.
+const void* fr_debug_mlp2_gradients(const CDataset* dataset, const CModel* model, const double* lambda, size_t len, const uint32_t* queries,
+                                    size_t n_queries, double* g_w1, double* g_b1, double* g_w2, double* g_c, double* g_w3, double* g_bout) {
+    return json_call([&]() {
+        const CDataset& ds = require_dataset(dataset);
+        const CModel& cm = require_model(model);
+        const fr::Model& net = cm.actual;
+        if (net.kind != fr::Model::NeuralNet || net.nn_hidden2() == 0)
+            fr::fail_str("fr_debug_mlp2_gradients: the model must be a NeuralNet with hidden2_weights");
+        std::lock_guard<std::mutex> lk(api_mu_of(ds));
+        fr::DatasetView& view = *ds.view;
+        if (view.instances.empty()) fr::fail_str("fr_debug_mlp2_gradients: the dataset holds no instance");
+        frdev::DeviceDataset& dev = view.device();
+        const size_t h = net.nn_b1.size(), h2 = net.nn_hidden2(), d = dev.d();
+        Value o = Value::object();
+        o.set("h", Value::uint(h));
+        o.set("h2", Value::uint(h2));
+        o.set("d", Value::uint(d));
+        double* const outs[] = {g_w1, g_b1, g_w2, g_c, g_w3, g_bout};
+        const size_t sizes[] = {h * d, h, h2 * h, h2, h2, 1};
+        size_t given = 0;
+        for (double* q : outs) given += q != nullptr;
+        if (given == 0) return frjson::dump(o);  // the size question: nothing runs
+        if (!lambda || given != 6) fr::fail_str("NULL pointer: fr_debug_mlp2_gradients");
+        std::vector<unsigned char> flags;
+        if (queries) flags = debug_query_flags(queries, n_queries, view.host_csr().nq);
+        size_t np = 0;
+        const uint32_t* instance_at = dev.position_instances(&np);
+        std::vector<double> lam(np, std::numeric_limits<double>::quiet_NaN());
+        for (size_t pos = 0; pos < np; pos++) {
+            const uint32_t id = instance_at[pos];
+            if (id == 0xFFFFFFFFu) continue;
+            if (id >= len) fr::fail_str("fr_debug_mlp2_gradients: the gradient array is shorter than the largest instance id");
+            lam[pos] = lambda[id];
+        }
+        std::string err;
+        frdev::DeviceDataset::MlpPlan plan;
+        std::vector<double> grad(h * d + h + h2 * h + 2 * h2 + 1);
+        if (!dev.mlp2_backprop(fr::mlp2_net_of(net), lam.data(), queries ? flags.data() : nullptr, grad.data(), &err, &plan)) fr::fail_str(err);
+        const double* at = grad.data();
+        for (size_t k = 0; k < 6; at += sizes[k], k++) std::copy(at, at + sizes[k], outs[k]);
         const Value pj = fr::mlp_plan_json(plan);
         for (const auto& kv : pj.obj) o.set(kv.first.c_str(), kv.second);
         return frjson::dump(o);

@@ -501,6 +501,27 @@ def mlp_gradients(dataset: CDataset, model: CModel, lam: np.ndarray, queries=Non
     return {"hidden_weights": gw1, "hidden_bias": gb1, "output_weights": gw2, "output_bias": float(gb2[0])}
 
 
+def mlp2_gradients(dataset: CDataset, model: CModel, lam: np.ndarray, queries=None, plan: Optional[Dict] = None) -> Dict[str, np.ndarray]:
+    """`mlp_gradients` for a NeuralNet with a second hidden layer (mlp2_backprop_kernel; DESIGN.md section 19, "Two hidden
+    layers"): {"hidden_weights": [h, d], "hidden_bias": [h], "hidden2_weights": [h2, h], "hidden2_bias": [h2], "output_weights":
+    [h2], "output_bias": float}.  `plan` also receives hidden2."""
+    lam = np.ascontiguousarray(lam, dtype=np.float64)
+    if lam.ndim != 1:
+        raise ValueError("lam must be a 1-d array")
+    qs = None if queries is None else np.ascontiguousarray(queries, dtype=np.uint32)
+    call = _load().fr_debug_mlp2_gradients
+    size = _json_reply(call(dataset.pointer, model.pointer, None, 0, None, 0, None, None, None, None, None, None))
+    h, h2, d = int(size["h"]), int(size["h2"]), int(size["d"])
+    out = {"hidden_weights": np.zeros((h, d)), "hidden_bias": np.zeros(h), "hidden2_weights": np.zeros((h2, h)), "hidden2_bias": np.zeros(h2),
+           "output_weights": np.zeros(h2), "output_bias": np.zeros(1)}
+    rep = _json_reply(call(dataset.pointer, model.pointer, lam.ctypes.data, lam.shape[0], None if qs is None else qs.ctypes.data,
+                           0 if qs is None else len(qs), *(a.ctypes.data for a in out.values())))
+    if plan is not None:
+        plan.update(rep)
+    out["output_bias"] = float(out["output_bias"][0])
+    return out
+
+
 def adam_step(theta, grad, m, v, t: int, learning_rate: float, lambda_l2: float = 0.0, decays=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """The neural LambdaRank trainer's Adam ascent step alone (no device; csrc/neural_lambda.hpp): step `t` (1-based) on flat
     float64 arrays; `decays`: a mask of the parameters `lambda_l2` applies to (None: none).  Returns the new (theta, m, v)."""

@@ -281,7 +281,9 @@ class NeuralLambdaRankParams(_LearnerParams):
     iterate when none beats the initial net).  The training stats' "neural_lambdarank" object reports `initial_measure`,
     `train_measure`, `best_iteration`, milliseconds per stage, the kernels' plans and, under `trace`, the `initial` net and
     all `iterates` as models.  Held-out queries, a validation dataset and `init_model` are refused; a request that names
-    several devices trains on one.  The last four keys are written only when they differ from their defaults."""
+    several devices trains on one.  `hidden2` (None: one hidden layer; 1 to 64) puts a second hidden ReLU layer of that many
+    units between the first and the score (kernels_mlp2.inc; DESIGN.md section 19, "Two hidden layers"); for one seed the
+    initial W1 is the one-layer request's.  The last five keys are written only when they differ from their defaults."""
 
     VARIANT: ClassVar[str] = "NeuralLambdaRank"
 
@@ -296,8 +298,9 @@ class NeuralLambdaRankParams(_LearnerParams):
     truncation_level: int = 0
     lambda_norm: bool = False
     trace: bool = False
+    hidden2: Optional[int] = None
 
-    _WIRE_DEFAULTS: ClassVar[Dict[str, Any]] = {"objective": "ndcg", "truncation_level": 0, "lambda_norm": False, "trace": False}
+    _WIRE_DEFAULTS: ClassVar[Dict[str, Any]] = {"objective": "ndcg", "truncation_level": 0, "lambda_norm": False, "trace": False, "hidden2": None}
 
     __post_init__ = LinearLambdaRankParams.__post_init__
     to_dict = LinearLambdaRankParams.to_dict

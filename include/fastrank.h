@@ -413,6 +413,12 @@ const void *fr_debug_mlp_gradients(const CDataset *dataset, const CModel *model,
                                    const uint32_t *queries, size_t n_queries, double *g_w1, double *g_b1, double *g_w2, double *g_b2);
 const void *fr_debug_adam_step(double *theta, const double *grad, double *m, double *v, size_t n, const unsigned char *decays,
                                uint32_t t, double learning_rate, double lambda_l2);
+/* fr_debug_mlp2_gradients: fr_debug_mlp_gradients for a NeuralNet with a second hidden layer ("hidden2_weights",
+ * "hidden2_bias"; any other model is refused, as fr_debug_mlp_gradients refuses one that has them): g_w1[h * d], g_b1[h],
+ * g_w2[h2 * h] row-major (row k = unit k of the second layer), g_c[h2], g_w3[h2], g_bout[1].  The reply also holds "h2" and "hidden2"; with the six outputs NULL nothing runs and it is {"h","h2","d"}. */
+const void *fr_debug_mlp2_gradients(const CDataset *dataset, const CModel *model, const double *lambda, size_t len,
+                                    const uint32_t *queries, size_t n_queries, double *g_w1, double *g_b1, double *g_w2,
+                                    double *g_c, double *g_w3, double *g_bout);
 /* Full per-query rank order under the reference's total order (src/evaluators.rs:34-49):
  * out_instance_ids[n] grouped by query (device query order), best first; out_offsets[nq+1]. */
 const void *fr_rank_order(const CModel *model, const CDataset *dataset, uint32_t *out_instance_ids,
