@@ -172,6 +172,8 @@ const void* fr_debug_lambda_gradients_sampled(const CModel* model, const CDatase
 // under "map" / "mrr" the norms are the AP / RR evaluator's (DESIGN.md section 11, "Objectives").  "objective": "xendcg" is
 // the listwise pass (section 11, "Listwise objective") under the key "xe_key" (u64, default 0; read under "xendcg" only); it
 // keeps the NDCG norms, reads neither sigma nor the measure's depth, and refuses truncation_level != 0 and lambda_norm.
+// "objective": "approxndcg" is the smooth NDCG's gradient (section 11, "ApproxNDCG objective"): NDCG norms, sigma is the
+// sigmoid's steepness, every weight is 0, and truncation_level != 0 and lambda_norm are refused.
 const void* fr_debug_lambda_gradients_opts(const CModel* model, const CDataset* dataset, const CQRel* qrel, const void* measure,
                                            double sigma, const uint32_t* queries, size_t n_queries, const void* options_json,
                                            double* lambda_out, double* weight_out, size_t out_len) {

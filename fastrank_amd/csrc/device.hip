@@ -30,6 +30,8 @@
 //                           lambda_grad_trunc_kernel: the same under a truncation level / per-query normalisation
 //                           (both are templates over the objective: NDCG, MAP or MRR pair weights)
 //   kernels_xendcg.inc      lambda_grad_xe_kernel: LambdaMART's listwise objective, one wave per query, O(n) per query
+//   kernels_approx.inc      lambda_grad_approx_kernel / _wave_kernel: the ApproxNDCG objective's gradient, two n^2 passes over
+//                           64 x 64 LDS tiles of the pair triangle, one exp per unordered pair and pass
 //   kernels_hist.inc        LambdaMART's histogram grower: one-byte bins, int64 fixed-point gradients, per-node histograms
 //   kernels_histreg.inc     the histogram grower's scan kernels under lambda_l1 / max_delta_step / path_smooth
 //   kernels_goss.inc        LambdaMART's gradient-based one-side sampling: an on-device radix select of the n-th largest |lambda|,
@@ -62,7 +64,7 @@
 //     score_trees.inc         forest scoring: the launchers of kernels_treerank.inc and kernels_tree.inc over forest_pack.hpp's buffers,
 //                             the packed-forest cache, the plan of the last call
 //     train_rf.inc            the launchers of kernels_rf.inc
-//     train_lambda.inc        the launchers of kernels_lambda.inc and kernels_xendcg.inc
+//     train_lambda.inc        the launchers of kernels_lambda.inc, kernels_xendcg.inc and kernels_approx.inc
 //     train_dart.inc          the launchers of kernels_dart.inc
 //     train_hist.inc          the launchers of kernels_hist.inc and kernels_histreg.inc, level-wise and leaf-wise, of kernels_goss.inc and kernels_histquant.inc
 //   kernels_text.inc        the device text parser's kernels (line scan, the two parsing passes); text_parse.inc launches them
@@ -126,6 +128,7 @@ namespace frdev {
 #include "kernels_rf.inc"
 #include "kernels_lambda.inc"
 #include "kernels_xendcg.inc"
+#include "kernels_approx.inc"
 #include "kernels_hist.inc"
 #include "kernels_histreg.inc"
 #include "kernels_goss.inc"

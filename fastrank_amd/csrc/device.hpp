@@ -47,6 +47,9 @@ inline const char* pricing_env(const char* name) {
 enum Measure : int { M_NDCG = 0, M_AP = 1, M_RR = 2, M_DCG = 3, M_PRECISION = 4, M_RECALL = 5, M_SUCCESS = 6, M_ERR = 7 };
 // LambdaMART's objectives are spelled as their measures; the listwise objective "xendcg" has no measure of its own
 constexpr int LM_OBJECTIVE_XENDCG = 3;
+// "approxndcg" (the neural trainer's; DESIGN.md section 11, "ApproxNDCG objective") neither: its id lies past every measure's
+constexpr int LM_OBJECTIVE_APPROXNDCG = 8;
+static_assert(LM_OBJECTIVE_APPROXNDCG > M_ERR, "the ApproxNDCG objective's id is no measure's");
 
 // Error bound E >= |R - sum_j x_j v_j| of a trainer's resident sums, u = 2^-53, T from column
 // maxima.  One place for the constants: the trainer (host.hpp), compute_eps2 (device_dataset.inc) and the CPU test
@@ -323,6 +326,9 @@ class DeviceDataset {
         // lambda_grad_xe_kernel; norms are the NDCG evaluator's (read for `> 0` only), depth and sigma are not read, and
         // truncation_level / lambda_norm must be at their defaults.  xe_key: the tree's key of the gamma stream
         uint64_t xe_key = 0;
+        // objective = LM_OBJECTIVE_APPROXNDCG (8; DESIGN.md section 11, "ApproxNDCG objective"): the smooth NDCG's gradient,
+        // lambda_grad_approx_kernel and its wave kernel; norms are the NDCG evaluator's, sigma is the sigmoid's alpha, depth is
+        // not read, w comes back 0, and truncation_level / lambda_norm must be at their defaults
     };
     bool lambda_gradients(const double* norms, int64_t depth, double sigma, const LambdaPass& pass, std::string* err);
     // the last pass's lambda / w by padded position ([np] each)

@@ -130,11 +130,13 @@ struct LambdaMARTParams {
     bool goss() const { return goss_top_rate > 0.0; }
     bool dart() const { return drop_rate > 0.0; }
     bool xendcg() const { return objective == frdev::LM_OBJECTIVE_XENDCG; }
+    bool approxndcg() const { return objective == frdev::LM_OBJECTIVE_APPROXNDCG; }
     static const char* objective_name(int objective) {
-        return objective == frdev::M_AP ? "map" : objective == frdev::M_RR ? "mrr" : objective == frdev::LM_OBJECTIVE_XENDCG ? "xendcg" : "ndcg";
+        return objective == frdev::M_AP ? "map" : objective == frdev::M_RR ? "mrr" : objective == frdev::LM_OBJECTIVE_XENDCG ? "xendcg"
+               : objective == frdev::LM_OBJECTIVE_APPROXNDCG ? "approxndcg" : "ndcg";
     }
     // the measure whose evaluator the trainer needs under `objective`
-    int objective_evaluator() const { return xendcg() ? (int)frdev::M_NDCG : objective; }
+    int objective_evaluator() const { return xendcg() || approxndcg() ? (int)frdev::M_NDCG : objective; }
     // the evaluator the trainer gets under `objective` (the request's own measure is then read for nothing else)
     const char* objective_measure() const { return objective == frdev::M_AP ? "ap" : objective == frdev::M_RR ? "rr" : nullptr; }
     bool sampling() const { return query_sampling_rate < 1.0 || feature_sampling_rate < 1.0; }
@@ -145,6 +147,10 @@ struct LambdaMARTParams {
     }
     // what "xendcg" cannot be combined with (the keys speak of pairs, and there are none)
     void check_objective_options() const {
+        if (approxndcg()) {  // ("ApproxNDCG objective": every pair counts, at every rank)
+            if (truncation_level != 0) invalid("truncation_level cannot be combined with objective `approxndcg` (a smooth objective has no ranks to truncate at)");
+            if (lambda_norm) invalid("lambda_norm cannot be combined with objective `approxndcg` (the gradient of a function has no pair terms to normalise by)");
+        }
         if (!xendcg()) return;
         if (truncation_level != 0) invalid("truncation_level cannot be combined with objective `xendcg` (a listwise objective has no pairs to truncate)");
         if (lambda_norm) invalid("lambda_norm cannot be combined with objective `xendcg` (a listwise objective has no pair terms to normalise by)");
@@ -163,6 +169,7 @@ struct LambdaMARTParams {
         if (g.s == "map" || g.s == "ap") return frdev::M_AP;
         if (g.s == "mrr" || g.s == "rr") return frdev::M_RR;
         if (g.s == "xendcg") return frdev::LM_OBJECTIVE_XENDCG;
+        if (g.s == "approxndcg") return frdev::LM_OBJECTIVE_APPROXNDCG;
         // (the text predates the fourth value and is kept byte for byte: DESIGN.md section 11, "Listwise objective")
         invalid("objective must be `ndcg`, `map` or `mrr`, not `" + g.s + "`");
     }
@@ -207,6 +214,8 @@ struct LambdaMARTParams {
         if (const Value* r = v.find("truncation_level")) p.truncation_level = json_u32(*r, "truncation_level");
         if (const Value* r = v.find("lambda_norm")) p.lambda_norm = json_bool(*r, "lambda_norm");
         if (const Value* g = v.find("objective")) p.objective = objective_from_json(*g);
+        if (p.approxndcg())
+            invalid("objective `approxndcg` is not supported by LambdaMART (its trees need the hessian weight w, and the objective's second derivative is not sign-definite; NeuralLambdaRank takes it)");
         if (const Value* r = v.find("drop_rate")) p.drop_rate = json_f64(*r, "drop_rate");
         if (const Value* r = v.find("max_drop")) p.max_drop = json_u32(*r, "max_drop");
         if (const Value* r = v.find("skip_drop")) p.skip_drop = json_f64(*r, "skip_drop");

@@ -50,6 +50,8 @@ struct LinearLambdaRankParams {
         p.sigma = json_f64(json_field(v, "sigma"), "sigma");
         p.quiet = json_bool(json_field(v, "quiet"), "quiet");
         if (const Value* g = v.find("objective")) p.objective = LambdaMARTParams::objective_from_json(*g);
+        if (p.objective == frdev::LM_OBJECTIVE_APPROXNDCG)
+            LambdaMARTParams::invalid("objective `approxndcg` is not supported by LinearLambdaRank (its Gram matrix needs the hessian weight w, and the objective's second derivative is not sign-definite; NeuralLambdaRank takes it)");
         if (const Value* r = v.find("truncation_level")) p.truncation_level = json_u32(*r, "truncation_level");
         if (const Value* r = v.find("lambda_norm")) p.lambda_norm = json_bool(*r, "lambda_norm");
         for (const auto& kv : v.obj) {

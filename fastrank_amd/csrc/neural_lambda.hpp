@@ -47,7 +47,8 @@ struct NeuralLambdaRankParams {
     uint32_t hidden2 = 0;  // units of a second hidden layer (0: none; optional, written only when it is set)
 
     bool xendcg() const { return objective == frdev::LM_OBJECTIVE_XENDCG; }
-    int objective_evaluator() const { return xendcg() ? (int)frdev::M_NDCG : objective; }
+    bool approxndcg() const { return objective == frdev::LM_OBJECTIVE_APPROXNDCG; }
+    int objective_evaluator() const { return xendcg() || approxndcg() ? (int)frdev::M_NDCG : objective; }
     const char* objective_measure() const { return objective == frdev::M_AP ? "ap" : objective == frdev::M_RR ? "rr" : nullptr; }
     frdev::DeviceDataset::LambdaPass pass() const { return {nullptr, false, truncation_level, lambda_norm, objective, 0}; }
 

@@ -1,6 +1,6 @@
-// Part of device.hip (single translation unit; see that file's header).  LambdaMART's gradient pass: the launchers of kernels_lambda.inc and kernels_xendcg.inc.
+// Part of device.hip (single translation unit; see that file's header).  LambdaMART's gradient pass: the launchers of kernels_lambda.inc, kernels_xendcg.inc and kernels_approx.inc.
 // ----------------------------------------------------------------------------------------------
-// LambdaMART gradient pass (kernels_lambda.inc, kernels_xendcg.inc)
+// LambdaMART gradient pass (kernels_lambda.inc, kernels_xendcg.inc, kernels_approx.inc)
 // ----------------------------------------------------------------------------------------------
 // per query the positions of its documents in stored order (instance ids ascending), and the launch order (longest first)
 bool DeviceDataset::Impl::lm_build(std::string* err) {
@@ -42,12 +42,16 @@ bool DeviceDataset::lambda_gradients(const double* norms, int64_t depth, double 
         if (err) *err = "lambda_gradients: no scores resident";
         return false;
     }
-    if (pass.objective < LM_OBJ_NDCG || pass.objective > LM_OBJ_XENDCG) {
+    if ((pass.objective < LM_OBJ_NDCG || pass.objective > LM_OBJ_XENDCG) && pass.objective != LM_OBJ_APPROX) {
         if (err) *err = "lambda_gradients: unknown objective " + std::to_string(pass.objective);
         return false;
     }
     if (pass.objective == LM_OBJ_XENDCG && (pass.truncation_level != 0 || pass.lambda_norm)) {
         if (err) *err = "lambda_gradients: the listwise objective has no pairs to truncate or normalise";
+        return false;
+    }
+    if (pass.objective == LM_OBJ_APPROX && (pass.truncation_level != 0 || pass.lambda_norm)) {
+        if (err) *err = "lambda_gradients: the ApproxNDCG objective has no ranks to truncate at and no pair terms to normalise by";
         return false;
     }
     if (!m.lm_build(err)) return false;
@@ -83,6 +87,23 @@ bool DeviceDataset::lambda_gradients(const double* norms, int64_t depth, double 
         ProfScope ps("lambda_grad_xe_kernel", m.stream);
         lambda_grad_xe_kernel<<<(n_q + XE_WAVES - 1) / XE_WAVES, 64 * XE_WAVES, 0, m.stream>>>(
             m.scores.p, lm.off.p, lm.pos.p, qorder, n_q, m.gexp.p, m.perm.p, m.norms.p, pass.xe_key, lm.lam.p, lm.wt.p, lm.target.p);
+        FR_HIP(hipGetLastError());
+        return true;
+    }
+    if (pass.objective == LM_OBJ_APPROX) {  // DESIGN.md section 11, "ApproxNDCG objective": a workgroup per query over 64 documents, a wave per shorter one
+        const std::vector<uint32_t>& order = pass.query_flags != nullptr ? lm.qsel_h : lm.order_h;  // (what qorder holds, longest first)
+        const uint32_t n_q = n_long + n_lds;
+        const uint32_t n_group = (uint32_t)(std::partition_point(order.begin(), order.begin() + n_q, [&](uint32_t q) { return m.qlen_h[q] > AX_WAVE_MAX; }) - order.begin());
+        ProfScope ps("lambda_grad_approx_kernel", m.stream);
+        if (n_group != 0) {
+            lambda_grad_approx_kernel<<<n_group, 256, AX_GROUP_LDS, m.stream>>>(m.scores.p, lm.off.p, lm.pos.p, qorder, m.gexp.p, m.norms.p, sigma, lm.lam.p,
+                                                                                lm.wt.p, lm.target.p);
+        }
+        if (n_q != n_group) {
+            FR_HIP(hipFuncSetAttribute((const void*)lambda_grad_approx_wave_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)AX_WAVE_LDS));
+            lambda_grad_approx_wave_kernel<<<(n_q - n_group + AX_WAVES - 1) / AX_WAVES, 64 * AX_WAVES, AX_WAVE_LDS, m.stream>>>(
+                m.scores.p, lm.off.p, lm.pos.p, qorder, n_group, n_q, m.gexp.p, m.norms.p, sigma, lm.lam.p, lm.wt.p, lm.target.p);
+        }
         FR_HIP(hipGetLastError());
         return true;
     }

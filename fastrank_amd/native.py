@@ -210,7 +210,9 @@ def lambda_gradients(model: CModel, dataset: CDataset, measure: str = "ndcg", si
     options ("Truncation and normalisation"); `objective`: "ndcg", "map" or "mrr" (section 11,
     "Objectives"; `measure` must name NDCG all the same, and the norms are the AP / RR evaluator's) or "xendcg" (section 11,
     "Listwise objective": the listwise pass under the tree key `xe_key`, a u64; `sigma` and the measure's depth are not read,
-    a truncation level or `lambda_norm` is refused).  At their defaults the call is the one it was."""
+    a truncation level or `lambda_norm` is refused) or "approxndcg" (section 11, "ApproxNDCG objective": the gradient of the
+    smooth NDCG under the steepness `sigma`; the norms are NDCG's, the measure's depth reaches them and nothing else, every
+    weight comes back 0, a truncation level or `lambda_norm` is refused).  At their defaults the call is the one it was."""
     n = int(n_total if n_total is not None else _load().fr_dataset_num_instances(dataset.pointer))
     if n_total is None and dataset.is_sampled():
         n = 1 + max(max(ids) for ids in dataset.instances_by_query().values())

@@ -276,7 +276,10 @@ class NeuralLambdaRankParams(_LearnerParams):
     counter-based stream of `seed`; each of `num_iterations` iterations scores the current net, takes one gradient pass
     (LambdaMART's: `sigma`, `objective` "ndcg" / "map" / "mrr" / "xendcg", `truncation_level`, `lambda_norm` mean what they
     mean there and are refused where they are refused there), back-propagates lambda through the net in float64 on the matrix
-    units and takes one Adam step on the host (`learning_rate`; `lambda_l2` decays W1 and w2).  Normalise raw columns first
+    units and takes one Adam step on the host (`learning_rate`; `lambda_l2` decays W1 and w2).  `objective` "approxndcg" (this
+    trainer only; DESIGN.md section 11, "ApproxNDCG objective") ascends the smooth NDCG of sigmoid soft ranks, `sigma` being the
+    sigmoid's steepness: lambda is that function's gradient; `truncation_level` and `lambda_norm` are refused with it, and the
+    request's NDCG evaluator keeps every role of the training measure.  Normalise raw columns first
     (`Normalizer`).  The model is the NeuralNet iterate with the largest training measure (the first of equals; the first
     iterate when none beats the initial net).  The training stats' "neural_lambdarank" object reports `initial_measure`,
     `train_measure`, `best_iteration`, milliseconds per stage, the kernels' plans and, under `trace`, the `initial` net and

@@ -373,7 +373,10 @@ const void *fr_debug_hist_root_histogram(const CDataset *dataset, const double *
  * "objective": "xendcg" (lower case only) is the listwise cross-entropy pass ("Listwise
  * objective"; lambda_grad_xe_kernel) under the tree key "xe_key" (a fourth optional key: u64, default 0, read under
  * "xendcg" only).  The norms stay the NDCG evaluator's; sigma and the measure's depth are not read; a truncation_level
- * other than 0 or lambda_norm: true with it is an `invalid value` error, raised before any device work. */
+ * other than 0 or lambda_norm: true with it is an `invalid value` error, raised before any device work.
+ * "objective": "approxndcg" (lower case only) is the gradient of the smooth NDCG of sigmoid soft ranks (DESIGN.md section
+ * 11, "ApproxNDCG objective"; lambda_grad_approx_kernel): NDCG norms, sigma is the sigmoid's steepness, every weight comes
+ * back 0, and the same two keys are refused in the same way. */
 const void *fr_debug_lambda_gradients_opts(const CModel *model, const CDataset *dataset, const CQRel *qrel,
                                            const void *measure, double sigma, const uint32_t *queries,
                                            size_t n_queries, const void *options_json, double *lambda_out,
